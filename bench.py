@@ -14,6 +14,12 @@ With --gpus N > 1 and no launcher around it (no WORLD_SIZE in the environment) b
 child processes, one per GPU, before this process has made a single HIP or RCCL call -- and relays rank 0's line: a run
 that asks for N GPUs never measures fewer.  The line carries `n_ranks_seen`: the number of ranks counted by an all-reduce of
 ones INSIDE the library's exchange (cal_solver_comm_size), beside `n_gpus`, the launcher's claim.
+
+A plain run sets up, warms up, times the --steps steps and prints the line (its roofline only where the timed steps carry the
+kernel's events).  --full also measures everything reported beside the headline: the chi^2 rate, the shared layout and the kernels
+it replaced, every rank's share of the 8-GPU job, the device's streaming peaks, the CPU baselines, --extras, and the kernel duration
+of launch-bound problems (a pass of its own).  --dump-outputs DIR writes what the timed steps computed (their recorded losses, then
+the gains and coefficients after the last one, as returned by get_params) to DIR/<name>.npy.
 """
 import argparse
 import json
@@ -45,9 +51,13 @@ def parse():
     ap.add_argument("--optimizer", default="Adam")
     ap.add_argument("--reg", default="none", choices=["none", "sum"])
     ap.add_argument("--max-bls", type=int, default=None, help="bounded sample of the baselines (debugging)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-shared", action="store_true", help="skip the extra shared-layout (MFMA) measurement")
-    ap.add_argument("--extras", action="store_true", help="also time the tutorial-notebook and the redundant-groups configurations (they launch "
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline (CPU baselines, shared layout, "
+                    "the 8-GPU job's shares, streaming peaks, chi^2 rate, kernel duration of launch-bound problems)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed steps' losses and the parameters after the last one as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baselines")
+    ap.add_argument("--no-shared", action="store_true", help="(--full) skip the extra shared-layout (MFMA) measurement")
+    ap.add_argument("--extras", action="store_true", help="(--full) also time the tutorial-notebook and the redundant-groups configurations (they launch "
                     "the same kernels at other sizes, so a rocprofv3 --stats summary of such a run no longer averages the headline launches alone)")
     ap.add_argument("--cpu-sample-bls", type=int, default=192)
     ap.add_argument("--transport", default="rccl", choices=["rccl", "host", "gloo"],
@@ -65,7 +75,12 @@ def parse():
                     help="with ONE rank (plain or under torch.distributed.run --nproc-per-node 1): take the multi-rank code path anyway -- "
                          "T batched time slices, group partition, socket rendezvous, unique id broadcast, RCCL communicator of one rank, "
                          "grouped all-reduce every step -- so that path is exercised on a one-GPU box")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.extras and not args.full:
+        ap.error("--extras is part of a --full run")
+    if args.dump_outputs and args.split:
+        ap.error("--dump-outputs is not available with --split")
+    return args
 
 
 def host_info():
@@ -202,6 +217,27 @@ def cpu_baseline_strong(prob, start, dtype, optimizer, reg, same_updates=0):
                 loss_before_update=losses[: same_updates + 1],
                 sample=f"full job, {n} Adam steps of the C/OpenMP restatement (ragged, fused, shared unique basis blocks, "
                        f"{np.dtype(dtype).name}) on {cores} threads; {dt * 1e3:.0f} ms per step")
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(directory, arrays):
+    """Write every array of ``arrays`` (name -> float32 / float64 array) to directory/<name>.npy.  Should they exceed
+    DUMP_LIMIT_BYTES together, an array larger than an equal share of the limit is replaced by a fixed sample of its elements
+    (flattened, seed 0, in index order): the same for every run of the same arguments, so two builds compare element for element."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    if sum(a.nbytes for a in arrays.values()) > DUMP_LIMIT_BYTES:
+        share = DUMP_LIMIT_BYTES // len(arrays)
+        for k, a in arrays.items():
+            keep = share // a.itemsize
+            if a.size > keep:
+                arrays[k] = a.ravel()[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+    for k, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError(f"--dump-outputs: {k} is {a.dtype}, not float32 / float64")
+        np.save(os.path.join(directory, k + ".npy"), a)
 
 
 def ranks_sum_int(grp, vals):
@@ -507,7 +543,10 @@ def main():
     timed_losses = run_steps(args.steps, True)
     sync()
     dt = time.perf_counter() - t0
-    if launch_bound:
+    if args.dump_outputs and rank == 0:  # (before anything below steps the solvers on; a sharded run: this rank's coefficients)
+        g_r, g_i, c_r, c_i = solvers[0].get_params()
+        dump_outputs(args.dump_outputs, {"losses": np.asarray(timed_losses, dtype=np.float64), "g_r": g_r, "g_i": g_i, "c_r": c_r, "c_i": c_i})
+    if launch_bound and args.full:
         for s in solvers:
             s.timing_enable(True)
         run_steps(min(args.steps, 200), False)
@@ -518,19 +557,21 @@ def main():
     for s in solvers:
         s.timing_enable(False)
     # chi^2 evaluations per second (forward only), untimed part of the contract
-    sync()
-    t1 = time.perf_counter()
-    nev = max(3, args.steps // 2)
-    for _ in range(nev):
-        for s in solvers:
-            s.eval_loss()
-    sync()
-    chi2_rate = nev * ntimes / (time.perf_counter() - t1)
+    chi2_rate = None
+    if args.full:
+        sync()
+        t1 = time.perf_counter()
+        nev = max(3, args.steps // 2)
+        for _ in range(nev):
+            for s in solvers:
+                s.eval_loss()
+        sync()
+        chi2_rate = nev * ntimes / (time.perf_counter() - t1)
 
     # the SHARED layout of the same workload (baselines of one delay alias ONE basis block; dense MFMA path): measured
     # in the same run and reported beside the headline, against its own bounds
     shared = None
-    if not sharded and args.layout == "stream" and not args.no_shared and args.reg == "none":
+    if args.full and not sharded and args.layout == "stream" and not args.no_shared and args.reg == "none":
         s2 = HipFitSolver(dtype=dtype, device=0)
         s2.set_problem(prob, layout="shared")
         s2.set_params(start["g_r"], start["g_i"], start["c_r"], start["c_i"])
@@ -579,7 +620,7 @@ def main():
     # other on this GPU: the 8-GPU step is the slowest rank's step (+ the exchange), so the table says in advance what the scaling
     # run can reach and whether the partition (distributed.partition_groups: groups dealt round-robin) is balanced.
     rank_job = None
-    if (rank == 0 and not sharded and args.layout == "stream" and not args.no_shared and args.reg == "none" and args.config == "hera350"
+    if (args.full and rank == 0 and not sharded and args.layout == "stream" and not args.no_shared and args.reg == "none" and args.config == "hera350"
             and args.max_bls is None and dtype == np.float32):
         rows = []
         for r8 in range(8):
@@ -617,7 +658,7 @@ def main():
     # reference publishes a rate for (tutorial notebook: 15 antennas, 105 baselines x 200 channels, Adamax, 61.77 steps/s
     # on a P100) -- single-GPU runs only, after the solvers above have released their memory
     peaks, tutorial, redundant = None, None, None
-    if rank == 0 and not sharded and not args.no_shared:
+    if args.full and rank == 0 and not sharded and not args.no_shared:
         for s_ in solvers:
             s_.synchronize()
         try:
@@ -697,7 +738,9 @@ def main():
             "peak_measured": peaks,
             "frac_of_measured_read_peak": (achieved / peaks["read_GBps"]) if peaks and "read_GBps" in peaks else None,
         }
-        if tim["kernel_path"] == "dense":
+        if not tim["launches"]:
+            roofline = None  # (a launch-bound problem's kernel duration takes a pass of its own: --full)
+        elif tim["kernel_path"] == "dense":
             # the shared layout's dense kernel is bound by the matrix pipe, not by HBM: lead with that roofline
             d = dense_rooflines(prob, tim, kern_ms, dtype, args.config if (not sharded and args.max_bls is None and args.reg == "none") else None)
             roofline = dict(d["roofline_mfma"], kernel=d["kernel"], kernel_ms=kern_ms, peak_measured=peaks,
@@ -744,7 +787,7 @@ def main():
                 "redundant_groups_config": redundant,
             },
         }
-        if not args.no_cpu_baseline and not sharded:  # reported at N = 1 only
+        if args.full and not args.no_cpu_baseline and not sharded:  # reported at N = 1 only
             out["cpu_baseline"] = cpu_baseline(prob, start, dtype, args.optimizer, args.cpu_sample_bls, args.reg)
             nupd = args.warmup + args.steps - 1
             strong = cpu_baseline_strong(prob, start, dtype, args.optimizer, args.reg == "sum", same_updates=nupd if nupd <= 64 else 0)

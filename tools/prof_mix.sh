@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:?}"
 export TMPDIR=/tmp
 out=gpurun_out/$tag
 mkdir -p $out
-cmd="python3 bench.py --layout shared --steps 4 --warmup 1 --no-cpu-baseline --no-shared"
+cmd="python3 bench.py --full --layout shared --steps 4 --warmup 1 --no-cpu-baseline --no-shared"
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_INSTS_BRANCH SQ_INSTS_VMEM_RD -d $out/pmc -o mix1 --output-format csv -- $cmd > $out/mix1.log 2>&1
 echo "mix1 done"
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_MISC SQ_WAIT_INST_LDS SQ_INST_CYCLES_SALU -d $out/pmc -o mix2 --output-format csv -- $cmd > $out/mix2.log 2>&1

@@ -7,8 +7,8 @@ cd "${GRAFT_REPO_ROOT:?}"
 export TMPDIR=/tmp
 out=gpurun_out/$tag
 mkdir -p $out
-cmd="python3 bench.py --layout shared --dtype f32 --steps 4 --warmup 1 --no-cpu-baseline --no-shared"
-rocprofv3 --kernel-trace --stats -d $out/trace -o dense --output-format csv -- python3 bench.py --layout shared --dtype f32 --steps 20 --warmup 3 --no-cpu-baseline --no-shared > $out/trace_stdout.log 2>&1
+cmd="python3 bench.py --full --layout shared --dtype f32 --steps 4 --warmup 1 --no-cpu-baseline --no-shared"
+rocprofv3 --kernel-trace --stats -d $out/trace -o dense --output-format csv -- python3 bench.py --full --layout shared --dtype f32 --steps 20 --warmup 3 --no-cpu-baseline --no-shared > $out/trace_stdout.log 2>&1
 echo "trace done"
 i=0
 for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_BF16" \
