@@ -1562,10 +1562,15 @@ def _read_uvdata(files):
     files = [files] if isinstance(files, str) else list(files)
     try:
         from pyuvdata import UVData
-    except ImportError:
-        if len(files) != 1:
-            raise ImportError("reading several data files into one object needs pyuvdata")
-        return read_container(files[0])
+    except ImportError:  # uvh5 files (or archives of this package) read natively; several files are concatenated
+        uvd = read_container(files[0])
+        for fn in files[1:]:
+            more = read_container(fn)
+            rows = set(zip(uvd.ant_1_array.tolist(), uvd.ant_2_array.tolist(), uvd.time_array.tolist()))
+            if not rows.isdisjoint(zip(more.ant_1_array.tolist(), more.ant_2_array.tolist(), more.time_array.tolist())):
+                raise ValueError(f"{fn} holds (baseline, time) rows that an earlier input file already holds")
+            uvd = uvd + more
+        return uvd
     uvd = UVData()
     uvd.read(files)
     return uvd
@@ -1611,8 +1616,10 @@ def read_calibrate_and_model_dpss(
 ):
     """File driver of the DPSS fit -- calibration.py:1659-1817 (same arguments, returns and output files).
 
-    Inputs are paths (read with pyuvdata when it is installed; without it, containers written by this package) or the
-    objects themselves.  ``gpu_index`` picks the MI355X the solvers are created on (default: device 0, all of them are
+    Inputs are paths or the objects themselves.  Paths are read with pyuvdata when it is installed; without it, uvh5
+    data files (one or several, concatenated) are read by this package's own uvh5 reader (``uvh5.py``, the HDF5 subset
+    pyuvdata writes) and gain files must be containers written by this package.  Visibility outputs are written as uvh5
+    files pyuvdata and HDF5 tools open; gain outputs are containers.  ``gpu_index`` picks the MI355X the solvers are created on (default: device 0, all of them are
     visible); ``gpu_memory_limit`` [GiB] makes a fit that needs more device memory raise ``MemoryError`` instead of
     configuring an allocator pool.  As in the reference the baseline cuts are applied to the data only (:1767-1783
     select on ``uvd`` twice and never on the model) and ``fitted_info_outfilename`` is accepted but nothing is written.

@@ -81,11 +81,13 @@ def _copy_array(a):
 class SimpleUVData:
     """Container with the UVData attributes and methods the calamity path uses."""
 
-    def __init__(self, antpos, antpairs, freqs, times, pols=(-5,), data=None, flags=None, nsamples=None, antnums=None,
-                 x_orientation=None, future_shapes=False):
+    def __init__(self, antpos=None, antpairs=None, freqs=None, times=None, pols=(-5,), data=None, flags=None, nsamples=None,
+                 antnums=None, x_orientation=None, future_shapes=False):
+        if antpos is None:
+            return  # an empty object, filled by ``read_uvh5`` (pyuvdata's ``UVData()`` then ``read_uvh5(path)``)
         antpos = np.asarray(antpos, dtype=np.float64)
         self.antenna_numbers = np.arange(len(antpos)) if antnums is None else np.asarray(antnums)
-        self.antenna_positions = antpos  # ENU, metres (pyuvdata stores ECEF; only differences are used here)
+        self.antenna_positions = antpos  # ENU, metres (pyuvdata stores ECEF; uvh5.py converts on read and write)
         self.antenna_names = [f"ant{n}" for n in self.antenna_numbers]
         self.Nants_telescope = len(antpos)
         self.telescope_name = "synthetic"
@@ -126,7 +128,7 @@ class SimpleUVData:
         for k, v in self.__dict__.items():
             if isinstance(v, np.ndarray):
                 out.__dict__[k] = memo[id(v)] if id(v) in memo else _copy_array(v)  # (memo: arrays the caller will replace anyway)
-            elif isinstance(v, (list, tuple)):
+            elif isinstance(v, (list, tuple, dict)):
                 out.__dict__[k] = copy.copy(v)
         out._ap_index = dict(self._ap_index)
         return out
@@ -205,6 +207,12 @@ class SimpleUVData:
             keep &= np.isin(obj.time_array, np.atleast_1d(times))
         for name in ("ant_1_array", "ant_2_array", "time_array", "lst_array", "integration_time", "data_array", "flag_array", "nsample_array"):
             setattr(obj, name, getattr(obj, name)[keep])
+        if getattr(obj, "uvw_array", None) is not None:
+            obj.uvw_array = obj.uvw_array[keep]
+        if getattr(obj, "uvh5_header", None):
+            from .uvh5 import header_rows
+
+            obj.uvh5_header = header_rows(obj.uvh5_header, keep)
         obj._refresh()
         if not inplace:
             return obj
@@ -248,6 +256,15 @@ class SimpleUVData:
         out = copy.deepcopy(self)
         for name in ("ant_1_array", "ant_2_array", "time_array", "lst_array", "integration_time", "data_array", "flag_array", "nsample_array"):
             setattr(out, name, np.concatenate([getattr(self, name), getattr(other, name)]))
+        if getattr(self, "uvw_array", None) is not None:
+            if getattr(other, "uvw_array", None) is not None:
+                out.uvw_array = np.concatenate([self.uvw_array, other.uvw_array])
+            else:
+                del out.uvw_array  # (recomputed from the antenna positions when written)
+        if getattr(self, "uvh5_header", None):
+            from .uvh5 import header_concat
+
+            out.uvh5_header = header_concat(self.uvh5_header, getattr(other, "uvh5_header", None))
         out._refresh()
         return out
 
@@ -332,15 +349,22 @@ def _write_container(obj, path, clobber, kind):
 
 
 def read_container(path):
-    """Read a container written by ``SimpleUVData.write_uvh5`` / ``SimpleUVCal.write_calfits`` (an .npz archive whatever
-    its name; real uvh5 / calfits files need pyuvdata and are rejected here with a clear message)."""
+    """Read a uvh5 file (HDF5, by its signature) into a ``SimpleUVData``, or a container archive written by
+    ``SimpleUVCal.write_calfits`` / an earlier ``SimpleUVData.write_uvh5`` (.npz whatever its name).  calfits files need
+    pyuvdata and are rejected here with a clear message."""
     import json
 
+    from . import hdf5, uvh5
+
+    with open(path, "rb") as f:
+        head = f.read(8)
+    if head == hdf5.SIGNATURE:
+        return uvh5.read_uvh5(path)
     try:
         z = np.load(path, allow_pickle=False)
         kind = str(z["__kind__"])
     except Exception as e:  # not one of our archives (e.g. a real HDF5 / FITS file)
-        raise IOError(f"{path} is not a calamity_amd container archive; reading uvh5 / calfits files needs pyuvdata ({e})")
+        raise IOError(f"{path} is neither a uvh5 file nor a calamity_amd container archive; reading calfits files needs pyuvdata ({e})")
     obj = object.__new__(_KINDS[kind])
     for k, v in json.loads(str(z["__meta__"])).items():
         setattr(obj, k, v)
@@ -352,9 +376,24 @@ def read_container(path):
     return obj
 
 
-# The file driver (calibration.py:1659-1817) writes its outputs with these method names.  The duck-typed containers
-# store themselves as .npz archives under whatever name they are given; real uvh5 / calfits I/O needs pyuvdata objects.
-SimpleUVData.write_uvh5 = lambda self, path, clobber=False: _write_container(self, path, clobber, "uvdata")
+def _read_uvh5_into(self, path):
+    """pyuvdata's ``UVData.read_uvh5``: fill this object from a uvh5 file."""
+    from .uvh5 import read_uvh5
+
+    self.__dict__.clear()
+    self.__dict__.update(read_uvh5(path).__dict__)
+
+
+def _write_uvh5(self, path, clobber=False):
+    from .uvh5 import write_uvh5
+
+    write_uvh5(self, path, clobber=clobber)
+
+
+# The file driver (calibration.py:1659-1817) reads and writes with these method names: visibilities as real uvh5
+# (hdf5.py / uvh5.py); gains as an .npz container archive under whatever name they are given (calfits needs pyuvdata).
+SimpleUVData.read_uvh5 = _read_uvh5_into
+SimpleUVData.write_uvh5 = _write_uvh5
 SimpleUVCal.write_calfits = lambda self, path, clobber=False: _write_container(self, path, clobber, "uvcal")
 _KINDS.update(uvdata=SimpleUVData, uvcal=SimpleUVCal)
 
