@@ -1584,10 +1584,14 @@ def _read_uvcal(files):
     files = [files] if isinstance(files, str) else list(files)
     try:
         from pyuvdata import UVCal
-    except ImportError:
-        if len(files) != 1:
-            raise ImportError("reading several gain files into one object needs pyuvdata")
-        return read_container(files[0])
+    except ImportError:  # calfits files (or archives of this package) read natively; several files are concatenated in time
+        from .calfits import concat_times
+
+        objs = [read_container(fn) for fn in files]
+        for fn, obj in zip(files, objs):
+            if not is_uvcal(obj):
+                raise ValueError(f"{fn} holds visibilities, not gains")
+        return concat_times(objs, files)
     uvc = UVCal()
     uvc.read_calfits(files)
     return uvc
@@ -1618,8 +1622,9 @@ def read_calibrate_and_model_dpss(
 
     Inputs are paths or the objects themselves.  Paths are read with pyuvdata when it is installed; without it, uvh5
     data files (one or several, concatenated) are read by this package's own uvh5 reader (``uvh5.py``, the HDF5 subset
-    pyuvdata writes) and gain files must be containers written by this package.  Visibility outputs are written as uvh5
-    files pyuvdata and HDF5 tools open; gain outputs are containers.  ``gpu_index`` picks the MI355X the solvers are created on (default: device 0, all of them are
+    pyuvdata writes) and gain files (one or several, concatenated in time) by its calfits reader (``calfits.py``, the
+    FITS subset of ``fits.py``).  Visibility outputs are written as uvh5 files and gain outputs as calfits files, which
+    pyuvdata, HDF5 tools and FITS readers open.  ``gpu_index`` picks the MI355X the solvers are created on (default: device 0, all of them are
     visible); ``gpu_memory_limit`` [GiB] makes a fit that needs more device memory raise ``MemoryError`` instead of
     configuring an allocator pool.  As in the reference the baseline cuts are applied to the data only (:1767-1783
     select on ``uvd`` twice and never on the model) and ``fitted_info_outfilename`` is accepted but nothing is written.

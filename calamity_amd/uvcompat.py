@@ -326,7 +326,8 @@ _KINDS = {}  # kind tag -> container class (filled below)
 
 def _write_container(obj, path, clobber, kind):
     """Store a duck-typed container as an .npz archive (arrays as arrays, everything else as one JSON string) under
-    exactly the given name.  No pickle: reading one of these files can never execute code."""
+    exactly the given name.  No pickle: reading one of these files can never execute code.  (The format earlier versions
+    wrote gains and visibilities in; ``read_container`` still reads it.)"""
     import json
     import os
 
@@ -349,22 +350,23 @@ def _write_container(obj, path, clobber, kind):
 
 
 def read_container(path):
-    """Read a uvh5 file (HDF5, by its signature) into a ``SimpleUVData``, or a container archive written by
-    ``SimpleUVCal.write_calfits`` / an earlier ``SimpleUVData.write_uvh5`` (.npz whatever its name).  calfits files need
-    pyuvdata and are rejected here with a clear message."""
+    """Read a uvh5 file (HDF5, by its signature) into a ``SimpleUVData``, a calfits file (FITS, by its first card) into
+    a ``SimpleUVCal``, or a container archive written by an earlier version of this package (.npz whatever its name)."""
     import json
 
-    from . import hdf5, uvh5
+    from . import calfits, fits, hdf5, uvh5
 
     with open(path, "rb") as f:
-        head = f.read(8)
-    if head == hdf5.SIGNATURE:
+        head = f.read(len(fits.SIMPLE_CARD))
+    if head[:len(hdf5.SIGNATURE)] == hdf5.SIGNATURE:
         return uvh5.read_uvh5(path)
+    if head == fits.SIMPLE_CARD:
+        return calfits.read_calfits(path)
     try:
         z = np.load(path, allow_pickle=False)
         kind = str(z["__kind__"])
-    except Exception as e:  # not one of our archives (e.g. a real HDF5 / FITS file)
-        raise IOError(f"{path} is neither a uvh5 file nor a calamity_amd container archive; reading calfits files needs pyuvdata ({e})")
+    except Exception as e:  # not one of our archives
+        raise IOError(f"{path} is neither a uvh5 file, a calfits file nor a calamity_amd container archive ({e})")
     obj = object.__new__(_KINDS[kind])
     for k, v in json.loads(str(z["__meta__"])).items():
         setattr(obj, k, v)
@@ -390,11 +392,27 @@ def _write_uvh5(self, path, clobber=False):
     write_uvh5(self, path, clobber=clobber)
 
 
+def _read_calfits_into(self, path):
+    """pyuvdata's ``UVCal.read_calfits``: fill this object from a calfits file, or from a list of them concatenated
+    along time."""
+    from .calfits import read_calfits
+
+    self.__dict__.clear()
+    self.__dict__.update(read_calfits(path).__dict__)
+
+
+def _write_calfits(self, path, clobber=False):
+    from .calfits import write_calfits
+
+    write_calfits(self, path, clobber=clobber)
+
+
 # The file driver (calibration.py:1659-1817) reads and writes with these method names: visibilities as real uvh5
-# (hdf5.py / uvh5.py); gains as an .npz container archive under whatever name they are given (calfits needs pyuvdata).
+# (hdf5.py / uvh5.py), gains as real calfits (fits.py / calfits.py).
 SimpleUVData.read_uvh5 = _read_uvh5_into
 SimpleUVData.write_uvh5 = _write_uvh5
-SimpleUVCal.write_calfits = lambda self, path, clobber=False: _write_container(self, path, clobber, "uvcal")
+SimpleUVCal.read_calfits = _read_calfits_into
+SimpleUVCal.write_calfits = _write_calfits
 _KINDS.update(uvdata=SimpleUVData, uvcal=SimpleUVCal)
 
 
