@@ -17,7 +17,7 @@ CAL_PATH_AUTO, CAL_PATH_GENERAL, CAL_PATH_DENSE, CAL_PATH_DENSE_F32, CAL_PATH_DE
 CAL_LAUNCH_AUTO, CAL_LAUNCH_KERNELS, CAL_LAUNCH_ONE_TAIL, CAL_LAUNCH_GRAPH = 0, 1, 2, 3
 CAL_COMM_ID_BYTES = 128
 CAL_MAX_SLICES = 256
-CAL_ERR_NONFINITE = -6
+CAL_ERR_INVALID, CAL_ERR_NONFINITE = -1, -6
 
 
 class ProblemDesc(C.Structure):

@@ -65,17 +65,31 @@ def replicate_slices(prob, nt, groups=None, share_tiles=True):
 class _HostExchange:
     """In-process all-reduce between worker threads (cal_solver_set_exchange_hook): every worker leaves a view of its staging
     buffer, all of them reduce the views in rank order -- the same arithmetic on every worker -- and each writes the result
-    back into its own buffer."""
+    back into its own buffer.
+
+    Every worker also leaves the signature of its call, (dtype, size, op), and after the first barrier every worker checks
+    ALL of them: workers that issue different exchanges (a rank that took another path through a step) all raise the same
+    ExchangeMismatch, naming every rank's call, instead of reducing unrelated buffers or leaving one of them waiting alone."""
 
     def __init__(self, n):
         self.n = n
         self.barrier = threading.Barrier(n)
         self.slots = [None] * n
+        self.sigs = [None] * n
+        self.error = None  # the first mismatch seen (every worker raises it)
 
     def hook(self, rank):
         def all_reduce(arr, op):
             self.slots[rank] = arr
+            self.sigs[rank] = (arr.dtype.str, int(arr.size), op)
             self.barrier.wait(timeout=600)
+            sigs = list(self.sigs)  # (all workers read the same slots: all raise, or none)
+            if any(s != sigs[0] for s in sigs):
+                err = ExchangeMismatch("the workers issued different exchanges: "
+                                       + "; ".join(f"rank {r}: dtype {s[0]}, {s[1]} elements, {s[2]}" for r, s in enumerate(sigs)))
+                if self.error is None:
+                    self.error = err
+                raise err
             if op == "min":
                 out = np.minimum.reduce([self.slots[r] for r in range(self.n)])
             else:
@@ -90,6 +104,10 @@ class _HostExchange:
 
     def abort(self):
         self.barrier.abort()
+
+
+class ExchangeMismatch(RuntimeError):
+    """Workers of one fit issued exchanges of different dtype, size or reduction."""
 
 
 class SliceBatchFitter:
@@ -165,6 +183,9 @@ class SliceBatchFitter:
             t.start()
         for t in threads:
             t.join()
+        if self._host_exchange is not None and self._host_exchange.error is not None and any(e is not None for e in errs):
+            # (the library reports a failed hook by its return code only: name what the workers disagreed on)
+            raise self._host_exchange.error from next(e for e in errs if e is not None)
         for e in errs:
             if e is not None:
                 raise e
@@ -204,6 +225,23 @@ class SliceBatchFitter:
             c_r[self.cidx[r]] = o[2]
             c_i[self.cidx[r]] = o[3]
         return outs[0][0], outs[0][1], c_r, c_i  # the gains are replicated
+
+    def eval_grads(self):
+        """(loss, gain gradients, coefficient gradients) of the current parameters, like ``get_params``: the loss is the global
+        sum over slices, the gain gradients are all-reduced (every worker holds them), the coefficient gradients gathered."""
+        outs = self._each(lambda r, s: s.eval_grads())
+        if self.nworkers == 1:
+            return outs[0]
+        gc_r = np.empty(self.ncoeffs, dtype=self.dtype)
+        gc_i = np.empty(self.ncoeffs, dtype=self.dtype)
+        for r, o in enumerate(outs):
+            gc_r[self.cidx[r]] = o[3]
+            gc_i[self.cidx[r]] = o[4]
+        return outs[0][0], outs[0][1], outs[0][2], gc_r, gc_i
+
+    def slice_losses(self):
+        """Every slice's loss as of the last eval_grads (all-reduced: the same on every worker)."""
+        return self.solvers[0].slice_losses()
 
     def model(self):
         outs = self._each(lambda r, s: s.model())

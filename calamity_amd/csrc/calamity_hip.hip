@@ -218,6 +218,9 @@ struct SolverT final : cal_solver {
   int nheads = 0;                              // heads[0 .. nheads_mfma): fused_multi_mfma_kernel (at most kMmMaxVec vectors); the rest: fused_multi_kernel
   int nheads_mfma = 0;
   bool heads_one_pass = false;                 // the regularised step of the heads in ONE pass (all of them on fused_multi_mfma_kernel<.., REG = 2>)
+  bool heads_one_pass_local = false;           // ... as this rank's own heads allow (a communicator may clear heads_one_pass: agree_problem)
+  bool reg_prepass = false;                    // the regularised gradient pass is preceded by a loss pass and the slices' alpha (enqueue_pass);
+                                               // with a communicator agreed over the ranks: if one rank needs it, every rank runs it
   int mm_grid = 0;                             // workgroups of the matrix-core multi-slice launch: its head list is dealt over the 8 XCDs (-1: empty slot)
   size_t lds_multi_bytes = 0, lds_multi_mfma_bytes = 0;
   // dense (MFMA) path of the SHARED layout, fp32, one baseline per fitting group
@@ -376,19 +379,38 @@ struct SolverT final : cal_solver {
   // be taken by all ranks together -- and a rank whose set-up fails must not leave the others waiting in a collective.
   // So the rank-local part (validation, eligibility, every allocation and upload: set_problem_local) contains no collective
   // at all, and ONE agreement follows it on every path, failure included: the minimum over ranks of
-  // {set-up ok ? dense kernels built : -1, steps per host synchronisation}.  A negative minimum fails the call on every rank;
-  // a rank that built the dense path while another could not drops back to the general kernels (same buffers).
+  // {set-up ok ? kernel plan : -1, steps per host synchronisation, ...} (agree_problem).  A negative minimum fails the call
+  // on every rank; a rank that built the dense path while another could not drops back to the general kernels (same buffers);
+  // ranks whose problems differ in shape (nants, fpad, nslices, dtype) all fail with CAL_ERR_INVALID.
   int set_problem(const cal_problem_desc* d) override {
     const int rc = set_problem_local(d);
     if (!comm_on()) return rc;
     return agree_problem(rc);
   }
-  // the agreement: {set-up ok ? dense kernels built : -1, steps per host synchronisation, -(variables per slice), LAMB possible}
+  // the agreement: FOUR ints, minimum over the ranks (the exchange a set-up issues, pinned by tests/test_gpu_exchange_hook.py):
+  //   v[0] = set-up failed ? -1 : 4 * shape + plan, plan = 0: general kernels with the loss pre-pass of the regularised step,
+  //          1: general kernels without it, 2: dense kernels built.  The plans form a chain -- heads (STREAM layout) and the dense
+  //          kernels (SHARED layout) exclude each other, so "dense built" implies "no pre-pass" -- and the minimum of a chain is
+  //          both "every rank built the dense kernels" and "no rank needs the pre-pass"
+  //   v[1] = steps per host synchronisation (1 .. 256)
+  //   v[2] = LAMB possible ? -(variables per slice) : -2^30
+  //   v[3] = -shape
+  // shape (< 2^27) = (nslices - 1) << 19 | f64 << 18 | 18-bit hash of (nants, fpad): min(shape) == -min(-shape) only if every
+  // rank holds the same one (nslices and dtype compared exactly, nants and fpad through the hash)
+  static int shape_code(int na, int fp, int nsl) {
+    uint32_t h = 2166136261u;  // FNV-1a over the two words
+    for (uint32_t w : {(uint32_t)na, (uint32_t)fp})
+      for (int k = 0; k < 4; ++k) h = (h ^ ((w >> (8 * k)) & 0xffu)) * 16777619u;
+    return (nsl - 1) << 19 | (sizeof(T) == 8 ? 1 : 0) << 18 | (int)((h ^ (h >> 18)) & 0x3ffffu);
+  }
   int agree_problem(int rc) {
     const std::string msg = g_err;
     int local_nv = 0;
     for (int w : lamb_cvar_id) local_nv = std::max(local_nv, w + 1);
-    int v[4] = {rc == CAL_OK ? (mf_ok ? 1 : 0) : -1, rc == CAL_OK ? steps_per_sync : (1 << 30), -local_nv, rc == CAL_OK && lamb_ok ? 1 : 0};
+    const bool ok = rc == CAL_OK;
+    const int shape = ok ? shape_code(nants, fpad, nslices) : 0;
+    const int plan = mf_ok ? 2 : (nheads == 0 || heads_one_pass_local) ? 1 : 0;
+    int v[4] = {ok ? 4 * shape + plan : -1, ok ? steps_per_sync : (1 << 30), ok && lamb_ok ? -local_nv : -(1 << 30), -shape};
     const int arc = agree_min(v, 4);
     if (arc != CAL_OK) {
       has_problem = false;
@@ -402,10 +424,22 @@ struct SolverT final : cal_solver {
       has_problem = false;
       return fail(CAL_ERR_STATE, "set_problem failed on another rank of the communicator");
     }
-    if (!v[0]) mf_ok = false;
+    const int lo = v[0] >> 2, hi = -v[3];
+    if (lo != hi) {
+      has_problem = false;
+      const char* what = (lo >> 19) != (hi >> 19) ? "nslices" : ((lo >> 18) & 1) != ((hi >> 18) & 1) ? "the fit dtype" : "nants or fpad";
+      return fail(CAL_ERR_INVALID, "set_problem: the ranks of the communicator disagree on %s (this rank: nants %d, fpad %d, nslices %d, %d-byte reals)",
+                  what, nants, fpad, nslices, (int)sizeof(T));
+    }
+    const int agreed_plan = v[0] & 3;
+    if (agreed_plan < 2) mf_ok = false;
+    // the "sum" regulariser over heads: a rank that runs the loss pre-pass exchanges the slices' sums once more per step, so if
+    // one rank needs it every rank runs it (its heads then take the two-pass form, REG == 1, and its S partials join the sum)
+    heads_one_pass = heads_one_pass_local && agreed_plan >= 1;
+    reg_prepass = agreed_plan == 0;
     steps_per_sync = v[1];
-    lamb_nv = -v[2];
-    if (!v[3]) lamb_ok = false;
+    lamb_ok = lamb_ok && v[2] > -(1 << 30);
+    lamb_nv = lamb_ok ? -v[2] : 0;
     if (lamb_ok) {
       std::vector<int> slot(std::max(lamb_ncvar, 1), 0);
       for (int k = 0; k < lamb_ncvar; ++k) slot[k] = lamb_cvar_slice[k] * lamb_nv + lamb_cvar_id[k];
@@ -1028,6 +1062,8 @@ struct SolverT final : cal_solver {
     // ---- sets of baselines that share tiles -> head items with member lists (at most MultiCfg<T>::nb_max baselines each)
     nheads = 0;
     nheads_mfma = 0;
+    heads_one_pass_local = false;
+    local_reg_plan();
     lds_multi_bytes = 0;
     lds_multi_mfma_bytes = 0;
     {
@@ -1080,8 +1116,9 @@ struct SolverT final : cal_solver {
       nheads = (int)h_heads.size();
       // the "sum" regulariser over heads: one pass with two adjoint sets when every head is on the matrix-core kernel and narrow enough
       // for it (multi_mfma_kernels.hpp, REG == 2); else a loss pass for the slices' sums in front of the gradient pass (enqueue_pass)
-      heads_one_pass = nheads > 0 && nheads == nheads_mfma;
-      for (int head : h_heads) heads_one_pass = heads_one_pass && sorted[head].nvec <= kMmMaxVecOnePass<T>;
+      heads_one_pass_local = nheads > 0 && nheads == nheads_mfma;
+      for (int head : h_heads) heads_one_pass_local = heads_one_pass_local && sorted[head].nvec <= kMmMaxVecOnePass<T>;
+      local_reg_plan();
       // XCD-affine, antenna-grouped dispatch of the matrix-core heads: a head reads 2 gain rows per member (8 slices x 2 x 8 KB of a
       // 1024-channel band) -- a fifth of its bytes, 1.0 GB per pass of an 8-GPU rank's share against 23 MB of distinct gains, because
       // with the heads in cost order nothing a workgroup brings into its XCD's L2 is wanted by its neighbours (hit rate 17 %).
@@ -1291,9 +1328,14 @@ struct SolverT final : cal_solver {
     HIP_TRY(hipMemcpyAsync(dev, hook_buf, bytes, hipMemcpyHostToDevice, stream));
     return CAL_OK;
   }
+  // how the regularised step runs as far as this rank's own problem goes (no communicator; agree_problem may change it)
+  void local_reg_plan() {
+    heads_one_pass = heads_one_pass_local;
+    reg_prepass = nheads > 0 && !heads_one_pass_local;
+  }
   int agree_min(int* v, int n) {
     if (!comm_on()) return CAL_OK;
-    if (!agree_buf.p) CAL_TRY(agree_buf.alloc(4 * sizeof(int)));
+    if (agree_buf.bytes < (size_t)n * sizeof(int)) CAL_TRY(agree_buf.alloc((size_t)n * sizeof(int)));
     HIP_TRY(hipMemcpyAsync(agree_buf.p, v, n * sizeof(int), hipMemcpyHostToDevice, stream));
     CAL_TRY(all_reduce(agree_buf.p, n, CAL_XCHG_I32, CAL_XCHG_MIN));
     HIP_TRY(hipMemcpyAsync(v, agree_buf.p, n * sizeof(int), hipMemcpyDeviceToHost, stream));
@@ -1654,9 +1696,10 @@ struct SolverT final : cal_solver {
         if (grads) launch_dense<true>(m); else launch_dense<false>(m);
       }
     } else {
-      if (grads && R && nheads > 0 && !heads_one_pass) {
+      if (grads && R && reg_prepass) {
         // baselines that share tiles + the "sum" regulariser: their multi-slice kernels need alpha = 2 (S - P) of every slice BEFORE
         // the gradient pass (no second adjoint set there): a loss pass over everything, the slices' sums, alpha -- then the gradients
+        // (with a communicator also on a rank whose own heads would not need it: its partials are part of the slices' sums)
         launch_fused<MODE_LOSS>(a, true);
         hipLaunchKernelGGL((gain_grad_kernel<T, false>), dim3(nslices), dim3(256), 0, stream, q0.as<T2>(), q1.as<T2>(), gains.as<T2>(),
                            ant_ptr.as<int>(), ant_ent.as<int2>(), comm.as<T2>(), comm.as<T2>(), comm.as<T2>(), 0, fpad, part.as<double>(),
@@ -1738,7 +1781,7 @@ struct SolverT final : cal_solver {
   // exchange sits between the reduction and the update), general kernels, and not when every kernel is asked to be its own launch
   // (... nor with the regulariser over baselines that share tiles: alpha is needed between that path's two passes)
   bool one_launch_tail() const {
-    return !comm_on() && !mf_ok && tail_fits_one_launch() && launch_mode != CAL_LAUNCH_KERNELS && !(reg == CAL_REG_SUM && nheads > 0 && !heads_one_pass);
+    return !comm_on() && !mf_ok && tail_fits_one_launch() && launch_mode != CAL_LAUNCH_KERNELS && !(reg == CAL_REG_SUM && reg_prepass);
   }
   void launch_tail(const TailArgs<T>& a, unsigned grid, bool R) {
     if (R)
@@ -2189,6 +2232,7 @@ struct SolverT final : cal_solver {
     if (!fn) {
       nranks = 1;
       rank = 0;
+      local_reg_plan();
       return CAL_OK;
     }
     return joined(rk, nr);
@@ -2199,7 +2243,7 @@ struct SolverT final : cal_solver {
     if (!nranks_seen) return fail(CAL_ERR_INVALID, "comm_size: null");
     *nranks_seen = 1;
     if (!comm_on()) return CAL_OK;
-    if (!agree_buf.p) CAL_TRY(agree_buf.alloc(4 * sizeof(int)));
+    if (agree_buf.bytes < sizeof(int)) CAL_TRY(agree_buf.alloc(sizeof(int)));
     int one = 1;
     HIP_TRY(hipMemcpyAsync(agree_buf.p, &one, sizeof(int), hipMemcpyHostToDevice, stream));
     CAL_TRY(all_reduce(agree_buf.p, 1, CAL_XCHG_I32, CAL_XCHG_SUM));

@@ -1,6 +1,7 @@
 """One rank of a sharded fit whose exchange runs through cal_solver_set_exchange_hook over gloo (helper of
 tests/test_gpu_exchange_hook.py; started as a fresh process per rank, two of them sharing the one GPU)."""
 import argparse
+import datetime
 import os
 import sys
 
@@ -8,6 +9,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))  # (_slice_cases)
 
 
 def build_case(name):
@@ -52,6 +54,30 @@ def fit(sub, start, opts, run, reg_priors, hook=None, rank=0, world=1):
     return dict(losses=losses, stopped=stopped, nupd=nupd, g_r=g_r, g_i=g_i, c_r=c_r, c_i=c_i, path=path)
 
 
+def fit_slices(case_data, sub, rows, cidx, dtype, hook=None, rank=0, world=1):
+    """The multi-slice cases: T slices of a share in one solver (what a rank of ``bench.py --gpus N`` holds), STREAM layout,
+    the "sum" regulariser with every slice's own priors, 1 unrecorded + 12 recorded Adam steps through run_slices."""
+    from calamity_amd.solver import HipFitSolver
+
+    s = HipFitSolver(dtype=dtype)
+    if hook is not None:
+        s.set_exchange_hook(hook, rank, world)
+    s.set_problem(sub, layout="stream", kernel_path="general")
+    s.set_data(case_data["data_r"][rows], case_data["data_i"][rows], case_data["wgts"][rows])
+    s.set_params(case_data["g_r"], case_data["g_i"], case_data["c_r"][cidx], case_data["c_i"][cidx])
+    s.set_regularization("sum", case_data["prior_r"], case_data["prior_i"])
+    s.set_optimizer("Adam", learning_rate=1e-2)
+    s.run_slices(1, record=False)
+    res = s.run_slices(12, record=True, tol=0.0)
+    g_r, g_i, c_r, c_i = s.get_params()
+    s.close()
+    return dict(losses=np.stack([r[0] for r in res]), stopped=np.asarray([r[1] for r in res]), nupd=np.asarray([r[2] for r in res]),
+                g_r=g_r, g_i=g_i, c_r=c_r, c_i=c_i, path="general")
+
+
+SLICE_CASES = {"slices_wide32_sum": ("wide", np.float32)}  # case B of test_gpu_shard_agreement.py in fp32, one process per rank
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--case", required=True)
@@ -67,20 +93,39 @@ def main():
     import torch
     import torch.distributed as dist
 
-    dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{args.port}", rank=args.rank, world_size=args.world)
-    p, start, groups, opts, run, reg = build_case(args.case)
-    if groups is None:
-        sub, sub_start = D.shard_problem(p, start, args.rank, args.world)
-    else:
-        sub, sub_start = D.select_groups(p, start, groups[args.rank])
+    # (a rank that waits for a peer that never comes fails within a minute instead of holding the test until its timeout)
+    dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{args.port}", rank=args.rank, world_size=args.world,
+                            timeout=datetime.timedelta(seconds=60))
     calls = []
+    dtypes = {np.dtype(np.int32).str: 0, np.dtype(np.float32).str: 1, np.dtype(np.float64).str: 2}
 
     def all_reduce(arr, op):
         calls.append((arr.dtype.str, arr.size, op))
+        # every rank first shows what it is about to reduce: ranks that issue different exchanges all raise, naming each other's
+        # calls, instead of pairing unrelated buffers in the payload reduction
+        mine = torch.tensor([arr.size, dtypes[arr.dtype.str], 1 if op == "min" else 0], dtype=torch.int64)
+        every = [torch.zeros_like(mine) for _ in range(args.world)]
+        dist.all_gather(every, mine)
+        if any(not torch.equal(e, every[0]) for e in every):
+            raise RuntimeError("the ranks issued different exchanges (count, dtype code, op): "
+                               + "; ".join(f"rank {r}: {tuple(e.tolist())}" for r, e in enumerate(every)))
         t = torch.from_numpy(arr)  # shares the library's staging buffer: reduced in place
         dist.all_reduce(t, op=dist.ReduceOp.MIN if op == "min" else dist.ReduceOp.SUM)
 
-    out = fit(sub, sub_start, opts, run, priors(p) if reg else None, hook=all_reduce, rank=args.rank, world=args.world)
+    if args.case in SLICE_CASES:
+        import _slice_cases as SC
+
+        name, dtype = SLICE_CASES[args.case]
+        cd = SC.build(name, dtype)
+        sub, rows, cidx = SC.rank_share(cd, args.rank, args.world)
+        out = fit_slices(cd, sub, rows, cidx, dtype, hook=all_reduce, rank=args.rank, world=args.world)
+    else:
+        p, start, groups, opts, run, reg = build_case(args.case)
+        if groups is None:
+            sub, sub_start = D.shard_problem(p, start, args.rank, args.world)
+        else:
+            sub, sub_start = D.select_groups(p, start, groups[args.rank])
+        out = fit(sub, sub_start, opts, run, priors(p) if reg else None, hook=all_reduce, rank=args.rank, world=args.world)
     np.savez(args.out, ncalls=len(calls), call_sizes=np.asarray([c[1] for c in calls]), call_ops=np.asarray([c[2] for c in calls]),
              call_dtypes=np.asarray([c[0] for c in calls]), **{k: np.asarray(v) for k, v in out.items()})
     dist.barrier()

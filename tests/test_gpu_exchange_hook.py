@@ -104,3 +104,31 @@ def test_two_ranks_on_one_gpu_equal_the_single_solver_fit(case, tmp_path):
     per_step = [spec["gain_grad_reals"], 4] if not (reg and want_path == "dense") else [4, spec["gain_grad_reals"], 4]
     body = list(sizes[1:])
     assert len(body) % len(per_step) == 0 and body == per_step * (len(body) // len(per_step)), (case, body[:8])
+
+
+def test_two_rank_processes_with_a_wide_block_on_one_take_two_passes(tmp_path):
+    """T = 4 time slices per rank (what a rank of ``bench.py --gpus N`` holds), STREAM layout, fp32, "sum" regulariser: rank 0's
+    share holds a 230-vector block (its heads: a loss pre-pass), rank 1's not (alone it would take the one-pass form).  The two
+    processes agree in set_problem on the two-pass step and issue the same exchanges; against the one-solver fit of all slices
+    (fp32: losses 1e-4, parameters 1e-3), gains bit-identical on both ranks (tests/test_gpu_shard_agreement.py: case B)."""
+    import _exchange_rank as X
+    import _slice_cases as SC
+
+    name, dtype = X.SLICE_CASES["slices_wide32_sum"]
+    cd = SC.build(name, dtype)
+    sub, rows, cidx = SC.rank_share(cd, 0, 1)
+    ref = X.fit_slices(cd, sub, rows, cidx, dtype)
+    ranks = run_two_ranks("slices_wide32_sum", tmp_path)
+    for r, out in enumerate(ranks):
+        np.testing.assert_allclose(out["losses"], ref["losses"], rtol=1e-4)
+        assert out["losses"].shape == ref["losses"].shape and np.array_equal(out["nupd"], ref["nupd"]), r
+        assert relnorm(out["g_r"], ref["g_r"]) <= 1e-3 and relnorm(out["g_i"], ref["g_i"]) <= 1e-3, r
+        _, _, cidx_r = SC.rank_share(cd, r, 2)
+        assert relnorm(out["c_r"], ref["c_r"][cidx_r]) <= 1e-3 and relnorm(out["c_i"], ref["c_i"][cidx_r]) <= 1e-3, r
+    np.testing.assert_array_equal(ranks[0]["g_r"], ranks[1]["g_r"])
+    np.testing.assert_array_equal(ranks[0]["g_i"], ranks[1]["g_i"])
+    calls = [list(zip([str(d) for d in o["call_dtypes"]], [int(n) for n in o["call_sizes"]], [str(x) for x in o["call_ops"]])) for o in ranks]
+    assert calls[0] == calls[1]
+    assert calls[0][0] == (np.dtype(np.int32).str, 4, "min")
+    step = SC.per_step("two_pass", cd["nt"], dtype)
+    assert calls[0][1:] == step * 13, calls[0][1:4]  # (1 + 12 train steps)
