@@ -13,7 +13,7 @@ CAL_F32, CAL_F64 = 0, 1
 CAL_OPT_ADAM, CAL_OPT_ADAMAX, CAL_OPT_SGD, CAL_OPT_RMSPROP, CAL_OPT_ADAGRAD, CAL_OPT_NADAM, CAL_OPT_ADADELTA, CAL_OPT_FTRL, CAL_OPT_LAMB = range(9)
 CAL_REG_NONE, CAL_REG_SUM = 0, 1
 CAL_LAYOUT_STREAM, CAL_LAYOUT_SHARED = 0, 1
-CAL_PATH_AUTO, CAL_PATH_GENERAL, CAL_PATH_DENSE, CAL_PATH_DENSE_F32, CAL_PATH_DENSE_SPLIT1 = 0, 1, 2, 3, 4
+CAL_PATH_AUTO, CAL_PATH_GENERAL, CAL_PATH_DENSE, CAL_PATH_DENSE_F32, CAL_PATH_DENSE_SPLIT1, CAL_PATH_GENERAL_FULL = 0, 1, 2, 3, 4, 5
 CAL_LAUNCH_AUTO, CAL_LAUNCH_KERNELS, CAL_LAUNCH_ONE_TAIL, CAL_LAUNCH_GRAPH = 0, 1, 2, 3
 CAL_COMM_ID_BYTES = 128
 CAL_MAX_SLICES = 256
@@ -89,6 +89,8 @@ class KernelTiming(C.Structure):
         ("flops_per_launch", C.c_double),
         ("kernel_path", C.c_int32),
         ("dense_wg_per_cu", C.c_int32),
+        ("basis_folded", C.c_int32),
+        ("reserved", C.c_int32),
     ]
 
 
@@ -98,6 +100,7 @@ SYMBOLS = {
     "cal_last_error": (C.c_char_p, []),
     "cal_version": (C.c_char_p, []),
     "cal_device_count": (C.c_int, [C.POINTER(C.c_int)]),
+    "cal_basis_foldable": (C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "cal_device_info": (C.c_int, [C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "cal_device_stream_peak": (C.c_int, [C.c_int, C.c_size_t, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "cal_device_busy_clock_mhz": (C.c_int, [C.c_int, C.POINTER(C.c_double)]),

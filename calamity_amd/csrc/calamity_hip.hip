@@ -142,6 +142,39 @@ inline int grid_for(long long n, int block = 256, int cap = 16384) {
   return (int)std::max<long long>(1, std::min<long long>(g, cap));
 }
 
+// Mirror symmetry of one basis block, row-major [nfreqs][nvec]: A[F-1-f][k] = (-1)^k A[f][k] (discrete prolate spheroidal
+// sequences centred on zero delay alternate between symmetric and antisymmetric vectors).  Host only.  Returns false for a block
+// with a non-finite element; otherwise the largest |A[F-1-f][k] - (-1)^k A[f][k]| and the largest |A|.
+template <typename T>
+bool mirror_residual(const T* a, int nfreqs, int nvec, double* resid, double* amax) {
+  double r = 0, m = 0;
+  for (long long i = 0; i < (long long)nfreqs * nvec; ++i) {
+    const double x = std::fabs((double)a[i]);
+    if (!std::isfinite(x)) return false;
+    m = std::max(m, x);
+  }
+  for (int f = 0; f < nfreqs / 2; ++f) {
+    const T* lo = a + (long long)f * nvec;
+    const T* hi = a + (long long)(nfreqs - 1 - f) * nvec;
+    for (int k = 0; k < nvec; ++k) r = std::max(r, std::fabs((double)hi[k] - ((k & 1) ? -(double)lo[k] : (double)lo[k])));
+  }
+  *resid = r;
+  *amax = m;
+  return true;
+}
+// The streaming kernel may read channels [0, F/2) of such a block alone (fit_kernels.hpp: process_item, FOLD) when the mirror
+// half carries no information of its own: in fp32 when no element differs from its mirror partner by more than half a unit in
+// the last place of the block's largest element -- what the cast of an fp64 basis to fp32 leaves behind -- and in fp64 when the
+// halves agree exactly.  fb: the block's tile width; the band's half must consist of whole tiles.
+template <typename T>
+bool block_foldable(const T* a, int nfreqs, int nvec, int nrowblk, int fb, double* resid, double* amax) {
+  *resid = *amax = 0;
+  if (nrowblk != 1 || nfreqs < 2 || (nfreqs & 1) || fb <= 0 || (nfreqs / 2) % fb != 0) return false;
+  if (!mirror_residual(a, nfreqs, nvec, resid, amax)) return false;
+  if (sizeof(T) == 4) return *resid <= 0.5 * 1.1920928955078125e-07 * *amax;
+  return *resid == 0.0;
+}
+
 }  // namespace
 
 // ================================================================================================================
@@ -195,6 +228,7 @@ struct SolverT final : cal_solver {
   int nslices = 1, na_slice = 0;
   DevBuf slice_coff, slice_ipart_ptr, slice_ipart_idx, slice_ppart_ptr, slice_ppart_idx, slice_cblk;
   std::vector<int> h_slice_coff, h_slice_cblk;
+  bool fold = false;        // the single-baseline items read folded tiles: channels [0, nfreqs / 2) of a mirror-symmetric basis (process_item, FOLD)
   bool small_loads = false; // every single-baseline item's tile fits kSmallLoads loads per thread: the narrow instance of fused_basis_kernel serves the loss / gradient passes
   int nitems_simple = 0;   // items [0, nitems_simple) are single-baseline groups (fused_basis_kernel), the rest multi-baseline (fused_group_kernel)
   int nitems_plain = 0;    // items [0, nitems_plain) of those are not covered by a head item of the multi-slice kernels
@@ -365,13 +399,13 @@ struct SolverT final : cal_solver {
     if (fb == M / 8) return multi_lds_bytes<T, M / 8>();
     return multi_lds_bytes<T, M / 16>();
   }
-  static size_t lds_for(int fb) {
+  static size_t lds_for(int fb, bool fold) {
     constexpr int M = FbSet<T>::fb_max;
-    if (fb == M) return TileCfg<T, M>::lds_bytes();
-    if (fb == M / 2) return TileCfg<T, M / 2>::lds_bytes();
-    if (fb == M / 4) return TileCfg<T, M / 4>::lds_bytes();
-    if (fb == M / 8) return TileCfg<T, M / 8>::lds_bytes();
-    return TileCfg<T, M / 16>::lds_bytes();
+    if (fb == M) return TileCfg<T, M>::lds_bytes(fold);
+    if (fb == M / 2) return TileCfg<T, M / 2>::lds_bytes(fold);
+    if (fb == M / 4) return TileCfg<T, M / 4>::lds_bytes(fold);
+    if (fb == M / 8) return TileCfg<T, M / 8>::lds_bytes(fold);
+    return TileCfg<T, M / 16>::lds_bytes(fold);
   }
 
   // ------------------------------------------------------------------------------------------------------------
@@ -485,7 +519,7 @@ struct SolverT final : cal_solver {
     if (fb_used_max > pw) return fail(CAL_ERR_INVALID, "set_problem: internal error: tile width %d exceeds the row padding %d", fb_used_max, pw);
     fpad = (nfreqs + pw - 1) / pw * pw;
     if (d->kernel_path != CAL_PATH_AUTO && d->kernel_path != CAL_PATH_GENERAL && d->kernel_path != CAL_PATH_DENSE && d->kernel_path != CAL_PATH_DENSE_F32 &&
-        d->kernel_path != CAL_PATH_DENSE_SPLIT1)
+        d->kernel_path != CAL_PATH_DENSE_SPLIT1 && d->kernel_path != CAL_PATH_GENERAL_FULL)
       return fail(CAL_ERR_INVALID, "set_problem: bad kernel_path %d", d->kernel_path);
     if (d->kernel_path == CAL_PATH_DENSE_F32 && !std::is_same<T, float>::value)
       return fail(CAL_ERR_UNSUPPORTED, "set_problem: CAL_PATH_DENSE_F32 is the fp32 kernel on v_mfma_f32_32x32x2_f32; this solver is fp64");
@@ -515,9 +549,7 @@ struct SolverT final : cal_solver {
     // not fill the chip and the general kernel (one workgroup per baseline) is 2-3x faster (HERA-37 fp32: 25 vs 71 us)
     // (with a communicator the ranks then agree on ONE path -- the exchange payload of the "sum" regulariser differs between
     // the two -- in set_problem, behind all the rank-local work)
-    const bool want_mfma = dense_ok && d->kernel_path != CAL_PATH_GENERAL && (forced_dense || nbls >= 2048);
-    lds_bytes = 0;
-    for (int u = 0; u < nbasis; ++u) lds_bytes = std::max(lds_bytes, lds_for(fb_u[u]));
+    const bool want_mfma = dense_ok && d->kernel_path != CAL_PATH_GENERAL && d->kernel_path != CAL_PATH_GENERAL_FULL && (forced_dense || nbls >= 2048);
     for (int b = 0; b < d->nbls; ++b) {
       if (d->bl_ant0[b] < 0 || d->bl_ant0[b] >= nants || d->bl_ant1[b] < 0 || d->bl_ant1[b] >= nants)
         return fail(CAL_ERR_INVALID, "set_problem: baseline %d has an antenna index outside [0, %d)", b, nants);
@@ -617,6 +649,23 @@ struct SolverT final : cal_solver {
         alias_root[b] = r;
       }
     }
+    // ---- folded tiles: decided once per problem, from the description and the dtype alone (never from the communicator, the
+    // launch mode or the device: solvers that are compared bit for bit must take the same form).  The streaming layout, every
+    // item served by fused_basis_kernel (single-baseline groups, no shared tiles: the multi-slice and the group kernels keep
+    // full tiles) and every basis block in use mirror-symmetric; CAL_PATH_GENERAL_FULL keeps the full tiles.
+    fold = layout == CAL_LAYOUT_STREAM && d->kernel_path != CAL_PATH_GENERAL_FULL;
+    for (int g = 0; g < ngrps && fold; ++g) fold = d->grp_bl_start[g + 1] - d->grp_bl_start[g] == 1;
+    for (int b = 0; b < nbls && fold; ++b) fold = alias_root[b] < 0;
+    std::vector<char> basis_used(nbasis, 0);
+    for (int g = 0; g < ngrps; ++g) basis_used[d->grp_basis[g]] = 1;
+    for (int u = 0; u < nbasis && fold; ++u) {
+      double resid, amax;
+      if (basis_used[u])
+        fold = block_foldable(static_cast<const T*>(d->basis_data) + d->basis_offset[u], nfreqs, d->basis_nvec[u], d->basis_nrowblk[u], fb_u[u], &resid, &amax);
+    }
+    const int ftile = fold ? nfreqs / 2 : fpad;  // channels a baseline's tiles cover
+    lds_bytes = 0;
+    for (int u = 0; u < nbasis; ++u) lds_bytes = std::max(lds_bytes, lds_for(fb_u[u], fold));
     std::vector<char> in_alias_set(nbls, 0);
     const bool multi_ok = (long long)(nbls + 1) * fpad < (1LL << 31) && (long long)nants * fpad < (1LL << 31);  // the multi kernel's 32-bit sample offsets
     for (int b = 0; b < nbls; ++b)
@@ -628,14 +677,21 @@ struct SolverT final : cal_solver {
     CAL_TRY(raw.alloc((size_t)raw_elems * sizeof(T), false));
     HIP_TRY(hipMemcpyAsync(raw.p, d->basis_data, (size_t)raw_elems * sizeof(T), hipMemcpyHostToDevice, stream));
     std::vector<long long> uoff(nbasis + 1, 0);
-    for (int u = 0; u < nbasis; ++u) uoff[u + 1] = uoff[u] + (long long)d->basis_nrowblk[u] * fpad * d->basis_nvec[u];
+    // (folded: the lower half band of the blocks in use -- one row block each -- verbatim; the others are not needed)
+    for (int u = 0; u < nbasis; ++u)
+      uoff[u + 1] = uoff[u] + (fold ? (basis_used[u] ? (long long)ftile * d->basis_nvec[u] : 0LL) : (long long)d->basis_nrowblk[u] * fpad * d->basis_nvec[u]);
     // (+ a zeroed pad: fused_multi_mfma_kernel reads on past the last rows of a tile, against zero coefficients)
     CAL_TRY(utiles.alloc(((size_t)uoff[nbasis] + kMmTilePadElems) * sizeof(T), false));
     HIP_TRY(hipMemsetAsync(utiles.as<T>() + uoff[nbasis], 0, kMmTilePadElems * sizeof(T), stream));
     for (int u = 0; u < nbasis; ++u) {
       const long long n = uoff[u + 1] - uoff[u];
-      hipLaunchKernelGGL(retile_kernel<T>, dim3(grid_for(n)), dim3(256), 0, stream, raw.as<T>() + d->basis_offset[u],
-                         utiles.as<T>() + uoff[u], nfreqs, fpad, d->basis_nvec[u], d->basis_nrowblk[u], fb_u[u]);
+      if (n == 0) continue;
+      if (fold)  // channels [0, nfreqs / 2) of the block's only row block: whole tiles, no padding
+        hipLaunchKernelGGL(retile_kernel<T>, dim3(grid_for(n)), dim3(256), 0, stream, raw.as<T>() + d->basis_offset[u],
+                           utiles.as<T>() + uoff[u], ftile, ftile, d->basis_nvec[u], 1, fb_u[u]);
+      else
+        hipLaunchKernelGGL(retile_kernel<T>, dim3(grid_for(n)), dim3(256), 0, stream, raw.as<T>() + d->basis_offset[u],
+                           utiles.as<T>() + uoff[u], nfreqs, fpad, d->basis_nvec[u], d->basis_nrowblk[u], fb_u[u]);
     }
     HIP_TRY(hipGetLastError());
     std::vector<long long> h_bl_tile(nbls);
@@ -660,7 +716,7 @@ struct SolverT final : cal_solver {
       for (int b = 0; b < nbls; ++b) {
         const int u = d->grp_basis[grp_of_bl[b]];
         const int rb = d->bl_rowblk ? d->bl_rowblk[b] : 0;
-        const long long n = (long long)fpad * d->basis_nvec[u];
+        const long long n = (long long)ftile * d->basis_nvec[u];
         const bool alias = b > 0 && grp_of_bl[b - 1] == grp_of_bl[b] && (d->bl_rowblk ? d->bl_rowblk[b - 1] : 0) == rb;
         if (alias) {
           h_bl_tile[b] = h_bl_tile[b - 1];
@@ -681,7 +737,7 @@ struct SolverT final : cal_solver {
       hipLaunchKernelGGL(tile_copy_kernel<T>, dim3((unsigned)jobs.size()), dim3(256), 0, stream, utiles.as<T>(), tiles.as<T>(), djobs.as<CopyJob>());
       HIP_TRY(hipGetLastError());
       HIP_TRY(hipStreamSynchronize(stream));
-      basis_bytes = (double)off / fpad * nfreqs * sizeof(T);
+      basis_bytes = fold ? (double)off * sizeof(T) : (double)off / fpad * nfreqs * sizeof(T);
     }
     mf_ok = false;
     mf_split = false;
@@ -906,7 +962,7 @@ struct SolverT final : cal_solver {
     // ---- work items: whole groups when that already fills the chip, otherwise split along tiles
     long long total_tiles = 0;
     for (int g = 0; g < ngrps; ++g)
-      if (d->grp_bl_start[g + 1] - d->grp_bl_start[g] == 1) total_tiles += fpad / fb_u[d->grp_basis[g]];
+      if (d->grp_bl_start[g + 1] - d->grp_bl_start[g] == 1) total_tiles += ftile / fb_u[d->grp_basis[g]];  // (folded tiles where the problem folds)
     // one item per group when the groups alone fill the chip (256 CUs x ~4 resident workgroups, several waves of them);
     // otherwise split groups along their tiles (partial coefficient gradients are summed by coeff_partial_reduce_kernel)
     // With at least one group per CU an item is never smaller than 1024 channels of its group (8 tiles of the widest fp32
@@ -927,7 +983,7 @@ struct SolverT final : cal_solver {
     lds_group_bytes = 0;
     for (int g = 0; g < ngrps; ++g) {
       const int u = d->grp_basis[g];
-      const int ntpb = fpad / fb_u[u];
+      const int ntpb = ftile / fb_u[u];
       int fl = 0;
       while ((1 << fl) < fb_u[u]) ++fl;
       Item it{};
@@ -1574,6 +1630,7 @@ struct SolverT final : cal_solver {
     a.stream_once = layout == CAL_LAYOUT_STREAM ? 1 : 0;
     a.members = members.as<Member>();
     a.heads = nheads > 0 ? heads.as<int>() : nullptr;
+    a.nfreqs = nfreqs;
     return a;
   }
   // LDS buffer of gbar_G rows (MODE_GRAD); the narrowest tiles have the longest offset table
@@ -1586,7 +1643,20 @@ struct SolverT final : cal_solver {
     if (nsimple > 0) {
       a.item_base = 0;
       constexpr bool kHasSmall = MODE == MODE_LOSS || MODE == MODE_GRAD;
-      if (kHasSmall && small_loads) {
+      if (fold) {
+        // folded tiles: every item of the problem is one (set_problem)
+        if (kHasSmall && small_loads) {
+          if constexpr (kHasSmall) {
+            if (with_reg)
+              hipLaunchKernelGGL((fused_basis_kernel<T, MODE, true, kSmallLoads, true>), dim3(nsimple), dim3(kThreads), lds_bytes + (MODE == MODE_GRAD ? kQLdsMax2 : 0), stream, a);
+            else
+              hipLaunchKernelGGL((fused_basis_kernel<T, MODE, false, kSmallLoads, true>), dim3(nsimple), dim3(kThreads), lds_bytes + (MODE == MODE_GRAD ? kQLdsMax1 : 0), stream, a);
+          }
+        } else if (with_reg)
+          hipLaunchKernelGGL((fused_basis_kernel<T, MODE, true, kMaxLoads, true>), dim3(nsimple), dim3(kThreads), lds_bytes + (MODE == MODE_GRAD ? kQLdsMax2 : 0), stream, a);
+        else
+          hipLaunchKernelGGL((fused_basis_kernel<T, MODE, false, kMaxLoads, true>), dim3(nsimple), dim3(kThreads), lds_bytes + (MODE == MODE_GRAD ? kQLdsMax1 : 0), stream, a);
+      } else if (kHasSmall && small_loads) {
         if constexpr (kHasSmall) {
           if (with_reg)
             hipLaunchKernelGGL((fused_basis_kernel<T, MODE, true, kSmallLoads>), dim3(nsimple), dim3(kThreads), lds_bytes + (MODE == MODE_GRAD ? kQLdsMax2 : 0), stream, a);
@@ -2187,7 +2257,10 @@ struct SolverT final : cal_solver {
         basis_bytes + s * (3.0 * nfreqs * nbls + 2.0 * ncoef + 2.0 * nants * nfreqs) + s * (10.0 * ncoef + 10.0 * nants * nfreqs);
     // forward A c and adjoint A^T gbar_v, complex x real: 4 + 4 flops per (channel, vector); the dense path's regularised step
     // runs the forward twice (loss-only pass for S, then the gradient pass) inside the timed region
-    out->flops_per_launch = ((mf_ok && reg == CAL_REG_SUM) ? 12.0 : 8.0) * nfreqs * (double)ncoef;
+    // (folded tiles: half the channels are multiplied, like half the basis bytes are read)
+    out->flops_per_launch = ((mf_ok && reg == CAL_REG_SUM) ? 12.0 : 8.0) * (fold ? nfreqs / 2 : nfreqs) * (double)ncoef;
+    out->basis_folded = fold ? 1 : 0;
+    out->reserved = 0;
     out->kernel_path = mf_ok ? ((mf_split || !std::is_same<T, float>::value) ? (mf_split && !mf_split2 ? CAL_PATH_DENSE_SPLIT1 : CAL_PATH_DENSE) : CAL_PATH_DENSE_F32) : CAL_PATH_GENERAL;
     // the dense kernels are written for two workgroups per CU (160 KB of LDS): a basis block of ~250 vectors needs more than
     // 80 KB for its coefficient panel + rings and runs one
@@ -2305,6 +2378,17 @@ int cal_debug_read_stamps(void* out) { return (int)hipMemcpyFromSymbol(out, HIP_
 #endif
 const char* cal_last_error(void) { return g_err.c_str(); }
 const char* cal_version(void) { return "calamity_hip 0.1 (gfx950)"; }
+
+int cal_basis_foldable(int dtype, const void* block, int32_t nfreqs, int32_t nvec, int32_t nrowblk, double* max_residual, double* max_abs) {
+  if (!block || nfreqs <= 0 || nvec <= 0 || nrowblk <= 0 || (dtype != CAL_F32 && dtype != CAL_F64)) return fail(CAL_ERR_INVALID, "cal_basis_foldable: bad argument");
+  double resid = 0, amax = 0;
+  bool ok;
+  if (dtype == CAL_F32) ok = block_foldable(static_cast<const float*>(block), nfreqs, nvec, nrowblk, SolverT<float>::choose_fb(nvec, nfreqs), &resid, &amax);
+  else ok = block_foldable(static_cast<const double*>(block), nfreqs, nvec, nrowblk, SolverT<double>::choose_fb(nvec, nfreqs), &resid, &amax);
+  if (max_residual) *max_residual = resid;
+  if (max_abs) *max_abs = amax;
+  return ok ? 1 : 0;
+}
 
 int cal_device_count(int* count) {
   if (!count) return fail(CAL_ERR_INVALID, "cal_device_count: null");

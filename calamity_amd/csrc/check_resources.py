@@ -6,7 +6,8 @@ a wave is in that count, and register spills are vector-memory operations (scrat
 just be slower, it would read ring slots before they have landed.  So: no scratch, no spills, in any kernel whose name
 contains `fused_dense`; and two waves per SIMD where the kernels are written for two.
 `fused_multi_mfma_kernel<float>` sits at 245 of the 256 registers two waves per SIMD leave it (the double instance has a
-CU to itself): no scratch and no spilled VGPRs there either (a few SGPR spills into lanes of a VGPR are tolerated: they sit outside its job loop)."""
+CU to itself): no scratch and no spilled VGPRs there either (a few SGPR spills into lanes of a VGPR are tolerated: they sit outside its job loop).
+`fused_basis_kernel`: no scratch in any instance; four waves per SIMD in the fp32 gradient instances with full and with folded tiles."""
 import re
 import sys
 
@@ -27,6 +28,16 @@ for line in sys.stdin:
         elif m and int(m.group(2)) != 0:
             bad.append(f"{cur}: {m.group(1)} = {m.group(2)}")
         continue
+    if cur is not None and "fused_basis_kernel" in cur:
+        # the streaming kernel's headline instances (fp32, gradient pass, no regulariser, full and folded tiles) hide HBM latency with
+        # four workgroups per CU: four waves per SIMD and no scratch; no instance of the kernel may use scratch at all
+        m = re.search(r"remark:\s+(ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
+        if m and m.group(1).startswith("Occupancy"):
+            if re.search(r"fused_basis_kernelIfLi1ELb0ELi7ELb[01]E", cur) and int(m.group(2)) < 4:
+                bad.append(f"{cur}: occupancy {m.group(2)} waves/SIMD (< 4)")
+        elif m and int(m.group(2)) != 0:
+            bad.append(f"{cur}: {m.group(1)} = {m.group(2)}")
+        continue
     if cur is None or "fused_dense" not in cur:
         continue
     m = re.search(r"remark:\s+(ScratchSize \[bytes/lane\]|SGPRs Spill|VGPRs Spill|Occupancy \[waves/SIMD\]): (\d+)", line)
@@ -42,6 +53,6 @@ for line in sys.stdin:
 if seen == 0:
     bad.append("no fused_dense kernel found in the compiler's resource remarks")
 if bad:
-    sys.stderr.write("check_resources: the dense kernels must not spill (scratch traffic breaks their counted waits):\n  " + "\n  ".join(bad) + "\n")
+    sys.stderr.write("check_resources: the dense kernels must not spill (scratch traffic breaks their counted waits), the streaming kernel must keep its occupancy:\n  " + "\n  ".join(bad) + "\n")
     sys.exit(1)
 print(f"check_resources: {seen} dense kernels, no scratch, no spills")

@@ -147,6 +147,7 @@ struct FusedArgs {
   int item_base;             // index of this launch's first item in `items` / `part`
   const Member* members;     // multi kernel: the baselines of every head item
   const int* heads;          // multi kernel: [grid] item index of each head
+  int nfreqs;                // channels of the band (folded tiles: channel f and its mirror nfreqs - 1 - f travel together)
 };
 
 enum { MODE_LOSS = 0, MODE_GRAD = 1, MODE_MODEL = 2, MODE_INIT = 3 };  // INIT: c = A^T (src * [w != 0]), calibration.py:875-902
@@ -158,8 +159,9 @@ struct TileCfg {
   static constexpr int LPR = FB / VEC;                 // lanes that hold one row of the tile
   static constexpr int NS = kThreads / LPR;            // rows covered by one 256-thread load = MAXK / kMaxLoads
   static constexpr int QT = 1024 / FB;                 // tiles of gbar_G the LDS buffer holds (1024 channels)
-  static constexpr size_t lds_bytes() {
-    return (2 * (size_t)kWaves * FB + 2 * (size_t)FB + MAXK) * 2 * sizeof(T)  // forward partials (two parities), gbar_v, c
+  // fold: the even- and the odd-vector partials stay apart and gbar_v covers the tile's mirror channels too
+  static constexpr size_t lds_bytes(bool fold = false) {
+    return ((fold ? 4 : 2) * (size_t)kWaves * FB + (fold ? 4 : 2) * (size_t)FB + MAXK) * 2 * sizeof(T)  // forward partials (two parities), gbar_v, c
            + 64;
   }
   // MODE_GRAD only: gbar_G rows (and the regulariser's second set) waiting for the flush, and their row offsets
@@ -257,13 +259,15 @@ __device__ __forceinline__ double pair_sum8(double x) {
   return x + __builtin_bit_cast(double, ((long long)hi << 32) | (long long)(unsigned)lo);
 }
 // sum over the 64 / LPR lanes {lane ^ k LPR}: the rows of a tile held by the other lanes of the wave (ascending strides)
-template <int LPR, typename T> __device__ __forceinline__ T sum_row_lanes(T x) {
-  if constexpr (LPR <= 1) x += __shfl_xor(x, 1, 64);
-  if constexpr (LPR <= 2) x += __shfl_xor(x, 2, 64);
-  if constexpr (LPR <= 4) x += __shfl_xor(x, 4, 64);
-  if constexpr (LPR <= 8) x = pair_sum8(x);
-  if constexpr (LPR <= 16) x = pair_sum16(x);
-  if constexpr (LPR <= 32) x = pair_sum32(x);
+// SPLIT: without the stride-LPR stage, the one that adds rows of the other parity: lanes [0, LPR) end up with the sum over
+// the wave's even rows, lanes [LPR, 2 LPR) with the sum over its odd rows (folded tiles)
+template <int LPR, bool SPLIT = false, typename T> __device__ __forceinline__ T sum_row_lanes(T x) {
+  if constexpr (LPR <= 1 && !(SPLIT && LPR == 1)) x += __shfl_xor(x, 1, 64);
+  if constexpr (LPR <= 2 && !(SPLIT && LPR == 2)) x += __shfl_xor(x, 2, 64);
+  if constexpr (LPR <= 4 && !(SPLIT && LPR == 4)) x += __shfl_xor(x, 4, 64);
+  if constexpr (LPR <= 8 && !(SPLIT && LPR == 8)) x = pair_sum8(x);
+  if constexpr (LPR <= 16 && !(SPLIT && LPR == 16)) x = pair_sum16(x);
+  if constexpr (LPR <= 32 && !(SPLIT && LPR == 32)) x = pair_sum32(x);
   return x;
 }
 
@@ -289,7 +293,17 @@ template <typename T> __device__ __forceinline__ T ldsum(T v) {
 // L: 16-byte loads per thread and tile the body is unrolled for (rows l NS + ks, l < L): kMaxLoads covers every tile; problems whose
 // blocks all fit two loads (the tutorial's: at most 2 NS vectors) run an instance with L = 2 -- a fraction of the registers, twice
 // the workgroups per CU, no loads and products spent on rows past nvec
-template <typename T, int FB, int MODE, bool REG, int L = kMaxLoads>
+//
+// FOLD: the basis is mirror-symmetric about the band centre, A[F-1-f][k] = (-1)^k A[f][k] (discrete prolate spheroidal
+// sequences centred on zero delay), and only its channels [0, F/2) are in HBM.  A tile then serves its FB channels AND their
+// FB mirror channels:
+//   forward  E[f] = sum over even k, O[f] = sum over odd k;   v[f] = E[f] + O[f],   v[F-1-f] = E[f] - O[f]
+//   adjoint  gc[k] = sum_{f < F/2} A[k][f] (gbar_v[f] + (-1)^k gbar_v[F-1-f])
+// NS is even for every FB, so all rows l NS + ks of a thread have the parity of ks: its forward partial is purely an E or
+// purely an O partial, and its adjoint needs one of the two combinations only.  The products per loaded byte stay the same;
+// the bytes halve.  The per-channel stage runs on 2 FB threads (the second FB take the mirror block, in that block's own
+// channel order); tiles are counted in folded tiles: tile j = channel blocks j and F / FB - 1 - j.
+template <typename T, int FB, int MODE, bool REG, int L = kMaxLoads, bool FOLD = false>
 __device__ __forceinline__ void process_item(const FusedArgs<T>& A, const Item it, unsigned char* smem, int item_idx, const DevState* st_own) {
   using C = TileCfg<T, FB>;
   using T2 = vec2_t<T>;
@@ -305,12 +319,14 @@ __device__ __forceinline__ void process_item(const FusedArgs<T>& A, const Item i
   const int ks = tid / LPR;
   const int f0 = fq * VEC;
   const int nvec = it.nvec;
-  const int ntpb = A.fpad / FB;
+  constexpr int NP = FOLD ? 2 : 1;          // row parities kept apart in the forward partials; channel blocks per tile
+  constexpr int CH = NP * FB;               // channels of the per-channel stage
+  const int ntpb = FOLD ? A.nfreqs / (2 * FB) : A.fpad / FB;
   const int tile_elems = nvec * FB;
 
-  T2* s_pv = reinterpret_cast<T2*>(smem);   // [2][kWaves][FB] forward partials of the four waves, by tile parity
-  T2* s_gv = s_pv + 2 * kWaves * FB;        // [2][FB]: gbar_v of e0, of the w part (regulariser)
-  T2* s_c = s_gv + 2 * FB;                  // [MAXK] coefficients of the group
+  T2* s_pv = reinterpret_cast<T2*>(smem);   // [2][kWaves][NP][FB] forward partials of the four waves, by tile parity
+  T2* s_gv = s_pv + 2 * kWaves * CH;        // [2][NP][FB]: gbar_v of e0, of the w part (regulariser); FOLD: [.][1][i] belongs to the mirror of channel i
+  T2* s_c = s_gv + 2 * CH;                  // [MAXK] coefficients of the group
   T2* s_q = s_c + C::MAXK;                  // MODE_GRAD: [REG ? 2 : 1][QT][FB] gbar_G rows waiting for the flush
   long long* s_qo = reinterpret_cast<long long*>(s_q + (REG ? 2 : 1) * C::QT * FB);  // [QT] their offsets in q0 / q1
 
@@ -371,8 +387,7 @@ __device__ __forceinline__ void process_item(const FusedArgs<T>& A, const Item i
     const int blrel = tau / ntpb;
     const int fbk = tau - blrel * ntpb;
     const int bl = it.bl0 + blrel;
-    const long long o_row = (long long)bl * A.fpad + fbk * FB;  // this tile's channels in the [nbls][fpad] arrays
-    if (MODE == MODE_GRAD && q_count == C::QT) flush_q();       // s_q was last written before the previous barrier
+    if (MODE == MODE_GRAD && q_count == C::QT) flush_q();       // s_q was last written before the previous barrier (QT is even: a folded tile's two rows fit)
 
 
     // ---- issue everything the tile needs: per-channel operands first (threads < FB), then the tile
@@ -381,17 +396,23 @@ __device__ __forceinline__ void process_item(const FusedArgs<T>& A, const Item i
     g0.x = g0.y = g1.x = g1.y = 0;
     // the per-channel stage (FB threads) moves to the next group of FB threads with every tile, so that over an item
     // all four SIMDs of the CU carry the same share of it
-    const int ch = (tid + FB * (tau % (kThreads / FB))) % kThreads;  // this thread's channel in the per-channel stage
-    if (ch < FB) {
+    const int ch = (tid + CH * (tau % (kThreads / CH))) % kThreads;  // this thread's channel in the per-channel stage
+    // FOLD: threads [FB, 2 FB) take the mirror block, channels nfreqs - (fbk + 1) FB + cp in that block's own order;
+    // cp is the mirror of channel ci = FB - 1 - cp of the tile
+    const bool hi = FOLD && ch >= FB;
+    const int cp = hi ? ch - FB : ch;
+    const int col = hi ? A.nfreqs - (fbk + 1) * FB + cp : fbk * FB + cp;  // channel of the band
+    const long long o_ch = (long long)bl * A.fpad + col;
+    if (ch < CH) {
       if (MODE != MODE_MODEL) {
         // read once per pass: non-temporal, like the tiles of the streaming layout
-        d_r = __builtin_nontemporal_load(A.data_r + o_row + ch);
-        d_i = __builtin_nontemporal_load(A.data_i + o_row + ch);
-        w = __builtin_nontemporal_load(A.wgts + o_row + ch);
+        d_r = __builtin_nontemporal_load(A.data_r + o_ch);
+        d_i = __builtin_nontemporal_load(A.data_i + o_ch);
+        w = __builtin_nontemporal_load(A.wgts + o_ch);
       }
       if (MODE == MODE_LOSS || MODE == MODE_GRAD) {
-        g0 = A.gains[(long long)ant.x * A.fpad + fbk * FB + ch];
-        g1 = A.gains[(long long)ant.y * A.fpad + fbk * FB + ch];
+        g0 = A.gains[(long long)ant.x * A.fpad + col];
+        g1 = A.gains[(long long)ant.y * A.fpad + col];
       }
     }
     // Every load is unconditional and unmasked: a lane-masked load next to a zero fill of the other lanes makes the
@@ -411,7 +432,7 @@ __device__ __forceinline__ void process_item(const FusedArgs<T>& A, const Item i
     }
 
     // ---- forward
-    T2* pv_par = s_pv + (tau & 1) * kWaves * FB;
+    T2* pv_par = s_pv + (tau & 1) * kWaves * CH;
     if (FWD) {
       T2 pv[VEC];
 #pragma unroll
@@ -420,40 +441,57 @@ __device__ __forceinline__ void process_item(const FusedArgs<T>& A, const Item i
       for (int l = 0; l < L; ++l) {
         fma_rows(pv, stage[l], s_c[l * NS + ks]);
       }
-      // rows held by the other lanes of this wave
+      // rows held by the other lanes of this wave (FOLD: those of this thread's parity; lane / LPR is 0 for the even, 1 for the odd rows)
 #pragma unroll
       for (int u = 0; u < VEC; ++u) {
-        pv[u].x = sum_row_lanes<LPR>(pv[u].x);
-        pv[u].y = sum_row_lanes<LPR>(pv[u].y);
+        pv[u].x = sum_row_lanes<LPR, FOLD>(pv[u].x);
+        pv[u].y = sum_row_lanes<LPR, FOLD>(pv[u].y);
       }
-      if (lane < LPR) {
+      if (lane < NP * LPR) {
 #pragma unroll
-        for (int u = 0; u < VEC; ++u) pv_par[wave * FB + f0 + u] = pv[u];
+        for (int u = 0; u < VEC; ++u) pv_par[wave * CH + (lane / LPR) * FB + f0 + u] = pv[u];
       }
     }
     __syncthreads();
 
     // ---- per-channel stage: thread = channel ch
-    if (ch < FB) {
+    if (ch < CH) {
+      const int ci = hi ? FB - 1 - cp : cp;       // the tile's channel this thread's products come from
+      const int gslot = (hi ? FB : 0) + ci;       // where its gbar_v goes
       T vr = 0, vi = 0;
       if (FWD) {
+        if (FOLD) {
+          T orr = 0, oi = 0;
 #pragma unroll
-        for (int wv = 0; wv < kWaves; ++wv) {
-          const T2 p = pv_par[wv * FB + ch];
-          vr += p.x;
-          vi += p.y;
+          for (int wv = 0; wv < kWaves; ++wv) {
+            const T2 e = pv_par[wv * CH + ci];
+            const T2 o = pv_par[wv * CH + FB + ci];
+            vr += e.x;
+            vi += e.y;
+            orr += o.x;
+            oi += o.y;
+          }
+          vr = hi ? vr - orr : vr + orr;
+          vi = hi ? vi - oi : vi + oi;
+        } else {
+#pragma unroll
+          for (int wv = 0; wv < kWaves; ++wv) {
+            const T2 p = pv_par[wv * FB + ch];
+            vr += p.x;
+            vi += p.y;
+          }
         }
       }
       if (MODE == MODE_MODEL) {
-        A.model_r[o_row + ch] = vr;
-        A.model_i[o_row + ch] = vi;
+        A.model_r[o_ch] = vr;
+        A.model_i[o_ch] = vi;
       } else if (MODE == MODE_INIT) {
         // binary weights of calibration.py:875-877: ~np.isclose(w, 0.0) (atol 1e-8)
         const T msk = (fabs(w) <= (T)1e-8) ? (T)0 : (T)1;
         T2 gv;
         gv.x = d_r * msk;
         gv.y = d_i * msk;
-        s_gv[ch] = gv;
+        s_gv[gslot] = gv;
       } else {
         // G = g0 conj(g1)   (calibration.py:1598-1601: grgr + gigi, gigr - grgi)
         const T G_r = g0.x * g1.x + g0.y * g1.y;
@@ -474,23 +512,24 @@ __device__ __forceinline__ void process_item(const FusedArgs<T>& A, const Item i
           T2 gv;
           gv.x = G_r * e_r + G_i * e_i;
           gv.y = G_r * e_i - G_i * e_r;
-          s_gv[ch] = gv;
-          // gbar_G = conj(v) e
+          s_gv[gslot] = gv;
+          // gbar_G = conj(v) e   (FOLD: the mirror block is a row of its own, in its own channel order)
+          const int qs = q_count + (hi ? 1 : 0);
           T2 q;
           q.x = vr * e_r + vi * e_i;
           q.y = vr * e_i - vi * e_r;
-          s_q[q_count * FB + ch] = q;
-          if (ch == 0) s_qo[q_count] = o_row;
+          s_q[qs * FB + cp] = q;
+          if (cp == 0) s_qo[qs] = o_ch;
           if (REG) {
             // the part of e that multiplies alpha: w (real)
             T2 gw;
             gw.x = G_r * w;
             gw.y = -G_i * w;
-            s_gv[FB + ch] = gw;
+            s_gv[CH + gslot] = gw;
             T2 qw;
             qw.x = vr * w;
             qw.y = -vi * w;
-            s_q[(C::QT + q_count) * FB + ch] = qw;
+            s_q[(C::QT + qs) * FB + cp] = qw;
           }
         }
       }
@@ -502,14 +541,26 @@ __device__ __forceinline__ void process_item(const FusedArgs<T>& A, const Item i
 #pragma unroll
       for (int u = 0; u < VEC; ++u) {
         gv0[u] = s_gv[f0 + u];
-        if (REG) gv1[u] = s_gv[FB + f0 + u];
+        if (REG) gv1[u] = s_gv[CH + f0 + u];
+        if (FOLD) {
+          // gbar_v[f] + (-1)^k gbar_v[F-1-f]: every row of this thread has the parity of ks
+          const T sg = (ks & 1) ? (T)-1 : (T)1;
+          const T2 m0 = s_gv[FB + f0 + u];
+          gv0[u].x = fma_(sg, m0.x, gv0[u].x);
+          gv0[u].y = fma_(sg, m0.y, gv0[u].y);
+          if (REG) {
+            const T2 m1 = s_gv[CH + FB + f0 + u];
+            gv1[u].x = fma_(sg, m1.x, gv1[u].x);
+            gv1[u].y = fma_(sg, m1.y, gv1[u].y);
+          }
+        }
       }
 #pragma unroll
       for (int l = 0; l < L; ++l) {
         fma_cols(acc0[l], stage[l], gv0);
         if (REG) fma_cols(acc1[l], stage[l], gv1);
       }
-      if (MODE == MODE_GRAD) ++q_count;
+      if (MODE == MODE_GRAD) q_count += NP;
     }
     // no barrier here: the next tile writes the other parity of s_pv, and s_gv / s_q are rewritten only behind the
     // next tile's first barrier, which no wave reaches before it has finished this tile
@@ -1127,8 +1178,10 @@ constexpr size_t group_lds_bytes() {
 #define CAL_WAVES_EU 4
 #endif
 constexpr int kSmallLoads = 2;  // the narrow instance of fused_basis_kernel: blocks of at most 2 NS vectors
-template <typename T, int MODE, bool REG, int L = kMaxLoads>
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L < kMaxLoads ? (sizeof(T) == 4 ? 8 : 6) : ((sizeof(T) == 4 && !REG) ? CAL_WAVES_EU : 1))))
+// FOLD: every item of the launch reads folded tiles (process_item).  (The narrow instance with the regulariser's second adjoint
+// set and the mirror combinations does not fit the registers of 8 / 6 waves per SIMD without scratch: two fewer.)
+template <typename T, int MODE, bool REG, int L = kMaxLoads, bool FOLD = false>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L < kMaxLoads ? (sizeof(T) == 4 ? 8 : 6) - (FOLD && REG ? 2 : 0) : ((sizeof(T) == 4 && !REG) ? CAL_WAVES_EU : 1))))
 void fused_basis_kernel(const FusedArgs<T> A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int idx = A.item_base + blockIdx.x;
@@ -1142,11 +1195,11 @@ void fused_basis_kernel(const FusedArgs<T> A) {
   if ((MODE == MODE_LOSS || MODE == MODE_GRAD) && (it.role_n & 3) != 0 && A.heads != nullptr) return;
   constexpr int FBM = FbSet<T>::fb_max;
   const int fb = 1 << it.fb_log2;
-  if (fb == FBM) process_item<T, FBM, MODE, REG, L>(A, it, smem, idx, st_own);
-  else if (fb == FBM / 2) process_item<T, FBM / 2, MODE, REG, L>(A, it, smem, idx, st_own);
-  else if (fb == FBM / 4) process_item<T, FBM / 4, MODE, REG, L>(A, it, smem, idx, st_own);
-  else if (fb == FBM / 8) process_item<T, FBM / 8, MODE, REG, L>(A, it, smem, idx, st_own);
-  else process_item<T, FBM / 16, MODE, REG, L>(A, it, smem, idx, st_own);
+  if (fb == FBM) process_item<T, FBM, MODE, REG, L, FOLD>(A, it, smem, idx, st_own);
+  else if (fb == FBM / 2) process_item<T, FBM / 2, MODE, REG, L, FOLD>(A, it, smem, idx, st_own);
+  else if (fb == FBM / 4) process_item<T, FBM / 4, MODE, REG, L, FOLD>(A, it, smem, idx, st_own);
+  else if (fb == FBM / 8) process_item<T, FBM / 8, MODE, REG, L, FOLD>(A, it, smem, idx, st_own);
+  else process_item<T, FBM / 16, MODE, REG, L, FOLD>(A, it, smem, idx, st_own);
 }
 
 template <typename T, int MODE, bool REG>

@@ -53,7 +53,9 @@ enum cal_layout {
 };
 enum cal_kernel_path {
   CAL_PATH_AUTO = 0,    /* dense kernel when the problem is eligible and large enough to fill the chip, else general */
-  CAL_PATH_GENERAL = 1, /* register-direct streaming / group kernels (any dtype, layout, group shape) */
+  CAL_PATH_GENERAL = 1, /* register-direct streaming / group kernels (any dtype, layout, group shape).  STREAM layout: like
+                           CAL_PATH_AUTO it reads only channels [0, nfreqs / 2) of a basis whose blocks are all mirror-symmetric
+                           (cal_basis_foldable) when every fitting group has one baseline and no baseline shares tiles */
   CAL_PATH_DENSE = 2,   /* matrix-core kernel wherever the problem is eligible (SHARED layout, one baseline per fitting
                            group, basis_nvec <= 256, nfreqs > 64); CAL_ERR_UNSUPPORTED when it is not.  fp32: the split-bf16
                            kernel (six v_mfma_f32_32x32x16_bf16 per fp32 product block, four panels of a workgroup on one
@@ -61,8 +63,10 @@ enum cal_kernel_path {
                            product); fp64: v_mfma_f64_16x16x4_f64 */
   CAL_PATH_DENSE_F32 = 3, /* fp32 only: the dense kernel on v_mfma_f32_32x32x2_f32 (one panel per workgroup) that CAL_PATH_DENSE
                             ran before the split-bf16 kernel replaced it; kept for A/B measurements and as the accuracy yardstick */
-  CAL_PATH_DENSE_SPLIT1 = 4 /* fp32 only: the first split-bf16 kernel (two packed operand streams through an LDS ring, coefficient
+  CAL_PATH_DENSE_SPLIT1 = 4, /* fp32 only: the first split-bf16 kernel (two packed operand streams through an LDS ring, coefficient
                             panels in LDS), which CAL_PATH_DENSE ran until the one-image form replaced it; kept for A/B measurements */
+  CAL_PATH_GENERAL_FULL = 5 /* CAL_PATH_GENERAL that always keeps and streams the full band of every basis block: the comparator of
+                               the folded form in tests and A/B measurements */
 };
 
 enum cal_launch_mode {
@@ -169,11 +173,22 @@ typedef struct cal_kernel_timing { /* HIP-event timing of the dominant kernel of
                                           regularised step times its loss-only pass too) */
   int32_t kernel_path;                 /* CAL_PATH_GENERAL or CAL_PATH_DENSE: the family the timed launches belong to */
   int32_t dense_wg_per_cu;             /* dense path: workgroups per CU its LDS footprint allows (2 is what the kernels are tuned for) */
+  int32_t basis_folded;                /* 1: the streaming kernel reads half the band of a mirror-symmetric basis (cal_basis_foldable); the
+                                          byte and flop figures above count what that pass reads and multiplies */
+  int32_t reserved;
 } cal_kernel_timing;
 
 const char* cal_last_error(void);
 const char* cal_version(void);
 int cal_device_count(int* count);
+/* Host only (no device is touched).  Whether the streaming kernel may keep just channels [0, nfreqs / 2) of the basis block
+ * `block` (row-major [nrowblk * nfreqs][nvec], dtype CAL_F32 / CAL_F64): one row block, nfreqs even, nfreqs / 2 a whole number of
+ * the block's channel tiles, and mirror symmetry with alternating sign in the block's own vector order,
+ * A[nfreqs-1-f][k] = (-1)^k A[f][k] -- what modeling.dpss_windows delivers.  CAL_F32: no element may differ from its mirror partner by
+ * more than half a unit in the last place of the block's largest element (the trace of the cast from fp64); CAL_F64: the two
+ * halves agree exactly.  Returns 1 / 0, or a negative cal_status.  max_residual, max_abs (either may be NULL): the largest
+ * |A[nfreqs-1-f][k] - (-1)^k A[f][k]| and the largest |A| of the block (zeros where the shape already rules folding out). */
+int cal_basis_foldable(int dtype, const void* block, int32_t nfreqs, int32_t nvec, int32_t nrowblk, double* max_residual, double* max_abs);
 int cal_device_info(int device, char* name, size_t name_len, int64_t* total_mem_bytes, int32_t* compute_units);
 /* Measured streaming peaks of the device (no reference counterpart; BASELINE.md section 3 asks for the roofline against a
  * stream kernel measured on the box next to the nominal 8 TB/s): a read-only sweep (16-byte non-temporal loads, the

@@ -1,11 +1,17 @@
 #!/usr/bin/env python3
-"""Kernel experiment harness: time the fused basis kernel of several library builds on the same problem, in one
-process per build (the child assigns calamity_amd._lib.LIB_PATH before the library is loaded).  Usage: kbench.py [--config hera350] [--max-bls N] lib1.so lib2.so ..."""
+"""Kernel experiment harness: time the fused basis kernel of several builds on the same seeded problem, alternating
+between them, one fresh process per build and round.  A build is a library (.so: the child of THIS tree assigns
+calamity_amd._lib.LIB_PATH before the library is loaded) or a whole source tree with its library built (a directory: its own
+tools/kbench.py child runs with its own Python package -- for builds whose binding differs from this tree's).  The harness stops
+at the first child that exits non-zero or exceeds --child-timeout: nothing more is started on the device after a failure.
+Usage: kbench.py [--config hera350] [--max-bls N] [--rounds 5] [--kernel-path general_full] build1 build2 ..."""
 import argparse
 import json
 import os
 import subprocess
 import sys
+
+import statistics
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -34,7 +40,10 @@ def child(args):
             import pickle
             pickle.dump((prob, start), open(args.cache, "wb"), protocol=4)
     s = HipFitSolver(dtype=dtype)
-    s.set_problem(prob, layout=args.layout)
+    if args.kernel_path:
+        s.set_problem(prob, layout=args.layout, kernel_path=args.kernel_path)
+    else:
+        s.set_problem(prob, layout=args.layout)
     s.set_params(start["g_r"], start["g_i"], start["c_r"], start["c_i"])
     if args.reg:
         src_r, src_i = (prob.sky_r, prob.sky_i) if prob.sky_r is not None else (0.9 * prob.data_r, 1.1 * prob.data_i)  # (a sharded job carries no sky: any prior will do for timing)
@@ -56,6 +65,8 @@ def child(args):
         s.eval_loss()
     t = s.timing_get()
     out["loss_ms"] = t["total_ms"] / t["launches"]
+    out["basis_folded"] = t.get("basis_folded", 0)
+    out["device_memory_GB"] = s.memory_bytes() / 1e9
     print("KBENCH " + json.dumps(out))
 
 
@@ -72,14 +83,46 @@ if __name__ == "__main__":
     ap.add_argument("--cache", default="/tmp/kbench_problem.pkl")
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--lib", default=None, help="(child) the library build to load")
-    ap.add_argument("libs", nargs="*")
+    ap.add_argument("--rounds", type=int, default=2, help="alternations over the builds")
+    ap.add_argument("--kernel-path", default=None, help="kernel_path of set_problem (e.g. general_full: the unfolded streaming kernel); only builds that know it")
+    ap.add_argument("--child-timeout", type=float, default=300.0, help="seconds one child may take")
+    ap.add_argument("libs", nargs="*", help="builds: .so files, or source trees with a built library; NAME@kernel_path runs a build under that kernel path")
     args = ap.parse_args()
     if args.child:
         child(args)
         sys.exit(0)
-    for rnd in range(2):
-        for lib in args.libs:
-            cmd = [sys.executable, os.path.abspath(__file__), "--child", "--lib", os.path.abspath(lib)] + [a for a in sys.argv[1:] if not a.endswith(".so")]
-            r = subprocess.run(cmd, capture_output=True, text=True)
+    passthrough = []
+    for name in ("config", "dtype", "layout", "cache"):
+        passthrough += ["--" + name, str(getattr(args, name))]
+    passthrough += ["--steps", str(args.steps), "--slices", str(args.slices)]
+    if args.max_bls is not None:
+        passthrough += ["--max-bls", str(args.max_bls)]
+    passthrough += ["--reg"] * args.reg + ["--redundant"] * args.redundant
+    results = {}
+    for rnd in range(args.rounds):
+        for spec in args.libs:
+            build, _, path = spec.partition("@")
+            path = path or args.kernel_path
+            if os.path.isdir(build):  # a tree: its own harness and package
+                cmd = [sys.executable, os.path.join(os.path.abspath(build), "tools", "kbench.py"), "--child"] + passthrough
+                cwd = os.path.abspath(build)
+            else:
+                cmd = [sys.executable, os.path.abspath(__file__), "--child", "--lib", os.path.abspath(build)] + passthrough
+                cwd = ROOT
+            if path:
+                cmd += ["--kernel-path", path]
+            try:
+                r = subprocess.run(cmd, capture_output=True, text=True, cwd=cwd, timeout=args.child_timeout)
+            except subprocess.TimeoutExpired:
+                print(rnd, spec, f"TIMEOUT after {args.child_timeout:.0f} s: stopping", flush=True)
+                sys.exit(124)
             line = [l for l in r.stdout.splitlines() if l.startswith("KBENCH ")]
-            print(rnd, os.path.basename(lib), line[0][7:] if line else ("FAILED " + r.stderr[-400:]), flush=True)
+            if r.returncode != 0 or not line:
+                print(rnd, spec, f"FAILED (exit {r.returncode}): stopping\n" + r.stderr[-800:], flush=True)
+                sys.exit(r.returncode or 1)
+            print(rnd, spec, line[0][7:], flush=True)
+            results.setdefault(spec, []).append(json.loads(line[0][7:]))
+    for spec, rows in results.items():
+        for key in ("step_ms", "grad_ms", "loss_ms"):
+            v = [row[key] for row in rows]
+            print(f"SUMMARY {spec} {key}: median {statistics.median(v):.4f} min {min(v):.4f} max {max(v):.4f} (n={len(v)})", flush=True)
