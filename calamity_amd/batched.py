@@ -263,6 +263,16 @@ class SliceBatchFitter:
     def set_optimizer(self, optimizer, **kw):
         self._each(lambda r, s: s.set_optimizer(optimizer, **kw))
 
+    def set_gain_basis(self, basis):
+        """One gain basis ``[nfreqs, K]`` for every slice (``HipFitSolver.set_gain_basis``; ``None`` detaches it).  The gains are
+        replicated over the workers, so every worker gets the same basis; with several workers a train step then exchanges the
+        projected gain gradients."""
+        self._each(lambda r, s: s.set_gain_basis(basis))
+
+    def get_gain_coeffs(self, which=0):
+        """``(y_r, y_i)``, ``[nt * nants, K]`` (replicated over the workers, like the gains)."""
+        return self.solvers[0].get_gain_coeffs(which)
+
     def timing_enable(self, on):
         self._each(lambda r, s: s.timing_enable(on))
 

@@ -639,6 +639,7 @@ def fit_gains_and_foregrounds(
     sky_model_i=None,
     model_regularization=None,
     graph_args_dict=None,
+    gain_basis=None,
     **opt_kwargs,
 ):
     """Run the optimization loop that fits gains and foreground coefficients -- calibration.py:447-738.
@@ -649,7 +650,14 @@ def fit_gains_and_foregrounds(
     (:702-710); the loop ends when ``step >= 1 and |l_k - l_{k-1}| < tol`` (:712-717); ``freeze_model`` optimises
     gains only and returns ``fg_r, fg_i`` untouched (:598-603, :730-732).  The whole loop runs on the GPU; losses come
     back once at the end instead of once per step (:701).
+
+    Not in the reference: ``gain_basis`` (real ``[Nfreqs, K]``, e.g. ``modeling.gain_dpss_basis``) confines the CORRECTION to the
+    gains to its span, ``g = g_in + B y`` with the coefficients ``y`` (zero at the start) as the optimizer's variables in place of
+    the per-channel gains; everything else -- loss, loop semantics, returns (full gains) -- is unchanged.  Default ``None``: free
+    per-channel gains.
     """
+    if gain_basis is not None:
+        gain_basis = _check_gain_basis(gain_basis, np.asarray(g_r).shape[-1])
     echo(f"Using {str(dtype)} precision.")
     echo(f"{datetime.datetime.now()} Provided the following opt_kwargs")
     for k in opt_kwargs:
@@ -663,6 +671,8 @@ def fit_gains_and_foregrounds(
     w_flat = _flatten(wgts, prob)
     solver.set_data(_flatten(data_r, prob), _flatten(data_i, prob), w_flat)
     solver.set_params(g_r, np.asarray(g_i), coeffs_from_chunks(prob, fg_r), coeffs_from_chunks(prob, fg_i))
+    if gain_basis is not None or solver.gain_nvec:  # (the solver is kept between calls: a basis of an earlier call goes)
+        solver.set_gain_basis(gain_basis)  # g0 = the gains just set, y = 0
     echo(f"{datetime.datetime.now()} Performing gradient descent on {np.prod(g_r.shape)} complex gain parameters...", verbose=verbose)
     if not freeze_model:
         echo(f"Performing gradient descent on total of {prob.ncoeffs} complex foreground parameters", verbose=verbose)
@@ -702,6 +712,18 @@ def fit_gains_and_foregrounds(
 # ------------------------------------------------------------------------------------------------------------------
 # write-back: calibration.py:741-825, :1334-1350
 # ------------------------------------------------------------------------------------------------------------------
+def _check_gain_basis(basis, nfreqs):
+    """A gain basis as the solver takes it: real, finite, ``[nfreqs, K >= 1]`` (ValueError otherwise, before any device work)."""
+    basis = np.asarray(basis)
+    if np.iscomplexobj(basis):
+        raise ValueError("gain_basis must be real")
+    if basis.ndim != 2 or basis.shape[0] != nfreqs or not 1 <= basis.shape[1] <= nfreqs:
+        raise ValueError(f"gain_basis must have shape (Nfreqs = {nfreqs}, 1 <= K <= Nfreqs), got {basis.shape}")
+    if not np.all(np.isfinite(basis)):
+        raise ValueError("gain_basis has non-finite elements")
+    return np.ascontiguousarray(basis, dtype=np.float64)
+
+
 def insert_model_into_uvdata_tensor(uvdata, time, polarization, ants_map, red_grps, model_r, model_i, scale_factor=1.0):
     """Insert ``(Nants, Nants, Nfreqs)`` model cubes back into a UVData object, conjugating pairs stored in reversed
     order and multiplying by ``scale_factor`` -- calibration.py:741-795.  Modifies ``uvdata``."""
@@ -777,6 +799,8 @@ def calibrate_and_model_tensor(
     devices=None,
     layout=None,
     device_split=None,
+    gain_basis=None,
+    gain_max_dly=None,
     **opt_kwargs,
 ):
     """Simultaneous calibration and foreground fitting -- calibration.py:963-1331, same arguments, defaults and
@@ -798,10 +822,22 @@ def calibrate_and_model_tensor(
       between them, every slice is fitted exactly as on one device (bit for bit); "groups": each device takes a share of the
       fitting groups of every slice, with one exchange of the gain gradients per step.  Default: "slices" when the call has at
       least as many batches as devices, else "groups".
+    * ``gain_basis`` / ``gain_max_dly`` (give one, default neither: free per-channel gains): fit the gains in a smooth frequency
+      basis.  ``gain_basis``: real ``[Nfreqs, K]``; ``gain_max_dly``: a delay in ns, the basis is then
+      ``modeling.gain_dpss_basis(freqs, gain_max_dly)``.  Every (polarization, time) slice is fitted as ``g = g_in + B y`` with
+      ``g_in`` the gains it starts from (unity, the ``gains`` object's, or the previous time's with
+      ``init_guesses_from_previous_time_step``): output gains minus input gains lie in span(B).  Works in the loop, in batches and
+      on several devices (``device_split="groups"`` then exchanges the projected gradient, K instead of Nfreqs numbers per antenna).
     * ``layout``: "shared" (default; baselines alias the distinct basis blocks) or "stream" (every baseline owns its tiles).
     * ``parallel_fits`` (default 1): with ``batch_slices=False``, fits that many slices concurrently, each on its own
       solver and HIP stream.
     (Nothing here is steered by environment variables: layout, devices and concurrency are arguments.)"""
+    if gain_basis is not None and gain_max_dly is not None:
+        raise ValueError("give gain_basis or gain_max_dly, not both")
+    if gain_max_dly is not None:
+        gain_basis = modeling.gain_dpss_basis(np.asarray(uvdata.freq_array, dtype=np.float64).ravel(), gain_max_dly)
+    if gain_basis is not None:
+        gain_basis = _check_gain_basis(gain_basis, uvdata.Nfreqs)
     antpairs_data = uvdata.get_antpairs()
     if not include_autos:
         antpairs_data = set([ap for ap in antpairs_data if ap[0] != ap[1]])
@@ -859,7 +895,7 @@ def calibrate_and_model_tensor(
             use_model_snr_weights=use_model_snr_weights, optimizer=optimizer, use_min=use_min, freeze_model=freeze_model, tol=tol,
             maxsteps=maxsteps, n_profile_steps=n_profile_steps, profile_log_dir=profile_log_dir, model_regularization=model_regularization,
             verbose=verbose, max_batch=max_batch, devices=devices, layout=layout, opt_kwargs=opt_kwargs,
-            correct_model=correct_model, correct_resid=correct_resid, device_split=device_split,
+            correct_model=correct_model, correct_resid=correct_resid, device_split=device_split, gain_basis=gain_basis,
         )
         return model, resid, gains, fit_history  # (every slice left _fit_slices_batched in its final state)
     if layout is not None:
@@ -918,7 +954,7 @@ def calibrate_and_model_tensor(
                 corr_inds=corr_inds, optimizer=optimizer, use_min=use_min, freeze_model=freeze_model,
                 notebook_progressbar=notebook_progressbar, verbose=verbose, tol=tol, dtype=dtype, maxsteps=maxsteps,
                 graph_mode=graph_mode, n_profile_steps=n_profile_steps, profile_log_dir=profile_log_dir,
-                sky_model_r=sky_model_r, sky_model_i=sky_model_i, model_regularization=model_regularization, **opt_kwargs,
+                sky_model_r=sky_model_r, sky_model_i=sky_model_i, model_regularization=model_regularization, gain_basis=gain_basis, **opt_kwargs,
             )
             # yield_fg_model_array x 2 + insert_model_into_uvdata_tensor (calibration.py:1271-1292) without the
             # nants x nants cubes: one A c pass for both components, rows written straight back
@@ -1145,7 +1181,7 @@ def _batch_fitter(prob, nt, dtype, layout, devices):
 def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds, ants_map, times, weights, nsamples_in_weights, dtype,
                         skip_threshold, use_model_snr_weights, optimizer, use_min, freeze_model, tol, maxsteps, n_profile_steps,
                         profile_log_dir, model_regularization, verbose, max_batch, devices, layout, opt_kwargs, correct_model=True,
-                        correct_resid=False, device_split=None):
+                        correct_resid=False, device_split=None, gain_basis=None):
     """The pol x time loop of calibration.py:1160-1331 with the fits of all unskipped slices issued as batches: per slice
     exactly the host-side steps of the loop body (skip test :1173-1177, rms scale :1178-1182, tensorize :1184-1233, write-back
     :1271-1300, post-hoc renormalisation :1311-1319, residual and calibration state of the outputs :1322-1331), the gradient
@@ -1242,6 +1278,7 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
             w_all = w_new.astype(dtype)
             fitter.set_data(d_r, d_i, w_all)
         fitter.set_params(arrs["g_r"], arrs["g_i"], c_r, c_i)
+        fitter.set_gain_basis(gain_basis)  # (the fitter is kept between calls: None detaches an earlier call's) g0 = the gains just set
         if model_regularization == "sum":
             # priors of calibration.py:619-625, one pair per slice (accumulated in float64 on the host)
             nb = prob.nbls
@@ -1704,6 +1741,8 @@ def fitting_argparser():
     sp.add_argument("--nsamples_in_weights", default=False, action="store_true", help="multiply the weights by nsamples")
     sp.add_argument("--use_model_snr_weights", default=False, action="store_true", help="weight samples by the model's signal to noise")
     sp.add_argument("--use_autocorrs_in_weights", default=False, action="store_true", help="inverse-variance weights from the autocorrelations")
+    sp.add_argument("--gain_max_dly", type=float, default=None,
+                    help="fit the gains in a DPSS basis that is smooth up to this delay [ns]; default: free per-channel gains")
     return ap
 
 

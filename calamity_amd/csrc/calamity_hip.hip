@@ -23,6 +23,7 @@
 #include "split2_kernels.hpp"
 #include "dense64_kernels.hpp"
 #include "multi_mfma_kernels.hpp"
+#include "gain_basis_kernels.hpp"
 #include <cstdlib>
 #include <dlfcn.h>
 #include <type_traits>
@@ -206,6 +207,9 @@ struct cal_solver {
   virtual int set_launch_mode(int mode) = 0;
   virtual int set_exchange_hook(cal_exchange_fn fn, void* ctx, int rank, int nranks) = 0;
   virtual int comm_size(int* nranks_seen) = 0;
+  virtual int set_gain_basis(const void* basis, int nvec) = 0;
+  virtual int get_gain_coeffs(int which, void* y_r, void* y_i) = 0;
+  virtual int eval_gain_coeff_grads(double* loss, void* gy_r, void* gy_i) = 0;
 };
 
 template <typename T>
@@ -274,9 +278,10 @@ struct SolverT final : cal_solver {
   struct GraphKey {
     int optimizer, freeze, reg, losses_cap, st_par, tail, nsteps;
     const void *gains, *snap, *losses;
+    const void *y, *ysnap;  // gain basis: the coefficient arrays the captured update and gain_expand_kernel work on (null without one)
     bool operator==(const GraphKey& o) const {
       return optimizer == o.optimizer && freeze == o.freeze && reg == o.reg && losses_cap == o.losses_cap && st_par == o.st_par && tail == o.tail &&
-             nsteps == o.nsteps && gains == o.gains && snap == o.snap && losses == o.losses;
+             nsteps == o.nsteps && gains == o.gains && snap == o.snap && losses == o.losses && y == o.y && ysnap == o.ysnap;
     }
   } graph_key{};
   DevBuf agree_buf;
@@ -311,6 +316,12 @@ struct SolverT final : cal_solver {
   std::vector<int> lamb_cvar_slice, lamb_cvar_id;
   int lamb_nv = 0;
   int reg = CAL_REG_NONE;
+  // gain basis (set_gain_basis; gain_basis_kernels.hpp): gains = gb_g0 + B y.  The optimizer's gain variables are then y ([nants][gb_kpad]
+  // (re, im), like the gains with row length gb_kpad), its gradient the projected planes gb_proj (p0 | p1 | p2, contiguous for the all-reduce)
+  int gb_nvec = 0, gb_kpad = 0;
+  DevBuf gb_B, gb_Bt;                          // [fpad][gb_kpad] and [gb_kpad][fpad], zero-padded
+  DevBuf gb_g0, gb_y, gb_ym, gb_yv, gb_ysnap, gb_proj;
+  bool gb_on() const { return gb_nvec > 0; }
   // timing
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
@@ -487,6 +498,7 @@ struct SolverT final : cal_solver {
     HIP_TRY(hipSetDevice(device));
     has_problem = has_data = has_gains = has_coef = false;
     drop_graph();
+    release_gain_basis();  // a new problem fits per channel until a basis is set again
     if (!d || d->nants <= 0 || d->nfreqs <= 0 || d->ngrps <= 0 || d->nbls <= 0 || d->nbasis <= 0)
       return fail(CAL_ERR_INVALID, "set_problem: non-positive dimension");
     if (!d->basis_offset || !d->basis_nvec || !d->basis_nrowblk || !d->basis_data || !d->grp_basis || !d->grp_bl_start ||
@@ -1405,7 +1417,10 @@ struct SolverT final : cal_solver {
     return CAL_OK;
   }
   // host [rows][nfreqs] -> device [rows][fpad] * stride + off
-  int upload_rows(const void* src, T* dst, long long rows, int stride, int off) {
+  int upload_rows(const void* src, T* dst, long long rows, int stride, int off) { return upload_rows(src, dst, rows, stride, off, nfreqs, fpad); }
+  int download_rows(void* dst, const T* src, long long rows, int stride, int off) { return download_rows(dst, src, rows, stride, off, nfreqs, fpad); }
+  // (rows of nfreqs elements padded to fpad: the gains and per-baseline arrays; the gain-basis coefficients bring their own two lengths)
+  int upload_rows(const void* src, T* dst, long long rows, int stride, int off, int nfreqs, int fpad) {
     const size_t bytes = (size_t)rows * nfreqs * sizeof(T);
     if (stride == 1 && fpad == nfreqs) {
       HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream));
@@ -1420,7 +1435,7 @@ struct SolverT final : cal_solver {
     HIP_TRY(hipStreamSynchronize(stream));
     return CAL_OK;
   }
-  int download_rows(void* dst, const T* src, long long rows, int stride, int off) {
+  int download_rows(void* dst, const T* src, long long rows, int stride, int off, int nfreqs, int fpad) {
     const size_t bytes = (size_t)rows * nfreqs * sizeof(T);
     if (stride == 1 && fpad == nfreqs) {
       HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream));
@@ -1480,6 +1495,9 @@ struct SolverT final : cal_solver {
     if (!d) return fail(CAL_ERR_INVALID, "set_optimizer: null");
     if (d->optimizer < CAL_OPT_ADAM || d->optimizer > CAL_OPT_LAMB)
       return fail(CAL_ERR_INVALID, "set_optimizer: unknown optimizer id %d", d->optimizer);
+    if (d->optimizer == CAL_OPT_LAMB && gb_on())
+      return fail(CAL_ERR_UNSUPPORTED, "set_optimizer: LAMB is not supported while a gain basis is set (its per-variable norms are defined over the "
+                  "per-channel gains); detach the basis (nvec = 0) or choose another optimizer");
     if (d->optimizer == CAL_OPT_LAMB && !lamb_ok)
       return fail(CAL_ERR_UNSUPPORTED, "set_optimizer: LAMB takes one trust ratio per variable; the groups of a variable (cal_problem_desc::grp_var) must be "
                   "contiguous inside a time slice");
@@ -1492,11 +1510,16 @@ struct SolverT final : cal_solver {
                          (long long)(gains_v.bytes / sizeof(T)), (T)d->initial_accumulator_value);
       hipLaunchKernelGGL(fill_kernel<T>, dim3(grid_for((long long)(coef_v.bytes / sizeof(T)))), dim3(256), 0, stream, coef_v.as<T>(),
                          (long long)(coef_v.bytes / sizeof(T)), (T)d->initial_accumulator_value);
+      if (gb_on())
+        hipLaunchKernelGGL(fill_kernel<T>, dim3(grid_for((long long)(gb_yv.bytes / sizeof(T)))), dim3(256), 0, stream, gb_yv.as<T>(),
+                           (long long)(gb_yv.bytes / sizeof(T)), (T)d->initial_accumulator_value);
       HIP_TRY(hipGetLastError());
     } else {
       HIP_TRY(hipMemsetAsync(gains_v.p, 0, gains_v.bytes, stream));
       HIP_TRY(hipMemsetAsync(coef_v.p, 0, coef_v.bytes, stream));
+      if (gb_on()) HIP_TRY(hipMemsetAsync(gb_yv.p, 0, gb_yv.bytes, stream));
     }
+    if (gb_on()) HIP_TRY(hipMemsetAsync(gb_ym.p, 0, gb_ym.bytes, stream));
     drop_graph();
     for (int t = 0; t < nslices; ++t) reset_loop_state(h_state[t]);  // a new fit begins
     has_opt = true;
@@ -1509,6 +1532,7 @@ struct SolverT final : cal_solver {
     if (!has_problem) return fail(CAL_ERR_STATE, "set_params before set_problem");
     if (g_r) CAL_TRY(upload_rows(g_r, gains.as<T>(), nants, 2, 0));
     if (g_i) CAL_TRY(upload_rows(g_i, gains.as<T>(), nants, 2, 1));
+    if ((g_r || g_i) && gb_on()) CAL_TRY(rebase_gain_basis());  // the fit now starts from these gains: g0 := gains, y := 0
     if (c_r) HIP_TRY(copy_sync(coef.as<T>(), c_r, (size_t)ncoef * sizeof(T), hipMemcpyHostToDevice));
     if (c_i) HIP_TRY(copy_sync(coef.as<T>() + ncoef, c_i, (size_t)ncoef * sizeof(T), hipMemcpyHostToDevice));
     if (g_r && g_i) has_gains = true;
@@ -1523,6 +1547,11 @@ struct SolverT final : cal_solver {
     const T* c = coef.as<T>();
     if (which == 1) {
       if (!gains_snap.p) return fail(CAL_ERR_STATE, "get_params(which=1): no use_min snapshot was taken");
+      if (gb_on()) {
+        // the snapshot of a basis fit is y's: the gains it stands for are expanded into gains_snap (which no kernel writes while a basis is set)
+        if (!gb_ysnap.p) return fail(CAL_ERR_STATE, "get_params(which=1): no use_min snapshot was taken since the gain basis was set");
+        CAL_TRY(enqueue_expand(gb_ysnap.as<T2>(), gains_snap.as<T2>()));
+      }
       g = gains_snap.as<T>();
       c = coef_snap.as<T>();
     } else if (which != 0) {
@@ -1540,6 +1569,7 @@ struct SolverT final : cal_solver {
                   int64_t* t) override {
     HIP_TRY(hipSetDevice(device));
     if (!has_problem) return fail(CAL_ERR_STATE, "get_moments before set_problem");
+    if (gb_on()) return fail(CAL_ERR_UNSUPPORTED, "get_moments: checkpoint / resume of a fit with a gain basis is not supported");
     HIP_TRY(hipStreamSynchronize(stream));
     if (t && nslices > 1) {
       // every slice counts its own updates (slices stop on their own and then freeze): ONE t only describes a solver whose slices agree
@@ -1565,6 +1595,7 @@ struct SolverT final : cal_solver {
                   const void* cv_r, const void* cv_i, int64_t t) override {
     HIP_TRY(hipSetDevice(device));
     if (!has_problem) return fail(CAL_ERR_STATE, "set_moments before set_problem");
+    if (gb_on()) return fail(CAL_ERR_UNSUPPORTED, "set_moments: checkpoint / resume of a fit with a gain basis is not supported");
     if (t < 0) return fail(CAL_ERR_INVALID, "set_moments: negative iteration count");
     if (gm_r) CAL_TRY(upload_rows(gm_r, gains_m.as<T>(), nants, 2, 0));
     if (gm_i) CAL_TRY(upload_rows(gm_i, gains_m.as<T>(), nants, 2, 1));
@@ -1712,7 +1743,9 @@ struct SolverT final : cal_solver {
 
   // enqueue: loss (+ gradients) of the current parameters; leaves loss in state, final gradients in comm[0] / grad_c0()
   // one_launch_tail: the caller follows up with step_tail_kernel (enqueue_update), which does everything behind the fused pass
-  int enqueue_pass(bool grads, bool apply_update, int losses_cap, bool one_launch_tail = false) {
+  // project: a gain basis is set and the pass serves y (a train step, cal_solver_eval_gain_coeff_grads): the gain-gradient planes are
+  // projected on the basis BEFORE the exchange, which then carries planes x 2 nants gb_kpad reals instead of planes x 2 nants fpad
+  int enqueue_pass(bool grads, bool apply_update, int losses_cap, bool one_launch_tail = false, bool project = false) {
     const bool R = reg == CAL_REG_SUM;
     FusedArgs<T> a = fused_args();
     DevState* st = st_cur();
@@ -1816,13 +1849,21 @@ struct SolverT final : cal_solver {
       hipLaunchKernelGGL((gain_grad_kernel<T, false>), dim3(nslices), dim3(256), 0, stream, q0.as<T2>(), q1.as<T2>(), gains.as<T2>(),
                          ant_ptr.as<int>(), ant_ent.as<int2>(), r0, r1, r2, 0, fpad, part.as<double>(), n_parts, scal.as<double>(), st, sm);
     }
+    const bool proj = project && grads;
+    if (proj) {
+      hipLaunchKernelGGL((gain_project_kernel<T>), dim3(nants, Rk ? 3 : 1), dim3(256), 0, stream, r0, gb_B.as<T>(), gb_proj.as<T>(), nants, fpad, gb_kpad,
+                         st, sm);
+      HIP_TRY(hipGetLastError());
+    }
+    const size_t xn = proj ? (size_t)nants * gb_kpad : gn;  // complex elements per plane of the gain gradient from here on
+    T2* x0 = proj ? gb_proj.as<T2>() : r0;
     if (comm_on()) {
       // the one exchange step of the sharded fit: sum gain-gradient parts and loss scalars over ranks
       // (issued for a 1-rank communicator too, so the path can be exercised on a single GPU)
       const int gdt = sizeof(T) == 4 ? CAL_XCHG_F32 : CAL_XCHG_F64;
       if (nccl) NCCL_TRY(ncclGroupStart());
       int rc = CAL_OK;
-      if (grads) rc = all_reduce(r0, (size_t)(Rk ? 3 : 1) * gn * 2, gdt, CAL_XCHG_SUM);
+      if (grads) rc = all_reduce(x0, (size_t)(Rk ? 3 : 1) * xn * 2, gdt, CAL_XCHG_SUM);
       if (rc == CAL_OK) rc = all_reduce(scal.p, 4 * (size_t)nslices, CAL_XCHG_F64, CAL_XCHG_SUM);
       if (nccl) NCCL_TRY(ncclGroupEnd());
       CAL_TRY(rc);
@@ -1831,7 +1872,8 @@ struct SolverT final : cal_solver {
       hipLaunchKernelGGL(finalize_kernel, dim3((nslices + 63) / 64), dim3(64), 0, stream, st, scal.as<double>(), losses.as<double>(), losses_cap,
                          apply_update ? 1 : 0, nslices);
     if (grads && Rk) {
-      hipLaunchKernelGGL(combine_gain_kernel<T>, dim3((int)((gn + 255) / 256)), dim3(256), 0, stream, r0, r1, r2, (int)gn, st, sm, fpad);
+      hipLaunchKernelGGL(combine_gain_kernel<T>, dim3((int)((xn + 255) / 256)), dim3(256), 0, stream, x0, x0 + xn, x0 + 2 * xn, (int)xn, st, sm,
+                         proj ? gb_kpad : fpad);
       hipLaunchKernelGGL(combine_coeff_kernel<T>, dim3((ncoef + 255) / 256), dim3(256), 0, stream, grad_c0(), grad_c0() + ncoef,
                          grad_c1(), grad_c1() + ncoef, ncoef, st, sm);
     }
@@ -1851,7 +1893,8 @@ struct SolverT final : cal_solver {
   // exchange sits between the reduction and the update), general kernels, and not when every kernel is asked to be its own launch
   // (... nor with the regulariser over baselines that share tiles: alpha is needed between that path's two passes)
   bool one_launch_tail() const {
-    return !comm_on() && !mf_ok && tail_fits_one_launch() && launch_mode != CAL_LAUNCH_KERNELS && !(reg == CAL_REG_SUM && reg_prepass);
+    // (... nor with a gain basis: the projection sits between the antenna reduction and the update, which step_tail_kernel fuses)
+    return !comm_on() && !mf_ok && !gb_on() && tail_fits_one_launch() && launch_mode != CAL_LAUNCH_KERNELS && !(reg == CAL_REG_SUM && reg_prepass);
   }
   void launch_tail(const TailArgs<T>& a, unsigned grid, bool R) {
     if (R)
@@ -1904,6 +1947,11 @@ struct SolverT final : cal_solver {
     const long long gn = 2LL * nants * fpad;
     T* gsnap = gains_snap.p ? gains_snap.as<T>() : gains.as<T>();
     T* csnap = coef_snap.p ? coef_snap.as<T>() : coef.as<T>();
+    // with a gain basis the gain set is y: the same kernels on flat arrays of row length gb_kpad, then the gains are rebuilt from y
+    if (gb_on()) {
+      CAL_TRY(enqueue_update_y(freeze_model, losses_cap));
+      return enqueue_expand(gb_y.as<T2>(), gains.as<T2>());
+    }
     const AdamSet<T> ga{gains.as<T>(), comm.as<T>(), gains_m.as<T>(), gains_v.as<T>(), gsnap, gn};
     const AdamSet<T> ca{coef.as<T>(), grad_c0(), coef_m.as<T>(), coef_v.as<T>(), csnap, freeze_model ? 0LL : 2LL * ncoef};
     const int nblk_a = (int)((ga.n + 255) / 256), nblk_b = (int)((ca.n + 255) / 256);
@@ -1955,6 +2003,127 @@ struct SolverT final : cal_solver {
     return CAL_OK;
   }
 
+  // the update of a basis fit: enqueue_update's common path and its adam2_kernel path with the y arrays as the gain set (LAMB is refused
+  // while a basis is set: set_optimizer, set_gain_basis)
+  int enqueue_update_y(bool freeze_model, int losses_cap) {
+    DevState* st = st_cur();
+    T* ysnap = gb_ysnap.p ? gb_ysnap.as<T>() : gb_y.as<T>();
+    T* csnap = coef_snap.p ? coef_snap.as<T>() : coef.as<T>();
+    const AdamSet<T> ga{gb_y.as<T>(), gb_proj.as<T>(), gb_ym.as<T>(), gb_yv.as<T>(), ysnap, 2LL * nants * gb_kpad};
+    const AdamSet<T> ca{coef.as<T>(), grad_c0(), coef_m.as<T>(), coef_v.as<T>(), csnap, freeze_model ? 0LL : 2LL * ncoef};
+    const bool Rk = reg == CAL_REG_SUM && !mf_ok;
+    if (!Rk && tail_fits_one_launch()) {
+      PartialSum<T> ps{};
+      if (!gc_direct && !mf_ok && !freeze_model)
+        ps = PartialSum<T>{gcp0.as<T>(), gcp0.as<T>() + gcp_len, coef_grp.as<int>(), grp_coff.as<int>(), grp_item_ptr.as<int>(),
+                           item_goff.as<int>(), ncoef};
+      const int nblk = (int)((ga.n + 255) / 256) + (int)((ca.n + 255) / 256);
+      const unsigned nb = (unsigned)std::max(1, std::min(nblk, 16384));
+      hipLaunchKernelGGL((step_update_kernel<T>), dim3(nb), dim3(256), (size_t)nslices * sizeof(SliceStep<T>), stream, ga, ca, ps, st, st_nxt(),
+                         scal.as<double>(), losses.as<double>(), losses_cap, smap(mf_ok), gb_kpad, ncoef);
+      st_par ^= 1;
+      HIP_TRY(hipGetLastError());
+      return CAL_OK;
+    }
+    constexpr long long per = 256LL * kAdamVec<T>;  // elements per block
+    const int va = (int)((ga.n + per - 1) / per), vb = (int)((ca.n + per - 1) / per);
+    hipLaunchKernelGGL((adam2_kernel<T>), dim3((unsigned)(va + vb)), dim3(256), 0, stream, ga, ca, va, st, smap(mf_ok), gb_kpad, ncoef);
+    HIP_TRY(hipGetLastError());
+    return CAL_OK;
+  }
+  // dst = g0 + B src (src: y or its use_min snapshot)
+  int enqueue_expand(const T2* src, T2* dst) {
+    constexpr int per = 256 * (16 / (int)sizeof(T));  // channels per block
+    hipLaunchKernelGGL((gain_expand_kernel<T>), dim3((fpad + per - 1) / per, nants), dim3(256), 0, stream, gb_g0.as<T2>(), gb_Bt.as<T>(), src, dst, fpad,
+                       gb_kpad);
+    HIP_TRY(hipGetLastError());
+    return CAL_OK;
+  }
+  void release_gain_basis() {
+    gb_nvec = gb_kpad = 0;
+    for (DevBuf* b : {&gb_B, &gb_Bt, &gb_g0, &gb_y, &gb_ym, &gb_yv, &gb_ysnap, &gb_proj}) b->release();
+  }
+  // the fit starts from the gains the solver holds now: g0 := gains, y := 0 (and its snapshot with it)
+  int rebase_gain_basis() {
+    HIP_TRY(hipMemcpyAsync(gb_g0.p, gains.p, gains.bytes, hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipMemsetAsync(gb_y.p, 0, gb_y.bytes, stream));
+    if (gb_ysnap.p) HIP_TRY(hipMemsetAsync(gb_ysnap.p, 0, gb_ysnap.bytes, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return CAL_OK;
+  }
+  int set_gain_basis(const void* basis, int nvec) override {
+    HIP_TRY(hipSetDevice(device));
+    if (!has_problem) return fail(CAL_ERR_STATE, "set_gain_basis before set_problem");
+    if (nvec < 0 || nvec > nfreqs) return fail(CAL_ERR_INVALID, "set_gain_basis: nvec = %d; a basis has 1 .. nfreqs = %d vectors (0 detaches it)", nvec, nfreqs);
+    if (nvec > 0 && !basis) return fail(CAL_ERR_INVALID, "set_gain_basis: null basis");
+    if (nvec == 0 && !gb_on()) return CAL_OK;  // nothing to detach: the per-channel fit goes on as it stands, moments included
+    if (nvec > 0 && has_opt && opt.optimizer == CAL_OPT_LAMB)
+      return fail(CAL_ERR_UNSUPPORTED, "set_gain_basis: LAMB is not supported with a gain basis (its per-variable norms are defined over the per-channel gains)");
+    HIP_TRY(hipStreamSynchronize(stream));
+    drop_graph();
+    if (nvec == 0) {
+      // back to the per-channel fit, from the gains as they stand
+      release_gain_basis();
+    } else {
+      const T* b = static_cast<const T*>(basis);
+      for (long long i = 0; i < (long long)nfreqs * nvec; ++i)
+        if (!std::isfinite((double)b[i])) return fail(CAL_ERR_INVALID, "set_gain_basis: the basis has a non-finite element");
+      const int kpad = (nvec + kGainBasisPad - 1) / kGainBasisPad * kGainBasisPad;
+      std::vector<T> hB((size_t)fpad * kpad, (T)0), hBt((size_t)kpad * fpad, (T)0);
+      for (int f = 0; f < nfreqs; ++f)
+        for (int k = 0; k < nvec; ++k) hB[(size_t)f * kpad + k] = hBt[(size_t)k * fpad + f] = b[(size_t)f * nvec + k];
+      release_gain_basis();
+      const size_t ybytes = (size_t)nants * kpad * sizeof(T2);
+      CAL_TRY(gb_B.alloc(hB.size() * sizeof(T), false));
+      CAL_TRY(gb_Bt.alloc(hBt.size() * sizeof(T), false));
+      HIP_TRY(copy_sync(gb_B.p, hB.data(), hB.size() * sizeof(T), hipMemcpyHostToDevice));
+      HIP_TRY(copy_sync(gb_Bt.p, hBt.data(), hBt.size() * sizeof(T), hipMemcpyHostToDevice));
+      CAL_TRY(gb_g0.alloc(gains.bytes, false));
+      CAL_TRY(gb_y.alloc(ybytes));
+      CAL_TRY(gb_ym.alloc(ybytes));
+      CAL_TRY(gb_yv.alloc(ybytes));
+      CAL_TRY(gb_proj.alloc(3 * ybytes));
+      gb_nvec = nvec;
+      gb_kpad = kpad;
+      CAL_TRY(rebase_gain_basis());
+    }
+    if (has_opt) {
+      // moments and iteration count start over, exactly as set_optimizer leaves them (of y, of the gains, of the coefficients)
+      const cal_optimizer_desc same = opt;
+      CAL_TRY(set_optimizer(&same));
+    }
+    return CAL_OK;
+  }
+  int get_gain_coeffs(int which, void* y_r, void* y_i) override {
+    HIP_TRY(hipSetDevice(device));
+    if (!gb_on()) return fail(CAL_ERR_STATE, "get_gain_coeffs: no gain basis is set (cal_solver_set_gain_basis)");
+    if (which != 0 && which != 1) return fail(CAL_ERR_INVALID, "get_gain_coeffs: which must be 0 or 1");
+    if (which == 1 && !gb_ysnap.p) return fail(CAL_ERR_STATE, "get_gain_coeffs(which=1): no use_min snapshot was taken since the gain basis was set");
+    const T* y = which == 1 ? gb_ysnap.as<T>() : gb_y.as<T>();
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (y_r) CAL_TRY(download_rows(y_r, y, nants, 2, 0, gb_nvec, gb_kpad));
+    if (y_i) CAL_TRY(download_rows(y_i, y, nants, 2, 1, gb_nvec, gb_kpad));
+    return CAL_OK;
+  }
+  int eval_gain_coeff_grads(double* loss, void* gy_r, void* gy_i) override {
+    HIP_TRY(hipSetDevice(device));
+    CAL_TRY(ready());
+    if (!gb_on()) return fail(CAL_ERR_STATE, "eval_gain_coeff_grads: no gain basis is set (cal_solver_set_gain_basis)");
+    begin_pass_state();
+    CAL_TRY(push_state());
+    CAL_TRY(enqueue_pass(true, false, 0, false, true));
+    CAL_TRY(pull_state());
+    if (timing) CAL_TRY(collect_timing());
+    if (loss) {
+      double tot = 0;
+      for (int t = 0; t < nslices; ++t) tot += h_state[t].loss;
+      *loss = tot;
+    }
+    if (gy_r) CAL_TRY(download_rows(gy_r, gb_proj.as<T>(), nants, 2, 0, gb_nvec, gb_kpad));
+    if (gy_i) CAL_TRY(download_rows(gy_i, gb_proj.as<T>(), nants, 2, 1, gb_nvec, gb_kpad));
+    return CAL_OK;
+  }
+
   void drop_graph() {
     if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
     graph_exec = nullptr;
@@ -1968,7 +2137,7 @@ struct SolverT final : cal_solver {
   // pass(es), gain_grad_kernel, finalize_kernel, the update): a host whose cores are busy elsewhere then pays ONE launch per `nsteps` steps
   // instead of four or five per step (measured on shared boxes: 2.4-3.2 ms per step of a 0.6-ms kernel while the host was contended).
   int replay_steps(bool freeze_model, int cap, bool tail, int nsteps) {
-    const GraphKey key{opt.optimizer, freeze_model ? 1 : 0, reg, cap, st_par, tail ? 1 : 0, nsteps, gains.p, gains_snap.p, losses.p};
+    const GraphKey key{opt.optimizer, freeze_model ? 1 : 0, reg, cap, st_par, tail ? 1 : 0, nsteps, gains.p, gains_snap.p, losses.p, gb_y.p, gb_ysnap.p};
     if (!graph_exec || !(key == graph_key)) {
       drop_graph();
       hipGraph_t graph = nullptr;
@@ -1986,7 +2155,7 @@ struct SolverT final : cal_solver {
       HIP_TRY(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
       int rc = CAL_OK;
       for (int k = 0; k < nsteps && rc == CAL_OK; ++k) {
-        rc = enqueue_pass(true, true, cap, tail);
+        rc = enqueue_pass(true, true, cap, tail, gb_on());
         if (rc == CAL_OK) rc = tail ? enqueue_tail(freeze_model, cap) : enqueue_update(freeze_model, cap);
       }
       const hipError_t e = hipStreamEndCapture(stream, &graph);
@@ -2103,6 +2272,7 @@ struct SolverT final : cal_solver {
       CAL_TRY(gains_snap.alloc(gains.bytes));
       CAL_TRY(coef_snap.alloc(coef.bytes));
     }
+    if (r->use_min && gb_on() && !gb_ysnap.p) CAL_TRY(gb_ysnap.alloc(gb_y.bytes));
     const size_t lbytes = (size_t)nslices * r->nsteps * sizeof(double);
     if (r->record && losses.bytes < lbytes) CAL_TRY(losses.alloc(lbytes));
     if (!losses.p) CAL_TRY(losses.alloc((size_t)nslices * sizeof(double)));
@@ -2150,7 +2320,7 @@ struct SolverT final : cal_solver {
         for (; gsteps >= 2 && s + gsteps <= n; s += gsteps) CAL_TRY(replay_steps(r->freeze_model != 0, cap, tail1, gsteps));
       }
       for (; s < n; ++s) {
-        CAL_TRY(enqueue_pass(true, true, cap, tail1));
+        CAL_TRY(enqueue_pass(true, true, cap, tail1, gb_on()));
         if (tail1) CAL_TRY(enqueue_tail(r->freeze_model != 0, cap)); else CAL_TRY(enqueue_update(r->freeze_model != 0, cap));
       }
       issued += n;
@@ -2273,7 +2443,7 @@ struct SolverT final : cal_solver {
                            &data_r, &data_i, &wgts, &gains, &gains_alt, &gains_m, &gains_v, &gains_snap, &coef, &coef_m, &coef_v, &coef_snap,
                            &q0, &q1, &comm, &scal, &gcp0, &gcp1, &gc0, &gc1, &part, &state, &losses, &scratch, &model_buf,
                            &mf_ops, &mf_panels, &mf_map, &members, &heads, &lamb_vars, &lamb_cvar_ptr, &lamb_partial, &lamb_ratio, &lamb_glob, &lamb_slot, &slice_coff, &slice_ipart_ptr, &slice_ipart_idx,
-                           &slice_ppart_ptr, &slice_ppart_idx, &slice_cblk};
+                           &slice_ppart_ptr, &slice_ppart_idx, &slice_cblk, &gb_B, &gb_Bt, &gb_g0, &gb_y, &gb_ym, &gb_yv, &gb_ysnap, &gb_proj};
     int64_t n = 0;
     for (auto* d : all) n += (int64_t)d->bytes;
     *b = n;
@@ -2579,5 +2749,8 @@ int cal_comm_unique_id(void* id_out) {
 int cal_solver_comm_init(cal_solver* s, const void* id, int rank, int nranks) { NEED(s); return s->comm_init(id, rank, nranks); }
 int cal_solver_set_exchange_hook(cal_solver* s, cal_exchange_fn fn, void* ctx, int rank, int nranks) { NEED(s); return s->set_exchange_hook(fn, ctx, rank, nranks); }
 int cal_solver_comm_size(cal_solver* s, int* nranks_seen) { NEED(s); return s->comm_size(nranks_seen); }
+int cal_solver_set_gain_basis(cal_solver* s, const void* basis, int32_t nvec) { NEED(s); return s->set_gain_basis(basis, nvec); }
+int cal_solver_get_gain_coeffs(cal_solver* s, int which, void* y_r, void* y_i) { NEED(s); return s->get_gain_coeffs(which, y_r, y_i); }
+int cal_solver_eval_gain_coeff_grads(cal_solver* s, double* loss, void* gy_r, void* gy_i) { NEED(s); return s->eval_gain_coeff_grads(loss, gy_r, gy_i); }
 
 }  // extern "C"

@@ -7,7 +7,8 @@ just be slower, it would read ring slots before they have landed.  So: no scratc
 contains `fused_dense`; and two waves per SIMD where the kernels are written for two.
 `fused_multi_mfma_kernel<float>` sits at 245 of the 256 registers two waves per SIMD leave it (the double instance has a
 CU to itself): no scratch and no spilled VGPRs there either (a few SGPR spills into lanes of a VGPR are tolerated: they sit outside its job loop).
-`fused_basis_kernel`: no scratch in any instance; four waves per SIMD in the fp32 gradient instances with full and with folded tiles."""
+`fused_basis_kernel`: no scratch in any instance; four waves per SIMD in the fp32 gradient instances with full and with folded tiles.
+`gain_project_kernel`, `gain_expand_kernel` (gain_basis_kernels.hpp): no scratch, no spilled VGPRs."""
 import re
 import sys
 
@@ -36,6 +37,12 @@ for line in sys.stdin:
             if re.search(r"fused_basis_kernelIfLi1ELb0ELi7ELb[01]E", cur) and int(m.group(2)) < 4:
                 bad.append(f"{cur}: occupancy {m.group(2)} waves/SIMD (< 4)")
         elif m and int(m.group(2)) != 0:
+            bad.append(f"{cur}: {m.group(1)} = {m.group(2)}")
+        continue
+    if cur is not None and ("gain_project_kernel" in cur or "gain_expand_kernel" in cur):
+        # the two kernels around the update of a gain-basis fit keep their accumulators in registers: no scratch
+        m = re.search(r"remark:\s+(ScratchSize \[bytes/lane\]|VGPRs Spill): (\d+)", line)
+        if m and int(m.group(2)) != 0:
             bad.append(f"{cur}: {m.group(1)} = {m.group(2)}")
         continue
     if cur is None or "fused_dense" not in cur:

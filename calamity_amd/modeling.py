@@ -218,6 +218,18 @@ def _dpss_block(delay_ns, freqs, eigenval_cutoff, operator_cache=None):
     return operator_cache[key]
 
 
+def gain_dpss_basis(freqs, max_dly_ns, eigenval_cutoff=1e-10):
+    """The frequency basis of gains that are smooth up to a delay of ``max_dly_ns`` nanoseconds: the real DPSS block
+    ``dpss_operator(freqs, [0.0], [max_dly_ns * 1e-9], [eigenval_cutoff])`` of that half width centred on zero delay, ``[Nfreqs, K]``
+    with orthonormal columns (HERA's 1024 channels over 100-200 MHz: K = 18 / 30 / 51 at 50 / 100 / 200 ns).  One basis serves every
+    antenna, polarization and time (``HipFitSolver.set_gain_basis``, ``calibrate_and_model_tensor(gain_max_dly=...)``); it is cached
+    like the foreground blocks (read-only array)."""
+    max_dly_ns = float(max_dly_ns)
+    if not np.isfinite(max_dly_ns) or max_dly_ns <= 0.0:
+        raise ValueError(f"gain_max_dly must be a positive delay in ns, got {max_dly_ns}")
+    return _dpss_block(max_dly_ns, np.asarray(freqs, dtype=np.float64), eigenval_cutoff)
+
+
 def get_redundant_grps_data(uvdata, remove_redundancy=False, tol=1.0, include_autos=False):
     """Redundant groups of the antenna pairs that carry data -- same arguments and return tuple as modeling.py:10-81:
     ``(antpairs, red_grps, vec_bin_centers, lengths)`` with one bin centre / length per returned group.

@@ -102,6 +102,7 @@ class HipFitSolver:
         self.problem = prob
         self.nants, self.nfreqs, self.nbls, self.ncoeffs = prob.nants, prob.nfreqs, prob.nbls, prob.ncoeffs
         self.nslices = int(getattr(prob, "nslices", 1) or 1)
+        self.gain_nvec = 0  # a new problem fits per channel until set_gain_basis
         if prob.data_r is not None:
             self.set_data(prob.data_r, prob.data_i, prob.wgts)
         return self
@@ -152,6 +153,42 @@ class HipFitSolver:
         c_i = np.empty_like(c_r)
         _lib.check(self._lib.cal_solver_get_params(self._h, int(which), _ptr(g_r), _ptr(g_i), _ptr(c_r), _ptr(c_i)))
         return g_r, g_i, c_r, c_i
+
+    # ---- gain basis ----------------------------------------------------------------------------------------
+    def set_gain_basis(self, basis):
+        """Confine the fit's correction to the gains to span(B): ``g = g0 + B y`` with ``basis`` real ``[nfreqs, K]`` shared by
+        every antenna (and time slice), ``g0`` the gains the solver holds at this call (or is given later by ``set_params``),
+        ``y`` the optimizer's variables (zero at the start).  Call after ``set_problem``; moments and iteration count start
+        over as after ``set_optimizer``.  ``None`` detaches the basis: the fit is per channel again."""
+        if basis is None:
+            _lib.check(self._lib.cal_solver_set_gain_basis(self._h, None, 0))
+            self.gain_nvec = 0
+            return
+        b = np.asarray(basis)
+        if np.iscomplexobj(b):
+            raise ValueError("the gain basis must be real")
+        if b.ndim != 2 or b.shape[0] != self.nfreqs or b.shape[1] < 1:
+            raise ValueError(f"expected a gain basis of shape ({self.nfreqs}, K >= 1), got {b.shape}")
+        b = np.ascontiguousarray(b, dtype=self.dtype)
+        _lib.check(self._lib.cal_solver_set_gain_basis(self._h, _ptr(b), int(b.shape[1])))
+        self.gain_nvec = int(b.shape[1])
+
+    def get_gain_coeffs(self, which=0):
+        """The coefficients ``y`` of the gain basis, ``(y_r, y_i)`` of shape ``[nants, K]`` (``which`` as in ``get_params``)."""
+        k = int(getattr(self, "gain_nvec", 0))
+        y_r = np.empty((self.nants, k), dtype=self.dtype)
+        y_i = np.empty_like(y_r)
+        _lib.check(self._lib.cal_solver_get_gain_coeffs(self._h, int(which), _ptr(y_r), _ptr(y_i)))
+        return y_r, y_i
+
+    def eval_gain_coeff_grads(self):
+        """Loss and its gradient with respect to ``y``: ``grad g @ B``, ``(loss, gy_r, gy_i)``."""
+        k = int(getattr(self, "gain_nvec", 0))
+        gy_r = np.empty((self.nants, k), dtype=self.dtype)
+        gy_i = np.empty_like(gy_r)
+        loss = C.c_double(0)
+        _lib.check(self._lib.cal_solver_eval_gain_coeff_grads(self._h, C.byref(loss), _ptr(gy_r), _ptr(gy_i)))
+        return loss.value, gy_r, gy_i
 
     def get_moments(self):
         g = [np.empty((self.nants, self.nfreqs), dtype=self.dtype) for _ in range(4)]

@@ -285,6 +285,27 @@ int cal_solver_set_exchange_hook(cal_solver* s, cal_exchange_fn fn, void* ctx, i
  * communicator / hook (1 without either).  A launcher's rank count is a claim; this is what the data path sees (bench.py reports it). */
 int cal_solver_comm_size(cal_solver* s, int* nranks_seen);
 
+/* Gains that are smooth in frequency WHILE they are fitted (no counterpart in the reference, whose gains are free per channel,
+ * calibration.py:596-599):  g_a(f) = g0_a(f) + sum_k B(f, k) y_a(k)  with one real basis B shared by every antenna and time
+ * slice.  g0 are the gains the solver holds when the basis is set (or is given afterwards: cal_solver_set_params with gains sets
+ * g0 to them and y to 0), so the fit starts exactly where the per-channel fit starts and only the CORRECTION lies in span(B).
+ * The optimizer's gain variables are y_r, y_i [nants][nvec] (chain rule: grad y = grad g @ B); loss, coefficients and loop
+ * semantics are unchanged, use_min snapshots y.  Under a communicator or exchange hook the PROJECTED gradient is exchanged:
+ * planes x 2 nants kpad reals per step instead of planes x 2 nants fpad, kpad = nvec rounded up to a multiple of 8 (planes = 3
+ * with the "sum" regulariser on the general kernels, else 1).
+ *   basis: real (solver dtype) [nfreqs][nvec] row-major, 1 <= nvec <= nfreqs; call after set_problem (a new problem detaches
+ *   the basis).  Moments and t are zeroed as by set_optimizer.  nvec = 0 detaches: the fit is per channel again, from the gains
+ *   as they stand.
+ * cal_solver_get_params keeps returning the full gains [nants][nfreqs]; cal_solver_eval_grads the per-channel gradient.
+ * While a basis is set: the optimizer LAMB (set_optimizer / set_gain_basis) and cal_solver_get_moments / set_moments
+ * (checkpoint / resume) fail with CAL_ERR_UNSUPPORTED; a train step always runs kernel by kernel (CAL_LAUNCH_ONE_TAIL falls
+ * back to that form; CAL_LAUNCH_GRAPH replays the kernel-by-kernel step, the two basis kernels included). */
+int cal_solver_set_gain_basis(cal_solver* s, const void* basis, int32_t nvec);
+/* y [nants][nvec] real each; which as in cal_solver_get_params */
+int cal_solver_get_gain_coeffs(cal_solver* s, int which, void* y_r, void* y_i);
+/* loss and its gradient with respect to y (the projected gain gradient): gy_* [nants][nvec] (parity tests) */
+int cal_solver_eval_gain_coeff_grads(cal_solver* s, double* loss, void* gy_r, void* gy_i);
+
 #ifdef __cplusplus
 }
 #endif
