@@ -134,6 +134,7 @@ SYMBOLS = {
     "cal_solver_set_exchange_hook": (C.c_int, [_P, _P, _P, C.c_int, C.c_int]),
     "cal_solver_comm_size": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "cal_solver_set_gain_basis": (C.c_int, [_P, _P, C.c_int32]),
+    "cal_solver_set_gain_time_basis": (C.c_int, [_P, _P, C.c_int32, C.c_int32]),
     "cal_solver_get_gain_coeffs": (C.c_int, [_P, C.c_int, _P, _P]),
     "cal_solver_eval_gain_coeff_grads": (C.c_int, [_P, C.POINTER(C.c_double), _P, _P]),
 }

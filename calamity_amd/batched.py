@@ -115,8 +115,11 @@ class SliceBatchFitter:
     repeat, the workers then share that GPU and exchange through host memory).  Arrays handed in and out are GLOBAL and
     slice-major: per-sample arrays ``[nt * nbls, nfreqs]``, gains ``[nt * nants, nfreqs]``, coefficients ``[nt * ncoeffs]``."""
 
-    def __init__(self, prob, nt, dtype=np.float32, layout="shared", devices=(0,), kernel_path="auto", communicator_of_one=False):
-        """``communicator_of_one``: with a single device, join a one-rank RCCL communicator anyway (from the worker thread, like the
+    def __init__(self, prob, nt, dtype=np.float32, layout="shared", devices=(0,), kernel_path="auto", communicator_of_one=False, joint=False):
+        """``joint``: the slices are ONE fit with one loop state whose loss is the sum over them (``nslices = 1``, the layout of
+        ``distributed.batch_time_slices(per_slice=False)``): what a gain time basis needs (``set_gain_time_basis``).  ``run_slices``
+        then returns one result.
+        ``communicator_of_one``: with a single device, join a one-rank RCCL communicator anyway (from the worker thread, like the
         workers of several devices do) so that the exchange path -- the set-up agreement, an all-reduce per step -- runs on a
         one-GPU box; the numbers are those of the plain fit."""
         self.prob, self.nt, self.dtype = prob, int(nt), np.dtype(dtype)
@@ -131,6 +134,8 @@ class SliceBatchFitter:
         self.subs, self.rows, self.cidx = [], [], []
         for r in range(D):
             sub, bl, cidx = replicate_slices(prob, self.nt, shares[r])
+            if joint:
+                sub.nslices = 1
             self.subs.append(sub)
             # rows / coefficients of this worker in the global slice-major arrays
             self.rows.append(np.concatenate([bl + t * prob.nbls for t in range(self.nt)]))
@@ -269,8 +274,12 @@ class SliceBatchFitter:
         projected gain gradients."""
         self._each(lambda r, s: s.set_gain_basis(basis))
 
+    def set_gain_time_basis(self, basis_t):
+        """One time basis ``[nt, L]`` over the slices of a ``joint`` fitter (``HipFitSolver.set_gain_time_basis``; ``None`` detaches it)."""
+        self._each(lambda r, s: s.set_gain_time_basis(basis_t))
+
     def get_gain_coeffs(self, which=0):
-        """``(y_r, y_i)``, ``[nt * nants, K]`` (replicated over the workers, like the gains)."""
+        """``(y_r, y_i)``, ``[nt * nants, K]`` (replicated over the workers, like the gains); ``[nants, L, K]`` with a time basis."""
         return self.solvers[0].get_gain_coeffs(which)
 
     def timing_enable(self, on):

@@ -724,6 +724,18 @@ def _check_gain_basis(basis, nfreqs):
     return np.ascontiguousarray(basis, dtype=np.float64)
 
 
+def _check_gain_time_basis(basis, ntimes):
+    """``gain_time_basis`` as a real float64 ``[Ntimes, L]`` array, 1 <= L <= Ntimes (ValueError otherwise)."""
+    basis = np.asarray(basis)
+    if np.iscomplexobj(basis):
+        raise ValueError("gain_time_basis must be real")
+    if basis.ndim != 2 or basis.shape[0] != ntimes or not 1 <= basis.shape[1] <= ntimes:
+        raise ValueError(f"gain_time_basis must have shape (Ntimes = {ntimes}, 1 <= L <= Ntimes), got {basis.shape}")
+    if not np.all(np.isfinite(basis)):
+        raise ValueError("gain_time_basis has non-finite elements")
+    return np.ascontiguousarray(basis, dtype=np.float64)
+
+
 def insert_model_into_uvdata_tensor(uvdata, time, polarization, ants_map, red_grps, model_r, model_i, scale_factor=1.0):
     """Insert ``(Nants, Nants, Nfreqs)`` model cubes back into a UVData object, conjugating pairs stored in reversed
     order and multiplying by ``scale_factor`` -- calibration.py:741-795.  Modifies ``uvdata``."""
@@ -801,6 +813,8 @@ def calibrate_and_model_tensor(
     device_split=None,
     gain_basis=None,
     gain_max_dly=None,
+    gain_time_basis=None,
+    gain_time_scale=None,
     **opt_kwargs,
 ):
     """Simultaneous calibration and foreground fitting -- calibration.py:963-1331, same arguments, defaults and
@@ -828,6 +842,21 @@ def calibrate_and_model_tensor(
       ``g_in`` the gains it starts from (unity, the ``gains`` object's, or the previous time's with
       ``init_guesses_from_previous_time_step``): output gains minus input gains lie in span(B).  Works in the loop, in batches and
       on several devices (``device_split="groups"`` then exchanges the projected gradient, K instead of Nfreqs numbers per antenna).
+    * ``gain_time_basis`` / ``gain_time_scale`` (give one, default neither: every time fits its own gains): fit gains that are smooth
+      in time.  ``gain_time_basis``: real ``[Ntimes, L]`` on the times of ``uvdata``; ``gain_time_scale``: a time in seconds, the basis
+      is then ``modeling.gain_time_dpss_basis(times, gain_time_scale)``.  It stands alone (gains free per channel, smooth in time) or
+      combines with ``gain_basis`` / ``gain_max_dly``.  All unskipped times of a polarization are then ONE joint fit on one device,
+      ``g[t] = g_in[t] + sum_l Bt[t, l] (B) y[l]`` with ``y`` shared by the times (``HipFitSolver.set_gain_time_basis``); the
+      per-slice host work (skip test, rms scale, weights, initial coefficients, write-back, post-hoc renormalisation, residual) is
+      that of the batched path.  A skipped time is flagged as always; ``Bt`` is evaluated on all times and the rows of the fitted
+      ones are used (its first columns, should fewer times be fitted than it has columns).  The joint fit has ONE loss, the sum over
+      its times: ``tol`` acts on that sum, and ``fit_history[pol][t]["loss"]`` is that same list for every fitted ``t``.
+      ``model_regularization="sum"`` uses one pair of sums for the joint fit, ``S = sum_t S_t`` and ``P = sum_t P_t`` with every
+      time's weights normalised as before: the per-slice regulariser exactly only for one time.  Refused with ``ValueError``:
+      ``init_guesses_from_previous_time_step`` (a chain is not a joint fit), ``batch_slices=False``, ``batch_slices=N`` below the number
+      of times (the times share variables: one batch, whose device memory is that of the same times batched -- ``_auto_batch``'s
+      sizing does not apply, ``gpu_memory_limit`` does), ``parallel_fits > 1``, more than one device or a ``device_split``, and a basis
+      that is complex, non-finite or of another shape.
     * ``layout``: "shared" (default; baselines alias the distinct basis blocks) or "stream" (every baseline owns its tiles).
     * ``parallel_fits`` (default 1): with ``batch_slices=False``, fits that many slices concurrently, each on its own
       solver and HIP stream.
@@ -836,8 +865,27 @@ def calibrate_and_model_tensor(
         raise ValueError("give gain_basis or gain_max_dly, not both")
     if gain_max_dly is not None:
         gain_basis = modeling.gain_dpss_basis(np.asarray(uvdata.freq_array, dtype=np.float64).ravel(), gain_max_dly)
+    if gain_time_basis is not None and gain_time_scale is not None:
+        raise ValueError("give gain_time_basis or gain_time_scale, not both")
+    if gain_time_basis is not None or gain_time_scale is not None:
+        if init_guesses_from_previous_time_step:
+            raise ValueError("a gain time basis fits all times jointly: init_guesses_from_previous_time_step (a chain over the times) contradicts it")
+        if batch_slices is not None and not batch_slices:
+            raise ValueError("a gain time basis fits all times jointly: batch_slices=False (the loop over the times) contradicts it")
+        if parallel_fits is not None and parallel_fits > 1:
+            raise ValueError("a gain time basis fits all times jointly: parallel_fits > 1 (concurrent fits of single times) contradicts it")
+        if device_split is not None or isinstance(devices, str) or (devices is not None and len(list(devices)) > 1):
+            raise ValueError("a gain time basis fits on one device: give devices=None or one device index, and no device_split")
     if gain_basis is not None:
         gain_basis = _check_gain_basis(gain_basis, uvdata.Nfreqs)
+    if gain_time_scale is not None:
+        gain_time_basis = modeling.gain_time_dpss_basis(np.unique(uvdata.time_array), gain_time_scale)
+    if gain_time_basis is not None:
+        ntimes_all = len(np.unique(uvdata.time_array))
+        gain_time_basis = _check_gain_time_basis(gain_time_basis, ntimes_all)
+        if batch_slices is not None and batch_slices is not True and int(batch_slices) < ntimes_all:
+            raise ValueError(f"a gain time basis fits all {ntimes_all} times of a polarization as ONE fit, which batch_slices={batch_slices} cannot "
+                             "hold: the times share their variables and cannot be split into smaller batches")
     antpairs_data = uvdata.get_antpairs()
     if not include_autos:
         antpairs_data = set([ap for ap in antpairs_data if ap[0] != ap[1]])
@@ -884,11 +932,16 @@ def calibrate_and_model_tensor(
         parallel_fits = 1
     times = np.unique(uvdata.time_array)
     if batch_slices is None:
-        batch_slices = parallel_fits <= 1
+        batch_slices = parallel_fits <= 1 or gain_time_basis is not None
     if init_guesses_from_previous_time_step:
         batch_slices = False  # every time starts from the previous one's result: a chain, not a batch
     if batch_slices:
-        max_batch = _auto_batch(prob, dtype, layout) if batch_slices is True else max(1, min(int(batch_slices), _lib_max_slices()))
+        if gain_time_basis is not None:
+            # the joint fit of a polarization holds all of its times, whatever _auto_batch would make of them: its device memory is
+            # about that of the same times as one batch (gpu_memory_limit raises MemoryError as for any batch)
+            max_batch = len(times)
+        else:
+            max_batch = _auto_batch(prob, dtype, layout) if batch_slices is True else max(1, min(int(batch_slices), _lib_max_slices()))
         fit_history = _fit_slices_batched(
             uvdata=uvdata, sky_model=sky_model, gains=gains, resid=resid, model=model, prob=prob, corr_inds=corr_inds, ants_map=ants_map,
             times=times, weights=weights, nsamples_in_weights=nsamples_in_weights, dtype=dtype, skip_threshold=skip_threshold,
@@ -896,8 +949,10 @@ def calibrate_and_model_tensor(
             maxsteps=maxsteps, n_profile_steps=n_profile_steps, profile_log_dir=profile_log_dir, model_regularization=model_regularization,
             verbose=verbose, max_batch=max_batch, devices=devices, layout=layout, opt_kwargs=opt_kwargs,
             correct_model=correct_model, correct_resid=correct_resid, device_split=device_split, gain_basis=gain_basis,
+            gain_time_basis=gain_time_basis,
         )
         return model, resid, gains, fit_history  # (every slice left _fit_slices_batched in its final state)
+    assert gain_time_basis is None, "a gain time basis must not reach the loop over single times"
     if layout is not None:
         prob.__dict__["_layout"] = layout
     if devices is not None:
@@ -1159,16 +1214,17 @@ def _resolve_devices(devices):
     return [int(d) for d in devices], False
 
 
-def _batch_fitter(prob, nt, dtype, layout, devices):
-    """The SliceBatchFitter of ``nt`` slices of these components (kept with them: a second call re-uses the device copy)."""
+def _batch_fitter(prob, nt, dtype, layout, devices, joint=False):
+    """The SliceBatchFitter of ``nt`` slices of these components (kept with them: a second call re-uses the device copy);
+    ``joint``: the slices are one fit with one loop state (a gain time basis)."""
     from .batched import SliceBatchFitter
 
     cache = prob.__dict__.setdefault("_batch_fitters", {})
-    key = (np.dtype(dtype).str, layout, tuple(devices), int(nt), threading.get_ident())
+    key = (np.dtype(dtype).str, layout, tuple(devices), int(nt) if not joint else -int(nt), threading.get_ident())
     if key not in cache:
         for k in [k for k in cache if k[:3] == key[:3] and k[4] == key[4]]:  # another batch size of the same call: free it first
             cache.pop(k).close()
-        fitter = SliceBatchFitter(prob, nt, dtype=dtype, layout=layout, devices=devices)
+        fitter = SliceBatchFitter(prob, nt, dtype=dtype, layout=layout, devices=devices, joint=joint)
         limit = _DEVICE["memory_limit_gib"]
         if limit is not None and fitter.memory_bytes() > limit * 2.0**30:
             used = fitter.memory_bytes() / 2.0**30
@@ -1181,12 +1237,13 @@ def _batch_fitter(prob, nt, dtype, layout, devices):
 def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds, ants_map, times, weights, nsamples_in_weights, dtype,
                         skip_threshold, use_model_snr_weights, optimizer, use_min, freeze_model, tol, maxsteps, n_profile_steps,
                         profile_log_dir, model_regularization, verbose, max_batch, devices, layout, opt_kwargs, correct_model=True,
-                        correct_resid=False, device_split=None, gain_basis=None):
+                        correct_resid=False, device_split=None, gain_basis=None, gain_time_basis=None):
     """The pol x time loop of calibration.py:1160-1331 with the fits of all unskipped slices issued as batches: per slice
     exactly the host-side steps of the loop body (skip test :1173-1177, rms scale :1178-1182, tensorize :1184-1233, write-back
     :1271-1300, post-hoc renormalisation :1311-1319, residual and calibration state of the outputs :1322-1331), the gradient
     descent of :1244-1269 for up to ``max_batch`` slices at once with per-slice loop control.  Returns ``fit_history``; model,
-    resid and gains are complete when it returns."""
+    resid and gains are complete when it returns.  ``gain_time_basis`` (``[len(times), L]``): the unskipped times of a polarization
+    are one batch and one JOINT fit (one loop state, loss = the sum over the times; calibrate_and_model_tensor's docstring)."""
     OPTIMIZERS[optimizer]  # unknown optimizer -> KeyError, like calibration.py:571
     dtype = np.dtype(dtype)
     layout = layout or "shared"
@@ -1195,6 +1252,7 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
     todo = [dict(polnum=polnum, pol=pol, time_index=time_index, time=time) for polnum, pol in enumerate(pols) for time_index, time in enumerate(times)]
     finish = _output_finisher(uvdata, model, resid, gains, correct_model, correct_resid)
     devices, chose_devices = _resolve_devices(devices)
+    joint = gain_time_basis is not None
     cat = lambda parts_: parts_[0] if len(parts_) == 1 else np.concatenate(parts_)  # noqa: E731
 
     # One batch goes through three stages: prep (host: the slices' rows out of the containers), fit (device), post (host: the model
@@ -1245,7 +1303,7 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
         nt = len(batch)
         echo(f"{datetime.datetime.now()} Working on {nt} (polarization, time) slices together...\n", verbose=verbose)
         try:
-            fitter = _batch_fitter(prob, nt, dtype, layout, devices if on is None else on)
+            fitter = _batch_fitter(prob, nt, dtype, layout, devices if on is None else on, joint=joint)
         except Exception as err:  # noqa: BLE001
             if on is not None:
                 raise
@@ -1259,7 +1317,7 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
             warnings.warn(f"calamity_amd: the fit could not be set up on devices {devices} ({type(err).__name__}: {err}); continuing on device {devices[0]}",
                           RuntimeWarning, stacklevel=2)
             devices = devices[:1]
-            fitter = _batch_fitter(prob, nt, dtype, layout, devices)
+            fitter = _batch_fitter(prob, nt, dtype, layout, devices, joint=joint)
         w_all, d_r, d_i, s_r, s_i = arrs["w"], arrs["d_r"], arrs["d_i"], arrs["s_r"], arrs["s_i"]
         # tensorize_fg_coeffs x 2 (calibration.py:1219-1233) for every slice: one device pass gives both components (the weights
         # it masks with are those of set_data; the sky model arrives as the pass's own source rows)
@@ -1279,13 +1337,19 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
             fitter.set_data(d_r, d_i, w_all)
         fitter.set_params(arrs["g_r"], arrs["g_i"], c_r, c_i)
         fitter.set_gain_basis(gain_basis)  # (the fitter is kept between calls: None detaches an earlier call's) g0 = the gains just set
+        if joint:
+            # the rows of the fitted times; no more vectors than times (the first columns: the smoothest sequences)
+            fitter.set_gain_time_basis(gain_time_basis[[sl["time_index"] for sl in batch]][:, :nt])
         if model_regularization == "sum":
             # priors of calibration.py:619-625, one pair per slice (accumulated in float64 on the host)
             nb = prob.nbls
             pri = arrs["pri"]
             if pri is None:
                 pri = np.asarray([_prior_sums(s_r[t * nb : (t + 1) * nb], s_i[t * nb : (t + 1) * nb], w_all[t * nb : (t + 1) * nb]) for t in range(nt)])
-            fitter.set_regularization("sum", pri[:, 0], pri[:, 1])
+            if joint:
+                fitter.set_regularization("sum", float(np.sum(pri[:, 0])), float(np.sum(pri[:, 1])))  # one pair of sums for the one fit
+            else:
+                fitter.set_regularization("sum", pri[:, 0], pri[:, 1])
         else:
             fitter.set_regularization(None)
         fitter.set_optimizer(optimizer, **opt_kwargs)
@@ -1298,6 +1362,8 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
             fitter.timing_enable(False)
         fitter.run_slices(1, record=False, freeze_model=freeze_model)  # the unrecorded step of calibration.py:693
         results = fitter.run_slices(maxsteps, record=True, tol=tol, use_min=use_min, freeze_model=freeze_model)
+        if joint:
+            results = results * nt  # one loop, one loss history: every time of the fit reports it
         cur = fitter.get_params(0)
         best = fitter.get_params(1) if use_min and any(len(r[0]) for r in results) else None
         if freeze_model:
@@ -1334,6 +1400,8 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
         echo(f"{datetime.datetime.now()} {len(batch)} (polarization, time) slices written back.\n", verbose=verbose)
 
     batches = [todo[lo : lo + max_batch] for lo in range(0, len(todo), max_batch)]
+    if joint:
+        batches = [[sl for sl in todo if sl["polnum"] == polnum] for polnum in range(len(pols))]
     if device_split not in (None, "slices", "groups"):
         raise ValueError(f"device_split={device_split!r}: 'slices', 'groups' or None")
     D = len(devices)
@@ -1743,6 +1811,9 @@ def fitting_argparser():
     sp.add_argument("--use_autocorrs_in_weights", default=False, action="store_true", help="inverse-variance weights from the autocorrelations")
     sp.add_argument("--gain_max_dly", type=float, default=None,
                     help="fit the gains in a DPSS basis that is smooth up to this delay [ns]; default: free per-channel gains")
+    sp.add_argument("--gain_time_scale", type=float, default=None,
+                    help="fit the times of a polarization jointly, with gains in a DPSS basis that drifts no faster than this [s]; "
+                         "default: every time fits its own gains")
     return ap
 
 

@@ -24,6 +24,7 @@
 #include "dense64_kernels.hpp"
 #include "multi_mfma_kernels.hpp"
 #include "gain_basis_kernels.hpp"
+#include "gain_time_basis_kernels.hpp"
 #include <cstdlib>
 #include <dlfcn.h>
 #include <type_traits>
@@ -208,6 +209,7 @@ struct cal_solver {
   virtual int set_exchange_hook(cal_exchange_fn fn, void* ctx, int rank, int nranks) = 0;
   virtual int comm_size(int* nranks_seen) = 0;
   virtual int set_gain_basis(const void* basis, int nvec) = 0;
+  virtual int set_gain_time_basis(const void* basis_t, int ntimes, int nvec_t) = 0;
   virtual int get_gain_coeffs(int which, void* y_r, void* y_i) = 0;
   virtual int eval_gain_coeff_grads(double* loss, void* gy_r, void* gy_i) = 0;
 };
@@ -279,9 +281,10 @@ struct SolverT final : cal_solver {
     int optimizer, freeze, reg, losses_cap, st_par, tail, nsteps;
     const void *gains, *snap, *losses;
     const void *y, *ysnap;  // gain basis: the coefficient arrays the captured update and gain_expand_kernel work on (null without one)
+    const void *tz, *tpf;   // time basis over a frequency basis: what the two time kernels hand to / take from the frequency kernels
     bool operator==(const GraphKey& o) const {
       return optimizer == o.optimizer && freeze == o.freeze && reg == o.reg && losses_cap == o.losses_cap && st_par == o.st_par && tail == o.tail &&
-             nsteps == o.nsteps && gains == o.gains && snap == o.snap && losses == o.losses && y == o.y && ysnap == o.ysnap;
+             nsteps == o.nsteps && gains == o.gains && snap == o.snap && losses == o.losses && y == o.y && ysnap == o.ysnap && tz == o.tz && tpf == o.tpf;
     }
   } graph_key{};
   DevBuf agree_buf;
@@ -322,6 +325,19 @@ struct SolverT final : cal_solver {
   DevBuf gb_B, gb_Bt;                          // [fpad][gb_kpad] and [gb_kpad][fpad], zero-padded
   DevBuf gb_g0, gb_y, gb_ym, gb_yv, gb_ysnap, gb_proj;
   bool gb_on() const { return gb_nvec > 0; }
+  // gain time basis (set_gain_time_basis; gain_time_basis_kernels.hpp): the solver's nants = tb_T tb_na rows are tb_T times of tb_na antennas,
+  // gains = gb_g0 + Bt (x) (B) y.  y, its moments, snapshot and gradient planes live in the gb_ buffers above, [tb_na][tb_L][W] complex with
+  // W = gb_kpad or, without a frequency basis, fpad.  With both bases tb_pf holds gain_project_kernel's planes ([3][nants][gb_kpad]) and
+  // tb_z what gain_expand_kernel expands ([nants][gb_kpad]).
+  int tb_T = 0, tb_L = 0, tb_lpad = 0, tb_tpad = 0, tb_na = 0;
+  DevBuf tb_B, tb_Bt;                          // [tb_T][tb_lpad] and [tb_L][tb_tpad], zero-padded
+  DevBuf tb_z, tb_pf;
+  bool tb_on() const { return tb_L > 0; }
+  bool yb_on() const { return gb_on() || tb_on(); }                 // the optimizer's gain variables are y
+  int y_w() const { return gb_on() ? gb_kpad : fpad; }               // W
+  int y_cols() const { return gb_on() ? gb_nvec : nfreqs; }          // ... and its unpadded length
+  int y_rows() const { return tb_on() ? tb_na : nants; }
+  long long y_row() const { return (long long)(tb_on() ? tb_L : 1) * y_w(); }  // complex elements per row of y
   // timing
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
@@ -1495,7 +1511,7 @@ struct SolverT final : cal_solver {
     if (!d) return fail(CAL_ERR_INVALID, "set_optimizer: null");
     if (d->optimizer < CAL_OPT_ADAM || d->optimizer > CAL_OPT_LAMB)
       return fail(CAL_ERR_INVALID, "set_optimizer: unknown optimizer id %d", d->optimizer);
-    if (d->optimizer == CAL_OPT_LAMB && gb_on())
+    if (d->optimizer == CAL_OPT_LAMB && yb_on())
       return fail(CAL_ERR_UNSUPPORTED, "set_optimizer: LAMB is not supported while a gain basis is set (its per-variable norms are defined over the "
                   "per-channel gains); detach the basis (nvec = 0) or choose another optimizer");
     if (d->optimizer == CAL_OPT_LAMB && !lamb_ok)
@@ -1510,16 +1526,16 @@ struct SolverT final : cal_solver {
                          (long long)(gains_v.bytes / sizeof(T)), (T)d->initial_accumulator_value);
       hipLaunchKernelGGL(fill_kernel<T>, dim3(grid_for((long long)(coef_v.bytes / sizeof(T)))), dim3(256), 0, stream, coef_v.as<T>(),
                          (long long)(coef_v.bytes / sizeof(T)), (T)d->initial_accumulator_value);
-      if (gb_on())
+      if (yb_on())
         hipLaunchKernelGGL(fill_kernel<T>, dim3(grid_for((long long)(gb_yv.bytes / sizeof(T)))), dim3(256), 0, stream, gb_yv.as<T>(),
                            (long long)(gb_yv.bytes / sizeof(T)), (T)d->initial_accumulator_value);
       HIP_TRY(hipGetLastError());
     } else {
       HIP_TRY(hipMemsetAsync(gains_v.p, 0, gains_v.bytes, stream));
       HIP_TRY(hipMemsetAsync(coef_v.p, 0, coef_v.bytes, stream));
-      if (gb_on()) HIP_TRY(hipMemsetAsync(gb_yv.p, 0, gb_yv.bytes, stream));
+      if (yb_on()) HIP_TRY(hipMemsetAsync(gb_yv.p, 0, gb_yv.bytes, stream));
     }
-    if (gb_on()) HIP_TRY(hipMemsetAsync(gb_ym.p, 0, gb_ym.bytes, stream));
+    if (yb_on()) HIP_TRY(hipMemsetAsync(gb_ym.p, 0, gb_ym.bytes, stream));
     drop_graph();
     for (int t = 0; t < nslices; ++t) reset_loop_state(h_state[t]);  // a new fit begins
     has_opt = true;
@@ -1532,7 +1548,7 @@ struct SolverT final : cal_solver {
     if (!has_problem) return fail(CAL_ERR_STATE, "set_params before set_problem");
     if (g_r) CAL_TRY(upload_rows(g_r, gains.as<T>(), nants, 2, 0));
     if (g_i) CAL_TRY(upload_rows(g_i, gains.as<T>(), nants, 2, 1));
-    if ((g_r || g_i) && gb_on()) CAL_TRY(rebase_gain_basis());  // the fit now starts from these gains: g0 := gains, y := 0
+    if ((g_r || g_i) && yb_on()) CAL_TRY(rebase_gain_basis());  // the fit now starts from these gains: g0 := gains, y := 0
     if (c_r) HIP_TRY(copy_sync(coef.as<T>(), c_r, (size_t)ncoef * sizeof(T), hipMemcpyHostToDevice));
     if (c_i) HIP_TRY(copy_sync(coef.as<T>() + ncoef, c_i, (size_t)ncoef * sizeof(T), hipMemcpyHostToDevice));
     if (g_r && g_i) has_gains = true;
@@ -1547,7 +1563,7 @@ struct SolverT final : cal_solver {
     const T* c = coef.as<T>();
     if (which == 1) {
       if (!gains_snap.p) return fail(CAL_ERR_STATE, "get_params(which=1): no use_min snapshot was taken");
-      if (gb_on()) {
+      if (yb_on()) {
         // the snapshot of a basis fit is y's: the gains it stands for are expanded into gains_snap (which no kernel writes while a basis is set)
         if (!gb_ysnap.p) return fail(CAL_ERR_STATE, "get_params(which=1): no use_min snapshot was taken since the gain basis was set");
         CAL_TRY(enqueue_expand(gb_ysnap.as<T2>(), gains_snap.as<T2>()));
@@ -1569,6 +1585,7 @@ struct SolverT final : cal_solver {
                   int64_t* t) override {
     HIP_TRY(hipSetDevice(device));
     if (!has_problem) return fail(CAL_ERR_STATE, "get_moments before set_problem");
+    if (tb_on()) return fail(CAL_ERR_UNSUPPORTED, "get_moments: checkpoint / resume of a fit with a gain time basis is not supported");
     if (gb_on()) return fail(CAL_ERR_UNSUPPORTED, "get_moments: checkpoint / resume of a fit with a gain basis is not supported");
     HIP_TRY(hipStreamSynchronize(stream));
     if (t && nslices > 1) {
@@ -1595,6 +1612,7 @@ struct SolverT final : cal_solver {
                   const void* cv_r, const void* cv_i, int64_t t) override {
     HIP_TRY(hipSetDevice(device));
     if (!has_problem) return fail(CAL_ERR_STATE, "set_moments before set_problem");
+    if (tb_on()) return fail(CAL_ERR_UNSUPPORTED, "set_moments: checkpoint / resume of a fit with a gain time basis is not supported");
     if (gb_on()) return fail(CAL_ERR_UNSUPPORTED, "set_moments: checkpoint / resume of a fit with a gain basis is not supported");
     if (t < 0) return fail(CAL_ERR_INVALID, "set_moments: negative iteration count");
     if (gm_r) CAL_TRY(upload_rows(gm_r, gains_m.as<T>(), nants, 2, 0));
@@ -1851,11 +1869,22 @@ struct SolverT final : cal_solver {
     }
     const bool proj = project && grads;
     if (proj) {
-      hipLaunchKernelGGL((gain_project_kernel<T>), dim3(nants, Rk ? 3 : 1), dim3(256), 0, stream, r0, gb_B.as<T>(), gb_proj.as<T>(), nants, fpad, gb_kpad,
-                         st, sm);
+      const int planes = Rk ? 3 : 1;
+      if (gb_on())
+        hipLaunchKernelGGL((gain_project_kernel<T>), dim3(nants, planes), dim3(256), 0, stream, r0, gb_B.as<T>(), (tb_on() ? tb_pf : gb_proj).template as<T>(),
+                           nants, fpad, gb_kpad, st, sm);
+      if (tb_on()) {
+        // the contraction over time, of the frequency-projected planes or of the per-channel ones
+        constexpr int V = 16 / (int)sizeof(T);
+        const int row = 2 * y_w();
+        const long long nvecs = (long long)tb_na * (row / V);
+        hipLaunchKernelGGL((gain_time_project_kernel<T>), dim3((unsigned)((nvecs + 255) / 256), (tb_L + kTimeTile - 1) / kTimeTile, planes), dim3(256), 0, stream,
+                           gb_on() ? tb_pf.as<T>() : reinterpret_cast<const T*>(r0), tb_B.as<T>(), gb_proj.as<T>(), tb_na, tb_T, tb_L, tb_lpad, row,
+                           (size_t)nants * row);
+      }
       HIP_TRY(hipGetLastError());
     }
-    const size_t xn = proj ? (size_t)nants * gb_kpad : gn;  // complex elements per plane of the gain gradient from here on
+    const size_t xn = proj ? (size_t)y_rows() * y_row() : gn;  // complex elements per plane of the gain gradient from here on
     T2* x0 = proj ? gb_proj.as<T2>() : r0;
     if (comm_on()) {
       // the one exchange step of the sharded fit: sum gain-gradient parts and loss scalars over ranks
@@ -1873,7 +1902,7 @@ struct SolverT final : cal_solver {
                          apply_update ? 1 : 0, nslices);
     if (grads && Rk) {
       hipLaunchKernelGGL(combine_gain_kernel<T>, dim3((int)((xn + 255) / 256)), dim3(256), 0, stream, x0, x0 + xn, x0 + 2 * xn, (int)xn, st, sm,
-                         proj ? gb_kpad : fpad);
+                         proj ? (int)y_row() : fpad);
       hipLaunchKernelGGL(combine_coeff_kernel<T>, dim3((ncoef + 255) / 256), dim3(256), 0, stream, grad_c0(), grad_c0() + ncoef,
                          grad_c1(), grad_c1() + ncoef, ncoef, st, sm);
     }
@@ -1894,7 +1923,7 @@ struct SolverT final : cal_solver {
   // (... nor with the regulariser over baselines that share tiles: alpha is needed between that path's two passes)
   bool one_launch_tail() const {
     // (... nor with a gain basis: the projection sits between the antenna reduction and the update, which step_tail_kernel fuses)
-    return !comm_on() && !mf_ok && !gb_on() && tail_fits_one_launch() && launch_mode != CAL_LAUNCH_KERNELS && !(reg == CAL_REG_SUM && reg_prepass);
+    return !comm_on() && !mf_ok && !yb_on() && tail_fits_one_launch() && launch_mode != CAL_LAUNCH_KERNELS && !(reg == CAL_REG_SUM && reg_prepass);
   }
   void launch_tail(const TailArgs<T>& a, unsigned grid, bool R) {
     if (R)
@@ -1948,7 +1977,7 @@ struct SolverT final : cal_solver {
     T* gsnap = gains_snap.p ? gains_snap.as<T>() : gains.as<T>();
     T* csnap = coef_snap.p ? coef_snap.as<T>() : coef.as<T>();
     // with a gain basis the gain set is y: the same kernels on flat arrays of row length gb_kpad, then the gains are rebuilt from y
-    if (gb_on()) {
+    if (yb_on()) {
       CAL_TRY(enqueue_update_y(freeze_model, losses_cap));
       return enqueue_expand(gb_y.as<T2>(), gains.as<T2>());
     }
@@ -2009,7 +2038,7 @@ struct SolverT final : cal_solver {
     DevState* st = st_cur();
     T* ysnap = gb_ysnap.p ? gb_ysnap.as<T>() : gb_y.as<T>();
     T* csnap = coef_snap.p ? coef_snap.as<T>() : coef.as<T>();
-    const AdamSet<T> ga{gb_y.as<T>(), gb_proj.as<T>(), gb_ym.as<T>(), gb_yv.as<T>(), ysnap, 2LL * nants * gb_kpad};
+    const AdamSet<T> ga{gb_y.as<T>(), gb_proj.as<T>(), gb_ym.as<T>(), gb_yv.as<T>(), ysnap, 2LL * y_rows() * y_row()};
     const AdamSet<T> ca{coef.as<T>(), grad_c0(), coef_m.as<T>(), coef_v.as<T>(), csnap, freeze_model ? 0LL : 2LL * ncoef};
     const bool Rk = reg == CAL_REG_SUM && !mf_ok;
     if (!Rk && tail_fits_one_launch()) {
@@ -2020,20 +2049,33 @@ struct SolverT final : cal_solver {
       const int nblk = (int)((ga.n + 255) / 256) + (int)((ca.n + 255) / 256);
       const unsigned nb = (unsigned)std::max(1, std::min(nblk, 16384));
       hipLaunchKernelGGL((step_update_kernel<T>), dim3(nb), dim3(256), (size_t)nslices * sizeof(SliceStep<T>), stream, ga, ca, ps, st, st_nxt(),
-                         scal.as<double>(), losses.as<double>(), losses_cap, smap(mf_ok), gb_kpad, ncoef);
+                         scal.as<double>(), losses.as<double>(), losses_cap, smap(mf_ok), (int)y_row(), ncoef);
       st_par ^= 1;
       HIP_TRY(hipGetLastError());
       return CAL_OK;
     }
     constexpr long long per = 256LL * kAdamVec<T>;  // elements per block
     const int va = (int)((ga.n + per - 1) / per), vb = (int)((ca.n + per - 1) / per);
-    hipLaunchKernelGGL((adam2_kernel<T>), dim3((unsigned)(va + vb)), dim3(256), 0, stream, ga, ca, va, st, smap(mf_ok), gb_kpad, ncoef);
+    hipLaunchKernelGGL((adam2_kernel<T>), dim3((unsigned)(va + vb)), dim3(256), 0, stream, ga, ca, va, st, smap(mf_ok), (int)y_row(), ncoef);
     HIP_TRY(hipGetLastError());
     return CAL_OK;
   }
-  // dst = g0 + B src (src: y or its use_min snapshot)
+  // dst = g0 + B src (src: y or its use_min snapshot); with a time basis dst = g0 + Bt (x) B src
   int enqueue_expand(const T2* src, T2* dst) {
     constexpr int per = 256 * (16 / (int)sizeof(T));  // channels per block
+    if (tb_on()) {
+      constexpr int V = 16 / (int)sizeof(T);
+      const int row = 2 * y_w();
+      const long long nvecs = (long long)tb_na * (row / V);
+      hipLaunchKernelGGL((gain_time_expand_kernel<T>), dim3((unsigned)((nvecs + 255) / 256), (tb_T + kTimeTile - 1) / kTimeTile), dim3(256), 0, stream,
+                         gb_on() ? nullptr : gb_g0.as<T>(), tb_Bt.as<T>(), reinterpret_cast<const T*>(src),
+                         gb_on() ? tb_z.as<T>() : reinterpret_cast<T*>(dst), tb_na, tb_T, tb_L, tb_tpad, row);
+      if (!gb_on()) {
+        HIP_TRY(hipGetLastError());
+        return CAL_OK;
+      }
+      src = tb_z.as<T2>();
+    }
     hipLaunchKernelGGL((gain_expand_kernel<T>), dim3((fpad + per - 1) / per, nants), dim3(256), 0, stream, gb_g0.as<T2>(), gb_Bt.as<T>(), src, dst, fpad,
                        gb_kpad);
     HIP_TRY(hipGetLastError());
@@ -2041,7 +2083,8 @@ struct SolverT final : cal_solver {
   }
   void release_gain_basis() {
     gb_nvec = gb_kpad = 0;
-    for (DevBuf* b : {&gb_B, &gb_Bt, &gb_g0, &gb_y, &gb_ym, &gb_yv, &gb_ysnap, &gb_proj}) b->release();
+    tb_T = tb_L = tb_lpad = tb_tpad = tb_na = 0;
+    for (DevBuf* b : {&gb_B, &gb_Bt, &gb_g0, &gb_y, &gb_ym, &gb_yv, &gb_ysnap, &gb_proj, &tb_B, &tb_Bt, &tb_z, &tb_pf}) b->release();
   }
   // the fit starts from the gains the solver holds now: g0 := gains, y := 0 (and its snapshot with it)
   int rebase_gain_basis() {
@@ -2051,40 +2094,20 @@ struct SolverT final : cal_solver {
     HIP_TRY(hipStreamSynchronize(stream));
     return CAL_OK;
   }
-  int set_gain_basis(const void* basis, int nvec) override {
-    HIP_TRY(hipSetDevice(device));
-    if (!has_problem) return fail(CAL_ERR_STATE, "set_gain_basis before set_problem");
-    if (nvec < 0 || nvec > nfreqs) return fail(CAL_ERR_INVALID, "set_gain_basis: nvec = %d; a basis has 1 .. nfreqs = %d vectors (0 detaches it)", nvec, nfreqs);
-    if (nvec > 0 && !basis) return fail(CAL_ERR_INVALID, "set_gain_basis: null basis");
-    if (nvec == 0 && !gb_on()) return CAL_OK;  // nothing to detach: the per-channel fit goes on as it stands, moments included
-    if (nvec > 0 && has_opt && opt.optimizer == CAL_OPT_LAMB)
-      return fail(CAL_ERR_UNSUPPORTED, "set_gain_basis: LAMB is not supported with a gain basis (its per-variable norms are defined over the per-channel gains)");
-    HIP_TRY(hipStreamSynchronize(stream));
-    drop_graph();
-    if (nvec == 0) {
-      // back to the per-channel fit, from the gains as they stand
-      release_gain_basis();
-    } else {
-      const T* b = static_cast<const T*>(basis);
-      for (long long i = 0; i < (long long)nfreqs * nvec; ++i)
-        if (!std::isfinite((double)b[i])) return fail(CAL_ERR_INVALID, "set_gain_basis: the basis has a non-finite element");
-      const int kpad = (nvec + kGainBasisPad - 1) / kGainBasisPad * kGainBasisPad;
-      std::vector<T> hB((size_t)fpad * kpad, (T)0), hBt((size_t)kpad * fpad, (T)0);
-      for (int f = 0; f < nfreqs; ++f)
-        for (int k = 0; k < nvec; ++k) hB[(size_t)f * kpad + k] = hBt[(size_t)k * fpad + f] = b[(size_t)f * nvec + k];
-      release_gain_basis();
-      const size_t ybytes = (size_t)nants * kpad * sizeof(T2);
-      CAL_TRY(gb_B.alloc(hB.size() * sizeof(T), false));
-      CAL_TRY(gb_Bt.alloc(hBt.size() * sizeof(T), false));
-      HIP_TRY(copy_sync(gb_B.p, hB.data(), hB.size() * sizeof(T), hipMemcpyHostToDevice));
-      HIP_TRY(copy_sync(gb_Bt.p, hBt.data(), hBt.size() * sizeof(T), hipMemcpyHostToDevice));
+  // after either setter changed its basis: the y arrays in the shape the two bases now give them, g0 := gains, y := 0, moments and t zeroed
+  int reshape_gain_coeffs() {
+    for (DevBuf* b : {&gb_g0, &gb_y, &gb_ym, &gb_yv, &gb_ysnap, &gb_proj, &tb_z, &tb_pf}) b->release();
+    if (yb_on()) {
+      const size_t ybytes = (size_t)y_rows() * y_row() * sizeof(T2);
       CAL_TRY(gb_g0.alloc(gains.bytes, false));
       CAL_TRY(gb_y.alloc(ybytes));
       CAL_TRY(gb_ym.alloc(ybytes));
       CAL_TRY(gb_yv.alloc(ybytes));
       CAL_TRY(gb_proj.alloc(3 * ybytes));
-      gb_nvec = nvec;
-      gb_kpad = kpad;
+      if (gb_on() && tb_on()) {
+        CAL_TRY(tb_z.alloc((size_t)nants * gb_kpad * sizeof(T2)));
+        CAL_TRY(tb_pf.alloc(3 * (size_t)nants * gb_kpad * sizeof(T2)));
+      }
       CAL_TRY(rebase_gain_basis());
     }
     if (has_opt) {
@@ -2094,21 +2117,111 @@ struct SolverT final : cal_solver {
     }
     return CAL_OK;
   }
+  // the device copies of a basis and of its transpose
+  int upload_basis_pair(DevBuf& d, DevBuf& dt, const std::vector<T>& h, const std::vector<T>& ht) {
+    CAL_TRY(d.alloc(h.size() * sizeof(T), false));
+    CAL_TRY(dt.alloc(ht.size() * sizeof(T), false));
+    HIP_TRY(copy_sync(d.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+    HIP_TRY(copy_sync(dt.p, ht.data(), ht.size() * sizeof(T), hipMemcpyHostToDevice));
+    return CAL_OK;
+  }
+  // a setter that failed half way (an allocation, a copy) must not leave one basis on with y arrays in the shape of another
+  // configuration: BOTH bases go, the fit is per channel from the gains as they stand, and the caller gets the error
+  int detach_bases_after(int rc) {
+    if (rc != CAL_OK) release_gain_basis();
+    return rc;
+  }
+  int set_gain_basis(const void* basis, int nvec) override {
+    HIP_TRY(hipSetDevice(device));
+    if (!has_problem) return fail(CAL_ERR_STATE, "set_gain_basis before set_problem");
+    if (nvec < 0 || nvec > nfreqs) return fail(CAL_ERR_INVALID, "set_gain_basis: nvec = %d; a basis has 1 .. nfreqs = %d vectors (0 detaches it)", nvec, nfreqs);
+    if (nvec > 0 && !basis) return fail(CAL_ERR_INVALID, "set_gain_basis: null basis");
+    if (nvec == 0 && !gb_on()) return CAL_OK;  // nothing to detach: the fit goes on as it stands, moments included
+    if (nvec > 0 && has_opt && opt.optimizer == CAL_OPT_LAMB)
+      return fail(CAL_ERR_UNSUPPORTED, "set_gain_basis: LAMB is not supported with a gain basis (its per-variable norms are defined over the per-channel gains)");
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (nvec == 0) {
+      // back to the per-channel fit (or the one smooth in time only), from the gains as they stand
+      drop_graph();
+      gb_nvec = gb_kpad = 0;
+      gb_B.release();
+      gb_Bt.release();
+    } else {
+      const T* b = static_cast<const T*>(basis);
+      for (long long i = 0; i < (long long)nfreqs * nvec; ++i)
+        if (!std::isfinite((double)b[i])) return fail(CAL_ERR_INVALID, "set_gain_basis: the basis has a non-finite element");
+      drop_graph();
+      const int kpad = (nvec + kGainBasisPad - 1) / kGainBasisPad * kGainBasisPad;
+      std::vector<T> hB((size_t)fpad * kpad, (T)0), hBt((size_t)kpad * fpad, (T)0);
+      for (int f = 0; f < nfreqs; ++f)
+        for (int k = 0; k < nvec; ++k) hB[(size_t)f * kpad + k] = hBt[(size_t)k * fpad + f] = b[(size_t)f * nvec + k];
+      gb_nvec = gb_kpad = 0;
+      const int rc = upload_basis_pair(gb_B, gb_Bt, hB, hBt);
+      if (rc != CAL_OK) return detach_bases_after(rc);
+      gb_nvec = nvec;
+      gb_kpad = kpad;
+    }
+    return detach_bases_after(reshape_gain_coeffs());
+  }
+  int set_gain_time_basis(const void* basis_t, int ntimes, int nvec_t) override {
+    HIP_TRY(hipSetDevice(device));
+    if (!has_problem) return fail(CAL_ERR_STATE, "set_gain_time_basis before set_problem");
+    if (nvec_t < 0) return fail(CAL_ERR_INVALID, "set_gain_time_basis: nvec_t = %d is negative (0 detaches the time basis)", nvec_t);
+    if (nvec_t == 0) {
+      if (!tb_on()) return CAL_OK;  // nothing to detach: the fit goes on as it stands, moments included
+      HIP_TRY(hipStreamSynchronize(stream));
+      drop_graph();
+      tb_T = tb_L = tb_lpad = tb_tpad = tb_na = 0;
+      tb_B.release();
+      tb_Bt.release();
+      return detach_bases_after(reshape_gain_coeffs());
+    }
+    if (nslices > 1)
+      return fail(CAL_ERR_UNSUPPORTED, "set_gain_time_basis: the solver holds %d time slices that stop on their own, which contradicts variables shared "
+                  "between them; build the times as one fit (nslices <= 1, nants = ntimes x antennas)", nslices);
+    if (ntimes <= 0 || nants % ntimes != 0)
+      return fail(CAL_ERR_INVALID, "set_gain_time_basis: nants = %d is not a multiple of ntimes = %d (antenna a at time t is row t * (nants / ntimes) + a)", nants,
+                  ntimes);
+    if (nvec_t > ntimes) return fail(CAL_ERR_INVALID, "set_gain_time_basis: nvec_t = %d; a time basis has 1 .. ntimes = %d vectors (0 detaches it)", nvec_t, ntimes);
+    if (!basis_t) return fail(CAL_ERR_INVALID, "set_gain_time_basis: null basis");
+    if (has_opt && opt.optimizer == CAL_OPT_LAMB)
+      return fail(CAL_ERR_UNSUPPORTED, "set_gain_time_basis: LAMB is not supported with a gain time basis (its per-variable norms are defined over the "
+                  "per-channel gains)");
+    const T* b = static_cast<const T*>(basis_t);
+    for (long long i = 0; i < (long long)ntimes * nvec_t; ++i)
+      if (!std::isfinite((double)b[i])) return fail(CAL_ERR_INVALID, "set_gain_time_basis: the basis has a non-finite element");
+    HIP_TRY(hipStreamSynchronize(stream));
+    drop_graph();
+    const int lpad = (nvec_t + kTimeTile - 1) / kTimeTile * kTimeTile, tpad = (ntimes + kTimeTile - 1) / kTimeTile * kTimeTile;
+    std::vector<T> hB((size_t)ntimes * lpad, (T)0), hBt((size_t)nvec_t * tpad, (T)0);
+    for (int t = 0; t < ntimes; ++t)
+      for (int l = 0; l < nvec_t; ++l) hB[(size_t)t * lpad + l] = hBt[(size_t)l * tpad + t] = b[(size_t)t * nvec_t + l];
+    tb_T = tb_L = tb_lpad = tb_tpad = tb_na = 0;
+    const int rc = upload_basis_pair(tb_B, tb_Bt, hB, hBt);
+    if (rc != CAL_OK) return detach_bases_after(rc);
+    tb_T = ntimes;
+    tb_L = nvec_t;
+    tb_lpad = lpad;
+    tb_tpad = tpad;
+    tb_na = nants / ntimes;
+    return detach_bases_after(reshape_gain_coeffs());
+  }
   int get_gain_coeffs(int which, void* y_r, void* y_i) override {
     HIP_TRY(hipSetDevice(device));
-    if (!gb_on()) return fail(CAL_ERR_STATE, "get_gain_coeffs: no gain basis is set (cal_solver_set_gain_basis)");
+    if (!yb_on()) return fail(CAL_ERR_STATE, "get_gain_coeffs: no gain basis is set (cal_solver_set_gain_basis, cal_solver_set_gain_time_basis)");
     if (which != 0 && which != 1) return fail(CAL_ERR_INVALID, "get_gain_coeffs: which must be 0 or 1");
     if (which == 1 && !gb_ysnap.p) return fail(CAL_ERR_STATE, "get_gain_coeffs(which=1): no use_min snapshot was taken since the gain basis was set");
     const T* y = which == 1 ? gb_ysnap.as<T>() : gb_y.as<T>();
     HIP_TRY(hipStreamSynchronize(stream));
-    if (y_r) CAL_TRY(download_rows(y_r, y, nants, 2, 0, gb_nvec, gb_kpad));
-    if (y_i) CAL_TRY(download_rows(y_i, y, nants, 2, 1, gb_nvec, gb_kpad));
+    const long long rows = y_rows() * (y_row() / y_w());
+    if (y_r) CAL_TRY(download_rows(y_r, y, rows, 2, 0, y_cols(), y_w()));
+    if (y_i) CAL_TRY(download_rows(y_i, y, rows, 2, 1, y_cols(), y_w()));
     return CAL_OK;
   }
   int eval_gain_coeff_grads(double* loss, void* gy_r, void* gy_i) override {
     HIP_TRY(hipSetDevice(device));
     CAL_TRY(ready());
-    if (!gb_on()) return fail(CAL_ERR_STATE, "eval_gain_coeff_grads: no gain basis is set (cal_solver_set_gain_basis)");
+    if (!yb_on()) return fail(CAL_ERR_STATE, "eval_gain_coeff_grads: no gain basis is set (cal_solver_set_gain_basis, cal_solver_set_gain_time_basis)");
     begin_pass_state();
     CAL_TRY(push_state());
     CAL_TRY(enqueue_pass(true, false, 0, false, true));
@@ -2119,8 +2232,9 @@ struct SolverT final : cal_solver {
       for (int t = 0; t < nslices; ++t) tot += h_state[t].loss;
       *loss = tot;
     }
-    if (gy_r) CAL_TRY(download_rows(gy_r, gb_proj.as<T>(), nants, 2, 0, gb_nvec, gb_kpad));
-    if (gy_i) CAL_TRY(download_rows(gy_i, gb_proj.as<T>(), nants, 2, 1, gb_nvec, gb_kpad));
+    const long long rows = y_rows() * (y_row() / y_w());
+    if (gy_r) CAL_TRY(download_rows(gy_r, gb_proj.as<T>(), rows, 2, 0, y_cols(), y_w()));
+    if (gy_i) CAL_TRY(download_rows(gy_i, gb_proj.as<T>(), rows, 2, 1, y_cols(), y_w()));
     return CAL_OK;
   }
 
@@ -2137,7 +2251,7 @@ struct SolverT final : cal_solver {
   // pass(es), gain_grad_kernel, finalize_kernel, the update): a host whose cores are busy elsewhere then pays ONE launch per `nsteps` steps
   // instead of four or five per step (measured on shared boxes: 2.4-3.2 ms per step of a 0.6-ms kernel while the host was contended).
   int replay_steps(bool freeze_model, int cap, bool tail, int nsteps) {
-    const GraphKey key{opt.optimizer, freeze_model ? 1 : 0, reg, cap, st_par, tail ? 1 : 0, nsteps, gains.p, gains_snap.p, losses.p, gb_y.p, gb_ysnap.p};
+    const GraphKey key{opt.optimizer, freeze_model ? 1 : 0, reg, cap, st_par, tail ? 1 : 0, nsteps, gains.p, gains_snap.p, losses.p, gb_y.p, gb_ysnap.p, tb_z.p, tb_pf.p};
     if (!graph_exec || !(key == graph_key)) {
       drop_graph();
       hipGraph_t graph = nullptr;
@@ -2155,7 +2269,7 @@ struct SolverT final : cal_solver {
       HIP_TRY(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
       int rc = CAL_OK;
       for (int k = 0; k < nsteps && rc == CAL_OK; ++k) {
-        rc = enqueue_pass(true, true, cap, tail, gb_on());
+        rc = enqueue_pass(true, true, cap, tail, yb_on());
         if (rc == CAL_OK) rc = tail ? enqueue_tail(freeze_model, cap) : enqueue_update(freeze_model, cap);
       }
       const hipError_t e = hipStreamEndCapture(stream, &graph);
@@ -2272,7 +2386,7 @@ struct SolverT final : cal_solver {
       CAL_TRY(gains_snap.alloc(gains.bytes));
       CAL_TRY(coef_snap.alloc(coef.bytes));
     }
-    if (r->use_min && gb_on() && !gb_ysnap.p) CAL_TRY(gb_ysnap.alloc(gb_y.bytes));
+    if (r->use_min && yb_on() && !gb_ysnap.p) CAL_TRY(gb_ysnap.alloc(gb_y.bytes));
     const size_t lbytes = (size_t)nslices * r->nsteps * sizeof(double);
     if (r->record && losses.bytes < lbytes) CAL_TRY(losses.alloc(lbytes));
     if (!losses.p) CAL_TRY(losses.alloc((size_t)nslices * sizeof(double)));
@@ -2320,7 +2434,7 @@ struct SolverT final : cal_solver {
         for (; gsteps >= 2 && s + gsteps <= n; s += gsteps) CAL_TRY(replay_steps(r->freeze_model != 0, cap, tail1, gsteps));
       }
       for (; s < n; ++s) {
-        CAL_TRY(enqueue_pass(true, true, cap, tail1, gb_on()));
+        CAL_TRY(enqueue_pass(true, true, cap, tail1, yb_on()));
         if (tail1) CAL_TRY(enqueue_tail(r->freeze_model != 0, cap)); else CAL_TRY(enqueue_update(r->freeze_model != 0, cap));
       }
       issued += n;
@@ -2443,7 +2557,7 @@ struct SolverT final : cal_solver {
                            &data_r, &data_i, &wgts, &gains, &gains_alt, &gains_m, &gains_v, &gains_snap, &coef, &coef_m, &coef_v, &coef_snap,
                            &q0, &q1, &comm, &scal, &gcp0, &gcp1, &gc0, &gc1, &part, &state, &losses, &scratch, &model_buf,
                            &mf_ops, &mf_panels, &mf_map, &members, &heads, &lamb_vars, &lamb_cvar_ptr, &lamb_partial, &lamb_ratio, &lamb_glob, &lamb_slot, &slice_coff, &slice_ipart_ptr, &slice_ipart_idx,
-                           &slice_ppart_ptr, &slice_ppart_idx, &slice_cblk, &gb_B, &gb_Bt, &gb_g0, &gb_y, &gb_ym, &gb_yv, &gb_ysnap, &gb_proj};
+                           &slice_ppart_ptr, &slice_ppart_idx, &slice_cblk, &gb_B, &gb_Bt, &gb_g0, &gb_y, &gb_ym, &gb_yv, &gb_ysnap, &gb_proj, &tb_B, &tb_Bt, &tb_z, &tb_pf};
     int64_t n = 0;
     for (auto* d : all) n += (int64_t)d->bytes;
     *b = n;
@@ -2750,6 +2864,7 @@ int cal_solver_comm_init(cal_solver* s, const void* id, int rank, int nranks) { 
 int cal_solver_set_exchange_hook(cal_solver* s, cal_exchange_fn fn, void* ctx, int rank, int nranks) { NEED(s); return s->set_exchange_hook(fn, ctx, rank, nranks); }
 int cal_solver_comm_size(cal_solver* s, int* nranks_seen) { NEED(s); return s->comm_size(nranks_seen); }
 int cal_solver_set_gain_basis(cal_solver* s, const void* basis, int32_t nvec) { NEED(s); return s->set_gain_basis(basis, nvec); }
+int cal_solver_set_gain_time_basis(cal_solver* s, const void* basis_t, int32_t ntimes, int32_t nvec_t) { NEED(s); return s->set_gain_time_basis(basis_t, ntimes, nvec_t); }
 int cal_solver_get_gain_coeffs(cal_solver* s, int which, void* y_r, void* y_i) { NEED(s); return s->get_gain_coeffs(which, y_r, y_i); }
 int cal_solver_eval_gain_coeff_grads(cal_solver* s, double* loss, void* gy_r, void* gy_i) { NEED(s); return s->eval_gain_coeff_grads(loss, gy_r, gy_i); }
 

@@ -230,6 +230,39 @@ def gain_dpss_basis(freqs, max_dly_ns, eigenval_cutoff=1e-10):
     return _dpss_block(max_dly_ns, np.asarray(freqs, dtype=np.float64), eigenval_cutoff)
 
 
+def gain_time_dpss_basis(times_jd, time_scale_s, eigenval_cutoff=1e-10):
+    """The time basis of gains that drift no faster than ``time_scale_s`` seconds: the real DPSS block
+    ``dpss_operator(x, [0.0], [1 / time_scale_s], [eigenval_cutoff])`` on ``x`` = seconds since the first of the (uniformly spaced,
+    ascending) Julian dates ``times_jd``, ``[Ntimes, L]`` with orthonormal columns (60 integrations of 10.7 s: L = 8 at 600 s, 5 at
+    1800 s).  One basis serves every antenna, channel and polarization (``HipFitSolver.set_gain_time_basis``,
+    ``calibrate_and_model_tensor(gain_time_scale=...)``).  One time gives ``[[1.0]]``; where the operator has no vector to give (two
+    times, or a scale far beyond the span of the times) the basis is the constant vector ``1 / sqrt(Ntimes)``: gains that do not drift
+    at all."""
+    time_scale_s = float(time_scale_s)
+    if not np.isfinite(time_scale_s) or time_scale_s <= 0.0:
+        raise ValueError(f"gain_time_scale must be a positive time in seconds, got {time_scale_s}")
+    t = np.asarray(times_jd, dtype=np.float64).ravel()
+    if len(t) == 0 or not np.all(np.isfinite(t)):
+        raise ValueError("gain_time_dpss_basis needs at least one finite time")
+    if len(t) == 1:
+        return np.ones((1, 1))
+    x = (t - t[0]) * 86400.0
+    dx = np.diff(x)
+    # (a Julian date near 2.46e6 resolves 4e-5 s: steps that agree to a thousandth of a step are the same step)
+    if np.any(dx <= 0.0) or np.max(np.abs(dx - dx[0])) > 1e-3 * dx[0]:
+        raise ValueError("gain_time_dpss_basis needs uniformly spaced, ascending times")
+    constant = np.full((len(t), 1), 1.0 / np.sqrt(len(t)))
+    if len(t) == 2:
+        return constant
+    try:
+        amat, _ = dpss_operator(x, [0.0], [1.0 / time_scale_s], [eigenval_cutoff])
+    except (ValueError, IndexError):  # no sequence reaches the eigenvalue cut
+        return constant
+    if amat.shape[1] == 0:
+        return constant
+    return np.ascontiguousarray(amat.real)
+
+
 def get_redundant_grps_data(uvdata, remove_redundancy=False, tol=1.0, include_autos=False):
     """Redundant groups of the antenna pairs that carry data -- same arguments and return tuple as modeling.py:10-81:
     ``(antpairs, red_grps, vec_bin_centers, lengths)`` with one bin centre / length per returned group.

@@ -103,6 +103,7 @@ class HipFitSolver:
         self.nants, self.nfreqs, self.nbls, self.ncoeffs = prob.nants, prob.nfreqs, prob.nbls, prob.ncoeffs
         self.nslices = int(getattr(prob, "nslices", 1) or 1)
         self.gain_nvec = 0  # a new problem fits per channel until set_gain_basis
+        self.gain_time_shape = None  # ... and per time until set_gain_time_basis: (ntimes, nvec_t)
         if prob.data_r is not None:
             self.set_data(prob.data_r, prob.data_i, prob.wgts)
         return self
@@ -173,18 +174,45 @@ class HipFitSolver:
         _lib.check(self._lib.cal_solver_set_gain_basis(self._h, _ptr(b), int(b.shape[1])))
         self.gain_nvec = int(b.shape[1])
 
-    def get_gain_coeffs(self, which=0):
-        """The coefficients ``y`` of the gain basis, ``(y_r, y_i)`` of shape ``[nants, K]`` (``which`` as in ``get_params``)."""
+    def set_gain_time_basis(self, basis_t):
+        """Fit gains that are smooth in time.  The solver holds ``T`` times as one fit (``distributed.batch_time_slices(parts,
+        per_slice=False)``: ``nants = T * Na``, antenna ``a`` at time ``t`` is row ``t * Na + a``) and
+        ``g[t * Na + a] = g0[t * Na + a] + sum_l Bt[t, l] z[a, l]`` with ``basis_t`` real ``[T, L]``, ``1 <= L <= T``; ``z[a, l]`` is
+        ``B y[a, l]`` when a frequency basis is set as well (``set_gain_basis``, in either order) and ``y[a, l]`` itself without
+        one.  ``g0`` are the gains the solver holds at this call (or is given later by ``set_params``), ``y`` starts at zero, moments
+        and iteration count start over.  ``None`` detaches the time basis alone."""
+        if basis_t is None:
+            _lib.check(self._lib.cal_solver_set_gain_time_basis(self._h, None, 0, 0))
+            self.gain_time_shape = None
+            return
+        b = np.asarray(basis_t)
+        if np.iscomplexobj(b):
+            raise ValueError("the gain time basis must be real")
+        if b.ndim != 2 or b.shape[0] < 1 or b.shape[1] < 1:
+            raise ValueError(f"expected a gain time basis of shape (T >= 1, 1 <= L <= T), got {b.shape}")
+        b = np.ascontiguousarray(b, dtype=self.dtype)
+        _lib.check(self._lib.cal_solver_set_gain_time_basis(self._h, _ptr(b), int(b.shape[0]), int(b.shape[1])))
+        self.gain_time_shape = (int(b.shape[0]), int(b.shape[1]))
+
+    def _gain_coeff_shape(self):
         k = int(getattr(self, "gain_nvec", 0))
-        y_r = np.empty((self.nants, k), dtype=self.dtype)
+        tshape = getattr(self, "gain_time_shape", None)
+        if tshape is None:
+            return (self.nants, k)
+        return (self.nants // tshape[0], tshape[1], k if k else self.nfreqs)
+
+    def get_gain_coeffs(self, which=0):
+        """The coefficients ``y`` of the gain basis, ``(y_r, y_i)`` of shape ``[nants, K]`` (``which`` as in ``get_params``); while a
+        time basis is set ``[Na, L, K]``, or ``[Na, L, nfreqs]`` without a frequency basis."""
+        y_r = np.empty(self._gain_coeff_shape(), dtype=self.dtype)
         y_i = np.empty_like(y_r)
         _lib.check(self._lib.cal_solver_get_gain_coeffs(self._h, int(which), _ptr(y_r), _ptr(y_i)))
         return y_r, y_i
 
     def eval_gain_coeff_grads(self):
-        """Loss and its gradient with respect to ``y``: ``grad g @ B``, ``(loss, gy_r, gy_i)``."""
-        k = int(getattr(self, "gain_nvec", 0))
-        gy_r = np.empty((self.nants, k), dtype=self.dtype)
+        """Loss and its gradient with respect to ``y``: ``grad g @ B`` (contracted with ``Bt`` over the times while a time basis is
+        set), ``(loss, gy_r, gy_i)`` in the shape of ``get_gain_coeffs``."""
+        gy_r = np.empty(self._gain_coeff_shape(), dtype=self.dtype)
         gy_i = np.empty_like(gy_r)
         loss = C.c_double(0)
         _lib.check(self._lib.cal_solver_eval_gain_coeff_grads(self._h, C.byref(loss), _ptr(gy_r), _ptr(gy_i)))

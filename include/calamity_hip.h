@@ -301,10 +301,32 @@ int cal_solver_comm_size(cal_solver* s, int* nranks_seen);
  * (checkpoint / resume) fail with CAL_ERR_UNSUPPORTED; a train step always runs kernel by kernel (CAL_LAUNCH_ONE_TAIL falls
  * back to that form; CAL_LAUNCH_GRAPH replays the kernel-by-kernel step, the two basis kernels included). */
 int cal_solver_set_gain_basis(cal_solver* s, const void* basis, int32_t nvec);
-/* y [nants][nvec] real each; which as in cal_solver_get_params */
+/* y [nants][nvec] real each; which as in cal_solver_get_params.  While a time basis is set (cal_solver_set_gain_time_basis):
+ * [Na][L][nvec], or [Na][L][nfreqs] without a frequency basis */
 int cal_solver_get_gain_coeffs(cal_solver* s, int which, void* y_r, void* y_i);
-/* loss and its gradient with respect to y (the projected gain gradient): gy_* [nants][nvec] (parity tests) */
+/* loss and its gradient with respect to y (the projected gain gradient): gy_* [nants][nvec] (parity tests); while a time basis
+ * is set the gradient contracted over the times as well, in the shape cal_solver_get_gain_coeffs then has */
 int cal_solver_eval_gain_coeff_grads(cal_solver* s, double* loss, void* gy_r, void* gy_i);
+
+/* Gains that are smooth in TIME while they are fitted.  The solver holds T time slices as ONE fit with one loop state (nslices <= 1,
+ * nants = T Na, antenna a at time t is row t Na + a: what distributed.batch_time_slices(per_slice=False) builds) and
+ *   g[t Na + a](f) = g0[t Na + a](f) + sum_l Bt(t, l) z_a,l(f),    Bt real [T][L], 1 <= L <= T,
+ *   z_a,l(f) = sum_k B(f, k) y_a(l, k) while a frequency basis is set too, y_a(l, f) without one (free per channel, smooth in time).
+ * The optimizer's gain variables are y_r, y_i [Na][L][W], W = kpad or fpad on the device, nvec or nfreqs at this interface.  Chain
+ * rule: grad y_a(l, .) = sum_t Bt(t, l) p[t Na + a](.), p the (frequency-projected) gain-gradient row, and the same for every plane.
+ * Loss, coefficients and loop semantics are unchanged; use_min snapshots y.  Under a communicator or exchange hook the
+ * time-projected planes are exchanged: planes x 2 Na L W reals per step (plus the loss scalars as before), W = kpad with a frequency
+ * basis, else fpad.
+ *   basis_t: real (solver dtype) [ntimes][nvec_t] row-major; call after set_problem.  Independent of cal_solver_set_gain_basis and
+ *   callable in either order: each setter sets g0 := the current gains, y := 0 and zeroes moments and t.  nvec_t = 0 detaches the
+ *   time basis only; a new set_problem detaches both.  A setter (this one or cal_solver_set_gain_basis) that fails half way, in an
+ *   allocation or a copy, detaches BOTH bases before it returns the error: the fit is per channel from the gains as they stand.
+ * Fails with CAL_ERR_UNSUPPORTED for a solver of several slices (nslices > 1) and for LAMB (here and in set_optimizer), with
+ * CAL_ERR_INVALID when nants % ntimes != 0, nvec_t > ntimes or the basis has a non-finite entry.  While it is set,
+ * cal_solver_get_moments / set_moments fail with CAL_ERR_UNSUPPORTED, cal_solver_get_gain_coeffs and
+ * cal_solver_eval_gain_coeff_grads return [Na][L][nvec] (or [Na][L][nfreqs]), get_params and eval_grads are unchanged, and a train
+ * step runs kernel by kernel as with the frequency basis (CAL_LAUNCH_GRAPH replays that step, the time kernels included). */
+int cal_solver_set_gain_time_basis(cal_solver* s, const void* basis_t, int32_t ntimes, int32_t nvec_t);
 
 #ifdef __cplusplus
 }

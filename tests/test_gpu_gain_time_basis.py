@@ -1,0 +1,666 @@
+"""Gains fitted smooth in time (cal_solver_set_gain_time_basis) on the GPU: T times of Na antennas as ONE fit,
+``g = g0 + Bt (x) Bf y`` (or ``g = g0 + Bt (x) y`` without a frequency basis), ``y`` ``[Na, L, W]`` the optimizer's variables,
+its gradient contracted over time by gain_time_project_kernel, the gains rebuilt after every update by gain_time_expand_kernel.
+
+Yardsticks: the CPU oracle (``oracle.ref_numpy``) for the projected gradient; the NumPy restatement of the joint fit
+(``tests/test_gain_time_basis_host.py: gamma2_fit``, which CPU tests pin to ``gamma_fit`` and to the oracle) for trajectories, loop
+controls and recovery; the frequency-basis fit of the same solver for ``Bt = I``.  Tolerances are the project's
+(tests/test_gpu_parity.py: TOL)."""
+import copy
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from calamity_amd import _lib, cal_utils, calfits, calibration, distributed, modeling, problem, synthetic, uvcompat  # noqa: E402
+from calamity_amd.batched import SliceBatchFitter, replicate_slices  # noqa: E402
+from oracle import ref_numpy as R  # noqa: E402
+from test_gain_time_basis_host import TIMES_60, gamma2_fit, joint_case, product_error, recovery_case, restated_recovery  # noqa: E402
+from test_gpu_parity import TOL, make_solver, oracle_inputs, relnorm  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+
+def cplx(a_r, a_i):
+    return np.asarray(a_r, dtype=np.float64) + 1j * np.asarray(a_i, dtype=np.float64)
+
+
+def freq_basis(nfreqs, dly_ns=100.0):
+    return np.array(modeling.gain_dpss_basis(150e6 + 400e3 * np.arange(nfreqs), dly_ns))
+
+
+def time_basis(ntimes, scale=400.0):
+    return np.array(modeling.gain_time_dpss_basis(TIMES_60[:ntimes], scale))
+
+
+def expand(Bt, y, Bf):
+    """``Bt (x) Bf y`` as rows ``t * Na + a``; ``Bf = None``: no frequency basis."""
+    z = np.einsum("tl,alk->tak", Bt, y) if Bf is None else np.einsum("tl,alk,fk->taf", Bt, y, Bf)
+    return z.reshape(-1, z.shape[-1])
+
+
+def outside_span(Bt, Bf, d, na):
+    """Norm of the part of d (complex rows ``t * Na + a``, ``[T * Na, F]``) outside span(Bt) (x) span(Bf)."""
+    T = Bt.shape[0]
+    Pt = Bt @ np.linalg.pinv(Bt)
+    Pf = np.eye(d.shape[1]) if Bf is None else Bf @ np.linalg.pinv(Bf)
+    d3 = d.reshape(T, na, -1)
+    return np.linalg.norm(d3 - np.einsum("st,taf,gf->sag", Pt, d3, Pf))
+
+
+# ---- 1. the projected gradient ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("layout", ["stream", "shared"])
+@pytest.mark.parametrize("reg", [False, True])
+@pytest.mark.parametrize("with_freq", [True, False])
+@pytest.mark.parametrize("kind", ["dpss", "random"])
+def test_projected_gradient(dtype, layout, reg, with_freq, kind):
+    T = 5
+    big, start, ch, fg_r, fg_i = joint_case(ntimes=T, nants=5, nfreqs=40, with_sky=reg)
+    na = big.nants // T
+    a0, a1 = R.ant_inds_from_corr_inds(ch["corr_inds"])
+    priors = R.prior_sums(ch["sky_model_r"], ch["sky_model_i"], ch["wgts"]) if reg else (None, None)
+    loss, gg_r, gg_i, _, _ = R.loss_and_grads(start["g_r"], start["g_i"], fg_r, fg_i, ch["fg_comps"], ch["data_r"], ch["data_i"], ch["wgts"],
+                                              a0, a1, *priors)
+    Bt = time_basis(T) if kind == "dpss" else np.random.default_rng(2).standard_normal((T, 3))  # (not orthogonal, odd L and T)
+    assert 1 < Bt.shape[1] < T
+    Bt = Bt.astype(dtype).astype(np.float64)  # the bases the device holds
+    Bf = freq_basis(big.nfreqs).astype(dtype).astype(np.float64) if with_freq else None
+    s = make_solver(big, start, dtype, layout, reg)
+    if with_freq:
+        s.set_gain_basis(Bf)
+    s.set_gain_time_basis(Bt)
+    W = Bf.shape[1] if with_freq else big.nfreqs
+
+    def contract(gg):
+        gg = gg.reshape(T, na, big.nfreqs)
+        return np.einsum("tl,taf,fk->alk", Bt, gg, Bf) if with_freq else np.einsum("tl,taf->alf", Bt, gg)
+
+    tol = TOL[dtype]
+    l2, gy_r, gy_i = s.eval_gain_coeff_grads()
+    assert gy_r.shape == gy_i.shape == (na, Bt.shape[1], W) and gy_r.dtype == np.dtype(dtype)
+    print(f"loss rel {abs(l2 - loss) / abs(loss):.2e}  grad y rel {relnorm(gy_r, contract(gg_r)):.2e} {relnorm(gy_i, contract(gg_i)):.2e}")
+    assert abs(l2 - loss) <= tol["loss"] * abs(loss)
+    assert relnorm(gy_r, contract(gg_r)) <= tol["grad"]
+    assert relnorm(gy_i, contract(gg_i)) <= tol["grad"]
+    # the per-channel entry point keeps returning the per-channel gradient; nothing has moved
+    _, hg_r, hg_i, _, _ = s.eval_grads()
+    assert relnorm(hg_r, gg_r) <= tol["grad"] and relnorm(hg_i, gg_i) <= tol["grad"]
+    y_r, y_i = s.get_gain_coeffs()
+    assert y_r.shape == (na, Bt.shape[1], W) and not y_r.any() and not y_i.any()
+    np.testing.assert_array_equal(s.get_params()[0], np.asarray(start["g_r"], dtype=dtype))
+    s.close()
+
+
+# ---- 2. trajectories ----------------------------------------------------------------------------------------------------
+CASES = {"general": dict(nants=7, nfreqs=40, ntimes=3, layout="stream", kernel_path="auto"),
+         "dense": dict(nants=7, nfreqs=200, ntimes=3, layout="shared", kernel_path="dense")}
+
+
+def gpu_fit(big, start, dtype, Bt, Bf, case, optimizer, reg=False, maxsteps=30, lr=1e-2, launch=None, time_first=False, **run_kw):
+    s = make_solver(big, start, dtype, case["layout"], reg, kernel_path=case["kernel_path"])
+    if launch:
+        s.set_launch_mode(launch)
+    if time_first and Bt is not None:
+        s.set_gain_time_basis(Bt)
+    if Bf is not None:
+        s.set_gain_basis(Bf)
+    if not time_first and Bt is not None:
+        s.set_gain_time_basis(Bt)
+    s.set_optimizer(optimizer, learning_rate=lr)
+    s.run(1, record=False, freeze_model=run_kw.get("freeze_model", False))
+    losses, stopped, nupd = s.run(maxsteps, record=True, **run_kw)
+    which = 1 if run_kw.get("use_min") else 0
+    g_r, g_i, c_r, c_i = s.get_params(which)
+    y_r, y_i = s.get_gain_coeffs(which)
+    s.close()
+    return dict(loss=losses, stopped=stopped, nupd=nupd, g=cplx(g_r, g_i), c_r=c_r, c_i=c_i, y=cplx(y_r, y_i))
+
+
+def check_against(out, ref, big, tol):
+    ref_g, ref_y = cplx(ref["g_r"], ref["g_i"]), cplx(ref["y_r"], ref["y_i"])
+    ref_c_r, ref_c_i = problem.coeffs_from_chunks(big, ref["fg_r"]), problem.coeffs_from_chunks(big, ref["fg_i"])
+    assert len(out["loss"]) == len(ref["loss"])
+    print(f"loss {np.max(np.abs(out['loss'] - ref['loss']) / ref['loss']):.2e}  g {relnorm(out['g'], ref_g):.2e}  y {relnorm(out['y'], ref_y):.2e}  "
+          f"c {relnorm(out['c_r'], ref_c_r):.2e} {relnorm(out['c_i'], ref_c_i):.2e}")
+    np.testing.assert_allclose(out["loss"], ref["loss"], rtol=max(tol, 1e-7) if tol > 1e-8 else tol)
+    assert relnorm(out["g"], ref_g) <= tol
+    assert relnorm(out["y"], ref_y) <= tol
+    assert relnorm(out["c_r"], ref_c_r) <= tol and relnorm(out["c_i"], ref_c_i) <= tol
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("optimizer", ["Adam", "Adamax"])
+@pytest.mark.parametrize("case", ["general", "dense"])
+@pytest.mark.parametrize("reg", [False, True])
+def test_trajectory(dtype, optimizer, case, reg):
+    cs = CASES[case]
+    big, start, ch, fg_r, fg_i = joint_case(ntimes=cs["ntimes"], nants=cs["nants"], nfreqs=cs["nfreqs"], with_sky=reg)
+    Bt = time_basis(cs["ntimes"]).astype(dtype).astype(np.float64)
+    Bf = freq_basis(big.nfreqs).astype(dtype).astype(np.float64)
+    assert Bt.shape[1] == 2 and 1 < Bf.shape[1] < big.nfreqs // 2
+    ref = gamma2_fit(Bt, Bf, start["g_r"], start["g_i"], fg_r, fg_i, ch, 30, optimizer, reg=reg, learning_rate=1e-2)
+    out = gpu_fit(big, start, dtype, Bt, Bf, cs, optimizer, reg=reg, tol=1e-14, time_first=reg)  # (the two setters in either order)
+    tol = TOL[dtype]["traj"]
+    check_against(out, ref, big, tol)
+    # the gains the solver returns are g0 + Bt (x) Bf y of the coefficients it returns; nothing of the correction lies outside the span
+    g0 = cplx(np.asarray(start["g_r"], dtype=dtype), np.asarray(start["g_i"], dtype=dtype))
+    assert relnorm(out["g"], g0 + expand(Bt, out["y"], Bf)) <= tol
+    if dtype == np.float64:
+        assert outside_span(Bt, Bf, out["g"] - g0, cs["nants"]) <= 1e-12 * np.linalg.norm(out["g"])
+    assert np.linalg.norm(out["y"]) > 0
+
+
+# ---- 2b. more than one tile of vectors and of times ---------------------------------------------------------------------
+# Both kernels hold a tile of 8 accumulator vectors per thread and put further tiles into grid.y: T = 19 times are three tiles of the
+# expansion, L = 11 vectors two of the projection, the last tile partial in both.
+MANY = dict(ntimes=19, nvec=11, nants=4, nfreqs=40)
+_many = {}
+
+
+def many_times_case(reg):
+    if reg not in _many:
+        big, start, ch, fg_r, fg_i = joint_case(ntimes=MANY["ntimes"], nants=MANY["nants"], nfreqs=MANY["nfreqs"], with_sky=reg, seed=80)
+        Bt = np.random.default_rng(9).standard_normal((MANY["ntimes"], MANY["nvec"])) / np.sqrt(MANY["ntimes"])  # (not orthogonal)
+        _many[reg] = (big, start, ch, fg_r, fg_i, Bt)
+    return _many[reg]
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("with_freq", [True, False])
+@pytest.mark.parametrize("reg", [False, True])
+def test_projected_gradient_of_several_tiles(dtype, with_freq, reg):
+    big, start, ch, fg_r, fg_i, Bt = many_times_case(reg)
+    T, L, na = MANY["ntimes"], MANY["nvec"], MANY["nants"]
+    a0, a1 = R.ant_inds_from_corr_inds(ch["corr_inds"])
+    priors = R.prior_sums(ch["sky_model_r"], ch["sky_model_i"], ch["wgts"]) if reg else (None, None)
+    loss, gg_r, gg_i, _, _ = R.loss_and_grads(start["g_r"], start["g_i"], fg_r, fg_i, ch["fg_comps"], ch["data_r"], ch["data_i"], ch["wgts"],
+                                              a0, a1, *priors)
+    Bt = Bt.astype(dtype).astype(np.float64)
+    Bf = freq_basis(big.nfreqs).astype(dtype).astype(np.float64) if with_freq else np.eye(big.nfreqs)
+    s = make_solver(big, start, dtype, "stream", reg)
+    s.set_gain_time_basis(Bt)
+    if with_freq:
+        s.set_gain_basis(Bf)
+    contract = lambda gg: np.einsum("tl,taf,fk->alk", Bt, gg.reshape(T, na, big.nfreqs), Bf)  # noqa: E731
+    tol = TOL[dtype]
+    l2, gy_r, gy_i = s.eval_gain_coeff_grads()
+    s.close()
+    assert gy_r.shape == (na, L, Bf.shape[1])
+    print(f"loss rel {abs(l2 - loss) / abs(loss):.2e}  grad y rel {relnorm(gy_r, contract(gg_r)):.2e} {relnorm(gy_i, contract(gg_i)):.2e}")
+    assert abs(l2 - loss) <= tol["loss"] * abs(loss)
+    assert relnorm(gy_r, contract(gg_r)) <= tol["grad"] and relnorm(gy_i, contract(gg_i)) <= tol["grad"]
+    # every vector of every tile got its own sum: no row of the gradient is zero or repeats another
+    flat = gy_r.reshape(na * L, -1)
+    assert np.all(np.linalg.norm(flat, axis=1) > 0) and len(np.unique(flat, axis=0)) == na * L
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("with_freq", [True, False])
+def test_trajectory_of_several_tiles(dtype, with_freq):
+    """12 steps against the restatement, then the same fit replayed from a graph: bit for bit."""
+    big, start, ch, fg_r, fg_i, Bt = many_times_case(True)
+    cs = dict(layout="stream", kernel_path="auto")
+    Bt = Bt.astype(dtype).astype(np.float64)
+    Bf = freq_basis(big.nfreqs).astype(dtype).astype(np.float64) if with_freq else None
+    ref = gamma2_fit(Bt, Bf if with_freq else np.eye(big.nfreqs), start["g_r"], start["g_i"], fg_r, fg_i, ch, 12, "Adam", reg=True, learning_rate=1e-2)
+    out = gpu_fit(big, start, dtype, Bt, Bf, cs, "Adam", reg=True, maxsteps=12, tol=1e-14, launch="kernels")
+    tol = TOL[dtype]["traj"]
+    check_against(out, ref, big, tol)
+    g0 = cplx(np.asarray(start["g_r"], dtype=dtype), np.asarray(start["g_i"], dtype=dtype))
+    assert relnorm(out["g"], g0 + expand(Bt, out["y"], Bf)) <= tol
+    if dtype == np.float64:
+        assert outside_span(Bt, Bf, out["g"] - g0, MANY["nants"]) <= 1e-12 * np.linalg.norm(out["g"])
+    graph = gpu_fit(big, start, dtype, Bt, Bf, cs, "Adam", reg=True, maxsteps=12, tol=1e-14, launch="graph")
+    for k in ("loss", "g", "y", "c_r", "c_i"):
+        np.testing.assert_array_equal(graph[k], out[k], err_msg=k)
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_trajectory_without_a_frequency_basis(dtype):
+    """W = fpad: gains free per channel, smooth in time; against the restatement with ``Bf = I``."""
+    cs = CASES["general"]
+    big, start, ch, fg_r, fg_i = joint_case(ntimes=cs["ntimes"], nants=cs["nants"], nfreqs=cs["nfreqs"], with_sky=True)
+    Bt = time_basis(cs["ntimes"]).astype(dtype).astype(np.float64)
+    ref = gamma2_fit(Bt, np.eye(big.nfreqs), start["g_r"], start["g_i"], fg_r, fg_i, ch, 30, "Adam", reg=True, learning_rate=1e-2)
+    out = gpu_fit(big, start, dtype, Bt, None, cs, "Adam", reg=True, tol=1e-14)
+    assert out["y"].shape == (cs["nants"], Bt.shape[1], big.nfreqs)
+    tol = TOL[dtype]["traj"]
+    check_against(out, ref, big, tol)
+    g0 = cplx(np.asarray(start["g_r"], dtype=dtype), np.asarray(start["g_i"], dtype=dtype))
+    assert relnorm(out["g"], g0 + expand(Bt, out["y"], None)) <= tol
+    if dtype == np.float64:
+        assert outside_span(Bt, None, out["g"] - g0, cs["nants"]) <= 1e-12 * np.linalg.norm(out["g"])
+
+
+# ---- 3. Bt = I ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("case", ["general", "dense"])
+def test_identity_time_basis_is_the_frequency_basis_fit(dtype, case):
+    cs = CASES[case]
+    T, na = cs["ntimes"], cs["nants"]
+    big, start, _, _, _ = joint_case(ntimes=T, nants=na, nfreqs=cs["nfreqs"], with_sky=True)
+    Bf = freq_basis(big.nfreqs)
+    ref = gpu_fit(big, start, dtype, None, Bf, cs, "Adam", reg=True, tol=0.0, use_min=True)
+    out = gpu_fit(big, start, dtype, np.eye(T), Bf, cs, "Adam", reg=True, tol=0.0, use_min=True)
+    y = out["y"].transpose(1, 0, 2).reshape(T * na, -1)  # y[a, t, k] of the joint fit is y[t Na + a, k] of the other
+    tol = 1e-12 if dtype == np.float64 else TOL[dtype]["traj"]
+    np.testing.assert_allclose(out["loss"], ref["loss"], rtol=tol)
+    assert relnorm(out["g"], ref["g"]) <= tol and relnorm(y, ref["y"]) <= tol
+    assert relnorm(out["c_r"], ref["c_r"]) <= tol and relnorm(out["c_i"], ref["c_i"]) <= tol
+    # every product with the identity is exact and a sum of one term and zeros is that term: the two fits are the same numbers
+    for k, a, b in (("loss", out["loss"], ref["loss"]), ("g", out["g"], ref["g"]), ("y", y, ref["y"]), ("c_r", out["c_r"], ref["c_r"])):
+        np.testing.assert_array_equal(a, b, err_msg=k)
+
+
+# ---- 4. loop controls -----------------------------------------------------------------------------------------------------
+def test_loop_controls():
+    """freeze_model, use_min and the tolerance stop with both bases, against the restatement (fp64)."""
+    cs = CASES["general"]
+    big, start, ch, fg_r, fg_i = joint_case(ntimes=cs["ntimes"], nants=cs["nants"], nfreqs=cs["nfreqs"], perturb=False, seed=40)
+    Bt, Bf = time_basis(cs["ntimes"]), freq_basis(big.nfreqs)
+    g0 = cplx(start["g_r"], start["g_i"])
+    args = (Bt, Bf, start["g_r"], start["g_i"], fg_r, fg_i, ch)
+    # tolerance stop: on the same step
+    ref = gamma2_fit(*args, 400, "Adam", tol=1e-6, learning_rate=5e-2)
+    assert 2 <= len(ref["loss"]) < 400
+    out = gpu_fit(big, start, np.float64, Bt, Bf, cs, "Adam", maxsteps=400, lr=5e-2, tol=1e-6)
+    assert out["stopped"] and len(out["loss"]) == len(ref["loss"]) == out["nupd"]
+    assert relnorm(out["g"], cplx(ref["g_r"], ref["g_i"])) <= 1e-8
+    # use_min: the snapshot is y's; the returned gains are g0 + Bt (x) Bf y_snap
+    ref = gamma2_fit(*args, 60, "RMSprop", use_min=True, learning_rate=0.1)
+    assert np.argmin(ref["loss"]) < 59  # (RMSprop at this step size wanders around the minimum: the snapshot is not the last state)
+    out = gpu_fit(big, start, np.float64, Bt, Bf, cs, "RMSprop", maxsteps=60, lr=0.1, use_min=True, tol=1e-14)
+    np.testing.assert_allclose(out["loss"], ref["loss"], rtol=1e-8)
+    assert relnorm(out["y"], cplx(ref["y_r"], ref["y_i"])) <= 1e-8 and relnorm(out["g"], cplx(ref["g_r"], ref["g_i"])) <= 1e-8
+    assert relnorm(out["g"], g0 + expand(Bt, out["y"], Bf)) <= 1e-12
+    assert relnorm(out["c_r"], problem.coeffs_from_chunks(big, ref["fg_r"])) <= 1e-8
+    # freeze_model: gains only
+    ref = gamma2_fit(*args, 20, "Adam", freeze_model=True, learning_rate=5e-2)
+    out = gpu_fit(big, start, np.float64, Bt, Bf, cs, "Adam", maxsteps=20, lr=5e-2, freeze_model=True, tol=1e-14)
+    np.testing.assert_allclose(out["loss"], ref["loss"], rtol=1e-8)
+    assert relnorm(out["g"], cplx(ref["g_r"], ref["g_i"])) <= 1e-8
+    np.testing.assert_array_equal(out["c_r"], start["c_r"])
+
+
+# ---- 5. launch modes --------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("case,reg,with_freq", [("general", False, True), ("general", True, True), ("general", True, False), ("dense", False, True)])
+def test_launch_modes_bit_identical(dtype, case, reg, with_freq):
+    cs = CASES[case]
+    big, start, _, _, _ = joint_case(ntimes=cs["ntimes"], nants=cs["nants"], nfreqs=cs["nfreqs"], with_sky=reg, seed=50)
+    Bt, Bf = time_basis(cs["ntimes"]), freq_basis(big.nfreqs) if with_freq else None
+    runs = {}
+    for mode in ("kernels", "auto", "one_tail", "graph", "kernels"):
+        out = gpu_fit(big, start, dtype, Bt, Bf, cs, "Adam", reg=reg, maxsteps=53, lr=2e-2, launch=mode, use_min=True, tol=0.0)
+        assert len(out["loss"]) == 53 and np.all(np.isfinite(out["loss"])) and out["loss"][-1] < out["loss"][0]
+        if "kernels" in runs:  # (the second "kernels" run: two runs are bitwise equal)
+            for k in ("loss", "g", "y", "c_r", "c_i"):
+                np.testing.assert_array_equal(out[k], runs["kernels"][k], err_msg=f"{mode}: {k}")
+        runs[mode] = out
+
+
+# ---- 6. exchange ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("reg", [False, True])
+@pytest.mark.parametrize("with_freq", [True, False])
+def test_exchange_carries_the_time_projected_gradient(dtype, reg, with_freq):
+    from calamity_amd.solver import HipFitSolver
+
+    cs = CASES["general"]
+    T, na = cs["ntimes"], cs["nants"]
+    big, start, _, _, _ = joint_case(ntimes=T, nants=na, nfreqs=cs["nfreqs"], with_sky=reg)
+    Bt, Bf = time_basis(T), freq_basis(big.nfreqs) if with_freq else None
+    L = Bt.shape[1]
+    fpad = 64  # 40 channels: rows are padded to min(128, next power of two)
+    W = (Bf.shape[1] + 7) // 8 * 8 if with_freq else fpad  # documented: include/calamity_hip.h
+    calls = []
+    s = HipFitSolver(dtype=dtype)
+    s.set_exchange_hook(lambda arr, op: calls.append((arr.dtype.str, int(arr.size))), 0, 1)
+    s.set_problem(big, layout="stream", kernel_path="general")
+    s.set_params(start["g_r"], start["g_i"], start["c_r"], start["c_i"])
+    if reg:
+        s.set_regularization("sum", np.sum(big.sky_r * big.wgts), np.sum(big.sky_i * big.wgts))
+    if with_freq:
+        s.set_gain_basis(Bf)
+    s.set_gain_time_basis(Bt)
+    s.set_optimizer("Adam", learning_rate=1e-2)
+    real = np.dtype(dtype).str
+    planes = 3 if reg else 1
+    del calls[:]
+    s.run(1, record=False)
+    losses, _, _ = s.run(5, record=True, tol=0.0)
+    grad_calls = [c for c in calls if c[0] == real and c[1] > 4]
+    assert [c[1] for c in grad_calls] == [planes * 2 * na * L * W] * 6, calls
+    assert planes * 2 * na * L * W < planes * 2 * big.nants * W  # fewer numbers than the fit without the time basis exchanges
+    # per step: the gradient planes and the four loss scalars, nothing else.  (With the "sum" regulariser the scalars go twice: the times
+    # share basis tiles, and that path needs S of the whole fit before its gradient pass -- DESIGN 3.1d, as without a time basis.)
+    scalars = [c for c in calls if c not in grad_calls]
+    assert scalars == [(np.dtype(np.float64).str, 4)] * (12 if reg else 6) and len(calls) == len(grad_calls) + len(scalars)
+    # ... and the one-rank exchange changes no number
+    ref = gpu_fit(big, start, dtype, Bt, Bf, cs, "Adam", reg=reg, maxsteps=5, launch="kernels", tol=0.0)
+    np.testing.assert_array_equal(losses, ref["loss"])
+    s.close()
+
+
+@pytest.mark.parametrize("reg", [False, True])
+def test_two_ranks_on_one_gpu_equal_one_rank(reg):
+    """Two workers on one GPU share the fitting groups of every time of the joint problem and exchange the time-projected planes
+    through the library's hook (host memory between two threads: batched._HostExchange) -- against one worker, fp64 1e-10.
+    The two ranks are threads of this process, as in tests/test_gpu_gain_basis.py; the form of tests/test_gpu_exchange_hook.py,
+    two child PROCESSES that reduce through the hook, is not covered with a time basis."""
+    T, na, nfreqs = 4, 7, 40
+    cache, parts = {}, []
+    for t in range(T):
+        p, _, start = synthetic.make_problem(na, nfreqs, f0=150e6, df=400e3, seed=60, data_seed=61 + t, with_sky=True, operator_cache=cache)
+        parts.append((p, start))
+    prob = parts[0][0]
+    cat = lambda name: np.concatenate([getattr(p, name) for p, _ in parts])  # noqa: E731
+    rng = np.random.default_rng(7)
+    g_r, g_i = 1.0 + 0.05 * rng.standard_normal((T * na, nfreqs)), 0.05 * rng.standard_normal((T * na, nfreqs))
+    c_r, c_i = np.concatenate([s["c_r"] for _, s in parts]), np.concatenate([s["c_i"] for _, s in parts])
+    Bt, Bf = time_basis(T), freq_basis(nfreqs)
+    assert 1 < Bt.shape[1] < T
+    outs = []
+    for devices in ([0], [0, 0]):
+        f = SliceBatchFitter(prob, T, dtype=np.float64, layout="stream", devices=devices, kernel_path="general", joint=True)
+        try:
+            f.set_data(cat("data_r"), cat("data_i"), cat("wgts"))
+            f.set_params(g_r, g_i, c_r, c_i)
+            f.set_gain_basis(Bf)
+            f.set_gain_time_basis(Bt)
+            if reg:
+                f.set_regularization("sum", float(np.sum(cat("sky_r") * cat("wgts"))), float(np.sum(cat("sky_i") * cat("wgts"))))
+            else:
+                f.set_regularization(None)
+            f.set_optimizer("Adam", learning_rate=1e-2)
+            f.run_slices(1, record=False)
+            res = f.run_slices(25, record=True, tol=0.0)
+            assert len(res) == 1 and len(res[0][0]) == 25
+            outs.append((res[0][0], f.get_params(0), f.get_gain_coeffs(0)))
+        finally:
+            f.close()
+    (l1, p1, y1), (l2, p2, y2) = outs
+    assert y1[0].shape == (na, Bt.shape[1], Bf.shape[1]) and np.any(y1[0])
+    np.testing.assert_allclose(l2, l1, rtol=1e-10)
+    for a, b in list(zip(p2, p1)) + list(zip(y2, y1)):
+        assert relnorm(a, b) <= 1e-10
+
+
+# ---- 7. refusals, detaching -------------------------------------------------------------------------------------------------
+def test_refusals():
+    cs = CASES["general"]
+    T = cs["ntimes"]
+    big, start, _, _, _ = joint_case(ntimes=T, nants=cs["nants"], nfreqs=cs["nfreqs"])
+    Bt = time_basis(T)
+    s = make_solver(big, start, np.float64)
+
+    def refused(code, match, fn, *a, **kw):
+        with pytest.raises(_lib.CalamityHipError, match=match) as err:
+            fn(*a, **kw)
+        assert err.value.code == code
+
+    INVALID, UNSUPPORTED = -1, -5
+    refused(INVALID, "not a multiple of ntimes", s.set_gain_time_basis, np.ones((4, 2)))  # 21 antenna rows, 4 times
+    refused(INVALID, "nvec_t = 4", s.set_gain_time_basis, np.ones((T, T + 1)))
+    refused(INVALID, "non-finite", s.set_gain_time_basis, np.full((T, 2), np.nan))
+    refused(INVALID, "non-finite", s.set_gain_time_basis, np.array([[1.0, 0.0], [np.inf, 1.0], [0.0, 1.0]]))
+    for bad in (np.ones(T), np.ones((T, 2)) * 1j, np.ones((T, 0))):
+        with pytest.raises(ValueError):
+            s.set_gain_time_basis(bad)
+    with pytest.raises(_lib.CalamityHipError, match="no gain basis"):  # nothing was set by the refused calls
+        s.get_gain_coeffs()
+    s.get_moments()
+    # LAMB at either entry
+    s.set_optimizer("LAMB")
+    refused(UNSUPPORTED, "LAMB", s.set_gain_time_basis, Bt)
+    s.set_optimizer("Adam", learning_rate=1e-2)
+    s.set_gain_time_basis(Bt)
+    refused(UNSUPPORTED, "LAMB", s.set_optimizer, "LAMB")
+    # checkpoint / resume
+    refused(UNSUPPORTED, "time basis is not supported", s.get_moments)
+    m = {k: (np.zeros((big.nants, big.nfreqs)) if k[0] == "g" else np.zeros(big.ncoeffs)) for k in ("gm_r", "gm_i", "gv_r", "gv_i", "cm_r", "cm_i", "cv_r", "cv_i")}
+    refused(UNSUPPORTED, "time basis is not supported", s.set_moments, t=0, **m)
+    s.close()
+    # slices that stop on their own contradict shared variables
+    parts = [synthetic.make_problem(5, 40, f0=150e6, df=400e3, seed=3, data_seed=4 + t)[::2] for t in range(2)]
+    sliced, st = distributed.batch_time_slices(parts, per_slice=True)
+    s = make_solver(sliced, st, np.float64)
+    refused(UNSUPPORTED, "time slices", s.set_gain_time_basis, np.eye(2))
+    s.close()
+    # before set_problem
+    from calamity_amd.solver import HipFitSolver
+
+    s = HipFitSolver(dtype=np.float64)
+    with pytest.raises(_lib.CalamityHipError, match="before set_problem"):
+        s.set_gain_time_basis(Bt)
+    s.close()
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_detach_and_rebase(dtype):
+    cs = CASES["general"]
+    T, na = cs["ntimes"], cs["nants"]
+    big, start, _, _, _ = joint_case(ntimes=T, nants=na, nfreqs=cs["nfreqs"], seed=70)
+    Bt, Bf = time_basis(T), freq_basis(big.nfreqs)
+
+    def fit(s):
+        s.set_params(start["g_r"], start["g_i"], start["c_r"], start["c_i"])
+        s.set_optimizer("Adam", learning_rate=1e-2)
+        s.run(1, record=False)
+        losses, _, _ = s.run(40, record=True, tol=0.0, use_min=True)
+        return [losses] + list(s.get_params(0)) + list(s.get_params(1))
+
+    plain = make_solver(big, start, dtype)
+    want_plain = fit(plain)
+    plain.set_gain_basis(Bf)
+    want_freq = fit(plain) + list(plain.get_gain_coeffs(0))
+    plain.close()
+    s = make_solver(big, start, dtype)
+    s.set_gain_basis(Bf)
+    s.set_gain_time_basis(Bt)
+    s.set_optimizer("Adam", learning_rate=1e-2)
+    s.run(7, record=True, use_min=True)
+    assert s.get_gain_coeffs()[0].shape == (na, Bt.shape[1], Bf.shape[1])
+    # the time basis alone goes: the frequency-basis fit is left, bit for bit
+    s.set_gain_time_basis(None)
+    assert s.get_gain_coeffs()[0].shape == (big.nants, Bf.shape[1]) and not np.any(s.get_gain_coeffs()[0])
+    for a, b in zip(fit(s) + list(s.get_gain_coeffs(0)), want_freq):
+        np.testing.assert_array_equal(a, b)
+    # the frequency basis alone goes: y is [Na, L, nfreqs]
+    s.set_gain_time_basis(Bt)
+    s.set_gain_basis(None)
+    assert s.get_gain_coeffs()[0].shape == (na, Bt.shape[1], big.nfreqs)
+    s.set_optimizer("Adam", learning_rate=1e-2)
+    s.run(3, record=False)
+    # both gone: the per-channel fit, bit for bit, and the moments can be read again
+    s.set_gain_time_basis(None)
+    with pytest.raises(_lib.CalamityHipError, match="no gain basis"):
+        s.get_gain_coeffs()
+    for a, b in zip(fit(s), want_plain):
+        np.testing.assert_array_equal(a, b)
+    s.get_moments()
+    # set_params with gains while the bases are set: g0 := those gains, y := 0
+    s.set_gain_time_basis(Bt)
+    s.set_gain_basis(Bf)
+    s.set_optimizer("Adam", learning_rate=1e-2)
+    s.run(5, record=False)
+    assert np.any(s.get_gain_coeffs()[0])
+    s.set_params(g_r=start["g_r"], g_i=start["g_i"])
+    assert not np.any(s.get_gain_coeffs()[0]) and not np.any(s.get_gain_coeffs()[1])
+    np.testing.assert_array_equal(s.get_params()[0], np.asarray(start["g_r"], dtype=dtype))
+    # a new problem detaches both
+    s.set_problem(big, layout="stream")
+    with pytest.raises(_lib.CalamityHipError, match="no gain basis"):
+        s.get_gain_coeffs()
+    s.close()
+
+
+# ---- 8. recovery ------------------------------------------------------------------------------------------------------------
+def test_recovery_on_the_device():
+    """The inputs of tests/test_gain_time_basis_host.py::test_joint_fit_recovers_smooth_gains_better: the joint fit's gain-product
+    error is at most 0.8 of the per-time fit's -- of the restatement first, then of the fp64 and fp32 device fits."""
+    case = recovery_case()
+    big, start, Bt, Bf = case["big"], case["start"], case["Bt"], case["Bf"]
+    ref_per_time, ref_joint = restated_recovery(case)
+    print(f"restatement: per-time {ref_per_time:.4f}, joint {ref_joint:.4f}, ratio {ref_joint / ref_per_time:.3f}")
+    assert ref_joint <= 0.8 * ref_per_time
+    cs = dict(layout="stream", kernel_path="auto")
+    for dtype in (np.float64, np.float32):
+        errs = []
+        for bt in (np.eye(Bt.shape[0]), Bt):
+            out = gpu_fit(big, start, dtype, bt, Bf, cs, "Adam", maxsteps=300, lr=1e-2, tol=0.0, freeze_model=True)
+            errs.append(product_error(case, out["g"]))
+        print(f"{np.dtype(dtype).name}: per-time {errs[0]:.4f}, joint {errs[1]:.4f}, ratio {errs[1] / errs[0]:.3f}")
+        assert errs[1] <= 0.8 * errs[0]
+        if dtype == np.float64:
+            assert abs(errs[1] - ref_joint) <= TOL[dtype]["traj"] * ref_joint and abs(errs[0] - ref_per_time) <= TOL[dtype]["traj"] * ref_per_time
+
+
+# ---- 9. drop-in -------------------------------------------------------------------------------------------------------------
+# synthetic.make_uvdata's times are two days apart; with so few samples the eigenvalue cut keeps many sequences: 3 of 6 at this scale
+SCALE_S = 100.0 * 86400.0
+
+
+def smooth_uvdata(seed=7, nants=7, nfreqs=64, ntimes=6, sigma=0.05, noise=1e-4, skip=None):
+    """synthetic.make_uvdata's array (its gains are unity) with gains multiplied in that ARE smooth in both axes:
+    ``1 + Bt (x) Bf y_true`` with the 60-ns frequency basis and the time basis of twice ``SCALE_S`` (inside what the fits below
+    allow).  ``skip``: a time index whose samples are all flagged."""
+    uvd, sky, _ = synthetic.make_uvdata(nants=nants, nfreqs=nfreqs, ntimes=ntimes, seed=seed, redundant=True, flag_frac=0.02)
+    rng = np.random.default_rng(seed + 1)
+    freqs = np.asarray(uvd.freq_array, dtype=np.float64).ravel()
+    times = np.unique(uvd.time_array)
+    Bf = np.array(modeling.gain_dpss_basis(freqs, 60.0))
+    Bt = modeling.gain_time_dpss_basis(times, 2.0 * SCALE_S)
+    ants = np.asarray(cal_utils.blank_uvcal_from_uvdata(uvd).ant_array).tolist()
+    y = sigma * (rng.standard_normal((len(ants), Bt.shape[1], Bf.shape[1])) + 1j * rng.standard_normal((len(ants), Bt.shape[1], Bf.shape[1])))
+    g = 1.0 + np.einsum("tl,alk,fk->taf", Bt, y, Bf)
+    vis = uvcompat.vis3(uvd.data_array)
+    amp = np.sqrt(np.mean(np.abs(vis) ** 2))
+    for k, t in enumerate(times):
+        sel = np.where(np.isclose(uvd.time_array, t, atol=1e-7, rtol=0.0))[0]
+        for n in sel:
+            i, j = ants.index(uvd.ant_1_array[n]), ants.index(uvd.ant_2_array[n])
+            vis[n, :, 0] *= g[k, i] * np.conj(g[k, j])
+        vis[sel, :, 0] += amp * noise * (rng.standard_normal((len(sel), nfreqs)) + 1j * rng.standard_normal((len(sel), nfreqs)))
+        if k == skip:
+            uvd.flag_array[sel] = True
+    return uvd, freqs, times
+
+
+def restated_quality(uvd, Bt, Bf, maxsteps, dtype=np.float64):
+    """rms(data) / rms(resid) of the restatement's joint fit on the tensors the drop-in call builds from ``uvd`` (every time fitted,
+    unity start, coefficients ``A^T (d mask)``, Adam at 1e-2, the "sum" regulariser of the joint fit with the data as the sky model)."""
+    comps = modeling.yield_pbl_dpss_model_comps(uvd, offset=2.0 / 0.3, min_dly=2.0 / 0.3)
+    ants_map = {ant: i for i, ant in enumerate(np.asarray(cal_utils.blank_uvcal_from_uvdata(uvd).ant_array).tolist())}
+    prob, _ = calibration.tensorize_fg_model_comps_dict(fg_model_comps_dict=comps, ants_map=ants_map, dtype=dtype, nfreqs=uvd.Nfreqs)
+    times, pol = np.unique(uvd.time_array), uvd.get_pols()[0]
+    d_r, d_i, w = [], [], []
+    for t in times:
+        bltsel = np.isclose(uvd.time_array, t, atol=1e-7, rtol=0.0)
+        _, rms = calibration._slice_stats(uvd, bltsel, 0)
+        a, b, c = calibration._tensorize_flat(uvd, prob, ants_map, pol, t, data_scale_factor=rms, dtype=dtype)
+        d_r.append(a), d_i.append(b), w.append(c)
+    big, _, _ = replicate_slices(prob, len(times))
+    big.nslices = 1
+    big.data_r, big.data_i, big.wgts = np.concatenate(d_r), np.concatenate(d_i), np.concatenate(w)
+    big.sky_r, big.sky_i = big.data_r.copy(), big.data_i.copy()
+    mask = (big.wgts > 0).astype(np.float64)
+    coff = big.grp_coff
+    c0 = np.zeros(big.ncoeffs, dtype=np.complex128)
+    assert np.all(np.diff(big.grp_bl_start) == 1)
+    for n, u in enumerate(big.grp_basis):
+        c0[coff[n]:coff[n + 1]] = big.basis[u].T @ ((big.data_r[n] + 1j * big.data_i[n]) * mask[n])
+    start = dict(g_r=np.ones((big.nants, big.nfreqs)), g_i=np.zeros((big.nants, big.nfreqs)), c_r=np.ascontiguousarray(c0.real),
+                 c_i=np.ascontiguousarray(c0.imag))
+    ch, fg_r, fg_i = oracle_inputs(big, start)
+    out = gamma2_fit(Bt, Bf, start["g_r"], start["g_i"], fg_r, fg_i, ch, maxsteps, "Adam", tol=0.0, reg=True, learning_rate=1e-2)
+    g = cplx(out["g_r"], out["g_i"])
+    c = cplx(problem.coeffs_from_chunks(big, out["fg_r"]), problem.coeffs_from_chunks(big, out["fg_i"]))
+    m = np.stack([g[big.bl_ant0[n]] * np.conj(g[big.bl_ant1[n]]) * (big.basis[u] @ c[coff[n]:coff[n + 1]]) for n, u in enumerate(big.grp_basis)])
+    sel = big.wgts > 0
+    d = big.data_r + 1j * big.data_i
+    return np.sqrt(np.mean(np.abs(d[sel]) ** 2)) / np.sqrt(np.mean(np.abs((d - m)[sel]) ** 2))
+
+
+def test_dropin_joint_fit_over_times(tmp_path, monkeypatch):
+    maxsteps = 400
+    uvd, freqs, times = smooth_uvdata()
+    Bf = np.array(modeling.gain_dpss_basis(freqs, 100.0))
+    Bt = modeling.gain_time_dpss_basis(times, SCALE_S)
+    assert 1 < Bt.shape[1] < len(times)
+    q_ref = restated_quality(uvd, Bt, Bf, maxsteps)
+    print(f"restatement: rms(data) / rms(resid) = {q_ref:.1f}")
+    assert q_ref >= 100.0
+    kw = dict(min_dly=2.0 / 0.3, offset=2.0 / 0.3, sky_model=None, maxsteps=maxsteps, tol=0.0, correct_resid=False, correct_model=False,
+              optimizer="Adam", learning_rate=1e-2, dtype=np.float64, model_regularization="sum", gains=None)
+    model, resid, gains, hist = calibration.calibrate_and_model_dpss(uvdata=uvd, gain_time_scale=SCALE_S, gain_max_dly=100.0, **kw)
+    g = uvcompat.gain4(gains.gain_array)[:, :, :, 0]  # [ants, freqs, times]
+    na = g.shape[0]
+    d = np.transpose(g, (2, 0, 1)).reshape(len(times) * na, -1) - 1.0
+    assert np.abs(d).max() > 1e-2
+    # (here and below the bound is relative to the CORRECTION g - g_in, what the fit found, not to the gains, which are 20 times larger)
+    assert outside_span(Bt, Bf, d, na) <= 1e-10 * np.linalg.norm(d)
+    unflagged = ~uvcompat.vis3(uvd.flag_array)[:, :, 0]
+    rms = lambda x: np.sqrt(np.mean(np.abs(uvcompat.vis3(x.data_array)[:, :, 0][unflagged]) ** 2))  # noqa: E731
+    print(f"device: rms(data) / rms(resid) = {rms(uvd) / rms(resid):.1f}")
+    assert rms(uvd) >= 100.0 * rms(resid)
+    assert sorted(hist[0]) == list(range(len(times)))
+    for ti in hist[0]:
+        assert len(hist[0][ti]["loss"]) == maxsteps and hist[0][ti]["loss"] == hist[0][0]["loss"]
+    # the basis given as an array is the same call
+    given = calibration.calibrate_and_model_dpss(uvdata=uvd, gain_time_basis=Bt, gain_max_dly=100.0, **kw)
+    np.testing.assert_array_equal(given[2].gain_array, gains.gain_array)
+    # a skipped time is flagged and left out of the joint fit: the gains of the others lie in the span of Bt's rows at THEIR times
+    skip = 2
+    uvs, _, _ = smooth_uvdata(skip=skip)
+    _, _, gs, hs = calibration.calibrate_and_model_dpss(uvdata=uvs, gain_time_scale=SCALE_S, gain_max_dly=100.0, **kw)
+    fitted = [t for t in range(len(times)) if t != skip]
+    assert sorted(hs[0]) == fitted and all(hs[0][t]["loss"] == hs[0][fitted[0]]["loss"] for t in fitted)
+    gflags = uvcompat.gain4(gs.flag_array)[:, :, :, 0]
+    assert np.all(gflags[:, :, skip]) and not np.any(gflags[:, :, fitted])
+    ds = np.transpose(uvcompat.gain4(gs.gain_array)[:, :, fitted, 0], (2, 0, 1)).reshape(len(fitted) * na, -1) - 1.0
+    assert np.abs(ds).max() > 1e-2 and outside_span(Bt[fitted], Bf, ds, na) <= 1e-10 * np.linalg.norm(ds)
+    # a basis alone: free per channel, smooth in time
+    _, _, gt, _ = calibration.calibrate_and_model_dpss(uvdata=uvd, gain_time_scale=SCALE_S, **dict(kw, maxsteps=50))
+    dt = np.transpose(uvcompat.gain4(gt.gain_array)[:, :, :, 0], (2, 0, 1)).reshape(len(times) * na, -1) - 1.0
+    assert outside_span(Bt, None, dt, na) <= 1e-10 * np.linalg.norm(dt) and outside_span(Bt, Bf, dt, na) > 1e-6 * np.linalg.norm(dt)
+
+
+def test_dropin_one_time_equals_the_frequency_basis_call():
+    uvd, _, _ = smooth_uvdata(ntimes=1)
+    kw = dict(min_dly=2.0 / 0.3, offset=2.0 / 0.3, uvdata=uvd, sky_model=None, maxsteps=200, tol=3e-9, correct_resid=True, optimizer="Adam",
+              learning_rate=1e-2, dtype=np.float64, model_regularization="sum", use_min=True, gains=None, gain_max_dly=100.0)
+    (m1, r1, g1, h1), (m2, r2, g2, h2) = calibration.calibrate_and_model_dpss(**kw), calibration.calibrate_and_model_dpss(gain_time_scale=600.0, **kw)
+    np.testing.assert_allclose(np.asarray(h2[0][0]["loss"]), np.asarray(h1[0][0]["loss"]), rtol=1e-10)
+    for a, b, rtol in ((m2.data_array, m1.data_array, 1e-10), (g2.gain_array, g1.gain_array, 1e-10), (r2.data_array, r1.data_array, 1e-10)):
+        print(f"one time against the frequency-basis call: {np.linalg.norm(a - b) / np.linalg.norm(b):.2e}")
+        assert np.linalg.norm(a - b) <= rtol * np.linalg.norm(b)
+    assert np.abs(g1.gain_array - 1.0).max() > 1e-3
+
+
+def test_command_line_round_trip(tmp_path, monkeypatch):
+    uvd, freqs, times = smooth_uvdata(ntimes=4)
+    data = str(tmp_path / "data.uvh5")
+    uvd.write_uvh5(data)
+    outs = [str(tmp_path / n) for n in ("resid.uvh5", "model.uvh5", "gains.calfits")]
+    monkeypatch.setattr(sys, "argv", [sys.argv[0], "--input_data_files", data, "--resid_outfilename", outs[0], "--model_outfilename", outs[1],
+                                      "--gain_outfilename", outs[2], "--precision", "64", "--maxsteps", "100", "--optimizer", "Adam",
+                                      "--gain_max_dly", "100", "--gain_time_scale", str(SCALE_S), "--model_regularization", "sum",
+                                      "--min_dly", str(2.0 / 0.3), "--offset", str(2.0 / 0.3)])
+    args = calibration.dpss_fit_argparser().parse_args()
+    assert args.gain_time_scale == SCALE_S
+    cli = calibration.read_calibrate_and_model_dpss(**vars(args))
+    assert cli[3]["calibration_kwargs"]["gain_time_scale"] == SCALE_S and cli[3]["calibration_kwargs"]["gain_max_dly"] == 100.0
+    api = calibration.read_calibrate_and_model_dpss(**dict(vars(args), input_data_files=copy.deepcopy(uvd), resid_outfilename=None,
+                                                           model_outfilename=None, gain_outfilename=None))
+    written = calfits.read_calfits(outs[2]).gain_array
+    assert np.array_equal(written, cli[2].gain_array)
+    assert np.linalg.norm(api[2].gain_array - written) <= 1e-10 * np.linalg.norm(written)
+    Bt, Bf = modeling.gain_time_dpss_basis(times, SCALE_S), np.array(modeling.gain_dpss_basis(freqs, 100.0))
+    g = uvcompat.gain4(written)[:, :, :, 0]
+    d = np.transpose(g, (2, 0, 1)).reshape(len(times) * g.shape[0], -1) - 1.0
+    assert np.abs(d).max() > 1e-3 and outside_span(Bt, Bf, d, g.shape[0]) <= 1e-10 * np.linalg.norm(d)
