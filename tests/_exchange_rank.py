@@ -17,6 +17,20 @@ def build_case(name):
     from calamity_amd import synthetic
 
     reg = name.endswith("_sum")
+    if name.startswith("general_tbasis"):
+        # T = 4 times of 7 antennas at 40 channels as ONE fit (antenna a at time t is row t * 7 + a), the problem of
+        # tests/test_gain_time_basis_host.py: joint_case -- built here: a rank imports no test module
+        from calamity_amd import distributed as D
+
+        cache, parts = {}, []
+        for t in range(len(TBASIS_TIMES)):
+            p, _, start = synthetic.make_problem(7, 40, f0=150e6, df=400e3, seed=60, data_seed=61 + t, with_sky=reg, operator_cache=cache)
+            parts.append((p, start))
+        big, start = D.batch_time_slices(parts, per_slice=False)
+        rng = np.random.default_rng(7)
+        start["g_r"] = 1.0 + 0.05 * rng.standard_normal((big.nants, big.nfreqs))
+        start["g_i"] = 0.05 * rng.standard_normal((big.nants, big.nfreqs))
+        return big, start, None, dict(layout="stream", kernel_path="general"), dict(nsteps=12, tol=0.0), reg
     if name.startswith("fallback"):
         # 70 antennas = 2415 baselines: rank 0's share (2100) is large enough for the dense kernels, rank 1's (315) is not
         p, _, start = synthetic.make_problem(70, 128, f0=150e6, df=400e3, seed=4, with_sky=reg)
@@ -31,11 +45,25 @@ def build_case(name):
     return p, start, None, dict(layout="shared", kernel_path=path), run, reg
 
 
+TBASIS_TIMES = 2458101.25 + np.arange(4) * 10.7 / 86400.0  # (the first four of tests/test_gain_time_basis_host.py: TIMES_60)
+
+
+def case_bases(name, p):
+    """(frequency basis or None, time basis or None) of a case: the 100 ns DPSS basis of its channels for "gbasis" and "tbasis", the
+    400 s DPSS basis of its four times for "tbasis"."""
+    from calamity_amd import modeling
+
+    if "_gbasis" not in name and "_tbasis" not in name:
+        return None, None
+    Bf = np.array(modeling.gain_dpss_basis(150e6 + 400e3 * np.arange(p.nfreqs), 100.0))
+    return Bf, (np.array(modeling.gain_time_dpss_basis(TBASIS_TIMES, 400.0)) if "_tbasis" in name else None)
+
+
 def priors(p):
     return float(np.sum(p.sky_r * p.wgts)), float(np.sum(p.sky_i * p.wgts))
 
 
-def fit(sub, start, opts, run, reg_priors, hook=None, rank=0, world=1):
+def fit(sub, start, opts, run, reg_priors, hook=None, rank=0, world=1, bases=(None, None)):
     from calamity_amd.solver import HipFitSolver
 
     s = HipFitSolver(dtype=np.float64)
@@ -45,13 +73,19 @@ def fit(sub, start, opts, run, reg_priors, hook=None, rank=0, world=1):
     s.set_params(start["g_r"], start["g_i"], start["c_r"], start["c_i"])
     if reg_priors is not None:
         s.set_regularization("sum", *reg_priors)
+    if bases[0] is not None:
+        s.set_gain_basis(bases[0])
+    if bases[1] is not None:
+        s.set_gain_time_basis(bases[1])
     s.set_optimizer("Adam", learning_rate=2e-2)
     s.run(1, record=False)
     losses, stopped, nupd = s.run(run["nsteps"], record=True, tol=run["tol"])
     g_r, g_i, c_r, c_i = s.get_params()
-    path = s.timing_get()["kernel_path"]
+    out = dict(losses=losses, stopped=stopped, nupd=nupd, g_r=g_r, g_i=g_i, c_r=c_r, c_i=c_i, path=s.timing_get()["kernel_path"])
+    if bases[0] is not None or bases[1] is not None:
+        out["y_r"], out["y_i"] = s.get_gain_coeffs()
     s.close()
-    return dict(losses=losses, stopped=stopped, nupd=nupd, g_r=g_r, g_i=g_i, c_r=c_r, c_i=c_i, path=path)
+    return out
 
 
 def fit_slices(case_data, sub, rows, cidx, dtype, hook=None, rank=0, world=1):
@@ -125,7 +159,7 @@ def main():
             sub, sub_start = D.shard_problem(p, start, args.rank, args.world)
         else:
             sub, sub_start = D.select_groups(p, start, groups[args.rank])
-        out = fit(sub, sub_start, opts, run, priors(p) if reg else None, hook=all_reduce, rank=args.rank, world=args.world)
+        out = fit(sub, sub_start, opts, run, priors(p) if reg else None, hook=all_reduce, rank=args.rank, world=args.world, bases=case_bases(args.case, p))
     np.savez(args.out, ncalls=len(calls), call_sizes=np.asarray([c[1] for c in calls]), call_ops=np.asarray([c[2] for c in calls]),
              call_dtypes=np.asarray([c[0] for c in calls]), **{k: np.asarray(v) for k, v in out.items()})
     dist.barrier()

@@ -350,8 +350,8 @@ def test_exchange_carries_the_time_projected_gradient(dtype, reg, with_freq):
 def test_two_ranks_on_one_gpu_equal_one_rank(reg):
     """Two workers on one GPU share the fitting groups of every time of the joint problem and exchange the time-projected planes
     through the library's hook (host memory between two threads: batched._HostExchange) -- against one worker, fp64 1e-10.
-    The two ranks are threads of this process, as in tests/test_gpu_gain_basis.py; the form of tests/test_gpu_exchange_hook.py,
-    two child PROCESSES that reduce through the hook, is not covered with a time basis."""
+    The two ranks are threads of this process, as in tests/test_gpu_gain_basis.py; two child PROCESSES that reduce through the hook
+    are tests/test_gpu_exchange_hook.py::test_two_ranks_with_a_gain_basis_equal_the_single_solver_fit (case general_tbasis_sum)."""
     T, na, nfreqs = 4, 7, 40
     cache, parts = {}, []
     for t in range(T):
