@@ -259,6 +259,20 @@ class SliceBatchFitter:
             m_i[self.rows[r]] = o[1]
         return m_r, m_i
 
+    def fit_quality(self, g_r=None, g_i=None):
+        """``HipFitSolver.fit_quality`` on the global arrays: ``chisq_ant``, ``wsum_ant`` ``[nt * nants, nfreqs]`` (with several
+        workers the library has summed them over the workers: worker 0's), ``chisq_bl``, ``wsum_bl`` ``[nt * nbls]`` put back into
+        the global slice-major row order like the rows of ``model()``."""
+        outs = self._each(lambda r, s: s.fit_quality(g_r, g_i))
+        if self.nworkers == 1:
+            return outs[0]
+        res = dict(chisq_ant=outs[0]["chisq_ant"], wsum_ant=outs[0]["wsum_ant"],
+                   chisq_bl=np.empty(self.nbls, dtype=np.float64), wsum_bl=np.empty(self.nbls, dtype=np.float64))
+        for r, o in enumerate(outs):
+            res["chisq_bl"][self.rows[r]] = o["chisq_bl"]
+            res["wsum_bl"][self.rows[r]] = o["wsum_bl"]
+        return res
+
     def set_regularization(self, mode=None, prior_r=None, prior_i=None):
         if mode == "sum":
             self._each(lambda r, s: s.set_regularization("sum", np.asarray(prior_r, dtype=np.float64), np.asarray(prior_i, dtype=np.float64)))

@@ -776,6 +776,35 @@ def flag_poltime(data_object, time, polarization):
         raise ValueError("only supports data_object that is UVCal or UVData.")
 
 
+def fit_quality_arrays(q, rms=1.0):
+    """The sums of ``HipFitSolver.fit_quality`` (solver units: the data divided by ``rms``, the slice's ``data_scale_factor``) as
+    weighted mean squared residuals in the data's units: ``(per_antenna [nants, nfreqs], total [nfreqs], per_baseline [nbls])``,
+    ``rms^2 chisq / wsum`` each (the total: both sums taken over the antennas first), 0 where the sum of weights is 0."""
+    def ratio(c, w):
+        c, w = np.asarray(c, dtype=np.float64), np.asarray(w, dtype=np.float64)
+        return float(rms) ** 2 * np.divide(c, w, out=np.zeros_like(c), where=w != 0)
+
+    return (ratio(q["chisq_ant"], q["wsum_ant"]), ratio(np.sum(q["chisq_ant"], axis=0), np.sum(q["wsum_ant"], axis=0)),
+            ratio(q["chisq_bl"], q["wsum_bl"]))
+
+
+def insert_fit_quality(uvcal, hist, time, polarization, q, rms, prob):
+    """Write one (polarization, time) slice's fit quality (``fit_quality_arrays``) into ``uvcal.quality_array[a, f, t, pol]`` and
+    ``uvcal.total_quality_array[f, t, pol]`` (``(Nfreqs, Ntimes, Njones)``, created when ``None``) and, as
+    ``hist["chisq_per_baseline"]``, a dict ``{(ant0, ant1): value}`` with antenna NUMBERS, one entry per baseline row of ``prob``."""
+    per_ant, total, per_bl = fit_quality_arrays(q, rms)
+    polnum = np.where(np.asarray(uvcal.jones_array) == polstr2num(polarization, x_orientation=uvcal.x_orientation))[0][0]
+    gindt = np.where(np.isclose(uvcal.time_array, time, atol=1e-7, rtol=0.0))[0][0]
+    gain4(uvcal.quality_array)[:, :, gindt, polnum] = per_ant
+    if getattr(uvcal, "total_quality_array", None) is None:
+        shape = gain4(uvcal.quality_array).shape
+        uvcal.total_quality_array = np.zeros(shape[1:], dtype=np.float64)
+    tot = uvcal.total_quality_array
+    (tot[0] if np.ndim(tot) == 4 else tot)[:, gindt, polnum] = total
+    ants = np.asarray(uvcal.ant_array)
+    hist["chisq_per_baseline"] = {(int(ants[i]), int(ants[j])): float(v) for i, j, v in zip(prob.bl_ant0, prob.bl_ant1, per_bl)}
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # orchestration: calibration.py:963-1331, :1503-1584
 # ------------------------------------------------------------------------------------------------------------------
@@ -815,6 +844,7 @@ def calibrate_and_model_tensor(
     gain_max_dly=None,
     gain_time_basis=None,
     gain_time_scale=None,
+    fit_quality=False,
     **opt_kwargs,
 ):
     """Simultaneous calibration and foreground fitting -- calibration.py:963-1331, same arguments, defaults and
@@ -857,6 +887,15 @@ def calibrate_and_model_tensor(
       of times (the times share variables: one batch, whose device memory is that of the same times batched -- ``_auto_batch``'s
       sizing does not apply, ``gpu_memory_limit`` does), ``parallel_fits > 1``, more than one device or a ``device_split``, and a basis
       that is complex, non-finite or of another shape.
+    * ``fit_quality`` (default off: ``quality_array`` stays zero as in the reference, cal_utils.py:48): report where the residual power
+      of every fitted slice sits.  With ``e = w |d - g_i conj(g_j) m|^2`` in the fit's own units (``w`` the weights the fit used,
+      ``m`` the returned model before gains, ``g`` the returned gains, evaluated before any post-hoc renormalisation, which leaves the
+      product unchanged) and ``rms`` the slice's data scale: ``gains.quality_array[a, f, t, pol] = rms^2 sum_{b with a} e / sum_{b with a} w``,
+      the weighted mean squared residual of antenna ``a``'s baselines in the data's units; ``gains.total_quality_array[f, t, pol]``
+      (``(Nfreqs, Ntimes, Njones)``, created if ``None``) the same with both sums taken over all antennas;
+      ``fit_history[polnum][time_index]["chisq_per_baseline"]`` a dict ``{(ant0, ant1): rms^2 sum_f e / sum_f w}`` with antenna
+      numbers, one entry per baseline of the fit.  0 where the weights sum to 0.  A skipped slice keeps zeros and has no dict.  One
+      device pass after the fit (``HipFitSolver.fit_quality``); no step of the fit changes.
     * ``layout``: "shared" (default; baselines alias the distinct basis blocks) or "stream" (every baseline owns its tiles).
     * ``parallel_fits`` (default 1): with ``batch_slices=False``, fits that many slices concurrently, each on its own
       solver and HIP stream.
@@ -903,6 +942,9 @@ def calibrate_and_model_tensor(
     if gains is None:
         echo(f"{datetime.datetime.now()} Gains are None. Initializing gains starting with unity...\n", verbose=verbose)
         gains = cal_utils.blank_uvcal_from_uvdata(uvdata)
+    if fit_quality and getattr(gains, "total_quality_array", None) is None:
+        # (here, once, not by whichever slice is written first: with parallel_fits the slices are written from several threads)
+        gains.total_quality_array = np.zeros(gain4(gains.quality_array).shape[1:], dtype=np.float64)
     if sky_model is None and model_regularization is not None:
         echo(f"{datetime.datetime.now()} Sky model is None. Initializing from data...\n", verbose=verbose)
         # data / (g_i conj(g_j)) with the initial gains (:1131-1136).  With the unity, unflagged gains built just above that is
@@ -949,7 +991,7 @@ def calibrate_and_model_tensor(
             maxsteps=maxsteps, n_profile_steps=n_profile_steps, profile_log_dir=profile_log_dir, model_regularization=model_regularization,
             verbose=verbose, max_batch=max_batch, devices=devices, layout=layout, opt_kwargs=opt_kwargs,
             correct_model=correct_model, correct_resid=correct_resid, device_split=device_split, gain_basis=gain_basis,
-            gain_time_basis=gain_time_basis,
+            gain_time_basis=gain_time_basis, fit_quality=fit_quality,
         )
         return model, resid, gains, fit_history  # (every slice left _fit_slices_batched in its final state)
     assert gain_time_basis is None, "a gain time basis must not reach the loop over single times"
@@ -1017,6 +1059,8 @@ def calibrate_and_model_tensor(
             m_r, m_i = solver.model()
             _insert_model_rows(model, time, pol, ants_map, prob, m_r, m_i, scale_factor=rmsdata)
             insert_gains_into_uvcal(uvcal=gains, time=time, polarization=pol, gains_re=g_r, gains_im=g_i)
+            if fit_quality:  # at the reported parameters, on the data and weights the fit used (the solver still holds them)
+                insert_fit_quality(gains, hist, time, pol, solver.fit_quality(g_r, g_i), rmsdata, prob)
         else:
             echo(f"{datetime.datetime.now()}: Only {frac_unflagged * 100}-percent of data unflagged. Skipping...\n", verbose=verbose)
             flag_poltime(resid, time=time, polarization=pol)
@@ -1237,7 +1281,7 @@ def _batch_fitter(prob, nt, dtype, layout, devices, joint=False):
 def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds, ants_map, times, weights, nsamples_in_weights, dtype,
                         skip_threshold, use_model_snr_weights, optimizer, use_min, freeze_model, tol, maxsteps, n_profile_steps,
                         profile_log_dir, model_regularization, verbose, max_batch, devices, layout, opt_kwargs, correct_model=True,
-                        correct_resid=False, device_split=None, gain_basis=None, gain_time_basis=None):
+                        correct_resid=False, device_split=None, gain_basis=None, gain_time_basis=None, fit_quality=False):
     """The pol x time loop of calibration.py:1160-1331 with the fits of all unskipped slices issued as batches: per slice
     exactly the host-side steps of the loop body (skip test :1173-1177, rms scale :1178-1182, tensorize :1184-1233, write-back
     :1271-1300, post-hoc renormalisation :1311-1319, residual and calibration state of the outputs :1322-1331), the gradient
@@ -1380,8 +1424,10 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
         # yield_fg_model_array x 2 + insert_model_into_uvdata_tensor (:1271-1292) for every slice from one A c pass
         fitter.set_params(c_r=cm_r, c_i=cm_i)
         m_r, m_i = fitter.model()
+        # at the reported parameters (every slice's own minimum with use_min), on the data and weights the fit used
+        quality = fitter.fit_quality(gm_r, gm_i) if fit_quality else None
         echo(f"{datetime.datetime.now()} ... fitted.\n", verbose=verbose)
-        return dict(results=results, m_r=m_r, m_i=m_i, gm_r=gm_r, gm_i=gm_i)
+        return dict(results=results, m_r=m_r, m_i=m_i, gm_r=gm_r, gm_i=gm_i, quality=quality)
 
     def post(batch, out):
         for t, (sl, res) in enumerate(zip(batch, out["results"])):
@@ -1389,6 +1435,11 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
             _insert_model_rows(model, sl["time"], sl["pol"], ants_map, prob, out["m_r"][rows], out["m_i"][rows], scale_factor=sl["rmsdata"])
             insert_gains_into_uvcal(uvcal=gains, time=sl["time"], polarization=sl["pol"], gains_re=out["gm_r"][ga], gains_im=out["gm_i"][ga])
             fit_history[sl["polnum"]][sl["time_index"]] = {"loss": [dtype.type(l) for l in res[0]]}
+            if out.get("quality") is not None:  # (before the post-hoc renormalisation, which leaves g_i conj(g_j) m as it is)
+                q = out["quality"]
+                insert_fit_quality(gains, fit_history[sl["polnum"]][sl["time_index"]], sl["time"], sl["pol"],
+                                   dict(chisq_ant=q["chisq_ant"][ga], wsum_ant=q["wsum_ant"][ga], chisq_bl=q["chisq_bl"][rows], wsum_bl=q["wsum_bl"][rows]),
+                                   sl["rmsdata"], prob)
             if res[1]:
                 echo(f"Tolerance thresshold met for time {sl['time_index']}. Terminating...\n ", verbose=verbose)
             if not freeze_model and model_regularization == "post_hoc":  # (:1311-1319)
@@ -1814,6 +1865,9 @@ def fitting_argparser():
     sp.add_argument("--gain_time_scale", type=float, default=None,
                     help="fit the times of a polarization jointly, with gains in a DPSS basis that drifts no faster than this [s]; "
                          "default: every time fits its own gains")
+    sp.add_argument("--fit_quality", default=False, action="store_true",
+                    help="write the weighted mean squared residual per antenna and channel into the gains' quality column and the total "
+                         "over antennas into TOTQLTY; default: zeros")
     return ap
 
 

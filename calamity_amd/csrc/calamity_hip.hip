@@ -25,6 +25,7 @@
 #include "multi_mfma_kernels.hpp"
 #include "gain_basis_kernels.hpp"
 #include "gain_time_basis_kernels.hpp"
+#include "fit_quality_kernels.hpp"
 #include <cstdlib>
 #include <dlfcn.h>
 #include <type_traits>
@@ -199,6 +200,7 @@ struct cal_solver {
   virtual int eval(bool grads, double* loss, void* gg_r, void* gg_i, void* gc_r, void* gc_i) = 0;
   virtual int run(const cal_run_desc* r, double* losses_out, cal_run_result* res, bool per_slice) = 0;
   virtual int model(void* mr, void* mi, bool with_gains) = 0;
+  virtual int fit_quality(const void* g_r, const void* g_i, double* chisq_ant, double* wsum_ant, double* chisq_bl, double* wsum_bl) = 0;
   virtual int init_coeffs(const void* sr, const void* si) = 0;
   virtual int synchronize() = 0;
   virtual int timing_enable(int e) = 0;
@@ -254,6 +256,7 @@ struct SolverT final : cal_solver {
   DevBuf scal;                                 // [nslices] x 4 doubles: loss, s_r, s_i, spare
   DevBuf gcp0, gcp1, gc0, gc1;                 // coefficient-gradient partials and (multi-item groups) their sums
   DevBuf part, state, losses, scratch, model_buf;
+  DevBuf fq_out, fq_gains;                     // fit_quality: chisq_ant | wsum_ant ([nants][nfreqs] doubles each, the exchange payload) | chisq_bl | wsum_bl; gains given for one evaluation
   DevBuf members, heads;                       // baselines that share tiles (bl_alias): member lists of the head items, head item indices
   int nheads = 0;                              // heads[0 .. nheads_mfma): fused_multi_mfma_kernel (at most kMmMaxVec vectors); the rest: fused_multi_kernel
   int nheads_mfma = 0;
@@ -1320,6 +1323,8 @@ struct SolverT final : cal_solver {
     CAL_TRY(part.alloc((size_t)std::max(nitems, mf_npanels) * 4 * sizeof(double)));
     model_buf.release();
     scratch.release();
+    fq_out.release();
+    fq_gains.release();
     has_problem = true;
     reg = CAL_REG_NONE;
     // ~ tens of milliseconds of GPU time between two host synchronisations of run(); the same on every rank, or ranks
@@ -2489,6 +2494,58 @@ struct SolverT final : cal_solver {
     return CAL_OK;
   }
 
+  // cal_solver_fit_quality: the model pass of model(), then quality_rows_kernel and quality_ant_kernel (fit_quality_kernels.hpp).
+  // The host mirror of the loop state is put back and pushed again afterwards: the pass clears the slices' stop flags for itself.
+  int fit_quality(const void* g_r, const void* g_i, double* chisq_ant, double* wsum_ant, double* chisq_bl, double* wsum_bl) override {
+    HIP_TRY(hipSetDevice(device));
+    if (!has_problem) return fail(CAL_ERR_STATE, "fit_quality: no problem set (cal_solver_set_problem)");
+    if (!has_data) return fail(CAL_ERR_STATE, "fit_quality: no data set (cal_solver_set_data)");
+    if (!has_coef) return fail(CAL_ERR_STATE, "fit_quality: the coefficients must be set (cal_solver_set_params)");
+    if ((g_r == nullptr) != (g_i == nullptr)) return fail(CAL_ERR_INVALID, "fit_quality: give both g_r and g_i, or neither");
+    if (!g_r && !has_gains) return fail(CAL_ERR_STATE, "fit_quality: the gains must be set (cal_solver_set_params) or given");
+    const size_t rowbytes = (size_t)nbls * fpad * sizeof(T);
+    if (model_buf.bytes < 2 * rowbytes) CAL_TRY(model_buf.alloc(2 * rowbytes));
+    const size_t nant_out = (size_t)nants * nfreqs;
+    const size_t out_bytes = (2 * nant_out + 2 * (size_t)nbls) * sizeof(double);
+    if (fq_out.bytes < out_bytes) CAL_TRY(fq_out.alloc(out_bytes));
+    const T2* g = gains.as<T2>();
+    if (g_r) {
+      const size_t gbytes = (size_t)nants * fpad * sizeof(T2);
+      if (fq_gains.bytes < gbytes) CAL_TRY(fq_gains.alloc(gbytes));
+      CAL_TRY(upload_rows(g_r, fq_gains.as<T>(), nants, 2, 0));
+      CAL_TRY(upload_rows(g_i, fq_gains.as<T>(), nants, 2, 1));
+      g = fq_gains.as<T2>();
+    }
+    const std::vector<DevState> saved(h_state, h_state + nslices);
+    begin_pass_state();
+    CAL_TRY(push_state());
+    FusedArgs<T> a = fused_args();
+    a.model_r = model_buf.as<T>();
+    a.model_i = model_buf.as<T>() + (size_t)nbls * fpad;
+    launch_fused<MODE_MODEL>(a, false);
+    double* o_ca = fq_out.as<double>();
+    double* o_wa = o_ca + nant_out;
+    double* o_cb = o_wa + nant_out;
+    double* o_wb = o_cb + nbls;
+    hipLaunchKernelGGL(quality_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, a.model_r, a.model_i, data_r.as<T>(), data_i.as<T>(),
+                       wgts.as<T>(), g, bl_ant.as<int2>(), nbls, nfreqs, fpad, o_cb, o_wb);
+    constexpr int V = 16 / (int)sizeof(T);
+    const int cblocks = (fpad + 64 * V - 1) / (64 * V);
+    hipLaunchKernelGGL(quality_ant_kernel<T>, dim3(nants * cblocks), dim3(256), 0, stream, a.model_r, wgts.as<T>(), ant_ptr.as<int>(),
+                       ant_ent.as<int2>(), nants, nfreqs, fpad, o_ca, o_wa);
+    HIP_TRY(hipGetLastError());
+    std::copy(saved.begin(), saved.end(), h_state);
+    CAL_TRY(push_state());
+    // the antenna planes of every rank's baselines add up to the array's: ONE all-reduce of 2 nants nfreqs doubles
+    if (comm_on()) CAL_TRY(all_reduce(o_ca, 2 * nant_out, CAL_XCHG_F64, CAL_XCHG_SUM));
+    if (chisq_ant) HIP_TRY(hipMemcpyAsync(chisq_ant, o_ca, nant_out * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (wsum_ant) HIP_TRY(hipMemcpyAsync(wsum_ant, o_wa, nant_out * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (chisq_bl) HIP_TRY(hipMemcpyAsync(chisq_bl, o_cb, (size_t)nbls * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (wsum_bl) HIP_TRY(hipMemcpyAsync(wsum_bl, o_wb, (size_t)nbls * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return CAL_OK;
+  }
+
   int init_coeffs(const void* sr, const void* si) override {
     HIP_TRY(hipSetDevice(device));
     if (!has_problem || !has_data) return fail(CAL_ERR_STATE, "init_coeffs: problem and data (weights) must be set");
@@ -2555,7 +2612,7 @@ struct SolverT final : cal_solver {
     if (!b) return fail(CAL_ERR_INVALID, "memory_bytes: null");
     const DevBuf* all[] = {&tiles, &bl_tile, &bl_ant, &items, &ant_ptr, &ant_ent, &coef_grp, &grp_coff, &grp_item_ptr, &item_goff,
                            &data_r, &data_i, &wgts, &gains, &gains_alt, &gains_m, &gains_v, &gains_snap, &coef, &coef_m, &coef_v, &coef_snap,
-                           &q0, &q1, &comm, &scal, &gcp0, &gcp1, &gc0, &gc1, &part, &state, &losses, &scratch, &model_buf,
+                           &q0, &q1, &comm, &scal, &gcp0, &gcp1, &gc0, &gc1, &part, &state, &losses, &scratch, &model_buf, &fq_out, &fq_gains,
                            &mf_ops, &mf_panels, &mf_map, &members, &heads, &lamb_vars, &lamb_cvar_ptr, &lamb_partial, &lamb_ratio, &lamb_glob, &lamb_slot, &slice_coff, &slice_ipart_ptr, &slice_ipart_idx,
                            &slice_ppart_ptr, &slice_ppart_idx, &slice_cblk, &gb_B, &gb_Bt, &gb_g0, &gb_y, &gb_ym, &gb_yv, &gb_ysnap, &gb_proj, &tb_B, &tb_Bt, &tb_z, &tb_pf};
     int64_t n = 0;
@@ -2845,6 +2902,10 @@ int cal_solver_run(cal_solver* s, const cal_run_desc* r, double* losses_out, cal
 int cal_solver_run_slices(cal_solver* s, const cal_run_desc* r, double* losses_out, cal_run_result* res) { NEED(s); return s->run(r, losses_out, res, true); }
 int cal_solver_model(cal_solver* s, void* mr, void* mi) { NEED(s); return s->model(mr, mi, false); }
 int cal_solver_data_model(cal_solver* s, void* mr, void* mi) { NEED(s); return s->model(mr, mi, true); }
+int cal_solver_fit_quality(cal_solver* s, const void* g_r, const void* g_i, double* chisq_ant, double* wsum_ant, double* chisq_bl, double* wsum_bl) {
+  NEED(s);
+  return s->fit_quality(g_r, g_i, chisq_ant, wsum_ant, chisq_bl, wsum_bl);
+}
 int cal_solver_init_coeffs(cal_solver* s, const void* sr, const void* si) { NEED(s); return s->init_coeffs(sr, si); }
 int cal_solver_synchronize(cal_solver* s) { NEED(s); return s->synchronize(); }
 int cal_solver_set_launch_mode(cal_solver* s, int mode) { NEED(s); return s->set_launch_mode(mode); }

@@ -283,6 +283,23 @@ class HipFitSolver:
         _lib.check(self._lib.cal_solver_data_model(self._h, _ptr(m_r), _ptr(m_i)))
         return m_r, m_i
 
+    def fit_quality(self, g_r=None, g_i=None):
+        """Where the residual power sits (cal_solver_fit_quality), in solver units: with ``e = w |d - g_i conj(g_j) (A c)|^2``,
+        ``chisq_bl``, ``wsum_bl`` ``[nbls]`` (sums of ``e`` and ``w`` over the channels) and ``chisq_ant``, ``wsum_ant``
+        ``[nants, nfreqs]`` (sums over the baselines of each antenna), all float64.  ``g_r``, ``g_i`` ``[nants, nfreqs]``: gains to
+        evaluate at for this call only; ``None``: the solver's current gains.  Under an exchange the antenna planes are summed over
+        the ranks; the baseline arrays stay this rank's own."""
+        if (g_r is None) != (g_i is None):
+            raise ValueError("give both g_r and g_i, or neither")
+        gs = (self.nants, self.nfreqs)
+        a = None if g_r is None else self._real(g_r, gs)
+        b = None if g_i is None else self._real(g_i, gs)
+        out = dict(chisq_ant=np.empty(gs, dtype=np.float64), wsum_ant=np.empty(gs, dtype=np.float64),
+                   chisq_bl=np.empty(self.nbls, dtype=np.float64), wsum_bl=np.empty(self.nbls, dtype=np.float64))
+        _lib.check(self._lib.cal_solver_fit_quality(self._h, _ptr(a), _ptr(b), _ptr(out["chisq_ant"]), _ptr(out["wsum_ant"]),
+                                                    _ptr(out["chisq_bl"]), _ptr(out["wsum_bl"])))
+        return out
+
     def init_coeffs(self, src_r, src_i):
         shp = (self.nbls, self.nfreqs)
         a, b = self._real(src_r, shp), self._real(src_i, shp)

@@ -253,6 +253,29 @@ int cal_solver_model(cal_solver* s, void* model_r, void* model_i);
 /* data_model, calibration.py:1593-1605: the foreground model of every baseline times its antennas' current gains,
  * g_ant0 conj(g_ant1) (A c): [nbls][nfreqs] (gains and coefficients must be set) */
 int cal_solver_data_model(cal_solver* s, void* model_r, void* model_i);
+/* Where the residual power of the fit sits (no counterpart in the reference, which reports one loss per slice and fills the gain
+ * object's quality_array with zeros, cal_utils.py:48): mse, calibration.py:1608-1609, kept per baseline and per (antenna, channel)
+ * instead of summed to one number.  In solver units, for baseline b with antennas (i, j) and channel f:
+ *   w = the weights of cal_solver_set_data, m = A c with the current coefficients, g = the gains the quality is evaluated at,
+ *   e[b][f] = w[b][f] |d[b][f] - g_i[f] conj(g_j[f]) m[b][f]|^2
+ *   chisq_bl[b] = sum_f e[b][f],  wsum_bl[b] = sum_f w[b][f]                                       [nbls]
+ *   chisq_ant[a][f] = sum over the baselines b that hold a of e[b][f],  wsum_ant[a][f] likewise of w   [nants][nfreqs]
+ * An autocorrelation baseline (ant0 == ant1) counts ONCE for its antenna.  sum_b chisq_bl is the unregularised loss; without
+ * autocorrelations sum_a chisq_ant[a][f] = 2 sum_b e[b][f].  All four outputs are double for both dtypes: products are formed in
+ * the solver's dtype as the loss kernels form them, sums are taken in double in a fixed order (no float atomics): two calls give
+ * the same bits.  Any output pointer may be NULL.
+ *   g_r, g_i: [nants][nfreqs] real (solver dtype), or both NULL.  NULL: the solver's current full gains (the expanded g, whatever
+ *   gain bases are set).  Given: uploaded to a buffer of their own and used for this evaluation only -- the solver's gains, g0, y,
+ *   moments and t are not touched.
+ * Problem, data and coefficients must be set, gains set or given (CAL_ERR_STATE otherwise).  Works for every layout and kernel
+ * path, fitting groups of several baselines, bl_alias, nslices > 1 and the joint time-basis layout (antenna row t Na + a is simply
+ * a row; slices that have stopped are evaluated like the others).  It runs the model pass of cal_solver_model and leaves everything
+ * a later cal_solver_run reads as it found it: a run continued after this call is bit-identical to one without it.
+ * Under a communicator or exchange hook chisq_ant | wsum_ant are summed over the ranks in ONE all-reduce of 2 nants nfreqs doubles
+ * (CAL_XCHG_F64, CAL_XCHG_SUM), whichever outputs are asked for: every rank returns identical planes.  chisq_bl and wsum_bl stay
+ * the rank's own baselines. */
+int cal_solver_fit_quality(cal_solver* s, const void* g_r, const void* g_i, double* chisq_ant, double* wsum_ant, double* chisq_bl,
+                           double* wsum_bl);
 /* tensorize_fg_coeffs, calibration.py:828-913: per group least squares of src on the basis with samples of zero
  * weight zeroed; the result becomes the current coefficients.  src_*: [nbls][nfreqs] real. */
 int cal_solver_init_coeffs(cal_solver* s, const void* src_r, const void* src_i);

@@ -62,6 +62,7 @@ def main():
     ap.add_argument("--ntimes", type=int, default=1)
     ap.add_argument("--verbose", action="store_true", help="the entry point's progress lines (time-stamped) on stderr-free stdout lines that do not start with {")
     ap.add_argument("--loop", action="store_true", help="the sequential time loop (batch_slices=False) instead of the batched call")
+    ap.add_argument("--fit-quality", action="store_true", help="fit_quality=True: the per-antenna / per-baseline quality pass after the fit")
     ap.add_argument("--second-call", action="store_true", help="time the SECOND call of the process (a short first call runs before it)")
     args = ap.parse_args()
     dtype = np.float32 if args.dtype == "f32" else np.float64
@@ -91,6 +92,7 @@ def main():
     timed(calibration, "_init_coeffs", "initial coefficients (device A^T d + download)")
     timed(calibration, "_insert_model_rows", "write-back (model rows -> UVData)")
     timed(calibration, "insert_gains_into_uvcal", "write-back (gains -> UVCal)")
+    timed(calibration, "insert_fit_quality", "write-back (fit quality -> UVCal, fit history)")
     timed(calibration, "fit_gains_and_foregrounds", "fit wrapper (flatten, set_params, history)")
     timed(calibration, "coeffs_to_chunks", "coefficient re-chunking")
     timed(calibration, "coeffs_from_chunks", "coefficient re-chunking")
@@ -113,12 +115,15 @@ def main():
         timed(H, "init_coeffs", "initial coefficients (device A^T d + download)")
         timed(H, "model", "model evaluation A c (device) + download")
         timed(H, "get_params", "download parameters")
+        timed(H, "fit_quality", "fit quality (model pass + two reductions, device) + download")
     kw = dict(maxsteps=args.maxsteps, tol=0.0, optimizer="Adam", learning_rate=1e-2, dtype=dtype,
               model_regularization=None if args.reg == "none" else args.reg)
     if args.loop:
         kw["batch_slices"] = False
     if args.verbose:
         kw["verbose"] = True
+    if args.fit_quality:
+        kw["fit_quality"] = True
     if args.reg == "none":
         kw["sky_model"] = uvd  # the reference needs a sky model when there is no regularisation to build one for
     if args.second_call:
@@ -141,7 +146,7 @@ def main():
     accounted = sum(TIMES.values())
     out = dict(call="second call of the process (DPSS blocks cached, runtime up)" if args.second_call else "first call of the process",
                workload=f"calibrate_and_model_dpss ({'time loop' if args.loop else 'batched slices'}): {args.nants} antennas, {len(antpairs)} baselines x {args.nfreqs} channels x {args.ntimes} time(s), "
-                        f"{np.dtype(dtype).name}, Adam lr 1e-2, model_regularization={args.reg}, maxsteps={args.maxsteps}",
+                        f"{np.dtype(dtype).name}, Adam lr 1e-2, model_regularization={args.reg}, maxsteps={args.maxsteps}" + (", fit_quality=True" if args.fit_quality else ""),
                total_s=total, recorded_steps=nsteps, host_only=args.host_only,
                split_s={k: round(v, 4) for k, v in sorted(TIMES.items(), key=lambda kv: -kv[1])},
                calls=CALLS, other_s=round(total - accounted, 4),
