@@ -17,7 +17,7 @@ CAL_PATH_AUTO, CAL_PATH_GENERAL, CAL_PATH_DENSE, CAL_PATH_DENSE_F32, CAL_PATH_DE
 CAL_LAUNCH_AUTO, CAL_LAUNCH_KERNELS, CAL_LAUNCH_ONE_TAIL, CAL_LAUNCH_GRAPH = 0, 1, 2, 3
 CAL_COMM_ID_BYTES = 128
 CAL_MAX_SLICES = 256
-CAL_ERR_INVALID, CAL_ERR_STATE, CAL_ERR_NONFINITE = -1, -4, -6
+CAL_ERR_INVALID, CAL_ERR_STATE, CAL_ERR_UNSUPPORTED, CAL_ERR_NONFINITE = -1, -4, -5, -6
 
 
 class ProblemDesc(C.Structure):
@@ -76,6 +76,10 @@ class RunDesc(C.Structure):
     ]
 
 
+class GainSolveDesc(C.Structure):
+    _fields_ = [("nsweeps", C.c_int32), ("reset_gain_moments", C.c_int32), ("damping", C.c_double), ("slice_mask", C.c_void_p)]
+
+
 class RunResult(C.Structure):
     _fields_ = [("nrecorded", C.c_int32), ("stopped", C.c_int32), ("nupdates", C.c_int32), ("nonfinite", C.c_int32)]
 
@@ -123,6 +127,8 @@ SYMBOLS = {
     "cal_solver_model": (C.c_int, [_P, _P, _P]),
     "cal_solver_data_model": (C.c_int, [_P, _P, _P]),
     "cal_solver_fit_quality": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    "cal_solver_solve_gains": (C.c_int, [_P, C.POINTER(GainSolveDesc)]),
+    "cal_solver_hold_slices": (C.c_int, [_P, _P]),
     "cal_weighted_square_error": (C.c_int, [C.c_int, C.c_int, C.c_int64, _P, _P, _P, _P, _P, C.POINTER(C.c_double)]),
     "cal_solver_init_coeffs": (C.c_int, [_P, _P, _P]),
     "cal_solver_synchronize": (C.c_int, [_P]),

@@ -273,6 +273,16 @@ class SliceBatchFitter:
             res["wsum_bl"][self.rows[r]] = o["wsum_bl"]
         return res
 
+    def solve_gains(self, nsweeps, damping=0.5, slice_mask=None, reset_gain_moments=False):
+        """``HipFitSolver.solve_gains`` on every worker (``slice_mask``: one entry per slice of the batch; one entry for a ``joint``
+        fitter).  With several workers each sweep sums the three antenna planes of the workers' baselines in one exchange, and every
+        worker applies the same update to its replica of the gains."""
+        self._each(lambda r, s: s.solve_gains(nsweeps, damping=damping, slice_mask=slice_mask, reset_gain_moments=reset_gain_moments))
+
+    def hold_slices(self, mask=None):
+        """``HipFitSolver.hold_slices`` on every worker."""
+        self._each(lambda r, s: s.hold_slices(mask))
+
     def set_regularization(self, mode=None, prior_r=None, prior_i=None):
         if mode == "sum":
             self._each(lambda r, s: s.set_regularization("sum", np.asarray(prior_r, dtype=np.float64), np.asarray(prior_i, dtype=np.float64)))

@@ -640,6 +640,9 @@ def fit_gains_and_foregrounds(
     model_regularization=None,
     graph_args_dict=None,
     gain_basis=None,
+    gain_solve_sweeps=0,
+    gain_solve_every=0,
+    gain_solve_damping=0.5,
     **opt_kwargs,
 ):
     """Run the optimization loop that fits gains and foreground coefficients -- calibration.py:447-738.
@@ -654,8 +657,10 @@ def fit_gains_and_foregrounds(
     Not in the reference: ``gain_basis`` (real ``[Nfreqs, K]``, e.g. ``modeling.gain_dpss_basis``) confines the CORRECTION to the
     gains to its span, ``g = g_in + B y`` with the coefficients ``y`` (zero at the start) as the optimizer's variables in place of
     the per-channel gains; everything else -- loss, loop semantics, returns (full gains) -- is unchanged.  Default ``None``: free
-    per-channel gains.
+    per-channel gains.  ``gain_solve_sweeps`` / ``gain_solve_every`` / ``gain_solve_damping``: closed-form gain sweeps before and
+    between the descent steps, see ``calibrate_and_model_tensor``.
     """
+    _check_gain_solve(gain_solve_sweeps, gain_solve_every, gain_solve_damping, gain_basis is not None)
     if gain_basis is not None:
         gain_basis = _check_gain_basis(gain_basis, np.asarray(g_r).shape[-1])
     echo(f"Using {str(dtype)} precision.")
@@ -682,6 +687,8 @@ def fit_gains_and_foregrounds(
     else:
         solver.set_regularization(None)
     solver.set_optimizer(optimizer, **opt_kwargs)
+    if gain_solve_sweeps > 0:  # the coefficients are initialised: the gains in closed form before any descent step
+        solver.solve_gains(gain_solve_sweeps, damping=gain_solve_damping)
     fit_history = {"loss": []}
     if n_profile_steps > 0:
         echo(f"{datetime.datetime.now()} Profiling with {n_profile_steps}. And writing output to {profile_log_dir}...")
@@ -694,7 +701,20 @@ def fit_gains_and_foregrounds(
     echo(f"{datetime.datetime.now()} Building Computational Graph...\n", verbose=verbose)
     solver.run(1, record=False, freeze_model=freeze_model)  # the unrecorded step of calibration.py:693
     echo(f"{datetime.datetime.now()} Performing Gradient Descent...\n", verbose=verbose)
-    losses, stopped, _ = solver.run(maxsteps, record=True, tol=tol, use_min=use_min, freeze_model=freeze_model)
+    if gain_solve_every > 0:
+        # the recorded loop in chunks (the solver's loop state -- step count, previous and lowest loss -- persists from run to run), a
+        # gain solve between two chunks while the loop goes on
+        losses, stopped = np.zeros(0), False
+        while len(losses) < maxsteps and not stopped:
+            n = min(gain_solve_every, maxsteps - len(losses))
+            part, stopped, _ = solver.run(n, record=True, tol=tol, use_min=use_min, freeze_model=freeze_model)
+            losses = np.concatenate([losses, part])
+            if len(part) < n:
+                break
+            if not stopped and len(losses) < maxsteps:
+                solver.solve_gains(max(1, gain_solve_sweeps), damping=gain_solve_damping, reset_gain_moments=True)
+    else:
+        losses, stopped, _ = solver.run(maxsteps, record=True, tol=tol, use_min=use_min, freeze_model=freeze_model)
     fit_history["loss"] = [dtype.type(l) for l in losses]
     if stopped:
         echo(f"Tolerance thresshold met with delta of {np.abs(losses[-1] - losses[-2]):.2e}. Terminating...\n ", verbose=verbose)
@@ -722,6 +742,17 @@ def _check_gain_basis(basis, nfreqs):
     if not np.all(np.isfinite(basis)):
         raise ValueError("gain_basis has non-finite elements")
     return np.ascontiguousarray(basis, dtype=np.float64)
+
+
+def _check_gain_solve(sweeps, every, damping, gain_basis_given):
+    """The arguments of the closed-form gain sweeps (ValueError before any device work)."""
+    if int(sweeps) != sweeps or sweeps < 0 or int(every) != every or every < 0:
+        raise ValueError(f"gain_solve_sweeps and gain_solve_every must be non-negative integers, got {sweeps!r} and {every!r}")
+    if not 0.0 < float(damping) <= 1.0:
+        raise ValueError(f"gain_solve_damping must lie in (0, 1], got {damping!r}")
+    if (sweeps or every) and gain_basis_given:
+        raise ValueError("gain_solve_sweeps / gain_solve_every solve free per-channel gains in closed form: they cannot be combined with "
+                         "gain_basis / gain_max_dly / gain_time_basis / gain_time_scale (projecting the solved gains onto a basis is not implemented)")
 
 
 def _check_gain_time_basis(basis, ntimes):
@@ -845,6 +876,9 @@ def calibrate_and_model_tensor(
     gain_time_basis=None,
     gain_time_scale=None,
     fit_quality=False,
+    gain_solve_sweeps=0,
+    gain_solve_every=0,
+    gain_solve_damping=0.5,
     **opt_kwargs,
 ):
     """Simultaneous calibration and foreground fitting -- calibration.py:963-1331, same arguments, defaults and
@@ -896,12 +930,28 @@ def calibrate_and_model_tensor(
       ``fit_history[polnum][time_index]["chisq_per_baseline"]`` a dict ``{(ant0, ant1): rms^2 sum_f e / sum_f w}`` with antenna
       numbers, one entry per baseline of the fit.  0 where the weights sum to 0.  A skipped slice keeps zeros and has no dict.  One
       device pass after the fit (``HipFitSolver.fit_quality``); no step of the fit changes.
+    * ``gain_solve_sweeps`` / ``gain_solve_every`` / ``gain_solve_damping`` (defaults 0, 0, 0.5: descent only, no call changes by a bit):
+      solve the gains in closed form.  With the foreground model held fixed the chi-square is linear least squares in one antenna's
+      gain while the others are held fixed; a damped StefCal sweep (``HipFitSolver.solve_gains``) sets every antenna's gain to
+      ``(1 - damping) g + damping num / den`` from the old gains of the others.  ``gain_solve_sweeps=N``: N sweeps on every fitted
+      slice after its coefficients are initialised and before the first (unrecorded) descent step -- what a fit against a
+      ``sky_model`` (with or without ``freeze_model``) otherwise spends hundreds of descent steps on.  ``gain_solve_every=K``: the
+      recorded loop is issued in chunks of K steps, and between two chunks ``gain_solve_sweeps`` sweeps (1 if that is 0) run on the
+      slices whose loop has not ended, with the optimizer's gain moments started over (stale momentum after a jump in the gains is
+      harmful); no sweeps follow the last chunk, so the returned parameters are those of the last step (or of the lowest loss with
+      ``use_min``) as always.  ``fit_history`` keeps one loss per recorded step.  The sweeps minimise the chi-square term only:
+      the ``"sum"`` regulariser depends on the gains and is NOT part of the closed form; it is allowed, and the descent steps that
+      follow see it as before.  Works in the loop, in batches and on several devices (``device_split="groups"`` sums the three planes
+      of a sweep over the devices in one exchange).  ``ValueError`` when combined with ``gain_basis`` / ``gain_max_dly`` /
+      ``gain_time_basis`` / ``gain_time_scale``.
     * ``layout``: "shared" (default; baselines alias the distinct basis blocks) or "stream" (every baseline owns its tiles).
     * ``parallel_fits`` (default 1): with ``batch_slices=False``, fits that many slices concurrently, each on its own
       solver and HIP stream.
     (Nothing here is steered by environment variables: layout, devices and concurrency are arguments.)"""
     if gain_basis is not None and gain_max_dly is not None:
         raise ValueError("give gain_basis or gain_max_dly, not both")
+    _check_gain_solve(gain_solve_sweeps, gain_solve_every, gain_solve_damping,
+                      any(b is not None for b in (gain_basis, gain_max_dly, gain_time_basis, gain_time_scale)))
     if gain_max_dly is not None:
         gain_basis = modeling.gain_dpss_basis(np.asarray(uvdata.freq_array, dtype=np.float64).ravel(), gain_max_dly)
     if gain_time_basis is not None and gain_time_scale is not None:
@@ -992,6 +1042,7 @@ def calibrate_and_model_tensor(
             verbose=verbose, max_batch=max_batch, devices=devices, layout=layout, opt_kwargs=opt_kwargs,
             correct_model=correct_model, correct_resid=correct_resid, device_split=device_split, gain_basis=gain_basis,
             gain_time_basis=gain_time_basis, fit_quality=fit_quality,
+            gain_solve=(gain_solve_sweeps, gain_solve_every, gain_solve_damping),
         )
         return model, resid, gains, fit_history  # (every slice left _fit_slices_batched in its final state)
     assert gain_time_basis is None, "a gain time basis must not reach the loop over single times"
@@ -1051,7 +1102,8 @@ def calibrate_and_model_tensor(
                 corr_inds=corr_inds, optimizer=optimizer, use_min=use_min, freeze_model=freeze_model,
                 notebook_progressbar=notebook_progressbar, verbose=verbose, tol=tol, dtype=dtype, maxsteps=maxsteps,
                 graph_mode=graph_mode, n_profile_steps=n_profile_steps, profile_log_dir=profile_log_dir,
-                sky_model_r=sky_model_r, sky_model_i=sky_model_i, model_regularization=model_regularization, gain_basis=gain_basis, **opt_kwargs,
+                sky_model_r=sky_model_r, sky_model_i=sky_model_i, model_regularization=model_regularization, gain_basis=gain_basis,
+                gain_solve_sweeps=gain_solve_sweeps, gain_solve_every=gain_solve_every, gain_solve_damping=gain_solve_damping, **opt_kwargs,
             )
             # yield_fg_model_array x 2 + insert_model_into_uvdata_tensor (calibration.py:1271-1292) without the
             # nants x nants cubes: one A c pass for both components, rows written straight back
@@ -1281,13 +1333,16 @@ def _batch_fitter(prob, nt, dtype, layout, devices, joint=False):
 def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds, ants_map, times, weights, nsamples_in_weights, dtype,
                         skip_threshold, use_model_snr_weights, optimizer, use_min, freeze_model, tol, maxsteps, n_profile_steps,
                         profile_log_dir, model_regularization, verbose, max_batch, devices, layout, opt_kwargs, correct_model=True,
-                        correct_resid=False, device_split=None, gain_basis=None, gain_time_basis=None, fit_quality=False):
+                        correct_resid=False, device_split=None, gain_basis=None, gain_time_basis=None, fit_quality=False,
+                        gain_solve=(0, 0, 0.5)):
     """The pol x time loop of calibration.py:1160-1331 with the fits of all unskipped slices issued as batches: per slice
     exactly the host-side steps of the loop body (skip test :1173-1177, rms scale :1178-1182, tensorize :1184-1233, write-back
     :1271-1300, post-hoc renormalisation :1311-1319, residual and calibration state of the outputs :1322-1331), the gradient
     descent of :1244-1269 for up to ``max_batch`` slices at once with per-slice loop control.  Returns ``fit_history``; model,
     resid and gains are complete when it returns.  ``gain_time_basis`` (``[len(times), L]``): the unskipped times of a polarization
-    are one batch and one JOINT fit (one loop state, loss = the sum over the times; calibrate_and_model_tensor's docstring)."""
+    are one batch and one JOINT fit (one loop state, loss = the sum over the times; calibrate_and_model_tensor's docstring).
+    ``gain_solve``: (gain_solve_sweeps, gain_solve_every, gain_solve_damping) of calibrate_and_model_tensor."""
+    gs_sweeps, gs_every, gs_damping = gain_solve
     OPTIMIZERS[optimizer]  # unknown optimizer -> KeyError, like calibration.py:571
     dtype = np.dtype(dtype)
     layout = layout or "shared"
@@ -1397,6 +1452,8 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
         else:
             fitter.set_regularization(None)
         fitter.set_optimizer(optimizer, **opt_kwargs)
+        if gs_sweeps > 0:  # the coefficients are initialised: the gains in closed form before any descent step
+            fitter.solve_gains(gs_sweeps, damping=gs_damping)
         if n_profile_steps > 0:
             fitter.timing_enable(True)
             fitter.run_slices(n_profile_steps, record=False, freeze_model=freeze_model)
@@ -1405,7 +1462,25 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
                 json.dump(dict(n_profile_steps=n_profile_steps, slices=nt, fused_basis_kernel=fitter.timing_get()), f)
             fitter.timing_enable(False)
         fitter.run_slices(1, record=False, freeze_model=freeze_model)  # the unrecorded step of calibration.py:693
-        results = fitter.run_slices(maxsteps, record=True, tol=tol, use_min=use_min, freeze_model=freeze_model)
+        if gs_every > 0:
+            # the recorded loop in chunks (every slice's loop state persists from run to run); a slice whose loop has ended is held
+            # in the chunks that follow, as one call would leave it, and takes no part in the gain solves between the chunks
+            parts, over, nupd, issued = [[] for _ in range(nt)], np.zeros(nt, dtype=bool), np.zeros(nt, dtype=np.int64), 0
+            while issued < maxsteps and not np.all(over):
+                n = min(gs_every, maxsteps - issued)
+                for t, (part, stopped, nu) in enumerate(fitter.run_slices(n, record=True, tol=tol, use_min=use_min, freeze_model=freeze_model)):
+                    if not over[t]:
+                        parts[t].append(part)
+                        nupd[t] += nu
+                        over[t] = stopped or len(part) < n
+                issued += n
+                if issued < maxsteps and not np.all(over):
+                    fitter.hold_slices(over)
+                    fitter.solve_gains(max(1, gs_sweeps), damping=gs_damping, slice_mask=~over, reset_gain_moments=True)
+            fitter.hold_slices(None)
+            results = [(np.concatenate(parts[t]), bool(over[t]), int(nupd[t])) for t in range(nt)]
+        else:
+            results = fitter.run_slices(maxsteps, record=True, tol=tol, use_min=use_min, freeze_model=freeze_model)
         if joint:
             results = results * nt  # one loop, one loss history: every time of the fit reports it
         cur = fitter.get_params(0)
@@ -1868,6 +1943,12 @@ def fitting_argparser():
     sp.add_argument("--fit_quality", default=False, action="store_true",
                     help="write the weighted mean squared residual per antenna and channel into the gains' quality column and the total "
                          "over antennas into TOTQLTY; default: zeros")
+    sp.add_argument("--gain_solve_sweeps", type=int, default=0,
+                    help="solve the gains in closed form (damped StefCal sweeps) this many times before the first descent step; default 0: descent only")
+    sp.add_argument("--gain_solve_every", type=int, default=0,
+                    help="run gain sweeps (--gain_solve_sweeps of them, at least one) after every this many recorded descent steps; default 0: never")
+    sp.add_argument("--gain_solve_damping", type=float, default=0.5,
+                    help="damping of a gain sweep, in (0, 1]: g <- (1 - damping) g + damping x the closed-form minimiser; default 0.5")
     return ap
 
 

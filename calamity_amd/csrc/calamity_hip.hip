@@ -26,6 +26,7 @@
 #include "gain_basis_kernels.hpp"
 #include "gain_time_basis_kernels.hpp"
 #include "fit_quality_kernels.hpp"
+#include "gain_solve_kernels.hpp"
 #include <cstdlib>
 #include <dlfcn.h>
 #include <type_traits>
@@ -201,6 +202,8 @@ struct cal_solver {
   virtual int run(const cal_run_desc* r, double* losses_out, cal_run_result* res, bool per_slice) = 0;
   virtual int model(void* mr, void* mi, bool with_gains) = 0;
   virtual int fit_quality(const void* g_r, const void* g_i, double* chisq_ant, double* wsum_ant, double* chisq_bl, double* wsum_bl) = 0;
+  virtual int solve_gains(const cal_gain_solve_desc* d) = 0;
+  virtual int hold_slices(const uint8_t* mask) = 0;
   virtual int init_coeffs(const void* sr, const void* si) = 0;
   virtual int synchronize() = 0;
   virtual int timing_enable(int e) = 0;
@@ -256,6 +259,8 @@ struct SolverT final : cal_solver {
   DevBuf scal;                                 // [nslices] x 4 doubles: loss, s_r, s_i, spare
   DevBuf gcp0, gcp1, gc0, gc1;                 // coefficient-gradient partials and (multi-item groups) their sums
   DevBuf part, state, losses, scratch, model_buf;
+  DevBuf gs_out, gs_ptr, gs_ent, gs_mask;      // solve_gains: num_r | num_i | den ([3][nants][nfreqs] doubles, the exchange payload); the antenna lists without autocorrelations; [nslices] mask bytes
+  std::vector<uint8_t> held;                   // hold_slices: [nslices], 1 = the slice enters every later run as stopped (empty: none)
   DevBuf fq_out, fq_gains;                     // fit_quality: chisq_ant | wsum_ant ([nants][nfreqs] doubles each, the exchange payload) | chisq_bl | wsum_bl; gains given for one evaluation
   DevBuf members, heads;                       // baselines that share tiles (bl_alias): member lists of the head items, head item indices
   int nheads = 0;                              // heads[0 .. nheads_mfma): fused_multi_mfma_kernel (at most kMmMaxVec vectors); the rest: fused_multi_kernel
@@ -1325,6 +1330,11 @@ struct SolverT final : cal_solver {
     scratch.release();
     fq_out.release();
     fq_gains.release();
+    gs_out.release();
+    gs_ptr.release();
+    gs_ent.release();
+    gs_mask.release();
+    held.clear();
     has_problem = true;
     reg = CAL_REG_NONE;
     // ~ tens of milliseconds of GPU time between two host synchronisations of run(); the same on every rank, or ranks
@@ -1543,6 +1553,7 @@ struct SolverT final : cal_solver {
     if (yb_on()) HIP_TRY(hipMemsetAsync(gb_ym.p, 0, gb_ym.bytes, stream));
     drop_graph();
     for (int t = 0; t < nslices; ++t) reset_loop_state(h_state[t]);  // a new fit begins
+    held.clear();
     has_opt = true;
     HIP_TRY(hipStreamSynchronize(stream));
     return CAL_OK;
@@ -2397,7 +2408,8 @@ struct SolverT final : cal_solver {
     if (!losses.p) CAL_TRY(losses.alloc((size_t)nslices * sizeof(double)));
     for (int t = 0; t < nslices; ++t) {
       DevState& h = h_state[t];
-      h.done = h.done_after = 0;
+      h.done = held.empty() ? 0 : held[t];  // (cal_solver_hold_slices: a slice that ended its loop in an earlier call of a chunked run)
+      h.done_after = 0;
       h.n_recorded = 0;
       h.nupdates = 0;
       h.improved = 0;
@@ -2546,6 +2558,123 @@ struct SolverT final : cal_solver {
     return CAL_OK;
   }
 
+  // cal_solver_hold_slices: slices that enter every later run as stopped (a chunked loop keeps the slices that met the tolerance in
+  // an earlier chunk as they are); NULL or all zeros: none.  set_optimizer and set_problem clear it.
+  int hold_slices(const uint8_t* mask) override {
+    if (!has_problem) return fail(CAL_ERR_STATE, "hold_slices before set_problem");
+    held.clear();
+    if (mask && std::any_of(mask, mask + nslices, [](uint8_t m) { return m != 0; })) {
+      held.resize(nslices);
+      for (int t = 0; t < nslices; ++t) held[t] = mask[t] ? 1 : 0;
+    }
+    return CAL_OK;
+  }
+
+  // the per-antenna lists of gain_solve_ant_kernel: ant_ptr / ant_ent without the autocorrelation rows, in baseline order (built at the
+  // first cal_solver_solve_gains of a problem from the device's own baseline table)
+  int build_solve_lists() {
+    if (gs_ptr.p) return CAL_OK;
+    std::vector<int2> h_ant(nbls);
+    HIP_TRY(copy_sync(h_ant.data(), bl_ant.p, (size_t)nbls * sizeof(int2), hipMemcpyDeviceToHost));
+    std::vector<int> ptr(nants + 1, 0);
+    for (int b = 0; b < nbls; ++b) {
+      if (h_ant[b].x == h_ant[b].y) continue;
+      ptr[h_ant[b].x + 1]++;
+      ptr[h_ant[b].y + 1]++;
+    }
+    for (int a = 0; a < nants; ++a) ptr[a + 1] += ptr[a];
+    std::vector<int2> ent((size_t)std::max(1, ptr[nants]));
+    std::vector<int> fill(ptr.begin(), ptr.end() - 1);
+    for (int b = 0; b < nbls; ++b) {
+      if (h_ant[b].x == h_ant[b].y) continue;
+      ent[fill[h_ant[b].x]++] = make_int2(b * 2 + 0, h_ant[b].y);
+      ent[fill[h_ant[b].y]++] = make_int2(b * 2 + 1, h_ant[b].x);
+    }
+    CAL_TRY(gs_ent.alloc(ent.size() * sizeof(int2), false));
+    HIP_TRY(copy_sync(gs_ent.p, ent.data(), ent.size() * sizeof(int2), hipMemcpyHostToDevice));
+    CAL_TRY(gs_ptr.alloc((nants + 1) * sizeof(int), false));
+    HIP_TRY(copy_sync(gs_ptr.p, ptr.data(), (nants + 1) * sizeof(int), hipMemcpyHostToDevice));
+    return CAL_OK;
+  }
+
+  // cal_solver_solve_gains: the model pass of model(), gain_solve_rows_kernel once, then per sweep gain_solve_ant_kernel, the exchange of
+  // its three planes and gain_solve_apply_kernel (gain_solve_kernels.hpp).  Like fit_quality, the host mirror of the loop state is put
+  // back and pushed again afterwards: the pass clears the slices' stop flags for itself.
+  int solve_gains(const cal_gain_solve_desc* d) override {
+    HIP_TRY(hipSetDevice(device));
+    if (!d) return fail(CAL_ERR_INVALID, "solve_gains: null description");
+    if (!has_problem) return fail(CAL_ERR_STATE, "solve_gains: no problem set (cal_solver_set_problem)");
+    if (!has_data) return fail(CAL_ERR_STATE, "solve_gains: no data set (cal_solver_set_data)");
+    if (!has_coef) return fail(CAL_ERR_STATE, "solve_gains: the coefficients must be set (cal_solver_set_params)");
+    if (!has_gains) return fail(CAL_ERR_STATE, "solve_gains: the gains must be set (cal_solver_set_params)");
+    if (d->nsweeps < 1) return fail(CAL_ERR_INVALID, "solve_gains: nsweeps = %d, at least one sweep", d->nsweeps);
+    if (!(d->damping > 0.0 && d->damping <= 1.0)) return fail(CAL_ERR_INVALID, "solve_gains: damping = %g lies outside (0, 1]", d->damping);
+    if (yb_on())
+      return fail(CAL_ERR_UNSUPPORTED, "solve_gains: a gain basis is set (cal_solver_set_gain_basis, cal_solver_set_gain_time_basis): the closed form solves "
+                  "free per-channel gains, and projecting them onto a basis is not implemented; detach the basis (nvec = 0) first");
+    if (d->reset_gain_moments && !has_opt) return fail(CAL_ERR_STATE, "solve_gains: reset_gain_moments without an optimizer (cal_solver_set_optimizer)");
+    CAL_TRY(build_solve_lists());
+    const size_t rowbytes = (size_t)nbls * fpad * sizeof(T);
+    if (model_buf.bytes < 3 * rowbytes) CAL_TRY(model_buf.alloc(3 * rowbytes));
+    const size_t nant_out = (size_t)nants * nfreqs;
+    if (gs_out.bytes < 3 * nant_out * sizeof(double)) CAL_TRY(gs_out.alloc(3 * nant_out * sizeof(double)));
+    const unsigned char* mask = nullptr;
+    if (d->slice_mask) {
+      if (gs_mask.bytes < (size_t)nslices) CAL_TRY(gs_mask.alloc((size_t)nslices, false));
+      HIP_TRY(copy_sync(gs_mask.p, d->slice_mask, (size_t)nslices, hipMemcpyHostToDevice));
+      mask = gs_mask.as<unsigned char>();
+    }
+    const std::vector<DevState> saved(h_state, h_state + nslices);
+    begin_pass_state();
+    CAL_TRY(push_state());
+    FusedArgs<T> a = fused_args();
+    a.model_r = model_buf.as<T>();
+    a.model_i = model_buf.as<T>() + (size_t)nbls * fpad;
+    T* q_rows = model_buf.as<T>() + 2 * (size_t)nbls * fpad;
+    launch_fused<MODE_MODEL>(a, false);
+    hipLaunchKernelGGL(gain_solve_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, a.model_r, a.model_i, q_rows, data_r.as<T>(),
+                       data_i.as<T>(), wgts.as<T>(), bl_ant.as<int2>(), nbls, nfreqs, fpad);
+    HIP_TRY(hipGetLastError());
+    std::copy(saved.begin(), saved.end(), h_state);
+    CAL_TRY(push_state());
+    constexpr int V = 16 / (int)sizeof(T);
+    const int cblocks = (fpad + 64 * V - 1) / (64 * V);
+    for (int k = 0; k < d->nsweeps; ++k) {
+      hipLaunchKernelGGL(gain_solve_ant_kernel<T>, dim3(nants * cblocks), dim3(256), 0, stream, a.model_r, a.model_i, q_rows, gains.as<T2>(),
+                         gs_ptr.as<int>(), gs_ent.as<int2>(), nants, nfreqs, fpad, gs_out.as<double>());
+      HIP_TRY(hipGetLastError());
+      // the planes of every rank's baselines add up to the array's: ONE all-reduce of 3 nants nfreqs doubles per sweep
+      if (comm_on()) CAL_TRY(all_reduce(gs_out.p, 3 * nant_out, CAL_XCHG_F64, CAL_XCHG_SUM));
+      hipLaunchKernelGGL(gain_solve_apply_kernel<T>, dim3(grid_for((long long)nant_out)), dim3(256), 0, stream, gains.as<T2>(), gs_out.as<double>(),
+                         mask, na_slice, nants, nfreqs, fpad, d->damping);
+      HIP_TRY(hipGetLastError());
+    }
+    if (d->reset_gain_moments) {
+      // what set_optimizer leaves in the gain slots, for the selected slices (runs of neighbouring slices in one call each)
+      const bool acc = (opt.optimizer == CAL_OPT_ADAGRAD || opt.optimizer == CAL_OPT_FTRL) && opt.initial_accumulator_value != 0.0;
+      const size_t per = (size_t)na_slice * fpad * 2;  // reals per slice
+      for (int t = 0; t < nslices;) {
+        if (d->slice_mask && !d->slice_mask[t]) {
+          ++t;
+          continue;
+        }
+        int t1 = t + 1;
+        while (t1 < nslices && (!d->slice_mask || d->slice_mask[t1])) ++t1;
+        const size_t off = (size_t)t * per, n = (size_t)(t1 - t) * per;
+        HIP_TRY(hipMemsetAsync(gains_m.as<T>() + off, 0, n * sizeof(T), stream));
+        if (acc)
+          hipLaunchKernelGGL(fill_kernel<T>, dim3(grid_for((long long)n)), dim3(256), 0, stream, gains_v.as<T>() + off, (long long)n,
+                             (T)opt.initial_accumulator_value);
+        else
+          HIP_TRY(hipMemsetAsync(gains_v.as<T>() + off, 0, n * sizeof(T), stream));
+        t = t1;
+      }
+      HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(stream));
+    return CAL_OK;
+  }
+
   int init_coeffs(const void* sr, const void* si) override {
     HIP_TRY(hipSetDevice(device));
     if (!has_problem || !has_data) return fail(CAL_ERR_STATE, "init_coeffs: problem and data (weights) must be set");
@@ -2612,7 +2741,7 @@ struct SolverT final : cal_solver {
     if (!b) return fail(CAL_ERR_INVALID, "memory_bytes: null");
     const DevBuf* all[] = {&tiles, &bl_tile, &bl_ant, &items, &ant_ptr, &ant_ent, &coef_grp, &grp_coff, &grp_item_ptr, &item_goff,
                            &data_r, &data_i, &wgts, &gains, &gains_alt, &gains_m, &gains_v, &gains_snap, &coef, &coef_m, &coef_v, &coef_snap,
-                           &q0, &q1, &comm, &scal, &gcp0, &gcp1, &gc0, &gc1, &part, &state, &losses, &scratch, &model_buf, &fq_out, &fq_gains,
+                           &q0, &q1, &comm, &scal, &gcp0, &gcp1, &gc0, &gc1, &part, &state, &losses, &scratch, &model_buf, &fq_out, &fq_gains, &gs_out, &gs_ptr, &gs_ent, &gs_mask,
                            &mf_ops, &mf_panels, &mf_map, &members, &heads, &lamb_vars, &lamb_cvar_ptr, &lamb_partial, &lamb_ratio, &lamb_glob, &lamb_slot, &slice_coff, &slice_ipart_ptr, &slice_ipart_idx,
                            &slice_ppart_ptr, &slice_ppart_idx, &slice_cblk, &gb_B, &gb_Bt, &gb_g0, &gb_y, &gb_ym, &gb_yv, &gb_ysnap, &gb_proj, &tb_B, &tb_Bt, &tb_z, &tb_pf};
     int64_t n = 0;
@@ -2902,6 +3031,8 @@ int cal_solver_run(cal_solver* s, const cal_run_desc* r, double* losses_out, cal
 int cal_solver_run_slices(cal_solver* s, const cal_run_desc* r, double* losses_out, cal_run_result* res) { NEED(s); return s->run(r, losses_out, res, true); }
 int cal_solver_model(cal_solver* s, void* mr, void* mi) { NEED(s); return s->model(mr, mi, false); }
 int cal_solver_data_model(cal_solver* s, void* mr, void* mi) { NEED(s); return s->model(mr, mi, true); }
+int cal_solver_solve_gains(cal_solver* s, const cal_gain_solve_desc* desc) { NEED(s); return s->solve_gains(desc); }
+int cal_solver_hold_slices(cal_solver* s, const uint8_t* mask) { NEED(s); return s->hold_slices(mask); }
 int cal_solver_fit_quality(cal_solver* s, const void* g_r, const void* g_i, double* chisq_ant, double* wsum_ant, double* chisq_bl, double* wsum_bl) {
   NEED(s);
   return s->fit_quality(g_r, g_i, chisq_ant, wsum_ant, chisq_bl, wsum_bl);

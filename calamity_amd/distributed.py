@@ -148,5 +148,8 @@ def exchange_spec(nants, nfreqs, reg_sum=False):
     """What one step exchanges between ranks: the gain-gradient parts (interleaved re/im, one part
     without and three with the "sum" regulariser) in the fit dtype, plus four float64 scalars (loss, S_r, S_i, spare).
     ``fit_quality_f64``: what ONE ``fit_quality`` call exchanges, once (not per step): the planes chisq_ant | wsum_ant,
-    ``[nants][nfreqs]`` float64 each, unpadded (cal_solver_fit_quality)."""
-    return dict(gain_grad_reals=(3 if reg_sum else 1) * 2 * nants * nfreqs, scalars_f64=4, fit_quality_f64=2 * nants * nfreqs)
+    ``[nants][nfreqs]`` float64 each, unpadded (cal_solver_fit_quality).
+    ``gain_solve_f64``: what ONE sweep of ``solve_gains`` exchanges, in one collective: the planes num_r | num_i | den,
+    ``[nants][nfreqs]`` float64 each, unpadded (cal_solver_solve_gains)."""
+    return dict(gain_grad_reals=(3 if reg_sum else 1) * 2 * nants * nfreqs, scalars_f64=4, fit_quality_f64=2 * nants * nfreqs,
+                gain_solve_f64=3 * nants * nfreqs)

@@ -300,6 +300,35 @@ class HipFitSolver:
                                                     _ptr(out["chisq_bl"]), _ptr(out["wsum_bl"])))
         return out
 
+    def _slice_mask(self, mask):
+        if mask is None:
+            return None
+        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if m.shape != (self.nslices,):
+            raise ValueError(f"expected one mask entry per time slice ({self.nslices}), got shape {m.shape}")
+        return m
+
+    def solve_gains(self, nsweeps, damping=0.5, slice_mask=None, reset_gain_moments=False):
+        """``nsweeps`` damped StefCal sweeps over the gains with the foreground model ``m = A c`` held fixed at the solver's
+        coefficients (cal_solver_solve_gains): per antenna ``a`` and channel, with the other antennas at their OLD gains,
+        ``g_a <- (1 - damping) g_a + damping num_a / den_a``, ``num_a = sum_b w d conj(m) g_other`` (conjugated where ``a`` is the
+        baseline's second antenna), ``den_a = sum_b w |m|^2 |g_other|^2`` over the cross-correlation baselines of ``a``; unchanged
+        where ``den_a`` is 0.  The sweeps minimise the chi-square term only (not the "sum" regulariser).  ``slice_mask``:
+        ``[nslices]``, the slices to solve (``None``: all); the others keep their gains bit for bit.  ``reset_gain_moments``: the
+        optimizer's gain slots of the solved slices start over as after ``set_optimizer`` (iteration counts and coefficient slots
+        stay).  Not available while a gain basis is set.  Under an exchange every sweep sums three ``[nants, nfreqs]`` float64 planes
+        over the ranks, and every rank applies the same update."""
+        m = self._slice_mask(slice_mask)
+        d = _lib.GainSolveDesc(int(nsweeps), int(bool(reset_gain_moments)), float(damping), None if m is None else m.ctypes.data)
+        _lib.check(self._lib.cal_solver_solve_gains(self._h, C.byref(d)))
+
+    def hold_slices(self, mask=None):
+        """Slices that enter every later ``run`` / ``run_slices`` as already stopped (``[nslices]``, nonzero = held; ``None``: no
+        slice): a loop issued in several calls keeps the slices that met the tolerance earlier as they are.  ``set_optimizer``
+        clears it.  (cal_solver_hold_slices)"""
+        m = self._slice_mask(mask)
+        _lib.check(self._lib.cal_solver_hold_slices(self._h, _ptr(m)))
+
     def init_coeffs(self, src_r, src_i):
         shp = (self.nbls, self.nfreqs)
         a, b = self._real(src_r, shp), self._real(src_i, shp)

@@ -276,6 +276,42 @@ int cal_solver_data_model(cal_solver* s, void* model_r, void* model_i);
  * the rank's own baselines. */
 int cal_solver_fit_quality(cal_solver* s, const void* g_r, const void* g_i, double* chisq_ant, double* wsum_ant, double* chisq_bl,
                            double* wsum_bl);
+/* The gains in closed form (no counterpart in the reference, which moves them by first-order descent only): damped StefCal sweeps
+ * (Salvini & Wijnholds 2014).  With the foreground model m = A c held fixed at the solver's coefficients, the chi-square
+ * sum w |d - g_i conj(g_j) m|^2 is linear least squares in one antenna's gain while the others are held fixed, with a closed-form
+ * minimiser per (antenna, channel).  Baseline b has antennas (i, j) = (bl_ant0, bl_ant1); d, w are the solver's data and weights, g
+ * its gains:
+ *   P[b][f] = w d conj(m)        (complex)        Q[b][f] = w |m|^2        (real)
+ *   role 0 (a == i):  num[a][f] += P g_j              den[a][f] += Q |g_j|^2
+ *   role 1 (a == j):  num[a][f] += conj(P) g_i        den[a][f] += Q |g_i|^2
+ *   g_new[a][f] = (1 - damping) g[a][f] + damping num/den    where den > 0, else g[a][f] unchanged
+ * An autocorrelation row (i == j) enters neither sum (its model is quadratic in one gain).  All antennas are updated from the OLD
+ * gains (a Jacobi sweep); damping = 0.5 is StefCal's averaging (damping = 1 stalls on this project's test problems).  Products are
+ * formed in the solver's dtype; num and den are accumulated in double in a fixed order (no float atomics: two calls give the same
+ * bits), and the update is evaluated in double and rounded once.  The sweeps minimise the chi-square term alone: the "sum"
+ * regulariser is not part of the closed form.
+ *   nsweeps >= 1 and 0 < damping <= 1 (CAL_ERR_INVALID otherwise); problem, data, coefficients and gains must be set (CAL_ERR_STATE).
+ *   slice_mask: [nslices] bytes or NULL (all slices): the gains of a slice whose byte is 0 keep their bits.
+ *   reset_gain_moments = 1: the optimizer's gain slots of the selected slices go back to what cal_solver_set_optimizer initialises
+ *   them to (stale momentum after a jump in the gains is harmful); iteration counts and the coefficient slots stay.  Needs an
+ *   optimizer (CAL_ERR_STATE).
+ * With a frequency or time gain basis attached the call fails with CAL_ERR_UNSUPPORTED (projecting the solved gains onto a basis is
+ * not implemented).  Works for every layout and kernel path, fitting groups of several baselines, bl_alias and nslices > 1: it runs
+ * the model pass of cal_solver_model once, then one pass over (b, f) for P and Q, then per sweep one walk of the antennas' baseline
+ * lists.  Like cal_solver_fit_quality it puts the loop state back: a run continued after a call with an all-zero mask is
+ * bit-identical to one without the call.  Under a communicator or exchange hook every sweep sums num_r | num_i | den over the ranks in
+ * ONE all-reduce of 3 nants nfreqs doubles (CAL_XCHG_F64, CAL_XCHG_SUM), and every rank applies the same update. */
+typedef struct cal_gain_solve_desc {
+  int32_t nsweeps;
+  int32_t reset_gain_moments;
+  double damping;
+  const uint8_t* slice_mask;
+} cal_gain_solve_desc;
+int cal_solver_solve_gains(cal_solver* s, const cal_gain_solve_desc* desc);
+/* Slices that enter every later cal_solver_run / cal_solver_run_slices as already stopped (mask [nslices] bytes, 1 = held; NULL or
+ * all zeros: none): a loop issued in several calls keeps a slice that met the tolerance in an earlier call as it is, as one call
+ * would.  A held slice reports stopped = 1 and records nothing.  cal_solver_set_optimizer and cal_solver_set_problem clear it. */
+int cal_solver_hold_slices(cal_solver* s, const uint8_t* mask);
 /* tensorize_fg_coeffs, calibration.py:828-913: per group least squares of src on the basis with samples of zero
  * weight zeroed; the result becomes the current coefficients.  src_*: [nbls][nfreqs] real. */
 int cal_solver_init_coeffs(cal_solver* s, const void* src_r, const void* src_i);
