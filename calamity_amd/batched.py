@@ -279,6 +279,13 @@ class SliceBatchFitter:
         worker applies the same update to its replica of the gains."""
         self._each(lambda r, s: s.solve_gains(nsweeps, damping=damping, slice_mask=slice_mask, reset_gain_moments=reset_gain_moments))
 
+    def solve_coeffs(self, niters=1, damping=1.0, ridge=1e-6, slice_mask=None, reset_coeff_moments=False):
+        """``HipFitSolver.solve_coeffs`` on every worker (``slice_mask``: one entry per slice of the batch; one entry for a ``joint``
+        fitter).  Every fitting group belongs to one worker and the gains are replicated: no exchange.  The counts are summed."""
+        outs = self._each(lambda r, s: s.solve_coeffs(niters=niters, damping=damping, ridge=ridge, slice_mask=slice_mask,
+                                                      reset_coeff_moments=reset_coeff_moments))
+        return {k: sum(o[k] for o in outs) for k in ("nsolved", "nsingular")}
+
     def hold_slices(self, mask=None):
         """``HipFitSolver.hold_slices`` on every worker."""
         self._each(lambda r, s: s.hold_slices(mask))

@@ -643,6 +643,8 @@ def fit_gains_and_foregrounds(
     gain_solve_sweeps=0,
     gain_solve_every=0,
     gain_solve_damping=0.5,
+    coeff_solve_rounds=0,
+    coeff_solve_ridge=1e-6,
     **opt_kwargs,
 ):
     """Run the optimization loop that fits gains and foreground coefficients -- calibration.py:447-738.
@@ -658,9 +660,11 @@ def fit_gains_and_foregrounds(
     gains to its span, ``g = g_in + B y`` with the coefficients ``y`` (zero at the start) as the optimizer's variables in place of
     the per-channel gains; everything else -- loss, loop semantics, returns (full gains) -- is unchanged.  Default ``None``: free
     per-channel gains.  ``gain_solve_sweeps`` / ``gain_solve_every`` / ``gain_solve_damping``: closed-form gain sweeps before and
-    between the descent steps, see ``calibrate_and_model_tensor``.
+    between the descent steps, and ``coeff_solve_rounds`` / ``coeff_solve_ridge``: closed-form coefficient solves in front of them,
+    see ``calibrate_and_model_tensor``.
     """
     _check_gain_solve(gain_solve_sweeps, gain_solve_every, gain_solve_damping, gain_basis is not None)
+    _check_coeff_solve(coeff_solve_rounds, coeff_solve_ridge, freeze_model)
     if gain_basis is not None:
         gain_basis = _check_gain_basis(gain_basis, np.asarray(g_r).shape[-1])
     echo(f"Using {str(dtype)} precision.")
@@ -687,7 +691,13 @@ def fit_gains_and_foregrounds(
     else:
         solver.set_regularization(None)
     solver.set_optimizer(optimizer, **opt_kwargs)
-    if gain_solve_sweeps > 0:  # the coefficients are initialised: the gains in closed form before any descent step
+    nsingular = None
+    if coeff_solve_rounds > 0:  # alternating least squares: rounds of (the coefficients in closed form, then the gain sweeps)
+        for _ in range(coeff_solve_rounds):
+            nsingular = solver.solve_coeffs(ridge=coeff_solve_ridge)["nsingular"]
+            if gain_solve_sweeps > 0:
+                solver.solve_gains(gain_solve_sweeps, damping=gain_solve_damping)
+    elif gain_solve_sweeps > 0:  # the coefficients are initialised: the gains in closed form before any descent step
         solver.solve_gains(gain_solve_sweeps, damping=gain_solve_damping)
     fit_history = {"loss": []}
     if n_profile_steps > 0:
@@ -712,10 +722,14 @@ def fit_gains_and_foregrounds(
             if len(part) < n:
                 break
             if not stopped and len(losses) < maxsteps:
+                if coeff_solve_rounds > 0:
+                    nsingular = solver.solve_coeffs(ridge=coeff_solve_ridge, reset_coeff_moments=True)["nsingular"]
                 solver.solve_gains(max(1, gain_solve_sweeps), damping=gain_solve_damping, reset_gain_moments=True)
     else:
         losses, stopped, _ = solver.run(maxsteps, record=True, tol=tol, use_min=use_min, freeze_model=freeze_model)
     fit_history["loss"] = [dtype.type(l) for l in losses]
+    if nsingular is not None:
+        fit_history["coeff_solve_singular"] = int(nsingular)
     if stopped:
         echo(f"Tolerance thresshold met with delta of {np.abs(losses[-1] - losses[-2]):.2e}. Terminating...\n ", verbose=verbose)
     g_r_opt, g_i_opt, c_r, c_i = solver.get_params(which=1 if (use_min and len(losses) > 0) else 0)
@@ -753,6 +767,17 @@ def _check_gain_solve(sweeps, every, damping, gain_basis_given):
     if (sweeps or every) and gain_basis_given:
         raise ValueError("gain_solve_sweeps / gain_solve_every solve free per-channel gains in closed form: they cannot be combined with "
                          "gain_basis / gain_max_dly / gain_time_basis / gain_time_scale (projecting the solved gains onto a basis is not implemented)")
+
+
+def _check_coeff_solve(rounds, ridge, freeze_model):
+    """The arguments of the closed-form coefficient solves (ValueError before any device work)."""
+    if isinstance(rounds, bool) or int(rounds) != rounds or rounds < 0:
+        raise ValueError(f"coeff_solve_rounds must be a non-negative integer, got {rounds!r}")
+    if not (np.isfinite(float(ridge)) and float(ridge) >= 0.0):
+        raise ValueError(f"coeff_solve_ridge must be finite and >= 0, got {ridge!r}")
+    if rounds and freeze_model:
+        raise ValueError("coeff_solve_rounds solves the foreground coefficients in closed form: it cannot be combined with freeze_model, "
+                         "which keeps them as given")
 
 
 def _check_gain_time_basis(basis, ntimes):
@@ -879,6 +904,8 @@ def calibrate_and_model_tensor(
     gain_solve_sweeps=0,
     gain_solve_every=0,
     gain_solve_damping=0.5,
+    coeff_solve_rounds=0,
+    coeff_solve_ridge=1e-6,
     **opt_kwargs,
 ):
     """Simultaneous calibration and foreground fitting -- calibration.py:963-1331, same arguments, defaults and
@@ -944,6 +971,17 @@ def calibrate_and_model_tensor(
       follow see it as before.  Works in the loop, in batches and on several devices (``device_split="groups"`` sums the three planes
       of a sweep over the devices in one exchange).  ``ValueError`` when combined with ``gain_basis`` / ``gain_max_dly`` /
       ``gain_time_basis`` / ``gain_time_scale``.
+    * ``coeff_solve_rounds`` / ``coeff_solve_ridge`` (defaults 0, 1e-6: off, no call changes by a bit): solve the foreground
+      coefficients in closed form.  With the gains held fixed the chi-square is linear least squares in the coefficients of every
+      fitting group; ``HipFitSolver.solve_coeffs`` solves ``(N + ridge tr(N) / nvec I) delta = rhs`` per group and adds ``delta``.
+      ``coeff_solve_rounds=R``: at the point where the gain sweeps run (after the initial coefficients and the optimizer are set,
+      before the first unrecorded descent step) R rounds of [one coefficient solve, then ``gain_solve_sweeps`` sweeps if that is
+      > 0] -- alternating least squares.  Under ``gain_solve_every=K`` every between-chunk point runs one coefficient solve, with the
+      optimizer's coefficient moments started over, in front of its sweeps, on the slices whose loop has not ended.  Allowed with
+      ``gain_basis`` / ``gain_max_dly`` / ``gain_time_basis`` / ``gain_time_scale`` (the solve only reads the gains; the sweeps remain
+      refused there).  ``ValueError`` with ``freeze_model``.  Like the sweeps it minimises the chi-square term only.
+      ``fit_history[polnum][time_index]["coeff_solve_singular"]`` (present only with the feature on): the groups the last solve left
+      alone because their normal matrix was singular (wholly flagged); in a batch the count is over the slices fitted together.
     * ``layout``: "shared" (default; baselines alias the distinct basis blocks) or "stream" (every baseline owns its tiles).
     * ``parallel_fits`` (default 1): with ``batch_slices=False``, fits that many slices concurrently, each on its own
       solver and HIP stream.
@@ -952,6 +990,7 @@ def calibrate_and_model_tensor(
         raise ValueError("give gain_basis or gain_max_dly, not both")
     _check_gain_solve(gain_solve_sweeps, gain_solve_every, gain_solve_damping,
                       any(b is not None for b in (gain_basis, gain_max_dly, gain_time_basis, gain_time_scale)))
+    _check_coeff_solve(coeff_solve_rounds, coeff_solve_ridge, freeze_model)
     if gain_max_dly is not None:
         gain_basis = modeling.gain_dpss_basis(np.asarray(uvdata.freq_array, dtype=np.float64).ravel(), gain_max_dly)
     if gain_time_basis is not None and gain_time_scale is not None:
@@ -1042,7 +1081,7 @@ def calibrate_and_model_tensor(
             verbose=verbose, max_batch=max_batch, devices=devices, layout=layout, opt_kwargs=opt_kwargs,
             correct_model=correct_model, correct_resid=correct_resid, device_split=device_split, gain_basis=gain_basis,
             gain_time_basis=gain_time_basis, fit_quality=fit_quality,
-            gain_solve=(gain_solve_sweeps, gain_solve_every, gain_solve_damping),
+            gain_solve=(gain_solve_sweeps, gain_solve_every, gain_solve_damping), coeff_solve=(coeff_solve_rounds, coeff_solve_ridge),
         )
         return model, resid, gains, fit_history  # (every slice left _fit_slices_batched in its final state)
     assert gain_time_basis is None, "a gain time basis must not reach the loop over single times"
@@ -1103,7 +1142,8 @@ def calibrate_and_model_tensor(
                 notebook_progressbar=notebook_progressbar, verbose=verbose, tol=tol, dtype=dtype, maxsteps=maxsteps,
                 graph_mode=graph_mode, n_profile_steps=n_profile_steps, profile_log_dir=profile_log_dir,
                 sky_model_r=sky_model_r, sky_model_i=sky_model_i, model_regularization=model_regularization, gain_basis=gain_basis,
-                gain_solve_sweeps=gain_solve_sweeps, gain_solve_every=gain_solve_every, gain_solve_damping=gain_solve_damping, **opt_kwargs,
+                gain_solve_sweeps=gain_solve_sweeps, gain_solve_every=gain_solve_every, gain_solve_damping=gain_solve_damping,
+                coeff_solve_rounds=coeff_solve_rounds, coeff_solve_ridge=coeff_solve_ridge, **opt_kwargs,
             )
             # yield_fg_model_array x 2 + insert_model_into_uvdata_tensor (calibration.py:1271-1292) without the
             # nants x nants cubes: one A c pass for both components, rows written straight back
@@ -1334,15 +1374,17 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
                         skip_threshold, use_model_snr_weights, optimizer, use_min, freeze_model, tol, maxsteps, n_profile_steps,
                         profile_log_dir, model_regularization, verbose, max_batch, devices, layout, opt_kwargs, correct_model=True,
                         correct_resid=False, device_split=None, gain_basis=None, gain_time_basis=None, fit_quality=False,
-                        gain_solve=(0, 0, 0.5)):
+                        gain_solve=(0, 0, 0.5), coeff_solve=(0, 1e-6)):
     """The pol x time loop of calibration.py:1160-1331 with the fits of all unskipped slices issued as batches: per slice
     exactly the host-side steps of the loop body (skip test :1173-1177, rms scale :1178-1182, tensorize :1184-1233, write-back
     :1271-1300, post-hoc renormalisation :1311-1319, residual and calibration state of the outputs :1322-1331), the gradient
     descent of :1244-1269 for up to ``max_batch`` slices at once with per-slice loop control.  Returns ``fit_history``; model,
     resid and gains are complete when it returns.  ``gain_time_basis`` (``[len(times), L]``): the unskipped times of a polarization
     are one batch and one JOINT fit (one loop state, loss = the sum over the times; calibrate_and_model_tensor's docstring).
-    ``gain_solve``: (gain_solve_sweeps, gain_solve_every, gain_solve_damping) of calibrate_and_model_tensor."""
+    ``gain_solve``: (gain_solve_sweeps, gain_solve_every, gain_solve_damping), ``coeff_solve``: (coeff_solve_rounds, coeff_solve_ridge) of
+    calibrate_and_model_tensor."""
     gs_sweeps, gs_every, gs_damping = gain_solve
+    cs_rounds, cs_ridge = coeff_solve
     OPTIMIZERS[optimizer]  # unknown optimizer -> KeyError, like calibration.py:571
     dtype = np.dtype(dtype)
     layout = layout or "shared"
@@ -1452,7 +1494,13 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
         else:
             fitter.set_regularization(None)
         fitter.set_optimizer(optimizer, **opt_kwargs)
-        if gs_sweeps > 0:  # the coefficients are initialised: the gains in closed form before any descent step
+        nsingular = None
+        if cs_rounds > 0:  # alternating least squares: rounds of (the coefficients in closed form, then the gain sweeps)
+            for _ in range(cs_rounds):
+                nsingular = fitter.solve_coeffs(ridge=cs_ridge)["nsingular"]
+                if gs_sweeps > 0:
+                    fitter.solve_gains(gs_sweeps, damping=gs_damping)
+        elif gs_sweeps > 0:  # the coefficients are initialised: the gains in closed form before any descent step
             fitter.solve_gains(gs_sweeps, damping=gs_damping)
         if n_profile_steps > 0:
             fitter.timing_enable(True)
@@ -1476,6 +1524,8 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
                 issued += n
                 if issued < maxsteps and not np.all(over):
                     fitter.hold_slices(over)
+                    if cs_rounds > 0:
+                        nsingular = fitter.solve_coeffs(ridge=cs_ridge, slice_mask=~over, reset_coeff_moments=True)["nsingular"]
                     fitter.solve_gains(max(1, gs_sweeps), damping=gs_damping, slice_mask=~over, reset_gain_moments=True)
             fitter.hold_slices(None)
             results = [(np.concatenate(parts[t]), bool(over[t]), int(nupd[t])) for t in range(nt)]
@@ -1502,7 +1552,7 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
         # at the reported parameters (every slice's own minimum with use_min), on the data and weights the fit used
         quality = fitter.fit_quality(gm_r, gm_i) if fit_quality else None
         echo(f"{datetime.datetime.now()} ... fitted.\n", verbose=verbose)
-        return dict(results=results, m_r=m_r, m_i=m_i, gm_r=gm_r, gm_i=gm_i, quality=quality)
+        return dict(results=results, m_r=m_r, m_i=m_i, gm_r=gm_r, gm_i=gm_i, quality=quality, nsingular=nsingular)
 
     def post(batch, out):
         for t, (sl, res) in enumerate(zip(batch, out["results"])):
@@ -1510,6 +1560,8 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
             _insert_model_rows(model, sl["time"], sl["pol"], ants_map, prob, out["m_r"][rows], out["m_i"][rows], scale_factor=sl["rmsdata"])
             insert_gains_into_uvcal(uvcal=gains, time=sl["time"], polarization=sl["pol"], gains_re=out["gm_r"][ga], gains_im=out["gm_i"][ga])
             fit_history[sl["polnum"]][sl["time_index"]] = {"loss": [dtype.type(l) for l in res[0]]}
+            if out.get("nsingular") is not None:
+                fit_history[sl["polnum"]][sl["time_index"]]["coeff_solve_singular"] = int(out["nsingular"])
             if out.get("quality") is not None:  # (before the post-hoc renormalisation, which leaves g_i conj(g_j) m as it is)
                 q = out["quality"]
                 insert_fit_quality(gains, fit_history[sl["polnum"]][sl["time_index"]], sl["time"], sl["pol"],
@@ -1949,6 +2001,12 @@ def fitting_argparser():
                     help="run gain sweeps (--gain_solve_sweeps of them, at least one) after every this many recorded descent steps; default 0: never")
     sp.add_argument("--gain_solve_damping", type=float, default=0.5,
                     help="damping of a gain sweep, in (0, 1]: g <- (1 - damping) g + damping x the closed-form minimiser; default 0.5")
+    sp.add_argument("--coeff_solve_rounds", type=int, default=0,
+                    help="before the first descent step, this many rounds of [the foreground coefficients in closed form, then "
+                         "--gain_solve_sweeps gain sweeps]; with --gain_solve_every one coefficient solve in front of every later group of sweeps; "
+                         "default 0: descent only")
+    sp.add_argument("--coeff_solve_ridge", type=float, default=1e-6,
+                    help="ridge of a coefficient solve, as a fraction of the mean diagonal of a group's normal matrix; default 1e-6")
     return ap
 
 

@@ -27,6 +27,7 @@
 #include "gain_time_basis_kernels.hpp"
 #include "fit_quality_kernels.hpp"
 #include "gain_solve_kernels.hpp"
+#include "coeff_solve_kernels.hpp"
 #include <cstdlib>
 #include <dlfcn.h>
 #include <type_traits>
@@ -204,6 +205,8 @@ struct cal_solver {
   virtual int fit_quality(const void* g_r, const void* g_i, double* chisq_ant, double* wsum_ant, double* chisq_bl, double* wsum_bl) = 0;
   virtual int solve_gains(const cal_gain_solve_desc* d) = 0;
   virtual int hold_slices(const uint8_t* mask) = 0;
+  virtual int solve_coeffs(const cal_coeff_solve_desc* d, cal_coeff_solve_result* res) = 0;
+  virtual int set_coeff_solve_scratch(int64_t bytes) = 0;
   virtual int init_coeffs(const void* sr, const void* si) = 0;
   virtual int synchronize() = 0;
   virtual int timing_enable(int e) = 0;
@@ -260,6 +263,15 @@ struct SolverT final : cal_solver {
   DevBuf gcp0, gcp1, gc0, gc1;                 // coefficient-gradient partials and (multi-item groups) their sums
   DevBuf part, state, losses, scratch, model_buf;
   DevBuf gs_out, gs_ptr, gs_ent, gs_mask;      // solve_gains: num_r | num_i | den ([3][nants][nfreqs] doubles, the exchange payload); the antenna lists without autocorrelations; [nslices] mask bytes
+  // solve_coeffs (coeff_solve_kernels.hpp): the groups as its kernels see them (host copy: set_problem; device copy, order, work list and
+  // chunks: the first call), N of a chunk of groups in T (cs_n) and its factor in double (cs_d), rhs [2][ncoef] T, the two counters
+  DevBuf cs_grp, cs_order, cs_work, cs_n, cs_d, cs_rhs, cs_cnt;
+  std::vector<CsGroup> h_cs_grp;
+  struct CsChunkRange { int g0, g1, w0, w1; size_t lds; };  // positions in cs_order / cs_work; dynamic LDS of its coeff_chol_kernel launch
+  std::vector<CsChunkRange> cs_chunks;
+  static constexpr int64_t kCsScratchDefault = 256ll << 20;  // bytes of cs_n + cs_d a chunk may take (one group alone may take more)
+  static constexpr int kCsLdsDoubles = 16384;                 // 128 KB: a factor of up to 126 vectors stays in LDS
+  int64_t cs_bound = kCsScratchDefault;
   std::vector<uint8_t> held;                   // hold_slices: [nslices], 1 = the slice enters every later run as stopped (empty: none)
   DevBuf fq_out, fq_gains;                     // fit_quality: chisq_ant | wsum_ant ([nants][nfreqs] doubles each, the exchange payload) | chisq_bl | wsum_bl; gains given for one evaluation
   DevBuf members, heads;                       // baselines that share tiles (bl_alias): member lists of the head items, head item indices
@@ -966,6 +978,14 @@ struct SolverT final : cal_solver {
     raw.release();
     CAL_TRY(bl_tile.alloc(nbls * sizeof(long long), false));
     HIP_TRY(copy_sync(bl_tile.p, h_bl_tile.data(), nbls * sizeof(long long), hipMemcpyHostToDevice));
+    h_cs_grp.assign(ngrps, CsGroup{});
+    for (int g = 0; g < ngrps; ++g) {
+      const int u = d->grp_basis[g];
+      int lg = 0;
+      while ((1 << lg) < fb_u[u]) ++lg;
+      h_cs_grp[g] = CsGroup{d->grp_bl_start[g], d->grp_bl_start[g + 1], d->basis_nvec[u], h_grp_coff[g], lg, grp_slice[g], 0, 0};
+    }
+    release_coeff_solve();
     std::vector<int2> h_ant(nbls);
     for (int b = 0; b < nbls; ++b) h_ant[b] = make_int2(d->bl_ant0[b], d->bl_ant1[b]);
     CAL_TRY(bl_ant.alloc(nbls * sizeof(int2), false));
@@ -1334,6 +1354,7 @@ struct SolverT final : cal_solver {
     gs_ptr.release();
     gs_ent.release();
     gs_mask.release();
+    cs_rhs.release();
     held.clear();
     has_problem = true;
     reg = CAL_REG_NONE;
@@ -2675,6 +2696,156 @@ struct SolverT final : cal_solver {
     return CAL_OK;
   }
 
+  // ---- cal_solver_solve_coeffs ----------------------------------------------------------------------------------
+  void release_coeff_solve() {  // the plan of a problem / a scratch bound: rebuilt by the next call
+    cs_grp.release();
+    cs_order.release();
+    cs_work.release();
+    cs_n.release();
+    cs_d.release();
+    cs_cnt.release();
+    cs_chunks.clear();
+  }
+  int set_coeff_solve_scratch(int64_t bytes) override {
+    if (bytes < 0) return fail(CAL_ERR_INVALID, "set_coeff_solve_scratch: negative bound");
+    cs_bound = bytes == 0 ? kCsScratchDefault : bytes;
+    release_coeff_solve();
+    return CAL_OK;
+  }
+  // Groups heaviest first (as everywhere: the tail of a launch is made of the lightest), cut into chunks whose N (T) and factor
+  // (double) stay under cs_bound bytes -- a group that alone needs more is a chunk of its own.  Every chunk reuses the two scratch
+  // buffers from offset 0; a group's result does not depend on the chunk it falls into.
+  int build_coeff_solve_plan() {
+    if (!cs_chunks.empty()) return CAL_OK;
+    std::vector<int> order(ngrps);
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return h_cs_grp[a].nvec > h_cs_grp[b].nvec; });
+    std::vector<CsWork> work;
+    std::vector<CsChunkRange> chunks;
+    long long n_max = 0, d_max = 0;
+    for (int p = 0; p < ngrps;) {
+      long long noff = 0, doff = 0;
+      int max_nvec = 0;
+      CsChunkRange ch{p, p, (int)work.size(), 0, 0};
+      for (; p < ngrps; ++p) {
+        CsGroup& g = h_cs_grp[order[p]];
+        const long long nn = (long long)g.nvec * g.nvec, dd = (long long)(g.nvec + 2) * g.nvec;
+        if (p > ch.g0 && (noff + nn) * (long long)sizeof(T) + (doff + dd) * 8 > cs_bound) break;
+        g.noff = noff;
+        g.doff = doff;
+        noff += nn;
+        doff += dd;
+        max_nvec = std::max(max_nvec, g.nvec);
+        const int nb = (g.nvec + kCsBlock - 1) / kCsBlock;
+        for (int bi = 0; bi < nb; ++bi)
+          for (int bj = 0; bj <= bi; ++bj) work.push_back(CsWork{order[p], bi, bj, 0});
+      }
+      ch.g1 = p;
+      ch.w1 = (int)work.size();
+      const long long want = (long long)(max_nvec + 2) * (max_nvec | 1);
+      ch.lds = (size_t)std::min<long long>(want, kCsLdsDoubles) * sizeof(double);
+      chunks.push_back(ch);
+      n_max = std::max(n_max, noff);
+      d_max = std::max(d_max, doff);
+    }
+    CAL_TRY(cs_grp.alloc((size_t)ngrps * sizeof(CsGroup), false));
+    HIP_TRY(copy_sync(cs_grp.p, h_cs_grp.data(), (size_t)ngrps * sizeof(CsGroup), hipMemcpyHostToDevice));
+    CAL_TRY(cs_order.alloc((size_t)ngrps * sizeof(int), false));
+    HIP_TRY(copy_sync(cs_order.p, order.data(), (size_t)ngrps * sizeof(int), hipMemcpyHostToDevice));
+    CAL_TRY(cs_work.alloc(work.size() * sizeof(CsWork), false));
+    HIP_TRY(copy_sync(cs_work.p, work.data(), work.size() * sizeof(CsWork), hipMemcpyHostToDevice));
+    CAL_TRY(cs_n.alloc((size_t)n_max * sizeof(T), false));
+    CAL_TRY(cs_d.alloc((size_t)d_max * sizeof(double), false));
+    CAL_TRY(cs_cnt.alloc(2 * sizeof(int)));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&coeff_chol_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                kCsLdsDoubles * (int)sizeof(double)));
+    cs_chunks = chunks;
+    return CAL_OK;
+  }
+
+  // cal_solver_solve_coeffs: per iteration the model pass of model(), coeff_solve_rows_kernel, then per chunk of groups
+  // coeff_gram_kernel and coeff_chol_kernel (coeff_solve_kernels.hpp).  Like fit_quality and solve_gains the host mirror of the loop
+  // state is put back and pushed again behind the model pass.  Every group is owned by one rank: no exchange.
+  int solve_coeffs(const cal_coeff_solve_desc* d, cal_coeff_solve_result* res) override {
+    HIP_TRY(hipSetDevice(device));
+    if (!d) return fail(CAL_ERR_INVALID, "solve_coeffs: null description");
+    if (!has_problem) return fail(CAL_ERR_STATE, "solve_coeffs: no problem set (cal_solver_set_problem)");
+    if (!has_data) return fail(CAL_ERR_STATE, "solve_coeffs: no data set (cal_solver_set_data)");
+    if (!has_coef) return fail(CAL_ERR_STATE, "solve_coeffs: the coefficients must be set (cal_solver_set_params)");
+    if (!has_gains) return fail(CAL_ERR_STATE, "solve_coeffs: the gains must be set (cal_solver_set_params)");
+    if (d->niters < 1) return fail(CAL_ERR_INVALID, "solve_coeffs: niters = %d, at least one iteration", d->niters);
+    if (!(d->damping > 0.0 && d->damping <= 1.0)) return fail(CAL_ERR_INVALID, "solve_coeffs: damping = %g lies outside (0, 1]", d->damping);
+    if (!(d->ridge >= 0.0) || !std::isfinite(d->ridge)) return fail(CAL_ERR_INVALID, "solve_coeffs: ridge = %g must be finite and >= 0", d->ridge);
+    if (d->reset_coeff_moments && !has_opt) return fail(CAL_ERR_STATE, "solve_coeffs: reset_coeff_moments without an optimizer (cal_solver_set_optimizer)");
+    CAL_TRY(build_coeff_solve_plan());
+    const size_t rowbytes = (size_t)nbls * fpad * sizeof(T);
+    if (model_buf.bytes < 3 * rowbytes) CAL_TRY(model_buf.alloc(3 * rowbytes));
+    if (cs_rhs.bytes < 2 * (size_t)ncoef * sizeof(T)) CAL_TRY(cs_rhs.alloc(2 * (size_t)ncoef * sizeof(T)));
+    const unsigned char* mask = nullptr;
+    if (d->slice_mask) {
+      if (gs_mask.bytes < (size_t)nslices) CAL_TRY(gs_mask.alloc((size_t)nslices, false));
+      HIP_TRY(copy_sync(gs_mask.p, d->slice_mask, (size_t)nslices, hipMemcpyHostToDevice));
+      mask = gs_mask.as<unsigned char>();
+    }
+    int counts[2] = {0, 0};
+    for (int it = 0; it < d->niters; ++it) {
+      const std::vector<DevState> saved(h_state, h_state + nslices);
+      begin_pass_state();
+      CAL_TRY(push_state());
+      FusedArgs<T> a = fused_args();
+      a.model_r = model_buf.as<T>();
+      a.model_i = model_buf.as<T>() + (size_t)nbls * fpad;
+      T* q_rows = model_buf.as<T>() + 2 * (size_t)nbls * fpad;
+      launch_fused<MODE_MODEL>(a, false);
+      hipLaunchKernelGGL(coeff_solve_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, a.model_r, a.model_i, q_rows, data_r.as<T>(),
+                         data_i.as<T>(), wgts.as<T>(), gains.as<T2>(), bl_ant.as<int2>(), nbls, nfreqs, fpad);
+      HIP_TRY(hipGetLastError());
+      std::copy(saved.begin(), saved.end(), h_state);
+      CAL_TRY(push_state());
+      HIP_TRY(hipMemsetAsync(cs_cnt.p, 0, 2 * sizeof(int), stream));
+      for (const CsChunkRange& ch : cs_chunks) {
+        hipLaunchKernelGGL(coeff_gram_kernel<T>, dim3(ch.w1 - ch.w0), dim3(256), 0, stream, tiles.as<T>(), bl_tile.as<long long>(), a.model_r,
+                           a.model_i, q_rows, cs_grp.as<CsGroup>(), cs_work.as<CsWork>() + ch.w0, cs_n.as<T>(), cs_rhs.as<T>(), ncoef, nfreqs, fpad,
+                           fold ? 1 : 0);
+        hipLaunchKernelGGL(coeff_chol_kernel<T>, dim3(ch.g1 - ch.g0), dim3(256), ch.lds, stream, cs_n.as<T>(), cs_rhs.as<T>(), cs_d.as<double>(),
+                           cs_grp.as<CsGroup>(), cs_order.as<int>() + ch.g0, coef.as<T>(), coef.as<T>() + ncoef, ncoef, mask, d->damping, d->ridge,
+                           cs_cnt.as<int>(), kCsLdsDoubles);
+        HIP_TRY(hipGetLastError());
+      }
+    }
+    HIP_TRY(hipMemcpyAsync(counts, cs_cnt.p, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
+    if (d->reset_coeff_moments) {
+      // what set_optimizer leaves in the coefficient slots, for the selected slices (runs of neighbouring slices in one call per plane)
+      const bool acc = (opt.optimizer == CAL_OPT_ADAGRAD || opt.optimizer == CAL_OPT_FTRL) && opt.initial_accumulator_value != 0.0;
+      for (int t = 0; t < nslices;) {
+        if (d->slice_mask && !d->slice_mask[t]) {
+          ++t;
+          continue;
+        }
+        int t1 = t + 1;
+        while (t1 < nslices && (!d->slice_mask || d->slice_mask[t1])) ++t1;
+        const size_t n = (size_t)(h_slice_coff[t1] - h_slice_coff[t]);
+        for (int plane = 0; plane < 2 && n > 0; ++plane) {
+          const size_t off = (size_t)plane * ncoef + h_slice_coff[t];
+          HIP_TRY(hipMemsetAsync(coef_m.as<T>() + off, 0, n * sizeof(T), stream));
+          if (acc)
+            hipLaunchKernelGGL(fill_kernel<T>, dim3(grid_for((long long)n)), dim3(256), 0, stream, coef_v.as<T>() + off, (long long)n,
+                               (T)opt.initial_accumulator_value);
+          else
+            HIP_TRY(hipMemsetAsync(coef_v.as<T>() + off, 0, n * sizeof(T), stream));
+        }
+        t = t1;
+      }
+      HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (res) {
+      res->nsolved = counts[0];
+      res->nsingular = counts[1];
+    }
+    return CAL_OK;
+  }
+
   int init_coeffs(const void* sr, const void* si) override {
     HIP_TRY(hipSetDevice(device));
     if (!has_problem || !has_data) return fail(CAL_ERR_STATE, "init_coeffs: problem and data (weights) must be set");
@@ -2741,7 +2912,7 @@ struct SolverT final : cal_solver {
     if (!b) return fail(CAL_ERR_INVALID, "memory_bytes: null");
     const DevBuf* all[] = {&tiles, &bl_tile, &bl_ant, &items, &ant_ptr, &ant_ent, &coef_grp, &grp_coff, &grp_item_ptr, &item_goff,
                            &data_r, &data_i, &wgts, &gains, &gains_alt, &gains_m, &gains_v, &gains_snap, &coef, &coef_m, &coef_v, &coef_snap,
-                           &q0, &q1, &comm, &scal, &gcp0, &gcp1, &gc0, &gc1, &part, &state, &losses, &scratch, &model_buf, &fq_out, &fq_gains, &gs_out, &gs_ptr, &gs_ent, &gs_mask,
+                           &q0, &q1, &comm, &scal, &gcp0, &gcp1, &gc0, &gc1, &part, &state, &losses, &scratch, &model_buf, &fq_out, &fq_gains, &gs_out, &gs_ptr, &gs_ent, &gs_mask, &cs_grp, &cs_order, &cs_work, &cs_n, &cs_d, &cs_rhs, &cs_cnt,
                            &mf_ops, &mf_panels, &mf_map, &members, &heads, &lamb_vars, &lamb_cvar_ptr, &lamb_partial, &lamb_ratio, &lamb_glob, &lamb_slot, &slice_coff, &slice_ipart_ptr, &slice_ipart_idx,
                            &slice_ppart_ptr, &slice_ppart_idx, &slice_cblk, &gb_B, &gb_Bt, &gb_g0, &gb_y, &gb_ym, &gb_yv, &gb_ysnap, &gb_proj, &tb_B, &tb_Bt, &tb_z, &tb_pf};
     int64_t n = 0;
@@ -3033,6 +3204,8 @@ int cal_solver_model(cal_solver* s, void* mr, void* mi) { NEED(s); return s->mod
 int cal_solver_data_model(cal_solver* s, void* mr, void* mi) { NEED(s); return s->model(mr, mi, true); }
 int cal_solver_solve_gains(cal_solver* s, const cal_gain_solve_desc* desc) { NEED(s); return s->solve_gains(desc); }
 int cal_solver_hold_slices(cal_solver* s, const uint8_t* mask) { NEED(s); return s->hold_slices(mask); }
+int cal_solver_solve_coeffs(cal_solver* s, const cal_coeff_solve_desc* desc, cal_coeff_solve_result* result) { NEED(s); return s->solve_coeffs(desc, result); }
+int cal_solver_set_coeff_solve_scratch(cal_solver* s, int64_t bytes) { NEED(s); return s->set_coeff_solve_scratch(bytes); }
 int cal_solver_fit_quality(cal_solver* s, const void* g_r, const void* g_i, double* chisq_ant, double* wsum_ant, double* chisq_bl, double* wsum_bl) {
   NEED(s);
   return s->fit_quality(g_r, g_i, chisq_ant, wsum_ant, chisq_bl, wsum_bl);

@@ -322,6 +322,26 @@ class HipFitSolver:
         d = _lib.GainSolveDesc(int(nsweeps), int(bool(reset_gain_moments)), float(damping), None if m is None else m.ctypes.data)
         _lib.check(self._lib.cal_solver_solve_gains(self._h, C.byref(d)))
 
+    def solve_coeffs(self, niters=1, damping=1.0, ridge=1e-6, slice_mask=None, reset_coeff_moments=False):
+        """The foreground coefficients in closed form with the gains held fixed (cal_solver_solve_coeffs): per fitting group the
+        normal equations ``(N + ridge tr(N)/nvec I) delta = rhs`` with ``N = sum_b A_b^T diag(w |G|^2) A_b`` and
+        ``rhs = sum_b A_b^T (w conj(G) (d - G A c))``, ``G = g_i conj(g_j)`` from the solver's full gains, then
+        ``c <- c + damping delta``.  ``N`` and ``rhs`` are formed in the solver's dtype on the matrix cores, the Cholesky solve runs in
+        float64.  ``niters`` repeats the whole sequence (in float32 a second iteration is iterative refinement).  ``slice_mask``:
+        ``[nslices]``, the slices to solve (``None``: all); the others keep their coefficients bit for bit.
+        ``reset_coeff_moments``: the optimizer's coefficient slots of the solved slices start over as after ``set_optimizer``.  Works
+        with a gain basis attached (the gains are only read) and issues no exchange.  Returns ``{"nsolved", "nsingular"}`` of the last
+        iteration: a singular group (wholly flagged, or a non-positive pivot) keeps its coefficients."""
+        m = self._slice_mask(slice_mask)
+        d = _lib.CoeffSolveDesc(int(niters), int(bool(reset_coeff_moments)), float(damping), float(ridge), None if m is None else m.ctypes.data)
+        r = _lib.CoeffSolveResult()
+        _lib.check(self._lib.cal_solver_solve_coeffs(self._h, C.byref(d), C.byref(r)))
+        return {"nsolved": int(r.nsolved), "nsingular": int(r.nsingular)}
+
+    def _set_coeff_solve_scratch(self, nbytes):
+        """Scratch bound of ``solve_coeffs`` in bytes (0: the default); the results do not depend on it (tests)."""
+        _lib.check(self._lib.cal_solver_set_coeff_solve_scratch(self._h, int(nbytes)))
+
     def hold_slices(self, mask=None):
         """Slices that enter every later ``run`` / ``run_slices`` as already stopped (``[nslices]``, nonzero = held; ``None``: no
         slice): a loop issued in several calls keeps the slices that met the tolerance earlier as they are.  ``set_optimizer``

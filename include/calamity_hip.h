@@ -312,6 +312,56 @@ int cal_solver_solve_gains(cal_solver* s, const cal_gain_solve_desc* desc);
  * all zeros: none): a loop issued in several calls keeps a slice that met the tolerance in an earlier call as it is, as one call
  * would.  A held slice reports stopped = 1 and records nothing.  cal_solver_set_optimizer and cal_solver_set_problem clear it. */
 int cal_solver_hold_slices(cal_solver* s, const uint8_t* mask);
+/* The foreground coefficients in closed form (no counterpart in the reference): the other half of alternating least squares next to
+ * cal_solver_solve_gains.  With the gains held fixed the chi-square sum w |d - g_i conj(g_j) (A c)|^2 is linear least squares in the
+ * coefficients and separates by fitting group.  Group gamma has nvec complex coefficients c; its baselines b have antennas (i, j) and
+ * the real row block A_b [nfreqs][nvec] of the group's basis; d, w are the solver's data and weights, g its full (expanded) gains,
+ * m = A c at the solver's current coefficients:
+ *   G[b][f] = g_i[f] conj(g_j[f])
+ *   u[b][f] = w conj(G) (d - G m)          (complex)
+ *   q[b][f] = w |G|^2                      (real)
+ *   N   = sum_{b in gamma} A_b^T diag(q_b) A_b   [nvec][nvec], real symmetric
+ *   rhs = sum_{b in gamma} A_b^T u_b             [nvec], complex
+ *   N_r = N + ridge (tr N / nvec) I
+ *   N_r delta = rhs                              (one factorisation, two right-hand sides: re, im)
+ *   c_new = c + damping delta
+ * rhs is minus half the chi-square gradient with respect to c: with ridge = 0 and damping = 1 the step lands on the minimiser; with
+ * ridge > 0 it is a Levenberg step whose fixed point is still the exact minimiser.  Baselines of a group that share a row block
+ * share A: their q and u are summed first.  An autocorrelation row is an ordinary row (the model is linear in c).  The solve
+ * minimises the chi-square term alone: the "sum" regulariser is not part of it.
+ * Precision: u, q, N and rhs are formed and accumulated in the solver's dtype in a fixed order (no atomics on reals: two calls give the
+ * same bits; N and rhs on v_mfma_f32_16x16x4_f32 / v_mfma_f64_16x16x4_f64); the Cholesky factorisation of N_r, the substitutions
+ * and the update are evaluated in double for both dtypes, and the update is rounded to the solver's dtype once.
+ * A group is singular when tr N <= 0 (wholly flagged) or a pivot is <= 0 or not finite: it keeps the bits of its coefficients and is
+ * counted in nsingular.  Suggested values: damping = 1, ridge = 1e-6 (flagged band edges take cond(N) to 1e8, beyond an fp32 Gram),
+ * niters = 1; every iteration repeats the whole sequence from the current coefficients (in fp32 a second one is iterative
+ * refinement).  result (may be NULL) counts the groups of the LAST iteration; groups of unselected slices count in neither field.
+ *   niters >= 1, 0 < damping <= 1, ridge >= 0 and finite (CAL_ERR_INVALID otherwise); problem, data, coefficients and gains must be
+ *   set, and reset_coeff_moments needs an optimizer (CAL_ERR_STATE).
+ *   slice_mask: [nslices] bytes or NULL (all slices): the coefficients of a slice whose byte is 0 keep their bits.
+ *   reset_coeff_moments = 1: the optimizer's coefficient slots of the selected slices go back to what cal_solver_set_optimizer
+ *   initialises them to; iteration counts and the gain slots stay.
+ * Gains, gain coefficients of a gain basis (y, g0), gain moments, t and iteration counts are never touched: unlike
+ * cal_solver_solve_gains the call works with a frequency and / or time gain basis attached (it reads the expanded gains).  Works for
+ * every layout and kernel path, folded and full tiles, fitting groups of several baselines, bl_alias, nslices > 1 and the joint
+ * time-basis layout: it runs the model pass of cal_solver_model, one pass over (b, f) for u and q, then per group the Gram product
+ * straight from the solver's basis tiles and the factorisation.  The groups are worked through heaviest first in chunks whose
+ * scratch (N in the solver's dtype plus its factor in double) stays under 256 MiB -- never less than the largest group needs.
+ * Like cal_solver_fit_quality it puts the loop state back: a run continued after a call with an all-zero mask is bit-identical to
+ * one without the call.  Under a communicator or exchange hook the call issues NO collective: every fitting group belongs to one
+ * rank, and the gains are replicated. */
+typedef struct cal_coeff_solve_desc {
+  int32_t niters;               /* >= 1 */
+  int32_t reset_coeff_moments;
+  double damping;               /* (0, 1] */
+  double ridge;                 /* >= 0 */
+  const uint8_t* slice_mask;    /* [nslices] or NULL */
+} cal_coeff_solve_desc;
+typedef struct cal_coeff_solve_result { int32_t nsolved; int32_t nsingular; } cal_coeff_solve_result; /* of the last iteration */
+int cal_solver_solve_coeffs(cal_solver* s, const cal_coeff_solve_desc* desc, cal_coeff_solve_result* result);
+/* The scratch bound of cal_solver_solve_coeffs in bytes (0: the default, 256 MiB).  The coefficients do not depend on it: tests use
+ * it to send a small problem through several chunks. */
+int cal_solver_set_coeff_solve_scratch(cal_solver* s, int64_t bytes);
 /* tensorize_fg_coeffs, calibration.py:828-913: per group least squares of src on the basis with samples of zero
  * weight zeroed; the result becomes the current coefficients.  src_*: [nbls][nfreqs] real. */
 int cal_solver_init_coeffs(cal_solver* s, const void* src_r, const void* src_i);
