@@ -11,7 +11,8 @@ the solver's coefficients, d, w its data and weights, g its full gains:
 The restatement works in fp64 on the inputs the solver holds (cast to its dtype first).  Tolerances are the project's own
 (tests/test_gpu_fit_quality.py: TOL): planes (c_r and c_i after the call) fp64 1e-10, fp32 1e-4 of the plane's largest element;
 losses fp64 1e-10, fp32 1e-5.  Every parity input is asserted to have cond(N) <= 1e4, so that an ill-conditioned input cannot pass as
-a tolerance problem (an fp32 Gram with an fp64 factorisation stays at 2e-8 ... 4e-6 of the plane on these shapes)."""
+a tolerance problem (an fp32 Gram with an fp64 factorisation stays at 2e-8 ... 4e-6 of the plane on these shapes; the wider blocks of
+tests/test_gpu_coeff_solve_shapes.py reach 1.6e-5 at cond(N) = 1e3)."""
 import copy
 import functools
 
@@ -329,6 +330,39 @@ def test_with_a_gain_basis_attached(dtype):
     s.close()
 
 
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("with_freq", [False, True], ids=["time", "time_x_freq"])
+def test_with_a_gain_time_basis_attached(with_freq, dtype):
+    """Three times of seven antennas as one fit, g = g0 + Bt (x) y or g0 + Bt (x) Bf y: the solve reads the expanded gains and writes
+    neither them nor y."""
+    from test_gain_time_basis_host import TIMES_60, joint_case
+
+    ntimes = 3
+    p, start = joint_case(ntimes=ntimes, nants=7, nfreqs=40)[:2]
+    assert p.nants == 7 * ntimes
+    label = f"gain time basis{' x frequency basis' if with_freq else ''} {np.dtype(dtype).name}"
+    s = solver_of(p, start, dtype, "stream")
+    if with_freq:
+        s.set_gain_basis(np.array(modeling.gain_dpss_basis(150e6 + 400e3 * np.arange(p.nfreqs), 100.0)))
+    s.set_gain_time_basis(np.array(modeling.gain_time_dpss_basis(TIMES_60[:ntimes], 400.0)))
+    s.set_optimizer("Adam", learning_rate=1e-2)
+    s.run(3, tol=0.0)  # y != 0
+    before, y0 = s.get_params(), s.get_gain_coeffs()
+    assert y0[0].shape[:2] == (7, 2) and np.any(y0[0] != 0) and np.any(before[0] != np.asarray(start["g_r"], dtype=dtype))
+    cur = dict(start, c_r=before[2], c_i=before[3])
+    want, chisq, conds, singular = restated(p, cur, dtype, gains=before[:2])
+    print(f"{label}: largest cond(N) {max(conds):.2e}")
+    assert max(conds) <= COND_MAX and not singular
+    assert s.solve_coeffs() == {"nsolved": p.ngrps, "nsingular": 0}
+    check_coeffs(s, want, dtype, label)
+    after, y1 = s.get_params(), s.get_gain_coeffs()
+    for a, b in zip(after[:2] + y1, before[:2] + y0):
+        np.testing.assert_array_equal(a, b)
+    check_loss(s, chisq, dtype, label)
+    s.run(2, tol=0.0)  # and the fit goes on
+    s.close()
+
+
 @pytest.mark.parametrize("optimizer", ["Adam", "Adagrad"])
 def test_reset_coeff_moments_restores_the_slots_of_set_optimizer(optimizer):
     """Adagrad's accumulator starts at 0.1, not 0."""
@@ -354,6 +388,58 @@ def test_reset_coeff_moments_restores_the_slots_of_set_optimizer(optimizer):
         np.testing.assert_array_equal(got[k], moved[k], err_msg=k)
     assert got["t"] == 5
     s.run(2, tol=0.0)  # and the fit goes on
+    s.close()
+
+
+@functools.lru_cache(maxsize=None)
+def three_slices():
+    """The blocks of the "256" case in three time slices of four groups each."""
+    rng = np.random.default_rng(286)
+    return small_problem([mirror_block(rng, 256, n) for n in FOLD_CASES["256"]["nvec"]], [0, 1, 0, 1], seed=287, nslices=3)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("mask", [[1, 0, 1], [0, 1, 1]])
+@pytest.mark.parametrize("optimizer", ["Adam", "Adagrad"])
+def test_a_mask_with_reset_coeff_moments_restores_the_selected_slices_only(optimizer, mask, dtype):
+    """What the batched driver calls: [1, 0, 1] are two runs of one selected slice, [0, 1, 1] one run of two.  The selected slices are
+    solved and their coefficient slots start over; the other slice keeps coefficients and slots to the bit; gain slots and t stay."""
+    p, start = three_slices()
+    label = f"{optimizer} mask {mask} {np.dtype(dtype).name}"
+    s = solver_of(p, start, dtype, "stream")
+    s.set_optimizer(optimizer, learning_rate=1e-2)
+    fresh = s.get_moments()
+    if optimizer == "Adagrad":
+        assert np.all(fresh["cv_r"] == dtype(0.1)) and np.all(fresh["cv_i"] == dtype(0.1)) and not np.any(fresh["cm_r"])
+    s.run_slices(4, tol=0.0)
+    moved, before = s.get_moments(), s.get_params()
+    per, ngrps = p.ncoeffs // 3, p.ngrps // 3
+    assert p.grp_coff[ngrps] == per and p.grp_coff[2 * ngrps] == 2 * per
+    parts = [slice(t * per, (t + 1) * per) for t in range(3)]
+    for part in parts:
+        assert np.any(moved["cv_r"][part] != fresh["cv_r"][part]) and np.any(moved["cv_i"][part] != fresh["cv_i"][part])
+    want, _, conds, singular = restated(p, dict(zip(("g_r", "g_i", "c_r", "c_i"), before)), dtype)
+    print(f"{label}: largest cond(N) {max(conds):.2e}")
+    assert max(conds) <= COND_MAX and not singular
+    res = s.solve_coeffs(slice_mask=mask, reset_coeff_moments=True)
+    assert res == {"nsolved": sum(mask) * ngrps, "nsingular": 0}, res
+    got, after = s.get_moments(), s.get_params()
+    for t, part in enumerate(parts):
+        for k in ("cm_r", "cm_i", "cv_r", "cv_i"):
+            np.testing.assert_array_equal(got[k][part], (fresh if mask[t] else moved)[k][part], err_msg=f"{k} of slice {t}")
+        for k, ref in ((2, want.real), (3, want.imag)):
+            if mask[t]:
+                err = plane_err(after[k][part], ref[part])
+                print(f"{label}: slice {t} plane {k} {err:.2e}")
+                assert err <= TOL[np.dtype(dtype)]["plane"] and np.all(after[k][part] != before[k][part])
+            else:
+                np.testing.assert_array_equal(after[k][part], before[k][part], err_msg=f"plane {k} of slice {t}")
+    for k in ("gm_r", "gm_i", "gv_r", "gv_i", "t"):
+        np.testing.assert_array_equal(got[k], moved[k], err_msg=k)
+    assert got["t"] == 4
+    np.testing.assert_array_equal(after[0], before[0])
+    np.testing.assert_array_equal(after[1], before[1])
+    assert len(s.run_slices(2, tol=0.0)[1][0]) == 2  # and the fit goes on
     s.close()
 
 

@@ -277,6 +277,57 @@ def test_reset_gain_moments_restores_the_slots_of_set_optimizer(optimizer):
     s.close()
 
 
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("mask", [[1, 0, 1], [0, 1, 1]])
+@pytest.mark.parametrize("optimizer", ["Adam", "Adagrad"])
+def test_a_mask_with_reset_gain_moments_restores_the_selected_slices_only(optimizer, mask, dtype):
+    """What the batched driver calls: [1, 0, 1] are two runs of one selected slice, [0, 1, 1] one run of two.  The selected slices are
+    swept and their gain slots start over; the other slice keeps gains and slots to the bit; coefficients, their slots and t stay."""
+    from calamity_amd.solver import HipFitSolver
+
+    T = 3
+    parts = [synthetic.make_problem(7, 200, f0=150e6, df=400e3, seed=21, data_seed=30 + t) for t in range(T)]
+    p0 = parts[0][0]
+    data = tuple(np.concatenate([getattr(parts[t][0], k) for t in range(T)]) for k in ("data_r", "data_i", "wgts"))
+    pars = [perturbed(parts[t][0], parts[t][2], seed=40 + t) for t in range(T)]
+    sub, _, _ = batched.replicate_slices(p0, T)
+    label = f"{optimizer} mask {mask} {np.dtype(dtype).name}"
+    s = HipFitSolver(dtype=dtype)
+    s.set_problem(sub, layout="stream")
+    s.set_data(*data)
+    s.set_params(*[np.concatenate([pars[t][k] for t in range(T)]) for k in ("g_r", "g_i", "c_r", "c_i")])
+    s.set_optimizer(optimizer, learning_rate=1e-2)
+    fresh = s.get_moments()
+    if optimizer == "Adagrad":
+        assert np.all(fresh["gv_r"] == dtype(0.1)) and np.all(fresh["gv_i"] == dtype(0.1)) and not np.any(fresh["gm_r"])
+    s.run_slices(4, tol=0.0)
+    moved, before = s.get_moments(), s.get_params()
+    na = p0.nants
+    rows = [slice(t * na, (t + 1) * na) for t in range(T)]
+    for part in rows:
+        assert np.any(moved["gv_r"][part] != fresh["gv_r"][part]) and np.any(moved["gv_i"][part] != fresh["gv_i"][part])
+    want = restated(sub, dict(zip(("g_r", "g_i", "c_r", "c_i"), before)), dtype, nsweeps=2, data=data)[0]
+    s.solve_gains(2, slice_mask=mask, reset_gain_moments=True)
+    got, after = s.get_moments(), s.get_params()
+    for t, part in enumerate(rows):
+        for k in ("gm_r", "gm_i", "gv_r", "gv_i"):
+            np.testing.assert_array_equal(got[k][part], (fresh if mask[t] else moved)[k][part], err_msg=f"{k} of slice {t}")
+        for k, ref in ((0, want.real), (1, want.imag)):
+            if mask[t]:
+                err = plane_err(after[k][part], ref[part])
+                print(f"{label}: slice {t} plane {k} {err:.2e}")
+                assert err <= TOL[np.dtype(dtype)]["plane"] and not np.array_equal(after[k][part], before[k][part])
+            else:
+                np.testing.assert_array_equal(after[k][part], before[k][part], err_msg=f"plane {k} of slice {t}")
+    for k in ("cm_r", "cm_i", "cv_r", "cv_i", "t"):
+        np.testing.assert_array_equal(got[k], moved[k], err_msg=k)
+    assert got["t"] == 4
+    np.testing.assert_array_equal(after[2], before[2])
+    np.testing.assert_array_equal(after[3], before[3])
+    assert len(s.run_slices(2, tol=0.0)[1][0]) == 2  # and the fit goes on
+    s.close()
+
+
 # ---- error codes
 def test_wrong_arguments_and_wrong_state_are_reported():
     from calamity_amd.solver import HipFitSolver
