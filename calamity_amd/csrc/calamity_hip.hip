@@ -28,6 +28,7 @@
 #include "fit_quality_kernels.hpp"
 #include "gain_solve_kernels.hpp"
 #include "coeff_solve_kernels.hpp"
+#include "problem_plan.hpp"
 #include <cstdlib>
 #include <dlfcn.h>
 #include <type_traits>
@@ -35,18 +36,6 @@
 using namespace calk;
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...) {
-  char buf[1024];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return code;
-}
 
 #define HIP_TRY(expr)                                                                                          \
   do {                                                                                                         \
@@ -57,11 +46,6 @@ int fail(int code, const char* fmt, ...) {
   do {                                                                                                         \
     ncclResult_t _e = (expr);                                                                                  \
     if (_e != ncclSuccess) return fail(CAL_ERR_RCCL, "%s failed: %s (%s:%d)", #expr, ncclGetErrorString(_e), __FILE__, __LINE__); \
-  } while (0)
-#define CAL_TRY(expr)      \
-  do {                     \
-    int _r = (expr);       \
-    if (_r != CAL_OK) return _r; \
   } while (0)
 
 // Zero fills of new allocations run on a non-blocking utility stream of the current device, never on the legacy stream: a
@@ -147,38 +131,6 @@ inline int grid_for(long long n, int block = 256, int cap = 16384) {
   return (int)std::max<long long>(1, std::min<long long>(g, cap));
 }
 
-// Mirror symmetry of one basis block, row-major [nfreqs][nvec]: A[F-1-f][k] = (-1)^k A[f][k] (discrete prolate spheroidal
-// sequences centred on zero delay alternate between symmetric and antisymmetric vectors).  Host only.  Returns false for a block
-// with a non-finite element; otherwise the largest |A[F-1-f][k] - (-1)^k A[f][k]| and the largest |A|.
-template <typename T>
-bool mirror_residual(const T* a, int nfreqs, int nvec, double* resid, double* amax) {
-  double r = 0, m = 0;
-  for (long long i = 0; i < (long long)nfreqs * nvec; ++i) {
-    const double x = std::fabs((double)a[i]);
-    if (!std::isfinite(x)) return false;
-    m = std::max(m, x);
-  }
-  for (int f = 0; f < nfreqs / 2; ++f) {
-    const T* lo = a + (long long)f * nvec;
-    const T* hi = a + (long long)(nfreqs - 1 - f) * nvec;
-    for (int k = 0; k < nvec; ++k) r = std::max(r, std::fabs((double)hi[k] - ((k & 1) ? -(double)lo[k] : (double)lo[k])));
-  }
-  *resid = r;
-  *amax = m;
-  return true;
-}
-// The streaming kernel may read channels [0, F/2) of such a block alone (fit_kernels.hpp: process_item, FOLD) when the mirror
-// half carries no information of its own: in fp32 when no element differs from its mirror partner by more than half a unit in
-// the last place of the block's largest element -- what the cast of an fp64 basis to fp32 leaves behind -- and in fp64 when the
-// halves agree exactly.  fb: the block's tile width; the band's half must consist of whole tiles.
-template <typename T>
-bool block_foldable(const T* a, int nfreqs, int nvec, int nrowblk, int fb, double* resid, double* amax) {
-  *resid = *amax = 0;
-  if (nrowblk != 1 || nfreqs < 2 || (nfreqs & 1) || fb <= 0 || (nfreqs / 2) % fb != 0) return false;
-  if (!mirror_residual(a, nfreqs, nvec, resid, amax)) return false;
-  if (sizeof(T) == 4) return *resid <= 0.5 * 1.1920928955078125e-07 * *amax;
-  return *resid == 0.0;
-}
 
 }  // namespace
 
@@ -223,7 +175,7 @@ struct cal_solver {
 };
 
 template <typename T>
-struct SolverT final : cal_solver {
+struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.hpp): what set-up decided about the problem
   using T2 = vec2_t<T>;
   hipStream_t stream = nullptr;
   // Synchronous copies go through the solver's OWN (non-blocking) stream, never the legacy stream: a copy there synchronises with
@@ -235,23 +187,10 @@ struct SolverT final : cal_solver {
     return hipStreamSynchronize(stream);
   }
   bool has_problem = false, has_data = false, has_gains = false, has_coef = false, has_opt = false;
-  // problem
-  int nants = 0, nfreqs = 0, fpad = 0, ngrps = 0, nbls = 0, ncoef = 0, nitems = 0, layout = 0;
-  // time slices (cal_problem_desc::nslices): independent fits held together; slice t owns antennas [t na_slice, (t + 1) na_slice),
-  // a contiguous run of the coefficient planes, its own loop state (state[par][t]), reduced sums (scal[4 t ..]) and loss history
-  int nslices = 1, na_slice = 0;
+  // time slices
   DevBuf slice_coff, slice_ipart_ptr, slice_ipart_idx, slice_ppart_ptr, slice_ppart_idx, slice_cblk;
   std::vector<int> h_slice_coff, h_slice_cblk;
-  bool fold = false;        // the single-baseline items read folded tiles: channels [0, nfreqs / 2) of a mirror-symmetric basis (process_item, FOLD)
-  bool small_loads = false; // every single-baseline item's tile fits kSmallLoads loads per thread: the narrow instance of fused_basis_kernel serves the loss / gradient passes
-  int nitems_simple = 0;   // items [0, nitems_simple) are single-baseline groups (fused_basis_kernel), the rest multi-baseline (fused_group_kernel)
-  int nitems_plain = 0;    // items [0, nitems_plain) of those are not covered by a head item of the multi-slice kernels
-  size_t lds_group_bytes = 0;
-  bool gc_direct = true;
-  size_t lds_bytes = 0;
-  long long gcp_len = 0;
   std::vector<int> h_grp_coff;
-  double basis_bytes = 0;
   // device buffers
   DevBuf tiles, bl_tile, bl_ant, runs, items, ant_ptr, ant_ent, coef_grp, grp_coff, grp_item_ptr, item_goff;
   DevBuf data_r, data_i, wgts;
@@ -275,24 +214,12 @@ struct SolverT final : cal_solver {
   std::vector<uint8_t> held;                   // hold_slices: [nslices], 1 = the slice enters every later run as stopped (empty: none)
   DevBuf fq_out, fq_gains;                     // fit_quality: chisq_ant | wsum_ant ([nants][nfreqs] doubles each, the exchange payload) | chisq_bl | wsum_bl; gains given for one evaluation
   DevBuf members, heads;                       // baselines that share tiles (bl_alias): member lists of the head items, head item indices
-  int nheads = 0;                              // heads[0 .. nheads_mfma): fused_multi_mfma_kernel (at most kMmMaxVec vectors); the rest: fused_multi_kernel
-  int nheads_mfma = 0;
   bool heads_one_pass = false;                 // the regularised step of the heads in ONE pass (all of them on fused_multi_mfma_kernel<.., REG = 2>)
-  bool heads_one_pass_local = false;           // ... as this rank's own heads allow (a communicator may clear heads_one_pass: agree_problem)
   bool reg_prepass = false;                    // the regularised gradient pass is preceded by a loss pass and the slices' alpha (enqueue_pass);
                                                // with a communicator agreed over the ranks: if one rank needs it, every rank runs it
-  int mm_grid = 0;                             // workgroups of the matrix-core multi-slice launch: its head list is dealt over the 8 XCDs (-1: empty slot)
-  size_t lds_multi_bytes = 0, lds_multi_mfma_bytes = 0;
   // dense (MFMA) path of the SHARED layout, fp32, one baseline per fitting group
   DevBuf mf_ops, mf_panels;                    // mf_ops: every basis block's packed MFMA operands (see mfma_pack_kernel / mfma_pack64_kernel)
-  int mf_npanels = 0;
-  bool mf_split2 = false;                      // ... in its one-image form (split2_kernels.hpp)
-  bool mf_split = false;                       // fp32: the split-bf16 kernel (split_kernels.hpp: super-panels of 4 panels) instead of fused_dense_kernel
   DevBuf mf_map;                               // [mf_grid] workgroup -> panel (-1: empty slot): XCD-affine dispatch of the dense launch
-  int mf_grid = 0;
-  size_t mf_lds_grad[2] = {0, 0}, mf_lds_loss[2] = {0, 0};  // per launch class
-  bool mf_ok = false;
-  int steps_per_sync = 1;                      // train steps enqueued between two host synchronisations of run()
   // small problems: a train step is two launches (fused pass, step_tail_kernel), replayed kGraphSteps at a time from a hipGraph
   int launch_mode = CAL_LAUNCH_AUTO;
   static constexpr int kGraphSteps = 16;       // even: the double-buffered loop state and gains end a replay where they began
@@ -331,8 +258,6 @@ struct SolverT final : cal_solver {
   cal_optimizer_desc opt{CAL_OPT_ADAMAX, 1e-3, 0.9, 0.999, 1e-7, 0.9, 0.0, 0.1, 0, 0, -0.5, 0.0, 0.0, 0.0, 0.0, 0.0};
   // LAMB: the optimizer's variables (g_r, g_i of every slice; the coefficient runs of every (slice, cal_problem_desc::grp_var) per plane)
   DevBuf lamb_vars, lamb_cvar_ptr, lamb_partial, lamb_ratio;
-  int lamb_nvar = 0, lamb_ncvar = 0;
-  bool lamb_ok = true;
   // ... over several ranks: a coefficient variable (slice t, grp_var w) is spread over the ranks that own its groups -> its two sums of
   // squares are all-reduced in slot t * lamb_nv + w of lamb_glob (the gain variables are replicated: every rank already holds their norms)
   DevBuf lamb_glob, lamb_slot;
@@ -422,39 +347,6 @@ struct SolverT final : cal_solver {
     h.nonfinite = 0;
   }
 
-  static int choose_fb(int nvec, int nfreqs) {
-    // widest channel block whose tile (nvec x FB) still fits the staging budget; never wider than the band needs
-    int cap = FbSet<T>::fb_min;
-    while (cap < FbSet<T>::fb_max && cap < nfreqs) cap *= 2;
-    for (int fb = std::min(cap, FbSet<T>::fb_max); fb >= FbSet<T>::fb_min; fb /= 2)
-      if ((long long)nvec * fb * (long long)sizeof(T) <= kTileBytes) return fb;
-    return -1;
-  }
-  static size_t group_lds_for(int fb) {
-    constexpr int M = FbSet<T>::fb_max;
-    if (fb == M) return group_lds_bytes<T, M>();
-    if (fb == M / 2) return group_lds_bytes<T, M / 2>();
-    if (fb == M / 4) return group_lds_bytes<T, M / 4>();
-    if (fb == M / 8) return group_lds_bytes<T, M / 8>();
-    return group_lds_bytes<T, M / 16>();
-  }
-  static size_t multi_lds_for(int fb) {
-    constexpr int M = FbSet<T>::fb_max;
-    if (fb == M) return multi_lds_bytes<T, M>();
-    if (fb == M / 2) return multi_lds_bytes<T, M / 2>();
-    if (fb == M / 4) return multi_lds_bytes<T, M / 4>();
-    if (fb == M / 8) return multi_lds_bytes<T, M / 8>();
-    return multi_lds_bytes<T, M / 16>();
-  }
-  static size_t lds_for(int fb, bool fold) {
-    constexpr int M = FbSet<T>::fb_max;
-    if (fb == M) return TileCfg<T, M>::lds_bytes(fold);
-    if (fb == M / 2) return TileCfg<T, M / 2>::lds_bytes(fold);
-    if (fb == M / 4) return TileCfg<T, M / 4>::lds_bytes(fold);
-    if (fb == M / 8) return TileCfg<T, M / 8>::lds_bytes(fold);
-    return TileCfg<T, M / 16>::lds_bytes(fold);
-  }
-
   // ------------------------------------------------------------------------------------------------------------
   // With a communicator attached, every decision a rank takes from its OWN shard and that changes what it exchanges must
   // be taken by all ranks together -- and a rank whose set-up fails must not leave the others waiting in a collective.
@@ -530,896 +422,163 @@ struct SolverT final : cal_solver {
     }
     return CAL_OK;
   }
+  // Set-up is three steps: reset, plan (problem_plan.hpp: every decision, on the host alone), upload.
   int set_problem_local(const cal_problem_desc* d) {
     HIP_TRY(hipSetDevice(device));
     has_problem = has_data = has_gains = has_coef = false;
     drop_graph();
     release_gain_basis();  // a new problem fits per channel until a basis is set again
-    if (!d || d->nants <= 0 || d->nfreqs <= 0 || d->ngrps <= 0 || d->nbls <= 0 || d->nbasis <= 0)
-      return fail(CAL_ERR_INVALID, "set_problem: non-positive dimension");
-    if (!d->basis_offset || !d->basis_nvec || !d->basis_nrowblk || !d->basis_data || !d->grp_basis || !d->grp_bl_start ||
-        !d->bl_ant0 || !d->bl_ant1)
-      return fail(CAL_ERR_INVALID, "set_problem: null pointer in problem description");
-    if (d->layout != CAL_LAYOUT_STREAM && d->layout != CAL_LAYOUT_SHARED) return fail(CAL_ERR_INVALID, "set_problem: bad layout");
-    if (d->grp_bl_start[0] != 0 || d->grp_bl_start[d->ngrps] != d->nbls)
-      return fail(CAL_ERR_INVALID, "set_problem: grp_bl_start must run from 0 to nbls");
-    nants = d->nants; nfreqs = d->nfreqs; ngrps = d->ngrps; nbls = d->nbls; layout = d->layout;
-    const int nbasis = d->nbasis;
-    std::vector<int> fb_u(nbasis);
-    int fb_used_max = 0;
-    for (int u = 0; u < nbasis; ++u) {
-      if (d->basis_nvec[u] <= 0 || d->basis_nrowblk[u] <= 0) return fail(CAL_ERR_INVALID, "set_problem: empty basis block %d", u);
-      const long long want = (long long)d->basis_nvec[u] * d->basis_nrowblk[u] * nfreqs;
-      if (d->basis_offset[u + 1] - d->basis_offset[u] != want)
-        return fail(CAL_ERR_INVALID, "set_problem: basis block %d has %lld elements, expected %lld", u,
-                    (long long)(d->basis_offset[u + 1] - d->basis_offset[u]), want);
-      fb_u[u] = choose_fb(d->basis_nvec[u], nfreqs);
-      if (fb_u[u] < 0)
-        return fail(CAL_ERR_UNSUPPORTED, "set_problem: basis block %d has %d vectors; at most %d are supported for this dtype", u,
-                    d->basis_nvec[u], (int)(kTileBytes / sizeof(T) / FbSet<T>::fb_min));
-      fb_used_max = std::max(fb_used_max, fb_u[u]);
-    }
-    // Row padding is a function of nfreqs alone (never of this rank's basis blocks or kernel choice): every rank of a
-    // sharded fit must lay the gains out identically and all-reduce the same number of reals.  pw = min(128,
-    // next_pow2(nfreqs)) is a multiple of every tile width in use and, for nfreqs > 64, of the dense kernel's chunk.
-    int pw = 8;
-    while (pw < 128 && pw < nfreqs) pw *= 2;
-    if (fb_used_max > pw) return fail(CAL_ERR_INVALID, "set_problem: internal error: tile width %d exceeds the row padding %d", fb_used_max, pw);
-    fpad = (nfreqs + pw - 1) / pw * pw;
-    if (d->kernel_path != CAL_PATH_AUTO && d->kernel_path != CAL_PATH_GENERAL && d->kernel_path != CAL_PATH_DENSE && d->kernel_path != CAL_PATH_DENSE_F32 &&
-        d->kernel_path != CAL_PATH_DENSE_SPLIT1 && d->kernel_path != CAL_PATH_GENERAL_FULL)
-      return fail(CAL_ERR_INVALID, "set_problem: bad kernel_path %d", d->kernel_path);
-    if (d->kernel_path == CAL_PATH_DENSE_F32 && !std::is_same<T, float>::value)
-      return fail(CAL_ERR_UNSUPPORTED, "set_problem: CAL_PATH_DENSE_F32 is the fp32 kernel on v_mfma_f32_32x32x2_f32; this solver is fp64");
-    if (d->kernel_path == CAL_PATH_DENSE_SPLIT1 && !std::is_same<T, float>::value)
-      return fail(CAL_ERR_UNSUPPORTED, "set_problem: CAL_PATH_DENSE_SPLIT1 is an fp32 kernel (split-bf16 operands); this solver is fp64");
-    const bool forced_dense = d->kernel_path == CAL_PATH_DENSE || d->kernel_path == CAL_PATH_DENSE_F32 || d->kernel_path == CAL_PATH_DENSE_SPLIT1;
-    bool want_split = std::is_same<T, float>::value && d->kernel_path != CAL_PATH_DENSE_F32;
-    for (int u = 0; u < nbasis && want_split; ++u) want_split = d->basis_nvec[u] <= kSplitMaxNvec;  // (wider blocks: the f32 kernel, up to 256 vectors)
-    // dense (matrix-core) path: eligibility, then -- for CAL_PATH_AUTO -- whether the problem fills the chip
-    bool dense_ok = layout == CAL_LAYOUT_SHARED && fpad % kChunk == 0;
-    for (int g = 0; g < ngrps && dense_ok; ++g) dense_ok = (d->grp_bl_start[g + 1] - d->grp_bl_start[g]) == 1;
-    for (int u = 0; u < nbasis && dense_ok; ++u) dense_ok = d->basis_nrowblk[u] == 1 && d->basis_nvec[u] <= DenseCfg<T>::max_nvec;
-    // the dense kernels address the per-sample arrays with 32-bit BYTE offsets; the widest sample is one (re, im) pair
-    if ((long long)(nbls + 2) * fpad * 2 * (long long)sizeof(T) >= (1LL << 32)) dense_ok = false;
-    // ... and its packed operands (two MFMA-native copies of every unique block) with 32-bit byte offsets from one base
-    long long dense_op_elems = 0;
-    for (int u = 0; u < nbasis && dense_ok; ++u)  // kilobyte positions: forward + adjoint (the same count for both dtypes' layouts up to padding)
-      dense_op_elems += want_split ? std::max(split_stream_bytes(fpad, d->basis_nvec[u], (d->basis_nvec[u] + 31) / 32), split2_stream_bytes(fpad, d->basis_nvec[u])) / 4
-                        : std::is_same<T, float>::value
-                            ? (long long)(fpad / 32) * ((d->basis_nvec[u] + 7) / 8) * 256 + (long long)(fpad / 32) * ((d->basis_nvec[u] + 31) / 32) * 4 * 256
-                            : (long long)(fpad / 16) * ((d->basis_nvec[u] + 7) / 8) * 128 + (long long)(fpad / 16) * ((d->basis_nvec[u] + 15) / 16) * 2 * 128;
-    if (dense_op_elems * (long long)(want_split ? 4 : sizeof(T)) >= (1LL << 32)) dense_ok = false;
-    if (forced_dense && !dense_ok)
-      return fail(CAL_ERR_UNSUPPORTED, "set_problem: CAL_PATH_DENSE needs the SHARED layout, one baseline per fitting group, "
-                  "basis_nvec <= %d and nfreqs > 64", DenseCfg<T>::max_nvec);
-    // a panel of 16 baselines occupies one CU for 60-70 us whatever the problem size; below ~2000 baselines the panels do
-    // not fill the chip and the general kernel (one workgroup per baseline) is 2-3x faster (HERA-37 fp32: 25 vs 71 us)
-    // (with a communicator the ranks then agree on ONE path -- the exchange payload of the "sum" regulariser differs between
-    // the two -- in set_problem, behind all the rank-local work)
-    const bool want_mfma = dense_ok && d->kernel_path != CAL_PATH_GENERAL && d->kernel_path != CAL_PATH_GENERAL_FULL && (forced_dense || nbls >= 2048);
-    for (int b = 0; b < d->nbls; ++b) {
-      if (d->bl_ant0[b] < 0 || d->bl_ant0[b] >= nants || d->bl_ant1[b] < 0 || d->bl_ant1[b] >= nants)
-        return fail(CAL_ERR_INVALID, "set_problem: baseline %d has an antenna index outside [0, %d)", b, nants);
-    }
-    // ---- time slices: independent fits over disjoint antenna ranges, listed slice by slice
-    const int NSL = d->nslices > 1 ? d->nslices : 1;
-    if (NSL > CAL_MAX_SLICES) return fail(CAL_ERR_UNSUPPORTED, "set_problem: %d time slices; at most %d are supported", NSL, CAL_MAX_SLICES);
-    if (nants % NSL != 0) return fail(CAL_ERR_INVALID, "set_problem: nants = %d is not a multiple of nslices = %d", nants, NSL);
-    const int nas = nants / NSL;
-    std::vector<int> grp_slice(ngrps, 0);
-    if (NSL > 1) {
-      std::vector<char> seen(NSL, 0);
-      for (int g = 0; g < ngrps; ++g) {
-        const int b0 = d->grp_bl_start[g], b1 = d->grp_bl_start[g + 1];
-        if (b0 < 0 || b1 > nbls || b1 <= b0) return fail(CAL_ERR_INVALID, "set_problem: group %d has no baselines", g);
-        const int t = d->bl_ant0[b0] / nas;
-        for (int b = b0; b < b1; ++b)
-          if (d->bl_ant0[b] / nas != t || d->bl_ant1[b] / nas != t)
-            return fail(CAL_ERR_INVALID, "set_problem: baseline %d of group %d leaves time slice %d (antennas %d, %d; %d antennas per slice)", b, g, t,
-                        d->bl_ant0[b], d->bl_ant1[b], nas);
-        if (g > 0 && t < grp_slice[g - 1]) return fail(CAL_ERR_INVALID, "set_problem: fitting groups must be listed slice by slice (group %d)", g);
-        grp_slice[g] = t;
-        seen[t] = 1;
-      }
-      for (int t = 0; t < NSL; ++t)
-        if (!seen[t]) return fail(CAL_ERR_INVALID, "set_problem: time slice %d has no fitting group", t);
-    }
-    nslices = NSL;
-    na_slice = nas;
-    CAL_TRY(size_state(NSL));
-    // ---- groups, coefficient offsets
-    h_grp_coff.assign(ngrps + 1, 0);
-    std::vector<int> grp_of_bl(nbls);
-    for (int g = 0; g < ngrps; ++g) {
-      const int u = d->grp_basis[g];
-      if (u < 0 || u >= nbasis) return fail(CAL_ERR_INVALID, "set_problem: group %d points at basis %d", g, u);
-      if (d->grp_bl_start[g + 1] <= d->grp_bl_start[g]) return fail(CAL_ERR_INVALID, "set_problem: group %d has no baselines", g);
-      h_grp_coff[g + 1] = h_grp_coff[g] + d->basis_nvec[u];
-      for (int b = d->grp_bl_start[g]; b < d->grp_bl_start[g + 1]; ++b) {
-        grp_of_bl[b] = g;
-        const int rb = d->bl_rowblk ? d->bl_rowblk[b] : 0;
-        if (rb < 0 || rb >= d->basis_nrowblk[u]) return fail(CAL_ERR_INVALID, "set_problem: baseline %d row block %d out of range", b, rb);
-      }
-    }
-    ncoef = h_grp_coff[ngrps];
-    h_slice_coff.assign(nslices + 1, ncoef);
-    h_slice_coff[0] = 0;
-    for (int g = ngrps - 1; g >= 0; --g) h_slice_coff[grp_slice[g]] = h_grp_coff[g];  // first group of every slice
-    h_slice_coff[0] = 0;
-    CAL_TRY(slice_coff.alloc((nslices + 1) * sizeof(int), false));
-    HIP_TRY(copy_sync(slice_coff.p, h_slice_coff.data(), (nslices + 1) * sizeof(int), hipMemcpyHostToDevice));
-    {
-      // the optimizer's variables (LAMB): a new coefficient variable wherever the (slice, grp_var) of the groups changes
-      lamb_ok = true;
-      std::vector<int> cptr;
-      lamb_cvar_slice.clear();
-      lamb_cvar_id.clear();
-      for (int g = 0; g < ngrps; ++g) {
-        const int var = d->grp_var ? d->grp_var[g] : 0;
-        if (var < 0) return fail(CAL_ERR_INVALID, "set_problem: grp_var[%d] = %d is negative", g, var);
-        // (groups of one variable scattered over a slice: fine for every element-wise optimizer; LAMB is refused in set_optimizer)
-        if (g > 0 && grp_slice[g] == grp_slice[g - 1] && d->grp_var && var < d->grp_var[g - 1]) lamb_ok = false;
-        if (g == 0 || grp_slice[g] != grp_slice[g - 1] || (d->grp_var && var != d->grp_var[g - 1])) {
-          cptr.push_back(h_grp_coff[g]);
-          lamb_cvar_slice.push_back(grp_slice[g]);
-          lamb_cvar_id.push_back(var);
-        }
-      }
-      lamb_ncvar = (int)cptr.size();
-      cptr.push_back(ncoef);
-      lamb_nvar = 2 * nslices + 2 * lamb_ncvar;
-      std::vector<LambVar> vars;
-      for (int t = 0; t < nslices; ++t)
-        for (int c = 0; c < 2; ++c) vars.push_back(LambVar{(long long)t * na_slice * fpad * 2 + c, (long long)na_slice * fpad, 2, 0});
-      for (int plane = 0; plane < 2; ++plane)
-        for (int k = 0; k < lamb_ncvar; ++k) vars.push_back(LambVar{(long long)plane * ncoef + cptr[k], (long long)(cptr[k + 1] - cptr[k]), 1, 1});
-      CAL_TRY(lamb_vars.alloc(vars.size() * sizeof(LambVar), false));
-      HIP_TRY(copy_sync(lamb_vars.p, vars.data(), vars.size() * sizeof(LambVar), hipMemcpyHostToDevice));
-      CAL_TRY(lamb_cvar_ptr.alloc(cptr.size() * sizeof(int), false));
-      HIP_TRY(copy_sync(lamb_cvar_ptr.p, cptr.data(), cptr.size() * sizeof(int), hipMemcpyHostToDevice));
-      CAL_TRY(lamb_partial.alloc((size_t)lamb_nvar * kLambSeg * 2 * sizeof(double)));
-      CAL_TRY(lamb_ratio.alloc((size_t)lamb_nvar * sizeof(double)));
-    }
-    // ---- baselines that read another baseline's tiles (STREAM layout): the same physical baseline in several time slices
-    std::vector<int> alias_root(nbls, -1);  // -1: owns its tiles
-    if (d->bl_alias && layout == CAL_LAYOUT_STREAM) {
-      for (int b = 0; b < nbls; ++b) {
-        const int r = d->bl_alias[b];
-        if (r < 0 || r == b) continue;
-        if (r >= nbls || (d->bl_alias[r] >= 0 && d->bl_alias[r] != r))
-          return fail(CAL_ERR_INVALID, "set_problem: bl_alias[%d] = %d must name a baseline that owns its tiles", b, r);
-        const int g = grp_of_bl[b], gr = grp_of_bl[r];
-        if (d->grp_basis[g] != d->grp_basis[gr] || (d->bl_rowblk ? d->bl_rowblk[b] != d->bl_rowblk[r] : false))
-          return fail(CAL_ERR_INVALID, "set_problem: bl_alias[%d] = %d: the two baselines use different basis rows", b, r);
-        if (d->grp_bl_start[g + 1] - d->grp_bl_start[g] != 1 || d->grp_bl_start[gr + 1] - d->grp_bl_start[gr] != 1)
-          return fail(CAL_ERR_INVALID, "set_problem: bl_alias is for single-baseline fitting groups (baseline %d)", b);
-        alias_root[b] = r;
-      }
-    }
-    // ---- folded tiles: decided once per problem, from the description and the dtype alone (never from the communicator, the
-    // launch mode or the device: solvers that are compared bit for bit must take the same form).  The streaming layout, every
-    // item served by fused_basis_kernel (single-baseline groups, no shared tiles: the multi-slice and the group kernels keep
-    // full tiles) and every basis block in use mirror-symmetric; CAL_PATH_GENERAL_FULL keeps the full tiles.
-    fold = layout == CAL_LAYOUT_STREAM && d->kernel_path != CAL_PATH_GENERAL_FULL;
-    for (int g = 0; g < ngrps && fold; ++g) fold = d->grp_bl_start[g + 1] - d->grp_bl_start[g] == 1;
-    for (int b = 0; b < nbls && fold; ++b) fold = alias_root[b] < 0;
-    std::vector<char> basis_used(nbasis, 0);
-    for (int g = 0; g < ngrps; ++g) basis_used[d->grp_basis[g]] = 1;
-    for (int u = 0; u < nbasis && fold; ++u) {
-      double resid, amax;
-      if (basis_used[u])
-        fold = block_foldable(static_cast<const T*>(d->basis_data) + d->basis_offset[u], nfreqs, d->basis_nvec[u], d->basis_nrowblk[u], fb_u[u], &resid, &amax);
-    }
-    const int ftile = fold ? nfreqs / 2 : fpad;  // channels a baseline's tiles cover
-    lds_bytes = 0;
-    for (int u = 0; u < nbasis; ++u) lds_bytes = std::max(lds_bytes, lds_for(fb_u[u], fold));
-    std::vector<char> in_alias_set(nbls, 0);
-    const bool multi_ok = (long long)(nbls + 1) * fpad < (1LL << 31) && (long long)nants * fpad < (1LL << 31);  // the multi kernel's 32-bit sample offsets
-    for (int b = 0; b < nbls; ++b)
-      if (alias_root[b] >= 0 && multi_ok) in_alias_set[b] = in_alias_set[alias_root[b]] = 1;  // (slices_share_heads: see below)
+    ProblemPlan<T> p;
+    CAL_TRY(plan_problem(d, p));
+    return upload_plan(d, p);
+  }
+  // allocation of max(v.size(), min_count) elements (not zeroed) + synchronous copy on the solver's stream
+  template <typename X>
+  int upload(DevBuf& b, const std::vector<X>& v, size_t min_count = 0, bool sync = true) {
+    CAL_TRY(b.alloc(std::max(v.size(), min_count) * sizeof(X), false));
+    if (v.empty()) return CAL_OK;
+    HIP_TRY(hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(X), hipMemcpyHostToDevice, stream));
+    if (sync) HIP_TRY(hipStreamSynchronize(stream));
+    return CAL_OK;
+  }
+  int upload_plan(const cal_problem_desc* d, const ProblemPlan<T>& p) {
+    static_cast<PlanScalars&>(*this) = p;
+    local_reg_plan();
+    lamb_cvar_slice = p.lamb_cvar_slice; lamb_cvar_id = p.lamb_cvar_id;
+    h_grp_coff = p.grp_coff; h_slice_coff = p.slice_coff; h_slice_cblk = p.slice_cblk; h_cs_grp = p.cs_grp;
+    CAL_TRY(size_state(nslices));
+    CAL_TRY(upload(slice_coff, p.slice_coff));
+    CAL_TRY(upload(lamb_vars, p.lamb_vars));
+    CAL_TRY(upload(lamb_cvar_ptr, p.lamb_cvar_ptr));
+    CAL_TRY(lamb_partial.alloc((size_t)lamb_nvar * kLambSeg * 2 * sizeof(double)));
+    CAL_TRY(lamb_ratio.alloc((size_t)lamb_nvar * sizeof(double)));
 
     // ---- unique basis blocks -> tile-major device layout
-    const long long raw_elems = d->basis_offset[nbasis];
     DevBuf raw, utiles;
-    CAL_TRY(raw.alloc((size_t)raw_elems * sizeof(T), false));
-    HIP_TRY(hipMemcpyAsync(raw.p, d->basis_data, (size_t)raw_elems * sizeof(T), hipMemcpyHostToDevice, stream));
-    std::vector<long long> uoff(nbasis + 1, 0);
-    // (folded: the lower half band of the blocks in use -- one row block each -- verbatim; the others are not needed)
-    for (int u = 0; u < nbasis; ++u)
-      uoff[u + 1] = uoff[u] + (fold ? (basis_used[u] ? (long long)ftile * d->basis_nvec[u] : 0LL) : (long long)d->basis_nrowblk[u] * fpad * d->basis_nvec[u]);
+    const size_t raw_bytes = (size_t)d->basis_offset[p.nbasis] * sizeof(T);
+    CAL_TRY(raw.alloc(raw_bytes, false));
+    HIP_TRY(hipMemcpyAsync(raw.p, d->basis_data, raw_bytes, hipMemcpyHostToDevice, stream));
     // (+ a zeroed pad: fused_multi_mfma_kernel reads on past the last rows of a tile, against zero coefficients)
-    CAL_TRY(utiles.alloc(((size_t)uoff[nbasis] + kMmTilePadElems) * sizeof(T), false));
-    HIP_TRY(hipMemsetAsync(utiles.as<T>() + uoff[nbasis], 0, kMmTilePadElems * sizeof(T), stream));
-    for (int u = 0; u < nbasis; ++u) {
-      const long long n = uoff[u + 1] - uoff[u];
+    CAL_TRY(utiles.alloc(((size_t)p.uoff.back() + kMmTilePadElems) * sizeof(T), false));
+    HIP_TRY(hipMemsetAsync(utiles.as<T>() + p.uoff.back(), 0, kMmTilePadElems * sizeof(T), stream));
+    for (int u = 0; u < p.nbasis; ++u) {
+      const long long n = p.uoff[u + 1] - p.uoff[u];
       if (n == 0) continue;
-      if (fold)  // channels [0, nfreqs / 2) of the block's only row block: whole tiles, no padding
-        hipLaunchKernelGGL(retile_kernel<T>, dim3(grid_for(n)), dim3(256), 0, stream, raw.as<T>() + d->basis_offset[u],
-                           utiles.as<T>() + uoff[u], ftile, ftile, d->basis_nvec[u], 1, fb_u[u]);
-      else
-        hipLaunchKernelGGL(retile_kernel<T>, dim3(grid_for(n)), dim3(256), 0, stream, raw.as<T>() + d->basis_offset[u],
-                           utiles.as<T>() + uoff[u], nfreqs, fpad, d->basis_nvec[u], d->basis_nrowblk[u], fb_u[u]);
+      // (folded: channels [0, nfreqs / 2) of the block's only row block: whole tiles, no padding)
+      hipLaunchKernelGGL(retile_kernel<T>, dim3(grid_for(n)), dim3(256), 0, stream, raw.as<T>() + d->basis_offset[u], utiles.as<T>() + p.uoff[u],
+                         fold ? p.ftile : nfreqs, fold ? p.ftile : fpad, d->basis_nvec[u], fold ? 1 : d->basis_nrowblk[u], p.fb_u[u]);
     }
     HIP_TRY(hipGetLastError());
-    std::vector<long long> h_bl_tile(nbls);
-    basis_bytes = 0;
-    if (layout == CAL_LAYOUT_SHARED) {
-      for (int b = 0; b < nbls; ++b) {
-        const int u = d->grp_basis[grp_of_bl[b]];
-        const int rb = d->bl_rowblk ? d->bl_rowblk[b] : 0;
-        h_bl_tile[b] = uoff[u] + (long long)rb * fpad * d->basis_nvec[u];
-      }
+    if (layout == CAL_LAYOUT_SHARED) {  // the baselines read the unique blocks themselves
       HIP_TRY(hipStreamSynchronize(stream));
       tiles.release();
       tiles.p = utiles.p; tiles.bytes = utiles.bytes;
       utiles.p = nullptr; utiles.bytes = 0;
-      basis_bytes = (double)uoff[nbasis] / fpad * nfreqs * sizeof(T);
     } else {
-      // every baseline owns its tiles, except that consecutive baselines of one group with the same row block (a
-      // redundant set: one forward product for all of them) share one copy
-      std::vector<CopyJob> jobs;
-      jobs.reserve(nbls);
-      long long off = 0;
-      for (int b = 0; b < nbls; ++b) {
-        const int u = d->grp_basis[grp_of_bl[b]];
-        const int rb = d->bl_rowblk ? d->bl_rowblk[b] : 0;
-        const long long n = (long long)ftile * d->basis_nvec[u];
-        const bool alias = b > 0 && grp_of_bl[b - 1] == grp_of_bl[b] && (d->bl_rowblk ? d->bl_rowblk[b - 1] : 0) == rb;
-        if (alias) {
-          h_bl_tile[b] = h_bl_tile[b - 1];
-          continue;
-        }
-        if (alias_root[b] >= 0) continue;  // filled in below, once its owner's offset is known (the owner may come later)
-        jobs.push_back(CopyJob{uoff[u] + (long long)rb * n, off, n});
-        h_bl_tile[b] = off;
-        off += n;
-      }
-      for (int b = 0; b < nbls; ++b)
-        if (alias_root[b] >= 0) h_bl_tile[b] = h_bl_tile[alias_root[b]];
-      CAL_TRY(tiles.alloc(((size_t)off + kMmTilePadElems) * sizeof(T), false));
-      HIP_TRY(hipMemsetAsync(tiles.as<T>() + off, 0, kMmTilePadElems * sizeof(T), stream));
+      CAL_TRY(tiles.alloc(((size_t)p.tiles_elems + kMmTilePadElems) * sizeof(T), false));
+      HIP_TRY(hipMemsetAsync(tiles.as<T>() + p.tiles_elems, 0, kMmTilePadElems * sizeof(T), stream));
       DevBuf djobs;
-      CAL_TRY(djobs.alloc(jobs.size() * sizeof(CopyJob), false));
-      HIP_TRY(hipMemcpyAsync(djobs.p, jobs.data(), jobs.size() * sizeof(CopyJob), hipMemcpyHostToDevice, stream));
-      hipLaunchKernelGGL(tile_copy_kernel<T>, dim3((unsigned)jobs.size()), dim3(256), 0, stream, utiles.as<T>(), tiles.as<T>(), djobs.as<CopyJob>());
+      CAL_TRY(upload(djobs, p.jobs, 0, false));
+      hipLaunchKernelGGL(tile_copy_kernel<T>, dim3((unsigned)p.jobs.size()), dim3(256), 0, stream, utiles.as<T>(), tiles.as<T>(), djobs.as<CopyJob>());
       HIP_TRY(hipGetLastError());
       HIP_TRY(hipStreamSynchronize(stream));
-      basis_bytes = fold ? (double)off * sizeof(T) : (double)off / fpad * nfreqs * sizeof(T);
     }
-    mf_ok = false;
-    mf_split = false;
-    mf_split2 = false;
-    if (want_mfma && want_split) {
-      if constexpr (std::is_same<T, float>::value) {
-        // ---- fp32, split-bf16 operands (split_kernels.hpp): super-panels of kSpWaves panels (64 baselines) with the same basis block and slice;
-        // an item carries at most kSplitNT vector tiles: a block of more than 128 vectors is two items per super-panel (each with its own packed
-        // stream: the whole forward, half of the adjoint tiles)
-        struct Half { int tile0, ntiles; long long obyte; };
-        std::vector<std::vector<Half>> halves(nbasis);
-        long long obytes = 0;
-        const bool v2 = d->kernel_path != CAL_PATH_DENSE_SPLIT1;  // the one-image form (split2_kernels.hpp) unless the first one is asked for by name
-        for (int u = 0; u < nbasis; ++u) {
-          const int ntu = (d->basis_nvec[u] + 31) / 32;
-          halves[u] = {Half{0, ntu, 0}};  // (kSplitNT = 8 tiles fit one item since the kernel runs one workgroup per CU)
-          for (Half& h : halves[u]) {
-            h.obyte = obytes;
-            obytes += v2 ? split2_stream_bytes(fpad, d->basis_nvec[u]) : split_stream_bytes(fpad, d->basis_nvec[u], h.ntiles);
-          }
-        }
-        CAL_TRY(mf_ops.alloc((size_t)obytes, false));
-        for (int u = 0; u < nbasis; ++u)
-          for (const Half& h : halves[u]) {
-            if (v2)
-              hipLaunchKernelGGL(split2_pack_kernel, dim3(grid_for((long long)fpad * 256)), dim3(256), 0, stream, raw.as<float>() + d->basis_offset[u],
-                                 mf_ops.as<unsigned char>() + h.obyte, nfreqs, fpad, d->basis_nvec[u]);
-            else
-              hipLaunchKernelGGL(split_pack_kernel, dim3(grid_for(split_stream_bytes(fpad, d->basis_nvec[u], h.ntiles) / 6)), dim3(256), 0, stream,
-                                 raw.as<float>() + d->basis_offset[u], reinterpret_cast<unsigned short*>(mf_ops.as<unsigned char>() + h.obyte), nfreqs, fpad,
-                                 d->basis_nvec[u], h.tile0, h.ntiles);
-          }
-        HIP_TRY(hipGetLastError());
-        std::vector<std::vector<int>> by_u((size_t)nbasis * nslices);
-        for (int b = 0; b < nbls; ++b) by_u[(size_t)d->grp_basis[grp_of_bl[b]] * nslices + grp_slice[grp_of_bl[b]]].push_back(b);
-        std::vector<int> uorder((size_t)nbasis * nslices);
-        std::iota(uorder.begin(), uorder.end(), 0);
-        std::stable_sort(uorder.begin(), uorder.end(), [&](int a, int b) { return d->basis_nvec[a / nslices] > d->basis_nvec[b / nslices]; });
-        std::vector<PanelItem> h_panels;
-        std::vector<double> h_cost;
-        const int wide = kPanel * kSpWaves;
-        for (int us : uorder) {
-          const int u = us / nslices;
+    // ---- dense path: every block's packed MFMA operands, the panel records, the workgroup -> panel map
+    if (p.mf_ok) {
+      CAL_TRY(mf_ops.alloc((size_t)p.op_off.back(), false));
+      for (int u = 0; u < p.nbasis; ++u) {
+        unsigned char* dst = mf_ops.as<unsigned char>() + p.op_off[u];
+        const long long bytes = p.op_off[u + 1] - p.op_off[u];
+        if constexpr (std::is_same<T, float>::value) {
+          const float* src = raw.as<float>() + d->basis_offset[u];
           const int nv = d->basis_nvec[u];
-          for (size_t i = 0; i < by_u[us].size(); i += wide) {
-            for (const Half& h : halves[u]) {
-              for (int w = 0; w < kSpWaves; ++w) {
-                PanelItem pi{};
-                pi.slice = us % nslices;
-                for (int k = 0; k < kPanel; ++k) {
-                  const size_t at = i + (size_t)w * kPanel + k;
-                  const int b = at < by_u[us].size() ? by_u[us][at] : -1;
-                  pi.bl[k] = b;
-                  pi.coff[k] = b >= 0 ? h_grp_coff[grp_of_bl[b]] : 0;
-                  pi.ant[k] = b >= 0 ? make_int2(d->bl_ant0[b], d->bl_ant1[b]) : make_int2(0, 0);
-                }
-                pi.a_kf4 = h.obyte / 4;
-                pi.a_fk4 = 0;
-                pi.nvec = nv;
-                pi.nvp2 = (nv + 15) / 16 * 16;
-                pi.nvp32 = 32 * h.ntiles;
-                pi.tile0 = h.tile0;
-                h_panels.push_back(pi);
-              }
-              // an item's time on a CU: per channel-block pair two element stages + its groups of 24 MFMAs
-              h_cost.push_back((fpad / 64) * (3000.0 + 900.0 * split_groups_per_pair(nv, h.ntiles)));
-            }
-          }
-        }
-        CAL_TRY(order_panels(h_panels, h_cost, kSpWaves));
-        mf_lds_grad[0] = mf_lds_loss[0] = v2 ? (size_t)kS2Lds : split_lds_bytes();
-        if (v2) {
-          HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_dense_split2_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mf_lds_grad[0]));
-          HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_dense_split2_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mf_lds_loss[0]));
+          if (mf_split2)
+            hipLaunchKernelGGL(split2_pack_kernel, dim3(grid_for((long long)fpad * 256)), dim3(256), 0, stream, src, dst, nfreqs, fpad, nv);
+          else if (mf_split)
+            hipLaunchKernelGGL(split_pack_kernel, dim3(grid_for(bytes / 6)), dim3(256), 0, stream, src, reinterpret_cast<unsigned short*>(dst), nfreqs, fpad,
+                               nv, 0, (nv + 31) / 32);
+          else
+            hipLaunchKernelGGL(mfma_pack_kernel, dim3(grid_for(bytes / 4)), dim3(256), 0, stream, src, reinterpret_cast<float*>(dst), nfreqs, fpad, nv,
+                               (nv + 31) / 32 * 32);
         } else {
-          HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_dense_split_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mf_lds_grad[0]));
-          HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_dense_split_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mf_lds_loss[0]));
+          hipLaunchKernelGGL(mfma_pack64_kernel, dim3(grid_for(bytes / 8)), dim3(256), 0, stream, raw.as<double>() + d->basis_offset[u],
+                             reinterpret_cast<double*>(dst), nfreqs, fpad, d->basis_nvec[u]);
         }
-        mf_ok = true;
-        mf_split = true;
-        mf_split2 = v2;
       }
-    } else if (want_mfma) {
-      if constexpr (std::is_same<T, float>::value) {
-        std::vector<long long> okf4(nbasis + 1, 0), ofk4(nbasis + 1, 0);
-        std::vector<int> nvp2(nbasis), nvp32(nbasis);
-        int nvec_max = 0;
-        for (int u = 0; u < nbasis; ++u) {
-          nvp2[u] = (d->basis_nvec[u] + 15) / 16 * 16;
-          nvp32[u] = (d->basis_nvec[u] + 31) / 32 * 32;
-          nvec_max = std::max(nvec_max, d->basis_nvec[u]);
-          okf4[u + 1] = okf4[u] + (long long)(fpad / 32) * ((d->basis_nvec[u] + 7) / 8 + nvp32[u] / 32 * 4) * 256;
-        }
-        CAL_TRY(mf_ops.alloc((size_t)okf4[nbasis] * sizeof(float), false));
-        for (int u = 0; u < nbasis; ++u)
-          hipLaunchKernelGGL(mfma_pack_kernel, dim3(grid_for(okf4[u + 1] - okf4[u])), dim3(256), 0, stream,
-                             raw.as<float>() + d->basis_offset[u], mf_ops.as<float>() + okf4[u], nfreqs, fpad, d->basis_nvec[u], nvp32[u]);
-        HIP_TRY(hipGetLastError());
-        // panels of kPanel baselines with the same basis, heaviest first
-        // (a panel never mixes time slices: one loop state, one alpha per panel)
-        std::vector<std::vector<int>> by_u((size_t)nbasis * nslices);
-        for (int b = 0; b < nbls; ++b) by_u[(size_t)d->grp_basis[grp_of_bl[b]] * nslices + grp_slice[grp_of_bl[b]]].push_back(b);
-        std::vector<int> uorder((size_t)nbasis * nslices);
-        std::iota(uorder.begin(), uorder.end(), 0);
-        std::stable_sort(uorder.begin(), uorder.end(), [&](int a, int b) { return d->basis_nvec[a / nslices] > d->basis_nvec[b / nslices]; });
-        // Panels of more than four vector tiles first, then the rest (two bodies of ONE launch); inside a class the
-        // heaviest panels come first (the hardware dispatches workgroups in index order, so the tail is made of the lightest).
-        // Per-XCD panel lists (all panels of a basis block on one XCD, its packed operands L2-resident there: the L2 hit
-        // rate of the operand requests is only 55-65 % without them) measured 3-5 % SLOWER with every generation of this
-        // kernel: panels of one block then walk the same lines in step.
-        std::vector<PanelItem> h_panels;
-        std::vector<double> h_cost;
-        for (int us : uorder) {
-          const int u = us / nslices;
-          for (size_t i = 0; i < by_u[us].size(); i += kPanel) {
-            PanelItem pi{};
-            pi.slice = us % nslices;
-            for (int k = 0; k < kPanel; ++k) {
-              const int b = i + k < by_u[us].size() ? by_u[us][i + k] : -1;
-              pi.bl[k] = b;
-              pi.coff[k] = b >= 0 ? h_grp_coff[grp_of_bl[b]] : 0;
-              pi.ant[k] = b >= 0 ? make_int2(d->bl_ant0[b], d->bl_ant1[b]) : make_int2(0, 0);
-            }
-            pi.a_kf4 = okf4[u];
-            pi.a_fk4 = 0;
-            pi.nvec = d->basis_nvec[u];
-            pi.nvp2 = nvp2[u];
-            pi.nvp32 = nvp32[u];
-            h_panels.push_back(pi);
-            // a panel's time on a CU: a fixed part (prologue, element stage, epilogue) + its MFMA positions (stamps of the HERA-350 pass)
-            h_cost.push_back(60e3 + 600.0 * (fpad / kChunk) * ((d->basis_nvec[u] + 7) / 8 + nvp32[u] / 32 * 4));
-          }
-        }
-        CAL_TRY(order_panels(h_panels, h_cost));
-        // one launch serves both panel classes (up to 4 / up to 8 vector tiles): the larger of their LDS footprints
-        mf_lds_grad[0] = std::max(dense_lds_bytes(nvec_max, true, nvec_max > 128 ? 8 : 4), dense_lds_bytes(std::min(nvec_max, 128), true, 4));
-        mf_lds_loss[0] = std::max(dense_lds_bytes(nvec_max, false, nvec_max > 128 ? 8 : 4), dense_lds_bytes(std::min(nvec_max, 128), false, 4));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_dense_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mf_lds_grad[0]));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_dense_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mf_lds_loss[0]));
-        mf_ok = true;
-      } else {
-        // ---- double precision: v_mfma_f64_16x16x4_f64 (dense64_kernels.hpp).  Two panel classes (bodies of one launch): blocks
-        // of more than 128 vectors with panels of 8 baselines (one column tile, 16 gradient tiles), the rest with panels of 16
-        std::vector<long long> okf(nbasis + 1, 0);
-        int nvec_a = 0, nvec_b = 0;
-        for (int u = 0; u < nbasis; ++u) {
-          const int nv = d->basis_nvec[u];
-          (nv > 128 ? nvec_a : nvec_b) = std::max(nv > 128 ? nvec_a : nvec_b, nv);
-          okf[u + 1] = okf[u] + (long long)(fpad / kCB64) * ((nv + 7) / 8 + (nv + kVT64 - 1) / kVT64 * 2) * 128;
-        }
-        CAL_TRY(mf_ops.alloc((size_t)okf[nbasis] * sizeof(double), false));
-        for (int u = 0; u < nbasis; ++u)
-          hipLaunchKernelGGL(mfma_pack64_kernel, dim3(grid_for(okf[u + 1] - okf[u])), dim3(256), 0, stream,
-                             raw.as<double>() + d->basis_offset[u], mf_ops.as<double>() + okf[u], nfreqs, fpad, d->basis_nvec[u]);
-        HIP_TRY(hipGetLastError());
-        std::vector<std::vector<int>> by_u((size_t)nbasis * nslices);
-        for (int b = 0; b < nbls; ++b) by_u[(size_t)d->grp_basis[grp_of_bl[b]] * nslices + grp_slice[grp_of_bl[b]]].push_back(b);
-        std::vector<int> uorder((size_t)nbasis * nslices);
-        std::iota(uorder.begin(), uorder.end(), 0);
-        std::stable_sort(uorder.begin(), uorder.end(), [&](int a, int b) { return d->basis_nvec[a / nslices] > d->basis_nvec[b / nslices]; });
-        std::vector<PanelItem> h_panels;
-        std::vector<double> h_cost;
-        for (int us : uorder) {
-          const int u = us / nslices;
-          const int width = d->basis_nvec[u] > 128 ? 8 : 16;
-          for (size_t i = 0; i < by_u[us].size(); i += width) {
-            PanelItem pi{};
-            pi.slice = us % nslices;
-            for (int k = 0; k < kPanel; ++k) {
-              const int b = k < width && i + k < by_u[us].size() ? by_u[us][i + k] : -1;
-              pi.bl[k] = b;
-              pi.coff[k] = b >= 0 ? h_grp_coff[grp_of_bl[b]] : 0;
-              pi.ant[k] = b >= 0 ? make_int2(d->bl_ant0[b], d->bl_ant1[b]) : make_int2(0, 0);
-            }
-            pi.a_kf4 = okf[u];
-            pi.a_fk4 = 0;
-            pi.nvec = d->basis_nvec[u];
-            h_panels.push_back(pi);
-            h_cost.push_back(60e3 + 300.0 * (width / 8) * (fpad / (4 * kCB64)) * ((d->basis_nvec[u] + 7) / 8 + (d->basis_nvec[u] + kVT64 - 1) / kVT64 * 2));
-          }
-        }
-        CAL_TRY(order_panels(h_panels, h_cost));
-        mf_lds_grad[0] = std::max(dense64_lds_bytes(nvec_a, 1, true), dense64_lds_bytes(nvec_b, 2, true));
-        mf_lds_loss[0] = std::max(dense64_lds_bytes(nvec_a, 1, false), dense64_lds_bytes(nvec_b, 2, false));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_dense64_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mf_lds_grad[0]));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_dense64_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mf_lds_loss[0]));
-        mf_ok = true;
+      HIP_TRY(hipGetLastError());
+      if (nslices > 1) {
+        CAL_TRY(upload(slice_ppart_ptr, p.slice_ppart_ptr, 0, false));
+        CAL_TRY(upload(slice_ppart_idx, p.slice_ppart_idx, 0, false));
+        HIP_TRY(hipStreamSynchronize(stream));
       }
+      CAL_TRY(upload(mf_panels, p.panels, 0, false));
+      CAL_TRY(upload(mf_map, p.panel_map, 0, false));
+      HIP_TRY(hipStreamSynchronize(stream));
     }
     raw.release();
-    CAL_TRY(bl_tile.alloc(nbls * sizeof(long long), false));
-    HIP_TRY(copy_sync(bl_tile.p, h_bl_tile.data(), nbls * sizeof(long long), hipMemcpyHostToDevice));
-    h_cs_grp.assign(ngrps, CsGroup{});
-    for (int g = 0; g < ngrps; ++g) {
-      const int u = d->grp_basis[g];
-      int lg = 0;
-      while ((1 << lg) < fb_u[u]) ++lg;
-      h_cs_grp[g] = CsGroup{d->grp_bl_start[g], d->grp_bl_start[g + 1], d->basis_nvec[u], h_grp_coff[g], lg, grp_slice[g], 0, 0};
-    }
+    CAL_TRY(upload(bl_tile, p.bl_tile));
     release_coeff_solve();
-    std::vector<int2> h_ant(nbls);
-    for (int b = 0; b < nbls; ++b) h_ant[b] = make_int2(d->bl_ant0[b], d->bl_ant1[b]);
-    CAL_TRY(bl_ant.alloc(nbls * sizeof(int2), false));
-    HIP_TRY(copy_sync(bl_ant.p, h_ant.data(), nbls * sizeof(int2), hipMemcpyHostToDevice));
-
-    // ---- runs of the multi-baseline groups: consecutive baselines with the same row block, cut to kRunMax
-    std::vector<int2> h_runs;
-    std::vector<int> h_grp_run0(ngrps + 1, 0);
-    int nsimple_grps = 0;
-    for (int g = 0; g < ngrps; ++g) {
-      const int s0 = d->grp_bl_start[g], s1 = d->grp_bl_start[g + 1];
-      h_grp_run0[g] = (int)h_runs.size();
-      if (s1 - s0 == 1) {
-        ++nsimple_grps;
-        continue;
-      }
-      int lo = s0;
-      for (int b = s0 + 1; b <= s1; ++b) {
-        const bool cut = b == s1 || (d->bl_rowblk && d->bl_rowblk[b] != d->bl_rowblk[lo]) || b - lo == kRunMax;
-        if (cut) {
-          h_runs.push_back(make_int2(lo, b));
-          lo = b;
-        }
-      }
-    }
-    h_grp_run0[ngrps] = (int)h_runs.size();
-    CAL_TRY(runs.alloc(std::max<size_t>(1, h_runs.size()) * sizeof(int2), false));
-    if (!h_runs.empty()) HIP_TRY(copy_sync(runs.p, h_runs.data(), h_runs.size() * sizeof(int2), hipMemcpyHostToDevice));
-
-    // ---- work items: whole groups when that already fills the chip, otherwise split along tiles
-    long long total_tiles = 0;
-    for (int g = 0; g < ngrps; ++g)
-      if (d->grp_bl_start[g + 1] - d->grp_bl_start[g] == 1) total_tiles += ftile / fb_u[d->grp_basis[g]];  // (folded tiles where the problem folds)
-    // one item per group when the groups alone fill the chip (256 CUs x ~4 resident workgroups, several waves of them);
-    // otherwise split groups along their tiles (partial coefficient gradients are summed by coeff_partial_reduce_kernel)
-    // With at least one group per CU an item is never smaller than 1024 channels of its group (8 tiles of the widest fp32
-    // shape, 16 of the widest fp64 one): a group of up to 56 vectors is then ONE item -- no partial coefficient gradients,
-    // no second launch to sum them -- and only wider groups (narrower tiles) are cut, which also evens the items out.
-    // Measured at HERA-37 (666 groups): fp64 76 -> 61 us per step, fp32 45 -> 42; cutting every group into 4-tile items
-    // (the earlier rule) bought parallelism the chip did not need and paid a prologue and a reduction for it.
-    const long long target_items = 8192;
-    const bool groups_fill_chip = nsimple_grps >= 2048;
-    const long long min_tiles = nsimple_grps >= 256 ? 1024 / FbSet<T>::fb_max : 4;
-    const long long tiles_per_item = groups_fill_chip ? std::max<long long>(64, 4 * total_tiles / std::max(1, nsimple_grps))
-                                                      : std::max<long long>(min_tiles, total_tiles / target_items);
-    std::vector<Item> h_items;
-    std::vector<int> h_grp_item_ptr(ngrps + 1, 0);
-    gc_direct = true;
-    std::vector<long long> h_item_cost;
-    std::vector<char> h_item_multi;
-    lds_group_bytes = 0;
-    for (int g = 0; g < ngrps; ++g) {
-      const int u = d->grp_basis[g];
-      const int ntpb = ftile / fb_u[u];
-      int fl = 0;
-      while ((1 << fl) < fb_u[u]) ++fl;
-      Item it{};
-      it.nvec = d->basis_nvec[u];
-      it.coff = h_grp_coff[g];
-      it.fb_log2 = fl;
-      it.slice = grp_slice[g];
-      if (d->grp_bl_start[g + 1] - d->grp_bl_start[g] == 1) {
-        const long long nt = ntpb;
-        // (a baseline that shares tiles stays ONE item: the multi kernel writes the whole coefficient gradient of its group)
-        const int nparts = in_alias_set[d->grp_bl_start[g]] ? 1 : (int)std::max<long long>(1, (nt + tiles_per_item - 1) / tiles_per_item);
-        if (nparts > 1) gc_direct = false;
-        for (int p = 0; p < nparts; ++p) {
-          it.bl0 = d->grp_bl_start[g];
-          it.tile0 = (int)(nt * p / nparts);
-          it.tile1 = (int)(nt * (p + 1) / nparts);
-          it.tile_first = h_bl_tile[it.bl0];
-          it.ant_first = make_int2(d->bl_ant0[it.bl0], d->bl_ant1[it.bl0]);
-          h_items.push_back(it);
-          h_item_cost.push_back((long long)(it.tile1 - it.tile0) * it.nvec * fb_u[u]);
-          h_item_multi.push_back(0);
-        }
-      } else {
-        // units = (run, channel block), run-major; a unit costs one tile (load, forward, adjoint: about 8 batches' worth)
-        // plus one batch of the per-channel stage per kThreads / FB baselines.  Items are cut at ~96 batch equivalents
-        // so that a big redundant set is spread over many workgroups (their partial coefficient gradients are summed).
-        lds_group_bytes = std::max(lds_group_bytes, group_lds_for(fb_u[u]));
-        const int bpt = kThreads / fb_u[u];
-        const int r0 = h_grp_run0[g], r1 = h_grp_run0[g + 1];
-        const long long budget = 96;
-        long long cost = 0;
-        int unit_lo = 0, nparts = 0;
-        const int nunits = (r1 - r0) * ntpb;
-        for (int uu = 0; uu < nunits; ++uu) {
-          const int2 rn = h_runs[r0 + uu / ntpb];
-          cost += 8 + (rn.y - rn.x + bpt - 1) / bpt;
-          if (cost >= budget || uu + 1 == nunits) {
-            it.bl0 = r0;
-            it.tile0 = unit_lo;
-            it.tile1 = uu + 1;
-            h_items.push_back(it);
-            h_item_cost.push_back(cost * 1024);  // same scale as nvec x FB of a full tile, roughly
-            h_item_multi.push_back(1);
-            unit_lo = uu + 1;
-            cost = 0;
-            ++nparts;
-          }
-        }
-        if (nparts > 1) gc_direct = false;
-      }
-      h_grp_item_ptr[g + 1] = (int)h_items.size();
-    }
-    nitems = (int)h_items.size();
-    small_loads = true;
-    for (const Item& q : h_items) {
-      const int lpr = (1 << q.fb_log2) / (16 / (int)sizeof(T));  // lanes per tile row; a load covers kThreads / lpr rows
-      if (q.nvec > kSmallLoads * (kThreads / lpr)) small_loads = false;
-    }
-    // single-baseline items first, then the multi-baseline ones (two launches); inside each class heaviest first: the
-    // hardware dispatches workgroups in index order, so the tail is made of the lightest items
-    // (among the single-baseline items those that a head item of the multi-slice kernels covers come last: the loss and gradient
-    // passes launch fused_basis_kernel over the plain ones only)
-    std::vector<std::vector<int>> alias_sets(nbls);
-    for (int b = 0; b < nbls; ++b)
-      if (in_alias_set[b]) alias_sets[alias_root[b] >= 0 ? alias_root[b] : b].push_back(b);
-    // members per head item: the matrix-core kernel takes 8 in both precisions (16 MFMA columns), fused_multi_kernel
-    // MultiCfg<T>::nb_max (its gradient accumulators live in registers: 4 in fp64)
-    auto mfma_shape = [&](const Item& q) { return q.nvec <= kMmMaxVec && (1 << q.fb_log2) >= kMmStrip && fpad % 128 == 0; };
-    std::vector<int> set_cap(nbls, MultiCfg<T>::nb_max);
-    for (int q = 0; q < nitems; ++q)
-      if (!h_item_multi[q] && mfma_shape(h_items[q])) set_cap[h_items[q].bl0] = kMmMembers;
-    std::vector<char> bl_covered(nbls, 0);
-    for (int r = 0; r < nbls; ++r)
-      for (size_t i = 0; i < alias_sets[r].size(); i += set_cap[r]) {
-        const size_t n = std::min<size_t>(set_cap[r], alias_sets[r].size() - i);
-        if (n >= 2)
-          for (size_t k = 0; k < n; ++k) bl_covered[alias_sets[r][i + k]] = 1;
-      }
-    auto item_class = [&](int q) { return h_item_multi[q] ? 2 : (bl_covered[h_items[q].bl0] ? 1 : 0); };
-    std::vector<int> order(nitems);
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-      if (item_class(a) != item_class(b)) return item_class(a) < item_class(b);
-      return h_item_cost[a] > h_item_cost[b];
-    });
-    nitems_simple = 0;
-    nitems_plain = 0;
-    for (int q = 0; q < nitems; ++q) {
-      nitems_simple += h_item_multi[q] ? 0 : 1;
-      nitems_plain += item_class(q) == 0 ? 1 : 0;
-    }
-    std::vector<int> h_item_goff(nitems);
-    gcp_len = 0;
-    if (gc_direct) {
-      for (int q = 0; q < nitems; ++q) h_item_goff[q] = h_items[q].coff;
-      gcp_len = ncoef;
-    } else {
-      for (int q = 0; q < nitems; ++q) {
-        h_item_goff[q] = (int)gcp_len;
-        gcp_len += h_items[q].nvec;
-      }
-    }
-    std::vector<Item> sorted(nitems);
-    for (int q = 0; q < nitems; ++q) {
-      sorted[q] = h_items[order[q]];
-      sorted[q].goff = h_item_goff[order[q]];
-      sorted[q].role_n = 0;
-      sorted[q].member0 = 0;
-    }
-    // the loss partials (one per item) of every time slice, in item order
+    CAL_TRY(upload(bl_ant, p.bl_ant));
+    CAL_TRY(upload(runs, p.runs, 1));
     if (nslices > 1) {
-      std::vector<int> ptr(nslices + 1, 0), idx(nitems);
-      for (int q = 0; q < nitems; ++q) ptr[sorted[q].slice + 1]++;
-      for (int t = 0; t < nslices; ++t) ptr[t + 1] += ptr[t];
-      std::vector<int> fill(ptr.begin(), ptr.end() - 1);
-      for (int q = 0; q < nitems; ++q) idx[fill[sorted[q].slice]++] = q;
-      CAL_TRY(slice_ipart_ptr.alloc(ptr.size() * sizeof(int), false));
-      HIP_TRY(copy_sync(slice_ipart_ptr.p, ptr.data(), ptr.size() * sizeof(int), hipMemcpyHostToDevice));
-      CAL_TRY(slice_ipart_idx.alloc(idx.size() * sizeof(int), false));
-      HIP_TRY(copy_sync(slice_ipart_idx.p, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice));
+      CAL_TRY(upload(slice_ipart_ptr, p.slice_ipart_ptr));
+      CAL_TRY(upload(slice_ipart_idx, p.slice_ipart_idx));
+      CAL_TRY(upload(slice_cblk, p.slice_cblk));
     }
-    // coefficient blocks of step_tail_kernel: every slice gets its own (a block works for ONE slice's decisions)
-    h_slice_cblk.assign(nslices + 1, 0);
-    for (int t = 0; t < nslices; ++t) {
-      const long long nb = (2LL * (h_slice_coff[t + 1] - h_slice_coff[t]) + 255) / 256;
-      h_slice_cblk[t + 1] = h_slice_cblk[t] + (int)std::max<long long>(1, std::min<long long>(nb, std::max(1, 4096 / nslices)));
+    members.release();
+    heads.release();
+    if (nheads > 0) {
+      CAL_TRY(upload(members, p.members));
+      CAL_TRY(upload(heads, p.heads));
     }
-    if (nslices > 1) {
-      CAL_TRY(slice_cblk.alloc((nslices + 1) * sizeof(int), false));
-      HIP_TRY(copy_sync(slice_cblk.p, h_slice_cblk.data(), (nslices + 1) * sizeof(int), hipMemcpyHostToDevice));
-    }
-    // ---- sets of baselines that share tiles -> head items with member lists (at most MultiCfg<T>::nb_max baselines each)
-    nheads = 0;
-    nheads_mfma = 0;
-    heads_one_pass_local = false;
-    local_reg_plan();
-    lds_multi_bytes = 0;
-    lds_multi_mfma_bytes = 0;
-    {
-      std::vector<int> item_of_bl(nbls, -1);
-      for (int q = 0; q < nitems; ++q)
-        if (!h_item_multi[order[q]]) item_of_bl[sorted[q].bl0] = q;
-      const std::vector<std::vector<int>>& sets = alias_sets;
-      std::vector<Member> h_members;
-      std::vector<int> h_heads;
-      for (int r = 0; r < nbls; ++r) {
-        const int NBM = set_cap[r];
-        for (size_t i = 0; i < sets[r].size(); i += NBM) {
-          const int n = (int)std::min<size_t>(NBM, sets[r].size() - i);
-          if (n < 2) continue;  // a lone baseline runs as an ordinary item
-          const int head = item_of_bl[sets[r][i]];
-          sorted[head].role_n = (n << 2) | 1;
-          sorted[head].member0 = (int)h_members.size();
-          h_heads.push_back(head);
-          for (int k = 0; k < n; ++k) {
-            const int b = sets[r][i + k], q = item_of_bl[b];
-            if (k > 0) sorted[q].role_n = 2;
-            Member m{};
-            m.bl = b;
-            m.coff = sorted[q].coff;
-            m.goff = sorted[q].goff;
-            m.ant0 = d->bl_ant0[b];
-            m.ant1 = d->bl_ant1[b];
-            m.slice = sorted[q].slice;
-            m.item = q;
-            h_members.push_back(m);
-          }
-        }
-      }
-      // the matrix-core form first (blocks of at most kMmMaxVec vectors), each list heaviest first
-      // (rows padded to a multiple of 128 channels -- any band of more than 64: its waves take an even number of 16-channel strips each)
-      auto on_mfma = [&](int head) { return mfma_shape(sorted[head]); };
-      std::stable_sort(h_heads.begin(), h_heads.end(), [&](int a, int b) {
-        const bool ma = on_mfma(a), mb = on_mfma(b);
-        if (ma != mb) return ma;
-        return (long long)sorted[a].nvec * (sorted[a].role_n >> 2) > (long long)sorted[b].nvec * (sorted[b].role_n >> 2);
-      });
-      for (int head : h_heads) {
-        if (on_mfma(head)) {
-          ++nheads_mfma;
-          lds_multi_mfma_bytes = std::max(lds_multi_mfma_bytes, multi_mfma_lds_bytes<T>(sorted[head].nvec));
-        } else {
-          lds_multi_bytes = std::max(lds_multi_bytes, multi_lds_for(1 << sorted[head].fb_log2));
-        }
-      }
-      nheads = (int)h_heads.size();
-      // the "sum" regulariser over heads: one pass with two adjoint sets when every head is on the matrix-core kernel and narrow enough
-      // for it (multi_mfma_kernels.hpp, REG == 2); else a loss pass for the slices' sums in front of the gradient pass (enqueue_pass)
-      heads_one_pass_local = nheads > 0 && nheads == nheads_mfma;
-      for (int head : h_heads) heads_one_pass_local = heads_one_pass_local && sorted[head].nvec <= kMmMaxVecOnePass<T>;
-      local_reg_plan();
-      // XCD-affine, antenna-grouped dispatch of the matrix-core heads: a head reads 2 gain rows per member (8 slices x 2 x 8 KB of a
-      // 1024-channel band) -- a fifth of its bytes, 1.0 GB per pass of an 8-GPU rank's share against 23 MB of distinct gains, because
-      // with the heads in cost order nothing a workgroup brings into its XCD's L2 is wanted by its neighbours (hit rate 17 %).
-      // Workgroups are dealt round-robin over the 8 XCDs (b and b + 8 share one): every first antenna -- all heads whose baseline
-      // starts at it -- goes to ONE of 8 lists of equal cost (longest-processing-time-first), heaviest antenna groups first in a
-      // list, heaviest head first in a group, and workgroup b takes entry b / 8 of list b % 8.  The ant0 rows of a group then stay
-      // in that XCD's L2 for the whole group.  (-1 where a list is shorter.)
-      mm_grid = nheads_mfma;
-      if (nheads_mfma >= 64) {
-        auto cost = [&](int h) { return (double)sorted[h].nvec * (sorted[h].role_n >> 2) + 64.0; };
-        std::map<int, std::vector<int>> by_ant;
-        for (int i = 0; i < nheads_mfma; ++i) by_ant[sorted[h_heads[i]].ant_first.x].push_back(h_heads[i]);  // (already heaviest first)
-        std::vector<std::pair<double, int>> groups;
-        for (auto& kv : by_ant) {
-          double c = 0;
-          for (int h : kv.second) c += cost(h);
-          groups.push_back({c, kv.first});
-        }
-        std::stable_sort(groups.begin(), groups.end(), [](const std::pair<double, int>& a, const std::pair<double, int>& b) { return a.first > b.first; });
-        double load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        std::vector<std::vector<int>> lists(8);
-        for (auto& g : groups) {
-          const int x = (int)(std::min_element(load, load + 8) - load);
-          load[x] += g.first;
-          for (int h : by_ant[g.second]) lists[x].push_back(h);
-        }
-        size_t longest = 0;
-        for (auto& l : lists) longest = std::max(longest, l.size());
-        std::vector<int> dealt(8 * longest, -1);
-        for (int x = 0; x < 8; ++x)
-          for (size_t j = 0; j < lists[x].size(); ++j) dealt[j * 8 + x] = lists[x][j];
-        dealt.insert(dealt.end(), h_heads.begin() + nheads_mfma, h_heads.end());
-        mm_grid = (int)(8 * longest);
-        h_heads.swap(dealt);
-      }
-      members.release();
-      heads.release();
-      if (nheads > 0) {
-        CAL_TRY(members.alloc(h_members.size() * sizeof(Member), false));
-        HIP_TRY(copy_sync(members.p, h_members.data(), h_members.size() * sizeof(Member), hipMemcpyHostToDevice));
-        CAL_TRY(heads.alloc(h_heads.size() * sizeof(int), false));
-        HIP_TRY(copy_sync(heads.p, h_heads.data(), h_heads.size() * sizeof(int), hipMemcpyHostToDevice));
-        if (nheads > nheads_mfma) {
-          HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_multi_kernel<T, MODE_GRAD, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_multi_bytes));
-          HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_multi_kernel<T, MODE_LOSS, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_multi_bytes));
-          HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_multi_kernel<T, MODE_GRAD, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_multi_bytes));
-          HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_multi_kernel<T, MODE_LOSS, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_multi_bytes));
-        }
-        if (nheads_mfma > 0) {
-          HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_multi_mfma_kernel<T, MODE_GRAD, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_multi_mfma_bytes));
-          HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_multi_mfma_kernel<T, MODE_LOSS, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_multi_mfma_bytes));
-          HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_multi_mfma_kernel<T, MODE_GRAD, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_multi_mfma_bytes));
-          HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_multi_mfma_kernel<T, MODE_LOSS, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_multi_mfma_bytes));
-          HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_multi_mfma_kernel<T, MODE_GRAD, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_multi_mfma_bytes));
-        }
-      }
-    }
-    CAL_TRY(items.alloc(nitems * sizeof(Item), false));
-    HIP_TRY(copy_sync(items.p, sorted.data(), nitems * sizeof(Item), hipMemcpyHostToDevice));
+    // the dynamic LDS every kernel of this problem may ask for
+    constexpr bool f32 = std::is_same<T, float>::value;
+    const bool multi = nheads > nheads_mfma, mm = nheads > 0 && nheads_mfma > 0;
+    const struct { bool on; const void* fn; size_t lds; } attrs[] = {
+        {mf_ok && mf_split2, reinterpret_cast<const void*>(&fused_dense_split2_kernel<true>), mf_lds_grad[0]},
+        {mf_ok && mf_split2, reinterpret_cast<const void*>(&fused_dense_split2_kernel<false>), mf_lds_loss[0]},
+        {mf_ok && mf_split && !mf_split2, reinterpret_cast<const void*>(&fused_dense_split_kernel<true>), mf_lds_grad[0]},
+        {mf_ok && mf_split && !mf_split2, reinterpret_cast<const void*>(&fused_dense_split_kernel<false>), mf_lds_loss[0]},
+        {mf_ok && f32 && !mf_split, reinterpret_cast<const void*>(&fused_dense_kernel<true>), mf_lds_grad[0]},
+        {mf_ok && f32 && !mf_split, reinterpret_cast<const void*>(&fused_dense_kernel<false>), mf_lds_loss[0]},
+        {mf_ok && !f32, reinterpret_cast<const void*>(&fused_dense64_kernel<true>), mf_lds_grad[0]},
+        {mf_ok && !f32, reinterpret_cast<const void*>(&fused_dense64_kernel<false>), mf_lds_loss[0]},
+        {multi, reinterpret_cast<const void*>(&fused_multi_kernel<T, MODE_GRAD, false>), lds_multi_bytes},
+        {multi, reinterpret_cast<const void*>(&fused_multi_kernel<T, MODE_LOSS, false>), lds_multi_bytes},
+        {multi, reinterpret_cast<const void*>(&fused_multi_kernel<T, MODE_GRAD, true>), lds_multi_bytes},
+        {multi, reinterpret_cast<const void*>(&fused_multi_kernel<T, MODE_LOSS, true>), lds_multi_bytes},
+        {mm, reinterpret_cast<const void*>(&fused_multi_mfma_kernel<T, MODE_GRAD, 0>), lds_multi_mfma_bytes},
+        {mm, reinterpret_cast<const void*>(&fused_multi_mfma_kernel<T, MODE_LOSS, 0>), lds_multi_mfma_bytes},
+        {mm, reinterpret_cast<const void*>(&fused_multi_mfma_kernel<T, MODE_GRAD, 1>), lds_multi_mfma_bytes},
+        {mm, reinterpret_cast<const void*>(&fused_multi_mfma_kernel<T, MODE_LOSS, 1>), lds_multi_mfma_bytes},
+        {mm, reinterpret_cast<const void*>(&fused_multi_mfma_kernel<T, MODE_GRAD, 2>), lds_multi_mfma_bytes},
+    };
+    for (const auto& a : attrs)
+      if (a.on) HIP_TRY(hipFuncSetAttribute(a.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds));
+    CAL_TRY(upload(items, p.items));
     if (!gc_direct) {
-      std::vector<int> h_coef_grp(ncoef);
-      for (int g = 0; g < ngrps; ++g)
-        for (int n = h_grp_coff[g]; n < h_grp_coff[g + 1]; ++n) h_coef_grp[n] = g;
-      CAL_TRY(coef_grp.alloc(ncoef * sizeof(int), false));
-      HIP_TRY(copy_sync(coef_grp.p, h_coef_grp.data(), ncoef * sizeof(int), hipMemcpyHostToDevice));
-      CAL_TRY(grp_coff.alloc((ngrps + 1) * sizeof(int), false));
-      HIP_TRY(copy_sync(grp_coff.p, h_grp_coff.data(), (ngrps + 1) * sizeof(int), hipMemcpyHostToDevice));
-      CAL_TRY(grp_item_ptr.alloc((ngrps + 1) * sizeof(int), false));
-      HIP_TRY(copy_sync(grp_item_ptr.p, h_grp_item_ptr.data(), (ngrps + 1) * sizeof(int), hipMemcpyHostToDevice));
-      CAL_TRY(item_goff.alloc(nitems * sizeof(int), false));
-      HIP_TRY(copy_sync(item_goff.p, h_item_goff.data(), nitems * sizeof(int), hipMemcpyHostToDevice));
+      CAL_TRY(upload(coef_grp, p.coef_grp));
+      CAL_TRY(upload(grp_coff, p.grp_coff));
+      CAL_TRY(upload(grp_item_ptr, p.grp_item_ptr));
+      CAL_TRY(upload(item_goff, p.item_goff));
       CAL_TRY(gc0.alloc(2 * (size_t)ncoef * sizeof(T)));
     }
+    CAL_TRY(upload(ant_ptr, p.ant_ptr));
+    CAL_TRY(upload(ant_ent, p.ant_ent));
 
-    // ---- per-antenna CSR of (baseline, role, other antenna), in baseline order: a fixed summation order
-    std::vector<int> h_ant_ptr(nants + 1, 0);
-    for (int b = 0; b < nbls; ++b) {
-      h_ant_ptr[d->bl_ant0[b] + 1]++;
-      h_ant_ptr[d->bl_ant1[b] + 1]++;
-    }
-    for (int a = 0; a < nants; ++a) h_ant_ptr[a + 1] += h_ant_ptr[a];
-    std::vector<int2> h_ent(2 * (size_t)nbls);
-    std::vector<int> fill(h_ant_ptr.begin(), h_ant_ptr.end() - 1);
-    for (int b = 0; b < nbls; ++b) {
-      h_ent[fill[d->bl_ant0[b]]++] = make_int2(b * 2 + 0, d->bl_ant1[b]);
-      h_ent[fill[d->bl_ant1[b]]++] = make_int2(b * 2 + 1, d->bl_ant0[b]);
-    }
-    CAL_TRY(ant_ptr.alloc((nants + 1) * sizeof(int), false));
-    HIP_TRY(copy_sync(ant_ptr.p, h_ant_ptr.data(), (nants + 1) * sizeof(int), hipMemcpyHostToDevice));
-    CAL_TRY(ant_ent.alloc(h_ent.size() * sizeof(int2), false));
-    HIP_TRY(copy_sync(ant_ent.p, h_ent.data(), h_ent.size() * sizeof(int2), hipMemcpyHostToDevice));
-
+    for (DevBuf* b : {&gains_snap, &gains_alt, &coef_snap, &q1, &gcp1, &gc1, &model_buf, &scratch, &fq_out, &fq_gains, &gs_out, &gs_ptr, &gs_ent, &gs_mask, &cs_rhs})
+      b->release();
     // ---- state arrays
     const size_t rowbytes = (size_t)(nbls + 1) * fpad * sizeof(T);  // + one all-zero spare row (padding slots of the dense path)
-    CAL_TRY(data_r.alloc(rowbytes));
-    CAL_TRY(data_i.alloc(rowbytes));
-    CAL_TRY(wgts.alloc(rowbytes));
-    const size_t gbytes = (size_t)nants * fpad * sizeof(T2);
-    CAL_TRY(gains.alloc(gbytes));
-    CAL_TRY(gains_m.alloc(gbytes));
-    CAL_TRY(gains_v.alloc(gbytes));
-    gains_snap.release();
-    gains_alt.release();
-    const size_t cbytes = 2 * (size_t)ncoef * sizeof(T);
-    CAL_TRY(coef.alloc(cbytes + 256));  // (the split-bf16 kernel reads whole pairs of 16-vector steps: up to 31 reals past the last group's coefficients)
-    CAL_TRY(coef_m.alloc(cbytes));
-    CAL_TRY(coef_v.alloc(cbytes));
-    coef_snap.release();
-    CAL_TRY(q0.alloc((size_t)(nbls + 1) * fpad * sizeof(T2)));
-    q1.release();
-    CAL_TRY(comm.alloc(3 * gbytes));
-    CAL_TRY(gcp0.alloc(2 * (size_t)gcp_len * sizeof(T)));
-    gcp1.release();
-    gc1.release();
-    CAL_TRY(part.alloc((size_t)std::max(nitems, mf_npanels) * 4 * sizeof(double)));
-    model_buf.release();
-    scratch.release();
-    fq_out.release();
-    fq_gains.release();
-    gs_out.release();
-    gs_ptr.release();
-    gs_ent.release();
-    gs_mask.release();
-    cs_rhs.release();
+    const size_t gbytes = (size_t)nants * fpad * sizeof(T2), cbytes = 2 * (size_t)ncoef * sizeof(T);
+    // (coef + 256: the split-bf16 kernel reads whole pairs of 16-vector steps, up to 31 reals past the last group's coefficients)
+    const std::pair<DevBuf*, size_t> zeroed[] = {{&data_r, rowbytes}, {&data_i, rowbytes}, {&wgts, rowbytes}, {&gains, gbytes}, {&gains_m, gbytes}, {&gains_v, gbytes},
+                                                 {&coef, cbytes + 256}, {&coef_m, cbytes}, {&coef_v, cbytes}, {&q0, (size_t)(nbls + 1) * fpad * sizeof(T2)}, {&comm, 3 * gbytes},
+                                                 {&gcp0, 2 * (size_t)gcp_len * sizeof(T)}, {&part, (size_t)std::max(nitems, mf_npanels) * 4 * sizeof(double)}};
+    for (const auto& z : zeroed) CAL_TRY(z.first->alloc(z.second));
     held.clear();
     has_problem = true;
     reg = CAL_REG_NONE;
-    // ~ tens of milliseconds of GPU time between two host synchronisations of run(); the same on every rank, or ranks
-    // would notice a tolerance stop after different step counts and issue different numbers of all-reduces
-    steps_per_sync = (int)std::max(1.0, std::min(256.0, 2.0e11 / ((double)basis_bytes + 1.0)));
-    return CAL_OK;
-  }
-
-  // XCD-affine dispatch of the dense launch (dense_kernels.hpp: fused_dense_kernel): every basis block -- all its panels -- goes
-  // to ONE of 8 lists, blocks dealt longest-processing-time first so the lists carry equal cost; inside a list the heaviest
-  // panels come first (the tail of the pass is made of the lightest).  Workgroup b takes entry b / 8 of list b % 8: the slot
-  // map interleaves the lists, -1 where a list is shorter than the longest.  Uploads the records and the map.
-  // `per` consecutive panel records form one work item (split-bf16 kernel: a super-panel); cost and the map count items.
-  int order_panels(std::vector<PanelItem>& panels, const std::vector<double>& cost, int per = 1) {
-    const int n = (int)panels.size() / per;
-    std::vector<long long> keys;
-    std::vector<double> kcost;
-    std::vector<int> blk(n);
-    for (int i = 0; i < n; ++i) {
-      size_t k = std::find(keys.begin(), keys.end(), panels[(size_t)i * per].a_kf4) - keys.begin();
-      if (k == keys.size()) { keys.push_back(panels[i].a_kf4); kcost.push_back(0.0); }
-      kcost[k] += cost[i];
-      blk[i] = (int)k;
-    }
-    std::vector<int> border(keys.size());
-    std::iota(border.begin(), border.end(), 0);
-    std::stable_sort(border.begin(), border.end(), [&](int a, int b) { return kcost[a] > kcost[b]; });
-    double load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    std::vector<int> list_of(keys.size());
-    for (int k : border) {
-      const int x = (int)(std::min_element(load, load + 8) - load);
-      list_of[k] = x;
-      load[x] += kcost[k];
-    }
-    std::vector<std::vector<int>> lists(8);
-    for (int i = 0; i < n; ++i) lists[list_of[blk[i]]].push_back(i);
-    size_t longest = 0;
-    for (auto& l : lists) {
-      std::stable_sort(l.begin(), l.end(), [&](int a, int b) { return cost[a] > cost[b]; });
-      longest = std::max(longest, l.size());
-    }
-    std::vector<int> h_map(8 * longest, -1);
-    for (int x = 0; x < 8; ++x)
-      for (size_t j = 0; j < lists[x].size(); ++j) h_map[j * 8 + x] = lists[x][j];
-    const int np = (int)panels.size();
-    mf_npanels = np;
-    mf_grid = (int)h_map.size();
-    if (nslices > 1) {  // the loss partials (one per panel) of every time slice, in panel order
-      std::vector<int> ptr(nslices + 1, 0), idx(np);
-      for (int i = 0; i < np; ++i) ptr[panels[i].slice + 1]++;
-      for (int t = 0; t < nslices; ++t) ptr[t + 1] += ptr[t];
-      std::vector<int> fill(ptr.begin(), ptr.end() - 1);
-      for (int i = 0; i < np; ++i) idx[fill[panels[i].slice]++] = i;
-      CAL_TRY(slice_ppart_ptr.alloc(ptr.size() * sizeof(int), false));
-      HIP_TRY(hipMemcpyAsync(slice_ppart_ptr.p, ptr.data(), ptr.size() * sizeof(int), hipMemcpyHostToDevice, stream));
-      CAL_TRY(slice_ppart_idx.alloc(idx.size() * sizeof(int), false));
-      HIP_TRY(hipMemcpyAsync(slice_ppart_idx.p, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice, stream));
-      HIP_TRY(hipStreamSynchronize(stream));  // (the vectors leave scope)
-    }
-    CAL_TRY(mf_panels.alloc((size_t)np * sizeof(PanelItem), false));
-    HIP_TRY(hipMemcpyAsync(mf_panels.p, panels.data(), (size_t)np * sizeof(PanelItem), hipMemcpyHostToDevice, stream));
-    CAL_TRY(mf_map.alloc(h_map.size() * sizeof(int), false));
-    HIP_TRY(hipMemcpyAsync(mf_map.p, h_map.data(), h_map.size() * sizeof(int), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
     return CAL_OK;
   }
 
@@ -3010,6 +2169,61 @@ int weighted_square_error(int64_t n, const void* const src[5], double* out) {
 }  // namespace
 
 // ================================================================================================================
+// cal_debug_plan: the host planner's arrays as bytes
+namespace {
+template <typename X>
+int plan_bytes(const std::vector<X>& v, void* out, int64_t cap, int64_t* bytes) {
+  *bytes = (int64_t)(v.size() * sizeof(X));
+  if (*bytes > cap) return fail(CAL_ERR_INVALID, "cal_debug_plan: the array has %lld bytes, the buffer %lld", (long long)*bytes, (long long)cap);
+  if (*bytes) memcpy(out, v.data(), (size_t)*bytes);
+  return CAL_OK;
+}
+template <typename T>
+int debug_plan(const cal_problem_desc* d, int what, void* out, int64_t cap, int64_t* bytes) {
+  ProblemPlan<T> p;
+  CAL_TRY(plan_problem(d, p));
+  switch (what) {
+    case 0: {
+      std::vector<int64_t> v = {p.fpad, p.ncoef, p.nslices, p.na_slice, p.fold, p.small_loads, p.nitems, p.nitems_simple, p.nitems_plain, p.gc_direct, p.gcp_len, 0,
+                                p.steps_per_sync, (int64_t)p.lds_bytes, (int64_t)p.lds_group_bytes, (int64_t)p.lds_multi_bytes, (int64_t)p.lds_multi_mfma_bytes,
+                                p.mf_ok, p.mf_split, p.mf_split2, p.mf_npanels, p.mf_grid, (int64_t)p.mf_lds_grad[0], (int64_t)p.mf_lds_loss[0], p.nheads, p.nheads_mfma,
+                                p.heads_one_pass_local, p.mm_grid, p.lamb_ok, p.lamb_nvar, p.lamb_ncvar};
+      memcpy(&v[11], &p.basis_bytes, sizeof(double));
+      return plan_bytes(v, out, cap, bytes);
+    }
+    case 1: return plan_bytes(p.fb_u, out, cap, bytes);
+    case 2: return plan_bytes(p.uoff, out, cap, bytes);
+    case 3: return plan_bytes(p.bl_tile, out, cap, bytes);
+    case 4: return plan_bytes(p.jobs, out, cap, bytes);
+    case 5: return plan_bytes(p.grp_coff, out, cap, bytes);
+    case 6: return plan_bytes(p.slice_coff, out, cap, bytes);
+    case 7: return plan_bytes(p.slice_cblk, out, cap, bytes);
+    case 8: return plan_bytes(p.lamb_vars, out, cap, bytes);
+    case 9: return plan_bytes(p.lamb_cvar_ptr, out, cap, bytes);
+    case 10: return plan_bytes(p.lamb_cvar_slice, out, cap, bytes);
+    case 11: return plan_bytes(p.lamb_cvar_id, out, cap, bytes);
+    case 12: return plan_bytes(p.runs, out, cap, bytes);
+    case 13: return plan_bytes(p.items, out, cap, bytes);
+    case 14: return plan_bytes(p.item_goff, out, cap, bytes);
+    case 15: return plan_bytes(p.grp_item_ptr, out, cap, bytes);
+    case 16: return plan_bytes(p.coef_grp, out, cap, bytes);
+    case 17: return plan_bytes(p.slice_ipart_ptr, out, cap, bytes);
+    case 18: return plan_bytes(p.slice_ipart_idx, out, cap, bytes);
+    case 19: return plan_bytes(p.slice_ppart_ptr, out, cap, bytes);
+    case 20: return plan_bytes(p.slice_ppart_idx, out, cap, bytes);
+    case 21: return plan_bytes(p.members, out, cap, bytes);
+    case 22: return plan_bytes(p.heads, out, cap, bytes);
+    case 23: return plan_bytes(p.panels, out, cap, bytes);
+    case 24: return plan_bytes(p.panel_map, out, cap, bytes);
+    case 25: return plan_bytes(p.op_off, out, cap, bytes);
+    case 26: return plan_bytes(p.cs_grp, out, cap, bytes);
+    case 27: return plan_bytes(p.ant_ptr, out, cap, bytes);
+    case 28: return plan_bytes(p.ant_ent, out, cap, bytes);
+  }
+  return fail(CAL_ERR_INVALID, "cal_debug_plan: what = %d", what);
+}
+}  // namespace
+
 extern "C" {
 
 
@@ -3024,11 +2238,16 @@ int cal_basis_foldable(int dtype, const void* block, int32_t nfreqs, int32_t nve
   if (!block || nfreqs <= 0 || nvec <= 0 || nrowblk <= 0 || (dtype != CAL_F32 && dtype != CAL_F64)) return fail(CAL_ERR_INVALID, "cal_basis_foldable: bad argument");
   double resid = 0, amax = 0;
   bool ok;
-  if (dtype == CAL_F32) ok = block_foldable(static_cast<const float*>(block), nfreqs, nvec, nrowblk, SolverT<float>::choose_fb(nvec, nfreqs), &resid, &amax);
-  else ok = block_foldable(static_cast<const double*>(block), nfreqs, nvec, nrowblk, SolverT<double>::choose_fb(nvec, nfreqs), &resid, &amax);
+  if (dtype == CAL_F32) ok = block_foldable(static_cast<const float*>(block), nfreqs, nvec, nrowblk, choose_fb<float>(nvec, nfreqs), &resid, &amax);
+  else ok = block_foldable(static_cast<const double*>(block), nfreqs, nvec, nrowblk, choose_fb<double>(nvec, nfreqs), &resid, &amax);
   if (max_residual) *max_residual = resid;
   if (max_abs) *max_abs = amax;
   return ok ? 1 : 0;
+}
+
+int cal_debug_plan(int dtype, const cal_problem_desc* d, int what, void* out, int64_t cap_bytes, int64_t* bytes) {
+  if (!out || !bytes || cap_bytes < 0 || (dtype != CAL_F32 && dtype != CAL_F64)) return fail(CAL_ERR_INVALID, "cal_debug_plan: bad argument");
+  return dtype == CAL_F32 ? debug_plan<float>(d, what, out, cap_bytes, bytes) : debug_plan<double>(d, what, out, cap_bytes, bytes);
 }
 
 int cal_device_count(int* count) {

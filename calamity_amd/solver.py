@@ -31,6 +31,40 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def problem_desc(prob, dtype, layout="stream", kernel_path="auto"):
+    """``(_lib.ProblemDesc, arrays)`` of ``prob`` for a solver of ``dtype``: what ``cal_solver_set_problem`` and the host-only
+    ``cal_debug_plan`` take.  The descriptor points into ``arrays``: keep them alive while it is in use."""
+    dtype = np.dtype(dtype)
+    basis = [np.ascontiguousarray(b, dtype=dtype) for b in prob.basis]
+    sizes = np.asarray([b.size for b in basis], dtype=np.int64)
+    offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    flat = np.concatenate([b.ravel() for b in basis]) if len(basis) > 1 else basis[0].ravel()
+    nvec = np.asarray([b.shape[1] for b in basis], dtype=np.int32)
+    nrb = np.asarray([b.shape[0] // prob.nfreqs for b in basis], dtype=np.int32)
+    keep = [
+        flat, offs, nvec, nrb,
+        np.ascontiguousarray(prob.grp_basis, dtype=np.int32),
+        np.ascontiguousarray(prob.grp_bl_start, dtype=np.int32),
+        np.ascontiguousarray(prob.bl_ant0, dtype=np.int32),
+        np.ascontiguousarray(prob.bl_ant1, dtype=np.int32),
+        np.ascontiguousarray(prob.bl_rowblk, dtype=np.int32),
+        None if getattr(prob, "bl_alias", None) is None else np.ascontiguousarray(prob.bl_alias, dtype=np.int32),
+        # the reference's variables fg_r[chunk] / fg_i[chunk] (a layer-wise optimizer -- LAMB -- takes one trust ratio per variable)
+        None if getattr(prob, "chunk_of_grp", None) is None else np.ascontiguousarray(prob.chunk_of_grp, dtype=np.int32),
+    ]
+    d = _lib.ProblemDesc(
+        nants=prob.nants, nfreqs=prob.nfreqs, ngrps=prob.ngrps, nbls=prob.nbls, nbasis=len(basis),
+        basis_offset=_ptr(offs), basis_nvec=_ptr(nvec), basis_nrowblk=_ptr(nrb), basis_data=_ptr(flat),
+        grp_basis=_ptr(keep[4]), grp_bl_start=_ptr(keep[5]), bl_ant0=_ptr(keep[6]), bl_ant1=_ptr(keep[7]),
+        bl_rowblk=_ptr(keep[8]), bl_alias=_ptr(keep[9]), nslices=int(getattr(prob, "nslices", 1) or 1), grp_var=_ptr(keep[10]),
+        layout={"stream": _lib.CAL_LAYOUT_STREAM, "shared": _lib.CAL_LAYOUT_SHARED}[layout],
+        kernel_path={"auto": _lib.CAL_PATH_AUTO, "general": _lib.CAL_PATH_GENERAL, "dense": _lib.CAL_PATH_DENSE,
+                     "dense_f32": _lib.CAL_PATH_DENSE_F32, "dense_split1": _lib.CAL_PATH_DENSE_SPLIT1,
+                     "general_full": _lib.CAL_PATH_GENERAL_FULL}[kernel_path],
+    )
+    return d, keep
+
+
 class HipFitSolver:
     """One gain + foreground fit resident on one MI355X."""
 
@@ -71,33 +105,7 @@ class HipFitSolver:
         "general" keep only the lower half band of a mirror-symmetric basis (``timing_get()["basis_folded"]``);
         "general_full" is "general" with the full band kept whatever the basis looks like."""
         prob.validate()
-        basis = [np.ascontiguousarray(b, dtype=self.dtype) for b in prob.basis]
-        sizes = np.asarray([b.size for b in basis], dtype=np.int64)
-        offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        flat = np.concatenate([b.ravel() for b in basis]) if len(basis) > 1 else basis[0].ravel()
-        nvec = np.asarray([b.shape[1] for b in basis], dtype=np.int32)
-        nrb = np.asarray([b.shape[0] // prob.nfreqs for b in basis], dtype=np.int32)
-        keep = [
-            flat, offs, nvec, nrb,
-            np.ascontiguousarray(prob.grp_basis, dtype=np.int32),
-            np.ascontiguousarray(prob.grp_bl_start, dtype=np.int32),
-            np.ascontiguousarray(prob.bl_ant0, dtype=np.int32),
-            np.ascontiguousarray(prob.bl_ant1, dtype=np.int32),
-            np.ascontiguousarray(prob.bl_rowblk, dtype=np.int32),
-            None if getattr(prob, "bl_alias", None) is None else np.ascontiguousarray(prob.bl_alias, dtype=np.int32),
-            # the reference's variables fg_r[chunk] / fg_i[chunk] (a layer-wise optimizer -- LAMB -- takes one trust ratio per variable)
-            None if getattr(prob, "chunk_of_grp", None) is None else np.ascontiguousarray(prob.chunk_of_grp, dtype=np.int32),
-        ]
-        d = _lib.ProblemDesc(
-            nants=prob.nants, nfreqs=prob.nfreqs, ngrps=prob.ngrps, nbls=prob.nbls, nbasis=len(basis),
-            basis_offset=_ptr(offs), basis_nvec=_ptr(nvec), basis_nrowblk=_ptr(nrb), basis_data=_ptr(flat),
-            grp_basis=_ptr(keep[4]), grp_bl_start=_ptr(keep[5]), bl_ant0=_ptr(keep[6]), bl_ant1=_ptr(keep[7]),
-            bl_rowblk=_ptr(keep[8]), bl_alias=_ptr(keep[9]), nslices=int(getattr(prob, "nslices", 1) or 1), grp_var=_ptr(keep[10]),
-            layout={"stream": _lib.CAL_LAYOUT_STREAM, "shared": _lib.CAL_LAYOUT_SHARED}[layout],
-            kernel_path={"auto": _lib.CAL_PATH_AUTO, "general": _lib.CAL_PATH_GENERAL, "dense": _lib.CAL_PATH_DENSE,
-                         "dense_f32": _lib.CAL_PATH_DENSE_F32, "dense_split1": _lib.CAL_PATH_DENSE_SPLIT1,
-                         "general_full": _lib.CAL_PATH_GENERAL_FULL}[kernel_path],
-        )
+        d, _keep = problem_desc(prob, self.dtype, layout, kernel_path)
         _lib.check(self._lib.cal_solver_set_problem(self._h, C.byref(d)))
         self.problem = prob
         self.nants, self.nfreqs, self.nbls, self.ncoeffs = prob.nants, prob.nfreqs, prob.nbls, prob.ncoeffs

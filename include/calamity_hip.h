@@ -189,6 +189,20 @@ int cal_device_count(int* count);
  * halves agree exactly.  Returns 1 / 0, or a negative cal_status.  max_residual, max_abs (either may be NULL): the largest
  * |A[nfreqs-1-f][k] - (-1)^k A[f][k]| and the largest |A| of the block (zeros where the shape already rules folding out). */
 int cal_basis_foldable(int dtype, const void* block, int32_t nfreqs, int32_t nvec, int32_t nrowblk, double* max_residual, double* max_abs);
+/* Host only (no device is touched): runs the planner of cal_solver_set_problem on `d` for a solver of `dtype` and copies plan array `what`
+ * to `out` as raw bytes (*bytes of them; CAL_ERR_INVALID if cap_bytes is too small).  Returns the planner's cal_status -- the code and
+ * message cal_solver_set_problem would give -- when the problem is refused.  For tests (tests/test_plan_host.py).
+ * what = 0: 31 scalars, 8 bytes each, int64 except [11]: fpad, ncoef, nslices, na_slice, fold, small_loads, nitems, nitems_simple, nitems_plain,
+ *   gc_direct, gcp_len, basis_bytes (double), steps_per_sync, the dynamic LDS of fused_basis / fused_group / fused_multi / fused_multi_mfma, mf_ok,
+ *   mf_split, mf_split2, mf_npanels, mf_grid, the dense launch's LDS (gradient, loss), nheads, nheads_mfma, heads_one_pass_local, mm_grid, lamb_ok,
+ *   lamb_nvar, lamb_ncvar.
+ * 1 fb (int32 per basis block), 2 tile offsets of the blocks (int64), 3 bl_tile (int64), 4 copy jobs (3 int64 each), 5 grp_coff, 6 slice_coff,
+ * 7 slice_cblk, 8 LAMB variables (LambVar), 9 / 10 / 11 the coefficient variables' first coefficients, slices and grp_var ids, 12 runs (int2),
+ * 13 items in launch order (Item), 14 item_goff, 15 grp_item_ptr, 16 coef_grp (empty when every group is one item), 17 / 18 and 19 / 20 the slices'
+ * loss-partial index (ptr, idx) over items and over panels (empty with one slice), 21 members (Member), 22 heads, 23 panels (PanelItem),
+ * 24 the panel map, 25 byte offsets of the blocks' packed operands, 26 CsGroup per group, 27 / 28 the antenna CSR (ptr; int2 entries).
+ * Records are the structs of the kernel headers; int32 where nothing else is said. */
+int cal_debug_plan(int dtype, const cal_problem_desc* d, int what, void* out, int64_t cap_bytes, int64_t* bytes);
 int cal_device_info(int device, char* name, size_t name_len, int64_t* total_mem_bytes, int32_t* compute_units);
 /* Measured streaming peaks of the device (no reference counterpart; BASELINE.md section 3 asks for the roofline against a
  * stream kernel measured on the box next to the nominal 8 TB/s): a read-only sweep (16-byte non-temporal loads, the

@@ -1,0 +1,106 @@
+// plan_sanitize.hip -- the set-up planner (calamity_amd/csrc/problem_plan.hpp) under the host sanitizers, with no device and no
+// interpreter: four problems built in code (folded STREAM, heads of baselines that share tiles, forced dense, multi-baseline runs),
+// planned for fp32 and fp64.  Exits non-zero on a planner error; the sanitizers abort on a finding.
+//
+//   hipcc --offload-arch=gfx950 -std=c++17 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
+//         -o plan_sanitize tools/plan_sanitize.hip && ./plan_sanitize
+#include "../calamity_amd/csrc/problem_plan.hpp"
+
+#include <cstdint>
+
+namespace {
+
+struct Case {
+  const char* name;
+  int nants, nfreqs, nslices, layout, kernel_path;
+  std::vector<int> nvec, nrowblk;          // per basis block
+  std::vector<int> grp_basis, grp_nbl;     // per group
+  std::vector<int> rowblk, alias;          // per baseline (empty: none)
+};
+
+template <typename T>
+int run(const Case& c) {
+  const int nbasis = (int)c.nvec.size(), ngrps = (int)c.grp_basis.size();
+  std::vector<int64_t> off(nbasis + 1, 0);
+  for (int u = 0; u < nbasis; ++u) off[u + 1] = off[u] + (int64_t)c.nvec[u] * c.nrowblk[u] * c.nfreqs;
+  // mirror-symmetric blocks, A[F-1-f][k] = (-1)^k A[f][k] exactly: a single-row-block STREAM problem folds in both dtypes
+  std::vector<T> data((size_t)off[nbasis]);
+  uint32_t seed = 12345u;
+  for (int u = 0; u < nbasis; ++u)
+    for (int r = 0; r < c.nrowblk[u]; ++r)
+      for (int f = 0; f < c.nfreqs; ++f)
+        for (int k = 0; k < c.nvec[u]; ++k) {
+          T* blk = data.data() + off[u] + (size_t)r * c.nfreqs * c.nvec[u];
+          if (f < (c.nfreqs + 1) / 2) {
+            seed = seed * 1664525u + 1013904223u;
+            blk[(size_t)f * c.nvec[u] + k] = (T)((seed >> 8) * (1.0 / 16777216.0) - 0.5);
+          } else {
+            const T m = blk[(size_t)(c.nfreqs - 1 - f) * c.nvec[u] + k];
+            blk[(size_t)f * c.nvec[u] + k] = (k & 1) ? -m : m;
+          }
+        }
+  std::vector<int> start(ngrps + 1, 0);
+  for (int g = 0; g < ngrps; ++g) start[g + 1] = start[g] + c.grp_nbl[g];
+  const int nbls = start[ngrps], nas = c.nants / c.nslices;
+  // baselines listed slice by slice: group g lies in slice g * nslices / ngrps, its baselines walk that slice's antenna pairs
+  std::vector<int> a0(nbls), a1(nbls);
+  for (int g = 0; g < ngrps; ++g)
+    for (int b = start[g]; b < start[g + 1]; ++b) {
+      const int t = (int)((long long)g * c.nslices / ngrps);
+      a0[b] = t * nas + b % nas;
+      a1[b] = t * nas + (b % nas + 1 + (b / nas) % (nas - 1)) % nas;
+    }
+  cal_problem_desc d{};
+  d.nants = c.nants; d.nfreqs = c.nfreqs; d.ngrps = ngrps; d.nbls = nbls; d.nbasis = nbasis;
+  d.basis_offset = off.data(); d.basis_nvec = c.nvec.data(); d.basis_nrowblk = c.nrowblk.data(); d.basis_data = data.data();
+  d.grp_basis = c.grp_basis.data(); d.grp_bl_start = start.data(); d.bl_ant0 = a0.data(); d.bl_ant1 = a1.data();
+  d.bl_rowblk = c.rowblk.empty() ? nullptr : c.rowblk.data();
+  d.bl_alias = c.alias.empty() ? nullptr : c.alias.data();
+  d.layout = c.layout; d.kernel_path = c.kernel_path; d.nslices = c.nslices;
+  ProblemPlan<T> p;
+  const int rc = plan_problem(&d, p);
+  if (rc != CAL_OK) {
+    fprintf(stderr, "%s (%d-byte reals): planner error %d: %s\n", c.name, (int)sizeof(T), rc, g_err.c_str());
+    return 1;
+  }
+  printf("%-12s %d-byte reals: fpad %d, %d items (%d simple, %d plain), fold %d, gc_direct %d, %d runs, %d heads (%d matrix-core, grid %d), dense %d: %d panels, grid %d\n",
+         c.name, (int)sizeof(T), p.fpad, p.nitems, p.nitems_simple, p.nitems_plain, (int)p.fold, (int)p.gc_direct, (int)p.runs.size(), p.nheads, p.nheads_mfma,
+         p.mm_grid, (int)p.mf_ok, p.mf_npanels, p.mf_grid);
+  return 0;
+}
+
+std::vector<int> cycle(int n, int m) {
+  std::vector<int> v(n);
+  for (int i = 0; i < n; ++i) v[i] = i % m;
+  return v;
+}
+
+}  // namespace
+
+int main() {
+  std::vector<Case> cases;
+  // folded STREAM: 45 single-baseline groups, tile widths from 128 down to 16, the widest block cut into several items
+  cases.push_back({"fold", 10, 256, 1, CAL_LAYOUT_STREAM, CAL_PATH_AUTO, {12, 60, 120, 200, 230}, {1, 1, 1, 1, 1}, cycle(45, 5), std::vector<int>(45, 1), {}, {}});
+  // heads: 3 slices of 70 single-baseline groups that share tiles; 66 heads for the matrix-core kernel, the 230-vector blocks beside it
+  {
+    Case c{"alias", 39, 256, 3, CAL_LAYOUT_STREAM, CAL_PATH_AUTO, {8, 33, 100, 224, 230}, {1, 1, 1, 1, 1}, {}, std::vector<int>(210, 1), {}, {}};
+    for (int t = 0; t < 3; ++t)
+      for (int g = 0; g < 70; ++g) {
+        c.grp_basis.push_back(g < 66 ? g % 4 : 4);
+        c.alias.push_back(t == 0 ? -1 : g);
+      }
+    cases.push_back(c);
+  }
+  // forced dense (fp32: split-bf16 operands; fp64: the fp64 matrix-core kernel), 2 slices, odd baseline counts per block
+  cases.push_back({"dense", 26, 256, 2, CAL_LAYOUT_SHARED, CAL_PATH_DENSE, {20, 45, 77, 130, 200}, {1, 1, 1, 1, 1}, cycle(150, 5), std::vector<int>(150, 1), {}, {}});
+  // multi-baseline groups over two row blocks, one run longer than kRunMax
+  {
+    Case c{"runs", 30, 96, 1, CAL_LAYOUT_STREAM, CAL_PATH_AUTO, {5, 12, 30, 7, 9}, {2, 2, 2, 2, 2}, {0, 1, 2, 3, 4}, {1, 3, 20, 70, 300}, {}, {}};
+    for (int g = 0; g < 5; ++g)
+      for (int b = 0; b < c.grp_nbl[g]; ++b) c.rowblk.push_back(g == 4 ? (b < 290 ? 0 : 1) : (b / 3) % 2);
+    cases.push_back(c);
+  }
+  int bad = 0;
+  for (const Case& c : cases) bad += run<float>(c) + run<double>(c);
+  return bad ? 1 : 0;
+}
