@@ -286,6 +286,14 @@ class SliceBatchFitter:
                                                       reset_coeff_moments=reset_coeff_moments))
         return {k: sum(o[k] for o in outs) for k in ("nsolved", "nsingular")}
 
+    def solve_gain_coeffs(self, nsweeps, damping=0.5, ridge=1e-6, slice_mask=None, reset_gain_moments=False):
+        """``HipFitSolver.solve_gain_coeffs`` on every worker (``slice_mask``: one entry per slice of the batch).  With several workers
+        each sweep sums the three antenna planes of the workers' baselines in one exchange; ``y`` is replicated, so every worker then
+        computes the same update of its replica: the counts are worker 0's."""
+        outs = self._each(lambda r, s: s.solve_gain_coeffs(nsweeps, damping=damping, ridge=ridge, slice_mask=slice_mask,
+                                                           reset_gain_moments=reset_gain_moments))
+        return outs[0]
+
     def hold_slices(self, mask=None):
         """``HipFitSolver.hold_slices`` on every worker."""
         self._each(lambda r, s: s.hold_slices(mask))

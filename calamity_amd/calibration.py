@@ -645,6 +645,10 @@ def fit_gains_and_foregrounds(
     gain_solve_damping=0.5,
     coeff_solve_rounds=0,
     coeff_solve_ridge=1e-6,
+    gain_basis_solve_sweeps=0,
+    gain_basis_solve_every=0,
+    gain_basis_solve_damping=0.5,
+    gain_basis_solve_ridge=1e-6,
     **opt_kwargs,
 ):
     """Run the optimization loop that fits gains and foreground coefficients -- calibration.py:447-738.
@@ -661,10 +665,19 @@ def fit_gains_and_foregrounds(
     the per-channel gains; everything else -- loss, loop semantics, returns (full gains) -- is unchanged.  Default ``None``: free
     per-channel gains.  ``gain_solve_sweeps`` / ``gain_solve_every`` / ``gain_solve_damping``: closed-form gain sweeps before and
     between the descent steps, and ``coeff_solve_rounds`` / ``coeff_solve_ridge``: closed-form coefficient solves in front of them,
-    see ``calibrate_and_model_tensor``.
+    and ``gain_basis_solve_sweeps`` / ``gain_basis_solve_every`` / ``gain_basis_solve_damping`` / ``gain_basis_solve_ridge``: the sweeps
+    of a fit with a ``gain_basis``, see ``calibrate_and_model_tensor``.
     """
     _check_gain_solve(gain_solve_sweeps, gain_solve_every, gain_solve_damping, gain_basis is not None)
     _check_coeff_solve(coeff_solve_rounds, coeff_solve_ridge, freeze_model)
+    _check_gain_basis_solve(gain_basis_solve_sweeps, gain_basis_solve_every, gain_basis_solve_damping, gain_basis_solve_ridge,
+                            gain_basis is not None, False)
+    if gain_basis_solve_sweeps or gain_basis_solve_every:  # a basis fit: its sweeps stand where the per-channel sweeps stand
+        sweep = lambda n, **kw: solver.solve_gain_coeffs(n, damping=gain_basis_solve_damping, ridge=gain_basis_solve_ridge, **kw)["nsingular"]  # noqa: E731
+        n_sweeps, every = gain_basis_solve_sweeps, gain_basis_solve_every
+    else:
+        sweep = lambda n, **kw: solver.solve_gains(n, damping=gain_solve_damping, **kw)  # noqa: E731
+        n_sweeps, every = gain_solve_sweeps, gain_solve_every
     if gain_basis is not None:
         gain_basis = _check_gain_basis(gain_basis, np.asarray(g_r).shape[-1])
     echo(f"Using {str(dtype)} precision.")
@@ -691,14 +704,14 @@ def fit_gains_and_foregrounds(
     else:
         solver.set_regularization(None)
     solver.set_optimizer(optimizer, **opt_kwargs)
-    nsingular = None
+    nsingular = gb_singular = None
     if coeff_solve_rounds > 0:  # alternating least squares: rounds of (the coefficients in closed form, then the gain sweeps)
         for _ in range(coeff_solve_rounds):
             nsingular = solver.solve_coeffs(ridge=coeff_solve_ridge)["nsingular"]
-            if gain_solve_sweeps > 0:
-                solver.solve_gains(gain_solve_sweeps, damping=gain_solve_damping)
-    elif gain_solve_sweeps > 0:  # the coefficients are initialised: the gains in closed form before any descent step
-        solver.solve_gains(gain_solve_sweeps, damping=gain_solve_damping)
+            if n_sweeps > 0:
+                gb_singular = sweep(n_sweeps)
+    elif n_sweeps > 0:  # the coefficients are initialised: the gains in closed form before any descent step
+        gb_singular = sweep(n_sweeps)
     fit_history = {"loss": []}
     if n_profile_steps > 0:
         echo(f"{datetime.datetime.now()} Profiling with {n_profile_steps}. And writing output to {profile_log_dir}...")
@@ -711,12 +724,12 @@ def fit_gains_and_foregrounds(
     echo(f"{datetime.datetime.now()} Building Computational Graph...\n", verbose=verbose)
     solver.run(1, record=False, freeze_model=freeze_model)  # the unrecorded step of calibration.py:693
     echo(f"{datetime.datetime.now()} Performing Gradient Descent...\n", verbose=verbose)
-    if gain_solve_every > 0:
+    if every > 0:
         # the recorded loop in chunks (the solver's loop state -- step count, previous and lowest loss -- persists from run to run), a
         # gain solve between two chunks while the loop goes on
         losses, stopped = np.zeros(0), False
         while len(losses) < maxsteps and not stopped:
-            n = min(gain_solve_every, maxsteps - len(losses))
+            n = min(every, maxsteps - len(losses))
             part, stopped, _ = solver.run(n, record=True, tol=tol, use_min=use_min, freeze_model=freeze_model)
             losses = np.concatenate([losses, part])
             if len(part) < n:
@@ -724,12 +737,14 @@ def fit_gains_and_foregrounds(
             if not stopped and len(losses) < maxsteps:
                 if coeff_solve_rounds > 0:
                     nsingular = solver.solve_coeffs(ridge=coeff_solve_ridge, reset_coeff_moments=True)["nsingular"]
-                solver.solve_gains(max(1, gain_solve_sweeps), damping=gain_solve_damping, reset_gain_moments=True)
+                gb_singular = sweep(max(1, n_sweeps), reset_gain_moments=True)
     else:
         losses, stopped, _ = solver.run(maxsteps, record=True, tol=tol, use_min=use_min, freeze_model=freeze_model)
     fit_history["loss"] = [dtype.type(l) for l in losses]
     if nsingular is not None:
         fit_history["coeff_solve_singular"] = int(nsingular)
+    if gain_basis_solve_sweeps or gain_basis_solve_every:
+        fit_history["gain_basis_solve_singular"] = int(gb_singular or 0)
     if stopped:
         echo(f"Tolerance thresshold met with delta of {np.abs(losses[-1] - losses[-2]):.2e}. Terminating...\n ", verbose=verbose)
     g_r_opt, g_i_opt, c_r, c_i = solver.get_params(which=1 if (use_min and len(losses) > 0) else 0)
@@ -766,7 +781,27 @@ def _check_gain_solve(sweeps, every, damping, gain_basis_given):
         raise ValueError(f"gain_solve_damping must lie in (0, 1], got {damping!r}")
     if (sweeps or every) and gain_basis_given:
         raise ValueError("gain_solve_sweeps / gain_solve_every solve free per-channel gains in closed form: they cannot be combined with "
-                         "gain_basis / gain_max_dly / gain_time_basis / gain_time_scale (projecting the solved gains onto a basis is not implemented)")
+                         "gain_basis / gain_max_dly / gain_time_basis / gain_time_scale (projecting the solved gains onto a basis is not implemented); a fit with a frequency gain basis has "
+                         "gain_basis_solve_sweeps / gain_basis_solve_every")
+
+
+def _check_gain_basis_solve(sweeps, every, damping, ridge, freq_basis_given, time_basis_given):
+    """The arguments of the closed-form sweeps of a gain-basis fit (ValueError before any device work)."""
+    for v in (sweeps, every):
+        if isinstance(v, bool) or int(v) != v or v < 0:
+            raise ValueError(f"gain_basis_solve_sweeps and gain_basis_solve_every must be non-negative integers, got {sweeps!r} and {every!r}")
+    if not 0.0 < float(damping) <= 1.0:
+        raise ValueError(f"gain_basis_solve_damping must lie in (0, 1], got {damping!r}")
+    if not (np.isfinite(float(ridge)) and float(ridge) >= 0.0):
+        raise ValueError(f"gain_basis_solve_ridge must be finite and >= 0, got {ridge!r}")
+    if not (sweeps or every):
+        return
+    if time_basis_given:
+        raise ValueError("gain_basis_solve_sweeps / gain_basis_solve_every solve the coefficients of a frequency gain basis antenna by antenna: they "
+                         "cannot be combined with gain_time_basis / gain_time_scale, whose variables couple the times (a joint system that is not implemented)")
+    if not freq_basis_given:
+        raise ValueError("gain_basis_solve_sweeps / gain_basis_solve_every solve the coefficients of a frequency gain basis: give gain_basis or "
+                         "gain_max_dly (free per-channel gains have gain_solve_sweeps / gain_solve_every)")
 
 
 def _check_coeff_solve(rounds, ridge, freeze_model):
@@ -906,6 +941,10 @@ def calibrate_and_model_tensor(
     gain_solve_damping=0.5,
     coeff_solve_rounds=0,
     coeff_solve_ridge=1e-6,
+    gain_basis_solve_sweeps=0,
+    gain_basis_solve_every=0,
+    gain_basis_solve_damping=0.5,
+    gain_basis_solve_ridge=1e-6,
     **opt_kwargs,
 ):
     """Simultaneous calibration and foreground fitting -- calibration.py:963-1331, same arguments, defaults and
@@ -982,6 +1021,26 @@ def calibrate_and_model_tensor(
       refused there).  ``ValueError`` with ``freeze_model``.  Like the sweeps it minimises the chi-square term only.
       ``fit_history[polnum][time_index]["coeff_solve_singular"]`` (present only with the feature on): the groups the last solve left
       alone because their normal matrix was singular (wholly flagged); in a batch the count is over the slices fitted together.
+    * ``gain_basis_solve_sweeps`` / ``gain_basis_solve_every`` / ``gain_basis_solve_damping`` / ``gain_basis_solve_ridge`` (defaults 0, 0,
+      0.5, 1e-6: off, no call changes by a bit): the closed-form sweeps for fits with ``gain_basis`` / ``gain_max_dly``
+      (``HipFitSolver.solve_gain_coeffs``): the StefCal sweep projected on the basis ``g = g0 + B y``.  With ``num``, ``den`` the
+      per-antenna sums of a per-channel sweep from the OLD gains, for antenna ``a``::
+
+          r_a[f]  = num_a[f] - den_a[f] g_a[f]                 (complex; minus half the chi-square gradient w.r.t. g_a)
+          N_a     = B^T diag(den_a) B                          [K][K], real symmetric
+          rhs_a   = B^T r_a                                    [K], complex
+          (N_a + ridge (tr N_a / K) I) delta_a = rhs_a         (one factorisation, two right-hand sides: re, im)
+          y_a    <- y_a + damping delta_a                      then gains = g0 + B y for the whole array
+
+      They act where ``gain_solve_sweeps`` / ``gain_solve_every`` act on per-channel fits, in the loop, in batches and on several
+      devices: ``gain_basis_solve_sweeps=N`` sweeps after the optimizer is set and before the first unrecorded step; with
+      ``coeff_solve_rounds=R``, R rounds of [coefficient solve, N sweeps]; ``gain_basis_solve_every=K``: the recorded loop in chunks of
+      K steps, between two chunks one coefficient solve (if ``coeff_solve_rounds > 0``) and ``max(1, N)`` sweeps with the optimizer's
+      ``y`` moments started over, on the slices whose loop has not ended.  A flagged channel of an antenna that has data elsewhere
+      moves (the basis interpolates across it).  ``ValueError`` without ``gain_basis`` / ``gain_max_dly`` and with ``gain_time_basis`` /
+      ``gain_time_scale`` (the joint system across times is a different solve).  The sweeps minimise the chi-square term only.
+      ``fit_history[polnum][time_index]["gain_basis_solve_singular"]`` (present only with the feature on): the antenna rows the last
+      sweep left alone (no unflagged cross-correlation, or a non-positive pivot); in a batch the count is over the slices fitted together.
     * ``layout``: "shared" (default; baselines alias the distinct basis blocks) or "stream" (every baseline owns its tiles).
     * ``parallel_fits`` (default 1): with ``batch_slices=False``, fits that many slices concurrently, each on its own
       solver and HIP stream.
@@ -991,6 +1050,8 @@ def calibrate_and_model_tensor(
     _check_gain_solve(gain_solve_sweeps, gain_solve_every, gain_solve_damping,
                       any(b is not None for b in (gain_basis, gain_max_dly, gain_time_basis, gain_time_scale)))
     _check_coeff_solve(coeff_solve_rounds, coeff_solve_ridge, freeze_model)
+    _check_gain_basis_solve(gain_basis_solve_sweeps, gain_basis_solve_every, gain_basis_solve_damping, gain_basis_solve_ridge,
+                            gain_basis is not None or gain_max_dly is not None, gain_time_basis is not None or gain_time_scale is not None)
     if gain_max_dly is not None:
         gain_basis = modeling.gain_dpss_basis(np.asarray(uvdata.freq_array, dtype=np.float64).ravel(), gain_max_dly)
     if gain_time_basis is not None and gain_time_scale is not None:
@@ -1082,6 +1143,7 @@ def calibrate_and_model_tensor(
             correct_model=correct_model, correct_resid=correct_resid, device_split=device_split, gain_basis=gain_basis,
             gain_time_basis=gain_time_basis, fit_quality=fit_quality,
             gain_solve=(gain_solve_sweeps, gain_solve_every, gain_solve_damping), coeff_solve=(coeff_solve_rounds, coeff_solve_ridge),
+            gain_basis_solve=(gain_basis_solve_sweeps, gain_basis_solve_every, gain_basis_solve_damping, gain_basis_solve_ridge),
         )
         return model, resid, gains, fit_history  # (every slice left _fit_slices_batched in its final state)
     assert gain_time_basis is None, "a gain time basis must not reach the loop over single times"
@@ -1143,7 +1205,9 @@ def calibrate_and_model_tensor(
                 graph_mode=graph_mode, n_profile_steps=n_profile_steps, profile_log_dir=profile_log_dir,
                 sky_model_r=sky_model_r, sky_model_i=sky_model_i, model_regularization=model_regularization, gain_basis=gain_basis,
                 gain_solve_sweeps=gain_solve_sweeps, gain_solve_every=gain_solve_every, gain_solve_damping=gain_solve_damping,
-                coeff_solve_rounds=coeff_solve_rounds, coeff_solve_ridge=coeff_solve_ridge, **opt_kwargs,
+                coeff_solve_rounds=coeff_solve_rounds, coeff_solve_ridge=coeff_solve_ridge, gain_basis_solve_sweeps=gain_basis_solve_sweeps,
+                gain_basis_solve_every=gain_basis_solve_every, gain_basis_solve_damping=gain_basis_solve_damping,
+                gain_basis_solve_ridge=gain_basis_solve_ridge, **opt_kwargs,
             )
             # yield_fg_model_array x 2 + insert_model_into_uvdata_tensor (calibration.py:1271-1292) without the
             # nants x nants cubes: one A c pass for both components, rows written straight back
@@ -1374,7 +1438,7 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
                         skip_threshold, use_model_snr_weights, optimizer, use_min, freeze_model, tol, maxsteps, n_profile_steps,
                         profile_log_dir, model_regularization, verbose, max_batch, devices, layout, opt_kwargs, correct_model=True,
                         correct_resid=False, device_split=None, gain_basis=None, gain_time_basis=None, fit_quality=False,
-                        gain_solve=(0, 0, 0.5), coeff_solve=(0, 1e-6)):
+                        gain_solve=(0, 0, 0.5), coeff_solve=(0, 1e-6), gain_basis_solve=(0, 0, 0.5, 1e-6)):
     """The pol x time loop of calibration.py:1160-1331 with the fits of all unskipped slices issued as batches: per slice
     exactly the host-side steps of the loop body (skip test :1173-1177, rms scale :1178-1182, tensorize :1184-1233, write-back
     :1271-1300, post-hoc renormalisation :1311-1319, residual and calibration state of the outputs :1322-1331), the gradient
@@ -1382,9 +1446,13 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
     resid and gains are complete when it returns.  ``gain_time_basis`` (``[len(times), L]``): the unskipped times of a polarization
     are one batch and one JOINT fit (one loop state, loss = the sum over the times; calibrate_and_model_tensor's docstring).
     ``gain_solve``: (gain_solve_sweeps, gain_solve_every, gain_solve_damping), ``coeff_solve``: (coeff_solve_rounds, coeff_solve_ridge) of
-    calibrate_and_model_tensor."""
+    calibrate_and_model_tensor, ``gain_basis_solve``: its (gain_basis_solve_sweeps, _every, _damping, _ridge), which stand in for
+    ``gain_solve`` on a fit with a frequency gain basis."""
     gs_sweeps, gs_every, gs_damping = gain_solve
     cs_rounds, cs_ridge = coeff_solve
+    gbs_on = bool(gain_basis_solve[0] or gain_basis_solve[1])
+    if gbs_on:
+        gs_sweeps, gs_every, gbs_damping, gbs_ridge = gain_basis_solve
     OPTIMIZERS[optimizer]  # unknown optimizer -> KeyError, like calibration.py:571
     dtype = np.dtype(dtype)
     layout = layout or "shared"
@@ -1494,14 +1562,18 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
         else:
             fitter.set_regularization(None)
         fitter.set_optimizer(optimizer, **opt_kwargs)
-        nsingular = None
+        nsingular = gb_singular = None
+        if gbs_on:  # a basis fit: its sweeps stand where the per-channel sweeps stand
+            sweep = lambda n, **kw: fitter.solve_gain_coeffs(n, damping=gbs_damping, ridge=gbs_ridge, **kw)["nsingular"]  # noqa: E731
+        else:
+            sweep = lambda n, **kw: fitter.solve_gains(n, damping=gs_damping, **kw)  # noqa: E731
         if cs_rounds > 0:  # alternating least squares: rounds of (the coefficients in closed form, then the gain sweeps)
             for _ in range(cs_rounds):
                 nsingular = fitter.solve_coeffs(ridge=cs_ridge)["nsingular"]
                 if gs_sweeps > 0:
-                    fitter.solve_gains(gs_sweeps, damping=gs_damping)
+                    gb_singular = sweep(gs_sweeps)
         elif gs_sweeps > 0:  # the coefficients are initialised: the gains in closed form before any descent step
-            fitter.solve_gains(gs_sweeps, damping=gs_damping)
+            gb_singular = sweep(gs_sweeps)
         if n_profile_steps > 0:
             fitter.timing_enable(True)
             fitter.run_slices(n_profile_steps, record=False, freeze_model=freeze_model)
@@ -1526,7 +1598,7 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
                     fitter.hold_slices(over)
                     if cs_rounds > 0:
                         nsingular = fitter.solve_coeffs(ridge=cs_ridge, slice_mask=~over, reset_coeff_moments=True)["nsingular"]
-                    fitter.solve_gains(max(1, gs_sweeps), damping=gs_damping, slice_mask=~over, reset_gain_moments=True)
+                    gb_singular = sweep(max(1, gs_sweeps), slice_mask=~over, reset_gain_moments=True)
             fitter.hold_slices(None)
             results = [(np.concatenate(parts[t]), bool(over[t]), int(nupd[t])) for t in range(nt)]
         else:
@@ -1552,7 +1624,8 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
         # at the reported parameters (every slice's own minimum with use_min), on the data and weights the fit used
         quality = fitter.fit_quality(gm_r, gm_i) if fit_quality else None
         echo(f"{datetime.datetime.now()} ... fitted.\n", verbose=verbose)
-        return dict(results=results, m_r=m_r, m_i=m_i, gm_r=gm_r, gm_i=gm_i, quality=quality, nsingular=nsingular)
+        return dict(results=results, m_r=m_r, m_i=m_i, gm_r=gm_r, gm_i=gm_i, quality=quality, nsingular=nsingular,
+                    gb_singular=int(gb_singular or 0) if gbs_on else None)
 
     def post(batch, out):
         for t, (sl, res) in enumerate(zip(batch, out["results"])):
@@ -1562,6 +1635,8 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
             fit_history[sl["polnum"]][sl["time_index"]] = {"loss": [dtype.type(l) for l in res[0]]}
             if out.get("nsingular") is not None:
                 fit_history[sl["polnum"]][sl["time_index"]]["coeff_solve_singular"] = int(out["nsingular"])
+            if out.get("gb_singular") is not None:
+                fit_history[sl["polnum"]][sl["time_index"]]["gain_basis_solve_singular"] = int(out["gb_singular"])
             if out.get("quality") is not None:  # (before the post-hoc renormalisation, which leaves g_i conj(g_j) m as it is)
                 q = out["quality"]
                 insert_fit_quality(gains, fit_history[sl["polnum"]][sl["time_index"]], sl["time"], sl["pol"],
@@ -2007,6 +2082,16 @@ def fitting_argparser():
                          "default 0: descent only")
     sp.add_argument("--coeff_solve_ridge", type=float, default=1e-6,
                     help="ridge of a coefficient solve, as a fraction of the mean diagonal of a group's normal matrix; default 1e-6")
+    sp.add_argument("--gain_basis_solve_sweeps", type=int, default=0,
+                    help="with --gain_max_dly: solve the gain-basis coefficients in closed form (damped StefCal sweeps projected on the basis) this "
+                         "many times before the first descent step; default 0: descent only")
+    sp.add_argument("--gain_basis_solve_every", type=int, default=0,
+                    help="with --gain_max_dly: run basis sweeps (--gain_basis_solve_sweeps of them, at least one) after every this many recorded "
+                         "descent steps; default 0: never")
+    sp.add_argument("--gain_basis_solve_damping", type=float, default=0.5,
+                    help="damping of a basis sweep, in (0, 1]: y <- y + damping x the closed-form step; default 0.5")
+    sp.add_argument("--gain_basis_solve_ridge", type=float, default=1e-6,
+                    help="ridge of a basis sweep, as a fraction of the mean diagonal of an antenna's normal matrix; default 1e-6")
     return ap
 
 

@@ -28,6 +28,7 @@
 #include "fit_quality_kernels.hpp"
 #include "gain_solve_kernels.hpp"
 #include "coeff_solve_kernels.hpp"
+#include "gain_basis_solve_kernels.hpp"
 #include "problem_plan.hpp"
 #include <cstdlib>
 #include <dlfcn.h>
@@ -159,6 +160,8 @@ struct cal_solver {
   virtual int hold_slices(const uint8_t* mask) = 0;
   virtual int solve_coeffs(const cal_coeff_solve_desc* d, cal_coeff_solve_result* res) = 0;
   virtual int set_coeff_solve_scratch(int64_t bytes) = 0;
+  virtual int solve_gain_coeffs(const cal_gain_coeff_solve_desc* d, cal_gain_coeff_solve_result* res) = 0;
+  virtual int get_gain_coeff_moments(void* ym_r, void* ym_i, void* yv_r, void* yv_i, void* cm_r, void* cm_i, void* cv_r, void* cv_i, int64_t* t) = 0;
   virtual int init_coeffs(const void* sr, const void* si) = 0;
   virtual int synchronize() = 0;
   virtual int timing_enable(int e) = 0;
@@ -211,6 +214,9 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
   static constexpr int64_t kCsScratchDefault = 256ll << 20;  // bytes of cs_n + cs_d a chunk may take (one group alone may take more)
   static constexpr int kCsLdsDoubles = 16384;                 // 128 KB: a factor of up to 126 vectors stays in LDS
   int64_t cs_bound = kCsScratchDefault;
+  // solve_gain_coeffs (gain_basis_solve_kernels.hpp): N_a of a chunk of antenna rows in T (gbs_n), its factor in double where it does not
+  // fit LDS (gbs_d), rhs [nants][2][K] T, the two counters; the chunks share cs_bound
+  DevBuf gbs_n, gbs_d, gbs_rhs, gbs_cnt;
   std::vector<uint8_t> held;                   // hold_slices: [nslices], 1 = the slice enters every later run as stopped (empty: none)
   DevBuf fq_out, fq_gains;                     // fit_quality: chisq_ant | wsum_ant ([nants][nfreqs] doubles each, the exchange payload) | chisq_bl | wsum_bl; gains given for one evaluation
   DevBuf members, heads;                       // baselines that share tiles (bl_alias): member lists of the head items, head item indices
@@ -1281,6 +1287,10 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     gb_nvec = gb_kpad = 0;
     tb_T = tb_L = tb_lpad = tb_tpad = tb_na = 0;
     for (DevBuf* b : {&gb_B, &gb_Bt, &gb_g0, &gb_y, &gb_ym, &gb_yv, &gb_ysnap, &gb_proj, &tb_B, &tb_Bt, &tb_z, &tb_pf}) b->release();
+    release_gain_coeff_solve();
+  }
+  void release_gain_coeff_solve() {  // the scratch of solve_gain_coeffs: sized again by the next call
+    for (DevBuf* b : {&gbs_n, &gbs_d, &gbs_rhs, &gbs_cnt}) b->release();
   }
   // the fit starts from the gains the solver holds now: g0 := gains, y := 0 (and its snapshot with it)
   int rebase_gain_basis() {
@@ -1412,6 +1422,27 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     const long long rows = y_rows() * (y_row() / y_w());
     if (y_r) CAL_TRY(download_rows(y_r, y, rows, 2, 0, y_cols(), y_w()));
     if (y_i) CAL_TRY(download_rows(y_i, y, rows, 2, 1, y_cols(), y_w()));
+    return CAL_OK;
+  }
+  // the optimizer's slots of a fit with a gain basis, read only (get_moments / set_moments stay refused there: no resume): the y slots
+  // in the shape of get_gain_coeffs, the coefficient slots, and every slice's own update count
+  int get_gain_coeff_moments(void* ym_r, void* ym_i, void* yv_r, void* yv_i, void* cm_r, void* cm_i, void* cv_r, void* cv_i, int64_t* t) override {
+    HIP_TRY(hipSetDevice(device));
+    if (!yb_on()) return fail(CAL_ERR_STATE, "get_gain_coeff_moments: no gain basis is set (cal_solver_set_gain_basis, cal_solver_set_gain_time_basis)");
+    if (!has_opt) return fail(CAL_ERR_STATE, "get_gain_coeff_moments: no optimizer is set (cal_solver_set_optimizer)");
+    HIP_TRY(hipStreamSynchronize(stream));
+    const long long rows = y_rows() * (y_row() / y_w());
+    if (ym_r) CAL_TRY(download_rows(ym_r, gb_ym.as<T>(), rows, 2, 0, y_cols(), y_w()));
+    if (ym_i) CAL_TRY(download_rows(ym_i, gb_ym.as<T>(), rows, 2, 1, y_cols(), y_w()));
+    if (yv_r) CAL_TRY(download_rows(yv_r, gb_yv.as<T>(), rows, 2, 0, y_cols(), y_w()));
+    if (yv_i) CAL_TRY(download_rows(yv_i, gb_yv.as<T>(), rows, 2, 1, y_cols(), y_w()));
+    const size_t cb = (size_t)ncoef * sizeof(T);
+    if (cm_r) HIP_TRY(copy_sync(cm_r, coef_m.as<T>(), cb, hipMemcpyDeviceToHost));
+    if (cm_i) HIP_TRY(copy_sync(cm_i, coef_m.as<T>() + ncoef, cb, hipMemcpyDeviceToHost));
+    if (cv_r) HIP_TRY(copy_sync(cv_r, coef_v.as<T>(), cb, hipMemcpyDeviceToHost));
+    if (cv_i) HIP_TRY(copy_sync(cv_i, coef_v.as<T>() + ncoef, cb, hipMemcpyDeviceToHost));
+    if (t)
+      for (int sl = 0; sl < nslices; ++sl) t[sl] = h_state[sl].t;
     return CAL_OK;
   }
   int eval_gain_coeff_grads(double* loss, void* gy_r, void* gy_i) override {
@@ -1791,7 +1822,8 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     if (!(d->damping > 0.0 && d->damping <= 1.0)) return fail(CAL_ERR_INVALID, "solve_gains: damping = %g lies outside (0, 1]", d->damping);
     if (yb_on())
       return fail(CAL_ERR_UNSUPPORTED, "solve_gains: a gain basis is set (cal_solver_set_gain_basis, cal_solver_set_gain_time_basis): the closed form solves "
-                  "free per-channel gains, and projecting them onto a basis is not implemented; detach the basis (nvec = 0) first");
+                  "free per-channel gains, and projecting them onto a basis is not implemented here; cal_solver_solve_gain_coeffs solves the coefficients of a "
+                  "frequency basis, or detach the basis (nvec = 0) first");
     if (d->reset_gain_moments && !has_opt) return fail(CAL_ERR_STATE, "solve_gains: reset_gain_moments without an optimizer (cal_solver_set_optimizer)");
     CAL_TRY(build_solve_lists());
     const size_t rowbytes = (size_t)nbls * fpad * sizeof(T);
@@ -1869,6 +1901,7 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     if (bytes < 0) return fail(CAL_ERR_INVALID, "set_coeff_solve_scratch: negative bound");
     cs_bound = bytes == 0 ? kCsScratchDefault : bytes;
     release_coeff_solve();
+    release_gain_coeff_solve();
     return CAL_OK;
   }
   // Groups heaviest first (as everywhere: the tail of a launch is made of the lightest), cut into chunks whose N (T) and factor
@@ -2005,6 +2038,127 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     return CAL_OK;
   }
 
+  // cal_solver_solve_gain_coeffs: solve_gains' sequence up to the exchanged planes, then per chunk of antenna rows gain_basis_gram_kernel
+  // and gain_basis_chol_kernel (gain_basis_solve_kernels.hpp), then the gains of the selected slices rebuilt from y.  Every chunk of a
+  // sweep reads the old gains: they are rebuilt behind the last one.  y is replicated and the planes are summed over the ranks, so
+  // every rank computes the same update: no collective beyond solve_gains' own.
+  int solve_gain_coeffs(const cal_gain_coeff_solve_desc* d, cal_gain_coeff_solve_result* res) override {
+    HIP_TRY(hipSetDevice(device));
+    if (!d) return fail(CAL_ERR_INVALID, "solve_gain_coeffs: null description");
+    if (!has_problem) return fail(CAL_ERR_STATE, "solve_gain_coeffs: no problem set (cal_solver_set_problem)");
+    if (!has_data) return fail(CAL_ERR_STATE, "solve_gain_coeffs: no data set (cal_solver_set_data)");
+    if (!has_coef) return fail(CAL_ERR_STATE, "solve_gain_coeffs: the coefficients must be set (cal_solver_set_params)");
+    if (!has_gains) return fail(CAL_ERR_STATE, "solve_gain_coeffs: the gains must be set (cal_solver_set_params)");
+    if (d->nsweeps < 1) return fail(CAL_ERR_INVALID, "solve_gain_coeffs: nsweeps = %d, at least one sweep", d->nsweeps);
+    if (!(d->damping > 0.0 && d->damping <= 1.0)) return fail(CAL_ERR_INVALID, "solve_gain_coeffs: damping = %g lies outside (0, 1]", d->damping);
+    if (!(d->ridge >= 0.0) || !std::isfinite(d->ridge)) return fail(CAL_ERR_INVALID, "solve_gain_coeffs: ridge = %g must be finite and >= 0", d->ridge);
+    if (tb_on())
+      return fail(CAL_ERR_UNSUPPORTED, "solve_gain_coeffs: a gain time basis is set (cal_solver_set_gain_time_basis): its coefficients couple the times of an "
+                  "antenna, a joint (l, k) system this call does not solve; detach the time basis (nvec_t = 0) first");
+    if (!gb_on()) return fail(CAL_ERR_STATE, "solve_gain_coeffs: no frequency gain basis is set (cal_solver_set_gain_basis); cal_solver_solve_gains solves free per-channel gains");
+    if (d->reset_gain_moments && !has_opt) return fail(CAL_ERR_STATE, "solve_gain_coeffs: reset_gain_moments without an optimizer (cal_solver_set_optimizer)");
+    CAL_TRY(build_solve_lists());
+    const size_t rowbytes = (size_t)nbls * fpad * sizeof(T);
+    if (model_buf.bytes < 3 * rowbytes) CAL_TRY(model_buf.alloc(3 * rowbytes));
+    const size_t nant_out = (size_t)nants * nfreqs;
+    if (gs_out.bytes < 3 * nant_out * sizeof(double)) CAL_TRY(gs_out.alloc(3 * nant_out * sizeof(double)));
+    // chunks of antenna rows whose N_a (T) and factor (double, only where it does not fit LDS) stay under cs_bound; at least one row
+    const int K = gb_nvec;
+    const bool in_lds = (long long)(K + 2) * (K | 1) <= kCsLdsDoubles;
+    const long long n_row = (long long)K * K, d_row = in_lds ? 0 : (long long)(K + 2) * K;
+    const long long row_bytes = n_row * (long long)sizeof(T) + d_row * 8;
+    const int rows_per_chunk = (int)std::max<long long>(1, std::min<long long>(nants, cs_bound / row_bytes));
+    if (gbs_n.bytes < (size_t)rows_per_chunk * n_row * sizeof(T)) CAL_TRY(gbs_n.alloc((size_t)rows_per_chunk * n_row * sizeof(T), false));
+    if (gbs_d.bytes < (size_t)rows_per_chunk * d_row * sizeof(double) || !gbs_d.p) CAL_TRY(gbs_d.alloc((size_t)rows_per_chunk * d_row * sizeof(double), false));
+    if (gbs_rhs.bytes < 2 * (size_t)nants * K * sizeof(T)) CAL_TRY(gbs_rhs.alloc(2 * (size_t)nants * K * sizeof(T)));
+    if (!gbs_cnt.p) CAL_TRY(gbs_cnt.alloc(2 * sizeof(int)));
+    const size_t chol_lds = (size_t)std::min<long long>((long long)(K + 2) * (K | 1), kCsLdsDoubles) * sizeof(double);
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&gain_basis_chol_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                kCsLdsDoubles * (int)sizeof(double)));
+    const unsigned char* mask = nullptr;
+    if (d->slice_mask) {
+      if (gs_mask.bytes < (size_t)nslices) CAL_TRY(gs_mask.alloc((size_t)nslices, false));
+      HIP_TRY(copy_sync(gs_mask.p, d->slice_mask, (size_t)nslices, hipMemcpyHostToDevice));
+      mask = gs_mask.as<unsigned char>();
+    }
+    const std::vector<DevState> saved(h_state, h_state + nslices);
+    begin_pass_state();
+    CAL_TRY(push_state());
+    FusedArgs<T> a = fused_args();
+    a.model_r = model_buf.as<T>();
+    a.model_i = model_buf.as<T>() + (size_t)nbls * fpad;
+    T* q_rows = model_buf.as<T>() + 2 * (size_t)nbls * fpad;
+    launch_fused<MODE_MODEL>(a, false);
+    hipLaunchKernelGGL(gain_solve_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, a.model_r, a.model_i, q_rows, data_r.as<T>(),
+                       data_i.as<T>(), wgts.as<T>(), bl_ant.as<int2>(), nbls, nfreqs, fpad);
+    HIP_TRY(hipGetLastError());
+    std::copy(saved.begin(), saved.end(), h_state);
+    CAL_TRY(push_state());
+    constexpr int V = 16 / (int)sizeof(T);
+    const int cblocks = (fpad + 64 * V - 1) / (64 * V);
+    const int nb = (K + kGbsBlock - 1) / kGbsBlock, npairs = nb * (nb + 1) / 2;
+    for (int k = 0; k < d->nsweeps; ++k) {
+      hipLaunchKernelGGL(gain_solve_ant_kernel<T>, dim3(nants * cblocks), dim3(256), 0, stream, a.model_r, a.model_i, q_rows, gains.as<T2>(),
+                         gs_ptr.as<int>(), gs_ent.as<int2>(), nants, nfreqs, fpad, gs_out.as<double>());
+      HIP_TRY(hipGetLastError());
+      if (comm_on()) CAL_TRY(all_reduce(gs_out.p, 3 * nant_out, CAL_XCHG_F64, CAL_XCHG_SUM));
+      HIP_TRY(hipMemsetAsync(gbs_cnt.p, 0, 2 * sizeof(int), stream));
+      for (int a0 = 0; a0 < nants; a0 += rows_per_chunk) {
+        const int nr = std::min(rows_per_chunk, nants - a0);
+        hipLaunchKernelGGL(gain_basis_gram_kernel<T>, dim3((unsigned)nr * npairs), dim3(256), 0, stream, gb_Bt.as<T>(), gs_out.as<double>(), gains.as<T2>(),
+                           gbs_n.as<T>(), gbs_rhs.as<T>(), mask, na_slice, a0, npairs, K, gb_kpad, nants, nfreqs, fpad);
+        hipLaunchKernelGGL(gain_basis_chol_kernel<T>, dim3(nr), dim3(256), chol_lds, stream, gbs_n.as<T>(), gbs_rhs.as<T>(), gbs_d.as<double>(),
+                           gb_y.as<T2>(), mask, na_slice, a0, K, gb_kpad, d->damping, d->ridge, gbs_cnt.as<int>(), kCsLdsDoubles);
+        HIP_TRY(hipGetLastError());
+      }
+      // gains = g0 + B y for the selected slices (runs of neighbouring slices in one launch each): the others keep their bits
+      constexpr int per = 256 * (16 / (int)sizeof(T));  // channels per block of gain_expand_kernel
+      for (int t = 0; t < nslices;) {
+        if (d->slice_mask && !d->slice_mask[t]) {
+          ++t;
+          continue;
+        }
+        int t1 = t + 1;
+        while (t1 < nslices && (!d->slice_mask || d->slice_mask[t1])) ++t1;
+        const size_t r0 = (size_t)t * na_slice;
+        hipLaunchKernelGGL((gain_expand_kernel<T>), dim3((fpad + per - 1) / per, (t1 - t) * na_slice), dim3(256), 0, stream, gb_g0.as<T2>() + r0 * fpad,
+                           gb_Bt.as<T>(), gb_y.as<T2>() + r0 * gb_kpad, gains.as<T2>() + r0 * fpad, fpad, gb_kpad);
+        t = t1;
+      }
+      HIP_TRY(hipGetLastError());
+    }
+    int counts[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(counts, gbs_cnt.p, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
+    if (d->reset_gain_moments) {
+      // what set_optimizer leaves in the y slots, for the selected slices (runs of neighbouring slices in one call each)
+      const bool acc = (opt.optimizer == CAL_OPT_ADAGRAD || opt.optimizer == CAL_OPT_FTRL) && opt.initial_accumulator_value != 0.0;
+      const size_t per = (size_t)na_slice * gb_kpad * 2;  // reals per slice
+      for (int t = 0; t < nslices;) {
+        if (d->slice_mask && !d->slice_mask[t]) {
+          ++t;
+          continue;
+        }
+        int t1 = t + 1;
+        while (t1 < nslices && (!d->slice_mask || d->slice_mask[t1])) ++t1;
+        const size_t off = (size_t)t * per, n = (size_t)(t1 - t) * per;
+        HIP_TRY(hipMemsetAsync(gb_ym.as<T>() + off, 0, n * sizeof(T), stream));
+        if (acc)
+          hipLaunchKernelGGL(fill_kernel<T>, dim3(grid_for((long long)n)), dim3(256), 0, stream, gb_yv.as<T>() + off, (long long)n,
+                             (T)opt.initial_accumulator_value);
+        else
+          HIP_TRY(hipMemsetAsync(gb_yv.as<T>() + off, 0, n * sizeof(T), stream));
+        t = t1;
+      }
+      HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (res) {
+      res->nsolved = counts[0];
+      res->nsingular = counts[1];
+    }
+    return CAL_OK;
+  }
+
   int init_coeffs(const void* sr, const void* si) override {
     HIP_TRY(hipSetDevice(device));
     if (!has_problem || !has_data) return fail(CAL_ERR_STATE, "init_coeffs: problem and data (weights) must be set");
@@ -2071,7 +2225,7 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     if (!b) return fail(CAL_ERR_INVALID, "memory_bytes: null");
     const DevBuf* all[] = {&tiles, &bl_tile, &bl_ant, &items, &ant_ptr, &ant_ent, &coef_grp, &grp_coff, &grp_item_ptr, &item_goff,
                            &data_r, &data_i, &wgts, &gains, &gains_alt, &gains_m, &gains_v, &gains_snap, &coef, &coef_m, &coef_v, &coef_snap,
-                           &q0, &q1, &comm, &scal, &gcp0, &gcp1, &gc0, &gc1, &part, &state, &losses, &scratch, &model_buf, &fq_out, &fq_gains, &gs_out, &gs_ptr, &gs_ent, &gs_mask, &cs_grp, &cs_order, &cs_work, &cs_n, &cs_d, &cs_rhs, &cs_cnt,
+                           &q0, &q1, &comm, &scal, &gcp0, &gcp1, &gc0, &gc1, &part, &state, &losses, &scratch, &model_buf, &fq_out, &fq_gains, &gs_out, &gs_ptr, &gs_ent, &gs_mask, &cs_grp, &cs_order, &cs_work, &cs_n, &cs_d, &cs_rhs, &cs_cnt, &gbs_n, &gbs_d, &gbs_rhs, &gbs_cnt,
                            &mf_ops, &mf_panels, &mf_map, &members, &heads, &lamb_vars, &lamb_cvar_ptr, &lamb_partial, &lamb_ratio, &lamb_glob, &lamb_slot, &slice_coff, &slice_ipart_ptr, &slice_ipart_idx,
                            &slice_ppart_ptr, &slice_ppart_idx, &slice_cblk, &gb_B, &gb_Bt, &gb_g0, &gb_y, &gb_ym, &gb_yv, &gb_ysnap, &gb_proj, &tb_B, &tb_Bt, &tb_z, &tb_pf};
     int64_t n = 0;
@@ -2425,6 +2579,11 @@ int cal_solver_solve_gains(cal_solver* s, const cal_gain_solve_desc* desc) { NEE
 int cal_solver_hold_slices(cal_solver* s, const uint8_t* mask) { NEED(s); return s->hold_slices(mask); }
 int cal_solver_solve_coeffs(cal_solver* s, const cal_coeff_solve_desc* desc, cal_coeff_solve_result* result) { NEED(s); return s->solve_coeffs(desc, result); }
 int cal_solver_set_coeff_solve_scratch(cal_solver* s, int64_t bytes) { NEED(s); return s->set_coeff_solve_scratch(bytes); }
+int cal_solver_get_gain_coeff_moments(cal_solver* s, void* ym_r, void* ym_i, void* yv_r, void* yv_i, void* cm_r, void* cm_i, void* cv_r, void* cv_i, int64_t* t) {
+  NEED(s);
+  return s->get_gain_coeff_moments(ym_r, ym_i, yv_r, yv_i, cm_r, cm_i, cv_r, cv_i, t);
+}
+int cal_solver_solve_gain_coeffs(cal_solver* s, const cal_gain_coeff_solve_desc* desc, cal_gain_coeff_solve_result* result) { NEED(s); return s->solve_gain_coeffs(desc, result); }
 int cal_solver_fit_quality(cal_solver* s, const void* g_r, const void* g_i, double* chisq_ant, double* wsum_ant, double* chisq_bl, double* wsum_bl) {
   NEED(s);
   return s->fit_quality(g_r, g_i, chisq_ant, wsum_ant, chisq_bl, wsum_bl);

@@ -217,6 +217,16 @@ class HipFitSolver:
         _lib.check(self._lib.cal_solver_get_gain_coeffs(self._h, int(which), _ptr(y_r), _ptr(y_i)))
         return y_r, y_i
 
+    def get_gain_coeff_moments(self):
+        """The optimizer's slots of a fit with a gain basis, read only (``get_moments`` / ``set_moments`` stay refused there):
+        ``ym_*``, ``yv_*`` in the shape of ``get_gain_coeffs``, ``cm_*``, ``cv_*`` ``[ncoeffs]`` and ``t`` ``[nslices]``, every slice's own
+        count of applied updates."""
+        y = [np.empty(self._gain_coeff_shape(), dtype=self.dtype) for _ in range(4)]
+        c = [np.empty(self.ncoeffs, dtype=self.dtype) for _ in range(4)]
+        t = np.zeros(self.nslices, dtype=np.int64)
+        _lib.check(self._lib.cal_solver_get_gain_coeff_moments(self._h, *[_ptr(a) for a in y + c], t.ctypes.data_as(C.POINTER(C.c_int64))))
+        return dict(ym_r=y[0], ym_i=y[1], yv_r=y[2], yv_i=y[3], cm_r=c[0], cm_i=c[1], cv_r=c[2], cv_i=c[3], t=t)
+
     def eval_gain_coeff_grads(self):
         """Loss and its gradient with respect to ``y``: ``grad g @ B`` (contracted with ``Bt`` over the times while a time basis is
         set), ``(loss, gy_r, gy_i)`` in the shape of ``get_gain_coeffs``."""
@@ -349,6 +359,31 @@ class HipFitSolver:
     def _set_coeff_solve_scratch(self, nbytes):
         """Scratch bound of ``solve_coeffs`` in bytes (0: the default); the results do not depend on it (tests)."""
         _lib.check(self._lib.cal_solver_set_coeff_solve_scratch(self._h, int(nbytes)))
+
+    def solve_gain_coeffs(self, nsweeps, damping=0.5, ridge=1e-6, slice_mask=None, reset_gain_moments=False):
+        """``nsweeps`` damped StefCal sweeps projected on the frequency gain basis ``g = g0 + B y`` (cal_solver_solve_gain_coeffs),
+        with the foreground model held fixed.  ``num``, ``den`` are ``solve_gains``' per-antenna sums from the OLD gains; for antenna
+        row ``a`` (one antenna of one slice), ``g_a`` the current expanded gains and ``B [nfreqs, K]`` the attached basis::
+
+            r_a[f]  = num_a[f] - den_a[f] g_a[f]                 (complex; minus half the chi-square gradient w.r.t. g_a)
+            N_a     = B^T diag(den_a) B                          [K][K], real symmetric
+            rhs_a   = B^T r_a                                    [K], complex
+            (N_a + ridge (tr N_a / K) I) delta_a = rhs_a         (one factorisation, two right-hand sides: re, im)
+            y_a    <- y_a + damping delta_a                      then gains = g0 + B y for the whole array
+
+        ``N_a`` and ``rhs_a`` are formed in the solver's dtype on the matrix cores, the Cholesky solve and the update run in float64.
+        ``B = I``, ``ridge = 0`` is ``solve_gains``' update; a channel with ``den = 0`` of a non-singular antenna does move (the basis
+        interpolates across it).  The sweeps minimise the chi-square term only (not the "sum" regulariser).  ``slice_mask``:
+        ``[nslices]``, the slices to solve (``None``: all); the others keep ``y`` and gains bit for bit.  ``reset_gain_moments``: the
+        optimizer's ``y`` slots of the solved slices start over as after ``set_optimizer``.  Needs a frequency gain basis
+        (``set_gain_basis``) and refuses a time gain basis.  Under an exchange every sweep sums three ``[nants, nfreqs]`` float64
+        planes over the ranks, and every rank applies the same update.  Returns ``{"nsolved", "nsingular"}``, the antenna rows of the
+        last sweep: a singular row (no unflagged cross-correlation, or a non-positive pivot) keeps its ``y``."""
+        m = self._slice_mask(slice_mask)
+        d = _lib.GainCoeffSolveDesc(int(nsweeps), int(bool(reset_gain_moments)), float(damping), float(ridge), None if m is None else m.ctypes.data)
+        r = _lib.GainCoeffSolveResult()
+        _lib.check(self._lib.cal_solver_solve_gain_coeffs(self._h, C.byref(d), C.byref(r)))
+        return {"nsolved": int(r.nsolved), "nsingular": int(r.nsingular)}
 
     def hold_slices(self, mask=None):
         """Slices that enter every later ``run`` / ``run_slices`` as already stopped (``[nslices]``, nonzero = held; ``None``: no

@@ -310,7 +310,7 @@ int cal_solver_fit_quality(cal_solver* s, const void* g_r, const void* g_i, doub
  *   them to (stale momentum after a jump in the gains is harmful); iteration counts and the coefficient slots stay.  Needs an
  *   optimizer (CAL_ERR_STATE).
  * With a frequency or time gain basis attached the call fails with CAL_ERR_UNSUPPORTED (projecting the solved gains onto a basis is
- * not implemented).  Works for every layout and kernel path, fitting groups of several baselines, bl_alias and nslices > 1: it runs
+ * not implemented here; cal_solver_solve_gain_coeffs solves the coefficients of a frequency basis).  Works for every layout and kernel path, fitting groups of several baselines, bl_alias and nslices > 1: it runs
  * the model pass of cal_solver_model once, then one pass over (b, f) for P and Q, then per sweep one walk of the antennas' baseline
  * lists.  Like cal_solver_fit_quality it puts the loop state back: a run continued after a call with an all-zero mask is
  * bit-identical to one without the call.  Under a communicator or exchange hook every sweep sums num_r | num_i | den over the ranks in
@@ -376,6 +376,55 @@ int cal_solver_solve_coeffs(cal_solver* s, const cal_coeff_solve_desc* desc, cal
 /* The scratch bound of cal_solver_solve_coeffs in bytes (0: the default, 256 MiB).  The coefficients do not depend on it: tests use
  * it to send a small problem through several chunks. */
 int cal_solver_set_coeff_solve_scratch(cal_solver* s, int64_t bytes);
+/* The coefficients of a frequency gain basis in closed form (no counterpart in the reference): the damped StefCal sweeps of
+ * cal_solver_solve_gains projected on the basis g = g0 + B y of cal_solver_set_gain_basis.  With the other antennas held fixed the
+ * chi-square is quadratic in one antenna's y.  num, den are exactly cal_solver_solve_gains': the model pass, then P, Q, then the
+ * per-antenna sums from the OLD gains, autocorrelations left out.  For antenna row a (one antenna of one slice), g_a the solver's
+ * current expanded gains, B [nfreqs][K] the attached basis:
+ *   r_a[f]  = num_a[f] - den_a[f] g_a[f]                 (complex; minus half the chi-square gradient w.r.t. g_a)
+ *   N_a     = B^T diag(den_a) B                          [K][K], real symmetric
+ *   rhs_a   = B^T r_a                                    [K], complex
+ *   (N_a + ridge (tr N_a / K) I) delta_a = rhs_a         (one factorisation, two right-hand sides: re, im)
+ *   y_a    <- y_a + damping delta_a                      then gains = g0 + B y for the whole array
+ * Every antenna is solved from the old gains (a Jacobi sweep); the gains are rebuilt once per sweep, after every row has been solved.
+ * B = I, ridge = 0 is the update of cal_solver_solve_gains; damping = 1, ridge = 0 lands on the exact per-antenna minimiser.  Unlike
+ * the per-channel sweep a channel with den = 0 of a non-singular antenna does move: the basis interpolates across it.  The sweeps
+ * minimise the chi-square term alone: the "sum" regulariser is not part of them.
+ * Precision: r_a is evaluated in double from the double num / den planes and rounded to the solver's dtype once; N_a and rhs_a are
+ * formed and accumulated in the solver's dtype in a fixed order (v_mfma_f32_16x16x4_f32 / v_mfma_f64_16x16x4_f64; no atomics on reals:
+ * two calls give the same bits); the Cholesky factorisation, both substitutions and the update of y run in double for both dtypes,
+ * and the update is rounded once.
+ * A row is singular when tr N_a <= 0 (no unflagged cross-correlation) or a pivot is <= 0 or not finite: it keeps the bits of its y and
+ * counts in nsingular.  result (may be NULL) counts the antenna rows of the LAST sweep; rows of unselected slices count in neither
+ * field.  Suggested values: damping = 0.5, ridge = 1e-6.
+ *   nsweeps >= 1, 0 < damping <= 1, ridge >= 0 and finite (CAL_ERR_INVALID otherwise); problem, data, coefficients, gains and a
+ *   frequency gain basis must be set, and reset_gain_moments needs an optimizer (CAL_ERR_STATE).  With a gain TIME basis attached the
+ *   call returns CAL_ERR_UNSUPPORTED: its variables couple the times of an antenna, a joint (l, k) system that is a different solve.
+ *   slice_mask: [nslices] bytes or NULL (all slices): the y rows and the gains of a slice whose byte is 0 keep their bits.
+ *   reset_gain_moments = 1: the optimizer's y slots of the selected slices go back to what cal_solver_set_optimizer initialises them
+ *   to (Adagrad's / Ftrl's initial_accumulator_value included).
+ * g0, the y snapshot of use_min, coefficients, their slots, t and iteration counts are never touched.  Works for every K the basis
+ * setter accepts, every layout and kernel path, fitting groups of several baselines, bl_alias and nslices > 1 (it reuses the model
+ * pass).  The antenna rows are worked through in chunks whose scratch (N_a in the solver's dtype, plus its factor in double where
+ * (K + 2) rows do not fit LDS) stays under the bound of cal_solver_set_coeff_solve_scratch; every chunk of a sweep reads the old gains.
+ * Like cal_solver_solve_gains it puts the loop state back (a run continued after a call with an all-zero mask is bit-identical to one
+ * without the call) and issues ONE all-reduce of 3 nants nfreqs doubles per sweep under a communicator or exchange hook: y is
+ * replicated, so every rank then computes the same update, bit for bit. */
+typedef struct cal_gain_coeff_solve_desc {
+  int32_t nsweeps;              /* >= 1 */
+  int32_t reset_gain_moments;
+  double damping;               /* (0, 1] */
+  double ridge;                 /* >= 0 */
+  const uint8_t* slice_mask;    /* [nslices] or NULL */
+} cal_gain_coeff_solve_desc;
+typedef struct cal_gain_coeff_solve_result { int32_t nsolved; int32_t nsingular; } cal_gain_coeff_solve_result; /* antenna rows of the last sweep */
+int cal_solver_solve_gain_coeffs(cal_solver* s, const cal_gain_coeff_solve_desc* desc, cal_gain_coeff_solve_result* result);
+/* The optimizer's slots of a fit with a gain basis, read only (cal_solver_get_moments / cal_solver_set_moments stay refused there:
+ * this is no checkpoint): ym_*, yv_* the first and second slot of y in the shape of cal_solver_get_gain_coeffs, cm_*, cv_* those of
+ * the coefficients [ncoeffs], t [nslices] every slice's own count of applied updates.  Any pointer may be NULL.  CAL_ERR_STATE without
+ * a gain basis or without an optimizer. */
+int cal_solver_get_gain_coeff_moments(cal_solver* s, void* ym_r, void* ym_i, void* yv_r, void* yv_i, void* cm_r, void* cm_i, void* cv_r,
+                                      void* cv_i, int64_t* t);
 /* tensorize_fg_coeffs, calibration.py:828-913: per group least squares of src on the basis with samples of zero
  * weight zeroed; the result becomes the current coefficients.  src_*: [nbls][nfreqs] real. */
 int cal_solver_init_coeffs(cal_solver* s, const void* src_r, const void* src_i);
