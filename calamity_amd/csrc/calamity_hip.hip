@@ -1717,17 +1717,80 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     return CAL_OK;
   }
 
+  // ---- what fit_quality and the closed-form solves share --------------------------------------------------------------
+  int require_set(const char* who, bool need_gains) {
+    if (!has_problem) return fail(CAL_ERR_STATE, "%s: no problem set (cal_solver_set_problem)", who);
+    if (!has_data) return fail(CAL_ERR_STATE, "%s: no data set (cal_solver_set_data)", who);
+    if (!has_coef) return fail(CAL_ERR_STATE, "%s: the coefficients must be set (cal_solver_set_params)", who);
+    if (need_gains && !has_gains) return fail(CAL_ERR_STATE, "%s: the gains must be set (cal_solver_set_params)", who);
+    return CAL_OK;
+  }
+  int check_damping_ridge(const char* who, double damping, const double* ridge) {
+    if (!(damping > 0.0 && damping <= 1.0)) return fail(CAL_ERR_INVALID, "%s: damping = %g lies outside (0, 1]", who, damping);
+    if (ridge && (!(*ridge >= 0.0) || !std::isfinite(*ridge))) return fail(CAL_ERR_INVALID, "%s: ridge = %g must be finite and >= 0", who, *ridge);
+    return CAL_OK;
+  }
+  // The model pass of model() into model_buf ([planes][nbls][fpad]), then rows(model_r, model_i, q_rows) launches what turns the planes
+  // into the call's own rows (q_rows: the third plane, null when two are asked for).  The host mirror of the loop state is put back and
+  // pushed again afterwards: the pass clears the slices' stop flags for itself.
+  template <typename Rows>
+  int model_pass(int planes, Rows rows) {
+    const size_t plane = (size_t)nbls * fpad;
+    if (model_buf.bytes < planes * plane * sizeof(T)) CAL_TRY(model_buf.alloc(planes * plane * sizeof(T)));
+    const std::vector<DevState> saved(h_state, h_state + nslices);
+    begin_pass_state();
+    CAL_TRY(push_state());
+    FusedArgs<T> a = fused_args();
+    a.model_r = model_buf.as<T>();
+    a.model_i = model_buf.as<T>() + plane;
+    launch_fused<MODE_MODEL>(a, false);
+    rows(a.model_r, a.model_i, planes == 3 ? model_buf.as<T>() + 2 * plane : nullptr);
+    HIP_TRY(hipGetLastError());
+    std::copy(saved.begin(), saved.end(), h_state);
+    CAL_TRY(push_state());
+    return CAL_OK;
+  }
+  // a call's slice mask on the device (gs_mask); *dev is null where the call has none
+  int upload_slice_mask(const uint8_t* host, const unsigned char** dev) {
+    *dev = nullptr;
+    if (!host) return CAL_OK;
+    if (gs_mask.bytes < (size_t)nslices) CAL_TRY(gs_mask.alloc((size_t)nslices, false));
+    HIP_TRY(copy_sync(gs_mask.p, host, (size_t)nslices, hipMemcpyHostToDevice));
+    *dev = gs_mask.as<unsigned char>();
+    return CAL_OK;
+  }
+  // fn(t, t1) for every run [t, t1) of neighbouring selected slices (no mask: one run of all)
+  template <typename Fn>
+  int for_selected_slice_runs(const uint8_t* mask, Fn fn) {
+    for (int t = 0; t < nslices;) {
+      if (mask && !mask[t]) {
+        ++t;
+        continue;
+      }
+      int t1 = t + 1;
+      while (t1 < nslices && (!mask || mask[t1])) ++t1;
+      CAL_TRY(fn(t, t1));
+      t = t1;
+    }
+    return CAL_OK;
+  }
+  // what set_optimizer leaves in n reals of the moment slots m and v from element off on
+  int reset_moment_slots(DevBuf& m, DevBuf& v, size_t off, size_t n) {
+    HIP_TRY(hipMemsetAsync(m.as<T>() + off, 0, n * sizeof(T), stream));
+    if ((opt.optimizer == CAL_OPT_ADAGRAD || opt.optimizer == CAL_OPT_FTRL) && opt.initial_accumulator_value != 0.0)
+      hipLaunchKernelGGL(fill_kernel<T>, dim3(grid_for((long long)n)), dim3(256), 0, stream, v.as<T>() + off, (long long)n,
+                         (T)opt.initial_accumulator_value);
+    else
+      HIP_TRY(hipMemsetAsync(v.as<T>() + off, 0, n * sizeof(T), stream));
+    return CAL_OK;
+  }
+
   // cal_solver_fit_quality: the model pass of model(), then quality_rows_kernel and quality_ant_kernel (fit_quality_kernels.hpp).
-  // The host mirror of the loop state is put back and pushed again afterwards: the pass clears the slices' stop flags for itself.
   int fit_quality(const void* g_r, const void* g_i, double* chisq_ant, double* wsum_ant, double* chisq_bl, double* wsum_bl) override {
     HIP_TRY(hipSetDevice(device));
-    if (!has_problem) return fail(CAL_ERR_STATE, "fit_quality: no problem set (cal_solver_set_problem)");
-    if (!has_data) return fail(CAL_ERR_STATE, "fit_quality: no data set (cal_solver_set_data)");
-    if (!has_coef) return fail(CAL_ERR_STATE, "fit_quality: the coefficients must be set (cal_solver_set_params)");
+    CAL_TRY(require_set("fit_quality", false));
     if ((g_r == nullptr) != (g_i == nullptr)) return fail(CAL_ERR_INVALID, "fit_quality: give both g_r and g_i, or neither");
     if (!g_r && !has_gains) return fail(CAL_ERR_STATE, "fit_quality: the gains must be set (cal_solver_set_params) or given");
-    const size_t rowbytes = (size_t)nbls * fpad * sizeof(T);
-    if (model_buf.bytes < 2 * rowbytes) CAL_TRY(model_buf.alloc(2 * rowbytes));
     const size_t nant_out = (size_t)nants * nfreqs;
     const size_t out_bytes = (2 * nant_out + 2 * (size_t)nbls) * sizeof(double);
     if (fq_out.bytes < out_bytes) CAL_TRY(fq_out.alloc(out_bytes));
@@ -1739,26 +1802,18 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
       CAL_TRY(upload_rows(g_i, fq_gains.as<T>(), nants, 2, 1));
       g = fq_gains.as<T2>();
     }
-    const std::vector<DevState> saved(h_state, h_state + nslices);
-    begin_pass_state();
-    CAL_TRY(push_state());
-    FusedArgs<T> a = fused_args();
-    a.model_r = model_buf.as<T>();
-    a.model_i = model_buf.as<T>() + (size_t)nbls * fpad;
-    launch_fused<MODE_MODEL>(a, false);
     double* o_ca = fq_out.as<double>();
     double* o_wa = o_ca + nant_out;
     double* o_cb = o_wa + nant_out;
     double* o_wb = o_cb + nbls;
-    hipLaunchKernelGGL(quality_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, a.model_r, a.model_i, data_r.as<T>(), data_i.as<T>(),
-                       wgts.as<T>(), g, bl_ant.as<int2>(), nbls, nfreqs, fpad, o_cb, o_wb);
-    constexpr int V = 16 / (int)sizeof(T);
-    const int cblocks = (fpad + 64 * V - 1) / (64 * V);
-    hipLaunchKernelGGL(quality_ant_kernel<T>, dim3(nants * cblocks), dim3(256), 0, stream, a.model_r, wgts.as<T>(), ant_ptr.as<int>(),
-                       ant_ent.as<int2>(), nants, nfreqs, fpad, o_ca, o_wa);
-    HIP_TRY(hipGetLastError());
-    std::copy(saved.begin(), saved.end(), h_state);
-    CAL_TRY(push_state());
+    CAL_TRY(model_pass(2, [&](T* model_r, T* model_i, T*) {
+      hipLaunchKernelGGL(quality_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, model_r, model_i, data_r.as<T>(), data_i.as<T>(),
+                         wgts.as<T>(), g, bl_ant.as<int2>(), nbls, nfreqs, fpad, o_cb, o_wb);
+      constexpr int V = 16 / (int)sizeof(T);
+      const int cblocks = (fpad + 64 * V - 1) / (64 * V);
+      hipLaunchKernelGGL(quality_ant_kernel<T>, dim3(nants * cblocks), dim3(256), 0, stream, model_r, wgts.as<T>(), ant_ptr.as<int>(),
+                         ant_ent.as<int2>(), nants, nfreqs, fpad, o_ca, o_wa);
+    }));
     // the antenna planes of every rank's baselines add up to the array's: ONE all-reduce of 2 nants nfreqs doubles
     if (comm_on()) CAL_TRY(all_reduce(o_ca, 2 * nant_out, CAL_XCHG_F64, CAL_XCHG_SUM));
     if (chisq_ant) HIP_TRY(hipMemcpyAsync(chisq_ant, o_ca, nant_out * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -1809,50 +1864,33 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
   }
 
   // cal_solver_solve_gains: the model pass of model(), gain_solve_rows_kernel once, then per sweep gain_solve_ant_kernel, the exchange of
-  // its three planes and gain_solve_apply_kernel (gain_solve_kernels.hpp).  Like fit_quality, the host mirror of the loop state is put
-  // back and pushed again afterwards: the pass clears the slices' stop flags for itself.
+  // its three planes and gain_solve_apply_kernel (gain_solve_kernels.hpp).
   int solve_gains(const cal_gain_solve_desc* d) override {
     HIP_TRY(hipSetDevice(device));
     if (!d) return fail(CAL_ERR_INVALID, "solve_gains: null description");
-    if (!has_problem) return fail(CAL_ERR_STATE, "solve_gains: no problem set (cal_solver_set_problem)");
-    if (!has_data) return fail(CAL_ERR_STATE, "solve_gains: no data set (cal_solver_set_data)");
-    if (!has_coef) return fail(CAL_ERR_STATE, "solve_gains: the coefficients must be set (cal_solver_set_params)");
-    if (!has_gains) return fail(CAL_ERR_STATE, "solve_gains: the gains must be set (cal_solver_set_params)");
+    CAL_TRY(require_set("solve_gains", true));
     if (d->nsweeps < 1) return fail(CAL_ERR_INVALID, "solve_gains: nsweeps = %d, at least one sweep", d->nsweeps);
-    if (!(d->damping > 0.0 && d->damping <= 1.0)) return fail(CAL_ERR_INVALID, "solve_gains: damping = %g lies outside (0, 1]", d->damping);
+    CAL_TRY(check_damping_ridge("solve_gains", d->damping, nullptr));
     if (yb_on())
       return fail(CAL_ERR_UNSUPPORTED, "solve_gains: a gain basis is set (cal_solver_set_gain_basis, cal_solver_set_gain_time_basis): the closed form solves "
                   "free per-channel gains, and projecting them onto a basis is not implemented here; cal_solver_solve_gain_coeffs solves the coefficients of a "
                   "frequency basis, or detach the basis (nvec = 0) first");
     if (d->reset_gain_moments && !has_opt) return fail(CAL_ERR_STATE, "solve_gains: reset_gain_moments without an optimizer (cal_solver_set_optimizer)");
     CAL_TRY(build_solve_lists());
-    const size_t rowbytes = (size_t)nbls * fpad * sizeof(T);
-    if (model_buf.bytes < 3 * rowbytes) CAL_TRY(model_buf.alloc(3 * rowbytes));
     const size_t nant_out = (size_t)nants * nfreqs;
     if (gs_out.bytes < 3 * nant_out * sizeof(double)) CAL_TRY(gs_out.alloc(3 * nant_out * sizeof(double)));
     const unsigned char* mask = nullptr;
-    if (d->slice_mask) {
-      if (gs_mask.bytes < (size_t)nslices) CAL_TRY(gs_mask.alloc((size_t)nslices, false));
-      HIP_TRY(copy_sync(gs_mask.p, d->slice_mask, (size_t)nslices, hipMemcpyHostToDevice));
-      mask = gs_mask.as<unsigned char>();
-    }
-    const std::vector<DevState> saved(h_state, h_state + nslices);
-    begin_pass_state();
-    CAL_TRY(push_state());
-    FusedArgs<T> a = fused_args();
-    a.model_r = model_buf.as<T>();
-    a.model_i = model_buf.as<T>() + (size_t)nbls * fpad;
-    T* q_rows = model_buf.as<T>() + 2 * (size_t)nbls * fpad;
-    launch_fused<MODE_MODEL>(a, false);
-    hipLaunchKernelGGL(gain_solve_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, a.model_r, a.model_i, q_rows, data_r.as<T>(),
-                       data_i.as<T>(), wgts.as<T>(), bl_ant.as<int2>(), nbls, nfreqs, fpad);
-    HIP_TRY(hipGetLastError());
-    std::copy(saved.begin(), saved.end(), h_state);
-    CAL_TRY(push_state());
+    CAL_TRY(upload_slice_mask(d->slice_mask, &mask));
+    T *u_r = nullptr, *u_i = nullptr, *q_rows = nullptr;
+    CAL_TRY(model_pass(3, [&](T* model_r, T* model_i, T* third) {
+      u_r = model_r, u_i = model_i, q_rows = third;
+      hipLaunchKernelGGL(gain_solve_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, u_r, u_i, q_rows, data_r.as<T>(), data_i.as<T>(),
+                         wgts.as<T>(), bl_ant.as<int2>(), nbls, nfreqs, fpad);
+    }));
     constexpr int V = 16 / (int)sizeof(T);
     const int cblocks = (fpad + 64 * V - 1) / (64 * V);
     for (int k = 0; k < d->nsweeps; ++k) {
-      hipLaunchKernelGGL(gain_solve_ant_kernel<T>, dim3(nants * cblocks), dim3(256), 0, stream, a.model_r, a.model_i, q_rows, gains.as<T2>(),
+      hipLaunchKernelGGL(gain_solve_ant_kernel<T>, dim3(nants * cblocks), dim3(256), 0, stream, u_r, u_i, q_rows, gains.as<T2>(),
                          gs_ptr.as<int>(), gs_ent.as<int2>(), nants, nfreqs, fpad, gs_out.as<double>());
       HIP_TRY(hipGetLastError());
       // the planes of every rank's baselines add up to the array's: ONE all-reduce of 3 nants nfreqs doubles per sweep
@@ -1863,24 +1901,8 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     }
     if (d->reset_gain_moments) {
       // what set_optimizer leaves in the gain slots, for the selected slices (runs of neighbouring slices in one call each)
-      const bool acc = (opt.optimizer == CAL_OPT_ADAGRAD || opt.optimizer == CAL_OPT_FTRL) && opt.initial_accumulator_value != 0.0;
       const size_t per = (size_t)na_slice * fpad * 2;  // reals per slice
-      for (int t = 0; t < nslices;) {
-        if (d->slice_mask && !d->slice_mask[t]) {
-          ++t;
-          continue;
-        }
-        int t1 = t + 1;
-        while (t1 < nslices && (!d->slice_mask || d->slice_mask[t1])) ++t1;
-        const size_t off = (size_t)t * per, n = (size_t)(t1 - t) * per;
-        HIP_TRY(hipMemsetAsync(gains_m.as<T>() + off, 0, n * sizeof(T), stream));
-        if (acc)
-          hipLaunchKernelGGL(fill_kernel<T>, dim3(grid_for((long long)n)), dim3(256), 0, stream, gains_v.as<T>() + off, (long long)n,
-                             (T)opt.initial_accumulator_value);
-        else
-          HIP_TRY(hipMemsetAsync(gains_v.as<T>() + off, 0, n * sizeof(T), stream));
-        t = t1;
-      }
+      CAL_TRY(for_selected_slice_runs(d->slice_mask, [&](int t, int t1) { return reset_moment_slots(gains_m, gains_v, (size_t)t * per, (size_t)(t1 - t) * per); }));
       HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipStreamSynchronize(stream));
@@ -1928,7 +1950,7 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
         noff += nn;
         doff += dd;
         max_nvec = std::max(max_nvec, g.nvec);
-        const int nb = (g.nvec + kCsBlock - 1) / kCsBlock;
+        const int nb = (g.nvec + kNsBlock - 1) / kNsBlock;
         for (int bi = 0; bi < nb; ++bi)
           for (int bj = 0; bj <= bi; ++bj) work.push_back(CsWork{order[p], bi, bj, 0});
       }
@@ -1956,48 +1978,30 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
   }
 
   // cal_solver_solve_coeffs: per iteration the model pass of model(), coeff_solve_rows_kernel, then per chunk of groups
-  // coeff_gram_kernel and coeff_chol_kernel (coeff_solve_kernels.hpp).  Like fit_quality and solve_gains the host mirror of the loop
-  // state is put back and pushed again behind the model pass.  Every group is owned by one rank: no exchange.
+  // coeff_gram_kernel and coeff_chol_kernel (coeff_solve_kernels.hpp).  Every group is owned by one rank: no exchange.
   int solve_coeffs(const cal_coeff_solve_desc* d, cal_coeff_solve_result* res) override {
     HIP_TRY(hipSetDevice(device));
     if (!d) return fail(CAL_ERR_INVALID, "solve_coeffs: null description");
-    if (!has_problem) return fail(CAL_ERR_STATE, "solve_coeffs: no problem set (cal_solver_set_problem)");
-    if (!has_data) return fail(CAL_ERR_STATE, "solve_coeffs: no data set (cal_solver_set_data)");
-    if (!has_coef) return fail(CAL_ERR_STATE, "solve_coeffs: the coefficients must be set (cal_solver_set_params)");
-    if (!has_gains) return fail(CAL_ERR_STATE, "solve_coeffs: the gains must be set (cal_solver_set_params)");
+    CAL_TRY(require_set("solve_coeffs", true));
     if (d->niters < 1) return fail(CAL_ERR_INVALID, "solve_coeffs: niters = %d, at least one iteration", d->niters);
-    if (!(d->damping > 0.0 && d->damping <= 1.0)) return fail(CAL_ERR_INVALID, "solve_coeffs: damping = %g lies outside (0, 1]", d->damping);
-    if (!(d->ridge >= 0.0) || !std::isfinite(d->ridge)) return fail(CAL_ERR_INVALID, "solve_coeffs: ridge = %g must be finite and >= 0", d->ridge);
+    CAL_TRY(check_damping_ridge("solve_coeffs", d->damping, &d->ridge));
     if (d->reset_coeff_moments && !has_opt) return fail(CAL_ERR_STATE, "solve_coeffs: reset_coeff_moments without an optimizer (cal_solver_set_optimizer)");
     CAL_TRY(build_coeff_solve_plan());
-    const size_t rowbytes = (size_t)nbls * fpad * sizeof(T);
-    if (model_buf.bytes < 3 * rowbytes) CAL_TRY(model_buf.alloc(3 * rowbytes));
     if (cs_rhs.bytes < 2 * (size_t)ncoef * sizeof(T)) CAL_TRY(cs_rhs.alloc(2 * (size_t)ncoef * sizeof(T)));
     const unsigned char* mask = nullptr;
-    if (d->slice_mask) {
-      if (gs_mask.bytes < (size_t)nslices) CAL_TRY(gs_mask.alloc((size_t)nslices, false));
-      HIP_TRY(copy_sync(gs_mask.p, d->slice_mask, (size_t)nslices, hipMemcpyHostToDevice));
-      mask = gs_mask.as<unsigned char>();
-    }
+    CAL_TRY(upload_slice_mask(d->slice_mask, &mask));
     int counts[2] = {0, 0};
     for (int it = 0; it < d->niters; ++it) {
-      const std::vector<DevState> saved(h_state, h_state + nslices);
-      begin_pass_state();
-      CAL_TRY(push_state());
-      FusedArgs<T> a = fused_args();
-      a.model_r = model_buf.as<T>();
-      a.model_i = model_buf.as<T>() + (size_t)nbls * fpad;
-      T* q_rows = model_buf.as<T>() + 2 * (size_t)nbls * fpad;
-      launch_fused<MODE_MODEL>(a, false);
-      hipLaunchKernelGGL(coeff_solve_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, a.model_r, a.model_i, q_rows, data_r.as<T>(),
-                         data_i.as<T>(), wgts.as<T>(), gains.as<T2>(), bl_ant.as<int2>(), nbls, nfreqs, fpad);
-      HIP_TRY(hipGetLastError());
-      std::copy(saved.begin(), saved.end(), h_state);
-      CAL_TRY(push_state());
+      T *u_r = nullptr, *u_i = nullptr, *q_rows = nullptr;
+      CAL_TRY(model_pass(3, [&](T* model_r, T* model_i, T* third) {
+        u_r = model_r, u_i = model_i, q_rows = third;
+        hipLaunchKernelGGL(coeff_solve_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, u_r, u_i, q_rows, data_r.as<T>(), data_i.as<T>(),
+                           wgts.as<T>(), gains.as<T2>(), bl_ant.as<int2>(), nbls, nfreqs, fpad);
+      }));
       HIP_TRY(hipMemsetAsync(cs_cnt.p, 0, 2 * sizeof(int), stream));
       for (const CsChunkRange& ch : cs_chunks) {
-        hipLaunchKernelGGL(coeff_gram_kernel<T>, dim3(ch.w1 - ch.w0), dim3(256), 0, stream, tiles.as<T>(), bl_tile.as<long long>(), a.model_r,
-                           a.model_i, q_rows, cs_grp.as<CsGroup>(), cs_work.as<CsWork>() + ch.w0, cs_n.as<T>(), cs_rhs.as<T>(), ncoef, nfreqs, fpad,
+        hipLaunchKernelGGL(coeff_gram_kernel<T>, dim3(ch.w1 - ch.w0), dim3(256), 0, stream, tiles.as<T>(), bl_tile.as<long long>(), u_r,
+                           u_i, q_rows, cs_grp.as<CsGroup>(), cs_work.as<CsWork>() + ch.w0, cs_n.as<T>(), cs_rhs.as<T>(), ncoef, nfreqs, fpad,
                            fold ? 1 : 0);
         hipLaunchKernelGGL(coeff_chol_kernel<T>, dim3(ch.g1 - ch.g0), dim3(256), ch.lds, stream, cs_n.as<T>(), cs_rhs.as<T>(), cs_d.as<double>(),
                            cs_grp.as<CsGroup>(), cs_order.as<int>() + ch.g0, coef.as<T>(), coef.as<T>() + ncoef, ncoef, mask, d->damping, d->ridge,
@@ -2008,26 +2012,11 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     HIP_TRY(hipMemcpyAsync(counts, cs_cnt.p, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
     if (d->reset_coeff_moments) {
       // what set_optimizer leaves in the coefficient slots, for the selected slices (runs of neighbouring slices in one call per plane)
-      const bool acc = (opt.optimizer == CAL_OPT_ADAGRAD || opt.optimizer == CAL_OPT_FTRL) && opt.initial_accumulator_value != 0.0;
-      for (int t = 0; t < nslices;) {
-        if (d->slice_mask && !d->slice_mask[t]) {
-          ++t;
-          continue;
-        }
-        int t1 = t + 1;
-        while (t1 < nslices && (!d->slice_mask || d->slice_mask[t1])) ++t1;
+      CAL_TRY(for_selected_slice_runs(d->slice_mask, [&](int t, int t1) {
         const size_t n = (size_t)(h_slice_coff[t1] - h_slice_coff[t]);
-        for (int plane = 0; plane < 2 && n > 0; ++plane) {
-          const size_t off = (size_t)plane * ncoef + h_slice_coff[t];
-          HIP_TRY(hipMemsetAsync(coef_m.as<T>() + off, 0, n * sizeof(T), stream));
-          if (acc)
-            hipLaunchKernelGGL(fill_kernel<T>, dim3(grid_for((long long)n)), dim3(256), 0, stream, coef_v.as<T>() + off, (long long)n,
-                               (T)opt.initial_accumulator_value);
-          else
-            HIP_TRY(hipMemsetAsync(coef_v.as<T>() + off, 0, n * sizeof(T), stream));
-        }
-        t = t1;
-      }
+        for (int plane = 0; plane < 2 && n > 0; ++plane) CAL_TRY(reset_moment_slots(coef_m, coef_v, (size_t)plane * ncoef + h_slice_coff[t], n));
+        return (int)CAL_OK;
+      }));
       HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipStreamSynchronize(stream));
@@ -2045,21 +2034,15 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
   int solve_gain_coeffs(const cal_gain_coeff_solve_desc* d, cal_gain_coeff_solve_result* res) override {
     HIP_TRY(hipSetDevice(device));
     if (!d) return fail(CAL_ERR_INVALID, "solve_gain_coeffs: null description");
-    if (!has_problem) return fail(CAL_ERR_STATE, "solve_gain_coeffs: no problem set (cal_solver_set_problem)");
-    if (!has_data) return fail(CAL_ERR_STATE, "solve_gain_coeffs: no data set (cal_solver_set_data)");
-    if (!has_coef) return fail(CAL_ERR_STATE, "solve_gain_coeffs: the coefficients must be set (cal_solver_set_params)");
-    if (!has_gains) return fail(CAL_ERR_STATE, "solve_gain_coeffs: the gains must be set (cal_solver_set_params)");
+    CAL_TRY(require_set("solve_gain_coeffs", true));
     if (d->nsweeps < 1) return fail(CAL_ERR_INVALID, "solve_gain_coeffs: nsweeps = %d, at least one sweep", d->nsweeps);
-    if (!(d->damping > 0.0 && d->damping <= 1.0)) return fail(CAL_ERR_INVALID, "solve_gain_coeffs: damping = %g lies outside (0, 1]", d->damping);
-    if (!(d->ridge >= 0.0) || !std::isfinite(d->ridge)) return fail(CAL_ERR_INVALID, "solve_gain_coeffs: ridge = %g must be finite and >= 0", d->ridge);
+    CAL_TRY(check_damping_ridge("solve_gain_coeffs", d->damping, &d->ridge));
     if (tb_on())
       return fail(CAL_ERR_UNSUPPORTED, "solve_gain_coeffs: a gain time basis is set (cal_solver_set_gain_time_basis): its coefficients couple the times of an "
                   "antenna, a joint (l, k) system this call does not solve; detach the time basis (nvec_t = 0) first");
     if (!gb_on()) return fail(CAL_ERR_STATE, "solve_gain_coeffs: no frequency gain basis is set (cal_solver_set_gain_basis); cal_solver_solve_gains solves free per-channel gains");
     if (d->reset_gain_moments && !has_opt) return fail(CAL_ERR_STATE, "solve_gain_coeffs: reset_gain_moments without an optimizer (cal_solver_set_optimizer)");
     CAL_TRY(build_solve_lists());
-    const size_t rowbytes = (size_t)nbls * fpad * sizeof(T);
-    if (model_buf.bytes < 3 * rowbytes) CAL_TRY(model_buf.alloc(3 * rowbytes));
     const size_t nant_out = (size_t)nants * nfreqs;
     if (gs_out.bytes < 3 * nant_out * sizeof(double)) CAL_TRY(gs_out.alloc(3 * nant_out * sizeof(double)));
     // chunks of antenna rows whose N_a (T) and factor (double, only where it does not fit LDS) stay under cs_bound; at least one row
@@ -2076,29 +2059,18 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&gain_basis_chol_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 kCsLdsDoubles * (int)sizeof(double)));
     const unsigned char* mask = nullptr;
-    if (d->slice_mask) {
-      if (gs_mask.bytes < (size_t)nslices) CAL_TRY(gs_mask.alloc((size_t)nslices, false));
-      HIP_TRY(copy_sync(gs_mask.p, d->slice_mask, (size_t)nslices, hipMemcpyHostToDevice));
-      mask = gs_mask.as<unsigned char>();
-    }
-    const std::vector<DevState> saved(h_state, h_state + nslices);
-    begin_pass_state();
-    CAL_TRY(push_state());
-    FusedArgs<T> a = fused_args();
-    a.model_r = model_buf.as<T>();
-    a.model_i = model_buf.as<T>() + (size_t)nbls * fpad;
-    T* q_rows = model_buf.as<T>() + 2 * (size_t)nbls * fpad;
-    launch_fused<MODE_MODEL>(a, false);
-    hipLaunchKernelGGL(gain_solve_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, a.model_r, a.model_i, q_rows, data_r.as<T>(),
-                       data_i.as<T>(), wgts.as<T>(), bl_ant.as<int2>(), nbls, nfreqs, fpad);
-    HIP_TRY(hipGetLastError());
-    std::copy(saved.begin(), saved.end(), h_state);
-    CAL_TRY(push_state());
+    CAL_TRY(upload_slice_mask(d->slice_mask, &mask));
+    T *u_r = nullptr, *u_i = nullptr, *q_rows = nullptr;
+    CAL_TRY(model_pass(3, [&](T* model_r, T* model_i, T* third) {
+      u_r = model_r, u_i = model_i, q_rows = third;
+      hipLaunchKernelGGL(gain_solve_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, u_r, u_i, q_rows, data_r.as<T>(), data_i.as<T>(),
+                         wgts.as<T>(), bl_ant.as<int2>(), nbls, nfreqs, fpad);
+    }));
     constexpr int V = 16 / (int)sizeof(T);
     const int cblocks = (fpad + 64 * V - 1) / (64 * V);
-    const int nb = (K + kGbsBlock - 1) / kGbsBlock, npairs = nb * (nb + 1) / 2;
+    const int nb = (K + kNsBlock - 1) / kNsBlock, npairs = nb * (nb + 1) / 2;
     for (int k = 0; k < d->nsweeps; ++k) {
-      hipLaunchKernelGGL(gain_solve_ant_kernel<T>, dim3(nants * cblocks), dim3(256), 0, stream, a.model_r, a.model_i, q_rows, gains.as<T2>(),
+      hipLaunchKernelGGL(gain_solve_ant_kernel<T>, dim3(nants * cblocks), dim3(256), 0, stream, u_r, u_i, q_rows, gains.as<T2>(),
                          gs_ptr.as<int>(), gs_ent.as<int2>(), nants, nfreqs, fpad, gs_out.as<double>());
       HIP_TRY(hipGetLastError());
       if (comm_on()) CAL_TRY(all_reduce(gs_out.p, 3 * nant_out, CAL_XCHG_F64, CAL_XCHG_SUM));
@@ -2113,42 +2085,20 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
       }
       // gains = g0 + B y for the selected slices (runs of neighbouring slices in one launch each): the others keep their bits
       constexpr int per = 256 * (16 / (int)sizeof(T));  // channels per block of gain_expand_kernel
-      for (int t = 0; t < nslices;) {
-        if (d->slice_mask && !d->slice_mask[t]) {
-          ++t;
-          continue;
-        }
-        int t1 = t + 1;
-        while (t1 < nslices && (!d->slice_mask || d->slice_mask[t1])) ++t1;
+      CAL_TRY(for_selected_slice_runs(d->slice_mask, [&](int t, int t1) {
         const size_t r0 = (size_t)t * na_slice;
         hipLaunchKernelGGL((gain_expand_kernel<T>), dim3((fpad + per - 1) / per, (t1 - t) * na_slice), dim3(256), 0, stream, gb_g0.as<T2>() + r0 * fpad,
                            gb_Bt.as<T>(), gb_y.as<T2>() + r0 * gb_kpad, gains.as<T2>() + r0 * fpad, fpad, gb_kpad);
-        t = t1;
-      }
+        return (int)CAL_OK;
+      }));
       HIP_TRY(hipGetLastError());
     }
     int counts[2] = {0, 0};
     HIP_TRY(hipMemcpyAsync(counts, gbs_cnt.p, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
     if (d->reset_gain_moments) {
       // what set_optimizer leaves in the y slots, for the selected slices (runs of neighbouring slices in one call each)
-      const bool acc = (opt.optimizer == CAL_OPT_ADAGRAD || opt.optimizer == CAL_OPT_FTRL) && opt.initial_accumulator_value != 0.0;
       const size_t per = (size_t)na_slice * gb_kpad * 2;  // reals per slice
-      for (int t = 0; t < nslices;) {
-        if (d->slice_mask && !d->slice_mask[t]) {
-          ++t;
-          continue;
-        }
-        int t1 = t + 1;
-        while (t1 < nslices && (!d->slice_mask || d->slice_mask[t1])) ++t1;
-        const size_t off = (size_t)t * per, n = (size_t)(t1 - t) * per;
-        HIP_TRY(hipMemsetAsync(gb_ym.as<T>() + off, 0, n * sizeof(T), stream));
-        if (acc)
-          hipLaunchKernelGGL(fill_kernel<T>, dim3(grid_for((long long)n)), dim3(256), 0, stream, gb_yv.as<T>() + off, (long long)n,
-                             (T)opt.initial_accumulator_value);
-        else
-          HIP_TRY(hipMemsetAsync(gb_yv.as<T>() + off, 0, n * sizeof(T), stream));
-        t = t1;
-      }
+      CAL_TRY(for_selected_slice_runs(d->slice_mask, [&](int t, int t1) { return reset_moment_slots(gb_ym, gb_yv, (size_t)t * per, (size_t)(t1 - t) * per); }));
       HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipStreamSynchronize(stream));

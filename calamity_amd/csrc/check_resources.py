@@ -11,7 +11,8 @@ CU to itself): no scratch and no spilled VGPRs there either (a few SGPR spills i
 `gain_project_kernel`, `gain_expand_kernel` (gain_basis_kernels.hpp), `gain_time_project_kernel`, `gain_time_expand_kernel`
 (gain_time_basis_kernels.hpp), `quality_rows_kernel`, `quality_ant_kernel` (fit_quality_kernels.hpp), `gain_solve_rows_kernel`, `gain_solve_ant_kernel`,
 `gain_solve_apply_kernel` (gain_solve_kernels.hpp), `coeff_solve_rows_kernel`, `coeff_gram_kernel`, `coeff_chol_kernel`
-(coeff_solve_kernels.hpp), `gain_basis_gram_kernel`, `gain_basis_chol_kernel` (gain_basis_solve_kernels.hpp): no scratch, no spilled VGPRs."""
+(coeff_solve_kernels.hpp), `gain_basis_gram_kernel`, `gain_basis_chol_kernel` (gain_basis_solve_kernels.hpp; both pairs are built on the
+shared Gram and Cholesky core of normal_solve.hpp): no scratch, no spilled VGPRs."""
 import re
 import sys
 

@@ -73,12 +73,13 @@ def test_one_sweep_equals_the_numpy_restatement(shape, layout, dtype):
 
 # ---- basis widths: one partial MFMA tile, the second 64-block with its off-diagonal block, the factor on both sides of its LDS bound
 WIDTHS = [((7, 200), K) for K in (1, 12, 33, 65, 130)] + [((12, 129), K) for K in (1, 12, 33, 65)] + [((5, 48), K) for K in (1, 12, 33)]
+WIDTHS += [((7, 200), K) for K in (127, 128)]  # the last factor in LDS and the first in scratch (appended: the case ids above keep their numbers)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("shape,K", WIDTHS)
 def test_basis_widths_and_one_row_chunks(shape, K, dtype):
-    """K = 130: (K + 2) rows of the factor no longer fit the 128 KB of LDS (the bound is K = 127).  The same call through chunks of one
+    """K = 127 is the last factor in LDS (128 KB), K = 128 the first in scratch, K = 130 well past it.  The same call through chunks of one
     antenna row gives the same bits."""
     p, params = edge_problem(*shape)
     B = random_basis(p.nfreqs, K)
