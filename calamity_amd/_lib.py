@@ -96,6 +96,14 @@ class GainCoeffSolveResult(C.Structure):
     _fields_ = [("nsolved", C.c_int32), ("nsingular", C.c_int32)]
 
 
+class GainTimeSolveDesc(C.Structure):
+    _fields_ = [("nsweeps", C.c_int32), ("reset_gain_moments", C.c_int32), ("damping", C.c_double), ("ridge", C.c_double)]
+
+
+class GainTimeSolveResult(C.Structure):
+    _fields_ = [("nsolved", C.c_int32), ("nsingular", C.c_int32)]
+
+
 class RunResult(C.Structure):
     _fields_ = [("nrecorded", C.c_int32), ("stopped", C.c_int32), ("nupdates", C.c_int32), ("nonfinite", C.c_int32)]
 
@@ -149,6 +157,7 @@ SYMBOLS = {
     "cal_solver_solve_coeffs": (C.c_int, [_P, C.POINTER(CoeffSolveDesc), C.POINTER(CoeffSolveResult)]),
     "cal_solver_set_coeff_solve_scratch": (C.c_int, [_P, C.c_int64]),
     "cal_solver_solve_gain_coeffs": (C.c_int, [_P, C.POINTER(GainCoeffSolveDesc), C.POINTER(GainCoeffSolveResult)]),
+    "cal_solver_solve_gain_time_coeffs": (C.c_int, [_P, C.POINTER(GainTimeSolveDesc), C.POINTER(GainTimeSolveResult)]),
     "cal_solver_get_gain_coeff_moments": (C.c_int, [_P] + [_P] * 8 + [C.POINTER(C.c_int64)]),
     "cal_weighted_square_error": (C.c_int, [C.c_int, C.c_int, C.c_int64, _P, _P, _P, _P, _P, C.POINTER(C.c_double)]),
     "cal_solver_init_coeffs": (C.c_int, [_P, _P, _P]),

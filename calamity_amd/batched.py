@@ -294,6 +294,13 @@ class SliceBatchFitter:
                                                            reset_gain_moments=reset_gain_moments))
         return outs[0]
 
+    def solve_gain_time_coeffs(self, nsweeps, damping=0.5, ridge=1e-6, reset_gain_moments=False):
+        """``HipFitSolver.solve_gain_time_coeffs`` on every worker of a ``joint`` fitter with a time basis.  With several workers each
+        sweep sums the three antenna planes of the workers' baselines in one exchange; ``y`` is replicated, so every worker then
+        computes the same update of its replica: the counts are worker 0's."""
+        outs = self._each(lambda r, s: s.solve_gain_time_coeffs(nsweeps, damping=damping, ridge=ridge, reset_gain_moments=reset_gain_moments))
+        return outs[0]
+
     def hold_slices(self, mask=None):
         """``HipFitSolver.hold_slices`` on every worker."""
         self._each(lambda r, s: s.hold_slices(mask))

@@ -649,6 +649,10 @@ def fit_gains_and_foregrounds(
     gain_basis_solve_every=0,
     gain_basis_solve_damping=0.5,
     gain_basis_solve_ridge=1e-6,
+    gain_time_solve_sweeps=0,
+    gain_time_solve_every=0,
+    gain_time_solve_damping=0.5,
+    gain_time_solve_ridge=1e-6,
     **opt_kwargs,
 ):
     """Run the optimization loop that fits gains and foreground coefficients -- calibration.py:447-738.
@@ -666,12 +670,17 @@ def fit_gains_and_foregrounds(
     per-channel gains.  ``gain_solve_sweeps`` / ``gain_solve_every`` / ``gain_solve_damping``: closed-form gain sweeps before and
     between the descent steps, and ``coeff_solve_rounds`` / ``coeff_solve_ridge``: closed-form coefficient solves in front of them,
     and ``gain_basis_solve_sweeps`` / ``gain_basis_solve_every`` / ``gain_basis_solve_damping`` / ``gain_basis_solve_ridge``: the sweeps
-    of a fit with a ``gain_basis``, see ``calibrate_and_model_tensor``.
+    of a fit with a ``gain_basis``, see ``calibrate_and_model_tensor``.  ``gain_time_solve_sweeps`` / ``gain_time_solve_every`` /
+    ``gain_time_solve_damping`` / ``gain_time_solve_ridge`` are checked like theirs, but belong to the joint fit over the times of
+    ``calibrate_and_model_tensor(gain_time_basis=... / gain_time_scale=...)``: this function fits one time, so switching them on raises
+    ``ValueError``.
     """
     _check_gain_solve(gain_solve_sweeps, gain_solve_every, gain_solve_damping, gain_basis is not None)
     _check_coeff_solve(coeff_solve_rounds, coeff_solve_ridge, freeze_model)
     _check_gain_basis_solve(gain_basis_solve_sweeps, gain_basis_solve_every, gain_basis_solve_damping, gain_basis_solve_ridge,
                             gain_basis is not None, False)
+    _check_gain_time_solve(gain_time_solve_sweeps, gain_time_solve_every, gain_time_solve_damping, gain_time_solve_ridge, False,
+                           bool(gain_basis_solve_sweeps or gain_basis_solve_every), bool(gain_solve_sweeps or gain_solve_every))
     if gain_basis_solve_sweeps or gain_basis_solve_every:  # a basis fit: its sweeps stand where the per-channel sweeps stand
         sweep = lambda n, **kw: solver.solve_gain_coeffs(n, damping=gain_basis_solve_damping, ridge=gain_basis_solve_ridge, **kw)["nsingular"]  # noqa: E731
         n_sweeps, every = gain_basis_solve_sweeps, gain_basis_solve_every
@@ -802,6 +811,26 @@ def _check_gain_basis_solve(sweeps, every, damping, ridge, freq_basis_given, tim
     if not freq_basis_given:
         raise ValueError("gain_basis_solve_sweeps / gain_basis_solve_every solve the coefficients of a frequency gain basis: give gain_basis or "
                          "gain_max_dly (free per-channel gains have gain_solve_sweeps / gain_solve_every)")
+
+
+def _check_gain_time_solve(sweeps, every, damping, ridge, time_basis_given, basis_solve_on, gain_solve_on):
+    """The arguments of the closed-form sweeps of a fit with a gain time basis (ValueError before any device work)."""
+    for v in (sweeps, every):
+        if isinstance(v, bool) or int(v) != v or v < 0:
+            raise ValueError(f"gain_time_solve_sweeps and gain_time_solve_every must be non-negative integers, got {sweeps!r} and {every!r}")
+    if not 0.0 < float(damping) <= 1.0:
+        raise ValueError(f"gain_time_solve_damping must lie in (0, 1], got {damping!r}")
+    if not (np.isfinite(float(ridge)) and float(ridge) >= 0.0):
+        raise ValueError(f"gain_time_solve_ridge must be finite and >= 0, got {ridge!r}")
+    if not (sweeps or every):
+        return
+    if not time_basis_given:
+        raise ValueError("gain_time_solve_sweeps / gain_time_solve_every solve the coefficients of a joint fit over the times: give gain_time_basis "
+                         "or gain_time_scale (a frequency gain basis alone has gain_basis_solve_sweeps / gain_basis_solve_every, free per-channel "
+                         "gains have gain_solve_sweeps / gain_solve_every)")
+    if basis_solve_on or gain_solve_on:
+        raise ValueError("gain_time_solve_sweeps / gain_time_solve_every are the sweeps of a fit with a gain time basis: they cannot be combined "
+                         "with gain_basis_solve_sweeps / gain_basis_solve_every or gain_solve_sweeps / gain_solve_every")
 
 
 def _check_coeff_solve(rounds, ridge, freeze_model):
@@ -945,6 +974,10 @@ def calibrate_and_model_tensor(
     gain_basis_solve_every=0,
     gain_basis_solve_damping=0.5,
     gain_basis_solve_ridge=1e-6,
+    gain_time_solve_sweeps=0,
+    gain_time_solve_every=0,
+    gain_time_solve_damping=0.5,
+    gain_time_solve_ridge=1e-6,
     **opt_kwargs,
 ):
     """Simultaneous calibration and foreground fitting -- calibration.py:963-1331, same arguments, defaults and
@@ -1041,6 +1074,24 @@ def calibrate_and_model_tensor(
       ``gain_time_scale`` (the joint system across times is a different solve).  The sweeps minimise the chi-square term only.
       ``fit_history[polnum][time_index]["gain_basis_solve_singular"]`` (present only with the feature on): the antenna rows the last
       sweep left alone (no unflagged cross-correlation, or a non-positive pivot); in a batch the count is over the slices fitted together.
+    * ``gain_time_solve_sweeps`` / ``gain_time_solve_every`` / ``gain_time_solve_damping`` / ``gain_time_solve_ridge`` (defaults 0, 0,
+      0.5, 1e-6: off, no call changes by a bit): the closed-form sweeps for the joint fit of ``gain_time_basis`` / ``gain_time_scale``
+      (``HipFitSolver.solve_gain_time_coeffs``), with or without ``gain_basis`` / ``gain_max_dly``.  ``num``, ``den`` are the per-row sums
+      of a per-channel sweep from the OLD gains, ``r = num - den g``; with a frequency basis (``n = L K``, index ``l K + k``),
+      ``M_{t,a} = B^T diag(den_{t,a}) B``::
+
+          N_a[(l,k),(l',k')] = sum_t Bt[t,l] Bt[t,l'] M_{t,a}[k,k']          rhs_a[(l,k)] = sum_t Bt[t,l] (B^T r_{t,a})[k]
+          (N_a + ridge (tr N_a / n) I) delta_a = rhs_a                        y_a <- y_a + damping delta_a
+
+      and without one, per (antenna, channel), ``N_{a,f}[l,l'] = sum_t Bt[t,l] Bt[t,l'] den[t,a,f]``,
+      ``rhs_{a,f}[l] = sum_t Bt[t,l] r[t,a,f]``, ridge ``ridge tr N_{a,f} / L``.  They act where ``gain_basis_solve_sweeps`` /
+      ``gain_basis_solve_every`` act: ``gain_time_solve_sweeps=N`` sweeps after the optimizer is set; with ``coeff_solve_rounds=R``, R
+      rounds of [coefficient solve, N sweeps]; ``gain_time_solve_every=K``: the recorded loop in chunks of K steps, between two chunks
+      one coefficient solve (if ``coeff_solve_rounds > 0``) and ``max(1, N)`` sweeps with the optimizer's ``y`` moments started over.
+      An antenna flagged at some times only is solved and its gains there move (the time basis interpolates).  ``ValueError`` without
+      ``gain_time_basis`` / ``gain_time_scale`` and together with ``gain_basis_solve_*`` or ``gain_solve_*``.  The sweeps minimise the
+      chi-square term only.  ``fit_history[polnum][time_index]["gain_time_solve_singular"]`` (present only with the feature on): the
+      systems the last sweep left alone (antennas with a frequency basis, (antenna, channel) pairs without one).
     * ``layout``: "shared" (default; baselines alias the distinct basis blocks) or "stream" (every baseline owns its tiles).
     * ``parallel_fits`` (default 1): with ``batch_slices=False``, fits that many slices concurrently, each on its own
       solver and HIP stream.
@@ -1052,6 +1103,9 @@ def calibrate_and_model_tensor(
     _check_coeff_solve(coeff_solve_rounds, coeff_solve_ridge, freeze_model)
     _check_gain_basis_solve(gain_basis_solve_sweeps, gain_basis_solve_every, gain_basis_solve_damping, gain_basis_solve_ridge,
                             gain_basis is not None or gain_max_dly is not None, gain_time_basis is not None or gain_time_scale is not None)
+    _check_gain_time_solve(gain_time_solve_sweeps, gain_time_solve_every, gain_time_solve_damping, gain_time_solve_ridge,
+                           gain_time_basis is not None or gain_time_scale is not None,
+                           bool(gain_basis_solve_sweeps or gain_basis_solve_every), bool(gain_solve_sweeps or gain_solve_every))
     if gain_max_dly is not None:
         gain_basis = modeling.gain_dpss_basis(np.asarray(uvdata.freq_array, dtype=np.float64).ravel(), gain_max_dly)
     if gain_time_basis is not None and gain_time_scale is not None:
@@ -1144,6 +1198,7 @@ def calibrate_and_model_tensor(
             gain_time_basis=gain_time_basis, fit_quality=fit_quality,
             gain_solve=(gain_solve_sweeps, gain_solve_every, gain_solve_damping), coeff_solve=(coeff_solve_rounds, coeff_solve_ridge),
             gain_basis_solve=(gain_basis_solve_sweeps, gain_basis_solve_every, gain_basis_solve_damping, gain_basis_solve_ridge),
+            gain_time_solve=(gain_time_solve_sweeps, gain_time_solve_every, gain_time_solve_damping, gain_time_solve_ridge),
         )
         return model, resid, gains, fit_history  # (every slice left _fit_slices_batched in its final state)
     assert gain_time_basis is None, "a gain time basis must not reach the loop over single times"
@@ -1207,7 +1262,9 @@ def calibrate_and_model_tensor(
                 gain_solve_sweeps=gain_solve_sweeps, gain_solve_every=gain_solve_every, gain_solve_damping=gain_solve_damping,
                 coeff_solve_rounds=coeff_solve_rounds, coeff_solve_ridge=coeff_solve_ridge, gain_basis_solve_sweeps=gain_basis_solve_sweeps,
                 gain_basis_solve_every=gain_basis_solve_every, gain_basis_solve_damping=gain_basis_solve_damping,
-                gain_basis_solve_ridge=gain_basis_solve_ridge, **opt_kwargs,
+                gain_basis_solve_ridge=gain_basis_solve_ridge, gain_time_solve_sweeps=gain_time_solve_sweeps,
+                gain_time_solve_every=gain_time_solve_every, gain_time_solve_damping=gain_time_solve_damping,
+                gain_time_solve_ridge=gain_time_solve_ridge, **opt_kwargs,
             )
             # yield_fg_model_array x 2 + insert_model_into_uvdata_tensor (calibration.py:1271-1292) without the
             # nants x nants cubes: one A c pass for both components, rows written straight back
@@ -1438,7 +1495,8 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
                         skip_threshold, use_model_snr_weights, optimizer, use_min, freeze_model, tol, maxsteps, n_profile_steps,
                         profile_log_dir, model_regularization, verbose, max_batch, devices, layout, opt_kwargs, correct_model=True,
                         correct_resid=False, device_split=None, gain_basis=None, gain_time_basis=None, fit_quality=False,
-                        gain_solve=(0, 0, 0.5), coeff_solve=(0, 1e-6), gain_basis_solve=(0, 0, 0.5, 1e-6)):
+                        gain_solve=(0, 0, 0.5), coeff_solve=(0, 1e-6), gain_basis_solve=(0, 0, 0.5, 1e-6),
+                        gain_time_solve=(0, 0, 0.5, 1e-6)):
     """The pol x time loop of calibration.py:1160-1331 with the fits of all unskipped slices issued as batches: per slice
     exactly the host-side steps of the loop body (skip test :1173-1177, rms scale :1178-1182, tensorize :1184-1233, write-back
     :1271-1300, post-hoc renormalisation :1311-1319, residual and calibration state of the outputs :1322-1331), the gradient
@@ -1447,12 +1505,16 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
     are one batch and one JOINT fit (one loop state, loss = the sum over the times; calibrate_and_model_tensor's docstring).
     ``gain_solve``: (gain_solve_sweeps, gain_solve_every, gain_solve_damping), ``coeff_solve``: (coeff_solve_rounds, coeff_solve_ridge) of
     calibrate_and_model_tensor, ``gain_basis_solve``: its (gain_basis_solve_sweeps, _every, _damping, _ridge), which stand in for
-    ``gain_solve`` on a fit with a frequency gain basis."""
+    ``gain_solve`` on a fit with a frequency gain basis, ``gain_time_solve``: its (gain_time_solve_sweeps, _every, _damping, _ridge), which
+    stand in for them on the joint fit of a gain time basis."""
     gs_sweeps, gs_every, gs_damping = gain_solve
     cs_rounds, cs_ridge = coeff_solve
     gbs_on = bool(gain_basis_solve[0] or gain_basis_solve[1])
     if gbs_on:
         gs_sweeps, gs_every, gbs_damping, gbs_ridge = gain_basis_solve
+    gts_on = bool(gain_time_solve[0] or gain_time_solve[1])
+    if gts_on:
+        gs_sweeps, gs_every, gts_damping, gts_ridge = gain_time_solve
     OPTIMIZERS[optimizer]  # unknown optimizer -> KeyError, like calibration.py:571
     dtype = np.dtype(dtype)
     layout = layout or "shared"
@@ -1563,7 +1625,9 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
             fitter.set_regularization(None)
         fitter.set_optimizer(optimizer, **opt_kwargs)
         nsingular = gb_singular = None
-        if gbs_on:  # a basis fit: its sweeps stand where the per-channel sweeps stand
+        if gts_on:  # the joint fit of a time basis: one system over the times, so no slice mask
+            sweep = lambda n, slice_mask=None, **kw: fitter.solve_gain_time_coeffs(n, damping=gts_damping, ridge=gts_ridge, **kw)["nsingular"]  # noqa: E731
+        elif gbs_on:  # a basis fit: its sweeps stand where the per-channel sweeps stand
             sweep = lambda n, **kw: fitter.solve_gain_coeffs(n, damping=gbs_damping, ridge=gbs_ridge, **kw)["nsingular"]  # noqa: E731
         else:
             sweep = lambda n, **kw: fitter.solve_gains(n, damping=gs_damping, **kw)  # noqa: E731
@@ -1585,7 +1649,8 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
         if gs_every > 0:
             # the recorded loop in chunks (every slice's loop state persists from run to run); a slice whose loop has ended is held
             # in the chunks that follow, as one call would leave it, and takes no part in the gain solves between the chunks
-            parts, over, nupd, issued = [[] for _ in range(nt)], np.zeros(nt, dtype=bool), np.zeros(nt, dtype=np.int64), 0
+            nl = 1 if joint else nt  # loops: a joint fit has one
+            parts, over, nupd, issued = [[] for _ in range(nl)], np.zeros(nl, dtype=bool), np.zeros(nl, dtype=np.int64), 0
             while issued < maxsteps and not np.all(over):
                 n = min(gs_every, maxsteps - issued)
                 for t, (part, stopped, nu) in enumerate(fitter.run_slices(n, record=True, tol=tol, use_min=use_min, freeze_model=freeze_model)):
@@ -1600,7 +1665,7 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
                         nsingular = fitter.solve_coeffs(ridge=cs_ridge, slice_mask=~over, reset_coeff_moments=True)["nsingular"]
                     gb_singular = sweep(max(1, gs_sweeps), slice_mask=~over, reset_gain_moments=True)
             fitter.hold_slices(None)
-            results = [(np.concatenate(parts[t]), bool(over[t]), int(nupd[t])) for t in range(nt)]
+            results = [(np.concatenate(parts[t]), bool(over[t]), int(nupd[t])) for t in range(nl)]
         else:
             results = fitter.run_slices(maxsteps, record=True, tol=tol, use_min=use_min, freeze_model=freeze_model)
         if joint:
@@ -1625,7 +1690,7 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
         quality = fitter.fit_quality(gm_r, gm_i) if fit_quality else None
         echo(f"{datetime.datetime.now()} ... fitted.\n", verbose=verbose)
         return dict(results=results, m_r=m_r, m_i=m_i, gm_r=gm_r, gm_i=gm_i, quality=quality, nsingular=nsingular,
-                    gb_singular=int(gb_singular or 0) if gbs_on else None)
+                    gb_singular=int(gb_singular or 0) if gbs_on else None, gt_singular=int(gb_singular or 0) if gts_on else None)
 
     def post(batch, out):
         for t, (sl, res) in enumerate(zip(batch, out["results"])):
@@ -1637,6 +1702,8 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
                 fit_history[sl["polnum"]][sl["time_index"]]["coeff_solve_singular"] = int(out["nsingular"])
             if out.get("gb_singular") is not None:
                 fit_history[sl["polnum"]][sl["time_index"]]["gain_basis_solve_singular"] = int(out["gb_singular"])
+            if out.get("gt_singular") is not None:
+                fit_history[sl["polnum"]][sl["time_index"]]["gain_time_solve_singular"] = int(out["gt_singular"])
             if out.get("quality") is not None:  # (before the post-hoc renormalisation, which leaves g_i conj(g_j) m as it is)
                 q = out["quality"]
                 insert_fit_quality(gains, fit_history[sl["polnum"]][sl["time_index"]], sl["time"], sl["pol"],
@@ -2092,6 +2159,16 @@ def fitting_argparser():
                     help="damping of a basis sweep, in (0, 1]: y <- y + damping x the closed-form step; default 0.5")
     sp.add_argument("--gain_basis_solve_ridge", type=float, default=1e-6,
                     help="ridge of a basis sweep, as a fraction of the mean diagonal of an antenna's normal matrix; default 1e-6")
+    sp.add_argument("--gain_time_solve_sweeps", type=int, default=0,
+                    help="with --gain_time_scale: solve the coefficients of the joint fit over the times in closed form (damped StefCal sweeps "
+                         "taken jointly over the times) this many times before the first descent step; default 0: descent only")
+    sp.add_argument("--gain_time_solve_every", type=int, default=0,
+                    help="with --gain_time_scale: run joint sweeps (--gain_time_solve_sweeps of them, at least one) after every this many "
+                         "recorded descent steps; default 0: never")
+    sp.add_argument("--gain_time_solve_damping", type=float, default=0.5,
+                    help="damping of a joint sweep, in (0, 1]: y <- y + damping x the closed-form step; default 0.5")
+    sp.add_argument("--gain_time_solve_ridge", type=float, default=1e-6,
+                    help="ridge of a joint sweep, as a fraction of the mean diagonal of a system's normal matrix; default 1e-6")
     return ap
 
 

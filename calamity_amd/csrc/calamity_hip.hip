@@ -29,6 +29,7 @@
 #include "gain_solve_kernels.hpp"
 #include "coeff_solve_kernels.hpp"
 #include "gain_basis_solve_kernels.hpp"
+#include "gain_time_solve_kernels.hpp"
 #include "problem_plan.hpp"
 #include <cstdlib>
 #include <dlfcn.h>
@@ -161,6 +162,7 @@ struct cal_solver {
   virtual int solve_coeffs(const cal_coeff_solve_desc* d, cal_coeff_solve_result* res) = 0;
   virtual int set_coeff_solve_scratch(int64_t bytes) = 0;
   virtual int solve_gain_coeffs(const cal_gain_coeff_solve_desc* d, cal_gain_coeff_solve_result* res) = 0;
+  virtual int solve_gain_time_coeffs(const cal_gain_time_solve_desc* d, cal_gain_time_solve_result* res) = 0;
   virtual int get_gain_coeff_moments(void* ym_r, void* ym_i, void* yv_r, void* yv_i, void* cm_r, void* cm_i, void* cv_r, void* cv_i, int64_t* t) = 0;
   virtual int init_coeffs(const void* sr, const void* si) = 0;
   virtual int synchronize() = 0;
@@ -217,6 +219,10 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
   // solve_gain_coeffs (gain_basis_solve_kernels.hpp): N_a of a chunk of antenna rows in T (gbs_n), its factor in double where it does not
   // fit LDS (gbs_d), rhs [nants][2][K] T, the two counters; the chunks share cs_bound
   DevBuf gbs_n, gbs_d, gbs_rhs, gbs_cnt;
+  // solve_gain_time_coeffs (gain_time_solve_kernels.hpp), per chunk of antennas: M_{t,a} [T][ca][K][K] T (gts_m), N_a [ca][n][n] and rhs_a
+  // [ca][2][n] T (gts_n, gts_rhsa), the factor in double where it leaves LDS or, without a frequency basis, the channel systems beyond
+  // kTimeTile vectors (gts_d); the per-row right-hand sides [nants][2][K] T (gts_rhs), the two counters; the chunks share cs_bound
+  DevBuf gts_m, gts_n, gts_rhsa, gts_d, gts_rhs, gts_cnt;
   std::vector<uint8_t> held;                   // hold_slices: [nslices], 1 = the slice enters every later run as stopped (empty: none)
   DevBuf fq_out, fq_gains;                     // fit_quality: chisq_ant | wsum_ant ([nants][nfreqs] doubles each, the exchange payload) | chisq_bl | wsum_bl; gains given for one evaluation
   DevBuf members, heads;                       // baselines that share tiles (bl_alias): member lists of the head items, head item indices
@@ -1291,6 +1297,10 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
   }
   void release_gain_coeff_solve() {  // the scratch of solve_gain_coeffs: sized again by the next call
     for (DevBuf* b : {&gbs_n, &gbs_d, &gbs_rhs, &gbs_cnt}) b->release();
+    release_gain_time_solve();
+  }
+  void release_gain_time_solve() {  // the scratch of solve_gain_time_coeffs: sized again by the next call
+    for (DevBuf* b : {&gts_m, &gts_n, &gts_rhsa, &gts_d, &gts_rhs, &gts_cnt}) b->release();
   }
   // the fit starts from the gains the solver holds now: g0 := gains, y := 0 (and its snapshot with it)
   int rebase_gain_basis() {
@@ -1303,6 +1313,7 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
   // after either setter changed its basis: the y arrays in the shape the two bases now give them, g0 := gains, y := 0, moments and t zeroed
   int reshape_gain_coeffs() {
     for (DevBuf* b : {&gb_g0, &gb_y, &gb_ym, &gb_yv, &gb_ysnap, &gb_proj, &tb_z, &tb_pf}) b->release();
+    release_gain_time_solve();
     if (yb_on()) {
       const size_t ybytes = (size_t)y_rows() * y_row() * sizeof(T2);
       CAL_TRY(gb_g0.alloc(gains.bytes, false));
@@ -2109,6 +2120,109 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     return CAL_OK;
   }
 
+  // cal_solver_solve_gain_time_coeffs: solve_gain_coeffs' sequence up to the exchanged planes, then per chunk of antennas either
+  // gain_basis_gram_kernel (every row of the chunk: M_{t,a} and B^T r), gain_time_kron_kernel and gain_time_chol_kernel, or, without a
+  // frequency basis, gain_time_chan_kernel (gain_time_solve_kernels.hpp); then the gains rebuilt from y.  Every chunk of a sweep reads
+  // the old gains.  y is replicated and the planes are summed over the ranks: no collective beyond solve_gains' own.
+  int solve_gain_time_coeffs(const cal_gain_time_solve_desc* d, cal_gain_time_solve_result* res) override {
+    HIP_TRY(hipSetDevice(device));
+    if (!d) return fail(CAL_ERR_INVALID, "solve_gain_time_coeffs: null description");
+    CAL_TRY(require_set("solve_gain_time_coeffs", true));
+    if (d->nsweeps < 1) return fail(CAL_ERR_INVALID, "solve_gain_time_coeffs: nsweeps = %d, at least one sweep", d->nsweeps);
+    CAL_TRY(check_damping_ridge("solve_gain_time_coeffs", d->damping, &d->ridge));
+    if (!tb_on())
+      return fail(CAL_ERR_STATE, "solve_gain_time_coeffs: no gain time basis is set (cal_solver_set_gain_time_basis); cal_solver_solve_gain_coeffs solves the "
+                  "coefficients of a frequency basis alone, cal_solver_solve_gains free per-channel gains");
+    if (d->reset_gain_moments && !has_opt) return fail(CAL_ERR_STATE, "solve_gain_time_coeffs: reset_gain_moments without an optimizer (cal_solver_set_optimizer)");
+    CAL_TRY(build_solve_lists());
+    const size_t nant_out = (size_t)nants * nfreqs;
+    if (gs_out.bytes < 3 * nant_out * sizeof(double)) CAL_TRY(gs_out.alloc(3 * nant_out * sizeof(double)));
+    const int K = gb_nvec, L = tb_L, Tn = tb_T, na = tb_na, n = L * K;
+    // chunks of antennas whose buffers stay under cs_bound; at least one antenna
+    const bool in_lds = (long long)(n + 2) * (n | 1) <= kCsLdsDoubles;
+    const bool chan_regs = L <= kTimeTile;
+    long long m_ant = 0, n_ant = 0, d_ant = 0;  // elements per antenna of gts_m, gts_n (T) and gts_d (double)
+    if (gb_on()) {
+      m_ant = (long long)Tn * K * K;
+      n_ant = (long long)n * n;
+      d_ant = in_lds ? 0 : (long long)(n + 2) * n;
+    } else {
+      d_ant = chan_regs ? 0 : (long long)nfreqs * (L * (L + 1) / 2 + 2 * L);
+    }
+    const long long ant_bytes = std::max<long long>(1, (m_ant + n_ant) * (long long)sizeof(T) + d_ant * 8);
+    const int ants_per_chunk = (int)std::max<long long>(1, std::min<long long>(na, cs_bound / ant_bytes));
+    if (gb_on()) {
+      if (gts_m.bytes < (size_t)ants_per_chunk * m_ant * sizeof(T)) CAL_TRY(gts_m.alloc((size_t)ants_per_chunk * m_ant * sizeof(T), false));
+      if (gts_n.bytes < (size_t)ants_per_chunk * n_ant * sizeof(T)) CAL_TRY(gts_n.alloc((size_t)ants_per_chunk * n_ant * sizeof(T), false));
+      if (gts_rhsa.bytes < 2 * (size_t)ants_per_chunk * n * sizeof(T)) CAL_TRY(gts_rhsa.alloc(2 * (size_t)ants_per_chunk * n * sizeof(T), false));
+      if (gts_rhs.bytes < 2 * (size_t)nants * K * sizeof(T)) CAL_TRY(gts_rhs.alloc(2 * (size_t)nants * K * sizeof(T)));
+    }
+    if (gts_d.bytes < (size_t)ants_per_chunk * d_ant * sizeof(double) || !gts_d.p)
+      CAL_TRY(gts_d.alloc(std::max<size_t>(8, (size_t)ants_per_chunk * d_ant * sizeof(double)), false));
+    if (!gts_cnt.p) CAL_TRY(gts_cnt.alloc(2 * sizeof(int)));
+    const size_t chol_lds = (size_t)std::min<long long>((long long)(n + 2) * (n | 1), kCsLdsDoubles) * sizeof(double);
+    if (gb_on())
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&gain_time_chol_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  kCsLdsDoubles * (int)sizeof(double)));
+    T *u_r = nullptr, *u_i = nullptr, *q_rows = nullptr;
+    CAL_TRY(model_pass(3, [&](T* model_r, T* model_i, T* third) {
+      u_r = model_r, u_i = model_i, q_rows = third;
+      hipLaunchKernelGGL(gain_solve_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, u_r, u_i, q_rows, data_r.as<T>(), data_i.as<T>(),
+                         wgts.as<T>(), bl_ant.as<int2>(), nbls, nfreqs, fpad);
+    }));
+    constexpr int V = 16 / (int)sizeof(T);
+    const int cblocks = (fpad + 64 * V - 1) / (64 * V);
+    const int nb = (K + kNsBlock - 1) / kNsBlock, npairs = nb * (nb + 1) / 2;
+    for (int k = 0; k < d->nsweeps; ++k) {
+      hipLaunchKernelGGL(gain_solve_ant_kernel<T>, dim3(nants * cblocks), dim3(256), 0, stream, u_r, u_i, q_rows, gains.as<T2>(),
+                         gs_ptr.as<int>(), gs_ent.as<int2>(), nants, nfreqs, fpad, gs_out.as<double>());
+      HIP_TRY(hipGetLastError());
+      if (comm_on()) CAL_TRY(all_reduce(gs_out.p, 3 * nant_out, CAL_XCHG_F64, CAL_XCHG_SUM));
+      HIP_TRY(hipMemsetAsync(gts_cnt.p, 0, 2 * sizeof(int), stream));
+      for (int a0 = 0; a0 < na; a0 += ants_per_chunk) {
+        const int ca = std::min(ants_per_chunk, na - a0);
+        if (gb_on()) {
+          if (ca == na) {  // the rows of every time lie side by side: one launch, M [t][a][K][K]
+            hipLaunchKernelGGL(gain_basis_gram_kernel<T>, dim3((unsigned)nants * npairs), dim3(256), 0, stream, gb_Bt.as<T>(), gs_out.as<double>(),
+                               gains.as<T2>(), gts_m.as<T>(), gts_rhs.as<T>(), (const unsigned char*)nullptr, na_slice, 0, npairs, K, gb_kpad, nants,
+                               nfreqs, fpad);
+          } else {
+            for (int t = 0; t < Tn; ++t)
+              hipLaunchKernelGGL(gain_basis_gram_kernel<T>, dim3((unsigned)ca * npairs), dim3(256), 0, stream, gb_Bt.as<T>(), gs_out.as<double>(),
+                                 gains.as<T2>(), gts_m.as<T>() + (size_t)t * ca * K * K, gts_rhs.as<T>(), (const unsigned char*)nullptr, na_slice,
+                                 t * na + a0, npairs, K, gb_kpad, nants, nfreqs, fpad);
+          }
+          hipLaunchKernelGGL(gain_time_kron_kernel<T>, dim3((unsigned)ca * L, (L + kTimeTile - 1) / kTimeTile), dim3(256), 0, stream, gts_m.as<T>(),
+                             gts_rhs.as<T>(), tb_B.as<T>(), gts_n.as<T>(), gts_rhsa.as<T>(), a0, ca, na, Tn, L, tb_lpad, K);
+          hipLaunchKernelGGL(gain_time_chol_kernel<T>, dim3(ca), dim3(256), chol_lds, stream, gts_n.as<T>(), gts_rhsa.as<T>(), gts_d.as<double>(),
+                             gb_y.as<T2>(), a0, L, K, gb_kpad, d->damping, d->ridge, gts_cnt.as<int>(), kCsLdsDoubles);
+        } else {
+          const unsigned blocks = (unsigned)(((long long)ca * nfreqs + 255) / 256);
+          if (chan_regs)
+            hipLaunchKernelGGL((gain_time_chan_kernel<T, kTimeTile>), dim3(blocks), dim3(256), 0, stream, gs_out.as<double>(), gains.as<T2>(), tb_B.as<T>(),
+                               gb_y.as<T2>(), gts_d.as<double>(), a0, ca, na, Tn, L, tb_lpad, nfreqs, fpad, d->damping, d->ridge, gts_cnt.as<int>());
+          else
+            hipLaunchKernelGGL((gain_time_chan_kernel<T, 0>), dim3(blocks), dim3(256), 0, stream, gs_out.as<double>(), gains.as<T2>(), tb_B.as<T>(),
+                               gb_y.as<T2>(), gts_d.as<double>(), a0, ca, na, Tn, L, tb_lpad, nfreqs, fpad, d->damping, d->ridge, gts_cnt.as<int>());
+        }
+        HIP_TRY(hipGetLastError());
+      }
+      CAL_TRY(enqueue_expand(gb_y.as<T2>(), gains.as<T2>()));  // gains = g0 + Bt (x) (B) y, behind the last chunk
+    }
+    int counts[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(counts, gts_cnt.p, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
+    if (d->reset_gain_moments) {
+      CAL_TRY(reset_moment_slots(gb_ym, gb_yv, 0, 2 * (size_t)y_rows() * (size_t)y_row()));  // what set_optimizer leaves in the y slots
+      HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (res) {
+      res->nsolved = counts[0];
+      res->nsingular = counts[1];
+    }
+    return CAL_OK;
+  }
+
   int init_coeffs(const void* sr, const void* si) override {
     HIP_TRY(hipSetDevice(device));
     if (!has_problem || !has_data) return fail(CAL_ERR_STATE, "init_coeffs: problem and data (weights) must be set");
@@ -2175,7 +2289,7 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     if (!b) return fail(CAL_ERR_INVALID, "memory_bytes: null");
     const DevBuf* all[] = {&tiles, &bl_tile, &bl_ant, &items, &ant_ptr, &ant_ent, &coef_grp, &grp_coff, &grp_item_ptr, &item_goff,
                            &data_r, &data_i, &wgts, &gains, &gains_alt, &gains_m, &gains_v, &gains_snap, &coef, &coef_m, &coef_v, &coef_snap,
-                           &q0, &q1, &comm, &scal, &gcp0, &gcp1, &gc0, &gc1, &part, &state, &losses, &scratch, &model_buf, &fq_out, &fq_gains, &gs_out, &gs_ptr, &gs_ent, &gs_mask, &cs_grp, &cs_order, &cs_work, &cs_n, &cs_d, &cs_rhs, &cs_cnt, &gbs_n, &gbs_d, &gbs_rhs, &gbs_cnt,
+                           &q0, &q1, &comm, &scal, &gcp0, &gcp1, &gc0, &gc1, &part, &state, &losses, &scratch, &model_buf, &fq_out, &fq_gains, &gs_out, &gs_ptr, &gs_ent, &gs_mask, &cs_grp, &cs_order, &cs_work, &cs_n, &cs_d, &cs_rhs, &cs_cnt, &gbs_n, &gbs_d, &gbs_rhs, &gbs_cnt, &gts_m, &gts_n, &gts_rhsa, &gts_d, &gts_rhs, &gts_cnt,
                            &mf_ops, &mf_panels, &mf_map, &members, &heads, &lamb_vars, &lamb_cvar_ptr, &lamb_partial, &lamb_ratio, &lamb_glob, &lamb_slot, &slice_coff, &slice_ipart_ptr, &slice_ipart_idx,
                            &slice_ppart_ptr, &slice_ppart_idx, &slice_cblk, &gb_B, &gb_Bt, &gb_g0, &gb_y, &gb_ym, &gb_yv, &gb_ysnap, &gb_proj, &tb_B, &tb_Bt, &tb_z, &tb_pf};
     int64_t n = 0;
@@ -2534,6 +2648,7 @@ int cal_solver_get_gain_coeff_moments(cal_solver* s, void* ym_r, void* ym_i, voi
   return s->get_gain_coeff_moments(ym_r, ym_i, yv_r, yv_i, cm_r, cm_i, cv_r, cv_i, t);
 }
 int cal_solver_solve_gain_coeffs(cal_solver* s, const cal_gain_coeff_solve_desc* desc, cal_gain_coeff_solve_result* result) { NEED(s); return s->solve_gain_coeffs(desc, result); }
+int cal_solver_solve_gain_time_coeffs(cal_solver* s, const cal_gain_time_solve_desc* desc, cal_gain_time_solve_result* result) { NEED(s); return s->solve_gain_time_coeffs(desc, result); }
 int cal_solver_fit_quality(cal_solver* s, const void* g_r, const void* g_i, double* chisq_ant, double* wsum_ant, double* chisq_bl, double* wsum_bl) {
   NEED(s);
   return s->fit_quality(g_r, g_i, chisq_ant, wsum_ant, chisq_bl, wsum_bl);

@@ -12,7 +12,8 @@ CU to itself): no scratch and no spilled VGPRs there either (a few SGPR spills i
 (gain_time_basis_kernels.hpp), `quality_rows_kernel`, `quality_ant_kernel` (fit_quality_kernels.hpp), `gain_solve_rows_kernel`, `gain_solve_ant_kernel`,
 `gain_solve_apply_kernel` (gain_solve_kernels.hpp), `coeff_solve_rows_kernel`, `coeff_gram_kernel`, `coeff_chol_kernel`
 (coeff_solve_kernels.hpp), `gain_basis_gram_kernel`, `gain_basis_chol_kernel` (gain_basis_solve_kernels.hpp; both pairs are built on the
-shared Gram and Cholesky core of normal_solve.hpp): no scratch, no spilled VGPRs."""
+shared Gram and Cholesky core of normal_solve.hpp), `gain_time_kron_kernel`, `gain_time_chol_kernel`, `gain_time_chan_kernel`
+(gain_time_solve_kernels.hpp): no scratch, no spilled VGPRs."""
 import re
 import sys
 
@@ -46,9 +47,11 @@ for line in sys.stdin:
     if cur is not None and any(k in cur for k in ("gain_project_kernel", "gain_expand_kernel", "gain_time_project_kernel", "gain_time_expand_kernel",
                                              "quality_rows_kernel", "quality_ant_kernel", "gain_solve_rows_kernel", "gain_solve_ant_kernel",
                                              "gain_solve_apply_kernel", "coeff_solve_rows_kernel", "coeff_gram_kernel", "coeff_chol_kernel",
-                                             "gain_basis_gram_kernel", "gain_basis_chol_kernel")):
+                                             "gain_basis_gram_kernel", "gain_basis_chol_kernel", "gain_time_kron_kernel", "gain_time_chol_kernel",
+                                             "gain_time_chan_kernel")):
         # the kernels around the update of a gain-basis fit, the two of the fit-quality pass, the three of the gain solve, the three
-        # of the coefficient solve and the two of the gain-coefficient solve keep their accumulators in registers: no scratch
+        # of the coefficient solve, the two of the gain-coefficient solve and the three of the time-basis solve keep their accumulators in
+        # registers: no scratch
         m = re.search(r"remark:\s+(ScratchSize \[bytes/lane\]|VGPRs Spill): (\d+)", line)
         if m and int(m.group(2)) != 0:
             bad.append(f"{cur}: {m.group(1)} = {m.group(2)}")

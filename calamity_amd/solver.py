@@ -385,6 +385,37 @@ class HipFitSolver:
         _lib.check(self._lib.cal_solver_solve_gain_coeffs(self._h, C.byref(d), C.byref(r)))
         return {"nsolved": int(r.nsolved), "nsingular": int(r.nsingular)}
 
+    def solve_gain_time_coeffs(self, nsweeps, damping=0.5, ridge=1e-6, reset_gain_moments=False):
+        """``nsweeps`` damped StefCal sweeps taken jointly over the times of a fit with a gain time basis
+        (cal_solver_solve_gain_time_coeffs), ``g[t] = g0[t] + sum_l Bt[t,l] z_l`` with ``z_l = B y_l`` under a frequency basis and
+        ``y_l`` without one, the foreground model held fixed.  The solver holds ``T`` times of ``Na`` antennas as one fit (row
+        ``t Na + a``); ``y`` is ``[Na, L, W]``.  ``num``, ``den`` are ``solve_gains``' per-row sums from the OLD gains,
+        ``r[row][f] = num - den g`` in float64.  With a frequency basis (``n = L K``, index ``l K + k``),
+        ``M_{t,a} = B^T diag(den_{t,a}) B`` as ``solve_gain_coeffs`` forms it::
+
+            N_a[(l,k),(l',k')] = sum_t Bt[t,l] Bt[t,l'] M_{t,a}[k,k']          rhs_a[(l,k)] = sum_t Bt[t,l] (B^T r_{t,a})[k]
+            (N_a + ridge (tr N_a / n) I) delta_a = rhs_a                        y_a <- y_a + damping delta_a
+
+        Without one the system decouples per (antenna, channel), ``L x L`` each, everything in float64::
+
+            N_{a,f}[l,l'] = sum_t Bt[t,l] Bt[t,l'] den[t,a,f]                   rhs_{a,f}[l] = sum_t Bt[t,l] r[t,a,f]
+            (N_{a,f} + ridge (tr N_{a,f} / L) I) delta = rhs                    y[a][:][f] <- y[a][:][f] + damping delta
+
+        Every system is solved from the old gains (a Jacobi sweep) and the gains are rebuilt once per sweep.  A system with
+        ``tr <= 0`` (no unflagged cross-correlation at any time) or a bad pivot keeps the bits of its ``y`` and gains; an antenna
+        flagged at some times only IS solved and its gains there move (the time basis interpolates), like a flagged channel under a
+        frequency basis.  ``T = 1, Bt = [[1]]`` gives the bits of ``solve_gain_coeffs``; ``Bt = I, ridge = 0`` is its sweep per time;
+        ``damping = 1, ridge = 0`` lands on the exact per-antenna minimiser.  The sweeps minimise the chi-square term only (not the
+        "sum" regulariser).  ``M_{t,a}`` and ``B^T r`` are in the solver's dtype, the sums over ``t`` run in float64 in ascending
+        ``t`` and are rounded once, the Cholesky solve and the update run in float64; two calls give the same bits.
+        ``reset_gain_moments``: the optimizer's ``y`` slots start over as after ``set_optimizer``.  Needs a gain time basis
+        (``set_gain_time_basis``).  Returns ``{"nsolved", "nsingular"}``, the systems of the last sweep: antennas with a frequency
+        basis, (antenna, channel) pairs without one."""
+        d = _lib.GainTimeSolveDesc(int(nsweeps), int(bool(reset_gain_moments)), float(damping), float(ridge))
+        r = _lib.GainTimeSolveResult()
+        _lib.check(self._lib.cal_solver_solve_gain_time_coeffs(self._h, C.byref(d), C.byref(r)))
+        return {"nsolved": int(r.nsolved), "nsingular": int(r.nsingular)}
+
     def hold_slices(self, mask=None):
         """Slices that enter every later ``run`` / ``run_slices`` as already stopped (``[nslices]``, nonzero = held; ``None``: no
         slice): a loop issued in several calls keeps the slices that met the tolerance earlier as they are.  ``set_optimizer``

@@ -419,6 +419,44 @@ typedef struct cal_gain_coeff_solve_desc {
 } cal_gain_coeff_solve_desc;
 typedef struct cal_gain_coeff_solve_result { int32_t nsolved; int32_t nsingular; } cal_gain_coeff_solve_result; /* antenna rows of the last sweep */
 int cal_solver_solve_gain_coeffs(cal_solver* s, const cal_gain_coeff_solve_desc* desc, cal_gain_coeff_solve_result* result);
+/* Damped StefCal sweeps taken jointly over the times of a fit with a gain TIME basis (cal_solver_set_gain_time_basis),
+ *   g[t] = g0[t] + sum_l Bt[t,l] z_l,   z_l = B y_l with a frequency basis, y_l without one.
+ * State: nslices <= 1, nants = T Na, row t Na + a is antenna a at time t; y is [Na][L][W] complex, W = kpad with a frequency basis and
+ * fpad without.  num, den are cal_solver_solve_gains' per-row sums from the OLD gains, autocorrelations left out (the model pass, P, Q,
+ * the per-antenna sums, the all-reduce of 3 nants nfreqs doubles under a communicator or hook), r[row][f] = num - den g in double.
+ * With a frequency basis (n = L K, index l K + k), M_{t,a} = B^T diag(den_{t,a}) B exactly as cal_solver_solve_gain_coeffs forms it:
+ *   N_a[(l,k),(l',k')] = sum_t Bt[t,l] Bt[t,l'] M_{t,a}[k,k']          rhs_a[(l,k)] = sum_t Bt[t,l] (B^T r_{t,a})[k]
+ *   (N_a + ridge (tr N_a / n) I) delta_a = rhs_a                        y_a <- y_a + damping delta_a
+ * Every antenna is solved from the old gains (a Jacobi sweep); the gains are rebuilt once per sweep.  An antenna is singular when
+ * tr N_a <= 0 (no unflagged cross-correlation at any time) or a pivot is <= 0 or not finite: it keeps the bits of its y and of its
+ * gains.  An antenna flagged wholly at some times but not all IS solved, and its gains at the flagged times move: the time basis
+ * interpolates; the same holds for a flagged channel.
+ * Without a frequency basis the system decouples per (antenna, channel), L x L each, everything in double from the double planes:
+ *   N_{a,f}[l,l'] = sum_t Bt[t,l] Bt[t,l'] den[t,a,f]                   rhs_{a,f}[l] = sum_t Bt[t,l] r[t,a,f]
+ *   (N_{a,f} + ridge (tr N_{a,f} / L) I) delta = rhs                    y[a][:][f] <- y[a][:][f] + damping delta
+ * and a system with tr <= 0 or a bad pivot keeps the bits of y[a][:][f].
+ * result (may be NULL) counts the systems of the LAST sweep: antennas with a frequency basis, (antenna, channel) pairs without one.
+ * T = 1, Bt = [[1]] with a frequency basis gives the bits of cal_solver_solve_gain_coeffs on a solver without the time basis;
+ * Bt = I, ridge = 0 is its sweep per time (with a ridge they differ: the joint trace runs over all times); damping = 1, ridge = 0
+ * lands on the exact per-antenna minimiser.  The "sum" regulariser is not part of the sweeps.
+ * Precision: M_{t,a} and B^T r are in the solver's dtype; the sums over t run in double in ascending t and are rounded to the dtype once
+ * on store; the factorisation, the substitutions and the update of y run in double, the update is rounded once.  Every sum of reals has
+ * a fixed order, atomics only on the two integer counters: two calls give the same bits.  Suggested: damping = 0.5, ridge = 1e-6.
+ *   nsweeps >= 1, 0 < damping <= 1, ridge >= 0 and finite (CAL_ERR_INVALID otherwise); problem, data, coefficients, gains and a gain
+ *   time basis must be set, and reset_gain_moments needs an optimizer (CAL_ERR_STATE).
+ *   reset_gain_moments = 1: the optimizer's y slots go back to what cal_solver_set_optimizer leaves there.
+ * g0, the y snapshot of use_min, coefficients, their slots, t and iteration counts are never touched; the loop state is put back around
+ * the model pass.  The antennas are worked in chunks whose buffers (the M, N_a, the factor where it leaves LDS, or the channel scratch
+ * beyond 8 time vectors) stay under the bound of cal_solver_set_coeff_solve_scratch, never less than one antenna; every chunk of a sweep
+ * reads the old gains.  There is no slice mask: it is one joint fit. */
+typedef struct cal_gain_time_solve_desc {
+  int32_t nsweeps;              /* >= 1 */
+  int32_t reset_gain_moments;
+  double damping;               /* (0, 1] */
+  double ridge;                 /* >= 0 */
+} cal_gain_time_solve_desc;
+typedef struct cal_gain_time_solve_result { int32_t nsolved; int32_t nsingular; } cal_gain_time_solve_result; /* systems of the last sweep */
+int cal_solver_solve_gain_time_coeffs(cal_solver* s, const cal_gain_time_solve_desc* desc, cal_gain_time_solve_result* result);
 /* The optimizer's slots of a fit with a gain basis, read only (cal_solver_get_moments / cal_solver_set_moments stay refused there:
  * this is no checkpoint): ym_*, yv_* the first and second slot of y in the shape of cal_solver_get_gain_coeffs, cm_*, cv_* those of
  * the coefficients [ncoeffs], t [nslices] every slice's own count of applied updates.  Any pointer may be NULL.  CAL_ERR_STATE without

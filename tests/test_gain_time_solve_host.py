@@ -1,0 +1,393 @@
+"""Host side of the closed-form sweeps of a fit with a gain time basis (cal_solver_solve_gain_time_coeffs; no GPU): the parser flags, the
+defaults, the argument checks of the drop-in (raised before any solver exists), the declarations in the header and the bindings, and the
+fp64 NumPy restatement that the GPU tests import.
+
+The restatement (include/calamity_hip.h).  T times of Na antennas are one fit (row t Na + a), g = g0 + Bt (x) B y with y [Na, L, K]
+(B = I without a frequency basis).  num, den are the per-row sums of a per-channel sweep from the OLD gains, r = num - den g.  It is built
+from the DENSE design matrix A[(t, f), (l, k)] = Bt[t, l] B[f, k], so it knows nothing of the Kronecker shortcut of the kernels:
+
+    N_a = A^T diag(den_a) A        rhs_a = A^T r_a        (N_a + ridge (tr N_a / n) I) delta_a = rhs_a        y_a <- y_a + damping delta_a
+
+with den_a, r_a the [T F] vectors of antenna a; without a frequency basis the same per (antenna, channel) with A = Bt.  A system with
+tr N <= 0 or a failed Cholesky factorisation keeps its y and counts as singular."""
+import ctypes as C
+import functools
+import inspect
+import os
+import re
+
+import numpy as np
+import pytest
+
+from calamity_amd import _lib, cal_utils, calibration, modeling, synthetic
+from calamity_amd.uvcompat import gain4, vis3
+from test_gain_basis_solve_host import basis_sweeps, no_solver  # noqa: F401  (no_solver: the fixture)
+from test_gain_time_basis_host import TIMES_60, joint_case, product_error, recovery_case, restated_recovery
+from test_gpu_gain_solve import model_of
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BASE = ["--input_data_files", "data.uvh5"]
+FLAGS = ("gain_time_solve_sweeps", "gain_time_solve_every", "gain_time_solve_damping", "gain_time_solve_ridge")
+
+# (T, Na, F), bases, (L, K): what each pins is in the GPU test's docstring
+SHAPES = [((4, 5, 48), ("dpss", 30.0, 100.0), (3, 10)), ((6, 7, 40), ("dpss", 40.0, 100.0), (5, 9)), ((9, 6, 64), ("dpss", 120.0, 100.0), (6, 12)),
+          ((7, 5, 48), ("rand",), (6, 12)), ((15, 4, 40), ("rand",), (14, 9)), ((2, 4, 200), ("rand",), (1, 127)), ((9, 4, 40), ("rand",), (8, 16)),
+          ((14, 4, 40), ("rand",), (13, 20))]
+TIME_ONLY_SHAPES = [((4, 5, 48), 3), ((9, 5, 48), 8), ((10, 5, 129), 9)]
+
+
+def rand_basis(rows, cols, seed):
+    q, _ = np.linalg.qr(np.random.default_rng(seed).standard_normal((rows, cols)))
+    return np.ascontiguousarray(q)
+
+
+def bases_of(shape, kind, LK):
+    """(Bt [T, L], B [F, K] or None for K = None)."""
+    (T, _, F), (L, K) = shape, LK
+    if kind[0] == "dpss":
+        Bt = modeling.gain_time_dpss_basis(2458101.25 + 10.7 / 86400.0 * np.arange(T), kind[1])
+        B = np.array(modeling.gain_dpss_basis(150e6 + 400e3 * np.arange(F), kind[2]))
+    else:
+        Bt, B = rand_basis(T, L, 1), None if K is None else rand_basis(F, K, 2)
+    assert Bt.shape == (T, L) and (K is None or B.shape == (F, K)), (Bt.shape, None if B is None else B.shape)
+    return np.ascontiguousarray(Bt), B
+
+
+@functools.lru_cache(maxsize=None)
+def flagged_case(T, nants, nfreqs):
+    """``joint_case`` with channel 3 of every baseline of antenna 1 flagged at every time, every baseline of the last antenna flagged at
+    every time and every baseline of antenna 2 flagged at time 0.  Returns (joint problem, params)."""
+    big, start = joint_case(ntimes=T, nants=nants, nfreqs=nfreqs)[:2]
+    a0, a1, t = big.bl_ant0 % nants, big.bl_ant1 % nants, big.bl_ant0 // nants
+    w = big.wgts.copy()
+    w[(a0 == 1) | (a1 == 1), 3] = 0.0
+    w[(a0 == nants - 1) | (a1 == nants - 1)] = 0.0
+    w[((a0 == 2) | (a1 == 2)) & (t == 0)] = 0.0
+    big.wgts = w
+    return big, {k: np.asarray(start[k]) for k in ("g_r", "g_i", "c_r", "c_i")}
+
+
+# ---- the restatement
+def row_sums(ant0, ant1, P, Q, g):
+    num, den = np.zeros(g.shape, dtype=np.complex128), np.zeros(g.shape)
+    for b in np.where(ant0 != ant1)[0]:
+        i, j = int(ant0[b]), int(ant1[b])
+        num[i] += P[b] * g[j]
+        den[i] += Q[b] * np.abs(g[j]) ** 2
+        num[j] += np.conj(P[b]) * g[i]
+        den[j] += Q[b] * np.abs(g[i]) ** 2
+    return num, den
+
+
+def solve_or_none(N, rhs, ridge):
+    n = N.shape[0]
+    tr = np.trace(N)
+    if not tr > 0:
+        return None
+    try:
+        Lc = np.linalg.cholesky(N + ridge * (tr / n) * np.eye(n))
+    except np.linalg.LinAlgError:
+        return None
+    return np.linalg.solve(Lc.T, np.linalg.solve(Lc, rhs))
+
+
+def time_sweeps(ant0, ant1, d, m, w, g0, y, Bt, B=None, nsweeps=1, damping=0.5, ridge=1e-6):
+    """``nsweeps`` joint sweeps in fp64 on the arrays as given (d, m complex and w real ``[nbls, F]`` over all times; g0 complex
+    ``[T Na, F]``; y complex ``[Na, L, K]`` (``[Na, L, F]`` with ``B = None``); Bt real ``[T, L]``; B real ``[F, K]``).  Returns (g, y,
+    chi-square after every sweep, den of the first sweep, singular systems of the last)."""
+    T, L = Bt.shape
+    F = g0.shape[1]
+    na = g0.shape[0] // T
+    y = np.array(y, dtype=np.complex128)
+    Bf = np.eye(F) if B is None else B
+    expand = lambda y_: np.einsum("tl,alk,fk->taf", Bt, y_, Bf).reshape(T * na, F)  # noqa: E731
+    P, Q = w * d * np.conj(m), w * np.abs(m) ** 2
+    A = None if B is None else np.kron(Bt, B)  # [(t, f), (l, k)]
+    g = g0 + expand(y)
+    chisq, den0, nsingular = [], None, 0
+    for _ in range(nsweeps):
+        num, den = row_sums(ant0, ant1, P, Q, g)
+        den0 = den if den0 is None else den0
+        r = num - den * g
+        nsingular = 0
+        for a in range(na):
+            den_a, r_a = den[a::na], r[a::na]  # [T, F]
+            if B is not None:
+                delta = solve_or_none(A.T @ (den_a.reshape(-1)[:, None] * A), A.T @ r_a.reshape(-1), ridge)
+                if delta is None:
+                    nsingular += 1
+                else:
+                    y[a] += damping * delta.reshape(L, -1)
+                continue
+            for f in range(F):
+                delta = solve_or_none(Bt.T @ (den_a[:, f][:, None] * Bt), Bt.T @ r_a[:, f], ridge)
+                if delta is None:
+                    nsingular += 1
+                else:
+                    y[a, :, f] += damping * delta
+        g = g0 + expand(y)
+        chisq.append(float(np.sum(w * np.abs(d - g[ant0] * np.conj(g[ant1]) * m) ** 2)))
+    return g, y, chisq, den0, nsingular
+
+
+def restated_time(p, params, dtype, Bt, B=None, nsweeps=1, damping=0.5, ridge=1e-6):
+    """``time_sweeps`` on the inputs a solver of ``dtype`` holds (cast to it first): g0 = the gains of ``params``, y = 0."""
+    cast = lambda a: np.asarray(a).astype(dtype).astype(np.float64)  # noqa: E731
+    d_r, d_i, w = cast(p.data_r), cast(p.data_i), cast(p.wgts)
+    g0 = cast(params["g_r"]) + 1j * cast(params["g_i"])
+    Btc, Bc = cast(Bt), None if B is None else cast(B)
+    na = p.nants // Bt.shape[0]
+    y0 = np.zeros((na, Bt.shape[1], p.nfreqs if B is None else B.shape[1]), dtype=np.complex128)
+    return time_sweeps(p.bl_ant0, p.bl_ant1, d_r + 1j * d_i, model_of(p, params, dtype), w, g0, y0, Btc, Bc, nsweeps, damping, ridge)
+
+
+# ---- the inputs of the drop-in test (tests/test_gpu_gain_time_solve_dropin.py) and what the restatement reaches on them
+DROPIN_TIME_SCALE = 60.0
+
+
+@functools.lru_cache(maxsize=None)
+def dropin_time_data_set(ntimes=4):
+    """(data, sky, Bt, B): data = g_i conj(g_j) x sky with g[t] = 1 + sum_l Bt[t, l] B y_l, B the 100 ns DPSS basis on the file's channels,
+    Bt the DPSS time basis of ``DROPIN_TIME_SCALE`` seconds on its times, y seeded and scaled so that g - 1 has rms 0.1 per real part."""
+    _, sky, _ = synthetic.make_uvdata(nants=6, nfreqs=64, ntimes=ntimes)
+    B = np.array(modeling.gain_dpss_basis(np.asarray(sky.freq_array, dtype=np.float64).ravel(), 100.0))
+    Bt = modeling.gain_time_dpss_basis(np.unique(sky.time_array), DROPIN_TIME_SCALE)
+    true = cal_utils.blank_uvcal_from_uvdata(sky)
+    garr = gain4(true.gain_array)  # (Nants, Nfreqs, Ntimes, Njones) view
+    rng = np.random.default_rng(5)
+    na, nf, nt, nj = garr.shape
+    y = rng.standard_normal((na, Bt.shape[1], B.shape[1], nj)) + 1j * rng.standard_normal((na, Bt.shape[1], B.shape[1], nj))
+    dg = np.einsum("tl,fk,alkj->aftj", Bt, B, y)
+    dg *= 0.1 / np.sqrt(np.mean(dg.real ** 2))
+    garr[...] = 1.0 + dg
+    return cal_utils.apply_gains(sky, true, inverse=True), sky, Bt, B
+
+
+@functools.lru_cache(maxsize=None)
+def dropin_time_restated_ratio(ntimes=4, nsweeps=30, damping=0.5, ridge=1e-6):
+    """rms(resid) / rms(data) at unity gains and after ``nsweeps`` joint sweeps of the restatement; the model is the sky itself and the
+    weights are uniform (nothing is flagged)."""
+    uvd, sky, Bt, B = dropin_time_data_set(ntimes)
+    ants = np.asarray(sorted(set(np.asarray(uvd.ant_1_array).tolist()) | set(np.asarray(uvd.ant_2_array).tolist())))
+    index = {int(a): n for n, a in enumerate(ants)}
+    na = len(ants)
+    a0, a1, d, m = [], [], [], []
+    for t, time in enumerate(np.unique(uvd.time_array)):
+        sel = np.where(np.isclose(uvd.time_array, time, atol=1e-7, rtol=0.0))[0]
+        a0.append(t * na + np.asarray([index[int(a)] for a in np.asarray(uvd.ant_1_array)[sel]]))
+        a1.append(t * na + np.asarray([index[int(a)] for a in np.asarray(uvd.ant_2_array)[sel]]))
+        d.append(vis3(uvd.data_array)[sel, :, 0])
+        m.append(vis3(sky.data_array)[sel, :, 0])
+    a0, a1, d, m = (np.concatenate(x) for x in (a0, a1, d, m))
+    g0 = np.ones((ntimes * na, d.shape[1]), dtype=np.complex128)
+    chisq = time_sweeps(a0, a1, d, m, np.ones(d.shape), g0, np.zeros((na, Bt.shape[1], B.shape[1])), Bt, B, nsweeps, damping, ridge)[2]
+    den = float(np.sum(np.abs(d) ** 2))
+    return float(np.sqrt(np.sum(np.abs(d - m) ** 2) / den)), float(np.sqrt(chisq[-1] / den))
+
+
+# ---- flags, defaults, checks
+def test_parser_flags_and_defaults():
+    for ap in (calibration.dpss_fit_argparser(), calibration.fitting_argparser()):
+        args = ap.parse_args(BASE)
+        assert tuple(getattr(args, k) for k in FLAGS) == (0, 0, 0.5, 1e-6)
+        args = ap.parse_args(BASE + ["--gain_time_solve_sweeps", "30", "--gain_time_solve_every", "5", "--gain_time_solve_damping", "0.25",
+                                     "--gain_time_solve_ridge", "1e-4"])
+        assert tuple(getattr(args, k) for k in FLAGS) == (30, 5, 0.25, 1e-4)
+        assert isinstance(args.gain_time_solve_sweeps, int) and isinstance(args.gain_time_solve_every, int)
+
+
+def test_signature_defaults():
+    from calamity_amd.batched import SliceBatchFitter
+    from calamity_amd.solver import HipFitSolver
+
+    for fn in (calibration.calibrate_and_model_tensor, calibration.fit_gains_and_foregrounds):
+        params = inspect.signature(fn).parameters
+        assert tuple(params[k].default for k in FLAGS) == (0, 0, 0.5, 1e-6)
+    for fn in (HipFitSolver.solve_gain_time_coeffs, SliceBatchFitter.solve_gain_time_coeffs):
+        params = inspect.signature(fn).parameters
+        assert list(params)[1:] == ["nsweeps", "damping", "ridge", "reset_gain_moments"]
+        assert (params["damping"].default, params["ridge"].default, params["reset_gain_moments"].default) == (0.5, 1e-6, False)
+
+
+@pytest.mark.parametrize("bad", [dict(gain_time_solve_sweeps=-1), dict(gain_time_solve_every=-2), dict(gain_time_solve_sweeps=1.5),
+                                 dict(gain_time_solve_sweeps=1, gain_time_solve_damping=0.0), dict(gain_time_solve_every=1, gain_time_solve_damping=1.5),
+                                 dict(gain_time_solve_sweeps=1, gain_time_solve_ridge=-1e-6), dict(gain_time_solve_sweeps=1, gain_time_solve_ridge=float("nan")),
+                                 dict(gain_time_solve_every=1, gain_time_solve_ridge=float("inf"))])
+def test_bad_values_are_refused_before_any_solver_exists(bad, no_solver):  # noqa: F811
+    uvd, _, comps = synthetic.make_uvdata(nants=4, nfreqs=16, ntimes=2)
+    with pytest.raises(ValueError, match="gain_time_solve"):
+        calibration.calibrate_and_model_tensor(uvdata=uvd, fg_model_comps_dict=comps, gain_time_scale=1e6, **bad)
+    with pytest.raises(ValueError, match="gain_time_solve"):
+        calibration.fit_gains_and_foregrounds(np.ones((3, 16)), np.zeros((3, 16)), None, None, None, None, None, None, None, **bad)
+
+
+@pytest.mark.parametrize("solve", [dict(gain_time_solve_sweeps=3), dict(gain_time_solve_every=5)])
+@pytest.mark.parametrize("freq_basis", [dict(), dict(gain_max_dly=100.0)])
+def test_the_sweeps_need_a_time_basis(freq_basis, solve, no_solver):  # noqa: F811
+    uvd, _, comps = synthetic.make_uvdata(nants=4, nfreqs=16, ntimes=2)
+    with pytest.raises(ValueError, match="gain_time_basis\\s+or gain_time_scale"):
+        calibration.calibrate_and_model_tensor(uvdata=uvd, fg_model_comps_dict=comps, **freq_basis, **solve)
+    with pytest.raises(ValueError, match="gain_time_basis\\s+or gain_time_scale"):
+        calibration.fit_gains_and_foregrounds(np.ones((3, 16)), np.zeros((3, 16)), None, None, None, None, None, None, None, **solve)
+
+
+@pytest.mark.parametrize("solve", [dict(gain_time_solve_sweeps=3), dict(gain_time_solve_every=5)])
+@pytest.mark.parametrize("other", [dict(gain_basis_solve_sweeps=3), dict(gain_basis_solve_every=2), dict(gain_solve_sweeps=3), dict(gain_solve_every=2)])
+@pytest.mark.parametrize("time_basis", [dict(gain_time_scale=1e6), dict(gain_time_basis=np.ones((2, 1)))])
+def test_the_other_sweeps_are_refused_beside_them(time_basis, other, solve, no_solver):  # noqa: F811
+    uvd, _, comps = synthetic.make_uvdata(nants=4, nfreqs=16, ntimes=2)
+    with pytest.raises(ValueError):
+        calibration.calibrate_and_model_tensor(uvdata=uvd, fg_model_comps_dict=comps, gain_max_dly=100.0, **time_basis, **other, **solve)
+    # the refusals that were there before stay: the per-channel and the frequency-basis sweeps with a time basis
+    with pytest.raises(ValueError, match="gain_time_basis"):
+        calibration.calibrate_and_model_tensor(uvdata=uvd, fg_model_comps_dict=comps, gain_max_dly=100.0, **time_basis, **other)
+
+
+# ---- header, bindings
+def test_the_call_is_declared_in_the_header_and_the_bindings():
+    with open(os.path.join(ROOT, "include", "calamity_hip.h")) as f:
+        header = f.read()
+    assert re.search(r"int\s+cal_solver_solve_gain_time_coeffs\s*\(\s*cal_solver\s*\*\s*s\s*,\s*const\s+cal_gain_time_solve_desc\s*\*\s*desc\s*,\s*"
+                     r"cal_gain_time_solve_result\s*\*\s*result\s*\)\s*;", header)
+    fields = re.search(r"typedef struct cal_gain_time_solve_desc \{(.*?)\} cal_gain_time_solve_desc;", header, re.S).group(1)
+    names = ["nsweeps", "reset_gain_moments", "damping", "ridge"]
+    assert re.findall(r"(\w+)\s*;", fields) == names
+    assert [n for n, _ in _lib.GainTimeSolveDesc._fields_] == names
+    fields = re.search(r"typedef struct cal_gain_time_solve_result \{(.*?)\} cal_gain_time_solve_result;", header, re.S).group(1)
+    assert re.findall(r"(\w+)\s*;", fields) == [n for n, _ in _lib.GainTimeSolveResult._fields_] == ["nsolved", "nsingular"]
+    assert "cal_solver_solve_gain_time_coeffs" in _lib.SYMBOLS
+    assert C.sizeof(_lib.GainTimeSolveDesc) == 24  # int32, int32, double, double: no slice mask
+    assert C.sizeof(_lib.GainTimeSolveResult) == 8
+    # the arithmetic is quoted in the header, the bindings and the kernels' file
+    with open(os.path.join(ROOT, "calamity_amd", "csrc", "gain_time_solve_kernels.hpp")) as f:
+        kernels = f.read()
+    from calamity_amd.solver import HipFitSolver
+
+    for text in (header, kernels, HipFitSolver.solve_gain_time_coeffs.__doc__):
+        assert "sum_t Bt[t,l] Bt[t,l'] M_{t,a}[k,k']" in text and "sum_t Bt[t,l] Bt[t,l'] den[t,a,f]" in text
+    # the calls beside it keep their descriptions
+    assert C.sizeof(_lib.GainCoeffSolveDesc) == 32 and C.sizeof(_lib.GainSolveDesc) == 24
+
+
+# ---- the restatement itself
+def kron_sweep(p, params, Bt, B, damping=0.5, ridge=1e-6):
+    """One sweep in the Kronecker form the kernels use: N_a = sum_t kron(Bt[t] Bt[t]^T, B^T diag(den_{t,a}) B)."""
+    T, L = Bt.shape
+    K, na = B.shape[1], p.nants // T
+    d, m, w = p.data_r + 1j * p.data_i, model_of(p, params, np.float64), p.wgts
+    g = np.asarray(params["g_r"]) + 1j * np.asarray(params["g_i"])
+    num, den = row_sums(p.bl_ant0, p.bl_ant1, w * d * np.conj(m), w * np.abs(m) ** 2, g)
+    r = num - den * g
+    y = np.zeros((na, L, K), dtype=np.complex128)
+    for a in range(na):
+        N, rhs = np.zeros((L * K, L * K)), np.zeros(L * K, dtype=np.complex128)
+        for t in range(T):
+            N += np.kron(np.outer(Bt[t], Bt[t]), B.T @ (den[t * na + a][:, None] * B))
+            rhs += np.kron(Bt[t], B.T @ r[t * na + a])
+        delta = solve_or_none(N, rhs, ridge)
+        if delta is not None:
+            y[a] = damping * delta.reshape(L, K)
+    return y
+
+
+@pytest.mark.parametrize("shape,kind,LK", [SHAPES[0], SHAPES[3]])
+def test_the_dense_form_equals_the_kronecker_form(shape, kind, LK):
+    p, params = flagged_case(*shape)
+    Bt, B = bases_of(shape, kind, LK)
+    y = restated_time(p, params, np.float64, Bt, B)[1]
+    want = kron_sweep(p, params, Bt, B)
+    err = float(np.max(np.abs(y - want)) / np.max(np.abs(want)))
+    print(f"{shape} dense against Kronecker: {err:.2e}")
+    assert err <= 1e-12
+
+
+def test_an_identity_time_basis_without_ridge_is_the_sweep_per_time():
+    big, start = joint_case()[:2]  # 3 times of 7 antennas x 40 channels, nothing flagged
+    T, na = 3, big.nants // 3
+    B = np.array(modeling.gain_dpss_basis(150e6 + 400e3 * np.arange(big.nfreqs), 100.0))
+    d, m = big.data_r + 1j * big.data_i, model_of(big, start, np.float64)
+    g0 = np.asarray(start["g_r"]) + 1j * np.asarray(start["g_i"])
+    want_g, want_y = basis_sweeps(big.bl_ant0, big.bl_ant1, d, m, big.wgts, g0, np.zeros((big.nants, B.shape[1])), B, nsweeps=3, ridge=0.0)[:2]
+    g, y = restated_time(big, start, np.float64, np.eye(T), B, nsweeps=3, ridge=0.0)[:2]
+    # y[a, t, k] of the joint fit with Bt = I is y[t Na + a, k] of the batched one
+    errs = (float(np.max(np.abs(g - want_g)) / np.max(np.abs(want_g))),
+            float(np.max(np.abs(y.transpose(1, 0, 2).reshape(T * na, -1) - want_y)) / np.max(np.abs(want_y))))
+    print(f"identity time basis against the sweep per time: g {errs[0]:.2e}, y {errs[1]:.2e}")
+    assert max(errs) <= 1e-12
+
+
+def test_one_time_is_the_frequency_basis_sweep_ridge_included():
+    big, start = joint_case(ntimes=1)[:2]
+    B = np.array(modeling.gain_dpss_basis(150e6 + 400e3 * np.arange(big.nfreqs), 100.0))
+    d, m = big.data_r + 1j * big.data_i, model_of(big, start, np.float64)
+    g0 = np.asarray(start["g_r"]) + 1j * np.asarray(start["g_i"])
+    want_g, want_y = basis_sweeps(big.bl_ant0, big.bl_ant1, d, m, big.wgts, g0, np.zeros((big.nants, B.shape[1])), B, nsweeps=3, ridge=1e-3)[:2]
+    g, y = restated_time(big, start, np.float64, np.ones((1, 1)), B, nsweeps=3, ridge=1e-3)[:2]
+    assert np.max(np.abs(g - want_g)) <= 1e-12 * np.max(np.abs(want_g)) and np.max(np.abs(y[:, 0] - want_y)) <= 1e-12 * np.max(np.abs(want_y))
+
+
+@pytest.mark.parametrize("with_freq", [True, False])
+def test_a_full_undamped_step_lands_on_the_per_antenna_minimiser(with_freq):
+    """damping = 1, ridge = 0: the gradient of the chi-square with respect to y_a vanishes at the new y_a with the others at their old gains."""
+    shape, kind, LK = SHAPES[1]
+    p, params = flagged_case(*shape)
+    Bt, B = bases_of(shape, kind, LK)
+    B = B if with_freq else None
+    T, na = Bt.shape[0], p.nants // Bt.shape[0]
+    g_new = restated_time(p, params, np.float64, Bt, B, damping=1.0, ridge=0.0)[0]
+    g_old = np.asarray(params["g_r"]) + 1j * np.asarray(params["g_i"])
+    d, m, w = p.data_r + 1j * p.data_i, model_of(p, params, np.float64), p.wgts
+    a = 2
+    g = g_old.copy()
+    g[a::na] = g_new[a::na]
+    num, den = row_sums(p.bl_ant0, p.bl_ant1, w * d * np.conj(m), w * np.abs(m) ** 2, g_old)
+    Bf = np.eye(p.nfreqs) if B is None else B
+    grad = np.einsum("tl,tf,fk->lk", Bt, (num - den * g)[a::na], Bf)
+    scale = np.max(np.abs(np.einsum("tl,tf,fk->lk", Bt, num[a::na], Bf)))
+    assert np.max(np.abs(grad)) <= 1e-9 * scale
+
+
+def chisq_at(p, params, g):
+    d, m = p.data_r + 1j * p.data_i, model_of(p, params, np.float64)
+    return float(np.sum(p.wgts * np.abs(d - g[p.bl_ant0] * np.conj(g[p.bl_ant1]) * m) ** 2))
+
+
+@pytest.mark.parametrize("shape,kind,LK", SHAPES + [(s, ("rand",), (L, None)) for s, L in TIME_ONLY_SHAPES])
+def test_the_chi_square_never_rises_over_ten_half_damped_sweeps(shape, kind, LK):
+    p, params = flagged_case(*shape)
+    T, na, F = shape
+    Bt, B = bases_of(shape, kind, LK)
+    g, y, chisq, den, nsingular = restated_time(p, params, np.float64, Bt, B, nsweeps=10)
+    g_start = np.asarray(params["g_r"]) + 1j * np.asarray(params["g_i"])
+    losses = np.asarray([chisq_at(p, params, g_start)] + chisq)
+    print(f"{shape} L, K = {LK}: chi-square {losses[0]:.4e} -> {losses[-1]:.4e}, largest step up {np.max(np.diff(losses)) / losses[0]:.2e} of the start")
+    assert np.all(np.diff(losses) <= 0.0)
+    # the last antenna has no data at any time; channel 3 of antenna 1 has none; antenna 2 has none at time 0 but is solved
+    assert not np.any(den[na - 1 :: na]) and not np.any(y[na - 1]) and np.array_equal(g[na - 1 :: na], g_start[na - 1 :: na])
+    assert not np.any(den[2]) and np.all(g[2] != g_start[2])
+    assert not np.any(den[1::na, 3])
+    if B is not None:
+        assert nsingular == 1 and np.all(g[1::na, 3] != g_start[1::na, 3])  # the frequency basis interpolates across the channel
+    else:
+        assert nsingular == F + 1 and np.array_equal(g[1::na, 3], g_start[1::na, 3]) and not np.any(y[1, :, 3])
+
+
+def test_thirty_sweeps_recover_smooth_gains_like_the_descent_fit():
+    case = recovery_case()
+    big, start = case["big"], case["start"]
+    g = {}
+    for label, Bt in (("joint", case["Bt"]), ("per time", np.eye(case["Bt"].shape[0]))):
+        g[label] = restated_time(big, start, np.float64, Bt, case["Bf"], nsweeps=30)[0]
+    errs = {k: product_error(case, v) for k, v in g.items()}
+    descent = restated_recovery(case)[1]
+    print(f"gain-product error: 30 joint sweeps {errs['joint']:.3f}, 300 Adam steps {descent:.3f}, 30 per-time sweeps {errs['per time']:.3f}")
+    assert errs["joint"] <= 1.05 * descent
+    assert errs["joint"] <= 0.8 * errs["per time"]
+
+
+def test_thirty_sweeps_on_the_inputs_of_the_drop_in_test():
+    """The ratio the drop-in test bounds (3 x this one): recorded here, and at most 1/30 of the ratio at unity gains."""
+    r0, r1 = dropin_time_restated_ratio()
+    print(f"rms(resid) / rms(data) {r0:.3e} at unity, {r1:.3e} after 30 joint sweeps of the restatement: 1/{r0 / r1:.0f}")
+    assert r0 > 0.1
+    assert r1 <= r0 / 30.0
