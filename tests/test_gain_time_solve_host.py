@@ -34,6 +34,7 @@ SHAPES = [((4, 5, 48), ("dpss", 30.0, 100.0), (3, 10)), ((6, 7, 40), ("dpss", 40
           ((7, 5, 48), ("rand",), (6, 12)), ((15, 4, 40), ("rand",), (14, 9)), ((2, 4, 200), ("rand",), (1, 127)), ((9, 4, 40), ("rand",), (8, 16)),
           ((14, 4, 40), ("rand",), (13, 20))]
 TIME_ONLY_SHAPES = [((4, 5, 48), 3), ((9, 5, 48), 8), ((10, 5, 129), 9)]
+TIME_ONLY_SHAPES += [((3, 5, 48), 1), ((4, 5, 48), 2)]  # the unrolled loops of the register instance cut at their first and second trip (appended: the case ids above keep their numbers)
 
 
 def rand_basis(rows, cols, seed):

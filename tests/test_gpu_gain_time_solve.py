@@ -9,7 +9,8 @@ bound for the 2 ... 3 x that sequential device sums cost.
 What the shapes pin ((T, Na, F); L, K, n = L K): (4, 5, 48) 3, 10, 30: kpad != K, one partial tile; (6, 7, 40) 5, 9, 45; (9, 6, 64) 6, 12,
 72: n past one 64-block; (7, 5, 48) 6, 12, 72; (15, 4, 40) 14, 9, 126: the factor in LDS, two tiles of time vectors; (2, 4, 200) 1, 127,
 127: the last n in LDS; (9, 4, 40) 8, 16, 128: the first n in scratch; (14, 4, 40) 13, 20, 260: past 256, T and L no multiples of 8.
-Without a frequency basis: L = 3 and 8 in registers, L = 9 in scratch.  In every problem the last antenna is flagged wholly (the singular
+Without a frequency basis: L = 1, 2, 3 and 8 in registers (L = 1 and 2 cut the unrolled loops at their first and second trip), L = 9 in
+scratch.  In every problem the last antenna is flagged wholly (the singular
 system), antenna 2 at time 0 (it is solved and moves there) and channel 3 of antenna 1 (it moves with a frequency basis only)."""
 import functools
 
