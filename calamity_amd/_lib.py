@@ -80,6 +80,17 @@ class GainSolveDesc(C.Structure):
     _fields_ = [("nsweeps", C.c_int32), ("reset_gain_moments", C.c_int32), ("damping", C.c_double), ("slice_mask", C.c_void_p)]
 
 
+class RobustDesc(C.Structure):
+    """cal_robust_desc: kind (ROBUST_KINDS), threshold k in sigma, slice_mask [nslices] bytes or NULL.  With w0 the weights of set_data:
+    e = w0 |d - g_i conj(g_j) (A c)|^2, med_b the ((n_b + 1) // 2)-th smallest e over the row's samples with w0 > 0, scale_b = med_b / ln 2,
+    z2 = e / scale_b; huber psi = 1 if z2 <= k^2 else k / sqrt(z2), cauchy psi = 1 / (1 + z2 / k^2), clip psi = 1 if z2 <= k^2 else 0;
+    w = w0 psi (include/calamity_hip.h: cal_solver_robust_weights)."""
+    _fields_ = [("kind", C.c_int), ("threshold", C.c_double), ("slice_mask", C.c_void_p)]
+
+
+ROBUST_KINDS = {"none": 0, "huber": 1, "cauchy": 2, "clip": 3}
+
+
 class CoeffSolveDesc(C.Structure):
     _fields_ = [("niters", C.c_int32), ("reset_coeff_moments", C.c_int32), ("damping", C.c_double), ("ridge", C.c_double), ("slice_mask", C.c_void_p)]
 
@@ -154,6 +165,8 @@ SYMBOLS = {
     "cal_solver_fit_quality": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     "cal_solver_solve_gains": (C.c_int, [_P, C.POINTER(GainSolveDesc)]),
     "cal_solver_hold_slices": (C.c_int, [_P, _P]),
+    "cal_solver_robust_weights": (C.c_int, [_P, C.POINTER(RobustDesc), _P, _P]),
+    "cal_solver_get_weights": (C.c_int, [_P, _P, C.c_int]),
     "cal_solver_solve_coeffs": (C.c_int, [_P, C.POINTER(CoeffSolveDesc), C.POINTER(CoeffSolveResult)]),
     "cal_solver_set_coeff_solve_scratch": (C.c_int, [_P, C.c_int64]),
     "cal_solver_solve_gain_coeffs": (C.c_int, [_P, C.POINTER(GainCoeffSolveDesc), C.POINTER(GainCoeffSolveResult)]),

@@ -273,6 +273,29 @@ class SliceBatchFitter:
             res["wsum_bl"][self.rows[r]] = o["wsum_bl"]
         return res
 
+    def robust_weights(self, kind="huber", threshold=3.0, slice_mask=None):
+        """``HipFitSolver.robust_weights`` on every worker (``slice_mask``: one entry per slice of the batch; one entry for a ``joint``
+        fitter): each worker reweights its own baseline rows, nothing is exchanged.  ``scale_bl``, ``ndown_bl`` ``[nt * nbls]`` put
+        back into the global slice-major row order like the rows of ``model()``."""
+        outs = self._each(lambda r, s: s.robust_weights(kind=kind, threshold=threshold, slice_mask=slice_mask))
+        if self.nworkers == 1:
+            return outs[0]
+        res = dict(scale_bl=np.empty(self.nbls, dtype=np.float64), ndown_bl=np.empty(self.nbls, dtype=np.float64))
+        for r, o in enumerate(outs):
+            res["scale_bl"][self.rows[r]] = o["scale_bl"]
+            res["ndown_bl"][self.rows[r]] = o["ndown_bl"]
+        return res
+
+    def get_weights(self, which=0):
+        """``HipFitSolver.get_weights`` of every worker, the rows put back into the global slice-major order."""
+        outs = self._each(lambda r, s: s.get_weights(which))
+        if self.nworkers == 1:
+            return outs[0]
+        w = np.empty((self.nbls, self.nfreqs), dtype=self.dtype)
+        for r, o in enumerate(outs):
+            w[self.rows[r]] = o
+        return w
+
     def solve_gains(self, nsweeps, damping=0.5, slice_mask=None, reset_gain_moments=False):
         """``HipFitSolver.solve_gains`` on every worker (``slice_mask``: one entry per slice of the batch; one entry for a ``joint``
         fitter).  With several workers each sweep sums the three antenna planes of the workers' baselines in one exchange, and every

@@ -653,6 +653,10 @@ def fit_gains_and_foregrounds(
     gain_time_solve_every=0,
     gain_time_solve_damping=0.5,
     gain_time_solve_ridge=1e-6,
+    robust_every=0,
+    robust_rounds=0,
+    robust_kind="huber",
+    robust_threshold=3.0,
     **opt_kwargs,
 ):
     """Run the optimization loop that fits gains and foreground coefficients -- calibration.py:447-738.
@@ -673,8 +677,12 @@ def fit_gains_and_foregrounds(
     of a fit with a ``gain_basis``, see ``calibrate_and_model_tensor``.  ``gain_time_solve_sweeps`` / ``gain_time_solve_every`` /
     ``gain_time_solve_damping`` / ``gain_time_solve_ridge`` are checked like theirs, but belong to the joint fit over the times of
     ``calibrate_and_model_tensor(gain_time_basis=... / gain_time_scale=...)``: this function fits one time, so switching them on raises
-    ``ValueError``.
+    ``ValueError``.  ``robust_every`` / ``robust_rounds`` / ``robust_kind`` / ``robust_threshold``: iteratively reweighted least squares
+    between chunks of the recorded loop, see ``calibrate_and_model_tensor``; here ``fit_history["robust"]`` holds the last reweight in
+    solver units and row order, ``{"rounds": n, "ndown_bl": [nbls], "scale_bl": [nbls]}`` (``HipFitSolver.robust_weights``).
     """
+    _check_robust(robust_every, robust_rounds, robust_kind, robust_threshold, use_min,
+                  (gain_solve_every, gain_basis_solve_every, gain_time_solve_every))
     _check_gain_solve(gain_solve_sweeps, gain_solve_every, gain_solve_damping, gain_basis is not None)
     _check_coeff_solve(coeff_solve_rounds, coeff_solve_ridge, freeze_model)
     _check_gain_basis_solve(gain_basis_solve_sweeps, gain_basis_solve_every, gain_basis_solve_damping, gain_basis_solve_ridge,
@@ -733,20 +741,28 @@ def fit_gains_and_foregrounds(
     echo(f"{datetime.datetime.now()} Building Computational Graph...\n", verbose=verbose)
     solver.run(1, record=False, freeze_model=freeze_model)  # the unrecorded step of calibration.py:693
     echo(f"{datetime.datetime.now()} Performing Gradient Descent...\n", verbose=verbose)
-    if every > 0:
+    robust = None
+    if robust_every > 0:
+        robust = {"rounds": 0, "ndown_bl": np.zeros(prob.nbls), "scale_bl": np.zeros(prob.nbls)}
+    if every > 0 or robust_every > 0:
         # the recorded loop in chunks (the solver's loop state -- step count, previous and lowest loss -- persists from run to run), a
-        # gain solve between two chunks while the loop goes on
+        # gain solve between two chunks while the loop goes on; with robust_every the weights are recomputed first (_check_robust: one
+        # chunk length)
         losses, stopped = np.zeros(0), False
         while len(losses) < maxsteps and not stopped:
-            n = min(every, maxsteps - len(losses))
+            n = min(every or robust_every, maxsteps - len(losses))
             part, stopped, _ = solver.run(n, record=True, tol=tol, use_min=use_min, freeze_model=freeze_model)
             losses = np.concatenate([losses, part])
             if len(part) < n:
                 break
             if not stopped and len(losses) < maxsteps:
-                if coeff_solve_rounds > 0:
-                    nsingular = solver.solve_coeffs(ridge=coeff_solve_ridge, reset_coeff_moments=True)["nsingular"]
-                gb_singular = sweep(max(1, n_sweeps), reset_gain_moments=True)
+                if robust is not None and (robust_rounds == 0 or robust["rounds"] < robust_rounds):
+                    rw = solver.robust_weights(kind=robust_kind, threshold=robust_threshold)
+                    robust = {"rounds": robust["rounds"] + 1, "ndown_bl": rw["ndown_bl"], "scale_bl": rw["scale_bl"]}
+                if every > 0:
+                    if coeff_solve_rounds > 0:
+                        nsingular = solver.solve_coeffs(ridge=coeff_solve_ridge, reset_coeff_moments=True)["nsingular"]
+                    gb_singular = sweep(max(1, n_sweeps), reset_gain_moments=True)
     else:
         losses, stopped, _ = solver.run(maxsteps, record=True, tol=tol, use_min=use_min, freeze_model=freeze_model)
     fit_history["loss"] = [dtype.type(l) for l in losses]
@@ -754,6 +770,8 @@ def fit_gains_and_foregrounds(
         fit_history["coeff_solve_singular"] = int(nsingular)
     if gain_basis_solve_sweeps or gain_basis_solve_every:
         fit_history["gain_basis_solve_singular"] = int(gb_singular or 0)
+    if robust is not None:
+        fit_history["robust"] = robust
     if stopped:
         echo(f"Tolerance thresshold met with delta of {np.abs(losses[-1] - losses[-2]):.2e}. Terminating...\n ", verbose=verbose)
     g_r_opt, g_i_opt, c_r, c_i = solver.get_params(which=1 if (use_min and len(losses) > 0) else 0)
@@ -831,6 +849,37 @@ def _check_gain_time_solve(sweeps, every, damping, ridge, time_basis_given, basi
     if basis_solve_on or gain_solve_on:
         raise ValueError("gain_time_solve_sweeps / gain_time_solve_every are the sweeps of a fit with a gain time basis: they cannot be combined "
                          "with gain_basis_solve_sweeps / gain_basis_solve_every or gain_solve_sweeps / gain_solve_every")
+
+
+def _check_robust(every, rounds, kind, threshold, use_min, solve_everys=()):
+    """The arguments of the robust reweighting (ValueError before any device work); ``solve_everys``: the chunk lengths of the
+    closed-form sweeps that share the loop's gaps."""
+    for v in (every, rounds):
+        if isinstance(v, bool) or int(v) != v or v < 0:
+            raise ValueError(f"robust_every and robust_rounds must be non-negative integers, got {every!r} and {rounds!r}")
+    if kind not in ("huber", "cauchy", "clip"):
+        raise ValueError(f"robust_kind must be 'huber', 'cauchy' or 'clip', got {kind!r}")
+    if not (np.isfinite(float(threshold)) and float(threshold) > 0.0):
+        raise ValueError(f"robust_threshold must be finite and > 0 (it is in sigma), got {threshold!r}")
+    if not every:
+        return
+    if use_min:
+        raise ValueError("robust_every rewrites the weights between chunks of the loop: losses under different weights are not comparable, so "
+                         "use_min (the minimum over them) cannot be combined with it")
+    for other in solve_everys:
+        if other and other != every:
+            raise ValueError(f"robust_every={every} and the closed-form sweeps' chunk length {other} (gain_solve_every / gain_basis_solve_every / "
+                             "gain_time_solve_every) share the gaps of one chunked loop: give them the same value")
+
+
+def robust_history(rounds, ndown_bl, scale_bl, rms, prob, ant_numbers):
+    """One slice's ``fit_history[...]["robust"]``: ``{"rounds": n, "downweighted": {(ant0, ant1): count}, "scale": {(ant0, ant1):
+    rms^2 scale_b}}`` with antenna NUMBERS, one entry per baseline row of ``prob``, from the last reweight of the slice
+    (``HipFitSolver.robust_weights``; the scale in the data's units)."""
+    ants = np.asarray(ant_numbers)
+    keys = [(int(ants[i]), int(ants[j])) for i, j in zip(prob.bl_ant0, prob.bl_ant1)]
+    return {"rounds": int(rounds), "downweighted": {k: int(v) for k, v in zip(keys, ndown_bl)},
+            "scale": {k: float(rms) ** 2 * float(v) for k, v in zip(keys, scale_bl)}}
 
 
 def _check_coeff_solve(rounds, ridge, freeze_model):
@@ -978,6 +1027,10 @@ def calibrate_and_model_tensor(
     gain_time_solve_every=0,
     gain_time_solve_damping=0.5,
     gain_time_solve_ridge=1e-6,
+    robust_every=0,
+    robust_rounds=0,
+    robust_kind="huber",
+    robust_threshold=3.0,
     **opt_kwargs,
 ):
     """Simultaneous calibration and foreground fitting -- calibration.py:963-1331, same arguments, defaults and
@@ -1093,6 +1146,21 @@ def calibrate_and_model_tensor(
       chi-square term only.  ``fit_history[polnum][time_index]["gain_time_solve_singular"]`` (present only with the feature on): the
       systems the last sweep left alone (antennas with a frequency basis, (antenna, channel) pairs without one).
     * ``layout``: "shared" (default; baselines alias the distinct basis blocks) or "stream" (every baseline owns its tiles).
+    * ``robust_every`` / ``robust_rounds`` / ``robust_kind`` / ``robust_threshold`` (defaults 0, 0, ``"huber"``, 3.0: a plain weighted
+      chi-square, no call changes by a bit and no new kernel is launched): iteratively reweighted least squares against outliers that
+      escaped the flags.  ``robust_every=K``: the recorded loop is issued in chunks of K steps (the machinery of ``gain_solve_every``,
+      held slices included); between two chunks the weights of the slices whose loop has not ended are recomputed from the residual at
+      the current parameters (``HipFitSolver.robust_weights``), at most ``robust_rounds`` times (0: after every chunk).  With ``w0`` the
+      slice's weights as tensorized, ``e = w0 |d - g_i conj(g_j) (A c)|^2``, ``med_b`` the lower median of ``e`` over the unflagged
+      channels of baseline ``b``, ``scale_b = med_b / ln 2``, ``z2 = e / scale_b`` and ``k = robust_threshold`` (in sigma):
+      ``huber: psi = 1 if z2 <= k^2 else k / sqrt(z2)``, ``cauchy: psi = 1 / (1 + z2 / k^2)``, ``clip: psi = 1 if z2 <= k^2 else 0``,
+      ``w = w0 psi``.  Every reweight starts from ``w0``; the weights are not renormalised, so the losses of different chunks are
+      under different weights -- ``use_min`` together with ``robust_every`` raises ``ValueError``.  Together with ``gain_solve_every`` /
+      ``gain_basis_solve_every`` / ``gain_time_solve_every`` both use ONE chunk length (``ValueError`` if they differ), and in the gap
+      the reweight comes first, then the coefficient solve and the sweeps.  A baseline that is bad at every channel is not caught (its
+      own median scales it): that is what ``fit_quality`` reports.  ``fit_history[pol][t]["robust"] = {"rounds": n, "downweighted":
+      {(ant0, ant1): count}, "scale": {(ant0, ant1): rms^2 scale_b}}`` from the slice's last reweight.  ``fit_quality=True`` then
+      reports under the robust weights.  The model, residual and flag outputs are computed as always: no sample is flagged.
     * ``parallel_fits`` (default 1): with ``batch_slices=False``, fits that many slices concurrently, each on its own
       solver and HIP stream.
     (Nothing here is steered by environment variables: layout, devices and concurrency are arguments.)"""
@@ -1106,6 +1174,8 @@ def calibrate_and_model_tensor(
     _check_gain_time_solve(gain_time_solve_sweeps, gain_time_solve_every, gain_time_solve_damping, gain_time_solve_ridge,
                            gain_time_basis is not None or gain_time_scale is not None,
                            bool(gain_basis_solve_sweeps or gain_basis_solve_every), bool(gain_solve_sweeps or gain_solve_every))
+    _check_robust(robust_every, robust_rounds, robust_kind, robust_threshold, use_min,
+                  (gain_solve_every, gain_basis_solve_every, gain_time_solve_every))
     if gain_max_dly is not None:
         gain_basis = modeling.gain_dpss_basis(np.asarray(uvdata.freq_array, dtype=np.float64).ravel(), gain_max_dly)
     if gain_time_basis is not None and gain_time_scale is not None:
@@ -1199,6 +1269,7 @@ def calibrate_and_model_tensor(
             gain_solve=(gain_solve_sweeps, gain_solve_every, gain_solve_damping), coeff_solve=(coeff_solve_rounds, coeff_solve_ridge),
             gain_basis_solve=(gain_basis_solve_sweeps, gain_basis_solve_every, gain_basis_solve_damping, gain_basis_solve_ridge),
             gain_time_solve=(gain_time_solve_sweeps, gain_time_solve_every, gain_time_solve_damping, gain_time_solve_ridge),
+            robust=(robust_every, robust_rounds, robust_kind, robust_threshold),
         )
         return model, resid, gains, fit_history  # (every slice left _fit_slices_batched in its final state)
     assert gain_time_basis is None, "a gain time basis must not reach the loop over single times"
@@ -1264,8 +1335,12 @@ def calibrate_and_model_tensor(
                 gain_basis_solve_every=gain_basis_solve_every, gain_basis_solve_damping=gain_basis_solve_damping,
                 gain_basis_solve_ridge=gain_basis_solve_ridge, gain_time_solve_sweeps=gain_time_solve_sweeps,
                 gain_time_solve_every=gain_time_solve_every, gain_time_solve_damping=gain_time_solve_damping,
-                gain_time_solve_ridge=gain_time_solve_ridge, **opt_kwargs,
+                gain_time_solve_ridge=gain_time_solve_ridge, robust_every=robust_every, robust_rounds=robust_rounds,
+                robust_kind=robust_kind, robust_threshold=robust_threshold, **opt_kwargs,
             )
+            if "robust" in hist:  # (solver units and row order -> the data's units, keyed by antenna numbers)
+                rb = hist["robust"]
+                hist["robust"] = robust_history(rb["rounds"], rb["ndown_bl"], rb["scale_bl"], rmsdata, prob, gains.ant_array)
             # yield_fg_model_array x 2 + insert_model_into_uvdata_tensor (calibration.py:1271-1292) without the
             # nants x nants cubes: one A c pass for both components, rows written straight back
             solver.set_params(c_r=coeffs_from_chunks(prob, fg_r), c_i=coeffs_from_chunks(prob, fg_i))
@@ -1496,7 +1571,7 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
                         profile_log_dir, model_regularization, verbose, max_batch, devices, layout, opt_kwargs, correct_model=True,
                         correct_resid=False, device_split=None, gain_basis=None, gain_time_basis=None, fit_quality=False,
                         gain_solve=(0, 0, 0.5), coeff_solve=(0, 1e-6), gain_basis_solve=(0, 0, 0.5, 1e-6),
-                        gain_time_solve=(0, 0, 0.5, 1e-6)):
+                        gain_time_solve=(0, 0, 0.5, 1e-6), robust=(0, 0, "huber", 3.0)):
     """The pol x time loop of calibration.py:1160-1331 with the fits of all unskipped slices issued as batches: per slice
     exactly the host-side steps of the loop body (skip test :1173-1177, rms scale :1178-1182, tensorize :1184-1233, write-back
     :1271-1300, post-hoc renormalisation :1311-1319, residual and calibration state of the outputs :1322-1331), the gradient
@@ -1506,7 +1581,8 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
     ``gain_solve``: (gain_solve_sweeps, gain_solve_every, gain_solve_damping), ``coeff_solve``: (coeff_solve_rounds, coeff_solve_ridge) of
     calibrate_and_model_tensor, ``gain_basis_solve``: its (gain_basis_solve_sweeps, _every, _damping, _ridge), which stand in for
     ``gain_solve`` on a fit with a frequency gain basis, ``gain_time_solve``: its (gain_time_solve_sweeps, _every, _damping, _ridge), which
-    stand in for them on the joint fit of a gain time basis."""
+    stand in for them on the joint fit of a gain time basis, ``robust``: its (robust_every, robust_rounds, robust_kind, robust_threshold)."""
+    rb_every, rb_rounds, rb_kind, rb_threshold = robust
     gs_sweeps, gs_every, gs_damping = gain_solve
     cs_rounds, cs_ridge = coeff_solve
     gbs_on = bool(gain_basis_solve[0] or gain_basis_solve[1])
@@ -1646,13 +1722,17 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
                 json.dump(dict(n_profile_steps=n_profile_steps, slices=nt, fused_basis_kernel=fitter.timing_get()), f)
             fitter.timing_enable(False)
         fitter.run_slices(1, record=False, freeze_model=freeze_model)  # the unrecorded step of calibration.py:693
-        if gs_every > 0:
+        robust_out = None
+        if rb_every > 0:  # per loop the reweights it took part in; per baseline row what its last one reported
+            robust_out = dict(rounds=np.zeros(1 if joint else nt, dtype=np.int64), ndown_bl=np.zeros(nt * prob.nbls), scale_bl=np.zeros(nt * prob.nbls))
+        if gs_every > 0 or rb_every > 0:
             # the recorded loop in chunks (every slice's loop state persists from run to run); a slice whose loop has ended is held
-            # in the chunks that follow, as one call would leave it, and takes no part in the gain solves between the chunks
+            # in the chunks that follow, as one call would leave it, and takes no part in the reweighting and the gain solves between
+            # the chunks (_check_robust: the two share one chunk length)
             nl = 1 if joint else nt  # loops: a joint fit has one
             parts, over, nupd, issued = [[] for _ in range(nl)], np.zeros(nl, dtype=bool), np.zeros(nl, dtype=np.int64), 0
             while issued < maxsteps and not np.all(over):
-                n = min(gs_every, maxsteps - issued)
+                n = min(gs_every or rb_every, maxsteps - issued)
                 for t, (part, stopped, nu) in enumerate(fitter.run_slices(n, record=True, tol=tol, use_min=use_min, freeze_model=freeze_model)):
                     if not over[t]:
                         parts[t].append(part)
@@ -1661,9 +1741,18 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
                 issued += n
                 if issued < maxsteps and not np.all(over):
                     fitter.hold_slices(over)
-                    if cs_rounds > 0:
-                        nsingular = fitter.solve_coeffs(ridge=cs_ridge, slice_mask=~over, reset_coeff_moments=True)["nsingular"]
-                    gb_singular = sweep(max(1, gs_sweeps), slice_mask=~over, reset_gain_moments=True)
+                    if robust_out is not None:
+                        todo_rb = ~over if rb_rounds == 0 else ~over & (robust_out["rounds"] < rb_rounds)
+                        if np.any(todo_rb):
+                            rw = fitter.robust_weights(kind=rb_kind, threshold=rb_threshold, slice_mask=todo_rb)
+                            rows_rb = np.repeat(todo_rb, len(rw["scale_bl"]) // nl)  # (a joint fit: one loop over all the rows)
+                            robust_out["ndown_bl"][rows_rb] = rw["ndown_bl"][rows_rb]
+                            robust_out["scale_bl"][rows_rb] = rw["scale_bl"][rows_rb]
+                            robust_out["rounds"] += todo_rb
+                    if gs_every > 0:
+                        if cs_rounds > 0:
+                            nsingular = fitter.solve_coeffs(ridge=cs_ridge, slice_mask=~over, reset_coeff_moments=True)["nsingular"]
+                        gb_singular = sweep(max(1, gs_sweeps), slice_mask=~over, reset_gain_moments=True)
             fitter.hold_slices(None)
             results = [(np.concatenate(parts[t]), bool(over[t]), int(nupd[t])) for t in range(nl)]
         else:
@@ -1689,7 +1778,7 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
         # at the reported parameters (every slice's own minimum with use_min), on the data and weights the fit used
         quality = fitter.fit_quality(gm_r, gm_i) if fit_quality else None
         echo(f"{datetime.datetime.now()} ... fitted.\n", verbose=verbose)
-        return dict(results=results, m_r=m_r, m_i=m_i, gm_r=gm_r, gm_i=gm_i, quality=quality, nsingular=nsingular,
+        return dict(results=results, m_r=m_r, m_i=m_i, gm_r=gm_r, gm_i=gm_i, quality=quality, nsingular=nsingular, robust=robust_out,
                     gb_singular=int(gb_singular or 0) if gbs_on else None, gt_singular=int(gb_singular or 0) if gts_on else None)
 
     def post(batch, out):
@@ -1704,6 +1793,10 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
                 fit_history[sl["polnum"]][sl["time_index"]]["gain_basis_solve_singular"] = int(out["gb_singular"])
             if out.get("gt_singular") is not None:
                 fit_history[sl["polnum"]][sl["time_index"]]["gain_time_solve_singular"] = int(out["gt_singular"])
+            if out.get("robust") is not None:
+                rb = out["robust"]
+                fit_history[sl["polnum"]][sl["time_index"]]["robust"] = robust_history(rb["rounds"][0 if joint else t],
+                                                                                      rb["ndown_bl"][rows], rb["scale_bl"][rows], sl["rmsdata"], prob, gains.ant_array)
             if out.get("quality") is not None:  # (before the post-hoc renormalisation, which leaves g_i conj(g_j) m as it is)
                 q = out["quality"]
                 insert_fit_quality(gains, fit_history[sl["polnum"]][sl["time_index"]], sl["time"], sl["pol"],
@@ -2169,6 +2262,13 @@ def fitting_argparser():
                     help="damping of a joint sweep, in (0, 1]: y <- y + damping x the closed-form step; default 0.5")
     sp.add_argument("--gain_time_solve_ridge", type=float, default=1e-6,
                     help="ridge of a joint sweep, as a fraction of the mean diagonal of a system's normal matrix; default 1e-6")
+    sp.add_argument("--robust_every", type=int, default=0,
+                    help="downweight outliers: recompute the weights from the residual (iteratively reweighted least squares, scale from each "
+                         "baseline's median) after every this many recorded descent steps; with a --gain*_solve_every flag both must be equal; "
+                         "default 0: never")
+    sp.add_argument("--robust_rounds", type=int, default=0, help="with --robust_every: reweight at most this many times; default 0: after every chunk")
+    sp.add_argument("--robust_kind", type=str, default="huber", help="weight function of --robust_every: huber, cauchy or clip; default huber")
+    sp.add_argument("--robust_threshold", type=float, default=3.0, help="threshold of the weight function in sigma; default 3")
     return ap
 
 

@@ -26,6 +26,7 @@
 #include "gain_basis_kernels.hpp"
 #include "gain_time_basis_kernels.hpp"
 #include "fit_quality_kernels.hpp"
+#include "robust_weight_kernels.hpp"
 #include "gain_solve_kernels.hpp"
 #include "coeff_solve_kernels.hpp"
 #include "gain_basis_solve_kernels.hpp"
@@ -157,6 +158,8 @@ struct cal_solver {
   virtual int run(const cal_run_desc* r, double* losses_out, cal_run_result* res, bool per_slice) = 0;
   virtual int model(void* mr, void* mi, bool with_gains) = 0;
   virtual int fit_quality(const void* g_r, const void* g_i, double* chisq_ant, double* wsum_ant, double* chisq_bl, double* wsum_bl) = 0;
+  virtual int robust_weights(const cal_robust_desc* d, double* scale_bl, double* ndown_bl) = 0;
+  virtual int get_weights(void* out, int which) = 0;
   virtual int solve_gains(const cal_gain_solve_desc* d) = 0;
   virtual int hold_slices(const uint8_t* mask) = 0;
   virtual int solve_coeffs(const cal_coeff_solve_desc* d, cal_coeff_solve_result* res) = 0;
@@ -225,6 +228,8 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
   DevBuf gts_m, gts_n, gts_rhsa, gts_d, gts_rhs, gts_cnt;
   std::vector<uint8_t> held;                   // hold_slices: [nslices], 1 = the slice enters every later run as stopped (empty: none)
   DevBuf fq_out, fq_gains;                     // fit_quality: chisq_ant | wsum_ant ([nants][nfreqs] doubles each, the exchange payload) | chisq_bl | wsum_bl; gains given for one evaluation
+  DevBuf rw_w0, rw_out;                        // robust_weights: w0, the weights as set_data gave them (first call after a set_data); scale_bl | ndown_bl ([nbls] doubles each)
+  bool rw_w0_valid = false;
   DevBuf members, heads;                       // baselines that share tiles (bl_alias): member lists of the head items, head item indices
   bool heads_one_pass = false;                 // the regularised step of the heads in ONE pass (all of them on fused_multi_mfma_kernel<.., REG = 2>)
   bool reg_prepass = false;                    // the regularised gradient pass is preceded by a loss pass and the slices' alpha (enqueue_pass);
@@ -438,6 +443,7 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
   int set_problem_local(const cal_problem_desc* d) {
     HIP_TRY(hipSetDevice(device));
     has_problem = has_data = has_gains = has_coef = false;
+    rw_w0_valid = false;
     drop_graph();
     release_gain_basis();  // a new problem fits per channel until a basis is set again
     ProblemPlan<T> p;
@@ -578,7 +584,7 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     CAL_TRY(upload(ant_ptr, p.ant_ptr));
     CAL_TRY(upload(ant_ent, p.ant_ent));
 
-    for (DevBuf* b : {&gains_snap, &gains_alt, &coef_snap, &q1, &gcp1, &gc1, &model_buf, &scratch, &fq_out, &fq_gains, &gs_out, &gs_ptr, &gs_ent, &gs_mask, &cs_rhs})
+    for (DevBuf* b : {&gains_snap, &gains_alt, &coef_snap, &q1, &gcp1, &gc1, &model_buf, &scratch, &fq_out, &fq_gains, &gs_out, &gs_ptr, &gs_ent, &gs_mask, &cs_rhs, &rw_w0, &rw_out})
       b->release();
     // ---- state arrays
     const size_t rowbytes = (size_t)(nbls + 1) * fpad * sizeof(T);  // + one all-zero spare row (padding slots of the dense path)
@@ -681,6 +687,7 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     CAL_TRY(upload_rows(dr, data_r.as<T>(), nbls, 1, 0));
     CAL_TRY(upload_rows(di, data_i.as<T>(), nbls, 1, 0));
     CAL_TRY(upload_rows(w, wgts.as<T>(), nbls, 1, 0));
+    rw_w0_valid = false;  // robust_weights: the next call takes w0 from these
     has_data = true;
     return CAL_OK;
   }
@@ -1835,6 +1842,55 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     return CAL_OK;
   }
 
+  // cal_solver_robust_weights: the model pass of model(), then robust_rows_kernel (robust_weight_kernels.hpp) over the weight plane in place.
+  // Nothing leaves a baseline row: no exchange under a communicator.
+  int robust_weights(const cal_robust_desc* d, double* scale_bl, double* ndown_bl) override {
+    HIP_TRY(hipSetDevice(device));
+    if (!d) return fail(CAL_ERR_INVALID, "robust_weights: null description");
+    CAL_TRY(require_set("robust_weights", true));
+    if (d->kind != CAL_ROBUST_NONE && d->kind != CAL_ROBUST_HUBER && d->kind != CAL_ROBUST_CAUCHY && d->kind != CAL_ROBUST_CLIP)
+      return fail(CAL_ERR_INVALID, "robust_weights: unknown kind %d", d->kind);
+    if (!(d->threshold > 0.0) || !std::isfinite(d->threshold)) return fail(CAL_ERR_INVALID, "robust_weights: threshold = %g must be finite and > 0", d->threshold);
+    if (rw_out.bytes < 2 * (size_t)nbls * sizeof(double)) CAL_TRY(rw_out.alloc(2 * (size_t)nbls * sizeof(double)));
+    double* o_scale = rw_out.as<double>();
+    double* o_ndown = o_scale + nbls;
+    HIP_TRY(hipMemsetAsync(o_scale, 0, 2 * (size_t)nbls * sizeof(double), stream));  // rows of unselected slices report 0
+    if (d->kind != CAL_ROBUST_NONE || rw_w0_valid) {  // (kind NONE before any reweighting: the weights are w0 already)
+      if (!rw_w0_valid) {
+        if (rw_w0.bytes < wgts.bytes) CAL_TRY(rw_w0.alloc(wgts.bytes, false));
+        HIP_TRY(hipMemcpyAsync(rw_w0.p, wgts.p, wgts.bytes, hipMemcpyDeviceToDevice, stream));
+        rw_w0_valid = true;
+      }
+      const unsigned char* mask = nullptr;
+      CAL_TRY(upload_slice_mask(d->slice_mask, &mask));
+      const bool lds = fpad <= robust_lds_fpad<T>();
+      const size_t lds_bytes = lds ? (size_t)kRobustRows * fpad * sizeof(T) : 0;
+      auto launch = [&](T* model_r, T* model_i) {
+        auto* kern = lds ? robust_rows_kernel<T, true> : robust_rows_kernel<T, false>;
+        hipLaunchKernelGGL(kern, dim3((nbls + kRobustRows - 1) / kRobustRows), dim3(64 * kRobustRows), lds_bytes, stream, model_r, model_i,
+                           data_r.as<T>(), data_i.as<T>(), rw_w0.as<T>(), wgts.as<T>(), gains.as<T2>(), bl_ant.as<int2>(), mask, na_slice, nbls, nfreqs,
+                           fpad, d->kind, d->threshold, o_scale, o_ndown);
+      };
+      if (d->kind == CAL_ROBUST_NONE) {
+        launch(nullptr, nullptr);
+        HIP_TRY(hipGetLastError());
+      } else {
+        CAL_TRY(model_pass(2, [&](T* model_r, T* model_i, T*) { launch(model_r, model_i); }));
+      }
+    }
+    if (scale_bl) HIP_TRY(hipMemcpyAsync(scale_bl, o_scale, (size_t)nbls * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (ndown_bl) HIP_TRY(hipMemcpyAsync(ndown_bl, o_ndown, (size_t)nbls * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return CAL_OK;
+  }
+  int get_weights(void* out, int which) override {
+    HIP_TRY(hipSetDevice(device));
+    if (!has_problem || !has_data) return fail(CAL_ERR_STATE, "get_weights: problem and data must be set");
+    if (!out) return fail(CAL_ERR_INVALID, "get_weights: null output");
+    if (which != 0 && which != 1) return fail(CAL_ERR_INVALID, "get_weights: which = %d (0: current, 1: w0)", which);
+    return download_rows(out, which == 1 && rw_w0_valid ? rw_w0.as<T>() : wgts.as<T>(), nbls, 1, 0);
+  }
+
   // cal_solver_hold_slices: slices that enter every later run as stopped (a chunked loop keeps the slices that met the tolerance in
   // an earlier chunk as they are); NULL or all zeros: none.  set_optimizer and set_problem clear it.
   int hold_slices(const uint8_t* mask) override {
@@ -2289,7 +2345,7 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     if (!b) return fail(CAL_ERR_INVALID, "memory_bytes: null");
     const DevBuf* all[] = {&tiles, &bl_tile, &bl_ant, &items, &ant_ptr, &ant_ent, &coef_grp, &grp_coff, &grp_item_ptr, &item_goff,
                            &data_r, &data_i, &wgts, &gains, &gains_alt, &gains_m, &gains_v, &gains_snap, &coef, &coef_m, &coef_v, &coef_snap,
-                           &q0, &q1, &comm, &scal, &gcp0, &gcp1, &gc0, &gc1, &part, &state, &losses, &scratch, &model_buf, &fq_out, &fq_gains, &gs_out, &gs_ptr, &gs_ent, &gs_mask, &cs_grp, &cs_order, &cs_work, &cs_n, &cs_d, &cs_rhs, &cs_cnt, &gbs_n, &gbs_d, &gbs_rhs, &gbs_cnt, &gts_m, &gts_n, &gts_rhsa, &gts_d, &gts_rhs, &gts_cnt,
+                           &q0, &q1, &comm, &scal, &gcp0, &gcp1, &gc0, &gc1, &part, &state, &losses, &scratch, &model_buf, &fq_out, &fq_gains, &rw_w0, &rw_out, &gs_out, &gs_ptr, &gs_ent, &gs_mask, &cs_grp, &cs_order, &cs_work, &cs_n, &cs_d, &cs_rhs, &cs_cnt, &gbs_n, &gbs_d, &gbs_rhs, &gbs_cnt, &gts_m, &gts_n, &gts_rhsa, &gts_d, &gts_rhs, &gts_cnt,
                            &mf_ops, &mf_panels, &mf_map, &members, &heads, &lamb_vars, &lamb_cvar_ptr, &lamb_partial, &lamb_ratio, &lamb_glob, &lamb_slot, &slice_coff, &slice_ipart_ptr, &slice_ipart_idx,
                            &slice_ppart_ptr, &slice_ppart_idx, &slice_cblk, &gb_B, &gb_Bt, &gb_g0, &gb_y, &gb_ym, &gb_yv, &gb_ysnap, &gb_proj, &tb_B, &tb_Bt, &tb_z, &tb_pf};
     int64_t n = 0;
@@ -2653,6 +2709,8 @@ int cal_solver_fit_quality(cal_solver* s, const void* g_r, const void* g_i, doub
   NEED(s);
   return s->fit_quality(g_r, g_i, chisq_ant, wsum_ant, chisq_bl, wsum_bl);
 }
+int cal_solver_robust_weights(cal_solver* s, const cal_robust_desc* desc, double* scale_bl, double* ndown_bl) { NEED(s); return s->robust_weights(desc, scale_bl, ndown_bl); }
+int cal_solver_get_weights(cal_solver* s, void* out, int which) { NEED(s); return s->get_weights(out, which); }
 int cal_solver_init_coeffs(cal_solver* s, const void* sr, const void* si) { NEED(s); return s->init_coeffs(sr, si); }
 int cal_solver_synchronize(cal_solver* s) { NEED(s); return s->synchronize(); }
 int cal_solver_set_launch_mode(cal_solver* s, int mode) { NEED(s); return s->set_launch_mode(mode); }

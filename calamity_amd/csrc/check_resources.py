@@ -9,7 +9,8 @@ contains `fused_dense`; and two waves per SIMD where the kernels are written for
 CU to itself): no scratch and no spilled VGPRs there either (a few SGPR spills into lanes of a VGPR are tolerated: they sit outside its job loop).
 `fused_basis_kernel`: no scratch in any instance; four waves per SIMD in the fp32 gradient instances with full and with folded tiles.
 `gain_project_kernel`, `gain_expand_kernel` (gain_basis_kernels.hpp), `gain_time_project_kernel`, `gain_time_expand_kernel`
-(gain_time_basis_kernels.hpp), `quality_rows_kernel`, `quality_ant_kernel` (fit_quality_kernels.hpp), `gain_solve_rows_kernel`, `gain_solve_ant_kernel`,
+(gain_time_basis_kernels.hpp), `quality_rows_kernel`, `quality_ant_kernel` (fit_quality_kernels.hpp), `robust_rows_kernel` (robust_weight_kernels.hpp, both
+instances of both dtypes), `gain_solve_rows_kernel`, `gain_solve_ant_kernel`,
 `gain_solve_apply_kernel` (gain_solve_kernels.hpp), `coeff_solve_rows_kernel`, `coeff_gram_kernel`, `coeff_chol_kernel`
 (coeff_solve_kernels.hpp), `gain_basis_gram_kernel`, `gain_basis_chol_kernel` (gain_basis_solve_kernels.hpp; both pairs are built on the
 shared Gram and Cholesky core of normal_solve.hpp), `gain_time_kron_kernel`, `gain_time_chol_kernel`, `gain_time_chan_kernel`
@@ -45,11 +46,11 @@ for line in sys.stdin:
             bad.append(f"{cur}: {m.group(1)} = {m.group(2)}")
         continue
     if cur is not None and any(k in cur for k in ("gain_project_kernel", "gain_expand_kernel", "gain_time_project_kernel", "gain_time_expand_kernel",
-                                             "quality_rows_kernel", "quality_ant_kernel", "gain_solve_rows_kernel", "gain_solve_ant_kernel",
+                                             "quality_rows_kernel", "quality_ant_kernel", "robust_rows_kernel", "gain_solve_rows_kernel", "gain_solve_ant_kernel",
                                              "gain_solve_apply_kernel", "coeff_solve_rows_kernel", "coeff_gram_kernel", "coeff_chol_kernel",
                                              "gain_basis_gram_kernel", "gain_basis_chol_kernel", "gain_time_kron_kernel", "gain_time_chol_kernel",
                                              "gain_time_chan_kernel")):
-        # the kernels around the update of a gain-basis fit, the two of the fit-quality pass, the three of the gain solve, the three
+        # the kernels around the update of a gain-basis fit, the two of the fit-quality pass, the one of the robust reweighting, the three of the gain solve, the three
         # of the coefficient solve, the two of the gain-coefficient solve and the three of the time-basis solve keep their accumulators in
         # registers: no scratch
         m = re.search(r"remark:\s+(ScratchSize \[bytes/lane\]|VGPRs Spill): (\d+)", line)

@@ -326,6 +326,42 @@ class HipFitSolver:
             raise ValueError(f"expected one mask entry per time slice ({self.nslices}), got shape {m.shape}")
         return m
 
+    def robust_weights(self, kind="huber", threshold=3.0, slice_mask=None):
+        """One round of iteratively reweighted least squares (cal_solver_robust_weights): the weight plane every kernel path reads is
+        rewritten in place from the residual at the solver's current parameters.  With ``w0`` the weights as ``set_data`` gave them,
+        ``(i, j)`` the antennas of baseline row ``b``, ``m = A c``, ``g`` the solver's gains and ``k = threshold`` (in sigma)::
+
+            e[b][f]  = w0[b][f] |d[b][f] - g_i[f] conj(g_j[f]) m[b][f]|^2     (products in the solver's dtype)
+            S_b      = { f < nfreqs : w0[b][f] > 0 },  n_b = |S_b|
+            med_b    = the ((n_b + 1) // 2)-th smallest of e[b][S_b]          (the lower median: an element of the row)
+            scale_b  = med_b / ln 2
+            z2       = e / scale_b
+            huber  : psi = 1 if z2 <= k^2 else k / sqrt(z2)
+            cauchy : psi = 1 / (1 + z2 / k^2)
+            clip   : psi = 1 if z2 <= k^2 else 0
+            w[b][f]  = w0[b][f] * psi
+
+        ``scale_b = med_b / ln 2`` because ``w |r|^2`` of complex Gaussian residuals is exponentially distributed (median = ``ln 2`` x
+        mean).  Rows with ``n_b = 0`` or ``med_b = 0`` keep ``w = w0``.  Every call starts from ``w0``, never from the previous ``w``;
+        the weights are not renormalised, so losses before and after a call are not comparable.  ``kind="none"`` puts ``w0`` back.
+        ``slice_mask``: ``[nslices]``, the slices to reweight (``None``: all); the rows of the others keep their bits.  The call is
+        local to a baseline row: no exchange under a communicator.  Returns ``{"scale_bl", "ndown_bl"}``, ``[nbls]`` float64:
+        ``scale_b`` and the number of samples with ``psi < 1`` (both 0 for rows of unselected slices)."""
+        if kind not in _lib.ROBUST_KINDS:
+            raise ValueError(f"unknown robust kind {kind!r}: one of {sorted(_lib.ROBUST_KINDS)}")
+        m = self._slice_mask(slice_mask)
+        d = _lib.RobustDesc(_lib.ROBUST_KINDS[kind], float(threshold), None if m is None else m.ctypes.data)
+        out = dict(scale_bl=np.empty(self.nbls, dtype=np.float64), ndown_bl=np.empty(self.nbls, dtype=np.float64))
+        _lib.check(self._lib.cal_solver_robust_weights(self._h, C.byref(d), _ptr(out["scale_bl"]), _ptr(out["ndown_bl"])))
+        return out
+
+    def get_weights(self, which=0):
+        """The weight plane ``[nbls, nfreqs]``: ``which=0`` the weights the kernels read now, ``which=1`` ``w0``, the weights as
+        ``set_data`` gave them (the same until ``robust_weights`` has run)."""
+        out = np.empty((self.nbls, self.nfreqs), dtype=self.dtype)
+        _lib.check(self._lib.cal_solver_get_weights(self._h, _ptr(out), int(which)))
+        return out
+
     def solve_gains(self, nsweeps, damping=0.5, slice_mask=None, reset_gain_moments=False):
         """``nsweeps`` damped StefCal sweeps over the gains with the foreground model ``m = A c`` held fixed at the solver's
         coefficients (cal_solver_solve_gains): per antenna ``a`` and channel, with the other antennas at their OLD gains,

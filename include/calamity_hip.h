@@ -290,6 +290,46 @@ int cal_solver_data_model(cal_solver* s, void* model_r, void* model_i);
  * the rank's own baselines. */
 int cal_solver_fit_quality(cal_solver* s, const void* g_r, const void* g_i, double* chisq_ant, double* wsum_ant, double* chisq_bl,
                            double* wsum_bl);
+/* Downweight outliers from the residual (no counterpart in the reference, which minimises a plain weighted chi-square): one round of
+ * iteratively reweighted least squares.  The call rewrites the ONE weight plane that every kernel path, cal_solver_fit_quality and
+ * the closed-form solves read, in place: no fit kernel changes and no recorded step graph goes stale.  With w0 the weights as
+ * cal_solver_set_data gave them, (i, j) the antennas of baseline row b, m = A c at the solver's coefficients, g the solver's gains:
+ *   e[b][f]  = w0[b][f] |d[b][f] - g_i[f] conj(g_j[f]) m[b][f]|^2     (products in the solver's dtype, in cal_solver_fit_quality's order)
+ *   S_b      = { f < nfreqs : w0[b][f] > 0 },  n_b = |S_b|
+ *   med_b    = the ((n_b + 1) // 2)-th smallest of e[b][S_b]          (the lower median: an element of the row, never an average)
+ *   scale_b  = med_b / ln 2
+ *   z2       = e / scale_b                                            (scale_b, z2 and psi in double)
+ *   huber  : psi = 1 if z2 <= k^2 else k / sqrt(z2)
+ *   cauchy : psi = 1 / (1 + z2 / k^2)
+ *   clip   : psi = 1 if z2 <= k^2 else 0
+ *   w[b][f]  = w0[b][f] * psi                                         (rounded once to the solver's dtype)
+ * scale_b = med_b / ln 2 because w |r|^2 of complex Gaussian residuals is exponentially distributed, whose median is ln 2 times its
+ * mean; k = threshold is in sigma (for that law P(z2 > 9) = e^-9 ~ 1.2e-4).  Rows with n_b = 0 or med_b = 0 keep w = w0 and report
+ * scale 0; autocorrelation rows are rows like any other; channels outside S_b and the padding keep their bits.  The scale is per
+ * baseline row: nothing leaves the row, so a sharded fit issues NO collective under a communicator or exchange hook.  Every call starts
+ * from w0, never from the previous w; the weights are not renormalised, so losses before and after a call are under different weights
+ * and are not comparable.  The median is exact (a bisection on the IEEE bit pattern of e, integer counts): two calls give the same bits.
+ * A NaN in e orders above every number.
+ *   kind: CAL_ROBUST_NONE copies w0 back for the selected slices (and frees nothing); HUBER, CAUCHY, CLIP as above; anything else, or a
+ *   threshold that is not finite and > 0, is CAL_ERR_INVALID.  Problem, data, coefficients and gains must be set (CAL_ERR_STATE).
+ *   slice_mask: [nslices] bytes or NULL (all slices): the rows of a slice whose byte is 0 (slice of a row = its first antenna row /
+ *   antennas per slice) keep their bits, in the weights and in both outputs' device copies (the outputs report 0 for them).
+ *   scale_bl, ndown_bl: [nbls] doubles each, either may be NULL: scale_b, and the number of samples of S_b with psi < 1.
+ * w0 lives in a device plane of its own, allocated and copied from the weights by the first call after a cal_solver_set_data;
+ * cal_solver_set_data and cal_solver_set_problem invalidate it, so a fit that never calls this pays no memory for it.  Works for every
+ * layout and kernel path, fitting groups of several baselines, bl_alias, nslices > 1, the joint time-basis layout and with gain bases
+ * attached.  It runs the model pass of cal_solver_model and, like cal_solver_fit_quality, puts the loop state back: a run continued
+ * after a call with an all-zero mask is bit-identical to one without the call. */
+enum { CAL_ROBUST_NONE = 0, CAL_ROBUST_HUBER = 1, CAL_ROBUST_CAUCHY = 2, CAL_ROBUST_CLIP = 3 };
+typedef struct cal_robust_desc {
+  int kind; /* CAL_ROBUST_NONE | HUBER | CAUCHY | CLIP */
+  double threshold;
+  const uint8_t* slice_mask;
+} cal_robust_desc;
+int cal_solver_robust_weights(cal_solver* s, const cal_robust_desc* desc, double* scale_bl, double* ndown_bl);
+/* The weight plane: which = 0 the weights every kernel reads now, which = 1 w0 (the weights of cal_solver_set_data; equal to the
+ * current ones until cal_solver_robust_weights has run).  out: [nbls][nfreqs] in the solver's dtype. */
+int cal_solver_get_weights(cal_solver* s, void* out, int which);
 /* The gains in closed form (no counterpart in the reference, which moves them by first-order descent only): damped StefCal sweeps
  * (Salvini & Wijnholds 2014).  With the foreground model m = A c held fixed at the solver's coefficients, the chi-square
  * sum w |d - g_i conj(g_j) m|^2 is linear least squares in one antenna's gain while the others are held fixed, with a closed-form
