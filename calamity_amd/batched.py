@@ -220,29 +220,25 @@ class SliceBatchFitter:
 
         self._each(one)
 
+    def _scatter(self, parts, index):
+        """The global array of the workers' ``parts``, worker ``r``'s at ``index[r]`` (``self.rows``: baseline rows, ``self.cidx``:
+        coefficients); one worker's part is the array already."""
+        if self.nworkers == 1:
+            return parts[0]
+        out = np.empty((sum(len(i) for i in index),) + parts[0].shape[1:], dtype=parts[0].dtype)
+        for i, part in zip(index, parts):
+            out[i] = part
+        return out
+
     def get_params(self, which=0):
         outs = self._each(lambda r, s: s.get_params(which))
-        if self.nworkers == 1:
-            return outs[0]
-        c_r = np.empty(self.ncoeffs, dtype=self.dtype)
-        c_i = np.empty(self.ncoeffs, dtype=self.dtype)
-        for r, o in enumerate(outs):
-            c_r[self.cidx[r]] = o[2]
-            c_i[self.cidx[r]] = o[3]
-        return outs[0][0], outs[0][1], c_r, c_i  # the gains are replicated
+        return (*outs[0][:2], *(self._scatter([o[k] for o in outs], self.cidx) for k in (2, 3)))  # the gains are replicated
 
     def eval_grads(self):
         """(loss, gain gradients, coefficient gradients) of the current parameters, like ``get_params``: the loss is the global
         sum over slices, the gain gradients are all-reduced (every worker holds them), the coefficient gradients gathered."""
         outs = self._each(lambda r, s: s.eval_grads())
-        if self.nworkers == 1:
-            return outs[0]
-        gc_r = np.empty(self.ncoeffs, dtype=self.dtype)
-        gc_i = np.empty(self.ncoeffs, dtype=self.dtype)
-        for r, o in enumerate(outs):
-            gc_r[self.cidx[r]] = o[3]
-            gc_i[self.cidx[r]] = o[4]
-        return outs[0][0], outs[0][1], outs[0][2], gc_r, gc_i
+        return (*outs[0][:3], *(self._scatter([o[k] for o in outs], self.cidx) for k in (3, 4)))
 
     def slice_losses(self):
         """Every slice's loss as of the last eval_grads (all-reduced: the same on every worker)."""
@@ -250,51 +246,25 @@ class SliceBatchFitter:
 
     def model(self):
         outs = self._each(lambda r, s: s.model())
-        if self.nworkers == 1:
-            return outs[0]
-        m_r = np.empty((self.nbls, self.nfreqs), dtype=self.dtype)
-        m_i = np.empty_like(m_r)
-        for r, o in enumerate(outs):
-            m_r[self.rows[r]] = o[0]
-            m_i[self.rows[r]] = o[1]
-        return m_r, m_i
+        return tuple(self._scatter([o[k] for o in outs], self.rows) for k in (0, 1))
 
     def fit_quality(self, g_r=None, g_i=None):
         """``HipFitSolver.fit_quality`` on the global arrays: ``chisq_ant``, ``wsum_ant`` ``[nt * nants, nfreqs]`` (with several
         workers the library has summed them over the workers: worker 0's), ``chisq_bl``, ``wsum_bl`` ``[nt * nbls]`` put back into
         the global slice-major row order like the rows of ``model()``."""
         outs = self._each(lambda r, s: s.fit_quality(g_r, g_i))
-        if self.nworkers == 1:
-            return outs[0]
-        res = dict(chisq_ant=outs[0]["chisq_ant"], wsum_ant=outs[0]["wsum_ant"],
-                   chisq_bl=np.empty(self.nbls, dtype=np.float64), wsum_bl=np.empty(self.nbls, dtype=np.float64))
-        for r, o in enumerate(outs):
-            res["chisq_bl"][self.rows[r]] = o["chisq_bl"]
-            res["wsum_bl"][self.rows[r]] = o["wsum_bl"]
-        return res
+        return dict(outs[0], **{k: self._scatter([o[k] for o in outs], self.rows) for k in ("chisq_bl", "wsum_bl")})
 
     def robust_weights(self, kind="huber", threshold=3.0, slice_mask=None):
         """``HipFitSolver.robust_weights`` on every worker (``slice_mask``: one entry per slice of the batch; one entry for a ``joint``
         fitter): each worker reweights its own baseline rows, nothing is exchanged.  ``scale_bl``, ``ndown_bl`` ``[nt * nbls]`` put
         back into the global slice-major row order like the rows of ``model()``."""
         outs = self._each(lambda r, s: s.robust_weights(kind=kind, threshold=threshold, slice_mask=slice_mask))
-        if self.nworkers == 1:
-            return outs[0]
-        res = dict(scale_bl=np.empty(self.nbls, dtype=np.float64), ndown_bl=np.empty(self.nbls, dtype=np.float64))
-        for r, o in enumerate(outs):
-            res["scale_bl"][self.rows[r]] = o["scale_bl"]
-            res["ndown_bl"][self.rows[r]] = o["ndown_bl"]
-        return res
+        return {k: self._scatter([o[k] for o in outs], self.rows) for k in ("scale_bl", "ndown_bl")}
 
     def get_weights(self, which=0):
         """``HipFitSolver.get_weights`` of every worker, the rows put back into the global slice-major order."""
-        outs = self._each(lambda r, s: s.get_weights(which))
-        if self.nworkers == 1:
-            return outs[0]
-        w = np.empty((self.nbls, self.nfreqs), dtype=self.dtype)
-        for r, o in enumerate(outs):
-            w[self.rows[r]] = o
-        return w
+        return self._scatter(self._each(lambda r, s: s.get_weights(which)), self.rows)
 
     def solve_gains(self, nsweeps, damping=0.5, slice_mask=None, reset_gain_moments=False):
         """``HipFitSolver.solve_gains`` on every worker (``slice_mask``: one entry per slice of the batch; one entry for a ``joint``

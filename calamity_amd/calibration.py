@@ -20,14 +20,14 @@ import argparse
 import collections
 import concurrent.futures
 import copy
+import dataclasses
 import datetime
-import json
-import os
 import threading
 
 import numpy as np
 
 from . import cal_utils, modeling, utils
+from .fit_loop import FitOptions, drive, history_entry
 from .problem import FitProblem, coeffs_from_chunks, coeffs_to_chunks, problem_from_chunks
 from .solver import OPTIMIZERS, HipFitSolver
 from .utils import PBARS, echo
@@ -681,20 +681,8 @@ def fit_gains_and_foregrounds(
     between chunks of the recorded loop, see ``calibrate_and_model_tensor``; here ``fit_history["robust"]`` holds the last reweight in
     solver units and row order, ``{"rounds": n, "ndown_bl": [nbls], "scale_bl": [nbls]}`` (``HipFitSolver.robust_weights``).
     """
-    _check_robust(robust_every, robust_rounds, robust_kind, robust_threshold, use_min,
-                  (gain_solve_every, gain_basis_solve_every, gain_time_solve_every))
-    _check_gain_solve(gain_solve_sweeps, gain_solve_every, gain_solve_damping, gain_basis is not None)
-    _check_coeff_solve(coeff_solve_rounds, coeff_solve_ridge, freeze_model)
-    _check_gain_basis_solve(gain_basis_solve_sweeps, gain_basis_solve_every, gain_basis_solve_damping, gain_basis_solve_ridge,
-                            gain_basis is not None, False)
-    _check_gain_time_solve(gain_time_solve_sweeps, gain_time_solve_every, gain_time_solve_damping, gain_time_solve_ridge, False,
-                           bool(gain_basis_solve_sweeps or gain_basis_solve_every), bool(gain_solve_sweeps or gain_solve_every))
-    if gain_basis_solve_sweeps or gain_basis_solve_every:  # a basis fit: its sweeps stand where the per-channel sweeps stand
-        sweep = lambda n, **kw: solver.solve_gain_coeffs(n, damping=gain_basis_solve_damping, ridge=gain_basis_solve_ridge, **kw)["nsingular"]  # noqa: E731
-        n_sweeps, every = gain_basis_solve_sweeps, gain_basis_solve_every
-    else:
-        sweep = lambda n, **kw: solver.solve_gains(n, damping=gain_solve_damping, **kw)  # noqa: E731
-        n_sweeps, every = gain_solve_sweeps, gain_solve_every
+    opts = FitOptions.pick(locals())
+    opts.check(gain_basis is not None, False, freeze_model, use_min, robust_first=True)
     if gain_basis is not None:
         gain_basis = _check_gain_basis(gain_basis, np.asarray(g_r).shape[-1])
     echo(f"Using {str(dtype)} precision.")
@@ -721,57 +709,15 @@ def fit_gains_and_foregrounds(
     else:
         solver.set_regularization(None)
     solver.set_optimizer(optimizer, **opt_kwargs)
-    nsingular = gb_singular = None
-    if coeff_solve_rounds > 0:  # alternating least squares: rounds of (the coefficients in closed form, then the gain sweeps)
-        for _ in range(coeff_solve_rounds):
-            nsingular = solver.solve_coeffs(ridge=coeff_solve_ridge)["nsingular"]
-            if n_sweeps > 0:
-                gb_singular = sweep(n_sweeps)
-    elif n_sweeps > 0:  # the coefficients are initialised: the gains in closed form before any descent step
-        gb_singular = sweep(n_sweeps)
-    fit_history = {"loss": []}
     if n_profile_steps > 0:
         echo(f"{datetime.datetime.now()} Profiling with {n_profile_steps}. And writing output to {profile_log_dir}...")
-        solver.timing_enable(True)
-        solver.run(n_profile_steps, record=False, freeze_model=freeze_model)
-        os.makedirs(profile_log_dir, exist_ok=True)
-        with open(os.path.join(profile_log_dir, f"calamity_amd_profile_{datetime.datetime.now():%Y%m%d_%H%M%S_%f}.json"), "w") as f:
-            json.dump(dict(n_profile_steps=n_profile_steps, fused_basis_kernel=solver.timing_get()), f)
-        solver.timing_enable(False)
     echo(f"{datetime.datetime.now()} Building Computational Graph...\n", verbose=verbose)
-    solver.run(1, record=False, freeze_model=freeze_model)  # the unrecorded step of calibration.py:693
     echo(f"{datetime.datetime.now()} Performing Gradient Descent...\n", verbose=verbose)
-    robust = None
-    if robust_every > 0:
-        robust = {"rounds": 0, "ndown_bl": np.zeros(prob.nbls), "scale_bl": np.zeros(prob.nbls)}
-    if every > 0 or robust_every > 0:
-        # the recorded loop in chunks (the solver's loop state -- step count, previous and lowest loss -- persists from run to run), a
-        # gain solve between two chunks while the loop goes on; with robust_every the weights are recomputed first (_check_robust: one
-        # chunk length)
-        losses, stopped = np.zeros(0), False
-        while len(losses) < maxsteps and not stopped:
-            n = min(every or robust_every, maxsteps - len(losses))
-            part, stopped, _ = solver.run(n, record=True, tol=tol, use_min=use_min, freeze_model=freeze_model)
-            losses = np.concatenate([losses, part])
-            if len(part) < n:
-                break
-            if not stopped and len(losses) < maxsteps:
-                if robust is not None and (robust_rounds == 0 or robust["rounds"] < robust_rounds):
-                    rw = solver.robust_weights(kind=robust_kind, threshold=robust_threshold)
-                    robust = {"rounds": robust["rounds"] + 1, "ndown_bl": rw["ndown_bl"], "scale_bl": rw["scale_bl"]}
-                if every > 0:
-                    if coeff_solve_rounds > 0:
-                        nsingular = solver.solve_coeffs(ridge=coeff_solve_ridge, reset_coeff_moments=True)["nsingular"]
-                    gb_singular = sweep(max(1, n_sweeps), reset_gain_moments=True)
-    else:
-        losses, stopped, _ = solver.run(maxsteps, record=True, tol=tol, use_min=use_min, freeze_model=freeze_model)
-    fit_history["loss"] = [dtype.type(l) for l in losses]
-    if nsingular is not None:
-        fit_history["coeff_solve_singular"] = int(nsingular)
-    if gain_basis_solve_sweeps or gain_basis_solve_every:
-        fit_history["gain_basis_solve_singular"] = int(gb_singular or 0)
-    if robust is not None:
-        fit_history["robust"] = robust
+    ((losses, stopped, _),), nsingular, sweep_singular, robust = drive(
+        solver, opts, 1, prob.nbls, maxsteps, tol, use_min, freeze_model, n_profile_steps, profile_log_dir)
+    if robust is not None:  # (solver units and row order: the documented shape of this function)
+        robust = {"rounds": int(robust["rounds"][0]), "ndown_bl": robust["ndown_bl"], "scale_bl": robust["scale_bl"]}
+    fit_history = history_entry(opts, losses, dtype, nsingular, sweep_singular, robust)
     if stopped:
         echo(f"Tolerance thresshold met with delta of {np.abs(losses[-1] - losses[-2]):.2e}. Terminating...\n ", verbose=verbose)
     g_r_opt, g_i_opt, c_r, c_i = solver.get_params(which=1 if (use_min and len(losses) > 0) else 0)
@@ -800,78 +746,6 @@ def _check_gain_basis(basis, nfreqs):
     return np.ascontiguousarray(basis, dtype=np.float64)
 
 
-def _check_gain_solve(sweeps, every, damping, gain_basis_given):
-    """The arguments of the closed-form gain sweeps (ValueError before any device work)."""
-    if int(sweeps) != sweeps or sweeps < 0 or int(every) != every or every < 0:
-        raise ValueError(f"gain_solve_sweeps and gain_solve_every must be non-negative integers, got {sweeps!r} and {every!r}")
-    if not 0.0 < float(damping) <= 1.0:
-        raise ValueError(f"gain_solve_damping must lie in (0, 1], got {damping!r}")
-    if (sweeps or every) and gain_basis_given:
-        raise ValueError("gain_solve_sweeps / gain_solve_every solve free per-channel gains in closed form: they cannot be combined with "
-                         "gain_basis / gain_max_dly / gain_time_basis / gain_time_scale (projecting the solved gains onto a basis is not implemented); a fit with a frequency gain basis has "
-                         "gain_basis_solve_sweeps / gain_basis_solve_every")
-
-
-def _check_gain_basis_solve(sweeps, every, damping, ridge, freq_basis_given, time_basis_given):
-    """The arguments of the closed-form sweeps of a gain-basis fit (ValueError before any device work)."""
-    for v in (sweeps, every):
-        if isinstance(v, bool) or int(v) != v or v < 0:
-            raise ValueError(f"gain_basis_solve_sweeps and gain_basis_solve_every must be non-negative integers, got {sweeps!r} and {every!r}")
-    if not 0.0 < float(damping) <= 1.0:
-        raise ValueError(f"gain_basis_solve_damping must lie in (0, 1], got {damping!r}")
-    if not (np.isfinite(float(ridge)) and float(ridge) >= 0.0):
-        raise ValueError(f"gain_basis_solve_ridge must be finite and >= 0, got {ridge!r}")
-    if not (sweeps or every):
-        return
-    if time_basis_given:
-        raise ValueError("gain_basis_solve_sweeps / gain_basis_solve_every solve the coefficients of a frequency gain basis antenna by antenna: they "
-                         "cannot be combined with gain_time_basis / gain_time_scale, whose variables couple the times (a joint system that is not implemented)")
-    if not freq_basis_given:
-        raise ValueError("gain_basis_solve_sweeps / gain_basis_solve_every solve the coefficients of a frequency gain basis: give gain_basis or "
-                         "gain_max_dly (free per-channel gains have gain_solve_sweeps / gain_solve_every)")
-
-
-def _check_gain_time_solve(sweeps, every, damping, ridge, time_basis_given, basis_solve_on, gain_solve_on):
-    """The arguments of the closed-form sweeps of a fit with a gain time basis (ValueError before any device work)."""
-    for v in (sweeps, every):
-        if isinstance(v, bool) or int(v) != v or v < 0:
-            raise ValueError(f"gain_time_solve_sweeps and gain_time_solve_every must be non-negative integers, got {sweeps!r} and {every!r}")
-    if not 0.0 < float(damping) <= 1.0:
-        raise ValueError(f"gain_time_solve_damping must lie in (0, 1], got {damping!r}")
-    if not (np.isfinite(float(ridge)) and float(ridge) >= 0.0):
-        raise ValueError(f"gain_time_solve_ridge must be finite and >= 0, got {ridge!r}")
-    if not (sweeps or every):
-        return
-    if not time_basis_given:
-        raise ValueError("gain_time_solve_sweeps / gain_time_solve_every solve the coefficients of a joint fit over the times: give gain_time_basis "
-                         "or gain_time_scale (a frequency gain basis alone has gain_basis_solve_sweeps / gain_basis_solve_every, free per-channel "
-                         "gains have gain_solve_sweeps / gain_solve_every)")
-    if basis_solve_on or gain_solve_on:
-        raise ValueError("gain_time_solve_sweeps / gain_time_solve_every are the sweeps of a fit with a gain time basis: they cannot be combined "
-                         "with gain_basis_solve_sweeps / gain_basis_solve_every or gain_solve_sweeps / gain_solve_every")
-
-
-def _check_robust(every, rounds, kind, threshold, use_min, solve_everys=()):
-    """The arguments of the robust reweighting (ValueError before any device work); ``solve_everys``: the chunk lengths of the
-    closed-form sweeps that share the loop's gaps."""
-    for v in (every, rounds):
-        if isinstance(v, bool) or int(v) != v or v < 0:
-            raise ValueError(f"robust_every and robust_rounds must be non-negative integers, got {every!r} and {rounds!r}")
-    if kind not in ("huber", "cauchy", "clip"):
-        raise ValueError(f"robust_kind must be 'huber', 'cauchy' or 'clip', got {kind!r}")
-    if not (np.isfinite(float(threshold)) and float(threshold) > 0.0):
-        raise ValueError(f"robust_threshold must be finite and > 0 (it is in sigma), got {threshold!r}")
-    if not every:
-        return
-    if use_min:
-        raise ValueError("robust_every rewrites the weights between chunks of the loop: losses under different weights are not comparable, so "
-                         "use_min (the minimum over them) cannot be combined with it")
-    for other in solve_everys:
-        if other and other != every:
-            raise ValueError(f"robust_every={every} and the closed-form sweeps' chunk length {other} (gain_solve_every / gain_basis_solve_every / "
-                             "gain_time_solve_every) share the gaps of one chunked loop: give them the same value")
-
-
 def robust_history(rounds, ndown_bl, scale_bl, rms, prob, ant_numbers):
     """One slice's ``fit_history[...]["robust"]``: ``{"rounds": n, "downweighted": {(ant0, ant1): count}, "scale": {(ant0, ant1):
     rms^2 scale_b}}`` with antenna NUMBERS, one entry per baseline row of ``prob``, from the last reweight of the slice
@@ -880,17 +754,6 @@ def robust_history(rounds, ndown_bl, scale_bl, rms, prob, ant_numbers):
     keys = [(int(ants[i]), int(ants[j])) for i, j in zip(prob.bl_ant0, prob.bl_ant1)]
     return {"rounds": int(rounds), "downweighted": {k: int(v) for k, v in zip(keys, ndown_bl)},
             "scale": {k: float(rms) ** 2 * float(v) for k, v in zip(keys, scale_bl)}}
-
-
-def _check_coeff_solve(rounds, ridge, freeze_model):
-    """The arguments of the closed-form coefficient solves (ValueError before any device work)."""
-    if isinstance(rounds, bool) or int(rounds) != rounds or rounds < 0:
-        raise ValueError(f"coeff_solve_rounds must be a non-negative integer, got {rounds!r}")
-    if not (np.isfinite(float(ridge)) and float(ridge) >= 0.0):
-        raise ValueError(f"coeff_solve_ridge must be finite and >= 0, got {ridge!r}")
-    if rounds and freeze_model:
-        raise ValueError("coeff_solve_rounds solves the foreground coefficients in closed form: it cannot be combined with freeze_model, "
-                         "which keeps them as given")
 
 
 def _check_gain_time_basis(basis, ntimes):
@@ -1166,16 +1029,8 @@ def calibrate_and_model_tensor(
     (Nothing here is steered by environment variables: layout, devices and concurrency are arguments.)"""
     if gain_basis is not None and gain_max_dly is not None:
         raise ValueError("give gain_basis or gain_max_dly, not both")
-    _check_gain_solve(gain_solve_sweeps, gain_solve_every, gain_solve_damping,
-                      any(b is not None for b in (gain_basis, gain_max_dly, gain_time_basis, gain_time_scale)))
-    _check_coeff_solve(coeff_solve_rounds, coeff_solve_ridge, freeze_model)
-    _check_gain_basis_solve(gain_basis_solve_sweeps, gain_basis_solve_every, gain_basis_solve_damping, gain_basis_solve_ridge,
-                            gain_basis is not None or gain_max_dly is not None, gain_time_basis is not None or gain_time_scale is not None)
-    _check_gain_time_solve(gain_time_solve_sweeps, gain_time_solve_every, gain_time_solve_damping, gain_time_solve_ridge,
-                           gain_time_basis is not None or gain_time_scale is not None,
-                           bool(gain_basis_solve_sweeps or gain_basis_solve_every), bool(gain_solve_sweeps or gain_solve_every))
-    _check_robust(robust_every, robust_rounds, robust_kind, robust_threshold, use_min,
-                  (gain_solve_every, gain_basis_solve_every, gain_time_solve_every))
+    opts = FitOptions.pick(locals())
+    opts.check(gain_basis is not None or gain_max_dly is not None, gain_time_basis is not None or gain_time_scale is not None, freeze_model, use_min)
     if gain_max_dly is not None:
         gain_basis = modeling.gain_dpss_basis(np.asarray(uvdata.freq_array, dtype=np.float64).ravel(), gain_max_dly)
     if gain_time_basis is not None and gain_time_scale is not None:
@@ -1266,10 +1121,7 @@ def calibrate_and_model_tensor(
             verbose=verbose, max_batch=max_batch, devices=devices, layout=layout, opt_kwargs=opt_kwargs,
             correct_model=correct_model, correct_resid=correct_resid, device_split=device_split, gain_basis=gain_basis,
             gain_time_basis=gain_time_basis, fit_quality=fit_quality,
-            gain_solve=(gain_solve_sweeps, gain_solve_every, gain_solve_damping), coeff_solve=(coeff_solve_rounds, coeff_solve_ridge),
-            gain_basis_solve=(gain_basis_solve_sweeps, gain_basis_solve_every, gain_basis_solve_damping, gain_basis_solve_ridge),
-            gain_time_solve=(gain_time_solve_sweeps, gain_time_solve_every, gain_time_solve_damping, gain_time_solve_ridge),
-            robust=(robust_every, robust_rounds, robust_kind, robust_threshold),
+            opts=opts,
         )
         return model, resid, gains, fit_history  # (every slice left _fit_slices_batched in its final state)
     assert gain_time_basis is None, "a gain time basis must not reach the loop over single times"
@@ -1330,13 +1182,7 @@ def calibrate_and_model_tensor(
                 notebook_progressbar=notebook_progressbar, verbose=verbose, tol=tol, dtype=dtype, maxsteps=maxsteps,
                 graph_mode=graph_mode, n_profile_steps=n_profile_steps, profile_log_dir=profile_log_dir,
                 sky_model_r=sky_model_r, sky_model_i=sky_model_i, model_regularization=model_regularization, gain_basis=gain_basis,
-                gain_solve_sweeps=gain_solve_sweeps, gain_solve_every=gain_solve_every, gain_solve_damping=gain_solve_damping,
-                coeff_solve_rounds=coeff_solve_rounds, coeff_solve_ridge=coeff_solve_ridge, gain_basis_solve_sweeps=gain_basis_solve_sweeps,
-                gain_basis_solve_every=gain_basis_solve_every, gain_basis_solve_damping=gain_basis_solve_damping,
-                gain_basis_solve_ridge=gain_basis_solve_ridge, gain_time_solve_sweeps=gain_time_solve_sweeps,
-                gain_time_solve_every=gain_time_solve_every, gain_time_solve_damping=gain_time_solve_damping,
-                gain_time_solve_ridge=gain_time_solve_ridge, robust_every=robust_every, robust_rounds=robust_rounds,
-                robust_kind=robust_kind, robust_threshold=robust_threshold, **opt_kwargs,
+                **dataclasses.asdict(opts), **opt_kwargs,
             )
             if "robust" in hist:  # (solver units and row order -> the data's units, keyed by antenna numbers)
                 rb = hist["robust"]
@@ -1570,27 +1416,14 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
                         skip_threshold, use_model_snr_weights, optimizer, use_min, freeze_model, tol, maxsteps, n_profile_steps,
                         profile_log_dir, model_regularization, verbose, max_batch, devices, layout, opt_kwargs, correct_model=True,
                         correct_resid=False, device_split=None, gain_basis=None, gain_time_basis=None, fit_quality=False,
-                        gain_solve=(0, 0, 0.5), coeff_solve=(0, 1e-6), gain_basis_solve=(0, 0, 0.5, 1e-6),
-                        gain_time_solve=(0, 0, 0.5, 1e-6), robust=(0, 0, "huber", 3.0)):
+                        opts=FitOptions()):
     """The pol x time loop of calibration.py:1160-1331 with the fits of all unskipped slices issued as batches: per slice
     exactly the host-side steps of the loop body (skip test :1173-1177, rms scale :1178-1182, tensorize :1184-1233, write-back
     :1271-1300, post-hoc renormalisation :1311-1319, residual and calibration state of the outputs :1322-1331), the gradient
     descent of :1244-1269 for up to ``max_batch`` slices at once with per-slice loop control.  Returns ``fit_history``; model,
     resid and gains are complete when it returns.  ``gain_time_basis`` (``[len(times), L]``): the unskipped times of a polarization
     are one batch and one JOINT fit (one loop state, loss = the sum over the times; calibrate_and_model_tensor's docstring).
-    ``gain_solve``: (gain_solve_sweeps, gain_solve_every, gain_solve_damping), ``coeff_solve``: (coeff_solve_rounds, coeff_solve_ridge) of
-    calibrate_and_model_tensor, ``gain_basis_solve``: its (gain_basis_solve_sweeps, _every, _damping, _ridge), which stand in for
-    ``gain_solve`` on a fit with a frequency gain basis, ``gain_time_solve``: its (gain_time_solve_sweeps, _every, _damping, _ridge), which
-    stand in for them on the joint fit of a gain time basis, ``robust``: its (robust_every, robust_rounds, robust_kind, robust_threshold)."""
-    rb_every, rb_rounds, rb_kind, rb_threshold = robust
-    gs_sweeps, gs_every, gs_damping = gain_solve
-    cs_rounds, cs_ridge = coeff_solve
-    gbs_on = bool(gain_basis_solve[0] or gain_basis_solve[1])
-    if gbs_on:
-        gs_sweeps, gs_every, gbs_damping, gbs_ridge = gain_basis_solve
-    gts_on = bool(gain_time_solve[0] or gain_time_solve[1])
-    if gts_on:
-        gs_sweeps, gs_every, gts_damping, gts_ridge = gain_time_solve
+    ``opts``: the closed-form and robust keywords of calibrate_and_model_tensor (``fit_loop.FitOptions``)."""
     OPTIMIZERS[optimizer]  # unknown optimizer -> KeyError, like calibration.py:571
     dtype = np.dtype(dtype)
     layout = layout or "shared"
@@ -1700,63 +1533,9 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
         else:
             fitter.set_regularization(None)
         fitter.set_optimizer(optimizer, **opt_kwargs)
-        nsingular = gb_singular = None
-        if gts_on:  # the joint fit of a time basis: one system over the times, so no slice mask
-            sweep = lambda n, slice_mask=None, **kw: fitter.solve_gain_time_coeffs(n, damping=gts_damping, ridge=gts_ridge, **kw)["nsingular"]  # noqa: E731
-        elif gbs_on:  # a basis fit: its sweeps stand where the per-channel sweeps stand
-            sweep = lambda n, **kw: fitter.solve_gain_coeffs(n, damping=gbs_damping, ridge=gbs_ridge, **kw)["nsingular"]  # noqa: E731
-        else:
-            sweep = lambda n, **kw: fitter.solve_gains(n, damping=gs_damping, **kw)  # noqa: E731
-        if cs_rounds > 0:  # alternating least squares: rounds of (the coefficients in closed form, then the gain sweeps)
-            for _ in range(cs_rounds):
-                nsingular = fitter.solve_coeffs(ridge=cs_ridge)["nsingular"]
-                if gs_sweeps > 0:
-                    gb_singular = sweep(gs_sweeps)
-        elif gs_sweeps > 0:  # the coefficients are initialised: the gains in closed form before any descent step
-            gb_singular = sweep(gs_sweeps)
-        if n_profile_steps > 0:
-            fitter.timing_enable(True)
-            fitter.run_slices(n_profile_steps, record=False, freeze_model=freeze_model)
-            os.makedirs(profile_log_dir, exist_ok=True)
-            with open(os.path.join(profile_log_dir, f"calamity_amd_profile_{datetime.datetime.now():%Y%m%d_%H%M%S_%f}.json"), "w") as f:
-                json.dump(dict(n_profile_steps=n_profile_steps, slices=nt, fused_basis_kernel=fitter.timing_get()), f)
-            fitter.timing_enable(False)
-        fitter.run_slices(1, record=False, freeze_model=freeze_model)  # the unrecorded step of calibration.py:693
-        robust_out = None
-        if rb_every > 0:  # per loop the reweights it took part in; per baseline row what its last one reported
-            robust_out = dict(rounds=np.zeros(1 if joint else nt, dtype=np.int64), ndown_bl=np.zeros(nt * prob.nbls), scale_bl=np.zeros(nt * prob.nbls))
-        if gs_every > 0 or rb_every > 0:
-            # the recorded loop in chunks (every slice's loop state persists from run to run); a slice whose loop has ended is held
-            # in the chunks that follow, as one call would leave it, and takes no part in the reweighting and the gain solves between
-            # the chunks (_check_robust: the two share one chunk length)
-            nl = 1 if joint else nt  # loops: a joint fit has one
-            parts, over, nupd, issued = [[] for _ in range(nl)], np.zeros(nl, dtype=bool), np.zeros(nl, dtype=np.int64), 0
-            while issued < maxsteps and not np.all(over):
-                n = min(gs_every or rb_every, maxsteps - issued)
-                for t, (part, stopped, nu) in enumerate(fitter.run_slices(n, record=True, tol=tol, use_min=use_min, freeze_model=freeze_model)):
-                    if not over[t]:
-                        parts[t].append(part)
-                        nupd[t] += nu
-                        over[t] = stopped or len(part) < n
-                issued += n
-                if issued < maxsteps and not np.all(over):
-                    fitter.hold_slices(over)
-                    if robust_out is not None:
-                        todo_rb = ~over if rb_rounds == 0 else ~over & (robust_out["rounds"] < rb_rounds)
-                        if np.any(todo_rb):
-                            rw = fitter.robust_weights(kind=rb_kind, threshold=rb_threshold, slice_mask=todo_rb)
-                            rows_rb = np.repeat(todo_rb, len(rw["scale_bl"]) // nl)  # (a joint fit: one loop over all the rows)
-                            robust_out["ndown_bl"][rows_rb] = rw["ndown_bl"][rows_rb]
-                            robust_out["scale_bl"][rows_rb] = rw["scale_bl"][rows_rb]
-                            robust_out["rounds"] += todo_rb
-                    if gs_every > 0:
-                        if cs_rounds > 0:
-                            nsingular = fitter.solve_coeffs(ridge=cs_ridge, slice_mask=~over, reset_coeff_moments=True)["nsingular"]
-                        gb_singular = sweep(max(1, gs_sweeps), slice_mask=~over, reset_gain_moments=True)
-            fitter.hold_slices(None)
-            results = [(np.concatenate(parts[t]), bool(over[t]), int(nupd[t])) for t in range(nl)]
-        else:
-            results = fitter.run_slices(maxsteps, record=True, tol=tol, use_min=use_min, freeze_model=freeze_model)
+        results, nsingular, sweep_singular, robust_out = drive(
+            fitter, opts, 1 if joint else nt, nt * prob.nbls if joint else prob.nbls, maxsteps, tol, use_min, freeze_model,
+            n_profile_steps, profile_log_dir, dict(slices=nt))
         if joint:
             results = results * nt  # one loop, one loss history: every time of the fit reports it
         cur = fitter.get_params(0)
@@ -1779,24 +1558,17 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
         quality = fitter.fit_quality(gm_r, gm_i) if fit_quality else None
         echo(f"{datetime.datetime.now()} ... fitted.\n", verbose=verbose)
         return dict(results=results, m_r=m_r, m_i=m_i, gm_r=gm_r, gm_i=gm_i, quality=quality, nsingular=nsingular, robust=robust_out,
-                    gb_singular=int(gb_singular or 0) if gbs_on else None, gt_singular=int(gb_singular or 0) if gts_on else None)
+                    sweep_singular=sweep_singular)
 
     def post(batch, out):
         for t, (sl, res) in enumerate(zip(batch, out["results"])):
             rows, ga = slice(t * prob.nbls, (t + 1) * prob.nbls), slice(t * prob.nants, (t + 1) * prob.nants)
             _insert_model_rows(model, sl["time"], sl["pol"], ants_map, prob, out["m_r"][rows], out["m_i"][rows], scale_factor=sl["rmsdata"])
             insert_gains_into_uvcal(uvcal=gains, time=sl["time"], polarization=sl["pol"], gains_re=out["gm_r"][ga], gains_im=out["gm_i"][ga])
-            fit_history[sl["polnum"]][sl["time_index"]] = {"loss": [dtype.type(l) for l in res[0]]}
-            if out.get("nsingular") is not None:
-                fit_history[sl["polnum"]][sl["time_index"]]["coeff_solve_singular"] = int(out["nsingular"])
-            if out.get("gb_singular") is not None:
-                fit_history[sl["polnum"]][sl["time_index"]]["gain_basis_solve_singular"] = int(out["gb_singular"])
-            if out.get("gt_singular") is not None:
-                fit_history[sl["polnum"]][sl["time_index"]]["gain_time_solve_singular"] = int(out["gt_singular"])
-            if out.get("robust") is not None:
-                rb = out["robust"]
-                fit_history[sl["polnum"]][sl["time_index"]]["robust"] = robust_history(rb["rounds"][0 if joint else t],
-                                                                                      rb["ndown_bl"][rows], rb["scale_bl"][rows], sl["rmsdata"], prob, gains.ant_array)
+            rb = out["robust"]
+            if rb is not None:
+                rb = robust_history(rb["rounds"][0 if joint else t], rb["ndown_bl"][rows], rb["scale_bl"][rows], sl["rmsdata"], prob, gains.ant_array)
+            fit_history[sl["polnum"]][sl["time_index"]] = history_entry(opts, res[0], dtype, out["nsingular"], out["sweep_singular"], rb)
             if out.get("quality") is not None:  # (before the post-hoc renormalisation, which leaves g_i conj(g_j) m as it is)
                 q = out["quality"]
                 insert_fit_quality(gains, fit_history[sl["polnum"]][sl["time_index"]], sl["time"], sl["pol"],
