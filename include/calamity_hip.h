@@ -309,7 +309,12 @@ int cal_solver_fit_quality(cal_solver* s, const void* g_r, const void* g_i, doub
  * baseline row: nothing leaves the row, so a sharded fit issues NO collective under a communicator or exchange hook.  Every call starts
  * from w0, never from the previous w; the weights are not renormalised, so losses before and after a call are under different weights
  * and are not comparable.  The median is exact (a bisection on the IEEE bit pattern of e, integer counts): two calls give the same bits.
- * A NaN in e orders above every number.
+ * Non-finite samples of S_b (w0 > 0, data not finite) take what the lines above give literally.  A NaN in e orders above every number,
+ * +inf included: a row in which fewer than n_b - (n_b + 1) // 2 + 1 samples are NaN has a number for its median, and a row whose
+ * median is a NaN (or zero) keeps w = w0 and reports scale 0, count 0.  Behind a finite scale a NaN sample has z2 = NaN, for which both
+ * comparisons are false: psi is NaN under HUBER and CAUCHY (the weight becomes NaN and the sample is not counted in ndown_bl) and 0
+ * under CLIP (weight w0 * 0 = 0; counted, so under CLIP ndown_bl stays the number of weights the call set to zero).  An infinite
+ * sample has psi = 0 under all three kinds and is counted.  The finite samples of such a row are weighted as in any other row.
  *   kind: CAL_ROBUST_NONE copies w0 back for the selected slices (and frees nothing); HUBER, CAUCHY, CLIP as above; anything else, or a
  *   threshold that is not finite and > 0, is CAL_ERR_INVALID.  Problem, data, coefficients and gains must be set (CAL_ERR_STATE).
  *   slice_mask: [nslices] bytes or NULL (all slices): the rows of a slice whose byte is 0 (slice of a row = its first antenna row /
