@@ -99,6 +99,10 @@ class CoeffSolveResult(C.Structure):
     _fields_ = [("nsolved", C.c_int32), ("nsingular", C.c_int32)]
 
 
+class FitErrorsCounts(C.Structure):
+    _fields_ = [("nsolved", C.c_int32), ("nsingular", C.c_int32)]
+
+
 class GainCoeffSolveDesc(C.Structure):
     _fields_ = [("nsweeps", C.c_int32), ("reset_gain_moments", C.c_int32), ("damping", C.c_double), ("ridge", C.c_double), ("slice_mask", C.c_void_p)]
 
@@ -169,6 +173,7 @@ SYMBOLS = {
     "cal_solver_get_weights": (C.c_int, [_P, _P, C.c_int]),
     "cal_solver_solve_coeffs": (C.c_int, [_P, C.POINTER(CoeffSolveDesc), C.POINTER(CoeffSolveResult)]),
     "cal_solver_set_coeff_solve_scratch": (C.c_int, [_P, C.c_int64]),
+    "cal_solver_fit_errors": (C.c_int, [_P, C.c_double, _P, _P, _P, _P, _P, C.POINTER(FitErrorsCounts)]),
     "cal_solver_solve_gain_coeffs": (C.c_int, [_P, C.POINTER(GainCoeffSolveDesc), C.POINTER(GainCoeffSolveResult)]),
     "cal_solver_solve_gain_time_coeffs": (C.c_int, [_P, C.POINTER(GainTimeSolveDesc), C.POINTER(GainTimeSolveResult)]),
     "cal_solver_get_gain_coeff_moments": (C.c_int, [_P] + [_P] * 8 + [C.POINTER(C.c_int64)]),

@@ -255,6 +255,22 @@ class SliceBatchFitter:
         outs = self._each(lambda r, s: s.fit_quality(g_r, g_i))
         return dict(outs[0], **{k: self._scatter([o[k] for o in outs], self.rows) for k in ("chisq_bl", "wsum_bl")})
 
+    def fit_errors(self, ridge=1e-6, model_var=True, gain_var=True, coeffs=True):
+        """``HipFitSolver.fit_errors`` on the global arrays: ``gain_var`` ``[nt * nants, nfreqs]`` (with several workers the library
+        has summed ``den`` over the workers: worker 0's), ``model_var``, ``leverage_bl``, ``nsamp_bl`` with their rows and
+        ``coeff_var`` with its coefficients put back into the global slice-major order like ``model()`` and ``get_params()``; the
+        counts are summed."""
+        outs = self._each(lambda r, s: s.fit_errors(ridge=ridge, model_var=model_var, gain_var=gain_var, coeffs=coeffs))
+        out = {k: sum(o[k] for o in outs) for k in ("nsolved", "nsingular")}
+        for k in ("model_var", "leverage_bl", "nsamp_bl"):
+            if k in outs[0]:
+                out[k] = self._scatter([o[k] for o in outs], self.rows)
+        if "coeff_var" in outs[0]:
+            out["coeff_var"] = self._scatter([o["coeff_var"] for o in outs], self.cidx)
+        if "gain_var" in outs[0]:
+            out["gain_var"] = outs[0]["gain_var"]
+        return out
+
     def robust_weights(self, kind="huber", threshold=3.0, slice_mask=None):
         """``HipFitSolver.robust_weights`` on every worker (``slice_mask``: one entry per slice of the batch; one entry for a ``joint``
         fitter): each worker reweights its own baseline rows, nothing is exchanged.  ``scale_bl``, ``ndown_bl`` ``[nt * nbls]`` put

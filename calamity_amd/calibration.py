@@ -22,6 +22,7 @@ import concurrent.futures
 import copy
 import dataclasses
 import datetime
+import os
 import threading
 
 import numpy as np
@@ -820,6 +821,68 @@ def fit_quality_arrays(q, rms=1.0):
             ratio(q["chisq_bl"], q["wsum_bl"]))
 
 
+def fit_errors_arrays(e, chisq_bl, rms=1.0):
+    """The outputs of ``HipFitSolver.fit_errors`` of ONE slice (solver units; any of ``leverage_bl``, ``gain_var``, ``model_var`` may be
+    missing) and the slice's ``chisq_bl`` (``fit_quality``) as what ``fit_history`` reports.  With ``n`` the samples with ``w != 0``
+    and ``p = sum leverage_bl + #{(a, f): gain_var > 0}`` the parameters the fit spent on them::
+
+        chisq_red_bl = chisq_bl / (nsamp_bl - leverage_bl)        nan where the denominator is <= 0
+        noise_scale  = sum chisq_bl / (n - p)                     1.0 with underdetermined = True where n - p < 1
+        gain_std     = sqrt(noise_scale gain_var)                 [nants, nfreqs], dimensionless
+        model_std    = rms sqrt(noise_scale model_var)            [nbls, nfreqs] float32, the data's units (``rms``: the slice's
+                                                                  ``data_scale_factor``, as in ``fit_quality_arrays``)
+
+    Returns a dict with ``noise_scale``, ``underdetermined``, ``n``, ``p`` and, where their inputs are given, ``leverage_bl``,
+    ``chisq_red_bl``, ``gain_std``, ``model_std``."""
+    chisq_bl = np.asarray(chisq_bl, dtype=np.float64)
+    nsamp = np.asarray(e["nsamp_bl"], dtype=np.float64)
+    out = {}
+    n, p = float(np.sum(nsamp)), 0.0
+    if "leverage_bl" in e:
+        lev = np.asarray(e["leverage_bl"], dtype=np.float64)
+        dof = nsamp - lev
+        out["leverage_bl"] = lev
+        out["chisq_red_bl"] = np.divide(chisq_bl, dof, out=np.full_like(chisq_bl, np.nan), where=dof > 0)
+        p += float(np.sum(lev))
+    if "gain_var" in e:
+        p += float(np.count_nonzero(np.asarray(e["gain_var"]) > 0))
+    under = n - p < 1.0
+    scale = 1.0 if under else float(np.sum(chisq_bl)) / (n - p)
+    out.update(noise_scale=scale, underdetermined=bool(under), n=n, p=p)
+    if "gain_var" in e:
+        out["gain_std"] = np.sqrt(scale * np.asarray(e["gain_var"], dtype=np.float64))
+    if "model_var" in e:
+        out["model_std"] = (float(rms) * np.sqrt(scale * np.asarray(e["model_var"], dtype=np.float64))).astype(np.float32)
+    return out
+
+
+def insert_fit_errors(gain_std, uvcal, hist, time, polarization, e, chisq_bl, rms, prob, nsingular=None):
+    """File one (polarization, time) slice's fit errors (``fit_errors_arrays``): ``hist["errors"]`` with ``noise_scale``,
+    ``underdetermined``, ``nsingular`` and, unless the model was frozen, ``leverage_per_baseline`` and ``chisq_red_per_baseline`` (dicts
+    ``{(ant0, ant1): value}`` with antenna NUMBERS like ``chisq_per_baseline``) and, where ``model_var`` was asked for, ``model_std``
+    ``[rows, nfreqs]`` with its ``antpairs``; the slice's plane of ``gain_std`` (``[Nants, Nfreqs, Ntimes, Njones]`` or ``None``)."""
+    a = fit_errors_arrays(e, chisq_bl, rms)
+    ants = np.asarray(uvcal.ant_array)
+    keys = [(int(ants[i]), int(ants[j])) for i, j in zip(prob.bl_ant0, prob.bl_ant1)]
+    entry = {"noise_scale": a["noise_scale"], "underdetermined": a["underdetermined"], "nsingular": int(e.get("nsingular", 0) if nsingular is None else nsingular)}
+    if "leverage_bl" in a:
+        entry["leverage_per_baseline"] = {k: float(v) for k, v in zip(keys, a["leverage_bl"])}
+        entry["chisq_red_per_baseline"] = {k: float(v) for k, v in zip(keys, a["chisq_red_bl"])}
+    if "model_std" in a:
+        entry["model_std"], entry["antpairs"] = a["model_std"], keys
+    hist["errors"] = entry
+    if gain_std is not None and "gain_std" in a:
+        polnum = np.where(np.asarray(uvcal.jones_array) == polstr2num(polarization, x_orientation=uvcal.x_orientation))[0][0]
+        gindt = np.where(np.isclose(uvcal.time_array, time, atol=1e-7, rtol=0.0))[0][0]
+        gain_std[:, :, gindt, polnum] = a["gain_std"]
+
+
+def _fit_errors_mode(fit_errors):
+    if fit_errors not in (False, True, "samples"):
+        raise ValueError(f"fit_errors must be False, True or 'samples', got {fit_errors!r}")
+    return fit_errors
+
+
 def insert_fit_quality(uvcal, hist, time, polarization, q, rms, prob):
     """Write one (polarization, time) slice's fit quality (``fit_quality_arrays``) into ``uvcal.quality_array[a, f, t, pol]`` and
     ``uvcal.total_quality_array[f, t, pol]`` (``(Nfreqs, Ntimes, Njones)``, created when ``None``) and, as
@@ -894,6 +957,8 @@ def calibrate_and_model_tensor(
     robust_rounds=0,
     robust_kind="huber",
     robust_threshold=3.0,
+    fit_errors=False,
+    fit_errors_ridge=1e-6,
     **opt_kwargs,
 ):
     """Simultaneous calibration and foreground fitting -- calibration.py:963-1331, same arguments, defaults and
@@ -945,6 +1010,19 @@ def calibrate_and_model_tensor(
       ``fit_history[polnum][time_index]["chisq_per_baseline"]`` a dict ``{(ant0, ant1): rms^2 sum_f e / sum_f w}`` with antenna
       numbers, one entry per baseline of the fit.  0 where the weights sum to 0.  A skipped slice keeps zeros and has no dict.  One
       device pass after the fit (``HipFitSolver.fit_quality``); no step of the fit changes.
+    * ``fit_errors`` / ``fit_errors_ridge`` (default off: no call changes by a bit): report how well the fit is determined
+      (``HipFitSolver.fit_errors``: one device pass after the fit, at the reported parameters, on the data and weights the fit used).
+      ``fit_history[polnum][time_index]["errors"]`` holds ``leverage_per_baseline`` (the parameters the model spent on each baseline)
+      and ``chisq_red_per_baseline = chisq_bl / (nsamp_bl - leverage_bl)`` (``nan`` where the denominator is <= 0), dicts keyed by
+      antenna numbers like ``chisq_per_baseline``; ``noise_scale = chisq / (n - p)`` with ``n`` the samples of non-zero weight and
+      ``p = sum leverage + #{(a, f): den > 0}`` (1.0 with ``underdetermined = True`` where ``n - p < 1``); ``nsingular``.
+      ``fit_errors="samples"`` adds ``model_std`` ``[rows, nfreqs]`` float32, the standard deviation of the model before the gains in the
+      data's units, with ``antpairs`` (as large as the data, hence on request).  ``fit_history["gain_std"]``
+      ``[Nants, Nfreqs, Ntimes, Njones]`` is ``sqrt(noise_scale gain_var)``, dimensionless, zero where the gain is flagged.  These are
+      CONDITIONAL errors -- the gains held fixed for the model, the model and the other gains for a gain: the block diagonal of the
+      Gauss-Newton matrix, which ignores the gain-foreground covariance and the degeneracies, so they are lower bounds.  With a gain
+      basis (frequency or time) ``gain_std`` is absent: the variance of a basis gain is ``b_f^T N_a^-1 b_f`` with the projected normal
+      matrix, which is not computed (``p`` then counts no gain parameters).  With ``freeze_model`` only the gain part runs (no leverage tables).
     * ``gain_solve_sweeps`` / ``gain_solve_every`` / ``gain_solve_damping`` (defaults 0, 0, 0.5: descent only, no call changes by a bit):
       solve the gains in closed form.  With the foreground model held fixed the chi-square is linear least squares in one antenna's
       gain while the others are held fixed; a damped StefCal sweep (``HipFitSolver.solve_gains``) sets every antenna's gain to
@@ -1074,6 +1152,13 @@ def calibrate_and_model_tensor(
     if fit_quality and getattr(gains, "total_quality_array", None) is None:
         # (here, once, not by whichever slice is written first: with parallel_fits the slices are written from several threads)
         gains.total_quality_array = np.zeros(gain4(gains.quality_array).shape[1:], dtype=np.float64)
+    errs = None
+    if _fit_errors_mode(fit_errors):
+        if not (np.isfinite(float(fit_errors_ridge)) and float(fit_errors_ridge) >= 0.0):
+            raise ValueError(f"fit_errors_ridge must be finite and >= 0, got {fit_errors_ridge!r}")
+        with_gains = gain_basis is None and gain_time_basis is None
+        errs = dict(samples=fit_errors == "samples", ridge=float(fit_errors_ridge), with_gains=with_gains,
+                    gain_std=np.zeros(gain4(gains.gain_array).shape, dtype=np.float64) if with_gains else None)
     if sky_model is None and model_regularization is not None:
         echo(f"{datetime.datetime.now()} Sky model is None. Initializing from data...\n", verbose=verbose)
         # data / (g_i conj(g_j)) with the initial gains (:1131-1136).  With the unity, unflagged gains built just above that is
@@ -1121,8 +1206,9 @@ def calibrate_and_model_tensor(
             verbose=verbose, max_batch=max_batch, devices=devices, layout=layout, opt_kwargs=opt_kwargs,
             correct_model=correct_model, correct_resid=correct_resid, device_split=device_split, gain_basis=gain_basis,
             gain_time_basis=gain_time_basis, fit_quality=fit_quality,
-            opts=opts,
+            opts=opts, errs=errs,
         )
+        _file_gain_std(fit_history, errs, gains)
         return model, resid, gains, fit_history  # (every slice left _fit_slices_batched in its final state)
     assert gain_time_basis is None, "a gain time basis must not reach the loop over single times"
     if layout is not None:
@@ -1195,6 +1281,10 @@ def calibrate_and_model_tensor(
             insert_gains_into_uvcal(uvcal=gains, time=time, polarization=pol, gains_re=g_r, gains_im=g_i)
             if fit_quality:  # at the reported parameters, on the data and weights the fit used (the solver still holds them)
                 insert_fit_quality(gains, hist, time, pol, solver.fit_quality(g_r, g_i), rmsdata, prob)
+            if errs is not None and (errs["with_gains"] or not freeze_model):
+                solver.set_params(g_r, g_i)  # the reported gains (use_min: the minimum's); the fit is over, the next one sets its own
+                e = solver.fit_errors(ridge=errs["ridge"], model_var=errs["samples"], gain_var=errs["with_gains"], coeffs=not freeze_model)
+                insert_fit_errors(errs["gain_std"], gains, hist, time, pol, e, solver.fit_quality(g_r, g_i)["chisq_bl"], rmsdata, prob)
         else:
             echo(f"{datetime.datetime.now()}: Only {frac_unflagged * 100}-percent of data unflagged. Skipping...\n", verbose=verbose)
             flag_poltime(resid, time=time, polarization=pol)
@@ -1229,7 +1319,15 @@ def calibrate_and_model_tensor(
         fit_history[polnum] = fit_history_p
     if pool is not None:
         pool.shutdown()
-    return _finish_outputs(uvdata, model, resid, gains, fit_history, correct_model, correct_resid)
+    out = _finish_outputs(uvdata, model, resid, gains, fit_history, correct_model, correct_resid)
+    _file_gain_std(fit_history, errs, gains)
+    return out
+
+
+def _file_gain_std(fit_history, errs, gains):
+    """``fit_history["gain_std"]`` of a call with ``fit_errors`` and free per-channel gains: zero where the gain is flagged."""
+    if errs is not None and errs["gain_std"] is not None:
+        fit_history["gain_std"] = np.where(gain4(gains.flag_array), 0.0, errs["gain_std"])
 
 
 def _output_finisher(uvdata, model, resid, gains, correct_model, correct_resid):
@@ -1416,7 +1514,7 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
                         skip_threshold, use_model_snr_weights, optimizer, use_min, freeze_model, tol, maxsteps, n_profile_steps,
                         profile_log_dir, model_regularization, verbose, max_batch, devices, layout, opt_kwargs, correct_model=True,
                         correct_resid=False, device_split=None, gain_basis=None, gain_time_basis=None, fit_quality=False,
-                        opts=FitOptions()):
+                        opts=FitOptions(), errs=None):
     """The pol x time loop of calibration.py:1160-1331 with the fits of all unskipped slices issued as batches: per slice
     exactly the host-side steps of the loop body (skip test :1173-1177, rms scale :1178-1182, tensorize :1184-1233, write-back
     :1271-1300, post-hoc renormalisation :1311-1319, residual and calibration state of the outputs :1322-1331), the gradient
@@ -1556,9 +1654,14 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
         m_r, m_i = fitter.model()
         # at the reported parameters (every slice's own minimum with use_min), on the data and weights the fit used
         quality = fitter.fit_quality(gm_r, gm_i) if fit_quality else None
+        errors = None
+        if errs is not None and (errs["with_gains"] or not freeze_model):
+            fitter.set_params(gm_r, gm_i)  # the reported gains (use_min: every slice's minimum); the fit is over, the next one sets its own
+            errors = fitter.fit_errors(ridge=errs["ridge"], model_var=errs["samples"], gain_var=errs["with_gains"], coeffs=not freeze_model)
+            errors["chisq_bl"] = (quality if quality is not None else fitter.fit_quality(gm_r, gm_i))["chisq_bl"]
         echo(f"{datetime.datetime.now()} ... fitted.\n", verbose=verbose)
         return dict(results=results, m_r=m_r, m_i=m_i, gm_r=gm_r, gm_i=gm_i, quality=quality, nsingular=nsingular, robust=robust_out,
-                    sweep_singular=sweep_singular)
+                    sweep_singular=sweep_singular, errors=errors)
 
     def post(batch, out):
         for t, (sl, res) in enumerate(zip(batch, out["results"])):
@@ -1574,6 +1677,15 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
                 insert_fit_quality(gains, fit_history[sl["polnum"]][sl["time_index"]], sl["time"], sl["pol"],
                                    dict(chisq_ant=q["chisq_ant"][ga], wsum_ant=q["wsum_ant"][ga], chisq_bl=q["chisq_bl"][rows], wsum_bl=q["wsum_bl"][rows]),
                                    sl["rmsdata"], prob)
+            if out.get("errors") is not None:
+                e = out["errors"]
+                coefs = slice(t * prob.ncoeffs, (t + 1) * prob.ncoeffs)
+                part = {k: e[k][{"gain_var": ga, "coeff_var": coefs}.get(k, rows)] for k in ("coeff_var", "model_var", "leverage_bl", "nsamp_bl", "gain_var") if k in e}
+                nsing = None
+                if "coeff_var" in part:  # (the library counts over the batch: the slice's own are its groups with an all-zero coeff_var)
+                    nsing = sum(1 for g in range(prob.ngrps) if not np.any(part["coeff_var"][prob.grp_coff[g] : prob.grp_coff[g + 1]]))
+                insert_fit_errors(errs["gain_std"], gains, fit_history[sl["polnum"]][sl["time_index"]], sl["time"], sl["pol"], part,
+                                  e["chisq_bl"][rows], sl["rmsdata"], prob, nsingular=nsing)
             if res[1]:
                 echo(f"Tolerance thresshold met for time {sl['time_index']}. Terminating...\n ", verbose=verbose)
             if not freeze_model and model_regularization == "post_hoc":  # (:1311-1319)
@@ -1906,6 +2018,9 @@ def read_calibrate_and_model_dpss(
     gpu_memory_limit=None,
     precision=32,
     use_autocorrs_in_weights=False,
+    fit_errors=False,
+    fit_errors_samples=False,
+    fit_errors_ridge=1e-6,
     **calibration_kwargs,
 ):
     """File driver of the DPSS fit -- calibration.py:1659-1817 (same arguments, returns and output files).
@@ -1917,7 +2032,11 @@ def read_calibrate_and_model_dpss(
     pyuvdata, HDF5 tools and FITS readers open.  ``gpu_index`` picks the MI355X the solvers are created on (default: device 0, all of them are
     visible); ``gpu_memory_limit`` [GiB] makes a fit that needs more device memory raise ``MemoryError`` instead of
     configuring an allocator pool.  As in the reference the baseline cuts are applied to the data only (:1767-1783
-    select on ``uvd`` twice and never on the model) and ``fitted_info_outfilename`` is accepted but nothing is written.
+    select on ``uvd`` twice and never on the model) and ``fitted_info_outfilename`` is accepted but nothing is written --
+    unless ``fit_errors`` (``fit_errors_samples``: with ``model_std``; ``fit_errors_ridge``: see ``calibrate_and_model_tensor``) is on:
+    then ``gain_std`` (where the gains are free per channel) and the per-baseline tables go there as an ``.npz`` archive: ``antpairs``
+    ``[rows, 2]`` and, ``[Npols, Ntimes, rows]`` each with ``nan`` for a skipped slice, ``leverage_per_baseline``,
+    ``chisq_red_per_baseline``; ``noise_scale`` ``[Npols, Ntimes]``.
     """
     uvd = _read_uvdata(input_data_files)
     weights = get_auto_weights(uvd) if use_autocorrs_in_weights else None
@@ -1932,7 +2051,8 @@ def read_calibrate_and_model_dpss(
     _DEVICE["memory_limit_gib"] = gpu_memory_limit
     try:
         model_fit, resid_fit, gains_fit, fit_info = calibrate_and_model_dpss(
-            uvdata=uvd, sky_model=uvd_model, gains=uvc, dtype=dtype, weights=weights, **calibration_kwargs
+            uvdata=uvd, sky_model=uvd_model, gains=uvc, dtype=dtype, weights=weights, **calibration_kwargs,
+            **(dict(fit_errors="samples" if fit_errors_samples else True, fit_errors_ridge=fit_errors_ridge) if fit_errors or fit_errors_samples else {}),
         )
     finally:
         _DEVICE.update(saved)
@@ -1943,9 +2063,42 @@ def read_calibrate_and_model_dpss(
         gains_fit.write_calfits(gain_outfilename, clobber=clobber)
     if model_outfilename is not None:
         model_fit.write_uvh5(model_outfilename, clobber=clobber)
+    if (fit_errors or fit_errors_samples) and fitted_info_outfilename is not None:
+        _write_fit_errors(fitted_info_outfilename, fit_info, clobber)
     fit_info["calibration_kwargs"] = calibration_kwargs
     fit_info["calibration_kwargs"]["dtype"] = dtype
     return model_fit, resid_fit, gains_fit, fit_info
+
+
+def fit_errors_tables(fit_info):
+    """The arrays the file driver writes from a ``fit_history`` with ``errors`` entries (``read_calibrate_and_model_dpss``)."""
+    pols = sorted(k for k in fit_info if isinstance(k, int))
+    ntimes = 1 + max([t for p in pols for t in fit_info[p]], default=-1)
+    entries = [h["errors"] for p in pols for h in fit_info[p].values() if "errors" in h]
+    out = {"noise_scale": np.full((len(pols), ntimes), np.nan)}
+    pairs = next((list(h["leverage_per_baseline"]) for h in entries if "leverage_per_baseline" in h), None)
+    if pairs is not None:
+        out["antpairs"] = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+        for k in ("leverage_per_baseline", "chisq_red_per_baseline"):
+            out[k] = np.full((len(pols), ntimes, len(pairs)), np.nan)
+    for i, p in enumerate(pols):
+        for t, h in fit_info[p].items():
+            if "errors" not in h:
+                continue
+            out["noise_scale"][i, t] = h["errors"]["noise_scale"]
+            for k in ("leverage_per_baseline", "chisq_red_per_baseline"):
+                if k in h["errors"]:
+                    out[k][i, t] = [h["errors"][k][ap] for ap in pairs]
+    if "gain_std" in fit_info:
+        out["gain_std"] = np.asarray(fit_info["gain_std"])
+    return out
+
+
+def _write_fit_errors(filename, fit_info, clobber):
+    if os.path.exists(filename) and not clobber:
+        raise IOError(f"{filename} exists; use clobber=True to overwrite")
+    with open(filename, "wb") as f:  # (a file object: np.savez appends no suffix to the name the caller gave)
+        np.savez(f, **fit_errors_tables(fit_info))
 
 
 def input_output_parser():
@@ -2002,6 +2155,13 @@ def fitting_argparser():
     sp.add_argument("--fit_quality", default=False, action="store_true",
                     help="write the weighted mean squared residual per antenna and channel into the gains' quality column and the total "
                          "over antennas into TOTQLTY; default: zeros")
+    sp.add_argument("--fit_errors", default=False, action="store_true",
+                    help="report the errors of the fit: a standard deviation per gain, the leverage and the reduced chi-square per baseline "
+                         "(conditional errors: lower bounds); the file driver writes them to fitted_info_outfilename as an .npz archive; default: off")
+    sp.add_argument("--fit_errors_samples", default=False, action="store_true",
+                    help="--fit_errors plus the standard deviation of the fitted model at every sample (as large as the data)")
+    sp.add_argument("--fit_errors_ridge", type=float, default=1e-6,
+                    help="ridge of the factorisation behind --fit_errors, as a fraction of the mean diagonal of a group's normal matrix; default 1e-6")
     sp.add_argument("--gain_solve_sweeps", type=int, default=0,
                     help="solve the gains in closed form (damped StefCal sweeps) this many times before the first descent step; default 0: descent only")
     sp.add_argument("--gain_solve_every", type=int, default=0,

@@ -29,6 +29,7 @@
 #include "robust_weight_kernels.hpp"
 #include "gain_solve_kernels.hpp"
 #include "coeff_solve_kernels.hpp"
+#include "fit_error_kernels.hpp"
 #include "gain_basis_solve_kernels.hpp"
 #include "gain_time_solve_kernels.hpp"
 #include "problem_plan.hpp"
@@ -164,6 +165,8 @@ struct cal_solver {
   virtual int hold_slices(const uint8_t* mask) = 0;
   virtual int solve_coeffs(const cal_coeff_solve_desc* d, cal_coeff_solve_result* res) = 0;
   virtual int set_coeff_solve_scratch(int64_t bytes) = 0;
+  virtual int fit_errors(double ridge, double* coeff_var, double* model_var, double* leverage_bl, double* nsamp_bl, double* gain_var,
+                         cal_fit_errors_counts* counts) = 0;
   virtual int solve_gain_coeffs(const cal_gain_coeff_solve_desc* d, cal_gain_coeff_solve_result* res) = 0;
   virtual int solve_gain_time_coeffs(const cal_gain_time_solve_desc* d, cal_gain_time_solve_result* res) = 0;
   virtual int get_gain_coeff_moments(void* ym_r, void* ym_i, void* yv_r, void* yv_i, void* cm_r, void* cm_i, void* cv_r, void* cv_i, int64_t* t) = 0;
@@ -219,6 +222,14 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
   static constexpr int64_t kCsScratchDefault = 256ll << 20;  // bytes of cs_n + cs_d a chunk may take (one group alone may take more)
   static constexpr int kCsLdsDoubles = 16384;                 // 128 KB: a factor of up to 126 vectors stays in LDS
   int64_t cs_bound = kCsScratchDefault;
+  // fit_errors (fit_error_kernels.hpp): a plan of its own (the chunks also hold W, so they are cut elsewhere than solve_coeffs'): the
+  // groups with this plan's offsets, order, Gram work list, W offsets, the leverage kernel's work list; per chunk N (fe_n), the factor
+  // (fe_d) and W (fe_w); rhs of the Gram kernel (unused), ok [ngrps] ints + the two counters (fe_ok), the partial sums
+  // [nbls][slots] (fe_part), the outputs coeff_var | leverage_bl | nsamp_bl (fe_out) and, only when asked for, model_var (fe_mv)
+  DevBuf fe_grp, fe_order, fe_work, fe_woff, fe_lwork, fe_n, fe_d, fe_w, fe_rhs, fe_ok, fe_part, fe_out, fe_mv;
+  struct FeChunkRange { int g0, g1, w0, w1, l0, l1; size_t lds; };  // positions in fe_order / fe_work / fe_lwork
+  std::vector<FeChunkRange> fe_chunks;
+  int fe_npieces = 0;
   // solve_gain_coeffs (gain_basis_solve_kernels.hpp): N_a of a chunk of antenna rows in T (gbs_n), its factor in double where it does not
   // fit LDS (gbs_d), rhs [nants][2][K] T, the two counters; the chunks share cs_bound
   DevBuf gbs_n, gbs_d, gbs_rhs, gbs_cnt;
@@ -1985,6 +1996,8 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     cs_d.release();
     cs_cnt.release();
     cs_chunks.clear();
+    for (DevBuf* b : {&fe_grp, &fe_order, &fe_work, &fe_woff, &fe_lwork, &fe_n, &fe_d, &fe_w, &fe_rhs, &fe_ok, &fe_part, &fe_out, &fe_mv}) b->release();
+    fe_chunks.clear();
   }
   int set_coeff_solve_scratch(int64_t bytes) override {
     if (bytes < 0) return fail(CAL_ERR_INVALID, "set_coeff_solve_scratch: negative bound");
@@ -2090,6 +2103,174 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     if (res) {
       res->nsolved = counts[0];
       res->nsingular = counts[1];
+    }
+    return CAL_OK;
+  }
+
+  // ---- cal_solver_fit_errors -------------------------------------------------------------------------------------
+  // build_coeff_solve_plan's cut with W (padded to whole 16 x 16 tiles, T) counted in a chunk's bytes, and per chunk the leverage
+  // kernel's work: every run of a group's baselines on one row block x every 64 channels of the (half) band.
+  int build_fit_error_plan() {
+    if (!fe_chunks.empty()) return CAL_OK;
+    std::vector<CsGroup> grp = h_cs_grp;
+    std::vector<long long> h_tile(nbls);
+    HIP_TRY(copy_sync(h_tile.data(), bl_tile.p, (size_t)nbls * sizeof(long long), hipMemcpyDeviceToHost));
+    std::vector<int> order(ngrps);
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return grp[a].nvec > grp[b].nvec; });
+    const int npieces = ((fold ? nfreqs / 2 : fpad) + kFePiece - 1) / kFePiece;
+    std::vector<CsWork> work;
+    std::vector<FeWork> lwork;
+    std::vector<long long> woff(ngrps, 0);
+    std::vector<FeChunkRange> chunks;
+    long long n_max = 0, d_max = 0, w_max = 0;
+    for (int p = 0; p < ngrps;) {
+      long long noff = 0, doff = 0, wo = 0;
+      int max_nvec = 0;
+      FeChunkRange ch{p, p, (int)work.size(), 0, (int)lwork.size(), 0, 0};
+      for (; p < ngrps; ++p) {
+        CsGroup& g = grp[order[p]];
+        const long long nn = (long long)g.nvec * g.nvec, dd = (long long)(g.nvec + 2) * g.nvec, ww = (long long)fe_pad(g.nvec) * fe_pad(g.nvec);
+        if (p > ch.g0 && (noff + nn + wo + ww) * (long long)sizeof(T) + (doff + dd) * 8 > cs_bound) break;
+        g.noff = noff;
+        g.doff = doff;
+        woff[order[p]] = wo;
+        noff += nn;
+        doff += dd;
+        wo += ww;
+        max_nvec = std::max(max_nvec, g.nvec);
+        const int nb = (g.nvec + kNsBlock - 1) / kNsBlock;
+        for (int bi = 0; bi < nb; ++bi)
+          for (int bj = 0; bj <= bi; ++bj) work.push_back(CsWork{order[p], bi, bj, 0});
+        for (int b = g.b0; b < g.b1;) {
+          int e = b + 1;
+          while (e < g.b1 && h_tile[e] == h_tile[b]) ++e;
+          for (int piece = 0; piece < npieces; ++piece) lwork.push_back(FeWork{order[p], b, e, piece});
+          b = e;
+        }
+      }
+      ch.g1 = p;
+      ch.w1 = (int)work.size();
+      ch.l1 = (int)lwork.size();
+      const long long want = (long long)(max_nvec + 2) * (max_nvec | 1);
+      ch.lds = (size_t)std::min<long long>(want, kCsLdsDoubles) * sizeof(double);
+      chunks.push_back(ch);
+      n_max = std::max(n_max, noff);
+      d_max = std::max(d_max, doff);
+      w_max = std::max(w_max, wo);
+    }
+    auto put = [&](DevBuf& buf, const void* src, size_t bytes) {
+      CAL_TRY(buf.alloc(bytes, false));
+      HIP_TRY(copy_sync(buf.p, src, bytes, hipMemcpyHostToDevice));
+      return (int)CAL_OK;
+    };
+    CAL_TRY(put(fe_grp, grp.data(), (size_t)ngrps * sizeof(CsGroup)));
+    CAL_TRY(put(fe_order, order.data(), (size_t)ngrps * sizeof(int)));
+    CAL_TRY(put(fe_work, work.data(), work.size() * sizeof(CsWork)));
+    CAL_TRY(put(fe_woff, woff.data(), (size_t)ngrps * sizeof(long long)));
+    CAL_TRY(put(fe_lwork, lwork.data(), lwork.size() * sizeof(FeWork)));
+    CAL_TRY(fe_n.alloc((size_t)n_max * sizeof(T), false));
+    CAL_TRY(fe_d.alloc((size_t)d_max * sizeof(double), false));
+    CAL_TRY(fe_w.alloc((size_t)w_max * sizeof(T), false));
+    CAL_TRY(fe_rhs.alloc(2 * (size_t)ncoef * sizeof(T)));
+    CAL_TRY(fe_ok.alloc(((size_t)ngrps + 2) * sizeof(int)));
+    CAL_TRY(fe_part.alloc((size_t)nbls * (fold ? 2 : 1) * npieces * sizeof(double)));
+    CAL_TRY(fe_out.alloc(((size_t)ncoef + 2 * (size_t)nbls) * sizeof(double)));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fit_error_factor_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                kCsLdsDoubles * (int)sizeof(double)));
+    fe_npieces = npieces;
+    fe_chunks = chunks;
+    return CAL_OK;
+  }
+
+  // cal_solver_fit_errors: the model pass of model() and coeff_solve_rows_kernel for q, then per chunk of groups coeff_gram_kernel (as
+  // it is; its rhs is not used), fit_error_factor_kernel and fit_error_leverage_kernel, then fit_error_rows_kernel; for gain_var the
+  // model pass once more with gain_solve_rows_kernel, gain_solve_ant_kernel and the exchange of its den plane.
+  int fit_errors(double ridge, double* coeff_var, double* model_var, double* leverage_bl, double* nsamp_bl, double* gain_var,
+                 cal_fit_errors_counts* counts) override {
+    HIP_TRY(hipSetDevice(device));
+    CAL_TRY(require_set("fit_errors", true));
+    if (!(ridge >= 0.0) || !std::isfinite(ridge)) return fail(CAL_ERR_INVALID, "fit_errors: ridge = %g must be finite and >= 0", ridge);
+    if (gain_var && yb_on())
+      return fail(CAL_ERR_UNSUPPORTED, "fit_errors: gain_var with a gain basis set (cal_solver_set_gain_basis, cal_solver_set_gain_time_basis): the variance of "
+                  "a basis gain is b_f^T N_a^-1 b_f with the projected N_a, which is not implemented here; pass gain_var = NULL (the coefficient "
+                  "outputs use the expanded gains), or detach the basis (nvec = 0) first");
+    const bool want_lev = model_var || leverage_bl;
+    const bool want_coef = coeff_var || want_lev;
+    int cnt[2] = {0, 0};
+    if (want_coef || nsamp_bl) {
+      CAL_TRY(build_fit_error_plan());
+      const int nslot = (fold ? 2 : 1) * fe_npieces;
+      double* o_cv = fe_out.as<double>();
+      double* o_lev = o_cv + ncoef;
+      double* o_ns = o_lev + nbls;
+      int* ok = fe_ok.as<int>();
+      int* dcnt = ok + ngrps;
+      const size_t mv_bytes = (size_t)nbls * nfreqs * sizeof(double);
+      if (model_var && fe_mv.bytes < mv_bytes) CAL_TRY(fe_mv.alloc(mv_bytes, false));
+      if (want_coef) {
+        T* q_rows = nullptr;
+        T *u_r = nullptr, *u_i = nullptr;
+        CAL_TRY(model_pass(3, [&](T* model_r, T* model_i, T* third) {
+          u_r = model_r, u_i = model_i, q_rows = third;
+          hipLaunchKernelGGL(coeff_solve_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, u_r, u_i, q_rows, data_r.as<T>(), data_i.as<T>(),
+                             wgts.as<T>(), gains.as<T2>(), bl_ant.as<int2>(), nbls, nfreqs, fpad);
+        }));
+        // a singular group keeps zeros
+        HIP_TRY(hipMemsetAsync(fe_ok.p, 0, ((size_t)ngrps + 2) * sizeof(int), stream));
+        HIP_TRY(hipMemsetAsync(o_cv, 0, ((size_t)ncoef + (size_t)nbls) * sizeof(double), stream));
+        if (want_lev) HIP_TRY(hipMemsetAsync(fe_part.p, 0, (size_t)nbls * nslot * sizeof(double), stream));
+        if (model_var) HIP_TRY(hipMemsetAsync(fe_mv.p, 0, mv_bytes, stream));
+        for (const FeChunkRange& ch : fe_chunks) {
+          hipLaunchKernelGGL(coeff_gram_kernel<T>, dim3(ch.w1 - ch.w0), dim3(256), 0, stream, tiles.as<T>(), bl_tile.as<long long>(), u_r,
+                             u_i, q_rows, fe_grp.as<CsGroup>(), fe_work.as<CsWork>() + ch.w0, fe_n.as<T>(), fe_rhs.as<T>(), ncoef, nfreqs, fpad,
+                             fold ? 1 : 0);
+          hipLaunchKernelGGL(fit_error_factor_kernel<T>, dim3(ch.g1 - ch.g0), dim3(256), ch.lds, stream, fe_n.as<T>(), fe_d.as<double>(),
+                             fe_grp.as<CsGroup>(), fe_order.as<int>() + ch.g0, fe_woff.as<long long>(), fe_w.as<T>(), o_cv, ok, ridge, dcnt,
+                             kCsLdsDoubles);
+          if (want_lev && ch.l1 > ch.l0)
+            hipLaunchKernelGGL(fit_error_leverage_kernel<T>, dim3(ch.l1 - ch.l0), dim3(256), 0, stream, tiles.as<T>(), bl_tile.as<long long>(),
+                               q_rows, fe_grp.as<CsGroup>(), fe_woff.as<long long>(), ok, fe_lwork.as<FeWork>() + ch.l0, fe_w.as<T>(),
+                               model_var ? fe_mv.as<double>() : nullptr, fe_part.as<double>(), nfreqs, fpad, fold ? 1 : 0, fe_npieces);
+          HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipMemcpyAsync(cnt, dcnt, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
+      }
+      if (leverage_bl || nsamp_bl) {
+        hipLaunchKernelGGL(fit_error_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, fe_part.as<double>(), wgts.as<T>(), nbls, nfreqs,
+                           fpad, nslot, leverage_bl ? o_lev : nullptr, nsamp_bl ? o_ns : nullptr);
+        HIP_TRY(hipGetLastError());
+      }
+      if (coeff_var) HIP_TRY(hipMemcpyAsync(coeff_var, o_cv, (size_t)ncoef * sizeof(double), hipMemcpyDeviceToHost, stream));
+      if (model_var) HIP_TRY(hipMemcpyAsync(model_var, fe_mv.p, mv_bytes, hipMemcpyDeviceToHost, stream));
+      if (leverage_bl) HIP_TRY(hipMemcpyAsync(leverage_bl, o_lev, (size_t)nbls * sizeof(double), hipMemcpyDeviceToHost, stream));
+      if (nsamp_bl) HIP_TRY(hipMemcpyAsync(nsamp_bl, o_ns, (size_t)nbls * sizeof(double), hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipStreamSynchronize(stream));
+    }
+    if (gain_var) {
+      CAL_TRY(build_solve_lists());
+      const size_t nant_out = (size_t)nants * nfreqs;
+      if (gs_out.bytes < 3 * nant_out * sizeof(double)) CAL_TRY(gs_out.alloc(3 * nant_out * sizeof(double)));
+      T *p_r = nullptr, *p_i = nullptr, *q_rows = nullptr;
+      CAL_TRY(model_pass(3, [&](T* model_r, T* model_i, T* third) {
+        p_r = model_r, p_i = model_i, q_rows = third;
+        hipLaunchKernelGGL(gain_solve_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, p_r, p_i, q_rows, data_r.as<T>(), data_i.as<T>(),
+                           wgts.as<T>(), bl_ant.as<int2>(), nbls, nfreqs, fpad);
+      }));
+      constexpr int V = 16 / (int)sizeof(T);
+      const int cblocks = (fpad + 64 * V - 1) / (64 * V);
+      hipLaunchKernelGGL(gain_solve_ant_kernel<T>, dim3(nants * cblocks), dim3(256), 0, stream, p_r, p_i, q_rows, gains.as<T2>(), gs_ptr.as<int>(),
+                         gs_ent.as<int2>(), nants, nfreqs, fpad, gs_out.as<double>());
+      HIP_TRY(hipGetLastError());
+      double* den = gs_out.as<double>() + 2 * nant_out;
+      // the den planes of every rank's baselines add up to the array's: ONE all-reduce of nants nfreqs doubles
+      if (comm_on()) CAL_TRY(all_reduce(den, nant_out, CAL_XCHG_F64, CAL_XCHG_SUM));
+      HIP_TRY(copy_sync(gain_var, den, nant_out * sizeof(double), hipMemcpyDeviceToHost));
+      for (size_t k = 0; k < nant_out; ++k) gain_var[k] = gain_var[k] > 0.0 ? 1.0 / gain_var[k] : 0.0;
+    }
+    if (counts) {
+      counts->nsolved = cnt[0];
+      counts->nsingular = cnt[1];
     }
     return CAL_OK;
   }
@@ -2345,7 +2526,7 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     if (!b) return fail(CAL_ERR_INVALID, "memory_bytes: null");
     const DevBuf* all[] = {&tiles, &bl_tile, &bl_ant, &items, &ant_ptr, &ant_ent, &coef_grp, &grp_coff, &grp_item_ptr, &item_goff,
                            &data_r, &data_i, &wgts, &gains, &gains_alt, &gains_m, &gains_v, &gains_snap, &coef, &coef_m, &coef_v, &coef_snap,
-                           &q0, &q1, &comm, &scal, &gcp0, &gcp1, &gc0, &gc1, &part, &state, &losses, &scratch, &model_buf, &fq_out, &fq_gains, &rw_w0, &rw_out, &gs_out, &gs_ptr, &gs_ent, &gs_mask, &cs_grp, &cs_order, &cs_work, &cs_n, &cs_d, &cs_rhs, &cs_cnt, &gbs_n, &gbs_d, &gbs_rhs, &gbs_cnt, &gts_m, &gts_n, &gts_rhsa, &gts_d, &gts_rhs, &gts_cnt,
+                           &q0, &q1, &comm, &scal, &gcp0, &gcp1, &gc0, &gc1, &part, &state, &losses, &scratch, &model_buf, &fq_out, &fq_gains, &rw_w0, &rw_out, &gs_out, &gs_ptr, &gs_ent, &gs_mask, &cs_grp, &cs_order, &cs_work, &cs_n, &cs_d, &cs_rhs, &cs_cnt, &fe_grp, &fe_order, &fe_work, &fe_woff, &fe_lwork, &fe_n, &fe_d, &fe_w, &fe_rhs, &fe_ok, &fe_part, &fe_out, &fe_mv, &gbs_n, &gbs_d, &gbs_rhs, &gbs_cnt, &gts_m, &gts_n, &gts_rhsa, &gts_d, &gts_rhs, &gts_cnt,
                            &mf_ops, &mf_panels, &mf_map, &members, &heads, &lamb_vars, &lamb_cvar_ptr, &lamb_partial, &lamb_ratio, &lamb_glob, &lamb_slot, &slice_coff, &slice_ipart_ptr, &slice_ipart_idx,
                            &slice_ppart_ptr, &slice_ppart_idx, &slice_cblk, &gb_B, &gb_Bt, &gb_g0, &gb_y, &gb_ym, &gb_yv, &gb_ysnap, &gb_proj, &tb_B, &tb_Bt, &tb_z, &tb_pf};
     int64_t n = 0;
@@ -2699,6 +2880,11 @@ int cal_solver_solve_gains(cal_solver* s, const cal_gain_solve_desc* desc) { NEE
 int cal_solver_hold_slices(cal_solver* s, const uint8_t* mask) { NEED(s); return s->hold_slices(mask); }
 int cal_solver_solve_coeffs(cal_solver* s, const cal_coeff_solve_desc* desc, cal_coeff_solve_result* result) { NEED(s); return s->solve_coeffs(desc, result); }
 int cal_solver_set_coeff_solve_scratch(cal_solver* s, int64_t bytes) { NEED(s); return s->set_coeff_solve_scratch(bytes); }
+int cal_solver_fit_errors(cal_solver* s, double ridge, double* coeff_var, double* model_var, double* leverage_bl, double* nsamp_bl, double* gain_var,
+                          cal_fit_errors_counts* counts) {
+  NEED(s);
+  return s->fit_errors(ridge, coeff_var, model_var, leverage_bl, nsamp_bl, gain_var, counts);
+}
 int cal_solver_get_gain_coeff_moments(cal_solver* s, void* ym_r, void* ym_i, void* yv_r, void* yv_i, void* cm_r, void* cm_i, void* cv_r, void* cv_i, int64_t* t) {
   NEED(s);
   return s->get_gain_coeff_moments(ym_r, ym_i, yv_r, yv_i, cm_r, cm_i, cv_r, cv_i, t);

@@ -14,7 +14,8 @@ instances of both dtypes), `gain_solve_rows_kernel`, `gain_solve_ant_kernel`,
 `gain_solve_apply_kernel` (gain_solve_kernels.hpp), `coeff_solve_rows_kernel`, `coeff_gram_kernel`, `coeff_chol_kernel`
 (coeff_solve_kernels.hpp), `gain_basis_gram_kernel`, `gain_basis_chol_kernel` (gain_basis_solve_kernels.hpp; both pairs are built on the
 shared Gram and Cholesky core of normal_solve.hpp), `gain_time_kron_kernel`, `gain_time_chol_kernel`, `gain_time_chan_kernel`
-(gain_time_solve_kernels.hpp): no scratch, no spilled VGPRs."""
+(gain_time_solve_kernels.hpp), `fit_error_factor_kernel`, `fit_error_leverage_kernel`, `fit_error_rows_kernel` (fit_error_kernels.hpp):
+no scratch, no spilled VGPRs."""
 import re
 import sys
 
@@ -49,9 +50,9 @@ for line in sys.stdin:
                                              "quality_rows_kernel", "quality_ant_kernel", "robust_rows_kernel", "gain_solve_rows_kernel", "gain_solve_ant_kernel",
                                              "gain_solve_apply_kernel", "coeff_solve_rows_kernel", "coeff_gram_kernel", "coeff_chol_kernel",
                                              "gain_basis_gram_kernel", "gain_basis_chol_kernel", "gain_time_kron_kernel", "gain_time_chol_kernel",
-                                             "gain_time_chan_kernel")):
+                                             "gain_time_chan_kernel", "fit_error_factor_kernel", "fit_error_leverage_kernel", "fit_error_rows_kernel")):
         # the kernels around the update of a gain-basis fit, the two of the fit-quality pass, the one of the robust reweighting, the three of the gain solve, the three
-        # of the coefficient solve, the two of the gain-coefficient solve and the three of the time-basis solve keep their accumulators in
+        # of the coefficient solve, the two of the gain-coefficient solve, the three of the time-basis solve and the three of the fit errors keep their accumulators in
         # registers: no scratch
         m = re.search(r"remark:\s+(ScratchSize \[bytes/lane\]|VGPRs Spill): (\d+)", line)
         if m and int(m.group(2)) != 0:

@@ -3,7 +3,8 @@
 //   N = A^T diag(w) A   [n][n], real symmetric        rhs = A^T u   [n], complex        (N + ridge (tr N / n) I) delta = rhs,
 // N and rhs in T on the matrix cores, the solve in double.  Here are
 //   the Gram core     normal_gram_njt, normal_gram_step, normal_gram_store: one workgroup per 64 x 64 block (bi, bj <= bi) of N
-//   the solve         normal_chol_solve: one workgroup per N, Cholesky and both substitutions
+//   the solve         normal_chol_solve: one workgroup per N, Cholesky and both substitutions (normal_chol_load and normal_chol_factor,
+//                     which the factor kernel of fit_error_kernels.hpp calls too)
 // A kernel brings what is its own: which rows A has and where they lie, the three per-channel vectors w, u_r, u_i of a step, where
 // N, rhs and the update go.  N and rhs are accumulated in a fixed order (no atomics on reals: two calls give the same bits).
 #pragma once
@@ -86,19 +87,15 @@ __device__ __forceinline__ void normal_gram_store(T* __restrict__ N, int n, int 
   }
 }
 
-// (N + ridge (tr N / n) I) x = rhs for both right-hand sides, by the whole workgroup (256 threads), everything in double.  The
-// lower triangle of N (+ the ridge on its diagonal) and, as rows n and n + 1, the two right-hand sides form one [n + 2][ld] matrix M
-// (LDS or global scratch, the caller's choice; s_red: 256 doubles of LDS).  Left-looking Cholesky by columns: column j of every row
-// i >= j (the right-hand-side rows included, which is the forward substitution) takes its dot product with row j, then the column is
-// divided by the pivot's root.  Back substitution by columns; x replaces the two rows behind the last column.  Returns false, the same
-// in every thread, when N is singular: tr N <= 0 or not finite, or a pivot <= 0 or not finite.  Returns true behind a barrier, x in
-// M[n] and M[n + 1].
+// What every caller of the Cholesky shares (normal_chol_solve below, fit_error_factor_kernel of fit_error_kernels.hpp), by the whole
+// workgroup (256 threads), everything in double; s_red: 256 doubles of LDS.
+// normal_chol_load: the trace of N in a fixed order, then the lower triangle of N + ridge (tr N / n) I into rows [0, n) of M (pitch
+// ld).  Returns false, the same in every thread, when tr N <= 0 or not finite.  No barrier behind the writes: the caller may fill
+// further rows of M first; normal_chol_factor begins with one.
 template <typename T>
-__device__ __forceinline__ bool normal_chol_solve(double* M, int ld, int n, const T* __restrict__ Ng, const T* __restrict__ rhs_r,
-                                                  const T* __restrict__ rhs_i, double ridge, double* s_red) {
+__device__ __forceinline__ bool normal_chol_load(double* M, int ld, int n, const T* __restrict__ Ng, double ridge, double* s_red) {
 #pragma clang fp contract(off)
   const int tid = threadIdx.x;
-  // the trace, in a fixed order
   double part = 0;
   for (int k = tid; k < n; k += 256) part += (double)Ng[(long long)k * n + k];
   s_red[tid] = part;
@@ -116,14 +113,19 @@ __device__ __forceinline__ bool normal_chol_solve(double* M, int ld, int n, cons
     const int i = (int)(idx / n), k = (int)(idx - (long long)i * n);
     if (k <= i) M[(long long)i * ld + k] = (double)Ng[idx] + (k == i ? shift : 0.0);
   }
-  for (int k = tid; k < n; k += 256) {
-    M[(long long)n * ld + k] = (double)rhs_r[k];
-    M[(long long)(n + 1) * ld + k] = (double)rhs_i[k];
-  }
+  return true;
+}
+// normal_chol_factor: left-looking Cholesky by columns of the first n columns of the [nrows][ld] matrix M, nrows >= n.  Column j of
+// every row i >= j (rows [n, nrows) are right-hand sides, for which this is the forward substitution) takes its dot product with row
+// j, then the column is divided by the pivot's root.  Returns false, the same in every thread, at a pivot <= 0 or not finite; true
+// behind a barrier, L in the lower triangle of rows [0, n).
+__device__ __forceinline__ bool normal_chol_factor(double* M, int ld, int n, int nrows) {
+#pragma clang fp contract(off)
+  const int tid = threadIdx.x;
   __syncthreads();
   for (int j = 0; j < n; ++j) {
     const double* __restrict__ Lj = M + (long long)j * ld;
-    for (int i = j + tid; i < n + 2; i += 256) {
+    for (int i = j + tid; i < nrows; i += 256) {
       double* Li = M + (long long)i * ld;
       double s = Li[j];
       for (int k = 0; k < j; ++k) s -= Li[k] * Lj[k];
@@ -134,10 +136,29 @@ __device__ __forceinline__ bool normal_chol_solve(double* M, int ld, int n, cons
     if (!(d > 0.0) || !isfinite(d)) return false;
     __syncthreads();  // every thread has read the pivot
     const double root = sqrt(d);
-    for (int i = j + 1 + tid; i < n + 2; i += 256) M[(long long)i * ld + j] /= root;
+    for (int i = j + 1 + tid; i < nrows; i += 256) M[(long long)i * ld + j] /= root;
     if (tid == 0) M[(long long)j * ld + j] = root;
     __syncthreads();
   }
+  return true;
+}
+
+// (N + ridge (tr N / n) I) x = rhs for both right-hand sides, by the whole workgroup (256 threads), everything in double.  The
+// lower triangle of N (+ the ridge on its diagonal) and, as rows n and n + 1, the two right-hand sides form one [n + 2][ld] matrix M
+// (LDS or global scratch, the caller's choice; s_red: 256 doubles of LDS): normal_chol_load, normal_chol_factor over all n + 2 rows,
+// then the back substitution by columns; x replaces the two rows behind the last column.  Returns false, the same in every thread,
+// when N is singular: tr N <= 0 or not finite, or a pivot <= 0 or not finite.  Returns true behind a barrier, x in M[n] and M[n + 1].
+template <typename T>
+__device__ __forceinline__ bool normal_chol_solve(double* M, int ld, int n, const T* __restrict__ Ng, const T* __restrict__ rhs_r,
+                                                  const T* __restrict__ rhs_i, double ridge, double* s_red) {
+#pragma clang fp contract(off)
+  const int tid = threadIdx.x;
+  if (!normal_chol_load(M, ld, n, Ng, ridge, s_red)) return false;
+  for (int k = tid; k < n; k += 256) {
+    M[(long long)n * ld + k] = (double)rhs_r[k];
+    M[(long long)(n + 1) * ld + k] = (double)rhs_i[k];
+  }
+  if (!normal_chol_factor(M, ld, n, n + 2)) return false;
   // L^T x = z for the two rows z = M[n], M[n + 1].  Column j leaves z[j] alone (every thread divides it for itself), so no thread
   // waits for another's write inside the loop; the same division once more, behind the loop, puts x in place of z.
   double* yr = M + (long long)n * ld;

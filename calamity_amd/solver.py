@@ -318,6 +318,45 @@ class HipFitSolver:
                                                     _ptr(out["chisq_bl"]), _ptr(out["wsum_bl"])))
         return out
 
+    def fit_errors(self, ridge=1e-6, model_var=True, gain_var=True, coeffs=True):
+        """The errors of the fit at the solver's current parameters (cal_solver_fit_errors): the inverses of the curvature matrices
+        of ``solve_coeffs`` and ``solve_gains``.  With ``G = g_i conj(g_j)`` from the full (expanded) gains, ``q = w |G|^2``, ``A_b``
+        the row block of baseline row ``b`` in fitting group ``gamma`` and ``a_{b,f}`` its row ``f``::
+
+            N_gamma = sum_{b in gamma} A_b^T diag(q_b) A_b      N_r = N_gamma + ridge (tr N_gamma / nvec) I      L L^T = N_r
+            coeff_var[k]    = (N_r^-1)[k][k]                                [ncoef]         (re and im of c_k: this variance / 2 each)
+            model_var[b][f] = a_{b,f}^T N_r^-1 a_{b,f} = |L^-1 a_{b,f}|^2   [nbls, nfreqs]  (variance of m = A c, before the gains)
+            leverage_bl[b]  = sum_f q[b][f] model_var[b][f]                 [nbls]          (q model_var lies in [0, 1])
+            nsamp_bl[b]     = #{f : w[b][f] != 0}                           [nbls]
+            gain_var[a][f]  = 1 / den_a[f], den_a = sum_b w |m|^2 |g_other|^2 of ``solve_gains``; 0 where den_a <= 0   [nants, nfreqs]
+
+        All float64, variances for unit noise scale: exact where the weights are inverse noise variances.  These are CONDITIONAL
+        errors -- the gains are held fixed for the coefficients and the model, the model and the other gains for a gain: the block
+        diagonal of the Gauss-Newton matrix.  The gain-foreground covariance and with it the degeneracies are ignored, so they are
+        lower bounds.  With ``ridge = 0`` and ``N`` of full rank the ``leverage_bl`` of a group add up to its ``nvec``.  A singular
+        group (wholly flagged, or a non-positive pivot) keeps zeros and counts in ``nsingular``.
+
+        ``model_var=False`` leaves the ``[nbls, nfreqs]`` plane out (it is as large as the data); ``gain_var=False`` skips the antenna
+        part; ``coeffs=False`` skips the coefficient part (``coeff_var``, ``model_var``, ``leverage_bl``).  With a gain basis attached
+        ``gain_var=True`` raises: the variance of a basis gain is ``b_f^T N_a^-1 b_f`` with the projected ``N_a``, which is not
+        computed.  The parameters, the optimizer's slots, the weights and the loop state are untouched.  Under an exchange only
+        ``den`` is summed over the ranks (one ``[nants, nfreqs]`` float64 plane); every other output is this rank's own rows and groups.
+        Returns a dict of the arrays asked for plus ``nsolved`` and ``nsingular``."""
+        out = {}
+        if coeffs:
+            out["coeff_var"] = np.empty(self.ncoeffs, dtype=np.float64)
+            if model_var:
+                out["model_var"] = np.empty((self.nbls, self.nfreqs), dtype=np.float64)
+            out["leverage_bl"] = np.empty(self.nbls, dtype=np.float64)
+        out["nsamp_bl"] = np.empty(self.nbls, dtype=np.float64)
+        if gain_var:
+            out["gain_var"] = np.empty((self.nants, self.nfreqs), dtype=np.float64)
+        cnt = _lib.FitErrorsCounts()
+        _lib.check(self._lib.cal_solver_fit_errors(self._h, float(ridge), *(_ptr(out.get(k)) for k in ("coeff_var", "model_var", "leverage_bl",
+                                                                                                      "nsamp_bl", "gain_var")), C.byref(cnt)))
+        out["nsolved"], out["nsingular"] = int(cnt.nsolved), int(cnt.nsingular)
+        return out
+
     def _slice_mask(self, mask):
         if mask is None:
             return None

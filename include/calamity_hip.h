@@ -421,6 +421,42 @@ int cal_solver_solve_coeffs(cal_solver* s, const cal_coeff_solve_desc* desc, cal
 /* The scratch bound of cal_solver_solve_coeffs in bytes (0: the default, 256 MiB).  The coefficients do not depend on it: tests use
  * it to send a small problem through several chunks. */
 int cal_solver_set_coeff_solve_scratch(cal_solver* s, int64_t bytes);
+/* The errors of a fit (no counterpart in the reference): the inverses of the curvature matrices that cal_solver_solve_coeffs and
+ * cal_solver_solve_gains build.  In their notation -- baseline row b of fitting group gamma has antennas (i, j) and row block
+ * A_b [nfreqs][nvec], a_{b,f} is row f of A_b, d, w are the solver's data and current weights, g its full (expanded) gains, m = A c at
+ * the current coefficients:
+ *   G[b][f]   = g_i[f] conj(g_j[f])          q[b][f] = w |G|^2
+ *   N_gamma   = sum_{b in gamma} A_b^T diag(q_b) A_b      N_r = N_gamma + ridge (tr N_gamma / nvec) I      L L^T = N_r
+ *   coeff_var[k]    = (N_r^-1)[k][k]                               [ncoef]           (re and im of c_k each have this variance / 2)
+ *   model_var[b][f] = a_{b,f}^T N_r^-1 a_{b,f} = |L^-1 a_{b,f}|^2  [nbls][nfreqs]    (variance of m = A c, before the gains)
+ *   lev[b][f]       = q[b][f] model_var[b][f]                      in [0, 1]
+ *   leverage_bl[b]  = sum_f lev[b][f]                              [nbls]            (the parameters the model spent on row b)
+ *   nsamp_bl[b]     = #{f : w[b][f] != 0}                          [nbls]            (an integer, returned as a double)
+ *   gain_var[a][f]  = 1 / den_a[f], den_a = sum_b w |m|^2 |g_other|^2 as in cal_solver_solve_gains (autocorrelations left out);
+ *                     0 where den_a <= 0                           [nants][nfreqs]
+ * All outputs are doubles and variances for unit noise scale: exact where the weights are inverse noise variances 1 / E|n|^2.  They
+ * are CONDITIONAL errors: the gains are held fixed for the coefficients and the model, the model and the other gains for a gain.
+ * That is the block diagonal of the Gauss-Newton matrix; it ignores the gain-foreground covariance and with it the degeneracies,
+ * so these are lower bounds.  With ridge = 0 and N of full rank, sum_{b in gamma} leverage_bl[b] = nvec.
+ * N is formed in the solver's dtype on the matrix cores (coeff_gram_kernel as it is), factorised in double with
+ * cal_solver_solve_coeffs' trace, ridge and singularity tests; W = L^-1 is rounded to the solver's dtype once and |W a|^2 runs on
+ * the matrix cores, its squares summed in double.  A group that is singular by those tests keeps zeros in coeff_var, model_var and
+ * leverage_bl and counts in nsingular.  Channels [nfreqs, fpad) never contribute.  Everything is summed in a fixed order: two calls
+ * give the same bits.
+ *   Any output pointer may be NULL.  Without model_var and leverage_bl the per-sample kernel is not launched; without coeff_var
+ *   too nothing of the coefficient part runs; without gain_var the antenna part does not run.  counts may be NULL.
+ *   ridge >= 0 and finite (CAL_ERR_INVALID); problem, data, coefficients and gains must be set (CAL_ERR_STATE).
+ * Works with nslices > 1, bl_alias, groups of several baselines on several row blocks, both layouts, every kernel path and folded
+ * tiles.  The coefficient outputs work with a frequency or time gain basis attached (the expanded gains are read); gain_var then
+ * fails with CAL_ERR_UNSUPPORTED: the variance of a basis gain is b_f^T N_a^-1 b_f with the projected N_a, which is not computed here.
+ * The groups are worked through in chunks under the bound of cal_solver_set_coeff_solve_scratch (N, the factor in double and W).
+ * Like cal_solver_fit_quality it puts the loop state back: a run continued after the call is bit-identical to one without it.
+ * Under a communicator or exchange hook every fitting group belongs to one rank and each rank fills its own rows: the coefficient
+ * outputs need no exchange.  den is summed over the ranks in ONE all-reduce of nants nfreqs doubles (CAL_XCHG_F64, CAL_XCHG_SUM),
+ * issued only when gain_var is asked for. */
+typedef struct cal_fit_errors_counts { int32_t nsolved; int32_t nsingular; } cal_fit_errors_counts;
+int cal_solver_fit_errors(cal_solver* s, double ridge, double* coeff_var, double* model_var, double* leverage_bl, double* nsamp_bl,
+                          double* gain_var, cal_fit_errors_counts* counts);
 /* The coefficients of a frequency gain basis in closed form (no counterpart in the reference): the damped StefCal sweeps of
  * cal_solver_solve_gains projected on the basis g = g0 + B y of cal_solver_set_gain_basis.  With the other antennas held fixed the
  * chi-square is quadratic in one antenna's y.  num, den are exactly cal_solver_solve_gains': the model pass, then P, Q, then the
