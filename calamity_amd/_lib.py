@@ -119,6 +119,16 @@ class GainTimeSolveResult(C.Structure):
     _fields_ = [("nsolved", C.c_int32), ("nsingular", C.c_int32)]
 
 
+class GaussNewtonDesc(C.Structure):
+    """cal_gauss_newton_desc: at most ``ncg`` iterations of conjugate gradients on (N + lambda_t D) p = rhs per slice, stopped at
+    sqrt(rz / rz0) <= cg_tol; lambda [nslices] doubles, slice_mask [nslices] bytes or NULL (include/calamity_hip.h)."""
+    _fields_ = [("ncg", C.c_int32), ("reset_moments", C.c_int32), ("cg_tol", C.c_double), ("lambda", C.c_void_p), ("slice_mask", C.c_void_p)]
+
+
+class GaussNewtonResult(C.Structure):
+    _fields_ = [("loss_before", C.c_double), ("loss_after", C.c_double), ("cg_residual", C.c_double), ("cg_iters", C.c_int32), ("accepted", C.c_int32)]
+
+
 class RunResult(C.Structure):
     _fields_ = [("nrecorded", C.c_int32), ("stopped", C.c_int32), ("nupdates", C.c_int32), ("nonfinite", C.c_int32)]
 
@@ -169,6 +179,8 @@ SYMBOLS = {
     "cal_solver_fit_quality": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     "cal_solver_solve_gains": (C.c_int, [_P, C.POINTER(GainSolveDesc)]),
     "cal_solver_hold_slices": (C.c_int, [_P, _P]),
+    "cal_solver_normal_product": (C.c_int, [_P] + [_P] * 8),
+    "cal_solver_gauss_newton_step": (C.c_int, [_P, C.POINTER(GaussNewtonDesc), C.POINTER(GaussNewtonResult)]),
     "cal_solver_robust_weights": (C.c_int, [_P, C.POINTER(RobustDesc), _P, _P]),
     "cal_solver_get_weights": (C.c_int, [_P, _P, C.c_int]),
     "cal_solver_solve_coeffs": (C.c_int, [_P, C.POINTER(CoeffSolveDesc), C.POINTER(CoeffSolveResult)]),

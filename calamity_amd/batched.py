@@ -295,6 +295,12 @@ class SliceBatchFitter:
                                                       reset_coeff_moments=reset_coeff_moments))
         return {k: sum(o[k] for o in outs) for k in ("nsolved", "nsingular")}
 
+    def gauss_newton_step(self, ncg=20, lam=1e-3, cg_tol=1e-3, slice_mask=None, reset_moments=False):
+        """``HipFitSolver.gauss_newton_step`` (``lam``, ``slice_mask``: one entry per slice of the batch).  A slice's step needs the slice
+        whole on one worker: with several workers (the fitting groups shared out) the library refuses the call, since the per-slice
+        scalars of conjugate gradients would need an exchange.  Returns the dict of per-slice arrays, the slices in global order."""
+        return self._each(lambda r, s: s.gauss_newton_step(ncg=ncg, lam=lam, cg_tol=cg_tol, slice_mask=slice_mask, reset_moments=reset_moments))[0]
+
     def solve_gain_coeffs(self, nsweeps, damping=0.5, ridge=1e-6, slice_mask=None, reset_gain_moments=False):
         """``HipFitSolver.solve_gain_coeffs`` on every worker (``slice_mask``: one entry per slice of the batch).  With several workers
         each sweep sums the three antenna planes of the workers' baselines in one exchange; ``y`` is replicated, so every worker then

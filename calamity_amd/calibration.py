@@ -28,7 +28,7 @@ import threading
 import numpy as np
 
 from . import cal_utils, modeling, utils
-from .fit_loop import FitOptions, drive, history_entry
+from .fit_loop import FitOptions, GaussNewtonOptions, drive, history_entry, newton_history
 from .problem import FitProblem, coeffs_from_chunks, coeffs_to_chunks, problem_from_chunks
 from .solver import OPTIMIZERS, HipFitSolver
 from .utils import PBARS, echo
@@ -658,6 +658,11 @@ def fit_gains_and_foregrounds(
     robust_rounds=0,
     robust_kind="huber",
     robust_threshold=3.0,
+    gauss_newton_rounds=0,
+    gauss_newton_every=0,
+    gauss_newton_cg_iters=20,
+    gauss_newton_lambda=1e-3,
+    gauss_newton_cg_tol=1e-3,
     **opt_kwargs,
 ):
     """Run the optimization loop that fits gains and foreground coefficients -- calibration.py:447-738.
@@ -681,9 +686,13 @@ def fit_gains_and_foregrounds(
     ``ValueError``.  ``robust_every`` / ``robust_rounds`` / ``robust_kind`` / ``robust_threshold``: iteratively reweighted least squares
     between chunks of the recorded loop, see ``calibrate_and_model_tensor``; here ``fit_history["robust"]`` holds the last reweight in
     solver units and row order, ``{"rounds": n, "ndown_bl": [nbls], "scale_bl": [nbls]}`` (``HipFitSolver.robust_weights``).
+    ``gauss_newton_rounds`` / ``gauss_newton_every`` / ``gauss_newton_cg_iters`` / ``gauss_newton_lambda`` / ``gauss_newton_cg_tol``: joint
+    Gauss-Newton steps over gains and coefficients, see ``calibrate_and_model_tensor``.
     """
     opts = FitOptions.pick(locals())
     opts.check(gain_basis is not None, False, freeze_model, use_min, robust_first=True)
+    newton = GaussNewtonOptions.pick(locals())
+    newton.check(opts, gain_basis is not None, False, freeze_model)
     if gain_basis is not None:
         gain_basis = _check_gain_basis(gain_basis, np.asarray(g_r).shape[-1])
     echo(f"Using {str(dtype)} precision.")
@@ -714,11 +723,11 @@ def fit_gains_and_foregrounds(
         echo(f"{datetime.datetime.now()} Profiling with {n_profile_steps}. And writing output to {profile_log_dir}...")
     echo(f"{datetime.datetime.now()} Building Computational Graph...\n", verbose=verbose)
     echo(f"{datetime.datetime.now()} Performing Gradient Descent...\n", verbose=verbose)
-    ((losses, stopped, _),), nsingular, sweep_singular, robust = drive(
-        solver, opts, 1, prob.nbls, maxsteps, tol, use_min, freeze_model, n_profile_steps, profile_log_dir)
+    ((losses, stopped, _),), nsingular, sweep_singular, robust, gn = drive(
+        solver, opts, 1, prob.nbls, maxsteps, tol, use_min, freeze_model, n_profile_steps, profile_log_dir, newton=newton)
     if robust is not None:  # (solver units and row order: the documented shape of this function)
         robust = {"rounds": int(robust["rounds"][0]), "ndown_bl": robust["ndown_bl"], "scale_bl": robust["scale_bl"]}
-    fit_history = history_entry(opts, losses, dtype, nsingular, sweep_singular, robust)
+    fit_history = history_entry(opts, losses, dtype, nsingular, sweep_singular, robust, newton_history(gn, 0))
     if stopped:
         echo(f"Tolerance thresshold met with delta of {np.abs(losses[-1] - losses[-2]):.2e}. Terminating...\n ", verbose=verbose)
     g_r_opt, g_i_opt, c_r, c_i = solver.get_params(which=1 if (use_min and len(losses) > 0) else 0)
@@ -957,6 +966,11 @@ def calibrate_and_model_tensor(
     robust_rounds=0,
     robust_kind="huber",
     robust_threshold=3.0,
+    gauss_newton_rounds=0,
+    gauss_newton_every=0,
+    gauss_newton_cg_iters=20,
+    gauss_newton_lambda=1e-3,
+    gauss_newton_cg_tol=1e-3,
     fit_errors=False,
     fit_errors_ridge=1e-6,
     **opt_kwargs,
@@ -1102,6 +1116,24 @@ def calibrate_and_model_tensor(
       own median scales it): that is what ``fit_quality`` reports.  ``fit_history[pol][t]["robust"] = {"rounds": n, "downweighted":
       {(ant0, ant1): count}, "scale": {(ant0, ant1): rms^2 scale_b}}`` from the slice's last reweight.  ``fit_quality=True`` then
       reports under the robust weights.  The model, residual and flag outputs are computed as always: no sample is flagged.
+    * ``gauss_newton_rounds`` / ``gauss_newton_every`` / ``gauss_newton_cg_iters`` / ``gauss_newton_lambda`` / ``gauss_newton_cg_tol``
+      (defaults 0, 0, 20, 1e-3, 1e-3: off, no call changes by a bit and no new kernel is launched): Levenberg-damped Gauss-Newton steps over
+      gains and coefficients TOGETHER (``HipFitSolver.gauss_newton_step``).  The descent loop is first-order and the closed forms above
+      are block-wise: alternated they stall in the valley where gains and foregrounds trade against each other.  A step solves
+      ``(N + lambda D) p = rhs`` with the joint ``N = J^H W J``, ``rhs`` minus half the chi-square gradient and ``D`` a diagonal estimate of
+      ``N``, by ``gauss_newton_cg_iters`` iterations of preconditioned conjugate gradients (stopped early at a relative residual of
+      ``gauss_newton_cg_tol``), and keeps the trial parameters iff the slice's loss (regulariser included) is finite and strictly lower.
+      ``gauss_newton_rounds=R``: R steps after the rounds of ``coeff_solve_rounds`` and the start-up sweeps, before the first unrecorded
+      descent step.  ``gauss_newton_every=K``: the recorded loop in chunks of K steps (one chunk length for every ``*_every``,
+      ``ValueError`` if they differ); in every gap, after the reweighting, the coefficient solve and the sweeps, one step on the slices
+      whose loop has not ended, with the optimizer's slots of the accepted slices started over.  The damping is kept per slice:
+      ``gauss_newton_lambda`` at first, a tenth after an accepted step, ten times ``max(lambda, 1e-6)`` after a rejected one; a rejected
+      start-up round is simply followed by the next.  ``ValueError`` with ``gain_basis`` / ``gain_max_dly``, ``gain_time_basis`` /
+      ``gain_time_scale``, ``freeze_model`` (the sweeps are the exact answer for gains alone) and with several devices that share out the
+      fitting groups (``device_split="groups"`` or the automatic choice of it; ``device_split="slices"`` works).
+      ``fit_history[polnum][time_index]["gauss_newton"] = {"steps", "accepted", "lambda", "loss", "cg_iters"}`` (present only with the
+      feature on): the steps the slice took part in, how many were accepted, the damping a next step would use, and per step the
+      loss after it and the iterations it ran.
     * ``parallel_fits`` (default 1): with ``batch_slices=False``, fits that many slices concurrently, each on its own
       solver and HIP stream.
     (Nothing here is steered by environment variables: layout, devices and concurrency are arguments.)"""
@@ -1109,6 +1141,8 @@ def calibrate_and_model_tensor(
         raise ValueError("give gain_basis or gain_max_dly, not both")
     opts = FitOptions.pick(locals())
     opts.check(gain_basis is not None or gain_max_dly is not None, gain_time_basis is not None or gain_time_scale is not None, freeze_model, use_min)
+    newton = GaussNewtonOptions.pick(locals())
+    newton.check(opts, gain_basis is not None or gain_max_dly is not None, gain_time_basis is not None or gain_time_scale is not None, freeze_model)
     if gain_max_dly is not None:
         gain_basis = modeling.gain_dpss_basis(np.asarray(uvdata.freq_array, dtype=np.float64).ravel(), gain_max_dly)
     if gain_time_basis is not None and gain_time_scale is not None:
@@ -1206,7 +1240,7 @@ def calibrate_and_model_tensor(
             verbose=verbose, max_batch=max_batch, devices=devices, layout=layout, opt_kwargs=opt_kwargs,
             correct_model=correct_model, correct_resid=correct_resid, device_split=device_split, gain_basis=gain_basis,
             gain_time_basis=gain_time_basis, fit_quality=fit_quality,
-            opts=opts, errs=errs,
+            opts=opts, errs=errs, newton=newton,
         )
         _file_gain_std(fit_history, errs, gains)
         return model, resid, gains, fit_history  # (every slice left _fit_slices_batched in its final state)
@@ -1268,7 +1302,7 @@ def calibrate_and_model_tensor(
                 notebook_progressbar=notebook_progressbar, verbose=verbose, tol=tol, dtype=dtype, maxsteps=maxsteps,
                 graph_mode=graph_mode, n_profile_steps=n_profile_steps, profile_log_dir=profile_log_dir,
                 sky_model_r=sky_model_r, sky_model_i=sky_model_i, model_regularization=model_regularization, gain_basis=gain_basis,
-                **dataclasses.asdict(opts), **opt_kwargs,
+                **dataclasses.asdict(opts), **dataclasses.asdict(newton), **opt_kwargs,
             )
             if "robust" in hist:  # (solver units and row order -> the data's units, keyed by antenna numbers)
                 rb = hist["robust"]
@@ -1514,14 +1548,15 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
                         skip_threshold, use_model_snr_weights, optimizer, use_min, freeze_model, tol, maxsteps, n_profile_steps,
                         profile_log_dir, model_regularization, verbose, max_batch, devices, layout, opt_kwargs, correct_model=True,
                         correct_resid=False, device_split=None, gain_basis=None, gain_time_basis=None, fit_quality=False,
-                        opts=FitOptions(), errs=None):
+                        opts=FitOptions(), errs=None, newton=GaussNewtonOptions()):
     """The pol x time loop of calibration.py:1160-1331 with the fits of all unskipped slices issued as batches: per slice
     exactly the host-side steps of the loop body (skip test :1173-1177, rms scale :1178-1182, tensorize :1184-1233, write-back
     :1271-1300, post-hoc renormalisation :1311-1319, residual and calibration state of the outputs :1322-1331), the gradient
     descent of :1244-1269 for up to ``max_batch`` slices at once with per-slice loop control.  Returns ``fit_history``; model,
     resid and gains are complete when it returns.  ``gain_time_basis`` (``[len(times), L]``): the unskipped times of a polarization
     are one batch and one JOINT fit (one loop state, loss = the sum over the times; calibrate_and_model_tensor's docstring).
-    ``opts``: the closed-form and robust keywords of calibrate_and_model_tensor (``fit_loop.FitOptions``)."""
+    ``opts``: the closed-form and robust keywords of calibrate_and_model_tensor (``fit_loop.FitOptions``); ``newton``: those of the
+    Gauss-Newton steps (``fit_loop.GaussNewtonOptions``)."""
     OPTIMIZERS[optimizer]  # unknown optimizer -> KeyError, like calibration.py:571
     dtype = np.dtype(dtype)
     layout = layout or "shared"
@@ -1631,9 +1666,9 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
         else:
             fitter.set_regularization(None)
         fitter.set_optimizer(optimizer, **opt_kwargs)
-        results, nsingular, sweep_singular, robust_out = drive(
+        results, nsingular, sweep_singular, robust_out, gn = drive(
             fitter, opts, 1 if joint else nt, nt * prob.nbls if joint else prob.nbls, maxsteps, tol, use_min, freeze_model,
-            n_profile_steps, profile_log_dir, dict(slices=nt))
+            n_profile_steps, profile_log_dir, dict(slices=nt), newton=newton)
         if joint:
             results = results * nt  # one loop, one loss history: every time of the fit reports it
         cur = fitter.get_params(0)
@@ -1661,7 +1696,7 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
             errors["chisq_bl"] = (quality if quality is not None else fitter.fit_quality(gm_r, gm_i))["chisq_bl"]
         echo(f"{datetime.datetime.now()} ... fitted.\n", verbose=verbose)
         return dict(results=results, m_r=m_r, m_i=m_i, gm_r=gm_r, gm_i=gm_i, quality=quality, nsingular=nsingular, robust=robust_out,
-                    sweep_singular=sweep_singular, errors=errors)
+                    sweep_singular=sweep_singular, errors=errors, newton=gn)
 
     def post(batch, out):
         for t, (sl, res) in enumerate(zip(batch, out["results"])):
@@ -1671,7 +1706,8 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
             rb = out["robust"]
             if rb is not None:
                 rb = robust_history(rb["rounds"][0 if joint else t], rb["ndown_bl"][rows], rb["scale_bl"][rows], sl["rmsdata"], prob, gains.ant_array)
-            fit_history[sl["polnum"]][sl["time_index"]] = history_entry(opts, res[0], dtype, out["nsingular"], out["sweep_singular"], rb)
+            fit_history[sl["polnum"]][sl["time_index"]] = history_entry(opts, res[0], dtype, out["nsingular"], out["sweep_singular"], rb,
+                                                                        newton_history(out["newton"], t))
             if out.get("quality") is not None:  # (before the post-hoc renormalisation, which leaves g_i conj(g_j) m as it is)
                 q = out["quality"]
                 insert_fit_quality(gains, fit_history[sl["polnum"]][sl["time_index"]], sl["time"], sl["pol"],
@@ -1702,6 +1738,8 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
     if device_split not in (None, "slices", "groups"):
         raise ValueError(f"device_split={device_split!r}: 'slices', 'groups' or None")
     D = len(devices)
+    newton.check(opts, gain_basis is not None, joint, freeze_model,
+                 groups_split=D > 1 and not (device_split == "slices" or (device_split is None and len(batches) >= D)))
     if D > 1 and (device_split == "slices" or (device_split is None and len(batches) >= D)):
         # Whole batches on different devices: device d fits batches d, d + D, ... on a thread of its own (its solvers live on that
         # thread), nothing is exchanged between devices, and every slice is fitted exactly as it would be on one device.  One prep
@@ -2201,6 +2239,17 @@ def fitting_argparser():
     sp.add_argument("--robust_rounds", type=int, default=0, help="with --robust_every: reweight at most this many times; default 0: after every chunk")
     sp.add_argument("--robust_kind", type=str, default="huber", help="weight function of --robust_every: huber, cauchy or clip; default huber")
     sp.add_argument("--robust_threshold", type=float, default=3.0, help="threshold of the weight function in sigma; default 3")
+    sp.add_argument("--gauss_newton_rounds", type=int, default=0,
+                    help="joint Gauss-Newton steps over gains and coefficients (conjugate gradients on the joint normal matrix) before the first "
+                         "descent step, after the --coeff_solve_rounds rounds and the start-up sweeps; default 0: none")
+    sp.add_argument("--gauss_newton_every", type=int, default=0,
+                    help="one joint Gauss-Newton step after every this many recorded descent steps, behind the reweighting, the coefficient solve "
+                         "and the sweeps of the gap; with another --*_every flag both must be equal; default 0: never")
+    sp.add_argument("--gauss_newton_cg_iters", type=int, default=20, help="conjugate-gradient iterations of a Gauss-Newton step; default 20")
+    sp.add_argument("--gauss_newton_lambda", type=float, default=1e-3,
+                    help="initial Levenberg damping of a Gauss-Newton step (a tenth after an accepted step, ten times after a rejected one); default 1e-3")
+    sp.add_argument("--gauss_newton_cg_tol", type=float, default=1e-3,
+                    help="relative preconditioned residual at which the conjugate gradients of a step stop early; default 1e-3")
     return ap
 
 

@@ -32,6 +32,7 @@
 #include "fit_error_kernels.hpp"
 #include "gain_basis_solve_kernels.hpp"
 #include "gain_time_solve_kernels.hpp"
+#include "gauss_newton_kernels.hpp"
 #include "problem_plan.hpp"
 #include <cstdlib>
 #include <dlfcn.h>
@@ -168,6 +169,9 @@ struct cal_solver {
   virtual int fit_errors(double ridge, double* coeff_var, double* model_var, double* leverage_bl, double* nsamp_bl, double* gain_var,
                          cal_fit_errors_counts* counts) = 0;
   virtual int solve_gain_coeffs(const cal_gain_coeff_solve_desc* d, cal_gain_coeff_solve_result* res) = 0;
+  virtual int normal_product(const void* p_g_r, const void* p_g_i, const void* p_c_r, const void* p_c_i, void* out_g_r, void* out_g_i, void* out_c_r,
+                             void* out_c_i) = 0;
+  virtual int gauss_newton_step(const cal_gauss_newton_desc* d, cal_gauss_newton_result* res) = 0;
   virtual int solve_gain_time_coeffs(const cal_gain_time_solve_desc* d, cal_gain_time_solve_result* res) = 0;
   virtual int get_gain_coeff_moments(void* ym_r, void* ym_i, void* yv_r, void* yv_i, void* cm_r, void* cm_i, void* cv_r, void* cv_i, int64_t* t) = 0;
   virtual int init_coeffs(const void* sr, const void* si) = 0;
@@ -241,6 +245,11 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
   DevBuf fq_out, fq_gains;                     // fit_quality: chisq_ant | wsum_ant ([nants][nfreqs] doubles each, the exchange payload) | chisq_bl | wsum_bl; gains given for one evaluation
   DevBuf rw_w0, rw_out;                        // robust_weights: w0, the weights as set_data gave them (first call after a set_data); scale_bl | ndown_bl ([nbls] doubles each)
   bool rw_w0_valid = false;
+  // normal_product / gauss_newton_step (gauss_newton_kernels.hpp), vectors over the flat parameter space (gn_np() elements): the direction s, the
+  // gradient of G m and the saved parameters in T; the solution x, the residual, N s and D in double.  gn_m: m = A c, gn_sd: the data planes while
+  // they are substituted ([2][nbls][fpad] T each); gn_rows: the rows' sums (3 nbls doubles); the dot products' partials, the slices' scalars and
+  // damping, the groups as gn_precond_coeff_kernel sees them, the first baseline row of every slice ([nslices + 1] ints)
+  DevBuf gn_s, gn_g0, gn_save, gn_x, gn_res, gn_ns, gn_D, gn_m, gn_sd, gn_rows, gn_part, gn_scal, gn_lam, gn_grp, gn_rowptr;
   DevBuf members, heads;                       // baselines that share tiles (bl_alias): member lists of the head items, head item indices
   bool heads_one_pass = false;                 // the regularised step of the heads in ONE pass (all of them on fused_multi_mfma_kernel<.., REG = 2>)
   bool reg_prepass = false;                    // the regularised gradient pass is preceded by a loss pass and the slices' alpha (enqueue_pass);
@@ -595,7 +604,8 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     CAL_TRY(upload(ant_ptr, p.ant_ptr));
     CAL_TRY(upload(ant_ent, p.ant_ent));
 
-    for (DevBuf* b : {&gains_snap, &gains_alt, &coef_snap, &q1, &gcp1, &gc1, &model_buf, &scratch, &fq_out, &fq_gains, &gs_out, &gs_ptr, &gs_ent, &gs_mask, &cs_rhs, &rw_w0, &rw_out})
+    for (DevBuf* b : {&gains_snap, &gains_alt, &coef_snap, &q1, &gcp1, &gc1, &model_buf, &scratch, &fq_out, &fq_gains, &gs_out, &gs_ptr, &gs_ent, &gs_mask, &cs_rhs, &rw_w0, &rw_out,
+                       &gn_s, &gn_g0, &gn_save, &gn_x, &gn_res, &gn_ns, &gn_D, &gn_m, &gn_sd, &gn_rows, &gn_part, &gn_scal, &gn_lam, &gn_grp, &gn_rowptr})
       b->release();
     // ---- state arrays
     const size_t rowbytes = (size_t)(nbls + 1) * fpad * sizeof(T);  // + one all-zero spare row (padding slots of the dense path)
@@ -1987,6 +1997,309 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     return CAL_OK;
   }
 
+  // ---- cal_solver_normal_product / cal_solver_gauss_newton_step (gauss_newton_kernels.hpp) -----------------------
+  // N p = J^H W J p through the solver's own passes: the model pass on substituted coefficients gives A dc, the gradient pass on substituted
+  // data planes gives J^H W y.  Both are substituted by copying in place and back (the idiom of robust_weights), so every kernel family
+  // reads the substituted operands through the pointers it always reads and no recorded step graph goes stale.
+  size_t gn_go() const { return 2 * (size_t)nants * fpad; }
+  size_t gn_np() const { return gn_go() + 2 * (size_t)ncoef; }
+  GnSpace gn_space() const {
+    GnSpace S{};
+    S.coff = slice_coff.as<int>();
+    S.na_slice = na_slice;
+    S.nfreqs = nfreqs;
+    S.fpad = fpad;
+    S.ncoef = ncoef;
+    S.go = (long long)gn_go();
+    return S;
+  }
+  int gn_check(const char* who) {
+    CAL_TRY(require_set(who, true));
+    if (yb_on())
+      return fail(CAL_ERR_UNSUPPORTED, "%s: a gain basis is set (cal_solver_set_gain_basis, cal_solver_set_gain_time_basis): the optimizer's gain variables are "
+                  "then the basis coefficients y, and the Gauss-Newton matrix projected on them is not implemented; detach the basis (nvec = 0) first", who);
+    if (comm_on())
+      return fail(CAL_ERR_UNSUPPORTED, "%s: a communicator or exchange hook is set: the per-slice scalars of the product and of conjugate gradients would "
+                  "need an exchange over the ranks, which is not implemented", who);
+    return CAL_OK;
+  }
+  int gn_alloc(bool cg) {
+    const size_t np = gn_np(), plane = (size_t)nbls * fpad;
+    auto need = [](DevBuf& b, size_t bytes) { return b.bytes >= bytes && b.p ? (int)CAL_OK : b.alloc(bytes); };
+    CAL_TRY(need(gn_s, np * sizeof(T)));
+    CAL_TRY(need(gn_g0, np * sizeof(T)));
+    CAL_TRY(need(gn_save, np * sizeof(T)));
+    CAL_TRY(need(gn_ns, np * sizeof(double)));
+    CAL_TRY(need(gn_m, 2 * plane * sizeof(T)));
+    CAL_TRY(need(gn_sd, 2 * plane * sizeof(T)));
+    CAL_TRY(need(gn_rows, 3 * (size_t)nbls * sizeof(double)));
+    CAL_TRY(need(gn_part, (size_t)nslices * kGnBlocks * sizeof(double)));
+    CAL_TRY(need(gn_scal, (size_t)nslices * sizeof(GnScal)));
+    if (!gn_rowptr.p) {
+      // the groups are listed slice by slice and a group's rows are contiguous: so are a slice's rows
+      std::vector<int> ptr(nslices + 1, nbls);
+      for (int k = ngrps - 1; k >= 0; --k) ptr[h_cs_grp[k].slice] = std::min(ptr[h_cs_grp[k].slice], h_cs_grp[k].b0);
+      for (int t = nslices - 1; t >= 0; --t) ptr[t] = std::min(ptr[t], ptr[t + 1]);
+      CAL_TRY(gn_rowptr.alloc(ptr.size() * sizeof(int), false));
+      HIP_TRY(copy_sync(gn_rowptr.p, ptr.data(), ptr.size() * sizeof(int), hipMemcpyHostToDevice));
+    }
+    if (!cg) return CAL_OK;
+    CAL_TRY(need(gn_x, np * sizeof(double)));
+    CAL_TRY(need(gn_res, np * sizeof(double)));
+    CAL_TRY(need(gn_D, np * sizeof(double)));
+    CAL_TRY(need(gn_lam, (size_t)nslices * sizeof(double)));
+    if (!gn_grp.p) {
+      std::vector<GnGroup> g(ngrps);
+      for (int k = 0; k < ngrps; ++k) g[k] = GnGroup{h_cs_grp[k].b0, h_cs_grp[k].b1, h_cs_grp[k].coff, h_cs_grp[k].nvec};
+      CAL_TRY(gn_grp.alloc((size_t)ngrps * sizeof(GnGroup), false));
+      HIP_TRY(copy_sync(gn_grp.p, g.data(), (size_t)ngrps * sizeof(GnGroup), hipMemcpyHostToDevice));
+    }
+    return CAL_OK;
+  }
+  struct GnGuard {  // what a call has substituted and must put back, and the loop state it found
+    bool data = false, coefs = false;
+    std::vector<DevState> saved;
+  };
+  int gn_begin(GnGuard& G) {
+    G.saved.assign(h_state, h_state + nslices);
+    begin_pass_state();
+    return push_state();
+  }
+  int gn_restore_data(GnGuard& G) {
+    if (!G.data) return CAL_OK;
+    const size_t plane = (size_t)nbls * fpad;
+    HIP_TRY(hipMemcpyAsync(data_r.p, gn_sd.p, plane * sizeof(T), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(data_i.p, gn_sd.as<T>() + plane, plane * sizeof(T), hipMemcpyDeviceToDevice, stream));
+    G.data = false;
+    return CAL_OK;
+  }
+  int gn_restore_coefs(GnGuard& G) {
+    if (!G.coefs) return CAL_OK;
+    HIP_TRY(hipMemcpyAsync(coef.p, gn_save.as<T>() + gn_go(), 2 * (size_t)ncoef * sizeof(T), hipMemcpyDeviceToDevice, stream));
+    G.coefs = false;
+    return CAL_OK;
+  }
+  // data, coefficients and loop state back as the call found them -- on every path out of a call, failures included
+  int gn_end(GnGuard& G, int rc) {
+    const std::string msg = g_err;
+    int rc2 = gn_restore_data(G);
+    if (rc2 == CAL_OK) rc2 = gn_restore_coefs(G);
+    std::copy(G.saved.begin(), G.saved.end(), h_state);
+    if (rc2 == CAL_OK) rc2 = push_state();
+    if (rc2 == CAL_OK && hipStreamSynchronize(stream) != hipSuccess) rc2 = fail(CAL_ERR_HIP, "hipStreamSynchronize failed after a Gauss-Newton call");
+    if (timing && rc2 == CAL_OK) rc2 = collect_timing();
+    if (rc != CAL_OK) {
+      g_err = msg;
+      return rc;
+    }
+    return rc2;
+  }
+  // the gradient pass on the data planes as they stand; dst (may be null): the flat copy of the four planes
+  int gn_grad_pass(T* dst) {
+    CAL_TRY(enqueue_pass(true, false, 0));
+    if (dst) {
+      HIP_TRY(hipMemcpyAsync(dst, comm.p, gn_go() * sizeof(T), hipMemcpyDeviceToDevice, stream));
+      HIP_TRY(hipMemcpyAsync(dst + gn_go(), grad_c0(), 2 * (size_t)ncoef * sizeof(T), hipMemcpyDeviceToDevice, stream));
+    }
+    return CAL_OK;
+  }
+  // m = A c into gn_m (with_precond: D into gn_D from the same model pass), then the data planes saved and replaced by G m and the gradient
+  // of that into gn_g0
+  int gn_linearize(GnGuard& G, bool with_precond) {
+    const size_t plane = (size_t)nbls * fpad;
+    hipError_t ce = hipSuccess;
+    if (with_precond) {
+      CAL_TRY(build_solve_lists());
+      const size_t nant_out = (size_t)nants * nfreqs;
+      if (gs_out.bytes < 3 * nant_out * sizeof(double)) CAL_TRY(gs_out.alloc(3 * nant_out * sizeof(double)));
+    }
+    T *u_r = nullptr, *u_i = nullptr, *q_rows = nullptr;
+    CAL_TRY(model_pass(with_precond ? 3 : 2, [&](T* model_r, T* model_i, T* third) {
+      ce = hipMemcpyAsync(gn_m.p, model_r, 2 * plane * sizeof(T), hipMemcpyDeviceToDevice, stream);  // (model_i = model_r + plane)
+      (void)model_i;
+      if (with_precond) {
+        u_r = model_r, u_i = model_i, q_rows = third;
+        hipLaunchKernelGGL(gain_solve_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, u_r, u_i, q_rows, data_r.as<T>(), data_i.as<T>(),
+                           wgts.as<T>(), bl_ant.as<int2>(), nbls, nfreqs, fpad);
+      }
+    }));
+    HIP_TRY(ce);
+    if (with_precond) {
+      constexpr int V = 16 / (int)sizeof(T);
+      const int cblocks = (fpad + 64 * V - 1) / (64 * V);
+      hipLaunchKernelGGL(gain_solve_ant_kernel<T>, dim3(nants * cblocks), dim3(256), 0, stream, u_r, u_i, q_rows, gains.as<T2>(), gs_ptr.as<int>(),
+                         gs_ent.as<int2>(), nants, nfreqs, fpad, gs_out.as<double>());
+      hipLaunchKernelGGL(gn_precond_gain_kernel, dim3(grid_for((long long)nants * fpad)), dim3(256), 0, stream,
+                         gs_out.as<double>() + 2 * (size_t)nants * nfreqs, gn_D.as<double>(), nants, nfreqs, fpad);
+      double* rowq = gn_rows.as<double>() + 2 * (size_t)nbls;
+      hipLaunchKernelGGL(gn_precond_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, gains.as<T2>(), wgts.as<T>(), bl_ant.as<int2>(), nbls,
+                         nfreqs, fpad, rowq);
+      hipLaunchKernelGGL(gn_precond_coeff_kernel, dim3((ngrps + 255) / 256), dim3(256), 0, stream, rowq, gn_grp.as<GnGroup>(), ngrps, ncoef,
+                         gn_D.as<double>() + gn_go());
+      HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(gn_sd.p, data_r.p, plane * sizeof(T), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(gn_sd.as<T>() + plane, data_i.p, plane * sizeof(T), hipMemcpyDeviceToDevice, stream));
+    G.data = true;
+    hipLaunchKernelGGL(gn_data_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, gn_m.as<T>(), gn_m.as<T>() + plane, (const T*)nullptr,
+                       (const T*)nullptr, gains.as<T2>(), bl_ant.as<int2>(), (const GnScal*)nullptr, na_slice, data_r.as<T>(), data_i.as<T>(), nbls, nfreqs,
+                       fpad);
+    HIP_TRY(hipGetLastError());
+    return gn_grad_pass(gn_g0.as<T>());
+  }
+  // gn_ns = N s (+ lambda D s with D) for the direction in gn_s, and the partials of s . gn_ns; the coefficients are put back before it returns,
+  // the data planes stay substituted
+  int gn_product(GnGuard& G, const double* D) {
+    const size_t plane = (size_t)nbls * fpad, cb = 2 * (size_t)ncoef * sizeof(T);
+    HIP_TRY(hipMemcpyAsync(gn_save.as<T>() + gn_go(), coef.p, cb, hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(coef.p, gn_s.as<T>() + gn_go(), cb, hipMemcpyDeviceToDevice, stream));
+    G.coefs = true;
+    CAL_TRY(model_pass(2, [&](T* model_r, T* model_i, T*) {
+      hipLaunchKernelGGL(gn_tangent_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, gn_m.as<T>(), gn_m.as<T>() + plane, model_r, model_i,
+                         gains.as<T2>(), gn_s.as<T2>(), wgts.as<T>(), bl_ant.as<int2>(), nbls, nfreqs, fpad, gn_rows.as<double>());
+    }));
+    CAL_TRY(gn_restore_coefs(G));
+    hipLaunchKernelGGL(gn_scale_kernel, dim3(nslices), dim3(256), 0, stream, gn_rows.as<double>(), gn_rowptr.as<int>(), gn_scal.as<GnScal>());
+    hipLaunchKernelGGL(gn_data_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, gn_m.as<T>(), gn_m.as<T>() + plane, model_buf.as<T>(),
+                       model_buf.as<T>() + plane, gains.as<T2>(), bl_ant.as<int2>(), gn_scal.as<GnScal>(), na_slice, data_r.as<T>(), data_i.as<T>(), nbls,
+                       nfreqs, fpad);
+    HIP_TRY(hipGetLastError());
+    CAL_TRY(gn_grad_pass(nullptr));
+    hipLaunchKernelGGL(gn_diff_kernel<T>, dim3(kGnBlocks, nslices), dim3(256), 0, stream, gn_space(), comm.as<T>(), grad_c0(), gn_g0.as<T>(), gn_s.as<T>(), D,
+                       gn_scal.as<GnScal>(), gn_ns.as<double>(), gn_part.as<double>());
+    HIP_TRY(hipGetLastError());
+    return CAL_OK;
+  }
+
+  int normal_product(const void* p_g_r, const void* p_g_i, const void* p_c_r, const void* p_c_i, void* out_g_r, void* out_g_i, void* out_c_r,
+                     void* out_c_i) override {
+    HIP_TRY(hipSetDevice(device));
+    if (!p_g_r || !p_g_i || !p_c_r || !p_c_i || !out_g_r || !out_g_i || !out_c_r || !out_c_i) return fail(CAL_ERR_INVALID, "normal_product: null pointer");
+    CAL_TRY(gn_check("normal_product"));
+    CAL_TRY(gn_alloc(false));
+    const size_t cb = (size_t)ncoef * sizeof(T);
+    CAL_TRY(upload_rows(p_g_r, gn_s.as<T>(), nants, 2, 0));
+    CAL_TRY(upload_rows(p_g_i, gn_s.as<T>(), nants, 2, 1));
+    HIP_TRY(copy_sync(gn_s.as<T>() + gn_go(), p_c_r, cb, hipMemcpyHostToDevice));
+    HIP_TRY(copy_sync(gn_s.as<T>() + gn_go() + ncoef, p_c_i, cb, hipMemcpyHostToDevice));
+    std::vector<GnScal> sc(nslices);
+    for (auto& x : sc) {
+      x = GnScal{};
+      x.scale = 1.0;
+    }
+    HIP_TRY(copy_sync(gn_scal.p, sc.data(), sc.size() * sizeof(GnScal), hipMemcpyHostToDevice));
+    GnGuard G;
+    int rc = gn_begin(G);
+    if (rc == CAL_OK) rc = gn_linearize(G, false);
+    if (rc == CAL_OK) rc = gn_product(G, nullptr);
+    if (rc == CAL_OK) {
+      T* out = gn_g0.as<T>();  // (the gradient of G m has served)
+      hipLaunchKernelGGL(gn_round_kernel<T>, dim3(grid_for((long long)gn_np())), dim3(256), 0, stream, gn_ns.as<double>(), out, (long long)gn_np());
+      if (hipGetLastError() != hipSuccess) rc = fail(CAL_ERR_HIP, "normal_product: launch failed");
+    }
+    CAL_TRY(gn_end(G, rc));
+    const T* out = gn_g0.as<T>();
+    CAL_TRY(download_rows(out_g_r, out, nants, 2, 0));
+    CAL_TRY(download_rows(out_g_i, out, nants, 2, 1));
+    HIP_TRY(copy_sync(out_c_r, out + gn_go(), cb, hipMemcpyDeviceToHost));
+    HIP_TRY(copy_sync(out_c_i, out + gn_go() + ncoef, cb, hipMemcpyDeviceToHost));
+    return CAL_OK;
+  }
+
+  int gauss_newton_step(const cal_gauss_newton_desc* d, cal_gauss_newton_result* res) override {
+    HIP_TRY(hipSetDevice(device));
+    if (!d || !res) return fail(CAL_ERR_INVALID, "gauss_newton_step: null description or results");
+    if (d->ncg < 1) return fail(CAL_ERR_INVALID, "gauss_newton_step: ncg = %d, at least one iteration", d->ncg);
+    if (!(d->cg_tol >= 0.0) || !std::isfinite(d->cg_tol)) return fail(CAL_ERR_INVALID, "gauss_newton_step: cg_tol = %g must be finite and >= 0", d->cg_tol);
+    if (!d->lambda) return fail(CAL_ERR_INVALID, "gauss_newton_step: null lambda");
+    CAL_TRY(gn_check("gauss_newton_step"));
+    for (int t = 0; t < nslices; ++t)
+      if (!(d->lambda[t] >= 0.0) || !std::isfinite(d->lambda[t]))
+        return fail(CAL_ERR_INVALID, "gauss_newton_step: lambda[%d] = %g must be finite and >= 0", t, d->lambda[t]);
+    if (d->reset_moments && !has_opt) return fail(CAL_ERR_STATE, "gauss_newton_step: reset_moments without an optimizer (cal_solver_set_optimizer)");
+    CAL_TRY(gn_alloc(true));
+    const unsigned char* mask = nullptr;
+    CAL_TRY(upload_slice_mask(d->slice_mask, &mask));
+    HIP_TRY(copy_sync(gn_lam.p, d->lambda, (size_t)nslices * sizeof(double), hipMemcpyHostToDevice));
+    std::vector<double> before(nslices), after(nslices);
+    std::vector<GnScal> sc(nslices);
+    std::vector<uint8_t> accepted(nslices, 0);
+    const GnSpace S = gn_space();
+    const dim3 vgrid(kGnBlocks, nslices), sgrid((nslices + 63) / 64);
+    GnScal* scal_d = gn_scal.as<GnScal>();
+    double *x = gn_x.as<double>(), *r = gn_res.as<double>(), *ns = gn_ns.as<double>(), *D = gn_D.as<double>(), *part = gn_part.as<double>();
+    T* s = gn_s.as<T>();
+    GnGuard G;
+    auto body = [&]() -> int {
+      // the gradient at the data (its loss is the loss before the step), the linearisation, the right-hand side
+      CAL_TRY(gn_grad_pass(s));
+      CAL_TRY(pull_state());
+      for (int t = 0; t < nslices; ++t) before[t] = h_state[t].loss;
+      CAL_TRY(gn_linearize(G, true));
+      hipLaunchKernelGGL(gn_rhs_kernel<T>, vgrid, dim3(256), 0, stream, S, s, s + gn_go(), gn_g0.as<T>(), r);
+      hipLaunchKernelGGL(gn_init_kernel<T>, vgrid, dim3(256), 0, stream, S, r, D, x, s, part);
+      hipLaunchKernelGGL(gn_scalar0_kernel, sgrid, dim3(64), 0, stream, scal_d, part, kGnBlocks, nslices, mask, gn_lam.as<double>(), d->cg_tol);
+      HIP_TRY(hipGetLastError());
+      for (int it = 0; it < d->ncg; ++it) {  // the host reads no scalar in here: a frozen slice's kernels return at once
+        CAL_TRY(gn_product(G, D));
+        hipLaunchKernelGGL(gn_scalar1_kernel, sgrid, dim3(64), 0, stream, scal_d, part, kGnBlocks, nslices);
+        hipLaunchKernelGGL(gn_update1_kernel<T>, vgrid, dim3(256), 0, stream, S, scal_d, s, ns, D, x, r, part);
+        hipLaunchKernelGGL(gn_scalar2_kernel, sgrid, dim3(64), 0, stream, scal_d, part, kGnBlocks, nslices);
+        hipLaunchKernelGGL(gn_update2_kernel<T>, vgrid, dim3(256), 0, stream, S, scal_d, r, D, s);
+        HIP_TRY(hipGetLastError());
+      }
+      CAL_TRY(gn_restore_data(G));
+      // the trial parameters of the selected slices, their loss, and the rejected slices back bit for bit
+      HIP_TRY(hipMemcpyAsync(gn_save.p, gains.p, gn_go() * sizeof(T), hipMemcpyDeviceToDevice, stream));
+      HIP_TRY(hipMemcpyAsync(gn_save.as<T>() + gn_go(), coef.p, 2 * (size_t)ncoef * sizeof(T), hipMemcpyDeviceToDevice, stream));
+      hipLaunchKernelGGL(gn_apply_kernel<T>, vgrid, dim3(256), 0, stream, S, mask, x, gains.as<T>(), coef.as<T>());
+      HIP_TRY(hipGetLastError());
+      CAL_TRY(enqueue_pass(false, false, 0));
+      HIP_TRY(hipMemcpyAsync(sc.data(), scal_d, sc.size() * sizeof(GnScal), hipMemcpyDeviceToHost, stream));
+      CAL_TRY(pull_state());
+      std::vector<uint8_t> rejected(nslices, 0);
+      for (int t = 0; t < nslices; ++t) {
+        after[t] = h_state[t].loss;
+        const bool sel = !d->slice_mask || d->slice_mask[t];
+        accepted[t] = sel && std::isfinite(after[t]) && after[t] < before[t] ? 1 : 0;
+        rejected[t] = sel && !accepted[t] ? 1 : 0;
+      }
+      const size_t ng = 2 * (size_t)na_slice * fpad;  // gain reals per slice
+      CAL_TRY(for_selected_slice_runs(rejected.data(), [&](int t, int t1) {
+        HIP_TRY(hipMemcpyAsync(gains.as<T>() + (size_t)t * ng, gn_save.as<T>() + (size_t)t * ng, (size_t)(t1 - t) * ng * sizeof(T), hipMemcpyDeviceToDevice, stream));
+        const size_t n = (size_t)(h_slice_coff[t1] - h_slice_coff[t]);
+        for (int plane = 0; plane < 2 && n > 0; ++plane) {
+          const size_t off = (size_t)plane * ncoef + h_slice_coff[t];
+          HIP_TRY(hipMemcpyAsync(coef.as<T>() + off, gn_save.as<T>() + gn_go() + off, n * sizeof(T), hipMemcpyDeviceToDevice, stream));
+        }
+        return (int)CAL_OK;
+      }));
+      if (d->reset_moments) {
+        // what set_optimizer leaves in the gain and coefficient slots, for the accepted slices
+        CAL_TRY(for_selected_slice_runs(accepted.data(), [&](int t, int t1) {
+          CAL_TRY(reset_moment_slots(gains_m, gains_v, (size_t)t * ng, (size_t)(t1 - t) * ng));
+          const size_t n = (size_t)(h_slice_coff[t1] - h_slice_coff[t]);
+          for (int plane = 0; plane < 2 && n > 0; ++plane) CAL_TRY(reset_moment_slots(coef_m, coef_v, (size_t)plane * ncoef + h_slice_coff[t], n));
+          return (int)CAL_OK;
+        }));
+        HIP_TRY(hipGetLastError());
+      }
+      return CAL_OK;
+    };
+    int rc = gn_begin(G);
+    if (rc == CAL_OK) rc = body();
+    CAL_TRY(gn_end(G, rc));
+    for (int t = 0; t < nslices; ++t) {
+      const bool sel = !d->slice_mask || d->slice_mask[t];
+      res[t].loss_before = before[t];
+      res[t].loss_after = sel ? after[t] : before[t];
+      res[t].cg_residual = sc[t].resid;
+      res[t].cg_iters = sc[t].iters;
+      res[t].accepted = accepted[t];
+    }
+    return CAL_OK;
+  }
+
   // ---- cal_solver_solve_coeffs ----------------------------------------------------------------------------------
   void release_coeff_solve() {  // the plan of a problem / a scratch bound: rebuilt by the next call
     cs_grp.release();
@@ -2528,7 +2841,8 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
                            &data_r, &data_i, &wgts, &gains, &gains_alt, &gains_m, &gains_v, &gains_snap, &coef, &coef_m, &coef_v, &coef_snap,
                            &q0, &q1, &comm, &scal, &gcp0, &gcp1, &gc0, &gc1, &part, &state, &losses, &scratch, &model_buf, &fq_out, &fq_gains, &rw_w0, &rw_out, &gs_out, &gs_ptr, &gs_ent, &gs_mask, &cs_grp, &cs_order, &cs_work, &cs_n, &cs_d, &cs_rhs, &cs_cnt, &fe_grp, &fe_order, &fe_work, &fe_woff, &fe_lwork, &fe_n, &fe_d, &fe_w, &fe_rhs, &fe_ok, &fe_part, &fe_out, &fe_mv, &gbs_n, &gbs_d, &gbs_rhs, &gbs_cnt, &gts_m, &gts_n, &gts_rhsa, &gts_d, &gts_rhs, &gts_cnt,
                            &mf_ops, &mf_panels, &mf_map, &members, &heads, &lamb_vars, &lamb_cvar_ptr, &lamb_partial, &lamb_ratio, &lamb_glob, &lamb_slot, &slice_coff, &slice_ipart_ptr, &slice_ipart_idx,
-                           &slice_ppart_ptr, &slice_ppart_idx, &slice_cblk, &gb_B, &gb_Bt, &gb_g0, &gb_y, &gb_ym, &gb_yv, &gb_ysnap, &gb_proj, &tb_B, &tb_Bt, &tb_z, &tb_pf};
+                           &slice_ppart_ptr, &slice_ppart_idx, &slice_cblk, &gb_B, &gb_Bt, &gb_g0, &gb_y, &gb_ym, &gb_yv, &gb_ysnap, &gb_proj, &tb_B, &tb_Bt, &tb_z, &tb_pf,
+                           &gn_s, &gn_g0, &gn_save, &gn_x, &gn_res, &gn_ns, &gn_D, &gn_m, &gn_sd, &gn_rows, &gn_part, &gn_scal, &gn_lam, &gn_grp, &gn_rowptr};
     int64_t n = 0;
     for (auto* d : all) n += (int64_t)d->bytes;
     *b = n;
@@ -2878,6 +3192,12 @@ int cal_solver_model(cal_solver* s, void* mr, void* mi) { NEED(s); return s->mod
 int cal_solver_data_model(cal_solver* s, void* mr, void* mi) { NEED(s); return s->model(mr, mi, true); }
 int cal_solver_solve_gains(cal_solver* s, const cal_gain_solve_desc* desc) { NEED(s); return s->solve_gains(desc); }
 int cal_solver_hold_slices(cal_solver* s, const uint8_t* mask) { NEED(s); return s->hold_slices(mask); }
+int cal_solver_normal_product(cal_solver* s, const void* p_g_r, const void* p_g_i, const void* p_c_r, const void* p_c_i, void* out_g_r, void* out_g_i,
+                              void* out_c_r, void* out_c_i) {
+  NEED(s);
+  return s->normal_product(p_g_r, p_g_i, p_c_r, p_c_i, out_g_r, out_g_i, out_c_r, out_c_i);
+}
+int cal_solver_gauss_newton_step(cal_solver* s, const cal_gauss_newton_desc* desc, cal_gauss_newton_result* results) { NEED(s); return s->gauss_newton_step(desc, results); }
 int cal_solver_solve_coeffs(cal_solver* s, const cal_coeff_solve_desc* desc, cal_coeff_solve_result* result) { NEED(s); return s->solve_coeffs(desc, result); }
 int cal_solver_set_coeff_solve_scratch(cal_solver* s, int64_t bytes) { NEED(s); return s->set_coeff_solve_scratch(bytes); }
 int cal_solver_fit_errors(cal_solver* s, double ridge, double* coeff_var, double* model_var, double* leverage_bl, double* nsamp_bl, double* gain_var,

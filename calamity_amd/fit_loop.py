@@ -1,5 +1,5 @@
 """The host loop of a fit, stated once: ``FitOptions`` holds the keywords of the closed-form solves and of the robust reweighting,
-``drive`` issues everything between ``set_optimizer`` and reading the parameters back, ``history_entry`` files what it returns.
+``GaussNewtonOptions`` those of the joint Gauss-Newton steps, ``drive`` issues everything between ``set_optimizer`` and reading the parameters back, ``history_entry`` files what it returns.
 Host only: NumPy, never the library ("The host loop")."""
 import dataclasses
 import datetime
@@ -144,15 +144,78 @@ class FitOptions:
             self._check_robust(use_min)
 
 
+@dataclasses.dataclass(frozen=True)
+class GaussNewtonOptions:
+    """The keywords of the joint Gauss-Newton steps of ``calibrate_and_model_tensor`` / ``fit_gains_and_foregrounds`` (documented
+    there), under their public names and defaults."""
+    gauss_newton_rounds: int = 0
+    gauss_newton_every: int = 0
+    gauss_newton_cg_iters: int = 20
+    gauss_newton_lambda: float = 1e-3
+    gauss_newton_cg_tol: float = 1e-3
+
+    @classmethod
+    def pick(cls, keywords):
+        """The options out of a mapping that holds them among others (a public function's ``locals()``)."""
+        return cls(**{f.name: keywords[f.name] for f in dataclasses.fields(cls)})
+
+    @property
+    def on(self):
+        return bool(self.gauss_newton_rounds or self.gauss_newton_every)
+
+    def check(self, opts, freq_basis_given, time_basis_given, freeze_model, groups_split=False):
+        """``ValueError`` before any device work.  ``opts``: the call's ``FitOptions`` (one chunk length for every ``*_every``);
+        ``groups_split``: several devices share out the fitting groups of a slice."""
+        rounds, every, iters = self.gauss_newton_rounds, self.gauss_newton_every, self.gauss_newton_cg_iters
+        if not (_count(rounds) and _count(every)):
+            raise ValueError(f"gauss_newton_rounds and gauss_newton_every must be non-negative integers, got {rounds!r} and {every!r}")
+        if not (_count(iters) and iters >= 1):
+            raise ValueError(f"gauss_newton_cg_iters must be a positive integer, got {iters!r}")
+        if not _finite_nonneg(self.gauss_newton_lambda):
+            raise ValueError(f"gauss_newton_lambda must be finite and >= 0, got {self.gauss_newton_lambda!r}")
+        if not _finite_nonneg(self.gauss_newton_cg_tol):
+            raise ValueError(f"gauss_newton_cg_tol must be finite and >= 0, got {self.gauss_newton_cg_tol!r}")
+        if not self.on:
+            return
+        if freq_basis_given:
+            raise ValueError("gauss_newton_rounds / gauss_newton_every step the free per-channel gains and the coefficients together: they cannot be "
+                             "combined with gain_basis / gain_max_dly (the step projected on the basis coefficients is not implemented)")
+        if time_basis_given:
+            raise ValueError("gauss_newton_rounds / gauss_newton_every step the free per-channel gains and the coefficients together: they cannot be "
+                             "combined with gain_time_basis / gain_time_scale (the step projected on the basis coefficients is not implemented)")
+        if freeze_model:
+            raise ValueError("gauss_newton_rounds / gauss_newton_every move the foreground coefficients: they cannot be combined with freeze_model, "
+                             "which keeps them as given (gain_solve_sweeps is the exact answer for the gains alone)")
+        if groups_split:
+            raise ValueError("gauss_newton_rounds / gauss_newton_every need every slice whole on one device: several devices that share out the "
+                             "fitting groups (device_split='groups', or too few batches for the devices) would have to exchange the per-slice scalars of "
+                             "conjugate gradients, which is not implemented; device_split='slices' works")
+        if every and opts.chunk and opts.chunk != every:
+            raise ValueError(f"gauss_newton_every={every} and the chunk length {opts.chunk} of gain_solve_every / gain_basis_solve_every / "
+                             "gain_time_solve_every / robust_every share the gaps of one chunked loop: give them the same value")
+
+
+def next_lambda(lam, accepted):
+    """The damping after a step: a tenth where the step was accepted, ten times ``max(lambda, 1e-6)`` where it was rejected."""
+    lam = np.asarray(lam, dtype=np.float64)
+    return np.where(np.asarray(accepted, dtype=bool), lam / 10.0, 10.0 * np.maximum(lam, 1e-6))
+
+
 def drive(fitter, opts, nl, rows_per_loop, maxsteps, tol, use_min, freeze_model, n_profile_steps=0, profile_log_dir="./logdir",
-          profile_extra=None):
+          profile_extra=None, newton=None):
     """Everything between ``set_optimizer`` and reading the parameters back, on a ``SliceBatchFitter`` or a one-slice
     ``HipFitSolver``: the start-up rounds of closed-form solves, ``n_profile_steps`` profiled steps (their timings, with the keys of
     ``profile_extra``, as JSON into ``profile_log_dir``), the unrecorded step, the recorded loop.  ``nl``: the loops of the fitter (1 for
     a single solver and for a joint fit, else the slices of the batch), ``rows_per_loop``: the baseline rows of each.  Returns
     ``(results, nsingular, sweep_singular, robust)``: per loop ``(losses, stopped, nupdates)``; the singular count of the last
     coefficient solve and of the last sweep of a basis or time family (``None`` where there is none); with ``robust_every`` what the
-    last reweight of every loop reported, ``{"rounds": [nl], "ndown_bl", "scale_bl": [nl * rows_per_loop]}``, else ``None``."""
+    last reweight of every loop reported, ``{"rounds": [nl], "ndown_bl", "scale_bl": [nl * rows_per_loop]}``, else ``None``.
+    ``newton`` (``GaussNewtonOptions``): ``gauss_newton_rounds`` joint steps after the start-up rounds and sweeps, and with
+    ``gauss_newton_every`` one step in every gap of the chunked loop behind the reweighting, the coefficient solve and the sweeps, on the
+    loops not yet over and with the optimizer's slots of the accepted ones started over.  The damping is kept per loop (``next_lambda``);
+    a rejected step is simply followed by the next one.  With ``newton`` given a fifth value is returned: ``None`` while it is off,
+    else ``{"steps", "accepted": [nl], "lambda": [nl] (the damping a next step would use), "loss", "cg_iters": per loop the loss after and the
+    iterations of every step it took part in}``."""
     family = opts.family
     sweeps, every, damping, ridge = opts.sweep
 
@@ -172,6 +235,25 @@ def drive(fitter, opts, nl, rows_per_loop, maxsteps, tol, use_min, freeze_model,
                 last = sweep(sweeps)
     elif sweeps > 0:  # the coefficients are initialised: the gains in closed form before any descent step
         last = sweep(sweeps)
+    gn = None
+    if newton is not None and newton.on:
+        gn = dict(steps=np.zeros(nl, dtype=np.int64), accepted=np.zeros(nl, dtype=np.int64), loss=[[] for _ in range(nl)],
+                  cg_iters=[[] for _ in range(nl)])
+        gn["lambda"] = np.full(nl, float(newton.gauss_newton_lambda))
+
+    def newton_step(todo, **kw):
+        out = fitter.gauss_newton_step(ncg=newton.gauss_newton_cg_iters, lam=gn["lambda"], cg_tol=newton.gauss_newton_cg_tol, **kw)
+        ok = np.asarray(out["accepted"], dtype=bool)
+        gn["lambda"] = np.where(todo, next_lambda(gn["lambda"], ok), gn["lambda"])
+        gn["steps"] += todo
+        gn["accepted"] += ok & todo
+        for t in np.where(todo)[0]:
+            gn["loss"][t].append(float(out["loss_after"][t] if ok[t] else out["loss_before"][t]))
+            gn["cg_iters"][t].append(int(out["cg_iters"][t]))
+
+    if gn is not None:
+        for _ in range(newton.gauss_newton_rounds):
+            newton_step(np.ones(nl, dtype=bool))
     if n_profile_steps > 0:
         fitter.timing_enable(True)
         fitter.run_slices(n_profile_steps, record=False, freeze_model=freeze_model)
@@ -184,12 +266,13 @@ def drive(fitter, opts, nl, rows_per_loop, maxsteps, tol, use_min, freeze_model,
     robust = None
     if opts.robust_every > 0:  # per loop the reweights it took part in; per baseline row what its last one reported
         robust = dict(rounds=np.zeros(nl, dtype=np.int64), ndown_bl=np.zeros(nl * rows_per_loop), scale_bl=np.zeros(nl * rows_per_loop))
-    if opts.chunked:
+    chunk = opts.chunk or (newton.gauss_newton_every if gn is not None else 0)
+    if chunk > 0:
         # the recorded loop in chunks (every loop's state -- step count, previous and lowest loss -- persists from run to run); a loop
         # that has ended is held in the chunks that follow, as one call would leave it, and takes no part in the gaps between them
         parts, over, nupd, issued = [[] for _ in range(nl)], np.zeros(nl, dtype=bool), np.zeros(nl, dtype=np.int64), 0
         while issued < maxsteps and not np.all(over):
-            n = min(opts.chunk, maxsteps - issued)
+            n = min(chunk, maxsteps - issued)
             for t, (part, stopped, nu) in enumerate(fitter.run_slices(n, **run)):
                 if not over[t]:
                     parts[t].append(part)
@@ -210,15 +293,27 @@ def drive(fitter, opts, nl, rows_per_loop, maxsteps, tol, use_min, freeze_model,
                     if opts.coeff_solve_rounds > 0:
                         nsingular = fitter.solve_coeffs(ridge=opts.coeff_solve_ridge, slice_mask=~over, reset_coeff_moments=True)["nsingular"]
                     last = sweep(max(1, sweeps), slice_mask=~over, reset_gain_moments=True)
+                if gn is not None and newton.gauss_newton_every > 0:
+                    newton_step(~over, slice_mask=~over, reset_moments=True)
         fitter.hold_slices(None)
         results = [(np.concatenate([np.zeros(0)] + parts[t]), bool(over[t]), int(nupd[t])) for t in range(nl)]
     else:
         results = fitter.run_slices(maxsteps, **run)
-    return results, nsingular, (int(last or 0) if family in ("basis", "time") else None), robust
+    out = (results, nsingular, (int(last or 0) if family in ("basis", "time") else None), robust)
+    return out if newton is None else out + (gn,)
 
 
-def history_entry(opts, losses, dtype, nsingular, sweep_singular, robust):
-    """One slice's ``fit_history`` entry from what ``drive`` returned for it (``robust``: the entry as the caller reports it)."""
+def newton_history(gn, t):
+    """Loop ``t``'s ``fit_history[...]["gauss_newton"]`` from the fifth value of ``drive`` (``None`` while the steps are off)."""
+    if gn is None:
+        return None
+    return {"steps": int(gn["steps"][t]), "accepted": int(gn["accepted"][t]), "lambda": float(gn["lambda"][t]), "loss": list(gn["loss"][t]),
+            "cg_iters": list(gn["cg_iters"][t])}
+
+
+def history_entry(opts, losses, dtype, nsingular, sweep_singular, robust, newton=None):
+    """One slice's ``fit_history`` entry from what ``drive`` returned for it (``robust``, ``newton``: the entries as the caller reports
+    them, ``newton_history`` for the latter)."""
     hist = {"loss": [dtype.type(l) for l in losses]}
     if nsingular is not None:
         hist["coeff_solve_singular"] = int(nsingular)
@@ -226,4 +321,6 @@ def history_entry(opts, losses, dtype, nsingular, sweep_singular, robust):
         hist[_FAMILIES[opts.family][0] + "_singular"] = int(sweep_singular)
     if robust is not None:
         hist["robust"] = robust
+    if newton is not None:
+        hist["gauss_newton"] = newton
     return hist

@@ -431,6 +431,44 @@ class HipFitSolver:
         _lib.check(self._lib.cal_solver_solve_coeffs(self._h, C.byref(d), C.byref(r)))
         return {"nsolved": int(r.nsolved), "nsingular": int(r.nsingular)}
 
+    def normal_product(self, p_g_r, p_g_i, p_c_r, p_c_i):
+        """``N p`` for the joint Gauss-Newton matrix ``N = J^H W J`` over gains and coefficients at the solver's current parameters
+        (cal_solver_normal_product).  With ``m = A c``, ``G = g_i conj(g_j)`` and the direction ``p = (dg [nants, nfreqs], dc [ncoeffs])``
+        complex, held as (re, im) like the parameters::
+
+            (J p)[b][f] = (dg_i conj(g_j) + g_i conj(dg_j)) m + G (A dc)
+            N p = -1/2 (grad(G m + J p) - grad(G m))
+
+        where ``grad(d')`` is what ``eval_grads`` returns when the data are ``d'``: the product runs the solver's own model and gradient
+        passes on substituted operands and puts everything back (data, weights, loss and loop state keep their bits).  ``N`` is that of
+        the chi-square term alone, regulariser on or off.  Returns ``(out_g_r, out_g_i, out_c_r, out_c_i)``, laid out like the gradient.
+        Not available with a gain basis or under an exchange."""
+        gs, cs = (self.nants, self.nfreqs), (self.ncoeffs,)
+        arrs = [self._real(a, shp) for a, shp in ((p_g_r, gs), (p_g_i, gs), (p_c_r, cs), (p_c_i, cs))]
+        out = [np.empty(gs, dtype=self.dtype), np.empty(gs, dtype=self.dtype), np.empty(cs, dtype=self.dtype), np.empty(cs, dtype=self.dtype)]
+        _lib.check(self._lib.cal_solver_normal_product(self._h, *[_ptr(a) for a in arrs + out]))
+        return tuple(out)
+
+    def gauss_newton_step(self, ncg=20, lam=1e-3, cg_tol=1e-3, slice_mask=None, reset_moments=False):
+        """One Levenberg-damped Gauss-Newton step over gains and coefficients together (cal_solver_gauss_newton_step): per slice
+        ``(N + lam D) p = rhs`` with ``N = J^H W J`` (``normal_product``), ``rhs = J^H W (d - G m)`` (minus half the chi-square gradient)
+        and the diagonal ``D`` (for a gain ``den`` of ``solve_gains``, for a coefficient of group ``gamma`` ``sum_b mean_f w |G|^2``), solved
+        by at most ``ncg`` iterations of conjugate gradients preconditioned with ``D`` from ``p = 0``; a slice stops once
+        ``sqrt(rz / rz0) <= cg_tol``.  The trial parameters ``g + dg``, ``c + dc`` are kept iff their loss (as ``eval_loss``, regulariser
+        included) is finite and strictly below the loss before; a rejected slice and a slice whose ``slice_mask`` entry is 0 keep the
+        bits of their parameters.  ``lam``: one number or one per slice.  ``reset_moments``: the optimizer's gain and coefficient slots
+        of the accepted slices start over as after ``set_optimizer`` (iteration counts stay).  Nothing else the fit reads changes.
+        Not available with a gain basis or under an exchange.  Returns a dict of per-slice arrays: ``loss_before``, ``loss_after``,
+        ``cg_residual`` (float64), ``cg_iters`` (int) and ``accepted`` (bool)."""
+        m = self._slice_mask(slice_mask)
+        lam = np.ascontiguousarray(np.broadcast_to(np.asarray(lam, dtype=np.float64), (self.nslices,)))
+        d = _lib.GaussNewtonDesc(int(ncg), int(bool(reset_moments)), float(cg_tol), lam.ctypes.data, None if m is None else m.ctypes.data)
+        res = (_lib.GaussNewtonResult * self.nslices)()
+        _lib.check(self._lib.cal_solver_gauss_newton_step(self._h, C.byref(d), res))
+        return dict(loss_before=np.asarray([r.loss_before for r in res]), loss_after=np.asarray([r.loss_after for r in res]),
+                    cg_residual=np.asarray([r.cg_residual for r in res]), cg_iters=np.asarray([r.cg_iters for r in res], dtype=np.int64),
+                    accepted=np.asarray([bool(r.accepted) for r in res]))
+
     def _set_coeff_solve_scratch(self, nbytes):
         """Scratch bound of ``solve_coeffs`` in bytes (0: the default); the results do not depend on it (tests)."""
         _lib.check(self._lib.cal_solver_set_coeff_solve_scratch(self._h, int(nbytes)))

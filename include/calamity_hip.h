@@ -371,6 +371,50 @@ int cal_solver_solve_gains(cal_solver* s, const cal_gain_solve_desc* desc);
  * all zeros: none): a loop issued in several calls keeps a slice that met the tolerance in an earlier call as it is, as one call
  * would.  A held slice reports stopped = 1 and records nothing.  cal_solver_set_optimizer and cal_solver_set_problem clear it. */
 int cal_solver_hold_slices(cal_solver* s, const uint8_t* mask);
+/* Joint Gauss-Newton steps over gains and coefficients together (no counterpart in the reference): the descent loop is first-order and the
+ * closed forms above are block-wise, so alternated they stall in the valley where gains and foregrounds trade against each other.  The joint
+ * matrix N = J^H W J is far too large to form and cheap to apply.  Baseline row b has antennas (i, j); d, w are the solver's data and current
+ * weights, g its gains, c its coefficients, m = A c what cal_solver_model returns, G = g_i conj(g_j).  grad(d') means the four planes
+ * cal_solver_eval_grads returns at the solver's current parameters when the data are d'.  A direction p = (dg [nants][nfreqs], dc [ncoef]) is
+ * complex, held as (re, im) planes like the parameters:
+ *   (J p)[b][f] = (dg_i conj(g_j) + g_i conj(dg_j)) m + G (A dc)        autocorrelation rows included, by the same formula
+ *   N p  = J^H W J p := -1/2 ( grad(G m + J p) - grad(G m) )            four planes, laid out like the gradient
+ *   rhs  = J^H W r   := -1/2 ( grad(d)         - grad(G m) )            r = d - G m
+ * grad(G m) is zero without the regulariser and the regulariser's own gradient with "sum" (it does not depend on the data): N and rhs are
+ * those of the chi-square term alone in both modes, as in every closed form above.  On the device it also cancels the rounding difference
+ * between the model pass and the fused pass; it is computed once per call.  In fp32 those two passes round m differently by about 1e-7 |m| and
+ * a direction of conjugate gradients near convergence makes J p smaller than that, so the pass evaluates grad(G m + s_t J p) and divides by
+ * s_t, one scale per slice: s_t = sqrt(sum w |G m|^2 / sum w |J p|^2) over the slice's rows (sums in double, fixed order; 1 where either is 0).
+ * cal_solver_normal_product returns N p in the solver's dtype: p_* and out_* are [nants][nfreqs] and [ncoef] like cal_solver_set_params.
+ * cal_solver_gauss_newton_step solves (N + lambda_t D) p = rhs per slice (N is block-diagonal over the slices) by at most ncg iterations of
+ * conjugate gradients preconditioned with the diagonal D, from p = 0 (which never moves along a null direction of N: the flux-scale degeneracy
+ * stays out of the step):
+ *   D_g[a][f] = den_a[f] of cal_solver_solve_gains at the current parameters (autocorrelations left out)
+ *   D_c[k]    = sum_{b in gamma} (1 / nfreqs) sum_f w |G|^2 for every coefficient k of group gamma
+ *   entries <= 0 or non-finite become 1
+ * Each slice has its own alpha_t, beta_t on the device; it freezes once sqrt(rz_t / rz0_t) <= cg_tol, or once s . N s <= 0 or a non-finite
+ * scalar appears.  The trial parameters are g + dg, c + dc; the slice's loss there is evaluated as cal_solver_eval_loss does (regulariser
+ * included when set) and the slice is accepted iff that loss is finite and strictly below its loss before the step.  A rejected slice, and a
+ * slice whose mask byte is 0, keeps the bits of its gains and coefficients.  Nothing else the fit reads differs after the call (data, weights,
+ * w0, regulariser, loop state, t, any recorded step graph; the moments unless reset_moments): a run continued after a call with an all-zero
+ * mask is bit-identical to one without it.  Dot products run in double in a fixed order: two calls give the same bits.
+ * Passes per step: 1 model pass of c, ncg model passes of directions, ncg + 2 gradient passes, 1 loss pass.  The substituted operands are
+ * copied into the solver's own data and coefficient planes and back, so every layout and kernel path, folded tiles, groups of several
+ * baselines, bl_alias and nslices > 1 work, regulariser on or off.
+ *   CAL_ERR_INVALID: null pointers, ncg < 1, cg_tol or a lambda negative or not finite.  CAL_ERR_STATE: problem, data, coefficients or gains
+ *   not set; reset_moments without an optimizer.  CAL_ERR_UNSUPPORTED: a frequency or time gain basis is attached (the variables there are y;
+ *   the projected step is not implemented), or a communicator or exchange hook is set (the per-slice scalars would need an exchange). */
+int cal_solver_normal_product(cal_solver* s, const void* p_g_r, const void* p_g_i, const void* p_c_r, const void* p_c_i,
+                              void* out_g_r, void* out_g_i, void* out_c_r, void* out_c_i);      /* N p, solver dtype */
+typedef struct cal_gauss_newton_desc {
+  int32_t ncg;               /* >= 1 */
+  int32_t reset_moments;     /* accepted slices: gain and coefficient slots back to what cal_solver_set_optimizer leaves */
+  double cg_tol;             /* >= 0, finite */
+  const double* lambda;      /* [nslices], each finite and >= 0 */
+  const uint8_t* slice_mask; /* [nslices] or NULL */
+} cal_gauss_newton_desc;
+typedef struct cal_gauss_newton_result { double loss_before, loss_after, cg_residual; int32_t cg_iters, accepted; } cal_gauss_newton_result;
+int cal_solver_gauss_newton_step(cal_solver* s, const cal_gauss_newton_desc* desc, cal_gauss_newton_result* results /* [nslices] */);
 /* The foreground coefficients in closed form (no counterpart in the reference): the other half of alternating least squares next to
  * cal_solver_solve_gains.  With the gains held fixed the chi-square sum w |d - g_i conj(g_j) (A c)|^2 is linear least squares in the
  * coefficients and separates by fitting group.  Group gamma has nvec complex coefficients c; its baselines b have antennas (i, j) and
