@@ -33,7 +33,7 @@
 #include "gain_basis_solve_kernels.hpp"
 #include "gain_time_solve_kernels.hpp"
 #include "gauss_newton_kernels.hpp"
-#include "problem_plan.hpp"
+#include "solve_plan.hpp"  // (and problem_plan.hpp)
 #include <cstdlib>
 #include <dlfcn.h>
 #include <type_traits>
@@ -79,9 +79,25 @@ static hipError_t zero_fill(void* p, size_t n) {
   return hipStreamSynchronize(st);
 }
 
+// A solver counts its device memory (memory_bytes) over the DevBufs it is made of, without a list to keep: DevBufRegistry is SolverT's
+// first base class, and every DevBuf constructed on this thread between its constructor and the body of SolverT's, which clears
+// g_registering -- the solver's members, all of them -- enters its list.  A DevBuf made at any other time (a local of a member function)
+// belongs to nobody.
+struct DevBuf;
+thread_local std::vector<const DevBuf*>* g_registering = nullptr;
+struct DevBufRegistry {
+  std::vector<const DevBuf*> bufs;
+  DevBufRegistry() { g_registering = &bufs; }
+};
+
 struct DevBuf {  // owning device allocation
   void* p = nullptr;
   size_t bytes = 0;
+  DevBuf() {
+    if (g_registering) g_registering->push_back(this);
+  }
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
   ~DevBuf() { release(); }
   void release() {
     if (p) (void)hipFree(p);
@@ -105,6 +121,8 @@ struct DevBuf {  // owning device allocation
     }
     return CAL_OK;
   }
+  // at least n bytes: a new allocation only when there is none or it is too small (it never shrinks)
+  int reserve(size_t n, bool zero = true) { return p && bytes >= n ? (int)CAL_OK : alloc(n, zero); }
   template <typename U> U* as() const { return reinterpret_cast<U*>(p); }
 };
 
@@ -190,7 +208,7 @@ struct cal_solver {
 };
 
 template <typename T>
-struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.hpp): what set-up decided about the problem
+struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars (problem_plan.hpp): what set-up decided about the problem
   using T2 = vec2_t<T>;
   hipStream_t stream = nullptr;
   // Synchronous copies go through the solver's OWN (non-blocking) stream, never the legacy stream: a copy there synchronises with
@@ -217,22 +235,21 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
   DevBuf gcp0, gcp1, gc0, gc1;                 // coefficient-gradient partials and (multi-item groups) their sums
   DevBuf part, state, losses, scratch, model_buf;
   DevBuf gs_out, gs_ptr, gs_ent, gs_mask;      // solve_gains: num_r | num_i | den ([3][nants][nfreqs] doubles, the exchange payload); the antenna lists without autocorrelations; [nslices] mask bytes
-  // solve_coeffs (coeff_solve_kernels.hpp): the groups as its kernels see them (host copy: set_problem; device copy, order, work list and
-  // chunks: the first call), N of a chunk of groups in T (cs_n) and its factor in double (cs_d), rhs [2][ncoef] T, the two counters
-  DevBuf cs_grp, cs_order, cs_work, cs_n, cs_d, cs_rhs, cs_cnt;
+  // what the plans of the closed-form calls are made from (solve_plan.hpp), as set_problem's plan held it on the host
   std::vector<CsGroup> h_cs_grp;
-  struct CsChunkRange { int g0, g1, w0, w1; size_t lds; };  // positions in cs_order / cs_work; dynamic LDS of its coeff_chol_kernel launch
-  std::vector<CsChunkRange> cs_chunks;
-  static constexpr int64_t kCsScratchDefault = 256ll << 20;  // bytes of cs_n + cs_d a chunk may take (one group alone may take more)
-  static constexpr int kCsLdsDoubles = 16384;                 // 128 KB: a factor of up to 126 vectors stays in LDS
-  int64_t cs_bound = kCsScratchDefault;
+  std::vector<long long> h_bl_tile;
+  std::vector<int2> h_bl_ant;
+  // solve_coeffs (coeff_solve_kernels.hpp): the groups with its plan's offsets, order, work list and chunks (the first call), N of a
+  // chunk of groups in T (cs_n) and its factor in double (cs_d), rhs [2][ncoef] T, the two counters
+  DevBuf cs_grp, cs_order, cs_work, cs_n, cs_d, cs_rhs, cs_cnt;
+  std::vector<GroupChunk> cs_chunks;
+  int64_t cs_bound = kCsScratchDefault;        // bytes of scratch a chunk of any closed-form call may take (set_coeff_solve_scratch)
   // fit_errors (fit_error_kernels.hpp): a plan of its own (the chunks also hold W, so they are cut elsewhere than solve_coeffs'): the
   // groups with this plan's offsets, order, Gram work list, W offsets, the leverage kernel's work list; per chunk N (fe_n), the factor
   // (fe_d) and W (fe_w); rhs of the Gram kernel (unused), ok [ngrps] ints + the two counters (fe_ok), the partial sums
   // [nbls][slots] (fe_part), the outputs coeff_var | leverage_bl | nsamp_bl (fe_out) and, only when asked for, model_var (fe_mv)
   DevBuf fe_grp, fe_order, fe_work, fe_woff, fe_lwork, fe_n, fe_d, fe_w, fe_rhs, fe_ok, fe_part, fe_out, fe_mv;
-  struct FeChunkRange { int g0, g1, w0, w1, l0, l1; size_t lds; };  // positions in fe_order / fe_work / fe_lwork
-  std::vector<FeChunkRange> fe_chunks;
+  std::vector<GroupChunk> fe_chunks;
   int fe_npieces = 0;
   // solve_gain_coeffs (gain_basis_solve_kernels.hpp): N_a of a chunk of antenna rows in T (gbs_n), its factor in double where it does not
   // fit LDS (gbs_d), rhs [nants][2][K] T, the two counters; the chunks share cs_bound
@@ -337,6 +354,7 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
   size_t hook_bytes = 0;
   bool comm_on() const { return nccl != nullptr || hook != nullptr; }
 
+  SolverT() { g_registering = nullptr; }  // every member DevBuf is in bufs by now
   ~SolverT() override {
     (void)hipSetDevice(device);
     if (nccl) (void)ncclCommDestroy(nccl);
@@ -421,7 +439,7 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     const int shape = ok ? shape_code(nants, fpad, nslices) : 0;
     const int plan = mf_ok ? 2 : (nheads == 0 || heads_one_pass_local) ? 1 : 0;
     int v[4] = {ok ? 4 * shape + plan : -1, ok ? steps_per_sync : (1 << 30), ok && lamb_ok ? -local_nv : -(1 << 30), -shape};
-    const int arc = agree_min(v, 4);
+    const int arc = agree_ints(v, 4, CAL_XCHG_MIN);
     if (arc != CAL_OK) {
       has_problem = false;
       return arc;
@@ -453,8 +471,7 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     if (lamb_ok) {
       std::vector<int> slot(std::max(lamb_ncvar, 1), 0);
       for (int k = 0; k < lamb_ncvar; ++k) slot[k] = lamb_cvar_slice[k] * lamb_nv + lamb_cvar_id[k];
-      CAL_TRY(lamb_slot.alloc(slot.size() * sizeof(int), false));
-      HIP_TRY(copy_sync(lamb_slot.p, slot.data(), slot.size() * sizeof(int), hipMemcpyHostToDevice));
+      CAL_TRY(upload(lamb_slot, slot));
       CAL_TRY(lamb_glob.alloc((size_t)std::max(1, 2 * nslices * lamb_nv) * 2 * sizeof(double)));
     }
     return CAL_OK;
@@ -483,7 +500,7 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     static_cast<PlanScalars&>(*this) = p;
     local_reg_plan();
     lamb_cvar_slice = p.lamb_cvar_slice; lamb_cvar_id = p.lamb_cvar_id;
-    h_grp_coff = p.grp_coff; h_slice_coff = p.slice_coff; h_slice_cblk = p.slice_cblk; h_cs_grp = p.cs_grp;
+    h_grp_coff = p.grp_coff; h_slice_coff = p.slice_coff; h_slice_cblk = p.slice_cblk; h_cs_grp = p.cs_grp; h_bl_tile = p.bl_tile; h_bl_ant = p.bl_ant;
     CAL_TRY(size_state(nslices));
     CAL_TRY(upload(slice_coff, p.slice_coff));
     CAL_TRY(upload(lamb_vars, p.lamb_vars));
@@ -621,7 +638,6 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     return CAL_OK;
   }
 
-  // min over the ranks of the communicator (set-up decisions that every rank must take identically)
   // one in-place all-reduce over the ranks of the job, on the solver's stream: RCCL, or the caller's exchange hook (the
   // stream is drained, the buffer staged through pinned host memory, reduced by the callback and copied back)
   int all_reduce(void* dev, size_t count, int dtype_code, int op) {
@@ -651,11 +667,12 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     heads_one_pass = heads_one_pass_local;
     reg_prepass = nheads > 0 && !heads_one_pass_local;
   }
-  int agree_min(int* v, int n) {
+  // a few ints reduced over the ranks of the communicator: the minimum (set-up decisions that every rank must take identically) or the sum
+  int agree_ints(int* v, int n, int op) {
     if (!comm_on()) return CAL_OK;
-    if (agree_buf.bytes < (size_t)n * sizeof(int)) CAL_TRY(agree_buf.alloc((size_t)n * sizeof(int)));
+    CAL_TRY(agree_buf.reserve((size_t)n * sizeof(int)));
     HIP_TRY(hipMemcpyAsync(agree_buf.p, v, n * sizeof(int), hipMemcpyHostToDevice, stream));
-    CAL_TRY(all_reduce(agree_buf.p, n, CAL_XCHG_I32, CAL_XCHG_MIN));
+    CAL_TRY(all_reduce(agree_buf.p, n, CAL_XCHG_I32, op));
     HIP_TRY(hipMemcpyAsync(v, agree_buf.p, n * sizeof(int), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return CAL_OK;
@@ -663,7 +680,7 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
 
   // ---- padded copies ------------------------------------------------------------------------------------------
   int ensure_scratch(size_t bytes) {
-    if (scratch.bytes < bytes) CAL_TRY(scratch.alloc(bytes, false));
+    CAL_TRY(scratch.reserve(bytes, false));
     return CAL_OK;
   }
   // host [rows][nfreqs] -> device [rows][fpad] * stride + off
@@ -1654,7 +1671,7 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     }
     if (r->use_min && yb_on() && !gb_ysnap.p) CAL_TRY(gb_ysnap.alloc(gb_y.bytes));
     const size_t lbytes = (size_t)nslices * r->nsteps * sizeof(double);
-    if (r->record && losses.bytes < lbytes) CAL_TRY(losses.alloc(lbytes));
+    if (r->record) CAL_TRY(losses.reserve(lbytes));
     if (!losses.p) CAL_TRY(losses.alloc((size_t)nslices * sizeof(double)));
     for (int t = 0; t < nslices; ++t) {
       DevState& h = h_state[t];
@@ -1740,7 +1757,7 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     if (with_gains && !has_gains) return fail(CAL_ERR_STATE, "data_model: the gains must be set");
     if (!mr || !mi) return fail(CAL_ERR_INVALID, "model: null output");
     const size_t rowbytes = (size_t)nbls * fpad * sizeof(T);
-    if (model_buf.bytes < 2 * rowbytes) CAL_TRY(model_buf.alloc(2 * rowbytes));
+    CAL_TRY(model_buf.reserve(2 * rowbytes));
     begin_pass_state();
     CAL_TRY(push_state());
     FusedArgs<T> a = fused_args();
@@ -1764,18 +1781,13 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     if (need_gains && !has_gains) return fail(CAL_ERR_STATE, "%s: the gains must be set (cal_solver_set_params)", who);
     return CAL_OK;
   }
-  int check_damping_ridge(const char* who, double damping, const double* ridge) {
-    if (!(damping > 0.0 && damping <= 1.0)) return fail(CAL_ERR_INVALID, "%s: damping = %g lies outside (0, 1]", who, damping);
-    if (ridge && (!(*ridge >= 0.0) || !std::isfinite(*ridge))) return fail(CAL_ERR_INVALID, "%s: ridge = %g must be finite and >= 0", who, *ridge);
-    return CAL_OK;
-  }
   // The model pass of model() into model_buf ([planes][nbls][fpad]), then rows(model_r, model_i, q_rows) launches what turns the planes
   // into the call's own rows (q_rows: the third plane, null when two are asked for).  The host mirror of the loop state is put back and
   // pushed again afterwards: the pass clears the slices' stop flags for itself.
   template <typename Rows>
   int model_pass(int planes, Rows rows) {
     const size_t plane = (size_t)nbls * fpad;
-    if (model_buf.bytes < planes * plane * sizeof(T)) CAL_TRY(model_buf.alloc(planes * plane * sizeof(T)));
+    CAL_TRY(model_buf.reserve(planes * plane * sizeof(T)));
     const std::vector<DevState> saved(h_state, h_state + nslices);
     begin_pass_state();
     CAL_TRY(push_state());
@@ -1793,7 +1805,7 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
   int upload_slice_mask(const uint8_t* host, const unsigned char** dev) {
     *dev = nullptr;
     if (!host) return CAL_OK;
-    if (gs_mask.bytes < (size_t)nslices) CAL_TRY(gs_mask.alloc((size_t)nslices, false));
+    CAL_TRY(gs_mask.reserve((size_t)nslices, false));
     HIP_TRY(copy_sync(gs_mask.p, host, (size_t)nslices, hipMemcpyHostToDevice));
     *dev = gs_mask.as<unsigned char>();
     return CAL_OK;
@@ -1832,11 +1844,11 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     if (!g_r && !has_gains) return fail(CAL_ERR_STATE, "fit_quality: the gains must be set (cal_solver_set_params) or given");
     const size_t nant_out = (size_t)nants * nfreqs;
     const size_t out_bytes = (2 * nant_out + 2 * (size_t)nbls) * sizeof(double);
-    if (fq_out.bytes < out_bytes) CAL_TRY(fq_out.alloc(out_bytes));
+    CAL_TRY(fq_out.reserve(out_bytes));
     const T2* g = gains.as<T2>();
     if (g_r) {
       const size_t gbytes = (size_t)nants * fpad * sizeof(T2);
-      if (fq_gains.bytes < gbytes) CAL_TRY(fq_gains.alloc(gbytes));
+      CAL_TRY(fq_gains.reserve(gbytes));
       CAL_TRY(upload_rows(g_r, fq_gains.as<T>(), nants, 2, 0));
       CAL_TRY(upload_rows(g_i, fq_gains.as<T>(), nants, 2, 1));
       g = fq_gains.as<T2>();
@@ -1872,13 +1884,13 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     if (d->kind != CAL_ROBUST_NONE && d->kind != CAL_ROBUST_HUBER && d->kind != CAL_ROBUST_CAUCHY && d->kind != CAL_ROBUST_CLIP)
       return fail(CAL_ERR_INVALID, "robust_weights: unknown kind %d", d->kind);
     if (!(d->threshold > 0.0) || !std::isfinite(d->threshold)) return fail(CAL_ERR_INVALID, "robust_weights: threshold = %g must be finite and > 0", d->threshold);
-    if (rw_out.bytes < 2 * (size_t)nbls * sizeof(double)) CAL_TRY(rw_out.alloc(2 * (size_t)nbls * sizeof(double)));
+    CAL_TRY(rw_out.reserve(2 * (size_t)nbls * sizeof(double)));
     double* o_scale = rw_out.as<double>();
     double* o_ndown = o_scale + nbls;
     HIP_TRY(hipMemsetAsync(o_scale, 0, 2 * (size_t)nbls * sizeof(double), stream));  // rows of unselected slices report 0
     if (d->kind != CAL_ROBUST_NONE || rw_w0_valid) {  // (kind NONE before any reweighting: the weights are w0 already)
       if (!rw_w0_valid) {
-        if (rw_w0.bytes < wgts.bytes) CAL_TRY(rw_w0.alloc(wgts.bytes, false));
+        CAL_TRY(rw_w0.reserve(wgts.bytes, false));
         HIP_TRY(hipMemcpyAsync(rw_w0.p, wgts.p, wgts.bytes, hipMemcpyDeviceToDevice, stream));
         rw_w0_valid = true;
       }
@@ -1924,30 +1936,80 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     return CAL_OK;
   }
 
-  // the per-antenna lists of gain_solve_ant_kernel: ant_ptr / ant_ent without the autocorrelation rows, in baseline order (built at the
-  // first cal_solver_solve_gains of a problem from the device's own baseline table)
-  int build_solve_lists() {
-    if (gs_ptr.p) return CAL_OK;
-    std::vector<int2> h_ant(nbls);
-    HIP_TRY(copy_sync(h_ant.data(), bl_ant.p, (size_t)nbls * sizeof(int2), hipMemcpyDeviceToHost));
-    std::vector<int> ptr(nants + 1, 0);
-    for (int b = 0; b < nbls; ++b) {
-      if (h_ant[b].x == h_ant[b].y) continue;
-      ptr[h_ant[b].x + 1]++;
-      ptr[h_ant[b].y + 1]++;
+  // ---- the steps the closed-form solves are made of --------------------------------------------------------------------
+  // what every solve call checks first, behind its description (ridge: null where the call has none)
+  int check_solve_call(const char* who, const char* count_name, int count, const char* unit, double damping, const double* ridge) {
+    CAL_TRY(require_set(who, true));
+    if (count < 1) return fail(CAL_ERR_INVALID, "%s: %s = %d, at least one %s", who, count_name, count, unit);
+    if (!(damping > 0.0 && damping <= 1.0)) return fail(CAL_ERR_INVALID, "%s: damping = %g lies outside (0, 1]", who, damping);
+    if (ridge && (!(*ridge >= 0.0) || !std::isfinite(*ridge))) return fail(CAL_ERR_INVALID, "%s: ridge = %g must be finite and >= 0", who, *ridge);
+    return CAL_OK;
+  }
+  int check_moment_reset(const char* who, int reset, const char* flag) {
+    if (reset && !has_opt) return fail(CAL_ERR_STATE, "%s: %s without an optimizer (cal_solver_set_optimizer)", who, flag);
+    return CAL_OK;
+  }
+  // what the antenna sweeps work on: the per-antenna lists without the autocorrelation rows (problem_plan.hpp; uploaded at the first
+  // call of a problem) and their output planes
+  int gain_sweep_setup() {
+    if (!gs_ptr.p) {
+      std::vector<int> ptr;
+      std::vector<int2> ent;
+      antenna_lists(nants, h_bl_ant, true, ptr, ent);
+      CAL_TRY(upload(gs_ent, ent));
+      CAL_TRY(upload(gs_ptr, ptr));
     }
-    for (int a = 0; a < nants; ++a) ptr[a + 1] += ptr[a];
-    std::vector<int2> ent((size_t)std::max(1, ptr[nants]));
-    std::vector<int> fill(ptr.begin(), ptr.end() - 1);
-    for (int b = 0; b < nbls; ++b) {
-      if (h_ant[b].x == h_ant[b].y) continue;
-      ent[fill[h_ant[b].x]++] = make_int2(b * 2 + 0, h_ant[b].y);
-      ent[fill[h_ant[b].y]++] = make_int2(b * 2 + 1, h_ant[b].x);
+    return gs_out.reserve(3 * (size_t)nants * nfreqs * sizeof(double));
+  }
+  template <typename Kern>
+  int allow_chol_lds(Kern* kern) {  // a factor kernel may ask for kCsLdsDoubles of dynamic LDS
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kCsLdsDoubles * (int)sizeof(double)));
+    return CAL_OK;
+  }
+  struct RowPlanes { T *u_r = nullptr, *u_i = nullptr, *q = nullptr; };  // the three planes of model_buf behind a rows kernel
+  // the model pass of model(), then gain_solve_rows_kernel: the planes the antenna sweeps read
+  int gain_planes(RowPlanes& P) {
+    return model_pass(3, [&](T* model_r, T* model_i, T* third) {
+      P = RowPlanes{model_r, model_i, third};
+      hipLaunchKernelGGL(gain_solve_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, P.u_r, P.u_i, P.q, data_r.as<T>(), data_i.as<T>(),
+                         wgts.as<T>(), bl_ant.as<int2>(), nbls, nfreqs, fpad);
+    });
+  }
+  // the model pass of model(), then coeff_solve_rows_kernel: the planes the Gram kernel reads
+  int coeff_planes(RowPlanes& P) {
+    return model_pass(3, [&](T* model_r, T* model_i, T* third) {
+      P = RowPlanes{model_r, model_i, third};
+      hipLaunchKernelGGL(coeff_solve_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, P.u_r, P.u_i, P.q, data_r.as<T>(), data_i.as<T>(),
+                         wgts.as<T>(), gains.as<T2>(), bl_ant.as<int2>(), nbls, nfreqs, fpad);
+    });
+  }
+  // One antenna sweep: gain_solve_ant_kernel into gs_out (num_r | num_i | den), then the exchange of its last `nplanes` planes.  The
+  // planes of every rank's baselines add up to the array's: ONE all-reduce of nplanes nants nfreqs doubles per sweep.
+  int antenna_sweep(const RowPlanes& P, int nplanes) {
+    const size_t nant_out = (size_t)nants * nfreqs;
+    constexpr int V = 16 / (int)sizeof(T);
+    const int cblocks = (fpad + 64 * V - 1) / (64 * V);
+    hipLaunchKernelGGL(gain_solve_ant_kernel<T>, dim3(nants * cblocks), dim3(256), 0, stream, P.u_r, P.u_i, P.q, gains.as<T2>(), gs_ptr.as<int>(),
+                       gs_ent.as<int2>(), nants, nfreqs, fpad, gs_out.as<double>());
+    HIP_TRY(hipGetLastError());
+    if (comm_on()) CAL_TRY(all_reduce(gs_out.as<double>() + (3 - nplanes) * nant_out, nplanes * nant_out, CAL_XCHG_F64, CAL_XCHG_SUM));
+    return CAL_OK;
+  }
+  // The end of a solve call: its two counters (cnt: null where it has none), what set_optimizer leaves in the moment slots of the selected
+  // slices -- reset_run(t, t1) for every run of neighbouring ones -- then the stream drained and the result filled in.
+  template <typename Res, typename Reset>
+  int finish_solve(const DevBuf* cnt, Res* res, int reset, const uint8_t* mask, Reset reset_run) {
+    int counts[2] = {0, 0};
+    if (cnt) HIP_TRY(hipMemcpyAsync(counts, cnt->p, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
+    if (reset) {
+      CAL_TRY(for_selected_slice_runs(mask, reset_run));
+      HIP_TRY(hipGetLastError());
     }
-    CAL_TRY(gs_ent.alloc(ent.size() * sizeof(int2), false));
-    HIP_TRY(copy_sync(gs_ent.p, ent.data(), ent.size() * sizeof(int2), hipMemcpyHostToDevice));
-    CAL_TRY(gs_ptr.alloc((nants + 1) * sizeof(int), false));
-    HIP_TRY(copy_sync(gs_ptr.p, ptr.data(), (nants + 1) * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (res) {
+      res->nsolved = counts[0];
+      res->nsingular = counts[1];
+    }
     return CAL_OK;
   }
 
@@ -1956,45 +2018,26 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
   int solve_gains(const cal_gain_solve_desc* d) override {
     HIP_TRY(hipSetDevice(device));
     if (!d) return fail(CAL_ERR_INVALID, "solve_gains: null description");
-    CAL_TRY(require_set("solve_gains", true));
-    if (d->nsweeps < 1) return fail(CAL_ERR_INVALID, "solve_gains: nsweeps = %d, at least one sweep", d->nsweeps);
-    CAL_TRY(check_damping_ridge("solve_gains", d->damping, nullptr));
+    CAL_TRY(check_solve_call("solve_gains", "nsweeps", d->nsweeps, "sweep", d->damping, nullptr));
     if (yb_on())
       return fail(CAL_ERR_UNSUPPORTED, "solve_gains: a gain basis is set (cal_solver_set_gain_basis, cal_solver_set_gain_time_basis): the closed form solves "
                   "free per-channel gains, and projecting them onto a basis is not implemented here; cal_solver_solve_gain_coeffs solves the coefficients of a "
                   "frequency basis, or detach the basis (nvec = 0) first");
-    if (d->reset_gain_moments && !has_opt) return fail(CAL_ERR_STATE, "solve_gains: reset_gain_moments without an optimizer (cal_solver_set_optimizer)");
-    CAL_TRY(build_solve_lists());
-    const size_t nant_out = (size_t)nants * nfreqs;
-    if (gs_out.bytes < 3 * nant_out * sizeof(double)) CAL_TRY(gs_out.alloc(3 * nant_out * sizeof(double)));
+    CAL_TRY(check_moment_reset("solve_gains", d->reset_gain_moments, "reset_gain_moments"));
+    CAL_TRY(gain_sweep_setup());
     const unsigned char* mask = nullptr;
     CAL_TRY(upload_slice_mask(d->slice_mask, &mask));
-    T *u_r = nullptr, *u_i = nullptr, *q_rows = nullptr;
-    CAL_TRY(model_pass(3, [&](T* model_r, T* model_i, T* third) {
-      u_r = model_r, u_i = model_i, q_rows = third;
-      hipLaunchKernelGGL(gain_solve_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, u_r, u_i, q_rows, data_r.as<T>(), data_i.as<T>(),
-                         wgts.as<T>(), bl_ant.as<int2>(), nbls, nfreqs, fpad);
-    }));
-    constexpr int V = 16 / (int)sizeof(T);
-    const int cblocks = (fpad + 64 * V - 1) / (64 * V);
+    RowPlanes P;
+    CAL_TRY(gain_planes(P));
     for (int k = 0; k < d->nsweeps; ++k) {
-      hipLaunchKernelGGL(gain_solve_ant_kernel<T>, dim3(nants * cblocks), dim3(256), 0, stream, u_r, u_i, q_rows, gains.as<T2>(),
-                         gs_ptr.as<int>(), gs_ent.as<int2>(), nants, nfreqs, fpad, gs_out.as<double>());
-      HIP_TRY(hipGetLastError());
-      // the planes of every rank's baselines add up to the array's: ONE all-reduce of 3 nants nfreqs doubles per sweep
-      if (comm_on()) CAL_TRY(all_reduce(gs_out.p, 3 * nant_out, CAL_XCHG_F64, CAL_XCHG_SUM));
-      hipLaunchKernelGGL(gain_solve_apply_kernel<T>, dim3(grid_for((long long)nant_out)), dim3(256), 0, stream, gains.as<T2>(), gs_out.as<double>(),
+      CAL_TRY(antenna_sweep(P, 3));
+      hipLaunchKernelGGL(gain_solve_apply_kernel<T>, dim3(grid_for((long long)nants * nfreqs)), dim3(256), 0, stream, gains.as<T2>(), gs_out.as<double>(),
                          mask, na_slice, nants, nfreqs, fpad, d->damping);
       HIP_TRY(hipGetLastError());
     }
-    if (d->reset_gain_moments) {
-      // what set_optimizer leaves in the gain slots, for the selected slices (runs of neighbouring slices in one call each)
-      const size_t per = (size_t)na_slice * fpad * 2;  // reals per slice
-      CAL_TRY(for_selected_slice_runs(d->slice_mask, [&](int t, int t1) { return reset_moment_slots(gains_m, gains_v, (size_t)t * per, (size_t)(t1 - t) * per); }));
-      HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipStreamSynchronize(stream));
-    return CAL_OK;
+    const size_t per = (size_t)na_slice * fpad * 2;  // reals of the gain slots per slice
+    return finish_solve(nullptr, (cal_coeff_solve_result*)nullptr, d->reset_gain_moments, d->slice_mask,
+                        [&](int t, int t1) { return reset_moment_slots(gains_m, gains_v, (size_t)t * per, (size_t)(t1 - t) * per); });
   }
 
   // ---- cal_solver_normal_product / cal_solver_gauss_newton_step (gauss_newton_kernels.hpp) -----------------------
@@ -2025,34 +2068,31 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
   }
   int gn_alloc(bool cg) {
     const size_t np = gn_np(), plane = (size_t)nbls * fpad;
-    auto need = [](DevBuf& b, size_t bytes) { return b.bytes >= bytes && b.p ? (int)CAL_OK : b.alloc(bytes); };
-    CAL_TRY(need(gn_s, np * sizeof(T)));
-    CAL_TRY(need(gn_g0, np * sizeof(T)));
-    CAL_TRY(need(gn_save, np * sizeof(T)));
-    CAL_TRY(need(gn_ns, np * sizeof(double)));
-    CAL_TRY(need(gn_m, 2 * plane * sizeof(T)));
-    CAL_TRY(need(gn_sd, 2 * plane * sizeof(T)));
-    CAL_TRY(need(gn_rows, 3 * (size_t)nbls * sizeof(double)));
-    CAL_TRY(need(gn_part, (size_t)nslices * kGnBlocks * sizeof(double)));
-    CAL_TRY(need(gn_scal, (size_t)nslices * sizeof(GnScal)));
+    CAL_TRY(gn_s.reserve(np * sizeof(T)));
+    CAL_TRY(gn_g0.reserve(np * sizeof(T)));
+    CAL_TRY(gn_save.reserve(np * sizeof(T)));
+    CAL_TRY(gn_ns.reserve(np * sizeof(double)));
+    CAL_TRY(gn_m.reserve(2 * plane * sizeof(T)));
+    CAL_TRY(gn_sd.reserve(2 * plane * sizeof(T)));
+    CAL_TRY(gn_rows.reserve(3 * (size_t)nbls * sizeof(double)));
+    CAL_TRY(gn_part.reserve((size_t)nslices * kGnBlocks * sizeof(double)));
+    CAL_TRY(gn_scal.reserve((size_t)nslices * sizeof(GnScal)));
     if (!gn_rowptr.p) {
       // the groups are listed slice by slice and a group's rows are contiguous: so are a slice's rows
       std::vector<int> ptr(nslices + 1, nbls);
       for (int k = ngrps - 1; k >= 0; --k) ptr[h_cs_grp[k].slice] = std::min(ptr[h_cs_grp[k].slice], h_cs_grp[k].b0);
       for (int t = nslices - 1; t >= 0; --t) ptr[t] = std::min(ptr[t], ptr[t + 1]);
-      CAL_TRY(gn_rowptr.alloc(ptr.size() * sizeof(int), false));
-      HIP_TRY(copy_sync(gn_rowptr.p, ptr.data(), ptr.size() * sizeof(int), hipMemcpyHostToDevice));
+      CAL_TRY(upload(gn_rowptr, ptr));
     }
     if (!cg) return CAL_OK;
-    CAL_TRY(need(gn_x, np * sizeof(double)));
-    CAL_TRY(need(gn_res, np * sizeof(double)));
-    CAL_TRY(need(gn_D, np * sizeof(double)));
-    CAL_TRY(need(gn_lam, (size_t)nslices * sizeof(double)));
+    CAL_TRY(gn_x.reserve(np * sizeof(double)));
+    CAL_TRY(gn_res.reserve(np * sizeof(double)));
+    CAL_TRY(gn_D.reserve(np * sizeof(double)));
+    CAL_TRY(gn_lam.reserve((size_t)nslices * sizeof(double)));
     if (!gn_grp.p) {
       std::vector<GnGroup> g(ngrps);
       for (int k = 0; k < ngrps; ++k) g[k] = GnGroup{h_cs_grp[k].b0, h_cs_grp[k].b1, h_cs_grp[k].coff, h_cs_grp[k].nvec};
-      CAL_TRY(gn_grp.alloc((size_t)ngrps * sizeof(GnGroup), false));
-      HIP_TRY(copy_sync(gn_grp.p, g.data(), (size_t)ngrps * sizeof(GnGroup), hipMemcpyHostToDevice));
+      CAL_TRY(upload(gn_grp, g));
     }
     return CAL_OK;
   }
@@ -2108,11 +2148,7 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
   int gn_linearize(GnGuard& G, bool with_precond) {
     const size_t plane = (size_t)nbls * fpad;
     hipError_t ce = hipSuccess;
-    if (with_precond) {
-      CAL_TRY(build_solve_lists());
-      const size_t nant_out = (size_t)nants * nfreqs;
-      if (gs_out.bytes < 3 * nant_out * sizeof(double)) CAL_TRY(gs_out.alloc(3 * nant_out * sizeof(double)));
-    }
+    if (with_precond) CAL_TRY(gain_sweep_setup());
     T *u_r = nullptr, *u_i = nullptr, *q_rows = nullptr;
     CAL_TRY(model_pass(with_precond ? 3 : 2, [&](T* model_r, T* model_i, T* third) {
       ce = hipMemcpyAsync(gn_m.p, model_r, 2 * plane * sizeof(T), hipMemcpyDeviceToDevice, stream);  // (model_i = model_r + plane)
@@ -2302,14 +2338,8 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
 
   // ---- cal_solver_solve_coeffs ----------------------------------------------------------------------------------
   void release_coeff_solve() {  // the plan of a problem / a scratch bound: rebuilt by the next call
-    cs_grp.release();
-    cs_order.release();
-    cs_work.release();
-    cs_n.release();
-    cs_d.release();
-    cs_cnt.release();
     cs_chunks.clear();
-    for (DevBuf* b : {&fe_grp, &fe_order, &fe_work, &fe_woff, &fe_lwork, &fe_n, &fe_d, &fe_w, &fe_rhs, &fe_ok, &fe_part, &fe_out, &fe_mv}) b->release();
+    for (DevBuf* b : {&cs_grp, &cs_order, &cs_work, &cs_n, &cs_d, &cs_cnt, &fe_grp, &fe_order, &fe_work, &fe_woff, &fe_lwork, &fe_n, &fe_d, &fe_w, &fe_rhs, &fe_ok, &fe_part, &fe_out, &fe_mv}) b->release();
     fe_chunks.clear();
   }
   int set_coeff_solve_scratch(int64_t bytes) override {
@@ -2319,54 +2349,19 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     release_gain_coeff_solve();
     return CAL_OK;
   }
-  // Groups heaviest first (as everywhere: the tail of a launch is made of the lightest), cut into chunks whose N (T) and factor
-  // (double) stay under cs_bound bytes -- a group that alone needs more is a chunk of its own.  Every chunk reuses the two scratch
-  // buffers from offset 0; a group's result does not depend on the chunk it falls into.
+  // The plan of solve_plan.hpp for this problem and bound, uploaded at the first call.  Every chunk reuses the two scratch buffers from
+  // offset 0; a group's result does not depend on the chunk it falls into.
   int build_coeff_solve_plan() {
     if (!cs_chunks.empty()) return CAL_OK;
-    std::vector<int> order(ngrps);
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return h_cs_grp[a].nvec > h_cs_grp[b].nvec; });
-    std::vector<CsWork> work;
-    std::vector<CsChunkRange> chunks;
-    long long n_max = 0, d_max = 0;
-    for (int p = 0; p < ngrps;) {
-      long long noff = 0, doff = 0;
-      int max_nvec = 0;
-      CsChunkRange ch{p, p, (int)work.size(), 0, 0};
-      for (; p < ngrps; ++p) {
-        CsGroup& g = h_cs_grp[order[p]];
-        const long long nn = (long long)g.nvec * g.nvec, dd = (long long)(g.nvec + 2) * g.nvec;
-        if (p > ch.g0 && (noff + nn) * (long long)sizeof(T) + (doff + dd) * 8 > cs_bound) break;
-        g.noff = noff;
-        g.doff = doff;
-        noff += nn;
-        doff += dd;
-        max_nvec = std::max(max_nvec, g.nvec);
-        const int nb = (g.nvec + kNsBlock - 1) / kNsBlock;
-        for (int bi = 0; bi < nb; ++bi)
-          for (int bj = 0; bj <= bi; ++bj) work.push_back(CsWork{order[p], bi, bj, 0});
-      }
-      ch.g1 = p;
-      ch.w1 = (int)work.size();
-      const long long want = (long long)(max_nvec + 2) * (max_nvec | 1);
-      ch.lds = (size_t)std::min<long long>(want, kCsLdsDoubles) * sizeof(double);
-      chunks.push_back(ch);
-      n_max = std::max(n_max, noff);
-      d_max = std::max(d_max, doff);
-    }
-    CAL_TRY(cs_grp.alloc((size_t)ngrps * sizeof(CsGroup), false));
-    HIP_TRY(copy_sync(cs_grp.p, h_cs_grp.data(), (size_t)ngrps * sizeof(CsGroup), hipMemcpyHostToDevice));
-    CAL_TRY(cs_order.alloc((size_t)ngrps * sizeof(int), false));
-    HIP_TRY(copy_sync(cs_order.p, order.data(), (size_t)ngrps * sizeof(int), hipMemcpyHostToDevice));
-    CAL_TRY(cs_work.alloc(work.size() * sizeof(CsWork), false));
-    HIP_TRY(copy_sync(cs_work.p, work.data(), work.size() * sizeof(CsWork), hipMemcpyHostToDevice));
-    CAL_TRY(cs_n.alloc((size_t)n_max * sizeof(T), false));
-    CAL_TRY(cs_d.alloc((size_t)d_max * sizeof(double), false));
+    const GroupPlan P = plan_group_chunks(h_cs_grp, sizeof(T), cs_bound, {});  // (its offsets land in h_cs_grp; nothing else reads them)
+    CAL_TRY(upload(cs_grp, h_cs_grp));
+    CAL_TRY(upload(cs_order, P.order));
+    CAL_TRY(upload(cs_work, P.work));
+    CAL_TRY(cs_n.alloc((size_t)P.n_max * sizeof(T), false));
+    CAL_TRY(cs_d.alloc((size_t)P.d_max * sizeof(double), false));
     CAL_TRY(cs_cnt.alloc(2 * sizeof(int)));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&coeff_chol_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                kCsLdsDoubles * (int)sizeof(double)));
-    cs_chunks = chunks;
+    CAL_TRY(allow_chol_lds(&coeff_chol_kernel<T>));
+    cs_chunks = P.chunks;
     return CAL_OK;
   }
 
@@ -2375,26 +2370,19 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
   int solve_coeffs(const cal_coeff_solve_desc* d, cal_coeff_solve_result* res) override {
     HIP_TRY(hipSetDevice(device));
     if (!d) return fail(CAL_ERR_INVALID, "solve_coeffs: null description");
-    CAL_TRY(require_set("solve_coeffs", true));
-    if (d->niters < 1) return fail(CAL_ERR_INVALID, "solve_coeffs: niters = %d, at least one iteration", d->niters);
-    CAL_TRY(check_damping_ridge("solve_coeffs", d->damping, &d->ridge));
-    if (d->reset_coeff_moments && !has_opt) return fail(CAL_ERR_STATE, "solve_coeffs: reset_coeff_moments without an optimizer (cal_solver_set_optimizer)");
+    CAL_TRY(check_solve_call("solve_coeffs", "niters", d->niters, "iteration", d->damping, &d->ridge));
+    CAL_TRY(check_moment_reset("solve_coeffs", d->reset_coeff_moments, "reset_coeff_moments"));
     CAL_TRY(build_coeff_solve_plan());
-    if (cs_rhs.bytes < 2 * (size_t)ncoef * sizeof(T)) CAL_TRY(cs_rhs.alloc(2 * (size_t)ncoef * sizeof(T)));
+    CAL_TRY(cs_rhs.reserve(2 * (size_t)ncoef * sizeof(T)));
     const unsigned char* mask = nullptr;
     CAL_TRY(upload_slice_mask(d->slice_mask, &mask));
-    int counts[2] = {0, 0};
     for (int it = 0; it < d->niters; ++it) {
-      T *u_r = nullptr, *u_i = nullptr, *q_rows = nullptr;
-      CAL_TRY(model_pass(3, [&](T* model_r, T* model_i, T* third) {
-        u_r = model_r, u_i = model_i, q_rows = third;
-        hipLaunchKernelGGL(coeff_solve_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, u_r, u_i, q_rows, data_r.as<T>(), data_i.as<T>(),
-                           wgts.as<T>(), gains.as<T2>(), bl_ant.as<int2>(), nbls, nfreqs, fpad);
-      }));
+      RowPlanes P;
+      CAL_TRY(coeff_planes(P));
       HIP_TRY(hipMemsetAsync(cs_cnt.p, 0, 2 * sizeof(int), stream));
-      for (const CsChunkRange& ch : cs_chunks) {
-        hipLaunchKernelGGL(coeff_gram_kernel<T>, dim3(ch.w1 - ch.w0), dim3(256), 0, stream, tiles.as<T>(), bl_tile.as<long long>(), u_r,
-                           u_i, q_rows, cs_grp.as<CsGroup>(), cs_work.as<CsWork>() + ch.w0, cs_n.as<T>(), cs_rhs.as<T>(), ncoef, nfreqs, fpad,
+      for (const GroupChunk& ch : cs_chunks) {
+        hipLaunchKernelGGL(coeff_gram_kernel<T>, dim3(ch.w1 - ch.w0), dim3(256), 0, stream, tiles.as<T>(), bl_tile.as<long long>(), P.u_r,
+                           P.u_i, P.q, cs_grp.as<CsGroup>(), cs_work.as<CsWork>() + ch.w0, cs_n.as<T>(), cs_rhs.as<T>(), ncoef, nfreqs, fpad,
                            fold ? 1 : 0);
         hipLaunchKernelGGL(coeff_chol_kernel<T>, dim3(ch.g1 - ch.g0), dim3(256), ch.lds, stream, cs_n.as<T>(), cs_rhs.as<T>(), cs_d.as<double>(),
                            cs_grp.as<CsGroup>(), cs_order.as<int>() + ch.g0, coef.as<T>(), coef.as<T>() + ncoef, ncoef, mask, d->damping, d->ridge,
@@ -2402,97 +2390,36 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
         HIP_TRY(hipGetLastError());
       }
     }
-    HIP_TRY(hipMemcpyAsync(counts, cs_cnt.p, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
-    if (d->reset_coeff_moments) {
-      // what set_optimizer leaves in the coefficient slots, for the selected slices (runs of neighbouring slices in one call per plane)
-      CAL_TRY(for_selected_slice_runs(d->slice_mask, [&](int t, int t1) {
-        const size_t n = (size_t)(h_slice_coff[t1] - h_slice_coff[t]);
-        for (int plane = 0; plane < 2 && n > 0; ++plane) CAL_TRY(reset_moment_slots(coef_m, coef_v, (size_t)plane * ncoef + h_slice_coff[t], n));
-        return (int)CAL_OK;
-      }));
-      HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipStreamSynchronize(stream));
-    if (res) {
-      res->nsolved = counts[0];
-      res->nsingular = counts[1];
-    }
-    return CAL_OK;
+    // the coefficient slots of a run of slices, one call per plane
+    return finish_solve(&cs_cnt, res, d->reset_coeff_moments, d->slice_mask, [&](int t, int t1) {
+      const size_t n = (size_t)(h_slice_coff[t1] - h_slice_coff[t]);
+      for (int plane = 0; plane < 2 && n > 0; ++plane) CAL_TRY(reset_moment_slots(coef_m, coef_v, (size_t)plane * ncoef + h_slice_coff[t], n));
+      return (int)CAL_OK;
+    });
   }
 
   // ---- cal_solver_fit_errors -------------------------------------------------------------------------------------
-  // build_coeff_solve_plan's cut with W (padded to whole 16 x 16 tiles, T) counted in a chunk's bytes, and per chunk the leverage
-  // kernel's work: every run of a group's baselines on one row block x every 64 channels of the (half) band.
+  // solve_coeffs' plan with W counted in a chunk's bytes, and per chunk the leverage kernel's work (solve_plan.hpp).
   int build_fit_error_plan() {
     if (!fe_chunks.empty()) return CAL_OK;
-    std::vector<CsGroup> grp = h_cs_grp;
-    std::vector<long long> h_tile(nbls);
-    HIP_TRY(copy_sync(h_tile.data(), bl_tile.p, (size_t)nbls * sizeof(long long), hipMemcpyDeviceToHost));
-    std::vector<int> order(ngrps);
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return grp[a].nvec > grp[b].nvec; });
-    const int npieces = ((fold ? nfreqs / 2 : fpad) + kFePiece - 1) / kFePiece;
-    std::vector<CsWork> work;
-    std::vector<FeWork> lwork;
-    std::vector<long long> woff(ngrps, 0);
-    std::vector<FeChunkRange> chunks;
-    long long n_max = 0, d_max = 0, w_max = 0;
-    for (int p = 0; p < ngrps;) {
-      long long noff = 0, doff = 0, wo = 0;
-      int max_nvec = 0;
-      FeChunkRange ch{p, p, (int)work.size(), 0, (int)lwork.size(), 0, 0};
-      for (; p < ngrps; ++p) {
-        CsGroup& g = grp[order[p]];
-        const long long nn = (long long)g.nvec * g.nvec, dd = (long long)(g.nvec + 2) * g.nvec, ww = (long long)fe_pad(g.nvec) * fe_pad(g.nvec);
-        if (p > ch.g0 && (noff + nn + wo + ww) * (long long)sizeof(T) + (doff + dd) * 8 > cs_bound) break;
-        g.noff = noff;
-        g.doff = doff;
-        woff[order[p]] = wo;
-        noff += nn;
-        doff += dd;
-        wo += ww;
-        max_nvec = std::max(max_nvec, g.nvec);
-        const int nb = (g.nvec + kNsBlock - 1) / kNsBlock;
-        for (int bi = 0; bi < nb; ++bi)
-          for (int bj = 0; bj <= bi; ++bj) work.push_back(CsWork{order[p], bi, bj, 0});
-        for (int b = g.b0; b < g.b1;) {
-          int e = b + 1;
-          while (e < g.b1 && h_tile[e] == h_tile[b]) ++e;
-          for (int piece = 0; piece < npieces; ++piece) lwork.push_back(FeWork{order[p], b, e, piece});
-          b = e;
-        }
-      }
-      ch.g1 = p;
-      ch.w1 = (int)work.size();
-      ch.l1 = (int)lwork.size();
-      const long long want = (long long)(max_nvec + 2) * (max_nvec | 1);
-      ch.lds = (size_t)std::min<long long>(want, kCsLdsDoubles) * sizeof(double);
-      chunks.push_back(ch);
-      n_max = std::max(n_max, noff);
-      d_max = std::max(d_max, doff);
-      w_max = std::max(w_max, wo);
-    }
-    auto put = [&](DevBuf& buf, const void* src, size_t bytes) {
-      CAL_TRY(buf.alloc(bytes, false));
-      HIP_TRY(copy_sync(buf.p, src, bytes, hipMemcpyHostToDevice));
-      return (int)CAL_OK;
-    };
-    CAL_TRY(put(fe_grp, grp.data(), (size_t)ngrps * sizeof(CsGroup)));
-    CAL_TRY(put(fe_order, order.data(), (size_t)ngrps * sizeof(int)));
-    CAL_TRY(put(fe_work, work.data(), work.size() * sizeof(CsWork)));
-    CAL_TRY(put(fe_woff, woff.data(), (size_t)ngrps * sizeof(long long)));
-    CAL_TRY(put(fe_lwork, lwork.data(), lwork.size() * sizeof(FeWork)));
-    CAL_TRY(fe_n.alloc((size_t)n_max * sizeof(T), false));
-    CAL_TRY(fe_d.alloc((size_t)d_max * sizeof(double), false));
-    CAL_TRY(fe_w.alloc((size_t)w_max * sizeof(T), false));
+    std::vector<CsGroup> grp = h_cs_grp;  // (solve_coeffs' offsets stay where they are)
+    GroupPlan P = plan_group_chunks(grp, sizeof(T), cs_bound, fit_error_extra(grp));
+    plan_leverage_work(P, grp, h_bl_tile, fold ? nfreqs / 2 : fpad);
+    CAL_TRY(upload(fe_grp, grp));
+    CAL_TRY(upload(fe_order, P.order));
+    CAL_TRY(upload(fe_work, P.work));
+    CAL_TRY(upload(fe_woff, P.xoff));
+    CAL_TRY(upload(fe_lwork, P.lwork));
+    CAL_TRY(fe_n.alloc((size_t)P.n_max * sizeof(T), false));
+    CAL_TRY(fe_d.alloc((size_t)P.d_max * sizeof(double), false));
+    CAL_TRY(fe_w.alloc((size_t)P.x_max * sizeof(T), false));
     CAL_TRY(fe_rhs.alloc(2 * (size_t)ncoef * sizeof(T)));
     CAL_TRY(fe_ok.alloc(((size_t)ngrps + 2) * sizeof(int)));
-    CAL_TRY(fe_part.alloc((size_t)nbls * (fold ? 2 : 1) * npieces * sizeof(double)));
+    CAL_TRY(fe_part.alloc((size_t)nbls * (fold ? 2 : 1) * P.npieces * sizeof(double)));
     CAL_TRY(fe_out.alloc(((size_t)ncoef + 2 * (size_t)nbls) * sizeof(double)));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fit_error_factor_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                kCsLdsDoubles * (int)sizeof(double)));
-    fe_npieces = npieces;
-    fe_chunks = chunks;
+    CAL_TRY(allow_chol_lds(&fit_error_factor_kernel<T>));
+    fe_npieces = P.npieces;
+    fe_chunks = P.chunks;
     return CAL_OK;
   }
 
@@ -2520,30 +2447,25 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
       int* ok = fe_ok.as<int>();
       int* dcnt = ok + ngrps;
       const size_t mv_bytes = (size_t)nbls * nfreqs * sizeof(double);
-      if (model_var && fe_mv.bytes < mv_bytes) CAL_TRY(fe_mv.alloc(mv_bytes, false));
+      if (model_var) CAL_TRY(fe_mv.reserve(mv_bytes, false));
       if (want_coef) {
-        T* q_rows = nullptr;
-        T *u_r = nullptr, *u_i = nullptr;
-        CAL_TRY(model_pass(3, [&](T* model_r, T* model_i, T* third) {
-          u_r = model_r, u_i = model_i, q_rows = third;
-          hipLaunchKernelGGL(coeff_solve_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, u_r, u_i, q_rows, data_r.as<T>(), data_i.as<T>(),
-                             wgts.as<T>(), gains.as<T2>(), bl_ant.as<int2>(), nbls, nfreqs, fpad);
-        }));
+        RowPlanes P;
+        CAL_TRY(coeff_planes(P));
         // a singular group keeps zeros
         HIP_TRY(hipMemsetAsync(fe_ok.p, 0, ((size_t)ngrps + 2) * sizeof(int), stream));
         HIP_TRY(hipMemsetAsync(o_cv, 0, ((size_t)ncoef + (size_t)nbls) * sizeof(double), stream));
         if (want_lev) HIP_TRY(hipMemsetAsync(fe_part.p, 0, (size_t)nbls * nslot * sizeof(double), stream));
         if (model_var) HIP_TRY(hipMemsetAsync(fe_mv.p, 0, mv_bytes, stream));
-        for (const FeChunkRange& ch : fe_chunks) {
-          hipLaunchKernelGGL(coeff_gram_kernel<T>, dim3(ch.w1 - ch.w0), dim3(256), 0, stream, tiles.as<T>(), bl_tile.as<long long>(), u_r,
-                             u_i, q_rows, fe_grp.as<CsGroup>(), fe_work.as<CsWork>() + ch.w0, fe_n.as<T>(), fe_rhs.as<T>(), ncoef, nfreqs, fpad,
+        for (const GroupChunk& ch : fe_chunks) {
+          hipLaunchKernelGGL(coeff_gram_kernel<T>, dim3(ch.w1 - ch.w0), dim3(256), 0, stream, tiles.as<T>(), bl_tile.as<long long>(), P.u_r,
+                             P.u_i, P.q, fe_grp.as<CsGroup>(), fe_work.as<CsWork>() + ch.w0, fe_n.as<T>(), fe_rhs.as<T>(), ncoef, nfreqs, fpad,
                              fold ? 1 : 0);
           hipLaunchKernelGGL(fit_error_factor_kernel<T>, dim3(ch.g1 - ch.g0), dim3(256), ch.lds, stream, fe_n.as<T>(), fe_d.as<double>(),
                              fe_grp.as<CsGroup>(), fe_order.as<int>() + ch.g0, fe_woff.as<long long>(), fe_w.as<T>(), o_cv, ok, ridge, dcnt,
                              kCsLdsDoubles);
           if (want_lev && ch.l1 > ch.l0)
             hipLaunchKernelGGL(fit_error_leverage_kernel<T>, dim3(ch.l1 - ch.l0), dim3(256), 0, stream, tiles.as<T>(), bl_tile.as<long long>(),
-                               q_rows, fe_grp.as<CsGroup>(), fe_woff.as<long long>(), ok, fe_lwork.as<FeWork>() + ch.l0, fe_w.as<T>(),
+                               P.q, fe_grp.as<CsGroup>(), fe_woff.as<long long>(), ok, fe_lwork.as<FeWork>() + ch.l0, fe_w.as<T>(),
                                model_var ? fe_mv.as<double>() : nullptr, fe_part.as<double>(), nfreqs, fpad, fold ? 1 : 0, fe_npieces);
           HIP_TRY(hipGetLastError());
         }
@@ -2561,24 +2483,12 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
       HIP_TRY(hipStreamSynchronize(stream));
     }
     if (gain_var) {
-      CAL_TRY(build_solve_lists());
+      CAL_TRY(gain_sweep_setup());
+      RowPlanes P;
+      CAL_TRY(gain_planes(P));
+      CAL_TRY(antenna_sweep(P, 1));  // of the three planes only den is wanted, and exchanged
       const size_t nant_out = (size_t)nants * nfreqs;
-      if (gs_out.bytes < 3 * nant_out * sizeof(double)) CAL_TRY(gs_out.alloc(3 * nant_out * sizeof(double)));
-      T *p_r = nullptr, *p_i = nullptr, *q_rows = nullptr;
-      CAL_TRY(model_pass(3, [&](T* model_r, T* model_i, T* third) {
-        p_r = model_r, p_i = model_i, q_rows = third;
-        hipLaunchKernelGGL(gain_solve_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, p_r, p_i, q_rows, data_r.as<T>(), data_i.as<T>(),
-                           wgts.as<T>(), bl_ant.as<int2>(), nbls, nfreqs, fpad);
-      }));
-      constexpr int V = 16 / (int)sizeof(T);
-      const int cblocks = (fpad + 64 * V - 1) / (64 * V);
-      hipLaunchKernelGGL(gain_solve_ant_kernel<T>, dim3(nants * cblocks), dim3(256), 0, stream, p_r, p_i, q_rows, gains.as<T2>(), gs_ptr.as<int>(),
-                         gs_ent.as<int2>(), nants, nfreqs, fpad, gs_out.as<double>());
-      HIP_TRY(hipGetLastError());
-      double* den = gs_out.as<double>() + 2 * nant_out;
-      // the den planes of every rank's baselines add up to the array's: ONE all-reduce of nants nfreqs doubles
-      if (comm_on()) CAL_TRY(all_reduce(den, nant_out, CAL_XCHG_F64, CAL_XCHG_SUM));
-      HIP_TRY(copy_sync(gain_var, den, nant_out * sizeof(double), hipMemcpyDeviceToHost));
+      HIP_TRY(copy_sync(gain_var, gs_out.as<double>() + 2 * nant_out, nant_out * sizeof(double), hipMemcpyDeviceToHost));
       for (size_t k = 0; k < nant_out; ++k) gain_var[k] = gain_var[k] > 0.0 ? 1.0 / gain_var[k] : 0.0;
     }
     if (counts) {
@@ -2595,52 +2505,34 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
   int solve_gain_coeffs(const cal_gain_coeff_solve_desc* d, cal_gain_coeff_solve_result* res) override {
     HIP_TRY(hipSetDevice(device));
     if (!d) return fail(CAL_ERR_INVALID, "solve_gain_coeffs: null description");
-    CAL_TRY(require_set("solve_gain_coeffs", true));
-    if (d->nsweeps < 1) return fail(CAL_ERR_INVALID, "solve_gain_coeffs: nsweeps = %d, at least one sweep", d->nsweeps);
-    CAL_TRY(check_damping_ridge("solve_gain_coeffs", d->damping, &d->ridge));
+    CAL_TRY(check_solve_call("solve_gain_coeffs", "nsweeps", d->nsweeps, "sweep", d->damping, &d->ridge));
     if (tb_on())
       return fail(CAL_ERR_UNSUPPORTED, "solve_gain_coeffs: a gain time basis is set (cal_solver_set_gain_time_basis): its coefficients couple the times of an "
                   "antenna, a joint (l, k) system this call does not solve; detach the time basis (nvec_t = 0) first");
     if (!gb_on()) return fail(CAL_ERR_STATE, "solve_gain_coeffs: no frequency gain basis is set (cal_solver_set_gain_basis); cal_solver_solve_gains solves free per-channel gains");
-    if (d->reset_gain_moments && !has_opt) return fail(CAL_ERR_STATE, "solve_gain_coeffs: reset_gain_moments without an optimizer (cal_solver_set_optimizer)");
-    CAL_TRY(build_solve_lists());
-    const size_t nant_out = (size_t)nants * nfreqs;
-    if (gs_out.bytes < 3 * nant_out * sizeof(double)) CAL_TRY(gs_out.alloc(3 * nant_out * sizeof(double)));
-    // chunks of antenna rows whose N_a (T) and factor (double, only where it does not fit LDS) stay under cs_bound; at least one row
+    CAL_TRY(check_moment_reset("solve_gain_coeffs", d->reset_gain_moments, "reset_gain_moments"));
+    CAL_TRY(gain_sweep_setup());
+    // chunks of antenna rows whose N_a (T) and factor (double, only where it does not fit LDS) stay under cs_bound (solve_plan.hpp)
     const int K = gb_nvec;
-    const bool in_lds = (long long)(K + 2) * (K | 1) <= kCsLdsDoubles;
-    const long long n_row = (long long)K * K, d_row = in_lds ? 0 : (long long)(K + 2) * K;
-    const long long row_bytes = n_row * (long long)sizeof(T) + d_row * 8;
-    const int rows_per_chunk = (int)std::max<long long>(1, std::min<long long>(nants, cs_bound / row_bytes));
-    if (gbs_n.bytes < (size_t)rows_per_chunk * n_row * sizeof(T)) CAL_TRY(gbs_n.alloc((size_t)rows_per_chunk * n_row * sizeof(T), false));
-    if (gbs_d.bytes < (size_t)rows_per_chunk * d_row * sizeof(double) || !gbs_d.p) CAL_TRY(gbs_d.alloc((size_t)rows_per_chunk * d_row * sizeof(double), false));
-    if (gbs_rhs.bytes < 2 * (size_t)nants * K * sizeof(T)) CAL_TRY(gbs_rhs.alloc(2 * (size_t)nants * K * sizeof(T)));
-    if (!gbs_cnt.p) CAL_TRY(gbs_cnt.alloc(2 * sizeof(int)));
-    const size_t chol_lds = (size_t)std::min<long long>((long long)(K + 2) * (K | 1), kCsLdsDoubles) * sizeof(double);
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&gain_basis_chol_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                kCsLdsDoubles * (int)sizeof(double)));
+    const RowChunks rc = plan_row_chunks(K, 0, 0, nfreqs, sizeof(T), cs_bound, nants);
+    CAL_TRY(gbs_n.reserve((size_t)rc.rows * rc.n_row * sizeof(T), false));
+    CAL_TRY(gbs_d.reserve((size_t)rc.rows * rc.d_row * sizeof(double), false));
+    CAL_TRY(gbs_rhs.reserve(2 * (size_t)nants * K * sizeof(T)));
+    CAL_TRY(gbs_cnt.reserve(2 * sizeof(int)));
+    CAL_TRY(allow_chol_lds(&gain_basis_chol_kernel<T>));
     const unsigned char* mask = nullptr;
     CAL_TRY(upload_slice_mask(d->slice_mask, &mask));
-    T *u_r = nullptr, *u_i = nullptr, *q_rows = nullptr;
-    CAL_TRY(model_pass(3, [&](T* model_r, T* model_i, T* third) {
-      u_r = model_r, u_i = model_i, q_rows = third;
-      hipLaunchKernelGGL(gain_solve_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, u_r, u_i, q_rows, data_r.as<T>(), data_i.as<T>(),
-                         wgts.as<T>(), bl_ant.as<int2>(), nbls, nfreqs, fpad);
-    }));
-    constexpr int V = 16 / (int)sizeof(T);
-    const int cblocks = (fpad + 64 * V - 1) / (64 * V);
+    RowPlanes P;
+    CAL_TRY(gain_planes(P));
     const int nb = (K + kNsBlock - 1) / kNsBlock, npairs = nb * (nb + 1) / 2;
     for (int k = 0; k < d->nsweeps; ++k) {
-      hipLaunchKernelGGL(gain_solve_ant_kernel<T>, dim3(nants * cblocks), dim3(256), 0, stream, u_r, u_i, q_rows, gains.as<T2>(),
-                         gs_ptr.as<int>(), gs_ent.as<int2>(), nants, nfreqs, fpad, gs_out.as<double>());
-      HIP_TRY(hipGetLastError());
-      if (comm_on()) CAL_TRY(all_reduce(gs_out.p, 3 * nant_out, CAL_XCHG_F64, CAL_XCHG_SUM));
+      CAL_TRY(antenna_sweep(P, 3));
       HIP_TRY(hipMemsetAsync(gbs_cnt.p, 0, 2 * sizeof(int), stream));
-      for (int a0 = 0; a0 < nants; a0 += rows_per_chunk) {
-        const int nr = std::min(rows_per_chunk, nants - a0);
+      for (int a0 = 0; a0 < nants; a0 += rc.rows) {
+        const int nr = std::min(rc.rows, nants - a0);
         hipLaunchKernelGGL(gain_basis_gram_kernel<T>, dim3((unsigned)nr * npairs), dim3(256), 0, stream, gb_Bt.as<T>(), gs_out.as<double>(), gains.as<T2>(),
                            gbs_n.as<T>(), gbs_rhs.as<T>(), mask, na_slice, a0, npairs, K, gb_kpad, nants, nfreqs, fpad);
-        hipLaunchKernelGGL(gain_basis_chol_kernel<T>, dim3(nr), dim3(256), chol_lds, stream, gbs_n.as<T>(), gbs_rhs.as<T>(), gbs_d.as<double>(),
+        hipLaunchKernelGGL(gain_basis_chol_kernel<T>, dim3(nr), dim3(256), rc.lds, stream, gbs_n.as<T>(), gbs_rhs.as<T>(), gbs_d.as<double>(),
                            gb_y.as<T2>(), mask, na_slice, a0, K, gb_kpad, d->damping, d->ridge, gbs_cnt.as<int>(), kCsLdsDoubles);
         HIP_TRY(hipGetLastError());
       }
@@ -2654,20 +2546,9 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
       }));
       HIP_TRY(hipGetLastError());
     }
-    int counts[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(counts, gbs_cnt.p, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
-    if (d->reset_gain_moments) {
-      // what set_optimizer leaves in the y slots, for the selected slices (runs of neighbouring slices in one call each)
-      const size_t per = (size_t)na_slice * gb_kpad * 2;  // reals per slice
-      CAL_TRY(for_selected_slice_runs(d->slice_mask, [&](int t, int t1) { return reset_moment_slots(gb_ym, gb_yv, (size_t)t * per, (size_t)(t1 - t) * per); }));
-      HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipStreamSynchronize(stream));
-    if (res) {
-      res->nsolved = counts[0];
-      res->nsingular = counts[1];
-    }
-    return CAL_OK;
+    const size_t yper = (size_t)na_slice * gb_kpad * 2;  // reals of the y slots per slice
+    return finish_solve(&gbs_cnt, res, d->reset_gain_moments, d->slice_mask,
+                        [&](int t, int t1) { return reset_moment_slots(gb_ym, gb_yv, (size_t)t * yper, (size_t)(t1 - t) * yper); });
   }
 
   // cal_solver_solve_gain_time_coeffs: solve_gain_coeffs' sequence up to the exchanged planes, then per chunk of antennas either
@@ -2677,60 +2558,32 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
   int solve_gain_time_coeffs(const cal_gain_time_solve_desc* d, cal_gain_time_solve_result* res) override {
     HIP_TRY(hipSetDevice(device));
     if (!d) return fail(CAL_ERR_INVALID, "solve_gain_time_coeffs: null description");
-    CAL_TRY(require_set("solve_gain_time_coeffs", true));
-    if (d->nsweeps < 1) return fail(CAL_ERR_INVALID, "solve_gain_time_coeffs: nsweeps = %d, at least one sweep", d->nsweeps);
-    CAL_TRY(check_damping_ridge("solve_gain_time_coeffs", d->damping, &d->ridge));
+    CAL_TRY(check_solve_call("solve_gain_time_coeffs", "nsweeps", d->nsweeps, "sweep", d->damping, &d->ridge));
     if (!tb_on())
       return fail(CAL_ERR_STATE, "solve_gain_time_coeffs: no gain time basis is set (cal_solver_set_gain_time_basis); cal_solver_solve_gain_coeffs solves the "
                   "coefficients of a frequency basis alone, cal_solver_solve_gains free per-channel gains");
-    if (d->reset_gain_moments && !has_opt) return fail(CAL_ERR_STATE, "solve_gain_time_coeffs: reset_gain_moments without an optimizer (cal_solver_set_optimizer)");
-    CAL_TRY(build_solve_lists());
-    const size_t nant_out = (size_t)nants * nfreqs;
-    if (gs_out.bytes < 3 * nant_out * sizeof(double)) CAL_TRY(gs_out.alloc(3 * nant_out * sizeof(double)));
-    const int K = gb_nvec, L = tb_L, Tn = tb_T, na = tb_na, n = L * K;
-    // chunks of antennas whose buffers stay under cs_bound; at least one antenna
-    const bool in_lds = (long long)(n + 2) * (n | 1) <= kCsLdsDoubles;
-    const bool chan_regs = L <= kTimeTile;
-    long long m_ant = 0, n_ant = 0, d_ant = 0;  // elements per antenna of gts_m, gts_n (T) and gts_d (double)
+    CAL_TRY(check_moment_reset("solve_gain_time_coeffs", d->reset_gain_moments, "reset_gain_moments"));
+    CAL_TRY(gain_sweep_setup());
+    const int K = gb_nvec, L = tb_L, Tn = tb_T, na = tb_na;
+    // chunks of antennas whose buffers stay under cs_bound (solve_plan.hpp)
+    const RowChunks rc = plan_row_chunks(K, L, Tn, nfreqs, sizeof(T), cs_bound, na);
     if (gb_on()) {
-      m_ant = (long long)Tn * K * K;
-      n_ant = (long long)n * n;
-      d_ant = in_lds ? 0 : (long long)(n + 2) * n;
-    } else {
-      d_ant = chan_regs ? 0 : (long long)nfreqs * (L * (L + 1) / 2 + 2 * L);
+      CAL_TRY(gts_m.reserve((size_t)rc.rows * rc.m_row * sizeof(T), false));
+      CAL_TRY(gts_n.reserve((size_t)rc.rows * rc.n_row * sizeof(T), false));
+      CAL_TRY(gts_rhsa.reserve(2 * (size_t)rc.rows * rc.n * sizeof(T), false));
+      CAL_TRY(gts_rhs.reserve(2 * (size_t)nants * K * sizeof(T)));
     }
-    const long long ant_bytes = std::max<long long>(1, (m_ant + n_ant) * (long long)sizeof(T) + d_ant * 8);
-    const int ants_per_chunk = (int)std::max<long long>(1, std::min<long long>(na, cs_bound / ant_bytes));
-    if (gb_on()) {
-      if (gts_m.bytes < (size_t)ants_per_chunk * m_ant * sizeof(T)) CAL_TRY(gts_m.alloc((size_t)ants_per_chunk * m_ant * sizeof(T), false));
-      if (gts_n.bytes < (size_t)ants_per_chunk * n_ant * sizeof(T)) CAL_TRY(gts_n.alloc((size_t)ants_per_chunk * n_ant * sizeof(T), false));
-      if (gts_rhsa.bytes < 2 * (size_t)ants_per_chunk * n * sizeof(T)) CAL_TRY(gts_rhsa.alloc(2 * (size_t)ants_per_chunk * n * sizeof(T), false));
-      if (gts_rhs.bytes < 2 * (size_t)nants * K * sizeof(T)) CAL_TRY(gts_rhs.alloc(2 * (size_t)nants * K * sizeof(T)));
-    }
-    if (gts_d.bytes < (size_t)ants_per_chunk * d_ant * sizeof(double) || !gts_d.p)
-      CAL_TRY(gts_d.alloc(std::max<size_t>(8, (size_t)ants_per_chunk * d_ant * sizeof(double)), false));
-    if (!gts_cnt.p) CAL_TRY(gts_cnt.alloc(2 * sizeof(int)));
-    const size_t chol_lds = (size_t)std::min<long long>((long long)(n + 2) * (n | 1), kCsLdsDoubles) * sizeof(double);
-    if (gb_on())
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&gain_time_chol_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  kCsLdsDoubles * (int)sizeof(double)));
-    T *u_r = nullptr, *u_i = nullptr, *q_rows = nullptr;
-    CAL_TRY(model_pass(3, [&](T* model_r, T* model_i, T* third) {
-      u_r = model_r, u_i = model_i, q_rows = third;
-      hipLaunchKernelGGL(gain_solve_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, u_r, u_i, q_rows, data_r.as<T>(), data_i.as<T>(),
-                         wgts.as<T>(), bl_ant.as<int2>(), nbls, nfreqs, fpad);
-    }));
-    constexpr int V = 16 / (int)sizeof(T);
-    const int cblocks = (fpad + 64 * V - 1) / (64 * V);
+    CAL_TRY(gts_d.reserve(std::max<size_t>(8, (size_t)rc.rows * rc.d_row * sizeof(double)), false));
+    CAL_TRY(gts_cnt.reserve(2 * sizeof(int)));
+    if (gb_on()) CAL_TRY(allow_chol_lds(&gain_time_chol_kernel<T>));
+    RowPlanes P;
+    CAL_TRY(gain_planes(P));
     const int nb = (K + kNsBlock - 1) / kNsBlock, npairs = nb * (nb + 1) / 2;
     for (int k = 0; k < d->nsweeps; ++k) {
-      hipLaunchKernelGGL(gain_solve_ant_kernel<T>, dim3(nants * cblocks), dim3(256), 0, stream, u_r, u_i, q_rows, gains.as<T2>(),
-                         gs_ptr.as<int>(), gs_ent.as<int2>(), nants, nfreqs, fpad, gs_out.as<double>());
-      HIP_TRY(hipGetLastError());
-      if (comm_on()) CAL_TRY(all_reduce(gs_out.p, 3 * nant_out, CAL_XCHG_F64, CAL_XCHG_SUM));
+      CAL_TRY(antenna_sweep(P, 3));
       HIP_TRY(hipMemsetAsync(gts_cnt.p, 0, 2 * sizeof(int), stream));
-      for (int a0 = 0; a0 < na; a0 += ants_per_chunk) {
-        const int ca = std::min(ants_per_chunk, na - a0);
+      for (int a0 = 0; a0 < na; a0 += rc.rows) {
+        const int ca = std::min(rc.rows, na - a0);
         if (gb_on()) {
           if (ca == na) {  // the rows of every time lie side by side: one launch, M [t][a][K][K]
             hipLaunchKernelGGL(gain_basis_gram_kernel<T>, dim3((unsigned)nants * npairs), dim3(256), 0, stream, gb_Bt.as<T>(), gs_out.as<double>(),
@@ -2744,33 +2597,21 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
           }
           hipLaunchKernelGGL(gain_time_kron_kernel<T>, dim3((unsigned)ca * L, (L + kTimeTile - 1) / kTimeTile), dim3(256), 0, stream, gts_m.as<T>(),
                              gts_rhs.as<T>(), tb_B.as<T>(), gts_n.as<T>(), gts_rhsa.as<T>(), a0, ca, na, Tn, L, tb_lpad, K);
-          hipLaunchKernelGGL(gain_time_chol_kernel<T>, dim3(ca), dim3(256), chol_lds, stream, gts_n.as<T>(), gts_rhsa.as<T>(), gts_d.as<double>(),
+          hipLaunchKernelGGL(gain_time_chol_kernel<T>, dim3(ca), dim3(256), rc.lds, stream, gts_n.as<T>(), gts_rhsa.as<T>(), gts_d.as<double>(),
                              gb_y.as<T2>(), a0, L, K, gb_kpad, d->damping, d->ridge, gts_cnt.as<int>(), kCsLdsDoubles);
         } else {
           const unsigned blocks = (unsigned)(((long long)ca * nfreqs + 255) / 256);
-          if (chan_regs)
-            hipLaunchKernelGGL((gain_time_chan_kernel<T, kTimeTile>), dim3(blocks), dim3(256), 0, stream, gs_out.as<double>(), gains.as<T2>(), tb_B.as<T>(),
-                               gb_y.as<T2>(), gts_d.as<double>(), a0, ca, na, Tn, L, tb_lpad, nfreqs, fpad, d->damping, d->ridge, gts_cnt.as<int>());
-          else
-            hipLaunchKernelGGL((gain_time_chan_kernel<T, 0>), dim3(blocks), dim3(256), 0, stream, gs_out.as<double>(), gains.as<T2>(), tb_B.as<T>(),
-                               gb_y.as<T2>(), gts_d.as<double>(), a0, ca, na, Tn, L, tb_lpad, nfreqs, fpad, d->damping, d->ridge, gts_cnt.as<int>());
+          auto* chan = L <= kTimeTile ? gain_time_chan_kernel<T, kTimeTile> : gain_time_chan_kernel<T, 0>;  // the channel systems in registers, or in gts_d
+          hipLaunchKernelGGL(chan, dim3(blocks), dim3(256), 0, stream, gs_out.as<double>(), gains.as<T2>(), tb_B.as<T>(), gb_y.as<T2>(),
+                             gts_d.as<double>(), a0, ca, na, Tn, L, tb_lpad, nfreqs, fpad, d->damping, d->ridge, gts_cnt.as<int>());
         }
         HIP_TRY(hipGetLastError());
       }
       CAL_TRY(enqueue_expand(gb_y.as<T2>(), gains.as<T2>()));  // gains = g0 + Bt (x) (B) y, behind the last chunk
     }
-    int counts[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(counts, gts_cnt.p, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
-    if (d->reset_gain_moments) {
-      CAL_TRY(reset_moment_slots(gb_ym, gb_yv, 0, 2 * (size_t)y_rows() * (size_t)y_row()));  // what set_optimizer leaves in the y slots
-      HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipStreamSynchronize(stream));
-    if (res) {
-      res->nsolved = counts[0];
-      res->nsingular = counts[1];
-    }
-    return CAL_OK;
+    // (the times of an antenna share its coefficients: no slice mask, every y slot)
+    return finish_solve(&gts_cnt, res, d->reset_gain_moments, nullptr,
+                        [&](int, int) { return reset_moment_slots(gb_ym, gb_yv, 0, 2 * (size_t)y_rows() * (size_t)y_row()); });
   }
 
   int init_coeffs(const void* sr, const void* si) override {
@@ -2778,7 +2619,7 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     if (!has_problem || !has_data) return fail(CAL_ERR_STATE, "init_coeffs: problem and data (weights) must be set");
     if (!sr || !si) return fail(CAL_ERR_INVALID, "init_coeffs: null source");
     const size_t rowbytes = (size_t)nbls * fpad * sizeof(T);
-    if (model_buf.bytes < 2 * rowbytes) CAL_TRY(model_buf.alloc(2 * rowbytes));
+    CAL_TRY(model_buf.reserve(2 * rowbytes));
     T* s_r = model_buf.as<T>();
     T* s_i = s_r + (size_t)nbls * fpad;
     CAL_TRY(upload_rows(sr, s_r, nbls, 1, 0));
@@ -2837,15 +2678,8 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
   }
   int memory_bytes(int64_t* b) override {
     if (!b) return fail(CAL_ERR_INVALID, "memory_bytes: null");
-    const DevBuf* all[] = {&tiles, &bl_tile, &bl_ant, &items, &ant_ptr, &ant_ent, &coef_grp, &grp_coff, &grp_item_ptr, &item_goff,
-                           &data_r, &data_i, &wgts, &gains, &gains_alt, &gains_m, &gains_v, &gains_snap, &coef, &coef_m, &coef_v, &coef_snap,
-                           &q0, &q1, &comm, &scal, &gcp0, &gcp1, &gc0, &gc1, &part, &state, &losses, &scratch, &model_buf, &fq_out, &fq_gains, &rw_w0, &rw_out, &gs_out, &gs_ptr, &gs_ent, &gs_mask, &cs_grp, &cs_order, &cs_work, &cs_n, &cs_d, &cs_rhs, &cs_cnt, &fe_grp, &fe_order, &fe_work, &fe_woff, &fe_lwork, &fe_n, &fe_d, &fe_w, &fe_rhs, &fe_ok, &fe_part, &fe_out, &fe_mv, &gbs_n, &gbs_d, &gbs_rhs, &gbs_cnt, &gts_m, &gts_n, &gts_rhsa, &gts_d, &gts_rhs, &gts_cnt,
-                           &mf_ops, &mf_panels, &mf_map, &members, &heads, &lamb_vars, &lamb_cvar_ptr, &lamb_partial, &lamb_ratio, &lamb_glob, &lamb_slot, &slice_coff, &slice_ipart_ptr, &slice_ipart_idx,
-                           &slice_ppart_ptr, &slice_ppart_idx, &slice_cblk, &gb_B, &gb_Bt, &gb_g0, &gb_y, &gb_ym, &gb_yv, &gb_ysnap, &gb_proj, &tb_B, &tb_Bt, &tb_z, &tb_pf,
-                           &gn_s, &gn_g0, &gn_save, &gn_x, &gn_res, &gn_ns, &gn_D, &gn_m, &gn_sd, &gn_rows, &gn_part, &gn_scal, &gn_lam, &gn_grp, &gn_rowptr};
-    int64_t n = 0;
-    for (auto* d : all) n += (int64_t)d->bytes;
-    *b = n;
+    *b = 0;
+    for (const DevBuf* d : bufs) *b += (int64_t)d->bytes;  // every DevBuf member (DevBufRegistry)
     return CAL_OK;
   }
   int comm_init(const void* id, int rk, int nr) override {
@@ -2884,15 +2718,7 @@ struct SolverT final : cal_solver, PlanScalars {  // PlanScalars (problem_plan.h
     HIP_TRY(hipSetDevice(device));
     if (!nranks_seen) return fail(CAL_ERR_INVALID, "comm_size: null");
     *nranks_seen = 1;
-    if (!comm_on()) return CAL_OK;
-    if (agree_buf.bytes < sizeof(int)) CAL_TRY(agree_buf.alloc(sizeof(int)));
-    int one = 1;
-    HIP_TRY(hipMemcpyAsync(agree_buf.p, &one, sizeof(int), hipMemcpyHostToDevice, stream));
-    CAL_TRY(all_reduce(agree_buf.p, 1, CAL_XCHG_I32, CAL_XCHG_SUM));
-    HIP_TRY(hipMemcpyAsync(&one, agree_buf.p, sizeof(int), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    *nranks_seen = one;
-    return CAL_OK;
+    return agree_ints(nranks_seen, 1, CAL_XCHG_SUM);  // (no communicator: stays 1)
   }
   int joined(int rk, int nr) {
     nranks = nr;
@@ -2941,9 +2767,9 @@ int weighted_square_error(int64_t n, const void* const src[5], double* out) {
 // cal_debug_plan: the host planner's arrays as bytes
 namespace {
 template <typename X>
-int plan_bytes(const std::vector<X>& v, void* out, int64_t cap, int64_t* bytes) {
+int plan_bytes(const std::vector<X>& v, void* out, int64_t cap, int64_t* bytes, const char* who = "cal_debug_plan") {
   *bytes = (int64_t)(v.size() * sizeof(X));
-  if (*bytes > cap) return fail(CAL_ERR_INVALID, "cal_debug_plan: the array has %lld bytes, the buffer %lld", (long long)*bytes, (long long)cap);
+  if (*bytes > cap) return fail(CAL_ERR_INVALID, "%s: the array has %lld bytes, the buffer %lld", who, (long long)*bytes, (long long)cap);
   if (*bytes) memcpy(out, v.data(), (size_t)*bytes);
   return CAL_OK;
 }
@@ -2991,6 +2817,41 @@ int debug_plan(const cal_problem_desc* d, int what, void* out, int64_t cap, int6
   }
   return fail(CAL_ERR_INVALID, "cal_debug_plan: what = %d", what);
 }
+// cal_debug_solve_plan: the arrays of solve_plan.hpp as bytes
+template <typename T>
+int debug_solve_plan(const cal_problem_desc* d, int64_t bound, int what, void* out, int64_t cap, int64_t* bytes) {
+  const char* who = "cal_debug_solve_plan";
+  auto give = [&](const auto& v) { return plan_bytes(v, out, cap, bytes, who); };
+  ProblemPlan<T> p;
+  CAL_TRY(plan_problem(d, p));
+  if (what == 20 || what == 21) {
+    std::vector<int> ptr;
+    std::vector<int2> ent;
+    antenna_lists(p.nants, p.bl_ant, true, ptr, ent);
+    return what == 20 ? give(ptr) : give(ent);
+  }
+  if (what == 30) {
+    const int64_t* in = static_cast<const int64_t*>(out);
+    if (cap < 24 || in[0] < 0 || in[1] < 0 || in[0] + in[1] == 0 || (in[1] > 0 && (in[2] < 1 || p.nants % in[2] != 0)))
+      return fail(CAL_ERR_INVALID, "%s: what = 30 takes K, L, T (K + L > 0; T divides nants) in the first 24 bytes of out", who);
+    const int K = (int)in[0], L = (int)in[1], Tn = (int)in[2];
+    const RowChunks r = plan_row_chunks(K, L, Tn, p.nfreqs, sizeof(T), bound, L > 0 ? p.nants / Tn : p.nants);
+    return give(std::vector<int64_t>{r.rows, r.in_lds, (int64_t)r.lds, r.n, r.m_row, r.n_row, r.d_row});
+  }
+  if (what < 0 || what >= 20 || what % 10 > 6) return fail(CAL_ERR_INVALID, "%s: what = %d", who, what);
+  const bool fe = what >= 10;
+  GroupPlan P = plan_group_chunks(p.cs_grp, sizeof(T), bound, fe ? fit_error_extra(p.cs_grp) : std::vector<long long>{});
+  if (fe) plan_leverage_work(P, p.cs_grp, p.bl_tile, p.fold ? p.nfreqs / 2 : p.fpad);
+  switch (what % 10) {
+    case 0: return give(std::vector<int64_t>{P.n_max, P.d_max, P.x_max, P.npieces, (int64_t)P.chunks.size()});
+    case 1: return give(p.cs_grp);
+    case 2: return give(P.order);
+    case 3: return give(P.work);
+    case 4: return give(P.chunks);
+    case 5: return give(P.xoff);
+  }
+  return give(P.lwork);
+}
 }  // namespace
 
 extern "C" {
@@ -3017,6 +2878,13 @@ int cal_basis_foldable(int dtype, const void* block, int32_t nfreqs, int32_t nve
 int cal_debug_plan(int dtype, const cal_problem_desc* d, int what, void* out, int64_t cap_bytes, int64_t* bytes) {
   if (!out || !bytes || cap_bytes < 0 || (dtype != CAL_F32 && dtype != CAL_F64)) return fail(CAL_ERR_INVALID, "cal_debug_plan: bad argument");
   return dtype == CAL_F32 ? debug_plan<float>(d, what, out, cap_bytes, bytes) : debug_plan<double>(d, what, out, cap_bytes, bytes);
+}
+
+int cal_debug_solve_plan(int dtype, const cal_problem_desc* d, int64_t scratch_bytes, int what, void* out, int64_t cap_bytes, int64_t* bytes) {
+  if (!out || !bytes || cap_bytes < 0 || (dtype != CAL_F32 && dtype != CAL_F64)) return fail(CAL_ERR_INVALID, "cal_debug_solve_plan: bad argument");
+  if (scratch_bytes < 0) return fail(CAL_ERR_INVALID, "cal_debug_solve_plan: negative bound");
+  const int64_t bound = scratch_bytes == 0 ? kCsScratchDefault : scratch_bytes;  // as in set_coeff_solve_scratch
+  return dtype == CAL_F32 ? debug_solve_plan<float>(d, bound, what, out, cap_bytes, bytes) : debug_solve_plan<double>(d, bound, what, out, cap_bytes, bytes);
 }
 
 int cal_device_count(int* count) {

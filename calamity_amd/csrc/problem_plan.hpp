@@ -146,6 +146,27 @@ inline std::vector<int> deal_over_xcds(const std::vector<int>& group, int ngroup
   return slots;
 }
 
+// Per-antenna CSR of (baseline, role, other antenna), in baseline order: a fixed summation order.  skip_autos: without the
+// autocorrelation rows (the lists of gain_solve_ant_kernel; solve_plan.hpp).  ent is never empty (one spare entry).
+inline void antenna_lists(int nants, const std::vector<int2>& bl_ant, bool skip_autos, std::vector<int>& ptr, std::vector<int2>& ent) {
+  const int nbls = (int)bl_ant.size();
+  auto skip = [&](int b) { return skip_autos && bl_ant[b].x == bl_ant[b].y; };
+  ptr.assign(nants + 1, 0);
+  for (int b = 0; b < nbls; ++b) {
+    if (skip(b)) continue;
+    ptr[bl_ant[b].x + 1]++;
+    ptr[bl_ant[b].y + 1]++;
+  }
+  for (int a = 0; a < nants; ++a) ptr[a + 1] += ptr[a];
+  ent.assign((size_t)std::max(1, ptr[nants]), int2{});
+  std::vector<int> fill(ptr.begin(), ptr.end() - 1);
+  for (int b = 0; b < nbls; ++b) {
+    if (skip(b)) continue;
+    ent[fill[bl_ant[b].x]++] = make_int2(b * 2 + 0, bl_ant[b].y);
+    ent[fill[bl_ant[b].y]++] = make_int2(b * 2 + 1, bl_ant[b].x);
+  }
+}
+
 // What set-up decides about a problem and the solver keeps (SolverT derives from it; a communicator may still change mf_ok,
 // steps_per_sync and lamb_ok: agree_problem).
 struct PlanScalars {
@@ -804,21 +825,6 @@ struct ProblemPlan : PlanScalars {
     }
   }
 
-  // ---- per-antenna CSR of (baseline, role, other antenna), in baseline order: a fixed summation order
-  void antenna_csr(const cal_problem_desc* d) {
-    ant_ptr.assign(nants + 1, 0);
-    for (int b = 0; b < nbls; ++b) {
-      ant_ptr[d->bl_ant0[b] + 1]++;
-      ant_ptr[d->bl_ant1[b] + 1]++;
-    }
-    for (int a = 0; a < nants; ++a) ant_ptr[a + 1] += ant_ptr[a];
-    ant_ent.resize(2 * (size_t)nbls);
-    std::vector<int> fill(ant_ptr.begin(), ant_ptr.end() - 1);
-    for (int b = 0; b < nbls; ++b) {
-      ant_ent[fill[d->bl_ant0[b]]++] = make_int2(b * 2 + 0, d->bl_ant1[b]);
-      ant_ent[fill[d->bl_ant1[b]]++] = make_int2(b * 2 + 1, d->bl_ant0[b]);
-    }
-  }
 };
 
 // The checks run in this order: the first failure is the one reported (fail(): cal_last_error).
@@ -833,7 +839,7 @@ int plan_problem(const cal_problem_desc* d, ProblemPlan<T>& p) {
   p.dense_panels(d);
   p.runs_and_items(d);
   p.head_items(d);
-  p.antenna_csr(d);
+  antenna_lists(p.nants, p.bl_ant, false, p.ant_ptr, p.ant_ent);
   return CAL_OK;
 }
 

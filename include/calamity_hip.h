@@ -203,6 +203,17 @@ int cal_basis_foldable(int dtype, const void* block, int32_t nfreqs, int32_t nve
  * 24 the panel map, 25 byte offsets of the blocks' packed operands, 26 CsGroup per group, 27 / 28 the antenna CSR (ptr; int2 entries).
  * Records are the structs of the kernel headers; int32 where nothing else is said. */
 int cal_debug_plan(int dtype, const cal_problem_desc* d, int what, void* out, int64_t cap_bytes, int64_t* bytes);
+/* Host only, like cal_debug_plan: what the closed-form calls plan at their first call (csrc/solve_plan.hpp) for the problem `d`, a solver of
+ * `dtype` and the bound of cal_solver_set_coeff_solve_scratch (0: the default; negative: CAL_ERR_INVALID).  For tests
+ * (tests/test_solve_plan_host.py).  what = 0 .. 6: the plan of cal_solver_solve_coeffs, 10 .. 16: of cal_solver_fit_errors --
+ *   + 0: int64 n_max, d_max, x_max (elements of the N, factor and W scratch), npieces, number of chunks; + 1: CsGroup per group with the
+ *   plan's offsets; + 2: order; + 3: Gram work (CsWork); + 4: chunks (int32 g0, g1, w0, w1, l0, l1, then the dynamic LDS as int64);
+ *   + 5: W offsets (int64 per group); + 6: leverage work (FeWork).  The last two and npieces are empty / 0 for solve_coeffs.
+ * 20 / 21: the antenna lists without autocorrelations (ptr; int2 entries).
+ * 30: the row chunks of cal_solver_solve_gain_coeffs (L = 0) and cal_solver_solve_gain_time_coeffs.  On entry `out` holds int64 K, L, T
+ *   (vectors of the frequency basis, of the time basis, times; nants must be a multiple of T); on return int64 rows per chunk, in_lds,
+ *   the Cholesky launch's LDS bytes, unknowns per row, elements per row of M and N (dtype) and of the double scratch. */
+int cal_debug_solve_plan(int dtype, const cal_problem_desc* d, int64_t scratch_bytes, int what, void* out, int64_t cap_bytes, int64_t* bytes);
 int cal_device_info(int device, char* name, size_t name_len, int64_t* total_mem_bytes, int32_t* compute_units);
 /* Measured streaming peaks of the device (no reference counterpart; BASELINE.md section 3 asks for the roofline against a
  * stream kernel measured on the box next to the nominal 8 TB/s): a read-only sweep (16-byte non-temporal loads, the

@@ -161,3 +161,53 @@ def plan(lib, prob, dtype, layout, kernel_path, whats=None):
         out[name] = buf[: n.value].view(dt).copy()
     del keep
     return out
+
+
+# ---- the plans of the closed-form calls (calamity_amd/csrc/solve_plan.hpp; cal_debug_solve_plan) ---------------------------------
+SOLVE_CASES = ("groups_stream_f32", "groups_shared_f64", "stream_fold_f32", "dense_split2_f32", "dense_f64")
+# what -> (name, numpy dtype of the raw bytes); the fit-error plan's arrays are what + 10, named "fe_" instead of "cs_"
+SOLVE_ARRAYS = {0: ("cs_scalars", np.int64), 1: ("cs_grp", np.int32), 2: ("cs_order", np.int32), 3: ("cs_work", np.int32),
+                4: ("cs_chunks", np.int32), 5: ("cs_woff", np.int64), 6: ("cs_lwork", np.int32)}
+SOLVE_ARRAYS.update({10 + w: ("fe_" + nm[3:], dt) for w, (nm, dt) in list(SOLVE_ARRAYS.items())})
+SOLVE_LISTS = {20: ("gs_ptr", np.int32), 21: ("gs_ent", np.int32)}  # independent of the bound
+SOLVE_ARRAYS.update(SOLVE_LISTS)
+SOLVE_SCALARS = "n_max d_max x_max npieces nchunks".split()
+WHAT_ROW_CHUNKS = 30
+ROW_SCALARS = "rows in_lds lds n m_row n_row d_row".split()
+CS_DEFAULT_BOUND = 256 << 20  # kCsScratchDefault
+CS_LDS_DOUBLES = 16384        # kCsLdsDoubles
+TIME_TILE = 8                 # kTimeTile
+
+
+def solve_bounds(nvec, itemsize):
+    """{tag: scratch bound in bytes} for groups of ``nvec`` vectors: the default (0: one chunk), 1 byte (every group its own chunk),
+    and what holds the two heaviest groups but not a third -- by solve_coeffs' count (N in the dtype, the factor in double) and by
+    fit_errors' (W, padded to whole 16 x 16 tiles, on top)."""
+    n = np.sort(np.asarray(nvec, np.int64))[::-1][:2]
+    cs = int((n * n * itemsize + (n + 2) * n * 8).sum())
+    pad = (n + 15) // 16 * 16
+    return {"default": 0, "one": 1, "two_cs": cs, "two_fe": cs + int((pad * pad * itemsize).sum())}
+
+
+def solve_plan(call, prob, dtype, layout, kernel_path, bound, whats, row_shape=None):
+    """{name: array} of arrays ``whats`` at scratch bound ``bound``.  ``call(dtype code, desc pointer, bound, what, out pointer, capacity,
+    bytes pointer)`` is cal_debug_solve_plan (the recording of tests/golden/solve_plan/ passes the parent's loops instead).
+    ``row_shape``: (K, L, T) for WHAT_ROW_CHUNKS."""
+    import ctypes as C
+
+    from calamity_amd import _lib
+    from calamity_amd.solver import problem_desc
+
+    d, keep = problem_desc(prob, dtype, layout, kernel_path)
+    code = _lib.CAL_F32 if np.dtype(dtype) == np.float32 else _lib.CAL_F64
+    buf = np.empty(1 << 20, np.uint8)
+    out = {}
+    for what in whats:
+        name, dt = ("row_chunks", np.int64) if what == WHAT_ROW_CHUNKS else SOLVE_ARRAYS[what]
+        if what == WHAT_ROW_CHUNKS:
+            buf[:24].view(np.int64)[:] = row_shape
+        n = C.c_int64(0)
+        _lib.check(call(code, C.byref(d), bound, what, buf.ctypes.data_as(C.c_void_p), buf.nbytes, C.byref(n)))
+        out[name] = buf[: n.value].view(dt).copy()
+    del keep
+    return out

@@ -1,10 +1,11 @@
-// plan_sanitize.hip -- the set-up planner (calamity_amd/csrc/problem_plan.hpp) under the host sanitizers, with no device and no
-// interpreter: four problems built in code (folded STREAM, heads of baselines that share tiles, forced dense, multi-baseline runs),
-// planned for fp32 and fp64.  Exits non-zero on a planner error; the sanitizers abort on a finding.
+// plan_sanitize.hip -- the set-up planner (calamity_amd/csrc/problem_plan.hpp) and the planner of the closed-form calls
+// (calamity_amd/csrc/solve_plan.hpp) under the host sanitizers, with no device and no interpreter: four problems built in code (folded
+// STREAM, heads of baselines that share tiles, forced dense, multi-baseline runs), planned for fp32 and fp64; the closed-form plans at
+// the default scratch bound and at a bound of 1 byte.  Exits non-zero on a planner error; the sanitizers abort on a finding.
 //
 //   hipcc --offload-arch=gfx950 -std=c++17 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
 //         -o plan_sanitize tools/plan_sanitize.hip && ./plan_sanitize
-#include "../calamity_amd/csrc/problem_plan.hpp"
+#include "../calamity_amd/csrc/solve_plan.hpp"
 
 #include <cstdint>
 
@@ -66,7 +67,28 @@ int run(const Case& c) {
   printf("%-12s %d-byte reals: fpad %d, %d items (%d simple, %d plain), fold %d, gc_direct %d, %d runs, %d heads (%d matrix-core, grid %d), dense %d: %d panels, grid %d\n",
          c.name, (int)sizeof(T), p.fpad, p.nitems, p.nitems_simple, p.nitems_plain, (int)p.fold, (int)p.gc_direct, (int)p.runs.size(), p.nheads, p.nheads_mfma,
          p.mm_grid, (int)p.mf_ok, p.mf_npanels, p.mf_grid);
-  return 0;
+  // the plans of the closed-form calls: one chunk at the default bound; at 1 byte every group, every row a chunk of its own
+  std::vector<int> ptr;
+  std::vector<int2> ent;
+  antenna_lists(p.nants, p.bl_ant, true, ptr, ent);
+  int bad = ptr[p.nants] > 2 * p.nbls || ent.empty();
+  for (const int64_t bound : {kCsScratchDefault, (int64_t)1}) {
+    std::vector<CsGroup> grp = p.cs_grp;
+    const GroupPlan cs = plan_group_chunks(grp, sizeof(T), bound, {});
+    GroupPlan fe = plan_group_chunks(grp, sizeof(T), bound, fit_error_extra(grp));
+    plan_leverage_work(fe, grp, p.bl_tile, p.fold ? p.nfreqs / 2 : p.fpad);
+    const RowChunks rf = plan_row_chunks(150, 0, 0, p.nfreqs, sizeof(T), bound, p.nants);
+    const RowChunks rt = plan_row_chunks(20, 9, p.nslices, p.nfreqs, sizeof(T), bound, p.na_slice);
+    const RowChunks rc = plan_row_chunks(0, 9, p.nslices, p.nfreqs, sizeof(T), bound, p.na_slice);
+    const size_t want = bound == 1 ? (size_t)p.ngrps : 1;
+    bad += cs.chunks.size() != want || fe.chunks.size() != want || cs.chunks.back().g1 != p.ngrps || fe.chunks.back().g1 != p.ngrps ||
+           fe.chunks.back().l1 != (int)fe.lwork.size() || cs.chunks.back().w1 != (int)cs.work.size() || rf.rows < 1 || rt.rows < 1 || rc.rows < 1;
+    printf("%-12s   bound %lld: %zu / %zu chunks, %zu Gram blocks, %zu leverage items in %d pieces, scratch %lld + %lld + %lld elements; rows per chunk %d, %d, %d\n",
+           c.name, (long long)bound, cs.chunks.size(), fe.chunks.size(), cs.work.size(), fe.lwork.size(), fe.npieces, fe.n_max, fe.d_max, fe.x_max, rf.rows,
+           rt.rows, rc.rows);
+  }
+  if (bad) fprintf(stderr, "%s (%d-byte reals): the closed-form plans are inconsistent\n", c.name, (int)sizeof(T));
+  return bad ? 1 : 0;
 }
 
 std::vector<int> cycle(int n, int m) {
