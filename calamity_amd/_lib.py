@@ -156,6 +156,7 @@ SYMBOLS = {
     "cal_basis_foldable": (C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "cal_debug_plan": (C.c_int, [C.c_int, C.POINTER(ProblemDesc), C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "cal_debug_solve_plan": (C.c_int, [C.c_int, C.POINTER(ProblemDesc), C.c_int64, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "cal_debug_step_shape": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "cal_device_info": (C.c_int, [C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "cal_device_stream_peak": (C.c_int, [C.c_int, C.c_size_t, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "cal_device_busy_clock_mhz": (C.c_int, [C.c_int, C.POINTER(C.c_double)]),

@@ -34,6 +34,7 @@
 #include "gain_time_solve_kernels.hpp"
 #include "gauss_newton_kernels.hpp"
 #include "solve_plan.hpp"  // (and problem_plan.hpp)
+#include "step_plan.hpp"
 #include <cstdlib>
 #include <dlfcn.h>
 #include <type_traits>
@@ -274,9 +275,8 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
   // dense (MFMA) path of the SHARED layout, fp32, one baseline per fitting group
   DevBuf mf_ops, mf_panels;                    // mf_ops: every basis block's packed MFMA operands (see mfma_pack_kernel / mfma_pack64_kernel)
   DevBuf mf_map;                               // [mf_grid] workgroup -> panel (-1: empty slot): XCD-affine dispatch of the dense launch
-  // small problems: a train step is two launches (fused pass, step_tail_kernel), replayed kGraphSteps at a time from a hipGraph
+  // small problems: a train step is two launches (fused pass, step_tail_kernel), replayed kGraphSteps at a time from a hipGraph (step_plan.hpp)
   int launch_mode = CAL_LAUNCH_AUTO;
-  static constexpr int kGraphSteps = 16;       // even: the double-buffered loop state and gains end a replay where they began
   hipGraphExec_t graph_exec = nullptr;
   struct GraphKey {
     int optimizer, freeze, reg, losses_cap, st_par, tail, nsteps;
@@ -902,191 +902,205 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
   }
 
   // ---- one pass of the hot path -------------------------------------------------------------------------------
-  FusedArgs<T> fused_args() {
-    FusedArgs<T> a{};
-    a.tiles = tiles.as<T>();
-    a.bl_tile = bl_tile.as<long long>();
-    a.bl_ant = bl_ant.as<int2>();
+  template <typename A> A pass_args() {  // what the argument structs of the general and of the dense kernels share
+    A a{};
     a.data_r = data_r.as<T>();
     a.data_i = data_i.as<T>();
     a.wgts = wgts.as<T>();
     a.gains = gains.as<T2>();
     a.c_r = coef.as<T>();
     a.c_i = coef.as<T>() + ncoef;
-    a.items = items.as<Item>();
     a.q0 = q0.as<T2>();
+    a.part = part.as<double>();
+    a.state = st_cur();
+    a.nslices = nslices;
+    a.fpad = fpad;
+    a.nbls = nbls;
+    return a;
+  }
+  FusedArgs<T> fused_args() {
+    FusedArgs<T> a = pass_args<FusedArgs<T>>();
+    a.tiles = tiles.as<T>();
+    a.bl_tile = bl_tile.as<long long>();
+    a.bl_ant = bl_ant.as<int2>();
+    a.items = items.as<Item>();
     a.q1 = q1.as<T2>();
     a.gcp0_r = gcp0.as<T>();
     a.gcp0_i = gcp0.as<T>() + gcp_len;
     a.gcp1_r = gcp1.as<T>();
     a.gcp1_i = gcp1.p ? gcp1.as<T>() + gcp_len : nullptr;
-    a.part = part.as<double>();
-    a.model_r = nullptr;
-    a.model_i = nullptr;
-    a.state = st_cur();
-    a.nslices = nslices;
-    a.fpad = fpad;
-    a.nbls = nbls;
     a.runs = runs.as<int2>();
-    a.item_base = 0;
     a.stream_once = layout == CAL_LAYOUT_STREAM ? 1 : 0;
     a.members = members.as<Member>();
     a.heads = nheads > 0 ? heads.as<int>() : nullptr;
     a.nfreqs = nfreqs;
     return a;
   }
+  // ... pointed at the first two planes of model_buf ([planes][nbls][fpad]): model(), model_pass()
+  FusedArgs<T> model_args() {
+    FusedArgs<T> a = fused_args();
+    a.model_r = model_buf.as<T>();
+    a.model_i = model_buf.as<T>() + (size_t)nbls * fpad;
+    return a;
+  }
+  using DenseArgs = typename std::conditional<std::is_same<T, float>::value, MfmaArgs, Dense64Args>::type;
+  DenseArgs dense_args() {
+    DenseArgs m = pass_args<DenseArgs>();
+    m.ops = mf_ops.as<T>();
+    m.panels = mf_panels.as<PanelItem>();
+    m.gc_r = grad_c0();
+    m.gc_i = grad_c0() + ncoef;
+    m.slot_map = mf_map.as<int>();
+    return m;
+  }
+  // The shape of a pass or train step (step_plan.hpp) for the solver as it stands.  nsteps: of the run, for the replay rule alone.
+  StepShape step_shape(PassAsk ask, int nsteps = 0) const {
+    return plan_step(StepInputs{mf_ok, reg == CAL_REG_SUM, reg_prepass, gc_direct, comm_on(), yb_on(), 2LL * nants * fpad + 2LL * ncoef <= (1LL << 20), launch_mode,
+                                opt.optimizer == CAL_OPT_LAMB, ask, timing, nsteps >= kGraphMinSteps});
+  }
+
+  // ---- one launcher per kernel ---------------------------------------------------------------------------------
+  using FusedFn = void (*)(const FusedArgs<T>);
+  static FusedFn pick(bool with_reg, FusedFn reg, FusedFn plain) { return with_reg ? reg : plain; }
+  // fused_basis_kernel<T, MODE, REG, L, FOLD> (folded tiles: every item of the problem is one, set_problem)
+  template <int MODE, int L> FusedFn basis_kernel(bool with_reg) const {
+    return fold ? pick(with_reg, fused_basis_kernel<T, MODE, true, L, true>, fused_basis_kernel<T, MODE, false, L, true>)
+                : pick(with_reg, fused_basis_kernel<T, MODE, true, L, false>, fused_basis_kernel<T, MODE, false, L, false>);
+  }
   // LDS buffer of gbar_G rows (MODE_GRAD); the narrowest tiles have the longest offset table
   static constexpr size_t kQLdsMax1 = TileCfg<T, FbSet<T>::fb_min>::q_lds_bytes(false);
   static constexpr size_t kQLdsMax2 = TileCfg<T, FbSet<T>::fb_min>::q_lds_bytes(true);
-  template <int MODE> void launch_fused(const FusedArgs<T>& a0, bool with_reg) {
-    FusedArgs<T> a = a0;
-    // the passes with a multi-slice form leave the covered items to it (fused_basis_kernel would return at once for each of them)
-    const int nsimple = ((MODE == MODE_LOSS || MODE == MODE_GRAD) && nheads > 0) ? nitems_plain : nitems_simple;
+  template <int MODE> void launch_fused(FusedArgs<T> a, bool with_reg) {  // a.item_base = 0, as fused_args leaves it
+    constexpr bool kPass = MODE == MODE_LOSS || MODE == MODE_GRAD;  // the passes with a multi-slice form and a narrow instance
+    // they leave the covered items to the multi-slice form (fused_basis_kernel would return at once for each of them)
+    const int nsimple = (kPass && nheads > 0) ? nitems_plain : nitems_simple;
     if (nsimple > 0) {
-      a.item_base = 0;
-      constexpr bool kHasSmall = MODE == MODE_LOSS || MODE == MODE_GRAD;
-      if (fold) {
-        // folded tiles: every item of the problem is one (set_problem)
-        if (kHasSmall && small_loads) {
-          if constexpr (kHasSmall) {
-            if (with_reg)
-              hipLaunchKernelGGL((fused_basis_kernel<T, MODE, true, kSmallLoads, true>), dim3(nsimple), dim3(kThreads), lds_bytes + (MODE == MODE_GRAD ? kQLdsMax2 : 0), stream, a);
-            else
-              hipLaunchKernelGGL((fused_basis_kernel<T, MODE, false, kSmallLoads, true>), dim3(nsimple), dim3(kThreads), lds_bytes + (MODE == MODE_GRAD ? kQLdsMax1 : 0), stream, a);
-          }
-        } else if (with_reg)
-          hipLaunchKernelGGL((fused_basis_kernel<T, MODE, true, kMaxLoads, true>), dim3(nsimple), dim3(kThreads), lds_bytes + (MODE == MODE_GRAD ? kQLdsMax2 : 0), stream, a);
-        else
-          hipLaunchKernelGGL((fused_basis_kernel<T, MODE, false, kMaxLoads, true>), dim3(nsimple), dim3(kThreads), lds_bytes + (MODE == MODE_GRAD ? kQLdsMax1 : 0), stream, a);
-      } else if (kHasSmall && small_loads) {
-        if constexpr (kHasSmall) {
-          if (with_reg)
-            hipLaunchKernelGGL((fused_basis_kernel<T, MODE, true, kSmallLoads>), dim3(nsimple), dim3(kThreads), lds_bytes + (MODE == MODE_GRAD ? kQLdsMax2 : 0), stream, a);
-          else
-            hipLaunchKernelGGL((fused_basis_kernel<T, MODE, false, kSmallLoads>), dim3(nsimple), dim3(kThreads), lds_bytes + (MODE == MODE_GRAD ? kQLdsMax1 : 0), stream, a);
-        }
-      } else if (with_reg)
-        hipLaunchKernelGGL((fused_basis_kernel<T, MODE, true>), dim3(nsimple), dim3(kThreads), lds_bytes + (MODE == MODE_GRAD ? kQLdsMax2 : 0), stream, a);
-      else
-        hipLaunchKernelGGL((fused_basis_kernel<T, MODE, false>), dim3(nsimple), dim3(kThreads), lds_bytes + (MODE == MODE_GRAD ? kQLdsMax1 : 0), stream, a);
+      FusedFn k = basis_kernel<MODE, kMaxLoads>(with_reg);
+      if constexpr (kPass)
+        if (small_loads) k = basis_kernel<MODE, kSmallLoads>(with_reg);
+      const size_t lds = lds_bytes + (MODE == MODE_GRAD ? (with_reg ? kQLdsMax2 : kQLdsMax1) : 0);
+      hipLaunchKernelGGL(k, dim3(nsimple), dim3(kThreads), lds, stream, a);
     }
-    if constexpr (MODE == MODE_LOSS || MODE == MODE_GRAD) {
+    if constexpr (kPass) {
       // baselines that share tiles (skipped by the launch above): one workgroup per set.  With the regulariser these kernels take
       // the two-pass form (loss pass: S; gradient pass: alpha of each member's slice from the state) -- enqueue_pass orders the passes
       if (nheads > 0) {
         if (nheads_mfma > 0) {
-          if (with_reg && MODE == MODE_GRAD && heads_one_pass) hipLaunchKernelGGL((fused_multi_mfma_kernel<T, MODE_GRAD, 2>), dim3(mm_grid), dim3(kThreads), lds_multi_mfma_bytes, stream, a);
-          else if (with_reg) hipLaunchKernelGGL((fused_multi_mfma_kernel<T, MODE, 1>), dim3(mm_grid), dim3(kThreads), lds_multi_mfma_bytes, stream, a);
-          else hipLaunchKernelGGL((fused_multi_mfma_kernel<T, MODE, 0>), dim3(mm_grid), dim3(kThreads), lds_multi_mfma_bytes, stream, a);
+          FusedFn k = pick(with_reg, fused_multi_mfma_kernel<T, MODE, 1>, fused_multi_mfma_kernel<T, MODE, 0>);
+          if (with_reg && MODE == MODE_GRAD && heads_one_pass) k = fused_multi_mfma_kernel<T, MODE_GRAD, 2>;
+          hipLaunchKernelGGL(k, dim3(mm_grid), dim3(kThreads), lds_multi_mfma_bytes, stream, a);
         }
         if (nheads > nheads_mfma) {
           FusedArgs<T> b = a;
           b.heads = a.heads + mm_grid;
-          if (with_reg) hipLaunchKernelGGL((fused_multi_kernel<T, MODE, true>), dim3(nheads - nheads_mfma), dim3(kThreads), lds_multi_bytes, stream, b);
-          else hipLaunchKernelGGL((fused_multi_kernel<T, MODE, false>), dim3(nheads - nheads_mfma), dim3(kThreads), lds_multi_bytes, stream, b);
+          const FusedFn km = pick(with_reg, fused_multi_kernel<T, MODE, true>, fused_multi_kernel<T, MODE, false>);
+          hipLaunchKernelGGL(km, dim3(nheads - nheads_mfma), dim3(kThreads), lds_multi_bytes, stream, b);
         }
       }
     }
     if (nitems > nitems_simple) {
       a.item_base = nitems_simple;
-      if (with_reg)
-        hipLaunchKernelGGL((fused_group_kernel<T, MODE, true>), dim3(nitems - nitems_simple), dim3(kThreads), lds_group_bytes, stream, a);
-      else
-        hipLaunchKernelGGL((fused_group_kernel<T, MODE, false>), dim3(nitems - nitems_simple), dim3(kThreads), lds_group_bytes, stream, a);
+      const FusedFn kg = pick(with_reg, fused_group_kernel<T, MODE, true>, fused_group_kernel<T, MODE, false>);
+      hipLaunchKernelGGL(kg, dim3(nitems - nitems_simple), dim3(kThreads), lds_group_bytes, stream, a);
     }
   }
-  // the dense pass: panels with more than four vector tiles (kernel instance with eight accumulator tiles per wave), then the rest
-  template <bool GRAD> void launch_dense(Dense64Args m) {
-    m.slot_map = mf_map.as<int>();
-    hipLaunchKernelGGL((fused_dense64_kernel<GRAD>), dim3(mf_grid), dim3(kDenseThreads), (GRAD ? mf_lds_grad : mf_lds_loss)[0], stream, m);
-  }
-  template <bool GRAD> void launch_dense(MfmaArgs m) {
-    m.slot_map = mf_map.as<int>();
-    if (mf_split) {
-      if (mf_split2) hipLaunchKernelGGL((fused_dense_split2_kernel<GRAD>), dim3(mf_grid), dim3(kDenseThreads), (GRAD ? mf_lds_grad : mf_lds_loss)[0], stream, m);
-      else hipLaunchKernelGGL((fused_dense_split_kernel<GRAD>), dim3(mf_grid), dim3(kDenseThreads), (GRAD ? mf_lds_grad : mf_lds_loss)[0], stream, m);
-      return;
-    }
-    hipLaunchKernelGGL((fused_dense_kernel<GRAD>), dim3(mf_grid), dim3(kDenseThreads), (GRAD ? mf_lds_grad : mf_lds_loss)[0], stream, m);
+  // the dense pass: fp64 its own kernel; fp32 the split-operand kernels where set-up chose them
+  template <bool GRAD> void launch_dense(const DenseArgs& m) {
+    void (*k)(DenseArgs);
+    if constexpr (std::is_same<T, float>::value) k = !mf_split ? fused_dense_kernel<GRAD> : mf_split2 ? fused_dense_split2_kernel<GRAD> : fused_dense_split_kernel<GRAD>;
+    else k = fused_dense64_kernel<GRAD>;
+    hipLaunchKernelGGL(k, dim3(mf_grid), dim3(kDenseThreads), (GRAD ? mf_lds_grad : mf_lds_loss)[0], stream, m);
   }
   T* grad_c0() { return gc_direct ? gcp0.as<T>() : gc0.as<T>(); }
   T* grad_c1() { return gc_direct ? gcp1.as<T>() : gc1.as<T>(); }
+  // blocks of the per-antenna reduction (gain_grad_kernel, step_tail_kernel): one per antenna and 64 lanes of 16 bytes
+  int gain_blocks() const {
+    const int cpl = 16 / (int)sizeof(T2) > 0 ? 16 / (int)sizeof(T2) : 1;
+    return nants * ((fpad + 64 * cpl - 1) / (64 * cpl));
+  }
+  // gain_grad_kernel: the per-antenna reduction into r0 (REG: r1, r2 too) and, in one block per slice, its n_parts loss partials summed.
+  // nants_or_0 = 0: the partial sums alone (no antenna work)
+  template <bool REG> void launch_gain_grad(int blocks, T2* r0, T2* r1, T2* r2, int nants_or_0, int n_parts, const SliceMap& sm) {
+    hipLaunchKernelGGL((gain_grad_kernel<T, REG>), dim3(blocks), dim3(256), 0, stream, q0.as<T2>(), q1.as<T2>(), gains.as<T2>(), ant_ptr.as<int>(),
+                       ant_ent.as<int2>(), r0, r1, r2, nants_or_0, fpad, part.as<double>(), n_parts, scal.as<double>(), st_cur(), sm);
+  }
+  // coeff_partial_reduce_kernel: gc = the sums of the partials gcp of multi-item groups
+  void launch_partial_reduce(const DevBuf& gcp, const DevBuf& gc, const SliceMap& sm) {
+    hipLaunchKernelGGL(coeff_partial_reduce_kernel<T>, dim3((ncoef + 255) / 256), dim3(256), 0, stream, gcp.as<T>(), gcp.as<T>() + gcp_len, gc.as<T>(),
+                       gc.as<T>() + ncoef, coef_grp.as<int>(), grp_coff.as<int>(), grp_item_ptr.as<int>(), item_goff.as<int>(), ncoef, st_cur(), sm);
+  }
+  // ... or the same sums taken by the update itself (step_update_kernel, step_tail_kernel)
+  PartialSum<T> partial_sum(const DevBuf& gcp) {
+    return PartialSum<T>{gcp.as<T>(), gcp.p ? gcp.as<T>() + gcp_len : nullptr, coef_grp.as<int>(), grp_coff.as<int>(), grp_item_ptr.as<int>(), item_goff.as<int>(), ncoef};
+  }
+  // Behind a loss pass whose gradient pass needs alpha = 2 (S - P) of every slice (dense path with the regulariser; baselines that share
+  // tiles): the slices' sums -- with a communicator over the ranks, also on a rank whose own heads would not need it: its partials are part
+  // of the sums --, then alpha into the state
+  int enqueue_alpha_prepass(int n_parts, const SliceMap& sm) {
+    launch_gain_grad<false>(nslices, comm.as<T2>(), comm.as<T2>(), comm.as<T2>(), 0, n_parts, sm);
+    if (comm_on()) CAL_TRY(all_reduce(scal.p, 4 * (size_t)nslices, CAL_XCHG_F64, CAL_XCHG_SUM));
+    hipLaunchKernelGGL(alpha_kernel, dim3((nslices + 63) / 64), dim3(64), 0, stream, st_cur(), scal.as<double>(), nslices);
+    return CAL_OK;
+  }
+  // the time kernels' view of y and of the gradient planes: rows of time_row() reals, the tb_na antennas' 16-byte vectors in blocks of 256
+  int time_row() const { return 2 * y_w(); }
+  unsigned time_blocks() const { return (unsigned)(((long long)tb_na * (time_row() / (16 / (int)sizeof(T))) + 255) / 256); }
+  // the gain-gradient planes at r0 onto the basis, into gb_proj
+  int enqueue_project(int planes, T2* r0, const SliceMap& sm) {
+    const DevState* st = st_cur();
+    if (gb_on())
+      hipLaunchKernelGGL((gain_project_kernel<T>), dim3(nants, planes), dim3(256), 0, stream, r0, gb_B.as<T>(), (tb_on() ? tb_pf : gb_proj).template as<T>(),
+                         nants, fpad, gb_kpad, st, sm);
+    if (tb_on()) {
+      // the contraction over time, of the frequency-projected planes or of the per-channel ones
+      hipLaunchKernelGGL((gain_time_project_kernel<T>), dim3(time_blocks(), (tb_L + kTimeTile - 1) / kTimeTile, planes), dim3(256), 0, stream,
+                         gb_on() ? tb_pf.as<T>() : reinterpret_cast<const T*>(r0), tb_B.as<T>(), gb_proj.as<T>(), tb_na, tb_T, tb_L, tb_lpad, time_row(),
+                         (size_t)nants * time_row());
+    }
+    HIP_TRY(hipGetLastError());
+    return CAL_OK;
+  }
+  // a timed pass begins: the next pair of events of the pool, the first recorded now, *end behind the pass (enqueue_pass)
+  int begin_timed_pass(hipEvent_t* end) {
+    if (ev_used == ev_pool.size()) {
+      hipEvent_t x, y;
+      HIP_TRY(hipEventCreate(&x));
+      HIP_TRY(hipEventCreate(&y));
+      ev_pool.push_back({x, y});
+    }
+    *end = ev_pool[ev_used].second;
+    HIP_TRY(hipEventRecord(ev_pool[ev_used++].first, stream));
+    return CAL_OK;
+  }
 
-  // enqueue: loss (+ gradients) of the current parameters; leaves loss in state, final gradients in comm[0] / grad_c0()
-  // one_launch_tail: the caller follows up with step_tail_kernel (enqueue_update), which does everything behind the fused pass
-  // project: a gain basis is set and the pass serves y (a train step, cal_solver_eval_gain_coeff_grads): the gain-gradient planes are
-  // projected on the basis BEFORE the exchange, which then carries planes x 2 nants gb_kpad reals instead of planes x 2 nants fpad
-  int enqueue_pass(bool grads, bool apply_update, int losses_cap, bool one_launch_tail = false, bool project = false) {
-    const bool R = reg == CAL_REG_SUM;
-    FusedArgs<T> a = fused_args();
+  // enqueue: loss (+ gradients) of the current parameters in the shape `s` (step_shape); leaves loss in state, final gradients in
+  // comm[0] / grad_c0(), or with s.proj the gain gradient in gb_proj: the planes are projected BEFORE the exchange, which then carries
+  // planes x 2 nants gb_kpad reals instead of planes x 2 nants fpad.  With s.tail1 the caller follows up with step_tail_kernel
+  // (enqueue_step), which does everything behind the fused pass.
+  int enqueue_pass(const StepShape& s, int losses_cap) {
     DevState* st = st_cur();
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (timing) {
-      if (ev_used == ev_pool.size()) {
-        hipEvent_t x, y;
-        HIP_TRY(hipEventCreate(&x));
-        HIP_TRY(hipEventCreate(&y));
-        ev_pool.push_back({x, y});
+    hipEvent_t e1 = nullptr;
+    if (timing) CAL_TRY(begin_timed_pass(&e1));
+    const int n_parts = s.dense ? mf_npanels : nitems;
+    const SliceMap sm = smap(s.dense);
+    if (s.dense) {
+      DenseArgs m = dense_args();
+      if (s.two_pass) {
+        launch_dense<false>(m);
+        CAL_TRY(enqueue_alpha_prepass(n_parts, sm));
+        m.use_alpha = 1;
       }
-      e0 = ev_pool[ev_used].first;
-      e1 = ev_pool[ev_used].second;
-      ++ev_used;
-      HIP_TRY(hipEventRecord(e0, stream));
-    }
-    // dense path; with the "sum" regulariser it runs twice: a loss-only pass yields S (hence alpha = 2 (S - P)), then the
-    // gradient pass applies e = -2 w r + alpha w directly -- no second adjoint set, no combine kernels
-    const bool use_mfma = mf_ok;
-    const bool Rk = R && !use_mfma;  // the general kernel's two-adjoint-set form of the regulariser
-    const bool two_pass = use_mfma && R && grads;
-    if (use_mfma) {
-      {
-        typename std::conditional<std::is_same<T, float>::value, MfmaArgs, Dense64Args>::type m{};
-        m.ops = mf_ops.as<T>();
-        m.panels = mf_panels.as<PanelItem>();
-        m.data_r = data_r.as<T>();
-        m.data_i = data_i.as<T>();
-        m.wgts = wgts.as<T>();
-        m.gains = gains.as<T2>();
-        m.c_r = coef.as<T>();
-        m.c_i = coef.as<T>() + ncoef;
-        m.q0 = q0.as<T2>();
-        m.gc_r = grad_c0();
-        m.gc_i = grad_c0() + ncoef;
-        m.part = part.as<double>();
-        m.state = st;
-        m.nslices = nslices;
-        m.fpad = fpad;
-        m.nbls = nbls;
-        m.use_alpha = 0;
-        if (two_pass) {
-          launch_dense<false>(m);
-          hipLaunchKernelGGL((gain_grad_kernel<T, false>), dim3(nslices), dim3(256), 0, stream, q0.as<T2>(), q1.as<T2>(), gains.as<T2>(),
-                             ant_ptr.as<int>(), ant_ent.as<int2>(), comm.as<T2>(), comm.as<T2>(), comm.as<T2>(), 0, fpad, part.as<double>(),
-                             mf_npanels, scal.as<double>(), st, smap(true));
-          if (comm_on()) CAL_TRY(all_reduce(scal.p, 4 * (size_t)nslices, CAL_XCHG_F64, CAL_XCHG_SUM));
-          hipLaunchKernelGGL(alpha_kernel, dim3((nslices + 63) / 64), dim3(64), 0, stream, st, scal.as<double>(), nslices);
-          m.use_alpha = 1;
-        }
-        if (grads) launch_dense<true>(m); else launch_dense<false>(m);
-      }
+      if (s.grads) launch_dense<true>(m); else launch_dense<false>(m);
     } else {
-      if (grads && R && reg_prepass) {
-        // baselines that share tiles + the "sum" regulariser: their multi-slice kernels need alpha = 2 (S - P) of every slice BEFORE
-        // the gradient pass (no second adjoint set there): a loss pass over everything, the slices' sums, alpha -- then the gradients
-        // (with a communicator also on a rank whose own heads would not need it: its partials are part of the slices' sums)
+      const FusedArgs<T> a = fused_args();
+      if (s.prepass) {
         launch_fused<MODE_LOSS>(a, true);
-        hipLaunchKernelGGL((gain_grad_kernel<T, false>), dim3(nslices), dim3(256), 0, stream, q0.as<T2>(), q1.as<T2>(), gains.as<T2>(),
-                           ant_ptr.as<int>(), ant_ent.as<int2>(), comm.as<T2>(), comm.as<T2>(), comm.as<T2>(), 0, fpad, part.as<double>(),
-                           nitems, scal.as<double>(), st, smap(false));
-        if (comm_on()) CAL_TRY(all_reduce(scal.p, 4 * (size_t)nslices, CAL_XCHG_F64, CAL_XCHG_SUM));
-        hipLaunchKernelGGL(alpha_kernel, dim3((nslices + 63) / 64), dim3(64), 0, stream, st, scal.as<double>(), nslices);
+        CAL_TRY(enqueue_alpha_prepass(n_parts, sm));
       }
-      if (grads) launch_fused<MODE_GRAD>(a, R); else launch_fused<MODE_LOSS>(a, R);
+      if (s.grads) launch_fused<MODE_GRAD>(a, s.reg); else launch_fused<MODE_LOSS>(a, s.reg);
     }
-    const int n_parts = use_mfma ? mf_npanels : nitems;
-    const SliceMap sm = smap(use_mfma);
     if (timing) HIP_TRY(hipEventRecord(e1, stream));
-    if (one_launch_tail) {
+    if (s.tail1) {
       HIP_TRY(hipGetLastError());
       return CAL_OK;
     }
@@ -1094,68 +1108,33 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     T2* r0 = comm.as<T2>();
     T2* r1 = r0 + gn;
     T2* r2 = r1 + gn;
-    const bool fused_tail = apply_update && !Rk && tail_fits_one_launch();  // loop bookkeeping + update (+ partial-gradient sums) in ONE launch: enqueue_update
-    if (grads) {
-      if (!gc_direct && !use_mfma && !fused_tail) {
-        hipLaunchKernelGGL(coeff_partial_reduce_kernel<T>, dim3((ncoef + 255) / 256), dim3(256), 0, stream, gcp0.as<T>(),
-                           gcp0.as<T>() + gcp_len, gc0.as<T>(), gc0.as<T>() + ncoef, coef_grp.as<int>(), grp_coff.as<int>(),
-                           grp_item_ptr.as<int>(), item_goff.as<int>(), ncoef, st, sm);
-        if (Rk)
-          hipLaunchKernelGGL(coeff_partial_reduce_kernel<T>, dim3((ncoef + 255) / 256), dim3(256), 0, stream, gcp1.as<T>(),
-                             gcp1.as<T>() + gcp_len, gc1.as<T>(), gc1.as<T>() + ncoef, coef_grp.as<int>(), grp_coff.as<int>(),
-                             grp_item_ptr.as<int>(), item_goff.as<int>(), ncoef, st, sm);
-      }
-      const int cpl = 16 / (int)sizeof(T2) > 0 ? 16 / (int)sizeof(T2) : 1;
-      const int nb = nants * ((fpad + 64 * cpl - 1) / (64 * cpl)) + nslices;  // + one block per slice: its loss partial sums
-      if (Rk)
-        hipLaunchKernelGGL((gain_grad_kernel<T, true>), dim3(nb), dim3(256), 0, stream, q0.as<T2>(), q1.as<T2>(), gains.as<T2>(),
-                           ant_ptr.as<int>(), ant_ent.as<int2>(), r0, r1, r2, nants, fpad, part.as<double>(), n_parts,
-                           scal.as<double>(), st, sm);
-      else
-        hipLaunchKernelGGL((gain_grad_kernel<T, false>), dim3(nb), dim3(256), 0, stream, q0.as<T2>(), q1.as<T2>(), gains.as<T2>(),
-                           ant_ptr.as<int>(), ant_ent.as<int2>(), r0, r1, r2, nants, fpad, part.as<double>(), n_parts,
-                           scal.as<double>(), st, sm);
-    } else {
-      // loss only: just the partial-sum blocks of the gain kernel (nants = 0 -> no antenna work)
-      hipLaunchKernelGGL((gain_grad_kernel<T, false>), dim3(nslices), dim3(256), 0, stream, q0.as<T2>(), q1.as<T2>(), gains.as<T2>(),
-                         ant_ptr.as<int>(), ant_ent.as<int2>(), r0, r1, r2, 0, fpad, part.as<double>(), n_parts, scal.as<double>(), st, sm);
+    if (s.partial_reduce) {
+      launch_partial_reduce(gcp0, gc0, sm);
+      if (s.Rk) launch_partial_reduce(gcp1, gc1, sm);
     }
-    const bool proj = project && grads;
-    if (proj) {
-      const int planes = Rk ? 3 : 1;
-      if (gb_on())
-        hipLaunchKernelGGL((gain_project_kernel<T>), dim3(nants, planes), dim3(256), 0, stream, r0, gb_B.as<T>(), (tb_on() ? tb_pf : gb_proj).template as<T>(),
-                           nants, fpad, gb_kpad, st, sm);
-      if (tb_on()) {
-        // the contraction over time, of the frequency-projected planes or of the per-channel ones
-        constexpr int V = 16 / (int)sizeof(T);
-        const int row = 2 * y_w();
-        const long long nvecs = (long long)tb_na * (row / V);
-        hipLaunchKernelGGL((gain_time_project_kernel<T>), dim3((unsigned)((nvecs + 255) / 256), (tb_L + kTimeTile - 1) / kTimeTile, planes), dim3(256), 0, stream,
-                           gb_on() ? tb_pf.as<T>() : reinterpret_cast<const T*>(r0), tb_B.as<T>(), gb_proj.as<T>(), tb_na, tb_T, tb_L, tb_lpad, row,
-                           (size_t)nants * row);
-      }
-      HIP_TRY(hipGetLastError());
-    }
-    const size_t xn = proj ? (size_t)y_rows() * y_row() : gn;  // complex elements per plane of the gain gradient from here on
-    T2* x0 = proj ? gb_proj.as<T2>() : r0;
+    if (!s.grads) launch_gain_grad<false>(nslices, r0, r1, r2, 0, n_parts, sm);  // loss only: just the partial-sum blocks
+    else if (s.Rk) launch_gain_grad<true>(gain_blocks() + nslices, r0, r1, r2, nants, n_parts, sm);
+    else launch_gain_grad<false>(gain_blocks() + nslices, r0, r1, r2, nants, n_parts, sm);
+    if (s.proj) CAL_TRY(enqueue_project(s.planes, r0, sm));
+    const size_t xn = s.proj ? (size_t)y_rows() * y_row() : gn;  // complex elements per plane of the gain gradient from here on
+    T2* x0 = s.proj ? gb_proj.as<T2>() : r0;
     if (comm_on()) {
       // the one exchange step of the sharded fit: sum gain-gradient parts and loss scalars over ranks
       // (issued for a 1-rank communicator too, so the path can be exercised on a single GPU)
       const int gdt = sizeof(T) == 4 ? CAL_XCHG_F32 : CAL_XCHG_F64;
       if (nccl) NCCL_TRY(ncclGroupStart());
       int rc = CAL_OK;
-      if (grads) rc = all_reduce(x0, (size_t)(Rk ? 3 : 1) * xn * 2, gdt, CAL_XCHG_SUM);
+      if (s.grads) rc = all_reduce(x0, (size_t)s.planes * xn * 2, gdt, CAL_XCHG_SUM);
       if (rc == CAL_OK) rc = all_reduce(scal.p, 4 * (size_t)nslices, CAL_XCHG_F64, CAL_XCHG_SUM);
       if (nccl) NCCL_TRY(ncclGroupEnd());
       CAL_TRY(rc);
     }
-    if (!fused_tail)
+    if (s.finalize)
       hipLaunchKernelGGL(finalize_kernel, dim3((nslices + 63) / 64), dim3(64), 0, stream, st, scal.as<double>(), losses.as<double>(), losses_cap,
-                         apply_update ? 1 : 0, nslices);
-    if (grads && Rk) {
+                         s.update != UPDATE_NONE ? 1 : 0, nslices);
+    if (s.grads && s.Rk) {
       hipLaunchKernelGGL(combine_gain_kernel<T>, dim3((int)((xn + 255) / 256)), dim3(256), 0, stream, x0, x0 + xn, x0 + 2 * xn, (int)xn, st, sm,
-                         proj ? (int)y_row() : fpad);
+                         s.proj ? (int)y_row() : fpad);
       hipLaunchKernelGGL(combine_coeff_kernel<T>, dim3((ncoef + 255) / 256), dim3(256), 0, stream, grad_c0(), grad_c0() + ncoef,
                          grad_c1(), grad_c1() + ncoef, ncoef, st, sm);
     }
@@ -1163,29 +1142,7 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     return CAL_OK;
   }
 
-  // Small problems (a step of tens of microseconds: HERA-37, the tutorial) gain from one launch instead of three for the
-  // tail of a step; with millions of parameters the per-block decision prologue of the fused kernel costs more than the two
-  // kernel boundaries it saves (HERA-350: 105 us against 5 + 56 us), so those keep finalize_kernel + adam2_kernel.
-  // (CAL_LAUNCH_KERNELS keeps every kernel its own launch: finalize_kernel + adam2_kernel at any size)
-  // (... and LAMB's update is four launches of its own: per-variable norms sit between the moments and the parameters)
-  bool tail_fits_one_launch() const {
-    return 2LL * nants * fpad + 2LL * ncoef <= (1LL << 20) && launch_mode != CAL_LAUNCH_KERNELS && opt.optimizer != CAL_OPT_LAMB;
-  }
-  // Problems whose step is tens of microseconds: the whole tail as ONE launch (step_tail_kernel) -- no communicator (the
-  // exchange sits between the reduction and the update), general kernels, and not when every kernel is asked to be its own launch
-  // (... nor with the regulariser over baselines that share tiles: alpha is needed between that path's two passes)
-  bool one_launch_tail() const {
-    // (... nor with a gain basis: the projection sits between the antenna reduction and the update, which step_tail_kernel fuses)
-    return !comm_on() && !mf_ok && !yb_on() && tail_fits_one_launch() && launch_mode != CAL_LAUNCH_KERNELS && !(reg == CAL_REG_SUM && reg_prepass);
-  }
-  void launch_tail(const TailArgs<T>& a, unsigned grid, bool R) {
-    if (R)
-      hipLaunchKernelGGL((step_tail_kernel<T, true>), dim3(grid), dim3(256), 0, stream, a);
-    else
-      hipLaunchKernelGGL((step_tail_kernel<T, false>), dim3(grid), dim3(256), 0, stream, a);
-  }
-  int enqueue_tail(bool freeze_model, int losses_cap) {
-    const bool R = reg == CAL_REG_SUM;
+  int enqueue_tail(const StepShape& s, bool freeze_model, int losses_cap) {
     TailArgs<T> a{};
     a.q0 = q0.as<T2>();
     a.q1 = q1.as<T2>();
@@ -1199,16 +1156,15 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     a.coef = AdamSet<T>{coef.as<T>(), gcp0.as<T>(), coef_m.as<T>(), coef_v.as<T>(), coef_snap.p ? coef_snap.as<T>() : coef.as<T>(),
                         freeze_model ? 0LL : 2LL * ncoef};
     a.coef_g1 = gcp1.as<T>();
-    if (!gc_direct) {
-      a.ps0 = PartialSum<T>{gcp0.as<T>(), gcp0.as<T>() + gcp_len, coef_grp.as<int>(), grp_coff.as<int>(), grp_item_ptr.as<int>(), item_goff.as<int>(), ncoef};
-      a.ps1 = PartialSum<T>{gcp1.as<T>(), gcp1.p ? gcp1.as<T>() + gcp_len : nullptr, coef_grp.as<int>(), grp_coff.as<int>(), grp_item_ptr.as<int>(), item_goff.as<int>(), ncoef};
+    if (s.partials) {
+      a.ps0 = partial_sum(gcp0);
+      a.ps1 = partial_sum(gcp1);
     }
     a.part = part.as<double>();
     a.nparts = nitems;
     a.nants = nants;
     a.fpad = fpad;
-    const int cpl = 16 / (int)sizeof(T2) > 0 ? 16 / (int)sizeof(T2) : 1;
-    a.nblk_gain = nants * ((fpad + 64 * cpl - 1) / (64 * cpl));
+    a.nblk_gain = gain_blocks();
     a.in = st_cur();
     a.out = st_nxt();
     a.losses = losses.as<double>();
@@ -1217,46 +1173,38 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     a.cblk_ptr = nslices > 1 ? slice_cblk.as<int>() : nullptr;
     a.ncoef = ncoef;
     const long long nblk_c = freeze_model ? 0 : h_slice_cblk[nslices];
-    const unsigned grid = (unsigned)(a.nblk_gain + nblk_c);
-    launch_tail(a, grid, R);
+    if (s.reg) hipLaunchKernelGGL((step_tail_kernel<T, true>), dim3((unsigned)(a.nblk_gain + nblk_c)), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL((step_tail_kernel<T, false>), dim3((unsigned)(a.nblk_gain + nblk_c)), dim3(256), 0, stream, a);
     st_par ^= 1;
     std::swap(gains.p, gains_alt.p);  // the buffer just written is the current one
     HIP_TRY(hipGetLastError());
     return CAL_OK;
   }
-  int enqueue_update(bool freeze_model, int losses_cap) {
+  // the optimizer's gain variables, with a gain basis y (the same kernels on flat arrays of another row length), and that row length
+  AdamSet<T> gain_set() {
+    if (yb_on()) return AdamSet<T>{gb_y.as<T>(), gb_proj.as<T>(), gb_ym.as<T>(), gb_yv.as<T>(), gb_ysnap.p ? gb_ysnap.as<T>() : gb_y.as<T>(), 2LL * y_rows() * y_row()};
+    return AdamSet<T>{gains.as<T>(), comm.as<T>(), gains_m.as<T>(), gains_v.as<T>(), gains_snap.p ? gains_snap.as<T>() : gains.as<T>(), 2LL * nants * fpad};
+  }
+  int gain_row() const { return yb_on() ? (int)y_row() : fpad; }
+  int enqueue_update(const StepShape& s, bool freeze_model, int losses_cap) {
     DevState* st = st_cur();
-    const long long gn = 2LL * nants * fpad;
-    T* gsnap = gains_snap.p ? gains_snap.as<T>() : gains.as<T>();
-    T* csnap = coef_snap.p ? coef_snap.as<T>() : coef.as<T>();
-    // with a gain basis the gain set is y: the same kernels on flat arrays of row length gb_kpad, then the gains are rebuilt from y
-    if (yb_on()) {
-      CAL_TRY(enqueue_update_y(freeze_model, losses_cap));
-      return enqueue_expand(gb_y.as<T2>(), gains.as<T2>());
-    }
-    const AdamSet<T> ga{gains.as<T>(), comm.as<T>(), gains_m.as<T>(), gains_v.as<T>(), gsnap, gn};
-    const AdamSet<T> ca{coef.as<T>(), grad_c0(), coef_m.as<T>(), coef_v.as<T>(), csnap, freeze_model ? 0LL : 2LL * ncoef};
+    const AdamSet<T> ga = gain_set();
+    const AdamSet<T> ca{coef.as<T>(), grad_c0(), coef_m.as<T>(), coef_v.as<T>(), coef_snap.p ? coef_snap.as<T>() : coef.as<T>(), freeze_model ? 0LL : 2LL * ncoef};
     const int nblk_a = (int)((ga.n + 255) / 256), nblk_b = (int)((ca.n + 255) / 256);
-    const bool Rk = reg == CAL_REG_SUM && !mf_ok;
-    if (!Rk && tail_fits_one_launch()) {
+    if (s.update == UPDATE_FUSED) {
       // the common path: finalize + update (+ the partial coefficient-gradient sums of split groups) as one launch
       PartialSum<T> ps{};
-      if (!gc_direct && !mf_ok && !freeze_model)
-        ps = PartialSum<T>{gcp0.as<T>(), gcp0.as<T>() + gcp_len, coef_grp.as<int>(), grp_coff.as<int>(), grp_item_ptr.as<int>(),
-                           item_goff.as<int>(), ncoef};
+      if (s.partials && !freeze_model) ps = partial_sum(gcp0);
       const unsigned nb = (unsigned)std::max(1, std::min(nblk_a + nblk_b, 16384));
       hipLaunchKernelGGL((step_update_kernel<T>), dim3(nb), dim3(256), (size_t)nslices * sizeof(SliceStep<T>), stream, ga, ca, ps, st, st_nxt(),
-                         scal.as<double>(), losses.as<double>(), losses_cap, smap(mf_ok), fpad, ncoef);
+                         scal.as<double>(), losses.as<double>(), losses_cap, smap(s.dense), gain_row(), ncoef);
       st_par ^= 1;
-      HIP_TRY(hipGetLastError());
-      return CAL_OK;
-    }
-    if (opt.optimizer == CAL_OPT_LAMB) {
+    } else if (s.update == UPDATE_LAMB) {
       // moments + u (in place of the gradients), per-variable norms, trust ratios, parameters.  (With a frozen model the
       // coefficient variables are not touched: their set is empty and their ratios are never read.)
       T* ua = comm.as<T>();
       T* ub = grad_c0();
-      hipLaunchKernelGGL((lamb_moments_kernel<T>), dim3((unsigned)(nblk_a + nblk_b)), dim3(256), 0, stream, ga, ca, nblk_a, st, smap(mf_ok), fpad, ncoef, ua, ub);
+      hipLaunchKernelGGL((lamb_moments_kernel<T>), dim3((unsigned)(nblk_a + nblk_b)), dim3(256), 0, stream, ga, ca, nblk_a, st, smap(s.dense), fpad, ncoef, ua, ub);
       hipLaunchKernelGGL((lamb_norm_kernel<T>), dim3((unsigned)(lamb_nvar * kLambSeg)), dim3(256), 0, stream, lamb_vars.as<LambVar>(), gains.as<T>(), ua,
                          coef.as<T>(), ub, lamb_partial.as<double>());
       const double* glob = nullptr;
@@ -1271,66 +1219,33 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
       }
       hipLaunchKernelGGL(lamb_ratio_kernel, dim3((lamb_nvar + 63) / 64), dim3(64), 0, stream, lamb_partial.as<double>(), lamb_ratio.as<double>(), lamb_nvar,
                          glob, lamb_slot.as<int>(), 2 * nslices, lamb_ncvar, nslices * lamb_nv);
-      hipLaunchKernelGGL((lamb_apply_kernel<T>), dim3((unsigned)(nblk_a + nblk_b)), dim3(256), 0, stream, ga, ca, nblk_a, st, smap(mf_ok), fpad, ncoef, ua, ub,
+      hipLaunchKernelGGL((lamb_apply_kernel<T>), dim3((unsigned)(nblk_a + nblk_b)), dim3(256), 0, stream, ga, ca, nblk_a, st, smap(s.dense), fpad, ncoef, ua, ub,
                          lamb_ratio.as<double>(), lamb_cvar_ptr.as<int>(), lamb_ncvar);
-      HIP_TRY(hipGetLastError());
-      return CAL_OK;
-    }
-    {
+    } else {
       constexpr long long per = 256LL * kAdamVec<T>;  // elements per block
       const int va = (int)((ga.n + per - 1) / per), vb = (int)((ca.n + per - 1) / per);
-      hipLaunchKernelGGL((adam2_kernel<T>), dim3((unsigned)(va + vb)), dim3(256), 0, stream, ga, ca, va, st, smap(mf_ok), fpad, ncoef);
+      hipLaunchKernelGGL((adam2_kernel<T>), dim3((unsigned)(va + vb)), dim3(256), 0, stream, ga, ca, va, st, smap(s.dense), gain_row(), ncoef);
     }
     HIP_TRY(hipGetLastError());
-    return CAL_OK;
+    // with a gain basis the gains are rebuilt from y
+    return s.expand ? enqueue_expand(gb_y.as<T2>(), gains.as<T2>()) : (int)CAL_OK;
   }
-
-  // the update of a basis fit: enqueue_update's common path and its adam2_kernel path with the y arrays as the gain set (LAMB is refused
-  // while a basis is set: set_optimizer, set_gain_basis)
-  int enqueue_update_y(bool freeze_model, int losses_cap) {
-    DevState* st = st_cur();
-    T* ysnap = gb_ysnap.p ? gb_ysnap.as<T>() : gb_y.as<T>();
-    T* csnap = coef_snap.p ? coef_snap.as<T>() : coef.as<T>();
-    const AdamSet<T> ga{gb_y.as<T>(), gb_proj.as<T>(), gb_ym.as<T>(), gb_yv.as<T>(), ysnap, 2LL * y_rows() * y_row()};
-    const AdamSet<T> ca{coef.as<T>(), grad_c0(), coef_m.as<T>(), coef_v.as<T>(), csnap, freeze_model ? 0LL : 2LL * ncoef};
-    const bool Rk = reg == CAL_REG_SUM && !mf_ok;
-    if (!Rk && tail_fits_one_launch()) {
-      PartialSum<T> ps{};
-      if (!gc_direct && !mf_ok && !freeze_model)
-        ps = PartialSum<T>{gcp0.as<T>(), gcp0.as<T>() + gcp_len, coef_grp.as<int>(), grp_coff.as<int>(), grp_item_ptr.as<int>(),
-                           item_goff.as<int>(), ncoef};
-      const int nblk = (int)((ga.n + 255) / 256) + (int)((ca.n + 255) / 256);
-      const unsigned nb = (unsigned)std::max(1, std::min(nblk, 16384));
-      hipLaunchKernelGGL((step_update_kernel<T>), dim3(nb), dim3(256), (size_t)nslices * sizeof(SliceStep<T>), stream, ga, ca, ps, st, st_nxt(),
-                         scal.as<double>(), losses.as<double>(), losses_cap, smap(mf_ok), (int)y_row(), ncoef);
-      st_par ^= 1;
-      HIP_TRY(hipGetLastError());
-      return CAL_OK;
-    }
-    constexpr long long per = 256LL * kAdamVec<T>;  // elements per block
-    const int va = (int)((ga.n + per - 1) / per), vb = (int)((ca.n + per - 1) / per);
-    hipLaunchKernelGGL((adam2_kernel<T>), dim3((unsigned)(va + vb)), dim3(256), 0, stream, ga, ca, va, st, smap(mf_ok), (int)y_row(), ncoef);
-    HIP_TRY(hipGetLastError());
-    return CAL_OK;
+  // one train step: the pass, then its one-launch tail or its update
+  int enqueue_step(const StepShape& s, bool freeze_model, int cap) {
+    CAL_TRY(enqueue_pass(s, cap));
+    return s.tail1 ? enqueue_tail(s, freeze_model, cap) : enqueue_update(s, freeze_model, cap);
   }
   // dst = g0 + B src (src: y or its use_min snapshot); with a time basis dst = g0 + Bt (x) B src
   int enqueue_expand(const T2* src, T2* dst) {
     constexpr int per = 256 * (16 / (int)sizeof(T));  // channels per block
     if (tb_on()) {
-      constexpr int V = 16 / (int)sizeof(T);
-      const int row = 2 * y_w();
-      const long long nvecs = (long long)tb_na * (row / V);
-      hipLaunchKernelGGL((gain_time_expand_kernel<T>), dim3((unsigned)((nvecs + 255) / 256), (tb_T + kTimeTile - 1) / kTimeTile), dim3(256), 0, stream,
+      hipLaunchKernelGGL((gain_time_expand_kernel<T>), dim3(time_blocks(), (tb_T + kTimeTile - 1) / kTimeTile), dim3(256), 0, stream,
                          gb_on() ? nullptr : gb_g0.as<T>(), tb_Bt.as<T>(), reinterpret_cast<const T*>(src),
-                         gb_on() ? tb_z.as<T>() : reinterpret_cast<T*>(dst), tb_na, tb_T, tb_L, tb_tpad, row);
-      if (!gb_on()) {
-        HIP_TRY(hipGetLastError());
-        return CAL_OK;
-      }
+                         gb_on() ? tb_z.as<T>() : reinterpret_cast<T*>(dst), tb_na, tb_T, tb_L, tb_tpad, time_row());
       src = tb_z.as<T2>();
     }
-    hipLaunchKernelGGL((gain_expand_kernel<T>), dim3((fpad + per - 1) / per, nants), dim3(256), 0, stream, gb_g0.as<T2>(), gb_Bt.as<T>(), src, dst, fpad,
-                       gb_kpad);
+    if (gb_on())
+      hipLaunchKernelGGL((gain_expand_kernel<T>), dim3((fpad + per - 1) / per, nants), dim3(256), 0, stream, gb_g0.as<T2>(), gb_Bt.as<T>(), src, dst, fpad, gb_kpad);
     HIP_TRY(hipGetLastError());
     return CAL_OK;
   }
@@ -1473,11 +1388,13 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     if (!yb_on()) return fail(CAL_ERR_STATE, "get_gain_coeffs: no gain basis is set (cal_solver_set_gain_basis, cal_solver_set_gain_time_basis)");
     if (which != 0 && which != 1) return fail(CAL_ERR_INVALID, "get_gain_coeffs: which must be 0 or 1");
     if (which == 1 && !gb_ysnap.p) return fail(CAL_ERR_STATE, "get_gain_coeffs(which=1): no use_min snapshot was taken since the gain basis was set");
-    const T* y = which == 1 ? gb_ysnap.as<T>() : gb_y.as<T>();
     HIP_TRY(hipStreamSynchronize(stream));
+    return download_y(y_r, y_i, which == 1 ? gb_ysnap.as<T>() : gb_y.as<T>());
+  }
+  int download_y(void* y_r, void* y_i, const T* src) {  // the two planes of an array in the shape of y (null: not asked for)
     const long long rows = y_rows() * (y_row() / y_w());
-    if (y_r) CAL_TRY(download_rows(y_r, y, rows, 2, 0, y_cols(), y_w()));
-    if (y_i) CAL_TRY(download_rows(y_i, y, rows, 2, 1, y_cols(), y_w()));
+    if (y_r) CAL_TRY(download_rows(y_r, src, rows, 2, 0, y_cols(), y_w()));
+    if (y_i) CAL_TRY(download_rows(y_i, src, rows, 2, 1, y_cols(), y_w()));
     return CAL_OK;
   }
   // the optimizer's slots of a fit with a gain basis, read only (get_moments / set_moments stay refused there: no resume): the y slots
@@ -1487,11 +1404,8 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     if (!yb_on()) return fail(CAL_ERR_STATE, "get_gain_coeff_moments: no gain basis is set (cal_solver_set_gain_basis, cal_solver_set_gain_time_basis)");
     if (!has_opt) return fail(CAL_ERR_STATE, "get_gain_coeff_moments: no optimizer is set (cal_solver_set_optimizer)");
     HIP_TRY(hipStreamSynchronize(stream));
-    const long long rows = y_rows() * (y_row() / y_w());
-    if (ym_r) CAL_TRY(download_rows(ym_r, gb_ym.as<T>(), rows, 2, 0, y_cols(), y_w()));
-    if (ym_i) CAL_TRY(download_rows(ym_i, gb_ym.as<T>(), rows, 2, 1, y_cols(), y_w()));
-    if (yv_r) CAL_TRY(download_rows(yv_r, gb_yv.as<T>(), rows, 2, 0, y_cols(), y_w()));
-    if (yv_i) CAL_TRY(download_rows(yv_i, gb_yv.as<T>(), rows, 2, 1, y_cols(), y_w()));
+    CAL_TRY(download_y(ym_r, ym_i, gb_ym.as<T>()));
+    CAL_TRY(download_y(yv_r, yv_i, gb_yv.as<T>()));
     const size_t cb = (size_t)ncoef * sizeof(T);
     if (cm_r) HIP_TRY(copy_sync(cm_r, coef_m.as<T>(), cb, hipMemcpyDeviceToHost));
     if (cm_i) HIP_TRY(copy_sync(cm_i, coef_m.as<T>() + ncoef, cb, hipMemcpyDeviceToHost));
@@ -1505,20 +1419,8 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     HIP_TRY(hipSetDevice(device));
     CAL_TRY(ready());
     if (!yb_on()) return fail(CAL_ERR_STATE, "eval_gain_coeff_grads: no gain basis is set (cal_solver_set_gain_basis, cal_solver_set_gain_time_basis)");
-    begin_pass_state();
-    CAL_TRY(push_state());
-    CAL_TRY(enqueue_pass(true, false, 0, false, true));
-    CAL_TRY(pull_state());
-    if (timing) CAL_TRY(collect_timing());
-    if (loss) {
-      double tot = 0;
-      for (int t = 0; t < nslices; ++t) tot += h_state[t].loss;
-      *loss = tot;
-    }
-    const long long rows = y_rows() * (y_row() / y_w());
-    if (gy_r) CAL_TRY(download_rows(gy_r, gb_proj.as<T>(), rows, 2, 0, y_cols(), y_w()));
-    if (gy_i) CAL_TRY(download_rows(gy_i, gb_proj.as<T>(), rows, 2, 1, y_cols(), y_w()));
-    return CAL_OK;
+    CAL_TRY(eval_pass(kProjectedGradPass, loss));
+    return download_y(gy_r, gy_i, gb_proj.as<T>());
   }
 
   void drop_graph() {
@@ -1530,17 +1432,17 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
   // captured launches -- buffer pointers, optimizer, frozen model, regulariser, loss-history capacity, which halves of the
   // double-buffered state and gains are current -- is the key.  kGraphSteps is even, so a replay leaves both double buffers
   // where it found them and the same graph serves the next replay.
-  // `tail`: the two-launch form of small problems (fused pass + step_tail_kernel); else the kernels of a large problem's step (fused / dense
+  // s.tail1: the two-launch form of small problems (fused pass + step_tail_kernel); else the kernels of a large problem's step (fused / dense
   // pass(es), gain_grad_kernel, finalize_kernel, the update): a host whose cores are busy elsewhere then pays ONE launch per `nsteps` steps
   // instead of four or five per step (measured on shared boxes: 2.4-3.2 ms per step of a 0.6-ms kernel while the host was contended).
-  int replay_steps(bool freeze_model, int cap, bool tail, int nsteps) {
-    const GraphKey key{opt.optimizer, freeze_model ? 1 : 0, reg, cap, st_par, tail ? 1 : 0, nsteps, gains.p, gains_snap.p, losses.p, gb_y.p, gb_ysnap.p, tb_z.p, tb_pf.p};
+  int replay_steps(const StepShape& s, bool freeze_model, int cap, int nsteps) {
+    const GraphKey key{opt.optimizer, freeze_model ? 1 : 0, reg, cap, st_par, s.tail1 ? 1 : 0, nsteps, gains.p, gains_snap.p, losses.p, gb_y.p, gb_ysnap.p, tb_z.p, tb_pf.p};
     if (!graph_exec || !(key == graph_key)) {
       drop_graph();
       hipGraph_t graph = nullptr;
       // enqueue_tail flips the double-buffer parities on the HOST for every captured step; nothing has run on the device until the
-      // graph is launched, so every failure path below puts them back (an odd number of captured steps would otherwise leave the
-      // host pointing at the stale halves)
+      // graph is launched, so they are put back when the capture ends (a failure after an odd number of captured steps would otherwise
+      // leave the host pointing at the stale halves)
       const int par0 = st_par;
       void* const gains0 = gains.p;
       void* const alt0 = gains_alt.p;
@@ -1551,28 +1453,20 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
       };
       HIP_TRY(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
       int rc = CAL_OK;
-      for (int k = 0; k < nsteps && rc == CAL_OK; ++k) {
-        rc = enqueue_pass(true, true, cap, tail, yb_on());
-        if (rc == CAL_OK) rc = tail ? enqueue_tail(freeze_model, cap) : enqueue_update(freeze_model, cap);
-      }
+      for (int k = 0; k < nsteps && rc == CAL_OK; ++k) rc = enqueue_step(s, freeze_model, cap);
       const hipError_t e = hipStreamEndCapture(stream, &graph);
+      undo();  // on every path (after an even number of steps: the same values; said explicitly: the launch below is what moves the device)
       if (rc != CAL_OK) {
         if (graph) (void)hipGraphDestroy(graph);
-        undo();
         return rc;
       }
-      if (e != hipSuccess) {
-        undo();
-        return fail(CAL_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e));
-      }
+      if (e != hipSuccess) return fail(CAL_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e));
       const hipError_t ei = hipGraphInstantiate(&graph_exec, graph, nullptr, nullptr, 0);
       (void)hipGraphDestroy(graph);
       if (ei != hipSuccess) {
         graph_exec = nullptr;
-        undo();
         return fail(CAL_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(ei));
       }
-      undo();  // (kGraphSteps is even: the same values; said explicitly: the launch below is what moves the device)
       graph_key = key;
     }
     HIP_TRY(hipGraphLaunch(graph_exec, stream));
@@ -1633,12 +1527,11 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     return CAL_OK;
   }
 
-  int eval(bool grads, double* loss, void* gg_r, void* gg_i, void* gc_r, void* gc_i) override {
-    HIP_TRY(hipSetDevice(device));
-    CAL_TRY(ready());
+  // what the one-off evaluations share: no slice is stopped, one pass, the loop state back on the host, the timing
+  int eval_pass(PassAsk ask, double* loss) {
     begin_pass_state();
     CAL_TRY(push_state());
-    CAL_TRY(enqueue_pass(grads, false, 0));
+    CAL_TRY(enqueue_pass(step_shape(ask), 0));
     CAL_TRY(pull_state());
     if (timing) CAL_TRY(collect_timing());
     if (loss) {  // several time slices: the sum of their losses (cal_solver_get_slice_losses has each)
@@ -1646,6 +1539,12 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
       for (int t = 0; t < nslices; ++t) tot += h_state[t].loss;
       *loss = tot;
     }
+    return CAL_OK;
+  }
+  int eval(bool grads, double* loss, void* gg_r, void* gg_i, void* gc_r, void* gc_i) override {
+    HIP_TRY(hipSetDevice(device));
+    CAL_TRY(ready());
+    CAL_TRY(eval_pass(grads ? kGradPass : kLossPass, loss));
     if (grads) {
       if (gg_r) CAL_TRY(download_rows(gg_r, comm.as<T>(), nants, 2, 0));
       if (gg_i) CAL_TRY(download_rows(gg_i, comm.as<T>(), nants, 2, 1));
@@ -1690,20 +1589,10 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     // chunk fall through at once for it, so the host only synchronises once per chunk instead of once per step (:701)
     const int chunk = steps_per_sync;
     const int cap = r->record ? r->nsteps : 0;
-    const bool tail1 = one_launch_tail();
-    if (tail1 && !gains_alt.p) CAL_TRY(gains_alt.alloc(gains.bytes));
-    // hipGraph replay of kGraphSteps train steps at a time: the steps of such problems are bound by launch latency.  Timed
-    // runs (HIP events around every fused pass) issue their launches one by one.
-    // Large problems replay too unless the step holds an exchange (a collective or a host callback is not captured): see replay_steps.
-    // (capturing and instantiating the graph of a large problem's steps costs tens of milliseconds -- 40 for 16 steps of the dense path --, once
-    // per shape of call: calls of fewer than kGraphMinSteps steps launch kernel by kernel, longer ones replay 8 steps at a time)
-    constexpr int kGraphStepsLarge = 8, kGraphMinSteps = 256;
-    // Of the large problems only the dense path replays in "auto": measured at HERA-350 (tools/graph_ab.py) its step is the same or 0.5 % shorter
-    // from a graph, the streaming kernel's step 3-13 % LONGER (4.9 -> 5.1, 4.7 -> 5.3 ms on two boxes: what the passes leave in the caches
-    // for the kernels behind them does not survive the graph's node boundaries).
-    const bool replay = (tail1 || (!comm_on() && ((mf_ok && r->nsteps >= kGraphMinSteps) || launch_mode == CAL_LAUNCH_GRAPH))) && !timing &&
-                        (launch_mode == CAL_LAUNCH_AUTO || launch_mode == CAL_LAUNCH_GRAPH);
-    const int gsteps = tail1 ? kGraphSteps : std::min(kGraphStepsLarge, chunk & ~1);  // even: the double-buffered loop state ends a replay where it began
+    // the shape of every step of this call: its kernels, its update, launched one by one or replayed from a graph (step_plan.hpp)
+    const StepShape shape = step_shape(train_step(yb_on()), r->nsteps);
+    if (shape.tail1 && !gains_alt.p) CAL_TRY(gains_alt.alloc(gains.bytes));
+    const int gsteps = shape.tail1 ? kGraphSteps : std::min(kGraphStepsLarge, chunk & ~1);  // even: the double-buffered loop state ends a replay where it began
     int issued = 0;
     while (issued < r->nsteps) {
       const int n = std::min(chunk, r->nsteps - issued);
@@ -1714,13 +1603,9 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
         roctx().push(label);
       }
       int s = 0;
-      if (replay) {
-        for (; gsteps >= 2 && s + gsteps <= n; s += gsteps) CAL_TRY(replay_steps(r->freeze_model != 0, cap, tail1, gsteps));
-      }
-      for (; s < n; ++s) {
-        CAL_TRY(enqueue_pass(true, true, cap, tail1, yb_on()));
-        if (tail1) CAL_TRY(enqueue_tail(r->freeze_model != 0, cap)); else CAL_TRY(enqueue_update(r->freeze_model != 0, cap));
-      }
+      if (shape.replay)
+        for (; gsteps >= 2 && s + gsteps <= n; s += gsteps) CAL_TRY(replay_steps(shape, r->freeze_model != 0, cap, gsteps));
+      for (; s < n; ++s) CAL_TRY(enqueue_step(shape, r->freeze_model != 0, cap));
       issued += n;
       const int prc = pull_state();
       if (mark) roctx().pop();
@@ -1760,9 +1645,7 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     CAL_TRY(model_buf.reserve(2 * rowbytes));
     begin_pass_state();
     CAL_TRY(push_state());
-    FusedArgs<T> a = fused_args();
-    a.model_r = model_buf.as<T>();
-    a.model_i = model_buf.as<T>() + (size_t)nbls * fpad;
+    const FusedArgs<T> a = model_args();
     launch_fused<MODE_MODEL>(a, false);
     if (with_gains)
       hipLaunchKernelGGL(apply_gains_kernel<T>, dim3(grid_for((long long)nbls * fpad)), dim3(256), 0, stream, a.model_r, a.model_i, gains.as<T2>(),
@@ -1791,9 +1674,7 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     const std::vector<DevState> saved(h_state, h_state + nslices);
     begin_pass_state();
     CAL_TRY(push_state());
-    FusedArgs<T> a = fused_args();
-    a.model_r = model_buf.as<T>();
-    a.model_i = model_buf.as<T>() + plane;
+    const FusedArgs<T> a = model_args();
     launch_fused<MODE_MODEL>(a, false);
     rows(a.model_r, a.model_i, planes == 3 ? model_buf.as<T>() + 2 * plane : nullptr);
     HIP_TRY(hipGetLastError());
@@ -2136,7 +2017,7 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
   }
   // the gradient pass on the data planes as they stand; dst (may be null): the flat copy of the four planes
   int gn_grad_pass(T* dst) {
-    CAL_TRY(enqueue_pass(true, false, 0));
+    CAL_TRY(enqueue_pass(step_shape(kGradPass), 0));
     if (dst) {
       HIP_TRY(hipMemcpyAsync(dst, comm.p, gn_go() * sizeof(T), hipMemcpyDeviceToDevice, stream));
       HIP_TRY(hipMemcpyAsync(dst + gn_go(), grad_c0(), 2 * (size_t)ncoef * sizeof(T), hipMemcpyDeviceToDevice, stream));
@@ -2290,7 +2171,7 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
       HIP_TRY(hipMemcpyAsync(gn_save.as<T>() + gn_go(), coef.p, 2 * (size_t)ncoef * sizeof(T), hipMemcpyDeviceToDevice, stream));
       hipLaunchKernelGGL(gn_apply_kernel<T>, vgrid, dim3(256), 0, stream, S, mask, x, gains.as<T>(), coef.as<T>());
       HIP_TRY(hipGetLastError());
-      CAL_TRY(enqueue_pass(false, false, 0));
+      CAL_TRY(enqueue_pass(step_shape(kLossPass), 0));
       HIP_TRY(hipMemcpyAsync(sc.data(), scal_d, sc.size() * sizeof(GnScal), hipMemcpyDeviceToHost, stream));
       CAL_TRY(pull_state());
       std::vector<uint8_t> rejected(nslices, 0);
@@ -2630,10 +2511,7 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     a.data_r = s_r;
     a.data_i = s_i;
     launch_fused<MODE_INIT>(a, false);
-    if (!gc_direct)
-      hipLaunchKernelGGL(coeff_partial_reduce_kernel<T>, dim3((ncoef + 255) / 256), dim3(256), 0, stream, gcp0.as<T>(),
-                         gcp0.as<T>() + gcp_len, gc0.as<T>(), gc0.as<T>() + ncoef, coef_grp.as<int>(), grp_coff.as<int>(),
-                         grp_item_ptr.as<int>(), item_goff.as<int>(), ncoef, st_cur(), smap(false));
+    if (!gc_direct) launch_partial_reduce(gcp0, gc0, smap(false));
     HIP_TRY(hipGetLastError());
     // A^T b becomes the coefficient vector (orthonormal-column bases; the host applies the Gram solve otherwise)
     HIP_TRY(hipMemcpyAsync(coef.p, grad_c0(), 2 * (size_t)ncoef * sizeof(T), hipMemcpyDeviceToDevice, stream));
@@ -2885,6 +2763,12 @@ int cal_debug_solve_plan(int dtype, const cal_problem_desc* d, int64_t scratch_b
   if (scratch_bytes < 0) return fail(CAL_ERR_INVALID, "cal_debug_solve_plan: negative bound");
   const int64_t bound = scratch_bytes == 0 ? kCsScratchDefault : scratch_bytes;  // as in set_coeff_solve_scratch
   return dtype == CAL_F32 ? debug_solve_plan<float>(d, bound, what, out, cap_bytes, bytes) : debug_solve_plan<double>(d, bound, what, out, cap_bytes, bytes);
+}
+
+int cal_debug_step_shape(const int32_t* inputs, int32_t* shape) {
+  if (!inputs || !shape || inputs[7] < CAL_LAUNCH_AUTO || inputs[7] > CAL_LAUNCH_GRAPH) return fail(CAL_ERR_INVALID, "cal_debug_step_shape: bad argument");
+  step_shape_to(plan_step(step_inputs_from(inputs)), shape);
+  return CAL_OK;
 }
 
 int cal_device_count(int* count) {

@@ -214,6 +214,17 @@ int cal_debug_plan(int dtype, const cal_problem_desc* d, int what, void* out, in
  *   (vectors of the frequency basis, of the time basis, times; nants must be a multiple of T); on return int64 rows per chunk, in_lds,
  *   the Cholesky launch's LDS bytes, unknowns per row, elements per row of M and N (dtype) and of the double scratch. */
 int cal_debug_solve_plan(int dtype, const cal_problem_desc* d, int64_t scratch_bytes, int what, void* out, int64_t cap_bytes, int64_t* bytes);
+/* Host only, like cal_debug_plan: the shape of one pass or train step (csrc/step_plan.hpp) -- which kernels follow the fused or dense pass,
+ * the form of the update, whether a run replays its steps from a graph.  For tests (tests/test_step_plan_host.py).
+ * inputs, 14 int32 (flags 0 / 1 but [7]): the dense path serves the pass, the regulariser is "sum", the regularised gradient pass needs the
+ *   loss pre-pass, every group is one item (gc_direct), a communicator or exchange hook is set, a gain basis is set, 2 nants fpad + 2 ncoef
+ *   <= 2^20, [7] the cal_launch_mode, the optimizer is LAMB, the pass is asked for gradients, for the update, for the projection on the gain
+ *   basis, kernel timing is on, the run has at least 256 steps.  Every combination has a shape (CAL_ERR_INVALID: a null, an unknown mode).
+ * shape, 13 int32: the general kernels' two-adjoint-set regulariser, the dense two-pass form, the general alpha pre-pass, step_tail_kernel
+ *   behind the pass, step_update_kernel, coeff_partial_reduce_kernel runs, finalize_kernel runs, gain-gradient planes (1 or 3), the planes
+ *   are projected, the update (0 none, 1 tail, 2 fused, 3 LAMB, 4 adam2), the gains are expanded from y afterwards, the steps are replayed
+ *   from a graph, the pass leaves per-item partials of the coefficient gradient. */
+int cal_debug_step_shape(const int32_t* inputs, int32_t* shape);
 int cal_device_info(int device, char* name, size_t name_len, int64_t* total_mem_bytes, int32_t* compute_units);
 /* Measured streaming peaks of the device (no reference counterpart; BASELINE.md section 3 asks for the roofline against a
  * stream kernel measured on the box next to the nominal 8 TB/s): a read-only sweep (16-byte non-temporal loads, the

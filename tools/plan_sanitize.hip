@@ -1,11 +1,13 @@
-// plan_sanitize.hip -- the set-up planner (calamity_amd/csrc/problem_plan.hpp) and the planner of the closed-form calls
-// (calamity_amd/csrc/solve_plan.hpp) under the host sanitizers, with no device and no interpreter: four problems built in code (folded
-// STREAM, heads of baselines that share tiles, forced dense, multi-baseline runs), planned for fp32 and fp64; the closed-form plans at
-// the default scratch bound and at a bound of 1 byte.  Exits non-zero on a planner error; the sanitizers abort on a finding.
+// plan_sanitize.hip -- the set-up planner (calamity_amd/csrc/problem_plan.hpp), the planner of the closed-form calls
+// (calamity_amd/csrc/solve_plan.hpp) and the step's shape (calamity_amd/csrc/step_plan.hpp) under the host sanitizers, with no device and
+// no interpreter: four problems built in code (folded STREAM, heads of baselines that share tiles, forced dense, multi-baseline runs),
+// planned for fp32 and fp64; the closed-form plans at the default scratch bound and at a bound of 1 byte; plan_step over its whole input
+// table.  Exits non-zero on a planner error or an inconsistent plan; the sanitizers abort on a finding.
 //
 //   hipcc --offload-arch=gfx950 -std=c++17 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
 //         -o plan_sanitize tools/plan_sanitize.hip && ./plan_sanitize
 #include "../calamity_amd/csrc/solve_plan.hpp"
+#include "../calamity_amd/csrc/step_plan.hpp"
 
 #include <cstdint>
 
@@ -91,6 +93,26 @@ int run(const Case& c) {
   return bad ? 1 : 0;
 }
 
+// plan_step over every combination of its inputs (2^13 flag settings x 4 launch modes), through the layouts of cal_debug_step_shape:
+// the loop bookkeeping and the partial coefficient-gradient sums of a step happen exactly once
+int walk_step_shapes() {
+  int bad = 0, replays = 0, tails = 0;
+  for (int mode = CAL_LAUNCH_AUTO; mode <= CAL_LAUNCH_GRAPH; ++mode)
+    for (int bits = 0; bits < (1 << 13); ++bits) {
+      int32_t in[14], out[kStepShape];
+      for (int i = 0, k = 0; i < 14; ++i) in[i] = i == 7 ? mode : (bits >> k++) & 1;
+      const StepShape s = plan_step(step_inputs_from(in));
+      step_shape_to(s, out);
+      const bool own = s.update == UPDATE_FUSED || s.update == UPDATE_TAIL;
+      bad += s.finalize == own || (s.partial_reduce && own) || (s.update != UPDATE_NONE) != (in[10] != 0) || out[7] != (s.Rk ? 3 : 1) || out[9] != s.update;
+      replays += s.replay;
+      tails += s.tail1;
+    }
+  printf("step shapes   %d inputs: %d with the one-launch tail, %d replayed from a graph\n", 4 << 13, tails, replays);
+  if (bad) fprintf(stderr, "plan_step: %d inconsistent shapes\n", bad);
+  return bad ? 1 : 0;
+}
+
 std::vector<int> cycle(int n, int m) {
   std::vector<int> v(n);
   for (int i = 0; i < n; ++i) v[i] = i % m;
@@ -124,5 +146,6 @@ int main() {
   }
   int bad = 0;
   for (const Case& c : cases) bad += run<float>(c) + run<double>(c);
+  bad += walk_step_shapes();
   return bad ? 1 : 0;
 }
