@@ -129,6 +129,19 @@ class GaussNewtonResult(C.Structure):
     _fields_ = [("loss_before", C.c_double), ("loss_after", C.c_double), ("cg_residual", C.c_double), ("cg_iters", C.c_int32), ("accepted", C.c_int32)]
 
 
+class LbfgsDesc(C.Structure):
+    """cal_lbfgs_desc: ``nsteps`` iterations of L-BFGS with ``history`` stored pairs and a backtracking Armijo search of at most
+    ``max_ls`` trials (``c1``, ``shrink``); slice_mask [nslices] bytes or NULL (include/calamity_hip.h)."""
+    _fields_ = [("nsteps", C.c_int32), ("history", C.c_int32), ("max_ls", C.c_int32), ("freeze_model", C.c_int32), ("reset_moments", C.c_int32),
+                ("reserved", C.c_int32), ("c1", C.c_double), ("shrink", C.c_double), ("ftol", C.c_double), ("curvature_eps", C.c_double),
+                ("slice_mask", C.c_void_p)]
+
+
+class LbfgsResult(C.Structure):
+    _fields_ = [("loss_before", C.c_double), ("loss_after", C.c_double), ("iters", C.c_int32), ("evals", C.c_int32), ("pairs_dropped", C.c_int32),
+                ("status", C.c_int32)]
+
+
 class RunResult(C.Structure):
     _fields_ = [("nrecorded", C.c_int32), ("stopped", C.c_int32), ("nupdates", C.c_int32), ("nonfinite", C.c_int32)]
 
@@ -183,6 +196,8 @@ SYMBOLS = {
     "cal_solver_hold_slices": (C.c_int, [_P, _P]),
     "cal_solver_normal_product": (C.c_int, [_P] + [_P] * 8),
     "cal_solver_gauss_newton_step": (C.c_int, [_P, C.POINTER(GaussNewtonDesc), C.POINTER(GaussNewtonResult)]),
+    "cal_solver_lbfgs": (C.c_int, [_P, C.POINTER(LbfgsDesc), _P, C.POINTER(LbfgsResult)]),
+    "cal_debug_lbfgs_coefficients": (C.c_int, [C.c_int32, _P, _P, C.POINTER(C.c_double)]),
     "cal_solver_robust_weights": (C.c_int, [_P, C.POINTER(RobustDesc), _P, _P]),
     "cal_solver_get_weights": (C.c_int, [_P, _P, C.c_int]),
     "cal_solver_solve_coeffs": (C.c_int, [_P, C.POINTER(CoeffSolveDesc), C.POINTER(CoeffSolveResult)]),

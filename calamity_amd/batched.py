@@ -301,6 +301,15 @@ class SliceBatchFitter:
         scalars of conjugate gradients would need an exchange.  Returns the dict of per-slice arrays, the slices in global order."""
         return self._each(lambda r, s: s.gauss_newton_step(ncg=ncg, lam=lam, cg_tol=cg_tol, slice_mask=slice_mask, reset_moments=reset_moments))[0]
 
+    def lbfgs(self, nsteps, history=8, max_ls=20, c1=1e-4, shrink=0.5, ftol=0.0, curvature_eps=1e-8, slice_mask=None, freeze_model=False,
+              reset_moments=False):
+        """``HipFitSolver.lbfgs`` (``slice_mask``: one entry per slice of the batch; one entry for a ``joint`` fitter).  A slice's
+        iterations need the slice whole on one worker: with several workers (the fitting groups shared out) the library refuses the
+        call, since the dot products of the history would need an exchange.  Returns the dict of per-slice arrays and ``losses``, the
+        slices in global order."""
+        return self._each(lambda r, s: s.lbfgs(nsteps, history=history, max_ls=max_ls, c1=c1, shrink=shrink, ftol=ftol, curvature_eps=curvature_eps,
+                                               slice_mask=slice_mask, freeze_model=freeze_model, reset_moments=reset_moments))[0]
+
     def solve_gain_coeffs(self, nsweeps, damping=0.5, ridge=1e-6, slice_mask=None, reset_gain_moments=False):
         """``HipFitSolver.solve_gain_coeffs`` on every worker (``slice_mask``: one entry per slice of the batch).  With several workers
         each sweep sums the three antenna planes of the workers' baselines in one exchange; ``y`` is replicated, so every worker then

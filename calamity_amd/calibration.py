@@ -28,7 +28,8 @@ import threading
 import numpy as np
 
 from . import cal_utils, modeling, utils
-from .fit_loop import FitOptions, GaussNewtonOptions, drive, history_entry, newton_history
+from .fit_loop import FitOptions, GaussNewtonOptions, LbfgsOptions, drive, history_entry, newton_history
+from .fit_loop import lbfgs_history as _lbfgs_entry  # (``lbfgs_history`` is a keyword of the public calls)
 from .problem import FitProblem, coeffs_from_chunks, coeffs_to_chunks, problem_from_chunks
 from .solver import OPTIMIZERS, HipFitSolver
 from .utils import PBARS, echo
@@ -663,6 +664,11 @@ def fit_gains_and_foregrounds(
     gauss_newton_cg_iters=20,
     gauss_newton_lambda=1e-3,
     gauss_newton_cg_tol=1e-3,
+    lbfgs_steps=0,
+    lbfgs_every=0,
+    lbfgs_history=8,
+    lbfgs_max_ls=20,
+    lbfgs_ftol=0.0,
     **opt_kwargs,
 ):
     """Run the optimization loop that fits gains and foreground coefficients -- calibration.py:447-738.
@@ -687,12 +693,16 @@ def fit_gains_and_foregrounds(
     between chunks of the recorded loop, see ``calibrate_and_model_tensor``; here ``fit_history["robust"]`` holds the last reweight in
     solver units and row order, ``{"rounds": n, "ndown_bl": [nbls], "scale_bl": [nbls]}`` (``HipFitSolver.robust_weights``).
     ``gauss_newton_rounds`` / ``gauss_newton_every`` / ``gauss_newton_cg_iters`` / ``gauss_newton_lambda`` / ``gauss_newton_cg_tol``: joint
-    Gauss-Newton steps over gains and coefficients, see ``calibrate_and_model_tensor``.
+    Gauss-Newton steps over gains and coefficients, see ``calibrate_and_model_tensor``.  ``lbfgs_steps`` / ``lbfgs_every`` /
+    ``lbfgs_history`` / ``lbfgs_max_ls`` / ``lbfgs_ftol``: L-BFGS iterations over the optimizer's own variables (with a ``gain_basis``
+    its coefficients, with ``freeze_model`` the gains alone), see ``calibrate_and_model_tensor``; ``fit_history["lbfgs"]`` as there.
     """
     opts = FitOptions.pick(locals())
     opts.check(gain_basis is not None, False, freeze_model, use_min, robust_first=True)
     newton = GaussNewtonOptions.pick(locals())
     newton.check(opts, gain_basis is not None, False, freeze_model)
+    lbfgs = LbfgsOptions.pick(locals())
+    lbfgs.check(opts, newton)
     if gain_basis is not None:
         gain_basis = _check_gain_basis(gain_basis, np.asarray(g_r).shape[-1])
     echo(f"Using {str(dtype)} precision.")
@@ -723,11 +733,11 @@ def fit_gains_and_foregrounds(
         echo(f"{datetime.datetime.now()} Profiling with {n_profile_steps}. And writing output to {profile_log_dir}...")
     echo(f"{datetime.datetime.now()} Building Computational Graph...\n", verbose=verbose)
     echo(f"{datetime.datetime.now()} Performing Gradient Descent...\n", verbose=verbose)
-    ((losses, stopped, _),), nsingular, sweep_singular, robust, gn = drive(
-        solver, opts, 1, prob.nbls, maxsteps, tol, use_min, freeze_model, n_profile_steps, profile_log_dir, newton=newton)
+    ((losses, stopped, _),), nsingular, sweep_singular, robust, gn, lb = drive(
+        solver, opts, 1, prob.nbls, maxsteps, tol, use_min, freeze_model, n_profile_steps, profile_log_dir, newton=newton, lbfgs=lbfgs)
     if robust is not None:  # (solver units and row order: the documented shape of this function)
         robust = {"rounds": int(robust["rounds"][0]), "ndown_bl": robust["ndown_bl"], "scale_bl": robust["scale_bl"]}
-    fit_history = history_entry(opts, losses, dtype, nsingular, sweep_singular, robust, newton_history(gn, 0))
+    fit_history = history_entry(opts, losses, dtype, nsingular, sweep_singular, robust, newton_history(gn, 0), _lbfgs_entry(lb, 0))
     if stopped:
         echo(f"Tolerance thresshold met with delta of {np.abs(losses[-1] - losses[-2]):.2e}. Terminating...\n ", verbose=verbose)
     g_r_opt, g_i_opt, c_r, c_i = solver.get_params(which=1 if (use_min and len(losses) > 0) else 0)
@@ -971,6 +981,11 @@ def calibrate_and_model_tensor(
     gauss_newton_cg_iters=20,
     gauss_newton_lambda=1e-3,
     gauss_newton_cg_tol=1e-3,
+    lbfgs_steps=0,
+    lbfgs_every=0,
+    lbfgs_history=8,
+    lbfgs_max_ls=20,
+    lbfgs_ftol=0.0,
     fit_errors=False,
     fit_errors_ridge=1e-6,
     **opt_kwargs,
@@ -1134,6 +1149,18 @@ def calibrate_and_model_tensor(
       ``fit_history[polnum][time_index]["gauss_newton"] = {"steps", "accepted", "lambda", "loss", "cg_iters"}`` (present only with the
       feature on): the steps the slice took part in, how many were accepted, the damping a next step would use, and per step the
       loss after it and the iterations it ran.
+    * ``lbfgs_steps`` / ``lbfgs_every`` / ``lbfgs_history`` / ``lbfgs_max_ls`` / ``lbfgs_ftol`` (no counterpart in the reference): L-BFGS with
+      a backtracking Armijo line search over the optimizer's own variables (``HipFitSolver.lbfgs``): the gains -- with ``gain_basis`` /
+      ``gain_max_dly`` / ``gain_time_basis`` / ``gain_time_scale`` the basis coefficients -- and the foreground coefficients, or with
+      ``freeze_model`` the gains alone.  It needs only the loss and its gradient, so it is the curvature-aware move of the fits the
+      Gauss-Newton step refuses.  ``lbfgs_steps=N``: N iterations after the start-up rounds and the Gauss-Newton rounds, before the first
+      unrecorded descent step.  ``lbfgs_every=K`` (needs ``lbfgs_steps``): the recorded loop in chunks of K steps (one chunk length for every
+      ``*_every``) and N iterations last in every gap, on the slices still running, whose optimizer slots start over where they moved.
+      ``lbfgs_history`` stored pairs (1 .. 16), ``lbfgs_max_ls`` trials per line search, ``lbfgs_ftol``: a slice's iterations stop once
+      the loss falls by no more than this fraction (0: never).  Refused with several devices that share out the fitting groups
+      (``device_split="groups"`` or the automatic choice of it; ``device_split="slices"`` works).
+      ``fit_history[polnum][time_index]["lbfgs"] = {"calls", "iters", "evals", "loss", "status"}`` (present only with the feature on): the
+      calls the slice took part in, its iterations and trial losses over all of them, the loss after every call, the status of the last.
     * ``parallel_fits`` (default 1): with ``batch_slices=False``, fits that many slices concurrently, each on its own
       solver and HIP stream.
     (Nothing here is steered by environment variables: layout, devices and concurrency are arguments.)"""
@@ -1143,6 +1170,8 @@ def calibrate_and_model_tensor(
     opts.check(gain_basis is not None or gain_max_dly is not None, gain_time_basis is not None or gain_time_scale is not None, freeze_model, use_min)
     newton = GaussNewtonOptions.pick(locals())
     newton.check(opts, gain_basis is not None or gain_max_dly is not None, gain_time_basis is not None or gain_time_scale is not None, freeze_model)
+    lbfgs = LbfgsOptions.pick(locals())
+    lbfgs.check(opts, newton)
     if gain_max_dly is not None:
         gain_basis = modeling.gain_dpss_basis(np.asarray(uvdata.freq_array, dtype=np.float64).ravel(), gain_max_dly)
     if gain_time_basis is not None and gain_time_scale is not None:
@@ -1240,7 +1269,7 @@ def calibrate_and_model_tensor(
             verbose=verbose, max_batch=max_batch, devices=devices, layout=layout, opt_kwargs=opt_kwargs,
             correct_model=correct_model, correct_resid=correct_resid, device_split=device_split, gain_basis=gain_basis,
             gain_time_basis=gain_time_basis, fit_quality=fit_quality,
-            opts=opts, errs=errs, newton=newton,
+            opts=opts, errs=errs, newton=newton, lbfgs=lbfgs,
         )
         _file_gain_std(fit_history, errs, gains)
         return model, resid, gains, fit_history  # (every slice left _fit_slices_batched in its final state)
@@ -1302,7 +1331,7 @@ def calibrate_and_model_tensor(
                 notebook_progressbar=notebook_progressbar, verbose=verbose, tol=tol, dtype=dtype, maxsteps=maxsteps,
                 graph_mode=graph_mode, n_profile_steps=n_profile_steps, profile_log_dir=profile_log_dir,
                 sky_model_r=sky_model_r, sky_model_i=sky_model_i, model_regularization=model_regularization, gain_basis=gain_basis,
-                **dataclasses.asdict(opts), **dataclasses.asdict(newton), **opt_kwargs,
+                **dataclasses.asdict(opts), **dataclasses.asdict(newton), **dataclasses.asdict(lbfgs), **opt_kwargs,
             )
             if "robust" in hist:  # (solver units and row order -> the data's units, keyed by antenna numbers)
                 rb = hist["robust"]
@@ -1548,7 +1577,7 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
                         skip_threshold, use_model_snr_weights, optimizer, use_min, freeze_model, tol, maxsteps, n_profile_steps,
                         profile_log_dir, model_regularization, verbose, max_batch, devices, layout, opt_kwargs, correct_model=True,
                         correct_resid=False, device_split=None, gain_basis=None, gain_time_basis=None, fit_quality=False,
-                        opts=FitOptions(), errs=None, newton=GaussNewtonOptions()):
+                        opts=FitOptions(), errs=None, newton=GaussNewtonOptions(), lbfgs=LbfgsOptions()):
     """The pol x time loop of calibration.py:1160-1331 with the fits of all unskipped slices issued as batches: per slice
     exactly the host-side steps of the loop body (skip test :1173-1177, rms scale :1178-1182, tensorize :1184-1233, write-back
     :1271-1300, post-hoc renormalisation :1311-1319, residual and calibration state of the outputs :1322-1331), the gradient
@@ -1556,7 +1585,7 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
     resid and gains are complete when it returns.  ``gain_time_basis`` (``[len(times), L]``): the unskipped times of a polarization
     are one batch and one JOINT fit (one loop state, loss = the sum over the times; calibrate_and_model_tensor's docstring).
     ``opts``: the closed-form and robust keywords of calibrate_and_model_tensor (``fit_loop.FitOptions``); ``newton``: those of the
-    Gauss-Newton steps (``fit_loop.GaussNewtonOptions``)."""
+    Gauss-Newton steps (``fit_loop.GaussNewtonOptions``); ``lbfgs``: those of the L-BFGS iterations (``fit_loop.LbfgsOptions``)."""
     OPTIMIZERS[optimizer]  # unknown optimizer -> KeyError, like calibration.py:571
     dtype = np.dtype(dtype)
     layout = layout or "shared"
@@ -1666,9 +1695,9 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
         else:
             fitter.set_regularization(None)
         fitter.set_optimizer(optimizer, **opt_kwargs)
-        results, nsingular, sweep_singular, robust_out, gn = drive(
+        results, nsingular, sweep_singular, robust_out, gn, lb = drive(
             fitter, opts, 1 if joint else nt, nt * prob.nbls if joint else prob.nbls, maxsteps, tol, use_min, freeze_model,
-            n_profile_steps, profile_log_dir, dict(slices=nt), newton=newton)
+            n_profile_steps, profile_log_dir, dict(slices=nt), newton=newton, lbfgs=lbfgs)
         if joint:
             results = results * nt  # one loop, one loss history: every time of the fit reports it
         cur = fitter.get_params(0)
@@ -1696,7 +1725,7 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
             errors["chisq_bl"] = (quality if quality is not None else fitter.fit_quality(gm_r, gm_i))["chisq_bl"]
         echo(f"{datetime.datetime.now()} ... fitted.\n", verbose=verbose)
         return dict(results=results, m_r=m_r, m_i=m_i, gm_r=gm_r, gm_i=gm_i, quality=quality, nsingular=nsingular, robust=robust_out,
-                    sweep_singular=sweep_singular, errors=errors, newton=gn)
+                    sweep_singular=sweep_singular, errors=errors, newton=gn, lbfgs=lb)
 
     def post(batch, out):
         for t, (sl, res) in enumerate(zip(batch, out["results"])):
@@ -1707,7 +1736,8 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
             if rb is not None:
                 rb = robust_history(rb["rounds"][0 if joint else t], rb["ndown_bl"][rows], rb["scale_bl"][rows], sl["rmsdata"], prob, gains.ant_array)
             fit_history[sl["polnum"]][sl["time_index"]] = history_entry(opts, res[0], dtype, out["nsingular"], out["sweep_singular"], rb,
-                                                                        newton_history(out["newton"], t))
+                                                                        newton_history(out["newton"], t),
+                                                                        _lbfgs_entry(out["lbfgs"], 0 if joint else t))
             if out.get("quality") is not None:  # (before the post-hoc renormalisation, which leaves g_i conj(g_j) m as it is)
                 q = out["quality"]
                 insert_fit_quality(gains, fit_history[sl["polnum"]][sl["time_index"]], sl["time"], sl["pol"],
@@ -1740,6 +1770,7 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
     D = len(devices)
     newton.check(opts, gain_basis is not None, joint, freeze_model,
                  groups_split=D > 1 and not (device_split == "slices" or (device_split is None and len(batches) >= D)))
+    lbfgs.check(opts, newton, groups_split=D > 1 and not (device_split == "slices" or (device_split is None and len(batches) >= D)))
     if D > 1 and (device_split == "slices" or (device_split is None and len(batches) >= D)):
         # Whole batches on different devices: device d fits batches d, d + D, ... on a thread of its own (its solvers live on that
         # thread), nothing is exchanged between devices, and every slice is fitted exactly as it would be on one device.  One prep
@@ -2250,6 +2281,17 @@ def fitting_argparser():
                     help="initial Levenberg damping of a Gauss-Newton step (a tenth after an accepted step, ten times after a rejected one); default 1e-3")
     sp.add_argument("--gauss_newton_cg_tol", type=float, default=1e-3,
                     help="relative preconditioned residual at which the conjugate gradients of a step stop early; default 1e-3")
+    sp.add_argument("--lbfgs_steps", type=int, default=0,
+                    help="iterations of L-BFGS over the optimizer's own variables (gains or gain-basis coefficients, and the foreground "
+                         "coefficients unless the model is frozen) before the first descent step, after the start-up rounds and the "
+                         "Gauss-Newton rounds; works with --gain_max_dly, --gain_time_scale and a frozen model; default 0: none")
+    sp.add_argument("--lbfgs_every", type=int, default=0,
+                    help="with --lbfgs_steps: that many iterations again after every this many recorded descent steps, last in the gap; with "
+                         "another --*_every flag both must be equal; default 0: never")
+    sp.add_argument("--lbfgs_history", type=int, default=8, help="stored pairs of L-BFGS, 1 to 16; default 8")
+    sp.add_argument("--lbfgs_max_ls", type=int, default=20, help="trials of a backtracking line search of L-BFGS; default 20")
+    sp.add_argument("--lbfgs_ftol", type=float, default=0.0,
+                    help="a slice's L-BFGS iterations stop once the loss falls by no more than this fraction; default 0: never")
     return ap
 
 

@@ -10,6 +10,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -33,6 +34,7 @@
 #include "gain_basis_solve_kernels.hpp"
 #include "gain_time_solve_kernels.hpp"
 #include "gauss_newton_kernels.hpp"
+#include "lbfgs_kernels.hpp"
 #include "solve_plan.hpp"  // (and problem_plan.hpp)
 #include "step_plan.hpp"
 #include <cstdlib>
@@ -191,6 +193,7 @@ struct cal_solver {
   virtual int normal_product(const void* p_g_r, const void* p_g_i, const void* p_c_r, const void* p_c_i, void* out_g_r, void* out_g_i, void* out_c_r,
                              void* out_c_i) = 0;
   virtual int gauss_newton_step(const cal_gauss_newton_desc* d, cal_gauss_newton_result* res) = 0;
+  virtual int lbfgs(const cal_lbfgs_desc* d, double* losses_out, cal_lbfgs_result* res) = 0;
   virtual int solve_gain_time_coeffs(const cal_gain_time_solve_desc* d, cal_gain_time_solve_result* res) = 0;
   virtual int get_gain_coeff_moments(void* ym_r, void* ym_i, void* yv_r, void* yv_i, void* cm_r, void* cm_i, void* cv_r, void* cv_i, int64_t* t) = 0;
   virtual int init_coeffs(const void* sr, const void* si) = 0;
@@ -268,6 +271,9 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
   // they are substituted ([2][nbls][fpad] T each); gn_rows: the rows' sums (3 nbls doubles); the dot products' partials, the slices' scalars and
   // damping, the groups as gn_precond_coeff_kernel sees them, the first baseline row of every slice ([nslices + 1] ints)
   DevBuf gn_s, gn_g0, gn_save, gn_x, gn_res, gn_ns, gn_D, gn_m, gn_sd, gn_rows, gn_part, gn_scal, gn_lam, gn_grp, gn_rowptr;
+  // lbfgs (lbfgs_kernels.hpp): 2 history + 4 vectors of T over the variable space (the ring of history + 1 slots of (s, y), x_k, g_k), the
+  // dot products' block partials and sums, the slices' state, their recorded losses, the integer the host reads per trial round
+  DevBuf lb_vec, lb_part, lb_dots, lb_state, lb_losses, lb_count;
   DevBuf members, heads;                       // baselines that share tiles (bl_alias): member lists of the head items, head item indices
   bool heads_one_pass = false;                 // the regularised step of the heads in ONE pass (all of them on fused_multi_mfma_kernel<.., REG = 2>)
   bool reg_prepass = false;                    // the regularised gradient pass is preceded by a loss pass and the slices' alpha (enqueue_pass);
@@ -622,7 +628,8 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     CAL_TRY(upload(ant_ent, p.ant_ent));
 
     for (DevBuf* b : {&gains_snap, &gains_alt, &coef_snap, &q1, &gcp1, &gc1, &model_buf, &scratch, &fq_out, &fq_gains, &gs_out, &gs_ptr, &gs_ent, &gs_mask, &cs_rhs, &rw_w0, &rw_out,
-                       &gn_s, &gn_g0, &gn_save, &gn_x, &gn_res, &gn_ns, &gn_D, &gn_m, &gn_sd, &gn_rows, &gn_part, &gn_scal, &gn_lam, &gn_grp, &gn_rowptr})
+                       &gn_s, &gn_g0, &gn_save, &gn_x, &gn_res, &gn_ns, &gn_D, &gn_m, &gn_sd, &gn_rows, &gn_part, &gn_scal, &gn_lam, &gn_grp, &gn_rowptr,
+                       &lb_vec, &lb_part, &lb_dots, &lb_state, &lb_losses, &lb_count})
       b->release();
     // ---- state arrays
     const size_t rowbytes = (size_t)(nbls + 1) * fpad * sizeof(T);  // + one all-zero spare row (padding slots of the dense path)
@@ -2217,6 +2224,133 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     return CAL_OK;
   }
 
+  // ---- cal_solver_lbfgs (lbfgs_kernels.hpp) ------------------------------------------------------------------------
+  // L-BFGS over the optimizer's own variables (gain_set(): the gains or y; the coefficient planes): the gradient and the loss come from the
+  // passes every layout and kernel path already has, so a gain basis, a time gain basis and a frozen model all work.  The slices' scalars
+  // stay on the device; the host reads one integer per trial round of the line search (how many slices still search) and nothing else
+  // inside the loop.
+  int lbfgs(const cal_lbfgs_desc* d, double* losses_out, cal_lbfgs_result* res) override {
+    HIP_TRY(hipSetDevice(device));
+    if (!d || !res) return fail(CAL_ERR_INVALID, "lbfgs: null description or results");
+    if (d->nsteps < 1) return fail(CAL_ERR_INVALID, "lbfgs: nsteps = %d, at least one iteration", d->nsteps);
+    if (d->history < 1 || d->history > kLbfgsMaxHistory) return fail(CAL_ERR_INVALID, "lbfgs: history = %d is outside [1, %d]", d->history, kLbfgsMaxHistory);
+    if (d->max_ls < 1) return fail(CAL_ERR_INVALID, "lbfgs: max_ls = %d, at least one trial", d->max_ls);
+    if (!(d->c1 > 0.0 && d->c1 < 1.0)) return fail(CAL_ERR_INVALID, "lbfgs: c1 = %g is outside (0, 1)", d->c1);
+    if (!(d->shrink > 0.0 && d->shrink < 1.0)) return fail(CAL_ERR_INVALID, "lbfgs: shrink = %g is outside (0, 1)", d->shrink);
+    if (!(d->ftol >= 0.0) || !std::isfinite(d->ftol)) return fail(CAL_ERR_INVALID, "lbfgs: ftol = %g must be finite and >= 0", d->ftol);
+    if (!(d->curvature_eps >= 0.0) || !std::isfinite(d->curvature_eps))
+      return fail(CAL_ERR_INVALID, "lbfgs: curvature_eps = %g must be finite and >= 0", d->curvature_eps);
+    CAL_TRY(require_set("lbfgs", true));
+    if (comm_on())
+      return fail(CAL_ERR_UNSUPPORTED, "lbfgs: a communicator or exchange hook is set: the dot products of the history and the line search's scalars would "
+                  "need an exchange over the ranks, which is not implemented");
+    if (d->reset_moments && !has_opt) return fail(CAL_ERR_STATE, "lbfgs: reset_moments without an optimizer (cal_solver_set_optimizer)");
+    const bool frozen = d->freeze_model != 0;
+    const AdamSet<T> ga = gain_set();
+    const long long go = ga.n, np = go + 2LL * ncoef;
+    LbSpace S{};
+    S.coff = slice_coff.as<int>();
+    S.ngs = go / nslices;
+    S.go = go;
+    S.ncoef = ncoef;
+    S.w = yb_on() ? y_w() : fpad;
+    S.cols = yb_on() ? y_cols() : nfreqs;
+    S.freeze = frozen ? 1 : 0;
+    S.nslot = d->history + 1;
+    const LbParams P{d->nsteps, d->history, d->max_ls, d->c1, d->shrink, d->ftol, d->curvature_eps};
+    const size_t nloss = (size_t)nslices * (d->nsteps + 1);
+    CAL_TRY(lb_vec.reserve((size_t)(2 * S.nslot + 2) * np * sizeof(T)));
+    CAL_TRY(lb_part.reserve((size_t)nslices * kLbDots * kLbBlocks * sizeof(double)));
+    CAL_TRY(lb_dots.reserve((size_t)nslices * kLbDots * sizeof(double)));
+    CAL_TRY(lb_state.reserve((size_t)nslices * sizeof(LbState)));
+    CAL_TRY(lb_losses.reserve(nloss * sizeof(double)));
+    CAL_TRY(lb_count.reserve(sizeof(int)));
+    std::vector<LbState> hs(nslices);
+    for (int t = 0; t < nslices; ++t) {
+      std::memset(&hs[t], 0, sizeof(LbState));
+      if (d->slice_mask && !d->slice_mask[t]) {
+        hs[t].done = 1;
+        hs[t].status = 4;
+      }
+    }
+    std::vector<double> hl(nloss, std::numeric_limits<double>::quiet_NaN());
+    HIP_TRY(copy_sync(lb_state.p, hs.data(), hs.size() * sizeof(LbState), hipMemcpyHostToDevice));
+    HIP_TRY(copy_sync(lb_losses.p, hl.data(), nloss * sizeof(double), hipMemcpyHostToDevice));
+    constexpr int V = 16 / (int)sizeof(T);
+    const LbView<T> x{ga.p, coef.as<T>()};
+    const LbView<T> g{const_cast<T*>(ga.g), grad_c0()};
+    T* vec = lb_vec.as<T>();
+    LbState* st = lb_state.as<LbState>();
+    double *part = lb_part.as<double>(), *dots = lb_dots.as<double>(), *losses_d = lb_losses.as<double>();
+    const dim3 vgrid(kLbBlocks, nslices), rgrid(nslices, (kLbDots + 3) / 4);
+    const StepShape grad_shape = step_shape(yb_on() ? kProjectedGradPass : kGradPass), loss_shape = step_shape(kLossPass);
+    // the gradient pass at the point the solver holds, then the pair (or the start), the sums, the iteration's end and the next direction
+    auto advance = [&](int init) -> int {
+      CAL_TRY(enqueue_pass(grad_shape, 0));
+      hipLaunchKernelGGL(lbfgs_pair_kernel<T>, vgrid, dim3(256), 0, stream, S, x, g, vec, np, st, part, init);
+      hipLaunchKernelGGL(lbfgs_reduce_kernel<V>, rgrid, dim3(256), 0, stream, S, st, part, dots, init);
+      hipLaunchKernelGGL(lbfgs_coeff_kernel, dim3(nslices), dim3(64), 0, stream, st, dots, st_cur(), losses_d, P, init);
+      HIP_TRY(hipGetLastError());
+      return CAL_OK;
+    };
+    GnGuard G;
+    auto body = [&]() -> int {
+      CAL_TRY(advance(1));
+      for (int k = 0; k < d->nsteps; ++k) {
+        hipLaunchKernelGGL(lbfgs_direction_kernel<T>, vgrid, dim3(256), 0, stream, S, vec, np, st);
+        int n = 1;
+        // a search takes at most max_ls trials, twice where it starts over along the gradient
+        for (int r = 0; r < 2 * d->max_ls && n > 0; ++r) {
+          hipLaunchKernelGGL(lbfgs_trial_kernel<T>, vgrid, dim3(256), 0, stream, S, x, vec, np, st);
+          HIP_TRY(hipGetLastError());
+          if (yb_on()) CAL_TRY(enqueue_expand(gb_y.as<T2>(), gains.as<T2>()));
+          CAL_TRY(enqueue_pass(loss_shape, 0));
+          hipLaunchKernelGGL(lbfgs_armijo_kernel, dim3(1), dim3(256), 0, stream, st, st_cur(), nslices, P, lb_count.as<int>());
+          HIP_TRY(hipGetLastError());
+          HIP_TRY(hipMemcpyAsync(&n, lb_count.p, sizeof(int), hipMemcpyDeviceToHost, stream));  // the one readback of the loop
+          HIP_TRY(hipStreamSynchronize(stream));
+        }
+        if (n > 0) return fail(CAL_ERR_HIP, "lbfgs: the line search did not end within %d rounds", 2 * d->max_ls);
+        hipLaunchKernelGGL(lbfgs_restore_kernel<T>, vgrid, dim3(256), 0, stream, S, x, vec, np, st);
+        HIP_TRY(hipGetLastError());
+        if (yb_on()) CAL_TRY(enqueue_expand(gb_y.as<T2>(), gains.as<T2>()));
+        if (n < 0) break;  // every slice is done
+        CAL_TRY(advance(0));
+      }
+      HIP_TRY(hipMemcpyAsync(hs.data(), st, hs.size() * sizeof(LbState), hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipMemcpyAsync(hl.data(), losses_d, nloss * sizeof(double), hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipStreamSynchronize(stream));
+      if (d->reset_moments) {
+        // what set_optimizer leaves in the slots of the variables that moved
+        std::vector<uint8_t> moved(nslices);
+        for (int t = 0; t < nslices; ++t) moved[t] = hs[t].ever_moved ? 1 : 0;
+        const size_t ng = (size_t)S.ngs;
+        CAL_TRY(for_selected_slice_runs(moved.data(), [&](int t, int t1) {
+          CAL_TRY(reset_moment_slots(yb_on() ? gb_ym : gains_m, yb_on() ? gb_yv : gains_v, (size_t)t * ng, (size_t)(t1 - t) * ng));
+          const size_t n = frozen ? 0 : (size_t)(h_slice_coff[t1] - h_slice_coff[t]);
+          for (int plane = 0; plane < 2 && n > 0; ++plane) CAL_TRY(reset_moment_slots(coef_m, coef_v, (size_t)plane * ncoef + h_slice_coff[t], n));
+          return (int)CAL_OK;
+        }));
+        HIP_TRY(hipGetLastError());
+      }
+      return CAL_OK;
+    };
+    int rc = gn_begin(G);
+    if (rc == CAL_OK) rc = body();
+    CAL_TRY(gn_end(G, rc));
+    for (int t = 0; t < nslices; ++t) {
+      const double f0 = hs[t].status == 4 ? std::numeric_limits<double>::quiet_NaN() : hl[(size_t)t * (d->nsteps + 1)];
+      res[t].loss_before = hs[t].status == 3 ? std::numeric_limits<double>::quiet_NaN() : f0;
+      res[t].loss_after = hs[t].status >= 3 ? res[t].loss_before : hs[t].f;
+      res[t].iters = hs[t].iters;
+      res[t].evals = hs[t].evals;
+      res[t].pairs_dropped = hs[t].dropped;
+      res[t].status = hs[t].status;
+    }
+    if (losses_out) std::copy(hl.begin(), hl.end(), losses_out);
+    return CAL_OK;
+  }
+
   // ---- cal_solver_solve_coeffs ----------------------------------------------------------------------------------
   void release_coeff_solve() {  // the plan of a problem / a scratch bound: rebuilt by the next call
     cs_chunks.clear();
@@ -2950,6 +3084,16 @@ int cal_solver_normal_product(cal_solver* s, const void* p_g_r, const void* p_g_
   return s->normal_product(p_g_r, p_g_i, p_c_r, p_c_i, out_g_r, out_g_i, out_c_r, out_c_i);
 }
 int cal_solver_gauss_newton_step(cal_solver* s, const cal_gauss_newton_desc* desc, cal_gauss_newton_result* results) { NEED(s); return s->gauss_newton_step(desc, results); }
+int cal_solver_lbfgs(cal_solver* s, const cal_lbfgs_desc* desc, double* losses_out, cal_lbfgs_result* results) { NEED(s); return s->lbfgs(desc, losses_out, results); }
+int cal_debug_lbfgs_coefficients(int32_t npairs, const double* gram, double* delta, double* slope) {
+  if (npairs < 0 || npairs > kLbfgsMaxHistory) return fail(CAL_ERR_INVALID, "cal_debug_lbfgs_coefficients: npairs = %d is outside [0, %d]", npairs, kLbfgsMaxHistory);
+  if (!gram || !delta || !slope) return fail(CAL_ERR_INVALID, "cal_debug_lbfgs_coefficients: null pointer");
+  int idx[kLbfgsMaxBasis];
+  double alpha[kLbfgsMaxHistory];
+  for (int j = 0; j <= 2 * npairs; ++j) idx[j] = j;
+  *slope = lbfgs_two_loop(npairs, gram, 2 * npairs + 1, idx, delta, alpha);
+  return CAL_OK;
+}
 int cal_solver_solve_coeffs(cal_solver* s, const cal_coeff_solve_desc* desc, cal_coeff_solve_result* result) { NEED(s); return s->solve_coeffs(desc, result); }
 int cal_solver_set_coeff_solve_scratch(cal_solver* s, int64_t bytes) { NEED(s); return s->set_coeff_solve_scratch(bytes); }
 int cal_solver_fit_errors(cal_solver* s, double ridge, double* coeff_var, double* model_var, double* leverage_bl, double* nsamp_bl, double* gain_var,

@@ -15,7 +15,7 @@ instances of both dtypes), `gain_solve_rows_kernel`, `gain_solve_ant_kernel`,
 (coeff_solve_kernels.hpp), `gain_basis_gram_kernel`, `gain_basis_chol_kernel` (gain_basis_solve_kernels.hpp; both pairs are built on the
 shared Gram and Cholesky core of normal_solve.hpp), `gain_time_kron_kernel`, `gain_time_chol_kernel`, `gain_time_chan_kernel`
 (gain_time_solve_kernels.hpp), `fit_error_factor_kernel`, `fit_error_leverage_kernel`, `fit_error_rows_kernel` (fit_error_kernels.hpp), every `gn_*_kernel`
-(gauss_newton_kernels.hpp): no scratch, no spilled VGPRs."""
+(gauss_newton_kernels.hpp), every `lbfgs_*_kernel` (lbfgs_kernels.hpp): no scratch, no spilled VGPRs."""
 import re
 import sys
 
@@ -54,10 +54,11 @@ for line in sys.stdin:
                                              "gn_tangent_rows_kernel", "gn_scale_kernel", "gn_data_kernel", "gn_precond_rows_kernel", "gn_precond_gain_kernel",
                                              "gn_precond_coeff_kernel", "gn_rhs_kernel", "gn_init_kernel", "gn_scalar0_kernel", "gn_diff_kernel",
                                              "gn_scalar1_kernel", "gn_update1_kernel", "gn_scalar2_kernel", "gn_update2_kernel", "gn_apply_kernel",
-                                             "gn_round_kernel")):
+                                             "gn_round_kernel", "lbfgs_pair_kernel", "lbfgs_reduce_kernel", "lbfgs_coeff_kernel", "lbfgs_direction_kernel",
+                                             "lbfgs_trial_kernel", "lbfgs_armijo_kernel", "lbfgs_restore_kernel")):
         # the kernels around the update of a gain-basis fit, the two of the fit-quality pass, the one of the robust reweighting, the three of the gain solve, the three
-        # of the coefficient solve, the two of the gain-coefficient solve, the three of the time-basis solve, the three of the fit errors and those of the
-        # Gauss-Newton step keep their accumulators in registers: no scratch
+        # of the coefficient solve, the two of the gain-coefficient solve, the three of the time-basis solve, the three of the fit errors, those of the
+        # Gauss-Newton step and those of L-BFGS keep their accumulators in registers: no scratch
         m = re.search(r"remark:\s+(ScratchSize \[bytes/lane\]|VGPRs Spill): (\d+)", line)
         if m and int(m.group(2)) != 0:
             bad.append(f"{cur}: {m.group(1)} = {m.group(2)}")

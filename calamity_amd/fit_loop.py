@@ -1,5 +1,5 @@
 """The host loop of a fit, stated once: ``FitOptions`` holds the keywords of the closed-form solves and of the robust reweighting,
-``GaussNewtonOptions`` those of the joint Gauss-Newton steps, ``drive`` issues everything between ``set_optimizer`` and reading the parameters back, ``history_entry`` files what it returns.
+``GaussNewtonOptions`` those of the joint Gauss-Newton steps, ``LbfgsOptions`` those of the L-BFGS iterations, ``drive`` issues everything between ``set_optimizer`` and reading the parameters back, ``history_entry`` files what it returns.
 Host only: NumPy, never the library ("The host loop")."""
 import dataclasses
 import datetime
@@ -195,6 +195,53 @@ class GaussNewtonOptions:
                              "gain_time_solve_every / robust_every share the gaps of one chunked loop: give them the same value")
 
 
+@dataclasses.dataclass(frozen=True)
+class LbfgsOptions:
+    """The keywords of the L-BFGS iterations of ``calibrate_and_model_tensor`` / ``fit_gains_and_foregrounds`` (documented there),
+    under their public names and defaults."""
+    lbfgs_steps: int = 0
+    lbfgs_every: int = 0
+    lbfgs_history: int = 8
+    lbfgs_max_ls: int = 20
+    lbfgs_ftol: float = 0.0
+
+    @classmethod
+    def pick(cls, keywords):
+        """The options out of a mapping that holds them among others (a public function's ``locals()``)."""
+        return cls(**{f.name: keywords[f.name] for f in dataclasses.fields(cls)})
+
+    @property
+    def on(self):
+        return bool(self.lbfgs_steps or self.lbfgs_every)
+
+    def check(self, opts, newton=None, groups_split=False):
+        """``ValueError`` before any device work.  ``opts``: the call's ``FitOptions``, ``newton``: its ``GaussNewtonOptions`` (one chunk
+        length for every ``*_every``); ``groups_split``: several devices share out the fitting groups of a slice.  Gain bases and
+        ``freeze_model`` need no check: the iterations run on the optimizer's own variables."""
+        steps, every, history, max_ls = self.lbfgs_steps, self.lbfgs_every, self.lbfgs_history, self.lbfgs_max_ls
+        if not (_count(steps) and _count(every)):
+            raise ValueError(f"lbfgs_steps and lbfgs_every must be non-negative integers, got {steps!r} and {every!r}")
+        if not (_count(history) and 1 <= history <= 16):
+            raise ValueError(f"lbfgs_history must be an integer in [1, 16], got {history!r}")
+        if not (_count(max_ls) and max_ls >= 1):
+            raise ValueError(f"lbfgs_max_ls must be a positive integer, got {max_ls!r}")
+        if not _finite_nonneg(self.lbfgs_ftol):
+            raise ValueError(f"lbfgs_ftol must be finite and >= 0, got {self.lbfgs_ftol!r}")
+        if not self.on:
+            return
+        if every and not steps:
+            raise ValueError(f"lbfgs_every={every} says where the iterations run, lbfgs_steps how many: give lbfgs_steps >= 1 with it")
+        if groups_split:
+            raise ValueError("lbfgs_steps / lbfgs_every need every slice whole on one device: several devices that share out the fitting groups "
+                             "(device_split='groups', or too few batches for the devices) would have to exchange the dot products of the history, "
+                             "which is not implemented; device_split='slices' works")
+        others = [opts.chunk] + ([newton.gauss_newton_every] if newton is not None and newton.on else [])
+        for other in others:
+            if every and other and other != every:
+                raise ValueError(f"lbfgs_every={every} and the chunk length {other} of gain_solve_every / gain_basis_solve_every / "
+                                 "gain_time_solve_every / robust_every / gauss_newton_every share the gaps of one chunked loop: give them the same value")
+
+
 def next_lambda(lam, accepted):
     """The damping after a step: a tenth where the step was accepted, ten times ``max(lambda, 1e-6)`` where it was rejected."""
     lam = np.asarray(lam, dtype=np.float64)
@@ -202,7 +249,7 @@ def next_lambda(lam, accepted):
 
 
 def drive(fitter, opts, nl, rows_per_loop, maxsteps, tol, use_min, freeze_model, n_profile_steps=0, profile_log_dir="./logdir",
-          profile_extra=None, newton=None):
+          profile_extra=None, newton=None, lbfgs=None):
     """Everything between ``set_optimizer`` and reading the parameters back, on a ``SliceBatchFitter`` or a one-slice
     ``HipFitSolver``: the start-up rounds of closed-form solves, ``n_profile_steps`` profiled steps (their timings, with the keys of
     ``profile_extra``, as JSON into ``profile_log_dir``), the unrecorded step, the recorded loop.  ``nl``: the loops of the fitter (1 for
@@ -215,7 +262,12 @@ def drive(fitter, opts, nl, rows_per_loop, maxsteps, tol, use_min, freeze_model,
     loops not yet over and with the optimizer's slots of the accepted ones started over.  The damping is kept per loop (``next_lambda``);
     a rejected step is simply followed by the next one.  With ``newton`` given a fifth value is returned: ``None`` while it is off,
     else ``{"steps", "accepted": [nl], "lambda": [nl] (the damping a next step would use), "loss", "cg_iters": per loop the loss after and the
-    iterations of every step it took part in}``."""
+    iterations of every step it took part in}``.
+    ``lbfgs`` (``LbfgsOptions``): ``lbfgs_steps`` iterations of L-BFGS after the start-up rounds and the Gauss-Newton rounds, before the
+    profiled and unrecorded steps, and with ``lbfgs_every`` as many again last in every gap of the chunked loop, on the loops not yet
+    over and with the optimizer's slots of the loops that moved started over.  With ``lbfgs`` given one more value is appended: ``None``
+    while it is off, else ``{"calls", "iters", "evals": [nl], "loss": per loop the loss after every call it took part in, "status":
+    [nl] of its last call}``."""
     family = opts.family
     sweeps, every, damping, ridge = opts.sweep
 
@@ -254,6 +306,23 @@ def drive(fitter, opts, nl, rows_per_loop, maxsteps, tol, use_min, freeze_model,
     if gn is not None:
         for _ in range(newton.gauss_newton_rounds):
             newton_step(np.ones(nl, dtype=bool))
+    lb = None
+    if lbfgs is not None and lbfgs.on:
+        lb = dict(calls=np.zeros(nl, dtype=np.int64), iters=np.zeros(nl, dtype=np.int64), evals=np.zeros(nl, dtype=np.int64),
+                  loss=[[] for _ in range(nl)], status=np.full(nl, 4, dtype=np.int64))
+
+    def lbfgs_call(todo, **kw):
+        out = fitter.lbfgs(lbfgs.lbfgs_steps, history=lbfgs.lbfgs_history, max_ls=lbfgs.lbfgs_max_ls, ftol=lbfgs.lbfgs_ftol,
+                           freeze_model=freeze_model, **kw)
+        lb["calls"] += todo
+        lb["iters"] += np.where(todo, out["iters"], 0)
+        lb["evals"] += np.where(todo, out["evals"], 0)
+        lb["status"] = np.where(todo, out["status"], lb["status"])
+        for t in np.where(todo)[0]:
+            lb["loss"][t].append(float(out["loss_after"][t]))
+
+    if lb is not None and lbfgs.lbfgs_steps > 0:
+        lbfgs_call(np.ones(nl, dtype=bool))
     if n_profile_steps > 0:
         fitter.timing_enable(True)
         fitter.run_slices(n_profile_steps, record=False, freeze_model=freeze_model)
@@ -266,7 +335,7 @@ def drive(fitter, opts, nl, rows_per_loop, maxsteps, tol, use_min, freeze_model,
     robust = None
     if opts.robust_every > 0:  # per loop the reweights it took part in; per baseline row what its last one reported
         robust = dict(rounds=np.zeros(nl, dtype=np.int64), ndown_bl=np.zeros(nl * rows_per_loop), scale_bl=np.zeros(nl * rows_per_loop))
-    chunk = opts.chunk or (newton.gauss_newton_every if gn is not None else 0)
+    chunk = opts.chunk or (newton.gauss_newton_every if gn is not None else 0) or (lbfgs.lbfgs_every if lb is not None else 0)
     if chunk > 0:
         # the recorded loop in chunks (every loop's state -- step count, previous and lowest loss -- persists from run to run); a loop
         # that has ended is held in the chunks that follow, as one call would leave it, and takes no part in the gaps between them
@@ -295,12 +364,16 @@ def drive(fitter, opts, nl, rows_per_loop, maxsteps, tol, use_min, freeze_model,
                     last = sweep(max(1, sweeps), slice_mask=~over, reset_gain_moments=True)
                 if gn is not None and newton.gauss_newton_every > 0:
                     newton_step(~over, slice_mask=~over, reset_moments=True)
+                if lb is not None and lbfgs.lbfgs_every > 0:
+                    lbfgs_call(~over, slice_mask=~over, reset_moments=True)
         fitter.hold_slices(None)
         results = [(np.concatenate([np.zeros(0)] + parts[t]), bool(over[t]), int(nupd[t])) for t in range(nl)]
     else:
         results = fitter.run_slices(maxsteps, **run)
     out = (results, nsingular, (int(last or 0) if family in ("basis", "time") else None), robust)
-    return out if newton is None else out + (gn,)
+    if newton is not None:
+        out = out + (gn,)
+    return out if lbfgs is None else out + (lb,)
 
 
 def newton_history(gn, t):
@@ -311,9 +384,17 @@ def newton_history(gn, t):
             "cg_iters": list(gn["cg_iters"][t])}
 
 
-def history_entry(opts, losses, dtype, nsingular, sweep_singular, robust, newton=None):
-    """One slice's ``fit_history`` entry from what ``drive`` returned for it (``robust``, ``newton``: the entries as the caller reports
-    them, ``newton_history`` for the latter)."""
+def lbfgs_history(lb, t):
+    """Loop ``t``'s ``fit_history[...]["lbfgs"]`` from the value ``drive`` appends for ``lbfgs=`` (``None`` while the iterations are off)."""
+    if lb is None:
+        return None
+    return {"calls": int(lb["calls"][t]), "iters": int(lb["iters"][t]), "evals": int(lb["evals"][t]), "loss": list(lb["loss"][t]),
+            "status": int(lb["status"][t])}
+
+
+def history_entry(opts, losses, dtype, nsingular, sweep_singular, robust, newton=None, lbfgs=None):
+    """One slice's ``fit_history`` entry from what ``drive`` returned for it (``robust``, ``newton``, ``lbfgs``: the entries as the caller
+    reports them, ``newton_history`` and ``lbfgs_history`` for the latter two)."""
     hist = {"loss": [dtype.type(l) for l in losses]}
     if nsingular is not None:
         hist["coeff_solve_singular"] = int(nsingular)
@@ -323,4 +404,6 @@ def history_entry(opts, losses, dtype, nsingular, sweep_singular, robust, newton
         hist["robust"] = robust
     if newton is not None:
         hist["gauss_newton"] = newton
+    if lbfgs is not None:
+        hist["lbfgs"] = lbfgs
     return hist

@@ -469,6 +469,32 @@ class HipFitSolver:
                     cg_residual=np.asarray([r.cg_residual for r in res]), cg_iters=np.asarray([r.cg_iters for r in res], dtype=np.int64),
                     accepted=np.asarray([bool(r.accepted) for r in res]))
 
+    LBFGS_STATUS = {0: "nsteps", 1: "ftol", 2: "stalled", 3: "bad start", 4: "masked"}
+
+    def lbfgs(self, nsteps, history=8, max_ls=20, c1=1e-4, shrink=0.5, ftol=0.0, curvature_eps=1e-8, slice_mask=None, freeze_model=False,
+              reset_moments=False):
+        """``nsteps`` iterations of L-BFGS with a backtracking Armijo line search (cal_solver_lbfgs), every slice on its own, over the
+        optimizer's own variables: the gains -- with a frequency or time gain basis the coefficients ``y`` -- and the foreground
+        coefficients (``freeze_model``: the gains alone, the coefficients keep their bits).  It needs only the loss and its gradient,
+        so it runs where ``gauss_newton_step`` refuses: with gain bases and with a frozen model.  ``history`` in [1, 16] pairs; a trial
+        is accepted iff its loss (as ``eval_loss``, regulariser included) is finite and ``<= f + c1 t slope``, else ``t *= shrink``, at
+        most ``max_ls`` times; a pair enters the history iff ``s.y > curvature_eps sqrt(s.s y.y)``; a slice stops early once
+        ``ftol > 0`` and ``f_k - f_{k+1} <= ftol |f_k|``.  ``reset_moments``: the optimizer's slots of the variables of the slices
+        that moved start over as after ``set_optimizer``.  Nothing else the fit reads changes.  Not available under an exchange.
+        Returns a dict of per-slice arrays ``loss_before``, ``loss_after``, ``iters``, ``evals`` (trial losses), ``pairs_dropped``,
+        ``status`` (0 all iterations, 1 ``ftol``, 2 stalled: no trial accepted and the variables as they were, 3 the start's loss or
+        gradient not usable, 4 masked) and ``losses`` ``[nslices, nsteps + 1]``, NaN past ``iters``."""
+        m = self._slice_mask(slice_mask)
+        d = _lib.LbfgsDesc(int(nsteps), int(history), int(max_ls), int(bool(freeze_model)), int(bool(reset_moments)), 0, float(c1), float(shrink),
+                           float(ftol), float(curvature_eps), None if m is None else m.ctypes.data)
+        res = (_lib.LbfgsResult * self.nslices)()
+        losses = np.full((self.nslices, max(int(nsteps), 0) + 1), np.nan)
+        _lib.check(self._lib.cal_solver_lbfgs(self._h, C.byref(d), losses.ctypes.data, res))
+        return dict(loss_before=np.asarray([r.loss_before for r in res]), loss_after=np.asarray([r.loss_after for r in res]),
+                    iters=np.asarray([r.iters for r in res], dtype=np.int64), evals=np.asarray([r.evals for r in res], dtype=np.int64),
+                    pairs_dropped=np.asarray([r.pairs_dropped for r in res], dtype=np.int64),
+                    status=np.asarray([r.status for r in res], dtype=np.int64), losses=losses)
+
     def _set_coeff_solve_scratch(self, nbytes):
         """Scratch bound of ``solve_coeffs`` in bytes (0: the default); the results do not depend on it (tests)."""
         _lib.check(self._lib.cal_solver_set_coeff_solve_scratch(self._h, int(nbytes)))

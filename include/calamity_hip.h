@@ -437,6 +437,50 @@ typedef struct cal_gauss_newton_desc {
 } cal_gauss_newton_desc;
 typedef struct cal_gauss_newton_result { double loss_before, loss_after, cg_residual; int32_t cg_iters, accepted; } cal_gauss_newton_result;
 int cal_solver_gauss_newton_step(cal_solver* s, const cal_gauss_newton_desc* desc, cal_gauss_newton_result* results /* [nslices] */);
+/* Quasi-Newton fits (no counterpart in the reference): L-BFGS with a backtracking Armijo line search over the optimizer's own variables,
+ * per slice -- its gains (or, with a frequency or time gain basis, its rows of y) and its run of both coefficient planes; with freeze_model
+ * the gains alone.  It needs only what every layout and kernel path already produces, the loss and its gradient with respect to those
+ * variables, so gain bases and a frozen model are supported where cal_solver_gauss_newton_step refuses them.  Padding (channels past nfreqs,
+ * basis padding) takes part in no sum; the inner product is the real one over the (re, im) planes; the slices' scalars stay on the device in
+ * double and every sum runs in double in a fixed order (no atomics): two calls give the same bits, and a slice of a batch the bits of the
+ * same slice alone.
+ *   start       f_0, g_0 from one gradient pass.  f_0 not finite, or |g_0| zero or not finite: status 3, nothing is written.
+ *   direction   no stored pair: d = -g_k, t = min(1, 1 / |g_k|).  Else the two-loop recursion over the stored pairs with
+ *               gamma = s . y / y . y of the newest pair, t = 1.  slope = g_k . d; slope >= 0 or not finite: the pairs are dropped, d = -g_k.
+ *   search      at most max_ls trials x_k + t d (computed in double from the stored values, rounded once to the solver's dtype; with a
+ *               basis the gains are expanded from y), one loss pass each, regulariser included; accepted iff the trial loss is finite and
+ *               <= f_k + c1 t slope, else t *= shrink.  No trial accepted: with pairs stored they are dropped and the same iteration
+ *               searches again along -g_k (its trials count in evals); with none the slice gets the bits of x_k back, status 2.
+ *   pair        one gradient pass at the accepted point gives g_{k+1} and the recorded loss f_{k+1}; s = x_{k+1} - x_k, y = g_{k+1} - g_k
+ *               (stored in the solver's dtype) enter the ring of `history` pairs iff s . y is finite and > curvature_eps sqrt(s.s y.y).
+ *   stop        status 1 once ftol > 0 and f_k - f_{k+1} <= ftol |f_k|; status 0 after nsteps iterations; status 4: mask byte 0, never written.
+ * pairs_dropped counts the pairs the curvature test kept out and the pairs thrown away when a direction or a search failed.
+ * Passes: 1 + iters gradient passes and evals loss passes.  The host reads one integer per trial round (how many slices still search).
+ * Data, weights, w0, regulariser, loop state, t and any recorded step graph stay as found on every path out of the call; so do the moments
+ * unless reset_moments: then the slots of the variables of the slices that moved are what cal_solver_set_optimizer leaves.
+ * Device memory: 2 history + 4 vectors in the solver's dtype over the variable space (counted by cal_solver_memory_bytes).
+ *   CAL_ERR_INVALID: null desc or results, nsteps < 1, history outside [1, 16], max_ls < 1, c1 or shrink outside (0, 1), ftol or
+ *   curvature_eps negative or not finite.  CAL_ERR_STATE: problem, data, coefficients or gains not set; reset_moments without an optimizer.
+ *   CAL_ERR_UNSUPPORTED: a communicator or exchange hook is set (the dot products would need an exchange). */
+typedef struct cal_lbfgs_desc {
+  int32_t nsteps;            /* >= 1 iterations */
+  int32_t history;           /* 1 .. 16 stored pairs */
+  int32_t max_ls;            /* >= 1 trials per search */
+  int32_t freeze_model;      /* the coefficients are no variables and keep their bits */
+  int32_t reset_moments;
+  int32_t reserved;
+  double c1, shrink;         /* each in (0, 1) */
+  double ftol;               /* >= 0; 0: no loss test */
+  double curvature_eps;      /* >= 0 */
+  const uint8_t* slice_mask; /* [nslices] or NULL */
+} cal_lbfgs_desc;
+typedef struct cal_lbfgs_result { double loss_before, loss_after; int32_t iters, evals, pairs_dropped, status; } cal_lbfgs_result;
+int cal_solver_lbfgs(cal_solver* s, const cal_lbfgs_desc* desc, double* losses_out /* [nslices][nsteps + 1], NaN past iters, may be NULL */,
+                     cal_lbfgs_result* results /* [nslices] */);
+/* Host only, no device: the coefficients of the L-BFGS direction from the Gram matrix gram [2 npairs + 1][2 npairs + 1] of
+ * b = [s_1 .. s_p (oldest first), y_1 .. y_p, g]: delta [2 npairs + 1] with d = sum_j delta_j b_j, and *slope = g . d.  The function the
+ * device runs (lbfgs_core.hpp).  npairs in [0, 16]. */
+int cal_debug_lbfgs_coefficients(int32_t npairs, const double* gram, double* delta, double* slope);
 /* The foreground coefficients in closed form (no counterpart in the reference): the other half of alternating least squares next to
  * cal_solver_solve_gains.  With the gains held fixed the chi-square sum w |d - g_i conj(g_j) (A c)|^2 is linear least squares in the
  * coefficients and separates by fitting group.  Group gamma has nvec complex coefficients c; its baselines b have antennas (i, j) and

@@ -1,13 +1,14 @@
 // plan_sanitize.hip -- the set-up planner (calamity_amd/csrc/problem_plan.hpp), the planner of the closed-form calls
-// (calamity_amd/csrc/solve_plan.hpp) and the step's shape (calamity_amd/csrc/step_plan.hpp) under the host sanitizers, with no device and
-// no interpreter: four problems built in code (folded STREAM, heads of baselines that share tiles, forced dense, multi-baseline runs),
+// (calamity_amd/csrc/solve_plan.hpp), the step's shape (calamity_amd/csrc/step_plan.hpp) and the two-loop recursion of L-BFGS on
+// coefficients (calamity_amd/csrc/lbfgs_core.hpp) under the host sanitizers, with no device and no interpreter: four problems built in code (folded STREAM, heads of baselines that share tiles, forced dense, multi-baseline runs),
 // planned for fp32 and fp64; the closed-form plans at the default scratch bound and at a bound of 1 byte; plan_step over its whole input
-// table.  Exits non-zero on a planner error or an inconsistent plan; the sanitizers abort on a finding.
+// table; lbfgs_two_loop on Gram matrices of 0 .. 16 pairs held in arrays of exactly the sizes it may touch.  Exits non-zero on a planner error or an inconsistent plan; the sanitizers abort on a finding.
 //
 //   hipcc --offload-arch=gfx950 -std=c++17 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
 //         -o plan_sanitize tools/plan_sanitize.hip && ./plan_sanitize
 #include "../calamity_amd/csrc/solve_plan.hpp"
 #include "../calamity_amd/csrc/step_plan.hpp"
+#include "../calamity_amd/csrc/lbfgs_core.hpp"
 
 #include <cstdint>
 
@@ -113,6 +114,53 @@ int walk_step_shapes() {
   return bad ? 1 : 0;
 }
 
+// lbfgs_two_loop for p = 0 .. kLbfgsMaxHistory pairs of positive curvature (y = H s, H diagonal and positive) in dimension 40, the vectors
+// held in a permuted order behind idx: every array has exactly the size the function may touch, the slope must be finite and negative,
+// and d = sum delta_j b_j must give that slope again
+int walk_lbfgs() {
+  int bad = 0;
+  uint32_t seed = 777u;
+  auto rnd = [&]() {
+    seed = seed * 1664525u + 1013904223u;
+    return (seed >> 8) * (1.0 / 16777216.0) - 0.5;
+  };
+  const int dim = 40;
+  for (int p = 0; p <= calk::kLbfgsMaxHistory; ++p) {
+    const int n = 2 * p + 1;
+    std::vector<std::vector<double>> b(n, std::vector<double>(dim));
+    std::vector<double> h(dim);
+    for (double& x : h) x = 0.5 + (rnd() + 0.5);
+    for (int i = 0; i < p; ++i)
+      for (int k = 0; k < dim; ++k) {
+        b[i][k] = rnd();
+        b[p + i][k] = h[k] * b[i][k];
+      }
+    for (int k = 0; k < dim; ++k) b[2 * p][k] = rnd();
+    std::vector<int> idx(n);
+    for (int j = 0; j < n; ++j) idx[j] = (j * 7 + 3) % n;  // a permutation: gcd(7, n) = 1 for every odd n <= 33 but 7 and 21 ...
+    if (n % 7 == 0)
+      for (int j = 0; j < n; ++j) idx[j] = n - 1 - j;        // ... which get the reversal
+    std::vector<double> gram((size_t)n * n), delta(n), alpha(p);
+    for (int i = 0; i < n; ++i)
+      for (int j = 0; j < n; ++j) {
+        double acc = 0;
+        for (int k = 0; k < dim; ++k) acc += b[i][k] * b[j][k];
+        gram[(size_t)idx[i] * n + idx[j]] = acc;
+      }
+    const double slope = calk::lbfgs_two_loop(p, gram.data(), n, idx.data(), delta.data(), alpha.data());
+    double again = 0;
+    for (int k = 0; k < dim; ++k) {
+      double d = 0;
+      for (int j = 0; j < n; ++j) d += delta[j] * b[j][k];
+      again += d * b[2 * p][k];
+    }
+    bad += !(slope < 0.0) || !std::isfinite(slope) || std::fabs(again - slope) > 1e-10 * std::fabs(slope);
+  }
+  printf("lbfgs         0 .. %d pairs: the slopes are negative and those of the combined vectors\n", calk::kLbfgsMaxHistory);
+  if (bad) fprintf(stderr, "lbfgs_two_loop: %d inconsistent directions\n", bad);
+  return bad ? 1 : 0;
+}
+
 std::vector<int> cycle(int n, int m) {
   std::vector<int> v(n);
   for (int i = 0; i < n; ++i) v[i] = i % m;
@@ -147,5 +195,6 @@ int main() {
   int bad = 0;
   for (const Case& c : cases) bad += run<float>(c) + run<double>(c);
   bad += walk_step_shapes();
+  bad += walk_lbfgs();
   return bad ? 1 : 0;
 }
