@@ -20,7 +20,6 @@ import argparse
 import collections
 import concurrent.futures
 import copy
-import dataclasses
 import datetime
 import os
 import threading
@@ -28,8 +27,7 @@ import threading
 import numpy as np
 
 from . import cal_utils, modeling, utils
-from .fit_loop import FitOptions, GaussNewtonOptions, LbfgsOptions, drive, history_entry, newton_history
-from .fit_loop import lbfgs_history as _lbfgs_entry  # (``lbfgs_history`` is a keyword of the public calls)
+from .fit_loop import KEYWORD_HELP, FitControls, drive, history_entry
 from .problem import FitProblem, coeffs_from_chunks, coeffs_to_chunks, problem_from_chunks
 from .solver import OPTIMIZERS, HipFitSolver
 from .utils import PBARS, echo
@@ -697,12 +695,8 @@ def fit_gains_and_foregrounds(
     ``lbfgs_history`` / ``lbfgs_max_ls`` / ``lbfgs_ftol``: L-BFGS iterations over the optimizer's own variables (with a ``gain_basis``
     its coefficients, with ``freeze_model`` the gains alone), see ``calibrate_and_model_tensor``; ``fit_history["lbfgs"]`` as there.
     """
-    opts = FitOptions.pick(locals())
-    opts.check(gain_basis is not None, False, freeze_model, use_min, robust_first=True)
-    newton = GaussNewtonOptions.pick(locals())
-    newton.check(opts, gain_basis is not None, False, freeze_model)
-    lbfgs = LbfgsOptions.pick(locals())
-    lbfgs.check(opts, newton)
+    controls = FitControls.pick(locals())
+    controls.check(gain_basis is not None, False, freeze_model, use_min, robust_first=True)
     if gain_basis is not None:
         gain_basis = _check_gain_basis(gain_basis, np.asarray(g_r).shape[-1])
     echo(f"Using {str(dtype)} precision.")
@@ -733,11 +727,9 @@ def fit_gains_and_foregrounds(
         echo(f"{datetime.datetime.now()} Profiling with {n_profile_steps}. And writing output to {profile_log_dir}...")
     echo(f"{datetime.datetime.now()} Building Computational Graph...\n", verbose=verbose)
     echo(f"{datetime.datetime.now()} Performing Gradient Descent...\n", verbose=verbose)
-    ((losses, stopped, _),), nsingular, sweep_singular, robust, gn, lb = drive(
-        solver, opts, 1, prob.nbls, maxsteps, tol, use_min, freeze_model, n_profile_steps, profile_log_dir, newton=newton, lbfgs=lbfgs)
-    if robust is not None:  # (solver units and row order: the documented shape of this function)
-        robust = {"rounds": int(robust["rounds"][0]), "ndown_bl": robust["ndown_bl"], "scale_bl": robust["scale_bl"]}
-    fit_history = history_entry(opts, losses, dtype, nsingular, sweep_singular, robust, newton_history(gn, 0), _lbfgs_entry(lb, 0))
+    result = drive(solver, controls, 1, prob.nbls, maxsteps, tol, use_min, freeze_model, n_profile_steps, profile_log_dir)
+    ((losses, stopped, _),) = result.loops
+    fit_history = history_entry(controls, result, 0, dtype)  # (the reweighting in solver units and row order: the documented shape of this function)
     if stopped:
         echo(f"Tolerance thresshold met with delta of {np.abs(losses[-1] - losses[-2]):.2e}. Terminating...\n ", verbose=verbose)
     g_r_opt, g_i_opt, c_r, c_i = solver.get_params(which=1 if (use_min and len(losses) > 0) else 0)
@@ -917,6 +909,20 @@ def insert_fit_quality(uvcal, hist, time, polarization, q, rms, prob):
     (tot[0] if np.ndim(tot) == 4 else tot)[:, gindt, polnum] = total
     ants = np.asarray(uvcal.ant_array)
     hist["chisq_per_baseline"] = {(int(ants[i]), int(ants[j])): float(v) for i, j, v in zip(prob.bl_ant0, prob.bl_ant1, per_bl)}
+
+
+def _report_slice(hist, gains, time, polarization, rms, prob, quality, errors, errs):
+    """What one fitted (polarization, time) slice reports besides its losses, for the loop over the slices and for the batches alike:
+    ``hist["robust"]`` from solver units and row order into the data's units, keyed by antenna numbers (``robust_history``); the slice's
+    ``quality`` (``fit_quality``) and ``errors`` (``fit_errors``, with the slice's ``chisq_bl`` among them) where they were asked for
+    (``insert_fit_quality``, ``insert_fit_errors``).  ``errs``: the call's fit-errors settings."""
+    if "robust" in hist:
+        rb = hist["robust"]
+        hist["robust"] = robust_history(rb["rounds"], rb["ndown_bl"], rb["scale_bl"], rms, prob, gains.ant_array)
+    if quality is not None:
+        insert_fit_quality(gains, hist, time, polarization, quality, rms, prob)
+    if errors is not None:
+        insert_fit_errors(errs["gain_std"], gains, hist, time, polarization, errors, errors["chisq_bl"], rms, prob)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -1166,12 +1172,8 @@ def calibrate_and_model_tensor(
     (Nothing here is steered by environment variables: layout, devices and concurrency are arguments.)"""
     if gain_basis is not None and gain_max_dly is not None:
         raise ValueError("give gain_basis or gain_max_dly, not both")
-    opts = FitOptions.pick(locals())
-    opts.check(gain_basis is not None or gain_max_dly is not None, gain_time_basis is not None or gain_time_scale is not None, freeze_model, use_min)
-    newton = GaussNewtonOptions.pick(locals())
-    newton.check(opts, gain_basis is not None or gain_max_dly is not None, gain_time_basis is not None or gain_time_scale is not None, freeze_model)
-    lbfgs = LbfgsOptions.pick(locals())
-    lbfgs.check(opts, newton)
+    controls = FitControls.pick(locals())
+    controls.check(gain_basis is not None or gain_max_dly is not None, gain_time_basis is not None or gain_time_scale is not None, freeze_model, use_min)
     if gain_max_dly is not None:
         gain_basis = modeling.gain_dpss_basis(np.asarray(uvdata.freq_array, dtype=np.float64).ravel(), gain_max_dly)
     if gain_time_basis is not None and gain_time_scale is not None:
@@ -1269,7 +1271,7 @@ def calibrate_and_model_tensor(
             verbose=verbose, max_batch=max_batch, devices=devices, layout=layout, opt_kwargs=opt_kwargs,
             correct_model=correct_model, correct_resid=correct_resid, device_split=device_split, gain_basis=gain_basis,
             gain_time_basis=gain_time_basis, fit_quality=fit_quality,
-            opts=opts, errs=errs, newton=newton, lbfgs=lbfgs,
+            controls=controls, errs=errs,
         )
         _file_gain_std(fit_history, errs, gains)
         return model, resid, gains, fit_history  # (every slice left _fit_slices_batched in its final state)
@@ -1331,23 +1333,22 @@ def calibrate_and_model_tensor(
                 notebook_progressbar=notebook_progressbar, verbose=verbose, tol=tol, dtype=dtype, maxsteps=maxsteps,
                 graph_mode=graph_mode, n_profile_steps=n_profile_steps, profile_log_dir=profile_log_dir,
                 sky_model_r=sky_model_r, sky_model_i=sky_model_i, model_regularization=model_regularization, gain_basis=gain_basis,
-                **dataclasses.asdict(opts), **dataclasses.asdict(newton), **dataclasses.asdict(lbfgs), **opt_kwargs,
+                **controls.keywords(), **opt_kwargs,
             )
-            if "robust" in hist:  # (solver units and row order -> the data's units, keyed by antenna numbers)
-                rb = hist["robust"]
-                hist["robust"] = robust_history(rb["rounds"], rb["ndown_bl"], rb["scale_bl"], rmsdata, prob, gains.ant_array)
             # yield_fg_model_array x 2 + insert_model_into_uvdata_tensor (calibration.py:1271-1292) without the
             # nants x nants cubes: one A c pass for both components, rows written straight back
             solver.set_params(c_r=coeffs_from_chunks(prob, fg_r), c_i=coeffs_from_chunks(prob, fg_i))
             m_r, m_i = solver.model()
             _insert_model_rows(model, time, pol, ants_map, prob, m_r, m_i, scale_factor=rmsdata)
             insert_gains_into_uvcal(uvcal=gains, time=time, polarization=pol, gains_re=g_r, gains_im=g_i)
-            if fit_quality:  # at the reported parameters, on the data and weights the fit used (the solver still holds them)
-                insert_fit_quality(gains, hist, time, pol, solver.fit_quality(g_r, g_i), rmsdata, prob)
+            # at the reported parameters, on the data and weights the fit used (the solver still holds them)
+            quality = solver.fit_quality(g_r, g_i) if fit_quality else None
+            errors = None
             if errs is not None and (errs["with_gains"] or not freeze_model):
                 solver.set_params(g_r, g_i)  # the reported gains (use_min: the minimum's); the fit is over, the next one sets its own
-                e = solver.fit_errors(ridge=errs["ridge"], model_var=errs["samples"], gain_var=errs["with_gains"], coeffs=not freeze_model)
-                insert_fit_errors(errs["gain_std"], gains, hist, time, pol, e, solver.fit_quality(g_r, g_i)["chisq_bl"], rmsdata, prob)
+                errors = solver.fit_errors(ridge=errs["ridge"], model_var=errs["samples"], gain_var=errs["with_gains"], coeffs=not freeze_model)
+                errors["chisq_bl"] = solver.fit_quality(g_r, g_i)["chisq_bl"]
+            _report_slice(hist, gains, time, pol, rmsdata, prob, quality, errors, errs)
         else:
             echo(f"{datetime.datetime.now()}: Only {frac_unflagged * 100}-percent of data unflagged. Skipping...\n", verbose=verbose)
             flag_poltime(resid, time=time, polarization=pol)
@@ -1577,15 +1578,14 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
                         skip_threshold, use_model_snr_weights, optimizer, use_min, freeze_model, tol, maxsteps, n_profile_steps,
                         profile_log_dir, model_regularization, verbose, max_batch, devices, layout, opt_kwargs, correct_model=True,
                         correct_resid=False, device_split=None, gain_basis=None, gain_time_basis=None, fit_quality=False,
-                        opts=FitOptions(), errs=None, newton=GaussNewtonOptions(), lbfgs=LbfgsOptions()):
+                        controls=FitControls(), errs=None):
     """The pol x time loop of calibration.py:1160-1331 with the fits of all unskipped slices issued as batches: per slice
     exactly the host-side steps of the loop body (skip test :1173-1177, rms scale :1178-1182, tensorize :1184-1233, write-back
     :1271-1300, post-hoc renormalisation :1311-1319, residual and calibration state of the outputs :1322-1331), the gradient
     descent of :1244-1269 for up to ``max_batch`` slices at once with per-slice loop control.  Returns ``fit_history``; model,
     resid and gains are complete when it returns.  ``gain_time_basis`` (``[len(times), L]``): the unskipped times of a polarization
     are one batch and one JOINT fit (one loop state, loss = the sum over the times; calibrate_and_model_tensor's docstring).
-    ``opts``: the closed-form and robust keywords of calibrate_and_model_tensor (``fit_loop.FitOptions``); ``newton``: those of the
-    Gauss-Newton steps (``fit_loop.GaussNewtonOptions``); ``lbfgs``: those of the L-BFGS iterations (``fit_loop.LbfgsOptions``)."""
+    ``controls``: the closed-form, robust, Gauss-Newton and L-BFGS keywords of calibrate_and_model_tensor (``fit_loop.FitControls``)."""
     OPTIMIZERS[optimizer]  # unknown optimizer -> KeyError, like calibration.py:571
     dtype = np.dtype(dtype)
     layout = layout or "shared"
@@ -1695,11 +1695,9 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
         else:
             fitter.set_regularization(None)
         fitter.set_optimizer(optimizer, **opt_kwargs)
-        results, nsingular, sweep_singular, robust_out, gn, lb = drive(
-            fitter, opts, 1 if joint else nt, nt * prob.nbls if joint else prob.nbls, maxsteps, tol, use_min, freeze_model,
-            n_profile_steps, profile_log_dir, dict(slices=nt), newton=newton, lbfgs=lbfgs)
-        if joint:
-            results = results * nt  # one loop, one loss history: every time of the fit reports it
+        result = drive(fitter, controls, 1 if joint else nt, nt * prob.nbls if joint else prob.nbls, maxsteps, tol, use_min, freeze_model,
+                       n_profile_steps, profile_log_dir, dict(slices=nt))
+        results = result.loops * nt if joint else result.loops  # one loop, one loss history: every time of the fit reports it
         cur = fitter.get_params(0)
         best = fitter.get_params(1) if use_min and any(len(r[0]) for r in results) else None
         if freeze_model:
@@ -1724,34 +1722,28 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
             errors = fitter.fit_errors(ridge=errs["ridge"], model_var=errs["samples"], gain_var=errs["with_gains"], coeffs=not freeze_model)
             errors["chisq_bl"] = (quality if quality is not None else fitter.fit_quality(gm_r, gm_i))["chisq_bl"]
         echo(f"{datetime.datetime.now()} ... fitted.\n", verbose=verbose)
-        return dict(results=results, m_r=m_r, m_i=m_i, gm_r=gm_r, gm_i=gm_i, quality=quality, nsingular=nsingular, robust=robust_out,
-                    sweep_singular=sweep_singular, errors=errors, newton=gn, lbfgs=lb)
+        return dict(result=result, results=results, m_r=m_r, m_i=m_i, gm_r=gm_r, gm_i=gm_i, quality=quality, errors=errors)
 
     def post(batch, out):
         for t, (sl, res) in enumerate(zip(batch, out["results"])):
             rows, ga = slice(t * prob.nbls, (t + 1) * prob.nbls), slice(t * prob.nants, (t + 1) * prob.nants)
             _insert_model_rows(model, sl["time"], sl["pol"], ants_map, prob, out["m_r"][rows], out["m_i"][rows], scale_factor=sl["rmsdata"])
             insert_gains_into_uvcal(uvcal=gains, time=sl["time"], polarization=sl["pol"], gains_re=out["gm_r"][ga], gains_im=out["gm_i"][ga])
-            rb = out["robust"]
-            if rb is not None:
-                rb = robust_history(rb["rounds"][0 if joint else t], rb["ndown_bl"][rows], rb["scale_bl"][rows], sl["rmsdata"], prob, gains.ant_array)
-            fit_history[sl["polnum"]][sl["time_index"]] = history_entry(opts, res[0], dtype, out["nsingular"], out["sweep_singular"], rb,
-                                                                        newton_history(out["newton"], t),
-                                                                        _lbfgs_entry(out["lbfgs"], 0 if joint else t))
-            if out.get("quality") is not None:  # (before the post-hoc renormalisation, which leaves g_i conj(g_j) m as it is)
-                q = out["quality"]
-                insert_fit_quality(gains, fit_history[sl["polnum"]][sl["time_index"]], sl["time"], sl["pol"],
-                                   dict(chisq_ant=q["chisq_ant"][ga], wsum_ant=q["wsum_ant"][ga], chisq_bl=q["chisq_bl"][rows], wsum_bl=q["wsum_bl"][rows]),
-                                   sl["rmsdata"], prob)
-            if out.get("errors") is not None:
-                e = out["errors"]
+            result, loop = out["result"], 0 if joint else t  # (a joint fit is one loop: every time reports it)
+            rb = result.robust
+            if rb is not None:  # the slice's rows of it
+                rb = {"rounds": rb["rounds"][loop], "ndown_bl": rb["ndown_bl"][rows], "scale_bl": rb["scale_bl"][rows]}
+            hist = fit_history[sl["polnum"]][sl["time_index"]] = history_entry(controls, result, loop, dtype, robust=rb)
+            q, e = out["quality"], out["errors"]
+            if q is not None:
+                q = dict(chisq_ant=q["chisq_ant"][ga], wsum_ant=q["wsum_ant"][ga], chisq_bl=q["chisq_bl"][rows], wsum_bl=q["wsum_bl"][rows])
+            if e is not None:
                 coefs = slice(t * prob.ncoeffs, (t + 1) * prob.ncoeffs)
-                part = {k: e[k][{"gain_var": ga, "coeff_var": coefs}.get(k, rows)] for k in ("coeff_var", "model_var", "leverage_bl", "nsamp_bl", "gain_var") if k in e}
-                nsing = None
-                if "coeff_var" in part:  # (the library counts over the batch: the slice's own are its groups with an all-zero coeff_var)
-                    nsing = sum(1 for g in range(prob.ngrps) if not np.any(part["coeff_var"][prob.grp_coff[g] : prob.grp_coff[g + 1]]))
-                insert_fit_errors(errs["gain_std"], gains, fit_history[sl["polnum"]][sl["time_index"]], sl["time"], sl["pol"], part,
-                                  e["chisq_bl"][rows], sl["rmsdata"], prob, nsingular=nsing)
+                e = {k: e[k][{"gain_var": ga, "coeff_var": coefs}.get(k, rows)]
+                     for k in ("coeff_var", "model_var", "leverage_bl", "nsamp_bl", "gain_var", "chisq_bl") if k in e}
+                if "coeff_var" in e:  # (the library counts over the batch: the slice's own are its groups with an all-zero coeff_var)
+                    e["nsingular"] = sum(1 for g in range(prob.ngrps) if not np.any(e["coeff_var"][prob.grp_coff[g] : prob.grp_coff[g + 1]]))
+            _report_slice(hist, gains, sl["time"], sl["pol"], sl["rmsdata"], prob, q, e, errs)  # (before the post-hoc renormalisation, which leaves g_i conj(g_j) m as it is)
             if res[1]:
                 echo(f"Tolerance thresshold met for time {sl['time_index']}. Terminating...\n ", verbose=verbose)
             if not freeze_model and model_regularization == "post_hoc":  # (:1311-1319)
@@ -1768,10 +1760,10 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
     if device_split not in (None, "slices", "groups"):
         raise ValueError(f"device_split={device_split!r}: 'slices', 'groups' or None")
     D = len(devices)
-    newton.check(opts, gain_basis is not None, joint, freeze_model,
-                 groups_split=D > 1 and not (device_split == "slices" or (device_split is None and len(batches) >= D)))
-    lbfgs.check(opts, newton, groups_split=D > 1 and not (device_split == "slices" or (device_split is None and len(batches) >= D)))
-    if D > 1 and (device_split == "slices" or (device_split is None and len(batches) >= D)):
+    whole_slices = D > 1 and (device_split == "slices" or (device_split is None and len(batches) >= D))
+    # (the caller's check over again, now that it is known whether the devices share out the groups of a slice)
+    controls.check(gain_basis is not None, joint, freeze_model, use_min, groups_split=D > 1 and not whole_slices)
+    if whole_slices:
         # Whole batches on different devices: device d fits batches d, d + D, ... on a thread of its own (its solvers live on that
         # thread), nothing is exchanged between devices, and every slice is fitted exactly as it would be on one device.  One prep
         # thread runs at most D + 1 batches ahead of the fits (a batch of HERA-350 rows is 1.3 GB); one thread writes back in order.
@@ -2231,67 +2223,8 @@ def fitting_argparser():
                     help="--fit_errors plus the standard deviation of the fitted model at every sample (as large as the data)")
     sp.add_argument("--fit_errors_ridge", type=float, default=1e-6,
                     help="ridge of the factorisation behind --fit_errors, as a fraction of the mean diagonal of a group's normal matrix; default 1e-6")
-    sp.add_argument("--gain_solve_sweeps", type=int, default=0,
-                    help="solve the gains in closed form (damped StefCal sweeps) this many times before the first descent step; default 0: descent only")
-    sp.add_argument("--gain_solve_every", type=int, default=0,
-                    help="run gain sweeps (--gain_solve_sweeps of them, at least one) after every this many recorded descent steps; default 0: never")
-    sp.add_argument("--gain_solve_damping", type=float, default=0.5,
-                    help="damping of a gain sweep, in (0, 1]: g <- (1 - damping) g + damping x the closed-form minimiser; default 0.5")
-    sp.add_argument("--coeff_solve_rounds", type=int, default=0,
-                    help="before the first descent step, this many rounds of [the foreground coefficients in closed form, then "
-                         "--gain_solve_sweeps gain sweeps]; with --gain_solve_every one coefficient solve in front of every later group of sweeps; "
-                         "default 0: descent only")
-    sp.add_argument("--coeff_solve_ridge", type=float, default=1e-6,
-                    help="ridge of a coefficient solve, as a fraction of the mean diagonal of a group's normal matrix; default 1e-6")
-    sp.add_argument("--gain_basis_solve_sweeps", type=int, default=0,
-                    help="with --gain_max_dly: solve the gain-basis coefficients in closed form (damped StefCal sweeps projected on the basis) this "
-                         "many times before the first descent step; default 0: descent only")
-    sp.add_argument("--gain_basis_solve_every", type=int, default=0,
-                    help="with --gain_max_dly: run basis sweeps (--gain_basis_solve_sweeps of them, at least one) after every this many recorded "
-                         "descent steps; default 0: never")
-    sp.add_argument("--gain_basis_solve_damping", type=float, default=0.5,
-                    help="damping of a basis sweep, in (0, 1]: y <- y + damping x the closed-form step; default 0.5")
-    sp.add_argument("--gain_basis_solve_ridge", type=float, default=1e-6,
-                    help="ridge of a basis sweep, as a fraction of the mean diagonal of an antenna's normal matrix; default 1e-6")
-    sp.add_argument("--gain_time_solve_sweeps", type=int, default=0,
-                    help="with --gain_time_scale: solve the coefficients of the joint fit over the times in closed form (damped StefCal sweeps "
-                         "taken jointly over the times) this many times before the first descent step; default 0: descent only")
-    sp.add_argument("--gain_time_solve_every", type=int, default=0,
-                    help="with --gain_time_scale: run joint sweeps (--gain_time_solve_sweeps of them, at least one) after every this many "
-                         "recorded descent steps; default 0: never")
-    sp.add_argument("--gain_time_solve_damping", type=float, default=0.5,
-                    help="damping of a joint sweep, in (0, 1]: y <- y + damping x the closed-form step; default 0.5")
-    sp.add_argument("--gain_time_solve_ridge", type=float, default=1e-6,
-                    help="ridge of a joint sweep, as a fraction of the mean diagonal of a system's normal matrix; default 1e-6")
-    sp.add_argument("--robust_every", type=int, default=0,
-                    help="downweight outliers: recompute the weights from the residual (iteratively reweighted least squares, scale from each "
-                         "baseline's median) after every this many recorded descent steps; with a --gain*_solve_every flag both must be equal; "
-                         "default 0: never")
-    sp.add_argument("--robust_rounds", type=int, default=0, help="with --robust_every: reweight at most this many times; default 0: after every chunk")
-    sp.add_argument("--robust_kind", type=str, default="huber", help="weight function of --robust_every: huber, cauchy or clip; default huber")
-    sp.add_argument("--robust_threshold", type=float, default=3.0, help="threshold of the weight function in sigma; default 3")
-    sp.add_argument("--gauss_newton_rounds", type=int, default=0,
-                    help="joint Gauss-Newton steps over gains and coefficients (conjugate gradients on the joint normal matrix) before the first "
-                         "descent step, after the --coeff_solve_rounds rounds and the start-up sweeps; default 0: none")
-    sp.add_argument("--gauss_newton_every", type=int, default=0,
-                    help="one joint Gauss-Newton step after every this many recorded descent steps, behind the reweighting, the coefficient solve "
-                         "and the sweeps of the gap; with another --*_every flag both must be equal; default 0: never")
-    sp.add_argument("--gauss_newton_cg_iters", type=int, default=20, help="conjugate-gradient iterations of a Gauss-Newton step; default 20")
-    sp.add_argument("--gauss_newton_lambda", type=float, default=1e-3,
-                    help="initial Levenberg damping of a Gauss-Newton step (a tenth after an accepted step, ten times after a rejected one); default 1e-3")
-    sp.add_argument("--gauss_newton_cg_tol", type=float, default=1e-3,
-                    help="relative preconditioned residual at which the conjugate gradients of a step stop early; default 1e-3")
-    sp.add_argument("--lbfgs_steps", type=int, default=0,
-                    help="iterations of L-BFGS over the optimizer's own variables (gains or gain-basis coefficients, and the foreground "
-                         "coefficients unless the model is frozen) before the first descent step, after the start-up rounds and the "
-                         "Gauss-Newton rounds; works with --gain_max_dly, --gain_time_scale and a frozen model; default 0: none")
-    sp.add_argument("--lbfgs_every", type=int, default=0,
-                    help="with --lbfgs_steps: that many iterations again after every this many recorded descent steps, last in the gap; with "
-                         "another --*_every flag both must be equal; default 0: never")
-    sp.add_argument("--lbfgs_history", type=int, default=8, help="stored pairs of L-BFGS, 1 to 16; default 8")
-    sp.add_argument("--lbfgs_max_ls", type=int, default=20, help="trials of a backtracking line search of L-BFGS; default 20")
-    sp.add_argument("--lbfgs_ftol", type=float, default=0.0,
-                    help="a slice's L-BFGS iterations stop once the loss falls by no more than this fraction; default 0: never")
+    for f in FitControls.keyword_fields():  # the closed-form, robust, Gauss-Newton and L-BFGS keywords: name, type and default of the field
+        sp.add_argument("--" + f.name, type=f.type, default=f.default, help=KEYWORD_HELP[f.name])
     return ap
 
 

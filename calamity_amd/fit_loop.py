@@ -1,6 +1,7 @@
-"""The host loop of a fit, stated once: ``FitOptions`` holds the keywords of the closed-form solves and of the robust reweighting,
-``GaussNewtonOptions`` those of the joint Gauss-Newton steps, ``LbfgsOptions`` those of the L-BFGS iterations, ``drive`` issues everything between ``set_optimizer`` and reading the parameters back, ``history_entry`` files what it returns.
-Host only: NumPy, never the library ("The host loop")."""
+"""The host loop of a fit, stated once: ``FitControls`` holds the keywords that steer it in three sections (``FitOptions``: the
+closed-form solves and the robust reweighting, ``GaussNewtonOptions``: the joint Gauss-Newton steps, ``LbfgsOptions``: the L-BFGS
+iterations), ``drive`` issues everything between ``set_optimizer`` and reading the parameters back and returns one ``FitResult``,
+``history_entry`` files a loop of it.  Host only: NumPy, never the library ("The host loop")."""
 import dataclasses
 import datetime
 import json
@@ -26,8 +27,25 @@ def _finite_nonneg(v):
     return bool(np.isfinite(float(v)) and float(v) >= 0.0)
 
 
+def _one_chunk_length(name, every, others, other_named):
+    """The rule of the chunked loop: every ``*_every`` that is set names the same length.  ``others``: the lengths ``every`` (the
+    keyword ``name``) has to agree with, ``other_named``: how the message names the one that differs (``{}``: its value)."""
+    for other in others:
+        if every and other and other != every:
+            raise ValueError(f"{name}={every} and {other_named.format(other)} share the gaps of one chunked loop: give them the same value")
+
+
+class _Section:
+    """A group of public keywords as a frozen dataclass: the fields are the keywords, under their public names and defaults."""
+
+    @classmethod
+    def pick(cls, keywords):
+        """The options out of a mapping that holds them among others (a public function's ``locals()``)."""
+        return cls(**{f.name: keywords[f.name] for f in dataclasses.fields(cls)})
+
+
 @dataclasses.dataclass(frozen=True)
-class FitOptions:
+class FitOptions(_Section):
     """The closed-form and robust keywords of ``calibrate_and_model_tensor`` / ``fit_gains_and_foregrounds`` (documented there),
     under their public names and defaults."""
     gain_solve_sweeps: int = 0
@@ -47,11 +65,6 @@ class FitOptions:
     robust_rounds: int = 0
     robust_kind: str = "huber"
     robust_threshold: float = 3.0
-
-    @classmethod
-    def pick(cls, keywords):
-        """The options out of a mapping that holds them among others (a public function's ``locals()``)."""
-        return cls(**{f.name: keywords[f.name] for f in dataclasses.fields(cls)})
 
     def _on(self, family):
         prefix = _FAMILIES[family][0]
@@ -103,10 +116,8 @@ class FitOptions:
         if use_min:
             raise ValueError("robust_every rewrites the weights between chunks of the loop: losses under different weights are not comparable, so "
                              "use_min (the minimum over them) cannot be combined with it")
-        for other in (self.gain_solve_every, self.gain_basis_solve_every, self.gain_time_solve_every):
-            if other and other != every:
-                raise ValueError(f"robust_every={every} and the closed-form sweeps' chunk length {other} (gain_solve_every / gain_basis_solve_every / "
-                                 "gain_time_solve_every) share the gaps of one chunked loop: give them the same value")
+        _one_chunk_length("robust_every", every, (self.gain_solve_every, self.gain_basis_solve_every, self.gain_time_solve_every),
+                          "the closed-form sweeps' chunk length {} (gain_solve_every / gain_basis_solve_every / gain_time_solve_every)")
 
     def check(self, freq_basis_given, time_basis_given, freeze_model, use_min, robust_first=False):
         """``ValueError`` before any device work.  The families in the order gain, coefficients, basis, time; the robust keywords
@@ -145,7 +156,7 @@ class FitOptions:
 
 
 @dataclasses.dataclass(frozen=True)
-class GaussNewtonOptions:
+class GaussNewtonOptions(_Section):
     """The keywords of the joint Gauss-Newton steps of ``calibrate_and_model_tensor`` / ``fit_gains_and_foregrounds`` (documented
     there), under their public names and defaults."""
     gauss_newton_rounds: int = 0
@@ -153,11 +164,6 @@ class GaussNewtonOptions:
     gauss_newton_cg_iters: int = 20
     gauss_newton_lambda: float = 1e-3
     gauss_newton_cg_tol: float = 1e-3
-
-    @classmethod
-    def pick(cls, keywords):
-        """The options out of a mapping that holds them among others (a public function's ``locals()``)."""
-        return cls(**{f.name: keywords[f.name] for f in dataclasses.fields(cls)})
 
     @property
     def on(self):
@@ -190,13 +196,12 @@ class GaussNewtonOptions:
             raise ValueError("gauss_newton_rounds / gauss_newton_every need every slice whole on one device: several devices that share out the "
                              "fitting groups (device_split='groups', or too few batches for the devices) would have to exchange the per-slice scalars of "
                              "conjugate gradients, which is not implemented; device_split='slices' works")
-        if every and opts.chunk and opts.chunk != every:
-            raise ValueError(f"gauss_newton_every={every} and the chunk length {opts.chunk} of gain_solve_every / gain_basis_solve_every / "
-                             "gain_time_solve_every / robust_every share the gaps of one chunked loop: give them the same value")
+        _one_chunk_length("gauss_newton_every", every, (opts.chunk,),
+                          "the chunk length {} of gain_solve_every / gain_basis_solve_every / gain_time_solve_every / robust_every")
 
 
 @dataclasses.dataclass(frozen=True)
-class LbfgsOptions:
+class LbfgsOptions(_Section):
     """The keywords of the L-BFGS iterations of ``calibrate_and_model_tensor`` / ``fit_gains_and_foregrounds`` (documented there),
     under their public names and defaults."""
     lbfgs_steps: int = 0
@@ -204,11 +209,6 @@ class LbfgsOptions:
     lbfgs_history: int = 8
     lbfgs_max_ls: int = 20
     lbfgs_ftol: float = 0.0
-
-    @classmethod
-    def pick(cls, keywords):
-        """The options out of a mapping that holds them among others (a public function's ``locals()``)."""
-        return cls(**{f.name: keywords[f.name] for f in dataclasses.fields(cls)})
 
     @property
     def on(self):
@@ -235,11 +235,87 @@ class LbfgsOptions:
             raise ValueError("lbfgs_steps / lbfgs_every need every slice whole on one device: several devices that share out the fitting groups "
                              "(device_split='groups', or too few batches for the devices) would have to exchange the dot products of the history, "
                              "which is not implemented; device_split='slices' works")
-        others = [opts.chunk] + ([newton.gauss_newton_every] if newton is not None and newton.on else [])
-        for other in others:
-            if every and other and other != every:
-                raise ValueError(f"lbfgs_every={every} and the chunk length {other} of gain_solve_every / gain_basis_solve_every / "
-                                 "gain_time_solve_every / robust_every / gauss_newton_every share the gaps of one chunked loop: give them the same value")
+        _one_chunk_length("lbfgs_every", every, (opts.chunk, newton.gauss_newton_every if newton is not None else 0),
+                          "the chunk length {} of gain_solve_every / gain_basis_solve_every / gain_time_solve_every / robust_every / gauss_newton_every")
+
+
+@dataclasses.dataclass(frozen=True)
+class FitControls:
+    """Everything that steers the host loop of one call: the three sections of keywords."""
+    fit: FitOptions = FitOptions()
+    newton: GaussNewtonOptions = GaussNewtonOptions()
+    lbfgs: LbfgsOptions = LbfgsOptions()
+
+    @classmethod
+    def pick(cls, keywords):
+        """The controls out of a mapping that holds their keywords among others (a public function's ``locals()``)."""
+        return cls(*(f.type.pick(keywords) for f in dataclasses.fields(cls)))
+
+    @classmethod
+    def keyword_fields(cls):
+        """The dataclass fields of every keyword, in the order of the public signatures."""
+        return [k for f in dataclasses.fields(cls) for k in dataclasses.fields(f.type)]
+
+    def keywords(self):
+        """The keywords as one mapping, to pass on to a public function."""
+        return {f.name: getattr(section, f.name) for section in (self.fit, self.newton, self.lbfgs) for f in dataclasses.fields(section)}
+
+    @property
+    def chunk(self):
+        """Steps per chunk of the recorded loop, the one length of every ``*_every`` that is set (``check``); 0: one call."""
+        return self.fit.chunk or self.newton.gauss_newton_every or self.lbfgs.lbfgs_every
+
+    def check(self, freq_basis_given, time_basis_given, freeze_model, use_min, robust_first=False, groups_split=False):
+        """``ValueError`` before any device work: the sections' checks in the order ``FitOptions`` (``robust_first``: see there),
+        Gauss-Newton, L-BFGS.  ``groups_split``: several devices share out the fitting groups of a slice."""
+        self.fit.check(freq_basis_given, time_basis_given, freeze_model, use_min, robust_first=robust_first)
+        self.newton.check(self.fit, freq_basis_given, time_basis_given, freeze_model, groups_split=groups_split)
+        self.lbfgs.check(self.fit, self.newton, groups_split=groups_split)
+
+
+# keyword -> its help text on the command line (``calibration.fitting_argparser`` makes one argument of every field above)
+KEYWORD_HELP = {
+    "gain_solve_sweeps": "solve the gains in closed form (damped StefCal sweeps) this many times before the first descent step; default 0: descent only",
+    "gain_solve_every": "run gain sweeps (--gain_solve_sweeps of them, at least one) after every this many recorded descent steps; default 0: never",
+    "gain_solve_damping": "damping of a gain sweep, in (0, 1]: g <- (1 - damping) g + damping x the closed-form minimiser; default 0.5",
+    "coeff_solve_rounds": "before the first descent step, this many rounds of [the foreground coefficients in closed form, then "
+                          "--gain_solve_sweeps gain sweeps]; with --gain_solve_every one coefficient solve in front of every later group of sweeps; "
+                          "default 0: descent only",
+    "coeff_solve_ridge": "ridge of a coefficient solve, as a fraction of the mean diagonal of a group's normal matrix; default 1e-6",
+    "gain_basis_solve_sweeps": "with --gain_max_dly: solve the gain-basis coefficients in closed form (damped StefCal sweeps projected on the basis) this "
+                               "many times before the first descent step; default 0: descent only",
+    "gain_basis_solve_every": "with --gain_max_dly: run basis sweeps (--gain_basis_solve_sweeps of them, at least one) after every this many recorded "
+                              "descent steps; default 0: never",
+    "gain_basis_solve_damping": "damping of a basis sweep, in (0, 1]: y <- y + damping x the closed-form step; default 0.5",
+    "gain_basis_solve_ridge": "ridge of a basis sweep, as a fraction of the mean diagonal of an antenna's normal matrix; default 1e-6",
+    "gain_time_solve_sweeps": "with --gain_time_scale: solve the coefficients of the joint fit over the times in closed form (damped StefCal sweeps "
+                              "taken jointly over the times) this many times before the first descent step; default 0: descent only",
+    "gain_time_solve_every": "with --gain_time_scale: run joint sweeps (--gain_time_solve_sweeps of them, at least one) after every this many "
+                             "recorded descent steps; default 0: never",
+    "gain_time_solve_damping": "damping of a joint sweep, in (0, 1]: y <- y + damping x the closed-form step; default 0.5",
+    "gain_time_solve_ridge": "ridge of a joint sweep, as a fraction of the mean diagonal of a system's normal matrix; default 1e-6",
+    "robust_every": "downweight outliers: recompute the weights from the residual (iteratively reweighted least squares, scale from each "
+                    "baseline's median) after every this many recorded descent steps; with a --gain*_solve_every flag both must be equal; "
+                    "default 0: never",
+    "robust_rounds": "with --robust_every: reweight at most this many times; default 0: after every chunk",
+    "robust_kind": "weight function of --robust_every: huber, cauchy or clip; default huber",
+    "robust_threshold": "threshold of the weight function in sigma; default 3",
+    "gauss_newton_rounds": "joint Gauss-Newton steps over gains and coefficients (conjugate gradients on the joint normal matrix) before the first "
+                           "descent step, after the --coeff_solve_rounds rounds and the start-up sweeps; default 0: none",
+    "gauss_newton_every": "one joint Gauss-Newton step after every this many recorded descent steps, behind the reweighting, the coefficient solve "
+                          "and the sweeps of the gap; with another --*_every flag both must be equal; default 0: never",
+    "gauss_newton_cg_iters": "conjugate-gradient iterations of a Gauss-Newton step; default 20",
+    "gauss_newton_lambda": "initial Levenberg damping of a Gauss-Newton step (a tenth after an accepted step, ten times after a rejected one); default 1e-3",
+    "gauss_newton_cg_tol": "relative preconditioned residual at which the conjugate gradients of a step stop early; default 1e-3",
+    "lbfgs_steps": "iterations of L-BFGS over the optimizer's own variables (gains or gain-basis coefficients, and the foreground "
+                   "coefficients unless the model is frozen) before the first descent step, after the start-up rounds and the "
+                   "Gauss-Newton rounds; works with --gain_max_dly, --gain_time_scale and a frozen model; default 0: none",
+    "lbfgs_every": "with --lbfgs_steps: that many iterations again after every this many recorded descent steps, last in the gap; with "
+                   "another --*_every flag both must be equal; default 0: never",
+    "lbfgs_history": "stored pairs of L-BFGS, 1 to 16; default 8",
+    "lbfgs_max_ls": "trials of a backtracking line search of L-BFGS; default 20",
+    "lbfgs_ftol": "a slice's L-BFGS iterations stop once the loss falls by no more than this fraction; default 0: never",
+}
 
 
 def next_lambda(lam, accepted):
@@ -248,53 +324,116 @@ def next_lambda(lam, accepted):
     return np.where(np.asarray(accepted, dtype=bool), lam / 10.0, 10.0 * np.maximum(lam, 1e-6))
 
 
-def drive(fitter, opts, nl, rows_per_loop, maxsteps, tol, use_min, freeze_model, n_profile_steps=0, profile_log_dir="./logdir",
-          profile_extra=None, newton=None, lbfgs=None):
-    """Everything between ``set_optimizer`` and reading the parameters back, on a ``SliceBatchFitter`` or a one-slice
-    ``HipFitSolver``: the start-up rounds of closed-form solves, ``n_profile_steps`` profiled steps (their timings, with the keys of
-    ``profile_extra``, as JSON into ``profile_log_dir``), the unrecorded step, the recorded loop.  ``nl``: the loops of the fitter (1 for
-    a single solver and for a joint fit, else the slices of the batch), ``rows_per_loop``: the baseline rows of each.  Returns
-    ``(results, nsingular, sweep_singular, robust)``: per loop ``(losses, stopped, nupdates)``; the singular count of the last
-    coefficient solve and of the last sweep of a basis or time family (``None`` where there is none); with ``robust_every`` what the
-    last reweight of every loop reported, ``{"rounds": [nl], "ndown_bl", "scale_bl": [nl * rows_per_loop]}``, else ``None``.
-    ``newton`` (``GaussNewtonOptions``): ``gauss_newton_rounds`` joint steps after the start-up rounds and sweeps, and with
-    ``gauss_newton_every`` one step in every gap of the chunked loop behind the reweighting, the coefficient solve and the sweeps, on the
-    loops not yet over and with the optimizer's slots of the accepted ones started over.  The damping is kept per loop (``next_lambda``);
-    a rejected step is simply followed by the next one.  With ``newton`` given a fifth value is returned: ``None`` while it is off,
-    else ``{"steps", "accepted": [nl], "lambda": [nl] (the damping a next step would use), "loss", "cg_iters": per loop the loss after and the
-    iterations of every step it took part in}``.
-    ``lbfgs`` (``LbfgsOptions``): ``lbfgs_steps`` iterations of L-BFGS after the start-up rounds and the Gauss-Newton rounds, before the
-    profiled and unrecorded steps, and with ``lbfgs_every`` as many again last in every gap of the chunked loop, on the loops not yet
-    over and with the optimizer's slots of the loops that moved started over.  With ``lbfgs`` given one more value is appended: ``None``
-    while it is off, else ``{"calls", "iters", "evals": [nl], "loss": per loop the loss after every call it took part in, "status":
-    [nl] of its last call}``."""
-    family = opts.family
-    sweeps, every, damping, ridge = opts.sweep
+def newton_history(gn, t):
+    """Loop ``t``'s ``fit_history[...]["gauss_newton"]`` from ``FitResult.newton`` (``None`` while the steps are off)."""
+    if gn is None:
+        return None
+    return {"steps": int(gn["steps"][t]), "accepted": int(gn["accepted"][t]), "lambda": float(gn["lambda"][t]), "loss": list(gn["loss"][t]),
+            "cg_iters": list(gn["cg_iters"][t])}
 
-    def sweep(n, **kw):
-        if family == "time":  # one system over the times: no slice mask
+
+def lbfgs_history(lb, t):
+    """Loop ``t``'s ``fit_history[...]["lbfgs"]`` from ``FitResult.lbfgs`` (``None`` while the iterations are off)."""
+    if lb is None:
+        return None
+    return {"calls": int(lb["calls"][t]), "iters": int(lb["iters"][t]), "evals": int(lb["evals"][t]), "loss": list(lb["loss"][t]),
+            "status": int(lb["status"][t])}
+
+
+class _Action:
+    """One thing a fit does besides descent steps.  ``start()``: its work before the first descent step; ``gap(running)``: its work between
+    two chunks of the recorded loop, on the mask of the loops not yet over; ``fields()``: what it adds to the ``FitResult``, unless it says
+    otherwise its per-loop ``record`` as the field ``name``; ``entry(record, t)``: loop ``t`` of that record as ``fit_history`` reports it.
+    ``drive`` runs its list of actions front to back both times."""
+
+    def start(self):
+        pass
+
+    def gap(self, running):
+        pass
+
+    def fields(self):
+        return {self.name: self.record}
+
+
+class _Reweight(_Action):
+    """``robust_every``: per loop the reweights it took part in, per baseline row what its last one reported."""
+    name = "robust"
+
+    def __init__(self, fitter, o, nl, rows_per_loop):
+        self.fitter, self.o, self.rows_per_loop = fitter, o, rows_per_loop
+        self.record = dict(rounds=np.zeros(nl, dtype=np.int64), ndown_bl=np.zeros(nl * rows_per_loop), scale_bl=np.zeros(nl * rows_per_loop))
+
+    def gap(self, running):
+        o, rec = self.o, self.record
+        todo = running if o.robust_rounds == 0 else running & (rec["rounds"] < o.robust_rounds)
+        if np.any(todo):
+            rw = self.fitter.robust_weights(kind=o.robust_kind, threshold=o.robust_threshold, slice_mask=todo)
+            rows = np.repeat(todo, self.rows_per_loop)
+            rec["ndown_bl"][rows] = rw["ndown_bl"][rows]
+            rec["scale_bl"][rows] = rw["scale_bl"][rows]
+            rec["rounds"] += todo
+
+    @staticmethod
+    def entry(rec, t):
+        """Solver units and row order; a caller that reports other units hands ``history_entry`` its own."""
+        n = len(rec["ndown_bl"]) // len(rec["rounds"])
+        rows = slice(t * n, (t + 1) * n)
+        return {"rounds": int(rec["rounds"][t]), "ndown_bl": rec["ndown_bl"][rows], "scale_bl": rec["scale_bl"][rows]}
+
+
+class _ClosedForm(_Action):
+    """``coeff_solve_rounds`` and the sweeps of the fit's family: the singular counts of the last coefficient solve and the last sweep."""
+
+    def __init__(self, fitter, o):
+        self.fitter, self.o, self.family = fitter, o, o.family
+        self.sweeps, self.every, self.damping, self.ridge = o.sweep
+        self.nsingular = self.last = None
+
+    def _coeffs(self, **kw):
+        self.nsingular = self.fitter.solve_coeffs(ridge=self.o.coeff_solve_ridge, **kw)["nsingular"]
+
+    def _sweep(self, n, **kw):
+        if self.family == "time":  # one system over the times: no slice mask
             kw.pop("slice_mask", None)
-        if family != "gain":
-            kw["ridge"] = ridge
-        out = getattr(fitter, _FAMILIES[family][1])(n, damping=damping, **kw)
-        return None if family == "gain" else out["nsingular"]
+        if self.family != "gain":
+            kw["ridge"] = self.ridge
+        out = getattr(self.fitter, _FAMILIES[self.family][1])(n, damping=self.damping, **kw)
+        self.last = None if self.family == "gain" else out["nsingular"]
 
-    nsingular = last = None
-    if opts.coeff_solve_rounds > 0:  # alternating least squares: rounds of (the coefficients in closed form, then the gain sweeps)
-        for _ in range(opts.coeff_solve_rounds):
-            nsingular = fitter.solve_coeffs(ridge=opts.coeff_solve_ridge)["nsingular"]
-            if sweeps > 0:
-                last = sweep(sweeps)
-    elif sweeps > 0:  # the coefficients are initialised: the gains in closed form before any descent step
-        last = sweep(sweeps)
-    gn = None
-    if newton is not None and newton.on:
-        gn = dict(steps=np.zeros(nl, dtype=np.int64), accepted=np.zeros(nl, dtype=np.int64), loss=[[] for _ in range(nl)],
-                  cg_iters=[[] for _ in range(nl)])
-        gn["lambda"] = np.full(nl, float(newton.gauss_newton_lambda))
+    def start(self):
+        if self.o.coeff_solve_rounds > 0:  # alternating least squares: rounds of (the coefficients in closed form, then the gain sweeps)
+            for _ in range(self.o.coeff_solve_rounds):
+                self._coeffs()
+                if self.sweeps > 0:
+                    self._sweep(self.sweeps)
+        elif self.sweeps > 0:  # the coefficients are initialised: the gains in closed form before any descent step
+            self._sweep(self.sweeps)
 
-    def newton_step(todo, **kw):
-        out = fitter.gauss_newton_step(ncg=newton.gauss_newton_cg_iters, lam=gn["lambda"], cg_tol=newton.gauss_newton_cg_tol, **kw)
+    def gap(self, running):
+        if self.every > 0:
+            if self.o.coeff_solve_rounds > 0:
+                self._coeffs(slice_mask=running, reset_coeff_moments=True)
+            self._sweep(max(1, self.sweeps), slice_mask=running, reset_gain_moments=True)
+
+    def fields(self):
+        return dict(nsingular=self.nsingular, sweep_singular=int(self.last or 0) if self.family in ("basis", "time") else None)
+
+
+class _GaussNewton(_Action):
+    """``gauss_newton_rounds`` / ``gauss_newton_every``: the damping is kept per loop (``next_lambda``); a rejected step is simply
+    followed by the next one."""
+    name = "newton"
+
+    def __init__(self, fitter, o, nl):
+        self.fitter, self.o, self.nl = fitter, o, nl
+        self.record = dict(steps=np.zeros(nl, dtype=np.int64), accepted=np.zeros(nl, dtype=np.int64), loss=[[] for _ in range(nl)],
+                           cg_iters=[[] for _ in range(nl)])
+        self.record["lambda"] = np.full(nl, float(o.gauss_newton_lambda))
+
+    def _step(self, todo, **kw):
+        o, gn = self.o, self.record
+        out = self.fitter.gauss_newton_step(ncg=o.gauss_newton_cg_iters, lam=gn["lambda"], cg_tol=o.gauss_newton_cg_tol, **kw)
         ok = np.asarray(out["accepted"], dtype=bool)
         gn["lambda"] = np.where(todo, next_lambda(gn["lambda"], ok), gn["lambda"])
         gn["steps"] += todo
@@ -303,17 +442,29 @@ def drive(fitter, opts, nl, rows_per_loop, maxsteps, tol, use_min, freeze_model,
             gn["loss"][t].append(float(out["loss_after"][t] if ok[t] else out["loss_before"][t]))
             gn["cg_iters"][t].append(int(out["cg_iters"][t]))
 
-    if gn is not None:
-        for _ in range(newton.gauss_newton_rounds):
-            newton_step(np.ones(nl, dtype=bool))
-    lb = None
-    if lbfgs is not None and lbfgs.on:
-        lb = dict(calls=np.zeros(nl, dtype=np.int64), iters=np.zeros(nl, dtype=np.int64), evals=np.zeros(nl, dtype=np.int64),
-                  loss=[[] for _ in range(nl)], status=np.full(nl, 4, dtype=np.int64))
+    def start(self):
+        for _ in range(self.o.gauss_newton_rounds):
+            self._step(np.ones(self.nl, dtype=bool))
 
-    def lbfgs_call(todo, **kw):
-        out = fitter.lbfgs(lbfgs.lbfgs_steps, history=lbfgs.lbfgs_history, max_ls=lbfgs.lbfgs_max_ls, ftol=lbfgs.lbfgs_ftol,
-                           freeze_model=freeze_model, **kw)
+    def gap(self, running):
+        if self.o.gauss_newton_every > 0:
+            self._step(running, slice_mask=running, reset_moments=True)
+
+    entry = staticmethod(newton_history)
+
+
+class _Lbfgs(_Action):
+    """``lbfgs_steps`` / ``lbfgs_every``: per loop the calls, iterations and evaluations, the loss after every call, its last status."""
+    name = "lbfgs"
+
+    def __init__(self, fitter, o, nl, freeze_model):
+        self.fitter, self.o, self.nl, self.freeze_model = fitter, o, nl, freeze_model
+        self.record = dict(calls=np.zeros(nl, dtype=np.int64), iters=np.zeros(nl, dtype=np.int64), evals=np.zeros(nl, dtype=np.int64),
+                           loss=[[] for _ in range(nl)], status=np.full(nl, 4, dtype=np.int64))
+
+    def _call(self, todo, **kw):
+        o, lb = self.o, self.record
+        out = self.fitter.lbfgs(o.lbfgs_steps, history=o.lbfgs_history, max_ls=o.lbfgs_max_ls, ftol=o.lbfgs_ftol, freeze_model=self.freeze_model, **kw)
         lb["calls"] += todo
         lb["iters"] += np.where(todo, out["iters"], 0)
         lb["evals"] += np.where(todo, out["evals"], 0)
@@ -321,8 +472,51 @@ def drive(fitter, opts, nl, rows_per_loop, maxsteps, tol, use_min, freeze_model,
         for t in np.where(todo)[0]:
             lb["loss"][t].append(float(out["loss_after"][t]))
 
-    if lb is not None and lbfgs.lbfgs_steps > 0:
-        lbfgs_call(np.ones(nl, dtype=bool))
+    def start(self):
+        if self.o.lbfgs_steps > 0:
+            self._call(np.ones(self.nl, dtype=bool))
+
+    def gap(self, running):
+        if self.o.lbfgs_every > 0:
+            self._call(running, slice_mask=running, reset_moments=True)
+
+    entry = staticmethod(lbfgs_history)
+
+
+@dataclasses.dataclass
+class FitResult:
+    """What ``drive`` returns.  ``loops``: per loop ``(losses, stopped, nupdates)``; ``nsingular``, ``sweep_singular``: the singular count
+    of the last coefficient solve and of the last sweep of a basis or time family; ``robust``: what the last reweight of every loop
+    reported, ``{"rounds": [nl], "ndown_bl", "scale_bl": [nl * rows_per_loop]}``; ``newton``: ``{"steps", "accepted": [nl], "lambda": [nl]
+    (the damping a next step would use), "loss", "cg_iters": per loop the loss after and the iterations of every step it took part in}``;
+    ``lbfgs``: ``{"calls", "iters", "evals": [nl], "loss": per loop the loss after every call it took part in, "status": [nl] of its last
+    call}``.  ``None`` where the fit has no such thing."""
+    loops: list
+    nsingular: object = None
+    sweep_singular: object = None
+    robust: object = None
+    newton: object = None
+    lbfgs: object = None
+
+
+def drive(fitter, controls, nl, rows_per_loop, maxsteps, tol, use_min, freeze_model, n_profile_steps=0, profile_log_dir="./logdir",
+          profile_extra=None):
+    """Everything between ``set_optimizer`` and reading the parameters back, on a ``SliceBatchFitter`` or a one-slice
+    ``HipFitSolver``, as ``controls`` (``FitControls``) say: the start-up work of the actions (the rounds of closed-form solves, the
+    Gauss-Newton rounds, the L-BFGS iterations), ``n_profile_steps`` profiled steps (their timings, with the keys of ``profile_extra``,
+    as JSON into ``profile_log_dir``), the unrecorded step, the recorded loop -- with a chunk length (``controls.chunk``) in chunks,
+    with the actions' gap work between them (the reweighting, the coefficient solve and the sweeps, one Gauss-Newton step, the L-BFGS
+    iterations) on the loops not yet over and with the optimizer's slots of the loops that moved started over.  ``nl``: the loops of
+    the fitter (1 for a single solver and for a joint fit, else the slices of the batch), ``rows_per_loop``: the baseline rows of each.
+    An action that is switched off is not in the list and makes no call.  Returns a ``FitResult``."""
+    o = controls.fit
+    actions = [_Reweight(fitter, o, nl, rows_per_loop) if o.robust_every > 0 else None,
+               _ClosedForm(fitter, o) if o.coeff_solve_rounds > 0 or o.family is not None else None,
+               _GaussNewton(fitter, controls.newton, nl) if controls.newton.on else None,
+               _Lbfgs(fitter, controls.lbfgs, nl, freeze_model) if controls.lbfgs.on else None]
+    actions = [a for a in actions if a is not None]
+    for action in actions:
+        action.start()
     if n_profile_steps > 0:
         fitter.timing_enable(True)
         fitter.run_slices(n_profile_steps, record=False, freeze_model=freeze_model)
@@ -332,10 +526,7 @@ def drive(fitter, opts, nl, rows_per_loop, maxsteps, tol, use_min, freeze_model,
         fitter.timing_enable(False)
     fitter.run_slices(1, record=False, freeze_model=freeze_model)  # the unrecorded step of calibration.py:693
     run = dict(record=True, tol=tol, use_min=use_min, freeze_model=freeze_model)
-    robust = None
-    if opts.robust_every > 0:  # per loop the reweights it took part in; per baseline row what its last one reported
-        robust = dict(rounds=np.zeros(nl, dtype=np.int64), ndown_bl=np.zeros(nl * rows_per_loop), scale_bl=np.zeros(nl * rows_per_loop))
-    chunk = opts.chunk or (newton.gauss_newton_every if gn is not None else 0) or (lbfgs.lbfgs_every if lb is not None else 0)
+    chunk = controls.chunk
     if chunk > 0:
         # the recorded loop in chunks (every loop's state -- step count, previous and lowest loss -- persists from run to run); a loop
         # that has ended is held in the chunks that follow, as one call would leave it, and takes no part in the gaps between them
@@ -350,60 +541,27 @@ def drive(fitter, opts, nl, rows_per_loop, maxsteps, tol, use_min, freeze_model,
             issued += n
             if issued < maxsteps and not np.all(over):
                 fitter.hold_slices(over)
-                if robust is not None:
-                    todo = ~over if opts.robust_rounds == 0 else ~over & (robust["rounds"] < opts.robust_rounds)
-                    if np.any(todo):
-                        rw = fitter.robust_weights(kind=opts.robust_kind, threshold=opts.robust_threshold, slice_mask=todo)
-                        rows = np.repeat(todo, rows_per_loop)
-                        robust["ndown_bl"][rows] = rw["ndown_bl"][rows]
-                        robust["scale_bl"][rows] = rw["scale_bl"][rows]
-                        robust["rounds"] += todo
-                if every > 0:
-                    if opts.coeff_solve_rounds > 0:
-                        nsingular = fitter.solve_coeffs(ridge=opts.coeff_solve_ridge, slice_mask=~over, reset_coeff_moments=True)["nsingular"]
-                    last = sweep(max(1, sweeps), slice_mask=~over, reset_gain_moments=True)
-                if gn is not None and newton.gauss_newton_every > 0:
-                    newton_step(~over, slice_mask=~over, reset_moments=True)
-                if lb is not None and lbfgs.lbfgs_every > 0:
-                    lbfgs_call(~over, slice_mask=~over, reset_moments=True)
+                for action in actions:
+                    action.gap(~over)
         fitter.hold_slices(None)
-        results = [(np.concatenate([np.zeros(0)] + parts[t]), bool(over[t]), int(nupd[t])) for t in range(nl)]
+        loops = [(np.concatenate([np.zeros(0)] + parts[t]), bool(over[t]), int(nupd[t])) for t in range(nl)]
     else:
-        results = fitter.run_slices(maxsteps, **run)
-    out = (results, nsingular, (int(last or 0) if family in ("basis", "time") else None), robust)
-    if newton is not None:
-        out = out + (gn,)
-    return out if lbfgs is None else out + (lb,)
+        loops = fitter.run_slices(maxsteps, **run)
+    return FitResult(loops, **{k: v for action in actions for k, v in action.fields().items()})
 
 
-def newton_history(gn, t):
-    """Loop ``t``'s ``fit_history[...]["gauss_newton"]`` from the fifth value of ``drive`` (``None`` while the steps are off)."""
-    if gn is None:
-        return None
-    return {"steps": int(gn["steps"][t]), "accepted": int(gn["accepted"][t]), "lambda": float(gn["lambda"][t]), "loss": list(gn["loss"][t]),
-            "cg_iters": list(gn["cg_iters"][t])}
-
-
-def lbfgs_history(lb, t):
-    """Loop ``t``'s ``fit_history[...]["lbfgs"]`` from the value ``drive`` appends for ``lbfgs=`` (``None`` while the iterations are off)."""
-    if lb is None:
-        return None
-    return {"calls": int(lb["calls"][t]), "iters": int(lb["iters"][t]), "evals": int(lb["evals"][t]), "loss": list(lb["loss"][t]),
-            "status": int(lb["status"][t])}
-
-
-def history_entry(opts, losses, dtype, nsingular, sweep_singular, robust, newton=None, lbfgs=None):
-    """One slice's ``fit_history`` entry from what ``drive`` returned for it (``robust``, ``newton``, ``lbfgs``: the entries as the caller
-    reports them, ``newton_history`` and ``lbfgs_history`` for the latter two)."""
-    hist = {"loss": [dtype.type(l) for l in losses]}
-    if nsingular is not None:
-        hist["coeff_solve_singular"] = int(nsingular)
-    if sweep_singular is not None:
-        hist[_FAMILIES[opts.family][0] + "_singular"] = int(sweep_singular)
-    if robust is not None:
-        hist["robust"] = robust
-    if newton is not None:
-        hist["gauss_newton"] = newton
-    if lbfgs is not None:
-        hist["lbfgs"] = lbfgs
+def history_entry(controls, result, t, dtype, robust=None):
+    """Loop ``t`` of a ``FitResult`` as one slice's ``fit_history`` entry.  ``robust``: the reweighting as the caller reports it, where
+    that is not loop ``t`` in solver units and row order."""
+    hist = {"loss": [dtype.type(l) for l in result.loops[t][0]]}
+    if result.nsingular is not None:
+        hist["coeff_solve_singular"] = int(result.nsingular)
+    if result.sweep_singular is not None:
+        hist[_FAMILIES[controls.fit.family][0] + "_singular"] = int(result.sweep_singular)
+    if result.robust is not None:
+        hist["robust"] = _Reweight.entry(result.robust, t) if robust is None else robust
+    if result.newton is not None:
+        hist["gauss_newton"] = _GaussNewton.entry(result.newton, t)
+    if result.lbfgs is not None:
+        hist["lbfgs"] = _Lbfgs.entry(result.lbfgs, t)
     return hist

@@ -5,71 +5,15 @@ import json
 
 import numpy as np
 
-from calamity_amd.fit_loop import FitOptions, drive, history_entry
-
-TOL = 1e-9
-UNRECORDED = ("run_slices", (1,), dict(record=False, freeze_model=False))
-
-
-def recorded(n):
-    return ("run_slices", (n,), dict(record=True, tol=TOL, use_min=False, freeze_model=False))
-
-
-def going(n, nl):
-    """A chunk of ``n`` steps that every one of ``nl`` loops ran to its end."""
-    return [(np.arange(n, dtype=np.float64), False, n) for _ in range(nl)]
-
-
-class Fake:
-    """Every method ``drive`` may call; ``chunks``: what the recorded ``run_slices`` calls return, in order; ``rows``: the baseline
-    rows a reweight reports (call k: ``100 k + row`` for the rows of the selected loops, 0 for the others, like the library)."""
-
-    def __init__(self, chunks=(), nl=1, rows=0):
-        self.log, self.chunks, self.nl, self.rows, self.nrobust = [], list(chunks), nl, rows, 0
-
-    def _put(self, name, args, kw):
-        kw = {k: [int(x) for x in v] if k == "slice_mask" else v for k, v in kw.items()}
-        self.log.append((name, args, kw))
-
-    def run_slices(self, n, **kw):
-        self._put("run_slices", (n,), kw)
-        return self.chunks.pop(0) if kw["record"] else None
-
-    def hold_slices(self, mask=None):
-        self._put("hold_slices", (None if mask is None else [int(x) for x in mask],), {})
-
-    def robust_weights(self, **kw):
-        self._put("robust_weights", (), kw)
-        self.nrobust += 1
-        sel = np.repeat(np.asarray(kw["slice_mask"], dtype=bool), self.rows // self.nl)
-        vals = np.where(sel, 100.0 * self.nrobust + np.arange(self.rows), 0.0)
-        return dict(ndown_bl=vals, scale_bl=vals + 0.5)
-
-    def solve_gains(self, n, **kw):
-        self._put("solve_gains", (n,), kw)
-
-    def solve_coeffs(self, **kw):
-        self._put("solve_coeffs", (), kw)
-        return dict(nsolved=9, nsingular=len(self.log))
-
-    def solve_gain_coeffs(self, n, **kw):
-        self._put("solve_gain_coeffs", (n,), kw)
-        return dict(nsolved=9, nsingular=len(self.log))
-
-    def solve_gain_time_coeffs(self, n, **kw):
-        self._put("solve_gain_time_coeffs", (n,), kw)
-        return dict(nsolved=9, nsingular=len(self.log))
-
-    def timing_enable(self, on):
-        self._put("timing_enable", (on,), {})
-
-    def timing_get(self):
-        self._put("timing_get", (), {})
-        return {"mean_ms": 1.5}
+from calamity_amd.fit_loop import FitControls, FitOptions, FitResult, drive, history_entry
+from fit_loop_cases import TOL, UNRECORDED, Fake, going, recorded
 
 
 def run(fake, opts, nl, maxsteps, rows=0, **kw):
-    return drive(fake, opts, nl, rows // nl, maxsteps, TOL, False, False, **kw)
+    """The four fields of the result that the closed-form solves and the reweighting fill."""
+    r = drive(fake, FitControls(opts), nl, rows // nl, maxsteps, TOL, False, False, **kw)
+    assert r.newton is None and r.lbfgs is None
+    return r.loops, r.nsingular, r.sweep_singular, r.robust
 
 
 def test_plain_fit_is_one_unrecorded_step_and_one_call():
@@ -212,17 +156,25 @@ def test_profiled_steps_sit_between_the_solves_and_the_unrecorded_step(tmp_path)
 
 def test_use_min_freeze_model_and_tol_reach_every_step():
     fake = Fake([going(3, 1)])
-    drive(fake, FitOptions(), 1, 0, 3, 1e-3, True, True)
+    drive(fake, FitControls(), 1, 0, 3, 1e-3, True, True)
     assert fake.log == [("run_slices", (1,), dict(record=False, freeze_model=True)),
                         ("run_slices", (3,), dict(record=True, tol=1e-3, use_min=True, freeze_model=True))]
 
 
 def test_history_entry_keys_follow_the_configuration():
     f32 = np.dtype(np.float32)
-    plain = history_entry(FitOptions(), np.arange(3.0), f32, None, None, None)
+
+    def entry(opts, losses, nsingular, sweep_singular, robust, as_reported=None):
+        return history_entry(FitControls(opts), FitResult([(losses, False, 0)], nsingular, sweep_singular, robust), 0, f32, robust=as_reported)
+
+    plain = entry(FitOptions(), np.arange(3.0), None, None, None)
     assert list(plain) == ["loss"] and plain["loss"] == [0.0, 1.0, 2.0] and all(type(l) is np.float32 for l in plain["loss"])
-    basis = history_entry(FitOptions(gain_basis_solve_every=5), [], f32, 2, 0, {"rounds": 1})
+    reweights = dict(rounds=np.array([1]), ndown_bl=np.zeros(2), scale_bl=np.ones(2))
+    basis = entry(FitOptions(gain_basis_solve_every=5), [], 2, 0, reweights, as_reported={"rounds": 1})
     assert basis == {"loss": [], "coeff_solve_singular": 2, "gain_basis_solve_singular": 0, "robust": {"rounds": 1}}
     assert list(basis) == ["loss", "coeff_solve_singular", "gain_basis_solve_singular", "robust"]
-    assert list(history_entry(FitOptions(gain_time_solve_sweeps=1), [], f32, None, 4, None)) == ["loss", "gain_time_solve_singular"]
-    assert list(history_entry(FitOptions(gain_solve_sweeps=1), [], f32, None, None, None)) == ["loss"]
+    # without the caller's own: the loop's reweights in solver units and row order
+    own = entry(FitOptions(robust_every=5), [], None, None, reweights)["robust"]
+    assert own["rounds"] == 1 and own["ndown_bl"].tolist() == [0.0, 0.0] and own["scale_bl"].tolist() == [1.0, 1.0]
+    assert list(entry(FitOptions(gain_time_solve_sweeps=1), [], None, 4, None)) == ["loss", "gain_time_solve_singular"]
+    assert list(entry(FitOptions(gain_solve_sweeps=1), [], None, None, None)) == ["loss"]

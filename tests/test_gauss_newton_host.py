@@ -11,9 +11,9 @@ import numpy as np
 import pytest
 
 from calamity_amd import _lib, calibration, synthetic
-from calamity_amd.fit_loop import FitOptions, GaussNewtonOptions, drive, history_entry, newton_history, next_lambda
+from calamity_amd.fit_loop import FitControls, FitOptions, GaussNewtonOptions, drive, history_entry, next_lambda
+from fit_loop_cases import TOL, UNRECORDED, NewtonFake, going, recorded
 from gauss_newton_ref import Ref, dense_normal_matrix, flatten
-from test_fit_loop_host import TOL, UNRECORDED, Fake, going, recorded
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -227,22 +227,6 @@ def test_public_calls_refuse_before_any_device_work():
 
 
 # ---- the calls drive issues
-class NewtonFake(Fake):
-    """``accept``: per call the slices whose step is accepted."""
-
-    def __init__(self, chunks=(), nl=1, rows=0, accept=()):
-        super().__init__(chunks, nl, rows)
-        self.accept = list(accept)
-
-    def gauss_newton_step(self, **kw):
-        lam = [float(x) for x in kw.pop("lam")]
-        self._put("gauss_newton_step", (), dict(kw, lam=lam))
-        ok = np.asarray(self.accept.pop(0), dtype=bool)
-        k = len(self.log)
-        return dict(loss_before=np.full(self.nl, 10.0 * k), loss_after=np.full(self.nl, 10.0 * k - 1.0), cg_residual=np.zeros(self.nl),
-                    cg_iters=np.full(self.nl, k), accepted=ok)
-
-
 def step(lam, **kw):
     return ("gauss_newton_step", (), dict(ncg=20, cg_tol=1e-3, lam=lam, **kw))
 
@@ -250,18 +234,20 @@ def step(lam, **kw):
 def test_defaults_issue_no_call_and_return_none():
     script = going(7, 2)
     fake = NewtonFake([script], nl=2)
-    out = drive(fake, FitOptions(), 2, 0, 7, TOL, False, False, newton=GaussNewtonOptions())
-    assert fake.log == [UNRECORDED, recorded(7)] and len(out) == 5 and out[0] is script and out[4] is None
-    assert newton_history(None, 0) is None and "gauss_newton" not in history_entry(FitOptions(), [1.0], np.dtype(np.float32), None, None, None)
+    out = drive(fake, FitControls(newton=GaussNewtonOptions()), 2, 0, 7, TOL, False, False)
+    assert fake.log == [UNRECORDED, recorded(7)] and out.loops is script and out.newton is None
+    assert "gauss_newton" not in history_entry(FitControls(), out, 0, np.dtype(np.float32))
     fake = NewtonFake([going(7, 2)], nl=2)
-    assert len(drive(fake, FitOptions(), 2, 0, 7, TOL, False, False)) == 4  # (callers that know nothing of the steps)
+    out = drive(fake, FitControls(FitOptions()), 2, 0, 7, TOL, False, False)  # (callers that know nothing of the steps)
+    assert out.newton is None and out.lbfgs is None
 
 
 def test_start_up_rounds_follow_the_solves_and_keep_a_damping_per_slice():
     fake = NewtonFake([going(4, 2)], nl=2, accept=[[1, 0], [1, 1], [0, 1]])
     opts = FitOptions(coeff_solve_rounds=1, gain_solve_sweeps=2)
     newton = GaussNewtonOptions(gauss_newton_rounds=3, gauss_newton_lambda=1e-2)
-    *_, gn = drive(fake, opts, 2, 0, 4, TOL, False, False, newton=newton)
+    out = drive(fake, FitControls(opts, newton), 2, 0, 4, TOL, False, False)
+    gn = out.newton
     want = [("solve_coeffs", (), dict(ridge=1e-6)), ("solve_gains", (2,), dict(damping=0.5)), step([1e-2, 1e-2]), step([1e-3, 1e-1]), step([1e-4, 1e-2]),
             UNRECORDED, recorded(4)]
     assert [e[:2] for e in fake.log] == [e[:2] for e in want]
@@ -273,7 +259,7 @@ def test_start_up_rounds_follow_the_solves_and_keep_a_damping_per_slice():
     assert list(gn["steps"]) == [3, 3] and list(gn["accepted"]) == [2, 2]
     # the loss after every step: the trial's where accepted, the loss before where rejected (calls are log entries 3, 4, 5)
     assert gn["loss"] == [[29.0, 39.0, 50.0], [30.0, 39.0, 49.0]] and gn["cg_iters"] == [[3, 4, 5], [3, 4, 5]]
-    h = history_entry(opts, [1.0], np.dtype(np.float64), None, None, None, newton_history(gn, 1))
+    h = history_entry(FitControls(opts, newton), out, 1, np.dtype(np.float64))
     assert h["gauss_newton"] == {"steps": 3, "accepted": 2, "lambda": pytest.approx(1e-3), "loss": [30.0, 39.0, 49.0], "cg_iters": [3, 4, 5]}
 
 
@@ -282,7 +268,7 @@ def test_a_step_in_every_gap_comes_last_and_skips_the_loops_that_are_over():
     second[1] = (np.arange(3, dtype=np.float64), True, 3)  # loop 1 meets the tolerance inside the second chunk
     fake = NewtonFake([going(5, 3), second, going(2, 3)], nl=3, rows=6, accept=[[1, 1, 1], [1, 0, 0]])
     opts = FitOptions(gain_solve_every=5, coeff_solve_rounds=1, robust_every=5)
-    *_, gn = drive(fake, opts, 3, 2, 12, TOL, False, False, newton=GaussNewtonOptions(gauss_newton_every=5))
+    gn = drive(fake, FitControls(opts, GaussNewtonOptions(gauss_newton_every=5)), 3, 2, 12, TOL, False, False).newton
     names = [e[0] for e in fake.log]
     gap = ["hold_slices", "robust_weights", "solve_coeffs", "solve_gains", "gauss_newton_step"]
     assert names == ["solve_coeffs", "run_slices", "run_slices"] + gap + ["run_slices"] + gap + ["run_slices", "hold_slices"]
@@ -296,7 +282,7 @@ def test_a_step_in_every_gap_comes_last_and_skips_the_loops_that_are_over():
 
 def test_steps_alone_chunk_the_loop():
     fake = NewtonFake([going(4, 1), going(4, 1), going(2, 1)], accept=[[1], [1]])
-    *_, gn = drive(fake, FitOptions(), 1, 0, 10, TOL, False, False, newton=GaussNewtonOptions(gauss_newton_every=4, gauss_newton_cg_iters=3, gauss_newton_cg_tol=0.0))
+    gn = drive(fake, FitControls(newton=GaussNewtonOptions(gauss_newton_every=4, gauss_newton_cg_iters=3, gauss_newton_cg_tol=0.0)), 1, 0, 10, TOL, False, False).newton
     assert [e[0] for e in fake.log] == ["run_slices", "run_slices", "hold_slices", "gauss_newton_step", "run_slices", "hold_slices", "gauss_newton_step",
                                         "run_slices", "hold_slices"]
     assert fake.log[3][2] == dict(ncg=3, cg_tol=0.0, lam=[1e-3], slice_mask=[1], reset_moments=True) and list(gn["steps"]) == [2]

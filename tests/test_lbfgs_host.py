@@ -12,11 +12,10 @@ import numpy as np
 import pytest
 
 from calamity_amd import _lib, calibration, synthetic
-from calamity_amd.fit_loop import FitOptions, GaussNewtonOptions, LbfgsOptions, drive, history_entry, lbfgs_history
+from calamity_amd.fit_loop import FitControls, FitOptions, GaussNewtonOptions, LbfgsOptions, drive, history_entry
+from fit_loop_cases import TOL, UNRECORDED, LbfgsFake, going, recorded
 from gauss_newton_ref import Ref
 from lbfgs_ref import LbfgsRef, two_loop
-from test_fit_loop_host import TOL, UNRECORDED, going, recorded
-from test_gauss_newton_host import NewtonFake
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -178,18 +177,6 @@ def test_public_calls_refuse_before_any_device_work():
 
 
 # ---- the calls drive issues
-class LbfgsFake(NewtonFake):
-    """``done``: per call the iterations every slice reports."""
-
-    def lbfgs(self, nsteps, **kw):
-        self._put("lbfgs", (nsteps,), kw)
-        k = len(self.log)
-        mask = np.asarray(kw.get("slice_mask", np.ones(self.nl)), dtype=bool)
-        return dict(loss_before=np.full(self.nl, 10.0 * k), loss_after=np.full(self.nl, 10.0 * k - 1.0), iters=np.where(mask, nsteps, 0),
-                    evals=np.where(mask, nsteps + 1, 0), pairs_dropped=np.zeros(self.nl, dtype=np.int64), status=np.where(mask, 0, 4),
-                    losses=np.zeros((self.nl, nsteps + 1)))
-
-
 def call(n, **kw):
     return ("lbfgs", (n,), dict(dict(history=8, max_ls=20, ftol=0.0, freeze_model=False), **kw))
 
@@ -197,25 +184,26 @@ def call(n, **kw):
 def test_defaults_issue_no_call_and_the_tuples_stay_as_they_are():
     script = going(7, 2)
     fake = LbfgsFake([script], nl=2)
-    out = drive(fake, FitOptions(), 2, 0, 7, TOL, False, False, lbfgs=LbfgsOptions())
-    assert fake.log == [UNRECORDED, recorded(7)] and len(out) == 5 and out[0] is script and out[4] is None
-    assert len(drive(LbfgsFake([going(7, 2)], nl=2), FitOptions(), 2, 0, 7, TOL, False, False)) == 4
-    assert len(drive(LbfgsFake([going(7, 2)], nl=2), FitOptions(), 2, 0, 7, TOL, False, False, newton=GaussNewtonOptions())) == 5
-    out = drive(LbfgsFake([going(7, 2)], nl=2), FitOptions(), 2, 0, 7, TOL, False, False, newton=GaussNewtonOptions(), lbfgs=LbfgsOptions())
-    assert len(out) == 6 and out[4] is None and out[5] is None
-    assert lbfgs_history(None, 0) is None and "lbfgs" not in history_entry(FitOptions(), [1.0], np.dtype(np.float32), None, None, None)
+    out = drive(fake, FitControls(lbfgs=LbfgsOptions()), 2, 0, 7, TOL, False, False)
+    assert fake.log == [UNRECORDED, recorded(7)] and out.loops is script and out.lbfgs is None
+    for controls in (FitControls(FitOptions()), FitControls(newton=GaussNewtonOptions()), FitControls(newton=GaussNewtonOptions(), lbfgs=LbfgsOptions())):
+        out = drive(LbfgsFake([going(7, 2)], nl=2), controls, 2, 0, 7, TOL, False, False)
+        assert out.newton is None and out.lbfgs is None and out.robust is None and out.nsingular is None and out.sweep_singular is None
+    assert "lbfgs" not in history_entry(FitControls(), out, 0, np.dtype(np.float32))
 
 
 def test_start_up_iterations_follow_the_gauss_newton_rounds():
     fake = LbfgsFake([going(4, 2)], nl=2, accept=[[1, 1]])
     opts = FitOptions(coeff_solve_rounds=1, gain_solve_sweeps=2)
-    *_, gn, lb = drive(fake, opts, 2, 0, 4, TOL, False, False, newton=GaussNewtonOptions(gauss_newton_rounds=1),
-                       lbfgs=LbfgsOptions(lbfgs_steps=6, lbfgs_history=3, lbfgs_max_ls=5, lbfgs_ftol=1e-7))
+    controls = FitControls(opts, GaussNewtonOptions(gauss_newton_rounds=1), LbfgsOptions(lbfgs_steps=6, lbfgs_history=3, lbfgs_max_ls=5, lbfgs_ftol=1e-7))
+    out = drive(fake, controls, 2, 0, 4, TOL, False, False)
+    gn, lb = out.newton, out.lbfgs
     assert [e[0] for e in fake.log] == ["solve_coeffs", "solve_gains", "gauss_newton_step", "lbfgs", "run_slices", "run_slices"]
     assert fake.log[3] == call(6, history=3, max_ls=5, ftol=1e-7) and fake.log[4] == UNRECORDED
     assert list(gn["steps"]) == [1, 1]
     assert list(lb["calls"]) == [1, 1] and list(lb["iters"]) == [6, 6] and list(lb["evals"]) == [7, 7] and lb["loss"] == [[39.0], [39.0]]
-    h = history_entry(opts, [1.0], np.dtype(np.float64), None, None, None, None, lbfgs_history(lb, 1))
+    out.newton = None  # (the entry of a fit without the steps)
+    h = history_entry(controls, out, 1, np.dtype(np.float64))
     assert h["lbfgs"] == {"calls": 1, "iters": 6, "evals": 7, "loss": [39.0], "status": 0} and "gauss_newton" not in h
 
 
@@ -224,7 +212,7 @@ def test_the_iterations_of_a_gap_come_last_and_skip_the_loops_that_are_over():
     second[1] = (np.arange(3, dtype=np.float64), True, 3)  # loop 1 meets the tolerance inside the second chunk
     fake = LbfgsFake([going(5, 3), second, going(2, 3)], nl=3, rows=6, accept=[[1, 1, 1], [1, 0, 0]])
     opts = FitOptions(gain_solve_every=5, coeff_solve_rounds=1, robust_every=5)
-    *_, lb = drive(fake, opts, 3, 2, 12, TOL, False, True, newton=GaussNewtonOptions(gauss_newton_every=5), lbfgs=LbfgsOptions(lbfgs_steps=2, lbfgs_every=5))
+    lb = drive(fake, FitControls(opts, GaussNewtonOptions(gauss_newton_every=5), LbfgsOptions(lbfgs_steps=2, lbfgs_every=5)), 3, 2, 12, TOL, False, True).lbfgs
     names = [e[0] for e in fake.log]
     gap = ["hold_slices", "robust_weights", "solve_coeffs", "solve_gains", "gauss_newton_step", "lbfgs"]
     assert names == ["solve_coeffs", "lbfgs", "run_slices", "run_slices"] + gap + ["run_slices"] + gap + ["run_slices", "hold_slices"]
@@ -237,7 +225,7 @@ def test_the_iterations_of_a_gap_come_last_and_skip_the_loops_that_are_over():
 
 def test_iterations_alone_chunk_the_loop():
     fake = LbfgsFake([going(4, 1), going(4, 1), going(2, 1)])
-    *_, lb = drive(fake, FitOptions(), 1, 0, 10, TOL, False, False, lbfgs=LbfgsOptions(lbfgs_steps=3, lbfgs_every=4))
+    lb = drive(fake, FitControls(lbfgs=LbfgsOptions(lbfgs_steps=3, lbfgs_every=4)), 1, 0, 10, TOL, False, False).lbfgs
     assert [e[0] for e in fake.log] == ["lbfgs", "run_slices", "run_slices", "hold_slices", "lbfgs", "run_slices", "hold_slices", "lbfgs", "run_slices",
                                         "hold_slices"]
     assert fake.log[4] == call(3, slice_mask=[1], reset_moments=True) and list(lb["calls"]) == [3]
