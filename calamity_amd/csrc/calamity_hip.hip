@@ -1678,16 +1678,45 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
   int model_pass(int planes, Rows rows) {
     const size_t plane = (size_t)nbls * fpad;
     CAL_TRY(model_buf.reserve(planes * plane * sizeof(T)));
-    const std::vector<DevState> saved(h_state, h_state + nslices);
-    begin_pass_state();
-    CAL_TRY(push_state());
+    PassGuard G;
+    CAL_TRY(pass_begin(G));
     const FusedArgs<T> a = model_args();
     launch_fused<MODE_MODEL>(a, false);
     rows(a.model_r, a.model_i, planes == 3 ? model_buf.as<T>() + 2 * plane : nullptr);
     HIP_TRY(hipGetLastError());
-    std::copy(saved.begin(), saved.end(), h_state);
-    CAL_TRY(push_state());
-    return CAL_OK;
+    return pass_restore_state(G);
+  }
+  // The loop state around one-off passes: pass_begin saves the host mirror, clears the stop flags and pushes; pass_restore_state puts it
+  // back and pushes again.  A Gauss-Newton or L-BFGS call holds one guard over all its passes, with what it has substituted: pass_end.
+  struct PassGuard {
+    bool data = false, coefs = false;
+    std::vector<DevState> saved;
+  };
+  int pass_begin(PassGuard& G) {
+    G.saved.assign(h_state, h_state + nslices);
+    begin_pass_state();
+    return push_state();
+  }
+  int pass_restore_state(const PassGuard& G) {
+    std::copy(G.saved.begin(), G.saved.end(), h_state);
+    return push_state();
+  }
+
+  // ---- the two launch shapes of the post-fit kernels: every row kernel and antenna kernel goes through these ---------------
+  struct RowPlanes { T *u_r = nullptr, *u_i = nullptr, *q = nullptr; };  // the three planes of model_buf behind a rows kernel
+  template <typename K, typename... A>
+  void launch_rows(K kern, size_t lds, A... a) {  // one wave per baseline row, four rows per block (row_walk.hpp)
+    hipLaunchKernelGGL(kern, dim3((nbls + 3) / 4), dim3(256), lds, stream, a...);
+  }
+  template <typename K, typename... A>
+  void launch_ants(K kern, A... a) {  // block = (antenna, 64 V channels), channel-block major
+    constexpr int V = 16 / (int)sizeof(T);
+    const int cblocks = (fpad + 64 * V - 1) / (64 * V);
+    hipLaunchKernelGGL(kern, dim3(nants * cblocks), dim3(256), 0, stream, a...);
+  }
+  void launch_gn_data(const T* jp_r, const T* jp_i, const GnScal* scal) {  // G m (+ s_t J p) from gn_m into the data planes
+    launch_rows(gn_data_kernel<T>, 0, gn_m.as<T>(), gn_m.as<T>() + (size_t)nbls * fpad, jp_r, jp_i, gains.as<T2>(), bl_ant.as<int2>(), scal, na_slice,
+                data_r.as<T>(), data_i.as<T>(), nbls, nfreqs, fpad);
   }
   // a call's slice mask on the device (gs_mask); *dev is null where the call has none
   int upload_slice_mask(const uint8_t* host, const unsigned char** dev) {
@@ -1723,6 +1752,18 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
       HIP_TRY(hipMemsetAsync(v.as<T>() + off, 0, n * sizeof(T), stream));
     return CAL_OK;
   }
+  // ... in the slots of the selected slices (no mask: all), one run of neighbouring slices at a time: gain_reals reals of the gain slots
+  // gain_m, gain_v per slice (0: none of them) and, with_coeffs, the slice's run of both coefficient planes
+  int reset_slice_moments(const uint8_t* mask, DevBuf& gain_m, DevBuf& gain_v, size_t gain_reals, bool with_coeffs) {
+    CAL_TRY(for_selected_slice_runs(mask, [&](int t, int t1) {
+      if (gain_reals) CAL_TRY(reset_moment_slots(gain_m, gain_v, (size_t)t * gain_reals, (size_t)(t1 - t) * gain_reals));
+      const size_t n = with_coeffs ? (size_t)(h_slice_coff[t1] - h_slice_coff[t]) : 0;
+      for (int plane = 0; plane < 2 && n > 0; ++plane) CAL_TRY(reset_moment_slots(coef_m, coef_v, (size_t)plane * ncoef + h_slice_coff[t], n));
+      return (int)CAL_OK;
+    }));
+    HIP_TRY(hipGetLastError());
+    return CAL_OK;
+  }
 
   // cal_solver_fit_quality: the model pass of model(), then quality_rows_kernel and quality_ant_kernel (fit_quality_kernels.hpp).
   int fit_quality(const void* g_r, const void* g_i, double* chisq_ant, double* wsum_ant, double* chisq_bl, double* wsum_bl) override {
@@ -1746,12 +1787,9 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     double* o_cb = o_wa + nant_out;
     double* o_wb = o_cb + nbls;
     CAL_TRY(model_pass(2, [&](T* model_r, T* model_i, T*) {
-      hipLaunchKernelGGL(quality_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, model_r, model_i, data_r.as<T>(), data_i.as<T>(),
-                         wgts.as<T>(), g, bl_ant.as<int2>(), nbls, nfreqs, fpad, o_cb, o_wb);
-      constexpr int V = 16 / (int)sizeof(T);
-      const int cblocks = (fpad + 64 * V - 1) / (64 * V);
-      hipLaunchKernelGGL(quality_ant_kernel<T>, dim3(nants * cblocks), dim3(256), 0, stream, model_r, wgts.as<T>(), ant_ptr.as<int>(),
-                         ant_ent.as<int2>(), nants, nfreqs, fpad, o_ca, o_wa);
+      launch_rows(quality_rows_kernel<T>, 0, model_r, model_i, data_r.as<T>(), data_i.as<T>(), wgts.as<T>(), g, bl_ant.as<int2>(), nbls, nfreqs,
+                  fpad, o_cb, o_wb);
+      launch_ants(quality_ant_kernel<T>, model_r, wgts.as<T>(), ant_ptr.as<int>(), ant_ent.as<int2>(), nants, nfreqs, fpad, o_ca, o_wa);
     }));
     // the antenna planes of every rank's baselines add up to the array's: ONE all-reduce of 2 nants nfreqs doubles
     if (comm_on()) CAL_TRY(all_reduce(o_ca, 2 * nant_out, CAL_XCHG_F64, CAL_XCHG_SUM));
@@ -1784,13 +1822,12 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
       }
       const unsigned char* mask = nullptr;
       CAL_TRY(upload_slice_mask(d->slice_mask, &mask));
+      static_assert(kRobustRows == 4, "robust_rows_kernel walks the rows like the other row kernels");
       const bool lds = fpad <= robust_lds_fpad<T>();
-      const size_t lds_bytes = lds ? (size_t)kRobustRows * fpad * sizeof(T) : 0;
       auto launch = [&](T* model_r, T* model_i) {
-        auto* kern = lds ? robust_rows_kernel<T, true> : robust_rows_kernel<T, false>;
-        hipLaunchKernelGGL(kern, dim3((nbls + kRobustRows - 1) / kRobustRows), dim3(64 * kRobustRows), lds_bytes, stream, model_r, model_i,
-                           data_r.as<T>(), data_i.as<T>(), rw_w0.as<T>(), wgts.as<T>(), gains.as<T2>(), bl_ant.as<int2>(), mask, na_slice, nbls, nfreqs,
-                           fpad, d->kind, d->threshold, o_scale, o_ndown);
+        launch_rows(lds ? robust_rows_kernel<T, true> : robust_rows_kernel<T, false>, lds ? (size_t)kRobustRows * fpad * sizeof(T) : 0, model_r,
+                    model_i, data_r.as<T>(), data_i.as<T>(), rw_w0.as<T>(), wgts.as<T>(), gains.as<T2>(), bl_ant.as<int2>(), mask, na_slice, nbls,
+                    nfreqs, fpad, d->kind, d->threshold, o_scale, o_ndown);
       };
       if (d->kind == CAL_ROBUST_NONE) {
         launch(nullptr, nullptr);
@@ -1854,43 +1891,42 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kCsLdsDoubles * (int)sizeof(double)));
     return CAL_OK;
   }
-  struct RowPlanes { T *u_r = nullptr, *u_i = nullptr, *q = nullptr; };  // the three planes of model_buf behind a rows kernel
-  // the model pass of model(), then gain_solve_rows_kernel: the planes the antenna sweeps read
-  int gain_planes(RowPlanes& P) {
+  // the model pass of model(), then gain_solve_rows_kernel: the planes the antenna sweeps read.  before(P) sees the model planes
+  // (P.u_r, P.u_i) before the rows kernel overwrites them.
+  template <typename Before = void (*)(const RowPlanes&)>
+  int gain_planes(RowPlanes& P, Before before = [](const RowPlanes&) {}) {
     return model_pass(3, [&](T* model_r, T* model_i, T* third) {
       P = RowPlanes{model_r, model_i, third};
-      hipLaunchKernelGGL(gain_solve_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, P.u_r, P.u_i, P.q, data_r.as<T>(), data_i.as<T>(),
-                         wgts.as<T>(), bl_ant.as<int2>(), nbls, nfreqs, fpad);
+      before(P);
+      launch_rows(gain_solve_rows_kernel<T>, 0, P.u_r, P.u_i, P.q, data_r.as<T>(), data_i.as<T>(), wgts.as<T>(), bl_ant.as<int2>(), nbls, nfreqs, fpad);
     });
   }
   // the model pass of model(), then coeff_solve_rows_kernel: the planes the Gram kernel reads
   int coeff_planes(RowPlanes& P) {
     return model_pass(3, [&](T* model_r, T* model_i, T* third) {
       P = RowPlanes{model_r, model_i, third};
-      hipLaunchKernelGGL(coeff_solve_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, P.u_r, P.u_i, P.q, data_r.as<T>(), data_i.as<T>(),
-                         wgts.as<T>(), gains.as<T2>(), bl_ant.as<int2>(), nbls, nfreqs, fpad);
+      launch_rows(coeff_solve_rows_kernel<T>, 0, P.u_r, P.u_i, P.q, data_r.as<T>(), data_i.as<T>(), wgts.as<T>(), gains.as<T2>(), bl_ant.as<int2>(),
+                  nbls, nfreqs, fpad);
     });
   }
   // One antenna sweep: gain_solve_ant_kernel into gs_out (num_r | num_i | den), then the exchange of its last `nplanes` planes.  The
   // planes of every rank's baselines add up to the array's: ONE all-reduce of nplanes nants nfreqs doubles per sweep.
   int antenna_sweep(const RowPlanes& P, int nplanes) {
     const size_t nant_out = (size_t)nants * nfreqs;
-    constexpr int V = 16 / (int)sizeof(T);
-    const int cblocks = (fpad + 64 * V - 1) / (64 * V);
-    hipLaunchKernelGGL(gain_solve_ant_kernel<T>, dim3(nants * cblocks), dim3(256), 0, stream, P.u_r, P.u_i, P.q, gains.as<T2>(), gs_ptr.as<int>(),
-                       gs_ent.as<int2>(), nants, nfreqs, fpad, gs_out.as<double>());
+    launch_ants(gain_solve_ant_kernel<T>, P.u_r, P.u_i, P.q, gains.as<T2>(), gs_ptr.as<int>(), gs_ent.as<int2>(), nants, nfreqs, fpad,
+                gs_out.as<double>());
     HIP_TRY(hipGetLastError());
     if (comm_on()) CAL_TRY(all_reduce(gs_out.as<double>() + (3 - nplanes) * nant_out, nplanes * nant_out, CAL_XCHG_F64, CAL_XCHG_SUM));
     return CAL_OK;
   }
-  // The end of a solve call: its two counters (cnt: null where it has none), what set_optimizer leaves in the moment slots of the selected
-  // slices -- reset_run(t, t1) for every run of neighbouring ones -- then the stream drained and the result filled in.
+  // The end of a solve call: its two counters (cnt: null where it has none), what set_optimizer leaves in the moment slots the call
+  // has solved -- reset_moments() -- then the stream drained and the result filled in.
   template <typename Res, typename Reset>
-  int finish_solve(const DevBuf* cnt, Res* res, int reset, const uint8_t* mask, Reset reset_run) {
+  int finish_solve(const DevBuf* cnt, Res* res, int reset, Reset reset_moments) {
     int counts[2] = {0, 0};
     if (cnt) HIP_TRY(hipMemcpyAsync(counts, cnt->p, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
     if (reset) {
-      CAL_TRY(for_selected_slice_runs(mask, reset_run));
+      CAL_TRY(reset_moments());
       HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipStreamSynchronize(stream));
@@ -1924,8 +1960,8 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
       HIP_TRY(hipGetLastError());
     }
     const size_t per = (size_t)na_slice * fpad * 2;  // reals of the gain slots per slice
-    return finish_solve(nullptr, (cal_coeff_solve_result*)nullptr, d->reset_gain_moments, d->slice_mask,
-                        [&](int t, int t1) { return reset_moment_slots(gains_m, gains_v, (size_t)t * per, (size_t)(t1 - t) * per); });
+    return finish_solve(nullptr, (cal_coeff_solve_result*)nullptr, d->reset_gain_moments,
+                        [&] { return reset_slice_moments(d->slice_mask, gains_m, gains_v, per, false); });
   }
 
   // ---- cal_solver_normal_product / cal_solver_gauss_newton_step (gauss_newton_kernels.hpp) -----------------------
@@ -1984,16 +2020,7 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     }
     return CAL_OK;
   }
-  struct GnGuard {  // what a call has substituted and must put back, and the loop state it found
-    bool data = false, coefs = false;
-    std::vector<DevState> saved;
-  };
-  int gn_begin(GnGuard& G) {
-    G.saved.assign(h_state, h_state + nslices);
-    begin_pass_state();
-    return push_state();
-  }
-  int gn_restore_data(GnGuard& G) {
+  int gn_restore_data(PassGuard& G) {
     if (!G.data) return CAL_OK;
     const size_t plane = (size_t)nbls * fpad;
     HIP_TRY(hipMemcpyAsync(data_r.p, gn_sd.p, plane * sizeof(T), hipMemcpyDeviceToDevice, stream));
@@ -2001,20 +2028,20 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     G.data = false;
     return CAL_OK;
   }
-  int gn_restore_coefs(GnGuard& G) {
+  int gn_restore_coefs(PassGuard& G) {
     if (!G.coefs) return CAL_OK;
     HIP_TRY(hipMemcpyAsync(coef.p, gn_save.as<T>() + gn_go(), 2 * (size_t)ncoef * sizeof(T), hipMemcpyDeviceToDevice, stream));
     G.coefs = false;
     return CAL_OK;
   }
   // data, coefficients and loop state back as the call found them -- on every path out of a call, failures included
-  int gn_end(GnGuard& G, int rc) {
+  int pass_end(PassGuard& G, int rc, const char* who) {
     const std::string msg = g_err;
     int rc2 = gn_restore_data(G);
     if (rc2 == CAL_OK) rc2 = gn_restore_coefs(G);
     std::copy(G.saved.begin(), G.saved.end(), h_state);
     if (rc2 == CAL_OK) rc2 = push_state();
-    if (rc2 == CAL_OK && hipStreamSynchronize(stream) != hipSuccess) rc2 = fail(CAL_ERR_HIP, "hipStreamSynchronize failed after a Gauss-Newton call");
+    if (rc2 == CAL_OK && hipStreamSynchronize(stream) != hipSuccess) rc2 = fail(CAL_ERR_HIP, "%s: hipStreamSynchronize failed", who);
     if (timing && rc2 == CAL_OK) rc2 = collect_timing();
     if (rc != CAL_OK) {
       g_err = msg;
@@ -2033,60 +2060,50 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
   }
   // m = A c into gn_m (with_precond: D into gn_D from the same model pass), then the data planes saved and replaced by G m and the gradient
   // of that into gn_g0
-  int gn_linearize(GnGuard& G, bool with_precond) {
+  int gn_linearize(PassGuard& G, bool with_precond) {
     const size_t plane = (size_t)nbls * fpad;
     hipError_t ce = hipSuccess;
-    if (with_precond) CAL_TRY(gain_sweep_setup());
-    T *u_r = nullptr, *u_i = nullptr, *q_rows = nullptr;
-    CAL_TRY(model_pass(with_precond ? 3 : 2, [&](T* model_r, T* model_i, T* third) {
-      ce = hipMemcpyAsync(gn_m.p, model_r, 2 * plane * sizeof(T), hipMemcpyDeviceToDevice, stream);  // (model_i = model_r + plane)
-      (void)model_i;
-      if (with_precond) {
-        u_r = model_r, u_i = model_i, q_rows = third;
-        hipLaunchKernelGGL(gain_solve_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, u_r, u_i, q_rows, data_r.as<T>(), data_i.as<T>(),
-                           wgts.as<T>(), bl_ant.as<int2>(), nbls, nfreqs, fpad);
-      }
-    }));
-    HIP_TRY(ce);
+    const auto keep_model = [&](const RowPlanes& M) {  // (the imaginary plane follows the real one)
+      ce = hipMemcpyAsync(gn_m.p, M.u_r, 2 * plane * sizeof(T), hipMemcpyDeviceToDevice, stream);
+    };
     if (with_precond) {
-      constexpr int V = 16 / (int)sizeof(T);
-      const int cblocks = (fpad + 64 * V - 1) / (64 * V);
-      hipLaunchKernelGGL(gain_solve_ant_kernel<T>, dim3(nants * cblocks), dim3(256), 0, stream, u_r, u_i, q_rows, gains.as<T2>(), gs_ptr.as<int>(),
-                         gs_ent.as<int2>(), nants, nfreqs, fpad, gs_out.as<double>());
+      CAL_TRY(gain_sweep_setup());
+      RowPlanes P;
+      CAL_TRY(gain_planes(P, keep_model));
+      HIP_TRY(ce);
+      CAL_TRY(antenna_sweep(P, 3));  // (gn_check has refused a communicator: no exchange)
       hipLaunchKernelGGL(gn_precond_gain_kernel, dim3(grid_for((long long)nants * fpad)), dim3(256), 0, stream,
                          gs_out.as<double>() + 2 * (size_t)nants * nfreqs, gn_D.as<double>(), nants, nfreqs, fpad);
       double* rowq = gn_rows.as<double>() + 2 * (size_t)nbls;
-      hipLaunchKernelGGL(gn_precond_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, gains.as<T2>(), wgts.as<T>(), bl_ant.as<int2>(), nbls,
-                         nfreqs, fpad, rowq);
+      launch_rows(gn_precond_rows_kernel<T>, 0, gains.as<T2>(), wgts.as<T>(), bl_ant.as<int2>(), nbls, nfreqs, fpad, rowq);
       hipLaunchKernelGGL(gn_precond_coeff_kernel, dim3((ngrps + 255) / 256), dim3(256), 0, stream, rowq, gn_grp.as<GnGroup>(), ngrps, ncoef,
                          gn_D.as<double>() + gn_go());
       HIP_TRY(hipGetLastError());
+    } else {
+      CAL_TRY(model_pass(2, [&](T* model_r, T* model_i, T*) { keep_model(RowPlanes{model_r, model_i, nullptr}); }));
+      HIP_TRY(ce);
     }
     HIP_TRY(hipMemcpyAsync(gn_sd.p, data_r.p, plane * sizeof(T), hipMemcpyDeviceToDevice, stream));
     HIP_TRY(hipMemcpyAsync(gn_sd.as<T>() + plane, data_i.p, plane * sizeof(T), hipMemcpyDeviceToDevice, stream));
     G.data = true;
-    hipLaunchKernelGGL(gn_data_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, gn_m.as<T>(), gn_m.as<T>() + plane, (const T*)nullptr,
-                       (const T*)nullptr, gains.as<T2>(), bl_ant.as<int2>(), (const GnScal*)nullptr, na_slice, data_r.as<T>(), data_i.as<T>(), nbls, nfreqs,
-                       fpad);
+    launch_gn_data(nullptr, nullptr, nullptr);
     HIP_TRY(hipGetLastError());
     return gn_grad_pass(gn_g0.as<T>());
   }
   // gn_ns = N s (+ lambda D s with D) for the direction in gn_s, and the partials of s . gn_ns; the coefficients are put back before it returns,
   // the data planes stay substituted
-  int gn_product(GnGuard& G, const double* D) {
+  int gn_product(PassGuard& G, const double* D) {
     const size_t plane = (size_t)nbls * fpad, cb = 2 * (size_t)ncoef * sizeof(T);
     HIP_TRY(hipMemcpyAsync(gn_save.as<T>() + gn_go(), coef.p, cb, hipMemcpyDeviceToDevice, stream));
     HIP_TRY(hipMemcpyAsync(coef.p, gn_s.as<T>() + gn_go(), cb, hipMemcpyDeviceToDevice, stream));
     G.coefs = true;
     CAL_TRY(model_pass(2, [&](T* model_r, T* model_i, T*) {
-      hipLaunchKernelGGL(gn_tangent_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, gn_m.as<T>(), gn_m.as<T>() + plane, model_r, model_i,
-                         gains.as<T2>(), gn_s.as<T2>(), wgts.as<T>(), bl_ant.as<int2>(), nbls, nfreqs, fpad, gn_rows.as<double>());
+      launch_rows(gn_tangent_rows_kernel<T>, 0, gn_m.as<T>(), gn_m.as<T>() + plane, model_r, model_i, gains.as<T2>(), gn_s.as<T2>(), wgts.as<T>(),
+                  bl_ant.as<int2>(), nbls, nfreqs, fpad, gn_rows.as<double>());
     }));
     CAL_TRY(gn_restore_coefs(G));
     hipLaunchKernelGGL(gn_scale_kernel, dim3(nslices), dim3(256), 0, stream, gn_rows.as<double>(), gn_rowptr.as<int>(), gn_scal.as<GnScal>());
-    hipLaunchKernelGGL(gn_data_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, gn_m.as<T>(), gn_m.as<T>() + plane, model_buf.as<T>(),
-                       model_buf.as<T>() + plane, gains.as<T2>(), bl_ant.as<int2>(), gn_scal.as<GnScal>(), na_slice, data_r.as<T>(), data_i.as<T>(), nbls,
-                       nfreqs, fpad);
+    launch_gn_data(model_buf.as<T>(), model_buf.as<T>() + plane, gn_scal.as<GnScal>());
     HIP_TRY(hipGetLastError());
     CAL_TRY(gn_grad_pass(nullptr));
     hipLaunchKernelGGL(gn_diff_kernel<T>, dim3(kGnBlocks, nslices), dim3(256), 0, stream, gn_space(), comm.as<T>(), grad_c0(), gn_g0.as<T>(), gn_s.as<T>(), D,
@@ -2112,8 +2129,8 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
       x.scale = 1.0;
     }
     HIP_TRY(copy_sync(gn_scal.p, sc.data(), sc.size() * sizeof(GnScal), hipMemcpyHostToDevice));
-    GnGuard G;
-    int rc = gn_begin(G);
+    PassGuard G;
+    int rc = pass_begin(G);
     if (rc == CAL_OK) rc = gn_linearize(G, false);
     if (rc == CAL_OK) rc = gn_product(G, nullptr);
     if (rc == CAL_OK) {
@@ -2121,7 +2138,7 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
       hipLaunchKernelGGL(gn_round_kernel<T>, dim3(grid_for((long long)gn_np())), dim3(256), 0, stream, gn_ns.as<double>(), out, (long long)gn_np());
       if (hipGetLastError() != hipSuccess) rc = fail(CAL_ERR_HIP, "normal_product: launch failed");
     }
-    CAL_TRY(gn_end(G, rc));
+    CAL_TRY(pass_end(G, rc, "normal_product"));
     const T* out = gn_g0.as<T>();
     CAL_TRY(download_rows(out_g_r, out, nants, 2, 0));
     CAL_TRY(download_rows(out_g_i, out, nants, 2, 1));
@@ -2153,7 +2170,7 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     GnScal* scal_d = gn_scal.as<GnScal>();
     double *x = gn_x.as<double>(), *r = gn_res.as<double>(), *ns = gn_ns.as<double>(), *D = gn_D.as<double>(), *part = gn_part.as<double>();
     T* s = gn_s.as<T>();
-    GnGuard G;
+    PassGuard G;
     auto body = [&]() -> int {
       // the gradient at the data (its loss is the loss before the step), the linearisation, the right-hand side
       CAL_TRY(gn_grad_pass(s));
@@ -2198,21 +2215,13 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
         }
         return (int)CAL_OK;
       }));
-      if (d->reset_moments) {
-        // what set_optimizer leaves in the gain and coefficient slots, for the accepted slices
-        CAL_TRY(for_selected_slice_runs(accepted.data(), [&](int t, int t1) {
-          CAL_TRY(reset_moment_slots(gains_m, gains_v, (size_t)t * ng, (size_t)(t1 - t) * ng));
-          const size_t n = (size_t)(h_slice_coff[t1] - h_slice_coff[t]);
-          for (int plane = 0; plane < 2 && n > 0; ++plane) CAL_TRY(reset_moment_slots(coef_m, coef_v, (size_t)plane * ncoef + h_slice_coff[t], n));
-          return (int)CAL_OK;
-        }));
-        HIP_TRY(hipGetLastError());
-      }
+      // what set_optimizer leaves in the gain and coefficient slots, for the accepted slices
+      if (d->reset_moments) CAL_TRY(reset_slice_moments(accepted.data(), gains_m, gains_v, ng, true));
       return CAL_OK;
     };
-    int rc = gn_begin(G);
+    int rc = pass_begin(G);
     if (rc == CAL_OK) rc = body();
-    CAL_TRY(gn_end(G, rc));
+    CAL_TRY(pass_end(G, rc, "gauss_newton_step"));
     for (int t = 0; t < nslices; ++t) {
       const bool sel = !d->slice_mask || d->slice_mask[t];
       res[t].loss_before = before[t];
@@ -2293,7 +2302,7 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
       HIP_TRY(hipGetLastError());
       return CAL_OK;
     };
-    GnGuard G;
+    PassGuard G;
     auto body = [&]() -> int {
       CAL_TRY(advance(1));
       for (int k = 0; k < d->nsteps; ++k) {
@@ -2324,20 +2333,13 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
         // what set_optimizer leaves in the slots of the variables that moved
         std::vector<uint8_t> moved(nslices);
         for (int t = 0; t < nslices; ++t) moved[t] = hs[t].ever_moved ? 1 : 0;
-        const size_t ng = (size_t)S.ngs;
-        CAL_TRY(for_selected_slice_runs(moved.data(), [&](int t, int t1) {
-          CAL_TRY(reset_moment_slots(yb_on() ? gb_ym : gains_m, yb_on() ? gb_yv : gains_v, (size_t)t * ng, (size_t)(t1 - t) * ng));
-          const size_t n = frozen ? 0 : (size_t)(h_slice_coff[t1] - h_slice_coff[t]);
-          for (int plane = 0; plane < 2 && n > 0; ++plane) CAL_TRY(reset_moment_slots(coef_m, coef_v, (size_t)plane * ncoef + h_slice_coff[t], n));
-          return (int)CAL_OK;
-        }));
-        HIP_TRY(hipGetLastError());
+        CAL_TRY(reset_slice_moments(moved.data(), yb_on() ? gb_ym : gains_m, yb_on() ? gb_yv : gains_v, (size_t)S.ngs, !frozen));
       }
       return CAL_OK;
     };
-    int rc = gn_begin(G);
+    int rc = pass_begin(G);
     if (rc == CAL_OK) rc = body();
-    CAL_TRY(gn_end(G, rc));
+    CAL_TRY(pass_end(G, rc, "lbfgs"));
     for (int t = 0; t < nslices; ++t) {
       const double f0 = hs[t].status == 4 ? std::numeric_limits<double>::quiet_NaN() : hl[(size_t)t * (d->nsteps + 1)];
       res[t].loss_before = hs[t].status == 3 ? std::numeric_limits<double>::quiet_NaN() : f0;
@@ -2405,12 +2407,7 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
         HIP_TRY(hipGetLastError());
       }
     }
-    // the coefficient slots of a run of slices, one call per plane
-    return finish_solve(&cs_cnt, res, d->reset_coeff_moments, d->slice_mask, [&](int t, int t1) {
-      const size_t n = (size_t)(h_slice_coff[t1] - h_slice_coff[t]);
-      for (int plane = 0; plane < 2 && n > 0; ++plane) CAL_TRY(reset_moment_slots(coef_m, coef_v, (size_t)plane * ncoef + h_slice_coff[t], n));
-      return (int)CAL_OK;
-    });
+    return finish_solve(&cs_cnt, res, d->reset_coeff_moments, [&] { return reset_slice_moments(d->slice_mask, coef_m, coef_v, 0, true); });
   }
 
   // ---- cal_solver_fit_errors -------------------------------------------------------------------------------------
@@ -2487,8 +2484,8 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
         HIP_TRY(hipMemcpyAsync(cnt, dcnt, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
       }
       if (leverage_bl || nsamp_bl) {
-        hipLaunchKernelGGL(fit_error_rows_kernel<T>, dim3((nbls + 3) / 4), dim3(256), 0, stream, fe_part.as<double>(), wgts.as<T>(), nbls, nfreqs,
-                           fpad, nslot, leverage_bl ? o_lev : nullptr, nsamp_bl ? o_ns : nullptr);
+        launch_rows(fit_error_rows_kernel<T>, 0, fe_part.as<double>(), wgts.as<T>(), nbls, nfreqs, fpad, nslot, leverage_bl ? o_lev : nullptr,
+                    nsamp_bl ? o_ns : nullptr);
         HIP_TRY(hipGetLastError());
       }
       if (coeff_var) HIP_TRY(hipMemcpyAsync(coeff_var, o_cv, (size_t)ncoef * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -2562,8 +2559,7 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
       HIP_TRY(hipGetLastError());
     }
     const size_t yper = (size_t)na_slice * gb_kpad * 2;  // reals of the y slots per slice
-    return finish_solve(&gbs_cnt, res, d->reset_gain_moments, d->slice_mask,
-                        [&](int t, int t1) { return reset_moment_slots(gb_ym, gb_yv, (size_t)t * yper, (size_t)(t1 - t) * yper); });
+    return finish_solve(&gbs_cnt, res, d->reset_gain_moments, [&] { return reset_slice_moments(d->slice_mask, gb_ym, gb_yv, yper, false); });
   }
 
   // cal_solver_solve_gain_time_coeffs: solve_gain_coeffs' sequence up to the exchanged planes, then per chunk of antennas either
@@ -2625,8 +2621,7 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
       CAL_TRY(enqueue_expand(gb_y.as<T2>(), gains.as<T2>()));  // gains = g0 + Bt (x) (B) y, behind the last chunk
     }
     // (the times of an antenna share its coefficients: no slice mask, every y slot)
-    return finish_solve(&gts_cnt, res, d->reset_gain_moments, nullptr,
-                        [&](int, int) { return reset_moment_slots(gb_ym, gb_yv, 0, 2 * (size_t)y_rows() * (size_t)y_row()); });
+    return finish_solve(&gts_cnt, res, d->reset_gain_moments, [&] { return reset_moment_slots(gb_ym, gb_yv, 0, 2 * (size_t)y_rows() * (size_t)y_row()); });
   }
 
   int init_coeffs(const void* sr, const void* si) override {

@@ -13,6 +13,7 @@
 // blocks and the factorisation are the shared core of normal_solve.hpp; the two kernels here fetch its operands and write its result.
 #pragma once
 #include "normal_solve.hpp"
+#include "row_walk.hpp"
 
 namespace calk {
 
@@ -33,32 +34,21 @@ __global__ __launch_bounds__(256) void coeff_solve_rows_kernel(T* __restrict__ m
                                                                 const T* __restrict__ wgts, const vec2_t<T>* __restrict__ gains,
                                                                 const int2* __restrict__ bl_ant, int nbls, int nfreqs, int fpad) {
 #pragma clang fp contract(off)
-  constexpr int V = 16 / (int)sizeof(T);
-  typedef T vec_t __attribute__((ext_vector_type(V)));
-  const int lane = threadIdx.x & 63;
-  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);  // wave-uniform
-  if (b >= nbls) return;
-  const int2 ant = bl_ant[b];
-  const long long row = (long long)b * fpad;
-  const vec2_t<T>* __restrict__ gi = gains + (long long)ant.x * fpad;
-  const vec2_t<T>* __restrict__ gj = gains + (long long)ant.y * fpad;
-  for (int f = lane * V; f < fpad; f += 64 * V) {  // fpad is a multiple of 8: whole vectors
-    const vec_t mr = *reinterpret_cast<const vec_t*>(model_r + row + f);
-    const vec_t mi = *reinterpret_cast<const vec_t*>(model_i + row + f);
-    const vec_t dr = *reinterpret_cast<const vec_t*>(data_r + row + f);
-    const vec_t di = *reinterpret_cast<const vec_t*>(data_i + row + f);
-    const vec_t w = *reinterpret_cast<const vec_t*>(wgts + row + f);
-    vec_t a2[2], b2[2];  // V channels of (re, im)
-    a2[0] = *reinterpret_cast<const vec_t*>(gi + f);
-    a2[1] = *reinterpret_cast<const vec_t*>(gi + f + V / 2);
-    b2[0] = *reinterpret_cast<const vec_t*>(gj + f);
-    b2[1] = *reinterpret_cast<const vec_t*>(gj + f + V / 2);
+  constexpr int V = RowWalk<T>::V;
+  typedef typename RowWalk<T>::vec_t vec_t;
+  RowWalk<T> R;
+  if (!R.begin(bl_ant, nbls, fpad)) return;
+  GainPair<T> gp(gains, R.ant, fpad);
+  for (int f = R.lane * V; f < fpad; f += 64 * V) {  // fpad is a multiple of 8: whole vectors
+    const vec_t mr = R.load(model_r, f), mi = R.load(model_i, f);
+    const vec_t dr = R.load(data_r, f), di = R.load(data_i, f);
+    const vec_t w = R.load(wgts, f);
+    gp.load(f);
     vec_t ur, ui, q;
 #pragma unroll
     for (int c = 0; c < V; ++c) {
-      const T ax = a2[(2 * c) / V][(2 * c) % V], ay = a2[(2 * c) / V][(2 * c) % V + 1];
-      const T bx = b2[(2 * c) / V][(2 * c) % V], by = b2[(2 * c) / V][(2 * c) % V + 1];
-      const T Gr = ax * bx + ay * by, Gi = ay * bx - ax * by;  // g_i conj(g_j)
+      const auto g = gp.at(c);
+      const T Gr = g.Gr, Gi = g.Gi;                            // g_i conj(g_j)
       const T rr = dr[c] - (Gr * mr[c] - Gi * mi[c]);          // d - G m
       const T ri = di[c] - (Gr * mi[c] + Gi * mr[c]);
       const bool live = f + c < nfreqs;
@@ -66,9 +56,9 @@ __global__ __launch_bounds__(256) void coeff_solve_rows_kernel(T* __restrict__ m
       ui[c] = live ? w[c] * (Gr * ri - Gi * rr) : (T)0;
       q[c] = live ? w[c] * (Gr * Gr + Gi * Gi) : (T)0;
     }
-    *reinterpret_cast<vec_t*>(model_r + row + f) = ur;
-    *reinterpret_cast<vec_t*>(model_i + row + f) = ui;
-    *reinterpret_cast<vec_t*>(q_rows + row + f) = q;
+    R.store(model_r, f, ur);
+    R.store(model_i, f, ui);
+    R.store(q_rows, f, q);
   }
 }
 

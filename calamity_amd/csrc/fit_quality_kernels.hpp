@@ -9,7 +9,7 @@
 // in double in a fixed order (lane partials, a butterfly over the wave; four segments through LDS in ascending order): no float
 // atomics, two calls give the same bits.  Neither kernel looks at the loop state: a stopped slice is evaluated like any other.
 #pragma once
-#include "fit_kernels.hpp"
+#include "row_walk.hpp"
 
 namespace calk {
 
@@ -21,36 +21,23 @@ __global__ __launch_bounds__(256) void quality_rows_kernel(T* __restrict__ model
                                                             const vec2_t<T>* __restrict__ gains, const int2* __restrict__ bl_ant, int nbls, int nfreqs,
                                                             int fpad, double* __restrict__ chisq_bl, double* __restrict__ wsum_bl) {
 #pragma clang fp contract(off)
-  constexpr int V = 16 / (int)sizeof(T);
-  typedef T vec_t __attribute__((ext_vector_type(V)));
-  const int lane = threadIdx.x & 63;
-  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);  // wave-uniform
-  if (b >= nbls) return;
-  const int2 ant = bl_ant[b];
-  const long long row = (long long)b * fpad;
-  const vec2_t<T>* __restrict__ ga = gains + (long long)ant.x * fpad;
-  const vec2_t<T>* __restrict__ gb = gains + (long long)ant.y * fpad;
+  constexpr int V = RowWalk<T>::V;
+  typedef typename RowWalk<T>::vec_t vec_t;
+  RowWalk<T> R;
+  if (!R.begin(bl_ant, nbls, fpad)) return;
+  GainPair<T> gp(gains, R.ant, fpad);
   double acc_e = 0, acc_w = 0;
-  for (int f = lane * V; f < fpad; f += 64 * V) {  // fpad is a multiple of 8: whole vectors
-    const vec_t mr = *reinterpret_cast<const vec_t*>(model_r + row + f);
-    const vec_t mi = *reinterpret_cast<const vec_t*>(model_i + row + f);
-    const vec_t dr = *reinterpret_cast<const vec_t*>(data_r + row + f);
-    const vec_t di = *reinterpret_cast<const vec_t*>(data_i + row + f);
-    const vec_t w = *reinterpret_cast<const vec_t*>(wgts + row + f);
-    vec_t a2[2], b2[2];  // V channels of (re, im)
-    a2[0] = *reinterpret_cast<const vec_t*>(ga + f);
-    a2[1] = *reinterpret_cast<const vec_t*>(ga + f + V / 2);
-    b2[0] = *reinterpret_cast<const vec_t*>(gb + f);
-    b2[1] = *reinterpret_cast<const vec_t*>(gb + f + V / 2);
+  for (int f = R.lane * V; f < fpad; f += 64 * V) {  // fpad is a multiple of 8: whole vectors
+    const vec_t mr = R.load(model_r, f), mi = R.load(model_i, f);
+    const vec_t dr = R.load(data_r, f), di = R.load(data_i, f);
+    const vec_t w = R.load(wgts, f);
+    gp.load(f);
     vec_t e;
 #pragma unroll
     for (int c = 0; c < V; ++c) {
-      const T g0x = a2[(2 * c) / V][(2 * c) % V], g0y = a2[(2 * c) / V][(2 * c) % V + 1];
-      const T g1x = b2[(2 * c) / V][(2 * c) % V], g1y = b2[(2 * c) / V][(2 * c) % V + 1];
-      const T G_r = g0x * g1x + g0y * g1y;  // g0 conj(g1), calibration.py:1598-1601
-      const T G_i = g0y * g1x - g0x * g1y;
-      const T m_r = G_r * mr[c] - G_i * mi[c];
-      const T m_i = G_i * mr[c] + G_r * mi[c];
+      const auto g = gp.at(c);
+      const T m_r = g.Gr * mr[c] - g.Gi * mi[c];
+      const T m_i = g.Gi * mr[c] + g.Gr * mi[c];
       const T r_r = dr[c] - m_r;
       const T r_i = di[c] - m_i;
       const bool live = f + c < nfreqs;
@@ -59,13 +46,13 @@ __global__ __launch_bounds__(256) void quality_rows_kernel(T* __restrict__ model
       acc_e += (double)ec;
       acc_w += live ? (double)w[c] : 0.0;
     }
-    *reinterpret_cast<vec_t*>(model_r + row + f) = e;
+    R.store(model_r, f, e);
   }
   acc_e = ldsum(acc_e);
   acc_w = ldsum(acc_w);
-  if (lane == 0) {
-    chisq_bl[b] = acc_e;
-    wsum_bl[b] = acc_w;
+  if (R.lane == 0) {
+    chisq_bl[R.b] = acc_e;
+    wsum_bl[R.b] = acc_w;
   }
 }
 

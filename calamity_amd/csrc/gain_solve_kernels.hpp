@@ -13,7 +13,7 @@
 // Products are formed in T, num and den are accumulated in double in a fixed order (the list in baseline order, four segments
 // combined through LDS in ascending order): no float atomics, two calls give the same bits.
 #pragma once
-#include "fit_kernels.hpp"
+#include "row_walk.hpp"
 
 namespace calk {
 
@@ -25,20 +25,15 @@ __global__ __launch_bounds__(256) void gain_solve_rows_kernel(T* __restrict__ mo
                                                                const T* __restrict__ wgts, const int2* __restrict__ bl_ant, int nbls, int nfreqs,
                                                                int fpad) {
 #pragma clang fp contract(off)
-  constexpr int V = 16 / (int)sizeof(T);
-  typedef T vec_t __attribute__((ext_vector_type(V)));
-  const int lane = threadIdx.x & 63;
-  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);  // wave-uniform
-  if (b >= nbls) return;
-  const int2 ant = bl_ant[b];
-  const bool cross = ant.x != ant.y;
-  const long long row = (long long)b * fpad;
-  for (int f = lane * V; f < fpad; f += 64 * V) {  // fpad is a multiple of 8: whole vectors
-    const vec_t mr = *reinterpret_cast<const vec_t*>(model_r + row + f);
-    const vec_t mi = *reinterpret_cast<const vec_t*>(model_i + row + f);
-    const vec_t dr = *reinterpret_cast<const vec_t*>(data_r + row + f);
-    const vec_t di = *reinterpret_cast<const vec_t*>(data_i + row + f);
-    const vec_t w = *reinterpret_cast<const vec_t*>(wgts + row + f);
+  constexpr int V = RowWalk<T>::V;
+  typedef typename RowWalk<T>::vec_t vec_t;
+  RowWalk<T> R;
+  if (!R.begin(bl_ant, nbls, fpad)) return;
+  const bool cross = R.ant.x != R.ant.y;
+  for (int f = R.lane * V; f < fpad; f += 64 * V) {  // fpad is a multiple of 8: whole vectors
+    const vec_t mr = R.load(model_r, f), mi = R.load(model_i, f);
+    const vec_t dr = R.load(data_r, f), di = R.load(data_i, f);
+    const vec_t w = R.load(wgts, f);
     vec_t pr, pi, q;
 #pragma unroll
     for (int c = 0; c < V; ++c) {
@@ -47,9 +42,9 @@ __global__ __launch_bounds__(256) void gain_solve_rows_kernel(T* __restrict__ mo
       pi[c] = live ? w[c] * (di[c] * mr[c] - dr[c] * mi[c]) : (T)0;
       q[c] = live ? w[c] * (mr[c] * mr[c] + mi[c] * mi[c]) : (T)0;
     }
-    *reinterpret_cast<vec_t*>(model_r + row + f) = pr;
-    *reinterpret_cast<vec_t*>(model_i + row + f) = pi;
-    *reinterpret_cast<vec_t*>(q_rows + row + f) = q;
+    R.store(model_r, f, pr);
+    R.store(model_i, f, pi);
+    R.store(q_rows, f, q);
   }
 }
 

@@ -18,7 +18,7 @@
 // residual, N s and D are double.  Every sum of reals runs in double in a fixed order (per thread ascending, a butterfly over the wave,
 // the waves and then the blocks in ascending order): no atomics, two calls give the same bits.  The per-slice scalars live on the device.
 #pragma once
-#include "fit_kernels.hpp"
+#include "row_walk.hpp"
 
 namespace calk {
 
@@ -51,14 +51,9 @@ __device__ __forceinline__ long long gn_index(const GnSpace& S, int t, long long
   live = true;
   return S.go + (long long)plane * S.ncoef + S.coff[t] + (k - (long long)plane * nc);
 }
-__device__ __forceinline__ double gn_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 // the block's sum (256 threads) in thread 0
 __device__ __forceinline__ double gn_block_sum(double v, double* s_w) {
-  v = gn_wave_sum(v);
+  v = ldsum(v);
   if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
   __syncthreads();
   return s_w[0] + s_w[1] + s_w[2] + s_w[3];
@@ -124,8 +119,8 @@ __global__ __launch_bounds__(256) void gn_tangent_rows_kernel(const T* __restric
     *reinterpret_cast<vec_t*>(t_r + row + f) = jr;
     *reinterpret_cast<vec_t*>(t_i + row + f) = ji;
   }
-  sum_m = gn_wave_sum(sum_m);
-  sum_j = gn_wave_sum(sum_j);
+  sum_m = ldsum(sum_m);
+  sum_j = ldsum(sum_j);
   if (lane == 0) {
     row_sums[2 * (long long)b] = sum_m;
     row_sums[2 * (long long)b + 1] = sum_j;
@@ -167,36 +162,25 @@ __global__ __launch_bounds__(256) void gn_data_kernel(const T* __restrict__ m_r,
                                                        const int2* __restrict__ bl_ant, const GnScal* __restrict__ scal, int na_slice,
                                                        T* __restrict__ data_r, T* __restrict__ data_i, int nbls, int nfreqs, int fpad) {
 #pragma clang fp contract(off)
-  constexpr int V = 16 / (int)sizeof(T);
-  typedef T vec_t __attribute__((ext_vector_type(V)));
-  const int lane = threadIdx.x & 63;
-  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);  // wave-uniform
-  if (b >= nbls) return;
-  const int2 ant = bl_ant[b];
-  const long long row = (long long)b * fpad;
-  const vec2_t<T>* __restrict__ gi = gains + (long long)ant.x * fpad;
-  const vec2_t<T>* __restrict__ gj = gains + (long long)ant.y * fpad;
-  const T s = jp_r ? (T)scal[ant.x / na_slice].scale : (T)0;
-  for (int f = lane * V; f < fpad; f += 64 * V) {
-    const vec_t mr = *reinterpret_cast<const vec_t*>(m_r + row + f);
-    const vec_t mi = *reinterpret_cast<const vec_t*>(m_i + row + f);
+  constexpr int V = RowWalk<T>::V;
+  typedef typename RowWalk<T>::vec_t vec_t;
+  RowWalk<T> R;
+  if (!R.begin(bl_ant, nbls, fpad)) return;
+  GainPair<T> gp(gains, R.ant, fpad);
+  const T s = jp_r ? (T)scal[R.ant.x / na_slice].scale : (T)0;
+  for (int f = R.lane * V; f < fpad; f += 64 * V) {
+    const vec_t mr = R.load(m_r, f), mi = R.load(m_i, f);
     vec_t pr, pi;
     if (jp_r) {
-      pr = *reinterpret_cast<const vec_t*>(jp_r + row + f);
-      pi = *reinterpret_cast<const vec_t*>(jp_i + row + f);
+      pr = R.load(jp_r, f);
+      pi = R.load(jp_i, f);
     }
-    vec_t a2[2], b2[2];
-    a2[0] = *reinterpret_cast<const vec_t*>(gi + f);
-    a2[1] = *reinterpret_cast<const vec_t*>(gi + f + V / 2);
-    b2[0] = *reinterpret_cast<const vec_t*>(gj + f);
-    b2[1] = *reinterpret_cast<const vec_t*>(gj + f + V / 2);
+    gp.load(f);
     vec_t dr, di;
 #pragma unroll
     for (int c = 0; c < V; ++c) {
-      const T ax = a2[(2 * c) / V][(2 * c) % V], ay = a2[(2 * c) / V][(2 * c) % V + 1];
-      const T bx = b2[(2 * c) / V][(2 * c) % V], by = b2[(2 * c) / V][(2 * c) % V + 1];
-      const T Gr = ax * bx + ay * by, Gi = ay * bx - ax * by;
-      T xr = Gr * mr[c] - Gi * mi[c], xi = Gr * mi[c] + Gi * mr[c];
+      const auto g = gp.at(c);
+      T xr = g.Gr * mr[c] - g.Gi * mi[c], xi = g.Gr * mi[c] + g.Gi * mr[c];
       if (jp_r) {
         xr = xr + s * pr[c];
         xi = xi + s * pi[c];
@@ -205,8 +189,8 @@ __global__ __launch_bounds__(256) void gn_data_kernel(const T* __restrict__ m_r,
       dr[c] = live ? xr : (T)0;
       di[c] = live ? xi : (T)0;
     }
-    *reinterpret_cast<vec_t*>(data_r + row + f) = dr;
-    *reinterpret_cast<vec_t*>(data_i + row + f) = di;
+    R.store(data_r, f, dr);
+    R.store(data_i, f, di);
   }
 }
 
@@ -216,33 +200,25 @@ __global__ __launch_bounds__(256) void gn_precond_rows_kernel(const vec2_t<T>* _
                                                                const int2* __restrict__ bl_ant, int nbls, int nfreqs, int fpad,
                                                                double* __restrict__ rowq) {
 #pragma clang fp contract(off)
-  constexpr int V = 16 / (int)sizeof(T);
-  typedef T vec_t __attribute__((ext_vector_type(V)));
-  const int lane = threadIdx.x & 63;
-  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (b >= nbls) return;
-  const int2 ant = bl_ant[b];
-  const long long row = (long long)b * fpad;
-  const vec2_t<T>* __restrict__ gi = gains + (long long)ant.x * fpad;
-  const vec2_t<T>* __restrict__ gj = gains + (long long)ant.y * fpad;
+  constexpr int V = RowWalk<T>::V;
+  typedef typename RowWalk<T>::vec_t vec_t;
+  RowWalk<T> R;
+  if (!R.begin(bl_ant, nbls, fpad)) return;
+  GainPair<T> gp(gains, R.ant, fpad);
   double sum = 0;
-  for (int f = lane * V; f < fpad; f += 64 * V) {
-    const vec_t w = *reinterpret_cast<const vec_t*>(wgts + row + f);
-    vec_t a2[2], b2[2];
-    a2[0] = *reinterpret_cast<const vec_t*>(gi + f);
-    a2[1] = *reinterpret_cast<const vec_t*>(gi + f + V / 2);
-    b2[0] = *reinterpret_cast<const vec_t*>(gj + f);
-    b2[1] = *reinterpret_cast<const vec_t*>(gj + f + V / 2);
+  for (int f = R.lane * V; f < fpad; f += 64 * V) {
+    const vec_t w = R.load(wgts, f);
+    gp.load(f);
 #pragma unroll
     for (int c = 0; c < V; ++c) {
-      const T ax = a2[(2 * c) / V][(2 * c) % V], ay = a2[(2 * c) / V][(2 * c) % V + 1];
-      const T bx = b2[(2 * c) / V][(2 * c) % V], by = b2[(2 * c) / V][(2 * c) % V + 1];
-      const T Gr = ax * bx + ay * by, Gi = ay * bx - ax * by;
-      if (f + c < nfreqs) sum += (double)w[c] * ((double)Gr * (double)Gr + (double)Gi * (double)Gi);
+      if (f + c < nfreqs) {
+        const auto g = gp.at(c);
+        sum += (double)w[c] * ((double)g.Gr * (double)g.Gr + (double)g.Gi * (double)g.Gi);
+      }
     }
   }
-  sum = gn_wave_sum(sum);
-  if (lane == 0) rowq[b] = sum / (double)nfreqs;
+  sum = ldsum(sum);
+  if (R.lane == 0) rowq[R.b] = sum / (double)nfreqs;
 }
 __device__ __forceinline__ double gn_fix_diag(double d) { return (d > 0.0 && isfinite(d)) ? d : 1.0; }
 // D of the gains: den [nants][nfreqs] (the third plane of gain_solve_ant_kernel) to both reals of the (re, im) pair; the padding gets 1

@@ -153,7 +153,7 @@ __device__ __forceinline__ void lb_block_sums(const double (&acc)[N], double* s_
   __syncthreads();  // (s_w may still be read from the tile before)
 #pragma unroll
   for (int k = 0; k < N; ++k) {
-    const double v = gn_wave_sum(acc[k]);
+    const double v = ldsum(acc[k]);
     if ((threadIdx.x & 63) == 0) s_w[k * 4 + (threadIdx.x >> 6)] = v;
   }
   __syncthreads();
@@ -274,7 +274,7 @@ __global__ __launch_bounds__(256) void lbfgs_reduce_kernel(const LbSpace S, cons
   const double* part = part_all + ((long long)t * kLbDots + k) * kLbBlocks;
   double v = 0;
   for (int b = lane; b < nblk; b += 64) v += part[b];
-  v = gn_wave_sum(v);
+  v = ldsum(v);
   if (lane == 0) dots[(long long)t * kLbDots + k] = v;
 }
 
