@@ -84,12 +84,13 @@ class LbfgsRef:
 
     def run(self, v, c, nsteps, history=8, max_ls=20, c1=1e-4, shrink=0.5, ftol=0.0, curvature_eps=1e-8):
         """``v``: the gain variables (the gains, or y), ``c``: the coefficients, both complex and already rounded to T.  Returns
-        dict(v, c, losses [nsteps + 1] (NaN past iters), iters, evals, pairs_dropped, status, margin, margins: per iteration)."""
+        dict(v, c, losses [nsteps + 1] (NaN past iters), iters, evals, pairs_dropped, status, margin, margins: per iteration, stored: per
+        iteration whether its pair entered the ring)."""
         rnd, v_shape = self.rnd, v.shape
         x = self.pack(v, c)
         f, g = self.loss_and_grad(v, c)
         losses = np.full(nsteps + 1, np.nan)
-        out = dict(v=v, c=c, losses=losses, iters=0, evals=0, pairs_dropped=0, status=3, margin=np.inf, margins=[])
+        out = dict(v=v, c=c, losses=losses, iters=0, evals=0, pairs_dropped=0, status=3, margin=np.inf, margins=[], stored=[])
         gn = float(np.sqrt(g @ g))
         if not np.isfinite(f) or not np.isfinite(gn) or gn == 0.0:
             return out
@@ -145,7 +146,8 @@ class LbfgsRef:
             sy, ss, yy = float(s @ y), float(s @ s), float(y @ y)
             if ss > 0 and yy > 0:
                 out["margins"][-1] = min(out["margins"][-1], abs(sy / np.sqrt(ss * yy) - curvature_eps))
-            if np.isfinite(sy) and sy > curvature_eps * np.sqrt(ss * yy):
+            out["stored"].append(bool(np.isfinite(sy) and sy > curvature_eps * np.sqrt(ss * yy)))
+            if out["stored"][-1]:
                 pairs.append((s, y))
                 pairs = pairs[-history:]
             else:
