@@ -91,6 +91,17 @@ class RobustDesc(C.Structure):
 ROBUST_KINDS = {"none": 0, "huber": 1, "cauchy": 2, "clip": 3}
 
 
+class DelaySpectrumDesc(C.Structure):
+    """cal_delay_spectrum_desc (include/calamity_hip.h: cal_solver_delay_spectrum): ndelays columns of the operator op_r + i op_i
+    ([nfreqs][ndelays], solver dtype), what (DELAY_SPECTRUM_WHAT bits), calibrated 0 / 1, nbins and bin_of_bl [nbls] int32 in
+    [-1, nbins) (NULL iff nbins == 0), norm_f [nfreqs] float64."""
+    _fields_ = [("ndelays", C.c_int32), ("what", C.c_int32), ("calibrated", C.c_int32), ("nbins", C.c_int32), ("bin_of_bl", C.c_void_p),
+                ("op_r", C.c_void_p), ("op_i", C.c_void_p), ("norm_f", C.c_void_p)]
+
+
+DELAY_SPECTRUM_WHAT = {"data": 1, "model": 2, "resid": 4}
+
+
 class CoeffSolveDesc(C.Structure):
     _fields_ = [("niters", C.c_int32), ("reset_coeff_moments", C.c_int32), ("damping", C.c_double), ("ridge", C.c_double), ("slice_mask", C.c_void_p)]
 
@@ -199,6 +210,8 @@ SYMBOLS = {
     "cal_solver_lbfgs": (C.c_int, [_P, C.POINTER(LbfgsDesc), _P, C.POINTER(LbfgsResult)]),
     "cal_debug_lbfgs_coefficients": (C.c_int, [C.c_int32, _P, _P, C.POINTER(C.c_double)]),
     "cal_solver_robust_weights": (C.c_int, [_P, C.POINTER(RobustDesc), _P, _P]),
+    "cal_solver_delay_spectrum": (C.c_int, [_P, C.POINTER(DelaySpectrumDesc), _P, _P, _P, _P, _P, _P]),
+    "cal_solver_set_delay_spectrum_scratch": (C.c_int, [_P, C.c_int64]),
     "cal_solver_get_weights": (C.c_int, [_P, _P, C.c_int]),
     "cal_solver_solve_coeffs": (C.c_int, [_P, C.POINTER(CoeffSolveDesc), C.POINTER(CoeffSolveResult)]),
     "cal_solver_set_coeff_solve_scratch": (C.c_int, [_P, C.c_int64]),

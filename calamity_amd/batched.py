@@ -255,6 +255,23 @@ class SliceBatchFitter:
         outs = self._each(lambda r, s: s.fit_quality(g_r, g_i))
         return dict(outs[0], **{k: self._scatter([o[k] for o in outs], self.rows) for k in ("chisq_bl", "wsum_bl")})
 
+    def delay_spectrum(self, op, norm_f, what=("data", "model", "resid"), calibrated=False, bin_of_bl=None, nbins=0, per_baseline=False,
+                       g_r=None, g_i=None):
+        """``HipFitSolver.delay_spectrum`` on the global arrays: ``bin_of_bl`` ``[nt * nbls]`` in the global slice-major row order (it
+        decides which rows of which slices are summed together); the binned arrays and ``count_bin`` are worker 0's (with several
+        workers the library has summed them over the workers), ``norm_bl`` and the ``per_baseline`` arrays are put back into the
+        global row order like the rows of ``model()``."""
+        bins = None if bin_of_bl is None else np.asarray(bin_of_bl)
+        outs = self._each(lambda r, s: s.delay_spectrum(op, norm_f, what=what, calibrated=calibrated, bin_of_bl=None if bins is None else self._take(bins, r),
+                                                        nbins=nbins, per_baseline=per_baseline, g_r=g_r, g_i=g_i))
+        out = dict(outs[0], norm_bl=self._scatter([o["norm_bl"] for o in outs], self.rows))
+        if per_baseline:
+            out["per_baseline"] = {q: self._scatter([o["per_baseline"][q] for o in outs], self.rows) for q in outs[0]["per_baseline"]}
+        return out
+
+    def _set_delay_spectrum_scratch(self, nbytes):
+        self._each(lambda r, s: s._set_delay_spectrum_scratch(nbytes))
+
     def fit_errors(self, ridge=1e-6, model_var=True, gain_var=True, coeffs=True):
         """``HipFitSolver.fit_errors`` on the global arrays: ``gain_var`` ``[nt * nants, nfreqs]`` (with several workers the library
         has summed ``den`` over the workers: worker 0's), ``model_var``, ``leverage_bl``, ``nsamp_bl`` with their rows and

@@ -911,6 +911,74 @@ def insert_fit_quality(uvcal, hist, time, polarization, q, rms, prob):
     hist["chisq_per_baseline"] = {(int(ants[i]), int(ants[j])): float(v) for i, j, v in zip(prob.bl_ant0, prob.bl_ant1, per_bl)}
 
 
+def _check_delay_spectrum(delay_spectrum, taper, max_dly, bllen_bin):
+    """The delay-spectrum keywords of ``calibrate_and_model_tensor``, checked before anything is touched (``ValueError``)."""
+    if not any(delay_spectrum is v for v in (False, True)) and delay_spectrum != "baselines":
+        raise ValueError(f"delay_spectrum must be False, True or 'baselines', got {delay_spectrum!r}")
+    if isinstance(taper, str) and taper not in ("bh4", "none"):
+        raise ValueError(f"delay_spectrum_taper must be 'bh4', 'none' or an array of Nfreqs values, got {taper!r}")
+    if not (np.isfinite(float(bllen_bin)) and float(bllen_bin) > 0.0):
+        raise ValueError(f"delay_spectrum_bllen_bin must be a positive length in metres, got {bllen_bin!r}")
+    if max_dly is not None and not (np.isfinite(float(max_dly)) and float(max_dly) >= 0.0):
+        raise ValueError(f"delay_spectrum_max_dly must be a delay >= 0 in ns, got {max_dly!r}")
+
+
+def baseline_length_bins(lengths, width):
+    """Baseline rows into bins of ``width`` metres, bin ``floor(length / width)``, only the bins that hold a row, in ascending order:
+    ``(bin_of_bl [nbls] int32, bllen_m [nbins])`` with ``bllen_m`` the mean length of each bin's rows."""
+    lengths = np.asarray(lengths, dtype=np.float64)
+    idx = np.floor(lengths / float(width)).astype(np.int64)
+    used, bin_of_bl = np.unique(idx, return_inverse=True)
+    bin_of_bl = bin_of_bl.reshape(-1)
+    bllen = np.bincount(bin_of_bl, weights=lengths, minlength=len(used)) / np.bincount(bin_of_bl, minlength=len(used))
+    return bin_of_bl.astype(np.int32), bllen
+
+
+def delay_spectrum_setup(uvdata, ant_array, prob, taper="bh4", max_dly=None, bllen_bin=1.0, calibrated=False, per_baseline=False):
+    """What the delay-spectrum pass of every slice of a call shares: the operator, ``norm_f`` and delays (``modeling.delay_transform``
+    on the data's frequencies), the length bin of every baseline row of ``prob`` (``baseline_length_bins`` on the antenna positions of
+    ``uvdata``; ``ant_array``: the antenna numbers ``prob``'s antenna indices count through) and the two switches."""
+    op, norm_f, delays_ns = modeling.delay_transform(np.asarray(uvdata.freq_array, dtype=np.float64).ravel(), taper=taper, max_delay_ns=max_dly)
+    if op.shape[1] < 1 or op.shape[1] > 4096:
+        raise ValueError(f"the delay spectrum has {op.shape[1]} delays: between 1 and 4096 (delay_spectrum_max_dly)")
+    pos = {int(a): np.asarray(x, dtype=np.float64) for a, x in zip(np.asarray(uvdata.antenna_numbers), np.asarray(uvdata.antenna_positions))}
+    ants = np.asarray(ant_array)
+    lengths = np.asarray([np.linalg.norm(pos[int(ants[i])] - pos[int(ants[j])]) for i, j in zip(prob.bl_ant0, prob.bl_ant1)])
+    bin_of_bl, bllen_m = baseline_length_bins(lengths, bllen_bin)
+    return dict(op=op, norm_f=norm_f, delays_ns=delays_ns, bin_of_bl=bin_of_bl, nbins=len(bllen_m), bllen_m=bllen_m, calibrated=bool(calibrated),
+                per_baseline=bool(per_baseline))
+
+
+def delay_spectrum_slice_bins(dspec, nt):
+    """``bin_of_bl`` of ``nt`` slices in slice-major row order: row ``b`` of slice ``t`` goes to bin ``t nbins + bin_of_bl[b]``."""
+    return (np.repeat(np.arange(nt, dtype=np.int32) * dspec["nbins"], len(dspec["bin_of_bl"])) + np.tile(dspec["bin_of_bl"], nt)).astype(np.int32)
+
+
+def delay_spectrum_of_slice(spectra, dspec, t, nbls):
+    """Slice ``t``'s part of a ``SliceBatchFitter.delay_spectrum`` whose bins are those of ``delay_spectrum_slice_bins``."""
+    bins, rows = slice(t * dspec["nbins"], (t + 1) * dspec["nbins"]), slice(t * nbls, (t + 1) * nbls)
+    out = {k: spectra[k][bins] for k in ("data", "model", "resid", "count_bin")}
+    if "per_baseline" in spectra:
+        out["per_baseline"] = {k: v[rows] for k, v in spectra["per_baseline"].items()}
+    return out
+
+
+def delay_spectrum_entry(ds, dspec, rms, prob, ant_array):
+    """One slice's ``HipFitSolver.delay_spectrum`` (solver units: the data divided by ``rms``; sums over the bins' rows) as what
+    ``fit_history`` reports: the MEAN power per baseline-length bin in the data's units squared, ``rms^2 sum / count`` (0 for a bin
+    whose rows are all flagged), and with ``per_baseline`` every row's own spectrum keyed by antenna numbers."""
+    count = np.asarray(ds["count_bin"], dtype=np.float64)
+    scale = float(rms) ** 2 * np.divide(1.0, count, out=np.zeros_like(count), where=count > 0)
+    entry = {"delays_ns": dspec["delays_ns"], "bllen_m": dspec["bllen_m"], "nbls": count.astype(np.int64)}
+    for k in ("data", "model", "resid"):
+        entry[k] = scale[:, None] * np.asarray(ds[k])
+    if "per_baseline" in ds:
+        ants = np.asarray(ant_array)
+        pb = {k: float(rms) ** 2 * np.asarray(v) for k, v in ds["per_baseline"].items()}
+        entry["per_baseline"] = {(int(ants[i]), int(ants[j])): {k: pb[k][b] for k in pb} for b, (i, j) in enumerate(zip(prob.bl_ant0, prob.bl_ant1))}
+    return entry
+
+
 def _report_slice(hist, gains, time, polarization, rms, prob, quality, errors, errs):
     """What one fitted (polarization, time) slice reports besides its losses, for the loop over the slices and for the batches alike:
     ``hist["robust"]`` from solver units and row order into the data's units, keyed by antenna numbers (``robust_history``); the slice's
@@ -994,6 +1062,11 @@ def calibrate_and_model_tensor(
     lbfgs_ftol=0.0,
     fit_errors=False,
     fit_errors_ridge=1e-6,
+    delay_spectrum=False,
+    delay_spectrum_taper="bh4",
+    delay_spectrum_max_dly=None,
+    delay_spectrum_bllen_bin=1.0,
+    delay_spectrum_calibrated=False,
     **opt_kwargs,
 ):
     """Simultaneous calibration and foreground fitting -- calibration.py:963-1331, same arguments, defaults and
@@ -1167,11 +1240,26 @@ def calibrate_and_model_tensor(
       (``device_split="groups"`` or the automatic choice of it; ``device_split="slices"`` works).
       ``fit_history[polnum][time_index]["lbfgs"] = {"calls", "iters", "evals", "loss", "status"}`` (present only with the feature on): the
       calls the slice took part in, its iterations and trial losses over all of them, the loss after every call, the status of the last.
+    * ``delay_spectrum`` (``False`` | ``True`` | ``"baselines"``; default off: no call changes by a bit and no new kernel is launched),
+      ``delay_spectrum_taper`` (``"bh4"`` | ``"none"`` | an array ``[Nfreqs]``), ``delay_spectrum_max_dly`` (ns; ``None``: all delays),
+      ``delay_spectrum_bllen_bin`` (metres), ``delay_spectrum_calibrated``: report where the power of data, model and residual of every
+      fitted slice sits in delay (``HipFitSolver.delay_spectrum``: one device pass after the fit, at the reported parameters, on the data
+      and flags the fit used; the operator is ``modeling.delay_transform``).  ``fit_history[polnum][time_index]["delay_spectrum"]`` holds
+      ``delays_ns`` ``[Ndelays]``, ``bllen_m`` ``[nbins]`` (the mean length of each bin's baselines; bin ``floor(length / width)``, only the
+      bins that hold a baseline), ``nbls`` ``[nbins]`` (the baselines of the bin with an unflagged channel) and ``data``, ``model``,
+      ``resid`` ``[nbins, Ndelays]``: the mean over the bin's baselines of ``|sum_f mask t_f x_f exp(-2 pi i f k / Nfreqs)|^2 / sum_f mask t_f^2``
+      in the data's units squared, with ``x`` = data, gains x model, data - gains x model (``delay_spectrum_calibrated``: data / gains,
+      model, their difference) and ``mask`` the samples of non-zero weight.  ``"baselines"`` adds ``per_baseline``: ``{(ant0, ant1):
+      {"data", "model", "resid"}}`` with antenna numbers, ``[Ndelays]`` each.  A baseline is transformed the way round the fit holds it
+      (the antenna pairs of ``fg_model_comps_dict``, the keys of ``per_baseline``): held as ``(j, i)`` its spectrum is the mirror image
+      in delay of ``(i, j)``'s.  A joint time-basis fit reports every time on its own.
+      ``ValueError`` before any device work for an unknown taper, a bin width that is not positive, a negative ``delay_spectrum_max_dly``.
     * ``parallel_fits`` (default 1): with ``batch_slices=False``, fits that many slices concurrently, each on its own
       solver and HIP stream.
     (Nothing here is steered by environment variables: layout, devices and concurrency are arguments.)"""
     if gain_basis is not None and gain_max_dly is not None:
         raise ValueError("give gain_basis or gain_max_dly, not both")
+    _check_delay_spectrum(delay_spectrum, delay_spectrum_taper, delay_spectrum_max_dly, delay_spectrum_bllen_bin)
     controls = FitControls.pick(locals())
     controls.check(gain_basis is not None or gain_max_dly is not None, gain_time_basis is not None or gain_time_scale is not None, freeze_model, use_min)
     if gain_max_dly is not None:
@@ -1247,6 +1335,11 @@ def calibrate_and_model_tensor(
     echo(f"{datetime.datetime.now()}Finished Converting Foreground Modeling Components to Tensors...\n", verbose=verbose)
     del fg_model_comps_dict
     prob = fg_model_comps
+    dspec = None
+    if delay_spectrum:
+        dspec = delay_spectrum_setup(uvdata, gains.ant_array, prob, taper=delay_spectrum_taper, max_dly=delay_spectrum_max_dly,
+                                     bllen_bin=delay_spectrum_bllen_bin, calibrated=delay_spectrum_calibrated,
+                                     per_baseline=delay_spectrum == "baselines")
     if parallel_fits is None:
         parallel_fits = 1
     if init_guesses_from_previous_time_step:
@@ -1271,7 +1364,7 @@ def calibrate_and_model_tensor(
             verbose=verbose, max_batch=max_batch, devices=devices, layout=layout, opt_kwargs=opt_kwargs,
             correct_model=correct_model, correct_resid=correct_resid, device_split=device_split, gain_basis=gain_basis,
             gain_time_basis=gain_time_basis, fit_quality=fit_quality,
-            controls=controls, errs=errs,
+            controls=controls, errs=errs, dspec=dspec,
         )
         _file_gain_std(fit_history, errs, gains)
         return model, resid, gains, fit_history  # (every slice left _fit_slices_batched in its final state)
@@ -1349,6 +1442,10 @@ def calibrate_and_model_tensor(
                 errors = solver.fit_errors(ridge=errs["ridge"], model_var=errs["samples"], gain_var=errs["with_gains"], coeffs=not freeze_model)
                 errors["chisq_bl"] = solver.fit_quality(g_r, g_i)["chisq_bl"]
             _report_slice(hist, gains, time, pol, rmsdata, prob, quality, errors, errs)
+            if dspec is not None:
+                ds = solver.delay_spectrum(dspec["op"], dspec["norm_f"], calibrated=dspec["calibrated"], bin_of_bl=dspec["bin_of_bl"],
+                                           nbins=dspec["nbins"], per_baseline=dspec["per_baseline"], g_r=g_r, g_i=g_i)
+                hist["delay_spectrum"] = delay_spectrum_entry(ds, dspec, rmsdata, prob, gains.ant_array)
         else:
             echo(f"{datetime.datetime.now()}: Only {frac_unflagged * 100}-percent of data unflagged. Skipping...\n", verbose=verbose)
             flag_poltime(resid, time=time, polarization=pol)
@@ -1578,7 +1675,7 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
                         skip_threshold, use_model_snr_weights, optimizer, use_min, freeze_model, tol, maxsteps, n_profile_steps,
                         profile_log_dir, model_regularization, verbose, max_batch, devices, layout, opt_kwargs, correct_model=True,
                         correct_resid=False, device_split=None, gain_basis=None, gain_time_basis=None, fit_quality=False,
-                        controls=FitControls(), errs=None):
+                        controls=FitControls(), errs=None, dspec=None):
     """The pol x time loop of calibration.py:1160-1331 with the fits of all unskipped slices issued as batches: per slice
     exactly the host-side steps of the loop body (skip test :1173-1177, rms scale :1178-1182, tensorize :1184-1233, write-back
     :1271-1300, post-hoc renormalisation :1311-1319, residual and calibration state of the outputs :1322-1331), the gradient
@@ -1721,8 +1818,12 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
             fitter.set_params(gm_r, gm_i)  # the reported gains (use_min: every slice's minimum); the fit is over, the next one sets its own
             errors = fitter.fit_errors(ridge=errs["ridge"], model_var=errs["samples"], gain_var=errs["with_gains"], coeffs=not freeze_model)
             errors["chisq_bl"] = (quality if quality is not None else fitter.fit_quality(gm_r, gm_i))["chisq_bl"]
+        spectra = None
+        if dspec is not None:  # every slice (a joint fit: every time) has bins of its own: bin_of_bl encodes (t, length bin)
+            spectra = fitter.delay_spectrum(dspec["op"], dspec["norm_f"], calibrated=dspec["calibrated"], bin_of_bl=delay_spectrum_slice_bins(dspec, nt),
+                                            nbins=nt * dspec["nbins"], per_baseline=dspec["per_baseline"], g_r=gm_r, g_i=gm_i)
         echo(f"{datetime.datetime.now()} ... fitted.\n", verbose=verbose)
-        return dict(result=result, results=results, m_r=m_r, m_i=m_i, gm_r=gm_r, gm_i=gm_i, quality=quality, errors=errors)
+        return dict(result=result, results=results, m_r=m_r, m_i=m_i, gm_r=gm_r, gm_i=gm_i, quality=quality, errors=errors, spectra=spectra)
 
     def post(batch, out):
         for t, (sl, res) in enumerate(zip(batch, out["results"])):
@@ -1744,6 +1845,9 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
                 if "coeff_var" in e:  # (the library counts over the batch: the slice's own are its groups with an all-zero coeff_var)
                     e["nsingular"] = sum(1 for g in range(prob.ngrps) if not np.any(e["coeff_var"][prob.grp_coff[g] : prob.grp_coff[g + 1]]))
             _report_slice(hist, gains, sl["time"], sl["pol"], sl["rmsdata"], prob, q, e, errs)  # (before the post-hoc renormalisation, which leaves g_i conj(g_j) m as it is)
+            if out["spectra"] is not None:
+                hist["delay_spectrum"] = delay_spectrum_entry(delay_spectrum_of_slice(out["spectra"], dspec, t, prob.nbls), dspec, sl["rmsdata"], prob,
+                                                              gains.ant_array)
             if res[1]:
                 echo(f"Tolerance thresshold met for time {sl['time_index']}. Terminating...\n ", verbose=verbose)
             if not freeze_model and model_regularization == "post_hoc":  # (:1311-1319)
@@ -1907,10 +2011,17 @@ def calibrate_and_model_dpss(
     red_tol=1.0,
     notebook_progressbar=False,
     fg_model_comps_dict=None,
+    delay_spectrum=False,
+    delay_spectrum_taper="bh4",
+    delay_spectrum_max_dly=None,
+    delay_spectrum_bllen_bin=1.0,
+    delay_spectrum_calibrated=False,
     **fitting_kwargs,
 ):
     """Simultaneously solve for gains and model foregrounds with per-baseline DPSS vectors -- the kept entry point,
-    calibration.py:1503-1584.  ``fg_model_comps_dict`` is accepted and ignored, as in the reference (:1564)."""
+    calibration.py:1503-1584.  ``fg_model_comps_dict`` is accepted and ignored, as in the reference (:1564).  The ``delay_spectrum``
+    keywords are ``calibrate_and_model_tensor``'s."""
+    _check_delay_spectrum(delay_spectrum, delay_spectrum_taper, delay_spectrum_max_dly, delay_spectrum_bllen_bin)
     waker = _wake_device(fitting_kwargs.get("devices"))
     try:
         dpss_model_comps_dict = modeling.yield_pbl_dpss_model_comps(
@@ -1919,7 +2030,9 @@ def calibrate_and_model_dpss(
         )
         (model, resid, gains, fitted_info) = calibrate_and_model_tensor(
             uvdata=uvdata, fg_model_comps_dict=dpss_model_comps_dict, include_autos=include_autos, verbose=verbose,
-            notebook_progressbar=notebook_progressbar, **fitting_kwargs,
+            notebook_progressbar=notebook_progressbar, delay_spectrum=delay_spectrum, delay_spectrum_taper=delay_spectrum_taper,
+            delay_spectrum_max_dly=delay_spectrum_max_dly, delay_spectrum_bllen_bin=delay_spectrum_bllen_bin,
+            delay_spectrum_calibrated=delay_spectrum_calibrated, **fitting_kwargs,
         )
     finally:
         waker.join()
@@ -1947,12 +2060,18 @@ def calibrate_and_model_mixed(
     grp_size_threshold=5,
     model_comps_dict=None,
     save_dict_to=None,
+    delay_spectrum=False,
+    delay_spectrum_taper="bh4",
+    delay_spectrum_max_dly=None,
+    delay_spectrum_bllen_bin=1.0,
+    delay_spectrum_calibrated=False,
     **fitting_kwargs,
 ):
     """Gains + foregrounds with DPSS vectors for baselines without frequency redundancy and joint covariance
     eigenvectors for groups of baselines whose uv tracks overlap -- calibration.py:1353-1500 (same signature and
     returns).  ``use_tensorflow_to_derive_modeling_comps`` is accepted for compatibility; the eigenproblems run on the
-    host either way."""
+    host either way.  The ``delay_spectrum`` keywords are ``calibrate_and_model_tensor``'s."""
+    _check_delay_spectrum(delay_spectrum, delay_spectrum_taper, delay_spectrum_max_dly, delay_spectrum_bllen_bin)
     fitting_grps, blvecs, _, _ = modeling.get_uv_overlapping_grps_conjugated(
         uvdata, red_tol=red_tol, include_autos=include_autos, red_tol_freq=red_tol_freq, n_angle_bins=n_angle_bins,
         notebook_progressbar=notebook_progressbar, require_exact_angle_match=require_exact_angle_match,
@@ -1973,7 +2092,9 @@ def calibrate_and_model_mixed(
         np.save(save_dict_to, model_comps_dict)
     (model, resid, gains, fitted_info) = calibrate_and_model_tensor(
         uvdata=uvdata, fg_model_comps_dict=model_comps_dict, include_autos=include_autos, verbose=verbose,
-        notebook_progressbar=notebook_progressbar, use_redundancy=use_redundancy, **fitting_kwargs,
+        notebook_progressbar=notebook_progressbar, use_redundancy=use_redundancy, delay_spectrum=delay_spectrum, delay_spectrum_taper=delay_spectrum_taper,
+        delay_spectrum_max_dly=delay_spectrum_max_dly, delay_spectrum_bllen_bin=delay_spectrum_bllen_bin,
+        delay_spectrum_calibrated=delay_spectrum_calibrated, **fitting_kwargs,
     )
     return model, resid, gains, fitted_info
 
@@ -2082,6 +2203,12 @@ def read_calibrate_and_model_dpss(
     fit_errors=False,
     fit_errors_samples=False,
     fit_errors_ridge=1e-6,
+    delay_spectrum=False,
+    delay_spectrum_taper="bh4",
+    delay_spectrum_max_dly=None,
+    delay_spectrum_bllen_bin=1.0,
+    delay_spectrum_calibrated=False,
+    delay_spectrum_outfile=None,
     **calibration_kwargs,
 ):
     """File driver of the DPSS fit -- calibration.py:1659-1817 (same arguments, returns and output files).
@@ -2098,7 +2225,15 @@ def read_calibrate_and_model_dpss(
     then ``gain_std`` (where the gains are free per channel) and the per-baseline tables go there as an ``.npz`` archive: ``antpairs``
     ``[rows, 2]`` and, ``[Npols, Ntimes, rows]`` each with ``nan`` for a skipped slice, ``leverage_per_baseline``,
     ``chisq_red_per_baseline``; ``noise_scale`` ``[Npols, Ntimes]``.
+    The ``delay_spectrum`` keywords are ``calibrate_and_model_tensor``'s (Python keywords only: there is no command-line flag yet);
+    ``delay_spectrum_outfile`` writes the entries as one ``.npz`` archive (``delay_spectrum_tables``): ``delays_ns``, ``bllen_m`` and,
+    ``[Npols, Ntimes, nbins, Ndelays]`` each with ``nan`` for a skipped slice, ``data``, ``model``, ``resid``; ``nbls``
+    ``[Npols, Ntimes, nbins]``; with ``"baselines"`` also ``antpairs`` ``[rows, 2]`` and ``data_bl``, ``model_bl``, ``resid_bl``
+    ``[Npols, Ntimes, rows, Ndelays]``.
     """
+    _check_delay_spectrum(delay_spectrum, delay_spectrum_taper, delay_spectrum_max_dly, delay_spectrum_bllen_bin)
+    if delay_spectrum_outfile is not None and not delay_spectrum:
+        raise ValueError("delay_spectrum_outfile needs delay_spectrum=True or 'baselines'")
     uvd = _read_uvdata(input_data_files)
     weights = get_auto_weights(uvd) if use_autocorrs_in_weights else None
     utils.select_baselines(uvd, bllen_min=bllen_min, bllen_max=bllen_max, bl_ew_min=bl_ew_min, ex_ants=ex_ants, select_ants=select_ants)
@@ -2114,6 +2249,8 @@ def read_calibrate_and_model_dpss(
         model_fit, resid_fit, gains_fit, fit_info = calibrate_and_model_dpss(
             uvdata=uvd, sky_model=uvd_model, gains=uvc, dtype=dtype, weights=weights, **calibration_kwargs,
             **(dict(fit_errors="samples" if fit_errors_samples else True, fit_errors_ridge=fit_errors_ridge) if fit_errors or fit_errors_samples else {}),
+            **(dict(delay_spectrum=delay_spectrum, delay_spectrum_taper=delay_spectrum_taper, delay_spectrum_max_dly=delay_spectrum_max_dly,
+                    delay_spectrum_bllen_bin=delay_spectrum_bllen_bin, delay_spectrum_calibrated=delay_spectrum_calibrated) if delay_spectrum else {}),
         )
     finally:
         _DEVICE.update(saved)
@@ -2126,6 +2263,11 @@ def read_calibrate_and_model_dpss(
         model_fit.write_uvh5(model_outfilename, clobber=clobber)
     if (fit_errors or fit_errors_samples) and fitted_info_outfilename is not None:
         _write_fit_errors(fitted_info_outfilename, fit_info, clobber)
+    if delay_spectrum_outfile is not None:
+        if os.path.exists(delay_spectrum_outfile) and not clobber:
+            raise IOError(f"{delay_spectrum_outfile} exists; use clobber=True to overwrite")
+        with open(delay_spectrum_outfile, "wb") as f:  # (a file object: np.savez appends no suffix to the name the caller gave)
+            np.savez(f, **delay_spectrum_tables(fit_info))
     fit_info["calibration_kwargs"] = calibration_kwargs
     fit_info["calibration_kwargs"]["dtype"] = dtype
     return model_fit, resid_fit, gains_fit, fit_info
@@ -2152,6 +2294,36 @@ def fit_errors_tables(fit_info):
                     out[k][i, t] = [h["errors"][k][ap] for ap in pairs]
     if "gain_std" in fit_info:
         out["gain_std"] = np.asarray(fit_info["gain_std"])
+    return out
+
+
+def delay_spectrum_tables(fit_info):
+    """The arrays the file driver writes from a ``fit_history`` with ``delay_spectrum`` entries (``read_calibrate_and_model_dpss``)."""
+    pols = sorted(k for k in fit_info if isinstance(k, int))
+    ntimes = 1 + max([t for p in pols for t in fit_info[p]], default=-1)
+    entries = [h["delay_spectrum"] for p in pols for h in fit_info[p].values() if "delay_spectrum" in h]
+    if not entries:
+        return {}
+    first = entries[0]
+    nbins, nd = first["data"].shape
+    out = {"delays_ns": np.asarray(first["delays_ns"]), "bllen_m": np.asarray(first["bllen_m"]), "nbls": np.zeros((len(pols), ntimes, nbins), dtype=np.int64)}
+    for k in ("data", "model", "resid"):
+        out[k] = np.full((len(pols), ntimes, nbins, nd), np.nan)
+    pairs = list(first["per_baseline"]) if "per_baseline" in first else None
+    if pairs is not None:
+        out["antpairs"] = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+        for k in ("data", "model", "resid"):
+            out[k + "_bl"] = np.full((len(pols), ntimes, len(pairs), nd), np.nan)
+    for i, p in enumerate(pols):
+        for t, h in fit_info[p].items():
+            if "delay_spectrum" not in h:
+                continue
+            e = h["delay_spectrum"]
+            out["nbls"][i, t] = e["nbls"]
+            for k in ("data", "model", "resid"):
+                out[k][i, t] = e[k]
+                if pairs is not None:
+                    out[k + "_bl"][i, t] = [e["per_baseline"][ap][k] for ap in pairs]
     return out
 
 

@@ -31,6 +31,7 @@
 #include "gain_solve_kernels.hpp"
 #include "coeff_solve_kernels.hpp"
 #include "fit_error_kernels.hpp"
+#include "delay_spectrum_kernels.hpp"
 #include "gain_basis_solve_kernels.hpp"
 #include "gain_time_solve_kernels.hpp"
 #include "gauss_newton_kernels.hpp"
@@ -182,6 +183,9 @@ struct cal_solver {
   virtual int model(void* mr, void* mi, bool with_gains) = 0;
   virtual int fit_quality(const void* g_r, const void* g_i, double* chisq_ant, double* wsum_ant, double* chisq_bl, double* wsum_bl) = 0;
   virtual int robust_weights(const cal_robust_desc* d, double* scale_bl, double* ndown_bl) = 0;
+  virtual int delay_spectrum(const cal_delay_spectrum_desc* d, const void* g_r, const void* g_i, double* power_bl, double* norm_bl, double* power_bin,
+                             double* count_bin) = 0;
+  virtual int set_delay_spectrum_scratch(int64_t bytes) = 0;
   virtual int get_weights(void* out, int which) = 0;
   virtual int solve_gains(const cal_gain_solve_desc* d) = 0;
   virtual int hold_slices(const uint8_t* mask) = 0;
@@ -266,6 +270,10 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
   DevBuf fq_out, fq_gains;                     // fit_quality: chisq_ant | wsum_ant ([nants][nfreqs] doubles each, the exchange payload) | chisq_bl | wsum_bl; gains given for one evaluation
   DevBuf rw_w0, rw_out;                        // robust_weights: w0, the weights as set_data gave them (first call after a set_data); scale_bl | ndown_bl ([nbls] doubles each)
   bool rw_w0_valid = false;
+  // delay_spectrum (delay_spectrum_kernels.hpp): the operator image and norm_f of a call, the bins' sorted row lists and their pieces per chunk;
+  // a chunk's masked planes in T (ds_x) and power in double (ds_pow); norm_bl | power_bin | count_bin (ds_out; the last two are the exchange payload)
+  DevBuf ds_op, ds_normf, ds_ent, ds_ptr, ds_x, ds_pow, ds_out;
+  int64_t ds_bound = kCsScratchDefault;        // bytes of scratch a chunk of rows may take (set_delay_spectrum_scratch)
   // normal_product / gauss_newton_step (gauss_newton_kernels.hpp), vectors over the flat parameter space (gn_np() elements): the direction s, the
   // gradient of G m and the saved parameters in T; the solution x, the residual, N s and D in double.  gn_m: m = A c, gn_sd: the data planes while
   // they are substituted ([2][nbls][fpad] T each); gn_rows: the rows' sums (3 nbls doubles); the dot products' partials, the slices' scalars and
@@ -627,7 +635,7 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     CAL_TRY(upload(ant_ptr, p.ant_ptr));
     CAL_TRY(upload(ant_ent, p.ant_ent));
 
-    for (DevBuf* b : {&gains_snap, &gains_alt, &coef_snap, &q1, &gcp1, &gc1, &model_buf, &scratch, &fq_out, &fq_gains, &gs_out, &gs_ptr, &gs_ent, &gs_mask, &cs_rhs, &rw_w0, &rw_out,
+    for (DevBuf* b : {&gains_snap, &gains_alt, &coef_snap, &q1, &gcp1, &gc1, &model_buf, &scratch, &fq_out, &fq_gains, &gs_out, &gs_ptr, &gs_ent, &gs_mask, &cs_rhs, &rw_w0, &rw_out, &ds_op, &ds_normf, &ds_ent, &ds_ptr, &ds_x, &ds_pow, &ds_out,
                        &gn_s, &gn_g0, &gn_save, &gn_x, &gn_res, &gn_ns, &gn_D, &gn_m, &gn_sd, &gn_rows, &gn_part, &gn_scal, &gn_lam, &gn_grp, &gn_rowptr,
                        &lb_vec, &lb_part, &lb_dots, &lb_state, &lb_losses, &lb_count})
       b->release();
@@ -1798,6 +1806,128 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     if (chisq_bl) HIP_TRY(hipMemcpyAsync(chisq_bl, o_cb, (size_t)nbls * sizeof(double), hipMemcpyDeviceToHost, stream));
     if (wsum_bl) HIP_TRY(hipMemcpyAsync(wsum_bl, o_wb, (size_t)nbls * sizeof(double), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
+    return CAL_OK;
+  }
+
+  // cal_solver_delay_spectrum: the model pass of model(), then per chunk of rows dspec_rows_kernel, dspec_transform_kernel and
+  // dspec_bin_kernel (delay_spectrum_kernels.hpp).  A chunk's scratch -- the masked planes in T and, when power_bl or bins are asked
+  // for, its power in double -- stays under ds_bound; the chunks are cut at multiples of the transform's 128 rows where that fits.
+  int delay_spectrum(const cal_delay_spectrum_desc* d, const void* g_r, const void* g_i, double* power_bl, double* norm_bl, double* power_bin,
+                     double* count_bin) override {
+    HIP_TRY(hipSetDevice(device));
+    if (!d) return fail(CAL_ERR_INVALID, "delay_spectrum: null description");
+    CAL_TRY(require_set("delay_spectrum", false));
+    if ((g_r == nullptr) != (g_i == nullptr)) return fail(CAL_ERR_INVALID, "delay_spectrum: give both g_r and g_i, or neither");
+    if (!g_r && !has_gains) return fail(CAL_ERR_STATE, "delay_spectrum: the gains must be set (cal_solver_set_params) or given");
+    if (d->ndelays < 1 || d->ndelays > 4096) return fail(CAL_ERR_INVALID, "delay_spectrum: ndelays = %d lies outside [1, 4096]", d->ndelays);
+    if ((d->what & 7) == 0 || (d->what & ~7)) return fail(CAL_ERR_INVALID, "delay_spectrum: what = %d: bits 0 (data), 1 (model), 2 (residual), at least one", d->what);
+    if (d->calibrated != 0 && d->calibrated != 1) return fail(CAL_ERR_INVALID, "delay_spectrum: calibrated = %d (0 or 1)", d->calibrated);
+    if (!d->op_r || !d->op_i || !d->norm_f) return fail(CAL_ERR_INVALID, "delay_spectrum: null operator or norm_f");
+    if (d->nbins < 0) return fail(CAL_ERR_INVALID, "delay_spectrum: nbins = %d", d->nbins);
+    if ((d->nbins == 0) != (d->bin_of_bl == nullptr)) return fail(CAL_ERR_INVALID, "delay_spectrum: bin_of_bl goes with nbins > 0, and only with it");
+    if (d->nbins == 0 && (power_bin || count_bin)) return fail(CAL_ERR_INVALID, "delay_spectrum: binned outputs need nbins > 0");
+    const int nd = d->ndelays, nbins = d->nbins;
+    const int nq = (d->what & 1) + (d->what >> 1 & 1) + (d->what >> 2 & 1);
+    if ((long long)nq * nbins * nd + nbins > (1ll << 31) - 1) return fail(CAL_ERR_INVALID, "delay_spectrum: nbins = %d is too many", nbins);
+    // the sorted row list of every bin (CSR, like ant_ptr / ant_ent)
+    std::vector<int> bin_ptr(nbins + 1, 0), bin_ent;
+    for (int b = 0; b < nbls && nbins; ++b) {
+      const int n = d->bin_of_bl[b];
+      if (n < -1 || n >= nbins) return fail(CAL_ERR_INVALID, "delay_spectrum: bin_of_bl[%d] = %d lies outside [-1, %d)", b, n, nbins);
+      if (n >= 0) ++bin_ptr[n + 1];
+    }
+    if (nbins) {
+      for (int n = 0; n < nbins; ++n) bin_ptr[n + 1] += bin_ptr[n];
+      bin_ent.resize(bin_ptr[nbins]);
+      std::vector<int> fill(bin_ptr.begin(), bin_ptr.end() - 1);
+      for (int b = 0; b < nbls; ++b)
+        if (d->bin_of_bl[b] >= 0) bin_ent[fill[d->bin_of_bl[b]]++] = b;
+    }
+    // chunks of rows under the bound
+    const int xpitch = ds_xpitch(fpad), ndpad = ds_ndpad(nd);
+    const bool with_power = power_bl != nullptr || nbins > 0;
+    const size_t row_bytes = (size_t)nq * 2 * xpitch * sizeof(T) + (with_power ? (size_t)nq * nd * sizeof(double) : 0);
+    long long crows = std::max<long long>(1, ds_bound / (long long)row_bytes);
+    if (crows > kDsRows) crows -= crows % kDsRows;
+    crows = std::min<long long>(crows, nbls);
+    const int nchunks = (int)((nbls + crows - 1) / crows);
+    std::vector<int> chunk_ptr((size_t)nchunks * nbins * 2);  // per chunk and bin: its piece of the bin's list
+    for (int c = 0; c < nchunks && nbins; ++c) {
+      const long long b0 = c * crows, b1 = std::min<long long>(nbls, b0 + crows);
+      for (int n = 0; n < nbins; ++n) {
+        const int* e0 = bin_ent.data() + bin_ptr[n];
+        const int* e1 = bin_ent.data() + bin_ptr[n + 1];
+        chunk_ptr[((size_t)c * nbins + n) * 2] = (int)(std::lower_bound(e0, e1, (int)b0) - bin_ent.data());
+        chunk_ptr[((size_t)c * nbins + n) * 2 + 1] = (int)(std::lower_bound(e0, e1, (int)b1) - bin_ent.data());
+      }
+    }
+    // the operator image, built once per call: [re, im][xpitch][ndpad] T, zero beyond nfreqs and ndelays
+    std::vector<T> image((size_t)2 * xpitch * ndpad, (T)0);
+    for (int part = 0; part < 2; ++part) {
+      const T* src = static_cast<const T*>(part ? d->op_i : d->op_r);
+      for (int f = 0; f < nfreqs; ++f) std::copy(src + (size_t)f * nd, src + (size_t)(f + 1) * nd, image.begin() + ((size_t)part * xpitch + f) * ndpad);
+    }
+    std::vector<double> h_norm_f((size_t)xpitch, 0.0);
+    std::copy(d->norm_f, d->norm_f + nfreqs, h_norm_f.begin());
+    // (the buffers are kept between calls: a fit asks for the same sizes for every slice)
+    auto put = [&](DevBuf& b, const void* src, size_t bytes) -> int {
+      CAL_TRY(b.reserve(bytes, false));
+      if (bytes) HIP_TRY(copy_sync(b.p, src, bytes, hipMemcpyHostToDevice));
+      return CAL_OK;
+    };
+    CAL_TRY(put(ds_op, image.data(), image.size() * sizeof(T)));
+    CAL_TRY(put(ds_normf, h_norm_f.data(), h_norm_f.size() * sizeof(double)));
+    if (nbins) {
+      CAL_TRY(put(ds_ent, bin_ent.data(), bin_ent.size() * sizeof(int)));
+      CAL_TRY(put(ds_ptr, chunk_ptr.data(), chunk_ptr.size() * sizeof(int)));
+    }
+    const size_t nbin_out = (size_t)nq * nbins * nd + nbins;  // power_bin | count_bin: the exchange payload
+    CAL_TRY(ds_out.reserve(((size_t)nbls + nbin_out) * sizeof(double)));
+    CAL_TRY(ds_x.reserve((size_t)nq * 2 * crows * xpitch * sizeof(T), false));
+    if (with_power) CAL_TRY(ds_pow.reserve((size_t)nq * crows * nd * sizeof(double), false));
+    const T2* g = gains.as<T2>();
+    if (g_r) {
+      CAL_TRY(fq_gains.reserve((size_t)nants * fpad * sizeof(T2)));
+      CAL_TRY(upload_rows(g_r, fq_gains.as<T>(), nants, 2, 0));
+      CAL_TRY(upload_rows(g_i, fq_gains.as<T>(), nants, 2, 1));
+      g = fq_gains.as<T2>();
+    }
+    double* o_norm = ds_out.as<double>();
+    double* o_pbin = o_norm + nbls;
+    double* o_cbin = o_pbin + (size_t)nq * nbins * nd;
+    hipError_t copy_err = hipSuccess;
+    CAL_TRY(model_pass(2, [&](T* model_r, T* model_i, T*) {
+      for (int c = 0; c < nchunks; ++c) {
+        const long long b0 = c * crows;
+        const int nr = (int)std::min<long long>(crows, nbls - b0);
+        const size_t off = (size_t)b0 * fpad;
+        hipLaunchKernelGGL(dspec_rows_kernel<T>, dim3((nr + 3) / 4), dim3(256), 0, stream, model_r + off, model_i + off, data_r.as<T>() + off,
+                           data_i.as<T>() + off, wgts.as<T>() + off, g, bl_ant.as<int2>() + b0, ds_normf.as<double>(), nr, nfreqs, fpad, xpitch,
+                           d->what, d->calibrated, ds_x.as<T>(), o_norm + b0);
+        if (!with_power) continue;
+        hipLaunchKernelGGL(dspec_transform_kernel<T>, dim3((nr + kDsRows - 1) / kDsRows, ndpad / kDsCols, nq), dim3(256), 0, stream, ds_x.as<T>(),
+                           ds_op.as<T>(), o_norm + b0, nr, xpitch, nd, ndpad, ds_pow.as<double>());
+        if (nbins)
+          hipLaunchKernelGGL(dspec_bin_kernel, dim3(nbins, (nd + 255) / 256, nq), dim3(256), 0, stream, ds_pow.as<double>(), o_norm + b0,
+                             ds_ptr.as<int>() + (size_t)c * nbins * 2, ds_ent.as<int>(), (int)b0, nr, nd, nbins, c == 0 ? 1 : 0, o_pbin, o_cbin);
+        for (int q = 0; q < nq && power_bl && copy_err == hipSuccess; ++q)  // (the stream orders the copy before the next chunk's kernels)
+          copy_err = hipMemcpyAsync(power_bl + ((size_t)q * nbls + b0) * nd, ds_pow.as<double>() + (size_t)q * nr * nd, (size_t)nr * nd * sizeof(double),
+                                    hipMemcpyDeviceToHost, stream);
+      }
+    }));
+    HIP_TRY(copy_err);
+    // the bins of every rank's rows add up to the array's: ONE all-reduce of nwhat nbins ndelays + nbins doubles
+    if (nbins && comm_on()) CAL_TRY(all_reduce(o_pbin, nbin_out, CAL_XCHG_F64, CAL_XCHG_SUM));
+    if (norm_bl) HIP_TRY(hipMemcpyAsync(norm_bl, o_norm, (size_t)nbls * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (power_bin) HIP_TRY(hipMemcpyAsync(power_bin, o_pbin, (size_t)nq * nbins * nd * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (count_bin) HIP_TRY(hipMemcpyAsync(count_bin, o_cbin, (size_t)nbins * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return CAL_OK;
+  }
+  int set_delay_spectrum_scratch(int64_t bytes) override {
+    if (bytes < 0) return fail(CAL_ERR_INVALID, "set_delay_spectrum_scratch: negative bound");
+    ds_bound = bytes == 0 ? kCsScratchDefault : bytes;
+    for (DevBuf* b : {&ds_x, &ds_pow}) b->release();
     return CAL_OK;
   }
 
@@ -3106,6 +3236,12 @@ int cal_solver_fit_quality(cal_solver* s, const void* g_r, const void* g_i, doub
   NEED(s);
   return s->fit_quality(g_r, g_i, chisq_ant, wsum_ant, chisq_bl, wsum_bl);
 }
+int cal_solver_delay_spectrum(cal_solver* s, const cal_delay_spectrum_desc* desc, const void* g_r, const void* g_i, double* power_bl, double* norm_bl,
+                              double* power_bin, double* count_bin) {
+  NEED(s);
+  return s->delay_spectrum(desc, g_r, g_i, power_bl, norm_bl, power_bin, count_bin);
+}
+int cal_solver_set_delay_spectrum_scratch(cal_solver* s, int64_t bytes) { NEED(s); return s->set_delay_spectrum_scratch(bytes); }
 int cal_solver_robust_weights(cal_solver* s, const cal_robust_desc* desc, double* scale_bl, double* ndown_bl) { NEED(s); return s->robust_weights(desc, scale_bl, ndown_bl); }
 int cal_solver_get_weights(cal_solver* s, void* out, int which) { NEED(s); return s->get_weights(out, which); }
 int cal_solver_init_coeffs(cal_solver* s, const void* sr, const void* si) { NEED(s); return s->init_coeffs(sr, si); }

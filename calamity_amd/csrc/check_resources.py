@@ -15,7 +15,9 @@ instances of both dtypes), `gain_solve_rows_kernel`, `gain_solve_ant_kernel`,
 (coeff_solve_kernels.hpp), `gain_basis_gram_kernel`, `gain_basis_chol_kernel` (gain_basis_solve_kernels.hpp; both pairs are built on the
 shared Gram and Cholesky core of normal_solve.hpp), `gain_time_kron_kernel`, `gain_time_chol_kernel`, `gain_time_chan_kernel`
 (gain_time_solve_kernels.hpp), `fit_error_factor_kernel`, `fit_error_leverage_kernel`, `fit_error_rows_kernel` (fit_error_kernels.hpp), every `gn_*_kernel`
-(gauss_newton_kernels.hpp), every `lbfgs_*_kernel` (lbfgs_kernels.hpp): no scratch, no spilled VGPRs."""
+(gauss_newton_kernels.hpp), every `lbfgs_*_kernel` (lbfgs_kernels.hpp): no scratch, no spilled VGPRs.
+`dspec_rows_kernel`, `dspec_transform_kernel`, `dspec_bin_kernel` (delay_spectrum_kernels.hpp), both dtypes: no scratch, no spilled VGPRs, and
+two waves per SIMD in the transform kernel."""
 import re
 import sys
 
@@ -61,6 +63,16 @@ for line in sys.stdin:
         # Gauss-Newton step and those of L-BFGS keep their accumulators in registers: no scratch
         m = re.search(r"remark:\s+(ScratchSize \[bytes/lane\]|VGPRs Spill): (\d+)", line)
         if m and int(m.group(2)) != 0:
+            bad.append(f"{cur}: {m.group(1)} = {m.group(2)}")
+        continue
+    if cur is not None and any(k in cur for k in ("dspec_rows_kernel", "dspec_transform_kernel", "dspec_bin_kernel")):
+        # the three of the delay spectrum: no scratch, no spilled VGPRs; the transform keeps 2 x 8 accumulator tiles per wave and is
+        # written for two waves per SIMD in both dtypes
+        m = re.search(r"remark:\s+(ScratchSize \[bytes/lane\]|VGPRs Spill|Occupancy \[waves/SIMD\]): (\d+)", line)
+        if m and m.group(1).startswith("Occupancy"):
+            if "dspec_transform_kernel" in cur and int(m.group(2)) < 2:
+                bad.append(f"{cur}: occupancy {m.group(2)} waves/SIMD (< 2)")
+        elif m and int(m.group(2)) != 0:
             bad.append(f"{cur}: {m.group(1)} = {m.group(2)}")
         continue
     if cur is None or "fused_dense" not in cur:

@@ -263,6 +263,58 @@ def gain_time_dpss_basis(times_jd, time_scale_s, eigenval_cutoff=1e-10):
     return np.ascontiguousarray(amat.real)
 
 
+BH4_COEFFS = (0.35875, 0.48829, 0.14128, 0.01168)  # the four-term Blackman-Harris window
+
+
+def delay_taper(nfreqs, taper="bh4"):
+    """The taper of ``delay_transform`` on ``nfreqs`` channels, float64: ``"bh4"`` the four-term Blackman-Harris window
+    ``t_n = a0 - a1 cos(2 pi n / (N - 1)) + a2 cos(4 pi n / (N - 1)) - a3 cos(6 pi n / (N - 1))`` with ``a = BH4_COEFFS``; ``"none"``
+    ones; an array ``[nfreqs]`` itself.  Anything else raises ``ValueError``."""
+    nfreqs = int(nfreqs)
+    if isinstance(taper, str):
+        if taper == "none":
+            return np.ones(nfreqs)
+        if taper == "bh4":
+            if nfreqs == 1:
+                return np.ones(1)
+            x = 2.0 * np.pi * np.arange(nfreqs) / (nfreqs - 1)
+            a = BH4_COEFFS
+            return a[0] - a[1] * np.cos(x) + a[2] * np.cos(2.0 * x) - a[3] * np.cos(3.0 * x)
+        raise ValueError(f"delay_spectrum_taper must be 'bh4', 'none' or an array of Nfreqs values, got {taper!r}")
+    t = np.asarray(taper, dtype=np.float64)
+    if t.shape != (nfreqs,) or not np.all(np.isfinite(t)):
+        raise ValueError(f"a taper array must hold Nfreqs = {nfreqs} finite values, got shape {t.shape}")
+    return t
+
+
+def delay_transform(freqs, taper="bh4", max_delay_ns=None):
+    """The tapered discrete Fourier transform along frequency as a matrix, for ``HipFitSolver.delay_spectrum``:
+    ``(op [Nfreqs, Ndelays] complex128, norm_f [Nfreqs], delays_ns [Ndelays])`` with NumPy's FFT sign and an fftshifted axis,
+
+        op[f, k] = t_f exp(-2 pi i f k' / Nfreqs),   k' = k - Nfreqs // 2,   delays = k' / (Nfreqs df)
+
+    so that ``x @ op == np.fft.fftshift(np.fft.fft(t * x))``; ``df`` is the mean channel spacing.  ``max_delay_ns`` keeps only the
+    columns with ``|delay| <= max_delay_ns``.  ``taper``: see ``delay_taper``.  ``norm_f = t^2``: the power ``|X|^2 / sum_f mask
+    norm_f`` of white noise of unit variance per channel is then 1 at every delay, whatever is flagged."""
+    freqs = np.asarray(freqs, dtype=np.float64).ravel()
+    n = len(freqs)
+    if n < 1:
+        raise ValueError("delay_transform needs at least one frequency")
+    t = delay_taper(n, taper)
+    if max_delay_ns is not None and not (np.isfinite(float(max_delay_ns)) and float(max_delay_ns) >= 0.0):
+        raise ValueError(f"delay_spectrum_max_dly must be a delay >= 0 in ns, got {max_delay_ns!r}")
+    df = float(np.mean(np.diff(freqs))) if n > 1 else 1.0
+    kp = np.arange(n) - n // 2
+    delays_ns = kp / (n * df) * 1e9
+    if max_delay_ns is not None:
+        keep = np.abs(delays_ns) <= float(max_delay_ns)
+        kp, delays_ns = kp[keep], delays_ns[keep]
+    # (f k' mod Nfreqs taken in integers: the phase stays exact for any Nfreqs)
+    phase = (np.outer(np.arange(n), kp) % n).astype(np.float64)
+    op = t[:, None] * np.exp(-2j * np.pi * phase / n)
+    return op, t * t, delays_ns
+
+
 def get_redundant_grps_data(uvdata, remove_redundancy=False, tol=1.0, include_autos=False):
     """Redundant groups of the antenna pairs that carry data -- same arguments and return tuple as modeling.py:10-81:
     ``(antpairs, red_grps, vec_bin_centers, lengths)`` with one bin centre / length per returned group.

@@ -318,6 +318,68 @@ class HipFitSolver:
                                                     _ptr(out["chisq_bl"]), _ptr(out["wsum_bl"])))
         return out
 
+    def delay_spectrum(self, op, norm_f, what=("data", "model", "resid"), calibrated=False, bin_of_bl=None, nbins=0, per_baseline=False,
+                       g_r=None, g_i=None):
+        """Where the power of data, model and residual sits in delay (cal_solver_delay_spectrum), in solver units.  ``op``
+        ``[nfreqs, ndelays]`` complex: the transform along frequency with the taper folded in (``modeling.delay_transform``, or any
+        other linear spectral estimator); ``norm_f`` ``[nfreqs]``: what an unflagged channel adds to a row's normalisation (the
+        taper squared).  With ``G = g_i conj(g_j)``, ``m = A c`` and ``mask = (w != 0)`` for the weights the solver holds now::
+
+            x_q[b][f]  = mask q[b][f],   q = d, G m, d - G m        (calibrated: d / G, m, d / G - m, zero where |G|^2 == 0)
+            X_q[b][k]  = sum_f x_q[b][f] op[f][k]                   (products in the solver's dtype, on the matrix cores)
+            norm_bl[b] = sum_f mask norm_f[f]
+            power      = |X_q[b][k]|^2 / norm_bl[b]                 0 where norm_bl[b] == 0
+
+        ``what``: which of ``"data"``, ``"model"``, ``"resid"`` to form.  ``bin_of_bl`` ``[nbls]`` integers in ``[-1, nbins)`` (-1: the
+        row is left out): the returned entry of each quantity asked for is then ``[nbins, ndelays]``, the SUM of the power over the
+        bin's rows with ``norm_bl > 0`` in ascending row order, and ``"count_bin"`` ``[nbins]`` their number.  ``per_baseline=True``
+        adds ``"per_baseline": {quantity: [nbls, ndelays]}`` (as large as the data: off by default).  ``"norm_bl"`` is always
+        returned.  ``g_r``, ``g_i``: gains for this call only, as in ``fit_quality``.  All float64; sums in a fixed order: two calls
+        give the same bits.  The parameters, moments, weights and loop state are untouched.  Under an exchange the binned arrays are
+        summed over the ranks (one all-reduce); ``norm_bl`` and ``per_baseline`` stay this rank's own rows."""
+        if (g_r is None) != (g_i is None):
+            raise ValueError("give both g_r and g_i, or neither")
+        what = (what,) if isinstance(what, str) else tuple(what)
+        if not what or any(q not in _lib.DELAY_SPECTRUM_WHAT for q in what) or len(set(what)) != len(what):
+            raise ValueError(f"what must name one or more of {sorted(_lib.DELAY_SPECTRUM_WHAT)} once each, got {what!r}")
+        names = [q for q in ("data", "model", "resid") if q in what]  # the library's order
+        op = np.asarray(op)
+        if op.ndim != 2 or op.shape[0] != self.nfreqs:
+            raise ValueError(f"op must be [nfreqs = {self.nfreqs}, ndelays], got shape {op.shape}")
+        nd = op.shape[1]
+        op_r, op_i = self._real(op.real), self._real(op.imag)
+        norm_f = np.ascontiguousarray(norm_f, dtype=np.float64)
+        if norm_f.shape != (self.nfreqs,):
+            raise ValueError(f"norm_f must be [nfreqs = {self.nfreqs}], got shape {norm_f.shape}")
+        nbins = int(nbins)
+        if (bin_of_bl is None) != (nbins == 0):
+            raise ValueError("give bin_of_bl and nbins > 0 together, or neither")
+        bins = None
+        if bin_of_bl is not None:
+            bins = np.ascontiguousarray(bin_of_bl, dtype=np.int32)
+            if bins.shape != (self.nbls,):
+                raise ValueError(f"bin_of_bl must be [nbls = {self.nbls}], got shape {bins.shape}")
+        gs = (self.nants, self.nfreqs)
+        a = None if g_r is None else self._real(g_r, gs)
+        b = None if g_i is None else self._real(g_i, gs)
+        d = _lib.DelaySpectrumDesc(nd, sum(_lib.DELAY_SPECTRUM_WHAT[q] for q in names), int(bool(calibrated)), nbins,
+                                   None if bins is None else bins.ctypes.data, op_r.ctypes.data, op_i.ctypes.data, norm_f.ctypes.data)
+        norm_bl = np.empty(self.nbls, dtype=np.float64)
+        p_bl = np.empty((len(names), self.nbls, nd), dtype=np.float64) if per_baseline else None
+        p_bin = np.empty((len(names), nbins, nd), dtype=np.float64) if nbins else None
+        c_bin = np.empty(nbins, dtype=np.float64) if nbins else None
+        _lib.check(self._lib.cal_solver_delay_spectrum(self._h, C.byref(d), _ptr(a), _ptr(b), _ptr(p_bl), _ptr(norm_bl), _ptr(p_bin), _ptr(c_bin)))
+        out = {"norm_bl": norm_bl}
+        if nbins:
+            out.update({q: p_bin[i] for i, q in enumerate(names)}, count_bin=c_bin)
+        if per_baseline:
+            out["per_baseline"] = {q: p_bl[i] for i, q in enumerate(names)}
+        return out
+
+    def _set_delay_spectrum_scratch(self, nbytes):
+        """Scratch bound of ``delay_spectrum`` in bytes (0: the default); the results do not depend on it (tests)."""
+        _lib.check(self._lib.cal_solver_set_delay_spectrum_scratch(self._h, int(nbytes)))
+
     def fit_errors(self, ridge=1e-6, model_var=True, gain_var=True, coeffs=True):
         """The errors of the fit at the solver's current parameters (cal_solver_fit_errors): the inverses of the curvature matrices
         of ``solve_coeffs`` and ``solve_gains``.  With ``G = g_i conj(g_j)`` from the full (expanded) gains, ``q = w |G|^2``, ``A_b``

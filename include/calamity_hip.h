@@ -567,6 +567,57 @@ int cal_solver_set_coeff_solve_scratch(cal_solver* s, int64_t bytes);
 typedef struct cal_fit_errors_counts { int32_t nsolved; int32_t nsingular; } cal_fit_errors_counts;
 int cal_solver_fit_errors(cal_solver* s, double ridge, double* coeff_var, double* model_var, double* leverage_bl, double* nsamp_bl,
                           double* gain_var, cal_fit_errors_counts* counts);
+/* Where the power of data, model and residual sits in DELAY (no counterpart in the reference): the transform along frequency of
+ * every baseline row as one complex matrix product against a small operator shared by all rows, from the planes the solver holds.
+ * For baseline row b with antennas (i, j) and channel f, in solver units:
+ *   w = the weight plane as the solver holds it now, m = A c with the current coefficients, g = the gains of this call,
+ *   G[b][f]    = g_i[f] conj(g_j[f])                 mask[b][f] = (w[b][f] != 0)
+ *   q[b][f]    = d, G m, d - G m                     (calibrated = 0: data, model, residual, bits 0, 1, 2 of `what`)
+ *              = d / G, m, d / G - m                 (calibrated = 1; all three zero where |G|^2 == 0)
+ *   x_q[b][f]  = mask q[b][f]                        formed in the solver's dtype, in the order the loss kernels form them
+ *   X_q[b][k]  = sum_f x_q[b][f] (op_r + i op_i)[f][k]                            k < ndelays
+ *   norm_bl[b] = sum_f mask norm_f[f]                                             [nbls]
+ *   power_bl[q][b][k]  = |X_q[b][k]|^2 / norm_bl[b]; 0 where norm_bl[b] == 0      [nwhat][nbls][ndelays]
+ *   power_bin[q][n][k] = sum of power_bl[q][b][k] over the rows b with bin_of_bl[b] == n and norm_bl[b] > 0,
+ *                        taken in ascending b                                     [nwhat][nbins][ndelays]
+ *   count_bin[n]       = the number of such rows (an integer, returned as a double)   [nbins]
+ * nwhat is the number of bits set in `what`; the quantities asked for are stored in the order data, model, residual.  op is any
+ * operator [nfreqs][ndelays] -- a tapered DFT (modeling.delay_transform), a least-squares or DPSS spectral estimator -- with the taper
+ * folded in; norm_f is what an unflagged channel adds to a row's normalisation (the taper squared).  A row that is flagged throughout
+ * has power 0 and enters no bin.
+ * The products run on the matrix cores in the solver's dtype (v_mfma_f32_16x16x4_f32 / v_mfma_f64_16x16x4_f64); |X|^2, the division
+ * and every sum over rows are taken in double in a fixed order, no float atomics: two calls give the same bits.  All outputs are
+ * doubles; any output pointer may be NULL (power_bin and count_bin need nbins > 0).
+ *   g_r, g_i: as in cal_solver_fit_quality -- [nants][nfreqs] or both NULL; NULL: the solver's current full gains, whatever gain
+ *   bases are set; given gains are used for this call only.
+ * Errors: CAL_ERR_STATE when problem, data or coefficients are not set, or the gains neither set nor given; CAL_ERR_INVALID for a
+ * null description, a `what` without a bit of 1 | 2 | 4 (or with others), ndelays outside [1, 4096], a `calibrated` other than 0 or
+ * 1, nbins < 0, a bin_of_bl that is NULL with nbins > 0 (or given with nbins == 0) or holds an index outside [-1, nbins), a null
+ * operator or norm_f.
+ * Works for every layout and kernel path, fitting groups of several baselines, bl_alias, nslices > 1 and the joint time-basis layout:
+ * a row is a row, and the caller's bin_of_bl decides what is averaged with what.  It runs the model pass of cal_solver_model and, like
+ * cal_solver_fit_quality, puts the loop state back: a run continued after the call is bit-identical to one without it.
+ * The rows are worked through in chunks whose scratch -- the masked planes in the solver's dtype and, when power_bl or bins are asked
+ * for, the chunk's power in double -- stays under the bound of cal_solver_set_delay_spectrum_scratch (never less than one row).  The
+ * result does not depend on the chunks by a bit; the full [nwhat][nbls][ndelays] array never exists on the device.
+ * Under a communicator or exchange hook power_bin | count_bin are summed over the ranks in ONE all-reduce of
+ * nwhat nbins ndelays + nbins doubles (CAL_XCHG_F64, CAL_XCHG_SUM), whichever outputs are asked for (nbins == 0: none); power_bl and
+ * norm_bl stay the rank's own rows. */
+typedef struct cal_delay_spectrum_desc {
+  int32_t ndelays;          /* columns of the operator, 1 <= ndelays <= 4096 */
+  int32_t what;             /* bit 0: data, bit 1: model, bit 2: residual; at least one */
+  int32_t calibrated;       /* 0: d, G m, d - G m (G = g_i conj(g_j)); 1: d / G, m, d / G - m, zero where |G|^2 == 0 */
+  int32_t nbins;            /* 0: no binned output */
+  const int32_t* bin_of_bl; /* [nbls] in [-1, nbins): -1 leaves the row out; NULL iff nbins == 0 */
+  const void* op_r;         /* [nfreqs][ndelays], solver dtype: the transform along frequency, taper folded in */
+  const void* op_i;
+  const double* norm_f;     /* [nfreqs]: what an unflagged channel adds to the row's normalisation (the taper squared) */
+} cal_delay_spectrum_desc;
+int cal_solver_delay_spectrum(cal_solver* s, const cal_delay_spectrum_desc* desc, const void* g_r, const void* g_i, double* power_bl,
+                              double* norm_bl, double* power_bin, double* count_bin);
+/* The scratch bound of cal_solver_delay_spectrum in bytes (0: the default, 256 MiB; negative: CAL_ERR_INVALID).  The outputs do not
+ * depend on it: tests use it to send a small problem through several chunks. */
+int cal_solver_set_delay_spectrum_scratch(cal_solver* s, int64_t bytes);
 /* The coefficients of a frequency gain basis in closed form (no counterpart in the reference): the damped StefCal sweeps of
  * cal_solver_solve_gains projected on the basis g = g0 + B y of cal_solver_set_gain_basis.  With the other antennas held fixed the
  * chi-square is quadratic in one antenna's y.  num, den are exactly cal_solver_solve_gains': the model pass, then P, Q, then the
