@@ -102,6 +102,18 @@ class DelaySpectrumDesc(C.Structure):
 DELAY_SPECTRUM_WHAT = {"data": 1, "model": 2, "resid": 4}
 
 
+class DegeneracyDesc(C.Structure):
+    """cal_degeneracy_desc (include/calamity_hip.h: cal_solver_fix_degeneracies): mode (DEGENERACY_MODES), iters >= 1, the reference
+    planes ref_r, ref_i and their weights ref_w (NULL: the solver's) [nbls][nfreqs] in the solver's dtype, antpos [nants per slice][2]
+    and freqs [nfreqs] float64, the gains g and the reference gains gref [nants][nfreqs] (each pair may be NULL)."""
+    _fields_ = [("mode", C.c_int), ("iters", C.c_int32), ("ref_r", C.c_void_p), ("ref_i", C.c_void_p), ("ref_w", C.c_void_p),
+                ("antpos", C.c_void_p), ("freqs", C.c_void_p), ("g_r", C.c_void_p), ("g_i", C.c_void_p), ("gref_r", C.c_void_p),
+                ("gref_i", C.c_void_p)]
+
+
+DEGENERACY_MODES = {"channel": 0, "band": 1}
+
+
 class CoeffSolveDesc(C.Structure):
     _fields_ = [("niters", C.c_int32), ("reset_coeff_moments", C.c_int32), ("damping", C.c_double), ("ridge", C.c_double), ("slice_mask", C.c_void_p)]
 
@@ -212,6 +224,7 @@ SYMBOLS = {
     "cal_solver_robust_weights": (C.c_int, [_P, C.POINTER(RobustDesc), _P, _P]),
     "cal_solver_delay_spectrum": (C.c_int, [_P, C.POINTER(DelaySpectrumDesc), _P, _P, _P, _P, _P, _P]),
     "cal_solver_set_delay_spectrum_scratch": (C.c_int, [_P, C.c_int64]),
+    "cal_solver_fix_degeneracies": (C.c_int, [_P, C.POINTER(DegeneracyDesc), _P, _P, _P, _P, _P, _P, _P]),
     "cal_solver_get_weights": (C.c_int, [_P, _P, C.c_int]),
     "cal_solver_solve_coeffs": (C.c_int, [_P, C.POINTER(CoeffSolveDesc), C.POINTER(CoeffSolveResult)]),
     "cal_solver_set_coeff_solve_scratch": (C.c_int, [_P, C.c_int64]),

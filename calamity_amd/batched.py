@@ -269,6 +269,16 @@ class SliceBatchFitter:
             out["per_baseline"] = {q: self._scatter([o["per_baseline"][q] for o in outs], self.rows) for q in outs[0]["per_baseline"]}
         return out
 
+    def fix_degeneracies(self, ref_r, ref_i, antpos, ref_w=None, mode="channel", iters=6, freqs=None, g_r=None, g_i=None, gref_r=None,
+                         gref_i=None):
+        """``HipFitSolver.fix_degeneracies`` for all slices of the batch on the global arrays: ``ref_r``, ``ref_i``, ``ref_w``
+        ``[nt * nbls, nfreqs]`` slice-major, ``antpos`` ``[nants of one slice, 2]``; the per-channel results are ``[nt, nfreqs]``.  A
+        slice's sums need the slice whole on one worker: with several workers (the fitting groups shared out) the library refuses the
+        call, since the channel sums would need an exchange per iteration."""
+        return self._each(lambda r, s: s.fix_degeneracies(self._take(np.asarray(ref_r), r), self._take(np.asarray(ref_i), r), antpos,
+                                                          ref_w=None if ref_w is None else self._take(np.asarray(ref_w), r), mode=mode, iters=iters,
+                                                          freqs=freqs, g_r=g_r, g_i=g_i, gref_r=gref_r, gref_i=gref_i))[0]
+
     def _set_delay_spectrum_scratch(self, nbytes):
         self._each(lambda r, s: s._set_delay_spectrum_scratch(nbytes))
 

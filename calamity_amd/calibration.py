@@ -979,6 +979,61 @@ def delay_spectrum_entry(ds, dspec, rms, prob, ant_array):
     return entry
 
 
+DEGENERACY_MODES = {False: None, True: "channel", "channel": "channel", "band": "band"}
+
+
+def check_degeneracy_keywords(fix_degeneracies, degeneracy_iters, sky_model, freeze_model, model_regularization, devices=None, device_split=None):
+    """The degeneracy keywords of ``calibrate_and_model_tensor``, checked before anything is touched (``ValueError``).  Returns the mode,
+    ``None`` | ``"channel"`` | ``"band"``."""
+    if not any(fix_degeneracies is v for v in (False, True)) and fix_degeneracies not in ("channel", "band"):
+        raise ValueError(f"fix_degeneracies must be False, True, 'channel' or 'band', got {fix_degeneracies!r}")
+    mode = DEGENERACY_MODES[fix_degeneracies]
+    if mode is None:
+        return None
+    if isinstance(degeneracy_iters, bool) or int(degeneracy_iters) != degeneracy_iters or int(degeneracy_iters) < 1:
+        raise ValueError(f"degeneracy_iters must be an integer >= 1, got {degeneracy_iters!r}")
+    if sky_model is None:
+        raise ValueError("fix_degeneracies needs a sky_model: a reference made from the data themselves fixes nothing")
+    if freeze_model:
+        raise ValueError("fix_degeneracies with freeze_model: the model is the sky model already, nothing is degenerate")
+    if model_regularization == "post_hoc":
+        raise ValueError("fix_degeneracies and model_regularization='post_hoc' both set the amplitude: choose one")
+    if device_split == "groups" and devices is not None and (isinstance(devices, str) or len(list(devices)) > 1):
+        raise ValueError("fix_degeneracies with several devices that share out the fitting groups of a slice is not implemented (the channel sums "
+                         "would need an exchange per iteration): use one device or device_split='slices'")
+    return mode
+
+
+def _check_degeneracy_call(fix_degeneracies, degeneracy_iters, fitting_kwargs):
+    """``check_degeneracy_keywords`` for an entry point that hands ``fitting_kwargs`` on to ``calibrate_and_model_tensor``."""
+    return check_degeneracy_keywords(fix_degeneracies, degeneracy_iters, fitting_kwargs.get("sky_model"), fitting_kwargs.get("freeze_model", False),
+                                     fitting_kwargs.get("model_regularization", "sum"), fitting_kwargs.get("devices"), fitting_kwargs.get("device_split"))
+
+
+def degeneracy_setup(uvdata, ant_array, mode, iters, phase_ref):
+    """What the degeneracy fix of every slice of a call shares: the mode and iterations, the data's frequencies and the east, north
+    positions ``[Nants, 2]`` of the antennas in the order of ``ant_array`` (the positions ``delay_spectrum_setup`` takes its baseline
+    lengths from)."""
+    pos = {int(a): np.asarray(x, dtype=np.float64) for a, x in zip(np.asarray(uvdata.antenna_numbers), np.asarray(uvdata.antenna_positions))}
+    antpos = np.ascontiguousarray([pos[int(a)][:2] for a in np.asarray(ant_array)], dtype=np.float64)
+    return dict(mode=mode, iters=int(iters), phase_ref=bool(phase_ref), antpos=antpos, freqs=np.asarray(uvdata.freq_array, dtype=np.float64).ravel().copy())
+
+
+def degeneracy_entry(out, t, degen):
+    """Slice ``t`` of a ``fix_degeneracies`` result as what ``fit_history`` reports, per channel."""
+    return {"mode": degen["mode"], "amplitude": np.exp(out["eta"][t]), "phase": out["psi"][t].copy(), "tilt": out["tilt"][t].copy(),
+            "nsamples": out["nsamples"][t].astype(np.int64), "iters": degen["iters"], "last_step": out["last_step"][t].copy()}
+
+
+def _file_degeneracies(hist, gains, time, polarization, errs, entry):
+    """``hist["degeneracies"]`` of one slice; the slice's plane of ``gain_std`` follows the gains: times ``e^{-eta}``."""
+    hist["degeneracies"] = entry
+    if errs is not None and errs["gain_std"] is not None:
+        polnum = np.where(np.asarray(gains.jones_array) == polstr2num(polarization, x_orientation=gains.x_orientation))[0][0]
+        gindt = np.where(np.isclose(gains.time_array, time, atol=1e-7, rtol=0.0))[0][0]
+        errs["gain_std"][:, :, gindt, polnum] /= entry["amplitude"][None, :]
+
+
 def _report_slice(hist, gains, time, polarization, rms, prob, quality, errors, errs):
     """What one fitted (polarization, time) slice reports besides its losses, for the loop over the slices and for the batches alike:
     ``hist["robust"]`` from solver units and row order into the data's units, keyed by antenna numbers (``robust_history``); the slice's
@@ -1062,6 +1117,9 @@ def calibrate_and_model_tensor(
     lbfgs_ftol=0.0,
     fit_errors=False,
     fit_errors_ridge=1e-6,
+    fix_degeneracies=False,
+    degeneracy_iters=6,
+    degeneracy_phase_ref=True,
     delay_spectrum=False,
     delay_spectrum_taper="bh4",
     delay_spectrum_max_dly=None,
@@ -1254,9 +1312,26 @@ def calibrate_and_model_tensor(
       (the antenna pairs of ``fg_model_comps_dict``, the keys of ``per_baseline``): held as ``(j, i)`` its spectrum is the mirror image
       in delay of ``(i, j)``'s.  A joint time-basis fit reports every time on its own.
       ``ValueError`` before any device work for an unknown taper, a bin width that is not positive, a negative ``delay_spectrum_max_dly``.
+    * ``fix_degeneracies`` (``False`` | ``True`` = ``"channel"`` | ``"band"``; default off: no call changes by a bit and no new kernel is
+      launched), ``degeneracy_iters`` (6), ``degeneracy_phase_ref`` (``True``): refer every fitted slice to ``sky_model`` before it is
+      written (``HipFitSolver.fix_degeneracies``: one device pass after the fit).  The fit constrains only ``g_i conj(g_j) m``; an overall
+      amplitude, an overall phase and a phase gradient across the array are free per channel because the model absorbs them.  The call
+      estimates the amplitude ``e^{eta}`` and tilt ``Phi`` (rad / m, east and north) that bring the fitted model onto the sky model (the
+      slice's ``tensorize_data`` rows of it; weights: the sky model's own times ``data weights > 0``; positions: the antenna positions of
+      ``uvdata``) and, with ``degeneracy_phase_ref``, the phase against the gains the fit started from, and writes
+      ``g e^{-eta} e^{-i (Phi.r + psi)}`` and ``m e^{2 eta} e^{i Phi.d}`` instead of ``g`` and ``m``: gains of different times, nights
+      and runs then refer to the same sky.  ``"band"``: one amplitude and one sky shift ``Phi(f) = (nu_f / mean nu) Phi_0`` per slice.
+      ``resid`` does not change (to rounding), nor do quality, errors and delay spectra, which are taken before the transformation; the
+      values handed to the next time (``init_guesses_from_previous_time_step``) stay the raw fitted ones; the slice's plane of
+      ``fit_history["gain_std"]`` is multiplied by ``e^{-eta}``.  ``fit_history[polnum][time_index]["degeneracies"]`` holds ``mode``,
+      ``amplitude``, ``phase``, ``nsamples``, ``last_step`` ``[Nfreqs]``, ``tilt`` ``[Nfreqs, 2]`` and ``iters``; ``last_step`` (radians on
+      the longest baseline) tells a tilt outside the basin of about pi / 2.  ``ValueError`` before any device work for an unknown value,
+      ``degeneracy_iters < 1``, ``sky_model=None``, ``freeze_model``, ``model_regularization="post_hoc"`` (both set the amplitude) and
+      several devices that share out the fitting groups of a slice (``device_split="slices"`` works).
     * ``parallel_fits`` (default 1): with ``batch_slices=False``, fits that many slices concurrently, each on its own
       solver and HIP stream.
     (Nothing here is steered by environment variables: layout, devices and concurrency are arguments.)"""
+    degen_mode = check_degeneracy_keywords(fix_degeneracies, degeneracy_iters, sky_model, freeze_model, model_regularization, devices, device_split)
     if gain_basis is not None and gain_max_dly is not None:
         raise ValueError("give gain_basis or gain_max_dly, not both")
     _check_delay_spectrum(delay_spectrum, delay_spectrum_taper, delay_spectrum_max_dly, delay_spectrum_bllen_bin)
@@ -1340,6 +1415,7 @@ def calibrate_and_model_tensor(
         dspec = delay_spectrum_setup(uvdata, gains.ant_array, prob, taper=delay_spectrum_taper, max_dly=delay_spectrum_max_dly,
                                      bllen_bin=delay_spectrum_bllen_bin, calibrated=delay_spectrum_calibrated,
                                      per_baseline=delay_spectrum == "baselines")
+    degen = degeneracy_setup(uvdata, gains.ant_array, degen_mode, degeneracy_iters, degeneracy_phase_ref) if degen_mode is not None else None
     if parallel_fits is None:
         parallel_fits = 1
     if init_guesses_from_previous_time_step:
@@ -1364,7 +1440,7 @@ def calibrate_and_model_tensor(
             verbose=verbose, max_batch=max_batch, devices=devices, layout=layout, opt_kwargs=opt_kwargs,
             correct_model=correct_model, correct_resid=correct_resid, device_split=device_split, gain_basis=gain_basis,
             gain_time_basis=gain_time_basis, fit_quality=fit_quality,
-            controls=controls, errs=errs, dspec=dspec,
+            controls=controls, errs=errs, dspec=dspec, degen=degen,
         )
         _file_gain_std(fit_history, errs, gains)
         return model, resid, gains, fit_history  # (every slice left _fit_slices_batched in its final state)
@@ -1391,10 +1467,12 @@ def calibrate_and_model_tensor(
             )
             if sky_model is not None:
                 echo(f"{datetime.datetime.now()} Tensorizing sky model...\n", verbose=verbose)
-                sky_model_r, sky_model_i, _ = tensorize_data(
+                sky_model_r, sky_model_i, sky_wgts = tensorize_data(
                     sky_model, corr_inds=corr_inds, ants_map=ants_map, polarization=pol, time=time, data_scale_factor=rmsdata,
                     weights=weights, dtype=dtype,
                 )
+                if degen is not None:  # the reference's weights: the sky model's own, where the data have any
+                    degen_w = _flatten(sky_wgts, prob) * (_flatten(wgts, prob) > 0)
             else:
                 sky_model_r, sky_model_i = None, None
             if carry["first_time"] or not init_guesses_from_previous_time_step:
@@ -1420,6 +1498,7 @@ def calibrate_and_model_tensor(
                         new_wgts.append(w_new[start : start + n].reshape(w.shape).astype(dtype))
                         start += n
                     wgts = new_wgts
+            g0_r, g0_i = g_r, g_i  # the gains the fit starts from: the phase reference of fix_degeneracies
             (g_r, g_i, fg_r, fg_i, hist) = fit_gains_and_foregrounds(
                 g_r=g_r, g_i=g_i, fg_r=fg_r, fg_i=fg_i, data_r=data_r, data_i=data_i, wgts=wgts, fg_comps=fg_model_comps,
                 corr_inds=corr_inds, optimizer=optimizer, use_min=use_min, freeze_model=freeze_model,
@@ -1432,8 +1511,15 @@ def calibrate_and_model_tensor(
             # nants x nants cubes: one A c pass for both components, rows written straight back
             solver.set_params(c_r=coeffs_from_chunks(prob, fg_r), c_i=coeffs_from_chunks(prob, fg_i))
             m_r, m_i = solver.model()
+            w_r, w_i, fixed = g_r, g_i, None  # what is written; the values carried to the next time stay the fitted ones
+            if degen is not None:
+                ref_phase = (np.asarray(g0_r), np.asarray(g0_i)) if degen["phase_ref"] else (None, None)
+                fixed = solver.fix_degeneracies(_flatten(sky_model_r, prob), _flatten(sky_model_i, prob), degen["antpos"], ref_w=degen_w, mode=degen["mode"],
+                                                iters=degen["iters"], freqs=degen["freqs"], g_r=np.asarray(g_r), g_i=np.asarray(g_i), gref_r=ref_phase[0],
+                                                gref_i=ref_phase[1])
+                m_r, m_i, w_r, w_i = fixed["model_r"], fixed["model_i"], fixed["g_r"], fixed["g_i"]
             _insert_model_rows(model, time, pol, ants_map, prob, m_r, m_i, scale_factor=rmsdata)
-            insert_gains_into_uvcal(uvcal=gains, time=time, polarization=pol, gains_re=g_r, gains_im=g_i)
+            insert_gains_into_uvcal(uvcal=gains, time=time, polarization=pol, gains_re=w_r, gains_im=w_i)
             # at the reported parameters, on the data and weights the fit used (the solver still holds them)
             quality = solver.fit_quality(g_r, g_i) if fit_quality else None
             errors = None
@@ -1442,6 +1528,8 @@ def calibrate_and_model_tensor(
                 errors = solver.fit_errors(ridge=errs["ridge"], model_var=errs["samples"], gain_var=errs["with_gains"], coeffs=not freeze_model)
                 errors["chisq_bl"] = solver.fit_quality(g_r, g_i)["chisq_bl"]
             _report_slice(hist, gains, time, pol, rmsdata, prob, quality, errors, errs)
+            if fixed is not None:
+                _file_degeneracies(hist, gains, time, pol, errs, degeneracy_entry(fixed, 0, degen))
             if dspec is not None:
                 ds = solver.delay_spectrum(dspec["op"], dspec["norm_f"], calibrated=dspec["calibrated"], bin_of_bl=dspec["bin_of_bl"],
                                            nbins=dspec["nbins"], per_baseline=dspec["per_baseline"], g_r=g_r, g_i=g_i)
@@ -1675,7 +1763,7 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
                         skip_threshold, use_model_snr_weights, optimizer, use_min, freeze_model, tol, maxsteps, n_profile_steps,
                         profile_log_dir, model_regularization, verbose, max_batch, devices, layout, opt_kwargs, correct_model=True,
                         correct_resid=False, device_split=None, gain_basis=None, gain_time_basis=None, fit_quality=False,
-                        controls=FitControls(), errs=None, dspec=None):
+                        controls=FitControls(), errs=None, dspec=None, degen=None):
     """The pol x time loop of calibration.py:1160-1331 with the fits of all unskipped slices issued as batches: per slice
     exactly the host-side steps of the loop body (skip test :1173-1177, rms scale :1178-1182, tensorize :1184-1233, write-back
     :1271-1300, post-hoc renormalisation :1311-1319, residual and calibration state of the outputs :1322-1331), the gradient
@@ -1700,7 +1788,7 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
     # batches the host work of all but the first and the last disappears behind the fits.  The (polarization, time) slices of
     # different batches are disjoint parts of the containers, so the stages never touch the same rows.
     def prep(candidates):
-        d_r, d_i, w, s_r, s_i, g_r, g_i = [], [], [], [], [], [], []
+        d_r, d_i, w, s_r, s_i, g_r, g_i, r_w = [], [], [], [], [], [], [], []
         batch = []
         for sl in candidates:
             # skip test and rms scale of the slice (:1168-1182)
@@ -1721,11 +1809,14 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
             if sky_model is uvdata:  # (the data stand in for the sky model: the same rows)
                 s_r.append(dr_t)
                 s_i.append(di_t)
+                r_w.append(w_t)
             elif sky_model is not None:
-                sr_t, si_t, _ = _tensorize_flat(sky_model, prob, ants_map, sl["pol"], sl["time"], data_scale_factor=sl["rmsdata"], dtype=dtype,
-                                                want_weights=False)
+                sr_t, si_t, sw_t = _tensorize_flat(sky_model, prob, ants_map, sl["pol"], sl["time"], data_scale_factor=sl["rmsdata"], dtype=dtype,
+                                                   **({"weights": weights} if degen is not None else {"want_weights": False}))
                 s_r.append(sr_t)
                 s_i.append(si_t)
+                if degen is not None:  # the reference's weights of fix_degeneracies: the sky model's own, where the data have any
+                    r_w.append(sw_t * (w_t > 0))
             a, b = tensorize_gains(gains, dtype=dtype, time=sl["time"], polarization=sl["pol"])
             g_r.append(a)
             g_i.append(b)
@@ -1735,7 +1826,8 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
         pri = None
         if model_regularization == "sum" and not use_model_snr_weights:  # (with model-SNR weights the priors wait for the new weights: fit)
             pri = np.asarray([_prior_sums(a, b, c) for a, b, c in zip(s_r, s_i, w)])
-        return dict(batch=batch, w=cat(w), d_r=cat(d_r), d_i=cat(d_i), s_r=cat(s_r), s_i=cat(s_i), g_r=cat(g_r), g_i=cat(g_i), pri=pri)
+        return dict(batch=batch, w=cat(w), d_r=cat(d_r), d_i=cat(d_i), s_r=cat(s_r), s_i=cat(s_i), g_r=cat(g_r), g_i=cat(g_i), pri=pri,
+                    r_w=cat(r_w) if degen is not None else None)
 
     def fit(batch, arrs, on=None):
         nonlocal devices
@@ -1822,8 +1914,14 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
         if dspec is not None:  # every slice (a joint fit: every time) has bins of its own: bin_of_bl encodes (t, length bin)
             spectra = fitter.delay_spectrum(dspec["op"], dspec["norm_f"], calibrated=dspec["calibrated"], bin_of_bl=delay_spectrum_slice_bins(dspec, nt),
                                             nbins=nt * dspec["nbins"], per_baseline=dspec["per_baseline"], g_r=gm_r, g_i=gm_i)
+        fixed = None
+        if degen is not None:  # last: quality, errors and spectra are those of the fitted parameters (the product they depend on does not change)
+            ref_phase = (arrs["g_r"], arrs["g_i"]) if degen["phase_ref"] else (None, None)
+            fixed = fitter.fix_degeneracies(s_r, s_i, degen["antpos"], ref_w=arrs["r_w"], mode=degen["mode"], iters=degen["iters"], freqs=degen["freqs"],
+                                            g_r=gm_r, g_i=gm_i, gref_r=ref_phase[0], gref_i=ref_phase[1])
+            m_r, m_i, gm_r, gm_i = fixed["model_r"], fixed["model_i"], fixed["g_r"], fixed["g_i"]
         echo(f"{datetime.datetime.now()} ... fitted.\n", verbose=verbose)
-        return dict(result=result, results=results, m_r=m_r, m_i=m_i, gm_r=gm_r, gm_i=gm_i, quality=quality, errors=errors, spectra=spectra)
+        return dict(result=result, results=results, m_r=m_r, m_i=m_i, gm_r=gm_r, gm_i=gm_i, quality=quality, errors=errors, spectra=spectra, fixed=fixed)
 
     def post(batch, out):
         for t, (sl, res) in enumerate(zip(batch, out["results"])):
@@ -1845,6 +1943,8 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
                 if "coeff_var" in e:  # (the library counts over the batch: the slice's own are its groups with an all-zero coeff_var)
                     e["nsingular"] = sum(1 for g in range(prob.ngrps) if not np.any(e["coeff_var"][prob.grp_coff[g] : prob.grp_coff[g + 1]]))
             _report_slice(hist, gains, sl["time"], sl["pol"], sl["rmsdata"], prob, q, e, errs)  # (before the post-hoc renormalisation, which leaves g_i conj(g_j) m as it is)
+            if out["fixed"] is not None:
+                _file_degeneracies(hist, gains, sl["time"], sl["pol"], errs, degeneracy_entry(out["fixed"], t, degen))
             if out["spectra"] is not None:
                 hist["delay_spectrum"] = delay_spectrum_entry(delay_spectrum_of_slice(out["spectra"], dspec, t, prob.nbls), dspec, sl["rmsdata"], prob,
                                                               gains.ant_array)
@@ -1867,6 +1967,9 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
     whole_slices = D > 1 and (device_split == "slices" or (device_split is None and len(batches) >= D))
     # (the caller's check over again, now that it is known whether the devices share out the groups of a slice)
     controls.check(gain_basis is not None, joint, freeze_model, use_min, groups_split=D > 1 and not whole_slices)
+    if degen is not None and D > 1 and not whole_slices:
+        raise ValueError(f"fix_degeneracies on devices {devices} that share out the fitting groups of a slice is not implemented (the channel sums would "
+                         "need an exchange per iteration): use one device or device_split='slices'")
     if whole_slices:
         # Whole batches on different devices: device d fits batches d, d + D, ... on a thread of its own (its solvers live on that
         # thread), nothing is exchanged between devices, and every slice is fitted exactly as it would be on one device.  One prep
@@ -2011,6 +2114,9 @@ def calibrate_and_model_dpss(
     red_tol=1.0,
     notebook_progressbar=False,
     fg_model_comps_dict=None,
+    fix_degeneracies=False,
+    degeneracy_iters=6,
+    degeneracy_phase_ref=True,
     delay_spectrum=False,
     delay_spectrum_taper="bh4",
     delay_spectrum_max_dly=None,
@@ -2020,8 +2126,9 @@ def calibrate_and_model_dpss(
 ):
     """Simultaneously solve for gains and model foregrounds with per-baseline DPSS vectors -- the kept entry point,
     calibration.py:1503-1584.  ``fg_model_comps_dict`` is accepted and ignored, as in the reference (:1564).  The ``delay_spectrum``
-    keywords are ``calibrate_and_model_tensor``'s."""
+    and ``fix_degeneracies`` / ``degeneracy_*`` keywords are ``calibrate_and_model_tensor``'s."""
     _check_delay_spectrum(delay_spectrum, delay_spectrum_taper, delay_spectrum_max_dly, delay_spectrum_bllen_bin)
+    _check_degeneracy_call(fix_degeneracies, degeneracy_iters, fitting_kwargs)
     waker = _wake_device(fitting_kwargs.get("devices"))
     try:
         dpss_model_comps_dict = modeling.yield_pbl_dpss_model_comps(
@@ -2032,7 +2139,8 @@ def calibrate_and_model_dpss(
             uvdata=uvdata, fg_model_comps_dict=dpss_model_comps_dict, include_autos=include_autos, verbose=verbose,
             notebook_progressbar=notebook_progressbar, delay_spectrum=delay_spectrum, delay_spectrum_taper=delay_spectrum_taper,
             delay_spectrum_max_dly=delay_spectrum_max_dly, delay_spectrum_bllen_bin=delay_spectrum_bllen_bin,
-            delay_spectrum_calibrated=delay_spectrum_calibrated, **fitting_kwargs,
+            delay_spectrum_calibrated=delay_spectrum_calibrated, fix_degeneracies=fix_degeneracies, degeneracy_iters=degeneracy_iters,
+            degeneracy_phase_ref=degeneracy_phase_ref, **fitting_kwargs,
         )
     finally:
         waker.join()
@@ -2060,6 +2168,9 @@ def calibrate_and_model_mixed(
     grp_size_threshold=5,
     model_comps_dict=None,
     save_dict_to=None,
+    fix_degeneracies=False,
+    degeneracy_iters=6,
+    degeneracy_phase_ref=True,
     delay_spectrum=False,
     delay_spectrum_taper="bh4",
     delay_spectrum_max_dly=None,
@@ -2070,8 +2181,9 @@ def calibrate_and_model_mixed(
     """Gains + foregrounds with DPSS vectors for baselines without frequency redundancy and joint covariance
     eigenvectors for groups of baselines whose uv tracks overlap -- calibration.py:1353-1500 (same signature and
     returns).  ``use_tensorflow_to_derive_modeling_comps`` is accepted for compatibility; the eigenproblems run on the
-    host either way.  The ``delay_spectrum`` keywords are ``calibrate_and_model_tensor``'s."""
+    host either way.  The ``delay_spectrum`` and ``fix_degeneracies`` / ``degeneracy_*`` keywords are ``calibrate_and_model_tensor``'s."""
     _check_delay_spectrum(delay_spectrum, delay_spectrum_taper, delay_spectrum_max_dly, delay_spectrum_bllen_bin)
+    _check_degeneracy_call(fix_degeneracies, degeneracy_iters, fitting_kwargs)
     fitting_grps, blvecs, _, _ = modeling.get_uv_overlapping_grps_conjugated(
         uvdata, red_tol=red_tol, include_autos=include_autos, red_tol_freq=red_tol_freq, n_angle_bins=n_angle_bins,
         notebook_progressbar=notebook_progressbar, require_exact_angle_match=require_exact_angle_match,
@@ -2094,7 +2206,8 @@ def calibrate_and_model_mixed(
         uvdata=uvdata, fg_model_comps_dict=model_comps_dict, include_autos=include_autos, verbose=verbose,
         notebook_progressbar=notebook_progressbar, use_redundancy=use_redundancy, delay_spectrum=delay_spectrum, delay_spectrum_taper=delay_spectrum_taper,
         delay_spectrum_max_dly=delay_spectrum_max_dly, delay_spectrum_bllen_bin=delay_spectrum_bllen_bin,
-        delay_spectrum_calibrated=delay_spectrum_calibrated, **fitting_kwargs,
+        delay_spectrum_calibrated=delay_spectrum_calibrated, fix_degeneracies=fix_degeneracies, degeneracy_iters=degeneracy_iters,
+        degeneracy_phase_ref=degeneracy_phase_ref, **fitting_kwargs,
     )
     return model, resid, gains, fitted_info
 
@@ -2203,6 +2316,9 @@ def read_calibrate_and_model_dpss(
     fit_errors=False,
     fit_errors_samples=False,
     fit_errors_ridge=1e-6,
+    fix_degeneracies=False,
+    degeneracy_iters=6,
+    degeneracy_phase_ref=True,
     delay_spectrum=False,
     delay_spectrum_taper="bh4",
     delay_spectrum_max_dly=None,
@@ -2230,8 +2346,11 @@ def read_calibrate_and_model_dpss(
     ``[Npols, Ntimes, nbins, Ndelays]`` each with ``nan`` for a skipped slice, ``data``, ``model``, ``resid``; ``nbls``
     ``[Npols, Ntimes, nbins]``; with ``"baselines"`` also ``antpairs`` ``[rows, 2]`` and ``data_bl``, ``model_bl``, ``resid_bl``
     ``[Npols, Ntimes, rows, Ndelays]``.
+    ``fix_degeneracies``, ``degeneracy_iters``, ``degeneracy_phase_ref`` are ``calibrate_and_model_tensor``'s too (Python keywords only);
+    the sky model is ``input_model_files`` and the written gains and model are the fixed ones.
     """
     _check_delay_spectrum(delay_spectrum, delay_spectrum_taper, delay_spectrum_max_dly, delay_spectrum_bllen_bin)
+    _check_degeneracy_call(fix_degeneracies, degeneracy_iters, dict(calibration_kwargs, sky_model=input_model_files))
     if delay_spectrum_outfile is not None and not delay_spectrum:
         raise ValueError("delay_spectrum_outfile needs delay_spectrum=True or 'baselines'")
     uvd = _read_uvdata(input_data_files)
@@ -2251,6 +2370,8 @@ def read_calibrate_and_model_dpss(
             **(dict(fit_errors="samples" if fit_errors_samples else True, fit_errors_ridge=fit_errors_ridge) if fit_errors or fit_errors_samples else {}),
             **(dict(delay_spectrum=delay_spectrum, delay_spectrum_taper=delay_spectrum_taper, delay_spectrum_max_dly=delay_spectrum_max_dly,
                     delay_spectrum_bllen_bin=delay_spectrum_bllen_bin, delay_spectrum_calibrated=delay_spectrum_calibrated) if delay_spectrum else {}),
+            **(dict(fix_degeneracies=fix_degeneracies, degeneracy_iters=degeneracy_iters, degeneracy_phase_ref=degeneracy_phase_ref)
+               if fix_degeneracies else {}),
         )
     finally:
         _DEVICE.update(saved)

@@ -32,6 +32,7 @@
 #include "coeff_solve_kernels.hpp"
 #include "fit_error_kernels.hpp"
 #include "delay_spectrum_kernels.hpp"
+#include "degeneracy_kernels.hpp"
 #include "gain_basis_solve_kernels.hpp"
 #include "gain_time_solve_kernels.hpp"
 #include "gauss_newton_kernels.hpp"
@@ -186,6 +187,8 @@ struct cal_solver {
   virtual int delay_spectrum(const cal_delay_spectrum_desc* d, const void* g_r, const void* g_i, double* power_bl, double* norm_bl, double* power_bin,
                              double* count_bin) = 0;
   virtual int set_delay_spectrum_scratch(int64_t bytes) = 0;
+  virtual int fix_degeneracies(const cal_degeneracy_desc* d, double* params, double* nsamp, double* last_step, void* out_g_r, void* out_g_i, void* out_m_r,
+                               void* out_m_i) = 0;
   virtual int get_weights(void* out, int which) = 0;
   virtual int solve_gains(const cal_gain_solve_desc* d) = 0;
   virtual int hold_slices(const uint8_t* mask) = 0;
@@ -274,6 +277,11 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
   // a chunk's masked planes in T (ds_x) and power in double (ds_pow); norm_bl | power_bin | count_bin (ds_out; the last two are the exchange payload)
   DevBuf ds_op, ds_normf, ds_ent, ds_ptr, ds_x, ds_pow, ds_out;
   int64_t ds_bound = kCsScratchDefault;        // bytes of scratch a chunk of rows may take (set_delay_spectrum_scratch)
+  // fix_degeneracies (degeneracy_kernels.hpp): the reference planes, then z0 ([2][nbls][fpad] T); the reference's weights when given
+  // ([nbls][fpad] T); d_b | the slice's antenna positions | nu_f / nu_ref | the slices' longest |d_b| (doubles); the slices' row lists |
+  // first segments | segments (ints); the segments' partial sums ([8][nseg][fpad] doubles); the channels' state ([14][nsl][fpad] + [nsl][2]
+  // doubles); g' and gref ([nants][fpad] T2 each)
+  DevBuf dg_z, dg_w, dg_geo, dg_idx, dg_part, dg_st, dg_gout, dg_gref;
   // normal_product / gauss_newton_step (gauss_newton_kernels.hpp), vectors over the flat parameter space (gn_np() elements): the direction s, the
   // gradient of G m and the saved parameters in T; the solution x, the residual, N s and D in double.  gn_m: m = A c, gn_sd: the data planes while
   // they are substituted ([2][nbls][fpad] T each); gn_rows: the rows' sums (3 nbls doubles); the dot products' partials, the slices' scalars and
@@ -635,7 +643,7 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     CAL_TRY(upload(ant_ptr, p.ant_ptr));
     CAL_TRY(upload(ant_ent, p.ant_ent));
 
-    for (DevBuf* b : {&gains_snap, &gains_alt, &coef_snap, &q1, &gcp1, &gc1, &model_buf, &scratch, &fq_out, &fq_gains, &gs_out, &gs_ptr, &gs_ent, &gs_mask, &cs_rhs, &rw_w0, &rw_out, &ds_op, &ds_normf, &ds_ent, &ds_ptr, &ds_x, &ds_pow, &ds_out,
+    for (DevBuf* b : {&gains_snap, &gains_alt, &coef_snap, &q1, &gcp1, &gc1, &model_buf, &scratch, &fq_out, &fq_gains, &gs_out, &gs_ptr, &gs_ent, &gs_mask, &cs_rhs, &rw_w0, &rw_out, &ds_op, &ds_normf, &ds_ent, &ds_ptr, &ds_x, &ds_pow, &ds_out, &dg_z, &dg_w, &dg_geo, &dg_idx, &dg_part, &dg_st, &dg_gout, &dg_gref,
                        &gn_s, &gn_g0, &gn_save, &gn_x, &gn_res, &gn_ns, &gn_D, &gn_m, &gn_sd, &gn_rows, &gn_part, &gn_scal, &gn_lam, &gn_grp, &gn_rowptr,
                        &lb_vec, &lb_part, &lb_dots, &lb_state, &lb_losses, &lb_count})
       b->release();
@@ -1928,6 +1936,174 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     if (bytes < 0) return fail(CAL_ERR_INVALID, "set_delay_spectrum_scratch: negative bound");
     ds_bound = bytes == 0 ? kCsScratchDefault : bytes;
     for (DevBuf* b : {&ds_x, &ds_pow}) b->release();
+    return CAL_OK;
+  }
+
+  // cal_solver_fix_degeneracies: the model pass of model(), then the six kernels of degeneracy_kernels.hpp.  The rows of every slice and their
+  // segments, d_b and the longest |d_b| are planned on the host from the plan's bl_ant and the caller's positions; nothing is read back to plan.
+  // m stays in the model planes (model_buf) for the whole call -- no other pass runs in between -- and m' overwrites it there at the end.
+  int fix_degeneracies(const cal_degeneracy_desc* d, double* params, double* nsamp, double* last_step, void* out_g_r, void* out_g_i, void* out_m_r,
+                       void* out_m_i) override {
+    HIP_TRY(hipSetDevice(device));
+    if (!d) return fail(CAL_ERR_INVALID, "fix_degeneracies: null description");
+    CAL_TRY(require_set("fix_degeneracies", false));
+    if ((d->g_r == nullptr) != (d->g_i == nullptr)) return fail(CAL_ERR_INVALID, "fix_degeneracies: give both g_r and g_i, or neither");
+    if (!d->g_r && !has_gains) return fail(CAL_ERR_STATE, "fix_degeneracies: the gains must be set (cal_solver_set_params) or given");
+    if (comm_on() && nranks > 1)
+      return fail(CAL_ERR_STATE, "fix_degeneracies: a communicator or exchange hook of %d ranks is set: the channel sums over the baselines would need an "
+                  "all-reduce per iteration, which is not implemented", nranks);
+    if (d->mode != CAL_DEGEN_CHANNEL && d->mode != CAL_DEGEN_BAND) return fail(CAL_ERR_INVALID, "fix_degeneracies: mode = %d (CAL_DEGEN_CHANNEL or CAL_DEGEN_BAND)", d->mode);
+    if (d->iters < 1) return fail(CAL_ERR_INVALID, "fix_degeneracies: iters = %d (at least 1)", d->iters);
+    if (!d->ref_r || !d->ref_i) return fail(CAL_ERR_INVALID, "fix_degeneracies: null reference planes");
+    if (!d->antpos) return fail(CAL_ERR_INVALID, "fix_degeneracies: null antenna positions");
+    if ((d->gref_r == nullptr) != (d->gref_i == nullptr)) return fail(CAL_ERR_INVALID, "fix_degeneracies: give both gref_r and gref_i, or neither");
+    if ((out_g_r == nullptr) != (out_g_i == nullptr) || (out_m_r == nullptr) != (out_m_i == nullptr))
+      return fail(CAL_ERR_INVALID, "fix_degeneracies: the outputs come in (re, im) pairs");
+    const bool band = d->mode == CAL_DEGEN_BAND;
+    if (band && !d->freqs) return fail(CAL_ERR_INVALID, "fix_degeneracies: CAL_DEGEN_BAND needs freqs");
+    const int nsl = tb_on() ? tb_T : nslices, na = nants / nsl;  // joint time-basis layout: antenna row t na + a is slice t, antenna a
+    for (int k = 0; k < 2 * na; ++k)
+      if (!std::isfinite(d->antpos[k])) return fail(CAL_ERR_INVALID, "fix_degeneracies: antenna position %d is not finite", k / 2);
+    // ---- the plan: doubles (d_b | antpos | ratio | maxd) and ints (row lists | first segments | segments)
+    std::vector<double> geo(2 * (size_t)nbls + 2 * (size_t)na + fpad + nsl, 0.0);
+    double* h_d = geo.data();
+    double* h_pos = h_d + 2 * (size_t)nbls;
+    double* h_ratio = h_pos + 2 * (size_t)na;
+    double* h_maxd = h_ratio + fpad;
+    std::copy(d->antpos, d->antpos + 2 * (size_t)na, h_pos);
+    for (int f = 0; f < nfreqs; ++f) h_ratio[f] = 1.0;
+    if (band) {
+      double mean = 0.0;
+      for (int f = 0; f < nfreqs; ++f) mean += d->freqs[f];
+      mean /= nfreqs;
+      if (!std::isfinite(mean) || mean == 0.0) return fail(CAL_ERR_INVALID, "fix_degeneracies: the mean of freqs must be finite and not zero");
+      for (int f = 0; f < nfreqs; ++f) h_ratio[f] = d->freqs[f] / mean;
+    }
+    std::vector<int> cnt(nsl + 1, 0);
+    for (int b = 0; b < nbls; ++b) {
+      const int2 a = h_bl_ant[b];
+      const int t = a.x / na;
+      if (a.y / na != t) return fail(CAL_ERR_INVALID, "fix_degeneracies: baseline row %d joins antennas of two slices (%d, %d; %d antennas per slice)", b, a.x, a.y, na);
+      ++cnt[t + 1];
+      const int i = a.x % na, j = a.y % na;
+      const double de = h_pos[2 * i] - h_pos[2 * j], dn = h_pos[2 * i + 1] - h_pos[2 * j + 1];
+      h_d[2 * (size_t)b] = de;
+      h_d[2 * (size_t)b + 1] = dn;
+      h_maxd[t] = std::max(h_maxd[t], std::sqrt(de * de + dn * dn));
+    }
+    for (int t = 0; t < nsl; ++t) cnt[t + 1] += cnt[t];
+    int nseg = 0;
+    for (int t = 0; t < nsl; ++t) nseg += (cnt[t + 1] - cnt[t] + kDgSeg - 1) / kDgSeg;
+    std::vector<int> idx((size_t)nbls + nsl + 1 + 4 * (size_t)nseg);
+    int* h_ent = idx.data();
+    int* h_segptr = h_ent + nbls;
+    DgSeg* h_seg = reinterpret_cast<DgSeg*>(h_segptr + nsl + 1);
+    {
+      std::vector<int> fill(cnt.begin(), cnt.end() - 1);
+      for (int b = 0; b < nbls; ++b) h_ent[fill[h_bl_ant[b].x / na]++] = b;
+      int k = 0;
+      for (int t = 0; t < nsl; ++t) {
+        h_segptr[t] = k;
+        for (int e = cnt[t]; e < cnt[t + 1]; e += kDgSeg) h_seg[k++] = DgSeg{t, e, std::min(e + kDgSeg, cnt[t + 1]), 0};
+      }
+      h_segptr[nsl] = k;
+    }
+    auto put = [&](DevBuf& b, const void* src, size_t bytes) -> int {
+      CAL_TRY(b.reserve(bytes, false));
+      HIP_TRY(copy_sync(b.p, src, bytes, hipMemcpyHostToDevice));
+      return CAL_OK;
+    };
+    CAL_TRY(put(dg_geo, geo.data(), geo.size() * sizeof(double)));
+    CAL_TRY(put(dg_idx, idx.data(), idx.size() * sizeof(int)));
+    const size_t plane = (size_t)nbls * fpad, splane = (size_t)nsl * fpad;
+    const size_t st_count = kDgPlanes * splane + 2 * (size_t)nsl;
+    CAL_TRY(dg_z.reserve(2 * plane * sizeof(T)));
+    CAL_TRY(dg_part.reserve((size_t)kDgFirstSums * nseg * fpad * sizeof(double), false));
+    CAL_TRY(dg_st.reserve(st_count * sizeof(double), false));
+    T* z_r = dg_z.as<T>();
+    T* z_i = z_r + plane;
+    CAL_TRY(upload_rows(d->ref_r, z_r, nbls, 1, 0));
+    CAL_TRY(upload_rows(d->ref_i, z_i, nbls, 1, 0));
+    const T* w = wgts.as<T>();
+    if (d->ref_w) {
+      CAL_TRY(dg_w.reserve(plane * sizeof(T)));
+      CAL_TRY(upload_rows(d->ref_w, dg_w.as<T>(), nbls, 1, 0));
+      w = dg_w.as<T>();
+    }
+    const size_t gbytes = (size_t)nants * fpad * sizeof(T2);
+    const T2* g = gains.as<T2>();
+    if (d->g_r) {
+      CAL_TRY(fq_gains.reserve(gbytes));
+      CAL_TRY(upload_rows(d->g_r, fq_gains.as<T>(), nants, 2, 0));
+      CAL_TRY(upload_rows(d->g_i, fq_gains.as<T>(), nants, 2, 1));
+      g = fq_gains.as<T2>();
+    }
+    if (d->gref_r) {
+      CAL_TRY(dg_gref.reserve(gbytes));
+      CAL_TRY(upload_rows(d->gref_r, dg_gref.as<T>(), nants, 2, 0));
+      CAL_TRY(upload_rows(d->gref_i, dg_gref.as<T>(), nants, 2, 1));
+    }
+    if (out_g_r) CAL_TRY(dg_gout.reserve(gbytes));
+    const double2* dv = dg_geo.as<double2>();
+    const double2* pos = dv + nbls;
+    const double* ratio = dg_geo.as<double>() + 2 * (size_t)nbls + 2 * (size_t)na;
+    const double* maxd = ratio + fpad;
+    const int* ent = dg_idx.as<int>();
+    const int* segptr = ent + nbls;
+    const DgSeg* segs = reinterpret_cast<const DgSeg*>(segptr + nsl + 1);
+    double* st = dg_st.as<double>();
+    double* part = dg_part.as<double>();
+    T *m_r = nullptr, *m_i = nullptr;
+    hipError_t memset_err = hipSuccess;
+    CAL_TRY(model_pass(2, [&](T* model_r, T* model_i, T*) {
+      m_r = model_r, m_i = model_i;
+      memset_err = hipMemsetAsync(st, 0, st_count * sizeof(double), stream);
+      if (memset_err != hipSuccess) return;
+      launch_rows(degen_rows_kernel<T>, 0, model_r, model_i, z_r, z_i, w, bl_ant.as<int2>(), nbls, nfreqs, fpad);
+      const dim3 sum_grid(nseg, (nfreqs + 255) / 256), solve_grid((nfreqs + 63) / 64, nsl);
+      for (int it = 0; it <= d->iters; ++it) {  // iters steps, then the amplitude at the last Phi
+        const int first = it == 0, last = it == d->iters;
+        if (first)
+          hipLaunchKernelGGL((degen_sum_kernel<T, true>), sum_grid, dim3(256), 0, stream, z_r, z_i, model_r, model_i, w, ent, segs, dv, st, nsl, nfreqs, fpad,
+                             nseg, part);
+        else
+          hipLaunchKernelGGL((degen_sum_kernel<T, false>), sum_grid, dim3(256), 0, stream, z_r, z_i, model_r, model_i, w, ent, segs, dv, st, nsl, nfreqs, fpad,
+                             nseg, part);
+        hipLaunchKernelGGL(degen_solve_kernel, solve_grid, dim3(64, kDgParts), 0, stream, part, segptr, ratio, maxd, band ? 1 : 0, 0, first, last, nsl, nfreqs, fpad, nseg, st);
+        if (band)
+          hipLaunchKernelGGL(degen_solve_kernel, dim3(nsl), dim3(256), 0, stream, part, segptr, ratio, maxd, 1, 1, first, last, nsl, nfreqs, fpad, nseg, st);
+      }
+      if (d->gref_r)
+        hipLaunchKernelGGL(degen_phase_kernel<T>, solve_grid, dim3(64), 0, stream, g, dg_gref.as<T2>(), w, ant_ptr.as<int>(), ant_ent.as<int2>(), pos, nsl, na,
+                           nfreqs, fpad, st);
+      if (out_g_r)
+        hipLaunchKernelGGL(degen_apply_gains_kernel<T>, dim3(grid_for((long long)nants * fpad)), dim3(256), 0, stream, g, pos, st, nsl, na, nants, nfreqs, fpad,
+                           dg_gout.as<T2>());
+      if (out_m_r) launch_rows(degen_apply_rows_kernel<T>, 0, model_r, model_i, bl_ant.as<int2>(), dv, st, nsl, na, nbls, nfreqs, fpad);
+    }));
+    HIP_TRY(memset_err);
+    std::vector<double> h_st(kDgPlanes * splane);
+    HIP_TRY(copy_sync(h_st.data(), st, h_st.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int t = 0; t < nsl; ++t)
+      for (int f = 0; f < nfreqs; ++f) {
+        const size_t sf = (size_t)t * fpad + f, o = (size_t)t * nfreqs + f;
+        if (params) {
+          params[4 * o + 0] = h_st[DG_ETA * splane + sf];
+          params[4 * o + 1] = h_st[DG_PSI * splane + sf];
+          params[4 * o + 2] = h_st[DG_PE * splane + sf];
+          params[4 * o + 3] = h_st[DG_PN * splane + sf];
+        }
+        if (nsamp) nsamp[o] = h_st[DG_CNT * splane + sf];
+        if (last_step) last_step[o] = h_st[DG_STEP * splane + sf];
+      }
+    if (out_g_r) {
+      CAL_TRY(download_rows(out_g_r, dg_gout.as<T>(), nants, 2, 0));
+      CAL_TRY(download_rows(out_g_i, dg_gout.as<T>(), nants, 2, 1));
+    }
+    if (out_m_r) {
+      CAL_TRY(download_rows(out_m_r, m_r, nbls, 1, 0));
+      CAL_TRY(download_rows(out_m_i, m_i, nbls, 1, 0));
+    }
     return CAL_OK;
   }
 
@@ -3242,6 +3418,11 @@ int cal_solver_delay_spectrum(cal_solver* s, const cal_delay_spectrum_desc* desc
   return s->delay_spectrum(desc, g_r, g_i, power_bl, norm_bl, power_bin, count_bin);
 }
 int cal_solver_set_delay_spectrum_scratch(cal_solver* s, int64_t bytes) { NEED(s); return s->set_delay_spectrum_scratch(bytes); }
+int cal_solver_fix_degeneracies(cal_solver* s, const cal_degeneracy_desc* desc, double* params, double* nsamp, double* last_step, void* out_g_r,
+                                void* out_g_i, void* out_m_r, void* out_m_i) {
+  NEED(s);
+  return s->fix_degeneracies(desc, params, nsamp, last_step, out_g_r, out_g_i, out_m_r, out_m_i);
+}
 int cal_solver_robust_weights(cal_solver* s, const cal_robust_desc* desc, double* scale_bl, double* ndown_bl) { NEED(s); return s->robust_weights(desc, scale_bl, ndown_bl); }
 int cal_solver_get_weights(cal_solver* s, void* out, int which) { NEED(s); return s->get_weights(out, which); }
 int cal_solver_init_coeffs(cal_solver* s, const void* sr, const void* si) { NEED(s); return s->init_coeffs(sr, si); }

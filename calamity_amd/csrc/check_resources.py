@@ -17,7 +17,9 @@ shared Gram and Cholesky core of normal_solve.hpp), `gain_time_kron_kernel`, `ga
 (gain_time_solve_kernels.hpp), `fit_error_factor_kernel`, `fit_error_leverage_kernel`, `fit_error_rows_kernel` (fit_error_kernels.hpp), every `gn_*_kernel`
 (gauss_newton_kernels.hpp), every `lbfgs_*_kernel` (lbfgs_kernels.hpp): no scratch, no spilled VGPRs.
 `dspec_rows_kernel`, `dspec_transform_kernel`, `dspec_bin_kernel` (delay_spectrum_kernels.hpp), both dtypes: no scratch, no spilled VGPRs, and
-two waves per SIMD in the transform kernel."""
+two waves per SIMD in the transform kernel.
+`degen_rows_kernel`, `degen_sum_kernel`, `degen_solve_kernel`, `degen_phase_kernel`, `degen_apply_gains_kernel`, `degen_apply_rows_kernel`
+(degeneracy_kernels.hpp), both dtypes: no scratch, no spilled VGPRs."""
 import re
 import sys
 
@@ -73,6 +75,13 @@ for line in sys.stdin:
             if "dspec_transform_kernel" in cur and int(m.group(2)) < 2:
                 bad.append(f"{cur}: occupancy {m.group(2)} waves/SIMD (< 2)")
         elif m and int(m.group(2)) != 0:
+            bad.append(f"{cur}: {m.group(1)} = {m.group(2)}")
+        continue
+    if cur is not None and any(k in cur for k in ("degen_rows_kernel", "degen_sum_kernel", "degen_solve_kernel", "degen_phase_kernel",
+                                             "degen_apply_gains_kernel", "degen_apply_rows_kernel")):
+        # the six of the degeneracy fix keep their sums, and the double-precision sincos its argument reduction, in registers
+        m = re.search(r"remark:\s+(ScratchSize \[bytes/lane\]|VGPRs Spill): (\d+)", line)
+        if m and int(m.group(2)) != 0:
             bad.append(f"{cur}: {m.group(1)} = {m.group(2)}")
         continue
     if cur is None or "fused_dense" not in cur:

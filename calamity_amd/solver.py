@@ -376,6 +376,59 @@ class HipFitSolver:
             out["per_baseline"] = {q: p_bl[i] for i, q in enumerate(names)}
         return out
 
+    def fix_degeneracies(self, ref_r, ref_i, antpos, ref_w=None, mode="channel", iters=6, freqs=None, g_r=None, g_i=None, gref_r=None,
+                         gref_i=None, return_gains=True, return_model=True):
+        """Refer the fitted solution to a reference (sky) model (cal_solver_fix_degeneracies), in solver units.  The fit constrains
+        only ``g_i conj(g_j) m_b``; per slice and channel an amplitude ``eta``, a phase ``psi`` and a tilt ``Phi`` (rad / m, east and
+        north) are free.  ``ref_r``, ``ref_i`` ``[nbls, nfreqs]``: the reference visibilities ``s`` in the solver's row order;
+        ``ref_w``: their weights (``None``: the weights the solver reads now); ``antpos`` ``[nants per slice, 2]``: east, north in
+        metres, ``d_b = r_i - r_j``.  With ``m = A c`` and ``z0 = w conj(m) s`` (only ``w > 0`` counts)::
+
+            Q = sum_b w |m|^2        H = sum_b |z0| d d^T        Phi = 0
+            iters times:  q = sum_b Im(z0 e^{-i Phi.d}) d,   Phi += H^+ q         (a linear array: along H's dominant eigenvector)
+            e^{2 eta} = max(sum_b Re(z0 e^{-i Phi.d}), 0) / Q
+            psi = arg sum_a g_a e^{-i Phi.r_a} conj(gref_a)      over the antennas with an unflagged cross-correlation; 0 without gref
+            model' = m e^{2 eta} e^{i Phi.d}        g' = g e^{-eta} e^{-i (Phi.r + psi)}
+
+        so ``g'_i conj(g'_j) model'`` is what it was.  ``mode="band"``: one amplitude and one sky shift per slice,
+        ``Phi(f) = (freqs[f] / mean(freqs)) Phi_0``.  ``g_r``, ``g_i``: gains for this call only, as in ``fit_quality``.  A channel
+        without samples keeps the identity and reports 0 samples.  Returns ``eta``, ``psi``, ``nsamples``, ``last_step``
+        ``[nslices, nfreqs]`` and ``tilt`` ``[nslices, nfreqs, 2]`` (float64; with a time basis the slices are its times),
+        ``g_r``, ``g_i`` ``[nants, nfreqs]`` and ``model_r``, ``model_i`` ``[nbls, nfreqs]`` in the solver's dtype.  ``last_step``: the
+        last update of ``Phi`` times the longest baseline, in radians: a value that is not tiny tells a tilt outside the basin (about
+        pi / 2 on the longest baseline).  ``return_gains=False`` / ``return_model=False`` leave the transformed arrays out (the model rows
+        are as large as the data).  Sums in double in a fixed order: two calls give the same bits.  Nothing the fit reads changes."""
+        if mode not in _lib.DEGENERACY_MODES:
+            raise ValueError(f"mode must be one of {sorted(_lib.DEGENERACY_MODES)}, got {mode!r}")
+        if int(iters) < 1:
+            raise ValueError(f"iters must be at least 1, got {iters!r}")
+        if (g_r is None) != (g_i is None) or (gref_r is None) != (gref_i is None):
+            raise ValueError("give both parts of g and of gref, or neither")
+        if mode == "band" and freqs is None:
+            raise ValueError("mode='band' needs freqs")
+        nsl = self.gain_time_shape[0] if self.gain_time_shape is not None else self.nslices
+        rs, gs = (self.nbls, self.nfreqs), (self.nants, self.nfreqs)
+        keep = [self._real(ref_r, rs), self._real(ref_i, rs), None if ref_w is None else self._real(ref_w, rs),
+                np.ascontiguousarray(antpos, dtype=np.float64), None if freqs is None else np.ascontiguousarray(freqs, dtype=np.float64)]
+        keep += [None if a is None else self._real(a, gs) for a in (g_r, g_i, gref_r, gref_i)]
+        if keep[3].shape != (self.nants // nsl, 2):
+            raise ValueError(f"antpos must be [{self.nants // nsl}, 2], got shape {keep[3].shape}")
+        if keep[4] is not None and keep[4].shape != (self.nfreqs,):
+            raise ValueError(f"freqs must be [nfreqs = {self.nfreqs}], got shape {keep[4].shape}")
+        d = _lib.DegeneracyDesc(_lib.DEGENERACY_MODES[mode], int(iters), *(None if a is None else a.ctypes.data for a in keep))
+        params = np.empty((nsl, self.nfreqs, 4), dtype=np.float64)
+        nsamp, step = np.empty((nsl, self.nfreqs), dtype=np.float64), np.empty((nsl, self.nfreqs), dtype=np.float64)
+        o_gr, o_gi = (np.empty(gs, dtype=self.dtype), np.empty(gs, dtype=self.dtype)) if return_gains else (None, None)
+        o_mr, o_mi = (np.empty(rs, dtype=self.dtype), np.empty(rs, dtype=self.dtype)) if return_model else (None, None)
+        _lib.check(self._lib.cal_solver_fix_degeneracies(self._h, C.byref(d), _ptr(params), _ptr(nsamp), _ptr(step), _ptr(o_gr), _ptr(o_gi),
+                                                         _ptr(o_mr), _ptr(o_mi)))
+        out = dict(eta=params[..., 0].copy(), psi=params[..., 1].copy(), tilt=params[..., 2:].copy(), nsamples=nsamp, last_step=step)
+        if return_gains:
+            out.update(g_r=o_gr, g_i=o_gi)
+        if return_model:
+            out.update(model_r=o_mr, model_i=o_mi)
+        return out
+
     def _set_delay_spectrum_scratch(self, nbytes):
         """Scratch bound of ``delay_spectrum`` in bytes (0: the default); the results do not depend on it (tests)."""
         _lib.check(self._lib.cal_solver_set_delay_spectrum_scratch(self._h, int(nbytes)))

@@ -618,6 +618,60 @@ int cal_solver_delay_spectrum(cal_solver* s, const cal_delay_spectrum_desc* desc
 /* The scratch bound of cal_solver_delay_spectrum in bytes (0: the default, 256 MiB; negative: CAL_ERR_INVALID).  The outputs do not
  * depend on it: tests use it to send a small problem through several chunks. */
 int cal_solver_set_delay_spectrum_scratch(cal_solver* s, int64_t bytes);
+/* Fix the gain degeneracies against a reference (sky) model after a fit (the reference computes one band-wide amplitude on the host and
+ * never applies its phase).  A fit constrains only g_i conj(g_j) m_b; per slice t and channel f an amplitude eta, a phase psi and a
+ * phase gradient across the array Phi = (Phi_e, Phi_n) (rad / m; a shift of the sky) are free because the model absorbs them.  Baseline
+ * row b has antennas (i, j); r_a = antpos[a] (east, north, metres), d_b = r_i - r_j from the row's own (ant0, ant1) -- a row stored
+ * conjugated needs nothing special, an autocorrelation row has d_b = 0; m = A c at the solver's coefficients (cal_solver_model), s =
+ * ref_r + i ref_i the reference visibility, w = ref_w or, with NULL, the weight plane the solver reads now; g the given gains or the
+ * solver's full gains, as in cal_solver_fit_quality.  In solver units:
+ *   z0_b = w conj(m_b) s_b               products in the solver's dtype; only samples with w > 0 count, here and below
+ *   Q    = sum_b w |m_b|^2               H = sum_b |z0_b| d_b d_b^T  (2 x 2, formed once)
+ *   Phi  = 0;  iters times:  z_b = z0_b e^{-i Phi.d_b},  q = sum_b Im(z_b) d_b,  Phi += H^+ q
+ *   e^{2 eta} = max(sum_b Re z_b, 0) / Q                      z_b at the last Phi
+ *   H^+ q: the inverse where det H > 1e-12 (tr H / 2)^2; else (a linear array) the step along H's dominant eigenvector alone
+ *   psi  = arg sum_a g_a e^{-i Phi.r_a} conj(gref_a)          over the antennas that have a cross-correlation row with w > 0 at f, in
+ *                                                             ascending antenna order; 0 without gref
+ *   m'_b = m_b e^{2 eta} e^{i Phi.d_b}                        g'_a = g_a e^{-eta} e^{-i (Phi.r_a + psi)}
+ * so that g'_i conj(g'_j) m'_b = g_i conj(g_j) m_b.  The iteration is a chord method whose matrix is the Hessian at a noise-free solution:
+ * it converges from tilts up to about pi / 2 on the longest baseline (1e-15 rad after 4 iterations from 1.5 rad); last_step = |H^+ q| of the
+ * last iteration times the slice's longest |d_b|, in radians, tells a fit that did not settle.
+ * A channel with Q = 0, tr H = 0 or sum Re z <= 0 keeps the identity (eta = psi = Phi = 0, m' = m, g' = g bit for bit) and reports 0 samples.
+ * CAL_DEGEN_CHANNEL: every channel on its own.  CAL_DEGEN_BAND: one amplitude and one sky shift per slice, Phi(f) = (nu_f / nu_ref) Phi_0
+ * with nu_ref the mean of freqs: q_0 = sum_f (nu_f / nu_ref) q(f), H_0 = sum_f (nu_f / nu_ref)^2 H(f), e^{2 eta} = sum_f sum_b Re z_b /
+ * sum_f Q(f), over the channels with Q(f) > 0 and tr H(f) > 0 in ascending order (the others keep the identity); psi stays per channel.
+ * Arithmetic: every sum over baselines, antennas and channels is taken in double in an order the problem alone decides -- a slice's rows in
+ * ascending order, cut into segments of 128 rows, the segments' sums added in eight runs of neighbours, each in ascending order, and the
+ * runs in ascending order; no float atomics -- so two calls give the
+ * same bits and a slice of a batch the bits of the same slice alone.  sincos, the 2 x 2 solve, eta and the factors applied are in double;
+ * m' and g' are rounded once to the solver's dtype.
+ * Slices: t runs over nslices or, in the joint time-basis layout, over the ntimes of cal_solver_set_gain_time_basis (antenna row t Na + a is
+ * slice t, antenna a); antpos holds one slice's antennas.  Works for every layout and kernel path, fitting groups of several baselines,
+ * bl_alias and attached gain bases (g' is an output and need not lie in the basis).  Nothing the fit reads changes (gains, g0, y,
+ * coefficients, moments, t, weights, loop state): a run continued after the call is bit-identical to one without it.
+ * Device memory (counted by cal_solver_memory_bytes, kept until cal_solver_set_problem): two planes [nbls][fpad] of the solver's dtype
+ * (the reference, overwritten by z0), a third when ref_w is given, 8 ceil(rows / 128) fpad doubles of partial sums, g' and gref
+ * [nants][fpad] complex, and per-channel state of 14 nslices fpad doubles; m itself stays in the model planes of cal_solver_model and m'
+ * overwrites it there.
+ *   CAL_ERR_STATE: problem, data or coefficients not set, gains neither set nor given; a communicator or exchange hook of more than one
+ *   rank (the channel sums would need an all-reduce per iteration, which is not implemented).  CAL_ERR_INVALID: a null description, an
+ *   unknown mode, iters < 1, null ref_r / ref_i / antpos, CAL_DEGEN_BAND without freqs (or with a mean that is zero or not finite), a
+ *   position that is not finite, half a (re, im) pair, a row that joins antennas of two slices. */
+enum { CAL_DEGEN_CHANNEL = 0, CAL_DEGEN_BAND = 1 };
+typedef struct cal_degeneracy_desc {
+  int mode;                     /* CAL_DEGEN_CHANNEL | CAL_DEGEN_BAND */
+  int32_t iters;                /* >= 1 */
+  const void *ref_r, *ref_i;    /* [nbls][nfreqs], solver dtype, the solver's row order */
+  const void* ref_w;            /* same shape, or NULL: the solver's weights */
+  const double* antpos;         /* [nants_per_slice][2] east, north in metres */
+  const double* freqs;          /* [nfreqs], needed for CAL_DEGEN_BAND */
+  const void *g_r, *g_i;        /* [nants][nfreqs] or both NULL (as cal_solver_fit_quality) */
+  const void *gref_r, *gref_i;  /* [nants][nfreqs] or both NULL: psi = 0 */
+} cal_degeneracy_desc;
+int cal_solver_fix_degeneracies(cal_solver* s, const cal_degeneracy_desc* desc,
+                                double* params /* [nslices][nfreqs][4]: eta, psi, Phi_e, Phi_n */,
+                                double* nsamp /* [nslices][nfreqs] samples with w > 0 */, double* last_step /* [nslices][nfreqs] */,
+                                void* out_g_r, void* out_g_i /* [nants][nfreqs] */, void* out_m_r, void* out_m_i /* [nbls][nfreqs] */);
 /* The coefficients of a frequency gain basis in closed form (no counterpart in the reference): the damped StefCal sweeps of
  * cal_solver_solve_gains projected on the basis g = g0 + B y of cal_solver_set_gain_basis.  With the other antennas held fixed the
  * chi-square is quadratic in one antenna's y.  num, den are exactly cal_solver_solve_gains': the model pass, then P, Q, then the
