@@ -57,8 +57,9 @@ def solver_of(p, params, dtype, layout="shared"):
     return s
 
 
-def inject(m, ant0, ant1, antpos, freqs, seed, band=False, flag_channel=4, flag_antenna=2):
-    """The reference planes, their weights and reference gains' offsets for the model rows ``m`` of one slice."""
+def inject(m, ant0, ant1, antpos, freqs, seed, band=False, flag_channel=4, flag_antenna=2, direction=None):
+    """The reference planes, their weights and reference gains' offsets for the model rows ``m`` of one slice.  ``direction``: the unit
+    vector of a line array that does not lie along east (the tilt is injected along it: across it nothing is observable)."""
     rng = np.random.default_rng(seed)
     nbls, nf = m.shape
     d = antpos[ant0] - antpos[ant1]
@@ -71,6 +72,8 @@ def inject(m, ant0, ant1, antpos, freqs, seed, band=False, flag_channel=4, flag_
         eta = 0.2 * rng.normal(size=nf)
     if line:
         phi[:, 1] = 0.0
+    if direction is not None:
+        phi = (phi @ np.asarray(direction))[:, None] * np.asarray(direction)[None, :]
     phi = phi / np.abs(d @ phi.T).max()
     s = m * np.exp(2 * eta)[None, :] * np.exp(1j * (d @ phi.T))
     s = s + 0.02 * np.sqrt(np.mean(np.abs(m) ** 2)) * (rng.normal(size=m.shape) + 1j * rng.normal(size=m.shape))
@@ -119,12 +122,12 @@ def cast_c(r, i, dtype):
     return np.asarray(r).astype(dtype).astype(np.float64) + 1j * np.asarray(i).astype(dtype).astype(np.float64)
 
 
-def run_case(p, params, freqs, antpos, dtype, mode, seed, layout="shared", label=""):
+def run_case(p, params, freqs, antpos, dtype, mode, seed, layout="shared", label="", direction=None):
     s = solver_of(p, params, dtype, layout)
     m_r, m_i = s.model()
     m = m_r.astype(np.float64) + 1j * m_i.astype(np.float64)
     g = cast_c(params["g_r"], params["g_i"], dtype)
-    ref_s, ref_w = inject(m, p.bl_ant0, p.bl_ant1, antpos, freqs, seed, band=mode == "band")
+    ref_s, ref_w = inject(m, p.bl_ant0, p.bl_ant1, antpos, freqs, seed, band=mode == "band", direction=direction)
     rng = np.random.default_rng(seed + 1)
     gref = g * np.exp(1j * rng.uniform(-1, 1, size=NF))[None, :] * (1 + 0.05 * rng.normal(size=g.shape))
     args = dict(ref_w=ref_w, mode=mode, iters=6, freqs=freqs, g_r=params["g_r"], g_i=params["g_i"], gref_r=gref.real, gref_i=gref.imag)

@@ -12,20 +12,25 @@ all padding (fp64: 6, 7).  nfreqs = 260: the row padding is a function of nfreqs
 fp32 row needs a second trip of the wave with 32 live lanes (fp64: a second trip of 64), and the antenna kernels need a second
 (fp64: a third) channel block whose channels past 260 are not stored.
 
-Two slices in one solver; the calls that take a mask select slice 0, and slice 1 keeps its bits."""
+Two slices in one solver; the calls that take a mask select slice 0, and slice 1 keeps its bits.  cal_solver_fix_degeneracies and
+cal_solver_delay_spectrum take no mask: every slice is compared with the restatement of its own rows."""
 import copy
 import functools
 
 import numpy as np
 import pytest
 
+import degeneracy_ref as R
 import test_gpu_coeff_solve as CS
+import test_gpu_degeneracy as DG
+import test_gpu_delay_spectrum as DS
 import test_gpu_fit_quality as FQ
 import test_gpu_gain_solve as GS
 import test_gpu_gauss_newton as GN
 import test_gpu_robust_weights as RW
-from calamity_amd import batched, synthetic
+from calamity_amd import batched, modeling, synthetic
 from calamity_amd.problem import FitProblem
+from delay_spectrum_ref import NAMES, bin_rows, bound_ratio
 from gauss_newton_ref import Ref
 
 pytestmark = pytest.mark.gpu
@@ -202,4 +207,103 @@ def test_gauss_newton_step(nfreqs, dtype):
     for k in range(4):
         part = slice(na, None) if k < 2 else slice(nc, None)
         np.testing.assert_array_equal(got[k][part], before[k][part])
+    s.close()
+
+
+def fix_degeneracies_cases(s, nfreqs, dtype, label):
+    """Both modes on the open solver ``s`` of ``batch(nfreqs)``: every slice against the restatement of its own rows."""
+    full, parts, params, _ = batch(nfreqs)
+    p0, nb = parts[0], parts[0].nbls
+    assert not np.any(((p0.bl_ant0 == NA - 1) | (p0.bl_ant1 == NA - 1)) & (p0.bl_ant0 != p0.bl_ant1))  # antenna 6: its autocorrelation only
+    antpos, freqs = R.hex_array(NA), 150e6 + 400e3 * np.arange(nfreqs)
+    m_r, m_i = s.model()
+    m = m_r.astype(np.float64) + 1j * m_i.astype(np.float64)
+    g = DG.cast_c(params["g_r"], params["g_i"], dtype)
+    rng = np.random.default_rng(60)
+    gref = g * np.exp(1j * rng.uniform(-1, 1, size=nfreqs))[None, :] * (1 + 0.05 * rng.normal(size=g.shape))
+    gref[NA - 1 :: NA] = -g[NA - 1 :: NA]  # antenna 6 of every slice: counted into psi it would turn the sum by far more than the tolerance
+    gref_c = DG.cast_c(gref.real, gref.imag, dtype)
+    for mode in ("channel", "band"):
+        refs = [DG.inject(m[t * nb : (t + 1) * nb], p0.bl_ant0, p0.bl_ant1, antpos, freqs, seed=50 + t, band=mode == "band", flag_antenna=None if t else 2)
+                for t in range(T)]
+        ref_s, ref_w = np.concatenate([r[0] for r in refs]), np.concatenate([r[1] for r in refs])
+        out = s.fix_degeneracies(ref_s.real, ref_s.imag, antpos, ref_w=ref_w, mode=mode, iters=6, freqs=freqs, gref_r=gref.real, gref_i=gref.imag)
+        assert out["eta"].shape == (T, nfreqs)
+        for t in range(T):
+            a, rows = slice(t * NA, (t + 1) * NA), slice(t * nb, (t + 1) * nb)
+            ref = R.fix_degeneracies(m[rows], DG.cast_c(refs[t][0].real, refs[t][0].imag, dtype), refs[t][1].astype(dtype).astype(np.float64), g[a],
+                                     p0.bl_ant0, p0.bl_ant1, antpos, iters=6, mode=mode, freqs=freqs, gref=gref_c[a], dtype=dtype)
+            DG.check_slice(out, t, ref, dtype, f"{label} {mode}", NA, rows)
+            # antenna 6 is turned like every other antenna, from the device's own eta, tilt and psi
+            k = t * NA + NA - 1
+            want = g[k] * np.exp(-out["eta"][t]) * np.exp(-1j * (out["tilt"][t] @ antpos[NA - 1] + out["psi"][t]))
+            got = out["g_r"][k].astype(np.float64) + 1j * out["g_i"][k].astype(np.float64)
+            assert DG.err(got, want) <= DG.TOL[np.dtype(dtype)], (label, mode, t)
+            assert np.count_nonzero(out["nsamples"][t]) == nfreqs - 1 and out["nsamples"][t, 4] == 0  # channel 4 is flagged (inject)
+        DG.check_invariance(out, g, m, full.bl_ant0, full.bl_ant1, dtype, f"{label} {mode}")
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("nfreqs", NFREQS)
+def test_fix_degeneracies(nfreqs, dtype):
+    """nfreqs = 260 (fpad 384): two channel blocks of degen_sum_kernel, the second with 4 live channels; five of degen_solve_kernel stage 0
+    and of degen_phase_kernel, the last with 4; two trips of the `f += 256` loop of the band stage; two (fp32) or three (fp64) trips of a
+    wave along a row in degen_rows_kernel and degen_apply_rows_kernel.  nfreqs = 5 (fpad 8): the last 16-byte vector of a row is part or
+    all padding, and the flagged channel 4 is the last one before the padding.  Antenna 6 has only its autocorrelation: it stays out of psi
+    (its reference gain is -g: counted, it would turn psi by up to 0.23 rad at 5 channels and 0.32 rad at 260) and is turned by eta, the tilt and psi like the others."""
+    full, _, params, _ = batch(nfreqs)
+    assert DG.fpad_of(nfreqs) == {5: 8, 260: 384}[nfreqs]
+    s = solver_of(full, params, dtype)
+    fix_degeneracies_cases(s, nfreqs, dtype, f"fix_degeneracies {nfreqs} {np.dtype(dtype).name}")
+    s.close()
+
+
+def test_fix_degeneracies_stream_layout():
+    """The same at 260 channels in fp32 in the STREAM layout, where the replicated problem's rows share tiles through bl_alias."""
+    from calamity_amd.solver import HipFitSolver
+
+    full, _, params, _ = batch(260)
+    assert full.bl_alias is not None and DG.fpad_of(260) == 384
+    s = HipFitSolver(dtype=np.float32)
+    s.set_problem(full, layout="stream")
+    s.set_data(full.data_r, full.data_i, full.wgts)
+    s.set_params(*[params[k] for k in KEYS])
+    fix_degeneracies_cases(s, 260, np.float32, "fix_degeneracies 260 float32 stream")
+    s.close()
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("nfreqs", NFREQS)
+def test_delay_spectrum(nfreqs, dtype):
+    """All nfreqs delays.  nfreqs = 5: fpad = 8 but the masked planes' pitch is 32, so dspec_rows_kernel zeroes the channels in
+    [fpad, xpitch) through its branch without loads, and the transform runs one staged step that is mostly padding.  nfreqs = 260:
+    fpad = 384, a second trip of the wave along a row (fp32: 32 live lanes), twelve staged steps of the operator, and five column
+    blocks of which the last holds 4 delays."""
+    full, parts, params, _ = batch(nfreqs)
+    p0, nb = parts[0], parts[0].nbls
+    assert DG.fpad_of(nfreqs) == {5: 8, 260: 384}[nfreqs]
+    op, norm_f, _ = modeling.delay_transform(150e6 + 400e3 * np.arange(nfreqs))
+    assert op.shape == (nfreqs, nfreqs) and -(-nfreqs // 64) == {5: 1, 260: 5}[nfreqs] and nfreqs % 64 in (4, 5)
+    local, nbins = DS.bins_of(p0)  # row 3 of a slice is in no bin, bin 3 of a slice holds no row
+    bins = np.concatenate([np.where(local >= 0, local + t * nbins, -1) for t in range(T)]).astype(np.int32)
+    s = solver_of(full, params, dtype)
+    for calibrated in (False, True):
+        label = f"delay_spectrum {nfreqs} {np.dtype(dtype).name} calibrated={calibrated}"
+        out = s.delay_spectrum(op, norm_f, bin_of_bl=bins, nbins=T * nbins, per_baseline=True, calibrated=calibrated)
+        for t in range(T):
+            rows, mine = slice(t * nb, (t + 1) * nb), slice(t * nbins, (t + 1) * nbins)
+            ref = DS.reference(parts[t], sliced(params, t, p0), dtype, op, norm_f, calibrated)
+            worst = {}
+            for k in NAMES:
+                P = out["per_baseline"][k][rows]
+                assert P.shape == (nb, nfreqs) and np.all(np.isfinite(P)), (label, k)
+                worst[k] = bound_ratio(P, ref, k, dtype)
+            print(f"{label} slice {t}: error / bound  " + "  ".join(f"{k} {v:.3f}" for k, v in worst.items()))
+            assert max(worst.values()) <= 1.0, (label, t, worst)
+            np.testing.assert_allclose(out["norm_bl"][rows], ref["norm_bl"], rtol=1e-13, atol=0)
+            np.testing.assert_array_equal(out["count_bin"][mine], ref["count_bin"])
+            assert out["count_bin"][mine].sum() == nb - 1 and out["count_bin"][mine][nbins - 1] == 0
+            own = bin_rows({k: out["per_baseline"][k][rows] for k in NAMES}, out["norm_bl"][rows], local, nbins)
+            for k in NAMES:  # the bins against the sequential double sum of the device's own rows, as in the call's own file
+                assert np.max(np.abs(out[k][mine] - own[k])) <= nb * 2.0 ** -53 * np.max(np.abs(own[k])), (label, t, k)
     s.close()
