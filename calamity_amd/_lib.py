@@ -114,6 +114,14 @@ class DegeneracyDesc(C.Structure):
 DEGENERACY_MODES = {"channel": 0, "band": 1}
 
 
+class ReportPlanDesc(C.Structure):
+    """cal_report_plan_desc (include/calamity_hip.h: cal_debug_report_plan): the call whose host plan is asked for -- a spectrum
+    description with its scratch bound and whether power_bl is wanted, or a degeneracy description with the number of slices
+    (0: the problem's)."""
+    _fields_ = [("spectrum", C.POINTER(DelaySpectrumDesc)), ("degeneracy", C.POINTER(DegeneracyDesc)), ("scratch_bytes", C.c_int64),
+                ("with_power_bl", C.c_int32), ("nslices", C.c_int32)]
+
+
 class CoeffSolveDesc(C.Structure):
     _fields_ = [("niters", C.c_int32), ("reset_coeff_moments", C.c_int32), ("damping", C.c_double), ("ridge", C.c_double), ("slice_mask", C.c_void_p)]
 
@@ -192,6 +200,7 @@ SYMBOLS = {
     "cal_basis_foldable": (C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "cal_debug_plan": (C.c_int, [C.c_int, C.POINTER(ProblemDesc), C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "cal_debug_solve_plan": (C.c_int, [C.c_int, C.POINTER(ProblemDesc), C.c_int64, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "cal_debug_report_plan": (C.c_int, [C.c_int, C.POINTER(ProblemDesc), C.POINTER(ReportPlanDesc), C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "cal_debug_step_shape": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "cal_device_info": (C.c_int, [C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "cal_device_stream_peak": (C.c_int, [C.c_int, C.c_size_t, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -39,6 +39,7 @@
 #include "lbfgs_kernels.hpp"
 #include "solve_plan.hpp"  // (and problem_plan.hpp)
 #include "step_plan.hpp"
+#include "report_plan.hpp"
 #include <cstdlib>
 #include <dlfcn.h>
 #include <type_traits>
@@ -1687,6 +1688,32 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     if (need_gains && !has_gains) return fail(CAL_ERR_STATE, "%s: the gains must be set (cal_solver_set_params)", who);
     return CAL_OK;
   }
+  // the gains a post-fit report reads: the solver's, or the planes given for this call alone ([nants][nfreqs]), uploaded into fq_gains
+  int report_gains(const char* who, const void* g_r, const void* g_i, const T2** g) {
+    if ((g_r == nullptr) != (g_i == nullptr)) return fail(CAL_ERR_INVALID, "%s: give both g_r and g_i, or neither", who);
+    if (!g_r && !has_gains) return fail(CAL_ERR_STATE, "%s: the gains must be set (cal_solver_set_params) or given", who);
+    *g = gains.as<T2>();
+    if (!g_r) return CAL_OK;
+    CAL_TRY(fq_gains.reserve((size_t)nants * fpad * sizeof(T2)));
+    CAL_TRY(upload_rows(g_r, fq_gains.as<T>(), nants, 2, 0));
+    CAL_TRY(upload_rows(g_i, fq_gains.as<T>(), nants, 2, 1));
+    *g = fq_gains.as<T2>();
+    return CAL_OK;
+  }
+  // a call's plan array on the device (the buffers are kept between calls: a fit asks for the same sizes for every slice); an empty
+  // array is copied only where copy_empty says so
+  template <typename X>
+  int put(DevBuf& b, const std::vector<X>& v, bool copy_empty) {
+    const size_t bytes = v.size() * sizeof(X);
+    CAL_TRY(b.reserve(bytes, false));
+    if (bytes || copy_empty) HIP_TRY(copy_sync(b.p, v.data(), bytes, hipMemcpyHostToDevice));
+    return CAL_OK;
+  }
+  // an output the caller may leave out: n doubles to the host, on the stream
+  int give(double* host, const double* dev, size_t n) {
+    if (host) HIP_TRY(hipMemcpyAsync(host, dev, n * sizeof(double), hipMemcpyDeviceToHost, stream));
+    return CAL_OK;
+  }
   // The model pass of model() into model_buf ([planes][nbls][fpad]), then rows(model_r, model_i, q_rows) launches what turns the planes
   // into the call's own rows (q_rows: the third plane, null when two are asked for).  The host mirror of the loop state is put back and
   // pushed again afterwards: the pass clears the slices' stop flags for itself.
@@ -1785,19 +1812,11 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
   int fit_quality(const void* g_r, const void* g_i, double* chisq_ant, double* wsum_ant, double* chisq_bl, double* wsum_bl) override {
     HIP_TRY(hipSetDevice(device));
     CAL_TRY(require_set("fit_quality", false));
-    if ((g_r == nullptr) != (g_i == nullptr)) return fail(CAL_ERR_INVALID, "fit_quality: give both g_r and g_i, or neither");
-    if (!g_r && !has_gains) return fail(CAL_ERR_STATE, "fit_quality: the gains must be set (cal_solver_set_params) or given");
+    const T2* g = nullptr;
+    CAL_TRY(report_gains("fit_quality", g_r, g_i, &g));
     const size_t nant_out = (size_t)nants * nfreqs;
     const size_t out_bytes = (2 * nant_out + 2 * (size_t)nbls) * sizeof(double);
     CAL_TRY(fq_out.reserve(out_bytes));
-    const T2* g = gains.as<T2>();
-    if (g_r) {
-      const size_t gbytes = (size_t)nants * fpad * sizeof(T2);
-      CAL_TRY(fq_gains.reserve(gbytes));
-      CAL_TRY(upload_rows(g_r, fq_gains.as<T>(), nants, 2, 0));
-      CAL_TRY(upload_rows(g_i, fq_gains.as<T>(), nants, 2, 1));
-      g = fq_gains.as<T2>();
-    }
     double* o_ca = fq_out.as<double>();
     double* o_wa = o_ca + nant_out;
     double* o_cb = o_wa + nant_out;
@@ -1809,10 +1828,10 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     }));
     // the antenna planes of every rank's baselines add up to the array's: ONE all-reduce of 2 nants nfreqs doubles
     if (comm_on()) CAL_TRY(all_reduce(o_ca, 2 * nant_out, CAL_XCHG_F64, CAL_XCHG_SUM));
-    if (chisq_ant) HIP_TRY(hipMemcpyAsync(chisq_ant, o_ca, nant_out * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (wsum_ant) HIP_TRY(hipMemcpyAsync(wsum_ant, o_wa, nant_out * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (chisq_bl) HIP_TRY(hipMemcpyAsync(chisq_bl, o_cb, (size_t)nbls * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (wsum_bl) HIP_TRY(hipMemcpyAsync(wsum_bl, o_wb, (size_t)nbls * sizeof(double), hipMemcpyDeviceToHost, stream));
+    CAL_TRY(give(chisq_ant, o_ca, nant_out));
+    CAL_TRY(give(wsum_ant, o_wa, nant_out));
+    CAL_TRY(give(chisq_bl, o_cb, (size_t)nbls));
+    CAL_TRY(give(wsum_bl, o_wb, (size_t)nbls));
     HIP_TRY(hipStreamSynchronize(stream));
     return CAL_OK;
   }
@@ -1825,8 +1844,8 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     HIP_TRY(hipSetDevice(device));
     if (!d) return fail(CAL_ERR_INVALID, "delay_spectrum: null description");
     CAL_TRY(require_set("delay_spectrum", false));
-    if ((g_r == nullptr) != (g_i == nullptr)) return fail(CAL_ERR_INVALID, "delay_spectrum: give both g_r and g_i, or neither");
-    if (!g_r && !has_gains) return fail(CAL_ERR_STATE, "delay_spectrum: the gains must be set (cal_solver_set_params) or given");
+    const T2* g = nullptr;
+    CAL_TRY(report_gains("delay_spectrum", g_r, g_i, &g));
     if (d->ndelays < 1 || d->ndelays > 4096) return fail(CAL_ERR_INVALID, "delay_spectrum: ndelays = %d lies outside [1, 4096]", d->ndelays);
     if ((d->what & 7) == 0 || (d->what & ~7)) return fail(CAL_ERR_INVALID, "delay_spectrum: what = %d: bits 0 (data), 1 (model), 2 (residual), at least one", d->what);
     if (d->calibrated != 0 && d->calibrated != 1) return fail(CAL_ERR_INVALID, "delay_spectrum: calibrated = %d (0 or 1)", d->calibrated);
@@ -1834,79 +1853,27 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     if (d->nbins < 0) return fail(CAL_ERR_INVALID, "delay_spectrum: nbins = %d", d->nbins);
     if ((d->nbins == 0) != (d->bin_of_bl == nullptr)) return fail(CAL_ERR_INVALID, "delay_spectrum: bin_of_bl goes with nbins > 0, and only with it");
     if (d->nbins == 0 && (power_bin || count_bin)) return fail(CAL_ERR_INVALID, "delay_spectrum: binned outputs need nbins > 0");
-    const int nd = d->ndelays, nbins = d->nbins;
-    const int nq = (d->what & 1) + (d->what >> 1 & 1) + (d->what >> 2 & 1);
-    if ((long long)nq * nbins * nd + nbins > (1ll << 31) - 1) return fail(CAL_ERR_INVALID, "delay_spectrum: nbins = %d is too many", nbins);
-    // the sorted row list of every bin (CSR, like ant_ptr / ant_ent)
-    std::vector<int> bin_ptr(nbins + 1, 0), bin_ent;
-    for (int b = 0; b < nbls && nbins; ++b) {
-      const int n = d->bin_of_bl[b];
-      if (n < -1 || n >= nbins) return fail(CAL_ERR_INVALID, "delay_spectrum: bin_of_bl[%d] = %d lies outside [-1, %d)", b, n, nbins);
-      if (n >= 0) ++bin_ptr[n + 1];
-    }
+    const bool with_power = power_bl != nullptr || d->nbins > 0;
+    DelaySpectrumPlan<T> P;  // the bins' rows, the chunks, the operator image (report_plan.hpp)
+    CAL_TRY(plan_delay_spectrum(nbls, nfreqs, fpad, d, ds_bound, with_power, P));
+    const int nd = d->ndelays, nbins = d->nbins, nq = P.nq, xpitch = P.xpitch, ndpad = P.ndpad, crows = P.crows;
+    CAL_TRY(put(ds_op, P.image, false));
+    CAL_TRY(put(ds_normf, P.norm_f, false));
     if (nbins) {
-      for (int n = 0; n < nbins; ++n) bin_ptr[n + 1] += bin_ptr[n];
-      bin_ent.resize(bin_ptr[nbins]);
-      std::vector<int> fill(bin_ptr.begin(), bin_ptr.end() - 1);
-      for (int b = 0; b < nbls; ++b)
-        if (d->bin_of_bl[b] >= 0) bin_ent[fill[d->bin_of_bl[b]]++] = b;
+      CAL_TRY(put(ds_ent, P.bin_ent, false));
+      CAL_TRY(put(ds_ptr, P.chunk_ptr, false));
     }
-    // chunks of rows under the bound
-    const int xpitch = ds_xpitch(fpad), ndpad = ds_ndpad(nd);
-    const bool with_power = power_bl != nullptr || nbins > 0;
-    const size_t row_bytes = (size_t)nq * 2 * xpitch * sizeof(T) + (with_power ? (size_t)nq * nd * sizeof(double) : 0);
-    long long crows = std::max<long long>(1, ds_bound / (long long)row_bytes);
-    if (crows > kDsRows) crows -= crows % kDsRows;
-    crows = std::min<long long>(crows, nbls);
-    const int nchunks = (int)((nbls + crows - 1) / crows);
-    std::vector<int> chunk_ptr((size_t)nchunks * nbins * 2);  // per chunk and bin: its piece of the bin's list
-    for (int c = 0; c < nchunks && nbins; ++c) {
-      const long long b0 = c * crows, b1 = std::min<long long>(nbls, b0 + crows);
-      for (int n = 0; n < nbins; ++n) {
-        const int* e0 = bin_ent.data() + bin_ptr[n];
-        const int* e1 = bin_ent.data() + bin_ptr[n + 1];
-        chunk_ptr[((size_t)c * nbins + n) * 2] = (int)(std::lower_bound(e0, e1, (int)b0) - bin_ent.data());
-        chunk_ptr[((size_t)c * nbins + n) * 2 + 1] = (int)(std::lower_bound(e0, e1, (int)b1) - bin_ent.data());
-      }
-    }
-    // the operator image, built once per call: [re, im][xpitch][ndpad] T, zero beyond nfreqs and ndelays
-    std::vector<T> image((size_t)2 * xpitch * ndpad, (T)0);
-    for (int part = 0; part < 2; ++part) {
-      const T* src = static_cast<const T*>(part ? d->op_i : d->op_r);
-      for (int f = 0; f < nfreqs; ++f) std::copy(src + (size_t)f * nd, src + (size_t)(f + 1) * nd, image.begin() + ((size_t)part * xpitch + f) * ndpad);
-    }
-    std::vector<double> h_norm_f((size_t)xpitch, 0.0);
-    std::copy(d->norm_f, d->norm_f + nfreqs, h_norm_f.begin());
-    // (the buffers are kept between calls: a fit asks for the same sizes for every slice)
-    auto put = [&](DevBuf& b, const void* src, size_t bytes) -> int {
-      CAL_TRY(b.reserve(bytes, false));
-      if (bytes) HIP_TRY(copy_sync(b.p, src, bytes, hipMemcpyHostToDevice));
-      return CAL_OK;
-    };
-    CAL_TRY(put(ds_op, image.data(), image.size() * sizeof(T)));
-    CAL_TRY(put(ds_normf, h_norm_f.data(), h_norm_f.size() * sizeof(double)));
-    if (nbins) {
-      CAL_TRY(put(ds_ent, bin_ent.data(), bin_ent.size() * sizeof(int)));
-      CAL_TRY(put(ds_ptr, chunk_ptr.data(), chunk_ptr.size() * sizeof(int)));
-    }
-    const size_t nbin_out = (size_t)nq * nbins * nd + nbins;  // power_bin | count_bin: the exchange payload
-    CAL_TRY(ds_out.reserve(((size_t)nbls + nbin_out) * sizeof(double)));
-    CAL_TRY(ds_x.reserve((size_t)nq * 2 * crows * xpitch * sizeof(T), false));
-    if (with_power) CAL_TRY(ds_pow.reserve((size_t)nq * crows * nd * sizeof(double), false));
-    const T2* g = gains.as<T2>();
-    if (g_r) {
-      CAL_TRY(fq_gains.reserve((size_t)nants * fpad * sizeof(T2)));
-      CAL_TRY(upload_rows(g_r, fq_gains.as<T>(), nants, 2, 0));
-      CAL_TRY(upload_rows(g_i, fq_gains.as<T>(), nants, 2, 1));
-      g = fq_gains.as<T2>();
-    }
+    CAL_TRY(ds_out.reserve(P.n_out * sizeof(double)));
+    CAL_TRY(ds_x.reserve(P.n_x * sizeof(T), false));
+    if (with_power) CAL_TRY(ds_pow.reserve(P.n_pow * sizeof(double), false));
+    const size_t nbin_out = P.n_out - nbls;  // power_bin | count_bin: the exchange payload
     double* o_norm = ds_out.as<double>();
     double* o_pbin = o_norm + nbls;
     double* o_cbin = o_pbin + (size_t)nq * nbins * nd;
     hipError_t copy_err = hipSuccess;
     CAL_TRY(model_pass(2, [&](T* model_r, T* model_i, T*) {
-      for (int c = 0; c < nchunks; ++c) {
-        const long long b0 = c * crows;
+      for (int c = 0; c < P.nchunks; ++c) {
+        const long long b0 = (long long)c * crows;
         const int nr = (int)std::min<long long>(crows, nbls - b0);
         const size_t off = (size_t)b0 * fpad;
         hipLaunchKernelGGL(dspec_rows_kernel<T>, dim3((nr + 3) / 4), dim3(256), 0, stream, model_r + off, model_i + off, data_r.as<T>() + off,
@@ -1926,9 +1893,9 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     HIP_TRY(copy_err);
     // the bins of every rank's rows add up to the array's: ONE all-reduce of nwhat nbins ndelays + nbins doubles
     if (nbins && comm_on()) CAL_TRY(all_reduce(o_pbin, nbin_out, CAL_XCHG_F64, CAL_XCHG_SUM));
-    if (norm_bl) HIP_TRY(hipMemcpyAsync(norm_bl, o_norm, (size_t)nbls * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (power_bin) HIP_TRY(hipMemcpyAsync(power_bin, o_pbin, (size_t)nq * nbins * nd * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (count_bin) HIP_TRY(hipMemcpyAsync(count_bin, o_cbin, (size_t)nbins * sizeof(double), hipMemcpyDeviceToHost, stream));
+    CAL_TRY(give(norm_bl, o_norm, (size_t)nbls));
+    CAL_TRY(give(power_bin, o_pbin, (size_t)nq * nbins * nd));
+    CAL_TRY(give(count_bin, o_cbin, (size_t)nbins));
     HIP_TRY(hipStreamSynchronize(stream));
     return CAL_OK;
   }
@@ -1947,8 +1914,8 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     HIP_TRY(hipSetDevice(device));
     if (!d) return fail(CAL_ERR_INVALID, "fix_degeneracies: null description");
     CAL_TRY(require_set("fix_degeneracies", false));
-    if ((d->g_r == nullptr) != (d->g_i == nullptr)) return fail(CAL_ERR_INVALID, "fix_degeneracies: give both g_r and g_i, or neither");
-    if (!d->g_r && !has_gains) return fail(CAL_ERR_STATE, "fix_degeneracies: the gains must be set (cal_solver_set_params) or given");
+    const T2* g = nullptr;
+    CAL_TRY(report_gains("fix_degeneracies", d->g_r, d->g_i, &g));
     if (comm_on() && nranks > 1)
       return fail(CAL_ERR_STATE, "fix_degeneracies: a communicator or exchange hook of %d ranks is set: the channel sums over the baselines would need an "
                   "all-reduce per iteration, which is not implemented", nranks);
@@ -1962,59 +1929,11 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     const bool band = d->mode == CAL_DEGEN_BAND;
     if (band && !d->freqs) return fail(CAL_ERR_INVALID, "fix_degeneracies: CAL_DEGEN_BAND needs freqs");
     const int nsl = tb_on() ? tb_T : nslices, na = nants / nsl;  // joint time-basis layout: antenna row t na + a is slice t, antenna a
-    for (int k = 0; k < 2 * na; ++k)
-      if (!std::isfinite(d->antpos[k])) return fail(CAL_ERR_INVALID, "fix_degeneracies: antenna position %d is not finite", k / 2);
-    // ---- the plan: doubles (d_b | antpos | ratio | maxd) and ints (row lists | first segments | segments)
-    std::vector<double> geo(2 * (size_t)nbls + 2 * (size_t)na + fpad + nsl, 0.0);
-    double* h_d = geo.data();
-    double* h_pos = h_d + 2 * (size_t)nbls;
-    double* h_ratio = h_pos + 2 * (size_t)na;
-    double* h_maxd = h_ratio + fpad;
-    std::copy(d->antpos, d->antpos + 2 * (size_t)na, h_pos);
-    for (int f = 0; f < nfreqs; ++f) h_ratio[f] = 1.0;
-    if (band) {
-      double mean = 0.0;
-      for (int f = 0; f < nfreqs; ++f) mean += d->freqs[f];
-      mean /= nfreqs;
-      if (!std::isfinite(mean) || mean == 0.0) return fail(CAL_ERR_INVALID, "fix_degeneracies: the mean of freqs must be finite and not zero");
-      for (int f = 0; f < nfreqs; ++f) h_ratio[f] = d->freqs[f] / mean;
-    }
-    std::vector<int> cnt(nsl + 1, 0);
-    for (int b = 0; b < nbls; ++b) {
-      const int2 a = h_bl_ant[b];
-      const int t = a.x / na;
-      if (a.y / na != t) return fail(CAL_ERR_INVALID, "fix_degeneracies: baseline row %d joins antennas of two slices (%d, %d; %d antennas per slice)", b, a.x, a.y, na);
-      ++cnt[t + 1];
-      const int i = a.x % na, j = a.y % na;
-      const double de = h_pos[2 * i] - h_pos[2 * j], dn = h_pos[2 * i + 1] - h_pos[2 * j + 1];
-      h_d[2 * (size_t)b] = de;
-      h_d[2 * (size_t)b + 1] = dn;
-      h_maxd[t] = std::max(h_maxd[t], std::sqrt(de * de + dn * dn));
-    }
-    for (int t = 0; t < nsl; ++t) cnt[t + 1] += cnt[t];
-    int nseg = 0;
-    for (int t = 0; t < nsl; ++t) nseg += (cnt[t + 1] - cnt[t] + kDgSeg - 1) / kDgSeg;
-    std::vector<int> idx((size_t)nbls + nsl + 1 + 4 * (size_t)nseg);
-    int* h_ent = idx.data();
-    int* h_segptr = h_ent + nbls;
-    DgSeg* h_seg = reinterpret_cast<DgSeg*>(h_segptr + nsl + 1);
-    {
-      std::vector<int> fill(cnt.begin(), cnt.end() - 1);
-      for (int b = 0; b < nbls; ++b) h_ent[fill[h_bl_ant[b].x / na]++] = b;
-      int k = 0;
-      for (int t = 0; t < nsl; ++t) {
-        h_segptr[t] = k;
-        for (int e = cnt[t]; e < cnt[t + 1]; e += kDgSeg) h_seg[k++] = DgSeg{t, e, std::min(e + kDgSeg, cnt[t + 1]), 0};
-      }
-      h_segptr[nsl] = k;
-    }
-    auto put = [&](DevBuf& b, const void* src, size_t bytes) -> int {
-      CAL_TRY(b.reserve(bytes, false));
-      HIP_TRY(copy_sync(b.p, src, bytes, hipMemcpyHostToDevice));
-      return CAL_OK;
-    };
-    CAL_TRY(put(dg_geo, geo.data(), geo.size() * sizeof(double)));
-    CAL_TRY(put(dg_idx, idx.data(), idx.size() * sizeof(int)));
+    DegeneracyPlan P;  // d_b, the slices' rows and their segments (report_plan.hpp)
+    CAL_TRY(plan_degeneracies(h_bl_ant, nants, nsl, nfreqs, fpad, band, d->antpos, d->freqs, P));
+    const int nseg = P.nseg;
+    CAL_TRY(put(dg_geo, P.pack_geo(), true));
+    CAL_TRY(put(dg_idx, P.pack_idx(), true));
     const size_t plane = (size_t)nbls * fpad, splane = (size_t)nsl * fpad;
     const size_t st_count = kDgPlanes * splane + 2 * (size_t)nsl;
     CAL_TRY(dg_z.reserve(2 * plane * sizeof(T)));
@@ -2031,26 +1950,20 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
       w = dg_w.as<T>();
     }
     const size_t gbytes = (size_t)nants * fpad * sizeof(T2);
-    const T2* g = gains.as<T2>();
-    if (d->g_r) {
-      CAL_TRY(fq_gains.reserve(gbytes));
-      CAL_TRY(upload_rows(d->g_r, fq_gains.as<T>(), nants, 2, 0));
-      CAL_TRY(upload_rows(d->g_i, fq_gains.as<T>(), nants, 2, 1));
-      g = fq_gains.as<T2>();
-    }
     if (d->gref_r) {
       CAL_TRY(dg_gref.reserve(gbytes));
       CAL_TRY(upload_rows(d->gref_r, dg_gref.as<T>(), nants, 2, 0));
       CAL_TRY(upload_rows(d->gref_i, dg_gref.as<T>(), nants, 2, 1));
     }
     if (out_g_r) CAL_TRY(dg_gout.reserve(gbytes));
-    const double2* dv = dg_geo.as<double2>();
-    const double2* pos = dv + nbls;
-    const double* ratio = dg_geo.as<double>() + 2 * (size_t)nbls + 2 * (size_t)na;
-    const double* maxd = ratio + fpad;
+    const double* geo = dg_geo.as<double>();
+    const double2* dv = reinterpret_cast<const double2*>(geo);
+    const double2* pos = reinterpret_cast<const double2*>(geo + P.geo_pos());
+    const double* ratio = geo + P.geo_ratio();
+    const double* maxd = geo + P.geo_maxd();
     const int* ent = dg_idx.as<int>();
-    const int* segptr = ent + nbls;
-    const DgSeg* segs = reinterpret_cast<const DgSeg*>(segptr + nsl + 1);
+    const int* segptr = ent + P.idx_segptr();
+    const DgSeg* segs = reinterpret_cast<const DgSeg*>(ent + P.idx_segs());
     double* st = dg_st.as<double>();
     double* part = dg_part.as<double>();
     T *m_r = nullptr, *m_i = nullptr;
@@ -2142,8 +2055,8 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
         CAL_TRY(model_pass(2, [&](T* model_r, T* model_i, T*) { launch(model_r, model_i); }));
       }
     }
-    if (scale_bl) HIP_TRY(hipMemcpyAsync(scale_bl, o_scale, (size_t)nbls * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (ndown_bl) HIP_TRY(hipMemcpyAsync(ndown_bl, o_ndown, (size_t)nbls * sizeof(double), hipMemcpyDeviceToHost, stream));
+    CAL_TRY(give(scale_bl, o_scale, (size_t)nbls));
+    CAL_TRY(give(ndown_bl, o_ndown, (size_t)nbls));
     HIP_TRY(hipStreamSynchronize(stream));
     return CAL_OK;
   }
@@ -3165,6 +3078,50 @@ int debug_solve_plan(const cal_problem_desc* d, int64_t bound, int what, void* o
   }
   return give(P.lwork);
 }
+// cal_debug_report_plan: the arrays of report_plan.hpp as bytes
+template <typename T>
+int debug_report_plan(const cal_problem_desc* d, const cal_report_plan_desc* r, int what, void* out, int64_t cap, int64_t* bytes) {
+  const char* who = "cal_debug_report_plan";
+  auto give = [&](const auto& v) { return plan_bytes(v, out, cap, bytes, who); };
+  ProblemPlan<T> p;
+  CAL_TRY(plan_problem(d, p));
+  if (what >= 0 && what <= 4) {
+    const cal_delay_spectrum_desc* s = r->spectrum;
+    if (!s || s->ndelays < 1 || (s->what & 7) == 0 || (s->what & ~7) || s->nbins < 0 || (s->nbins == 0) != (s->bin_of_bl == nullptr) || !s->op_r || !s->op_i ||
+        !s->norm_f || r->scratch_bytes < 0)
+      return fail(CAL_ERR_INVALID, "%s: what = %d takes a spectrum description cal_solver_delay_spectrum would plan for, and a bound >= 0", who, what);
+    DelaySpectrumPlan<T> P;
+    CAL_TRY(plan_delay_spectrum(p.nbls, p.nfreqs, p.fpad, s, r->scratch_bytes == 0 ? kCsScratchDefault : r->scratch_bytes, r->with_power_bl != 0 || s->nbins > 0, P));
+    switch (what) {
+      case 0: return give(std::vector<int64_t>{P.nq, P.xpitch, P.ndpad, P.crows, P.nchunks, (int64_t)P.n_x, (int64_t)P.n_pow, (int64_t)P.n_out});
+      case 1: return give(P.bin_ent);
+      case 2: return give(P.chunk_ptr);
+      case 3: return give(P.image);
+    }
+    return give(P.norm_f);
+  }
+  if (what >= 10 && what <= 19) {
+    const cal_degeneracy_desc* g = r->degeneracy;
+    const int nsl = r->nslices ? r->nslices : p.nslices;
+    if (!g || (g->mode != CAL_DEGEN_CHANNEL && g->mode != CAL_DEGEN_BAND) || !g->antpos || (g->mode == CAL_DEGEN_BAND && !g->freqs) || nsl < 1 || p.nants % nsl != 0)
+      return fail(CAL_ERR_INVALID, "%s: what = %d takes a mode, antpos, freqs for CAL_DEGEN_BAND, and a number of slices that divides nants", who, what);
+    DegeneracyPlan P;
+    CAL_TRY(plan_degeneracies(p.bl_ant, p.nants, nsl, p.nfreqs, p.fpad, g->mode == CAL_DEGEN_BAND, g->antpos, g->freqs, P));
+    switch (what) {
+      case 10: return give(std::vector<int64_t>{P.nseg, (int64_t)P.geo_pos(), (int64_t)P.geo_ratio(), (int64_t)P.geo_maxd(), (int64_t)P.idx_segptr(), (int64_t)P.idx_segs()});
+      case 11: return give(P.d_b);
+      case 12: return give(P.pos);
+      case 13: return give(P.ratio);
+      case 14: return give(P.maxd);
+      case 15: return give(P.ent);
+      case 16: return give(P.segptr);
+      case 17: return give(P.segs);
+      case 18: return give(P.pack_geo());
+    }
+    return give(P.pack_idx());
+  }
+  return fail(CAL_ERR_INVALID, "%s: what = %d", who, what);
+}
 }  // namespace
 
 extern "C" {
@@ -3198,6 +3155,11 @@ int cal_debug_solve_plan(int dtype, const cal_problem_desc* d, int64_t scratch_b
   if (scratch_bytes < 0) return fail(CAL_ERR_INVALID, "cal_debug_solve_plan: negative bound");
   const int64_t bound = scratch_bytes == 0 ? kCsScratchDefault : scratch_bytes;  // as in set_coeff_solve_scratch
   return dtype == CAL_F32 ? debug_solve_plan<float>(d, bound, what, out, cap_bytes, bytes) : debug_solve_plan<double>(d, bound, what, out, cap_bytes, bytes);
+}
+
+int cal_debug_report_plan(int dtype, const cal_problem_desc* d, const cal_report_plan_desc* r, int what, void* out, int64_t cap_bytes, int64_t* bytes) {
+  if (!r || !out || !bytes || cap_bytes < 0 || (dtype != CAL_F32 && dtype != CAL_F64)) return fail(CAL_ERR_INVALID, "cal_debug_report_plan: bad argument");
+  return dtype == CAL_F32 ? debug_report_plan<float>(d, r, what, out, cap_bytes, bytes) : debug_report_plan<double>(d, r, what, out, cap_bytes, bytes);
 }
 
 int cal_debug_step_shape(const int32_t* inputs, int32_t* shape) {

@@ -1,0 +1,153 @@
+// report_plan.hpp -- what the post-fit reports cal_solver_delay_spectrum and cal_solver_fix_degeneracies decide before they launch, on the
+// host alone: the rows of every bin and of every slice, how they are cut into chunks and segments, and the padded images the kernels read.
+// No HIP or RCCL runtime call and no solver: SolverT uploads these plans at every call; cal_debug_report_plan returns them as bytes
+// (tests/test_report_plan_host.py).  dspec_bin_kernel adds a bin's rows, and degen_sum_kernel a slice's segments, in the order written
+// here, in double and without atomics: ascending rows, cut where the loops below cut them.  That order is what "two calls give the same
+// bits, a slice of a batch the bits of the same slice alone" rests on, so it is part of the plan.
+#pragma once
+#include "problem_plan.hpp"
+#include "delay_spectrum_kernels.hpp"
+#include "degeneracy_kernels.hpp"
+
+namespace {
+
+// ---- cal_solver_delay_spectrum ----------------------------------------------------------------------------------------------------
+template <typename T>
+struct DelaySpectrumPlan {
+  int nq = 0;                  // quantities asked for: the bits of `what`
+  int xpitch = 0, ndpad = 0;   // row pitch of the masked planes, columns of the operator image
+  int crows = 0, nchunks = 0;  // rows per chunk (the last may hold fewer)
+  std::vector<int> bin_ent;    // the sorted row list of every bin, one after the other (CSR, like ant_ent)
+  std::vector<int> chunk_ptr;  // [nchunks][nbins][2]: a bin's piece of a chunk as positions in bin_ent
+  std::vector<T> image;        // [re, im][xpitch][ndpad]: the operator, zero beyond nfreqs and ndelays
+  std::vector<double> norm_f;  // [xpitch], zero beyond nfreqs
+  size_t n_x = 0, n_pow = 0, n_out = 0;  // elements of ds_x (T), of ds_pow (double; 0 without power) and of ds_out (norm_bl | power_bin | count_bin)
+};
+
+// A chunk's scratch -- the masked planes in T and, with_power, its power in double -- stays under `bound` bytes (never less than one row);
+// the chunks are cut at multiples of the transform's kDsRows where that fits.  d: ndelays, what, nbins, bin_of_bl, op_r, op_i, norm_f.
+template <typename T>
+int plan_delay_spectrum(int nbls, int nfreqs, int fpad, const cal_delay_spectrum_desc* d, int64_t bound, bool with_power, DelaySpectrumPlan<T>& P) {
+  const int nd = d->ndelays, nbins = d->nbins;
+  P.nq = (d->what & 1) + (d->what >> 1 & 1) + (d->what >> 2 & 1);
+  if ((long long)P.nq * nbins * nd + nbins > (1ll << 31) - 1) return fail(CAL_ERR_INVALID, "delay_spectrum: nbins = %d is too many", nbins);
+  std::vector<int> bin_ptr(nbins + 1, 0);
+  for (int b = 0; b < nbls && nbins; ++b) {
+    const int n = d->bin_of_bl[b];
+    if (n < -1 || n >= nbins) return fail(CAL_ERR_INVALID, "delay_spectrum: bin_of_bl[%d] = %d lies outside [-1, %d)", b, n, nbins);
+    if (n >= 0) ++bin_ptr[n + 1];
+  }
+  if (nbins) {
+    for (int n = 0; n < nbins; ++n) bin_ptr[n + 1] += bin_ptr[n];
+    P.bin_ent.resize(bin_ptr[nbins]);
+    std::vector<int> fill(bin_ptr.begin(), bin_ptr.end() - 1);
+    for (int b = 0; b < nbls; ++b)
+      if (d->bin_of_bl[b] >= 0) P.bin_ent[fill[d->bin_of_bl[b]]++] = b;
+  }
+  P.xpitch = ds_xpitch(fpad);
+  P.ndpad = ds_ndpad(nd);
+  const size_t row_bytes = (size_t)P.nq * 2 * P.xpitch * sizeof(T) + (with_power ? (size_t)P.nq * nd * sizeof(double) : 0);
+  long long crows = std::max<long long>(1, bound / (long long)row_bytes);
+  if (crows > kDsRows) crows -= crows % kDsRows;
+  crows = std::min<long long>(crows, nbls);
+  P.crows = (int)crows;
+  P.nchunks = (int)((nbls + crows - 1) / crows);
+  P.chunk_ptr.resize((size_t)P.nchunks * nbins * 2);
+  for (int c = 0; c < P.nchunks && nbins; ++c) {
+    const long long b0 = c * crows, b1 = std::min<long long>(nbls, b0 + crows);
+    for (int n = 0; n < nbins; ++n) {
+      const int* e0 = P.bin_ent.data() + bin_ptr[n];
+      const int* e1 = P.bin_ent.data() + bin_ptr[n + 1];
+      P.chunk_ptr[((size_t)c * nbins + n) * 2] = (int)(std::lower_bound(e0, e1, (int)b0) - P.bin_ent.data());
+      P.chunk_ptr[((size_t)c * nbins + n) * 2 + 1] = (int)(std::lower_bound(e0, e1, (int)b1) - P.bin_ent.data());
+    }
+  }
+  P.image.assign((size_t)2 * P.xpitch * P.ndpad, (T)0);
+  for (int part = 0; part < 2; ++part) {
+    const T* src = static_cast<const T*>(part ? d->op_i : d->op_r);
+    for (int f = 0; f < nfreqs; ++f) std::copy(src + (size_t)f * nd, src + (size_t)(f + 1) * nd, P.image.begin() + ((size_t)part * P.xpitch + f) * P.ndpad);
+  }
+  P.norm_f.assign((size_t)P.xpitch, 0.0);
+  std::copy(d->norm_f, d->norm_f + nfreqs, P.norm_f.begin());
+  P.n_x = (size_t)P.nq * 2 * crows * P.xpitch;
+  P.n_pow = with_power ? (size_t)P.nq * crows * nd : 0;
+  P.n_out = (size_t)nbls + (size_t)P.nq * nbins * nd + nbins;
+  return CAL_OK;
+}
+
+// ---- cal_solver_fix_degeneracies --------------------------------------------------------------------------------------------------
+struct DegeneracyPlan {
+  std::vector<double> d_b;    // [nbls][2]: r_i - r_j of a row's own antennas
+  std::vector<double> pos;    // [na][2]: one slice's antenna positions
+  std::vector<double> ratio;  // [fpad]: nu_f / nu_ref (band mode) or 1, zero beyond nfreqs
+  std::vector<double> maxd;   // [nsl]: the slice's longest |d_b|
+  std::vector<int> ent;       // the row list of every slice, one after the other, each ascending
+  std::vector<int> segptr;    // [nsl + 1]: a slice's first segment
+  std::vector<DgSeg> segs;    // every kDgSeg rows of a slice's list
+  int nseg = 0;
+  // The two blobs the kernels read, dg_geo (doubles) and dg_idx (ints): where every array starts, and the arrays packed in that order.
+  size_t geo_pos() const { return d_b.size(); }
+  size_t geo_ratio() const { return geo_pos() + pos.size(); }
+  size_t geo_maxd() const { return geo_ratio() + ratio.size(); }
+  size_t idx_segptr() const { return ent.size(); }
+  size_t idx_segs() const { return idx_segptr() + segptr.size(); }
+  std::vector<double> pack_geo() const {
+    std::vector<double> v(d_b);
+    for (const std::vector<double>* a : {&pos, &ratio, &maxd}) v.insert(v.end(), a->begin(), a->end());
+    return v;
+  }
+  std::vector<int> pack_idx() const {
+    static_assert(sizeof(DgSeg) == 4 * sizeof(int), "a segment is four ints of dg_idx");
+    std::vector<int> v(ent);
+    v.insert(v.end(), segptr.begin(), segptr.end());
+    const int* s = reinterpret_cast<const int*>(segs.data());
+    v.insert(v.end(), s, s + 4 * segs.size());
+    return v;
+  }
+};
+
+// bl_ant: the plan's rows; nsl slices of na = nants / nsl antennas each (joint time-basis layout: antenna row t na + a is slice t, antenna a);
+// band: Phi(f) = (nu_f / nu_ref) Phi_0 with nu_ref the mean of freqs (read only then); antpos [na][2].
+inline int plan_degeneracies(const std::vector<int2>& bl_ant, int nants, int nsl, int nfreqs, int fpad, bool band, const double* antpos,
+                             const double* freqs, DegeneracyPlan& P) {
+  const int nbls = (int)bl_ant.size(), na = nants / nsl;
+  for (int k = 0; k < 2 * na; ++k)
+    if (!std::isfinite(antpos[k])) return fail(CAL_ERR_INVALID, "fix_degeneracies: antenna position %d is not finite", k / 2);
+  P.pos.assign(antpos, antpos + 2 * (size_t)na);
+  P.ratio.assign((size_t)fpad, 0.0);
+  std::fill(P.ratio.begin(), P.ratio.begin() + nfreqs, 1.0);
+  if (band) {
+    double mean = 0.0;
+    for (int f = 0; f < nfreqs; ++f) mean += freqs[f];
+    mean /= nfreqs;
+    if (!std::isfinite(mean) || mean == 0.0) return fail(CAL_ERR_INVALID, "fix_degeneracies: the mean of freqs must be finite and not zero");
+    for (int f = 0; f < nfreqs; ++f) P.ratio[f] = freqs[f] / mean;
+  }
+  P.d_b.assign(2 * (size_t)nbls, 0.0);
+  P.maxd.assign((size_t)nsl, 0.0);
+  std::vector<int> cnt(nsl + 1, 0);
+  for (int b = 0; b < nbls; ++b) {
+    const int2 a = bl_ant[b];
+    const int t = a.x / na;
+    if (a.y / na != t) return fail(CAL_ERR_INVALID, "fix_degeneracies: baseline row %d joins antennas of two slices (%d, %d; %d antennas per slice)", b, a.x, a.y, na);
+    ++cnt[t + 1];
+    const int i = a.x % na, j = a.y % na;
+    const double de = P.pos[2 * i] - P.pos[2 * j], dn = P.pos[2 * i + 1] - P.pos[2 * j + 1];
+    P.d_b[2 * (size_t)b] = de;
+    P.d_b[2 * (size_t)b + 1] = dn;
+    P.maxd[t] = std::max(P.maxd[t], std::sqrt(de * de + dn * dn));
+  }
+  for (int t = 0; t < nsl; ++t) cnt[t + 1] += cnt[t];
+  P.ent.resize(nbls);
+  std::vector<int> fill(cnt.begin(), cnt.end() - 1);
+  for (int b = 0; b < nbls; ++b) P.ent[fill[bl_ant[b].x / na]++] = b;
+  P.segptr.resize(nsl + 1);
+  for (int t = 0; t < nsl; ++t) {
+    P.segptr[t] = (int)P.segs.size();
+    for (int e = cnt[t]; e < cnt[t + 1]; e += kDgSeg) P.segs.push_back(DgSeg{t, e, std::min(e + kDgSeg, cnt[t + 1]), 0});
+  }
+  P.segptr[nsl] = P.nseg = (int)P.segs.size();
+  return CAL_OK;
+}
+
+}  // namespace

@@ -214,6 +214,30 @@ int cal_debug_plan(int dtype, const cal_problem_desc* d, int what, void* out, in
  *   (vectors of the frequency basis, of the time basis, times; nants must be a multiple of T); on return int64 rows per chunk, in_lds,
  *   the Cholesky launch's LDS bytes, unknowns per row, elements per row of M and N (dtype) and of the double scratch. */
 int cal_debug_solve_plan(int dtype, const cal_problem_desc* d, int64_t scratch_bytes, int what, void* out, int64_t cap_bytes, int64_t* bytes);
+/* Host only, like cal_debug_plan: what cal_solver_delay_spectrum and cal_solver_fix_degeneracies plan before they launch
+ * (csrc/report_plan.hpp) for the problem `d` and a solver of `dtype`.  For tests (tests/test_report_plan_host.py).  The call is described
+ * by `r` (NULL: CAL_ERR_INVALID); the planner's own refusals come back with the code and message the solver's call would give.
+ * what = 0 .. 4: the plan of cal_solver_delay_spectrum for r->spectrum (ndelays, what, nbins, bin_of_bl, op_r, op_i, norm_f are read; the
+ *   operator in `dtype`), the bound r->scratch_bytes of cal_solver_set_delay_spectrum_scratch (0: the default) and with_power_bl (power_bl
+ *   is asked for; bins ask for the power anyway) --
+ *   0: int64 nwhat, the row pitch of the masked planes, the columns of the operator image, rows per chunk, chunks, the elements of the
+ *   chunk's planes (dtype), of its power (double) and of norm_bl | power_bin | count_bin; 1: the bins' sorted row lists, one after the
+ *   other; 2: [chunks][nbins][2] a bin's piece of a chunk as positions in 1; 3: the operator image [re, im][pitch][columns] (dtype);
+ *   4: norm_f padded to the pitch (double).
+ * what = 10 .. 19: the plan of cal_solver_fix_degeneracies for r->degeneracy (mode, antpos and, for CAL_DEGEN_BAND, freqs are read) over
+ *   r->nslices slices (0: the problem's nslices; the ntimes of a joint time-basis layout otherwise: it must divide nants) --
+ *   10: int64 segments, then the first double of antpos, ratio and maxd in blob 18 and the first int of 16 and 17 in blob 19;
+ *   11: d_b [nbls][2]; 12: antpos; 13: nu_f / nu_ref [fpad]; 14: the slices' longest |d_b| (11 .. 14 double); 15: the slices' row lists,
+ *   one after the other; 16: a slice's first segment [slices + 1]; 17: the segments (DgSeg); 18 / 19: the two blobs as the device holds
+ *   them, 11 | 12 | 13 | 14 (double) and 15 | 16 | 17 (int32). */
+typedef struct cal_report_plan_desc {
+  const struct cal_delay_spectrum_desc* spectrum;
+  const struct cal_degeneracy_desc* degeneracy;
+  int64_t scratch_bytes;
+  int32_t with_power_bl;
+  int32_t nslices;
+} cal_report_plan_desc;
+int cal_debug_report_plan(int dtype, const cal_problem_desc* d, const cal_report_plan_desc* r, int what, void* out, int64_t cap_bytes, int64_t* bytes);
 /* Host only, like cal_debug_plan: the shape of one pass or train step (csrc/step_plan.hpp) -- which kernels follow the fused or dense pass,
  * the form of the update, whether a run replays its steps from a graph.  For tests (tests/test_step_plan_host.py).
  * inputs, 14 int32 (flags 0 / 1 but [7]): the dense path serves the pass, the regulariser is "sum", the regularised gradient pass needs the

@@ -1,13 +1,15 @@
 // plan_sanitize.hip -- the set-up planner (calamity_amd/csrc/problem_plan.hpp), the planner of the closed-form calls
-// (calamity_amd/csrc/solve_plan.hpp), the step's shape (calamity_amd/csrc/step_plan.hpp) and the two-loop recursion of L-BFGS on
+// (calamity_amd/csrc/solve_plan.hpp), of the post-fit reports (calamity_amd/csrc/report_plan.hpp), the step's shape (calamity_amd/csrc/step_plan.hpp) and the two-loop recursion of L-BFGS on
 // coefficients (calamity_amd/csrc/lbfgs_core.hpp) under the host sanitizers, with no device and no interpreter: four problems built in code (folded STREAM, heads of baselines that share tiles, forced dense, multi-baseline runs),
-// planned for fp32 and fp64; the closed-form plans at the default scratch bound and at a bound of 1 byte; plan_step over its whole input
+// planned for fp32 and fp64; the closed-form plans and the delay-spectrum plan at the default scratch bound and at a bound of 1 byte, the degeneracy plan in both modes,
+// the caller's arrays of exactly the sizes the planners may read; plan_step over its whole input
 // table; lbfgs_two_loop on Gram matrices of 0 .. 16 pairs held in arrays of exactly the sizes it may touch.  Exits non-zero on a planner error or an inconsistent plan; the sanitizers abort on a finding.
 //
 //   hipcc --offload-arch=gfx950 -std=c++17 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
 //         -o plan_sanitize tools/plan_sanitize.hip && ./plan_sanitize
 #include "../calamity_amd/csrc/solve_plan.hpp"
 #include "../calamity_amd/csrc/step_plan.hpp"
+#include "../calamity_amd/csrc/report_plan.hpp"
 #include "../calamity_amd/csrc/lbfgs_core.hpp"
 
 #include <cstdint>
@@ -91,7 +93,30 @@ int run(const Case& c) {
            rt.rows, rc.rows);
   }
   if (bad) fprintf(stderr, "%s (%d-byte reals): the closed-form plans are inconsistent\n", c.name, (int)sizeof(T));
-  return bad ? 1 : 0;
+  // the plans of the post-fit reports: 37 delays, rows dealt over three of four bins and every seventh left out; one chunk, then one per row
+  const int nd = 37, nbins = 4;
+  std::vector<T> op_r((size_t)p.nfreqs * nd, (T)1), op_i(op_r);
+  std::vector<double> norm_f(p.nfreqs, 1.0), antpos(2 * (size_t)p.na_slice), freqs(p.nfreqs);
+  std::vector<int> bin_of_bl(p.nbls);
+  for (int b = 0; b < p.nbls; ++b) bin_of_bl[b] = b % 7 == 3 ? -1 : b % (nbins - 1);
+  for (size_t k = 0; k < antpos.size(); ++k) antpos[k] = 14.6 * (double)((k * 7) % 11);
+  for (int f = 0; f < p.nfreqs; ++f) freqs[f] = 100e6 + 400e3 * f;
+  const cal_delay_spectrum_desc sd{nd, 7, 0, nbins, bin_of_bl.data(), op_r.data(), op_i.data(), norm_f.data()};
+  int rbad = 0;
+  for (const int64_t bound : {kCsScratchDefault, (int64_t)1}) {
+    DelaySpectrumPlan<T> P;
+    rbad += plan_delay_spectrum(p.nbls, p.nfreqs, p.fpad, &sd, bound, true, P) != CAL_OK || P.nchunks != (bound == 1 ? p.nbls : 1);
+    int rows = 0;
+    for (size_t k = 0; k < P.chunk_ptr.size(); k += 2) rows += P.chunk_ptr[k + 1] - P.chunk_ptr[k];
+    rbad += rows != (int)P.bin_ent.size() || P.bin_ent.size() != (size_t)(p.nbls - (p.nbls + 3) / 7);
+  }
+  for (const bool band : {false, true}) {
+    DegeneracyPlan P;
+    rbad += plan_degeneracies(p.bl_ant, p.nants, p.nslices, p.nfreqs, p.fpad, band, antpos.data(), band ? freqs.data() : nullptr, P) != CAL_OK ||
+            P.segs.empty() || P.segs.back().e1 != p.nbls || P.pack_geo().size() != P.geo_maxd() + p.nslices || P.pack_idx().size() != P.idx_segs() + 4 * (size_t)P.nseg;
+  }
+  if (rbad) fprintf(stderr, "%s (%d-byte reals): the report plans are inconsistent: %s\n", c.name, (int)sizeof(T), g_err.c_str());
+  return bad || rbad ? 1 : 0;
 }
 
 // plan_step over every combination of its inputs (2^13 flag settings x 4 launch modes), through the layouts of cal_debug_step_shape:
