@@ -23,11 +23,13 @@ import copy
 import datetime
 import os
 import threading
+import types
 
 import numpy as np
 
-from . import cal_utils, modeling, utils
+from . import cal_utils, modeling, slice_pipeline, utils
 from .fit_loop import KEYWORD_HELP, FitControls, drive, history_entry
+from .slice_pipeline import init_coeffs as _init_coeffs, slice_stats as _slice_stats  # noqa: F401 -- (names kept here for tools and tests)
 from .problem import FitProblem, coeffs_from_chunks, coeffs_to_chunks, problem_from_chunks
 from .solver import OPTIMIZERS, HipFitSolver
 from .utils import PBARS, echo
@@ -425,44 +427,6 @@ def get_solver(fg_model_comps, dtype=np.float32, layout=None, device=None):
     return cache[key]
 
 
-def _gram_factors(prob):
-    """Per fitting-group Gram matrices ``sum_bl A_bl^T A_bl`` that are not the identity (DPSS columns are orthonormal,
-    so for per-baseline DPSS this is empty).  Keyed by (basis, row blocks)."""
-    cache = prob.__dict__.setdefault("_gram", None)
-    if cache is not None:
-        return cache
-    F = prob.nfreqs
-    keys, out = {}, {}
-    for g in range(prob.ngrps):
-        rbs = tuple(prob.bl_rowblk[prob.grp_bl_start[g] : prob.grp_bl_start[g + 1]].tolist())
-        keys.setdefault((int(prob.grp_basis[g]), rbs), []).append(g)
-    for (u, rbs), grps in keys.items():
-        blk = prob.basis[u]
-        gram = sum(blk[rb * F : (rb + 1) * F].T @ blk[rb * F : (rb + 1) * F] for rb in rbs)
-        if not np.allclose(gram, np.eye(gram.shape[0]), atol=1e-9):
-            out[(u, rbs)] = (gram, np.asarray(grps))
-    prob.__dict__["_gram"] = out
-    return out
-
-
-def _init_coeffs(solver, prob, src_r, src_i):
-    """tensorize_fg_coeffs for both components at once: ``A^T (src * [w != 0])`` on the GPU, then the (rarely needed)
-    small Gram solves on the host.  Returns flat (c_r, c_i)."""
-    solver.init_coeffs(src_r, src_i)
-    _, _, c_r, c_i = solver.get_params()
-    grams = _gram_factors(prob)
-    if grams:
-        c_r = c_r.astype(np.float64)
-        c_i = c_i.astype(np.float64)
-        coff = prob.grp_coff
-        for (u, rbs), (gram, grps) in grams.items():
-            idx = coff[grps][None, :] + np.arange(gram.shape[0])[:, None]
-            c_r[idx] = np.linalg.solve(gram, c_r[idx])
-            c_i[idx] = np.linalg.solve(gram, c_i[idx])
-        solver.set_params(c_r=c_r, c_i=c_i)
-    return c_r, c_i
-
-
 def tensorize_fg_coeffs(data, wgts, fg_model_comps, notebook_progressbar=False, verbose=False, dtype=None):
     """Initial foreground coefficients of ONE real component by per-group linear least squares on ``data`` with
     zero-weight samples zeroed -- calibration.py:828-913.  Returns the reference's list of ``(nvecs, ngrps, 1, 1)``
@@ -712,17 +676,12 @@ def fit_gains_and_foregrounds(
     w_flat = _flatten(wgts, prob)
     solver.set_data(_flatten(data_r, prob), _flatten(data_i, prob), w_flat)
     solver.set_params(g_r, np.asarray(g_i), coeffs_from_chunks(prob, fg_r), coeffs_from_chunks(prob, fg_i))
-    if gain_basis is not None or solver.gain_nvec:  # (the solver is kept between calls: a basis of an earlier call goes)
-        solver.set_gain_basis(gain_basis)  # g0 = the gains just set, y = 0
     echo(f"{datetime.datetime.now()} Performing gradient descent on {np.prod(g_r.shape)} complex gain parameters...", verbose=verbose)
     if not freeze_model:
         echo(f"Performing gradient descent on total of {prob.ncoeffs} complex foreground parameters", verbose=verbose)
-    if model_regularization == "sum":
-        # priors of calibration.py:619-625 (accumulated in float64 on the host)
-        solver.set_regularization("sum", *_prior_sums(_flatten(sky_model_r, prob), _flatten(sky_model_i, prob), w_flat))
-    else:
-        solver.set_regularization(None)
-    solver.set_optimizer(optimizer, **opt_kwargs)
+    # priors of calibration.py:619-625 (accumulated in float64 on the host); the gain basis: g0 = the gains just set, y = 0
+    priors = slice_pipeline.prior_sums(_flatten(sky_model_r, prob), _flatten(sky_model_i, prob), w_flat) if model_regularization == "sum" else None
+    slice_pipeline.configure(solver, gain_basis, priors, optimizer, opt_kwargs)
     if n_profile_steps > 0:
         echo(f"{datetime.datetime.now()} Profiling with {n_profile_steps}. And writing output to {profile_log_dir}...")
     echo(f"{datetime.datetime.now()} Building Computational Graph...\n", verbose=verbose)
@@ -1023,29 +982,6 @@ def degeneracy_entry(out, t, degen):
     """Slice ``t`` of a ``fix_degeneracies`` result as what ``fit_history`` reports, per channel."""
     return {"mode": degen["mode"], "amplitude": np.exp(out["eta"][t]), "phase": out["psi"][t].copy(), "tilt": out["tilt"][t].copy(),
             "nsamples": out["nsamples"][t].astype(np.int64), "iters": degen["iters"], "last_step": out["last_step"][t].copy()}
-
-
-def _file_degeneracies(hist, gains, time, polarization, errs, entry):
-    """``hist["degeneracies"]`` of one slice; the slice's plane of ``gain_std`` follows the gains: times ``e^{-eta}``."""
-    hist["degeneracies"] = entry
-    if errs is not None and errs["gain_std"] is not None:
-        polnum = np.where(np.asarray(gains.jones_array) == polstr2num(polarization, x_orientation=gains.x_orientation))[0][0]
-        gindt = np.where(np.isclose(gains.time_array, time, atol=1e-7, rtol=0.0))[0][0]
-        errs["gain_std"][:, :, gindt, polnum] /= entry["amplitude"][None, :]
-
-
-def _report_slice(hist, gains, time, polarization, rms, prob, quality, errors, errs):
-    """What one fitted (polarization, time) slice reports besides its losses, for the loop over the slices and for the batches alike:
-    ``hist["robust"]`` from solver units and row order into the data's units, keyed by antenna numbers (``robust_history``); the slice's
-    ``quality`` (``fit_quality``) and ``errors`` (``fit_errors``, with the slice's ``chisq_bl`` among them) where they were asked for
-    (``insert_fit_quality``, ``insert_fit_errors``).  ``errs``: the call's fit-errors settings."""
-    if "robust" in hist:
-        rb = hist["robust"]
-        hist["robust"] = robust_history(rb["rounds"], rb["ndown_bl"], rb["scale_bl"], rms, prob, gains.ant_array)
-    if quality is not None:
-        insert_fit_quality(gains, hist, time, polarization, quality, rms, prob)
-    if errors is not None:
-        insert_fit_errors(errs["gain_std"], gains, hist, time, polarization, errors, errors["chisq_bl"], rms, prob)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -1367,12 +1303,8 @@ def calibrate_and_model_tensor(
         uvdata = uvdata.select(inplace=False, bls=[ap for ap in antpairs_data])
     # (with nothing to drop the input object itself is used: it is only read from here on, and the reference's
     # select(inplace=False) copy of a gigabyte of visibilities bought nothing but that guarantee)
-    resid = _blank_copy(uvdata, keep_flags=True)  # its visibilities are written at the end (_finish_outputs): data - gains x model
+    resid = _blank_copy(uvdata, keep_flags=True)  # its visibilities are written slice by slice (_output_finisher): data - gains x model
     model = _blank_copy(uvdata)
-    red_grps = []
-    for fit_grp in fg_model_comps_dict.keys():
-        for red_grp in fit_grp:
-            red_grps.append(red_grp)
     unity_gains = gains is None
     if gains is None:
         echo(f"{datetime.datetime.now()} Gains are None. Initializing gains starting with unity...\n", verbose=verbose)
@@ -1397,7 +1329,7 @@ def calibrate_and_model_tensor(
         sky_model = sky_model.select(inplace=False, bls=[ap for ap in antpairs_data])
     fit_history = {}
     ants_map = {ant: i for i, ant in enumerate(np.asarray(gains.ant_array).tolist())}
-    fg_model_comps, corr_inds = tensorize_fg_model_comps_dict(
+    prob, _ = tensorize_fg_model_comps_dict(
         fg_model_comps_dict=fg_model_comps_dict,
         ants_map=ants_map,
         dtype=dtype,
@@ -1409,7 +1341,6 @@ def calibrate_and_model_tensor(
     )
     echo(f"{datetime.datetime.now()}Finished Converting Foreground Modeling Components to Tensors...\n", verbose=verbose)
     del fg_model_comps_dict
-    prob = fg_model_comps
     dspec = None
     if delay_spectrum:
         dspec = delay_spectrum_setup(uvdata, gains.ant_array, prob, taper=delay_spectrum_taper, max_dly=delay_spectrum_max_dly,
@@ -1425,6 +1356,15 @@ def calibrate_and_model_tensor(
         batch_slices = parallel_fits <= 1 or gain_time_basis is not None
     if init_guesses_from_previous_time_step:
         batch_slices = False  # every time starts from the previous one's result: a chain, not a batch
+    # the call's settings, once, for the loop and the batches alike (slice_pipeline's stages read them)
+    cfg = types.SimpleNamespace(
+        uvdata=uvdata, sky_model=sky_model, gains=gains, resid=resid, model=model, prob=prob, ants_map=ants_map, times=times, weights=weights,
+        nsamples_in_weights=nsamples_in_weights, dtype=np.dtype(dtype), skip_threshold=skip_threshold, use_model_snr_weights=use_model_snr_weights,
+        optimizer=optimizer, opt_kwargs=opt_kwargs, use_min=use_min, freeze_model=freeze_model, tol=tol, maxsteps=maxsteps,
+        n_profile_steps=n_profile_steps, profile_log_dir=profile_log_dir, model_regularization=model_regularization, verbose=verbose,
+        devices=devices, layout=layout, device_split=device_split, gain_basis=gain_basis, gain_time_basis=gain_time_basis, fit_quality=fit_quality,
+        controls=controls, errs=errs, dspec=dspec, degen=degen,
+        finish=_output_finisher(uvdata, model, resid, gains, correct_model, correct_resid))
     if batch_slices:
         if gain_time_basis is not None:
             # the joint fit of a polarization holds all of its times, whatever _auto_batch would make of them: its device memory is
@@ -1432,18 +1372,9 @@ def calibrate_and_model_tensor(
             max_batch = len(times)
         else:
             max_batch = _auto_batch(prob, dtype, layout) if batch_slices is True else max(1, min(int(batch_slices), _lib_max_slices()))
-        fit_history = _fit_slices_batched(
-            uvdata=uvdata, sky_model=sky_model, gains=gains, resid=resid, model=model, prob=prob, corr_inds=corr_inds, ants_map=ants_map,
-            times=times, weights=weights, nsamples_in_weights=nsamples_in_weights, dtype=dtype, skip_threshold=skip_threshold,
-            use_model_snr_weights=use_model_snr_weights, optimizer=optimizer, use_min=use_min, freeze_model=freeze_model, tol=tol,
-            maxsteps=maxsteps, n_profile_steps=n_profile_steps, profile_log_dir=profile_log_dir, model_regularization=model_regularization,
-            verbose=verbose, max_batch=max_batch, devices=devices, layout=layout, opt_kwargs=opt_kwargs,
-            correct_model=correct_model, correct_resid=correct_resid, device_split=device_split, gain_basis=gain_basis,
-            gain_time_basis=gain_time_basis, fit_quality=fit_quality,
-            controls=controls, errs=errs, dspec=dspec, degen=degen,
-        )
+        fit_history = _fit_slices_batched(cfg, max_batch)
         _file_gain_std(fit_history, errs, gains)
-        return model, resid, gains, fit_history  # (every slice left _fit_slices_batched in its final state)
+        return model, resid, gains, fit_history  # (every fitted slice left its write-back in its final state)
     assert gain_time_basis is None, "a gain time basis must not reach the loop over single times"
     if layout is not None:
         prob.__dict__["_layout"] = layout
@@ -1451,126 +1382,41 @@ def calibrate_and_model_tensor(
         prob.__dict__["_device"] = 0 if isinstance(devices, str) else int(list(devices)[0])  # the loop fits on one device
 
     def fit_slice(polnum, pol, time_index, time, carry):
-        """One (polarization, time) slice: calibration.py:1167-1330.  ``carry`` holds the parameters handed from one time
-        to the next when init_guesses_from_previous_time_step is set."""
-        solver = get_solver(fg_model_comps, dtype)
-        hist = None
-        g_r, g_i, fg_r, fg_i = carry.get("g_r"), carry.get("g_i"), carry.get("fg_r"), carry.get("fg_i")
+        """One (polarization, time) slice: calibration.py:1167-1330, a batch of one on this thread's solver.  ``carry`` holds the
+        parameters handed from one time to the next when init_guesses_from_previous_time_step is set."""
         echo(f"{datetime.datetime.now()} Working on time {time_index + 1} of {uvdata.Ntimes}...\n", verbose=verbose)
-        bltsel = np.isclose(uvdata.time_array, time, atol=1e-7, rtol=0.0)
-        frac_unflagged, rmsdata = _slice_stats(uvdata, bltsel, polnum)
-        if frac_unflagged >= skip_threshold:
-            echo(f"{datetime.datetime.now()} Tensorizing data...\n", verbose=verbose)
-            data_r, data_i, wgts = tensorize_data(
-                uvdata, corr_inds=corr_inds, ants_map=ants_map, polarization=pol, time=time, data_scale_factor=rmsdata,
-                weights=weights, nsamples_in_weights=nsamples_in_weights, dtype=dtype,
-            )
-            if sky_model is not None:
-                echo(f"{datetime.datetime.now()} Tensorizing sky model...\n", verbose=verbose)
-                sky_model_r, sky_model_i, sky_wgts = tensorize_data(
-                    sky_model, corr_inds=corr_inds, ants_map=ants_map, polarization=pol, time=time, data_scale_factor=rmsdata,
-                    weights=weights, dtype=dtype,
-                )
-                if degen is not None:  # the reference's weights: the sky model's own, where the data have any
-                    degen_w = _flatten(sky_wgts, prob) * (_flatten(wgts, prob) > 0)
-            else:
-                sky_model_r, sky_model_i = None, None
-            if carry["first_time"] or not init_guesses_from_previous_time_step:
-                carry["first_time"] = False
-                echo(f"{datetime.datetime.now()} Tensorizing Gains...\n", verbose=verbose)
-                g_r, g_i = tensorize_gains(gains, dtype=dtype, time=time, polarization=pol)
-                echo(f"{datetime.datetime.now()} Tensorizing Foreground coeffs...\n", verbose=verbose)
-                # tensorize_fg_coeffs x 2 (calibration.py:1219-1233): one device pass gives both components
-                w_flat = _flatten(wgts, prob)
-                zeros = np.zeros_like(w_flat)
-                solver.set_data(zeros, zeros, w_flat)
-                c_r, c_i = _init_coeffs(solver, prob, _flatten(sky_model_r, prob), _flatten(sky_model_i, prob))
-                fg_r = coeffs_to_chunks(prob, c_r, dtype)
-                fg_i = coeffs_to_chunks(prob, c_i, dtype)
-                if use_model_snr_weights:
-                    m_r, m_i = solver.model()
-                    w_new = (np.square(m_r.astype(np.float64)) + np.square(m_i.astype(np.float64))) * w_flat
-                    w_new = w_new / np.sum(w_new)
-                    start = 0
-                    new_wgts = []
-                    for w in wgts:
-                        n = w.shape[0] * w.shape[1]
-                        new_wgts.append(w_new[start : start + n].reshape(w.shape).astype(dtype))
-                        start += n
-                    wgts = new_wgts
-            g0_r, g0_i = g_r, g_i  # the gains the fit starts from: the phase reference of fix_degeneracies
-            (g_r, g_i, fg_r, fg_i, hist) = fit_gains_and_foregrounds(
-                g_r=g_r, g_i=g_i, fg_r=fg_r, fg_i=fg_i, data_r=data_r, data_i=data_i, wgts=wgts, fg_comps=fg_model_comps,
-                corr_inds=corr_inds, optimizer=optimizer, use_min=use_min, freeze_model=freeze_model,
-                notebook_progressbar=notebook_progressbar, verbose=verbose, tol=tol, dtype=dtype, maxsteps=maxsteps,
-                graph_mode=graph_mode, n_profile_steps=n_profile_steps, profile_log_dir=profile_log_dir,
-                sky_model_r=sky_model_r, sky_model_i=sky_model_i, model_regularization=model_regularization, gain_basis=gain_basis,
-                **controls.keywords(), **opt_kwargs,
-            )
-            # yield_fg_model_array x 2 + insert_model_into_uvdata_tensor (calibration.py:1271-1292) without the
-            # nants x nants cubes: one A c pass for both components, rows written straight back
-            solver.set_params(c_r=coeffs_from_chunks(prob, fg_r), c_i=coeffs_from_chunks(prob, fg_i))
-            m_r, m_i = solver.model()
-            w_r, w_i, fixed = g_r, g_i, None  # what is written; the values carried to the next time stay the fitted ones
-            if degen is not None:
-                ref_phase = (np.asarray(g0_r), np.asarray(g0_i)) if degen["phase_ref"] else (None, None)
-                fixed = solver.fix_degeneracies(_flatten(sky_model_r, prob), _flatten(sky_model_i, prob), degen["antpos"], ref_w=degen_w, mode=degen["mode"],
-                                                iters=degen["iters"], freqs=degen["freqs"], g_r=np.asarray(g_r), g_i=np.asarray(g_i), gref_r=ref_phase[0],
-                                                gref_i=ref_phase[1])
-                m_r, m_i, w_r, w_i = fixed["model_r"], fixed["model_i"], fixed["g_r"], fixed["g_i"]
-            _insert_model_rows(model, time, pol, ants_map, prob, m_r, m_i, scale_factor=rmsdata)
-            insert_gains_into_uvcal(uvcal=gains, time=time, polarization=pol, gains_re=w_r, gains_im=w_i)
-            # at the reported parameters, on the data and weights the fit used (the solver still holds them)
-            quality = solver.fit_quality(g_r, g_i) if fit_quality else None
-            errors = None
-            if errs is not None and (errs["with_gains"] or not freeze_model):
-                solver.set_params(g_r, g_i)  # the reported gains (use_min: the minimum's); the fit is over, the next one sets its own
-                errors = solver.fit_errors(ridge=errs["ridge"], model_var=errs["samples"], gain_var=errs["with_gains"], coeffs=not freeze_model)
-                errors["chisq_bl"] = solver.fit_quality(g_r, g_i)["chisq_bl"]
-            _report_slice(hist, gains, time, pol, rmsdata, prob, quality, errors, errs)
-            if fixed is not None:
-                _file_degeneracies(hist, gains, time, pol, errs, degeneracy_entry(fixed, 0, degen))
-            if dspec is not None:
-                ds = solver.delay_spectrum(dspec["op"], dspec["norm_f"], calibrated=dspec["calibrated"], bin_of_bl=dspec["bin_of_bl"],
-                                           nbins=dspec["nbins"], per_baseline=dspec["per_baseline"], g_r=g_r, g_i=g_i)
-                hist["delay_spectrum"] = delay_spectrum_entry(ds, dspec, rmsdata, prob, gains.ant_array)
-        else:
-            echo(f"{datetime.datetime.now()}: Only {frac_unflagged * 100}-percent of data unflagged. Skipping...\n", verbose=verbose)
-            flag_poltime(resid, time=time, polarization=pol)
-            flag_poltime(gains, time=time, polarization=pol)
-            flag_poltime(model, time=time, polarization=pol)
-            pass  # the reference's fit_history[polnum] = "skipped!" (:1309) is overwritten at the end of the pol loop (:1321)
-        if not freeze_model and model_regularization == "post_hoc" and np.any(~model.flag_array[bltsel]):
-            renormalize(
-                uvdata_reference_model=sky_model, uvdata_deconv=model, gains=gains, polarization=pol, time=time,
-                additional_flags=uvdata.flag_array,
-            )
-        carry.update(g_r=g_r, g_i=g_i, fg_r=fg_r, fg_i=fg_i)
-        return hist
+        sl = slice_pipeline.tensorize(cfg, dict(polnum=polnum, pol=pol, time_index=time_index, time=time))
+        if sl is None:
+            return None  # (the reference's fit_history[polnum] = "skipped!" (:1309) is overwritten at the end of the pol loop (:1321))
+        arrs = slice_pipeline.gather([sl])
+        solver = get_solver(prob, dtype)
+        echo(f"Using {str(dtype)} precision.")  # (the lines of fit_gains_and_foregrounds, :447-738, which every fit of the loop prints)
+        echo(f"{datetime.datetime.now()} Provided the following opt_kwargs")
+        for k in opt_kwargs:
+            echo(f"{k}: {opt_kwargs[k]}")
+        OPTIMIZERS[optimizer]  # unknown optimizer -> KeyError, like calibration.py:571
+        slice_pipeline.start(solver, 1, arrs, cfg, handed=carry.get("fitted") if init_guesses_from_previous_time_step else None)
+        echo(f"{datetime.datetime.now()} Performing Gradient Descent...\n", verbose=verbose)
+        result = drive(solver, controls, 1, prob.nbls, maxsteps, tol, use_min, freeze_model, n_profile_steps, profile_log_dir)
+        out = slice_pipeline.report(solver, 1, arrs, cfg, result)
+        carry["fitted"] = out["fitted"]  # (the raw fitted values, whatever fix_degeneracies writes)
+        return slice_pipeline.write(cfg, sl, 0, out)
 
     # one pool for the whole call: its threads (and with them their solvers, get_solver) serve every polarization
     pool = concurrent.futures.ThreadPoolExecutor(max_workers=parallel_fits) if parallel_fits > 1 and len(times) > 1 else None
     for polnum, pol in enumerate(uvdata.get_pols()):
         echo(f"{datetime.datetime.now()} Working on pol {pol}, {polnum + 1} of {uvdata.Npols}...\n", verbose=verbose)
-        fit_history_p = {}
         if pool is not None:
-            futures = {ti: pool.submit(fit_slice, polnum, pol, ti, t, {"first_time": True}) for ti, t in enumerate(times)}
-            for ti, fut in futures.items():
-                hist = fut.result()
-                if hist is not None:
-                    fit_history_p[ti] = hist
+            futures = [pool.submit(fit_slice, polnum, pol, ti, t, {}) for ti, t in enumerate(times)]
+            hists = [fut.result() for fut in futures]
         else:
-            carry = {"first_time": True}
-            for time_index, time in enumerate(times):
-                hist = fit_slice(polnum, pol, time_index, time, carry)
-                if hist is not None:
-                    fit_history_p[time_index] = hist
-        fit_history[polnum] = fit_history_p
+            carry = {}
+            hists = [fit_slice(polnum, pol, ti, t, carry) for ti, t in enumerate(times)]
+        fit_history[polnum] = {ti: hist for ti, hist in enumerate(hists) if hist is not None}
     if pool is not None:
         pool.shutdown()
-    out = _finish_outputs(uvdata, model, resid, gains, fit_history, correct_model, correct_resid)
     _file_gain_std(fit_history, errs, gains)
-    return out
+    return model, resid, gains, fit_history  # (every fitted slice left its write-back in its final state; a skipped one is flagged)
 
 
 def _file_gain_std(fit_history, errs, gains):
@@ -1639,48 +1485,13 @@ def _output_finisher(uvdata, model, resid, gains, correct_model, correct_resid):
 
 
 def _finish_outputs(uvdata, model, resid, gains, fit_history, correct_model, correct_resid):
-    """Every (polarization, time) through _output_finisher: the outputs of calibrate_and_model_tensor."""
+    """Every (polarization, time) through _output_finisher in one go (calibrate_and_model_tensor itself finishes every fitted slice
+    as it is written, ``slice_pipeline.write``; a skipped slice is all flags and zeros, which finishing leaves as they are)."""
     finish = _output_finisher(uvdata, model, resid, gains, correct_model, correct_resid)
     for pnum in range(finish.npols):
         for time in finish.times:
             finish(pnum, time)
     return model, resid, gains, fit_history
-
-
-def _slice_stats(uvdata, bltsel, polnum):
-    """(fraction of unflagged samples, rms of the unflagged visibilities) of one (polarization, time) -- calibration.py:1168-1182
-    -- in one threaded pass over the slice's rows (the reference's boolean fancy indexing copies the slice twice)."""
-    rows = np.where(bltsel)[0]
-    vis, flg = vis3(np.asarray(uvdata.data_array)), vis3(np.asarray(uvdata.flag_array))
-    cnt = np.zeros(len(rows), dtype=np.int64)
-    ssq = np.zeros(len(rows), dtype=np.float64)
-
-    def chunk(lo, hi):
-        keep = ~np.take(flg[:, :, polnum], rows[lo:hi], axis=0)
-        d = np.take(vis[:, :, polnum], rows[lo:hi], axis=0)
-        p = d.real * d.real + d.imag * d.imag
-        cnt[lo:hi] = np.count_nonzero(keep, axis=1)
-        ssq[lo:hi] = np.sum(p * keep, axis=1)
-
-    utils.for_row_chunks(chunk, len(rows))
-    n = int(cnt.sum())
-    frac = n / (uvdata.Nbls * uvdata.Nfreqs)
-    return frac, (float(np.sqrt(ssq.sum() / n)) if n else float("nan"))
-
-
-def _prior_sums(sky_r, sky_i, wgts):
-    """``P_r, P_i = sum w * sky`` (calibration.py:619-625), accumulated in float64 baseline by baseline on the host's cores; the
-    total does not depend on how the rows are chunked."""
-    nb = len(wgts)
-    pr, pi = np.zeros(nb, dtype=np.float64), np.zeros(nb, dtype=np.float64)
-
-    def chunk(lo, hi):
-        w64 = wgts[lo:hi].astype(np.float64)
-        pr[lo:hi] = np.sum(sky_r[lo:hi] * w64, axis=1)
-        pi[lo:hi] = np.sum(sky_i[lo:hi] * w64, axis=1)
-
-    utils.for_row_chunks(chunk, nb)
-    return float(pr.sum()), float(pi.sum())
 
 
 def _lib_max_slices():
@@ -1759,28 +1570,24 @@ def _batch_fitter(prob, nt, dtype, layout, devices, joint=False):
     return cache[key]
 
 
-def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds, ants_map, times, weights, nsamples_in_weights, dtype,
-                        skip_threshold, use_model_snr_weights, optimizer, use_min, freeze_model, tol, maxsteps, n_profile_steps,
-                        profile_log_dir, model_regularization, verbose, max_batch, devices, layout, opt_kwargs, correct_model=True,
-                        correct_resid=False, device_split=None, gain_basis=None, gain_time_basis=None, fit_quality=False,
-                        controls=FitControls(), errs=None, dspec=None, degen=None):
+def _fit_slices_batched(cfg, max_batch):
     """The pol x time loop of calibration.py:1160-1331 with the fits of all unskipped slices issued as batches: per slice
-    exactly the host-side steps of the loop body (skip test :1173-1177, rms scale :1178-1182, tensorize :1184-1233, write-back
-    :1271-1300, post-hoc renormalisation :1311-1319, residual and calibration state of the outputs :1322-1331), the gradient
-    descent of :1244-1269 for up to ``max_batch`` slices at once with per-slice loop control.  Returns ``fit_history``; model,
-    resid and gains are complete when it returns.  ``gain_time_basis`` (``[len(times), L]``): the unskipped times of a polarization
-    are one batch and one JOINT fit (one loop state, loss = the sum over the times; calibrate_and_model_tensor's docstring).
-    ``controls``: the closed-form, robust, Gauss-Newton and L-BFGS keywords of calibrate_and_model_tensor (``fit_loop.FitControls``)."""
-    OPTIMIZERS[optimizer]  # unknown optimizer -> KeyError, like calibration.py:571
-    dtype = np.dtype(dtype)
-    layout = layout or "shared"
-    pols = list(uvdata.get_pols())
+    exactly the host-side steps of the loop body (``slice_pipeline``: skip test :1173-1177, rms scale :1178-1182, tensorize :1184-1233,
+    write-back :1271-1300, post-hoc renormalisation :1311-1319, residual and calibration state of the outputs :1322-1331), the gradient
+    descent of :1244-1269 for up to ``max_batch`` slices at once with per-slice loop control.  ``cfg``: the settings object of
+    ``calibrate_and_model_tensor``.  Returns ``fit_history``; model, resid and gains are complete when it returns.
+    ``cfg.gain_time_basis`` (``[len(times), L]``): the unskipped times of a polarization are one batch and one JOINT fit (one loop state,
+    loss = the sum over the times; calibrate_and_model_tensor's docstring).  ``cfg.controls``: the closed-form, robust, Gauss-Newton and
+    L-BFGS keywords of calibrate_and_model_tensor (``fit_loop.FitControls``)."""
+    OPTIMIZERS[cfg.optimizer]  # unknown optimizer -> KeyError, like calibration.py:571
+    prob, dtype, controls, degen, verbose = cfg.prob, cfg.dtype, cfg.controls, cfg.degen, cfg.verbose
+    gain_basis, freeze_model, use_min, device_split = cfg.gain_basis, cfg.freeze_model, cfg.use_min, cfg.device_split
+    layout = cfg.layout or "shared"
+    pols = list(cfg.uvdata.get_pols())
     fit_history = {polnum: {} for polnum in range(len(pols))}
-    todo = [dict(polnum=polnum, pol=pol, time_index=time_index, time=time) for polnum, pol in enumerate(pols) for time_index, time in enumerate(times)]
-    finish = _output_finisher(uvdata, model, resid, gains, correct_model, correct_resid)
-    devices, chose_devices = _resolve_devices(devices)
-    joint = gain_time_basis is not None
-    cat = lambda parts_: parts_[0] if len(parts_) == 1 else np.concatenate(parts_)  # noqa: E731
+    todo = [dict(polnum=polnum, pol=pol, time_index=time_index, time=time) for polnum, pol in enumerate(pols) for time_index, time in enumerate(cfg.times)]
+    devices, chose_devices = _resolve_devices(cfg.devices)
+    joint = cfg.gain_time_basis is not None
 
     # One batch goes through three stages: prep (host: the slices' rows out of the containers), fit (device), post (host: the model
     # rows and gains back into the containers).  The stages of neighbouring batches overlap -- while the device fits batch k, one
@@ -1788,46 +1595,11 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
     # batches the host work of all but the first and the last disappears behind the fits.  The (polarization, time) slices of
     # different batches are disjoint parts of the containers, so the stages never touch the same rows.
     def prep(candidates):
-        d_r, d_i, w, s_r, s_i, g_r, g_i, r_w = [], [], [], [], [], [], [], []
-        batch = []
-        for sl in candidates:
-            # skip test and rms scale of the slice (:1168-1182)
-            bltsel = np.isclose(uvdata.time_array, sl["time"], atol=1e-7, rtol=0.0)
-            frac_unflagged, sl["rmsdata"] = _slice_stats(uvdata, bltsel, sl["polnum"])
-            if frac_unflagged < skip_threshold:
-                echo(f"{datetime.datetime.now()}: Only {frac_unflagged * 100}-percent of data unflagged. Skipping...\n", verbose=verbose)
-                flag_poltime(resid, time=sl["time"], polarization=sl["pol"])
-                flag_poltime(gains, time=sl["time"], polarization=sl["pol"])
-                flag_poltime(model, time=sl["time"], polarization=sl["pol"])
-                continue
-            batch.append(sl)
-            dr_t, di_t, w_t = _tensorize_flat(uvdata, prob, ants_map, sl["pol"], sl["time"], data_scale_factor=sl["rmsdata"], weights=weights,
-                                              nsamples_in_weights=nsamples_in_weights, dtype=dtype)
-            d_r.append(dr_t)
-            d_i.append(di_t)
-            w.append(w_t)
-            if sky_model is uvdata:  # (the data stand in for the sky model: the same rows)
-                s_r.append(dr_t)
-                s_i.append(di_t)
-                r_w.append(w_t)
-            elif sky_model is not None:
-                sr_t, si_t, sw_t = _tensorize_flat(sky_model, prob, ants_map, sl["pol"], sl["time"], data_scale_factor=sl["rmsdata"], dtype=dtype,
-                                                   **({"weights": weights} if degen is not None else {"want_weights": False}))
-                s_r.append(sr_t)
-                s_i.append(si_t)
-                if degen is not None:  # the reference's weights of fix_degeneracies: the sky model's own, where the data have any
-                    r_w.append(sw_t * (w_t > 0))
-            a, b = tensorize_gains(gains, dtype=dtype, time=sl["time"], polarization=sl["pol"])
-            g_r.append(a)
-            g_i.append(b)
+        batch = [sl for sl in (slice_pipeline.tensorize(cfg, c) for c in candidates) if sl is not None]
         echo(f"{datetime.datetime.now()} {len(batch)} of {len(candidates)} (polarization, time) slices tensorized.\n", verbose=verbose)
-        if not batch:
-            return dict(batch=batch)
-        pri = None
-        if model_regularization == "sum" and not use_model_snr_weights:  # (with model-SNR weights the priors wait for the new weights: fit)
-            pri = np.asarray([_prior_sums(a, b, c) for a, b, c in zip(s_r, s_i, w)])
-        return dict(batch=batch, w=cat(w), d_r=cat(d_r), d_i=cat(d_i), s_r=cat(s_r), s_i=cat(s_i), g_r=cat(g_r), g_i=cat(g_i), pri=pri,
-                    r_w=cat(r_w) if degen is not None else None)
+        arrs = slice_pipeline.gather(batch) if batch else {}
+        # (the slices keep their scalars only: the arrays live on in the batch's, which die with the fit)
+        return dict(arrs, batch=[{k: v for k, v in sl.items() if not isinstance(v, np.ndarray)} for sl in batch])
 
     def fit(batch, arrs, on=None):
         nonlocal devices
@@ -1849,113 +1621,16 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
                           RuntimeWarning, stacklevel=2)
             devices = devices[:1]
             fitter = _batch_fitter(prob, nt, dtype, layout, devices, joint=joint)
-        w_all, d_r, d_i, s_r, s_i = arrs["w"], arrs["d_r"], arrs["d_i"], arrs["s_r"], arrs["s_i"]
-        # tensorize_fg_coeffs x 2 (calibration.py:1219-1233) for every slice: one device pass gives both components (the weights
-        # it masks with are those of set_data; the sky model arrives as the pass's own source rows)
-        fitter.set_data(d_r, d_i, w_all)
-        fitter.init_coeffs(s_r, s_i)
-        _, _, c_r, c_i = fitter.get_params()
-        if _gram_factors(prob):
-            c_r, c_i = _gram_solve(prob, c_r, c_i, nt)
-            fitter.set_params(c_r=c_r, c_i=c_i)
-        if use_model_snr_weights:
-            m_r, m_i = fitter.model()
-            w_new = (np.square(m_r.astype(np.float64)) + np.square(m_i.astype(np.float64))) * w_all
-            for t in range(nt):  # renormalised slice by slice (:1235-1242)
-                rows = slice(t * prob.nbls, (t + 1) * prob.nbls)
-                w_new[rows] /= np.sum(w_new[rows])
-            w_all = w_new.astype(dtype)
-            fitter.set_data(d_r, d_i, w_all)
-        fitter.set_params(arrs["g_r"], arrs["g_i"], c_r, c_i)
-        fitter.set_gain_basis(gain_basis)  # (the fitter is kept between calls: None detaches an earlier call's) g0 = the gains just set
-        if joint:
-            # the rows of the fitted times; no more vectors than times (the first columns: the smoothest sequences)
-            fitter.set_gain_time_basis(gain_time_basis[[sl["time_index"] for sl in batch]][:, :nt])
-        if model_regularization == "sum":
-            # priors of calibration.py:619-625, one pair per slice (accumulated in float64 on the host)
-            nb = prob.nbls
-            pri = arrs["pri"]
-            if pri is None:
-                pri = np.asarray([_prior_sums(s_r[t * nb : (t + 1) * nb], s_i[t * nb : (t + 1) * nb], w_all[t * nb : (t + 1) * nb]) for t in range(nt)])
-            if joint:
-                fitter.set_regularization("sum", float(np.sum(pri[:, 0])), float(np.sum(pri[:, 1])))  # one pair of sums for the one fit
-            else:
-                fitter.set_regularization("sum", pri[:, 0], pri[:, 1])
-        else:
-            fitter.set_regularization(None)
-        fitter.set_optimizer(optimizer, **opt_kwargs)
-        result = drive(fitter, controls, 1 if joint else nt, nt * prob.nbls if joint else prob.nbls, maxsteps, tol, use_min, freeze_model,
-                       n_profile_steps, profile_log_dir, dict(slices=nt))
-        results = result.loops * nt if joint else result.loops  # one loop, one loss history: every time of the fit reports it
-        cur = fitter.get_params(0)
-        best = fitter.get_params(1) if use_min and any(len(r[0]) for r in results) else None
-        if freeze_model:
-            cm_r, cm_i = c_r, c_i  # the coefficients the fit was handed (:730-732)
-        else:
-            cm_r, cm_i = np.array(cur[2]), np.array(cur[3])
-        gm_r, gm_i = np.array(cur[0]), np.array(cur[1])
-        for t, res in enumerate(results):
-            if best is not None and len(res[0]):  # the slice's own minimum (:702-710, :724-728)
-                ga, gb = slice(t * prob.nants, (t + 1) * prob.nants), slice(t * prob.ncoeffs, (t + 1) * prob.ncoeffs)
-                gm_r[ga], gm_i[ga] = best[0][ga], best[1][ga]
-                if not freeze_model:
-                    cm_r[gb], cm_i[gb] = best[2][gb], best[3][gb]
-        # yield_fg_model_array x 2 + insert_model_into_uvdata_tensor (:1271-1292) for every slice from one A c pass
-        fitter.set_params(c_r=cm_r, c_i=cm_i)
-        m_r, m_i = fitter.model()
-        # at the reported parameters (every slice's own minimum with use_min), on the data and weights the fit used
-        quality = fitter.fit_quality(gm_r, gm_i) if fit_quality else None
-        errors = None
-        if errs is not None and (errs["with_gains"] or not freeze_model):
-            fitter.set_params(gm_r, gm_i)  # the reported gains (use_min: every slice's minimum); the fit is over, the next one sets its own
-            errors = fitter.fit_errors(ridge=errs["ridge"], model_var=errs["samples"], gain_var=errs["with_gains"], coeffs=not freeze_model)
-            errors["chisq_bl"] = (quality if quality is not None else fitter.fit_quality(gm_r, gm_i))["chisq_bl"]
-        spectra = None
-        if dspec is not None:  # every slice (a joint fit: every time) has bins of its own: bin_of_bl encodes (t, length bin)
-            spectra = fitter.delay_spectrum(dspec["op"], dspec["norm_f"], calibrated=dspec["calibrated"], bin_of_bl=delay_spectrum_slice_bins(dspec, nt),
-                                            nbins=nt * dspec["nbins"], per_baseline=dspec["per_baseline"], g_r=gm_r, g_i=gm_i)
-        fixed = None
-        if degen is not None:  # last: quality, errors and spectra are those of the fitted parameters (the product they depend on does not change)
-            ref_phase = (arrs["g_r"], arrs["g_i"]) if degen["phase_ref"] else (None, None)
-            fixed = fitter.fix_degeneracies(s_r, s_i, degen["antpos"], ref_w=arrs["r_w"], mode=degen["mode"], iters=degen["iters"], freqs=degen["freqs"],
-                                            g_r=gm_r, g_i=gm_i, gref_r=ref_phase[0], gref_i=ref_phase[1])
-            m_r, m_i, gm_r, gm_i = fixed["model_r"], fixed["model_i"], fixed["g_r"], fixed["g_i"]
+        slice_pipeline.start(fitter, nt, arrs, cfg)
+        result = drive(fitter, controls, 1 if joint else nt, nt * prob.nbls if joint else prob.nbls, cfg.maxsteps, cfg.tol, use_min, freeze_model,
+                       cfg.n_profile_steps, cfg.profile_log_dir, dict(slices=nt))
+        out = slice_pipeline.report(fitter, nt, arrs, cfg, result)
         echo(f"{datetime.datetime.now()} ... fitted.\n", verbose=verbose)
-        return dict(result=result, results=results, m_r=m_r, m_i=m_i, gm_r=gm_r, gm_i=gm_i, quality=quality, errors=errors, spectra=spectra, fixed=fixed)
+        return out
 
     def post(batch, out):
-        for t, (sl, res) in enumerate(zip(batch, out["results"])):
-            rows, ga = slice(t * prob.nbls, (t + 1) * prob.nbls), slice(t * prob.nants, (t + 1) * prob.nants)
-            _insert_model_rows(model, sl["time"], sl["pol"], ants_map, prob, out["m_r"][rows], out["m_i"][rows], scale_factor=sl["rmsdata"])
-            insert_gains_into_uvcal(uvcal=gains, time=sl["time"], polarization=sl["pol"], gains_re=out["gm_r"][ga], gains_im=out["gm_i"][ga])
-            result, loop = out["result"], 0 if joint else t  # (a joint fit is one loop: every time reports it)
-            rb = result.robust
-            if rb is not None:  # the slice's rows of it
-                rb = {"rounds": rb["rounds"][loop], "ndown_bl": rb["ndown_bl"][rows], "scale_bl": rb["scale_bl"][rows]}
-            hist = fit_history[sl["polnum"]][sl["time_index"]] = history_entry(controls, result, loop, dtype, robust=rb)
-            q, e = out["quality"], out["errors"]
-            if q is not None:
-                q = dict(chisq_ant=q["chisq_ant"][ga], wsum_ant=q["wsum_ant"][ga], chisq_bl=q["chisq_bl"][rows], wsum_bl=q["wsum_bl"][rows])
-            if e is not None:
-                coefs = slice(t * prob.ncoeffs, (t + 1) * prob.ncoeffs)
-                e = {k: e[k][{"gain_var": ga, "coeff_var": coefs}.get(k, rows)]
-                     for k in ("coeff_var", "model_var", "leverage_bl", "nsamp_bl", "gain_var", "chisq_bl") if k in e}
-                if "coeff_var" in e:  # (the library counts over the batch: the slice's own are its groups with an all-zero coeff_var)
-                    e["nsingular"] = sum(1 for g in range(prob.ngrps) if not np.any(e["coeff_var"][prob.grp_coff[g] : prob.grp_coff[g + 1]]))
-            _report_slice(hist, gains, sl["time"], sl["pol"], sl["rmsdata"], prob, q, e, errs)  # (before the post-hoc renormalisation, which leaves g_i conj(g_j) m as it is)
-            if out["fixed"] is not None:
-                _file_degeneracies(hist, gains, sl["time"], sl["pol"], errs, degeneracy_entry(out["fixed"], t, degen))
-            if out["spectra"] is not None:
-                hist["delay_spectrum"] = delay_spectrum_entry(delay_spectrum_of_slice(out["spectra"], dspec, t, prob.nbls), dspec, sl["rmsdata"], prob,
-                                                              gains.ant_array)
-            if res[1]:
-                echo(f"Tolerance thresshold met for time {sl['time_index']}. Terminating...\n ", verbose=verbose)
-            if not freeze_model and model_regularization == "post_hoc":  # (:1311-1319)
-                bltsel = np.isclose(uvdata.time_array, sl["time"], atol=1e-7, rtol=0.0)
-                if np.any(~model.flag_array[bltsel]):
-                    renormalize(uvdata_reference_model=sky_model, uvdata_deconv=model, gains=gains, polarization=sl["pol"], time=sl["time"],
-                                additional_flags=uvdata.flag_array)
-            finish(sl["polnum"], sl["time"])  # (:1322-1331)
+        for t, sl in enumerate(batch):
+            fit_history[sl["polnum"]][sl["time_index"]] = slice_pipeline.write(cfg, sl, t, out)
         echo(f"{datetime.datetime.now()} {len(batch)} (polarization, time) slices written back.\n", verbose=verbose)
 
     batches = [todo[lo : lo + max_batch] for lo in range(0, len(todo), max_batch)]
@@ -2059,19 +1734,6 @@ def _fit_slices_batched(uvdata, sky_model, gains, resid, model, prob, corr_inds,
             for f in written:
                 f.result()
     return fit_history
-
-
-def _gram_solve(prob, c_r, c_i, nt=1):
-    """The per-group Gram solves of _init_coeffs for ``nt`` slices of flat coefficients."""
-    c_r = np.asarray(c_r, dtype=np.float64).copy()
-    c_i = np.asarray(c_i, dtype=np.float64).copy()
-    coff = prob.grp_coff
-    for (u, rbs), (gram, grps) in _gram_factors(prob).items():
-        for t in range(nt):
-            idx = t * prob.ncoeffs + coff[grps][None, :] + np.arange(gram.shape[0])[:, None]
-            c_r[idx] = np.linalg.solve(gram, c_r[idx])
-            c_i[idx] = np.linalg.solve(gram, c_i[idx])
-    return c_r, c_i
 
 
 def _blank_copy(uvdata, keep_flags=False):

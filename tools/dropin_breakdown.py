@@ -19,7 +19,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from calamity_amd import batched, cal_utils, calibration, modeling, solver as solver_mod, synthetic  # noqa: E402
+from calamity_amd import batched, cal_utils, calibration, modeling, slice_pipeline, solver as solver_mod, synthetic  # noqa: E402
 from calamity_amd.uvcompat import SimpleUVData  # noqa: E402
 
 TIMES, CALLS = {}, {}
@@ -87,9 +87,9 @@ def main():
 
     timed(modeling, "yield_pbl_dpss_model_comps", "basis_build (DPSS blocks + redundancy grouping)")
     timed(calibration, "tensorize_fg_model_comps_dict", "layout (groups -> ragged problem)")
-    timed(calibration, "tensorize_data", "tensorize_data (data, sky model -> rows)")
+    timed(calibration, "_tensorize_flat", "tensorize_data (data, sky model -> rows)")
     timed(calibration, "tensorize_gains", "tensorize_gains")
-    timed(calibration, "_init_coeffs", "initial coefficients (device A^T d + download)")
+    timed(slice_pipeline, "init_coeffs", "initial coefficients (device A^T d + download)")
     timed(calibration, "_insert_model_rows", "write-back (model rows -> UVData)")
     timed(calibration, "insert_gains_into_uvcal", "write-back (gains -> UVCal)")
     timed(calibration, "insert_fit_quality", "write-back (fit quality -> UVCal, fit history)")
