@@ -92,8 +92,9 @@ class Ref:
         return out
 
     def step(self, g, c, lam=1e-3, ncg=20, cg_tol=1e-3, priors=None):
-        """One damped Gauss-Newton step.  Returns dict(g, c, dg, dc, loss_before, loss_after, accepted, cg_iters, cg_residual);
-        ``g``, ``c`` are the inputs where the step is rejected."""
+        """One damped Gauss-Newton step.  Returns dict(g, c, dg, dc, loss_before, loss_after, accepted, cg_iters, cg_residual, rz0,
+        residuals); ``g``, ``c`` are the inputs where the step is rejected.  ``residuals[k]`` is the relative preconditioned residual
+        sqrt(rz / rz0) after iteration k + 1 (``cg_iters`` entries), ``rz0`` the first res . z."""
         dot = lambda a, b: float(np.sum(a[0].real * b[0].real + a[0].imag * b[0].imag) + np.sum(a[1].real * b[1].real + a[1].imag * b[1].imag))  # noqa: E731
         rhs, D = self.rhs(g, c), self.precond(g, c)
         x = [np.zeros_like(g), np.zeros_like(c)]
@@ -101,7 +102,7 @@ class Ref:
         z = [res[0] / D[0], res[1] / D[1]]
         s = [z[0].copy(), z[1].copy()]
         rz = rz0 = dot(res, z)
-        iters, resid = 0, 0.0
+        iters, resid, trace = 0, 0.0, []
         if rz0 > 0 and np.isfinite(rz0):
             resid = 1.0
             for _ in range(ncg):
@@ -118,6 +119,7 @@ class Ref:
                 rz_new = dot(res, z)
                 iters += 1
                 resid = float(np.sqrt(rz_new / rz0))
+                trace.append(resid)
                 if not np.isfinite(rz_new) or resid <= cg_tol:
                     break
                 beta = rz_new / rz
@@ -128,7 +130,7 @@ class Ref:
         after = self.loss(g + x[0], c + x[1], priors)
         ok = bool(np.isfinite(after) and after < before)
         return dict(g=g + x[0] if ok else g, c=c + x[1] if ok else c, dg=x[0], dc=x[1], loss_before=before, loss_after=after, accepted=ok,
-                    cg_iters=iters, cg_residual=resid)
+                    cg_iters=iters, cg_residual=resid, rz0=rz0, residuals=tuple(trace))
 
 
 def dense_normal_matrix(ref, g, c):
