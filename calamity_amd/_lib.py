@@ -173,6 +173,18 @@ class LbfgsResult(C.Structure):
                 ("status", C.c_int32)]
 
 
+class MixedCompsDesc(C.Structure):
+    """cal_mixed_comps_desc (include/calamity_hip.h: cal_mixed_comps_create): grp_bl_start [ngroups + 1] int32 into uvw [.][3] float64,
+    freqs [nfreqs] float64, grp_freq_start NULL (every group has all channels) or [ngroups + 1] int32 into freqs, the four parameters of
+    simple_cov_matrix, tol > 0, the scratch bound in bytes (0: 256 MiB)."""
+    _fields_ = [("ngroups", C.c_int32), ("nfreqs", C.c_int32), ("grp_bl_start", C.c_void_p), ("uvw", C.c_void_p), ("freqs", C.c_void_p),
+                ("grp_freq_start", C.c_void_p), ("ant_dly", C.c_double), ("horizon", C.c_double), ("offset", C.c_double), ("min_dly", C.c_double), ("tol", C.c_double),
+                ("scratch_bytes", C.c_int64)]
+
+
+MIXED_COMPS_STATUS = ("ok", "rank cap", "not run")
+
+
 class RunResult(C.Structure):
     _fields_ = [("nrecorded", C.c_int32), ("stopped", C.c_int32), ("nupdates", C.c_int32), ("nonfinite", C.c_int32)]
 
@@ -242,6 +254,13 @@ SYMBOLS = {
     "cal_solver_solve_gain_time_coeffs": (C.c_int, [_P, C.POINTER(GainTimeSolveDesc), C.POINTER(GainTimeSolveResult)]),
     "cal_solver_get_gain_coeff_moments": (C.c_int, [_P] + [_P] * 8 + [C.POINTER(C.c_int64)]),
     "cal_weighted_square_error": (C.c_int, [C.c_int, C.c_int, C.c_int64, _P, _P, _P, _P, _P, C.POINTER(C.c_double)]),
+    "cal_mixed_comps_create": (C.c_int, [C.POINTER(_P), C.c_int, C.POINTER(MixedCompsDesc)]),
+    "cal_mixed_comps_destroy": (C.c_int, [_P]),
+    "cal_mixed_comps_info": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    "cal_mixed_comps_gram": (C.c_int, [_P, _P, C.c_int64]),
+    "cal_mixed_comps_vectors": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.POINTER(C.c_double)]),
+    "cal_mixed_comps_factor": (C.c_int, [_P, C.c_int32, _P, _P]),
+    "cal_simple_cov_matrix": (C.c_int, [C.c_int, C.c_int32, _P, C.c_int32, _P, C.c_double, C.c_double, C.c_double, C.c_double, _P]),
     "cal_solver_init_coeffs": (C.c_int, [_P, _P, _P]),
     "cal_solver_synchronize": (C.c_int, [_P]),
     "cal_solver_set_launch_mode": (C.c_int, [_P, C.c_int]),

@@ -1809,6 +1809,18 @@ def calibrate_and_model_dpss(
     return model, resid, gains, fitted_info
 
 
+def _modeling_comps_device(use_device, devices):
+    """The ``device`` of ``modeling.yield_mixed_comps`` for ``use_tensorflow_to_derive_modeling_comps``: None (the host) when the flag is
+    off; else the first entry of ``devices`` when there is one, else 0."""
+    if not use_device:
+        return None
+    if devices is None or isinstance(devices, str):  # ("all": every visible GPU, the first of which is 0)
+        return 0
+    if isinstance(devices, (int, np.integer)):
+        return int(devices)
+    return int(devices[0]) if len(devices) else 0
+
+
 def calibrate_and_model_mixed(
     uvdata,
     horizon=1.0,
@@ -1842,8 +1854,9 @@ def calibrate_and_model_mixed(
 ):
     """Gains + foregrounds with DPSS vectors for baselines without frequency redundancy and joint covariance
     eigenvectors for groups of baselines whose uv tracks overlap -- calibration.py:1353-1500 (same signature and
-    returns).  ``use_tensorflow_to_derive_modeling_comps`` is accepted for compatibility; the eigenproblems run on the
-    host either way.  The ``delay_spectrum`` and ``fix_degeneracies`` / ``degeneracy_*`` keywords are ``calibrate_and_model_tensor``'s."""
+    returns).  ``use_tensorflow_to_derive_modeling_comps=True`` derives the joint groups' modeling vectors on the GPU
+    (``modeling.yield_mixed_comps(device=...)``: the first entry of ``devices`` when one is given, else device 0); the default derives
+    them on the host.  The ``delay_spectrum`` and ``fix_degeneracies`` / ``degeneracy_*`` keywords are ``calibrate_and_model_tensor``'s."""
     _check_delay_spectrum(delay_spectrum, delay_spectrum_taper, delay_spectrum_max_dly, delay_spectrum_bllen_bin)
     _check_degeneracy_call(fix_degeneracies, degeneracy_iters, fitting_kwargs)
     fitting_grps, blvecs, _, _ = modeling.get_uv_overlapping_grps_conjugated(
@@ -1858,7 +1871,7 @@ def calibrate_and_model_mixed(
             model_comps_dict = modeling.yield_mixed_comps(
                 fitting_grps, blvecs, freqs, eigenval_cutoff=eigenval_cutoff, ant_dly=ant_dly, horizon=horizon, offset=offset,
                 min_dly=min_dly, verbose=verbose, dtype=dtype_matinv, notebook_progressbar=notebook_progressbar,
-                grp_size_threshold=grp_size_threshold,
+                grp_size_threshold=grp_size_threshold, device=_modeling_comps_device(use_tensorflow_to_derive_modeling_comps, fitting_kwargs.get("devices")),
             )
         finally:
             waker.join()

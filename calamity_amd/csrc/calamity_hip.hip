@@ -37,6 +37,7 @@
 #include "gain_time_solve_kernels.hpp"
 #include "gauss_newton_kernels.hpp"
 #include "lbfgs_kernels.hpp"
+#include "mixed_comps_kernels.hpp"
 #include "solve_plan.hpp"  // (and problem_plan.hpp)
 #include "step_plan.hpp"
 #include "report_plan.hpp"
@@ -3124,7 +3125,419 @@ int debug_report_plan(const cal_problem_desc* d, const cal_report_plan_desc* r, 
 }
 }  // namespace
 
+// ================================================================================================================
+// cal_mixed_comps_*, cal_simple_cov_matrix: the kernels of mixed_comps_kernels.hpp
+namespace {
+int mx_use_device(int device, const char* who) {
+  int ndev = 0;
+  hipError_t e = hipGetDeviceCount(&ndev);
+  if (e != hipSuccess || ndev <= 0)
+    return fail(CAL_ERR_HIP, "no usable HIP device (%s); this library has no CPU fallback", e == hipSuccess ? "0 devices" : hipGetErrorString(e));
+  if (device < 0 || device >= ndev) return fail(CAL_ERR_INVALID, "%s: device %d out of range [0, %d)", who, device, ndev);
+  HIP_TRY(hipSetDevice(device));
+  return CAL_OK;
+}
+// (u, v, w, nu) of every sample of nbls baselines on nfreqs channels, baseline-major, appended to `out`: pts = uvw * (nu / 3e8) as
+// simple_cov_matrix forms it
+int mx_samples(const char* who, int64_t nbls, const double* uvw, int32_t nfreqs, const double* freqs, std::vector<double>& out) {
+  for (int64_t x = 0; x < nbls * 3; ++x)
+    if (!std::isfinite(uvw[x])) return fail(CAL_ERR_INVALID, "%s: uvw is not finite", who);
+  for (int32_t f = 0; f < nfreqs; ++f)
+    if (!std::isfinite(freqs[f])) return fail(CAL_ERR_INVALID, "%s: freqs is not finite", who);
+  size_t o = out.size();
+  out.resize(o + (size_t)nbls * nfreqs * 4);
+  for (int64_t a = 0; a < nbls; ++a)
+    for (int32_t f = 0; f < nfreqs; ++f) {
+      const double s = freqs[f] / 3e8;
+      out[o++] = uvw[3 * a] * s;
+      out[o++] = uvw[3 * a + 1] * s;
+      out[o++] = uvw[3 * a + 2] * s;
+      out[o++] = freqs[f];
+    }
+  return CAL_OK;
+}
+bool mx_params_ok(double ant_dly, double horizon, double offset, double min_dly) {
+  return std::isfinite(ant_dly) && std::isfinite(horizon) && std::isfinite(offset) && std::isfinite(min_dly);
+}
+long long mx_group_bytes(int ldl, int nblk, int cap) {  // a group's share of a chunk's scratch at rank cap `cap`
+  return (long long)ldl * ((cap + 15) / 16 * 16) * 8 + (long long)ldl * 8 + 2ll * nblk * (long long)sizeof(MxPart) + (long long)cap * 4;
+}
+struct MxEvents {
+  hipEvent_t e[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  ~MxEvents() {
+    for (hipEvent_t x : e)
+      if (x) (void)hipEventDestroy(x);
+  }
+  int create() {
+    for (hipEvent_t& x : e) HIP_TRY(hipEventCreate(&x));
+    return CAL_OK;
+  }
+};
+constexpr int kMxStepsPerRead = 32;  // steps enqueued between two reads of the chunk's count of finished groups
+}  // namespace
+
+struct cal_mixed_comps {
+  int device = 0;
+  hipStream_t st = nullptr;
+  MxParams P{};
+  double tol = 0;
+  std::vector<MxGroup> grps;                 // every group of the call, L the compact factor
+  std::vector<std::unique_ptr<DevBuf>> Lc;   // [ldl][kpad] per group
+  std::vector<std::vector<int>> piv;
+  std::vector<int> status, chunk;  // chunk: the chunk a group was factored in
+  std::vector<double> maxd, resid_fro, G;
+  DevBuf samples, dev_grps;
+  double ms[3] = {0, 0, 0};  // factor, Gram, certificate
+  ~cal_mixed_comps() {
+    if (st) (void)hipStreamDestroy(st);
+  }
+
+  int upload_groups() {
+    CAL_TRY(dev_grps.reserve(grps.size() * sizeof(MxGroup), false));
+    HIP_TRY(hipMemcpyAsync(dev_grps.p, grps.data(), grps.size() * sizeof(MxGroup), hipMemcpyHostToDevice, st));
+    return CAL_OK;
+  }
+
+  int run(const cal_mixed_comps_desc* d) {
+    const char* who = "cal_mixed_comps_create";
+    const int ng = d->ngroups;
+    const int64_t bound = d->scratch_bytes == 0 ? kCsScratchDefault : d->scratch_bytes;
+    P = MxParams{d->ant_dly, d->horizon, d->offset, d->min_dly};
+    tol = d->tol;
+    // a group's channels: all nfreqs of them, or its own piece [grp_freq_start[g], grp_freq_start[g + 1]) of freqs
+    auto f0 = [&](int g) { return d->grp_freq_start ? d->grp_freq_start[g] : 0; };
+    auto f1 = [&](int g) { return d->grp_freq_start ? d->grp_freq_start[g + 1] : d->nfreqs; };
+    std::vector<double> smp;
+    std::vector<long long> s_off(ng + 1, 0);
+    for (int g = 0; g < ng; ++g) {
+      const int64_t nb = (int64_t)d->grp_bl_start[g + 1] - d->grp_bl_start[g];
+      if (nb <= 0 || d->grp_bl_start[0] != 0) return fail(CAL_ERR_INVALID, "%s: grp_bl_start must start at 0 and ascend", who);
+      if (f0(g) < 0 || f1(g) <= f0(g) || f1(g) > d->nfreqs) return fail(CAL_ERR_INVALID, "%s: grp_freq_start must ascend within [0, nfreqs]", who);
+      if (nb * (f1(g) - f0(g)) > (1 << 22)) return fail(CAL_ERR_INVALID, "%s: a group holds at most 2^22 samples", who);
+      CAL_TRY(mx_samples(who, nb, d->uvw + 3 * (size_t)d->grp_bl_start[g], f1(g) - f0(g), d->freqs + f0(g), smp));
+      s_off[g + 1] = (long long)(smp.size() / 4);
+    }
+    HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    CAL_TRY(samples.alloc(smp.size() * sizeof(double), false));
+    HIP_TRY(hipMemcpyAsync(samples.p, smp.data(), smp.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    grps.assign(ng, MxGroup{});
+    Lc.resize(ng);
+    piv.resize(ng);
+    status.assign(ng, MX_NOT_RUN);
+    chunk.assign(ng, 0);
+    maxd.assign(ng, 0.0);
+    resid_fro.assign(ng, 0.0);
+    for (int g = 0; g < ng; ++g) {
+      MxGroup& q = grps[g];
+      q.n = (int)(s_off[g + 1] - s_off[g]);
+      q.ldl = (q.n + 63) / 64 * 64;
+      q.nblk = (q.n + kMxRows - 1) / kMxRows;
+      q.s_off = s_off[g];
+      // what the group asks of the bound: a third of its order (the ranks of these matrices stay below a quarter); what it gets alone
+      // in a chunk when that does not fit: the columns the bound holds, in sixteens
+      q.cap = std::min(std::min(q.n, kMxMaxCap), std::max(64, (q.n + 2) / 3));
+      if (mx_group_bytes(q.ldl, q.nblk, q.cap) > bound) {
+        const long long fixed = mx_group_bytes(q.ldl, q.nblk, 0);
+        const long long cols = bound > fixed ? (bound - fixed) / ((long long)q.ldl * 8 + 4) : 0;
+        q.cap = (int)std::min<long long>(q.cap, cols / 16 * 16);
+      }
+    }
+    MxEvents ev;
+    CAL_TRY(ev.create());
+    HIP_TRY(hipEventRecord(ev.e[0], st));
+    DevBuf scratch, d_work, d_state;
+    int nchunks = 0;
+    for (int g0 = 0; g0 < ng;) {
+      // the chunk: consecutive groups while their shares fit the bound (a group alone always fits: its cap was cut to it)
+      int g1 = g0;
+      long long bytes = 0;
+      while (g1 < ng && (g1 == g0 || bytes + mx_group_bytes(grps[g1].ldl, grps[g1].nblk, grps[g1].cap) <= bound)) {
+        bytes += mx_group_bytes(grps[g1].ldl, grps[g1].nblk, grps[g1].cap);
+        ++g1;
+      }
+      std::vector<int> run_g;  // groups of the chunk that have a column to compute
+      for (int g = g0; g < g1; ++g) chunk[g] = nchunks;
+      ++nchunks;
+      for (int g = g0; g < g1; ++g)
+        if (grps[g].cap >= 1) run_g.push_back(g);
+      if (!run_g.empty()) {
+        CAL_TRY(scratch.reserve((size_t)bytes + 256 * run_g.size(), false));
+        HIP_TRY(hipMemsetAsync(scratch.p, 0, scratch.bytes, st));
+        std::vector<MxGroup> cg;
+        std::vector<int2> work;
+        char* base = scratch.as<char>();
+        size_t off = 0;
+        int maxcap = 0;
+        auto take = [&](size_t nbytes) {
+          char* ptr = base + off;
+          off += (nbytes + 63) / 64 * 64;
+          return ptr;
+        };
+        for (int g : run_g) {
+          MxGroup q = grps[g];
+          q.L = reinterpret_cast<double*>(take((size_t)q.ldl * ((q.cap + 15) / 16 * 16) * 8));
+          q.d = reinterpret_cast<double*>(take((size_t)q.ldl * 8));
+          maxcap = std::max(maxcap, q.cap);
+          for (int b = 0; b < q.nblk; ++b) work.push_back(int2{(int)cg.size(), b});
+          cg.push_back(q);
+        }
+        for (MxGroup& q : cg) q.part = reinterpret_cast<MxPart*>(take(2 * (size_t)q.nblk * sizeof(MxPart)));  // two buffers, by step parity
+        for (MxGroup& q : cg) q.piv = reinterpret_cast<int*>(take((size_t)q.cap * 4));
+        if (off > scratch.bytes) return fail(CAL_ERR_STATE, "%s: the chunk's plan (%zu bytes) exceeds its scratch (%zu)", who, off, scratch.bytes);
+        const int nc = (int)cg.size();
+        CAL_TRY(d_work.reserve(work.size() * sizeof(int2) + cg.size() * sizeof(MxGroup), false));
+        CAL_TRY(d_state.reserve(nc * sizeof(MxState) + 64, false));
+        MxGroup* dg = reinterpret_cast<MxGroup*>(d_work.as<char>() + work.size() * sizeof(int2));
+        HIP_TRY(hipMemcpyAsync(d_work.p, work.data(), work.size() * sizeof(int2), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(dg, cg.data(), cg.size() * sizeof(MxGroup), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(d_state.p, 0, d_state.bytes, st));
+        MxState* dstate = d_state.as<MxState>();
+        int* dn = reinterpret_cast<int*>(d_state.as<char>() + (size_t)nc * sizeof(MxState));
+        const dim3 grid((unsigned)work.size());
+        hipLaunchKernelGGL(mixed_init_kernel, grid, dim3(256), 0, st, dg, d_work.as<int2>(), samples.as<double4>(), P);
+        int ndone = 0;
+        for (int step = 0; step <= maxcap && ndone < nc;) {  // step == cap is the launch that records a group at its cap
+          const int to = std::min(maxcap + 1, step + kMxStepsPerRead);
+          for (; step < to; ++step)
+            hipLaunchKernelGGL(mixed_step_kernel, grid, dim3(256), (size_t)maxcap * 8, st, dg, d_work.as<int2>(), samples.as<double4>(), dstate, dn, P, tol,
+                               step);
+          HIP_TRY(hipGetLastError());
+          HIP_TRY(hipMemcpyAsync(&ndone, dn, sizeof(int), hipMemcpyDeviceToHost, st));
+          HIP_TRY(hipStreamSynchronize(st));
+        }
+        if (ndone != nc) return fail(CAL_ERR_STATE, "%s: %d of %d groups finished within their caps", who, ndone, nc);
+        std::vector<MxState> hs(nc);
+        HIP_TRY(hipMemcpyAsync(hs.data(), dstate, nc * sizeof(MxState), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (int c = 0; c < nc; ++c) {
+          const int g = run_g[c];
+          MxGroup& q = grps[g];
+          q.k = hs[c].k;
+          q.kpad = std::max(16, (q.k + 15) / 16 * 16);
+          if (q.k < 0 || q.k > q.cap) return fail(CAL_ERR_STATE, "%s: group %d reports rank %d at cap %d", who, g, q.k, q.cap);
+          status[g] = hs[c].status;
+          maxd[g] = hs[c].maxd;
+          Lc[g] = std::make_unique<DevBuf>();
+          // (column-major: the first kpad columns are one piece; kpad <= the cap rounded up to 16, and columns [k, kpad) were never written)
+          const size_t lbytes = (size_t)q.ldl * std::min(q.kpad, (q.cap + 15) / 16 * 16) * 8;
+          CAL_TRY(Lc[g]->alloc((size_t)q.ldl * q.kpad * 8, true));
+          HIP_TRY(hipMemcpyAsync(Lc[g]->p, cg[c].L, lbytes, hipMemcpyDeviceToDevice, st));
+          piv[g].resize(q.k);
+          if (q.k) HIP_TRY(hipMemcpyAsync(piv[g].data(), cg[c].piv, (size_t)q.k * 4, hipMemcpyDeviceToHost, st));
+          q.L = Lc[g]->as<double>();
+        }
+        HIP_TRY(hipStreamSynchronize(st));
+      }
+      g0 = g1;
+    }
+    scratch.release();
+    HIP_TRY(hipEventRecord(ev.e[1], st));
+    // G of every factored group in one launch, one buffer, one download; then the certificate the same way
+    std::vector<MxWork> gw, cw;
+    long long g_total = 0, c_total = 0;
+    for (int g = 0; g < ng; ++g) {
+      MxGroup& q = grps[g];
+      q.d = nullptr;
+      q.part = nullptr;
+      q.piv = nullptr;
+      q.g_off = g_total;
+      q.c_off = c_total;
+      if (status[g] == MX_NOT_RUN) continue;
+      g_total += (long long)q.k * q.k;
+      const int nb = (q.k + kNsBlock - 1) / kNsBlock, nt = (q.n + kMxTile - 1) / kMxTile;
+      for (int bi = 0; bi < nb; ++bi)
+        for (int bj = 0; bj <= bi; ++bj) gw.push_back(MxWork{g, bi, bj});
+      for (int bi = 0; bi < nt; ++bi)
+        for (int bj = 0; bj <= bi; ++bj) cw.push_back(MxWork{g, bi, bj});
+      c_total += (long long)nt * (nt + 1) / 2;
+    }
+    CAL_TRY(upload_groups());
+    G.assign((size_t)g_total, 0.0);
+    std::vector<double> r2(ng, 0.0);
+    DevBuf d_G, d_c, d_r2;
+    CAL_TRY(d_G.alloc((size_t)g_total * 8, true));
+    CAL_TRY(d_c.alloc((size_t)c_total * 8, true));
+    CAL_TRY(d_r2.alloc((size_t)ng * 8, true));
+    HIP_TRY(hipEventRecord(ev.e[2], st));
+    if (!gw.empty()) {
+      CAL_TRY(d_work.reserve(gw.size() * sizeof(MxWork), false));
+      HIP_TRY(hipMemcpyAsync(d_work.p, gw.data(), gw.size() * sizeof(MxWork), hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL(mixed_gram_kernel, dim3((unsigned)gw.size()), dim3(256), 0, st, dev_grps.as<MxGroup>(), d_work.as<MxWork>(), d_G.as<double>());
+      HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(ev.e[3], st));
+    HIP_TRY(hipStreamSynchronize(st));  // (d_work is reused)
+    HIP_TRY(hipEventRecord(ev.e[4], st));
+    if (!cw.empty()) {
+      CAL_TRY(d_work.reserve(cw.size() * sizeof(MxWork), false));
+      HIP_TRY(hipMemcpyAsync(d_work.p, cw.data(), cw.size() * sizeof(MxWork), hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL(mixed_cert_kernel, dim3((unsigned)cw.size()), dim3(256), 0, st, dev_grps.as<MxGroup>(), d_work.as<MxWork>(), samples.as<double4>(), P,
+                         d_c.as<double>());
+      hipLaunchKernelGGL(mixed_cert_sum_kernel, dim3(ng), dim3(256), 0, st, dev_grps.as<MxGroup>(), d_c.as<double>(), d_r2.as<double>());
+      HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(ev.e[5], st));
+    if (g_total) HIP_TRY(hipMemcpyAsync(G.data(), d_G.p, (size_t)g_total * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(r2.data(), d_r2.p, (size_t)ng * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int g = 0; g < ng; ++g) {
+      resid_fro[g] = status[g] == MX_NOT_RUN ? 0.0 : std::sqrt(r2[g]);
+      if (status[g] == MX_NOT_RUN) continue;
+      // normal_gram_store leaves the lower triangle: mirror it
+      double* Gg = G.data() + grps[g].g_off;
+      const int k = grps[g].k;
+      for (int i = 0; i < k; ++i)
+        for (int j = i + 1; j < k; ++j) Gg[(size_t)i * k + j] = Gg[(size_t)j * k + i];
+    }
+    for (int x = 0; x < 3; ++x) {
+      float t = 0;
+      HIP_TRY(hipEventElapsedTime(&t, ev.e[2 * x], ev.e[2 * x + 1]));
+      ms[x] = t;
+    }
+    return CAL_OK;
+  }
+
+  template <typename T>
+  int vectors(const int32_t* nkeep, const double* U, const double* scale, void* V, double* ms_out) {
+    const int ng = (int)grps.size();
+    std::vector<MxWork> work;
+    long long u_total = 0, s_total = 0, v_total = 0;
+    for (int g = 0; g < ng; ++g) {
+      MxGroup& q = grps[g];
+      if (nkeep[g] < 0 || nkeep[g] > q.k || (nkeep[g] > 0 && status[g] == MX_NOT_RUN))
+        return fail(CAL_ERR_INVALID, "cal_mixed_comps_vectors: group %d keeps %d of %d vectors", g, nkeep[g], q.k);
+      q.r = nkeep[g];
+      q.u_off = u_total;
+      q.sc_off = s_total;
+      q.v_off = v_total;
+      u_total += (long long)q.k * q.r;
+      s_total += q.r;
+      v_total += (long long)q.n * q.r;
+      if (q.r == 0) continue;
+      for (int bi = 0; bi < (q.n + kMxTile - 1) / kMxTile; ++bi)
+        for (int bj = 0; bj < (q.r + kMxTile - 1) / kMxTile; ++bj) work.push_back(MxWork{g, bi, bj});
+    }
+    if (ms_out) *ms_out = 0.0;
+    if (work.empty()) return CAL_OK;
+    CAL_TRY(upload_groups());
+    DevBuf d_u, d_v, d_work;
+    MxEvents ev;
+    CAL_TRY(ev.create());
+    CAL_TRY(d_u.alloc((size_t)(u_total + s_total) * 8, false));
+    CAL_TRY(d_v.alloc((size_t)v_total * sizeof(T), false));
+    CAL_TRY(d_work.alloc(work.size() * sizeof(MxWork), false));
+    HIP_TRY(hipMemcpyAsync(d_u.p, U, (size_t)u_total * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_u.as<double>() + u_total, scale, (size_t)s_total * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_work.p, work.data(), work.size() * sizeof(MxWork), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(ev.e[0], st));
+    hipLaunchKernelGGL(mixed_backmul_kernel<T>, dim3((unsigned)work.size()), dim3(256), 0, st, dev_grps.as<MxGroup>(), d_work.as<MxWork>(), d_u.as<double>(),
+                       d_u.as<double>() + u_total, d_v.as<T>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev.e[1], st));
+    HIP_TRY(hipMemcpyAsync(V, d_v.p, (size_t)v_total * sizeof(T), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    float t = 0;
+    HIP_TRY(hipEventElapsedTime(&t, ev.e[0], ev.e[1]));
+    if (ms_out) *ms_out = t;
+    return CAL_OK;
+  }
+};
+
 extern "C" {
+
+int cal_mixed_comps_create(cal_mixed_comps** out, int device, const cal_mixed_comps_desc* d) {
+  const char* who = "cal_mixed_comps_create";
+  if (!out) return fail(CAL_ERR_INVALID, "%s: null handle pointer", who);
+  *out = nullptr;
+  if (!d || d->ngroups < 1 || d->nfreqs < 1 || !d->grp_bl_start || !d->uvw || !d->freqs) return fail(CAL_ERR_INVALID, "%s: the description needs groups, uvw and freqs", who);
+  if (!mx_params_ok(d->ant_dly, d->horizon, d->offset, d->min_dly)) return fail(CAL_ERR_INVALID, "%s: ant_dly, horizon, offset and min_dly must be finite", who);
+  if (!(d->tol > 0.0) || !std::isfinite(d->tol)) return fail(CAL_ERR_INVALID, "%s: tol must be finite and > 0", who);
+  if (d->scratch_bytes < 0) return fail(CAL_ERR_INVALID, "%s: negative scratch bound", who);
+  CAL_TRY(mx_use_device(device, who));
+  std::unique_ptr<cal_mixed_comps> h(new cal_mixed_comps());
+  h->device = device;
+  CAL_TRY(h->run(d));
+  *out = h.release();
+  return CAL_OK;
+}
+
+int cal_mixed_comps_destroy(cal_mixed_comps* h) {
+  if (!h) return fail(CAL_ERR_INVALID, "cal_mixed_comps_destroy: null handle");
+  (void)hipSetDevice(h->device);
+  delete h;
+  return CAL_OK;
+}
+
+int cal_mixed_comps_info(cal_mixed_comps* h, int32_t* rank, int32_t* status, int32_t* chunk, double* max_d, double* resid_fro, double* times_ms) {
+  if (!h) return fail(CAL_ERR_INVALID, "cal_mixed_comps_info: null handle");
+  for (size_t g = 0; g < h->grps.size(); ++g) {
+    if (rank) rank[g] = h->grps[g].k;
+    if (status) status[g] = h->status[g];
+    if (chunk) chunk[g] = h->chunk[g];
+    if (max_d) max_d[g] = h->maxd[g];
+    if (resid_fro) resid_fro[g] = h->resid_fro[g];
+  }
+  if (times_ms) memcpy(times_ms, h->ms, sizeof(h->ms));
+  return CAL_OK;
+}
+
+int cal_mixed_comps_gram(cal_mixed_comps* h, double* G, int64_t cap_doubles) {
+  if (!h || !G) return fail(CAL_ERR_INVALID, "cal_mixed_comps_gram: null argument");
+  if ((int64_t)h->G.size() > cap_doubles) return fail(CAL_ERR_INVALID, "cal_mixed_comps_gram: G has %lld doubles, the buffer %lld", (long long)h->G.size(), (long long)cap_doubles);
+  if (!h->G.empty()) memcpy(G, h->G.data(), h->G.size() * 8);
+  return CAL_OK;
+}
+
+int cal_mixed_comps_vectors(cal_mixed_comps* h, int dtype, const int32_t* nkeep, const double* U, const double* scale, void* V, double* ms) {
+  if (!h || !nkeep || !U || !scale || !V) return fail(CAL_ERR_INVALID, "cal_mixed_comps_vectors: null argument");
+  if (dtype != CAL_F32 && dtype != CAL_F64) return fail(CAL_ERR_INVALID, "cal_mixed_comps_vectors: unknown dtype %d", dtype);
+  HIP_TRY(hipSetDevice(h->device));
+  return dtype == CAL_F32 ? h->vectors<float>(nkeep, U, scale, V, ms) : h->vectors<double>(nkeep, U, scale, V, ms);
+}
+
+int cal_mixed_comps_factor(cal_mixed_comps* h, int32_t group, double* L, int32_t* pivots) {
+  if (!h || group < 0 || group >= (int32_t)h->grps.size()) return fail(CAL_ERR_INVALID, "cal_mixed_comps_factor: no such group");
+  const MxGroup& q = h->grps[group];
+  if (h->status[group] == MX_NOT_RUN || q.k == 0) return CAL_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  if (L) {  // (on the handle's stream, not the legacy one: see cal_simple_cov_matrix)
+    HIP_TRY(hipMemcpy2DAsync(L, (size_t)q.n * 8, q.L, (size_t)q.ldl * 8, (size_t)q.n * 8, (size_t)q.k, hipMemcpyDeviceToHost, h->st));
+    HIP_TRY(hipStreamSynchronize(h->st));
+  }
+  if (pivots) memcpy(pivots, h->piv[group].data(), (size_t)q.k * 4);
+  return CAL_OK;
+}
+
+int cal_simple_cov_matrix(int device, int32_t nbls, const double* uvw, int32_t nfreqs, const double* freqs, double ant_dly, double horizon, double offset,
+                          double min_dly, double* C) {
+  const char* who = "cal_simple_cov_matrix";
+  if (nbls < 1 || nfreqs < 1 || !uvw || !freqs || !C) return fail(CAL_ERR_INVALID, "%s: bad argument", who);
+  if (!mx_params_ok(ant_dly, horizon, offset, min_dly)) return fail(CAL_ERR_INVALID, "%s: ant_dly, horizon, offset and min_dly must be finite", who);
+  const int64_t n = (int64_t)nbls * nfreqs;
+  if (n > 46340) return fail(CAL_ERR_INVALID, "%s: %lld samples: the dense matrix is for orders up to 46340", who, (long long)n);
+  CAL_TRY(mx_use_device(device, who));
+  std::vector<double> smp;
+  CAL_TRY(mx_samples(who, nbls, uvw, nfreqs, freqs, smp));
+  DevBuf d_s, d_c;
+  CAL_TRY(d_s.alloc(smp.size() * 8, false));
+  CAL_TRY(d_c.alloc((size_t)n * n * 8, false));
+  hipStream_t st;  // (its own stream: the legacy stream would synchronise with a solver that captures a graph on another thread)
+  HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  int rc = CAL_OK;
+  auto step = [&](hipError_t e, const char* what) {
+    if (rc == CAL_OK && e != hipSuccess) rc = fail(CAL_ERR_HIP, "%s: %s failed: %s", who, what, hipGetErrorString(e));
+  };
+  step(hipMemcpyAsync(d_s.p, smp.data(), smp.size() * 8, hipMemcpyHostToDevice, st), "upload");
+  if (rc == CAL_OK) {
+    hipLaunchKernelGGL(mixed_dense_kernel, dim3(grid_for(n * n)), dim3(256), 0, st, d_s.as<double4>(), (int)n, MxParams{ant_dly, horizon, offset, min_dly},
+                       d_c.as<double>());
+    step(hipGetLastError(), "launch");
+    step(hipMemcpyAsync(C, d_c.p, (size_t)n * n * 8, hipMemcpyDeviceToHost, st), "download");
+    step(hipStreamSynchronize(st), "synchronize");
+  }
+  (void)hipStreamDestroy(st);
+  return rc;
+}
 
 
 #ifdef CAL_STAMP

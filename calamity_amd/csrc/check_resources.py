@@ -19,7 +19,9 @@ shared Gram and Cholesky core of normal_solve.hpp), `gain_time_kron_kernel`, `ga
 `dspec_rows_kernel`, `dspec_transform_kernel`, `dspec_bin_kernel` (delay_spectrum_kernels.hpp), both dtypes: no scratch, no spilled VGPRs, and
 two waves per SIMD in the transform kernel.
 `degen_rows_kernel`, `degen_sum_kernel`, `degen_solve_kernel`, `degen_phase_kernel`, `degen_apply_gains_kernel`, `degen_apply_rows_kernel`
-(degeneracy_kernels.hpp), both dtypes: no scratch, no spilled VGPRs."""
+(degeneracy_kernels.hpp), both dtypes: no scratch, no spilled VGPRs.
+`mixed_dense_kernel`, `mixed_init_kernel`, `mixed_step_kernel`, `mixed_gram_kernel`, `mixed_cert_kernel`, `mixed_cert_sum_kernel`,
+`mixed_backmul_kernel` (mixed_comps_kernels.hpp): no scratch, no spilled VGPRs."""
 import re
 import sys
 
@@ -80,6 +82,14 @@ for line in sys.stdin:
     if cur is not None and any(k in cur for k in ("degen_rows_kernel", "degen_sum_kernel", "degen_solve_kernel", "degen_phase_kernel",
                                              "degen_apply_gains_kernel", "degen_apply_rows_kernel")):
         # the six of the degeneracy fix keep their sums, and the double-precision sincos its argument reduction, in registers
+        m = re.search(r"remark:\s+(ScratchSize \[bytes/lane\]|VGPRs Spill): (\d+)", line)
+        if m and int(m.group(2)) != 0:
+            bad.append(f"{cur}: {m.group(1)} = {m.group(2)}")
+        continue
+    if cur is not None and any(k in cur for k in ("mixed_dense_kernel", "mixed_init_kernel", "mixed_step_kernel", "mixed_gram_kernel",
+                                             "mixed_cert_kernel", "mixed_cert_sum_kernel", "mixed_backmul_kernel")):
+        # the seven of the mixed-model components (mixed_comps_kernels.hpp): the double-precision sinpi of the covariance element and the
+        # four accumulator tiles of the tile products stay in registers
         m = re.search(r"remark:\s+(ScratchSize \[bytes/lane\]|VGPRs Spill): (\d+)", line)
         if m and int(m.group(2)) != 0:
             bad.append(f"{cur}: {m.group(1)} = {m.group(2)}")

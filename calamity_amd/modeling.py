@@ -507,6 +507,8 @@ def yield_mixed_comps(
     notebook_progressbar=False,
     use_tensorflow=False,
     grp_size_threshold=5,
+    device=None,
+    return_info=False,
 ):
     """Modeling vectors for jointly fitted groups -- modeling.py:377-474.
 
@@ -514,9 +516,18 @@ def yield_mixed_comps(
     (keyed ``(red_grp,)``; note the reference passes ``ant_dly`` as the DPSS offset here, :447-455); larger ones get
     the leading eigenvectors of the analytic covariance, ``(Nfreqs * len(fit_grp), Ncomponents)``, one ``Nfreqs`` row
     block per redundant group.
+
+    ``device`` (an index; the reference's ``use_tensorflow=True`` means 0) derives the joint groups' vectors on that device, all
+    groups in one call (``simple_cov.model_comps_of_groups``); a group the device route does not certify is computed on the host
+    as before.  The default is the host, bit for bit.  ``return_info=True`` returns ``(modeling_vectors, info)``, ``info`` keyed
+    by joint group: route, reason, n, k, kept, resid_fro, lambda_max.
     """
+    dev = simple_cov.device_index(device, use_tensorflow)
+    kw = dict(ant_dly=ant_dly, horizon=horizon, offset=offset, min_dly=min_dly, dtype=dtype, eigenval_cutoff=eigenval_cutoff, verbose=verbose)
     operator_cache = {}
     modeling_vectors = {}
+    info = {}
+    joint = []  # the device route's groups: derived together behind the loop
     for grpnum in PBARS[notebook_progressbar](range(len(fitting_grps)), disable=not verbose):
         fit_grp = tuple(fitting_grps[grpnum])
         blvecs = np.asarray(fitting_blvecs[grpnum], dtype=np.float64).reshape(-1, 3)
@@ -527,9 +538,14 @@ def yield_mixed_comps(
                     freqs=freqs, length=bllen, offset=ant_dly, horizon=horizon, min_dly=min_dly,
                     operator_cache=operator_cache, eigenval_cutoff=eigenval_cutoff,
                 )
+        elif dev is None:
+            modeling_vectors[fit_grp], info[fit_grp] = simple_cov.yield_simple_multi_baseline_model_comps(
+                blvecs=blvecs, freqs=freqs, return_info=True, **kw)
         else:
-            modeling_vectors[fit_grp] = simple_cov.yield_simple_multi_baseline_model_comps(
-                blvecs=blvecs, ant_dly=ant_dly, offset=offset, min_dly=min_dly, horizon=horizon, dtype=dtype, freqs=freqs,
-                eigenval_cutoff=eigenval_cutoff, verbose=verbose,
-            )
-    return modeling_vectors
+            modeling_vectors[fit_grp] = None  # (keeps the key's place)
+            joint.append((fit_grp, blvecs))
+    if joint:
+        vectors, infos = simple_cov.model_comps_of_groups([b for _, b in joint], freqs, device=dev, **kw)
+        for (fit_grp, _), vecs, inf in zip(joint, vectors, infos):
+            modeling_vectors[fit_grp], info[fit_grp] = vecs, inf
+    return (modeling_vectors, info) if return_info else modeling_vectors

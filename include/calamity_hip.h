@@ -263,6 +263,49 @@ int cal_device_busy_clock_mhz(int device, double* mhz);
 int cal_weighted_square_error(int device, int dtype, int64_t n, const void* model_r, const void* model_i, const void* data_r,
                               const void* data_i, const void* wgts, double* out);
 
+/* The joint-covariance modeling vectors of fitting groups, simple_cov.py:7-189 (the reference's use_tensorflow=True path), without the
+ * dense eigenproblem (csrc/mixed_comps_kernels.hpp).  Per group of Nbls baselines, n = Nbls nfreqs samples, baseline-major:
+ *   C[(a,i)][(b,j)] = sinc(2 max(min_dly dnu, horizon |u_a(nu_i) - u_b(nu_j)| + offset dnu)) sinc(2 ant_dly dnu), u = uvw nu / 3e8, dnu in GHz;
+ *   diagonally pivoted Cholesky C ~ L L^T (argmax of the running diagonal, ties to the lowest index), stopped when the largest
+ *   remaining diagonal is below tol (status 0, "ok") or at the group's rank cap (status 1); G = L^T L [k][k]; the certificate
+ *   resid_fro = ||C - L L^T||_F over the whole matrix.  The caller takes the eigenpairs of G (lambda, U) and asks for
+ *   V = L U diag(scale), scale = lambda^-1/2: orthonormal eigenvectors of L L^T.  All of it in double, on `device`; all sums in a
+ *   fixed order.
+ * Groups are factored in chunks of consecutive groups whose scratch fits scratch_bytes (0: 256 MiB; negative: CAL_ERR_INVALID).  A
+ * group asks for min(n, 6144, max(64, ceil(n / 3))) columns; one that does not fit the bound even alone gets the columns the bound holds
+ * (in sixteens) as its rank cap, and status 2 ("not run", rank 0) when that is none.  The factors (n rounded up to 64, times the rank
+ * rounded up to 16, doubles per group) stay on the device until the handle is destroyed. */
+typedef struct cal_mixed_comps_desc {
+  int32_t ngroups;
+  int32_t nfreqs;
+  const int32_t* grp_bl_start; /* [ngroups + 1]: the baselines of group g are rows [grp_bl_start[g], grp_bl_start[g + 1]) of uvw */
+  const double* uvw;           /* [grp_bl_start[ngroups]][3] metres */
+  const double* freqs;         /* [nfreqs] Hz */
+  const int32_t* grp_freq_start; /* NULL: every group has all nfreqs channels; else [ngroups + 1]: group g has channels
+                                    [grp_freq_start[g], grp_freq_start[g + 1]) of freqs (groups of different bands in one call) */
+  double ant_dly, horizon, offset, min_dly;
+  double tol;                  /* > 0 */
+  int64_t scratch_bytes;
+} cal_mixed_comps_desc;
+typedef struct cal_mixed_comps cal_mixed_comps;
+/* Factors every group, forms every G and every certificate; CAL_ERR_HIP without a device (there is no CPU fallback). */
+int cal_mixed_comps_create(cal_mixed_comps** out, int device, const cal_mixed_comps_desc* desc);
+int cal_mixed_comps_destroy(cal_mixed_comps* h);
+/* Per group (any pointer may be NULL): rank k, status, the chunk it was factored in (0, 1, ... in group order), the largest running
+ * diagonal at the end, resid_fro; times_ms [3]: the factorisations, the Gram launch and the certificate launches of the create call
+ * (HIP events). */
+int cal_mixed_comps_info(cal_mixed_comps* h, int32_t* rank, int32_t* status, int32_t* chunk, double* max_d, double* resid_fro, double* times_ms);
+/* G of every group, one after the other ([k][k] each, symmetric, both triangles), sum k^2 <= cap_doubles doubles. */
+int cal_mixed_comps_gram(cal_mixed_comps* h, double* G, int64_t cap_doubles);
+/* V = L U diag(scale) of every group in one upload, one launch, one download: nkeep [ngroups] (0: the group is skipped), U the
+ * groups' [k][nkeep] one after the other, scale their [nkeep], V their [n][nkeep] in dtype (CAL_F32 / CAL_F64).  ms (may be NULL): the launch. */
+int cal_mixed_comps_vectors(cal_mixed_comps* h, int dtype, const int32_t* nkeep, const double* U, const double* scale, void* V, double* ms);
+/* For tests: L of one group as [k][n] (column m of L is row m) and its k pivots (either may be NULL). */
+int cal_mixed_comps_factor(cal_mixed_comps* h, int32_t group, double* L, int32_t* pivots);
+/* The dense C [n][n] of one group, n = nbls nfreqs <= 46340, by the same element function. */
+int cal_simple_cov_matrix(int device, int32_t nbls, const double* uvw, int32_t nfreqs, const double* freqs, double ant_dly, double horizon,
+                          double offset, double min_dly, double* C);
+
 /* tf.device / GPU selection of read_calibrate_and_model_dpss, calibration.py:1741-1753, :1796-1804 */
 int cal_solver_create(cal_solver** out, int device, int dtype);
 int cal_solver_destroy(cal_solver* s);
