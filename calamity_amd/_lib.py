@@ -250,6 +250,7 @@ SYMBOLS = {
     "cal_solver_solve_coeffs": (C.c_int, [_P, C.POINTER(CoeffSolveDesc), C.POINTER(CoeffSolveResult)]),
     "cal_solver_set_coeff_solve_scratch": (C.c_int, [_P, C.c_int64]),
     "cal_solver_fit_errors": (C.c_int, [_P, C.c_double, _P, _P, _P, _P, _P, C.POINTER(FitErrorsCounts)]),
+    "cal_solver_gain_basis_errors": (C.c_int, [_P, C.c_double, _P, _P, _P, C.POINTER(FitErrorsCounts)]),
     "cal_solver_solve_gain_coeffs": (C.c_int, [_P, C.POINTER(GainCoeffSolveDesc), C.POINTER(GainCoeffSolveResult)]),
     "cal_solver_solve_gain_time_coeffs": (C.c_int, [_P, C.POINTER(GainTimeSolveDesc), C.POINTER(GainTimeSolveResult)]),
     "cal_solver_get_gain_coeff_moments": (C.c_int, [_P] + [_P] * 8 + [C.POINTER(C.c_int64)]),

@@ -337,6 +337,12 @@ class SliceBatchFitter:
         return self._each(lambda r, s: s.lbfgs(nsteps, history=history, max_ls=max_ls, c1=c1, shrink=shrink, ftol=ftol, curvature_eps=curvature_eps,
                                                slice_mask=slice_mask, freeze_model=freeze_model, reset_moments=reset_moments))[0]
 
+    def gain_basis_errors(self, ridge=1e-6, y_var=True):
+        """``HipFitSolver.gain_basis_errors`` on every worker: ``gain_var`` ``[nt * nants, nfreqs]``, ``y_var`` and ``gain_dof`` in the
+        layout of ``y``.  ``y`` is replicated and the library has summed ``den`` over the workers, so every worker computes the same
+        planes and counts: worker 0's are returned, as ``fit_errors`` does for ``gain_var``."""
+        return self._each(lambda r, s: s.gain_basis_errors(ridge=ridge, y_var=y_var))[0]
+
     def solve_gain_coeffs(self, nsweeps, damping=0.5, ridge=1e-6, slice_mask=None, reset_gain_moments=False):
         """``HipFitSolver.solve_gain_coeffs`` on every worker (``slice_mask``: one entry per slice of the batch).  With several workers
         each sweep sums the three antenna planes of the workers' baselines in one exchange; ``y`` is replicated, so every worker then

@@ -791,7 +791,7 @@ def fit_quality_arrays(q, rms=1.0):
             ratio(q["chisq_bl"], q["wsum_bl"]))
 
 
-def fit_errors_arrays(e, chisq_bl, rms=1.0):
+def fit_errors_arrays(e, chisq_bl, rms=1.0, gain_dof=None, ntimes=1):
     """The outputs of ``HipFitSolver.fit_errors`` of ONE slice (solver units; any of ``leverage_bl``, ``gain_var``, ``model_var`` may be
     missing) and the slice's ``chisq_bl`` (``fit_quality``) as what ``fit_history`` reports.  With ``n`` the samples with ``w != 0``
     and ``p = sum leverage_bl + #{(a, f): gain_var > 0}`` the parameters the fit spent on them::
@@ -801,6 +801,12 @@ def fit_errors_arrays(e, chisq_bl, rms=1.0):
         gain_std     = sqrt(noise_scale gain_var)                 [nants, nfreqs], dimensionless
         model_std    = rms sqrt(noise_scale model_var)            [nbls, nfreqs] float32, the data's units (``rms``: the slice's
                                                                   ``data_scale_factor``, as in ``fit_quality_arrays``)
+
+    ``gain_dof`` (``HipFitSolver.gain_basis_errors``; ``gain_var`` is then its ``gain_var`` of the slice): the complex parameters the
+    basis gains of the slice's antennas spent, one number per antenna; they replace the count in ``p``: ``p = sum leverage_bl +
+    sum gain_dof / ntimes``.  In a joint fit over ``ntimes`` times (a gain time basis) an antenna's coefficients are shared by the
+    times, and so is their cost: every time is charged ``1 / ntimes`` of the antenna's ``gain_dof``, so that the times' ``p`` add up
+    to what the joint fit spent.
 
     Returns a dict with ``noise_scale``, ``underdetermined``, ``n``, ``p`` and, where their inputs are given, ``leverage_bl``,
     ``chisq_red_bl``, ``gain_std``, ``model_std``."""
@@ -814,7 +820,9 @@ def fit_errors_arrays(e, chisq_bl, rms=1.0):
         out["leverage_bl"] = lev
         out["chisq_red_bl"] = np.divide(chisq_bl, dof, out=np.full_like(chisq_bl, np.nan), where=dof > 0)
         p += float(np.sum(lev))
-    if "gain_var" in e:
+    if gain_dof is not None:
+        p += float(np.sum(np.asarray(gain_dof, dtype=np.float64))) / float(ntimes)
+    elif "gain_var" in e:
         p += float(np.count_nonzero(np.asarray(e["gain_var"]) > 0))
     under = n - p < 1.0
     scale = 1.0 if under else float(np.sum(chisq_bl)) / (n - p)
@@ -826,12 +834,13 @@ def fit_errors_arrays(e, chisq_bl, rms=1.0):
     return out
 
 
-def insert_fit_errors(gain_std, uvcal, hist, time, polarization, e, chisq_bl, rms, prob, nsingular=None):
+def insert_fit_errors(gain_std, uvcal, hist, time, polarization, e, chisq_bl, rms, prob, nsingular=None, gain_dof=None, ntimes=1):
     """File one (polarization, time) slice's fit errors (``fit_errors_arrays``): ``hist["errors"]`` with ``noise_scale``,
     ``underdetermined``, ``nsingular`` and, unless the model was frozen, ``leverage_per_baseline`` and ``chisq_red_per_baseline`` (dicts
     ``{(ant0, ant1): value}`` with antenna NUMBERS like ``chisq_per_baseline``) and, where ``model_var`` was asked for, ``model_std``
-    ``[rows, nfreqs]`` with its ``antpairs``; the slice's plane of ``gain_std`` (``[Nants, Nfreqs, Ntimes, Njones]`` or ``None``)."""
-    a = fit_errors_arrays(e, chisq_bl, rms)
+    ``[rows, nfreqs]`` with its ``antpairs``; the slice's plane of ``gain_std`` (``[Nants, Nfreqs, Ntimes, Njones]`` or ``None``).
+    ``gain_dof``, ``ntimes``: ``fit_errors_arrays``' (basis gains)."""
+    a = fit_errors_arrays(e, chisq_bl, rms, gain_dof=gain_dof, ntimes=ntimes)
     ants = np.asarray(uvcal.ant_array)
     keys = [(int(ants[i]), int(ants[j])) for i, j in zip(prob.bl_ant0, prob.bl_ant1)]
     entry = {"noise_scale": a["noise_scale"], "underdetermined": a["underdetermined"], "nsingular": int(e.get("nsingular", 0) if nsingular is None else nsingular)}
@@ -1053,6 +1062,7 @@ def calibrate_and_model_tensor(
     lbfgs_ftol=0.0,
     fit_errors=False,
     fit_errors_ridge=1e-6,
+    gain_basis_errors=False,
     fix_degeneracies=False,
     degeneracy_iters=6,
     degeneracy_phase_ref=True,
@@ -1124,7 +1134,17 @@ def calibrate_and_model_tensor(
       CONDITIONAL errors -- the gains held fixed for the model, the model and the other gains for a gain: the block diagonal of the
       Gauss-Newton matrix, which ignores the gain-foreground covariance and the degeneracies, so they are lower bounds.  With a gain
       basis (frequency or time) ``gain_std`` is absent: the variance of a basis gain is ``b_f^T N_a^-1 b_f`` with the projected normal
-      matrix, which is not computed (``p`` then counts no gain parameters).  With ``freeze_model`` only the gain part runs (no leverage tables).
+      matrix, which is not computed (``p`` then counts no gain parameters) unless ``gain_basis_errors`` is on.  With ``freeze_model``
+      only the gain part runs (no leverage tables).
+    * ``gain_basis_errors`` (default off: no call changes by a bit; a Python keyword only, a report and no fit-loop control; needs
+      ``fit_errors`` and a gain basis -- ``gain_basis`` / ``gain_max_dly`` or ``gain_time_basis`` / ``gain_time_scale`` -- else
+      ``ValueError``): the error bars of basis gains (``HipFitSolver.gain_basis_errors``, one more device pass where ``fit_errors`` runs,
+      at the reported gains, with ``fit_errors_ridge``).  ``fit_history["gain_std"]`` is then ``sqrt(noise_scale gain_var)`` with
+      ``gain_var = b_f^T N_r^-1 b_f`` of the projected normal matrix (positive at flagged channels of an unflagged antenna: the basis
+      interpolates), and ``p`` of ``noise_scale`` counts ``sum_a gain_dof[a]``, the parameters the basis gains spent; in a joint fit
+      over ``T`` times every time is charged ``1 / T`` of an antenna's ``gain_dof``.  Model, residual, gains and every other history
+      number keep their bits; ``noise_scale`` (and with it ``model_std``) grows with ``p``.  With ``freeze_model`` ``gain_std`` is the
+      only error output.  The variances of the coefficients ``y`` stay at solver level.
     * ``gain_solve_sweeps`` / ``gain_solve_every`` / ``gain_solve_damping`` (defaults 0, 0, 0.5: descent only, no call changes by a bit):
       solve the gains in closed form.  With the foreground model held fixed the chi-square is linear least squares in one antenna's
       gain while the others are held fixed; a damped StefCal sweep (``HipFitSolver.solve_gains``) sets every antenna's gain to
@@ -1317,8 +1337,13 @@ def calibrate_and_model_tensor(
         if not (np.isfinite(float(fit_errors_ridge)) and float(fit_errors_ridge) >= 0.0):
             raise ValueError(f"fit_errors_ridge must be finite and >= 0, got {fit_errors_ridge!r}")
         with_gains = gain_basis is None and gain_time_basis is None
-        errs = dict(samples=fit_errors == "samples", ridge=float(fit_errors_ridge), with_gains=with_gains,
-                    gain_std=np.zeros(gain4(gains.gain_array).shape, dtype=np.float64) if with_gains else None)
+        if gain_basis_errors and with_gains:
+            raise ValueError("gain_basis_errors needs a gain basis (gain_basis / gain_max_dly or gain_time_basis / gain_time_scale): fit_errors alone "
+                             "reports gain_std of free per-channel gains")
+        errs = dict(samples=fit_errors == "samples", ridge=float(fit_errors_ridge), with_gains=with_gains, basis_gains=bool(gain_basis_errors),
+                    gain_std=np.zeros(gain4(gains.gain_array).shape, dtype=np.float64) if with_gains or gain_basis_errors else None)
+    elif gain_basis_errors:
+        raise ValueError("gain_basis_errors needs fit_errors=True or 'samples': it adds the basis gains' error bars to that report")
     if sky_model is None and model_regularization is not None:
         echo(f"{datetime.datetime.now()} Sky model is None. Initializing from data...\n", verbose=verbose)
         # data / (g_i conj(g_j)) with the initial gains (:1131-1136).  With the unity, unflagged gains built just above that is
@@ -1788,7 +1813,8 @@ def calibrate_and_model_dpss(
 ):
     """Simultaneously solve for gains and model foregrounds with per-baseline DPSS vectors -- the kept entry point,
     calibration.py:1503-1584.  ``fg_model_comps_dict`` is accepted and ignored, as in the reference (:1564).  The ``delay_spectrum``
-    and ``fix_degeneracies`` / ``degeneracy_*`` keywords are ``calibrate_and_model_tensor``'s."""
+    and ``fix_degeneracies`` / ``degeneracy_*`` keywords are ``calibrate_and_model_tensor``'s, and so are ``fit_errors`` and
+    ``gain_basis_errors`` among ``fitting_kwargs``."""
     _check_delay_spectrum(delay_spectrum, delay_spectrum_taper, delay_spectrum_max_dly, delay_spectrum_bllen_bin)
     _check_degeneracy_call(fix_degeneracies, degeneracy_iters, fitting_kwargs)
     waker = _wake_device(fitting_kwargs.get("devices"))
@@ -1856,7 +1882,8 @@ def calibrate_and_model_mixed(
     eigenvectors for groups of baselines whose uv tracks overlap -- calibration.py:1353-1500 (same signature and
     returns).  ``use_tensorflow_to_derive_modeling_comps=True`` derives the joint groups' modeling vectors on the GPU
     (``modeling.yield_mixed_comps(device=...)``: the first entry of ``devices`` when one is given, else device 0); the default derives
-    them on the host.  The ``delay_spectrum`` and ``fix_degeneracies`` / ``degeneracy_*`` keywords are ``calibrate_and_model_tensor``'s."""
+    them on the host.  The ``delay_spectrum`` and ``fix_degeneracies`` / ``degeneracy_*`` keywords are ``calibrate_and_model_tensor``'s,
+    and so are ``fit_errors`` and ``gain_basis_errors`` among ``fitting_kwargs``."""
     _check_delay_spectrum(delay_spectrum, delay_spectrum_taper, delay_spectrum_max_dly, delay_spectrum_bllen_bin)
     _check_degeneracy_call(fix_degeneracies, degeneracy_iters, fitting_kwargs)
     fitting_grps, blvecs, _, _ = modeling.get_uv_overlapping_grps_conjugated(
@@ -1991,6 +2018,7 @@ def read_calibrate_and_model_dpss(
     fit_errors=False,
     fit_errors_samples=False,
     fit_errors_ridge=1e-6,
+    gain_basis_errors=False,
     fix_degeneracies=False,
     degeneracy_iters=6,
     degeneracy_phase_ref=True,
@@ -2013,7 +2041,8 @@ def read_calibrate_and_model_dpss(
     configuring an allocator pool.  As in the reference the baseline cuts are applied to the data only (:1767-1783
     select on ``uvd`` twice and never on the model) and ``fitted_info_outfilename`` is accepted but nothing is written --
     unless ``fit_errors`` (``fit_errors_samples``: with ``model_std``; ``fit_errors_ridge``: see ``calibrate_and_model_tensor``) is on:
-    then ``gain_std`` (where the gains are free per channel) and the per-baseline tables go there as an ``.npz`` archive: ``antpairs``
+    then ``gain_std`` (where the gains are free per channel, or with ``gain_basis_errors``, ``calibrate_and_model_tensor``'s, a Python
+    keyword only) and the per-baseline tables go there as an ``.npz`` archive: ``antpairs``
     ``[rows, 2]`` and, ``[Npols, Ntimes, rows]`` each with ``nan`` for a skipped slice, ``leverage_per_baseline``,
     ``chisq_red_per_baseline``; ``noise_scale`` ``[Npols, Ntimes]``.
     The ``delay_spectrum`` keywords are ``calibrate_and_model_tensor``'s (Python keywords only: there is no command-line flag yet);
@@ -2047,6 +2076,7 @@ def read_calibrate_and_model_dpss(
                     delay_spectrum_bllen_bin=delay_spectrum_bllen_bin, delay_spectrum_calibrated=delay_spectrum_calibrated) if delay_spectrum else {}),
             **(dict(fix_degeneracies=fix_degeneracies, degeneracy_iters=degeneracy_iters, degeneracy_phase_ref=degeneracy_phase_ref)
                if fix_degeneracies else {}),
+            **(dict(gain_basis_errors=True) if gain_basis_errors else {}),
         )
     finally:
         _DEVICE.update(saved)

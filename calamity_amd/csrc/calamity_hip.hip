@@ -31,6 +31,7 @@
 #include "gain_solve_kernels.hpp"
 #include "coeff_solve_kernels.hpp"
 #include "fit_error_kernels.hpp"
+#include "gain_error_kernels.hpp"
 #include "delay_spectrum_kernels.hpp"
 #include "degeneracy_kernels.hpp"
 #include "gain_basis_solve_kernels.hpp"
@@ -198,6 +199,7 @@ struct cal_solver {
   virtual int set_coeff_solve_scratch(int64_t bytes) = 0;
   virtual int fit_errors(double ridge, double* coeff_var, double* model_var, double* leverage_bl, double* nsamp_bl, double* gain_var,
                          cal_fit_errors_counts* counts) = 0;
+  virtual int gain_basis_errors(double ridge, double* gain_var, double* y_var, double* gain_dof, cal_fit_errors_counts* counts) = 0;
   virtual int solve_gain_coeffs(const cal_gain_coeff_solve_desc* d, cal_gain_coeff_solve_result* res) = 0;
   virtual int normal_product(const void* p_g_r, const void* p_g_i, const void* p_c_r, const void* p_c_i, void* out_g_r, void* out_g_i, void* out_c_r,
                              void* out_c_i) = 0;
@@ -271,6 +273,10 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
   // [ca][2][n] T (gts_n, gts_rhsa), the factor in double where it leaves LDS or, without a frequency basis, the channel systems beyond
   // kTimeTile vectors (gts_d); the per-row right-hand sides [nants][2][K] T (gts_rhs), the two counters; the chunks share cs_bound
   DevBuf gts_m, gts_n, gts_rhsa, gts_d, gts_rhs, gts_cnt;
+  // gain_basis_errors (gain_error_kernels.hpp), per chunk of rows (antenna rows; antennas under a time basis): the buffers of the two
+  // solves above under its own chunking (gbe_m, gbe_n, gbe_rhsa, gbe_d, gbe_rhs), W [rows][np][np] T (gbe_w), ok [y_rows] and the two
+  // counters (gbe_ok), the outputs gain_var | y_var | gain_dof | the channels' dof of a time basis alone, doubles (gbe_out)
+  DevBuf gbe_m, gbe_n, gbe_rhsa, gbe_d, gbe_rhs, gbe_w, gbe_ok, gbe_out;
   std::vector<uint8_t> held;                   // hold_slices: [nslices], 1 = the slice enters every later run as stopped (empty: none)
   DevBuf fq_out, fq_gains;                     // fit_quality: chisq_ant | wsum_ant ([nants][nfreqs] doubles each, the exchange payload) | chisq_bl | wsum_bl; gains given for one evaluation
   DevBuf rw_w0, rw_out;                        // robust_weights: w0, the weights as set_data gave them (first call after a set_data); scale_bl | ndown_bl ([nbls] doubles each)
@@ -1286,6 +1292,7 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
   }
   void release_gain_time_solve() {  // the scratch of solve_gain_time_coeffs: sized again by the next call
     for (DevBuf* b : {&gts_m, &gts_n, &gts_rhsa, &gts_d, &gts_rhs, &gts_cnt}) b->release();
+    for (DevBuf* b : {&gbe_m, &gbe_n, &gbe_rhsa, &gbe_d, &gbe_rhs, &gbe_w, &gbe_ok, &gbe_out}) b->release();  // and of gain_basis_errors
   }
   // the fit starts from the gains the solver holds now: g0 := gains, y := 0 (and its snapshot with it)
   int rebase_gain_basis() {
@@ -2730,6 +2737,96 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     return CAL_OK;
   }
 
+  // cal_solver_gain_basis_errors: fit_errors' sequence for gain_var (the model pass, gain_solve_rows_kernel, gain_solve_ant_kernel and
+  // the exchange of its den plane), then per chunk of rows gain_basis_gram_kernel as it is (its rhs goes nowhere anyone reads),
+  // gain_time_kron_kernel as it is under a time basis, gain_error_factor_kernel and gain_error_var_kernel; a time basis alone runs
+  // gain_time_chan_var_kernel and gain_error_dof_kernel instead (gain_error_kernels.hpp).  The chunks count W (solve_plan.hpp).  y is
+  // replicated and den is summed over the ranks, so every rank computes the same planes: no collective beyond antenna_sweep's own.
+  int gain_basis_errors(double ridge, double* gain_var, double* y_var, double* gain_dof, cal_fit_errors_counts* counts) override {
+    HIP_TRY(hipSetDevice(device));
+    CAL_TRY(require_set("gain_basis_errors", true));
+    if (!(ridge >= 0.0) || !std::isfinite(ridge)) return fail(CAL_ERR_INVALID, "gain_basis_errors: ridge = %g must be finite and >= 0", ridge);
+    if (!yb_on())
+      return fail(CAL_ERR_STATE, "gain_basis_errors: no gain basis is set (cal_solver_set_gain_basis, cal_solver_set_gain_time_basis); cal_solver_fit_errors "
+                  "gives gain_var = 1 / den of free per-channel gains");
+    CAL_TRY(gain_sweep_setup());
+    const int K = gb_nvec, L = tb_on() ? tb_L : 0, Tn = tb_on() ? tb_T : 1, na = y_rows(), Lr = tb_on() ? tb_L : 1;
+    const int n = Lr * (gb_on() ? K : 1), np = fe_pad(n);
+    const RowChunks rc = plan_row_chunks(K, L, Tn, nfreqs, sizeof(T), cs_bound, na, gain_error_extra(K, L));
+    const size_t nant_out = (size_t)nants * nfreqs;
+    const size_t n_yvar = (size_t)na * Lr * (gb_on() ? K : nfreqs);
+    const size_t n_chan = gb_on() ? 0 : (size_t)na * nfreqs;  // the channels' dof of a time basis alone
+    if (gb_on()) {
+      if (tb_on()) {
+        CAL_TRY(gbe_m.reserve((size_t)rc.rows * rc.m_row * sizeof(T), false));
+        CAL_TRY(gbe_rhsa.reserve(2 * (size_t)rc.rows * rc.n * sizeof(T), false));
+      }
+      CAL_TRY(gbe_n.reserve((size_t)rc.rows * rc.n_row * sizeof(T), false));
+      CAL_TRY(gbe_rhs.reserve(2 * (size_t)nants * K * sizeof(T)));
+      CAL_TRY(gbe_w.reserve((size_t)rc.rows * rc.x_row * sizeof(T), false));
+      CAL_TRY(allow_chol_lds(&gain_error_factor_kernel<T>));
+    }
+    CAL_TRY(gbe_d.reserve(std::max<size_t>(8, (size_t)rc.rows * rc.d_row * sizeof(double)), false));
+    CAL_TRY(gbe_ok.reserve(((size_t)na + 2) * sizeof(int)));
+    CAL_TRY(gbe_out.reserve((nant_out + n_yvar + (size_t)na + n_chan) * sizeof(double), false));
+    double* o_gv = gbe_out.as<double>();
+    double* o_yv = o_gv + nant_out;
+    double* o_dof = o_yv + n_yvar;
+    double* o_chan = o_dof + na;
+    int* ok = gbe_ok.as<int>();
+    int* dcnt = ok + na;
+    RowPlanes P;
+    CAL_TRY(gain_planes(P));
+    CAL_TRY(antenna_sweep(P, 1));  // of the three planes only den is wanted, and exchanged
+    // a singular system keeps zeros
+    HIP_TRY(hipMemsetAsync(gbe_ok.p, 0, ((size_t)na + 2) * sizeof(int), stream));
+    HIP_TRY(hipMemsetAsync(gbe_out.p, 0, (nant_out + n_yvar + (size_t)na + n_chan) * sizeof(double), stream));
+    const int nb = (K + kNsBlock - 1) / kNsBlock, npairs = nb * (nb + 1) / 2;
+    const int npieces = (nfreqs + kFePiece - 1) / kFePiece;
+    for (int a0 = 0; a0 < na; a0 += rc.rows) {
+      const int ca = std::min(rc.rows, na - a0);
+      if (gb_on()) {
+        if (!tb_on()) {
+          hipLaunchKernelGGL(gain_basis_gram_kernel<T>, dim3((unsigned)ca * npairs), dim3(256), 0, stream, gb_Bt.as<T>(), gs_out.as<double>(), gains.as<T2>(),
+                             gbe_n.as<T>(), gbe_rhs.as<T>(), (const unsigned char*)nullptr, na_slice, a0, npairs, K, gb_kpad, nants, nfreqs, fpad);
+        } else {
+          for (int t = 0; t < Tn; ++t)  // M [t][rel][K][K]
+            hipLaunchKernelGGL(gain_basis_gram_kernel<T>, dim3((unsigned)ca * npairs), dim3(256), 0, stream, gb_Bt.as<T>(), gs_out.as<double>(),
+                               gains.as<T2>(), gbe_m.as<T>() + (size_t)t * ca * K * K, gbe_rhs.as<T>(), (const unsigned char*)nullptr, na_slice,
+                               t * na + a0, npairs, K, gb_kpad, nants, nfreqs, fpad);
+          hipLaunchKernelGGL(gain_time_kron_kernel<T>, dim3((unsigned)ca * L, (L + kTimeTile - 1) / kTimeTile), dim3(256), 0, stream, gbe_m.as<T>(),
+                             gbe_rhs.as<T>(), tb_B.as<T>(), gbe_n.as<T>(), gbe_rhsa.as<T>(), a0, ca, na, Tn, L, tb_lpad, K);
+        }
+        hipLaunchKernelGGL(gain_error_factor_kernel<T>, dim3(ca), dim3(256), rc.lds, stream, gbe_n.as<T>(), gbe_d.as<double>(), gbe_w.as<T>(),
+                           y_var ? o_yv : nullptr, gain_dof ? o_dof : nullptr, ok, a0, n, ridge, dcnt, kCsLdsDoubles);
+        if (gain_var)
+          hipLaunchKernelGGL(gain_error_var_kernel<T>, dim3((unsigned)Tn * ca * npieces), dim3(256), 0, stream, gbe_w.as<T>(), gb_Bt.as<T>(),
+                             tb_on() ? tb_B.as<T>() : (const T*)nullptr, ok, o_gv, a0, ca, na, Lr, tb_lpad, K, nfreqs, fpad, npieces);
+      } else {
+        const unsigned blocks = (unsigned)(((long long)ca * nfreqs + 255) / 256);
+        auto* chan = L <= kTimeTile ? gain_time_chan_var_kernel<T, kTimeTile> : gain_time_chan_var_kernel<T, 0>;  // the channel systems in registers, or in gbe_d
+        hipLaunchKernelGGL(chan, dim3(blocks), dim3(256), 0, stream, gs_out.as<double>(), tb_B.as<T>(), gbe_d.as<double>(), y_var ? o_yv : nullptr,
+                           gain_var ? o_gv : nullptr, gain_dof ? o_chan : nullptr, a0, ca, na, Tn, L, tb_lpad, nfreqs, ridge, dcnt);
+      }
+      HIP_TRY(hipGetLastError());
+    }
+    if (!gb_on() && gain_dof) {
+      hipLaunchKernelGGL(gain_error_dof_kernel, dim3((na + 255) / 256), dim3(256), 0, stream, o_chan, o_dof, na, nfreqs);
+      HIP_TRY(hipGetLastError());
+    }
+    int cnt[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(cnt, dcnt, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
+    if (gain_var) HIP_TRY(hipMemcpyAsync(gain_var, o_gv, nant_out * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (y_var) HIP_TRY(hipMemcpyAsync(y_var, o_yv, n_yvar * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (gain_dof) HIP_TRY(hipMemcpyAsync(gain_dof, o_dof, (size_t)na * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (counts) {
+      counts->nsolved = cnt[0];
+      counts->nsingular = cnt[1];
+    }
+    return CAL_OK;
+  }
+
   // cal_solver_solve_gain_coeffs: solve_gains' sequence up to the exchanged planes, then per chunk of antenna rows gain_basis_gram_kernel
   // and gain_basis_chol_kernel (gain_basis_solve_kernels.hpp), then the gains of the selected slices rebuilt from y.  Every chunk of a
   // sweep reads the old gains: they are rebuilt behind the last one.  y is replicated and the planes are summed over the ranks, so
@@ -3064,6 +3161,14 @@ int debug_solve_plan(const cal_problem_desc* d, int64_t bound, int what, void* o
     const int K = (int)in[0], L = (int)in[1], Tn = (int)in[2];
     const RowChunks r = plan_row_chunks(K, L, Tn, p.nfreqs, sizeof(T), bound, L > 0 ? p.nants / Tn : p.nants);
     return give(std::vector<int64_t>{r.rows, r.in_lds, (int64_t)r.lds, r.n, r.m_row, r.n_row, r.d_row});
+  }
+  if (what == 31) {  // gain_basis_errors: the same rows with W counted
+    const int64_t* in = static_cast<const int64_t*>(out);
+    if (cap < 24 || in[0] < 0 || in[1] < 0 || in[0] + in[1] == 0 || (in[1] > 0 && (in[2] < 1 || p.nants % in[2] != 0)))
+      return fail(CAL_ERR_INVALID, "%s: what = 31 takes K, L, T (K + L > 0; T divides nants) in the first 24 bytes of out", who);
+    const int K = (int)in[0], L = (int)in[1], Tn = (int)in[2];
+    const RowChunks r = plan_row_chunks(K, L, Tn, p.nfreqs, sizeof(T), bound, L > 0 ? p.nants / Tn : p.nants, gain_error_extra(K, L));
+    return give(std::vector<int64_t>{r.rows, r.in_lds, (int64_t)r.lds, r.n, r.m_row, r.n_row, r.d_row, r.x_row});
   }
   if (what < 0 || what >= 20 || what % 10 > 6) return fail(CAL_ERR_INVALID, "%s: what = %d", who, what);
   const bool fe = what >= 10;
@@ -3771,6 +3876,10 @@ int cal_debug_lbfgs_coefficients(int32_t npairs, const double* gram, double* del
   return CAL_OK;
 }
 int cal_solver_solve_coeffs(cal_solver* s, const cal_coeff_solve_desc* desc, cal_coeff_solve_result* result) { NEED(s); return s->solve_coeffs(desc, result); }
+int cal_solver_gain_basis_errors(cal_solver* s, double ridge, double* gain_var, double* y_var, double* gain_dof, cal_fit_errors_counts* counts) {
+  NEED(s);
+  return s->gain_basis_errors(ridge, gain_var, y_var, gain_dof, counts);
+}
 int cal_solver_set_coeff_solve_scratch(cal_solver* s, int64_t bytes) { NEED(s); return s->set_coeff_solve_scratch(bytes); }
 int cal_solver_fit_errors(cal_solver* s, double ridge, double* coeff_var, double* model_var, double* leverage_bl, double* nsamp_bl, double* gain_var,
                           cal_fit_errors_counts* counts) {

@@ -27,8 +27,7 @@ __host__ __device__ inline int fe_pad(int nvec) { return (nvec + 15) & ~15; }  /
 
 // One workgroup per group.  The factor M ([nvec + 1][ld] doubles: L, then a spare row) lies in LDS when [nvec + 2][ld] fits
 // `lds_doubles` (the bound of coeff_chol_kernel, so that both take the same branch) and in the chunk's double scratch otherwise.
-// W = L^-1 replaces L row by row: W[i][k] = -(sum_{j = k}^{i - 1} L[i][j] W[j][k]) / L[i][i] reads row i of L and the rows of W
-// above it; the row goes to the spare row first, because its elements are still being read as L.  A group that is singular by the
+// W = L^-1 replaces L row by row (normal_chol_invert of normal_solve.hpp).  A group that is singular by the
 // shared tests leaves ok[group] = 0 and its outputs alone (the host has zeroed them) and counts in counts[1].
 template <typename T>
 __global__ __launch_bounds__(256) void fit_error_factor_kernel(const T* __restrict__ nmat, double* __restrict__ dscr,
@@ -50,19 +49,7 @@ __global__ __launch_bounds__(256) void fit_error_factor_kernel(const T* __restri
     if (tid == 0) atomicAdd(counts + 1, 1);
     return;
   }
-  double* spare = M + (long long)n * ld;
-  for (int i = 0; i < n; ++i) {
-    double* Li = M + (long long)i * ld;
-    const double piv = Li[i];
-    for (int k = tid; k <= i; k += 256) {
-      double s = k == i ? 1.0 : 0.0;
-      for (int j = k; j < i; ++j) s -= Li[j] * M[(long long)j * ld + k];
-      spare[k] = s / piv;
-    }
-    __syncthreads();  // row i of L has been read
-    for (int k = tid; k <= i; k += 256) Li[k] = spare[k];
-    __syncthreads();
-  }
+  normal_chol_invert(M, ld, n);
   for (int k = tid; k < n; k += 256) {
     double s = 0;
     for (int i = k; i < n; ++i) {
@@ -83,12 +70,71 @@ __global__ __launch_bounds__(256) void fit_error_factor_kernel(const T* __restri
   }
 }
 
-// One workgroup per FeWork.  Z = W A^T for the piece's channels, 64 rows of Z at a time: wave w owns rows [64 ib + 16 w, + 16) and
-// four 16 x 16 accumulator tiles over the 64 channels (v_mfma_f32_16x16x4_f32 / v_mfma_f64_16x16x4_f64; the reduction index is the
-// vector k).  Per step of kNsChunk vectors the 64 x 32 block of W and the 32 x 64 block of the tiles ([vector][channel], as the tiles
-// store it, any tile width) are staged in LDS; blocks of W above the diagonal are never staged, and a wave stops at its own
-// diagonal tile.  The squares of a row block are summed in double per lane, then over the 16 (wave, lane quarter) partial sums in a
-// fixed order by the thread that owns the channel.  Folded tiles hold channels [0, nfreqs / 2): a second pass with
+// What the leverage kernel and gain_error_var_kernel (gain_error_kernels.hpp) share, by the whole workgroup (256 threads): the column
+// sums of the squares of Z = W X for 64 columns (channels), W [np][np] lower triangular in whole 16 x 16 tiles, X [np][64] given by
+// piece(k, c): the 16 bytes of row (vector) k from column c on, zeros where X has none.  64 rows of Z at a time: wave w owns rows
+// [64 ib + 16 w, + 16) and four 16 x 16 accumulator tiles; per step of kNsChunk vectors the 64 x 32 block of W and the 32 x 64 block
+// of X are staged in LDS (s_w, s_at); blocks of W above the diagonal are never staged, and a wave stops at its own diagonal tile.  The
+// squares of a row block are summed in double per lane (s_sq), then over the 16 (wave, lane quarter) partial sums in a fixed order by
+// the thread that owns the column: the sum of column tid is returned to the threads tid < 64.  Begins with a barrier.
+template <typename T, typename Piece>
+__device__ __forceinline__ double fe_sumsq(const T* __restrict__ Wg, int np, T (*s_w)[kNsPitch], T (*s_at)[kFePitch], double (*s_sq)[kFePiece],
+                                           Piece piece) {
+#pragma clang fp contract(off)
+  constexpr int V = 16 / (int)sizeof(T);
+  typedef ns_vec_t<T> vec_t;
+  typedef typename MmT<T>::v4 acc_t;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int col = lane & 15, kq = lane >> 4;
+  const int nrb = (np + kNsBlock - 1) / kNsBlock;
+  double mv = 0;
+  for (int ib = 0; ib < nrb; ++ib) {
+    acc_t acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[t] = acc_t{0, 0, 0, 0};
+    const int r0 = ib * kNsBlock + wave * 16;                         // the wave's first row
+    const int kend = np < (ib + 1) * kNsBlock ? np : (ib + 1) * kNsBlock;  // W is lower triangular
+    const int kmine = r0 < np ? (r0 + 16 < kend ? r0 + 16 : kend) : 0;
+    for (int kp = 0; kp < kend; kp += kNsChunk) {
+      __syncthreads();  // the previous step's operands (and s_sq) have been read
+      for (int idx = tid; idx < kNsBlock * (kNsChunk / V); idx += 256) {
+        const int r = idx / (kNsChunk / V), c = (idx - r * (kNsChunk / V)) * V;
+        const int row = ib * kNsBlock + r, k = kp + c;
+        vec_t v;
+#pragma unroll
+        for (int x = 0; x < V; ++x) v[x] = (T)0;
+        if (row < np && k < np) v = *reinterpret_cast<const vec_t*>(Wg + (long long)row * np + k);
+        *reinterpret_cast<vec_t*>(&s_w[r][c]) = v;
+      }
+      for (int idx = tid; idx < kNsChunk * (kFePiece / V); idx += 256) {
+        const int kk = idx / (kFePiece / V), c = (idx - kk * (kFePiece / V)) * V;
+        *reinterpret_cast<vec_t*>(&s_at[kk][c]) = piece(kp + kk, c);
+      }
+      __syncthreads();
+      const int ke = kmine - kp < kNsChunk ? kmine - kp : kNsChunk;
+      for (int kk = 0; kk < ke; kk += 4) {
+        const T a = s_w[wave * 16 + col][kk + kq];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) acc[t] = MmT<T>::mfma(a, s_at[kk + kq][t * 16 + col], acc[t]);
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      double s = 0;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) s += (double)acc[t][r] * (double)acc[t][r];
+      s_sq[wave * 4 + kq][t * 16 + col] = s;
+    }
+    __syncthreads();
+    if (tid < kFePiece)
+      for (int p = 0; p < 16; ++p) mv += s_sq[p][tid];
+  }
+  return mv;
+}
+
+// One workgroup per FeWork.  Z = W A^T for the piece's channels through fe_sumsq above (v_mfma_f32_16x16x4_f32 /
+// v_mfma_f64_16x16x4_f64; the reduction index is the vector k); its column operand is the 32 x 64 block of the tiles ([vector][channel],
+// as the tiles store it, any tile width).  Folded tiles hold channels [0, nfreqs / 2): a second pass with
 // a[k] (-1)^k gives the mirror channel nfreqs - 1 - f.  Every row of the run takes the same model_var (when asked for) and its own
 // partial sum of q model_var: part[row][slot], slot = piece, or 2 npieces - 1 - piece for the mirror pass, so that the slots are in
 // channel order.
@@ -102,7 +148,6 @@ __global__ __launch_bounds__(256) void fit_error_leverage_kernel(const T* __rest
 #pragma clang fp contract(off)
   constexpr int V = 16 / (int)sizeof(T);
   typedef ns_vec_t<T> vec_t;
-  typedef typename MmT<T>::v4 acc_t;
   __shared__ __attribute__((aligned(16))) T s_w[kNsBlock][kNsPitch];
   __shared__ __attribute__((aligned(16))) T s_at[kNsChunk][kFePitch];
   __shared__ double s_sq[16][kFePiece];  // [wave * 4 + lane quarter][channel]
@@ -111,7 +156,6 @@ __global__ __launch_bounds__(256) void fit_error_leverage_kernel(const T* __rest
   if (!ok[wk.grp]) return;
   const CsGroup g = grps[wk.grp];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int col = lane & 15, kq = lane >> 4;
   const int nvec = g.nvec, np = fe_pad(nvec);
   const int fb = 1 << g.fb_log2;
   const int nch = ((fold ? nfreqs / 2 : fpad) >> g.fb_log2) << g.fb_log2;  // what the group's tiles cover
@@ -120,58 +164,19 @@ __global__ __launch_bounds__(256) void fit_error_leverage_kernel(const T* __rest
   const T* __restrict__ Wg = wmat + woff[wk.grp];
   const T* __restrict__ tbase = tiles + bl_tile[wk.b0];
   const int nslot = (fold ? 2 : 1) * npieces;
-  const int nrb = (np + kNsBlock - 1) / kNsBlock;
   for (int mirror = 0; mirror <= fold; ++mirror) {
-    double mv = 0;  // of channel c0 + tid (tid < 64)
-    for (int ib = 0; ib < nrb; ++ib) {
-      acc_t acc[4];
+    // of channel c0 + tid (tid < 64)
+    const double mv = fe_sumsq<T>(Wg, np, s_w, s_at, s_sq, [&](int k, int c) {
+      vec_t v;
 #pragma unroll
-      for (int t = 0; t < 4; ++t) acc[t] = acc_t{0, 0, 0, 0};
-      const int r0 = ib * kNsBlock + wave * 16;                         // the wave's first row
-      const int kend = np < (ib + 1) * kNsBlock ? np : (ib + 1) * kNsBlock;  // W is lower triangular
-      const int kmine = r0 < np ? (r0 + 16 < kend ? r0 + 16 : kend) : 0;
-      for (int kp = 0; kp < kend; kp += kNsChunk) {
-        __syncthreads();  // the previous step's operands (and s_sq) have been read
-        for (int idx = tid; idx < kNsBlock * (kNsChunk / V); idx += 256) {
-          const int r = idx / (kNsChunk / V), c = (idx - r * (kNsChunk / V)) * V;
-          const int row = ib * kNsBlock + r, k = kp + c;
-          vec_t v;
-#pragma unroll
-          for (int x = 0; x < V; ++x) v[x] = (T)0;
-          if (row < np && k < np) v = *reinterpret_cast<const vec_t*>(Wg + (long long)row * np + k);
-          *reinterpret_cast<vec_t*>(&s_w[r][c]) = v;
-        }
-        for (int idx = tid; idx < kNsChunk * (kFePiece / V); idx += 256) {
-          const int kk = idx / (kFePiece / V), c = (idx - kk * (kFePiece / V)) * V;
-          const int k = kp + kk, ch = c0 + c;
-          vec_t v;
-#pragma unroll
-          for (int x = 0; x < V; ++x) v[x] = (T)0;
-          if (k < nvec && c < cn) {
-            v = *reinterpret_cast<const vec_t*>(tbase + (long long)(ch >> g.fb_log2) * nvec * fb + (long long)k * fb + (ch & (fb - 1)));
-            if (mirror && (k & 1)) v = -v;
-          }
-          *reinterpret_cast<vec_t*>(&s_at[kk][c]) = v;
-        }
-        __syncthreads();
-        const int ke = kmine - kp < kNsChunk ? kmine - kp : kNsChunk;
-        for (int kk = 0; kk < ke; kk += 4) {
-          const T a = s_w[wave * 16 + col][kk + kq];
-#pragma unroll
-          for (int t = 0; t < 4; ++t) acc[t] = MmT<T>::mfma(a, s_at[kk + kq][t * 16 + col], acc[t]);
-        }
+      for (int x = 0; x < V; ++x) v[x] = (T)0;
+      if (k < nvec && c < cn) {
+        const int ch = c0 + c;
+        v = *reinterpret_cast<const vec_t*>(tbase + (long long)(ch >> g.fb_log2) * nvec * fb + (long long)k * fb + (ch & (fb - 1)));
+        if (mirror && (k & 1)) v = -v;
       }
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        double s = 0;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) s += (double)acc[t][r] * (double)acc[t][r];
-        s_sq[wave * 4 + kq][t * 16 + col] = s;
-      }
-      __syncthreads();
-      if (tid < kFePiece)
-        for (int p = 0; p < 16; ++p) mv += s_sq[p][tid];
-    }
+      return v;
+    });
     if (tid < kFePiece) s_mv[tid] = mv;
     __syncthreads();
     // the rows of the run, one wave each: lane c has channel c0 + c of the (half) band

@@ -4,7 +4,8 @@
 // N and rhs in T on the matrix cores, the solve in double.  Here are
 //   the Gram core     normal_gram_njt, normal_gram_step, normal_gram_store: one workgroup per 64 x 64 block (bi, bj <= bi) of N
 //   the solve         normal_chol_solve: one workgroup per N, Cholesky and both substitutions (normal_chol_load and normal_chol_factor,
-//                     which the factor kernel of fit_error_kernels.hpp calls too)
+//                     which the factor kernels of fit_error_kernels.hpp and gain_error_kernels.hpp call too, and their
+//                     normal_chol_invert: W = L^-1 in place)
 // A kernel brings what is its own: which rows A has and where they lie, the three per-channel vectors w, u_r, u_i of a step, where
 // N, rhs and the update go.  N and rhs are accumulated in a fixed order (no atomics on reals: two calls give the same bits).
 #pragma once
@@ -91,7 +92,7 @@ __device__ __forceinline__ void normal_gram_store(T* __restrict__ N, int n, int 
 // workgroup (256 threads), everything in double; s_red: 256 doubles of LDS.
 // normal_chol_load: the trace of N in a fixed order, then the lower triangle of N + ridge (tr N / n) I into rows [0, n) of M (pitch
 // ld).  Returns false, the same in every thread, when tr N <= 0 or not finite.  No barrier behind the writes: the caller may fill
-// further rows of M first; normal_chol_factor begins with one.
+// further rows of M first; normal_chol_factor begins with one.  tr N stays in s_red[0] (gain_error_factor_kernel reads the shift from it).
 template <typename T>
 __device__ __forceinline__ bool normal_chol_load(double* M, int ld, int n, const T* __restrict__ Ng, double ridge, double* s_red) {
 #pragma clang fp contract(off)
@@ -141,6 +142,27 @@ __device__ __forceinline__ bool normal_chol_factor(double* M, int ld, int n, int
     __syncthreads();
   }
   return true;
+}
+
+// normal_chol_invert: W = L^-1 replaces L (rows [0, n) of M behind normal_chol_factor) row by row:
+// W[i][k] = -(sum_{j = k}^{i - 1} L[i][j] W[j][k]) / L[i][i] reads row i of L and the rows of W above it; the row goes to the spare row
+// M[n] first, because its elements are still being read as L.  Ends behind a barrier.
+__device__ __forceinline__ void normal_chol_invert(double* M, int ld, int n) {
+#pragma clang fp contract(off)
+  const int tid = threadIdx.x;
+  double* spare = M + (long long)n * ld;
+  for (int i = 0; i < n; ++i) {
+    double* Li = M + (long long)i * ld;
+    const double piv = Li[i];
+    for (int k = tid; k <= i; k += 256) {
+      double s = k == i ? 1.0 : 0.0;
+      for (int j = k; j < i; ++j) s -= Li[j] * M[(long long)j * ld + k];
+      spare[k] = s / piv;
+    }
+    __syncthreads();  // row i of L has been read
+    for (int k = tid; k <= i; k += 256) Li[k] = spare[k];
+    __syncthreads();
+  }
 }
 
 // (N + ridge (tr N / n) I) x = rhs for both right-hand sides, by the whole workgroup (256 threads), everything in double.  The

@@ -1,4 +1,5 @@
-// solve_plan.hpp -- what the closed-form calls (solve_gains, solve_coeffs, solve_gain_coeffs, solve_gain_time_coeffs, fit_errors) decide
+// solve_plan.hpp -- what the closed-form calls (solve_gains, solve_coeffs, solve_gain_coeffs, solve_gain_time_coeffs, fit_errors,
+// gain_basis_errors) decide
 // before they launch, on the host alone, from what plan_problem() (problem_plan.hpp) yields; the antenna lists without autocorrelations
 // are its antenna_lists.  No HIP or RCCL runtime call and no solver: SolverT uploads these plans at the first call that needs them;
 // cal_debug_solve_plan returns them as bytes (tests/test_solve_plan_host.py).  A group's result does not depend on its chunk, but the
@@ -110,8 +111,15 @@ struct RowChunks {
   bool in_lds;
   size_t lds;              // dynamic LDS of the Cholesky launch
   int rows;                // rows per chunk: what stays under the bound, at least one
+  long long x_row;         // T elements per row beyond the solves' own (gain_basis_errors: W); 0 for the solves
 };
-inline RowChunks plan_row_chunks(int K, int L, int Tn, int nfreqs, size_t elem, int64_t bound, int nrows) {
+// gain_basis_errors: W of a row (padded to whole 16 x 16 tiles, T) is counted in a chunk's bytes, so its chunks are cut elsewhere than
+// the solves'; the channel systems of a time basis alone keep no W
+inline long long gain_error_extra(int K, int L) {
+  const long long np = K > 0 ? fe_pad((L > 0 ? L : 1) * K) : 0;
+  return np * np;
+}
+inline RowChunks plan_row_chunks(int K, int L, int Tn, int nfreqs, size_t elem, int64_t bound, int nrows, long long extra = 0) {
   RowChunks r{};
   r.n = (L > 0 ? L : 1) * K;
   r.in_lds = chol_in_lds(r.n);
@@ -123,7 +131,8 @@ inline RowChunks plan_row_chunks(int K, int L, int Tn, int nfreqs, size_t elem, 
   } else {
     r.d_row = L <= kTimeTile ? 0 : (long long)nfreqs * (L * (L + 1) / 2 + 2 * L);
   }
-  const long long row_bytes = std::max<long long>(1, (r.m_row + r.n_row) * (long long)elem + r.d_row * 8);
+  r.x_row = extra;
+  const long long row_bytes = std::max<long long>(1, (r.m_row + r.n_row + r.x_row) * (long long)elem + r.d_row * 8);
   r.rows = (int)std::max<long long>(1, std::min<long long>(nrows, bound / row_bytes));
   return r;
 }

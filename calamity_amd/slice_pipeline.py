@@ -211,9 +211,12 @@ def report(fitter, nt, arrs, cfg, result):
     out = dict(result=result, results=results, fitted=(gm_r, gm_i, cm_r, cm_i), quality=None, errors=None, spectra=None, fixed=None)
     if cfg.fit_quality:
         out["quality"] = fitter.fit_quality(gm_r, gm_i)
-    if errs is not None and (errs["with_gains"] or not cfg.freeze_model):
+    if errs is not None and (errs["with_gains"] or errs["basis_gains"] or not cfg.freeze_model):
         fitter.set_params(gm_r, gm_i)  # the reported gains; the fit is over, the next one sets its own
         out["errors"] = fitter.fit_errors(ridge=errs["ridge"], model_var=errs["samples"], gain_var=errs["with_gains"], coeffs=not cfg.freeze_model)
+        if errs["basis_gains"]:  # the error bars of basis gains, and the parameters they spent (one per row of y)
+            basis = fitter.gain_basis_errors(ridge=errs["ridge"], y_var=False)
+            out["errors"].update(gain_var=basis["gain_var"], gain_dof=basis["gain_dof"])
         out["errors"]["chisq_bl"] = (out["quality"] if out["quality"] is not None else fitter.fit_quality(gm_r, gm_i))["chisq_bl"]
     if dspec is not None:  # every slice (a joint fit: every time) has bins of its own: bin_of_bl encodes (t, length bin)
         out["spectra"] = fitter.delay_spectrum(dspec["op"], dspec["norm_f"], calibrated=dspec["calibrated"], bin_of_bl=cal.delay_spectrum_slice_bins(dspec, nt),
@@ -251,7 +254,11 @@ def write(cfg, sl, t, out):
         e = {k: e[k][{"gain_var": ga, "coeff_var": coefs}.get(k, rows)] for k in ("coeff_var", "model_var", "leverage_bl", "nsamp_bl", "gain_var", "chisq_bl") if k in e}
         if "coeff_var" in e:  # (the library counts over the batch: a slice's singular groups are those it left an all-zero coeff_var)
             e["nsingular"] = sum(1 for g in range(prob.ngrps) if not np.any(e["coeff_var"][prob.grp_coff[g] : prob.grp_coff[g + 1]]))
-        cal.insert_fit_errors(errs["gain_std"], gains, hist, time, pol, e, e["chisq_bl"], rms, prob)
+        dof, joint = out["errors"].get("gain_dof"), cfg.gain_time_basis is not None
+        if dof is not None and not joint:
+            dof = dof[ga]
+        # (a joint fit shares an antenna's coefficients among its times: each is charged its share of them)
+        cal.insert_fit_errors(errs["gain_std"], gains, hist, time, pol, e, e["chisq_bl"], rms, prob, gain_dof=dof, ntimes=len(out["results"]) if joint else 1)
     if out["fixed"] is not None:
         hist["degeneracies"] = entry = cal.degeneracy_entry(out["fixed"], t, cfg.degen)
         if errs is not None and errs["gain_std"] is not None:  # the slice's plane of gain_std follows the gains: times e^{-eta}

@@ -454,7 +454,7 @@ class HipFitSolver:
         ``model_var=False`` leaves the ``[nbls, nfreqs]`` plane out (it is as large as the data); ``gain_var=False`` skips the antenna
         part; ``coeffs=False`` skips the coefficient part (``coeff_var``, ``model_var``, ``leverage_bl``).  With a gain basis attached
         ``gain_var=True`` raises: the variance of a basis gain is ``b_f^T N_a^-1 b_f`` with the projected ``N_a``, which is not
-        computed.  The parameters, the optimizer's slots, the weights and the loop state are untouched.  Under an exchange only
+        computed here but by ``gain_basis_errors``.  The parameters, the optimizer's slots, the weights and the loop state are untouched.  Under an exchange only
         ``den`` is summed over the ranks (one ``[nants, nfreqs]`` float64 plane); every other output is this rank's own rows and groups.
         Returns a dict of the arrays asked for plus ``nsolved`` and ``nsingular``."""
         out = {}
@@ -469,6 +469,46 @@ class HipFitSolver:
         cnt = _lib.FitErrorsCounts()
         _lib.check(self._lib.cal_solver_fit_errors(self._h, float(ridge), *(_ptr(out.get(k)) for k in ("coeff_var", "model_var", "leverage_bl",
                                                                                                       "nsamp_bl", "gain_var")), C.byref(cnt)))
+        out["nsolved"], out["nsingular"] = int(cnt.nsolved), int(cnt.nsingular)
+        return out
+
+    def gain_basis_errors(self, ridge=1e-6, y_var=True):
+        """The error bars of gains confined to a basis at the solver's current parameters (cal_solver_gain_basis_errors): the inverse
+        of the projected curvature matrix of ``solve_gain_coeffs`` / ``solve_gain_time_coeffs``.  ``den[row][f]`` is ``solve_gains``'
+        per-row sum (autocorrelations left out), ``shift = ridge tr N / n``.  With a frequency basis ``B [nfreqs, K]``, per antenna
+        row ``a`` (``n = K``)::
+
+            N_a = B^T diag(den_a) B     N_r = N_a + shift I     L L^T = N_r     W = L^-1
+            y_var[a][k]    = sum_i W[i][k]^2                        (variance of the complex y_k)
+            gain_var[a][f] = |W b_f|^2 = b_f^T N_r^-1 b_f           (b_f: row f of B), flagged channels included: the basis interpolates
+            gain_dof[a]    = n - shift sum_k y_var[a][k]            (= tr(N_a N_r^-1): complex parameters spent)
+
+        with a time basis ``Bt [T, L]`` on top, per antenna ``a``, ``n = L K``, index ``l K + k``, ``N_a`` as
+        ``solve_gain_time_coeffs`` forms it::
+
+            gain_var[t Na + a][f] = |W (Bt[t,:] (x) b_f)|^2         y_var[a][l][k] = sum_i W[i][l K + k]^2
+
+        and with a time basis alone, per (antenna, channel), ``L x L``, in float64 throughout::
+
+            N_{a,f}[l,l'] = sum_t Bt[t,l] Bt[t,l'] den[t,a,f]       y_var[a][l][f] = (N_r^-1)[l][l]
+            gain_var[t Na + a][f] = Bt[t,:] N_r^-1 Bt[t,:]^T        gain_dof[a] = sum over the solved f of (L - shift_f sum_l y_var[a][l][f])
+
+        All float64, variances for unit noise scale, CONDITIONAL on the other antennas and the model like ``fit_errors``'
+        ``gain_var``, which ``B = I`` reproduces.  A singular system (an antenna row, an antenna, or an (antenna, channel) pair
+        under a time basis alone: no unflagged cross-correlation, or a non-positive pivot) keeps zeros in all outputs and counts in
+        ``nsingular``.  ``y_var=False`` leaves ``y_var`` out.  Needs a gain basis (``set_gain_basis``, ``set_gain_time_basis``).
+        The parameters, ``y``, the optimizer's slots and the loop state are untouched; sums run in a fixed order, so two calls give
+        the same bits.  Under an exchange only ``den`` is summed over the ranks (one ``[nants, nfreqs]`` float64 plane) and every
+        rank computes the same planes.  Returns a dict: ``gain_var`` ``[nants, nfreqs]``, ``y_var`` in the shape of
+        ``get_gain_coeffs``, ``gain_dof`` (one per row of ``y``), ``nsolved``, ``nsingular``."""
+        shape = self._gain_coeff_shape()
+        out = dict(gain_var=np.empty((self.nants, self.nfreqs), dtype=np.float64))
+        if y_var:
+            out["y_var"] = np.empty(shape, dtype=np.float64)
+        out["gain_dof"] = np.empty(shape[0], dtype=np.float64)
+        cnt = _lib.FitErrorsCounts()
+        _lib.check(self._lib.cal_solver_gain_basis_errors(self._h, float(ridge), _ptr(out["gain_var"]), _ptr(out.get("y_var")), _ptr(out["gain_dof"]),
+                                                          C.byref(cnt)))
         out["nsolved"], out["nsingular"] = int(cnt.nsolved), int(cnt.nsingular)
         return out
 

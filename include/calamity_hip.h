@@ -212,7 +212,8 @@ int cal_debug_plan(int dtype, const cal_problem_desc* d, int what, void* out, in
  * 20 / 21: the antenna lists without autocorrelations (ptr; int2 entries).
  * 30: the row chunks of cal_solver_solve_gain_coeffs (L = 0) and cal_solver_solve_gain_time_coeffs.  On entry `out` holds int64 K, L, T
  *   (vectors of the frequency basis, of the time basis, times; nants must be a multiple of T); on return int64 rows per chunk, in_lds,
- *   the Cholesky launch's LDS bytes, unknowns per row, elements per row of M and N (dtype) and of the double scratch. */
+ *   the Cholesky launch's LDS bytes, unknowns per row, elements per row of M and N (dtype) and of the double scratch.
+ * 31: the row chunks of cal_solver_gain_basis_errors, in and out as 30 plus an eighth number: elements per row of W (dtype). */
 int cal_debug_solve_plan(int dtype, const cal_problem_desc* d, int64_t scratch_bytes, int what, void* out, int64_t cap_bytes, int64_t* bytes);
 /* Host only, like cal_debug_plan: what cal_solver_delay_spectrum and cal_solver_fix_degeneracies plan before they launch
  * (csrc/report_plan.hpp) for the problem `d` and a solver of `dtype`.  For tests (tests/test_report_plan_host.py).  The call is described
@@ -625,7 +626,8 @@ int cal_solver_set_coeff_solve_scratch(cal_solver* s, int64_t bytes);
  *   ridge >= 0 and finite (CAL_ERR_INVALID); problem, data, coefficients and gains must be set (CAL_ERR_STATE).
  * Works with nslices > 1, bl_alias, groups of several baselines on several row blocks, both layouts, every kernel path and folded
  * tiles.  The coefficient outputs work with a frequency or time gain basis attached (the expanded gains are read); gain_var then
- * fails with CAL_ERR_UNSUPPORTED: the variance of a basis gain is b_f^T N_a^-1 b_f with the projected N_a, which is not computed here.
+ * fails with CAL_ERR_UNSUPPORTED: the variance of a basis gain is b_f^T N_a^-1 b_f with the projected N_a, which is not computed here
+ * but by cal_solver_gain_basis_errors below.
  * The groups are worked through in chunks under the bound of cal_solver_set_coeff_solve_scratch (N, the factor in double and W).
  * Like cal_solver_fit_quality it puts the loop state back: a run continued after the call is bit-identical to one without it.
  * Under a communicator or exchange hook every fitting group belongs to one rank and each rank fills its own rows: the coefficient
@@ -634,6 +636,34 @@ int cal_solver_set_coeff_solve_scratch(cal_solver* s, int64_t bytes);
 typedef struct cal_fit_errors_counts { int32_t nsolved; int32_t nsingular; } cal_fit_errors_counts;
 int cal_solver_fit_errors(cal_solver* s, double ridge, double* coeff_var, double* model_var, double* leverage_bl, double* nsamp_bl,
                           double* gain_var, cal_fit_errors_counts* counts);
+/* The error bars of gains confined to a basis (no counterpart in the reference): the inverse of the projected curvature matrix that
+ * cal_solver_solve_gain_coeffs and cal_solver_solve_gain_time_coeffs build, at the solver's current parameters.  In their notation
+ * (den[row][f] of cal_solver_solve_gains, autocorrelations left out, summed over the ranks; shift = ridge tr N / n); conditional on the
+ * other antennas and the model like gain_var of cal_solver_fit_errors, which B = I reproduces (1 / den):
+ *   frequency basis B [nfreqs][K], per antenna row a (n = K):
+ *     N_a = B^T diag(den_a) B     N_r = N_a + shift I     L L^T = N_r     W = L^-1
+ *     y_var[a][k]    = sum_i W[i][k]^2                        (variance of the complex y_k)
+ *     gain_var[a][f] = |W b_f|^2 = b_f^T N_r^-1 b_f           (b_f: row f of B), every f < nfreqs, flagged channels included
+ *     gain_dof[a]    = n - shift sum_k y_var[a][k]            (= tr(N_a N_r^-1): complex parameters spent)
+ *   time x frequency basis Bt [T][L], per antenna a, n = L K, index l K + k, N_a[(l,k),(l',k')] = sum_t Bt[t,l] Bt[t,l'] M_{t,a}[k,k']:
+ *     gain_var[t Na + a][f] = |W (Bt[t,:] (x) b_f)|^2         y_var[a][l][k] = sum_i W[i][l K + k]^2        gain_dof[a] as above
+ *   time basis alone, per (antenna, channel), L x L:
+ *     N_{a,f}[l,l'] = sum_t Bt[t,l] Bt[t,l'] den[t,a,f]       y_var[a][l][f] = (N_r^-1)[l][l]
+ *     gain_var[t Na + a][f] = Bt[t,:] N_r^-1 Bt[t,:]^T        gain_dof[a] = sum over the solved f of (L - shift_f sum_l y_var[a][l][f])
+ * Outputs, all doubles, variances for unit noise scale, any may be NULL (its work is skipped): gain_var [nants][nfreqs];
+ * y_var [y_rows][L or 1][K, or nfreqs without a frequency basis], unpadded; gain_dof [y_rows] (y_rows: nants, or Na under a time basis).
+ * A system (an antenna row, an antenna, or an (antenna, channel) pair under a time basis alone) that is singular by the solves' tests
+ * (tr <= 0, a pivot <= 0, or not finite) leaves zeros in all its outputs and counts in nsingular, a solved one in nsolved.  N is formed
+ * in the solver's dtype (the solves' kernels as they are), factorised in double; W is rounded to the solver's dtype once and |W x|^2
+ * runs on the matrix cores, its squares summed in double; the time basis alone runs in double throughout.  Every sum has a fixed order:
+ * two calls give the same bits.  The rows are worked through in chunks under the bound of cal_solver_set_coeff_solve_scratch (the
+ * solves' buffers and W); the results do not depend on it.
+ *   ridge >= 0 and finite (CAL_ERR_INVALID); problem, data, coefficients and gains must be set, and a gain basis
+ *   (cal_solver_set_gain_basis, cal_solver_set_gain_time_basis): CAL_ERR_STATE without one -- cal_solver_fit_errors gives gain_var of free gains.
+ * y, the gains, the optimizer's slots and the loop state are untouched: a run continued after the call is bit-identical to one without
+ * it.  y is replicated and den is summed over the ranks in ONE all-reduce of nants nfreqs doubles (CAL_XCHG_F64, CAL_XCHG_SUM), so
+ * every rank computes the same planes. */
+int cal_solver_gain_basis_errors(cal_solver* s, double ridge, double* gain_var, double* y_var, double* gain_dof, cal_fit_errors_counts* counts);
 /* Where the power of data, model and residual sits in DELAY (no counterpart in the reference): the transform along frequency of
  * every baseline row as one complex matrix product against a small operator shared by all rows, from the planes the solver holds.
  * For baseline row b with antennas (i, j) and channel f, in solver units:
