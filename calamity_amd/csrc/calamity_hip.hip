@@ -266,17 +266,16 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
   DevBuf fe_grp, fe_order, fe_work, fe_woff, fe_lwork, fe_n, fe_d, fe_w, fe_rhs, fe_ok, fe_part, fe_out, fe_mv;
   std::vector<GroupChunk> fe_chunks;
   int fe_npieces = 0;
-  // solve_gain_coeffs (gain_basis_solve_kernels.hpp): N_a of a chunk of antenna rows in T (gbs_n), its factor in double where it does not
-  // fit LDS (gbs_d), rhs [nants][2][K] T, the two counters; the chunks share cs_bound
-  DevBuf gbs_n, gbs_d, gbs_rhs, gbs_cnt;
-  // solve_gain_time_coeffs (gain_time_solve_kernels.hpp), per chunk of antennas: M_{t,a} [T][ca][K][K] T (gts_m), N_a [ca][n][n] and rhs_a
-  // [ca][2][n] T (gts_n, gts_rhsa), the factor in double where it leaves LDS or, without a frequency basis, the channel systems beyond
-  // kTimeTile vectors (gts_d); the per-row right-hand sides [nants][2][K] T (gts_rhs), the two counters; the chunks share cs_bound
-  DevBuf gts_m, gts_n, gts_rhsa, gts_d, gts_rhs, gts_cnt;
-  // gain_basis_errors (gain_error_kernels.hpp), per chunk of rows (antenna rows; antennas under a time basis): the buffers of the two
-  // solves above under its own chunking (gbe_m, gbe_n, gbe_rhsa, gbe_d, gbe_rhs), W [rows][np][np] T (gbe_w), ok [y_rows] and the two
-  // counters (gbe_ok), the outputs gain_var | y_var | gain_dof | the channels' dof of a time basis alone, doubles (gbe_out)
-  DevBuf gbe_m, gbe_n, gbe_rhsa, gbe_d, gbe_rhs, gbe_w, gbe_ok, gbe_out;
+  // The projected gain systems of solve_gain_coeffs, solve_gain_time_coeffs and gain_basis_errors (gain_basis_solve_kernels.hpp,
+  // gain_time_solve_kernels.hpp, gain_error_kernels.hpp), one set for the three (reserve_gain_systems sizes it from a call's RowChunks,
+  // enqueue_gain_systems fills it), per chunk of rows (antenna rows; antennas under a time basis): M_{t,a} [T][ca][K][K] T of a time
+  // basis over a frequency basis (pg_m), N_a [ca][n][n] T (pg_n) and under both bases rhs_a [ca][2][n] T (pg_rhsa), the factor in double
+  // where it leaves LDS or, without a frequency basis, the channel systems beyond kTimeTile vectors (pg_d); the per-row right-hand sides
+  // [nants][2][K] T (pg_rhs) and the two counters of a sweep (pg_cnt).  The chunks share cs_bound.
+  DevBuf pg_m, pg_n, pg_rhsa, pg_d, pg_rhs, pg_cnt;
+  // gain_basis_errors' own, beside the set above: W [rows][np][np] T (gbe_w), ok [y_rows] and the two counters (gbe_ok), the outputs
+  // gain_var | y_var | gain_dof | the channels' dof of a time basis alone, doubles (gbe_out)
+  DevBuf gbe_w, gbe_ok, gbe_out;
   std::vector<uint8_t> held;                   // hold_slices: [nslices], 1 = the slice enters every later run as stopped (empty: none)
   DevBuf fq_out, fq_gains;                     // fit_quality: chisq_ant | wsum_ant ([nants][nfreqs] doubles each, the exchange payload) | chisq_bl | wsum_bl; gains given for one evaluation
   DevBuf rw_w0, rw_out;                        // robust_weights: w0, the weights as set_data gave them (first call after a set_data); scale_bl | ndown_bl ([nbls] doubles each)
@@ -1284,15 +1283,10 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     gb_nvec = gb_kpad = 0;
     tb_T = tb_L = tb_lpad = tb_tpad = tb_na = 0;
     for (DevBuf* b : {&gb_B, &gb_Bt, &gb_g0, &gb_y, &gb_ym, &gb_yv, &gb_ysnap, &gb_proj, &tb_B, &tb_Bt, &tb_z, &tb_pf}) b->release();
-    release_gain_coeff_solve();
+    release_gain_systems();
   }
-  void release_gain_coeff_solve() {  // the scratch of solve_gain_coeffs: sized again by the next call
-    for (DevBuf* b : {&gbs_n, &gbs_d, &gbs_rhs, &gbs_cnt}) b->release();
-    release_gain_time_solve();
-  }
-  void release_gain_time_solve() {  // the scratch of solve_gain_time_coeffs: sized again by the next call
-    for (DevBuf* b : {&gts_m, &gts_n, &gts_rhsa, &gts_d, &gts_rhs, &gts_cnt}) b->release();
-    for (DevBuf* b : {&gbe_m, &gbe_n, &gbe_rhsa, &gbe_d, &gbe_rhs, &gbe_w, &gbe_ok, &gbe_out}) b->release();  // and of gain_basis_errors
+  void release_gain_systems() {  // the scratch of the two basis sweeps and of gain_basis_errors: sized again by the next call
+    for (DevBuf* b : {&pg_m, &pg_n, &pg_rhsa, &pg_d, &pg_rhs, &pg_cnt, &gbe_w, &gbe_ok, &gbe_out}) b->release();
   }
   // the fit starts from the gains the solver holds now: g0 := gains, y := 0 (and its snapshot with it)
   int rebase_gain_basis() {
@@ -1305,7 +1299,7 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
   // after either setter changed its basis: the y arrays in the shape the two bases now give them, g0 := gains, y := 0, moments and t zeroed
   int reshape_gain_coeffs() {
     for (DevBuf* b : {&gb_g0, &gb_y, &gb_ym, &gb_yv, &gb_ysnap, &gb_proj, &tb_z, &tb_pf}) b->release();
-    release_gain_time_solve();
+    release_gain_systems();
     if (yb_on()) {
       const size_t ybytes = (size_t)y_rows() * y_row() * sizeof(T2);
       CAL_TRY(gb_g0.alloc(gains.bytes, false));
@@ -2590,7 +2584,7 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     if (bytes < 0) return fail(CAL_ERR_INVALID, "set_coeff_solve_scratch: negative bound");
     cs_bound = bytes == 0 ? kCsScratchDefault : bytes;
     release_coeff_solve();
-    release_gain_coeff_solve();
+    release_gain_systems();
     return CAL_OK;
   }
   // The plan of solve_plan.hpp for this problem and bound, uploaded at the first call.  Every chunk reuses the two scratch buffers from
@@ -2737,9 +2731,47 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     return CAL_OK;
   }
 
+  // ---- the projected gain systems: solve_gain_coeffs, solve_gain_time_coeffs, gain_basis_errors ------------------
+  // The pg_ set for the chunks of rc; the buffers only grow.  No call can read what another left behind: gain_basis_gram_kernel and
+  // gain_time_kron_kernel write every element of every row that a factor or Kronecker kernel of the same chunk then reads (N_a and M_{t,a}
+  // on and below the diagonal, which is all the readers touch; both rhs rows), rows of a masked slice are skipped by the Gram and the
+  // factor kernel alike, the factor in pg_d is written (normal_chol_load, ChanSystem::zero) before it is read, and a sweep zeroes the
+  // counters itself.  pg_rhs and pg_cnt are zero-filled when allocated, as they always were.
+  int reserve_gain_systems(const RowChunks& rc) {
+    if (rc.m_row) {
+      CAL_TRY(pg_m.reserve((size_t)rc.rows * rc.m_row * sizeof(T), false));
+      CAL_TRY(pg_rhsa.reserve(2 * (size_t)rc.rows * rc.n * sizeof(T), false));
+    }
+    if (rc.n_row) {
+      CAL_TRY(pg_n.reserve((size_t)rc.rows * rc.n_row * sizeof(T), false));
+      CAL_TRY(pg_rhs.reserve(2 * (size_t)nants * gb_nvec * sizeof(T)));
+      CAL_TRY(allow_chol_lds(&gain_basis_chol_kernel<T>));
+    }
+    CAL_TRY(pg_d.reserve(std::max<size_t>(8, (size_t)rc.rows * rc.d_row * sizeof(double)), false));
+    return pg_cnt.reserve(2 * sizeof(int));
+  }
+  // Enqueues the projected normal matrices of rows [a0, a0 + ca) (antenna rows; antennas under a time basis) and their right-hand
+  // sides: without a time basis gain_basis_gram_kernel into pg_n; with both bases the Gram of the rows of every time into pg_m
+  // ([t][rel][K][K]: one launch over all rows when the chunk holds every antenna, their rows then lie side by side; else one per
+  // time), then gain_time_kron_kernel into pg_n and pg_rhsa.  mask: the slice mask of solve_gain_coeffs, null otherwise.
+  void enqueue_gain_systems(int a0, int ca, const unsigned char* mask) {
+    const int K = gb_nvec, nb = (K + kNsBlock - 1) / kNsBlock, npairs = nb * (nb + 1) / 2;
+    auto gram = [&](int row0, int rows, T* nmat) {
+      hipLaunchKernelGGL(gain_basis_gram_kernel<T>, dim3((unsigned)rows * npairs), dim3(256), 0, stream, gb_Bt.as<T>(), gs_out.as<double>(), gains.as<T2>(),
+                         nmat, pg_rhs.as<T>(), mask, na_slice, row0, npairs, K, gb_kpad, nants, nfreqs, fpad);
+    };
+    if (!tb_on()) return gram(a0, ca, pg_n.as<T>());
+    const int na = tb_na, Tn = tb_T, L = tb_L;
+    if (ca == na) gram(0, nants, pg_m.as<T>());
+    else
+      for (int t = 0; t < Tn; ++t) gram(t * na + a0, ca, pg_m.as<T>() + (size_t)t * ca * K * K);
+    hipLaunchKernelGGL(gain_time_kron_kernel<T>, dim3((unsigned)ca * L, (L + kTimeTile - 1) / kTimeTile), dim3(256), 0, stream, pg_m.as<T>(),
+                       pg_rhs.as<T>(), tb_B.as<T>(), pg_n.as<T>(), pg_rhsa.as<T>(), a0, ca, na, Tn, L, tb_lpad, K);
+  }
+
   // cal_solver_gain_basis_errors: fit_errors' sequence for gain_var (the model pass, gain_solve_rows_kernel, gain_solve_ant_kernel and
-  // the exchange of its den plane), then per chunk of rows gain_basis_gram_kernel as it is (its rhs goes nowhere anyone reads),
-  // gain_time_kron_kernel as it is under a time basis, gain_error_factor_kernel and gain_error_var_kernel; a time basis alone runs
+  // the exchange of its den plane), then per chunk of rows enqueue_gain_systems (the kernels of the sweeps as they are),
+  // gain_error_factor_kernel and gain_error_var_kernel; a time basis alone runs
   // gain_time_chan_var_kernel and gain_error_dof_kernel instead (gain_error_kernels.hpp).  The chunks count W (solve_plan.hpp).  y is
   // replicated and den is summed over the ranks, so every rank computes the same planes: no collective beyond antenna_sweep's own.
   int gain_basis_errors(double ridge, double* gain_var, double* y_var, double* gain_dof, cal_fit_errors_counts* counts) override {
@@ -2756,17 +2788,11 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     const size_t nant_out = (size_t)nants * nfreqs;
     const size_t n_yvar = (size_t)na * Lr * (gb_on() ? K : nfreqs);
     const size_t n_chan = gb_on() ? 0 : (size_t)na * nfreqs;  // the channels' dof of a time basis alone
+    CAL_TRY(reserve_gain_systems(rc));
     if (gb_on()) {
-      if (tb_on()) {
-        CAL_TRY(gbe_m.reserve((size_t)rc.rows * rc.m_row * sizeof(T), false));
-        CAL_TRY(gbe_rhsa.reserve(2 * (size_t)rc.rows * rc.n * sizeof(T), false));
-      }
-      CAL_TRY(gbe_n.reserve((size_t)rc.rows * rc.n_row * sizeof(T), false));
-      CAL_TRY(gbe_rhs.reserve(2 * (size_t)nants * K * sizeof(T)));
       CAL_TRY(gbe_w.reserve((size_t)rc.rows * rc.x_row * sizeof(T), false));
       CAL_TRY(allow_chol_lds(&gain_error_factor_kernel<T>));
     }
-    CAL_TRY(gbe_d.reserve(std::max<size_t>(8, (size_t)rc.rows * rc.d_row * sizeof(double)), false));
     CAL_TRY(gbe_ok.reserve(((size_t)na + 2) * sizeof(int)));
     CAL_TRY(gbe_out.reserve((nant_out + n_yvar + (size_t)na + n_chan) * sizeof(double), false));
     double* o_gv = gbe_out.as<double>();
@@ -2781,31 +2807,20 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     // a singular system keeps zeros
     HIP_TRY(hipMemsetAsync(gbe_ok.p, 0, ((size_t)na + 2) * sizeof(int), stream));
     HIP_TRY(hipMemsetAsync(gbe_out.p, 0, (nant_out + n_yvar + (size_t)na + n_chan) * sizeof(double), stream));
-    const int nb = (K + kNsBlock - 1) / kNsBlock, npairs = nb * (nb + 1) / 2;
     const int npieces = (nfreqs + kFePiece - 1) / kFePiece;
     for (int a0 = 0; a0 < na; a0 += rc.rows) {
       const int ca = std::min(rc.rows, na - a0);
       if (gb_on()) {
-        if (!tb_on()) {
-          hipLaunchKernelGGL(gain_basis_gram_kernel<T>, dim3((unsigned)ca * npairs), dim3(256), 0, stream, gb_Bt.as<T>(), gs_out.as<double>(), gains.as<T2>(),
-                             gbe_n.as<T>(), gbe_rhs.as<T>(), (const unsigned char*)nullptr, na_slice, a0, npairs, K, gb_kpad, nants, nfreqs, fpad);
-        } else {
-          for (int t = 0; t < Tn; ++t)  // M [t][rel][K][K]
-            hipLaunchKernelGGL(gain_basis_gram_kernel<T>, dim3((unsigned)ca * npairs), dim3(256), 0, stream, gb_Bt.as<T>(), gs_out.as<double>(),
-                               gains.as<T2>(), gbe_m.as<T>() + (size_t)t * ca * K * K, gbe_rhs.as<T>(), (const unsigned char*)nullptr, na_slice,
-                               t * na + a0, npairs, K, gb_kpad, nants, nfreqs, fpad);
-          hipLaunchKernelGGL(gain_time_kron_kernel<T>, dim3((unsigned)ca * L, (L + kTimeTile - 1) / kTimeTile), dim3(256), 0, stream, gbe_m.as<T>(),
-                             gbe_rhs.as<T>(), tb_B.as<T>(), gbe_n.as<T>(), gbe_rhsa.as<T>(), a0, ca, na, Tn, L, tb_lpad, K);
-        }
-        hipLaunchKernelGGL(gain_error_factor_kernel<T>, dim3(ca), dim3(256), rc.lds, stream, gbe_n.as<T>(), gbe_d.as<double>(), gbe_w.as<T>(),
+        enqueue_gain_systems(a0, ca, nullptr);  // (the right-hand sides it also forms go nowhere anyone reads)
+        hipLaunchKernelGGL(gain_error_factor_kernel<T>, dim3(ca), dim3(256), rc.lds, stream, pg_n.as<T>(), pg_d.as<double>(), gbe_w.as<T>(),
                            y_var ? o_yv : nullptr, gain_dof ? o_dof : nullptr, ok, a0, n, ridge, dcnt, kCsLdsDoubles);
         if (gain_var)
           hipLaunchKernelGGL(gain_error_var_kernel<T>, dim3((unsigned)Tn * ca * npieces), dim3(256), 0, stream, gbe_w.as<T>(), gb_Bt.as<T>(),
                              tb_on() ? tb_B.as<T>() : (const T*)nullptr, ok, o_gv, a0, ca, na, Lr, tb_lpad, K, nfreqs, fpad, npieces);
       } else {
         const unsigned blocks = (unsigned)(((long long)ca * nfreqs + 255) / 256);
-        auto* chan = L <= kTimeTile ? gain_time_chan_var_kernel<T, kTimeTile> : gain_time_chan_var_kernel<T, 0>;  // the channel systems in registers, or in gbe_d
-        hipLaunchKernelGGL(chan, dim3(blocks), dim3(256), 0, stream, gs_out.as<double>(), tb_B.as<T>(), gbe_d.as<double>(), y_var ? o_yv : nullptr,
+        auto* chan = L <= kTimeTile ? gain_time_chan_var_kernel<T, kTimeTile> : gain_time_chan_var_kernel<T, 0>;  // the channel systems in registers, or in pg_d
+        hipLaunchKernelGGL(chan, dim3(blocks), dim3(256), 0, stream, gs_out.as<double>(), tb_B.as<T>(), pg_d.as<double>(), y_var ? o_yv : nullptr,
                            gain_var ? o_gv : nullptr, gain_dof ? o_chan : nullptr, a0, ca, na, Tn, L, tb_lpad, nfreqs, ridge, dcnt);
       }
       HIP_TRY(hipGetLastError());
@@ -2827,8 +2842,8 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     return CAL_OK;
   }
 
-  // cal_solver_solve_gain_coeffs: solve_gains' sequence up to the exchanged planes, then per chunk of antenna rows gain_basis_gram_kernel
-  // and gain_basis_chol_kernel (gain_basis_solve_kernels.hpp), then the gains of the selected slices rebuilt from y.  Every chunk of a
+  // cal_solver_solve_gain_coeffs: solve_gains' sequence up to the exchanged planes, then per chunk of antenna rows enqueue_gain_systems
+  // (gain_basis_gram_kernel) and gain_basis_chol_kernel (gain_basis_solve_kernels.hpp), then the gains of the selected slices rebuilt from y.  Every chunk of a
   // sweep reads the old gains: they are rebuilt behind the last one.  y is replicated and the planes are summed over the ranks, so
   // every rank computes the same update: no collective beyond solve_gains' own.
   int solve_gain_coeffs(const cal_gain_coeff_solve_desc* d, cal_gain_coeff_solve_result* res) override {
@@ -2844,25 +2859,19 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     // chunks of antenna rows whose N_a (T) and factor (double, only where it does not fit LDS) stay under cs_bound (solve_plan.hpp)
     const int K = gb_nvec;
     const RowChunks rc = plan_row_chunks(K, 0, 0, nfreqs, sizeof(T), cs_bound, nants);
-    CAL_TRY(gbs_n.reserve((size_t)rc.rows * rc.n_row * sizeof(T), false));
-    CAL_TRY(gbs_d.reserve((size_t)rc.rows * rc.d_row * sizeof(double), false));
-    CAL_TRY(gbs_rhs.reserve(2 * (size_t)nants * K * sizeof(T)));
-    CAL_TRY(gbs_cnt.reserve(2 * sizeof(int)));
-    CAL_TRY(allow_chol_lds(&gain_basis_chol_kernel<T>));
+    CAL_TRY(reserve_gain_systems(rc));
     const unsigned char* mask = nullptr;
     CAL_TRY(upload_slice_mask(d->slice_mask, &mask));
     RowPlanes P;
     CAL_TRY(gain_planes(P));
-    const int nb = (K + kNsBlock - 1) / kNsBlock, npairs = nb * (nb + 1) / 2;
     for (int k = 0; k < d->nsweeps; ++k) {
       CAL_TRY(antenna_sweep(P, 3));
-      HIP_TRY(hipMemsetAsync(gbs_cnt.p, 0, 2 * sizeof(int), stream));
+      HIP_TRY(hipMemsetAsync(pg_cnt.p, 0, 2 * sizeof(int), stream));
       for (int a0 = 0; a0 < nants; a0 += rc.rows) {
         const int nr = std::min(rc.rows, nants - a0);
-        hipLaunchKernelGGL(gain_basis_gram_kernel<T>, dim3((unsigned)nr * npairs), dim3(256), 0, stream, gb_Bt.as<T>(), gs_out.as<double>(), gains.as<T2>(),
-                           gbs_n.as<T>(), gbs_rhs.as<T>(), mask, na_slice, a0, npairs, K, gb_kpad, nants, nfreqs, fpad);
-        hipLaunchKernelGGL(gain_basis_chol_kernel<T>, dim3(nr), dim3(256), rc.lds, stream, gbs_n.as<T>(), gbs_rhs.as<T>(), gbs_d.as<double>(),
-                           gb_y.as<T2>(), mask, na_slice, a0, K, gb_kpad, d->damping, d->ridge, gbs_cnt.as<int>(), kCsLdsDoubles);
+        enqueue_gain_systems(a0, nr, mask);
+        hipLaunchKernelGGL(gain_basis_chol_kernel<T>, dim3(nr), dim3(256), rc.lds, stream, pg_n.as<T>(), pg_rhs.as<T>(), pg_d.as<double>(),
+                           gb_y.as<T2>(), mask, na_slice, a0, a0, 1, K, gb_kpad, d->damping, d->ridge, pg_cnt.as<int>(), kCsLdsDoubles);
         HIP_TRY(hipGetLastError());
       }
       // gains = g0 + B y for the selected slices (runs of neighbouring slices in one launch each): the others keep their bits
@@ -2876,11 +2885,12 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
       HIP_TRY(hipGetLastError());
     }
     const size_t yper = (size_t)na_slice * gb_kpad * 2;  // reals of the y slots per slice
-    return finish_solve(&gbs_cnt, res, d->reset_gain_moments, [&] { return reset_slice_moments(d->slice_mask, gb_ym, gb_yv, yper, false); });
+    return finish_solve(&pg_cnt, res, d->reset_gain_moments, [&] { return reset_slice_moments(d->slice_mask, gb_ym, gb_yv, yper, false); });
   }
 
   // cal_solver_solve_gain_time_coeffs: solve_gain_coeffs' sequence up to the exchanged planes, then per chunk of antennas either
-  // gain_basis_gram_kernel (every row of the chunk: M_{t,a} and B^T r), gain_time_kron_kernel and gain_time_chol_kernel, or, without a
+  // enqueue_gain_systems (gain_basis_gram_kernel on every row of the chunk: M_{t,a} and B^T r; gain_time_kron_kernel) and
+  // gain_basis_chol_kernel over the L blocks of an antenna, or, without a
   // frequency basis, gain_time_chan_kernel (gain_time_solve_kernels.hpp); then the gains rebuilt from y.  Every chunk of a sweep reads
   // the old gains.  y is replicated and the planes are summed over the ranks: no collective beyond solve_gains' own.
   int solve_gain_time_coeffs(const cal_gain_time_solve_desc* d, cal_gain_time_solve_result* res) override {
@@ -2895,50 +2905,31 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     const int K = gb_nvec, L = tb_L, Tn = tb_T, na = tb_na;
     // chunks of antennas whose buffers stay under cs_bound (solve_plan.hpp)
     const RowChunks rc = plan_row_chunks(K, L, Tn, nfreqs, sizeof(T), cs_bound, na);
-    if (gb_on()) {
-      CAL_TRY(gts_m.reserve((size_t)rc.rows * rc.m_row * sizeof(T), false));
-      CAL_TRY(gts_n.reserve((size_t)rc.rows * rc.n_row * sizeof(T), false));
-      CAL_TRY(gts_rhsa.reserve(2 * (size_t)rc.rows * rc.n * sizeof(T), false));
-      CAL_TRY(gts_rhs.reserve(2 * (size_t)nants * K * sizeof(T)));
-    }
-    CAL_TRY(gts_d.reserve(std::max<size_t>(8, (size_t)rc.rows * rc.d_row * sizeof(double)), false));
-    CAL_TRY(gts_cnt.reserve(2 * sizeof(int)));
-    if (gb_on()) CAL_TRY(allow_chol_lds(&gain_time_chol_kernel<T>));
+    CAL_TRY(reserve_gain_systems(rc));
     RowPlanes P;
     CAL_TRY(gain_planes(P));
-    const int nb = (K + kNsBlock - 1) / kNsBlock, npairs = nb * (nb + 1) / 2;
     for (int k = 0; k < d->nsweeps; ++k) {
       CAL_TRY(antenna_sweep(P, 3));
-      HIP_TRY(hipMemsetAsync(gts_cnt.p, 0, 2 * sizeof(int), stream));
+      HIP_TRY(hipMemsetAsync(pg_cnt.p, 0, 2 * sizeof(int), stream));
       for (int a0 = 0; a0 < na; a0 += rc.rows) {
         const int ca = std::min(rc.rows, na - a0);
         if (gb_on()) {
-          if (ca == na) {  // the rows of every time lie side by side: one launch, M [t][a][K][K]
-            hipLaunchKernelGGL(gain_basis_gram_kernel<T>, dim3((unsigned)nants * npairs), dim3(256), 0, stream, gb_Bt.as<T>(), gs_out.as<double>(),
-                               gains.as<T2>(), gts_m.as<T>(), gts_rhs.as<T>(), (const unsigned char*)nullptr, na_slice, 0, npairs, K, gb_kpad, nants,
-                               nfreqs, fpad);
-          } else {
-            for (int t = 0; t < Tn; ++t)
-              hipLaunchKernelGGL(gain_basis_gram_kernel<T>, dim3((unsigned)ca * npairs), dim3(256), 0, stream, gb_Bt.as<T>(), gs_out.as<double>(),
-                                 gains.as<T2>(), gts_m.as<T>() + (size_t)t * ca * K * K, gts_rhs.as<T>(), (const unsigned char*)nullptr, na_slice,
-                                 t * na + a0, npairs, K, gb_kpad, nants, nfreqs, fpad);
-          }
-          hipLaunchKernelGGL(gain_time_kron_kernel<T>, dim3((unsigned)ca * L, (L + kTimeTile - 1) / kTimeTile), dim3(256), 0, stream, gts_m.as<T>(),
-                             gts_rhs.as<T>(), tb_B.as<T>(), gts_n.as<T>(), gts_rhsa.as<T>(), a0, ca, na, Tn, L, tb_lpad, K);
-          hipLaunchKernelGGL(gain_time_chol_kernel<T>, dim3(ca), dim3(256), rc.lds, stream, gts_n.as<T>(), gts_rhsa.as<T>(), gts_d.as<double>(),
-                             gb_y.as<T2>(), a0, L, K, gb_kpad, d->damping, d->ridge, gts_cnt.as<int>(), kCsLdsDoubles);
+          enqueue_gain_systems(a0, ca, nullptr);
+          hipLaunchKernelGGL(gain_basis_chol_kernel<T>, dim3(ca), dim3(256), rc.lds, stream, pg_n.as<T>(), pg_rhsa.as<T>(), pg_d.as<double>(),
+                             gb_y.as<T2>(), (const unsigned char*)nullptr, na_slice, a0, 0, L, K, gb_kpad, d->damping, d->ridge, pg_cnt.as<int>(),
+                             kCsLdsDoubles);
         } else {
           const unsigned blocks = (unsigned)(((long long)ca * nfreqs + 255) / 256);
-          auto* chan = L <= kTimeTile ? gain_time_chan_kernel<T, kTimeTile> : gain_time_chan_kernel<T, 0>;  // the channel systems in registers, or in gts_d
+          auto* chan = L <= kTimeTile ? gain_time_chan_kernel<T, kTimeTile> : gain_time_chan_kernel<T, 0>;  // the channel systems in registers, or in pg_d
           hipLaunchKernelGGL(chan, dim3(blocks), dim3(256), 0, stream, gs_out.as<double>(), gains.as<T2>(), tb_B.as<T>(), gb_y.as<T2>(),
-                             gts_d.as<double>(), a0, ca, na, Tn, L, tb_lpad, nfreqs, fpad, d->damping, d->ridge, gts_cnt.as<int>());
+                             pg_d.as<double>(), a0, ca, na, Tn, L, tb_lpad, nfreqs, fpad, d->damping, d->ridge, pg_cnt.as<int>());
         }
         HIP_TRY(hipGetLastError());
       }
       CAL_TRY(enqueue_expand(gb_y.as<T2>(), gains.as<T2>()));  // gains = g0 + Bt (x) (B) y, behind the last chunk
     }
     // (the times of an antenna share its coefficients: no slice mask, every y slot)
-    return finish_solve(&gts_cnt, res, d->reset_gain_moments, [&] { return reset_moment_slots(gb_ym, gb_yv, 0, 2 * (size_t)y_rows() * (size_t)y_row()); });
+    return finish_solve(&pg_cnt, res, d->reset_gain_moments, [&] { return reset_moment_slots(gb_ym, gb_yv, 0, 2 * (size_t)y_rows() * (size_t)y_row()); });
   }
 
   int init_coeffs(const void* sr, const void* si) override {

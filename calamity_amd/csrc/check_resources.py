@@ -13,8 +13,8 @@ CU to itself): no scratch and no spilled VGPRs there either (a few SGPR spills i
 instances of both dtypes), `gain_solve_rows_kernel`, `gain_solve_ant_kernel`,
 `gain_solve_apply_kernel` (gain_solve_kernels.hpp), `coeff_solve_rows_kernel`, `coeff_gram_kernel`, `coeff_chol_kernel`
 (coeff_solve_kernels.hpp), `gain_basis_gram_kernel`, `gain_basis_chol_kernel` (gain_basis_solve_kernels.hpp; both pairs are built on the
-shared Gram and Cholesky core of normal_solve.hpp), `gain_time_kron_kernel`, `gain_time_chol_kernel`, `gain_time_chan_kernel`
-(gain_time_solve_kernels.hpp), `fit_error_factor_kernel`, `fit_error_leverage_kernel`, `fit_error_rows_kernel` (fit_error_kernels.hpp),
+shared Gram and Cholesky core of normal_solve.hpp; the second is the factor step of the time-basis solve too), `gain_time_kron_kernel`,
+`gain_time_chan_kernel` (gain_time_solve_kernels.hpp, both instances), `fit_error_factor_kernel`, `fit_error_leverage_kernel`, `fit_error_rows_kernel` (fit_error_kernels.hpp),
 `gain_error_factor_kernel`, `gain_error_var_kernel`, `gain_time_chan_var_kernel`, `gain_error_dof_kernel` (gain_error_kernels.hpp), every `gn_*_kernel`
 (gauss_newton_kernels.hpp), every `lbfgs_*_kernel` (lbfgs_kernels.hpp): no scratch, no spilled VGPRs.
 `dspec_rows_kernel`, `dspec_transform_kernel`, `dspec_bin_kernel` (delay_spectrum_kernels.hpp), both dtypes: no scratch, no spilled VGPRs, and
@@ -56,7 +56,7 @@ for line in sys.stdin:
     if cur is not None and any(k in cur for k in ("gain_project_kernel", "gain_expand_kernel", "gain_time_project_kernel", "gain_time_expand_kernel",
                                              "quality_rows_kernel", "quality_ant_kernel", "robust_rows_kernel", "gain_solve_rows_kernel", "gain_solve_ant_kernel",
                                              "gain_solve_apply_kernel", "coeff_solve_rows_kernel", "coeff_gram_kernel", "coeff_chol_kernel",
-                                             "gain_basis_gram_kernel", "gain_basis_chol_kernel", "gain_time_kron_kernel", "gain_time_chol_kernel",
+                                             "gain_basis_gram_kernel", "gain_basis_chol_kernel", "gain_time_kron_kernel",
                                              "gain_time_chan_kernel", "fit_error_factor_kernel", "fit_error_leverage_kernel", "fit_error_rows_kernel",
                                              "gain_error_factor_kernel", "gain_error_var_kernel", "gain_time_chan_var_kernel", "gain_error_dof_kernel",
                                              "gn_tangent_rows_kernel", "gn_scale_kernel", "gn_data_kernel", "gn_precond_rows_kernel", "gn_precond_gain_kernel",
@@ -65,7 +65,7 @@ for line in sys.stdin:
                                              "gn_round_kernel", "lbfgs_pair_kernel", "lbfgs_reduce_kernel", "lbfgs_coeff_kernel", "lbfgs_direction_kernel",
                                              "lbfgs_trial_kernel", "lbfgs_armijo_kernel", "lbfgs_restore_kernel")):
         # the kernels around the update of a gain-basis fit, the two of the fit-quality pass, the one of the robust reweighting, the three of the gain solve, the three
-        # of the coefficient solve, the two of the gain-coefficient solve, the three of the time-basis solve, the three of the fit errors, the four of the basis-gain errors, those of the
+        # of the coefficient solve, the two of the gain-coefficient solve, the two of the time-basis solve beside them, the three of the fit errors, the four of the basis-gain errors, those of the
         # Gauss-Newton step and those of L-BFGS keep their accumulators in registers: no scratch
         m = re.search(r"remark:\s+(ScratchSize \[bytes/lane\]|VGPRs Spill): (\d+)", line)
         if m and int(m.group(2)) != 0:

@@ -12,6 +12,7 @@
 // with den = 0 of a non-singular antenna does move: the basis interpolates across it.  Two kernels behind gain_solve_ant_kernel:
 //   gain_basis_gram_kernel   N_a (lower triangle) and rhs_a of every antenna row on the matrix cores, in T, from the transposed basis copy
 //   gain_basis_chol_kernel   per antenna row, in double: Cholesky of N_a + ridge, both substitutions, the masked damped update of y
+//                            (also the factor step of gain_time_solve_kernels.hpp: L blocks of K unknowns per antenna, no mask)
 // r_a is evaluated in double from the double planes and rounded to T once; N_a and rhs_a are formed and accumulated in T in a fixed
 // order (no atomics on reals: two calls give the same bits); the factorisation, the substitutions and the update run in double for
 // both dtypes, the update is rounded once.  The Gram blocks and the factorisation are the shared core of normal_solve.hpp; the two
@@ -89,15 +90,19 @@ __global__ __launch_bounds__(256) void gain_basis_gram_kernel(const T* __restric
                        [&](int col, int row) { return rhs + ((long long)a * 2 + col) * K + row; });
 }
 
-// One workgroup per antenna row of the chunk: normal_chol_solve of normal_solve.hpp on the row's N_a and rhs_a, its [K + 2][ld]
-// matrix M in LDS when it fits `lds_doubles` and in the chunk's L2-resident scratch otherwise.  A singular row (tr N_a <= 0: no
-// unflagged cross-correlation) leaves its y alone and counts in counts[1]; a solved row counts in counts[0]; the rows of a slice whose
-// mask byte is 0 do neither.  The update y + damping delta is rounded to T once.
+// One workgroup per row of the chunk (an antenna row; under a time basis an antenna over all its times, L > 1 blocks of K unknowns):
+// normal_chol_solve of normal_solve.hpp on the row's N_a and rhs_a, n = L K, its [n + 2][ld] matrix M in LDS when it fits
+// `lds_doubles` and in the chunk's L2-resident scratch otherwise.  nmat [rel][n][n]; the right-hand sides are rows [2][n] of rhs, the
+// row of chunk row rel being rhs_row0 + rel: rhs_row0 = a0 for the per-row buffer [nants][2][K] gain_basis_gram_kernel fills, 0 for the
+// chunk's own [ca][2][n] of gain_time_kron_kernel.  A singular row (tr N_a <= 0: no unflagged cross-correlation) leaves its y alone and
+// counts in counts[1]; a solved row counts in counts[0]; the rows of a slice whose mask byte is 0 (slice_mask may be null: every row)
+// do neither.  The update y[a][l][k] + damping delta[l K + k] (rows of y at pitch kpad; L = 1: y[a][k]) is rounded to T once.
+// (gain_time_chol_kernel of gain_time_solve_kernels.hpp was this kernel without the mask: merged into it.)
 template <typename T>
 __global__ __launch_bounds__(256) void gain_basis_chol_kernel(const T* __restrict__ nmat, const T* __restrict__ rhs, double* __restrict__ dscr,
                                                                vec2_t<T>* __restrict__ y, const unsigned char* __restrict__ slice_mask, int na_slice,
-                                                               int a0, int K, int kpad, double damping, double ridge, int* __restrict__ counts,
-                                                               int lds_doubles) {
+                                                               int a0, int rhs_row0, int L, int K, int kpad, double damping, double ridge,
+                                                               int* __restrict__ counts, int lds_doubles) {
 #pragma clang fp contract(off)
   extern __shared__ __attribute__((aligned(16))) double s_m[];
   __shared__ double s_red[256];
@@ -105,24 +110,25 @@ __global__ __launch_bounds__(256) void gain_basis_chol_kernel(const T* __restric
   const int a = a0 + rel;
   if (slice_mask && !slice_mask[a / na_slice]) return;
   const int tid = threadIdx.x;
-  const int n = K;
+  const int n = L * K;
   const bool in_lds = (long long)(n + 2) * (n | 1) <= lds_doubles;
   const int ld = in_lds ? (n | 1) : n;  // (odd pitch: the rows a column step reads side by side lie on different banks)
   double* M = in_lds ? s_m : dscr + (long long)rel * (n + 2) * n;
-  const T* __restrict__ ra = rhs + (long long)a * 2 * n;
+  const T* __restrict__ ra = rhs + (long long)(rhs_row0 + rel) * 2 * n;
   if (!normal_chol_solve(M, ld, n, nmat + (long long)rel * n * n, ra, ra + n, ridge, s_red)) {
     if (tid == 0) atomicAdd(counts + 1, 1);
     return;
   }
   const double* xr = M + (long long)n * ld;
   const double* xi = M + (long long)(n + 1) * ld;
-  vec2_t<T>* __restrict__ ya = y + (long long)a * kpad;
-  for (int k = tid; k < n; k += 256) {
-    const vec2_t<T> old = ya[k];
+  vec2_t<T>* __restrict__ ya = y + (long long)a * L * kpad;
+  for (int i = tid; i < n; i += 256) {
+    const int l = i / K, k = i - l * K;
+    const vec2_t<T> old = ya[(long long)l * kpad + k];
     vec2_t<T> out;
-    out.x = (T)((double)old.x + damping * xr[k]);
-    out.y = (T)((double)old.y + damping * xi[k]);
-    ya[k] = out;
+    out.x = (T)((double)old.x + damping * xr[i]);
+    out.y = (T)((double)old.y + damping * xi[i]);
+    ya[(long long)l * kpad + k] = out;
   }
   if (tid == 0) atomicAdd(counts, 1);
 }

@@ -17,7 +17,8 @@
 //                                 W rounded to T once into the chunk's scratch, padded to whole 16 x 16 tiles
 //   gain_error_var_kernel         per (row of gain_var, 64 channels): Z = W X on the matrix cores (fe_sumsq of fit_error_kernels.hpp),
 //                                 X the rows of the transposed basis copy, times Bt[t,l] with a time basis: the Kronecker row, never stored
-//   gain_time_chan_var_kernel     the time basis alone: one thread per (antenna, channel), everything in double
+//   gain_time_chan_var_kernel     the time basis alone: one thread per (antenna, channel), everything in double, on the per-thread
+//                                 system of gain_time_chan_kernel (ChanSystem, gain_time_solve_kernels.hpp)
 //   gain_error_dof_kernel         the time basis alone: the channels' dof added in channel order
 // A system that is singular by the shared tests (tr <= 0, a pivot <= 0, or not finite) leaves the zeros the host wrote in all its
 // outputs and counts in counts[1]; a solved one counts in counts[0].  Every sum of reals has a fixed order, atomics only on the two
@@ -29,8 +30,8 @@
 namespace calk {
 
 // One workgroup per row of the chunk (an antenna row; with a time basis an antenna): nmat [rel][n][n] T (i >= j), the factor
-// M ([n + 1][ld] doubles: L, then a spare row) in LDS when [n + 2][ld] fits `lds_doubles` (the bound of gain_basis_chol_kernel and
-// gain_time_chol_kernel, so that all take the same branch) and in the chunk's double scratch dscr [rel][n + 2][n] otherwise.  Output:
+// M ([n + 1][ld] doubles: L, then a spare row) in LDS when [n + 2][ld] fits `lds_doubles` (the bound of
+// gain_basis_chol_kernel, so that both take the same branch) and in the chunk's double scratch dscr [rel][n + 2][n] otherwise.  Output:
 // wmat [rel][np][np] T, np = fe_pad(n); y_var [a][n] and gain_dof [a] (either may be null), ok[a] = 1.
 template <typename T>
 __global__ __launch_bounds__(256) void gain_error_factor_kernel(const T* __restrict__ nmat, double* __restrict__ dscr, T* __restrict__ wmat,
@@ -119,9 +120,9 @@ __global__ __launch_bounds__(256) void gain_error_var_kernel(const T* __restrict
   if (threadIdx.x < kFePiece && f < nfreqs) gain_var[((long long)t * na + a) * nfreqs + f] = mv;
 }
 
-// The case without a frequency basis: one thread per (antenna of the chunk, channel), consecutive lanes on consecutive channels, as
-// gain_time_chan_kernel.  The lower triangle (element i (i + 1) / 2 + j) of the L x L system is doubles: registers for LT > 0
-// (L <= LT, every loop unrolled over LT and cut at L), for LT = 0 the chunk's scratch laid out [element][system], nsys = ca nfreqs.
+// The case without a frequency basis: one thread per (antenna of the chunk, channel), consecutive lanes on consecutive channels, on
+// the ChanSystem of gain_time_chan_kernel (gain_time_solve_kernels.hpp): registers for LT > 0, for LT = 0 the chunk's scratch laid out
+// [element][system], nsys = ca nfreqs, the row the solve is planned with (its 2 L right-hand-side slots stay unused here).
 // planes: num_r, num_i, den as [3][T Na][nfreqs] doubles (den alone is read); Btb [T][lpad].  Cholesky, then W = L^-1 in place, row
 // by row in ascending column order (an element of row i is read as L only by the columns before it).  Output (each may be null):
 // y_var [Na][L][nfreqs], gain_var [T Na][nfreqs], dof [Na][nfreqs] (L - shift sum_l y_var of a solved system; zero otherwise).
@@ -132,80 +133,46 @@ __global__ __launch_bounds__(256) void gain_time_chan_var_kernel(const double* _
                                                                   int ntimes, int L, int lpad, int nfreqs, double ridge,
                                                                   int* __restrict__ counts) {
 #pragma clang fp contract(off)
-  constexpr int LB = LT > 0 ? LT : 1;
-  constexpr int NE = LB * (LB + 1) / 2;
-  double ra[NE];
   const long long sys = (long long)blockIdx.x * 256 + threadIdx.x;
   const long long nsys = (long long)ca * nfreqs;
   const bool live = sys < nsys;
   const int lim = LT > 0 ? LT : L;  // the loops' bound: a constant in the register instance
-  auto A = [&](int e) -> double& {
-    if constexpr (LT > 0) return ra[e];
-    else return scr[(long long)e * nsys + sys];
-  };
+  ChanSystem<LT> A(scr, nsys, sys, L);
   bool ok = live;
   if (live) {
     const int rel = (int)(sys / nfreqs), f = (int)(sys - (long long)rel * nfreqs);
     const int a = a0 + rel;
     const long long plane = (long long)ntimes * na * nfreqs;
-#pragma unroll
-    for (int i = 0; i < lim; ++i) {
-      if (i >= L) break;
-#pragma unroll
-      for (int j = 0; j <= i; ++j) A(i * (i + 1) / 2 + j) = 0.0;
-    }
+    A.zero();
     for (int t = 0; t < ntimes; ++t) {
       const double den = planes[2 * plane + ((long long)t * na + a) * nfreqs + f];
       const T* __restrict__ b = Btb + (long long)t * lpad;
 #pragma unroll
       for (int i = 0; i < lim; ++i) {
         if (i >= L) break;
-        const double bi = (double)b[i];
-#pragma unroll
-        for (int j = 0; j <= i; ++j) {
-          const double w = bi * (double)b[j];
-          A(i * (i + 1) / 2 + j) = A(i * (i + 1) / 2 + j) + w * den;
-        }
+        A.accumulate_row(i, b, den);
       }
     }
-    double tr = 0.0;
-#pragma unroll
-    for (int i = 0; i < lim; ++i) {
-      if (i >= L) break;
-      tr += A(i * (i + 1) / 2 + i);
-    }
+    const double tr = A.trace();
     ok = tr > 0.0 && isfinite(tr);
     const double shift = ok ? ridge * (tr / L) : 0.0;
     // left-looking Cholesky by columns
 #pragma unroll
     for (int j = 0; j < lim; ++j) {
       if (j >= L) break;
-      double d = A(j * (j + 1) / 2 + j) + shift;
-#pragma unroll
-      for (int k = 0; k < j; ++k) d -= A(j * (j + 1) / 2 + k) * A(j * (j + 1) / 2 + k);
-      ok = ok && d > 0.0 && isfinite(d);
-      const double root = sqrt(ok ? d : 1.0);
-      A(j * (j + 1) / 2 + j) = root;
-#pragma unroll
-      for (int i = j + 1; i < lim; ++i) {
-        if (i >= L) break;
-        double s = A(i * (i + 1) / 2 + j);
-#pragma unroll
-        for (int k = 0; k < j; ++k) s -= A(i * (i + 1) / 2 + k) * A(j * (j + 1) / 2 + k);
-        A(i * (i + 1) / 2 + j) = s / root;
-      }
+      A.factor_column(j, shift, ok);
     }
     // W = L^-1 in place
 #pragma unroll
     for (int i = 0; i < lim; ++i) {
       if (i >= L) break;
-      const double piv = A(i * (i + 1) / 2 + i);
+      const double piv = A.at(i, i);
 #pragma unroll
       for (int k = 0; k <= i; ++k) {
         double s = k == i ? 1.0 : 0.0;
 #pragma unroll
-        for (int j = k; j < i; ++j) s -= A(i * (i + 1) / 2 + j) * A(j * (j + 1) / 2 + k);
-        A(i * (i + 1) / 2 + k) = s / piv;
+        for (int j = k; j < i; ++j) s -= A.at(i, j) * A.at(j, k);
+        A.at(i, k) = s / piv;
       }
     }
     if (ok) {
@@ -217,7 +184,7 @@ __global__ __launch_bounds__(256) void gain_time_chan_var_kernel(const double* _
 #pragma unroll
         for (int i = l; i < lim; ++i) {
           if (i >= L) break;
-          s += A(i * (i + 1) / 2 + l) * A(i * (i + 1) / 2 + l);
+          s += A.at(i, l) * A.at(i, l);
         }
         sum += s;
         if (y_var) y_var[((long long)a * L + l) * nfreqs + f] = s;
@@ -232,7 +199,7 @@ __global__ __launch_bounds__(256) void gain_time_chan_var_kernel(const double* _
             if (i >= L) break;
             double z = 0.0;
 #pragma unroll
-            for (int l = 0; l <= i; ++l) z += A(i * (i + 1) / 2 + l) * (double)b[l];
+            for (int l = 0; l <= i; ++l) z += A.at(i, l) * (double)b[l];
             v += z * z;
           }
           gain_var[((long long)t * na + a) * nfreqs + f] = v;

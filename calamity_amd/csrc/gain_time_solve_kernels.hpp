@@ -14,14 +14,16 @@
 // and its gains at the flagged times move: the time basis interpolates.  T = 1, Bt = [[1]] gives the bits of
 // cal_solver_solve_gain_coeffs; Bt = I, ridge = 0 is its sweep per time; damping = 1, ridge = 0 lands on the exact minimiser.
 //   gain_time_kron_kernel   N_a (lower triangle) and rhs_a from the M_{t,a} and the per-row right-hand sides of gain_basis_gram_kernel
-//   gain_time_chol_kernel   per antenna, in double: normal_chol_solve of normal_solve.hpp, the damped update of y
-//   gain_time_chan_kernel   the case without a frequency basis: one thread per (antenna, channel), everything in double
+//   gain_basis_chol_kernel  (gain_basis_solve_kernels.hpp, at L blocks of K unknowns, no mask) per antenna, in double: normal_chol_solve
+//                           of normal_solve.hpp, the damped update of y; the gain_time_chol_kernel that stood here merged into it
+//   gain_time_chan_kernel   the case without a frequency basis: one thread per (antenna, channel), everything in double, on the
+//                           per-thread system ChanSystem that gain_time_chan_var_kernel (gain_error_kernels.hpp) shares
 // M_{t,a} and B^T r are in T; the sums over t run in double in ascending t and are rounded to T once on store; the factorisation, the
 // substitutions and the update of y run in double, the update is rounded once.  Every sum of reals has a fixed order, atomics only on
 // the two integer counters: two calls give the same bits.
 #pragma once
+#include "gain_basis_solve_kernels.hpp"
 #include "gain_time_basis_kernels.hpp"
-#include "normal_solve.hpp"
 
 namespace calk {
 
@@ -114,45 +116,83 @@ __global__ __launch_bounds__(256) void gain_time_kron_kernel(const T* __restrict
   }
 }
 
-// One workgroup per antenna of the chunk: normal_chol_solve on the antenna's N_a and rhs_a (n = L K), its [n + 2][ld] matrix in LDS when
-// it fits `lds_doubles` and in the chunk's scratch otherwise.  A singular antenna leaves its y alone and counts in counts[1]; a solved
-// one counts in counts[0].  The update y[a][l][k] + damping delta[l K + k] (rows of y at pitch kpad) is rounded to T once.
-template <typename T>
-__global__ __launch_bounds__(256) void gain_time_chol_kernel(const T* __restrict__ nmat, const T* __restrict__ rhs, double* __restrict__ dscr,
-                                                              vec2_t<T>* __restrict__ y, int a0, int L, int K, int kpad, double damping, double ridge,
-                                                              int* __restrict__ counts, int lds_doubles) {
+// The L x L system of one thread, N[l,l'] = sum_t Bt[t,l] Bt[t,l'] den[t], as gain_time_chan_kernel solves it and
+// gain_time_chan_var_kernel (gain_error_kernels.hpp) inverts it: the lower triangle (element i (i + 1) / 2 + j) in doubles, registers
+// for LT > 0 (L <= LT, every loop unrolled over LT and cut at L), for LT = 0 the chunk's scratch laid out [element][system] (slot e of
+// system sys at scr[e nsys + sys]; the slots from L (L + 1) / 2 on are the kernel's own).  Every sum has the order it is written in:
+// the contraction pragma holds for the compound statement it stands in, so every body here carries its own.  The accumulation and the
+// factorisation come a row and a column at a time: the kernels keep the loops over them (unrolled over LT, cut at L) and put what is
+// theirs -- the solve's right-hand sides -- beside the call.  (A helper holding those loops itself, with a hook per column, costs the
+// register instances a wave per SIMD: 174 VGPRs against 132 / 148.)
+template <int LT>
+struct ChanSystem {
+  static constexpr int LB = LT > 0 ? LT : 1;
+  double reg[LB * (LB + 1) / 2];
+  double* __restrict__ scr;
+  long long nsys, sys;
+  int L;
+  __device__ __forceinline__ ChanSystem(double* __restrict__ scr_, long long nsys_, long long sys_, int L_) : scr(scr_), nsys(nsys_), sys(sys_), L(L_) {}
+  __device__ __forceinline__ int lim() const { return LT > 0 ? LT : L; }  // the loops' bound: a constant in the register instance
+  __device__ __forceinline__ double& slot(int e) { return scr[(long long)e * nsys + sys]; }
+  __device__ __forceinline__ double& at(int i, int j) {
+    if constexpr (LT > 0) return reg[i * (i + 1) / 2 + j];
+    else return slot(i * (i + 1) / 2 + j);
+  }
+  __device__ __forceinline__ void zero() {
+#pragma unroll
+    for (int i = 0; i < lim(); ++i) {
+      if (i >= L) break;
+#pragma unroll
+      for (int j = 0; j <= i; ++j) at(i, j) = 0.0;
+    }
+  }
+  // row i of one time's term Bt[t,i] Bt[t,j] den, j <= i: b the row Bt[t,:] of the padded basis copy
+  template <typename T>
+  __device__ __forceinline__ void accumulate_row(int i, const T* __restrict__ b, double den) {
 #pragma clang fp contract(off)
-  extern __shared__ __attribute__((aligned(16))) double s_m[];
-  __shared__ double s_red[256];
-  const int rel = blockIdx.x;
-  const int a = a0 + rel;
-  const int tid = threadIdx.x;
-  const int n = L * K;
-  const bool in_lds = (long long)(n + 2) * (n | 1) <= lds_doubles;
-  const int ld = in_lds ? (n | 1) : n;
-  double* Mx = in_lds ? s_m : dscr + (long long)rel * (n + 2) * n;
-  const T* __restrict__ ra = rhs + (long long)rel * 2 * n;
-  if (!normal_chol_solve(Mx, ld, n, nmat + (long long)rel * n * n, ra, ra + n, ridge, s_red)) {
-    if (tid == 0) atomicAdd(counts + 1, 1);
-    return;
+    const double bi = (double)b[i];
+#pragma unroll
+    for (int j = 0; j <= i; ++j) {
+      const double w = bi * (double)b[j];
+      at(i, j) = at(i, j) + w * den;
+    }
   }
-  const double* xr = Mx + (long long)n * ld;
-  const double* xi = Mx + (long long)(n + 1) * ld;
-  vec2_t<T>* __restrict__ ya = y + (long long)a * L * kpad;
-  for (int i = tid; i < n; i += 256) {
-    const int l = i / K, k = i - l * K;
-    const vec2_t<T> old = ya[(long long)l * kpad + k];
-    vec2_t<T> out;
-    out.x = (T)((double)old.x + damping * xr[i]);
-    out.y = (T)((double)old.y + damping * xi[i]);
-    ya[(long long)l * kpad + k] = out;
+  __device__ __forceinline__ double trace() {
+#pragma clang fp contract(off)
+    double tr = 0.0;
+#pragma unroll
+    for (int i = 0; i < lim(); ++i) {
+      if (i >= L) break;
+      tr += at(i, i);
+    }
+    return tr;
   }
-  if (tid == 0) atomicAdd(counts, 1);
-}
+  // Column j of the left-looking Cholesky of N + shift I, in place, the columns before it done: row j of the factor is final behind
+  // it, so a caller's right-hand sides can ride along.  Returns the pivot's root; ok stays true while every pivot is > 0 and finite
+  // (a failed pivot divides by 1 and the factor is not to be used).
+  __device__ __forceinline__ double factor_column(int j, double shift, bool& ok) {
+#pragma clang fp contract(off)
+    double d = at(j, j) + shift;
+#pragma unroll
+    for (int k = 0; k < j; ++k) d -= at(j, k) * at(j, k);
+    ok = ok && d > 0.0 && isfinite(d);
+    const double root = sqrt(ok ? d : 1.0);
+    at(j, j) = root;
+#pragma unroll
+    for (int i = j + 1; i < lim(); ++i) {
+      if (i >= L) break;
+      double s = at(i, j);
+#pragma unroll
+      for (int k = 0; k < j; ++k) s -= at(i, k) * at(j, k);
+      at(i, j) = s / root;
+    }
+    return root;
+  }
+};
 
 // The case without a frequency basis: one thread per (antenna of the chunk, channel), consecutive lanes on consecutive channels.  The
-// lower triangle (element i (i + 1) / 2 + j) and the two right-hand sides of the L x L system are doubles: registers for LT > 0
-// (L <= LT, every loop unrolled over LT and cut at L), for LT = 0 the chunk's scratch laid out [element][system], nsys = ca nfreqs.
+// system is a ChanSystem; its two right-hand sides are doubles beside it: registers for LT > 0, for LT = 0 the 2 L slots of the
+// chunk's scratch behind the triangle's, nsys = ca nfreqs.
 // planes: num_r, num_i, den as [3][T Na][nfreqs] doubles; gains [T Na][fpad]; Btb [T][lpad]; y [Na][L][fpad].  Cholesky and both
 // substitutions in place; a singular system keeps the bits of y[a][:][f].  One atomic per wave and counter.
 template <typename T, int LT>
@@ -162,35 +202,30 @@ __global__ __launch_bounds__(256) void gain_time_chan_kernel(const double* __res
                                                               double ridge, int* __restrict__ counts) {
 #pragma clang fp contract(off)
   constexpr int LB = LT > 0 ? LT : 1;
-  constexpr int NE = LB * (LB + 1) / 2;
-  double ra[NE], rr[LB], ri[LB];
+  double rr[LB], ri[LB];
   const long long sys = (long long)blockIdx.x * 256 + threadIdx.x;
   const long long nsys = (long long)ca * nfreqs;
   const bool live = sys < nsys;
   const int lim = LT > 0 ? LT : L;  // the loops' bound: a constant in the register instance
   const int ntri = L * (L + 1) / 2;
-  auto A = [&](int e) -> double& {
-    if constexpr (LT > 0) return ra[e];
-    else return scr[(long long)e * nsys + sys];
-  };
+  ChanSystem<LT> A(scr, nsys, sys, L);
   auto Br = [&](int l) -> double& {
     if constexpr (LT > 0) return rr[l];
-    else return scr[(long long)(ntri + l) * nsys + sys];
+    else return A.slot(ntri + l);
   };
   auto Bi = [&](int l) -> double& {
     if constexpr (LT > 0) return ri[l];
-    else return scr[(long long)(ntri + L + l) * nsys + sys];
+    else return A.slot(ntri + L + l);
   };
   bool ok = live;
   if (live) {
     const int rel = (int)(sys / nfreqs), f = (int)(sys - (long long)rel * nfreqs);
     const int a = a0 + rel;
     const long long plane = (long long)ntimes * na * nfreqs;
+    A.zero();
 #pragma unroll
     for (int i = 0; i < lim; ++i) {
       if (i >= L) break;
-#pragma unroll
-      for (int j = 0; j <= i; ++j) A(i * (i + 1) / 2 + j) = 0.0;
       Br(i) = 0.0;
       Bi(i) = 0.0;
     }
@@ -205,46 +240,24 @@ __global__ __launch_bounds__(256) void gain_time_chan_kernel(const double* __res
       for (int i = 0; i < lim; ++i) {
         if (i >= L) break;
         const double bi = (double)b[i];
-#pragma unroll
-        for (int j = 0; j <= i; ++j) {
-          const double w = bi * (double)b[j];
-          A(i * (i + 1) / 2 + j) = A(i * (i + 1) / 2 + j) + w * den;
-        }
+        A.accumulate_row(i, b, den);
         Br(i) = Br(i) + bi * r_r;
         Bi(i) = Bi(i) + bi * r_i;
       }
     }
-    double tr = 0.0;
-#pragma unroll
-    for (int i = 0; i < lim; ++i) {
-      if (i >= L) break;
-      tr += A(i * (i + 1) / 2 + i);
-    }
+    const double tr = A.trace();
     ok = tr > 0.0 && isfinite(tr);
     const double shift = ok ? ridge * (tr / L) : 0.0;
     // left-looking Cholesky by columns; the right-hand sides ride along (the forward substitution)
 #pragma unroll
     for (int j = 0; j < lim; ++j) {
       if (j >= L) break;
-      double d = A(j * (j + 1) / 2 + j) + shift;
-#pragma unroll
-      for (int k = 0; k < j; ++k) d -= A(j * (j + 1) / 2 + k) * A(j * (j + 1) / 2 + k);
-      ok = ok && d > 0.0 && isfinite(d);
-      const double root = sqrt(ok ? d : 1.0);
-      A(j * (j + 1) / 2 + j) = root;
-#pragma unroll
-      for (int i = j + 1; i < lim; ++i) {
-        if (i >= L) break;
-        double s = A(i * (i + 1) / 2 + j);
-#pragma unroll
-        for (int k = 0; k < j; ++k) s -= A(i * (i + 1) / 2 + k) * A(j * (j + 1) / 2 + k);
-        A(i * (i + 1) / 2 + j) = s / root;
-      }
+      const double root = A.factor_column(j, shift, ok);
       double sr = Br(j), si = Bi(j);
 #pragma unroll
       for (int k = 0; k < j; ++k) {
-        sr -= A(j * (j + 1) / 2 + k) * Br(k);
-        si -= A(j * (j + 1) / 2 + k) * Bi(k);
+        sr -= A.at(j, k) * Br(k);
+        si -= A.at(j, k) * Bi(k);
       }
       Br(j) = sr / root;
       Bi(j) = si / root;
@@ -258,11 +271,11 @@ __global__ __launch_bounds__(256) void gain_time_chan_kernel(const double* __res
 #pragma unroll
       for (int k = j + 1; k < lim; ++k) {
         if (k >= L) break;
-        sr -= A(k * (k + 1) / 2 + j) * Br(k);
-        si -= A(k * (k + 1) / 2 + j) * Bi(k);
+        sr -= A.at(k, j) * Br(k);
+        si -= A.at(k, j) * Bi(k);
       }
-      Br(j) = sr / A(j * (j + 1) / 2 + j);
-      Bi(j) = si / A(j * (j + 1) / 2 + j);
+      Br(j) = sr / A.at(j, j);
+      Bi(j) = si / A.at(j, j);
     }
     if (ok) {
       vec2_t<T>* __restrict__ ya = y + (long long)a * L * fpad + f;

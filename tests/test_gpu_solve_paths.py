@@ -446,7 +446,7 @@ def zero_column(basis, col):
 
 # (T, Na, F), (L, K), the basis with the zero column, the column.  A zero pivot part-way through a factorisation, and one at the LAST
 # column: there no later pivot (not finite behind a division by a zero root) can stand in for the test of the pivot itself.  In a system
-# over (l, k) only L = 1 with the last column of B zeroed puts the one zero pivot last.  gain_time_chol_kernel in LDS (n = 30, 10) and
+# over (l, k) only L = 1 with the last column of B zeroed puts the one zero pivot last.  gain_basis_chol_kernel at L > 1 in LDS (n = 30, 10) and
 # in scratch (n = 128); gain_time_chan_kernel in registers (L = 3) and in scratch (L = 9)
 ZERO_TIME = [((4, 5, 48), (3, 10), "Bt", 1), ((9, 4, 72), (8, 16), "Bt", 3), ((3, 5, 72), (1, 10), "B", 9), ((2, 4, 200), (1, 128), "B", 127),
              ((4, 5, 48), (3, None), "Bt", 1), ((4, 5, 48), (3, None), "Bt", 2), ((10, 5, 72), (9, None), "Bt", 4), ((10, 5, 72), (9, None), "Bt", 8)]
