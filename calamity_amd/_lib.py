@@ -102,6 +102,14 @@ class DelaySpectrumDesc(C.Structure):
 DELAY_SPECTRUM_WHAT = {"data": 1, "model": 2, "resid": 4}
 
 
+class DelayTransferDesc(C.Structure):
+    """cal_delay_transfer_desc (include/calamity_hip.h: cal_solver_delay_transfer): ndelays columns of the operator op_r + i op_i
+    ([nfreqs][ndelays], solver dtype), calibrated 0 / 1, nbins and bin_of_bl [nbls] int32 in [-1, nbins) (NULL iff nbins == 0), the
+    ridge of the factorisation (cal_solver_fit_errors')."""
+    _fields_ = [("ndelays", C.c_int32), ("calibrated", C.c_int32), ("nbins", C.c_int32), ("bin_of_bl", C.c_void_p), ("op_r", C.c_void_p),
+                ("op_i", C.c_void_p), ("ridge", C.c_double)]
+
+
 class DegeneracyDesc(C.Structure):
     """cal_degeneracy_desc (include/calamity_hip.h: cal_solver_fix_degeneracies): mode (DEGENERACY_MODES), iters >= 1, the reference
     planes ref_r, ref_i and their weights ref_w (NULL: the solver's) [nbls][nfreqs] in the solver's dtype, antpos [nants per slice][2]
@@ -116,10 +124,10 @@ DEGENERACY_MODES = {"channel": 0, "band": 1}
 
 class ReportPlanDesc(C.Structure):
     """cal_report_plan_desc (include/calamity_hip.h: cal_debug_report_plan): the call whose host plan is asked for -- a spectrum
-    description with its scratch bound and whether power_bl is wanted, or a degeneracy description with the number of slices
-    (0: the problem's)."""
+    description with its scratch bound and whether power_bl is wanted, a degeneracy description with the number of slices
+    (0: the problem's), or a transfer description with its scratch bound."""
     _fields_ = [("spectrum", C.POINTER(DelaySpectrumDesc)), ("degeneracy", C.POINTER(DegeneracyDesc)), ("scratch_bytes", C.c_int64),
-                ("with_power_bl", C.c_int32), ("nslices", C.c_int32)]
+                ("with_power_bl", C.c_int32), ("nslices", C.c_int32), ("transfer", C.POINTER(DelayTransferDesc))]
 
 
 class CoeffSolveDesc(C.Structure):
@@ -245,6 +253,8 @@ SYMBOLS = {
     "cal_solver_robust_weights": (C.c_int, [_P, C.POINTER(RobustDesc), _P, _P]),
     "cal_solver_delay_spectrum": (C.c_int, [_P, C.POINTER(DelaySpectrumDesc), _P, _P, _P, _P, _P, _P]),
     "cal_solver_set_delay_spectrum_scratch": (C.c_int, [_P, C.c_int64]),
+    "cal_solver_delay_transfer": (C.c_int, [_P, C.POINTER(DelayTransferDesc), _P, _P, _P, _P, _P, _P, C.POINTER(FitErrorsCounts)]),
+    "cal_solver_set_delay_transfer_scratch": (C.c_int, [_P, C.c_int64]),
     "cal_solver_fix_degeneracies": (C.c_int, [_P, C.POINTER(DegeneracyDesc), _P, _P, _P, _P, _P, _P, _P]),
     "cal_solver_get_weights": (C.c_int, [_P, _P, C.c_int]),
     "cal_solver_solve_coeffs": (C.c_int, [_P, C.POINTER(CoeffSolveDesc), C.POINTER(CoeffSolveResult)]),

@@ -282,6 +282,22 @@ class SliceBatchFitter:
     def _set_delay_spectrum_scratch(self, nbytes):
         self._each(lambda r, s: s._set_delay_spectrum_scratch(nbytes))
 
+    def delay_transfer(self, op, ridge=1e-6, calibrated=False, bin_of_bl=None, nbins=0, per_baseline=False, g_r=None, g_i=None):
+        """``HipFitSolver.delay_transfer`` on the global arrays, like ``delay_spectrum``: ``bin_of_bl`` ``[nt * nbls]`` in the global
+        slice-major row order; ``absorbed_bin`` and ``count_bin`` are worker 0's (with several workers the library has summed them
+        over the workers), ``absorbed_bl`` and ``noise_bl`` are put back into the global row order like the rows of ``model()``; the
+        counts of groups are summed."""
+        bins = None if bin_of_bl is None else np.asarray(bin_of_bl)
+        outs = self._each(lambda r, s: s.delay_transfer(op, ridge=ridge, calibrated=calibrated, bin_of_bl=None if bins is None else self._take(bins, r),
+                                                        nbins=nbins, per_baseline=per_baseline, g_r=g_r, g_i=g_i))
+        out = dict(outs[0], **{k: sum(o[k] for o in outs) for k in ("nsolved", "nsingular")})
+        if per_baseline:
+            out.update({k: self._scatter([o[k] for o in outs], self.rows) for k in ("absorbed_bl", "noise_bl")})
+        return out
+
+    def _set_delay_transfer_scratch(self, nbytes):
+        self._each(lambda r, s: s._set_delay_transfer_scratch(nbytes))
+
     def fit_errors(self, ridge=1e-6, model_var=True, gain_var=True, coeffs=True):
         """``HipFitSolver.fit_errors`` on the global arrays: ``gain_var`` ``[nt * nants, nfreqs]`` (with several workers the library
         has summed ``den`` over the workers: worker 0's), ``model_var``, ``leverage_bl``, ``nsamp_bl`` with their rows and

@@ -891,6 +891,20 @@ def _check_delay_spectrum(delay_spectrum, taper, max_dly, bllen_bin):
         raise ValueError(f"delay_spectrum_max_dly must be a delay >= 0 in ns, got {max_dly!r}")
 
 
+def _check_delay_transfer(delay_transfer, ridge, delay_spectrum, freeze_model):
+    """The delay-transfer keywords of ``calibrate_and_model_tensor``, checked before anything is touched (``ValueError``)."""
+    if not any(delay_transfer is v for v in (False, True)):
+        raise ValueError(f"delay_transfer must be False or True, got {delay_transfer!r}")
+    if not delay_transfer:
+        return
+    if not delay_spectrum:
+        raise ValueError("delay_transfer needs delay_spectrum=True or 'baselines': it reports the signal loss of that spectrum, with its operator and bins")
+    if freeze_model:
+        raise ValueError("delay_transfer with freeze_model: no foreground coefficients are fitted, so the fit absorbs nothing")
+    if not (np.isfinite(float(ridge)) and float(ridge) >= 0.0):
+        raise ValueError(f"delay_transfer_ridge must be finite and >= 0, got {ridge!r}")
+
+
 def baseline_length_bins(lengths, width):
     """Baseline rows into bins of ``width`` metres, bin ``floor(length / width)``, only the bins that hold a row, in ascending order:
     ``(bin_of_bl [nbls] int32, bllen_m [nbins])`` with ``bllen_m`` the mean length of each bin's rows."""
@@ -905,7 +919,8 @@ def baseline_length_bins(lengths, width):
 def delay_spectrum_setup(uvdata, ant_array, prob, taper="bh4", max_dly=None, bllen_bin=1.0, calibrated=False, per_baseline=False):
     """What the delay-spectrum pass of every slice of a call shares: the operator, ``norm_f`` and delays (``modeling.delay_transform``
     on the data's frequencies), the length bin of every baseline row of ``prob`` (``baseline_length_bins`` on the antenna positions of
-    ``uvdata``; ``ant_array``: the antenna numbers ``prob``'s antenna indices count through) and the two switches."""
+    ``uvdata``; ``ant_array``: the antenna numbers ``prob``'s antenna indices count through) and the two switches.  ``transfer_ridge``
+    stays ``None`` unless the call also asks for the delay transfer (``delay_transfer``: its ridge then)."""
     op, norm_f, delays_ns = modeling.delay_transform(np.asarray(uvdata.freq_array, dtype=np.float64).ravel(), taper=taper, max_delay_ns=max_dly)
     if op.shape[1] < 1 or op.shape[1] > 4096:
         raise ValueError(f"the delay spectrum has {op.shape[1]} delays: between 1 and 4096 (delay_spectrum_max_dly)")
@@ -914,7 +929,7 @@ def delay_spectrum_setup(uvdata, ant_array, prob, taper="bh4", max_dly=None, bll
     lengths = np.asarray([np.linalg.norm(pos[int(ants[i])] - pos[int(ants[j])]) for i, j in zip(prob.bl_ant0, prob.bl_ant1)])
     bin_of_bl, bllen_m = baseline_length_bins(lengths, bllen_bin)
     return dict(op=op, norm_f=norm_f, delays_ns=delays_ns, bin_of_bl=bin_of_bl, nbins=len(bllen_m), bllen_m=bllen_m, calibrated=bool(calibrated),
-                per_baseline=bool(per_baseline))
+                per_baseline=bool(per_baseline), transfer_ridge=None)
 
 
 def delay_spectrum_slice_bins(dspec, nt):
@@ -929,6 +944,32 @@ def delay_spectrum_of_slice(spectra, dspec, t, nbls):
     if "per_baseline" in spectra:
         out["per_baseline"] = {k: v[rows] for k, v in spectra["per_baseline"].items()}
     return out
+
+
+def delay_transfer_of_slice(transfer, dspec, t, nbls):
+    """Slice ``t``'s part of a ``SliceBatchFitter.delay_transfer`` whose bins are those of ``delay_spectrum_slice_bins``; the counts of
+    groups are those of the whole call."""
+    bins, rows = slice(t * dspec["nbins"], (t + 1) * dspec["nbins"]), slice(t * nbls, (t + 1) * nbls)
+    out = {k: transfer[k][bins] for k in ("absorbed_bin", "count_bin")}
+    out.update({k: transfer[k][rows] for k in ("absorbed_bl", "noise_bl") if k in transfer}, nsingular=transfer["nsingular"])
+    return out
+
+
+def delay_transfer_entry(tr, prob, ant_array):
+    """One slice's ``HipFitSolver.delay_transfer`` as what ``fit_history`` reports beside the spectrum: ``transfer`` ``[nbins, ndelays]``,
+    ``1 - absorbed_bin / count_bin`` -- the share of the power of a signal that is white in delay which survives the fit, per
+    baseline-length bin; dimensionless (0 for a bin without a counted row) --, ``transfer_nsingular``, the singular groups of the call
+    that held the slice, and with per-baseline rows ``transfer_per_baseline`` keyed by antenna numbers (``1 - absorbed_bl``; 0 for a
+    row that is flagged throughout or belongs to a singular group)."""
+    count = np.asarray(tr["count_bin"], dtype=np.float64)
+    mean = np.asarray(tr["absorbed_bin"]) * np.divide(1.0, count, out=np.zeros_like(count), where=count > 0)[:, None]
+    entry = {"transfer": np.where(count[:, None] > 0, 1.0 - mean, 0.0), "transfer_nsingular": int(tr["nsingular"])}
+    if "absorbed_bl" in tr:
+        ants = np.asarray(ant_array)
+        live = np.any(np.asarray(tr["noise_bl"]) != 0, axis=1)
+        rows = np.where(live[:, None], 1.0 - np.asarray(tr["absorbed_bl"]), 0.0)
+        entry["transfer_per_baseline"] = {(int(ants[i]), int(ants[j])): rows[b] for b, (i, j) in enumerate(zip(prob.bl_ant0, prob.bl_ant1))}
+    return entry
 
 
 def delay_spectrum_entry(ds, dspec, rms, prob, ant_array):
@@ -1066,6 +1107,8 @@ def calibrate_and_model_tensor(
     fix_degeneracies=False,
     degeneracy_iters=6,
     degeneracy_phase_ref=True,
+    delay_transfer=False,
+    delay_transfer_ridge=1e-6,
     delay_spectrum=False,
     delay_spectrum_taper="bh4",
     delay_spectrum_max_dly=None,
@@ -1268,6 +1311,16 @@ def calibrate_and_model_tensor(
       (the antenna pairs of ``fg_model_comps_dict``, the keys of ``per_baseline``): held as ``(j, i)`` its spectrum is the mirror image
       in delay of ``(i, j)``'s.  A joint time-basis fit reports every time on its own.
       ``ValueError`` before any device work for an unknown taper, a bin width that is not positive, a negative ``delay_spectrum_max_dly``.
+    * ``delay_transfer`` / ``delay_transfer_ridge`` (default off: no call changes by a bit and no new kernel is launched; needs
+      ``delay_spectrum`` on and a fitted model, else ``ValueError`` before anything is touched -- ``freeze_model=True`` is refused): the
+      signal loss of the fit in delay space (``HipFitSolver.delay_transfer``: one more device pass beside the spectrum's, at the reported
+      gains, with the spectrum's operator, bins and ``delay_spectrum_calibrated``).  The foreground basis absorbs every component of the
+      data in its span, so a residual spectrum is biased low near the edge of the basis.  The ``"delay_spectrum"`` entry gains
+      ``"transfer"`` ``[bins, Ndelays]`` = ``1 - absorbed_bin / count_bin``, the share of the power of a signal that is white in delay
+      which survives the fit (dimensionless: no ``rms`` factor; the gains held fixed: an upper bound on the transfer; 0 for a bin without
+      a counted row), ``"transfer_nsingular"`` (singular groups of the device call that held the slice) and, with
+      ``delay_spectrum="baselines"``, ``"transfer_per_baseline"`` keyed like ``"per_baseline"``.  ``delay_transfer_ridge`` is the ridge of
+      the factorisation, as ``fit_errors_ridge``.
     * ``fix_degeneracies`` (``False`` | ``True`` = ``"channel"`` | ``"band"``; default off: no call changes by a bit and no new kernel is
       launched), ``degeneracy_iters`` (6), ``degeneracy_phase_ref`` (``True``): refer every fitted slice to ``sky_model`` before it is
       written (``HipFitSolver.fix_degeneracies``: one device pass after the fit).  The fit constrains only ``g_i conj(g_j) m``; an overall
@@ -1291,6 +1344,7 @@ def calibrate_and_model_tensor(
     if gain_basis is not None and gain_max_dly is not None:
         raise ValueError("give gain_basis or gain_max_dly, not both")
     _check_delay_spectrum(delay_spectrum, delay_spectrum_taper, delay_spectrum_max_dly, delay_spectrum_bllen_bin)
+    _check_delay_transfer(delay_transfer, delay_transfer_ridge, delay_spectrum, freeze_model)
     controls = FitControls.pick(locals())
     controls.check(gain_basis is not None or gain_max_dly is not None, gain_time_basis is not None or gain_time_scale is not None, freeze_model, use_min)
     if gain_max_dly is not None:
@@ -1371,6 +1425,8 @@ def calibrate_and_model_tensor(
         dspec = delay_spectrum_setup(uvdata, gains.ant_array, prob, taper=delay_spectrum_taper, max_dly=delay_spectrum_max_dly,
                                      bllen_bin=delay_spectrum_bllen_bin, calibrated=delay_spectrum_calibrated,
                                      per_baseline=delay_spectrum == "baselines")
+        if delay_transfer:
+            dspec["transfer_ridge"] = float(delay_transfer_ridge)
     degen = degeneracy_setup(uvdata, gains.ant_array, degen_mode, degeneracy_iters, degeneracy_phase_ref) if degen_mode is not None else None
     if parallel_fits is None:
         parallel_fits = 1
@@ -1804,6 +1860,8 @@ def calibrate_and_model_dpss(
     fix_degeneracies=False,
     degeneracy_iters=6,
     degeneracy_phase_ref=True,
+    delay_transfer=False,
+    delay_transfer_ridge=1e-6,
     delay_spectrum=False,
     delay_spectrum_taper="bh4",
     delay_spectrum_max_dly=None,
@@ -1816,6 +1874,7 @@ def calibrate_and_model_dpss(
     and ``fix_degeneracies`` / ``degeneracy_*`` keywords are ``calibrate_and_model_tensor``'s, and so are ``fit_errors`` and
     ``gain_basis_errors`` among ``fitting_kwargs``."""
     _check_delay_spectrum(delay_spectrum, delay_spectrum_taper, delay_spectrum_max_dly, delay_spectrum_bllen_bin)
+    _check_delay_transfer(delay_transfer, delay_transfer_ridge, delay_spectrum, fitting_kwargs.get("freeze_model", False))
     _check_degeneracy_call(fix_degeneracies, degeneracy_iters, fitting_kwargs)
     waker = _wake_device(fitting_kwargs.get("devices"))
     try:
@@ -1827,7 +1886,8 @@ def calibrate_and_model_dpss(
             uvdata=uvdata, fg_model_comps_dict=dpss_model_comps_dict, include_autos=include_autos, verbose=verbose,
             notebook_progressbar=notebook_progressbar, delay_spectrum=delay_spectrum, delay_spectrum_taper=delay_spectrum_taper,
             delay_spectrum_max_dly=delay_spectrum_max_dly, delay_spectrum_bllen_bin=delay_spectrum_bllen_bin,
-            delay_spectrum_calibrated=delay_spectrum_calibrated, fix_degeneracies=fix_degeneracies, degeneracy_iters=degeneracy_iters,
+            delay_spectrum_calibrated=delay_spectrum_calibrated, delay_transfer=delay_transfer, delay_transfer_ridge=delay_transfer_ridge,
+            fix_degeneracies=fix_degeneracies, degeneracy_iters=degeneracy_iters,
             degeneracy_phase_ref=degeneracy_phase_ref, **fitting_kwargs,
         )
     finally:
@@ -1871,6 +1931,8 @@ def calibrate_and_model_mixed(
     fix_degeneracies=False,
     degeneracy_iters=6,
     degeneracy_phase_ref=True,
+    delay_transfer=False,
+    delay_transfer_ridge=1e-6,
     delay_spectrum=False,
     delay_spectrum_taper="bh4",
     delay_spectrum_max_dly=None,
@@ -1885,6 +1947,7 @@ def calibrate_and_model_mixed(
     them on the host.  The ``delay_spectrum`` and ``fix_degeneracies`` / ``degeneracy_*`` keywords are ``calibrate_and_model_tensor``'s,
     and so are ``fit_errors`` and ``gain_basis_errors`` among ``fitting_kwargs``."""
     _check_delay_spectrum(delay_spectrum, delay_spectrum_taper, delay_spectrum_max_dly, delay_spectrum_bllen_bin)
+    _check_delay_transfer(delay_transfer, delay_transfer_ridge, delay_spectrum, fitting_kwargs.get("freeze_model", False))
     _check_degeneracy_call(fix_degeneracies, degeneracy_iters, fitting_kwargs)
     fitting_grps, blvecs, _, _ = modeling.get_uv_overlapping_grps_conjugated(
         uvdata, red_tol=red_tol, include_autos=include_autos, red_tol_freq=red_tol_freq, n_angle_bins=n_angle_bins,
@@ -1908,7 +1971,8 @@ def calibrate_and_model_mixed(
         uvdata=uvdata, fg_model_comps_dict=model_comps_dict, include_autos=include_autos, verbose=verbose,
         notebook_progressbar=notebook_progressbar, use_redundancy=use_redundancy, delay_spectrum=delay_spectrum, delay_spectrum_taper=delay_spectrum_taper,
         delay_spectrum_max_dly=delay_spectrum_max_dly, delay_spectrum_bllen_bin=delay_spectrum_bllen_bin,
-        delay_spectrum_calibrated=delay_spectrum_calibrated, fix_degeneracies=fix_degeneracies, degeneracy_iters=degeneracy_iters,
+        delay_spectrum_calibrated=delay_spectrum_calibrated, delay_transfer=delay_transfer, delay_transfer_ridge=delay_transfer_ridge,
+            fix_degeneracies=fix_degeneracies, degeneracy_iters=degeneracy_iters,
         degeneracy_phase_ref=degeneracy_phase_ref, **fitting_kwargs,
     )
     return model, resid, gains, fitted_info
@@ -2022,6 +2086,8 @@ def read_calibrate_and_model_dpss(
     fix_degeneracies=False,
     degeneracy_iters=6,
     degeneracy_phase_ref=True,
+    delay_transfer=False,
+    delay_transfer_ridge=1e-6,
     delay_spectrum=False,
     delay_spectrum_taper="bh4",
     delay_spectrum_max_dly=None,
@@ -2050,10 +2116,14 @@ def read_calibrate_and_model_dpss(
     ``[Npols, Ntimes, nbins, Ndelays]`` each with ``nan`` for a skipped slice, ``data``, ``model``, ``resid``; ``nbls``
     ``[Npols, Ntimes, nbins]``; with ``"baselines"`` also ``antpairs`` ``[rows, 2]`` and ``data_bl``, ``model_bl``, ``resid_bl``
     ``[Npols, Ntimes, rows, Ndelays]``.
+    ``delay_transfer`` / ``delay_transfer_ridge`` are ``calibrate_and_model_tensor``'s (Python keywords only); the archive then also holds
+    ``transfer`` ``[Npols, Ntimes, nbins, Ndelays]``, ``transfer_nsingular`` ``[Npols, Ntimes]`` (-1 for a skipped slice) and, with
+    ``"baselines"``, ``transfer_bl`` ``[Npols, Ntimes, rows, Ndelays]``.
     ``fix_degeneracies``, ``degeneracy_iters``, ``degeneracy_phase_ref`` are ``calibrate_and_model_tensor``'s too (Python keywords only);
     the sky model is ``input_model_files`` and the written gains and model are the fixed ones.
     """
     _check_delay_spectrum(delay_spectrum, delay_spectrum_taper, delay_spectrum_max_dly, delay_spectrum_bllen_bin)
+    _check_delay_transfer(delay_transfer, delay_transfer_ridge, delay_spectrum, calibration_kwargs.get("freeze_model", False))
     _check_degeneracy_call(fix_degeneracies, degeneracy_iters, dict(calibration_kwargs, sky_model=input_model_files))
     if delay_spectrum_outfile is not None and not delay_spectrum:
         raise ValueError("delay_spectrum_outfile needs delay_spectrum=True or 'baselines'")
@@ -2074,6 +2144,7 @@ def read_calibrate_and_model_dpss(
             **(dict(fit_errors="samples" if fit_errors_samples else True, fit_errors_ridge=fit_errors_ridge) if fit_errors or fit_errors_samples else {}),
             **(dict(delay_spectrum=delay_spectrum, delay_spectrum_taper=delay_spectrum_taper, delay_spectrum_max_dly=delay_spectrum_max_dly,
                     delay_spectrum_bllen_bin=delay_spectrum_bllen_bin, delay_spectrum_calibrated=delay_spectrum_calibrated) if delay_spectrum else {}),
+            **(dict(delay_transfer=True, delay_transfer_ridge=delay_transfer_ridge) if delay_transfer else {}),
             **(dict(fix_degeneracies=fix_degeneracies, degeneracy_iters=degeneracy_iters, degeneracy_phase_ref=degeneracy_phase_ref)
                if fix_degeneracies else {}),
             **(dict(gain_basis_errors=True) if gain_basis_errors else {}),
@@ -2140,12 +2211,21 @@ def delay_spectrum_tables(fit_info):
         out["antpairs"] = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
         for k in ("data", "model", "resid"):
             out[k + "_bl"] = np.full((len(pols), ntimes, len(pairs), nd), np.nan)
+    if "transfer" in first:
+        out["transfer"] = np.full((len(pols), ntimes, nbins, nd), np.nan)
+        out["transfer_nsingular"] = np.full((len(pols), ntimes), -1, dtype=np.int64)
+        if "transfer_per_baseline" in first:
+            out["transfer_bl"] = np.full((len(pols), ntimes, len(pairs), nd), np.nan)
     for i, p in enumerate(pols):
         for t, h in fit_info[p].items():
             if "delay_spectrum" not in h:
                 continue
             e = h["delay_spectrum"]
             out["nbls"][i, t] = e["nbls"]
+            if "transfer" in e:
+                out["transfer"][i, t], out["transfer_nsingular"][i, t] = e["transfer"], e["transfer_nsingular"]
+                if "transfer_bl" in out:
+                    out["transfer_bl"][i, t] = [e["transfer_per_baseline"][ap] for ap in pairs]
             for k in ("data", "model", "resid"):
                 out[k][i, t] = e[k]
                 if pairs is not None:

@@ -33,6 +33,7 @@
 #include "fit_error_kernels.hpp"
 #include "gain_error_kernels.hpp"
 #include "delay_spectrum_kernels.hpp"
+#include "delay_transfer_kernels.hpp"
 #include "degeneracy_kernels.hpp"
 #include "gain_basis_solve_kernels.hpp"
 #include "gain_time_solve_kernels.hpp"
@@ -190,6 +191,9 @@ struct cal_solver {
   virtual int delay_spectrum(const cal_delay_spectrum_desc* d, const void* g_r, const void* g_i, double* power_bl, double* norm_bl, double* power_bin,
                              double* count_bin) = 0;
   virtual int set_delay_spectrum_scratch(int64_t bytes) = 0;
+  virtual int delay_transfer(const cal_delay_transfer_desc* d, const void* g_r, const void* g_i, double* absorbed_bl, double* noise_bl, double* absorbed_bin,
+                             double* count_bin, cal_fit_errors_counts* counts) = 0;
+  virtual int set_delay_transfer_scratch(int64_t bytes) = 0;
   virtual int fix_degeneracies(const cal_degeneracy_desc* d, double* params, double* nsamp, double* last_step, void* out_g_r, void* out_g_i, void* out_m_r,
                                void* out_m_i) = 0;
   virtual int get_weights(void* out, int which) = 0;
@@ -284,6 +288,12 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
   // a chunk's masked planes in T (ds_x) and power in double (ds_pow); norm_bl | power_bin | count_bin (ds_out; the last two are the exchange payload)
   DevBuf ds_op, ds_normf, ds_ent, ds_ptr, ds_x, ds_pow, ds_out;
   int64_t ds_bound = kCsScratchDefault;        // bytes of scratch a chunk of rows may take (set_delay_spectrum_scratch)
+  // delay_transfer (delay_transfer_kernels.hpp): the plan of a call (groups, order, Gram work, W offsets, runs, rows, the bins' lists and
+  // the operator image); per chunk N (dt_n), the factor (dt_d) and W | S (dt_x); rhs of the Gram kernel (unused), coeff_var of the factor
+  // kernel (unused), ok [ngrps] ints + the two counters; absorbed and noise [nbls][ndelays]; valid | absorbed_bin | count_bin (dt_out; the
+  // last two are the exchange payload)
+  DevBuf dt_grp, dt_order, dt_work, dt_woff, dt_runs, dt_rows, dt_ent, dt_ptr, dt_op, dt_n, dt_d, dt_x, dt_rhs, dt_cv, dt_ok, dt_abs, dt_noise, dt_out;
+  int64_t dt_bound = kCsScratchDefault;        // bytes of scratch a chunk of groups may take (set_delay_transfer_scratch)
   // fix_degeneracies (degeneracy_kernels.hpp): the reference planes, then z0 ([2][nbls][fpad] T); the reference's weights when given
   // ([nbls][fpad] T); d_b | the slice's antenna positions | nu_f / nu_ref | the slices' longest |d_b| (doubles); the slices' row lists |
   // first segments | segments (ints); the segments' partial sums ([8][nseg][fpad] doubles); the channels' state ([14][nsl][fpad] + [nsl][2]
@@ -650,7 +660,7 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     CAL_TRY(upload(ant_ptr, p.ant_ptr));
     CAL_TRY(upload(ant_ent, p.ant_ent));
 
-    for (DevBuf* b : {&gains_snap, &gains_alt, &coef_snap, &q1, &gcp1, &gc1, &model_buf, &scratch, &fq_out, &fq_gains, &gs_out, &gs_ptr, &gs_ent, &gs_mask, &cs_rhs, &rw_w0, &rw_out, &ds_op, &ds_normf, &ds_ent, &ds_ptr, &ds_x, &ds_pow, &ds_out, &dg_z, &dg_w, &dg_geo, &dg_idx, &dg_part, &dg_st, &dg_gout, &dg_gref,
+    for (DevBuf* b : {&gains_snap, &gains_alt, &coef_snap, &q1, &gcp1, &gc1, &model_buf, &scratch, &fq_out, &fq_gains, &gs_out, &gs_ptr, &gs_ent, &gs_mask, &cs_rhs, &rw_w0, &rw_out, &ds_op, &ds_normf, &ds_ent, &ds_ptr, &ds_x, &ds_pow, &ds_out, &dt_grp, &dt_order, &dt_work, &dt_woff, &dt_runs, &dt_rows, &dt_ent, &dt_ptr, &dt_op, &dt_n, &dt_d, &dt_x, &dt_rhs, &dt_cv, &dt_ok, &dt_abs, &dt_noise, &dt_out, &dg_z, &dg_w, &dg_geo, &dg_idx, &dg_part, &dg_st, &dg_gout, &dg_gref,
                        &gn_s, &gn_g0, &gn_save, &gn_x, &gn_res, &gn_ns, &gn_D, &gn_m, &gn_sd, &gn_rows, &gn_part, &gn_scal, &gn_lam, &gn_grp, &gn_rowptr,
                        &lb_vec, &lb_part, &lb_dots, &lb_state, &lb_losses, &lb_count})
       b->release();
@@ -1908,6 +1918,105 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     return CAL_OK;
   }
 
+  // cal_solver_delay_transfer: the model pass of model() and coeff_solve_rows_kernel for q (at the call's gains), then per chunk of
+  // groups coeff_gram_kernel and fit_error_factor_kernel (both as they are; rhs and coeff_var are not used), dtransfer_basis_kernel and
+  // dtransfer_power_kernel (delay_transfer_kernels.hpp), then dspec_bin_kernel (as it is) once over all rows.  The plan
+  // (report_plan.hpp) is made and uploaded at every call; fit_errors' and solve_coeffs' own plans stay where they are.
+  int delay_transfer(const cal_delay_transfer_desc* d, const void* g_r, const void* g_i, double* absorbed_bl, double* noise_bl, double* absorbed_bin,
+                     double* count_bin, cal_fit_errors_counts* counts) override {
+    HIP_TRY(hipSetDevice(device));
+    if (!d) return fail(CAL_ERR_INVALID, "delay_transfer: null description");
+    CAL_TRY(require_set("delay_transfer", false));
+    if ((g_r == nullptr) != (g_i == nullptr)) return fail(CAL_ERR_INVALID, "delay_transfer: give both g_r and g_i, or neither");
+    if (!g_r && !has_gains) return fail(CAL_ERR_STATE, "delay_transfer: the gains must be set (cal_solver_set_params) or given");
+    if (d->ndelays < 1 || d->ndelays > 4096) return fail(CAL_ERR_INVALID, "delay_transfer: ndelays = %d lies outside [1, 4096]", d->ndelays);
+    if (d->calibrated != 0 && d->calibrated != 1) return fail(CAL_ERR_INVALID, "delay_transfer: calibrated = %d (0 or 1)", d->calibrated);
+    if (!(d->ridge >= 0.0) || !std::isfinite(d->ridge)) return fail(CAL_ERR_INVALID, "delay_transfer: ridge = %g must be finite and >= 0", d->ridge);
+    if (!d->op_r || !d->op_i) return fail(CAL_ERR_INVALID, "delay_transfer: null operator");
+    if (d->nbins < 0) return fail(CAL_ERR_INVALID, "delay_transfer: nbins = %d", d->nbins);
+    if ((d->nbins == 0) != (d->bin_of_bl == nullptr)) return fail(CAL_ERR_INVALID, "delay_transfer: bin_of_bl goes with nbins > 0, and only with it");
+    if (d->nbins == 0 && (absorbed_bin || count_bin)) return fail(CAL_ERR_INVALID, "delay_transfer: binned outputs need nbins > 0");
+    DelayTransferPlan<T> P;  // the chunks of groups, their runs and rows, the bins' rows, the operator image (report_plan.hpp)
+    CAL_TRY(plan_delay_transfer(h_cs_grp, h_bl_tile, nbls, nfreqs, fpad, fold, d, dt_bound, P));
+    const T2* g = nullptr;
+    CAL_TRY(report_gains("delay_transfer", g_r, g_i, &g));
+    const int nd = d->ndelays, nbins = d->nbins, xpitch = P.xpitch, ndpad = P.ndpad;
+    CAL_TRY(put(dt_grp, P.grp, false));
+    CAL_TRY(put(dt_order, P.G.order, false));
+    CAL_TRY(put(dt_work, P.G.work, false));
+    CAL_TRY(put(dt_woff, P.G.xoff, false));
+    CAL_TRY(put(dt_runs, P.runs, false));
+    CAL_TRY(put(dt_rows, P.rows, false));
+    CAL_TRY(put(dt_op, P.image, false));
+    if (nbins) {
+      CAL_TRY(put(dt_ent, P.bin_ent, false));
+      CAL_TRY(put(dt_ptr, P.bin_ptr2, false));
+    }
+    CAL_TRY(dt_n.reserve((size_t)P.G.n_max * sizeof(T), false));
+    CAL_TRY(dt_d.reserve((size_t)P.G.d_max * sizeof(double), false));
+    CAL_TRY(dt_x.reserve((size_t)P.G.x_max * sizeof(T), false));
+    CAL_TRY(dt_rhs.reserve(2 * (size_t)ncoef * sizeof(T)));
+    CAL_TRY(dt_cv.reserve((size_t)ncoef * sizeof(double), false));
+    CAL_TRY(dt_ok.reserve(((size_t)ngrps + 2) * sizeof(int)));
+    CAL_TRY(dt_out.reserve(P.n_out * sizeof(double)));
+    const bool want_abs = absorbed_bl != nullptr || nbins > 0;
+    if (want_abs) CAL_TRY(dt_abs.reserve(P.n_rows_out * sizeof(double), false));
+    if (noise_bl) CAL_TRY(dt_noise.reserve(P.n_rows_out * sizeof(double), false));
+    CAL_TRY(allow_chol_lds(&fit_error_factor_kernel<T>));
+    double* o_valid = dt_out.as<double>();
+    double* o_abin = o_valid + nbls;
+    double* o_cbin = o_abin + (size_t)nbins * nd;
+    int* ok = dt_ok.as<int>();
+    int* dcnt = ok + ngrps;
+    int cnt[2] = {0, 0};
+    RowPlanes R;
+    CAL_TRY(coeff_planes(R, g));
+    HIP_TRY(hipMemsetAsync(dt_ok.p, 0, ((size_t)ngrps + 2) * sizeof(int), stream));
+    HIP_TRY(hipMemsetAsync(o_valid, 0, (size_t)nbls * sizeof(double), stream));
+    for (const TransferChunk& ch : P.chunks) {
+      // S is zero where the basis kernel writes nothing (the channels [nfreqs, xpitch)); W is written whole
+      HIP_TRY(hipMemsetAsync(dt_x.p, 0, (size_t)P.G.x_max * sizeof(T), stream));
+      hipLaunchKernelGGL(coeff_gram_kernel<T>, dim3(ch.w1 - ch.w0), dim3(256), 0, stream, tiles.as<T>(), bl_tile.as<long long>(), R.u_r, R.u_i, R.q,
+                         dt_grp.as<CsGroup>(), dt_work.as<CsWork>() + ch.w0, dt_n.as<T>(), dt_rhs.as<T>(), ncoef, nfreqs, fpad, fold ? 1 : 0);
+      hipLaunchKernelGGL(fit_error_factor_kernel<T>, dim3(ch.g1 - ch.g0), dim3(256), (size_t)ch.lds, stream, dt_n.as<T>(), dt_d.as<double>(),
+                         dt_grp.as<CsGroup>(), dt_order.as<int>() + ch.g0, dt_woff.as<long long>(), dt_x.as<T>(), dt_cv.as<double>(), ok, d->ridge,
+                         dcnt, kCsLdsDoubles);
+      if (ch.r1 > ch.r0)
+        hipLaunchKernelGGL(dtransfer_basis_kernel<T>, dim3((unsigned)(ch.r1 - ch.r0) * P.npieces), dim3(256), 0, stream, tiles.as<T>(),
+                           bl_tile.as<long long>(), dt_grp.as<CsGroup>(), dt_woff.as<long long>(), ok, dt_runs.as<DtRun>() + ch.r0, dt_x.as<T>(), nfreqs,
+                           fpad, xpitch, fold ? 1 : 0, P.npieces);
+      if (ch.q1 > ch.q0)
+        hipLaunchKernelGGL(dtransfer_power_kernel<T>, dim3((unsigned)(ch.q1 - ch.q0) * (ndpad / kDsCols)), dim3(256), 0, stream, dt_x.as<T>(),
+                           dt_op.as<T>(), wgts.as<T>(), g, bl_ant.as<int2>(), dt_grp.as<CsGroup>(), ok, dt_rows.as<DtRow>() + ch.q0, nfreqs, fpad, xpitch,
+                           nd, ndpad, d->calibrated, want_abs ? dt_abs.as<double>() : nullptr, noise_bl ? dt_noise.as<double>() : nullptr, o_valid);
+      HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(cnt, dcnt, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
+    if (nbins) {
+      hipLaunchKernelGGL(dspec_bin_kernel, dim3(nbins, (nd + 255) / 256, 1), dim3(256), 0, stream, dt_abs.as<double>(), o_valid, dt_ptr.as<int>(),
+                         dt_ent.as<int>(), 0, nbls, nd, nbins, 1, o_abin, o_cbin);
+      HIP_TRY(hipGetLastError());
+      // the bins of every rank's rows add up to the array's: ONE all-reduce of nbins ndelays + nbins doubles
+      if (comm_on()) CAL_TRY(all_reduce(o_abin, (size_t)nbins * nd + nbins, CAL_XCHG_F64, CAL_XCHG_SUM));
+    }
+    CAL_TRY(give(absorbed_bl, dt_abs.as<double>(), P.n_rows_out));
+    CAL_TRY(give(noise_bl, dt_noise.as<double>(), P.n_rows_out));
+    CAL_TRY(give(absorbed_bin, o_abin, (size_t)nbins * nd));
+    CAL_TRY(give(count_bin, o_cbin, (size_t)nbins));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (counts) {
+      counts->nsolved = cnt[0];
+      counts->nsingular = cnt[1];
+    }
+    return CAL_OK;
+  }
+  int set_delay_transfer_scratch(int64_t bytes) override {
+    if (bytes < 0) return fail(CAL_ERR_INVALID, "set_delay_transfer_scratch: negative bound");
+    dt_bound = bytes == 0 ? kCsScratchDefault : bytes;
+    for (DevBuf* b : {&dt_n, &dt_d, &dt_x}) b->release();
+    return CAL_OK;
+  }
+
   // cal_solver_fix_degeneracies: the model pass of model(), then the six kernels of degeneracy_kernels.hpp.  The rows of every slice and their
   // segments, d_b and the longest |d_b| are planned on the host from the plan's bl_ant and the caller's positions; nothing is read back to plan.
   // m stays in the model planes (model_buf) for the whole call -- no other pass runs in between -- and m' overwrites it there at the end.
@@ -2123,10 +2232,11 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     });
   }
   // the model pass of model(), then coeff_solve_rows_kernel: the planes the Gram kernel reads
-  int coeff_planes(RowPlanes& P) {
+  // (g: the gains of a report call that was given its own, report_gains; null: the solver's)
+  int coeff_planes(RowPlanes& P, const T2* g = nullptr) {
     return model_pass(3, [&](T* model_r, T* model_i, T* third) {
       P = RowPlanes{model_r, model_i, third};
-      launch_rows(coeff_solve_rows_kernel<T>, 0, P.u_r, P.u_i, P.q, data_r.as<T>(), data_i.as<T>(), wgts.as<T>(), gains.as<T2>(), bl_ant.as<int2>(),
+      launch_rows(coeff_solve_rows_kernel<T>, 0, P.u_r, P.u_i, P.q, data_r.as<T>(), data_i.as<T>(), wgts.as<T>(), g ? g : gains.as<T2>(), bl_ant.as<int2>(),
                   nbls, nfreqs, fpad);
     });
   }
@@ -3217,6 +3327,25 @@ int debug_report_plan(const cal_problem_desc* d, const cal_report_plan_desc* r, 
     }
     return give(P.pack_idx());
   }
+  if (what >= 40 && what <= 48) {
+    const cal_delay_transfer_desc* t = r->transfer;
+    if (!t || t->ndelays < 1 || t->nbins < 0 || (t->nbins == 0) != (t->bin_of_bl == nullptr) || !t->op_r || !t->op_i || r->scratch_bytes < 0)
+      return fail(CAL_ERR_INVALID, "%s: what = %d takes a transfer description cal_solver_delay_transfer would plan for, and a bound >= 0", who, what);
+    DelayTransferPlan<T> P;
+    CAL_TRY(plan_delay_transfer(p.cs_grp, p.bl_tile, p.nbls, p.nfreqs, p.fpad, p.fold, t, r->scratch_bytes == 0 ? kCsScratchDefault : r->scratch_bytes, P));
+    switch (what) {
+      case 40: return give(std::vector<int64_t>{P.xpitch, P.ndpad, P.npieces, P.G.n_max, P.G.d_max, P.G.x_max, (int64_t)P.chunks.size(), (int64_t)P.runs.size(),
+                                                (int64_t)P.rows.size(), (int64_t)P.n_rows_out, (int64_t)P.n_out});
+      case 41: return give(P.grp);
+      case 42: return give(P.G.order);
+      case 43: return give(P.chunks);
+      case 44: return give(P.G.xoff);
+      case 45: return give(P.runs);
+      case 46: return give(P.rows);
+      case 47: return give(P.bin_ent);
+    }
+    return give(P.bin_ptr2);
+  }
   return fail(CAL_ERR_INVALID, "%s: what = %d", who, what);
 }
 }  // namespace
@@ -3893,6 +4022,12 @@ int cal_solver_delay_spectrum(cal_solver* s, const cal_delay_spectrum_desc* desc
   return s->delay_spectrum(desc, g_r, g_i, power_bl, norm_bl, power_bin, count_bin);
 }
 int cal_solver_set_delay_spectrum_scratch(cal_solver* s, int64_t bytes) { NEED(s); return s->set_delay_spectrum_scratch(bytes); }
+int cal_solver_delay_transfer(cal_solver* s, const cal_delay_transfer_desc* desc, const void* g_r, const void* g_i, double* absorbed_bl, double* noise_bl,
+                              double* absorbed_bin, double* count_bin, cal_fit_errors_counts* counts) {
+  NEED(s);
+  return s->delay_transfer(desc, g_r, g_i, absorbed_bl, noise_bl, absorbed_bin, count_bin, counts);
+}
+int cal_solver_set_delay_transfer_scratch(cal_solver* s, int64_t bytes) { NEED(s); return s->set_delay_transfer_scratch(bytes); }
 int cal_solver_fix_degeneracies(cal_solver* s, const cal_degeneracy_desc* desc, double* params, double* nsamp, double* last_step, void* out_g_r,
                                 void* out_g_i, void* out_m_r, void* out_m_i) {
   NEED(s);

@@ -1,12 +1,14 @@
-// report_plan.hpp -- what the post-fit reports cal_solver_delay_spectrum and cal_solver_fix_degeneracies decide before they launch, on the
-// host alone: the rows of every bin and of every slice, how they are cut into chunks and segments, and the padded images the kernels read.
+// report_plan.hpp -- what the post-fit reports cal_solver_delay_spectrum, cal_solver_delay_transfer and cal_solver_fix_degeneracies decide
+// before they launch, on the host alone: the rows of every bin and of every slice, how they are cut into chunks and segments, and the padded images the kernels read.
 // No HIP or RCCL runtime call and no solver: SolverT uploads these plans at every call; cal_debug_report_plan returns them as bytes
 // (tests/test_report_plan_host.py).  dspec_bin_kernel adds a bin's rows, and degen_sum_kernel a slice's segments, in the order written
 // here, in double and without atomics: ascending rows, cut where the loops below cut them.  That order is what "two calls give the same
 // bits, a slice of a batch the bits of the same slice alone" rests on, so it is part of the plan.
 #pragma once
 #include "problem_plan.hpp"
+#include "solve_plan.hpp"
 #include "delay_spectrum_kernels.hpp"
+#include "delay_transfer_kernels.hpp"
 #include "degeneracy_kernels.hpp"
 
 namespace {
@@ -24,6 +26,33 @@ struct DelaySpectrumPlan {
   size_t n_x = 0, n_pow = 0, n_out = 0;  // elements of ds_x (T), of ds_pow (double; 0 without power) and of ds_out (norm_bl | power_bin | count_bin)
 };
 
+// The sorted row list of every bin, one after the other (CSR: bin n's rows are bin_ent[bin_ptr[n] .. bin_ptr[n + 1])), ascending in b.
+inline int plan_bin_lists(const char* who, int nbls, int nbins, const int32_t* bin_of_bl, std::vector<int>& bin_ptr, std::vector<int>& bin_ent) {
+  bin_ptr.assign(nbins + 1, 0);
+  for (int b = 0; b < nbls && nbins; ++b) {
+    const int n = bin_of_bl[b];
+    if (n < -1 || n >= nbins) return fail(CAL_ERR_INVALID, "%s: bin_of_bl[%d] = %d lies outside [-1, %d)", who, b, n, nbins);
+    if (n >= 0) ++bin_ptr[n + 1];
+  }
+  if (nbins) {
+    for (int n = 0; n < nbins; ++n) bin_ptr[n + 1] += bin_ptr[n];
+    bin_ent.resize(bin_ptr[nbins]);
+    std::vector<int> fill(bin_ptr.begin(), bin_ptr.end() - 1);
+    for (int b = 0; b < nbls; ++b)
+      if (bin_of_bl[b] >= 0) bin_ent[fill[bin_of_bl[b]]++] = b;
+  }
+  return CAL_OK;
+}
+// The operator as the kernels read it: [re, im][xpitch][ndpad], zero beyond nfreqs and nd.
+template <typename T>
+void plan_operator_image(int nfreqs, int nd, int xpitch, int ndpad, const void* op_r, const void* op_i, std::vector<T>& image) {
+  image.assign((size_t)2 * xpitch * ndpad, (T)0);
+  for (int part = 0; part < 2; ++part) {
+    const T* src = static_cast<const T*>(part ? op_i : op_r);
+    for (int f = 0; f < nfreqs; ++f) std::copy(src + (size_t)f * nd, src + (size_t)(f + 1) * nd, image.begin() + ((size_t)part * xpitch + f) * ndpad);
+  }
+}
+
 // A chunk's scratch -- the masked planes in T and, with_power, its power in double -- stays under `bound` bytes (never less than one row);
 // the chunks are cut at multiples of the transform's kDsRows where that fits.  d: ndelays, what, nbins, bin_of_bl, op_r, op_i, norm_f.
 template <typename T>
@@ -31,19 +60,8 @@ int plan_delay_spectrum(int nbls, int nfreqs, int fpad, const cal_delay_spectrum
   const int nd = d->ndelays, nbins = d->nbins;
   P.nq = (d->what & 1) + (d->what >> 1 & 1) + (d->what >> 2 & 1);
   if ((long long)P.nq * nbins * nd + nbins > (1ll << 31) - 1) return fail(CAL_ERR_INVALID, "delay_spectrum: nbins = %d is too many", nbins);
-  std::vector<int> bin_ptr(nbins + 1, 0);
-  for (int b = 0; b < nbls && nbins; ++b) {
-    const int n = d->bin_of_bl[b];
-    if (n < -1 || n >= nbins) return fail(CAL_ERR_INVALID, "delay_spectrum: bin_of_bl[%d] = %d lies outside [-1, %d)", b, n, nbins);
-    if (n >= 0) ++bin_ptr[n + 1];
-  }
-  if (nbins) {
-    for (int n = 0; n < nbins; ++n) bin_ptr[n + 1] += bin_ptr[n];
-    P.bin_ent.resize(bin_ptr[nbins]);
-    std::vector<int> fill(bin_ptr.begin(), bin_ptr.end() - 1);
-    for (int b = 0; b < nbls; ++b)
-      if (d->bin_of_bl[b] >= 0) P.bin_ent[fill[d->bin_of_bl[b]]++] = b;
-  }
+  std::vector<int> bin_ptr;
+  CAL_TRY(plan_bin_lists("delay_spectrum", nbls, nbins, d->bin_of_bl, bin_ptr, P.bin_ent));
   P.xpitch = ds_xpitch(fpad);
   P.ndpad = ds_ndpad(nd);
   const size_t row_bytes = (size_t)P.nq * 2 * P.xpitch * sizeof(T) + (with_power ? (size_t)P.nq * nd * sizeof(double) : 0);
@@ -62,16 +80,86 @@ int plan_delay_spectrum(int nbls, int nfreqs, int fpad, const cal_delay_spectrum
       P.chunk_ptr[((size_t)c * nbins + n) * 2 + 1] = (int)(std::lower_bound(e0, e1, (int)b1) - P.bin_ent.data());
     }
   }
-  P.image.assign((size_t)2 * P.xpitch * P.ndpad, (T)0);
-  for (int part = 0; part < 2; ++part) {
-    const T* src = static_cast<const T*>(part ? d->op_i : d->op_r);
-    for (int f = 0; f < nfreqs; ++f) std::copy(src + (size_t)f * nd, src + (size_t)(f + 1) * nd, P.image.begin() + ((size_t)part * P.xpitch + f) * P.ndpad);
-  }
+  plan_operator_image<T>(nfreqs, nd, P.xpitch, P.ndpad, d->op_r, d->op_i, P.image);
   P.norm_f.assign((size_t)P.xpitch, 0.0);
   std::copy(d->norm_f, d->norm_f + nfreqs, P.norm_f.begin());
   P.n_x = (size_t)P.nq * 2 * crows * P.xpitch;
   P.n_pow = with_power ? (size_t)P.nq * crows * nd : 0;
   P.n_out = (size_t)nbls + (size_t)P.nq * nbins * nd + nbins;
+  return CAL_OK;
+}
+
+// ---- cal_solver_delay_transfer -----------------------------------------------------------------------------------------------------
+// positions of a chunk of groups in order / work (plan_group_chunks' chunk), in runs and in rows; dynamic LDS of its factor launch
+struct TransferChunk { int g0, g1, w0, w1, r0, r1, q0, q1; long long lds; };
+template <typename T>
+struct DelayTransferPlan {
+  int xpitch = 0, ndpad = 0, npieces = 0;
+  std::vector<CsGroup> grp;         // the groups with this plan's offsets
+  GroupPlan G;                      // order, Gram work, xoff (a group's W, then S of its runs, in the chunk's third scratch)
+  std::vector<DtRun> runs;          // chunk by chunk: every run of a group's baselines on one row block
+  std::vector<DtRow> rows;          // chunk by chunk: the rows of its groups
+  std::vector<TransferChunk> chunks;
+  std::vector<int> bin_ent;         // the sorted row list of every bin (plan_bin_lists)
+  std::vector<int> bin_ptr2;        // [nbins][2]: a bin's list as positions in bin_ent (what dspec_bin_kernel reads for ONE chunk of all rows)
+  std::vector<T> image;             // [re, im][xpitch][ndpad]
+  size_t n_rows_out = 0;            // elements of absorbed (and of noise): nbls ndelays doubles
+  size_t n_out = 0;                 // valid | absorbed_bin | count_bin
+};
+
+// The groups are cut into chunks by plan_group_chunks' rule: N, W and S (T) and the factor (double) of a chunk stay under `bound` bytes,
+// never less than one group.  S of a run is [fe_pad(nvec)][xpitch].  The rows of absorbed and noise are kept whole ([nbls][ndelays]
+// doubles, outside the bound): the bins add their rows in ascending order, which is not the order of the chunks (heaviest group first).
+template <typename T>
+int plan_delay_transfer(const std::vector<CsGroup>& cs_grp, const std::vector<long long>& bl_tile, int nbls, int nfreqs, int fpad, bool fold,
+                        const cal_delay_transfer_desc* d, int64_t bound, DelayTransferPlan<T>& P) {
+  const int nd = d->ndelays, nbins = d->nbins;
+  if ((long long)nbins * nd + nbins > (1ll << 31) - 1) return fail(CAL_ERR_INVALID, "delay_transfer: nbins = %d is too many", nbins);
+  std::vector<int> bin_ptr;
+  CAL_TRY(plan_bin_lists("delay_transfer", nbls, nbins, d->bin_of_bl, bin_ptr, P.bin_ent));
+  P.bin_ptr2.resize((size_t)nbins * 2);
+  for (int n = 0; n < nbins; ++n) P.bin_ptr2[2 * (size_t)n] = bin_ptr[n], P.bin_ptr2[2 * (size_t)n + 1] = bin_ptr[n + 1];
+  P.xpitch = ds_xpitch(fpad);
+  P.ndpad = ds_ndpad(nd);
+  P.npieces = ((fold ? nfreqs / 2 : fpad) + kFePiece - 1) / kFePiece;
+  P.grp = cs_grp;
+  const int ngrps = (int)P.grp.size();
+  auto runs_of = [&](const CsGroup& g, auto fn) {
+    for (int b = g.b0; b < g.b1;) {
+      int e = b + 1;
+      while (e < g.b1 && bl_tile[e] == bl_tile[b]) ++e;
+      fn(b, e);
+      b = e;
+    }
+  };
+  std::vector<long long> extra(ngrps);
+  for (int gi = 0; gi < ngrps; ++gi) {
+    const long long np = fe_pad(P.grp[gi].nvec);
+    long long nruns = 0;
+    runs_of(P.grp[gi], [&](int, int) { ++nruns; });
+    extra[gi] = np * np + nruns * np * P.xpitch;
+  }
+  P.G = plan_group_chunks(P.grp, sizeof(T), bound, extra);
+  for (const GroupChunk& ch : P.G.chunks) {
+    TransferChunk tc{ch.g0, ch.g1, ch.w0, ch.w1, (int)P.runs.size(), 0, (int)P.rows.size(), 0, (long long)ch.lds};
+    for (int p = ch.g0; p < ch.g1; ++p) {
+      const int gi = P.G.order[p];
+      const CsGroup& g = P.grp[gi];
+      const long long np = fe_pad(g.nvec);
+      long long soff = P.G.xoff[gi] + np * np;
+      runs_of(g, [&](int b, int e) {
+        P.runs.push_back(DtRun{soff, gi, b, e, 0});
+        for (int bb = b; bb < e; ++bb) P.rows.push_back(DtRow{soff, bb, gi});
+        soff += np * P.xpitch;
+      });
+    }
+    tc.r1 = (int)P.runs.size();
+    tc.q1 = (int)P.rows.size();
+    P.chunks.push_back(tc);
+  }
+  plan_operator_image<T>(nfreqs, nd, P.xpitch, P.ndpad, d->op_r, d->op_i, P.image);
+  P.n_rows_out = (size_t)nbls * nd;
+  P.n_out = (size_t)nbls + (size_t)nbins * nd + nbins;
   return CAL_OK;
 }
 

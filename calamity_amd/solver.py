@@ -433,6 +433,68 @@ class HipFitSolver:
         """Scratch bound of ``delay_spectrum`` in bytes (0: the default); the results do not depend on it (tests)."""
         _lib.check(self._lib.cal_solver_set_delay_spectrum_scratch(self._h, int(nbytes)))
 
+    def delay_transfer(self, op, ridge=1e-6, calibrated=False, bin_of_bl=None, nbins=0, per_baseline=False, g_r=None, g_i=None):
+        """The signal loss of the fit in delay space (cal_solver_delay_transfer): the share of the power at every delay that the
+        coefficient fit itself removes.  ``op`` ``[nfreqs, ndelays]`` complex: the operator of ``delay_spectrum``.  With
+        ``G = g_i conj(g_j)``, ``q = w |G|^2``, ``mask = (w != 0)``, ``a_{b,f}`` row ``f`` of the basis of row ``b`` and ``L`` the
+        Cholesky factor of the group's ridged normal matrix (``fit_errors``')::
+
+                             calibrated=False (d - G m)     calibrated=True (d / G - m)
+            s[b][f]     =    mask G                         mask                    (0 where |G|^2 == 0)
+            v[b][f]     =    mask / w                       mask / q                (0 where |G|^2 == 0)
+            num[b][k]      = |L^-1 sum_f op[f][k] s[b][f] a_{b,f}|^2
+            noise_bl[b][k] = sum_f v[b][f] |op[f][k]|^2
+            absorbed_bl    = num / noise_bl                 0 where noise_bl == 0 or the group is singular; in [0, 1]
+
+        For noise of variance ``1 / w`` on the unflagged samples, the gains held fixed (the conditional view of ``fit_errors``: a lower
+        bound on the loss) and the coefficients at their weighted least-squares optimum, ``noise_bl`` is the expected delay power of
+        the masked data and ``noise_bl - num`` that of the masked residual; exact at ``ridge = 0``.  ``bin_of_bl`` ``[nbls]`` integers
+        in ``[-1, nbins)``: ``"absorbed_bin"`` ``[nbins, ndelays]`` is the SUM of ``absorbed_bl`` over the bin's rows that have an
+        unflagged sample and a factored group, in ascending row order, and ``"count_bin"`` ``[nbins]`` their number, so that
+        ``1 - absorbed_bin / count_bin`` is the transfer of a signal that is white in delay.  ``per_baseline=True`` adds
+        ``"absorbed_bl"`` and ``"noise_bl"`` ``[nbls, ndelays]`` (as large as the data: off by default).  ``g_r``, ``g_i``: gains for
+        this call only, as in ``fit_quality``.  All float64; sums in a fixed order: two calls give the same bits.  The parameters,
+        moments, weights and loop state are untouched.  Under an exchange the binned arrays are summed over the ranks (one
+        all-reduce); the per-baseline arrays stay this rank's own rows.  Returns a dict with ``nsolved`` and ``nsingular`` (groups)
+        beside the arrays."""
+        if (g_r is None) != (g_i is None):
+            raise ValueError("give both g_r and g_i, or neither")
+        op = np.asarray(op)
+        if op.ndim != 2 or op.shape[0] != self.nfreqs:
+            raise ValueError(f"op must be [nfreqs = {self.nfreqs}, ndelays], got shape {op.shape}")
+        nd = op.shape[1]
+        op_r, op_i = self._real(op.real), self._real(op.imag)
+        nbins = int(nbins)
+        if (bin_of_bl is None) != (nbins == 0):
+            raise ValueError("give bin_of_bl and nbins > 0 together, or neither")
+        bins = None
+        if bin_of_bl is not None:
+            bins = np.ascontiguousarray(bin_of_bl, dtype=np.int32)
+            if bins.shape != (self.nbls,):
+                raise ValueError(f"bin_of_bl must be [nbls = {self.nbls}], got shape {bins.shape}")
+        gs = (self.nants, self.nfreqs)
+        a = None if g_r is None else self._real(g_r, gs)
+        b = None if g_i is None else self._real(g_i, gs)
+        d = _lib.DelayTransferDesc(nd, int(bool(calibrated)), nbins, None if bins is None else bins.ctypes.data, op_r.ctypes.data, op_i.ctypes.data,
+                                   float(ridge))
+        a_bl = np.empty((self.nbls, nd), dtype=np.float64) if per_baseline else None
+        n_bl = np.empty((self.nbls, nd), dtype=np.float64) if per_baseline else None
+        a_bin = np.empty((nbins, nd), dtype=np.float64) if nbins else None
+        c_bin = np.empty(nbins, dtype=np.float64) if nbins else None
+        cnt = _lib.FitErrorsCounts()
+        _lib.check(self._lib.cal_solver_delay_transfer(self._h, C.byref(d), _ptr(a), _ptr(b), _ptr(a_bl), _ptr(n_bl), _ptr(a_bin), _ptr(c_bin),
+                                                       C.byref(cnt)))
+        out = {"nsolved": int(cnt.nsolved), "nsingular": int(cnt.nsingular)}
+        if nbins:
+            out.update(absorbed_bin=a_bin, count_bin=c_bin)
+        if per_baseline:
+            out.update(absorbed_bl=a_bl, noise_bl=n_bl)
+        return out
+
+    def _set_delay_transfer_scratch(self, nbytes):
+        """Scratch bound of ``delay_transfer`` in bytes (0: the default); the results do not depend on it (tests)."""
+        _lib.check(self._lib.cal_solver_set_delay_transfer_scratch(self._h, int(nbytes)))
+
     def fit_errors(self, ridge=1e-6, model_var=True, gain_var=True, coeffs=True):
         """The errors of the fit at the solver's current parameters (cal_solver_fit_errors): the inverses of the curvature matrices
         of ``solve_coeffs`` and ``solve_gains``.  With ``G = g_i conj(g_j)`` from the full (expanded) gains, ``q = w |G|^2``, ``A_b``

@@ -230,13 +230,22 @@ int cal_debug_solve_plan(int dtype, const cal_problem_desc* d, int64_t scratch_b
  *   10: int64 segments, then the first double of antpos, ratio and maxd in blob 18 and the first int of 16 and 17 in blob 19;
  *   11: d_b [nbls][2]; 12: antpos; 13: nu_f / nu_ref [fpad]; 14: the slices' longest |d_b| (11 .. 14 double); 15: the slices' row lists,
  *   one after the other; 16: a slice's first segment [slices + 1]; 17: the segments (DgSeg); 18 / 19: the two blobs as the device holds
- *   them, 11 | 12 | 13 | 14 (double) and 15 | 16 | 17 (int32). */
+ *   them, 11 | 12 | 13 | 14 (double) and 15 | 16 | 17 (int32).
+ * what = 40 .. 48: the plan of cal_solver_delay_transfer for r->transfer (ndelays, nbins, bin_of_bl, op_r, op_i are read) and the bound
+ *   r->scratch_bytes of cal_solver_set_delay_transfer_scratch (0: the default) --
+ *   40: int64 the row pitch of S, the columns of the operator image, the 64-channel pieces of the band, the elements of the chunk's N
+ *   (dtype), factor (double) and W | S (dtype) scratch, chunks, runs, rows, the elements of absorbed_bl and of valid | absorbed_bin |
+ *   count_bin; 41: CsGroup per group with the plan's offsets; 42: order; 43: chunks (int32 g0, g1, w0, w1, r0, r1, q0, q1 -- positions
+ *   in 42, in the Gram work, in 45 and in 46 -- then the dynamic LDS as int64); 44: int64 per group, the offset of its W in the third
+ *   scratch (S of its runs follows); 45: runs (int64 offset of S, int32 group, b0, b1, 0); 46: rows (int64 offset of S, int32 row,
+ *   group); 47: the bins' sorted row lists; 48: [nbins][2] a bin's list as positions in 47. */
 typedef struct cal_report_plan_desc {
   const struct cal_delay_spectrum_desc* spectrum;
   const struct cal_degeneracy_desc* degeneracy;
   int64_t scratch_bytes;
   int32_t with_power_bl;
   int32_t nslices;
+  const struct cal_delay_transfer_desc* transfer; /* what = 40 .. 48 only */
 } cal_report_plan_desc;
 int cal_debug_report_plan(int dtype, const cal_problem_desc* d, const cal_report_plan_desc* r, int what, void* out, int64_t cap_bytes, int64_t* bytes);
 /* Host only, like cal_debug_plan: the shape of one pass or train step (csrc/step_plan.hpp) -- which kernels follow the fused or dense pass,
@@ -715,6 +724,64 @@ int cal_solver_delay_spectrum(cal_solver* s, const cal_delay_spectrum_desc* desc
 /* The scratch bound of cal_solver_delay_spectrum in bytes (0: the default, 256 MiB; negative: CAL_ERR_INVALID).  The outputs do not
  * depend on it: tests use it to send a small problem through several chunks. */
 int cal_solver_set_delay_spectrum_scratch(cal_solver* s, int64_t bytes);
+/* The signal loss of the fit in delay space: the share of the power at every delay that the coefficient fit itself removes.  The
+ * foreground basis absorbs every component of the data in its span -- noise and cosmological signal as well as foregrounds -- so a
+ * residual delay spectrum (cal_solver_delay_spectrum) is biased low near the edge of the basis; this is the factor that undoes it.
+ * Notation of cal_solver_fit_errors and cal_solver_delay_spectrum: row b of fitting group gamma has antennas (i, j) and the basis rows
+ * a_{b,f}; G = g_i conj(g_j), q = w |G|^2, mask = (w != 0);
+ *   N_gamma = sum_{b in gamma} A_b^T diag(q_b) A_b    N_r = N_gamma + ridge (tr N_gamma / nvec) I    L L^T = N_r   (cal_solver_fit_errors')
+ *                    calibrated = 0 (d - G m)      calibrated = 1 (d / G - m)
+ *   s[b][f]     =    mask G                        mask                       (0 where |G|^2 == 0)
+ *   v[b][f]     =    mask / w                      mask / q                   (0 where |G|^2 == 0)
+ *   U[b][k]           = sum_f (op_r + i op_i)[f][k] s[b][f] a_{b,f}           complex, nvec numbers
+ *   num[b][k]         = |L^-1 U[b][k]|^2
+ *   noise_bl[b][k]    = sum_f v[b][f] |op[f][k]|^2                            [nbls][ndelays]
+ *   absorbed_bl[b][k] = num / noise_bl; 0 where noise_bl == 0 or the group is singular      [nbls][ndelays], in [0, 1]
+ *   absorbed_bin[n][k] = sum of absorbed_bl[b][k] over the rows b with bin_of_bl[b] == n, an unflagged sample and a factored group,
+ *                        taken in ascending b                                 [nbins][ndelays]
+ *   count_bin[n]      = the number of such rows (an integer, returned as a double)          [nbins]
+ * Meaning: with the gains held fixed (the conditional view of cal_solver_fit_errors: a lower bound on the loss), noise of variance
+ * 1 / w on the unflagged samples and the coefficients at their weighted least-squares optimum, noise_bl is the expected delay power of
+ * the masked data at delay k, as cal_solver_delay_spectrum masks them, and noise_bl - num that of the masked residual -- for groups of
+ * several baselines too.  Exact at ridge = 0 (a ridge only lowers num), and for any input whose variance is proportional to 1 / w:
+ * 1 - absorbed_bin / count_bin is the transfer of a signal that is white in delay wherever the weights are uniform over the unflagged
+ * samples.  With the unshifted rectangular DFT of all nfreqs delays, sum_k num[b][k] = nfreqs sum_f mask |G|^2 model_var[b][f].
+ * The two products -- S = L^-1 A^T per run of a group's baselines, then (S diag(s_b)) op per baseline row, real times complex -- run on
+ * the matrix cores in the solver's dtype (v_mfma_f32_16x16x4_f32 / v_mfma_f64_16x16x4_f64); the squares, noise_bl, the division and
+ * every sum over vectors and rows are taken in double in a fixed order, no float atomics: two calls give the same bits.  All outputs
+ * are doubles; any output pointer may be NULL (absorbed_bin and count_bin need nbins > 0).  counts (may be NULL): the groups factored
+ * and the singular ones, as in cal_solver_fit_errors; the rows of a singular group and the rows without an unflagged sample are zero
+ * and enter no bin.
+ *   g_r, g_i: as in cal_solver_delay_spectrum -- NULL: the solver's current full gains, whatever gain bases are set; given gains are
+ *   used for this call only (q and N are formed from them too).
+ * Errors, before any launch: CAL_ERR_STATE when problem, data or coefficients are not set, or the gains neither set nor given;
+ * CAL_ERR_INVALID for a null description, ndelays outside [1, 4096], a `calibrated` other than 0 or 1, a ridge that is negative or not
+ * finite, nbins < 0, a bin_of_bl that is NULL with nbins > 0 (or given with nbins == 0) or holds an index outside [-1, nbins), a null
+ * operator, binned outputs with nbins == 0.
+ * Works for every layout and kernel path, folded and full tiles, fitting groups of several baselines on several row blocks, bl_alias
+ * and nslices > 1.  A post-fit pass like cal_solver_fit_errors: it runs the model pass of cal_solver_model and puts the loop state
+ * back; nothing a later cal_solver_run reads changes, and a run continued after the call is bit-identical to one without it.
+ * The groups are worked through in chunks (heaviest first) whose scratch -- N, L^-1 and S in the solver's dtype and the factor in
+ * double -- stays under the bound of cal_solver_set_delay_transfer_scratch (never less than one group).  The result does not depend on
+ * the chunks by a bit.  The rows of absorbed_bl (and of noise_bl when asked for) are kept whole on the device, nbls ndelays doubles
+ * each: the bins add their rows in ascending order, which is not the order of the chunks.
+ * Under a communicator or exchange hook absorbed_bin | count_bin are summed over the ranks in ONE all-reduce of nbins ndelays + nbins
+ * doubles (CAL_XCHG_F64, CAL_XCHG_SUM), whichever outputs are asked for (nbins == 0: none); a group belongs to one rank, so the per-row
+ * outputs stay the rank's own rows. */
+typedef struct cal_delay_transfer_desc {
+  int32_t ndelays;          /* columns of the operator, 1 <= ndelays <= 4096 */
+  int32_t calibrated;       /* 0: the loss of d - G m; 1: of d / G - m */
+  int32_t nbins;            /* 0: no binned output */
+  const int32_t* bin_of_bl; /* [nbls] in [-1, nbins): -1 leaves the row out; NULL iff nbins == 0 */
+  const void* op_r;         /* [nfreqs][ndelays], solver dtype: the transform along frequency, taper folded in */
+  const void* op_i;
+  double ridge;             /* of the factorisation, as in cal_solver_fit_errors: finite, >= 0 */
+} cal_delay_transfer_desc;
+int cal_solver_delay_transfer(cal_solver* s, const cal_delay_transfer_desc* desc, const void* g_r, const void* g_i, double* absorbed_bl,
+                              double* noise_bl, double* absorbed_bin, double* count_bin, cal_fit_errors_counts* counts);
+/* The scratch bound of cal_solver_delay_transfer in bytes (0: the default, 256 MiB; negative: CAL_ERR_INVALID).  The outputs do not
+ * depend on it: tests use it to send a small problem through several chunks. */
+int cal_solver_set_delay_transfer_scratch(cal_solver* s, int64_t bytes);
 /* Fix the gain degeneracies against a reference (sky) model after a fit (the reference computes one band-wide amplitude on the host and
  * never applies its phase).  A fit constrains only g_i conj(g_j) m_b; per slice t and channel f an amplitude eta, a phase psi and a
  * phase gradient across the array Phi = (Phi_e, Phi_n) (rad / m; a shift of the sky) are free because the model absorbs them.  Baseline
