@@ -584,7 +584,9 @@ class HipFitSolver:
 
     def robust_weights(self, kind="huber", threshold=3.0, slice_mask=None):
         """One round of iteratively reweighted least squares (cal_solver_robust_weights): the weight plane every kernel path reads is
-        rewritten in place from the residual at the solver's current parameters.  With ``w0`` the weights as ``set_data`` gave them,
+        rewritten in place from the residual at the solver's current parameters.  ``fit_quality``, the closed-form solves and the five
+        post-fit reports read that one plane too: ``fit_errors``, ``gain_basis_errors``, ``delay_spectrum``, ``delay_transfer``, and
+        ``fix_degeneracies`` where its ``ref_w`` is ``None`` (given reference weights replace it).  With ``w0`` the weights as ``set_data`` gave them,
         ``(i, j)`` the antennas of baseline row ``b``, ``m = A c``, ``g`` the solver's gains and ``k = threshold`` (in sigma)::
 
             e[b][f]  = w0[b][f] |d[b][f] - g_i[f] conj(g_j[f]) m[b][f]|^2     (products in the solver's dtype)

@@ -390,8 +390,10 @@ int cal_solver_data_model(cal_solver* s, void* model_r, void* model_i);
 int cal_solver_fit_quality(cal_solver* s, const void* g_r, const void* g_i, double* chisq_ant, double* wsum_ant, double* chisq_bl,
                            double* wsum_bl);
 /* Downweight outliers from the residual (no counterpart in the reference, which minimises a plain weighted chi-square): one round of
- * iteratively reweighted least squares.  The call rewrites the ONE weight plane that every kernel path, cal_solver_fit_quality and
- * the closed-form solves read, in place: no fit kernel changes and no recorded step graph goes stale.  With w0 the weights as
+ * iteratively reweighted least squares.  The call rewrites the ONE weight plane that every kernel path, cal_solver_fit_quality, the
+ * closed-form solves and the five post-fit reports (cal_solver_fit_errors, cal_solver_gain_basis_errors, cal_solver_delay_spectrum,
+ * cal_solver_delay_transfer, and cal_solver_fix_degeneracies where its ref_w is NULL: given reference weights replace the plane, which
+ * is then not read) read, in place: no fit kernel changes and no recorded step graph goes stale.  With w0 the weights as
  * cal_solver_set_data gave them, (i, j) the antennas of baseline row b, m = A c at the solver's coefficients, g the solver's gains:
  *   e[b][f]  = w0[b][f] |d[b][f] - g_i[f] conj(g_j[f]) m[b][f]|^2     (products in the solver's dtype, in cal_solver_fit_quality's order)
  *   S_b      = { f < nfreqs : w0[b][f] > 0 },  n_b = |S_b|

@@ -29,30 +29,30 @@ def fpad_of(nfreqs):
 
 
 @functools.lru_cache(maxsize=None)
-def base_problem(nants, seed=0, kind="plain"):
-    p, truth, start = synthetic.make_problem(nants, NF, f0=150e6, df=1e6, seed=seed)
+def base_problem(nants, seed=0, kind="plain", nfreqs=NF):
+    p, truth, start = synthetic.make_problem(nants, nfreqs, f0=150e6, df=1e6, seed=seed)
     rng = np.random.default_rng(100 + seed)
-    params = dict(g_r=start["g_r"] + 0.1 * rng.standard_normal((nants, NF)), g_i=start["g_i"] + 0.1 * rng.standard_normal((nants, NF)),
+    params = dict(g_r=start["g_r"] + 0.1 * rng.standard_normal((nants, nfreqs)), g_i=start["g_i"] + 0.1 * rng.standard_normal((nants, nfreqs)),
                   c_r=start["c_r"].copy(), c_i=start["c_i"].copy())
     if kind == "group":  # a fitting group of three baselines
         p, params = synthetic.add_redundant_group(p, params, rng)
     if kind == "auto":  # one autocorrelation row of antenna 2 behind the others
         nv = p.basis[0].shape[1]
-        p = FitProblem(nants=nants, nfreqs=NF, basis=p.basis, grp_basis=np.concatenate([p.grp_basis, [0]]).astype(np.int32),
+        p = FitProblem(nants=nants, nfreqs=nfreqs, basis=p.basis, grp_basis=np.concatenate([p.grp_basis, [0]]).astype(np.int32),
                        grp_bl_start=np.arange(p.nbls + 2, dtype=np.int32), bl_ant0=np.concatenate([p.bl_ant0, [2]]).astype(np.int32),
                        bl_ant1=np.concatenate([p.bl_ant1, [2]]).astype(np.int32), bl_rowblk=np.zeros(p.nbls + 1, dtype=np.int32),
-                       data_r=np.concatenate([p.data_r, rng.standard_normal((1, NF))]), data_i=np.concatenate([p.data_i, rng.standard_normal((1, NF))]),
-                       wgts=np.concatenate([p.wgts, np.full((1, NF), p.wgts.max())]))
+                       data_r=np.concatenate([p.data_r, rng.standard_normal((1, nfreqs))]), data_i=np.concatenate([p.data_i, rng.standard_normal((1, nfreqs))]),
+                       wgts=np.concatenate([p.wgts, np.full((1, nfreqs), p.wgts.max())]))
         p.validate()
         params = dict(params, c_r=np.concatenate([params["c_r"], 1.0 + rng.standard_normal(nv)]), c_i=np.concatenate([params["c_i"], rng.standard_normal(nv)]))
     return p, params, truth["freqs"], truth["antpos"][:, :2].copy()
 
 
-def solver_of(p, params, dtype, layout="shared"):
+def solver_of(p, params, dtype, layout="shared", kernel_path="auto"):
     from calamity_amd.solver import HipFitSolver
 
     s = HipFitSolver(dtype=dtype)
-    s.set_problem(p, layout=layout)
+    s.set_problem(p, layout=layout, kernel_path=kernel_path)
     s.set_params(params["g_r"], params["g_i"], params["c_r"], params["c_i"])
     return s
 

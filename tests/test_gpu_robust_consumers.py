@@ -44,9 +44,10 @@ def inputs_of(kind, shape):
     return inputs(INPUTS_OF.get(kind, kind), shape)
 
 
-def reweighted(kind, shape, dtype, path, how=CLIP):
-    """Solver A behind its ``robust_weights`` call: (solver, the weights it holds now, w0)."""
-    p, params, B, Bt = inputs_of(kind, shape)
+def reweighted(kind, shape, dtype, path, how=CLIP, given=None):
+    """Solver A behind its ``robust_weights`` call: (solver, the weights it holds now, w0).  ``given``: (problem, params, frequency
+    basis or None, time basis or None) of a caller with inputs of its own, in place of ``inputs_of(kind, shape)``."""
+    p, params, B, Bt = given if given is not None else inputs_of(kind, shape)
     s = path_solver(p, params, dtype, path, B, Bt)
     w0 = s.get_weights()
     np.testing.assert_array_equal(w0, np.asarray(p.wgts).astype(dtype))
@@ -61,9 +62,9 @@ def reweighted(kind, shape, dtype, path, how=CLIP):
     return s, w, w0
 
 
-def uploaded(kind, shape, dtype, path, w):
-    """Solver B: a fresh solver that is given the weights ``w`` through ``set_data`` and never reweights."""
-    p, params, B, Bt = inputs_of(kind, shape)
+def uploaded(kind, shape, dtype, path, w, given=None):
+    """Solver B: a fresh solver that is given the weights ``w`` through ``set_data`` and never reweights (``given`` as above)."""
+    p, params, B, Bt = given if given is not None else inputs_of(kind, shape)
     s = path_solver(p, params, dtype, path, B, Bt)
     s.set_data(p.data_r, p.data_i, w)
     np.testing.assert_array_equal(s.get_weights(), w)
