@@ -102,6 +102,18 @@ class DelaySpectrumDesc(C.Structure):
 DELAY_SPECTRUM_WHAT = {"data": 1, "model": 2, "resid": 4}
 
 
+DELAY_CROSS_STATS = {"cross": 1, "diff": 2}
+
+
+class DelayCrossDesc(C.Structure):
+    """cal_delay_cross_desc (include/calamity_hip.h: cal_solver_delay_cross_spectrum): ndelays, what and calibrated as in
+    DelaySpectrumDesc; npairs, pairs [npairs][2] int32 (rows of the solver), scale [npairs][2] float64 (NULL: ones), stats
+    (DELAY_CROSS_STATS bits), nbins and bin_of_pair [npairs] int32 in [-1, nbins) (NULL iff nbins == 0), the operator and norm_f."""
+    _fields_ = [("ndelays", C.c_int32), ("what", C.c_int32), ("calibrated", C.c_int32), ("npairs", C.c_int32), ("pairs", C.c_void_p),
+                ("scale", C.c_void_p), ("stats", C.c_int32), ("nbins", C.c_int32), ("bin_of_pair", C.c_void_p), ("op_r", C.c_void_p),
+                ("op_i", C.c_void_p), ("norm_f", C.c_void_p)]
+
+
 class DelayTransferDesc(C.Structure):
     """cal_delay_transfer_desc (include/calamity_hip.h: cal_solver_delay_transfer): ndelays columns of the operator op_r + i op_i
     ([nfreqs][ndelays], solver dtype), calibrated 0 / 1, nbins and bin_of_bl [nbls] int32 in [-1, nbins) (NULL iff nbins == 0), the
@@ -128,6 +140,12 @@ class ReportPlanDesc(C.Structure):
     (0: the problem's), or a transfer description with its scratch bound."""
     _fields_ = [("spectrum", C.POINTER(DelaySpectrumDesc)), ("degeneracy", C.POINTER(DegeneracyDesc)), ("scratch_bytes", C.c_int64),
                 ("with_power_bl", C.c_int32), ("nslices", C.c_int32), ("transfer", C.POINTER(DelayTransferDesc))]
+
+
+class CrossReportPlanDesc(ReportPlanDesc):
+    """cal_report_plan_desc with its last field, read for the selectors 60 .. 65 only: a cross description, planned under scratch_bytes
+    (the spectrum's bound)."""
+    _fields_ = [("cross", C.POINTER(DelayCrossDesc))]
 
 
 class CoeffSolveDesc(C.Structure):
@@ -253,6 +271,7 @@ SYMBOLS = {
     "cal_solver_robust_weights": (C.c_int, [_P, C.POINTER(RobustDesc), _P, _P]),
     "cal_solver_delay_spectrum": (C.c_int, [_P, C.POINTER(DelaySpectrumDesc), _P, _P, _P, _P, _P, _P]),
     "cal_solver_set_delay_spectrum_scratch": (C.c_int, [_P, C.c_int64]),
+    "cal_solver_delay_cross_spectrum": (C.c_int, [_P, C.POINTER(DelayCrossDesc), _P, _P, _P, _P, _P, _P, _P, _P]),
     "cal_solver_delay_transfer": (C.c_int, [_P, C.POINTER(DelayTransferDesc), _P, _P, _P, _P, _P, _P, C.POINTER(FitErrorsCounts)]),
     "cal_solver_set_delay_transfer_scratch": (C.c_int, [_P, C.c_int64]),
     "cal_solver_fix_degeneracies": (C.c_int, [_P, C.POINTER(DegeneracyDesc), _P, _P, _P, _P, _P, _P, _P]),

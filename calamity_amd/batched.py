@@ -62,6 +62,26 @@ def replicate_slices(prob, nt, groups=None, share_tiles=True):
     return sub, bl, cidx
 
 
+def split_pairs(pairs, rows, nbls):
+    """Share out ``pairs`` ``[npairs, 2]`` of global rows over the workers whose global rows are ``rows[r]`` (in the worker's local
+    order): ``(sel, local)`` with ``sel[r]`` the positions of worker ``r``'s pairs in ``pairs`` and ``local[r]`` those pairs as its
+    local rows.  ``ValueError`` for a pair whose rows lie on two workers and for a worker without a pair."""
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    owner, where = np.full(nbls, -1, dtype=np.int64), np.zeros(nbls, dtype=np.int64)
+    for r, idx in enumerate(rows):
+        owner[idx], where[idx] = r, np.arange(len(idx))
+    own = owner[pairs]
+    split = np.nonzero(own[:, 0] != own[:, 1])[0]
+    if len(split):
+        p = int(split[0])
+        raise ValueError(f"pair {p} = ({pairs[p, 0]}, {pairs[p, 1]}) joins rows of two workers ({own[p, 0]}, {own[p, 1]})")
+    sel = [np.nonzero(own[:, 0] == r)[0] for r in range(len(rows))]
+    for r, s in enumerate(sel):
+        if len(s) == 0:
+            raise ValueError(f"worker {r} holds no pair: every worker must take part in the exchange of the bins")
+    return sel, [where[pairs[s]].astype(np.int32) for s in sel]
+
+
 class _HostExchange:
     """In-process all-reduce between worker threads (cal_solver_set_exchange_hook): every worker leaves a view of its staging
     buffer, all of them reduce the views in rank order -- the same arithmetic on every worker -- and each writes the result
@@ -281,6 +301,32 @@ class SliceBatchFitter:
 
     def _set_delay_spectrum_scratch(self, nbytes):
         self._each(lambda r, s: s._set_delay_spectrum_scratch(nbytes))
+
+    def delay_cross_spectrum(self, op, norm_f, pairs, scale=None, what=("data", "model", "resid"), stats=("cross", "diff"), calibrated=False,
+                             bin_of_pair=None, nbins=0, per_pair=False, g_r=None, g_i=None):
+        """``HipFitSolver.delay_cross_spectrum`` on global slice-major rows: ``pairs`` ``[npairs, 2]`` rows of the batch.  Every worker
+        takes the pairs whose two rows it holds, mapped to its local rows; a pair split over two workers raises ``ValueError`` (it
+        cannot happen for the same baseline in two slices: the groups of a share are replicated over the slices), and so does a
+        worker left without a pair (it could not join the exchange).  The binned arrays and ``count_bin`` are worker 0's (with several
+        workers the library has summed them over the workers); ``norm_pair`` and the ``per_pair`` arrays are put back into the
+        caller's pair order."""
+        pairs = np.asarray(pairs, dtype=np.int64)
+        if pairs.ndim != 2 or pairs.shape[1] != 2 or pairs.shape[0] < 1:
+            raise ValueError(f"pairs must be [npairs >= 1, 2], got shape {pairs.shape}")
+        if pairs.min() < 0 or pairs.max() >= self.nbls:
+            raise ValueError(f"pairs must hold rows in [0, {self.nbls})")
+        kw = dict(what=what, stats=stats, calibrated=calibrated, nbins=nbins, per_pair=per_pair, g_r=g_r, g_i=g_i)
+        scale = None if scale is None else np.asarray(scale, dtype=np.float64)
+        bins = None if bin_of_pair is None else np.asarray(bin_of_pair)
+        if self.nworkers == 1:
+            return self.solvers[0].delay_cross_spectrum(op, norm_f, pairs, scale=scale, bin_of_pair=bins, **kw)
+        sel, local = split_pairs(pairs, self.rows, self.nbls)
+        outs = self._each(lambda r, s: s.delay_cross_spectrum(op, norm_f, local[r], scale=None if scale is None else scale[sel[r]],
+                                                              bin_of_pair=None if bins is None else bins[sel[r]], **kw))
+        out = dict(outs[0], norm_pair=self._scatter([o["norm_pair"] for o in outs], sel))
+        if per_pair:
+            out["per_pair"] = {k: {q: self._scatter([o["per_pair"][k][q] for o in outs], sel) for q in v} for k, v in outs[0]["per_pair"].items()}
+        return out
 
     def delay_transfer(self, op, ridge=1e-6, calibrated=False, bin_of_bl=None, nbins=0, per_baseline=False, g_r=None, g_i=None):
         """``HipFitSolver.delay_transfer`` on the global arrays, like ``delay_spectrum``: ``bin_of_bl`` ``[nt * nbls]`` in the global

@@ -905,6 +905,68 @@ def _check_delay_transfer(delay_transfer, ridge, delay_spectrum, freeze_model):
         raise ValueError(f"delay_transfer_ridge must be finite and >= 0, got {ridge!r}")
 
 
+def _check_delay_cross(delay_cross_spectrum, delay_spectrum, batch_slices, init_guesses_from_previous_time_step):
+    """The ``delay_cross_spectrum`` keyword of ``calibrate_and_model_tensor``, checked before anything is touched (``ValueError``)."""
+    if not any(delay_cross_spectrum is v for v in (False, True)) and delay_cross_spectrum != "baselines":
+        raise ValueError(f"delay_cross_spectrum must be False, True or 'baselines', got {delay_cross_spectrum!r}")
+    if not delay_cross_spectrum:
+        return
+    if not delay_spectrum:
+        raise ValueError("delay_cross_spectrum needs delay_spectrum=True or 'baselines': it uses that spectrum's operator, taper, bins and calibrated switch")
+    if init_guesses_from_previous_time_step:
+        raise ValueError("delay_cross_spectrum pairs the times of a batch: init_guesses_from_previous_time_step (a chain of single times) contradicts it")
+    if batch_slices is not None and batch_slices is not True and int(batch_slices) < 2:
+        raise ValueError(f"delay_cross_spectrum pairs the times of a batch: batch_slices={batch_slices!r} leaves nothing to pair (True or at least 2)")
+
+
+def delay_cross_pairing(polnums, time_indices):
+    """The pairs of a batch's unskipped slices, given in order by their polarization numbers and time indices: slices ``i`` and
+    ``i + 1`` pair when they share the polarization and their time indices differ by exactly 1, and the walk then moves on by two;
+    otherwise it moves on by one and slice ``i`` stays unpaired.  Returns the list of ``(i, i + 1)``."""
+    pairs, i = [], 0
+    while i + 1 < len(polnums):
+        if polnums[i] == polnums[i + 1] and abs(int(time_indices[i + 1]) - int(time_indices[i])) == 1:
+            pairs.append((i, i + 1))
+            i += 2
+        else:
+            i += 1
+    return pairs
+
+
+def delay_cross_rows(pairing, dspec, rms, nbls):
+    """What ``SliceBatchFitter.delay_cross_spectrum`` takes for the slice pairs ``pairing`` of a batch: pair ``p`` of baseline row ``b``
+    is rows ``(t nbls + b, t' nbls + b)`` with scales ``(rms_t, rms_t')`` and bin ``pairindex nbins + bin_of_bl[b]``.  Returns
+    ``(pairs [npairs, 2] int32, scale [npairs, 2], bin_of_pair [npairs] int32)``, slice pair by slice pair."""
+    b = np.arange(nbls, dtype=np.int64)
+    pairs = np.concatenate([np.stack([t0 * nbls + b, t1 * nbls + b], axis=1) for t0, t1 in pairing]).astype(np.int32)
+    scale = np.concatenate([np.tile([float(rms[t0]), float(rms[t1])], (nbls, 1)) for t0, t1 in pairing])
+    bins = np.concatenate([k * dspec["nbins"] + np.asarray(dspec["bin_of_bl"], dtype=np.int64) for k in range(len(pairing))]).astype(np.int32)
+    return pairs, scale, bins
+
+
+def delay_cross_entry(cross, dspec, k, partner_time_index, prob, ant_array):
+    """Slice pair ``k`` of a ``delay_cross_spectrum`` over ``delay_cross_rows`` as what both of its members report under
+    ``fit_history[...]["delay_spectrum"]["cross"]``: ``data``, ``model``, ``resid`` ``[nbins, ndelays]``, the MEAN cross power per
+    baseline-length bin in the data's units squared (the scales were the slices' ``rms``; 0 for a bin without a counted pair),
+    ``noise`` with the mean half-difference power of the same three, ``nbls`` the counted pairs per bin, the partner's time index, and
+    with per-pair rows ``per_baseline`` keyed by antenna numbers."""
+    nb, nbins = prob.nbls, dspec["nbins"]
+    bins, rows = slice(k * nbins, (k + 1) * nbins), slice(k * nb, (k + 1) * nb)
+    count = np.asarray(cross["count_bin"][bins], dtype=np.float64)
+    mean = np.divide(1.0, count, out=np.zeros_like(count), where=count > 0)[:, None]
+    entry = {"partner_time_index": int(partner_time_index), "nbls": count.astype(np.int64), "noise": {}}
+    for q in ("data", "model", "resid"):
+        entry[q] = mean * np.asarray(cross["cross"][q][bins])
+        entry["noise"][q] = mean * np.asarray(cross["diff"][q][bins])
+    if "per_pair" in cross:
+        ants = np.asarray(ant_array)
+        pp = cross["per_pair"]
+        entry["per_baseline"] = {(int(ants[i]), int(ants[j])): dict({q: pp["cross"][q][rows][b] for q in ("data", "model", "resid")},
+                                                                     noise={q: pp["diff"][q][rows][b] for q in ("data", "model", "resid")})
+                                 for b, (i, j) in enumerate(zip(prob.bl_ant0, prob.bl_ant1))}
+    return entry
+
+
 def baseline_length_bins(lengths, width):
     """Baseline rows into bins of ``width`` metres, bin ``floor(length / width)``, only the bins that hold a row, in ascending order:
     ``(bin_of_bl [nbls] int32, bllen_m [nbins])`` with ``bllen_m`` the mean length of each bin's rows."""
@@ -920,7 +982,8 @@ def delay_spectrum_setup(uvdata, ant_array, prob, taper="bh4", max_dly=None, bll
     """What the delay-spectrum pass of every slice of a call shares: the operator, ``norm_f`` and delays (``modeling.delay_transform``
     on the data's frequencies), the length bin of every baseline row of ``prob`` (``baseline_length_bins`` on the antenna positions of
     ``uvdata``; ``ant_array``: the antenna numbers ``prob``'s antenna indices count through) and the two switches.  ``transfer_ridge``
-    stays ``None`` unless the call also asks for the delay transfer (``delay_transfer``: its ridge then)."""
+    stays ``None`` unless the call also asks for the delay transfer (``delay_transfer``: its ridge then), ``cross`` unless it asks for the
+    cross spectrum of paired times (``delay_cross_spectrum``: ``"bins"`` or ``"baselines"`` then)."""
     op, norm_f, delays_ns = modeling.delay_transform(np.asarray(uvdata.freq_array, dtype=np.float64).ravel(), taper=taper, max_delay_ns=max_dly)
     if op.shape[1] < 1 or op.shape[1] > 4096:
         raise ValueError(f"the delay spectrum has {op.shape[1]} delays: between 1 and 4096 (delay_spectrum_max_dly)")
@@ -929,7 +992,7 @@ def delay_spectrum_setup(uvdata, ant_array, prob, taper="bh4", max_dly=None, bll
     lengths = np.asarray([np.linalg.norm(pos[int(ants[i])] - pos[int(ants[j])]) for i, j in zip(prob.bl_ant0, prob.bl_ant1)])
     bin_of_bl, bllen_m = baseline_length_bins(lengths, bllen_bin)
     return dict(op=op, norm_f=norm_f, delays_ns=delays_ns, bin_of_bl=bin_of_bl, nbins=len(bllen_m), bllen_m=bllen_m, calibrated=bool(calibrated),
-                per_baseline=bool(per_baseline), transfer_ridge=None)
+                per_baseline=bool(per_baseline), transfer_ridge=None, cross=None)
 
 
 def delay_spectrum_slice_bins(dspec, nt):
@@ -1107,6 +1170,7 @@ def calibrate_and_model_tensor(
     fix_degeneracies=False,
     degeneracy_iters=6,
     degeneracy_phase_ref=True,
+    delay_cross_spectrum=False,
     delay_transfer=False,
     delay_transfer_ridge=1e-6,
     delay_spectrum=False,
@@ -1311,6 +1375,17 @@ def calibrate_and_model_tensor(
       (the antenna pairs of ``fg_model_comps_dict``, the keys of ``per_baseline``): held as ``(j, i)`` its spectrum is the mirror image
       in delay of ``(i, j)``'s.  A joint time-basis fit reports every time on its own.
       ``ValueError`` before any device work for an unknown taper, a bin width that is not positive, a negative ``delay_spectrum_max_dly``.
+    * ``delay_cross_spectrum`` (``False`` | ``True`` | ``"baselines"``; a Python keyword only; default off: no call changes by a bit and no
+      new kernel is launched; needs ``delay_spectrum`` on and batching, else ``ValueError`` before anything is touched -- ``batch_slices``
+      ``False`` or 1 and ``init_guesses_from_previous_time_step`` are refused; an automatic batch size becomes even): delay power that
+      the noise does not bias (``HipFitSolver.delay_cross_spectrum``: one more device pass beside the spectrum's, at the reported gains,
+      with the spectrum's operator, taper, bins and ``delay_spectrum_calibrated``).  Inside a batch the unskipped slices are paired in
+      order (``delay_cross_pairing``): slices ``i`` and ``i + 1`` pair when they share the polarization and their time indices differ by
+      exactly 1, and the walk moves on by two; otherwise slice ``i`` stays unpaired.  A joint time-basis fit pairs the same way.  Both
+      members of a pair get ``["delay_spectrum"]["cross"]``: ``partner_time_index``, ``data``, ``model``, ``resid`` ``[nbins, Ndelays]`` -- the
+      MEAN over the bin's baselines of ``Re(X_t conj(X_t')) / norm`` under the COMMON mask of the two times, data's units squared, signed --,
+      ``noise`` with the same three for the mean half-difference power ``|X_t - X_t'|^2 / (2 norm)``, the noise spectrum measured from the
+      data, and ``nbls``; ``"baselines"`` adds ``per_baseline`` keyed by antenna numbers.  An unpaired slice has no ``"cross"`` key.
     * ``delay_transfer`` / ``delay_transfer_ridge`` (default off: no call changes by a bit and no new kernel is launched; needs
       ``delay_spectrum`` on and a fitted model, else ``ValueError`` before anything is touched -- ``freeze_model=True`` is refused): the
       signal loss of the fit in delay space (``HipFitSolver.delay_transfer``: one more device pass beside the spectrum's, at the reported
@@ -1345,6 +1420,7 @@ def calibrate_and_model_tensor(
         raise ValueError("give gain_basis or gain_max_dly, not both")
     _check_delay_spectrum(delay_spectrum, delay_spectrum_taper, delay_spectrum_max_dly, delay_spectrum_bllen_bin)
     _check_delay_transfer(delay_transfer, delay_transfer_ridge, delay_spectrum, freeze_model)
+    _check_delay_cross(delay_cross_spectrum, delay_spectrum, batch_slices, init_guesses_from_previous_time_step)
     controls = FitControls.pick(locals())
     controls.check(gain_basis is not None or gain_max_dly is not None, gain_time_basis is not None or gain_time_scale is not None, freeze_model, use_min)
     if gain_max_dly is not None:
@@ -1427,6 +1503,7 @@ def calibrate_and_model_tensor(
                                      per_baseline=delay_spectrum == "baselines")
         if delay_transfer:
             dspec["transfer_ridge"] = float(delay_transfer_ridge)
+        dspec["cross"] = {False: None, True: "bins", "baselines": "baselines"}[delay_cross_spectrum]
     degen = degeneracy_setup(uvdata, gains.ant_array, degen_mode, degeneracy_iters, degeneracy_phase_ref) if degen_mode is not None else None
     if parallel_fits is None:
         parallel_fits = 1
@@ -1434,7 +1511,7 @@ def calibrate_and_model_tensor(
         parallel_fits = 1
     times = np.unique(uvdata.time_array)
     if batch_slices is None:
-        batch_slices = parallel_fits <= 1 or gain_time_basis is not None
+        batch_slices = parallel_fits <= 1 or gain_time_basis is not None or bool(delay_cross_spectrum)
     if init_guesses_from_previous_time_step:
         batch_slices = False  # every time starts from the previous one's result: a chain, not a batch
     # the call's settings, once, for the loop and the batches alike (slice_pipeline's stages read them)
@@ -1453,6 +1530,8 @@ def calibrate_and_model_tensor(
             max_batch = len(times)
         else:
             max_batch = _auto_batch(prob, dtype, layout) if batch_slices is True else max(1, min(int(batch_slices), _lib_max_slices()))
+            if delay_cross_spectrum and batch_slices is True:
+                max_batch = max(2, max_batch) // 2 * 2  # the times are paired inside a batch: an even number of them
         fit_history = _fit_slices_batched(cfg, max_batch)
         _file_gain_std(fit_history, errs, gains)
         return model, resid, gains, fit_history  # (every fitted slice left its write-back in its final state)
@@ -1860,6 +1939,7 @@ def calibrate_and_model_dpss(
     fix_degeneracies=False,
     degeneracy_iters=6,
     degeneracy_phase_ref=True,
+    delay_cross_spectrum=False,
     delay_transfer=False,
     delay_transfer_ridge=1e-6,
     delay_spectrum=False,
@@ -1875,6 +1955,7 @@ def calibrate_and_model_dpss(
     ``gain_basis_errors`` among ``fitting_kwargs``."""
     _check_delay_spectrum(delay_spectrum, delay_spectrum_taper, delay_spectrum_max_dly, delay_spectrum_bllen_bin)
     _check_delay_transfer(delay_transfer, delay_transfer_ridge, delay_spectrum, fitting_kwargs.get("freeze_model", False))
+    _check_delay_cross(delay_cross_spectrum, delay_spectrum, fitting_kwargs.get("batch_slices"), fitting_kwargs.get("init_guesses_from_previous_time_step", False))
     _check_degeneracy_call(fix_degeneracies, degeneracy_iters, fitting_kwargs)
     waker = _wake_device(fitting_kwargs.get("devices"))
     try:
@@ -1886,7 +1967,7 @@ def calibrate_and_model_dpss(
             uvdata=uvdata, fg_model_comps_dict=dpss_model_comps_dict, include_autos=include_autos, verbose=verbose,
             notebook_progressbar=notebook_progressbar, delay_spectrum=delay_spectrum, delay_spectrum_taper=delay_spectrum_taper,
             delay_spectrum_max_dly=delay_spectrum_max_dly, delay_spectrum_bllen_bin=delay_spectrum_bllen_bin,
-            delay_spectrum_calibrated=delay_spectrum_calibrated, delay_transfer=delay_transfer, delay_transfer_ridge=delay_transfer_ridge,
+            delay_spectrum_calibrated=delay_spectrum_calibrated, delay_transfer=delay_transfer, delay_transfer_ridge=delay_transfer_ridge, delay_cross_spectrum=delay_cross_spectrum,
             fix_degeneracies=fix_degeneracies, degeneracy_iters=degeneracy_iters,
             degeneracy_phase_ref=degeneracy_phase_ref, **fitting_kwargs,
         )
@@ -1931,6 +2012,7 @@ def calibrate_and_model_mixed(
     fix_degeneracies=False,
     degeneracy_iters=6,
     degeneracy_phase_ref=True,
+    delay_cross_spectrum=False,
     delay_transfer=False,
     delay_transfer_ridge=1e-6,
     delay_spectrum=False,
@@ -1948,6 +2030,7 @@ def calibrate_and_model_mixed(
     and so are ``fit_errors`` and ``gain_basis_errors`` among ``fitting_kwargs``."""
     _check_delay_spectrum(delay_spectrum, delay_spectrum_taper, delay_spectrum_max_dly, delay_spectrum_bllen_bin)
     _check_delay_transfer(delay_transfer, delay_transfer_ridge, delay_spectrum, fitting_kwargs.get("freeze_model", False))
+    _check_delay_cross(delay_cross_spectrum, delay_spectrum, fitting_kwargs.get("batch_slices"), fitting_kwargs.get("init_guesses_from_previous_time_step", False))
     _check_degeneracy_call(fix_degeneracies, degeneracy_iters, fitting_kwargs)
     fitting_grps, blvecs, _, _ = modeling.get_uv_overlapping_grps_conjugated(
         uvdata, red_tol=red_tol, include_autos=include_autos, red_tol_freq=red_tol_freq, n_angle_bins=n_angle_bins,
@@ -1971,7 +2054,7 @@ def calibrate_and_model_mixed(
         uvdata=uvdata, fg_model_comps_dict=model_comps_dict, include_autos=include_autos, verbose=verbose,
         notebook_progressbar=notebook_progressbar, use_redundancy=use_redundancy, delay_spectrum=delay_spectrum, delay_spectrum_taper=delay_spectrum_taper,
         delay_spectrum_max_dly=delay_spectrum_max_dly, delay_spectrum_bllen_bin=delay_spectrum_bllen_bin,
-        delay_spectrum_calibrated=delay_spectrum_calibrated, delay_transfer=delay_transfer, delay_transfer_ridge=delay_transfer_ridge,
+        delay_spectrum_calibrated=delay_spectrum_calibrated, delay_transfer=delay_transfer, delay_transfer_ridge=delay_transfer_ridge, delay_cross_spectrum=delay_cross_spectrum,
             fix_degeneracies=fix_degeneracies, degeneracy_iters=degeneracy_iters,
         degeneracy_phase_ref=degeneracy_phase_ref, **fitting_kwargs,
     )
@@ -2086,6 +2169,7 @@ def read_calibrate_and_model_dpss(
     fix_degeneracies=False,
     degeneracy_iters=6,
     degeneracy_phase_ref=True,
+    delay_cross_spectrum=False,
     delay_transfer=False,
     delay_transfer_ridge=1e-6,
     delay_spectrum=False,
@@ -2119,11 +2203,16 @@ def read_calibrate_and_model_dpss(
     ``delay_transfer`` / ``delay_transfer_ridge`` are ``calibrate_and_model_tensor``'s (Python keywords only); the archive then also holds
     ``transfer`` ``[Npols, Ntimes, nbins, Ndelays]``, ``transfer_nsingular`` ``[Npols, Ntimes]`` (-1 for a skipped slice) and, with
     ``"baselines"``, ``transfer_bl`` ``[Npols, Ntimes, rows, Ndelays]``.
+    ``delay_cross_spectrum`` is ``calibrate_and_model_tensor``'s (a Python keyword only); the archive then also holds ``cross_partner``
+    ``[Npols, Ntimes]`` (the partner's time index; -1 for a slice without one), ``cross_nbls`` ``[Npols, Ntimes, nbins]``, ``cross_data``,
+    ``cross_model``, ``cross_resid`` and ``cross_noise_data``, ``cross_noise_model``, ``cross_noise_resid`` ``[Npols, Ntimes, nbins, Ndelays]``
+    (``nan`` for a slice without a partner) and, with ``"baselines"``, ``cross_antpairs`` and the same six with ``_bl`` ``[Npols, Ntimes, rows, Ndelays]``.
     ``fix_degeneracies``, ``degeneracy_iters``, ``degeneracy_phase_ref`` are ``calibrate_and_model_tensor``'s too (Python keywords only);
     the sky model is ``input_model_files`` and the written gains and model are the fixed ones.
     """
     _check_delay_spectrum(delay_spectrum, delay_spectrum_taper, delay_spectrum_max_dly, delay_spectrum_bllen_bin)
     _check_delay_transfer(delay_transfer, delay_transfer_ridge, delay_spectrum, calibration_kwargs.get("freeze_model", False))
+    _check_delay_cross(delay_cross_spectrum, delay_spectrum, calibration_kwargs.get("batch_slices"), calibration_kwargs.get("init_guesses_from_previous_time_step", False))
     _check_degeneracy_call(fix_degeneracies, degeneracy_iters, dict(calibration_kwargs, sky_model=input_model_files))
     if delay_spectrum_outfile is not None and not delay_spectrum:
         raise ValueError("delay_spectrum_outfile needs delay_spectrum=True or 'baselines'")
@@ -2145,6 +2234,7 @@ def read_calibrate_and_model_dpss(
             **(dict(delay_spectrum=delay_spectrum, delay_spectrum_taper=delay_spectrum_taper, delay_spectrum_max_dly=delay_spectrum_max_dly,
                     delay_spectrum_bllen_bin=delay_spectrum_bllen_bin, delay_spectrum_calibrated=delay_spectrum_calibrated) if delay_spectrum else {}),
             **(dict(delay_transfer=True, delay_transfer_ridge=delay_transfer_ridge) if delay_transfer else {}),
+            **(dict(delay_cross_spectrum=delay_cross_spectrum) if delay_cross_spectrum else {}),
             **(dict(fix_degeneracies=fix_degeneracies, degeneracy_iters=degeneracy_iters, degeneracy_phase_ref=degeneracy_phase_ref)
                if fix_degeneracies else {}),
             **(dict(gain_basis_errors=True) if gain_basis_errors else {}),
@@ -2216,12 +2306,33 @@ def delay_spectrum_tables(fit_info):
         out["transfer_nsingular"] = np.full((len(pols), ntimes), -1, dtype=np.int64)
         if "transfer_per_baseline" in first:
             out["transfer_bl"] = np.full((len(pols), ntimes, len(pairs), nd), np.nan)
+    crossed = [e["cross"] for e in entries if "cross" in e]
+    if crossed:  # (nan, -1 and 0 pairs for a slice without a partner)
+        out["cross_partner"] = np.full((len(pols), ntimes), -1, dtype=np.int64)
+        out["cross_nbls"] = np.zeros((len(pols), ntimes, nbins), dtype=np.int64)
+        for k in ("data", "model", "resid"):
+            out["cross_" + k] = np.full((len(pols), ntimes, nbins, nd), np.nan)
+            out["cross_noise_" + k] = np.full((len(pols), ntimes, nbins, nd), np.nan)
+        cpairs = list(crossed[0]["per_baseline"]) if "per_baseline" in crossed[0] else None
+        if cpairs is not None:
+            out["cross_antpairs"] = np.asarray(cpairs, dtype=np.int64).reshape(-1, 2)
+            for k in ("data", "model", "resid"):
+                out["cross_" + k + "_bl"] = np.full((len(pols), ntimes, len(cpairs), nd), np.nan)
+                out["cross_noise_" + k + "_bl"] = np.full((len(pols), ntimes, len(cpairs), nd), np.nan)
     for i, p in enumerate(pols):
         for t, h in fit_info[p].items():
             if "delay_spectrum" not in h:
                 continue
             e = h["delay_spectrum"]
             out["nbls"][i, t] = e["nbls"]
+            if "cross" in e:
+                x = e["cross"]
+                out["cross_partner"][i, t], out["cross_nbls"][i, t] = x["partner_time_index"], x["nbls"]
+                for k in ("data", "model", "resid"):
+                    out["cross_" + k][i, t], out["cross_noise_" + k][i, t] = x[k], x["noise"][k]
+                    if "per_baseline" in x:
+                        out["cross_" + k + "_bl"][i, t] = [x["per_baseline"][ap][k] for ap in cpairs]
+                        out["cross_noise_" + k + "_bl"][i, t] = [x["per_baseline"][ap]["noise"][k] for ap in cpairs]
             if "transfer" in e:
                 out["transfer"][i, t], out["transfer_nsingular"][i, t] = e["transfer"], e["transfer_nsingular"]
                 if "transfer_bl" in out:

@@ -33,6 +33,7 @@
 #include "fit_error_kernels.hpp"
 #include "gain_error_kernels.hpp"
 #include "delay_spectrum_kernels.hpp"
+#include "delay_cross_kernels.hpp"
 #include "delay_transfer_kernels.hpp"
 #include "degeneracy_kernels.hpp"
 #include "gain_basis_solve_kernels.hpp"
@@ -191,6 +192,8 @@ struct cal_solver {
   virtual int delay_spectrum(const cal_delay_spectrum_desc* d, const void* g_r, const void* g_i, double* power_bl, double* norm_bl, double* power_bin,
                              double* count_bin) = 0;
   virtual int set_delay_spectrum_scratch(int64_t bytes) = 0;
+  virtual int delay_cross_spectrum(const cal_delay_cross_desc* d, const void* g_r, const void* g_i, double* cross_pair, double* diff_pair, double* norm_pair,
+                                   double* cross_bin, double* diff_bin, double* count_bin) = 0;
   virtual int delay_transfer(const cal_delay_transfer_desc* d, const void* g_r, const void* g_i, double* absorbed_bl, double* noise_bl, double* absorbed_bin,
                              double* count_bin, cal_fit_errors_counts* counts) = 0;
   virtual int set_delay_transfer_scratch(int64_t bytes) = 0;
@@ -288,6 +291,8 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
   // a chunk's masked planes in T (ds_x) and power in double (ds_pow); norm_bl | power_bin | count_bin (ds_out; the last two are the exchange payload)
   DevBuf ds_op, ds_normf, ds_ent, ds_ptr, ds_x, ds_pow, ds_out;
   int64_t ds_bound = kCsScratchDefault;        // bytes of scratch a chunk of rows may take (set_delay_spectrum_scratch)
+  // delay_cross_spectrum (delay_cross_kernels.hpp) reuses them all, with chunks of pairs; the pairs and their scales of a call
+  DevBuf dc_pairs, dc_scale;
   // delay_transfer (delay_transfer_kernels.hpp): the plan of a call (groups, order, Gram work, W offsets, runs, rows, the bins' lists and
   // the operator image); per chunk N (dt_n), the factor (dt_d) and W | S (dt_x); rhs of the Gram kernel (unused), coeff_var of the factor
   // kernel (unused), ok [ngrps] ints + the two counters; absorbed and noise [nbls][ndelays]; valid | absorbed_bin | count_bin (dt_out; the
@@ -660,7 +665,7 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     CAL_TRY(upload(ant_ptr, p.ant_ptr));
     CAL_TRY(upload(ant_ent, p.ant_ent));
 
-    for (DevBuf* b : {&gains_snap, &gains_alt, &coef_snap, &q1, &gcp1, &gc1, &model_buf, &scratch, &fq_out, &fq_gains, &gs_out, &gs_ptr, &gs_ent, &gs_mask, &cs_rhs, &rw_w0, &rw_out, &ds_op, &ds_normf, &ds_ent, &ds_ptr, &ds_x, &ds_pow, &ds_out, &dt_grp, &dt_order, &dt_work, &dt_woff, &dt_runs, &dt_rows, &dt_ent, &dt_ptr, &dt_op, &dt_n, &dt_d, &dt_x, &dt_rhs, &dt_cv, &dt_ok, &dt_abs, &dt_noise, &dt_out, &dg_z, &dg_w, &dg_geo, &dg_idx, &dg_part, &dg_st, &dg_gout, &dg_gref,
+    for (DevBuf* b : {&gains_snap, &gains_alt, &coef_snap, &q1, &gcp1, &gc1, &model_buf, &scratch, &fq_out, &fq_gains, &gs_out, &gs_ptr, &gs_ent, &gs_mask, &cs_rhs, &rw_w0, &rw_out, &ds_op, &ds_normf, &ds_ent, &ds_ptr, &ds_x, &ds_pow, &ds_out, &dc_pairs, &dc_scale, &dt_grp, &dt_order, &dt_work, &dt_woff, &dt_runs, &dt_rows, &dt_ent, &dt_ptr, &dt_op, &dt_n, &dt_d, &dt_x, &dt_rhs, &dt_cv, &dt_ok, &dt_abs, &dt_noise, &dt_out, &dg_z, &dg_w, &dg_geo, &dg_idx, &dg_part, &dg_st, &dg_gout, &dg_gref,
                        &gn_s, &gn_g0, &gn_save, &gn_x, &gn_res, &gn_ns, &gn_D, &gn_m, &gn_sd, &gn_rows, &gn_part, &gn_scal, &gn_lam, &gn_grp, &gn_rowptr,
                        &lb_vec, &lb_part, &lb_dots, &lb_state, &lb_losses, &lb_count})
       b->release();
@@ -1915,6 +1920,81 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     if (bytes < 0) return fail(CAL_ERR_INVALID, "set_delay_spectrum_scratch: negative bound");
     ds_bound = bytes == 0 ? kCsScratchDefault : bytes;
     for (DevBuf* b : {&ds_x, &ds_pow}) b->release();
+    return CAL_OK;
+  }
+
+  // cal_solver_delay_cross_spectrum: the model pass of model(), then per chunk of pairs dcross_rows_kernel, dcross_transform_kernel
+  // (delay_cross_kernels.hpp) and dspec_bin_kernel as it is, over pairs instead of rows and with nstat nq planes.  The buffers are
+  // those of delay_spectrum and the bound is ds_bound; the chunks are cut at multiples of the transform's 64 pairs where that fits.
+  int delay_cross_spectrum(const cal_delay_cross_desc* d, const void* g_r, const void* g_i, double* cross_pair, double* diff_pair, double* norm_pair,
+                           double* cross_bin, double* diff_bin, double* count_bin) override {
+    HIP_TRY(hipSetDevice(device));
+    if (!d) return fail(CAL_ERR_INVALID, "delay_cross_spectrum: null description");
+    CAL_TRY(require_set("delay_cross_spectrum", false));
+    const T2* g = nullptr;
+    CAL_TRY(report_gains("delay_cross_spectrum", g_r, g_i, &g));
+    if (d->ndelays < 1 || d->ndelays > 4096) return fail(CAL_ERR_INVALID, "delay_cross_spectrum: ndelays = %d lies outside [1, 4096]", d->ndelays);
+    if ((d->what & 7) == 0 || (d->what & ~7))
+      return fail(CAL_ERR_INVALID, "delay_cross_spectrum: what = %d: bits 0 (data), 1 (model), 2 (residual), at least one", d->what);
+    if (d->calibrated != 0 && d->calibrated != 1) return fail(CAL_ERR_INVALID, "delay_cross_spectrum: calibrated = %d (0 or 1)", d->calibrated);
+    if (!d->op_r || !d->op_i || !d->norm_f) return fail(CAL_ERR_INVALID, "delay_cross_spectrum: null operator or norm_f");
+    if (d->nbins < 0) return fail(CAL_ERR_INVALID, "delay_cross_spectrum: nbins = %d", d->nbins);
+    if ((d->nbins == 0) != (d->bin_of_pair == nullptr)) return fail(CAL_ERR_INVALID, "delay_cross_spectrum: bin_of_pair goes with nbins > 0, and only with it");
+    if (d->nbins == 0 && (cross_bin || diff_bin || count_bin)) return fail(CAL_ERR_INVALID, "delay_cross_spectrum: binned outputs need nbins > 0");
+    if (!(d->stats & 1) && (cross_pair || cross_bin)) return fail(CAL_ERR_INVALID, "delay_cross_spectrum: cross outputs need bit 0 of stats (stats = %d)", d->stats);
+    if (!(d->stats & 2) && (diff_pair || diff_bin)) return fail(CAL_ERR_INVALID, "delay_cross_spectrum: diff outputs need bit 1 of stats (stats = %d)", d->stats);
+    DelayCrossPlan<T> P;  // the refusals of pairs, stats and scales; the bins' pairs, the chunks, the operator image (report_plan.hpp)
+    CAL_TRY(plan_delay_cross(nbls, nfreqs, fpad, d, ds_bound, P));
+    const int nd = d->ndelays, nbins = d->nbins, np = d->npairs, nq = P.nq, nstat = P.nstat, xpitch = P.xpitch, ndpad = P.ndpad, cpairs = P.cpairs;
+    CAL_TRY(put(ds_op, P.image, false));
+    CAL_TRY(put(ds_normf, P.norm_f, false));
+    CAL_TRY(put(dc_scale, P.scale, false));
+    CAL_TRY(dc_pairs.reserve(2 * (size_t)np * sizeof(int32_t), false));
+    HIP_TRY(copy_sync(dc_pairs.p, d->pairs, 2 * (size_t)np * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (nbins) {
+      CAL_TRY(put(ds_ent, P.bin_ent, false));
+      CAL_TRY(put(ds_ptr, P.chunk_ptr, false));
+    }
+    CAL_TRY(ds_out.reserve(P.n_out * sizeof(double)));
+    CAL_TRY(ds_x.reserve(P.n_x * sizeof(T), false));
+    CAL_TRY(ds_pow.reserve(P.n_pow * sizeof(double), false));
+    const size_t nbin_stat = (size_t)nq * nbins * nd;   // one statistic's bins
+    const size_t nbin_out = P.n_out - np;                // cross_bin | diff_bin | count_bin: the exchange payload
+    double* o_norm = ds_out.as<double>();
+    double* o_sbin = o_norm + np;
+    double* o_cbin = o_sbin + (size_t)nstat * nbin_stat;
+    double* pair_out[2] = {cross_pair, diff_pair};
+    hipError_t copy_err = hipSuccess;
+    CAL_TRY(model_pass(2, [&](T* model_r, T* model_i, T*) {
+      for (int c = 0; c < P.nchunks; ++c) {
+        const long long p0 = (long long)c * cpairs;
+        const int nc = (int)std::min<long long>(cpairs, np - p0);
+        hipLaunchKernelGGL(dcross_rows_kernel<T>, dim3((nc + 3) / 4), dim3(256), 0, stream, model_r, model_i, data_r.as<T>(), data_i.as<T>(), wgts.as<T>(), g,
+                           bl_ant.as<int2>(), dc_pairs.as<int2>() + p0, ds_normf.as<double>(), nc, nfreqs, fpad, xpitch, d->what, d->calibrated,
+                           ds_x.as<T>(), o_norm + p0);
+        hipLaunchKernelGGL(dcross_transform_kernel<T>, dim3((nc + kDcPairs - 1) / kDcPairs, ndpad / kDsCols, nq), dim3(256), 0, stream, ds_x.as<T>(),
+                           ds_op.as<T>(), o_norm + p0, dc_scale.as<double>() + 2 * p0, nc, xpitch, nd, ndpad, d->stats, ds_pow.as<double>());
+        if (nbins)
+          hipLaunchKernelGGL(dspec_bin_kernel, dim3(nbins, (nd + 255) / 256, nstat * nq), dim3(256), 0, stream, ds_pow.as<double>(), o_norm + p0,
+                             ds_ptr.as<int>() + (size_t)c * nbins * 2, ds_ent.as<int>(), (int)p0, nc, nd, nbins, c == 0 ? 1 : 0, o_sbin, o_cbin);
+        int slot = 0;
+        for (int st = 0; st < 2; ++st) {
+          if (!(d->stats >> st & 1)) continue;
+          for (int q = 0; q < nq && pair_out[st] && copy_err == hipSuccess; ++q)  // (the stream orders the copy before the next chunk's kernels)
+            copy_err = hipMemcpyAsync(pair_out[st] + ((size_t)q * np + p0) * nd, ds_pow.as<double>() + ((size_t)slot * nq + q) * nc * nd,
+                                      (size_t)nc * nd * sizeof(double), hipMemcpyDeviceToHost, stream);
+          ++slot;
+        }
+      }
+    }));
+    HIP_TRY(copy_err);
+    // the bins of every rank's pairs add up to the array's: ONE all-reduce of nstat nwhat nbins ndelays + nbins doubles
+    if (nbins && comm_on()) CAL_TRY(all_reduce(o_sbin, nbin_out, CAL_XCHG_F64, CAL_XCHG_SUM));
+    CAL_TRY(give(norm_pair, o_norm, (size_t)np));
+    CAL_TRY(give(cross_bin, o_sbin, nbin_stat));
+    CAL_TRY(give(diff_bin, o_sbin + ((d->stats & 1) ? nbin_stat : 0), nbin_stat));
+    CAL_TRY(give(count_bin, o_cbin, (size_t)nbins));
+    HIP_TRY(hipStreamSynchronize(stream));
     return CAL_OK;
   }
 
@@ -3346,6 +3426,22 @@ int debug_report_plan(const cal_problem_desc* d, const cal_report_plan_desc* r, 
     }
     return give(P.bin_ptr2);
   }
+  if (what >= 60 && what <= 65) {
+    const cal_delay_cross_desc* x = r->cross;
+    if (!x || x->ndelays < 1 || (x->what & 7) == 0 || (x->what & ~7) || x->nbins < 0 || (x->nbins == 0) != (x->bin_of_pair == nullptr) || !x->op_r || !x->op_i ||
+        !x->norm_f || r->scratch_bytes < 0)
+      return fail(CAL_ERR_INVALID, "%s: what = %d takes a cross description cal_solver_delay_cross_spectrum would plan for, and a bound >= 0", who, what);
+    DelayCrossPlan<T> P;
+    CAL_TRY(plan_delay_cross(p.nbls, p.nfreqs, p.fpad, x, r->scratch_bytes == 0 ? kCsScratchDefault : r->scratch_bytes, P));
+    switch (what) {
+      case 60: return give(std::vector<int64_t>{P.nq, P.nstat, P.xpitch, P.ndpad, P.cpairs, P.nchunks, (int64_t)P.n_x, (int64_t)P.n_pow, (int64_t)P.n_out});
+      case 61: return give(P.bin_ent);
+      case 62: return give(P.chunk_ptr);
+      case 63: return give(P.image);
+      case 64: return give(P.norm_f);
+    }
+    return give(P.scale);
+  }
   return fail(CAL_ERR_INVALID, "%s: what = %d", who, what);
 }
 }  // namespace
@@ -4022,6 +4118,11 @@ int cal_solver_delay_spectrum(cal_solver* s, const cal_delay_spectrum_desc* desc
   return s->delay_spectrum(desc, g_r, g_i, power_bl, norm_bl, power_bin, count_bin);
 }
 int cal_solver_set_delay_spectrum_scratch(cal_solver* s, int64_t bytes) { NEED(s); return s->set_delay_spectrum_scratch(bytes); }
+int cal_solver_delay_cross_spectrum(cal_solver* s, const cal_delay_cross_desc* desc, const void* g_r, const void* g_i, double* cross_pair, double* diff_pair,
+                                    double* norm_pair, double* cross_bin, double* diff_bin, double* count_bin) {
+  NEED(s);
+  return s->delay_cross_spectrum(desc, g_r, g_i, cross_pair, diff_pair, norm_pair, cross_bin, diff_bin, count_bin);
+}
 int cal_solver_delay_transfer(cal_solver* s, const cal_delay_transfer_desc* desc, const void* g_r, const void* g_i, double* absorbed_bl, double* noise_bl,
                               double* absorbed_bin, double* count_bin, cal_fit_errors_counts* counts) {
   NEED(s);

@@ -19,6 +19,8 @@ shared Gram and Cholesky core of normal_solve.hpp; the second is the factor step
 (gauss_newton_kernels.hpp), every `lbfgs_*_kernel` (lbfgs_kernels.hpp): no scratch, no spilled VGPRs.
 `dspec_rows_kernel`, `dspec_transform_kernel`, `dspec_bin_kernel` (delay_spectrum_kernels.hpp), both dtypes: no scratch, no spilled VGPRs, and
 two waves per SIMD in the transform kernel.
+`dcross_rows_kernel`, `dcross_transform_kernel` (delay_cross_kernels.hpp), both dtypes: no scratch, no spilled VGPRs, and two waves per
+SIMD in the transform kernel.
 `dtransfer_basis_kernel`, `dtransfer_power_kernel` (delay_transfer_kernels.hpp), both dtypes: no scratch, no spilled VGPRs, and two waves
 per SIMD in the power kernel.
 `degen_rows_kernel`, `degen_sum_kernel`, `degen_solve_kernel`, `degen_phase_kernel`, `degen_apply_gains_kernel`, `degen_apply_rows_kernel`
@@ -79,6 +81,16 @@ for line in sys.stdin:
         m = re.search(r"remark:\s+(ScratchSize \[bytes/lane\]|VGPRs Spill|Occupancy \[waves/SIMD\]): (\d+)", line)
         if m and m.group(1).startswith("Occupancy"):
             if "dspec_transform_kernel" in cur and int(m.group(2)) < 2:
+                bad.append(f"{cur}: occupancy {m.group(2)} waves/SIMD (< 2)")
+        elif m and int(m.group(2)) != 0:
+            bad.append(f"{cur}: {m.group(1)} = {m.group(2)}")
+        continue
+    if cur is not None and any(k in cur for k in ("dcross_rows_kernel", "dcross_transform_kernel")):
+        # the two of the delay cross spectrum: no scratch, no spilled VGPRs; the transform runs the spectrum's loop (2 x 8 accumulator tiles
+        # per wave) and keeps its two waves per SIMD in both dtypes
+        m = re.search(r"remark:\s+(ScratchSize \[bytes/lane\]|VGPRs Spill|Occupancy \[waves/SIMD\]): (\d+)", line)
+        if m and m.group(1).startswith("Occupancy"):
+            if "dcross_transform_kernel" in cur and int(m.group(2)) < 2:
                 bad.append(f"{cur}: occupancy {m.group(2)} waves/SIMD (< 2)")
         elif m and int(m.group(2)) != 0:
             bad.append(f"{cur}: {m.group(1)} = {m.group(2)}")

@@ -92,42 +92,25 @@ __global__ __launch_bounds__(256) void dspec_rows_kernel(const T* __restrict__ m
   if (R.lane == 0) norm_bl[R.b] = acc_n;
 }
 
-// block = (128 rows, 64 delays, quantity).  The complex product is the real one of twice the depth, [x_r | x_i] . [op_r ; -op_i] and
-// [x_r | x_i] . [op_i ; op_r], with the two halves of the depth taken side by side: per step of kDsStep channels the pieces
-// [kDsStep][64] of op_r and op_i are staged in LDS once and serve all 128 rows (v_mfma_f32_16x16x4_f32 / v_mfma_f64_16x16x4_f64; wave w owns
-// the row tiles 2 w, 2 w + 1 and, for each, four column tiles of Re X and four of Im X).  A lane takes its row's channels as 16-byte
-// pieces straight from the plane: lane quarter kq holds channels kq V + s of a piece, so MFMA number s of a piece contracts the channels
-// {kq V + s}, and the operator's rows are read from LDS in that order -- the sum over a piece is complete after its V MFMAs.  The image
-// op ([fk][ndpad] per part, fk = xpitch) is zero beyond nfreqs and ndelays and the planes are zero beyond nfreqs: no tails in the loop.
-// Rows past the chunk's last read its last row again and write nothing.  out: [nq][nrows][ndelays] doubles.
+// The staged-operator loop of the transforms (dspec_transform_kernel, dcross_transform_kernel): X = x op for the wave's kDsRowTiles
+// 16-row tiles and the block's 64 delays from c0 on.  The complex product is the real one of twice the depth, [x_r | x_i] . [op_r ; -op_i]
+// and [x_r | x_i] . [op_i ; op_r], with the two halves of the depth taken side by side: per step of kDsStep channels the pieces
+// [kDsStep][64] of op_r and op_i are staged in LDS once and serve all the block's rows (v_mfma_f32_16x16x4_f32 / v_mfma_f64_16x16x4_f64;
+// per row tile four column tiles of Re X and four of Im X).  A lane takes its row's channels as 16-byte pieces straight from the plane
+// (xrow_r, xrow_i: its row of every tile, at channel kq V): lane quarter kq holds channels kq V + s of a piece, so MFMA number s of a
+// piece contracts the channels {kq V + s}, and the operator's rows are read from LDS in that order -- the sum over a piece is complete
+// after its V MFMAs.  The image op ([fk][ndpad] per part, fk = xpitch) is zero beyond nfreqs and ndelays and the planes are zero beyond
+// nfreqs: no tails in the loop.  All 256 threads of the block call it together (it holds the barriers of the staging).
 template <typename T>
-__global__ __launch_bounds__(256, 2) void dspec_transform_kernel(const T* __restrict__ x, const T* __restrict__ op, const double* __restrict__ norm_bl,
-                                                                  int nrows, int xpitch, int ndelays, int ndpad, double* __restrict__ out) {
+__device__ __forceinline__ void ds_transform_loop(const T* const (&xrow_r)[kDsRowTiles], const T* const (&xrow_i)[kDsRowTiles], const T* __restrict__ op_r,
+                                                  const T* __restrict__ op_i, int xpitch, int ndpad, int c0, T (&s_op)[2][kDsStep][kDsPitch<T>],
+                                                  typename MmT<T>::v4 (&acc_re)[kDsRowTiles][4], typename MmT<T>::v4 (&acc_im)[kDsRowTiles][4]) {
 #pragma clang fp contract(off)
   constexpr int V = 16 / (int)sizeof(T);
-  constexpr int P = kDsPitch<T>;
   typedef ns_vec_t<T> vec_t;
   typedef typename MmT<T>::v4 acc_t;
-  __shared__ __attribute__((aligned(16))) T s_op[2][kDsStep][P];  // [re, im][channel of the step][delay of the block]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
   const int col = lane & 15, kq = lane >> 4;
-  const int r0 = blockIdx.x * kDsRows + wave * (kDsRowTiles * 16);
-  const int c0 = blockIdx.y * kDsCols;
-  const long long plane = (long long)nrows * xpitch;
-  const T* __restrict__ xr = x + (long long)blockIdx.z * 2 * plane;
-  const T* __restrict__ xi = xr + plane;
-  const T* __restrict__ op_r = op;
-  const T* __restrict__ op_i = op + (long long)xpitch * ndpad;
-  const T* xrow_r[kDsRowTiles];
-  const T* xrow_i[kDsRowTiles];
-#pragma unroll
-  for (int rt = 0; rt < kDsRowTiles; ++rt) {
-    int row = r0 + rt * 16 + col;
-    row = row < nrows ? row : nrows - 1;
-    xrow_r[rt] = xr + (long long)row * xpitch + kq * V;
-    xrow_i[rt] = xi + (long long)row * xpitch + kq * V;
-  }
-  acc_t acc_re[kDsRowTiles][4], acc_im[kDsRowTiles][4];
 #pragma unroll
   for (int rt = 0; rt < kDsRowTiles; ++rt)
 #pragma unroll
@@ -172,6 +155,35 @@ __global__ __launch_bounds__(256, 2) void dspec_transform_kernel(const T* __rest
       }
     }
   }
+}
+
+// block = (128 rows, 64 delays, quantity): wave w owns the row tiles 2 w, 2 w + 1 of ds_transform_loop.  Rows past the chunk's last read
+// its last row again and write nothing.  out: [nq][nrows][ndelays] doubles.
+template <typename T>
+__global__ __launch_bounds__(256, 2) void dspec_transform_kernel(const T* __restrict__ x, const T* __restrict__ op, const double* __restrict__ norm_bl,
+                                                                  int nrows, int xpitch, int ndelays, int ndpad, double* __restrict__ out) {
+#pragma clang fp contract(off)
+  constexpr int V = 16 / (int)sizeof(T);
+  typedef typename MmT<T>::v4 acc_t;
+  __shared__ __attribute__((aligned(16))) T s_op[2][kDsStep][kDsPitch<T>];  // [re, im][channel of the step][delay of the block]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int col = lane & 15, kq = lane >> 4;
+  const int r0 = blockIdx.x * kDsRows + wave * (kDsRowTiles * 16);
+  const int c0 = blockIdx.y * kDsCols;
+  const long long plane = (long long)nrows * xpitch;
+  const T* __restrict__ xr = x + (long long)blockIdx.z * 2 * plane;
+  const T* __restrict__ xi = xr + plane;
+  const T* xrow_r[kDsRowTiles];
+  const T* xrow_i[kDsRowTiles];
+#pragma unroll
+  for (int rt = 0; rt < kDsRowTiles; ++rt) {
+    int row = r0 + rt * 16 + col;
+    row = row < nrows ? row : nrows - 1;
+    xrow_r[rt] = xr + (long long)row * xpitch + kq * V;
+    xrow_i[rt] = xi + (long long)row * xpitch + kq * V;
+  }
+  acc_t acc_re[kDsRowTiles][4], acc_im[kDsRowTiles][4];
+  ds_transform_loop<T>(xrow_r, xrow_i, op, op + (long long)xpitch * ndpad, xpitch, ndpad, c0, s_op, acc_re, acc_im);
   double* __restrict__ o = out + (long long)blockIdx.z * nrows * ndelays;
 #pragma unroll
   for (int rt = 0; rt < kDsRowTiles; ++rt) {

@@ -1,4 +1,5 @@
-// report_plan.hpp -- what the post-fit reports cal_solver_delay_spectrum, cal_solver_delay_transfer and cal_solver_fix_degeneracies decide
+// report_plan.hpp -- what the post-fit reports cal_solver_delay_spectrum, cal_solver_delay_cross_spectrum, cal_solver_delay_transfer and
+// cal_solver_fix_degeneracies decide
 // before they launch, on the host alone: the rows of every bin and of every slice, how they are cut into chunks and segments, and the padded images the kernels read.
 // No HIP or RCCL runtime call and no solver: SolverT uploads these plans at every call; cal_debug_report_plan returns them as bytes
 // (tests/test_report_plan_host.py).  dspec_bin_kernel adds a bin's rows, and degen_sum_kernel a slice's segments, in the order written
@@ -8,6 +9,7 @@
 #include "problem_plan.hpp"
 #include "solve_plan.hpp"
 #include "delay_spectrum_kernels.hpp"
+#include "delay_cross_kernels.hpp"
 #include "delay_transfer_kernels.hpp"
 #include "degeneracy_kernels.hpp"
 
@@ -86,6 +88,75 @@ int plan_delay_spectrum(int nbls, int nfreqs, int fpad, const cal_delay_spectrum
   P.n_x = (size_t)P.nq * 2 * crows * P.xpitch;
   P.n_pow = with_power ? (size_t)P.nq * crows * nd : 0;
   P.n_out = (size_t)nbls + (size_t)P.nq * nbins * nd + nbins;
+  return CAL_OK;
+}
+
+// ---- cal_solver_delay_cross_spectrum -----------------------------------------------------------------------------------------------
+template <typename T>
+struct DelayCrossPlan {
+  int nq = 0, nstat = 0;        // quantities and statistics asked for: the bits of `what` and of `stats`
+  int xpitch = 0, ndpad = 0;    // row pitch of the masked planes, columns of the operator image
+  int cpairs = 0, nchunks = 0;  // pairs per chunk (the last may hold fewer)
+  std::vector<int> bin_ent;     // the sorted pair list of every bin, one after the other (plan_bin_lists)
+  std::vector<int> chunk_ptr;   // [nchunks][nbins][2]: a bin's piece of a chunk as positions in bin_ent
+  std::vector<T> image;         // [re, im][xpitch][ndpad]: the operator, zero beyond nfreqs and ndelays
+  std::vector<double> norm_f;   // [xpitch], zero beyond nfreqs
+  std::vector<double> scale;    // [npairs][2]: the description's, or ones
+  size_t n_x = 0, n_pow = 0, n_out = 0;  // elements of ds_x (T), of ds_pow (double) and of ds_out (norm_pair | cross_bin | diff_bin | count_bin)
+};
+
+// A chunk of pairs' scratch -- the masked planes of both sides in T and its nstat statistics in double -- stays under `bound` bytes (never
+// less than one pair); the chunks are cut at multiples of the transform's kDcPairs where that fits.  Everything of the description that
+// can be refused on the host is refused here: npairs, the rows of the pairs, stats, the scales, the bins.
+template <typename T>
+int plan_delay_cross(int nbls, int nfreqs, int fpad, const cal_delay_cross_desc* d, int64_t bound, DelayCrossPlan<T>& P) {
+  const int nd = d->ndelays, nbins = d->nbins, np = d->npairs;
+  if (np < 1) return fail(CAL_ERR_INVALID, "delay_cross_spectrum: npairs = %d (at least 1)", np);
+  if (!d->pairs) return fail(CAL_ERR_INVALID, "delay_cross_spectrum: null pairs");
+  if ((d->stats & 3) == 0 || (d->stats & ~3)) return fail(CAL_ERR_INVALID, "delay_cross_spectrum: stats = %d: bits 0 (cross), 1 (diff), at least one", d->stats);
+  for (int p = 0; p < np; ++p)
+    for (int s = 0; s < 2; ++s) {
+      const int b = d->pairs[2 * (size_t)p + s];
+      if (b < 0 || b >= nbls) return fail(CAL_ERR_INVALID, "delay_cross_spectrum: pairs[%d][%d] = %d lies outside [0, %d)", p, s, b, nbls);
+    }
+  P.scale.assign(2 * (size_t)np, 1.0);
+  if (d->scale) {
+    for (size_t k = 0; k < 2 * (size_t)np; ++k)
+      if (!std::isfinite(d->scale[k])) return fail(CAL_ERR_INVALID, "delay_cross_spectrum: scale[%d][%d] is not finite", (int)(k / 2), (int)(k % 2));
+    std::copy(d->scale, d->scale + 2 * (size_t)np, P.scale.begin());
+  }
+  P.nq = (d->what & 1) + (d->what >> 1 & 1) + (d->what >> 2 & 1);
+  P.nstat = (d->stats & 1) + (d->stats >> 1 & 1);
+  if ((long long)P.nstat * P.nq * nbins * nd + nbins > (1ll << 31) - 1) return fail(CAL_ERR_INVALID, "delay_cross_spectrum: nbins = %d is too many", nbins);
+  for (int p = 0; p < np && nbins; ++p)
+    if (d->bin_of_pair[p] < -1 || d->bin_of_pair[p] >= nbins)
+      return fail(CAL_ERR_INVALID, "delay_cross_spectrum: bin_of_pair[%d] = %d lies outside [-1, %d)", p, d->bin_of_pair[p], nbins);
+  std::vector<int> bin_ptr;
+  CAL_TRY(plan_bin_lists("delay_cross_spectrum", np, nbins, d->bin_of_pair, bin_ptr, P.bin_ent));
+  P.xpitch = ds_xpitch(fpad);
+  P.ndpad = ds_ndpad(nd);
+  const size_t pair_bytes = (size_t)P.nq * 2 * 2 * P.xpitch * sizeof(T) + (size_t)P.nstat * P.nq * nd * sizeof(double);
+  long long cpairs = std::max<long long>(1, bound / (long long)pair_bytes);
+  if (cpairs > kDcPairs) cpairs -= cpairs % kDcPairs;
+  cpairs = std::min<long long>(cpairs, np);
+  P.cpairs = (int)cpairs;
+  P.nchunks = (int)((np + cpairs - 1) / cpairs);
+  P.chunk_ptr.resize((size_t)P.nchunks * nbins * 2);
+  for (int c = 0; c < P.nchunks && nbins; ++c) {
+    const long long p0 = c * cpairs, p1 = std::min<long long>(np, p0 + cpairs);
+    for (int n = 0; n < nbins; ++n) {
+      const int* e0 = P.bin_ent.data() + bin_ptr[n];
+      const int* e1 = P.bin_ent.data() + bin_ptr[n + 1];
+      P.chunk_ptr[((size_t)c * nbins + n) * 2] = (int)(std::lower_bound(e0, e1, (int)p0) - P.bin_ent.data());
+      P.chunk_ptr[((size_t)c * nbins + n) * 2 + 1] = (int)(std::lower_bound(e0, e1, (int)p1) - P.bin_ent.data());
+    }
+  }
+  plan_operator_image<T>(nfreqs, nd, P.xpitch, P.ndpad, d->op_r, d->op_i, P.image);
+  P.norm_f.assign((size_t)P.xpitch, 0.0);
+  std::copy(d->norm_f, d->norm_f + nfreqs, P.norm_f.begin());
+  P.n_x = (size_t)P.nq * 2 * 2 * cpairs * P.xpitch;
+  P.n_pow = (size_t)P.nstat * P.nq * cpairs * nd;
+  P.n_out = (size_t)np + (size_t)P.nstat * P.nq * nbins * nd + nbins;
   return CAL_OK;
 }
 

@@ -433,6 +433,80 @@ class HipFitSolver:
         """Scratch bound of ``delay_spectrum`` in bytes (0: the default); the results do not depend on it (tests)."""
         _lib.check(self._lib.cal_solver_set_delay_spectrum_scratch(self._h, int(nbytes)))
 
+    def delay_cross_spectrum(self, op, norm_f, pairs, scale=None, what=("data", "model", "resid"), stats=("cross", "diff"), calibrated=False,
+                             bin_of_pair=None, nbins=0, per_pair=False, g_r=None, g_i=None):
+        """Delay power that noise does not bias (cal_solver_delay_cross_spectrum), for pairs of rows that see the same sky with
+        independent noise -- two adjacent integrations of one baseline, held as rows of this solver.  ``op``, ``norm_f``, ``what``,
+        ``calibrated``, ``g_r``, ``g_i``: as in ``delay_spectrum``.  ``pairs`` ``[npairs, 2]`` row indices; ``scale`` ``[npairs, 2]``
+        (``None``: ones) puts both sides into common units before they are combined.  For pair ``p = (b0, b1)``, scales ``(a0, a1)``::
+
+            mask_p     = (w[b0] != 0) & (w[b1] != 0)                  the COMMON mask
+            X_q[p][s]  = (mask_p q[b_s]) @ op                          s = 0, 1; products in the solver's dtype, on the matrix cores
+            norm_pair  = sum_f mask_p norm_f
+            Y_s        = a_s X_q[p][s]                                 in float64
+            cross      = Re(Y_0 conj(Y_1)) / norm_pair                 signed; 0 where norm_pair == 0
+            diff       = |Y_0 - Y_1|^2 / (2 norm_pair)                 >= 0
+
+        With independent noise of equal variance on both sides ``cross`` expects the power of the common signal alone and ``diff`` the
+        noise power of one side.  ``stats``: which of ``"cross"``, ``"diff"`` to form.  ``bin_of_pair`` ``[npairs]`` integers in
+        ``[-1, nbins)``: the entry ``out[stat][quantity]`` is then ``[nbins, ndelays]``, the SUM over the bin's pairs with
+        ``norm_pair > 0`` in ascending order, and ``"count_bin"`` their number.  ``per_pair=True`` adds
+        ``"per_pair": {stat: {quantity: [npairs, ndelays]}}``.  ``"norm_pair"`` is always returned.  All float64; sums in a fixed
+        order: two calls give the same bits.  Nothing the fit reads changes.  Under an exchange the binned arrays are summed over the
+        ranks (one all-reduce); the per-pair arrays stay this rank's own."""
+        if (g_r is None) != (g_i is None):
+            raise ValueError("give both g_r and g_i, or neither")
+        what = (what,) if isinstance(what, str) else tuple(what)
+        if not what or any(q not in _lib.DELAY_SPECTRUM_WHAT for q in what) or len(set(what)) != len(what):
+            raise ValueError(f"what must name one or more of {sorted(_lib.DELAY_SPECTRUM_WHAT)} once each, got {what!r}")
+        stats = (stats,) if isinstance(stats, str) else tuple(stats)
+        if not stats or any(k not in _lib.DELAY_CROSS_STATS for k in stats) or len(set(stats)) != len(stats):
+            raise ValueError(f"stats must name one or more of {sorted(_lib.DELAY_CROSS_STATS)} once each, got {stats!r}")
+        names = [q for q in ("data", "model", "resid") if q in what]  # the library's order
+        snames = [k for k in ("cross", "diff") if k in stats]
+        op = np.asarray(op)
+        if op.ndim != 2 or op.shape[0] != self.nfreqs:
+            raise ValueError(f"op must be [nfreqs = {self.nfreqs}, ndelays], got shape {op.shape}")
+        nd = op.shape[1]
+        op_r, op_i = self._real(op.real), self._real(op.imag)
+        norm_f = np.ascontiguousarray(norm_f, dtype=np.float64)
+        if norm_f.shape != (self.nfreqs,):
+            raise ValueError(f"norm_f must be [nfreqs = {self.nfreqs}], got shape {norm_f.shape}")
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32)
+        if pairs.ndim != 2 or pairs.shape[1] != 2 or pairs.shape[0] < 1:
+            raise ValueError(f"pairs must be [npairs >= 1, 2], got shape {pairs.shape}")
+        npairs = pairs.shape[0]
+        if scale is not None:
+            scale = np.ascontiguousarray(scale, dtype=np.float64)
+            if scale.shape != (npairs, 2):
+                raise ValueError(f"scale must be [npairs = {npairs}, 2], got shape {scale.shape}")
+        nbins = int(nbins)
+        if (bin_of_pair is None) != (nbins == 0):
+            raise ValueError("give bin_of_pair and nbins > 0 together, or neither")
+        bins = None
+        if bin_of_pair is not None:
+            bins = np.ascontiguousarray(bin_of_pair, dtype=np.int32)
+            if bins.shape != (npairs,):
+                raise ValueError(f"bin_of_pair must be [npairs = {npairs}], got shape {bins.shape}")
+        gs = (self.nants, self.nfreqs)
+        a = None if g_r is None else self._real(g_r, gs)
+        b = None if g_i is None else self._real(g_i, gs)
+        d = _lib.DelayCrossDesc(nd, sum(_lib.DELAY_SPECTRUM_WHAT[q] for q in names), int(bool(calibrated)), npairs, pairs.ctypes.data,
+                                None if scale is None else scale.ctypes.data, sum(_lib.DELAY_CROSS_STATS[k] for k in snames), nbins,
+                                None if bins is None else bins.ctypes.data, op_r.ctypes.data, op_i.ctypes.data, norm_f.ctypes.data)
+        norm_pair = np.empty(npairs, dtype=np.float64)
+        pp = {k: np.empty((len(names), npairs, nd), dtype=np.float64) if per_pair and k in snames else None for k in ("cross", "diff")}
+        pb = {k: np.empty((len(names), nbins, nd), dtype=np.float64) if nbins and k in snames else None for k in ("cross", "diff")}
+        c_bin = np.empty(nbins, dtype=np.float64) if nbins else None
+        _lib.check(self._lib.cal_solver_delay_cross_spectrum(self._h, C.byref(d), _ptr(a), _ptr(b), _ptr(pp["cross"]), _ptr(pp["diff"]), _ptr(norm_pair),
+                                                             _ptr(pb["cross"]), _ptr(pb["diff"]), _ptr(c_bin)))
+        out = {"norm_pair": norm_pair}
+        if nbins:
+            out.update({k: {q: pb[k][i] for i, q in enumerate(names)} for k in snames}, count_bin=c_bin)
+        if per_pair:
+            out["per_pair"] = {k: {q: pp[k][i] for i, q in enumerate(names)} for k in snames}
+        return out
+
     def delay_transfer(self, op, ridge=1e-6, calibrated=False, bin_of_bl=None, nbins=0, per_baseline=False, g_r=None, g_i=None):
         """The signal loss of the fit in delay space (cal_solver_delay_transfer): the share of the power at every delay that the
         coefficient fit itself removes.  ``op`` ``[nfreqs, ndelays]`` complex: the operator of ``delay_spectrum``.  With

@@ -238,7 +238,13 @@ int cal_debug_solve_plan(int dtype, const cal_problem_desc* d, int64_t scratch_b
  *   count_bin; 41: CsGroup per group with the plan's offsets; 42: order; 43: chunks (int32 g0, g1, w0, w1, r0, r1, q0, q1 -- positions
  *   in 42, in the Gram work, in 45 and in 46 -- then the dynamic LDS as int64); 44: int64 per group, the offset of its W in the third
  *   scratch (S of its runs follows); 45: runs (int64 offset of S, int32 group, b0, b1, 0); 46: rows (int64 offset of S, int32 row,
- *   group); 47: the bins' sorted row lists; 48: [nbins][2] a bin's list as positions in 47. */
+ *   group); 47: the bins' sorted row lists; 48: [nbins][2] a bin's list as positions in 47.
+ * what = 60 .. 65: the plan of cal_solver_delay_cross_spectrum for r->cross (every field is read; the operator in `dtype`) and the bound
+ *   r->scratch_bytes of cal_solver_set_delay_spectrum_scratch (0: the default) --
+ *   60: int64 nwhat, nstat, the row pitch of the masked planes, the columns of the operator image, pairs per chunk, chunks, the elements
+ *   of the chunk's planes (dtype), of its statistics (double) and of norm_pair | cross_bin | diff_bin | count_bin; 61: the bins' sorted
+ *   pair lists, one after the other; 62: [chunks][nbins][2] a bin's piece of a chunk as positions in 61; 63: the operator image
+ *   [re, im][pitch][columns] (dtype); 64: norm_f padded to the pitch (double); 65: the scales [npairs][2] (double; ones for NULL). */
 typedef struct cal_report_plan_desc {
   const struct cal_delay_spectrum_desc* spectrum;
   const struct cal_degeneracy_desc* degeneracy;
@@ -246,6 +252,7 @@ typedef struct cal_report_plan_desc {
   int32_t with_power_bl;
   int32_t nslices;
   const struct cal_delay_transfer_desc* transfer; /* what = 40 .. 48 only */
+  const struct cal_delay_cross_desc* cross;       /* what = 60 .. 65 only */
 } cal_report_plan_desc;
 int cal_debug_report_plan(int dtype, const cal_problem_desc* d, const cal_report_plan_desc* r, int what, void* out, int64_t cap_bytes, int64_t* bytes);
 /* Host only, like cal_debug_plan: the shape of one pass or train step (csrc/step_plan.hpp) -- which kernels follow the fused or dense pass,
@@ -391,8 +398,8 @@ int cal_solver_fit_quality(cal_solver* s, const void* g_r, const void* g_i, doub
                            double* wsum_bl);
 /* Downweight outliers from the residual (no counterpart in the reference, which minimises a plain weighted chi-square): one round of
  * iteratively reweighted least squares.  The call rewrites the ONE weight plane that every kernel path, cal_solver_fit_quality, the
- * closed-form solves and the five post-fit reports (cal_solver_fit_errors, cal_solver_gain_basis_errors, cal_solver_delay_spectrum,
- * cal_solver_delay_transfer, and cal_solver_fix_degeneracies where its ref_w is NULL: given reference weights replace the plane, which
+ * closed-form solves and the six post-fit reports (cal_solver_fit_errors, cal_solver_gain_basis_errors, cal_solver_delay_spectrum,
+ * cal_solver_delay_cross_spectrum, cal_solver_delay_transfer, and cal_solver_fix_degeneracies where its ref_w is NULL: given reference weights replace the plane, which
  * is then not read) read, in place: no fit kernel changes and no recorded step graph goes stale.  With w0 the weights as
  * cal_solver_set_data gave them, (i, j) the antennas of baseline row b, m = A c at the solver's coefficients, g the solver's gains:
  *   e[b][f]  = w0[b][f] |d[b][f] - g_i[f] conj(g_j[f]) m[b][f]|^2     (products in the solver's dtype, in cal_solver_fit_quality's order)
@@ -724,8 +731,64 @@ typedef struct cal_delay_spectrum_desc {
 int cal_solver_delay_spectrum(cal_solver* s, const cal_delay_spectrum_desc* desc, const void* g_r, const void* g_i, double* power_bl,
                               double* norm_bl, double* power_bin, double* count_bin);
 /* The scratch bound of cal_solver_delay_spectrum in bytes (0: the default, 256 MiB; negative: CAL_ERR_INVALID).  The outputs do not
- * depend on it: tests use it to send a small problem through several chunks. */
+ * depend on it: tests use it to send a small problem through several chunks.  cal_solver_delay_cross_spectrum shares it. */
 int cal_solver_set_delay_spectrum_scratch(cal_solver* s, int64_t bytes);
+/* Delay power that noise does not bias: the cross power of two rows that see the same sky with independent noise -- two adjacent
+ * integrations of one baseline, as rows of one solver (nslices > 1, bl_alias, the joint time-basis layout) -- and the power of their
+ * half difference, the noise spectrum measured from the data.  cal_solver_delay_spectrum's |X|^2 of a residual is signal plus the
+ * full noise power; here the sky, slow in time, survives the product and the noise averages to zero.  Notation of
+ * cal_solver_delay_spectrum: row b, G, m, w and the quantities q = data, model, residual (calibrated or not), formed in the solver's
+ * dtype exactly as there.  For pair p = (b0, b1) = pairs[p] with scales (a0, a1) = scale[p]:
+ *   mask_p[f]      = (w[b0][f] != 0) && (w[b1][f] != 0)            the COMMON mask: two rows flagged differently leak foregrounds
+ *                                                                  differently, and the leakage would not cancel
+ *   x_q[p][s][f]   = mask_p q[b_s][f]                              s = 0, 1
+ *   X_q[p][s][k]   = sum_f x_q[p][s][f] (op_r + i op_i)[f][k]
+ *   norm_pair[p]   = sum_f mask_p norm_f[f]                                                         [npairs]
+ *   Y_s            = a_s X_q[p][s][k]                              in double, after the matrix product
+ *   cross[q][p][k] = (Re Y_0 Re Y_1 + Im Y_0 Im Y_1) / norm_pair[p]     0 where norm_pair[p] == 0   [nwhat][npairs][ndelays], signed
+ *   diff[q][p][k]  = ((Re Y_0 - Re Y_1)^2 + (Im Y_0 - Im Y_1)^2) / (2 norm_pair[p])                 [nwhat][npairs][ndelays], >= 0
+ *   cross_bin / diff_bin [q][n][k] = the sum over the pairs p with bin_of_pair[p] == n and norm_pair[p] > 0, in ascending p
+ *                                                                                                   [nwhat][nbins][ndelays]
+ *   count_bin[n]   = their number                                                                   [nbins]
+ * The scales put both sides into common units before they are combined (a caller that divides every slice by its own rms passes the
+ * rms values); NULL: ones.  A pair may join any two rows, (b, b) included: with unit scales its diff is exactly 0 and its cross is
+ * cal_solver_delay_spectrum's power_bl[b] to the bit.  With independent noise of equal variance on both sides the expectation of cross
+ * is that of the common signal alone and the expectation of diff is the noise power of one side.
+ * The products run on the matrix cores in the solver's dtype, by the loop of cal_solver_delay_spectrum; scaling, products, the division
+ * and every sum over pairs are taken in double in a fixed order, no float atomics: two calls give the same bits, and so do two
+ * chunkings.  All outputs are doubles; any output pointer may be NULL.
+ *   g_r, g_i: as in cal_solver_delay_spectrum -- NULL: the solver's current full gains; given gains are used for this call only.
+ * Errors, before any launch: those of cal_solver_delay_spectrum (CAL_ERR_STATE when problem, data or coefficients are not set, or the
+ * gains neither set nor given; CAL_ERR_INVALID for a null description, a bad `what`, ndelays, `calibrated`, nbins, bin_of_pair, a
+ * null operator or norm_f); CAL_ERR_INVALID for npairs < 1, null pairs, a row index outside [0, nbls), a `stats` without a bit of
+ * 1 | 2 (or with others), a scale that is not finite, cross_pair / cross_bin without bit 0 or diff_pair / diff_bin without bit 1,
+ * binned outputs with nbins == 0.
+ * Works for every layout and kernel path, fitting groups of several baselines, bl_alias, nslices > 1 and the joint time-basis layout.
+ * A post-fit pass: it runs the model pass of cal_solver_model and puts the loop state back; a run continued after the call is
+ * bit-identical to one without it.
+ * The pairs are worked through in chunks whose scratch -- the masked planes of both sides in the solver's dtype and the chunk's
+ * statistics in double -- stays under the bound of cal_solver_set_delay_spectrum_scratch (never less than one pair; cut at multiples
+ * of 64 pairs where that fits); the device buffers of cal_solver_delay_spectrum are reused.  The result does not depend on the chunks
+ * by a bit.
+ * Under a communicator or exchange hook cross_bin | diff_bin | count_bin (those of the bits set) are summed over the ranks in ONE
+ * all-reduce of nstat nwhat nbins ndelays + nbins doubles (CAL_XCHG_F64, CAL_XCHG_SUM), whichever outputs are asked for (nbins == 0:
+ * none); the per-pair outputs stay the rank's own. */
+typedef struct cal_delay_cross_desc {
+  int32_t ndelays;            /* columns of the operator, 1 <= ndelays <= 4096 */
+  int32_t what;               /* bit 0: data, bit 1: model, bit 2: residual; at least one */
+  int32_t calibrated;         /* as in cal_delay_spectrum_desc */
+  int32_t npairs;             /* >= 1 */
+  const int32_t* pairs;       /* [npairs][2]: any two rows of the solver, each in [0, nbls) */
+  const double* scale;        /* [npairs][2], finite; NULL: ones */
+  int32_t stats;              /* bit 0: cross, bit 1: diff; at least one */
+  int32_t nbins;              /* 0: no binned output */
+  const int32_t* bin_of_pair; /* [npairs] in [-1, nbins): -1 leaves the pair out; NULL iff nbins == 0 */
+  const void* op_r;           /* [nfreqs][ndelays], solver dtype: the transform along frequency, taper folded in */
+  const void* op_i;
+  const double* norm_f;       /* [nfreqs]: what a channel unflagged on both sides adds to the pair's normalisation */
+} cal_delay_cross_desc;
+int cal_solver_delay_cross_spectrum(cal_solver* s, const cal_delay_cross_desc* desc, const void* g_r, const void* g_i, double* cross_pair,
+                                    double* diff_pair, double* norm_pair, double* cross_bin, double* diff_bin, double* count_bin);
 /* The signal loss of the fit in delay space: the share of the power at every delay that the coefficient fit itself removes.  The
  * foreground basis absorbs every component of the data in its span -- noise and cosmological signal as well as foregrounds -- so a
  * residual delay spectrum (cal_solver_delay_spectrum) is biased low near the edge of the basis; this is the factor that undoes it.

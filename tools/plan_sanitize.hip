@@ -1,7 +1,7 @@
 // plan_sanitize.hip -- the set-up planner (calamity_amd/csrc/problem_plan.hpp), the planner of the closed-form calls
 // (calamity_amd/csrc/solve_plan.hpp), of the post-fit reports (calamity_amd/csrc/report_plan.hpp), the step's shape (calamity_amd/csrc/step_plan.hpp) and the two-loop recursion of L-BFGS on
 // coefficients (calamity_amd/csrc/lbfgs_core.hpp) under the host sanitizers, with no device and no interpreter: four problems built in code (folded STREAM, heads of baselines that share tiles, forced dense, multi-baseline runs),
-// planned for fp32 and fp64; the closed-form plans and the delay-spectrum plan at the default scratch bound and at a bound of 1 byte, the degeneracy plan in both modes,
+// planned for fp32 and fp64; the closed-form plans, the delay-spectrum plan and the cross-spectrum plan (with its refusals) at the default scratch bound and at a bound of 1 byte, the degeneracy plan in both modes,
 // the caller's arrays of exactly the sizes the planners may read; plan_step over its whole input
 // table; lbfgs_two_loop on Gram matrices of 0 .. 16 pairs held in arrays of exactly the sizes it may touch.  Exits non-zero on a planner error or an inconsistent plan; the sanitizers abort on a finding.
 //
@@ -13,6 +13,7 @@
 #include "../calamity_amd/csrc/lbfgs_core.hpp"
 
 #include <cstdint>
+#include <limits>
 
 namespace {
 
@@ -109,6 +110,32 @@ int run(const Case& c) {
     int rows = 0;
     for (size_t k = 0; k < P.chunk_ptr.size(); k += 2) rows += P.chunk_ptr[k + 1] - P.chunk_ptr[k];
     rbad += rows != (int)P.bin_ent.size() || P.bin_ent.size() != (size_t)(p.nbls - (p.nbls + 3) / 7);
+  }
+  // the cross spectrum's plan: a pair per row (row b with row (b + 5) % nbls), scales and bins of exactly npairs entries; then its refusals
+  {
+    const int np = p.nbls;
+    std::vector<int32_t> pairs(2 * (size_t)np), bin_of_pair(np);
+    std::vector<double> scale(2 * (size_t)np, 1.5);
+    for (int k = 0; k < np; ++k) pairs[2 * k] = k, pairs[2 * k + 1] = (k + 5) % np, bin_of_pair[k] = k % 7 == 3 ? -1 : k % (nbins - 1);
+    cal_delay_cross_desc cd{nd, 7, 0, np, pairs.data(), scale.data(), 3, nbins, bin_of_pair.data(), op_r.data(), op_i.data(), norm_f.data()};
+    for (const int64_t bound : {kCsScratchDefault, (int64_t)1}) {
+      DelayCrossPlan<T> P;
+      rbad += plan_delay_cross(p.nbls, p.nfreqs, p.fpad, &cd, bound, P) != CAL_OK || P.nchunks != (bound == 1 ? np : 1) || P.scale.size() != 2 * (size_t)np;
+      int n = 0;
+      for (size_t k = 0; k < P.chunk_ptr.size(); k += 2) n += P.chunk_ptr[k + 1] - P.chunk_ptr[k];
+      rbad += n != (int)P.bin_ent.size() || P.bin_ent.size() != (size_t)(np - (np + 3) / 7) || P.n_x != (size_t)3 * 4 * P.cpairs * P.xpitch;
+    }
+    DelayCrossPlan<T> R;
+    pairs[2 * (size_t)np - 1] = p.nbls;  // a row past the last
+    rbad += plan_delay_cross(p.nbls, p.nfreqs, p.fpad, &cd, kCsScratchDefault, R) != CAL_ERR_INVALID;
+    pairs[2 * (size_t)np - 1] = 0;
+    scale[1] = std::numeric_limits<double>::infinity();
+    rbad += plan_delay_cross(p.nbls, p.nfreqs, p.fpad, &cd, kCsScratchDefault, R) != CAL_ERR_INVALID;
+    cd.scale = nullptr;  // no scales: ones
+    cd.stats = 4;
+    rbad += plan_delay_cross(p.nbls, p.nfreqs, p.fpad, &cd, kCsScratchDefault, R) != CAL_ERR_INVALID;
+    cd.stats = 2;
+    rbad += plan_delay_cross(p.nbls, p.nfreqs, p.fpad, &cd, kCsScratchDefault, R) != CAL_OK || R.nstat != 1 || R.scale[1] != 1.0;
   }
   for (const bool band : {false, true}) {
     DegeneracyPlan P;
