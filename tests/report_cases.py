@@ -1,5 +1,5 @@
-"""The table of cases behind tests/test_gpu_report_paths.py and tests/test_gpu_robust_reports.py: the five post-fit reports
-(``fit_errors``, ``gain_basis_errors``, ``delay_spectrum``, ``delay_transfer``, ``fix_degeneracies``) on the smallest shapes that
+"""The table of cases behind tests/test_gpu_report_paths.py and tests/test_gpu_robust_reports.py: the six post-fit reports
+(``fit_errors``, ``gain_basis_errors``, ``delay_spectrum``, ``delay_cross_spectrum``, ``delay_transfer``, ``fix_degeneracies``) on the smallest shapes that
 qualify for the dense kernel paths (SHARED layout, one baseline per fitting group, more than 64 channels).  No GPU here: the inputs
 of every case, the one call per case on a solver it is handed, the restatement of that call (the one of the report's own test file,
 on the problem's weights or on others) and its ``check`` (the one of the report's own test file).  tests/test_report_paths_host.py
@@ -7,7 +7,11 @@ holds the table to its preconditions without a device.
 
 The ``fix_degeneracies`` problem is ``base_problem(7)`` of tests/test_gpu_degeneracy.py at 72 channels; its reference is ``inject`` on
 the fp64 NumPy model of the start parameters (an input like any other: the restatement is evaluated on the device's own model rows,
-as in that file), modes ``channel`` and ``band``, 6 iterations, with ``gref``; ``_own_w``: ``ref_w=None``, the solver's weights."""
+as in that file), modes ``channel`` and ``band``, 6 iterations, with ``gref``; ``_own_w``: ``ref_w=None``, the solver's weights.
+
+The ``delay_cross`` cases are the spectrum's problem and operator with the pairs of ``single_slice_case`` of tests/test_gpu_delay_cross.py
+(any two rows of ONE slice make a pair: (b, (b + 3) % nb) for every row, (2, 2) with unit scales, (nb - 1, 0), unequal scales elsewhere),
+four bins, both statistics of all three quantities per pair; ``reference``, ``check`` and the bound are that file's."""
 import copy
 import functools
 
@@ -17,6 +21,7 @@ import degeneracy_ref as R
 import delay_spectrum_ref as DSR
 import robust_ref
 import test_gpu_degeneracy as DG
+import test_gpu_delay_cross as DC
 import test_gpu_delay_spectrum as DS
 import test_gpu_delay_transfer as DT
 import test_gpu_fit_errors as FE
@@ -33,7 +38,7 @@ DEGEN_NF = 72
 TIME_SHAPE = (4, 5, 72)
 CASES = [("fit_errors", "7x200"), ("fit_errors", "12x129"), ("gain_basis_errors", "freq_K12"), ("gain_basis_errors", "freq_K65"),
          ("gain_basis_errors", "time_freq"), ("gain_basis_errors", "time"), ("delay_spectrum", "raw"), ("delay_spectrum", "calibrated"),
-         ("delay_transfer", "raw"), ("delay_transfer", "calibrated"), ("fix_degeneracies", "channel"), ("fix_degeneracies", "band"),
+         ("delay_cross", "raw"), ("delay_cross", "calibrated"), ("delay_transfer", "raw"), ("delay_transfer", "calibrated"), ("fix_degeneracies", "channel"), ("fix_degeneracies", "band"),
          ("fix_degeneracies", "channel_own_w"), ("fix_degeneracies", "band_own_w")]
 # the cases whose call reads the solver's weight plane (fix_degeneracies with ref_w given must not)
 WEIGHT_READERS = [c for c in CASES if c[0] != "fix_degeneracies" or c[1].endswith("_own_w")]
@@ -54,7 +59,7 @@ def inputs(kind, variant):
             return freq_case((7, 200)) + (rand_basis(200, int(variant[len("freq_K"):]), 2), None)
         Bt, B = bases_of(TIME_SHAPE, ("rand",), (3, 10 if variant == "time_freq" else None))
         return flagged_case(*TIME_SHAPE) + (B, Bt)
-    if kind in ("delay_spectrum", "delay_transfer"):
+    if kind in ("delay_spectrum", "delay_cross", "delay_transfer"):
         return DS.problem(7, 200) + (None, None)
     return DG.base_problem(7, nfreqs=DEGEN_NF)[:2] + (None, None)
 
@@ -78,6 +83,11 @@ def delay_operator(kind, variant):
     return DS.operator(200, 200)
 
 
+def cross_pairs(kind="delay_cross", variant="raw"):
+    """(pairs, scale, bins, nbins) of the ``delay_cross`` cases."""
+    return DC.single_slice_pairs(inputs(kind, variant)[0].nbls)
+
+
 def call(s, kind, variant):
     """The one call of the case on the solver ``s``: what it returns (``fix_degeneracies``: with the solver's model rows beside it)."""
     p = inputs(kind, variant)[0]
@@ -88,6 +98,10 @@ def call(s, kind, variant):
     if kind == "delay_spectrum":
         op, norm_f = delay_operator(kind, variant)
         return DS.call(s, p, op, norm_f, calibrated=variant == "calibrated")
+    if kind == "delay_cross":
+        op, norm_f = delay_operator(kind, variant)
+        pairs, scale, bins, nbins = cross_pairs(kind, variant)
+        return s.delay_cross_spectrum(op, norm_f, pairs, scale=scale, calibrated=variant == "calibrated", bin_of_pair=bins, nbins=nbins, per_pair=True)
     if kind == "delay_transfer":
         return DT.call(s, p, delay_operator(kind, variant)[0], ridge=RIDGE, calibrated=variant == "calibrated")
     ref_r, ref_i, antpos, kw, _ = degeneracy_args(variant)
@@ -97,11 +111,12 @@ def call(s, kind, variant):
 
 
 def flat(out):
-    """Nested dicts of arrays (``per_baseline`` of ``delay_spectrum``) as keys of their own, for a bit-for-bit comparison."""
+    """Nested dicts of arrays (``per_baseline`` of ``delay_spectrum``; ``per_pair[stat][quantity]`` of ``delay_cross_spectrum``, two levels)
+    as keys of their own, for a bit-for-bit comparison."""
     res = {}
     for k, v in out.items():
         if isinstance(v, dict):
-            res.update({f"{k}_{kk}": vv for kk, vv in v.items()})
+            res.update({f"{k}_{kk}": vv for kk, vv in flat(v).items()})
         else:
             res[k] = v
     return res
@@ -131,6 +146,10 @@ def restatement(kind, variant, dtype, p=None, model=None):
     if kind == "delay_spectrum":
         op, norm_f = delay_operator(kind, variant)
         return DS.reference(p, params, dtype, op, norm_f, variant == "calibrated")
+    if kind == "delay_cross":
+        op, norm_f = delay_operator(kind, variant)
+        pairs, scale, bins, nbins = cross_pairs(kind, variant)
+        return DC.reference(p, p, [params], dtype, op, norm_f, pairs, scale, variant == "calibrated", bins, nbins)
     if kind == "delay_transfer":
         return DT.reference(p, params, dtype, delay_operator(kind, variant)[0], ridge=RIDGE, calibrated=variant == "calibrated")
     ref_r, ref_i, antpos, kw, _ = degeneracy_args(variant)
@@ -163,6 +182,9 @@ def check(kind, variant, out, ref, dtype, label):
         return GBE.check(out, ref, dtype, label)
     if kind == "delay_spectrum":
         return DS.check(out, ref, p, dtype, label)
+    if kind == "delay_cross":
+        bins, nbins = cross_pairs(kind, variant)[2:]
+        return DC.check(out, ref, dtype, label, bins=bins, nbins=nbins)
     if kind == "delay_transfer":
         assert max(ref["conds"]) <= COND_MAX, label
         return DT.check(out, ref, p, dtype, label)
@@ -171,7 +193,8 @@ def check(kind, variant, out, ref, dtype, label):
 
 # ---- what the weights-matter precondition of the robust tests compares (planes of the restatement; the integers apart)
 MATTER_PLANES = {"fit_errors": ("coeff_var", "model_var", "leverage_bl", "gain_var"), "gain_basis_errors": ("gain_var", "y_var", "gain_dof"),
-                 "delay_spectrum": ("data", "model", "resid", "norm_bl"), "delay_transfer": ("absorbed_bl", "noise_bl"),
+                 "delay_spectrum": ("data", "model", "resid", "norm_bl"),
+                 "delay_cross": tuple(f"{st}_{k}" for st in DC.STATS for k in DSR.NAMES) + ("norm_pair",), "delay_transfer": ("absorbed_bl", "noise_bl"),
                  "fix_degeneracies": ("eta", "tilt", "psi", "g", "model")}
 # Outputs whose restatement does NOT move by 100 x TOL in fp32 under clip at k = 2 (it does in fp64, where TOL is 1e-10): a reader of w0
 # could pass their comparison with the restatement, so in fp32 they are held to solver B alone (bit for bit).  Two are identities that
@@ -194,6 +217,8 @@ def below_margin(case, dtype):
 def matter_planes(kind, ref):
     if kind == "delay_spectrum":
         return dict({k: ref["per_baseline"][k] for k in DSR.NAMES}, norm_bl=ref["norm_bl"])
+    if kind == "delay_cross":
+        return dict({f"{st}_{k}": ref["per_pair"][st][k] for st in DC.STATS for k in DSR.NAMES}, norm_pair=ref["norm_pair"])
     return {k: np.asarray(ref[k]) for k in MATTER_PLANES[kind]}
 
 

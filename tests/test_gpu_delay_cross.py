@@ -7,6 +7,7 @@ Every pair list holds: the same-baseline pairs of adjacent slices, a pair of dif
 pairs, a pair with one side wholly flagged, a pair whose masks are disjoint, and unequal scales.
 
 The bound is derived, not tuned (delay_cross_ref.py).  Every case prints its largest ratio of error to bound."""
+import copy
 import functools
 
 import numpy as np
@@ -180,13 +181,19 @@ def test_a_full_block_of_64_pairs_and_a_ragged_one(dtype):
     s.close()
 
 
-def single_slice_case(p, params, dtype, op, norm_f, label, layout="shared", path="auto"):
-    """Pairs among the rows of ONE slice (a pair is any two rows): what the kernel path and the groups can change is the model pass."""
-    nb = p.nbls
+def single_slice_pairs(nb):
+    """(pairs, scale, bins, nbins) among the rows of ONE slice: (b, (b + 3) % nb) for every row, (2, 2) with unit scales at position
+    nb, (nb - 1, 0); seeded unequal scales elsewhere."""
     pairs = np.array([(b, (b + 3) % nb) for b in range(nb)] + [(2, 2), (nb - 1, 0)], dtype=np.int32)
     scale = np.random.default_rng(8).uniform(0.5, 2.0, size=(len(pairs), 2))
     scale[nb] = 1.0
-    bins, nbins = bins_of_pairs(len(pairs))
+    return (pairs, scale) + bins_of_pairs(len(pairs))
+
+
+def single_slice_case(p, params, dtype, op, norm_f, label, layout="shared", path="auto"):
+    """Pairs among the rows of ONE slice (a pair is any two rows): what the kernel path and the groups can change is the model pass."""
+    nb = p.nbls
+    pairs, scale, bins, nbins = single_slice_pairs(nb)
     s = DS.solver_of(p, params, dtype, layout, path)
     if path != "auto":
         assert s.timing_get()["kernel_path"] == path
@@ -244,6 +251,61 @@ def test_row_walk_shapes(nfreqs, dtype):
             np.testing.assert_array_equal(out["per_pair"]["cross"][k][nb], spec["per_baseline"][k][2])
             np.testing.assert_array_equal(out["per_pair"]["diff"][k][nb + 1], out["per_pair"]["diff"][k][nb + 2])
     s.close()
+
+
+# ---- two kernels, one identity
+SHARED_FLAGS = (0, 1, 2, 3, 5, 20)  # rows of slice 1 given the flags of the same rows of slice 0 (row 1: all flagged; row 3: the even channels)
+# 2 diff = P[b0] + P[b1] - 2 cross is exact in the reals when both sides of a pair carry one mask and unit scales: dspec_rows_kernel and
+# dcross_rows_kernel then form the same planes, ds_transform_loop the same accumulators (re_s, im_s), and both epilogues work on them in
+# double without contraction.  Roundings of double, counted in the two epilogues (the unit scales multiply exactly):
+#   P[b]  = (re re + im im) / n                   2 products, 1 sum, 1 division: 4, all on non-negative terms: 4 u P
+#   cross = (re0 re1 + im0 im1) / n               2 products (u (|re0 re1| + |im0 im1|) / n <= u (P[b0] + P[b1]) / 2), 1 sum, 1 division: 4
+#   diff  = ((re0 - re1)^2 + (im0 - im1)^2) / 2n  2 differences (each counts twice under the square), 2 squares, 1 sum, 1 division: 6 operations, 5 u diff
+#   the test's own P[b0] + P[b1] - 2 cross         1 sum, 1 difference: 2
+# No quantity takes more than 8, so the identity is held to 16 u (P[b0] + P[b1] + 2 |cross| + 2 diff) per element, u = 2^-53: eight
+# roundings for each quantity as it enters the identity (P once, cross and diff doubled).
+IDENTITY_ROUNDINGS = 8
+
+
+@functools.lru_cache(maxsize=None)
+def shared_flag_batch():
+    """``batch(7, 61, 2)`` with the rows ``SHARED_FLAGS`` of slice 1 flagged exactly as the same rows of slice 0."""
+    full, p0, pars = batch(7, 61, 2)
+    nb = p0.nbls
+    twin = copy.copy(full)
+    w = np.array(full.wgts, dtype=np.float64)
+    for b in SHARED_FLAGS:
+        w[nb + b] = np.where(w[b] != 0, w.max(), 0.0)
+    twin.wgts = w
+    return twin, p0, pars
+
+
+@pytest.mark.parametrize("calibrated", [False, True], ids=["raw", "calibrated"])
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_cross_and_diff_of_equally_flagged_rows_add_up_to_the_spectrum_s_powers(dtype, calibrated):
+    full, p0, pars = shared_flag_batch()
+    nb = p0.nbls
+    op, norm_f = operator(61, 37)
+    pairs = np.array([(b, nb + b) for b in SHARED_FLAGS], dtype=np.int32)
+    assert np.array_equal(full.wgts[pairs[:, 0]] != 0, full.wgts[pairs[:, 1]] != 0)
+    assert np.any(full.wgts[pairs[:, 0]] != full.wgts[pairs[:, 1]])  # (the same flags, not the same weights)
+    s = solver_of(full, joined(pars), dtype)
+    out = s.delay_cross_spectrum(op, norm_f, pairs, calibrated=calibrated, per_pair=True)
+    spec = s.delay_spectrum(op, norm_f, per_baseline=True, calibrated=calibrated)
+    s.close()
+    for side in (0, 1):
+        np.testing.assert_array_equal(out["norm_pair"], spec["norm_bl"][pairs[:, side]])
+    assert out["norm_pair"][1] == 0 and np.all(np.delete(out["norm_pair"], 1) > 0)
+    worst = {}
+    for k in NAMES:
+        P0, P1 = (spec["per_baseline"][k][pairs[:, side]] for side in (0, 1))
+        cross, diff = out["per_pair"]["cross"][k], out["per_pair"]["diff"][k]
+        bound = 2 * IDENTITY_ROUNDINGS * 2.0 ** -53 * (P0 + P1 + 2.0 * np.abs(cross) + 2.0 * diff)
+        err = np.abs(2.0 * diff - (P0 + P1 - 2.0 * cross))
+        worst[k] = float(np.max(np.divide(err, bound, out=np.zeros_like(err), where=err > 0)))
+        assert np.all(diff[[0, 2, 3, 4, 5]].max(axis=1) > 0) and not np.any(diff[1]) and not np.any(P0[1])  # two times differ: the identity says something
+    print(f"identity {np.dtype(dtype).name} calibrated={calibrated}: error / bound  " + "  ".join(f"{k} {v:.3f}" for k, v in worst.items()))
+    assert max(worst.values()) <= 1.0, worst
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])

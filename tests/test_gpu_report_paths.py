@@ -1,5 +1,5 @@
-"""The five post-fit reports -- ``fit_errors``, ``gain_basis_errors``, ``delay_spectrum``, ``delay_transfer``, ``fix_degeneracies`` -- on
-the solver configurations production calls them in (``slice_pipeline`` runs them one after another at the end of every slice): the
+"""The six post-fit reports -- ``fit_errors``, ``gain_basis_errors``, ``delay_spectrum``, ``delay_cross_spectrum``, ``delay_transfer``,
+``fix_degeneracies`` -- on the solver configurations production calls them in (``slice_pipeline`` runs them one after another at the end of every slice): the
 dense matrix-core kernel paths, the "sum" regulariser set, a descent continued through them at graph length, several slices.
 
 The argument is the one of tests/test_gpu_solve_paths.py: every report goes through ``model_pass``, which launches
@@ -27,6 +27,18 @@ Shown once on scratch copies of the library (each inside its buffers: wrong numb
     ``test_every_report_gives_the_bits_of_the_general_path`` and the 4 dense ``fix_degeneracies`` cases of
     tests/test_gpu_robust_reports.py against the restatement (solvers A and B there are wrong alike).
 
+The same for the sixth report, ``delay_cross_spectrum``, each shown once and each passing tests/test_gpu_delay_cross.py,
+test_gpu_delay_cross_dropin.py and test_gpu_delay_cross_ranks.py as they stood before the report joined this file (60 tests):
+
+  * the cross call's ``model_pass`` on a dense path overwrites the loop state as ``set_optimizer`` does and nothing puts it back: fails
+    the same 48 + 8 dense cases of the two descent tests, through ``all_reports``; every ``general`` case passes.  With the restore
+    ALONE dropped for this call on the dense paths nothing fails, here or anywhere, and nothing can, for the reason above:
+    ``begin_pass_state`` changes only ``done`` / ``done_after`` of the mirror, and every entry that reads them writes them first;
+  * the two builds that read ``rw_w0`` in ``dcross_rows_kernel`` fail no test of this file (it never reweights), and the one that skips
+    the upload of ``ds_ptr`` / ``ds_ent`` behind a spectrum call none either (``all_reports`` gives both calls the same three bins over
+    the same rows, and ``slice_reports`` likewise: the stale lists are the right ones): see tests/test_gpu_robust_reports.py and
+    tests/test_gpu_report_order.py.
+
 Both pass tests/test_gpu_fit_errors.py, test_gpu_gain_basis_errors.py, test_gpu_delay_spectrum.py, test_gpu_delay_transfer.py,
 test_gpu_degeneracy.py, test_gpu_robust_consumers.py and test_gpu_solve_paths.py (742 tests), which run the reports on the default
 path.  The six builds that read ``w0`` behind a reweight fail no test of this file (it never reweights): see
@@ -40,6 +52,7 @@ import pytest
 import degeneracy_ref as R
 import report_cases as C
 import test_gpu_degeneracy as DG
+import test_gpu_delay_cross as DC
 import test_gpu_delay_spectrum as DS
 from test_gpu_fit_quality import TOL, plane_err
 from test_gpu_solve_paths import (DENSE, DTYPES, NSTEPS, PATHS, PRIORS, REG_IDS, REG_PATHS, REGS, assert_path, assert_same_bits, assert_same_state,
@@ -158,6 +171,9 @@ def all_reports(s, kind):
     if basis:
         out.append(s.gain_basis_errors())
     out.append(s.delay_spectrum(op, norm_f, bin_of_bl=bins, nbins=3))
+    pairs = np.stack([np.arange(p.nbls), (np.arange(p.nbls) + 1) % p.nbls], axis=1).astype(np.int32)
+    cross = s.delay_cross_spectrum(op, norm_f, pairs, bin_of_pair=bins, nbins=3)
+    assert cross["diff"]["resid"].sum() > 0
     out.append(s.delay_transfer(op, bin_of_bl=bins, nbins=3))
     na = p.nants // (Bt.shape[0] if Bt is not None else 1)
     gref = s.get_params()[:2]
@@ -239,17 +255,24 @@ def test_a_fresh_solver_resumed_behind_the_reports_continues_identically(dtype, 
 
 # ---- (d) several slices on the dense path
 def slice_reports(s, nb, nslices):
+    """The reports of every slice; the cross spectrum with the within-slice pairs (t nb + b, t nb + (b + 3) % nb), pair t nb + b in row
+    t nb + b's bin, the same seeded unequal scales in every slice: what a solver of ONE slice can restate."""
     op, norm_f = DS.operator(200, 200)
     bins = (np.repeat(np.arange(nslices), nb) * 2 + np.tile(np.arange(nb) % 2, nslices)).astype(np.int32)
+    pairs = np.array([(t * nb + b, t * nb + (b + 3) % nb) for t in range(nslices) for b in range(nb)], dtype=np.int32)
+    scale = np.tile(np.random.default_rng(9).uniform(0.5, 2.0, size=(nb, 2)), (nslices, 1))
     return dict(fit_errors=s.fit_errors(), delay_spectrum=C.flat(s.delay_spectrum(op, norm_f, bin_of_bl=bins, nbins=2 * nslices, per_baseline=True)),
+                delay_cross=C.flat(s.delay_cross_spectrum(op, norm_f, pairs, scale=scale, bin_of_pair=bins, nbins=2 * nslices, per_pair=True)),
                 delay_transfer=s.delay_transfer(op, bin_of_bl=bins, nbins=2 * nslices, per_baseline=True))
 
 
 def rows_of_slice(name, key, arr, t, p0):
-    """Slice ``t`` of one output of a solver of several slices (the bins encode (slice, bin) with two bins a slice)."""
+    """Slice ``t`` of one output of a solver of several slices (the bins encode (slice, bin) with two bins a slice; of the cross
+    spectrum ``cross_<quantity>`` and ``diff_<quantity>`` are bins, ``per_pair_...`` and ``norm_pair`` one pair a row)."""
     if np.isscalar(arr):
         return None
-    n = {"coeff_var": p0.ncoeffs, "gain_var": p0.nants}.get(key, 2 if key in ("data", "model", "resid", "count_bin", "absorbed_bin") else p0.nbls)
+    binned = key in ("data", "model", "resid", "count_bin", "absorbed_bin") or (name == "delay_cross" and key.startswith(("cross_", "diff_")))
+    n = {"coeff_var": p0.ncoeffs, "gain_var": p0.nants}.get(key, 2 if binned else p0.nbls)
     return arr[t * n : (t + 1) * n]
 
 
@@ -287,3 +310,67 @@ def test_three_slices_on_the_dense_path_equal_three_single_slice_solvers(dtype):
                 else:
                     assert rows.shape == alone[name][key].shape, (name, key)
                     np.testing.assert_array_equal(rows, alone[name][key], err_msg=f"slice {t} {np.dtype(dtype).name}: {name} {key}")
+
+
+# ---- the pairs production asks for: the same baseline in adjacent slices (no solver of one slice can restate them)
+def cross_slice_problem():
+    """``three_slices()`` as the cross spectrum's reference takes it: (problem with data and weights, p0, per-slice parameters)."""
+    p0, sub, data, start = three_slices()
+    full = copy.copy(sub)
+    full.data_r, full.data_i, full.wgts = data
+    sizes = dict(g_r=p0.nants, g_i=p0.nants, c_r=p0.ncoeffs, c_i=p0.ncoeffs)
+    pars = [{k: start[k][t * n : (t + 1) * n] for k, n in sizes.items()} for t in range(3)]
+    return full, p0, pars
+
+
+def cross_slice_pairs(nb):
+    """(pairs, scale, bins, nbins, forward, reversed, bb): (t nb + b, (t + 1) nb + b) for t = 0, 1, then (nb + 4, 4) -- pair 4 reversed,
+    with its scales exchanged -- and (nb + 2, nb + 2) with unit scales."""
+    pairs = np.array([(t * nb + b, (t + 1) * nb + b) for t in range(2) for b in range(nb)] + [(nb + 4, 4), (nb + 2, nb + 2)], dtype=np.int32)
+    forward, rev, bb = 4, 2 * nb, 2 * nb + 1
+    scale = np.random.default_rng(10).uniform(0.5, 2.0, size=(len(pairs), 2))
+    scale[rev] = scale[forward][::-1]
+    scale[bb] = 1.0
+    return (pairs, scale) + DC.bins_of_pairs(len(pairs)) + (forward, rev, bb)
+
+
+@functools.lru_cache(maxsize=None)
+def cross_slices(dtype_name, path, calibrated):
+    full, p0, pars = cross_slice_problem()
+    pairs, scale, bins, nbins = cross_slice_pairs(p0.nbls)[:4]
+    op, norm_f = DS.operator(200, 200)
+    s = DC.solver_of(full, DC.joined(pars), np.dtype(dtype_name).type, "shared", path)
+    assert_path(s, path)
+    out = s.delay_cross_spectrum(op, norm_f, pairs, scale=scale, calibrated=calibrated, bin_of_pair=bins, nbins=nbins, per_pair=True)
+    assert_path(s, path)
+    after = afterwards(s)
+    s.close()
+    return out, after
+
+
+@pytest.mark.parametrize("calibrated", [False, True], ids=["raw", "calibrated"])
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_pairs_across_adjacent_slices_on_the_dense_path(dtype, calibrated):
+    """Both paths against the restatement (``bound_ratio <= 1`` in tests/test_gpu_delay_cross.py's ``check``), ``dense`` against
+    ``general`` to the bit -- fit quality afterwards too --, the reversed pair against the forward one to the bit."""
+    name = np.dtype(dtype).name
+    full, p0, pars = cross_slice_problem()
+    nb = p0.nbls
+    pairs, scale, bins, nbins, forward, rev, bb = cross_slice_pairs(nb)
+    # every slice draws its own flags: the common mask of a pair is neither row's own
+    m0, m1 = full.wgts[pairs[:, 0]] != 0, full.wgts[pairs[:, 1]] != 0
+    own = np.any((m0 & m1) != m0, axis=1) & np.any((m0 & m1) != m1, axis=1)
+    assert own[: 2 * nb].sum() > nb and not own[bb]
+    op, norm_f = DS.operator(200, 200)
+    ref = DC.reference(full, p0, pars, dtype, op, norm_f, pairs, scale, calibrated, bins, nbins)
+    got = {}
+    for path in ("general", "dense"):
+        out, after = cross_slices(name, path, calibrated)
+        DC.check(out, ref, dtype, f"adjacent slices {path} {name} calibrated={calibrated}", bins=bins, nbins=nbins)
+        for st in DC.STATS:
+            for k in DC.NAMES:
+                np.testing.assert_array_equal(out["per_pair"][st][k][rev], out["per_pair"][st][k][forward], err_msg=f"{path} {st} {k}: the reversed pair")
+            assert np.all(np.abs(out["per_pair"][st]["resid"][: 2 * nb]).max(axis=1) > 0), (path, st)
+        assert not np.any(out["per_pair"]["diff"]["data"][bb]) and np.all(out["norm_pair"] > 0)
+        got[path] = dict(C.flat(out), **{k: v for k, v in after.items() if k.startswith("quality_")})
+    assert_same_bits(got["dense"], got["general"], f"adjacent slices {name} calibrated={calibrated}")

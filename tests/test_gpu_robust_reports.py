@@ -1,12 +1,14 @@
-"""The five post-fit reports behind a ``robust_weights`` call: include/calamity_hip.h promises ONE weight plane that everything reads,
+"""The six post-fit reports behind a ``robust_weights`` call: include/calamity_hip.h promises ONE weight plane that everything reads,
 tests/test_gpu_robust_consumers.py holds fit quality, the closed-form solves, ``init_coeffs`` and ``eval`` to it, and this file the
-reports, which read ``wgts`` through ``coeff_planes``, ``gain_planes``, ``fit_error_rows_kernel`` (``nsamp_bl``) and
-``degen_rows_kernel`` (``fix_degeneracies`` with ``ref_w=None``).
+reports, which read ``wgts`` through ``coeff_planes``, ``gain_planes``, ``fit_error_rows_kernel`` (``nsamp_bl``),
+``degen_rows_kernel`` (``fix_degeneracies`` with ``ref_w=None``) and ``dcross_rows_kernel`` (``delay_cross_spectrum``: the weights of BOTH rows
+of a pair, as a mask -- a stale plane on one side alone changes the common mask, ``norm_pair`` and every statistic).
 
 The scheme is that file's.  Solver A calls ``robust_weights("clip", 2.0)`` and then the report; solver B is a fresh solver given A's
 weights through ``set_data``.  B has never seen ``w0``, so a report of A that took anything from the plane of ``w0`` or from a plane
 cached before the reweight differs from B.  Everything is compared bit for bit, on every kernel path of tests/test_gpu_solve_paths.py
-(every solver asserts the path it asked for).  The cases are those of tests/report_cases.py; Huber at k = 2 once.  ``fix_degeneracies``
+(every solver asserts the path it asked for).  The cases are those of tests/report_cases.py; Huber at k = 2 once, and once more for the cross spectrum, which
+reads the weights as a mask alone: behind Huber (new values, the same zeros) it keeps every bit of a solver that never reweighted.  ``fix_degeneracies``
 reads the solver's weights only with ``ref_w=None``; with ``ref_w`` given its result is bit-identical with and without the reweight.
 
 On ``general`` and ``dense`` the reports are also held to their restatements on a copy of the problem whose weights are A's, with the
@@ -20,7 +22,10 @@ the restatement did reach: ``leverage_bl`` 3.4e-6 and 1.3e-4, ``gain_dof`` 2.7e-
 with B is what holds them.
 
 Three slices with the middle one reweighted (``slice_mask=[0, 1, 0]``): the rows of slices 0 and 2 of ``fit_errors``,
-``delay_spectrum`` and ``delay_transfer`` equal a solver that never reweighted, all rows a solver given the mixed plane.  A
+``delay_spectrum``, ``delay_cross_spectrum`` (within-slice pairs) and ``delay_transfer`` equal a solver that never reweighted, all rows a
+solver given the mixed plane; and the same-baseline pairs of the slices (0, 1), (1, 2) and (0, 2), of which the first two have ONE side
+in the reweighted slice: every output the mixed-plane solver's, the (0, 2) pairs the never-reweighted solver's, ``norm_pair`` of the
+others not.  A
 ``robust_weights("none")`` behind the reports restores ``w0``, and a report behind it equals the report of a fresh solver.
 
 Shown once on scratch copies of the library (each inside its buffers: wrong numbers, no fault; each passes the older report files):
@@ -40,7 +45,14 @@ in each the named reader takes ``rw_w0`` (the plane of ``w0``) once a reweight h
   * ``dtransfer_power_kernel``'s own weight argument in ``delay_transfer`` (``coeff_planes`` left right): fails 24 -- 12 in (a), 8 in
     (b), the 4 of (c).
 
-Each fails cases of its own report alone, passes every test of tests/test_gpu_report_paths.py (which never reweights) and the 742
+  * ``dcross_rows_kernel`` given ``rw_w0`` for BOTH sides of a pair: fails 36 -- the 12 ``delay_cross`` cases of (a), 8 in (b), the 4 of
+    (c) (its within-slice pairs), the 4 of ``test_pairs_with_one_side_in_the_reweighted_middle_slice``, 8 in (d);
+  * ``dcross_rows_kernel`` given ``rw_w0`` for side 1 alone: fails 28 -- 12 in (a), 8 in (b), the 4 of (c), the 4 of
+    ``test_pairs_with_one_side_in_the_reweighted_middle_slice``; (d) passes (side 0 makes the clipped report another one).  Neither can
+    fail the Huber case, which is there for a reader of the weights' VALUES: Huber leaves the zeros of ``w0`` where they are.
+
+The two of ``dcross_rows_kernel`` also pass tests/test_gpu_delay_cross.py, test_gpu_delay_cross_dropin.py and
+test_gpu_delay_cross_ranks.py as they stood before (60 tests: none reweights).  Each fails cases of its own report alone, passes every test of tests/test_gpu_report_paths.py (which never reweights) and the 742
 tests of the older files (tests/test_gpu_fit_errors.py, test_gpu_gain_basis_errors.py, test_gpu_delay_spectrum.py,
 test_gpu_delay_transfer.py, test_gpu_degeneracy.py, test_gpu_robust_consumers.py, test_gpu_solve_paths.py).  The two builds that are
 wrong on the dense paths only are listed in tests/test_gpu_report_paths.py."""
@@ -48,6 +60,7 @@ import numpy as np
 import pytest
 
 import report_cases as C
+import test_gpu_delay_spectrum as DS
 from test_gpu_report_paths import afterwards, outputs, rows_of_slice, slice_reports
 from test_gpu_robust_consumers import CLIP, HUBER, assert_the_weights_matter, reweighted, slice_solver, uploaded
 from test_gpu_solve_paths import PATHS, REG_PATHS, assert_path, assert_same_bits, check_loss, path_id, three_slices
@@ -100,6 +113,22 @@ def test_fix_degeneracies_with_ref_w_given_does_not_read_the_solver_s_weights(ca
     assert_same_bits(got, want, f"{C.case_id(case)} {path} {np.dtype(dtype).name}")
 
 
+@pytest.mark.parametrize("dtype,path", PATHS, ids=PATH_IDS)
+@pytest.mark.parametrize("variant", ["raw", "calibrated"])
+def test_the_cross_spectrum_reads_the_weights_as_a_mask_huber_changes_no_bit(variant, dtype, path):
+    """Huber at k = 2 changes weights and zeroes none; ``dcross_rows_kernel`` reads ``w != 0`` alone: the bits of a solver that never
+    reweighted (``fit_quality`` afterwards does read the values)."""
+    case = ("delay_cross", variant)
+    a, w, w0 = solver_a(case, dtype, path, HUBER)
+    now = a.get_weights(0)
+    assert np.any(now != w0) and np.array_equal(now == 0, w0 == 0) and np.array_equal(now, w)
+    got = C.flat(C.call(a, *case))
+    assert_path(a, path)
+    a.close()
+    want = C.flat(outputs(case, np.dtype(dtype).name, path)[0])
+    assert_same_bits(got, want, f"{C.case_id(case)} {path} {np.dtype(dtype).name} behind huber")
+
+
 # ---- (b) A against the restatement under its weights
 @pytest.mark.parametrize("dtype,path", REG_PATHS, ids=map(path_id, REG_PATHS))
 @pytest.mark.parametrize("case", C.WEIGHT_READERS, ids=map(C.case_id, C.WEIGHT_READERS))
@@ -122,6 +151,12 @@ def test_a_report_behind_the_call_equals_its_restatement_under_the_new_weights(c
     quality = a.fit_quality()
     assert_path(a, path)
     a.close()
+    if kind == "delay_cross":  # no integer output: norm_pair is the common mask's sum, at the tolerance of the report's own file
+        pairs = C.cross_pairs(*case)[0]
+        norm_f = C.delay_operator(*case)[1]
+        common = lambda ww: ((ww[pairs[:, 0]] != 0) & (ww[pairs[:, 1]] != 0)).astype(np.float64) @ norm_f  # noqa: E731
+        np.testing.assert_allclose(raw["norm_pair"], common(w), rtol=1e-13, atol=0, err_msg=label)
+        assert not np.array_equal(raw["norm_pair"], common(w0)), label
     counts = C.sample_counts(kind, new)
     if counts is not None:
         key = "nsamp_bl" if kind == "fit_errors" else "nsamples"
@@ -164,6 +199,45 @@ def test_three_slices_with_the_middle_one_reweighted(dtype, path):
                                               err_msg=f"{name} {key}: slice {t} against a solver that never reweighted")
             differs |= not np.array_equal(rows_of_slice(name, key, arr, 1, p0), rows_of_slice(name, key, never[name][key], 1, p0))
         assert differs, name
+
+
+def slice_pairs(nb):
+    """Same-baseline pairs of the slices (0, 1), (1, 2) and (0, 2), nb each, with seeded unequal scales and one bin per slice pair."""
+    pairs = np.array([(t0 * nb + b, t1 * nb + b) for t0, t1 in ((0, 1), (1, 2), (0, 2)) for b in range(nb)], dtype=np.int32)
+    scale = np.random.default_rng(11).uniform(0.5, 2.0, size=(len(pairs), 2))
+    return pairs, scale, np.repeat(np.arange(3), nb).astype(np.int32), 3
+
+
+@pytest.mark.parametrize("dtype,path", REG_PATHS, ids=map(path_id, REG_PATHS))
+def test_pairs_with_one_side_in_the_reweighted_middle_slice(dtype, path):
+    """The pairs (slice 0, slice 1) and (slice 1, slice 2) have ONE side in the reweighted slice: a reader that took either side from
+    the plane of ``w0`` differs from the solver given the mixed plane.  The pairs (slice 0, slice 2) touch no new weight."""
+    p0 = three_slices()[0]
+    nb = p0.nbls
+    pairs, scale, bins, nbins = slice_pairs(nb)
+    op, norm_f = DS.operator(200, 200)
+    a = slice_solver(dtype, path)
+    w_in = a.get_weights()
+    a.robust_weights(*CLIP, slice_mask=[0, 1, 0])
+    w = a.get_weights()
+    assert np.any((w[nb : 2 * nb] == 0) & (w_in[nb : 2 * nb] > 0)) and np.array_equal(w[:nb], w_in[:nb]) and np.array_equal(w[2 * nb :], w_in[2 * nb :])
+    results = []
+    for s in (a, slice_solver(dtype, path, wgts=w), slice_solver(dtype, path)):
+        results.append(C.flat(s.delay_cross_spectrum(op, norm_f, pairs, scale=scale, bin_of_pair=bins, nbins=nbins, per_pair=True)))
+        assert_path(s, path)
+        s.close()
+    got, mixed, never = results
+    label = f"{path} {np.dtype(dtype).name}"
+    assert_same_bits(got, mixed, label + ": against the solver given the mixed plane")
+    far, near = slice(2 * nb, 3 * nb), slice(0, 2 * nb)
+    for key, arr in got.items():
+        if key.startswith("per_pair_") or key == "norm_pair":
+            np.testing.assert_array_equal(arr[far], never[key][far], err_msg=f"{label} {key}: the pairs (slice 0, slice 2) against a solver that never reweighted")
+        else:
+            np.testing.assert_array_equal(arr[2], never[key][2], err_msg=f"{label} {key}: the bin of the pairs (slice 0, slice 2)")
+    changed = got["norm_pair"][near] != never["norm_pair"][near]
+    print(f"{label}: norm_pair differs in {changed[:nb].sum()} of {nb} pairs (0, 1) and {changed[nb:].sum()} of {nb} pairs (1, 2)")
+    assert changed[:nb].any() and changed[nb:].any(), label  # (slice 1 is side 1 of the first and side 0 of the second)
 
 
 # ---- (d) back to w0

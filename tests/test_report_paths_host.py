@@ -9,7 +9,9 @@ the two GPU files assume of it, without a device -- so a case cannot quietly sto
     between 5 % and 30 % of the good samples are clipped;
   * every case reaches its shape branch: more than 64 channels and one baseline per fitting group (what the dense paths need), the
     K = 65 case a ``W`` past one 64-row block, the flagged channel and the flagged antenna of the ``fix_degeneracies`` reference still
-    there at 72 channels."""
+    there at 72 channels;
+  * the pairs of the ``delay_cross`` cases keep what makes the common mask matter: exactly the two pairs that touch the wholly flagged
+    row have ``norm_pair == 0``, under ``w0`` and under the clipped weights, and a pair's common mask differs from both rows' own."""
 import numpy as np
 import pytest
 
@@ -38,7 +40,14 @@ def test_the_table_holds_the_shapes_it_is_meant_to():
     assert shapes["fit_errors-7x200"] == (7, 200) and shapes["fit_errors-12x129"] == (12, 129)
     assert shapes["gain_basis_errors-freq_K12"] == shapes["gain_basis_errors-freq_K65"] == (7, 200)
     assert shapes["gain_basis_errors-time_freq"] == shapes["gain_basis_errors-time"] == (4 * 5, 72)
-    assert all(shapes[f"{kind}-{v}"] == (7, 200) for kind in ("delay_spectrum", "delay_transfer") for v in ("raw", "calibrated"))
+    assert all(shapes[f"{kind}-{v}"] == (7, 200) for kind in ("delay_spectrum", "delay_cross", "delay_transfer") for v in ("raw", "calibrated"))
+    pairs, scale, bins, nbins = C.cross_pairs()
+    nb = C.inputs("delay_cross", "raw")[0].nbls
+    assert nb == 22 and pairs.shape == scale.shape == (nb + 2, 2) and bins.shape == (nb + 2,) and nbins == 4 and bins.max() == 2 and bins.min() == -1
+    assert [tuple(pr) for pr in pairs[:nb]] == [(b, (b + 3) % nb) for b in range(nb)] and tuple(pairs[nb]) == (2, 2) and tuple(pairs[nb + 1]) == (nb - 1, 0)
+    unequal = np.delete(scale, nb, axis=0)
+    assert np.all(scale[nb] == 1.0) and np.all(unequal != 1.0) and np.all(unequal[:, 0] != unequal[:, 1])
+    assert C.delay_operator("delay_cross", "raw")[0].shape == (200, 200)
     assert all(v == (7, C.DEGEN_NF) for k, v in shapes.items() if k.startswith("fix_degeneracies")) and C.DEGEN_NF == 72
     K = {v: C.inputs("gain_basis_errors", v)[2].shape[1] for v in ("freq_K12", "freq_K65")}
     assert K == {"freq_K12": 12, "freq_K65": 65}
@@ -112,3 +121,23 @@ def test_the_margin_table_names_cases_of_the_table():
     for case, keys in C.BELOW_MARGIN_FP32.items():
         assert set(keys) <= set(C.MATTER_PLANES[case[0]])
     assert [c for c in C.CASES if c not in C.WEIGHT_READERS] == C.GIVEN_REF_W == [("fix_degeneracies", "channel"), ("fix_degeneracies", "band")]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("variant", ["raw", "calibrated"])
+def test_the_cross_pairs_keep_two_dead_pairs_and_a_common_mask_of_their_own(variant, dtype):
+    """``norm_pair == 0`` for the two pairs that touch the wholly flagged row 1 and for no other, under ``w0`` and under the clipped
+    weights; some pair's common mask is neither row's own (a reader that took one side's mask for both would differ there)."""
+    case = ("delay_cross", variant)
+    pairs = C.cross_pairs(*case)[0]
+    w, w0, _ = C.clipped_weights(*case, dtype)
+    assert not np.any(w0[1]) and np.all(np.count_nonzero(np.delete(w0, 1, axis=0), axis=1) > 0)
+    touches = np.flatnonzero((pairs == 1).any(axis=1))
+    assert len(touches) == 2
+    for weights, ref in ((w0, C.reference(*case, np.dtype(dtype).name)), (w, C.restatement(*case, dtype, C.with_weights(C.inputs(*case)[0], w)))):
+        np.testing.assert_array_equal(np.flatnonzero(ref["norm_pair"] == 0), touches)
+        m0, m1 = weights[pairs[:, 0]] != 0, weights[pairs[:, 1]] != 0
+        common = m0 & m1
+        own = np.any(common != m0, axis=1) & np.any(common != m1, axis=1)
+        print(f"{C.case_id(case)} {np.dtype(dtype).name}: {own.sum()} of {len(pairs)} pairs have a common mask that is neither row's own")
+        assert own.any()
