@@ -114,6 +114,16 @@ class DelayCrossDesc(C.Structure):
                 ("op_i", C.c_void_p), ("norm_f", C.c_void_p)]
 
 
+class DelayFringeDesc(C.Structure):
+    """cal_delay_fringe_desc (include/calamity_hip.h: cal_solver_delay_fringe_spectrum): ndelays, what and calibrated as in
+    DelaySpectrumDesc; ngroups, ntimes, nrates, rows [ngroups][ntimes] int32 (rows of the solver), scale [ngroups][ntimes] float64
+    (NULL: ones), nbins and bin_of_group [ngroups] int32 in [-1, nbins) (NULL iff nbins == 0), the operator and norm_f, and the
+    transform along time opt_r, opt_i [ntimes][nrates] float64."""
+    _fields_ = [("ndelays", C.c_int32), ("what", C.c_int32), ("calibrated", C.c_int32), ("ngroups", C.c_int32), ("ntimes", C.c_int32),
+                ("nrates", C.c_int32), ("rows", C.c_void_p), ("scale", C.c_void_p), ("nbins", C.c_int32), ("bin_of_group", C.c_void_p),
+                ("op_r", C.c_void_p), ("op_i", C.c_void_p), ("norm_f", C.c_void_p), ("opt_r", C.c_void_p), ("opt_i", C.c_void_p)]
+
+
 class DelayTransferDesc(C.Structure):
     """cal_delay_transfer_desc (include/calamity_hip.h: cal_solver_delay_transfer): ndelays columns of the operator op_r + i op_i
     ([nfreqs][ndelays], solver dtype), calibrated 0 / 1, nbins and bin_of_bl [nbls] int32 in [-1, nbins) (NULL iff nbins == 0), the
@@ -146,6 +156,12 @@ class CrossReportPlanDesc(ReportPlanDesc):
     """cal_report_plan_desc with its last field, read for the selectors 60 .. 65 only: a cross description, planned under scratch_bytes
     (the spectrum's bound)."""
     _fields_ = [("cross", C.POINTER(DelayCrossDesc))]
+
+
+class FringeReportPlanDesc(CrossReportPlanDesc):
+    """cal_report_plan_desc with its last field, read for the selectors 70 .. 76 only: a fringe description, planned under
+    scratch_bytes (the spectrum's bound)."""
+    _fields_ = [("fringe", C.POINTER(DelayFringeDesc))]
 
 
 class CoeffSolveDesc(C.Structure):
@@ -272,6 +288,7 @@ SYMBOLS = {
     "cal_solver_delay_spectrum": (C.c_int, [_P, C.POINTER(DelaySpectrumDesc), _P, _P, _P, _P, _P, _P]),
     "cal_solver_set_delay_spectrum_scratch": (C.c_int, [_P, C.c_int64]),
     "cal_solver_delay_cross_spectrum": (C.c_int, [_P, C.POINTER(DelayCrossDesc), _P, _P, _P, _P, _P, _P, _P, _P]),
+    "cal_solver_delay_fringe_spectrum": (C.c_int, [_P, C.POINTER(DelayFringeDesc), _P, _P, _P, _P, _P, _P]),
     "cal_solver_delay_transfer": (C.c_int, [_P, C.POINTER(DelayTransferDesc), _P, _P, _P, _P, _P, _P, C.POINTER(FitErrorsCounts)]),
     "cal_solver_set_delay_transfer_scratch": (C.c_int, [_P, C.c_int64]),
     "cal_solver_fix_degeneracies": (C.c_int, [_P, C.POINTER(DegeneracyDesc), _P, _P, _P, _P, _P, _P, _P]),

@@ -82,6 +82,28 @@ def split_pairs(pairs, rows, nbls):
     return sel, [where[pairs[s]].astype(np.int32) for s in sel]
 
 
+def split_groups(groups, rows, nbls):
+    """``split_pairs`` for groups of any length: share out ``groups`` ``[ngroups, T]`` of global rows over the workers whose global
+    rows are ``rows[r]`` (in the worker's local order): ``(sel, local)`` with ``sel[r]`` the positions of worker ``r``'s groups in
+    ``groups`` and ``local[r]`` those groups as its local rows.  ``ValueError`` for a group whose rows lie on several workers and for a
+    worker without a group."""
+    groups = np.asarray(groups, dtype=np.int64)
+    groups = groups.reshape(-1, groups.shape[-1])
+    owner, where = np.full(nbls, -1, dtype=np.int64), np.zeros(nbls, dtype=np.int64)
+    for r, idx in enumerate(rows):
+        owner[idx], where[idx] = r, np.arange(len(idx))
+    own = owner[groups]
+    split = np.nonzero((own != own[:, :1]).any(axis=1))[0]
+    if len(split):
+        g = int(split[0])
+        raise ValueError(f"group {g} = {tuple(int(v) for v in groups[g])} joins rows of several workers {tuple(int(v) for v in own[g])}")
+    sel = [np.nonzero(own[:, 0] == r)[0] for r in range(len(rows))]
+    for r, s in enumerate(sel):
+        if len(s) == 0:
+            raise ValueError(f"worker {r} holds no group: every worker must take part in the exchange of the bins")
+    return sel, [where[groups[s]].astype(np.int32) for s in sel]
+
+
 class _HostExchange:
     """In-process all-reduce between worker threads (cal_solver_set_exchange_hook): every worker leaves a view of its staging
     buffer, all of them reduce the views in rank order -- the same arithmetic on every worker -- and each writes the result
@@ -326,6 +348,31 @@ class SliceBatchFitter:
         out = dict(outs[0], norm_pair=self._scatter([o["norm_pair"] for o in outs], sel))
         if per_pair:
             out["per_pair"] = {k: {q: self._scatter([o["per_pair"][k][q] for o in outs], sel) for q in v} for k, v in outs[0]["per_pair"].items()}
+        return out
+
+    def delay_fringe_spectrum(self, op, norm_f, rows, opt, scale=None, what=("data", "model", "resid"), calibrated=False,
+                              bin_of_group=None, nbins=0, per_group=False, g_r=None, g_i=None):
+        """``HipFitSolver.delay_fringe_spectrum`` on global slice-major rows: ``rows`` ``[ngroups, T]`` rows of the batch.  Every worker
+        takes the groups whose rows it all holds, mapped to its local rows; a group split over workers raises ``ValueError`` (it cannot
+        happen for one baseline in several slices: the groups of a share are replicated over the slices), and so does a worker left
+        without a group (it could not join the exchange).  The binned arrays and ``count_bin`` are worker 0's (with several workers the
+        library has summed them over the workers); ``norm_grp`` and the ``per_group`` arrays are put back into the caller's order."""
+        rows = np.asarray(rows, dtype=np.int64)
+        if rows.ndim != 2 or rows.shape[0] < 1 or rows.shape[1] < 1:
+            raise ValueError(f"rows must be [ngroups >= 1, ntimes >= 1], got shape {rows.shape}")
+        if rows.min() < 0 or rows.max() >= self.nbls:
+            raise ValueError(f"rows must hold rows in [0, {self.nbls})")
+        kw = dict(what=what, calibrated=calibrated, nbins=nbins, per_group=per_group, g_r=g_r, g_i=g_i)
+        scale = None if scale is None else np.asarray(scale, dtype=np.float64)
+        bins = None if bin_of_group is None else np.asarray(bin_of_group)
+        if self.nworkers == 1:
+            return self.solvers[0].delay_fringe_spectrum(op, norm_f, rows, opt, scale=scale, bin_of_group=bins, **kw)
+        sel, local = split_groups(rows, self.rows, self.nbls)
+        outs = self._each(lambda r, s: s.delay_fringe_spectrum(op, norm_f, local[r], opt, scale=None if scale is None else scale[sel[r]],
+                                                               bin_of_group=None if bins is None else bins[sel[r]], **kw))
+        out = dict(outs[0], norm_grp=self._scatter([o["norm_grp"] for o in outs], sel))
+        if per_group:
+            out["per_group"] = {q: self._scatter([o["per_group"][q] for o in outs], sel) for q in outs[0]["per_group"]}
         return out
 
     def delay_transfer(self, op, ridge=1e-6, calibrated=False, bin_of_bl=None, nbins=0, per_baseline=False, g_r=None, g_i=None):

@@ -967,6 +967,92 @@ def delay_cross_entry(cross, dspec, k, partner_time_index, prob, ant_array):
     return entry
 
 
+def _check_delay_fringe(delay_fringe_spectrum, delay_fringe_times, delay_fringe_taper, delay_spectrum, batch_slices, init_guesses_from_previous_time_step):
+    """The ``delay_fringe_spectrum`` keywords of ``calibrate_and_model_tensor``, checked before anything is touched (``ValueError``)."""
+    if not any(delay_fringe_spectrum is v for v in (False, True)) and delay_fringe_spectrum != "baselines":
+        raise ValueError(f"delay_fringe_spectrum must be False, True or 'baselines', got {delay_fringe_spectrum!r}")
+    if not delay_fringe_spectrum:
+        return
+    if not delay_spectrum:
+        raise ValueError("delay_fringe_spectrum needs delay_spectrum=True or 'baselines': it uses that spectrum's operator, taper, bins and calibrated switch")
+    if isinstance(delay_fringe_times, bool) or not isinstance(delay_fringe_times, (int, np.integer)) or not 2 <= int(delay_fringe_times) <= 64:
+        raise ValueError(f"delay_fringe_spectrum: delay_fringe_times must be an integer in [2, 64], got {delay_fringe_times!r}")
+    try:
+        modeling.delay_taper(int(delay_fringe_times), delay_fringe_taper)
+    except ValueError:
+        raise ValueError(f"delay_fringe_spectrum: delay_fringe_taper must be 'bh4', 'none' or an array of delay_fringe_times values, got {delay_fringe_taper!r}") from None
+    if init_guesses_from_previous_time_step:
+        raise ValueError("delay_fringe_spectrum transforms along the times of a batch: init_guesses_from_previous_time_step (a chain of single times) contradicts it")
+    if batch_slices is not None and batch_slices is not True and int(batch_slices) < int(delay_fringe_times):
+        raise ValueError(f"delay_fringe_spectrum transforms along the times of a batch: batch_slices={batch_slices!r} holds no window of "
+                         f"delay_fringe_times={int(delay_fringe_times)} (True or at least that many)")
+
+
+def delay_fringe_windows(polnums, time_indices, ntimes, times=None, dt=None):
+    """The windows of a batch's unskipped slices, given in order by their polarization numbers and time indices: every run of ``ntimes``
+    slices of one polarization whose time indices rise by exactly 1; the walk then moves on behind the run (windows do not overlap),
+    otherwise by one, and a slice left over belongs to no window.  Returns the list of tuples of ``ntimes`` positions.  With ``times``
+    (the data's distinct times, indexed by the time indices) and ``dt`` (their median spacing) a window whose spacings differ from
+    ``dt`` by more than 1 % raises ``ValueError`` naming the times: the transform along time takes evenly spaced integrations."""
+    n = int(ntimes)
+    windows, i = [], 0
+    while i + n <= len(polnums):
+        run = all(polnums[i + k] == polnums[i] and int(time_indices[i + k]) - int(time_indices[i]) == k for k in range(1, n))
+        if run:
+            windows.append(tuple(range(i, i + n)))
+            i += n
+        else:
+            i += 1
+    if times is not None:
+        for win in windows:
+            at = np.asarray([times[int(time_indices[k])] for k in win], dtype=np.float64)
+            if np.any(np.abs(np.diff(at) - dt) > 0.01 * abs(dt)):
+                raise ValueError(f"delay_fringe_spectrum: the times {at.tolist()} are not evenly spaced by the data's median spacing {dt!r}")
+    return windows
+
+
+def delay_fringe_setup(times, ntimes, taper="bh4", per_baseline=False):
+    """What the fringe-rate pass of every batch of a call shares: the data's distinct ``times`` (Julian days), their median spacing ``dt``
+    (the same unit), the transform along time (``modeling.fringe_rate_transform`` on ``ntimes`` integrations ``dt`` apart, all rates) and
+    its fringe rates in Hz."""
+    times = np.asarray(times, dtype=np.float64)
+    dt = float(np.median(np.diff(times))) if len(times) > 1 else 1.0
+    opt, rates_hz = modeling.fringe_rate_transform(int(ntimes), dt * 86400.0, taper=taper)
+    return dict(ntimes=int(ntimes), times=times, dt=dt, opt=opt, rates_hz=rates_hz, per_group=bool(per_baseline))
+
+
+def delay_fringe_rows(windows, dspec, rms, nbls):
+    """What ``SliceBatchFitter.delay_fringe_spectrum`` takes for the slice windows ``windows`` of a batch: group ``g`` of baseline row
+    ``b`` in window ``k`` is the rows ``t nbls + b`` of the window's slices ``t`` with their ``rms`` as scales and bin
+    ``k nbins + bin_of_bl[b]``.  Returns ``(rows [ngroups, ntimes] int32, scale [ngroups, ntimes], bin_of_group [ngroups] int32)``,
+    window by window."""
+    b = np.arange(nbls, dtype=np.int64)
+    rows = np.concatenate([np.stack([t * nbls + b for t in win], axis=1) for win in windows]).astype(np.int32)
+    scale = np.concatenate([np.tile([float(rms[t]) for t in win], (nbls, 1)) for win in windows])
+    bins = np.concatenate([k * dspec["nbins"] + np.asarray(dspec["bin_of_bl"], dtype=np.int64) for k in range(len(windows))]).astype(np.int32)
+    return rows, scale, bins
+
+
+def delay_fringe_entry(fringe, dspec, k, time_indices, prob, ant_array):
+    """Window ``k`` of a ``delay_fringe_spectrum`` over ``delay_fringe_rows`` as what every member of it reports under
+    ``fit_history[...]["delay_spectrum"]["fringe"]``: ``time_indices`` of the window, ``fringe_rates`` in Hz, ``data``, ``model``,
+    ``resid`` ``[nbins, nrates, ndelays]``, the MEAN power per baseline-length bin in the data's units squared (the scales were the
+    slices' ``rms``; 0 for a bin without a counted group), ``nbls`` the counted groups per bin, and with per-group rows
+    ``per_baseline`` keyed by antenna numbers."""
+    nb, nbins = prob.nbls, dspec["nbins"]
+    bins, rows = slice(k * nbins, (k + 1) * nbins), slice(k * nb, (k + 1) * nb)
+    count = np.asarray(fringe["count_bin"][bins], dtype=np.float64)
+    mean = np.divide(1.0, count, out=np.zeros_like(count), where=count > 0)[:, None, None]
+    entry = {"time_indices": [int(t) for t in time_indices], "fringe_rates": np.array(dspec["fringe"]["rates_hz"]), "nbls": count.astype(np.int64)}
+    for q in ("data", "model", "resid"):
+        entry[q] = mean * np.asarray(fringe[q][bins])
+    if "per_group" in fringe:
+        ants = np.asarray(ant_array)
+        entry["per_baseline"] = {(int(ants[i]), int(ants[j])): {q: fringe["per_group"][q][rows][b] for q in ("data", "model", "resid")}
+                                 for b, (i, j) in enumerate(zip(prob.bl_ant0, prob.bl_ant1))}
+    return entry
+
+
 def baseline_length_bins(lengths, width):
     """Baseline rows into bins of ``width`` metres, bin ``floor(length / width)``, only the bins that hold a row, in ascending order:
     ``(bin_of_bl [nbls] int32, bllen_m [nbins])`` with ``bllen_m`` the mean length of each bin's rows."""
@@ -983,7 +1069,8 @@ def delay_spectrum_setup(uvdata, ant_array, prob, taper="bh4", max_dly=None, bll
     on the data's frequencies), the length bin of every baseline row of ``prob`` (``baseline_length_bins`` on the antenna positions of
     ``uvdata``; ``ant_array``: the antenna numbers ``prob``'s antenna indices count through) and the two switches.  ``transfer_ridge``
     stays ``None`` unless the call also asks for the delay transfer (``delay_transfer``: its ridge then), ``cross`` unless it asks for the
-    cross spectrum of paired times (``delay_cross_spectrum``: ``"bins"`` or ``"baselines"`` then)."""
+    cross spectrum of paired times (``delay_cross_spectrum``: ``"bins"`` or ``"baselines"`` then), ``fringe`` unless it asks for the delay /
+    fringe-rate plane (``delay_fringe_spectrum``: ``delay_fringe_setup``'s dictionary then)."""
     op, norm_f, delays_ns = modeling.delay_transform(np.asarray(uvdata.freq_array, dtype=np.float64).ravel(), taper=taper, max_delay_ns=max_dly)
     if op.shape[1] < 1 or op.shape[1] > 4096:
         raise ValueError(f"the delay spectrum has {op.shape[1]} delays: between 1 and 4096 (delay_spectrum_max_dly)")
@@ -992,7 +1079,7 @@ def delay_spectrum_setup(uvdata, ant_array, prob, taper="bh4", max_dly=None, bll
     lengths = np.asarray([np.linalg.norm(pos[int(ants[i])] - pos[int(ants[j])]) for i, j in zip(prob.bl_ant0, prob.bl_ant1)])
     bin_of_bl, bllen_m = baseline_length_bins(lengths, bllen_bin)
     return dict(op=op, norm_f=norm_f, delays_ns=delays_ns, bin_of_bl=bin_of_bl, nbins=len(bllen_m), bllen_m=bllen_m, calibrated=bool(calibrated),
-                per_baseline=bool(per_baseline), transfer_ridge=None, cross=None)
+                per_baseline=bool(per_baseline), transfer_ridge=None, cross=None, fringe=None)
 
 
 def delay_spectrum_slice_bins(dspec, nt):
@@ -1170,6 +1257,9 @@ def calibrate_and_model_tensor(
     fix_degeneracies=False,
     degeneracy_iters=6,
     degeneracy_phase_ref=True,
+    delay_fringe_spectrum=False,
+    delay_fringe_times=8,
+    delay_fringe_taper="bh4",
     delay_cross_spectrum=False,
     delay_transfer=False,
     delay_transfer_ridge=1e-6,
@@ -1375,6 +1465,20 @@ def calibrate_and_model_tensor(
       (the antenna pairs of ``fg_model_comps_dict``, the keys of ``per_baseline``): held as ``(j, i)`` its spectrum is the mirror image
       in delay of ``(i, j)``'s.  A joint time-basis fit reports every time on its own.
       ``ValueError`` before any device work for an unknown taper, a bin width that is not positive, a negative ``delay_spectrum_max_dly``.
+    * ``delay_fringe_spectrum`` (``False`` | ``True`` | ``"baselines"``), ``delay_fringe_times`` (2 .. 64), ``delay_fringe_taper`` (Python
+      keywords only; default off: no call changes by a bit and no new kernel is launched; needs ``delay_spectrum`` on and batches that
+      hold a window, else ``ValueError`` before anything is touched -- ``batch_slices`` ``False`` or below ``delay_fringe_times`` and
+      ``init_guesses_from_previous_time_step`` are refused; an automatic batch size becomes a multiple of ``delay_fringe_times``): the
+      delay / fringe-rate plane (``HipFitSolver.delay_fringe_spectrum``: one more device pass beside the spectrum's, at the reported
+      gains, with the spectrum's operator, taper along frequency, bins and ``delay_spectrum_calibrated``; along time the tapered DFT of
+      ``modeling.fringe_rate_transform`` at the data's median spacing).  Inside a batch the unskipped slices are cut into windows in
+      order (``delay_fringe_windows``): every run of ``delay_fringe_times`` slices of one polarization whose time indices rise by
+      exactly 1; windows do not overlap and do not span batches; slices left over belong to no window; a window that is not evenly
+      spaced to 1 % is a ``ValueError``.  A joint time-basis fit is cut the same way.  Every member of a window gets
+      ``["delay_spectrum"]["fringe"]``: ``time_indices``, ``fringe_rates`` (Hz, ascending), ``data``, ``model``, ``resid``
+      ``[nbins, Nrates, Ndelays]`` -- the MEAN over the bin's baselines of ``|Z|^2 / norm`` under the COMMON mask of the window's times,
+      data's units squared --, and ``nbls``; ``"baselines"`` adds ``per_baseline`` keyed by antenna numbers.  A slice outside every
+      window has no ``"fringe"`` key.  Several devices are refused with ``ValueError`` where a window's rows would lie on two of them.
     * ``delay_cross_spectrum`` (``False`` | ``True`` | ``"baselines"``; a Python keyword only; default off: no call changes by a bit and no
       new kernel is launched; needs ``delay_spectrum`` on and batching, else ``ValueError`` before anything is touched -- ``batch_slices``
       ``False`` or 1 and ``init_guesses_from_previous_time_step`` are refused; an automatic batch size becomes even): delay power that
@@ -1421,6 +1525,7 @@ def calibrate_and_model_tensor(
     _check_delay_spectrum(delay_spectrum, delay_spectrum_taper, delay_spectrum_max_dly, delay_spectrum_bllen_bin)
     _check_delay_transfer(delay_transfer, delay_transfer_ridge, delay_spectrum, freeze_model)
     _check_delay_cross(delay_cross_spectrum, delay_spectrum, batch_slices, init_guesses_from_previous_time_step)
+    _check_delay_fringe(delay_fringe_spectrum, delay_fringe_times, delay_fringe_taper, delay_spectrum, batch_slices, init_guesses_from_previous_time_step)
     controls = FitControls.pick(locals())
     controls.check(gain_basis is not None or gain_max_dly is not None, gain_time_basis is not None or gain_time_scale is not None, freeze_model, use_min)
     if gain_max_dly is not None:
@@ -1504,6 +1609,8 @@ def calibrate_and_model_tensor(
         if delay_transfer:
             dspec["transfer_ridge"] = float(delay_transfer_ridge)
         dspec["cross"] = {False: None, True: "bins", "baselines": "baselines"}[delay_cross_spectrum]
+        if delay_fringe_spectrum:
+            dspec["fringe"] = delay_fringe_setup(np.unique(uvdata.time_array), delay_fringe_times, delay_fringe_taper, delay_fringe_spectrum == "baselines")
     degen = degeneracy_setup(uvdata, gains.ant_array, degen_mode, degeneracy_iters, degeneracy_phase_ref) if degen_mode is not None else None
     if parallel_fits is None:
         parallel_fits = 1
@@ -1511,7 +1618,7 @@ def calibrate_and_model_tensor(
         parallel_fits = 1
     times = np.unique(uvdata.time_array)
     if batch_slices is None:
-        batch_slices = parallel_fits <= 1 or gain_time_basis is not None or bool(delay_cross_spectrum)
+        batch_slices = parallel_fits <= 1 or gain_time_basis is not None or bool(delay_cross_spectrum) or bool(delay_fringe_spectrum)
     if init_guesses_from_previous_time_step:
         batch_slices = False  # every time starts from the previous one's result: a chain, not a batch
     # the call's settings, once, for the loop and the batches alike (slice_pipeline's stages read them)
@@ -1532,6 +1639,9 @@ def calibrate_and_model_tensor(
             max_batch = _auto_batch(prob, dtype, layout) if batch_slices is True else max(1, min(int(batch_slices), _lib_max_slices()))
             if delay_cross_spectrum and batch_slices is True:
                 max_batch = max(2, max_batch) // 2 * 2  # the times are paired inside a batch: an even number of them
+            if delay_fringe_spectrum and batch_slices is True:
+                n = int(delay_fringe_times) * (2 if delay_cross_spectrum and int(delay_fringe_times) % 2 else 1)
+                max_batch = max(n, max_batch) // n * n  # whole windows inside a batch (and whole pairs, where both are asked for)
         fit_history = _fit_slices_batched(cfg, max_batch)
         _file_gain_std(fit_history, errs, gains)
         return model, resid, gains, fit_history  # (every fitted slice left its write-back in its final state)
@@ -1939,6 +2049,9 @@ def calibrate_and_model_dpss(
     fix_degeneracies=False,
     degeneracy_iters=6,
     degeneracy_phase_ref=True,
+    delay_fringe_spectrum=False,
+    delay_fringe_times=8,
+    delay_fringe_taper="bh4",
     delay_cross_spectrum=False,
     delay_transfer=False,
     delay_transfer_ridge=1e-6,
@@ -1956,6 +2069,8 @@ def calibrate_and_model_dpss(
     _check_delay_spectrum(delay_spectrum, delay_spectrum_taper, delay_spectrum_max_dly, delay_spectrum_bllen_bin)
     _check_delay_transfer(delay_transfer, delay_transfer_ridge, delay_spectrum, fitting_kwargs.get("freeze_model", False))
     _check_delay_cross(delay_cross_spectrum, delay_spectrum, fitting_kwargs.get("batch_slices"), fitting_kwargs.get("init_guesses_from_previous_time_step", False))
+    _check_delay_fringe(delay_fringe_spectrum, delay_fringe_times, delay_fringe_taper, delay_spectrum, fitting_kwargs.get("batch_slices"),
+                        fitting_kwargs.get("init_guesses_from_previous_time_step", False))
     _check_degeneracy_call(fix_degeneracies, degeneracy_iters, fitting_kwargs)
     waker = _wake_device(fitting_kwargs.get("devices"))
     try:
@@ -1968,6 +2083,7 @@ def calibrate_and_model_dpss(
             notebook_progressbar=notebook_progressbar, delay_spectrum=delay_spectrum, delay_spectrum_taper=delay_spectrum_taper,
             delay_spectrum_max_dly=delay_spectrum_max_dly, delay_spectrum_bllen_bin=delay_spectrum_bllen_bin,
             delay_spectrum_calibrated=delay_spectrum_calibrated, delay_transfer=delay_transfer, delay_transfer_ridge=delay_transfer_ridge, delay_cross_spectrum=delay_cross_spectrum,
+            delay_fringe_spectrum=delay_fringe_spectrum, delay_fringe_times=delay_fringe_times, delay_fringe_taper=delay_fringe_taper,
             fix_degeneracies=fix_degeneracies, degeneracy_iters=degeneracy_iters,
             degeneracy_phase_ref=degeneracy_phase_ref, **fitting_kwargs,
         )
@@ -2012,6 +2128,9 @@ def calibrate_and_model_mixed(
     fix_degeneracies=False,
     degeneracy_iters=6,
     degeneracy_phase_ref=True,
+    delay_fringe_spectrum=False,
+    delay_fringe_times=8,
+    delay_fringe_taper="bh4",
     delay_cross_spectrum=False,
     delay_transfer=False,
     delay_transfer_ridge=1e-6,
@@ -2031,6 +2150,8 @@ def calibrate_and_model_mixed(
     _check_delay_spectrum(delay_spectrum, delay_spectrum_taper, delay_spectrum_max_dly, delay_spectrum_bllen_bin)
     _check_delay_transfer(delay_transfer, delay_transfer_ridge, delay_spectrum, fitting_kwargs.get("freeze_model", False))
     _check_delay_cross(delay_cross_spectrum, delay_spectrum, fitting_kwargs.get("batch_slices"), fitting_kwargs.get("init_guesses_from_previous_time_step", False))
+    _check_delay_fringe(delay_fringe_spectrum, delay_fringe_times, delay_fringe_taper, delay_spectrum, fitting_kwargs.get("batch_slices"),
+                        fitting_kwargs.get("init_guesses_from_previous_time_step", False))
     _check_degeneracy_call(fix_degeneracies, degeneracy_iters, fitting_kwargs)
     fitting_grps, blvecs, _, _ = modeling.get_uv_overlapping_grps_conjugated(
         uvdata, red_tol=red_tol, include_autos=include_autos, red_tol_freq=red_tol_freq, n_angle_bins=n_angle_bins,
@@ -2055,6 +2176,7 @@ def calibrate_and_model_mixed(
         notebook_progressbar=notebook_progressbar, use_redundancy=use_redundancy, delay_spectrum=delay_spectrum, delay_spectrum_taper=delay_spectrum_taper,
         delay_spectrum_max_dly=delay_spectrum_max_dly, delay_spectrum_bllen_bin=delay_spectrum_bllen_bin,
         delay_spectrum_calibrated=delay_spectrum_calibrated, delay_transfer=delay_transfer, delay_transfer_ridge=delay_transfer_ridge, delay_cross_spectrum=delay_cross_spectrum,
+            delay_fringe_spectrum=delay_fringe_spectrum, delay_fringe_times=delay_fringe_times, delay_fringe_taper=delay_fringe_taper,
             fix_degeneracies=fix_degeneracies, degeneracy_iters=degeneracy_iters,
         degeneracy_phase_ref=degeneracy_phase_ref, **fitting_kwargs,
     )
@@ -2169,6 +2291,9 @@ def read_calibrate_and_model_dpss(
     fix_degeneracies=False,
     degeneracy_iters=6,
     degeneracy_phase_ref=True,
+    delay_fringe_spectrum=False,
+    delay_fringe_times=8,
+    delay_fringe_taper="bh4",
     delay_cross_spectrum=False,
     delay_transfer=False,
     delay_transfer_ridge=1e-6,
@@ -2207,12 +2332,19 @@ def read_calibrate_and_model_dpss(
     ``[Npols, Ntimes]`` (the partner's time index; -1 for a slice without one), ``cross_nbls`` ``[Npols, Ntimes, nbins]``, ``cross_data``,
     ``cross_model``, ``cross_resid`` and ``cross_noise_data``, ``cross_noise_model``, ``cross_noise_resid`` ``[Npols, Ntimes, nbins, Ndelays]``
     (``nan`` for a slice without a partner) and, with ``"baselines"``, ``cross_antpairs`` and the same six with ``_bl`` ``[Npols, Ntimes, rows, Ndelays]``.
+    ``delay_fringe_spectrum``, ``delay_fringe_times``, ``delay_fringe_taper`` are ``calibrate_and_model_tensor``'s (Python keywords only);
+    the archive then also holds ``fringe_rates`` ``[Nrates]`` (Hz), ``fringe_window`` ``[Npols, Ntimes, delay_fringe_times]`` (the time
+    indices of the slice's window; -1 for a slice outside every window), ``fringe_nbls`` ``[Npols, Ntimes, nbins]``, ``fringe_data``,
+    ``fringe_model``, ``fringe_resid`` ``[Npols, Ntimes, nbins, Nrates, Ndelays]`` (``nan`` for a slice outside every window) and, with
+    ``"baselines"``, ``fringe_antpairs`` and the same three with ``_bl`` ``[Npols, Ntimes, rows, Nrates, Ndelays]``.
     ``fix_degeneracies``, ``degeneracy_iters``, ``degeneracy_phase_ref`` are ``calibrate_and_model_tensor``'s too (Python keywords only);
     the sky model is ``input_model_files`` and the written gains and model are the fixed ones.
     """
     _check_delay_spectrum(delay_spectrum, delay_spectrum_taper, delay_spectrum_max_dly, delay_spectrum_bllen_bin)
     _check_delay_transfer(delay_transfer, delay_transfer_ridge, delay_spectrum, calibration_kwargs.get("freeze_model", False))
     _check_delay_cross(delay_cross_spectrum, delay_spectrum, calibration_kwargs.get("batch_slices"), calibration_kwargs.get("init_guesses_from_previous_time_step", False))
+    _check_delay_fringe(delay_fringe_spectrum, delay_fringe_times, delay_fringe_taper, delay_spectrum, calibration_kwargs.get("batch_slices"),
+                        calibration_kwargs.get("init_guesses_from_previous_time_step", False))
     _check_degeneracy_call(fix_degeneracies, degeneracy_iters, dict(calibration_kwargs, sky_model=input_model_files))
     if delay_spectrum_outfile is not None and not delay_spectrum:
         raise ValueError("delay_spectrum_outfile needs delay_spectrum=True or 'baselines'")
@@ -2235,6 +2367,8 @@ def read_calibrate_and_model_dpss(
                     delay_spectrum_bllen_bin=delay_spectrum_bllen_bin, delay_spectrum_calibrated=delay_spectrum_calibrated) if delay_spectrum else {}),
             **(dict(delay_transfer=True, delay_transfer_ridge=delay_transfer_ridge) if delay_transfer else {}),
             **(dict(delay_cross_spectrum=delay_cross_spectrum) if delay_cross_spectrum else {}),
+            **(dict(delay_fringe_spectrum=delay_fringe_spectrum, delay_fringe_times=delay_fringe_times, delay_fringe_taper=delay_fringe_taper)
+               if delay_fringe_spectrum else {}),
             **(dict(fix_degeneracies=fix_degeneracies, degeneracy_iters=degeneracy_iters, degeneracy_phase_ref=degeneracy_phase_ref)
                if fix_degeneracies else {}),
             **(dict(gain_basis_errors=True) if gain_basis_errors else {}),
@@ -2319,12 +2453,32 @@ def delay_spectrum_tables(fit_info):
             for k in ("data", "model", "resid"):
                 out["cross_" + k + "_bl"] = np.full((len(pols), ntimes, len(cpairs), nd), np.nan)
                 out["cross_noise_" + k + "_bl"] = np.full((len(pols), ntimes, len(cpairs), nd), np.nan)
+    fringed = [e["fringe"] for e in entries if "fringe" in e]
+    if fringed:  # (nan, -1 and 0 groups for a slice outside every window)
+        nwin, nr = len(fringed[0]["time_indices"]), len(fringed[0]["fringe_rates"])
+        out["fringe_rates"] = np.array(fringed[0]["fringe_rates"], dtype=np.float64)
+        out["fringe_window"] = np.full((len(pols), ntimes, nwin), -1, dtype=np.int64)
+        out["fringe_nbls"] = np.zeros((len(pols), ntimes, nbins), dtype=np.int64)
+        for k in ("data", "model", "resid"):
+            out["fringe_" + k] = np.full((len(pols), ntimes, nbins, nr, nd), np.nan)
+        fpairs = list(fringed[0]["per_baseline"]) if "per_baseline" in fringed[0] else None
+        if fpairs is not None:
+            out["fringe_antpairs"] = np.asarray(fpairs, dtype=np.int64).reshape(-1, 2)
+            for k in ("data", "model", "resid"):
+                out["fringe_" + k + "_bl"] = np.full((len(pols), ntimes, len(fpairs), nr, nd), np.nan)
     for i, p in enumerate(pols):
         for t, h in fit_info[p].items():
             if "delay_spectrum" not in h:
                 continue
             e = h["delay_spectrum"]
             out["nbls"][i, t] = e["nbls"]
+            if "fringe" in e:
+                x = e["fringe"]
+                out["fringe_window"][i, t], out["fringe_nbls"][i, t] = x["time_indices"], x["nbls"]
+                for k in ("data", "model", "resid"):
+                    out["fringe_" + k][i, t] = x[k]
+                    if "per_baseline" in x:
+                        out["fringe_" + k + "_bl"][i, t] = [x["per_baseline"][ap][k] for ap in fpairs]
             if "cross" in e:
                 x = e["cross"]
                 out["cross_partner"][i, t], out["cross_nbls"][i, t] = x["partner_time_index"], x["nbls"]

@@ -34,6 +34,7 @@
 #include "gain_error_kernels.hpp"
 #include "delay_spectrum_kernels.hpp"
 #include "delay_cross_kernels.hpp"
+#include "delay_fringe_kernels.hpp"
 #include "delay_transfer_kernels.hpp"
 #include "degeneracy_kernels.hpp"
 #include "gain_basis_solve_kernels.hpp"
@@ -194,6 +195,8 @@ struct cal_solver {
   virtual int set_delay_spectrum_scratch(int64_t bytes) = 0;
   virtual int delay_cross_spectrum(const cal_delay_cross_desc* d, const void* g_r, const void* g_i, double* cross_pair, double* diff_pair, double* norm_pair,
                                    double* cross_bin, double* diff_bin, double* count_bin) = 0;
+  virtual int delay_fringe_spectrum(const cal_delay_fringe_desc* d, const void* g_r, const void* g_i, double* power_grp, double* norm_grp, double* power_bin,
+                                    double* count_bin) = 0;
   virtual int delay_transfer(const cal_delay_transfer_desc* d, const void* g_r, const void* g_i, double* absorbed_bl, double* noise_bl, double* absorbed_bin,
                              double* count_bin, cal_fit_errors_counts* counts) = 0;
   virtual int set_delay_transfer_scratch(int64_t bytes) = 0;
@@ -293,6 +296,9 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
   int64_t ds_bound = kCsScratchDefault;        // bytes of scratch a chunk of rows may take (set_delay_spectrum_scratch)
   // delay_cross_spectrum (delay_cross_kernels.hpp) reuses them all, with chunks of pairs; the pairs and their scales of a call
   DevBuf dc_pairs, dc_scale;
+  // delay_fringe_spectrum (delay_fringe_kernels.hpp) reuses them all as well, with chunks of whole groups: the rows of the groups in
+  // dc_pairs, their scales in dc_scale, Y and then the power in ds_pow; opt_r | opt_i of a call
+  DevBuf df_opt;
   // delay_transfer (delay_transfer_kernels.hpp): the plan of a call (groups, order, Gram work, W offsets, runs, rows, the bins' lists and
   // the operator image); per chunk N (dt_n), the factor (dt_d) and W | S (dt_x); rhs of the Gram kernel (unused), coeff_var of the factor
   // kernel (unused), ok [ngrps] ints + the two counters; absorbed and noise [nbls][ndelays]; valid | absorbed_bin | count_bin (dt_out; the
@@ -665,7 +671,7 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     CAL_TRY(upload(ant_ptr, p.ant_ptr));
     CAL_TRY(upload(ant_ent, p.ant_ent));
 
-    for (DevBuf* b : {&gains_snap, &gains_alt, &coef_snap, &q1, &gcp1, &gc1, &model_buf, &scratch, &fq_out, &fq_gains, &gs_out, &gs_ptr, &gs_ent, &gs_mask, &cs_rhs, &rw_w0, &rw_out, &ds_op, &ds_normf, &ds_ent, &ds_ptr, &ds_x, &ds_pow, &ds_out, &dc_pairs, &dc_scale, &dt_grp, &dt_order, &dt_work, &dt_woff, &dt_runs, &dt_rows, &dt_ent, &dt_ptr, &dt_op, &dt_n, &dt_d, &dt_x, &dt_rhs, &dt_cv, &dt_ok, &dt_abs, &dt_noise, &dt_out, &dg_z, &dg_w, &dg_geo, &dg_idx, &dg_part, &dg_st, &dg_gout, &dg_gref,
+    for (DevBuf* b : {&gains_snap, &gains_alt, &coef_snap, &q1, &gcp1, &gc1, &model_buf, &scratch, &fq_out, &fq_gains, &gs_out, &gs_ptr, &gs_ent, &gs_mask, &cs_rhs, &rw_w0, &rw_out, &ds_op, &ds_normf, &ds_ent, &ds_ptr, &ds_x, &ds_pow, &ds_out, &dc_pairs, &dc_scale, &df_opt, &dt_grp, &dt_order, &dt_work, &dt_woff, &dt_runs, &dt_rows, &dt_ent, &dt_ptr, &dt_op, &dt_n, &dt_d, &dt_x, &dt_rhs, &dt_cv, &dt_ok, &dt_abs, &dt_noise, &dt_out, &dg_z, &dg_w, &dg_geo, &dg_idx, &dg_part, &dg_st, &dg_gout, &dg_gref,
                        &gn_s, &gn_g0, &gn_save, &gn_x, &gn_res, &gn_ns, &gn_D, &gn_m, &gn_sd, &gn_rows, &gn_part, &gn_scal, &gn_lam, &gn_grp, &gn_rowptr,
                        &lb_vec, &lb_part, &lb_dots, &lb_state, &lb_losses, &lb_count})
       b->release();
@@ -1993,6 +1999,82 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     CAL_TRY(give(norm_pair, o_norm, (size_t)np));
     CAL_TRY(give(cross_bin, o_sbin, nbin_stat));
     CAL_TRY(give(diff_bin, o_sbin + ((d->stats & 1) ? nbin_stat : 0), nbin_stat));
+    CAL_TRY(give(count_bin, o_cbin, (size_t)nbins));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return CAL_OK;
+  }
+
+  // cal_solver_delay_fringe_spectrum: the model pass of model(), then per chunk of whole groups dfringe_rows_kernel,
+  // dfringe_transform_kernel, dfringe_time_kernel (delay_fringe_kernels.hpp) and dspec_bin_kernel as it is, over groups instead of rows
+  // and with nrates ndelays columns.  The buffers are those of delay_spectrum and the bound is ds_bound.
+  int delay_fringe_spectrum(const cal_delay_fringe_desc* d, const void* g_r, const void* g_i, double* power_grp, double* norm_grp, double* power_bin,
+                            double* count_bin) override {
+    HIP_TRY(hipSetDevice(device));
+    if (!d) return fail(CAL_ERR_INVALID, "delay_fringe_spectrum: null description");
+    CAL_TRY(require_set("delay_fringe_spectrum", false));
+    const T2* g = nullptr;
+    CAL_TRY(report_gains("delay_fringe_spectrum", g_r, g_i, &g));
+    if (d->ndelays < 1 || d->ndelays > 4096) return fail(CAL_ERR_INVALID, "delay_fringe_spectrum: ndelays = %d lies outside [1, 4096]", d->ndelays);
+    if ((d->what & 7) == 0 || (d->what & ~7))
+      return fail(CAL_ERR_INVALID, "delay_fringe_spectrum: what = %d: bits 0 (data), 1 (model), 2 (residual), at least one", d->what);
+    if (d->calibrated != 0 && d->calibrated != 1) return fail(CAL_ERR_INVALID, "delay_fringe_spectrum: calibrated = %d (0 or 1)", d->calibrated);
+    if (!d->op_r || !d->op_i || !d->norm_f) return fail(CAL_ERR_INVALID, "delay_fringe_spectrum: null operator or norm_f");
+    if (d->nbins < 0) return fail(CAL_ERR_INVALID, "delay_fringe_spectrum: nbins = %d", d->nbins);
+    if ((d->nbins == 0) != (d->bin_of_group == nullptr)) return fail(CAL_ERR_INVALID, "delay_fringe_spectrum: bin_of_group goes with nbins > 0, and only with it");
+    if (d->nbins == 0 && (power_bin || count_bin)) return fail(CAL_ERR_INVALID, "delay_fringe_spectrum: binned outputs need nbins > 0");
+    DelayFringePlan<T> P;  // the refusals of groups, rows, scales and opt; the bins' groups, the chunks, the operator image (report_plan.hpp)
+    CAL_TRY(plan_delay_fringe(nbls, nfreqs, fpad, d, ds_bound, P));
+    const int nd = d->ndelays, nbins = d->nbins, ng = d->ngroups, nt = d->ntimes, nr = d->nrates, nq = P.nq, xpitch = P.xpitch, ndpad = P.ndpad,
+              cgroups = P.cgroups;
+    CAL_TRY(put(ds_op, P.image, false));
+    CAL_TRY(put(ds_normf, P.norm_f, false));
+    CAL_TRY(put(dc_scale, P.scale, false));
+    CAL_TRY(put(df_opt, P.opt, false));
+    CAL_TRY(dc_pairs.reserve((size_t)ng * nt * sizeof(int32_t), false));
+    HIP_TRY(copy_sync(dc_pairs.p, d->rows, (size_t)ng * nt * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (nbins) {
+      CAL_TRY(put(ds_ent, P.bin_ent, false));
+      CAL_TRY(put(ds_ptr, P.chunk_ptr, false));
+    }
+    CAL_TRY(ds_out.reserve(P.n_out * sizeof(double)));
+    CAL_TRY(ds_x.reserve(P.n_x * sizeof(T), false));
+    CAL_TRY(ds_pow.reserve((P.n_y + P.n_pow) * sizeof(double), false));
+    const int ncols = nr * nd;                          // columns of a group's power: [nrates][ndelays]
+    const size_t nbin_out = P.n_out - ng;               // power_bin | count_bin: the exchange payload
+    double* o_norm = ds_out.as<double>();
+    double* o_pbin = o_norm + ng;
+    double* o_cbin = o_pbin + (size_t)nq * nbins * ncols;
+    double* y = ds_pow.as<double>();
+    double* pw = y + P.n_y;
+    const double* opt_r = df_opt.as<double>();
+    const double* opt_i = opt_r + (size_t)nt * nr;
+    const size_t time_lds = (size_t)nt * 2 * kDfCols * sizeof(double);
+    hipError_t copy_err = hipSuccess;
+    CAL_TRY(model_pass(2, [&](T* model_r, T* model_i, T*) {
+      for (int c = 0; c < P.nchunks; ++c) {
+        const long long g0 = (long long)c * cgroups;
+        const int nc = (int)std::min<long long>(cgroups, ng - g0);
+        const int nrows = nc * nt;
+        hipLaunchKernelGGL(dfringe_rows_kernel<T>, dim3((nc + 3) / 4), dim3(256), 0, stream, model_r, model_i, data_r.as<T>(), data_i.as<T>(), wgts.as<T>(), g,
+                           bl_ant.as<int2>(), dc_pairs.as<int>() + g0 * nt, ds_normf.as<double>(), nc, nt, nfreqs, fpad, xpitch, d->what, d->calibrated,
+                           ds_x.as<T>(), o_norm + g0);
+        hipLaunchKernelGGL(dfringe_transform_kernel<T>, dim3((nrows + kDsRows - 1) / kDsRows, ndpad / kDsCols, nq), dim3(256), 0, stream, ds_x.as<T>(),
+                           ds_op.as<T>(), dc_scale.as<double>() + g0 * nt, nrows, xpitch, nd, ndpad, y);
+        hipLaunchKernelGGL(dfringe_time_kernel, dim3(nc, (nd + kDfCols - 1) / kDfCols, nq), dim3(256), time_lds, stream, y, opt_r, opt_i, o_norm + g0, nc, nt,
+                           nr, nd, pw);
+        if (nbins)
+          hipLaunchKernelGGL(dspec_bin_kernel, dim3(nbins, (ncols + 255) / 256, nq), dim3(256), 0, stream, pw, o_norm + g0,
+                             ds_ptr.as<int>() + (size_t)c * nbins * 2, ds_ent.as<int>(), (int)g0, nc, ncols, nbins, c == 0 ? 1 : 0, o_pbin, o_cbin);
+        for (int q = 0; q < nq && power_grp && copy_err == hipSuccess; ++q)  // (the stream orders the copy before the next chunk's kernels)
+          copy_err = hipMemcpyAsync(power_grp + ((size_t)q * ng + g0) * ncols, pw + (size_t)q * nc * ncols, (size_t)nc * ncols * sizeof(double),
+                                    hipMemcpyDeviceToHost, stream);
+      }
+    }));
+    HIP_TRY(copy_err);
+    // the bins of every rank's groups add up to the array's: ONE all-reduce of nwhat nbins nrates ndelays + nbins doubles
+    if (nbins && comm_on()) CAL_TRY(all_reduce(o_pbin, nbin_out, CAL_XCHG_F64, CAL_XCHG_SUM));
+    CAL_TRY(give(norm_grp, o_norm, (size_t)ng));
+    CAL_TRY(give(power_bin, o_pbin, (size_t)nq * nbins * ncols));
     CAL_TRY(give(count_bin, o_cbin, (size_t)nbins));
     HIP_TRY(hipStreamSynchronize(stream));
     return CAL_OK;
@@ -3442,6 +3524,23 @@ int debug_report_plan(const cal_problem_desc* d, const cal_report_plan_desc* r, 
     }
     return give(P.scale);
   }
+  if (what >= 70 && what <= 76) {
+    const cal_delay_fringe_desc* x = r->fringe;
+    if (!x || x->ndelays < 1 || (x->what & 7) == 0 || (x->what & ~7) || x->nbins < 0 || (x->nbins == 0) != (x->bin_of_group == nullptr) || !x->op_r || !x->op_i ||
+        !x->norm_f || r->scratch_bytes < 0)
+      return fail(CAL_ERR_INVALID, "%s: what = %d takes a fringe description cal_solver_delay_fringe_spectrum would plan for, and a bound >= 0", who, what);
+    DelayFringePlan<T> P;
+    CAL_TRY(plan_delay_fringe(p.nbls, p.nfreqs, p.fpad, x, r->scratch_bytes == 0 ? kCsScratchDefault : r->scratch_bytes, P));
+    switch (what) {
+      case 70: return give(std::vector<int64_t>{P.nq, P.xpitch, P.ndpad, P.cgroups, P.nchunks, (int64_t)P.n_x, (int64_t)(P.n_y + P.n_pow), (int64_t)P.n_out});
+      case 71: return give(P.bin_ent);
+      case 72: return give(P.chunk_ptr);
+      case 73: return give(P.image);
+      case 74: return give(P.norm_f);
+      case 75: return give(P.scale);
+    }
+    return give(P.opt);
+  }
   return fail(CAL_ERR_INVALID, "%s: what = %d", who, what);
 }
 }  // namespace
@@ -4122,6 +4221,11 @@ int cal_solver_delay_cross_spectrum(cal_solver* s, const cal_delay_cross_desc* d
                                     double* norm_pair, double* cross_bin, double* diff_bin, double* count_bin) {
   NEED(s);
   return s->delay_cross_spectrum(desc, g_r, g_i, cross_pair, diff_pair, norm_pair, cross_bin, diff_bin, count_bin);
+}
+int cal_solver_delay_fringe_spectrum(cal_solver* s, const cal_delay_fringe_desc* desc, const void* g_r, const void* g_i, double* power_grp, double* norm_grp,
+                                     double* power_bin, double* count_bin) {
+  NEED(s);
+  return s->delay_fringe_spectrum(desc, g_r, g_i, power_grp, norm_grp, power_bin, count_bin);
 }
 int cal_solver_delay_transfer(cal_solver* s, const cal_delay_transfer_desc* desc, const void* g_r, const void* g_i, double* absorbed_bl, double* noise_bl,
                               double* absorbed_bin, double* count_bin, cal_fit_errors_counts* counts) {

@@ -21,6 +21,8 @@ shared Gram and Cholesky core of normal_solve.hpp; the second is the factor step
 two waves per SIMD in the transform kernel.
 `dcross_rows_kernel`, `dcross_transform_kernel` (delay_cross_kernels.hpp), both dtypes: no scratch, no spilled VGPRs, and two waves per
 SIMD in the transform kernel.
+`dfringe_rows_kernel`, `dfringe_transform_kernel` (both dtypes), `dfringe_time_kernel` (delay_fringe_kernels.hpp): no scratch, no spilled
+VGPRs, two waves per SIMD in the transform kernel and in the time kernel (two workgroups of four waves per CU at 64 times).
 `dtransfer_basis_kernel`, `dtransfer_power_kernel` (delay_transfer_kernels.hpp), both dtypes: no scratch, no spilled VGPRs, and two waves
 per SIMD in the power kernel.
 `degen_rows_kernel`, `degen_sum_kernel`, `degen_solve_kernel`, `degen_phase_kernel`, `degen_apply_gains_kernel`, `degen_apply_rows_kernel`
@@ -91,6 +93,16 @@ for line in sys.stdin:
         m = re.search(r"remark:\s+(ScratchSize \[bytes/lane\]|VGPRs Spill|Occupancy \[waves/SIMD\]): (\d+)", line)
         if m and m.group(1).startswith("Occupancy"):
             if "dcross_transform_kernel" in cur and int(m.group(2)) < 2:
+                bad.append(f"{cur}: occupancy {m.group(2)} waves/SIMD (< 2)")
+        elif m and int(m.group(2)) != 0:
+            bad.append(f"{cur}: {m.group(1)} = {m.group(2)}")
+        continue
+    if cur is not None and any(k in cur for k in ("dfringe_rows_kernel", "dfringe_transform_kernel", "dfringe_time_kernel")):
+        # the three of the delay / fringe-rate spectrum: no scratch, no spilled VGPRs; the transform runs the spectrum's loop and keeps its
+        # two waves per SIMD in both dtypes; the time kernel's LDS admits two workgroups per CU at 64 times, and its registers must too
+        m = re.search(r"remark:\s+(ScratchSize \[bytes/lane\]|VGPRs Spill|Occupancy \[waves/SIMD\]): (\d+)", line)
+        if m and m.group(1).startswith("Occupancy"):
+            if ("dfringe_transform_kernel" in cur or "dfringe_time_kernel" in cur) and int(m.group(2)) < 2:
                 bad.append(f"{cur}: occupancy {m.group(2)} waves/SIMD (< 2)")
         elif m and int(m.group(2)) != 0:
             bad.append(f"{cur}: {m.group(1)} = {m.group(2)}")

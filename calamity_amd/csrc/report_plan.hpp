@@ -1,5 +1,5 @@
-// report_plan.hpp -- what the post-fit reports cal_solver_delay_spectrum, cal_solver_delay_cross_spectrum, cal_solver_delay_transfer and
-// cal_solver_fix_degeneracies decide
+// report_plan.hpp -- what the post-fit reports cal_solver_delay_spectrum, cal_solver_delay_cross_spectrum, cal_solver_delay_fringe_spectrum,
+// cal_solver_delay_transfer and cal_solver_fix_degeneracies decide
 // before they launch, on the host alone: the rows of every bin and of every slice, how they are cut into chunks and segments, and the padded images the kernels read.
 // No HIP or RCCL runtime call and no solver: SolverT uploads these plans at every call; cal_debug_report_plan returns them as bytes
 // (tests/test_report_plan_host.py).  dspec_bin_kernel adds a bin's rows, and degen_sum_kernel a slice's segments, in the order written
@@ -10,6 +10,7 @@
 #include "solve_plan.hpp"
 #include "delay_spectrum_kernels.hpp"
 #include "delay_cross_kernels.hpp"
+#include "delay_fringe_kernels.hpp"
 #include "delay_transfer_kernels.hpp"
 #include "degeneracy_kernels.hpp"
 
@@ -157,6 +158,85 @@ int plan_delay_cross(int nbls, int nfreqs, int fpad, const cal_delay_cross_desc*
   P.n_x = (size_t)P.nq * 2 * 2 * cpairs * P.xpitch;
   P.n_pow = (size_t)P.nstat * P.nq * cpairs * nd;
   P.n_out = (size_t)np + (size_t)P.nstat * P.nq * nbins * nd + nbins;
+  return CAL_OK;
+}
+
+// ---- cal_solver_delay_fringe_spectrum ----------------------------------------------------------------------------------------------
+template <typename T>
+struct DelayFringePlan {
+  int nq = 0;                    // quantities asked for: the bits of `what`
+  int xpitch = 0, ndpad = 0;     // row pitch of the masked planes, columns of the operator image
+  int cgroups = 0, nchunks = 0;  // whole groups per chunk (the last may hold fewer)
+  std::vector<int> bin_ent;      // the sorted group list of every bin, one after the other (plan_bin_lists)
+  std::vector<int> chunk_ptr;    // [nchunks][nbins][2]: a bin's piece of a chunk as positions in bin_ent
+  std::vector<T> image;          // [re, im][xpitch][ndpad]: the operator, zero beyond nfreqs and ndelays
+  std::vector<double> norm_f;    // [xpitch], zero beyond nfreqs
+  std::vector<double> scale;     // [ngroups][ntimes]: the description's, or ones
+  std::vector<double> opt;       // opt_r | opt_i, [ntimes][nrates] each
+  size_t n_x = 0, n_y = 0, n_pow = 0, n_out = 0;  // elements of ds_x (T), of Y and of the power (both in ds_pow, double) and of ds_out
+                                                  // (norm_grp | power_bin | count_bin)
+};
+
+// A chunk of whole groups' scratch -- per group nq 2 T xpitch elements of T for the masked planes, nq 2 T ndelays doubles of Y and
+// nq nrates ndelays doubles of power -- stays under `bound` bytes (never less than one group).  Everything of the description that can
+// be refused on the host is refused here: ngroups, ntimes, nrates, the rows, the scales, opt, the bins.
+template <typename T>
+int plan_delay_fringe(int nbls, int nfreqs, int fpad, const cal_delay_fringe_desc* d, int64_t bound, DelayFringePlan<T>& P) {
+  const int nd = d->ndelays, nbins = d->nbins, ng = d->ngroups, nt = d->ntimes, nr = d->nrates;
+  if (ng < 1) return fail(CAL_ERR_INVALID, "delay_fringe_spectrum: ngroups = %d (at least 1)", ng);
+  if (nt < 1 || nt > 64) return fail(CAL_ERR_INVALID, "delay_fringe_spectrum: ntimes = %d lies outside [1, 64]", nt);
+  if (nr < 1 || nr > 64) return fail(CAL_ERR_INVALID, "delay_fringe_spectrum: nrates = %d lies outside [1, 64]", nr);
+  if (!d->rows) return fail(CAL_ERR_INVALID, "delay_fringe_spectrum: null rows");
+  if (!d->opt_r || !d->opt_i) return fail(CAL_ERR_INVALID, "delay_fringe_spectrum: null opt");
+  const size_t nrow = (size_t)ng * nt;
+  if (nrow > (size_t)(1u << 30)) return fail(CAL_ERR_INVALID, "delay_fringe_spectrum: ngroups ntimes = %lld is too many", (long long)nrow);
+  for (size_t k = 0; k < nrow; ++k)
+    if (d->rows[k] < 0 || d->rows[k] >= nbls)
+      return fail(CAL_ERR_INVALID, "delay_fringe_spectrum: rows[%d][%d] = %d lies outside [0, %d)", (int)(k / nt), (int)(k % nt), d->rows[k], nbls);
+  P.scale.assign(nrow, 1.0);
+  if (d->scale) {
+    for (size_t k = 0; k < nrow; ++k)
+      if (!std::isfinite(d->scale[k])) return fail(CAL_ERR_INVALID, "delay_fringe_spectrum: scale[%d][%d] is not finite", (int)(k / nt), (int)(k % nt));
+    std::copy(d->scale, d->scale + nrow, P.scale.begin());
+  }
+  const size_t nopt = (size_t)nt * nr;
+  for (size_t k = 0; k < nopt; ++k)
+    if (!std::isfinite(d->opt_r[k]) || !std::isfinite(d->opt_i[k]))
+      return fail(CAL_ERR_INVALID, "delay_fringe_spectrum: opt[%d][%d] is not finite", (int)(k / nr), (int)(k % nr));
+  P.opt.resize(2 * nopt);
+  std::copy(d->opt_r, d->opt_r + nopt, P.opt.begin());
+  std::copy(d->opt_i, d->opt_i + nopt, P.opt.begin() + nopt);
+  P.nq = (d->what & 1) + (d->what >> 1 & 1) + (d->what >> 2 & 1);
+  if ((long long)P.nq * nbins * nr * nd + nbins > (1ll << 31) - 1) return fail(CAL_ERR_INVALID, "delay_fringe_spectrum: nbins = %d is too many", nbins);
+  for (int g = 0; g < ng && nbins; ++g)
+    if (d->bin_of_group[g] < -1 || d->bin_of_group[g] >= nbins)
+      return fail(CAL_ERR_INVALID, "delay_fringe_spectrum: bin_of_group[%d] = %d lies outside [-1, %d)", g, d->bin_of_group[g], nbins);
+  std::vector<int> bin_ptr;
+  CAL_TRY(plan_bin_lists("delay_fringe_spectrum", ng, nbins, d->bin_of_group, bin_ptr, P.bin_ent));
+  P.xpitch = ds_xpitch(fpad);
+  P.ndpad = ds_ndpad(nd);
+  const size_t group_bytes = (size_t)P.nq * 2 * nt * P.xpitch * sizeof(T) + (size_t)P.nq * 2 * nt * nd * sizeof(double) + (size_t)P.nq * nr * nd * sizeof(double);
+  long long cgroups = std::max<long long>(1, bound / (long long)group_bytes);
+  cgroups = std::min<long long>(cgroups, ng);  // (ngroups ntimes fits an int: so do a chunk's rows)
+  P.cgroups = (int)cgroups;
+  P.nchunks = (int)((ng + cgroups - 1) / cgroups);
+  P.chunk_ptr.resize((size_t)P.nchunks * nbins * 2);
+  for (int c = 0; c < P.nchunks && nbins; ++c) {
+    const long long g0 = c * cgroups, g1 = std::min<long long>(ng, g0 + cgroups);
+    for (int n = 0; n < nbins; ++n) {
+      const int* e0 = P.bin_ent.data() + bin_ptr[n];
+      const int* e1 = P.bin_ent.data() + bin_ptr[n + 1];
+      P.chunk_ptr[((size_t)c * nbins + n) * 2] = (int)(std::lower_bound(e0, e1, (int)g0) - P.bin_ent.data());
+      P.chunk_ptr[((size_t)c * nbins + n) * 2 + 1] = (int)(std::lower_bound(e0, e1, (int)g1) - P.bin_ent.data());
+    }
+  }
+  plan_operator_image<T>(nfreqs, nd, P.xpitch, P.ndpad, d->op_r, d->op_i, P.image);
+  P.norm_f.assign((size_t)P.xpitch, 0.0);
+  std::copy(d->norm_f, d->norm_f + nfreqs, P.norm_f.begin());
+  P.n_x = (size_t)P.nq * 2 * cgroups * nt * P.xpitch;
+  P.n_y = (size_t)P.nq * 2 * cgroups * nt * nd;
+  P.n_pow = (size_t)P.nq * cgroups * nr * nd;
+  P.n_out = (size_t)ng + (size_t)P.nq * nbins * nr * nd + nbins;
   return CAL_OK;
 }
 

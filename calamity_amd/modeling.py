@@ -315,6 +315,38 @@ def delay_transform(freqs, taper="bh4", max_delay_ns=None):
     return op, t * t, delays_ns
 
 
+def fringe_rate_transform(ntimes, dt, taper="bh4", rates=None):
+    """The tapered discrete Fourier transform along time as a matrix, for ``HipFitSolver.delay_fringe_spectrum``:
+    ``(opt [ntimes, nrates] complex128, rates_hz [nrates])`` with NumPy's FFT sign,
+
+        opt[t, r] = w_t exp(-2 pi i rate_r t dt) / sqrt(sum_t w_t^2)
+
+    so that ``sum_t |opt[t, r]|^2 = 1`` at every rate: white noise of unit variance in every row has expected power 1 per rate, and a
+    signal constant in time sits at rate 0.  ``dt``: the spacing of the integrations in seconds.  ``rates=None`` gives all ``ntimes``
+    rates of the grid in ascending order, ``rate_r = (r - ntimes // 2) / (ntimes dt)`` (``y @ opt`` along time is then
+    ``np.fft.fftshift(np.fft.fft(w * y)) / sqrt(sum w^2)``); a sequence of rates in Hz gives those columns instead (1 to 64 of them).
+    ``taper``: see ``delay_taper``."""
+    n = int(ntimes)
+    if n < 1 or n > 64:
+        raise ValueError(f"fringe_rate_transform takes between 1 and 64 times, got {ntimes!r}")
+    dt = float(dt)
+    if not (np.isfinite(dt) and dt > 0.0):
+        raise ValueError(f"dt must be a spacing > 0 in seconds, got {dt!r}")
+    w = delay_taper(n, taper)
+    w = w / np.sqrt(np.sum(w * w))
+    if rates is None:
+        rp = np.arange(n) - n // 2
+        rates_hz = rp / (n * dt)
+        # (t r' mod ntimes taken in integers: the phase stays exact)
+        phase = (np.outer(np.arange(n), rp) % n).astype(np.float64) / n
+    else:
+        rates_hz = np.asarray(rates, dtype=np.float64).ravel()
+        if len(rates_hz) < 1 or len(rates_hz) > 64 or not np.all(np.isfinite(rates_hz)):
+            raise ValueError("rates must hold between 1 and 64 finite fringe rates in Hz")
+        phase = np.outer(np.arange(n) * dt, rates_hz)
+    return w[:, None] * np.exp(-2j * np.pi * phase), rates_hz
+
+
 def get_redundant_grps_data(uvdata, remove_redundancy=False, tol=1.0, include_autos=False):
     """Redundant groups of the antenna pairs that carry data -- same arguments and return tuple as modeling.py:10-81:
     ``(antpairs, red_grps, vec_bin_centers, lengths)`` with one bin centre / length per returned group.

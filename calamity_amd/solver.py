@@ -507,6 +507,82 @@ class HipFitSolver:
             out["per_pair"] = {k: {q: pp[k][i] for i, q in enumerate(names)} for k in snames}
         return out
 
+    def delay_fringe_spectrum(self, op, norm_f, rows, opt, scale=None, what=("data", "model", "resid"), calibrated=False,
+                              bin_of_group=None, nbins=0, per_group=False, g_r=None, g_i=None):
+        """The delay / fringe-rate plane (cal_solver_delay_fringe_spectrum): the delay transform of groups of ``T`` rows -- one
+        baseline at ``T`` integrations, held as rows of this solver -- and then a transform along time.  Instrument-locked residuals
+        sit at fringe rate 0, the sky at the rate its baseline gives it, noise is white in fringe rate.  ``op``, ``norm_f``, ``what``,
+        ``calibrated``, ``g_r``, ``g_i``: as in ``delay_spectrum``.  ``rows`` ``[ngroups, T]`` row indices (repeats allowed), ``T`` in
+        ``[1, 64]``; ``opt`` ``[T, nrates]`` complex, ``nrates`` in ``[1, 64]``: the transform along time with its taper and
+        normalisation folded in (``modeling.fringe_rate_transform``); ``scale`` ``[ngroups, T]`` (``None``: ones) puts the rows into
+        common units before they are combined.  For group ``g``::
+
+            mask_g     = AND over t of (w[rows[g][t]] != 0)            the COMMON mask of all T rows
+            X_q[g][t]  = (mask_g q[rows[g][t]]) @ op                   products in the solver's dtype, on the matrix cores
+            Y_t        = scale[g][t] X_q[g][t]                         in float64
+            Z_q[g][r]  = sum_t opt[t][r] Y_t                           in float64, t ascending
+            norm_grp   = sum_f mask_g norm_f
+            power      = |Z|^2 / norm_grp                              0 where norm_grp == 0
+
+        A group with one row flagged throughout has ``norm_grp == 0``, power 0, and enters no bin.  ``bin_of_group`` ``[ngroups]``
+        integers in ``[-1, nbins)``: the entry ``out[quantity]`` is then ``[nbins, nrates, ndelays]``, the SUM over the bin's groups
+        with ``norm_grp > 0`` in ascending order, and ``"count_bin"`` their number.  ``per_group=True`` adds
+        ``"per_group": {quantity: [ngroups, nrates, ndelays]}``.  ``"norm_grp"`` is always returned.  All float64; sums in a fixed
+        order: two calls give the same bits.  Nothing the fit reads changes.  Under an exchange the binned arrays are summed over the
+        ranks (one all-reduce); the per-group arrays stay this rank's own."""
+        if (g_r is None) != (g_i is None):
+            raise ValueError("give both g_r and g_i, or neither")
+        what = (what,) if isinstance(what, str) else tuple(what)
+        if not what or any(q not in _lib.DELAY_SPECTRUM_WHAT for q in what) or len(set(what)) != len(what):
+            raise ValueError(f"what must name one or more of {sorted(_lib.DELAY_SPECTRUM_WHAT)} once each, got {what!r}")
+        names = [q for q in ("data", "model", "resid") if q in what]  # the library's order
+        op = np.asarray(op)
+        if op.ndim != 2 or op.shape[0] != self.nfreqs:
+            raise ValueError(f"op must be [nfreqs = {self.nfreqs}, ndelays], got shape {op.shape}")
+        nd = op.shape[1]
+        op_r, op_i = self._real(op.real), self._real(op.imag)
+        norm_f = np.ascontiguousarray(norm_f, dtype=np.float64)
+        if norm_f.shape != (self.nfreqs,):
+            raise ValueError(f"norm_f must be [nfreqs = {self.nfreqs}], got shape {norm_f.shape}")
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        if rows.ndim != 2 or rows.shape[0] < 1 or rows.shape[1] < 1:
+            raise ValueError(f"rows must be [ngroups >= 1, ntimes >= 1], got shape {rows.shape}")
+        ngroups, ntimes = rows.shape
+        opt = np.asarray(opt, dtype=np.complex128)
+        if opt.ndim != 2 or opt.shape[0] != ntimes or opt.shape[1] < 1:
+            raise ValueError(f"opt must be [ntimes = {ntimes}, nrates >= 1], got shape {opt.shape}")
+        nrates = opt.shape[1]
+        opt_r, opt_i = np.ascontiguousarray(opt.real), np.ascontiguousarray(opt.imag)
+        if scale is not None:
+            scale = np.ascontiguousarray(scale, dtype=np.float64)
+            if scale.shape != (ngroups, ntimes):
+                raise ValueError(f"scale must be [ngroups = {ngroups}, ntimes = {ntimes}], got shape {scale.shape}")
+        nbins = int(nbins)
+        if (bin_of_group is None) != (nbins == 0):
+            raise ValueError("give bin_of_group and nbins > 0 together, or neither")
+        bins = None
+        if bin_of_group is not None:
+            bins = np.ascontiguousarray(bin_of_group, dtype=np.int32)
+            if bins.shape != (ngroups,):
+                raise ValueError(f"bin_of_group must be [ngroups = {ngroups}], got shape {bins.shape}")
+        gs = (self.nants, self.nfreqs)
+        a = None if g_r is None else self._real(g_r, gs)
+        b = None if g_i is None else self._real(g_i, gs)
+        d = _lib.DelayFringeDesc(nd, sum(_lib.DELAY_SPECTRUM_WHAT[q] for q in names), int(bool(calibrated)), ngroups, ntimes, nrates, rows.ctypes.data,
+                                 None if scale is None else scale.ctypes.data, nbins, None if bins is None else bins.ctypes.data, op_r.ctypes.data,
+                                 op_i.ctypes.data, norm_f.ctypes.data, opt_r.ctypes.data, opt_i.ctypes.data)
+        norm_grp = np.empty(ngroups, dtype=np.float64)
+        p_grp = np.empty((len(names), ngroups, nrates, nd), dtype=np.float64) if per_group else None
+        p_bin = np.empty((len(names), nbins, nrates, nd), dtype=np.float64) if nbins else None
+        c_bin = np.empty(nbins, dtype=np.float64) if nbins else None
+        _lib.check(self._lib.cal_solver_delay_fringe_spectrum(self._h, C.byref(d), _ptr(a), _ptr(b), _ptr(p_grp), _ptr(norm_grp), _ptr(p_bin), _ptr(c_bin)))
+        out = {"norm_grp": norm_grp}
+        if nbins:
+            out.update({q: p_bin[i] for i, q in enumerate(names)}, count_bin=c_bin)
+        if per_group:
+            out["per_group"] = {q: p_grp[i] for i, q in enumerate(names)}
+        return out
+
     def delay_transfer(self, op, ridge=1e-6, calibrated=False, bin_of_bl=None, nbins=0, per_baseline=False, g_r=None, g_i=None):
         """The signal loss of the fit in delay space (cal_solver_delay_transfer): the share of the power at every delay that the
         coefficient fit itself removes.  ``op`` ``[nfreqs, ndelays]`` complex: the operator of ``delay_spectrum``.  With

@@ -244,7 +244,14 @@ int cal_debug_solve_plan(int dtype, const cal_problem_desc* d, int64_t scratch_b
  *   60: int64 nwhat, nstat, the row pitch of the masked planes, the columns of the operator image, pairs per chunk, chunks, the elements
  *   of the chunk's planes (dtype), of its statistics (double) and of norm_pair | cross_bin | diff_bin | count_bin; 61: the bins' sorted
  *   pair lists, one after the other; 62: [chunks][nbins][2] a bin's piece of a chunk as positions in 61; 63: the operator image
- *   [re, im][pitch][columns] (dtype); 64: norm_f padded to the pitch (double); 65: the scales [npairs][2] (double; ones for NULL). */
+ *   [re, im][pitch][columns] (dtype); 64: norm_f padded to the pitch (double); 65: the scales [npairs][2] (double; ones for NULL).
+ * what = 70 .. 76: the plan of cal_solver_delay_fringe_spectrum for r->fringe (every field is read; the operator in `dtype`) and the
+ *   bound r->scratch_bytes of cal_solver_set_delay_spectrum_scratch (0: the default) --
+ *   70: int64 nwhat, the row pitch of the masked planes, the columns of the operator image, groups per chunk, chunks, the elements of
+ *   the chunk's planes (dtype), of its Y and power (double) and of norm_grp | power_bin | count_bin; 71: the bins' sorted group lists,
+ *   one after the other; 72: [chunks][nbins][2] a bin's piece of a chunk as positions in 71; 73: the operator image
+ *   [re, im][pitch][columns] (dtype); 74: norm_f padded to the pitch (double); 75: the scales [ngroups][ntimes] (double; ones for NULL);
+ *   76: opt_r | opt_i, [ntimes][nrates] each (double). */
 typedef struct cal_report_plan_desc {
   const struct cal_delay_spectrum_desc* spectrum;
   const struct cal_degeneracy_desc* degeneracy;
@@ -253,6 +260,7 @@ typedef struct cal_report_plan_desc {
   int32_t nslices;
   const struct cal_delay_transfer_desc* transfer; /* what = 40 .. 48 only */
   const struct cal_delay_cross_desc* cross;       /* what = 60 .. 65 only */
+  const struct cal_delay_fringe_desc* fringe;     /* what = 70 .. 76 only */
 } cal_report_plan_desc;
 int cal_debug_report_plan(int dtype, const cal_problem_desc* d, const cal_report_plan_desc* r, int what, void* out, int64_t cap_bytes, int64_t* bytes);
 /* Host only, like cal_debug_plan: the shape of one pass or train step (csrc/step_plan.hpp) -- which kernels follow the fused or dense pass,
@@ -789,6 +797,71 @@ typedef struct cal_delay_cross_desc {
 } cal_delay_cross_desc;
 int cal_solver_delay_cross_spectrum(cal_solver* s, const cal_delay_cross_desc* desc, const void* g_r, const void* g_i, double* cross_pair,
                                     double* diff_pair, double* norm_pair, double* cross_bin, double* diff_bin, double* count_bin);
+/* The delay / fringe-rate plane: the delay transform of T rows that are one baseline at T integrations, and then a transform ALONG
+ * time.  cal_solver_delay_spectrum, cal_solver_delay_transfer and cal_solver_delay_cross_spectrum treat time as a label; along time,
+ * cross-talk and other instrument-locked residuals sit at fringe rate 0, the sky at the fringe rate its baseline gives it, and noise
+ * is white.  The rate-0 row is the coherent time average every power-spectrum pipeline takes before squaring; the cross and
+ * half-difference powers of cal_solver_delay_cross_spectrum are the two fringe-rate channels of a window of two.  Notation of
+ * cal_solver_delay_spectrum: row b, G, m, w and the quantities q = data, model, residual (calibrated or not), formed in the solver's
+ * dtype exactly as there.  A group g is an ordered list of T = ntimes rows rows[g][0 .. T) -- any rows of the solver, repeats
+ * allowed; in practice one baseline at T consecutive integrations (nslices > 1, bl_alias, the joint time-basis layout) -- with scales
+ * a[g][t] = scale[g][t]:
+ *   mask_g[f]         = AND over t of (w[rows[g][t]][f] != 0)          the COMMON mask of all T rows: rows flagged differently leak
+ *                                                                     foregrounds differently
+ *   x_q[g][t][f]      = mask_g[f] q[rows[g][t]][f]
+ *   X_q[g][t][k]      = sum_f x_q[g][t][f] (op_r + i op_i)[f][k]      matrix cores, solver dtype, the loop of cal_solver_delay_spectrum
+ *   Y_t               = a[g][t] X_q[g][t][k]                          in double, after the matrix product
+ *   Z_q[g][r][k]      = sum_t (opt_r + i opt_i)[t][r] Y_t             complex, in double
+ *   norm_grp[g]       = sum_f mask_g[f] norm_f[f]                                                      [ngroups]
+ *   power_grp[q][g][r][k] = (Re Z^2 + Im Z^2) / norm_grp[g]     0 where norm_grp[g] == 0               [nwhat][ngroups][nrates][ndelays]
+ *   power_bin[q][n][r][k] = the sum over the groups g with bin_of_group[g] == n and norm_grp[g] > 0, in ascending g
+ *                                                                                                      [nwhat][nbins][nrates][ndelays]
+ *   count_bin[n]      = their number                                                                   [nbins]
+ * The order of operations for Z is part of the definition: the accumulators start at zero and, for t ascending,
+ * re += (opt_r yr - opt_i yi) and im += (opt_r yi + opt_i yr), without contraction.  Hence, to the bit: ntimes = 1 with opt = [[1]]
+ * and unit scale gives cal_solver_delay_spectrum's power_bl of the row; ntimes = 2 with opt = [[1, 1], [1, -1]] gives at rate 1 twice
+ * cal_solver_delay_cross_spectrum's diff of the same pairs.
+ * opt is any complex operator [ntimes][nrates] given in double: the caller folds the taper along time and its normalisation into
+ * it; there is no norm_t.  The scales put the rows into common units (a caller that divides every slice by its own rms passes the rms
+ * values); NULL: ones.
+ * The mask is common: a group with one row flagged throughout has norm_grp == 0, power 0, and enters no bin.
+ * Scaling, the sum over time, the division and every sum over groups are taken in double in a fixed order, no float atomics: two calls
+ * give the same bits, and so do two chunkings.  All outputs are doubles; any output pointer may be NULL.
+ *   g_r, g_i: as in cal_solver_delay_spectrum -- NULL: the solver's current full gains; given gains are used for this call only.
+ * Errors, before any launch: those of cal_solver_delay_spectrum (CAL_ERR_STATE when problem, data or coefficients are not set, or the
+ * gains neither set nor given; CAL_ERR_INVALID for a null description, a bad `what`, ndelays, `calibrated`, nbins, bin_of_group, a
+ * null operator or norm_f); CAL_ERR_INVALID for ngroups < 1, ntimes or nrates outside [1, 64], null rows or opt, a row outside
+ * [0, nbls), a scale or operator entry that is not finite, a bin outside [-1, nbins), binned outputs with nbins == 0.
+ * Works for every layout and kernel path, fitting groups of several baselines, bl_alias, nslices > 1 and the joint time-basis layout.
+ * A post-fit pass: it runs the model pass of cal_solver_model and puts the loop state back; a run continued after the call is
+ * bit-identical to one without it.  It reads the ONE weight plane the other reports read, the one cal_solver_robust_weights rewrites,
+ * not the weights as set.
+ * The groups are worked through in chunks of whole groups whose scratch -- per group nwhat 2 ntimes pitch elements of the solver's dtype
+ * for the masked planes, nwhat 2 ntimes ndelays doubles of Y and nwhat nrates ndelays doubles of power -- stays under the bound of
+ * cal_solver_set_delay_spectrum_scratch (never less than one group); the device buffers of cal_solver_delay_spectrum are reused.  The
+ * result does not depend on the chunks by a bit.
+ * Under a communicator or exchange hook power_bin | count_bin are summed over the ranks in ONE all-reduce of
+ * nwhat nbins nrates ndelays + nbins doubles (CAL_XCHG_F64, CAL_XCHG_SUM), whichever outputs are asked for (nbins == 0: none); the
+ * per-group outputs stay the rank's own. */
+typedef struct cal_delay_fringe_desc {
+  int32_t ndelays;             /* columns of the operator, 1 <= ndelays <= 4096 */
+  int32_t what;                /* bit 0: data, bit 1: model, bit 2: residual; at least one */
+  int32_t calibrated;          /* as in cal_delay_spectrum_desc */
+  int32_t ngroups;             /* >= 1 */
+  int32_t ntimes;              /* rows of a group, 1 <= ntimes <= 64 */
+  int32_t nrates;              /* columns of opt, 1 <= nrates <= 64 */
+  const int32_t* rows;         /* [ngroups][ntimes]: rows of the solver, each in [0, nbls), repeats allowed */
+  const double* scale;         /* [ngroups][ntimes], finite; NULL: ones */
+  int32_t nbins;               /* 0: no binned output */
+  const int32_t* bin_of_group; /* [ngroups] in [-1, nbins): -1 leaves the group out; NULL iff nbins == 0 */
+  const void* op_r;            /* [nfreqs][ndelays], solver dtype: the transform along frequency, taper folded in */
+  const void* op_i;
+  const double* norm_f;        /* [nfreqs]: what a channel unflagged in all rows adds to the group's normalisation */
+  const double* opt_r;         /* [ntimes][nrates], finite: the transform along time, taper and normalisation folded in */
+  const double* opt_i;
+} cal_delay_fringe_desc;
+int cal_solver_delay_fringe_spectrum(cal_solver* s, const cal_delay_fringe_desc* desc, const void* g_r, const void* g_i, double* power_grp,
+                                     double* norm_grp, double* power_bin, double* count_bin);
 /* The signal loss of the fit in delay space: the share of the power at every delay that the coefficient fit itself removes.  The
  * foreground basis absorbs every component of the data in its span -- noise and cosmological signal as well as foregrounds -- so a
  * residual delay spectrum (cal_solver_delay_spectrum) is biased low near the edge of the basis; this is the factor that undoes it.

@@ -1,7 +1,7 @@
 // plan_sanitize.hip -- the set-up planner (calamity_amd/csrc/problem_plan.hpp), the planner of the closed-form calls
 // (calamity_amd/csrc/solve_plan.hpp), of the post-fit reports (calamity_amd/csrc/report_plan.hpp), the step's shape (calamity_amd/csrc/step_plan.hpp) and the two-loop recursion of L-BFGS on
 // coefficients (calamity_amd/csrc/lbfgs_core.hpp) under the host sanitizers, with no device and no interpreter: four problems built in code (folded STREAM, heads of baselines that share tiles, forced dense, multi-baseline runs),
-// planned for fp32 and fp64; the closed-form plans, the delay-spectrum plan and the cross-spectrum plan (with its refusals) at the default scratch bound and at a bound of 1 byte, the degeneracy plan in both modes,
+// planned for fp32 and fp64; the closed-form plans, the delay-spectrum plan, the cross-spectrum plan and the delay / fringe-rate plan (each with its refusals) at the default scratch bound and at a bound of 1 byte, the degeneracy plan in both modes,
 // the caller's arrays of exactly the sizes the planners may read; plan_step over its whole input
 // table; lbfgs_two_loop on Gram matrices of 0 .. 16 pairs held in arrays of exactly the sizes it may touch.  Exits non-zero on a planner error or an inconsistent plan; the sanitizers abort on a finding.
 //
@@ -136,6 +136,53 @@ int run(const Case& c) {
     rbad += plan_delay_cross(p.nbls, p.nfreqs, p.fpad, &cd, kCsScratchDefault, R) != CAL_ERR_INVALID;
     cd.stats = 2;
     rbad += plan_delay_cross(p.nbls, p.nfreqs, p.fpad, &cd, kCsScratchDefault, R) != CAL_OK || R.nstat != 1 || R.scale[1] != 1.0;
+  }
+  // the delay / fringe-rate plan: a group of three rows per row (b, (b + 5) % nbls, b again: a repeat), scales of exactly ngroups ntimes
+  // entries, opt of exactly ntimes nrates, bins of exactly ngroups; both bounds; then its refusals
+  {
+    const int ng = p.nbls, nt = 3, nr = 2;
+    std::vector<int32_t> rows((size_t)ng * nt), bin_of_group(ng);
+    std::vector<double> scale((size_t)ng * nt, 1.5), opt_r((size_t)nt * nr, 0.5), opt_i((size_t)nt * nr, -0.25);
+    for (int k = 0; k < ng; ++k) rows[3 * k] = k, rows[3 * k + 1] = (k + 5) % ng, rows[3 * k + 2] = k, bin_of_group[k] = k % 7 == 3 ? -1 : k % (nbins - 1);
+    cal_delay_fringe_desc fd{nd, 7, 0, ng, nt, nr, rows.data(), scale.data(), nbins, bin_of_group.data(), op_r.data(), op_i.data(), norm_f.data(),
+                             opt_r.data(), opt_i.data()};
+    for (const int64_t bound : {kCsScratchDefault, (int64_t)1}) {
+      DelayFringePlan<T> P;
+      rbad += plan_delay_fringe(p.nbls, p.nfreqs, p.fpad, &fd, bound, P) != CAL_OK || P.nchunks != (bound == 1 ? ng : 1) || P.cgroups != (bound == 1 ? 1 : ng) ||
+              P.scale.size() != (size_t)ng * nt || P.opt.size() != 2 * (size_t)nt * nr || P.opt[0] != 0.5 || P.opt[(size_t)nt * nr] != -0.25;
+      int n = 0;
+      for (size_t k = 0; k < P.chunk_ptr.size(); k += 2) n += P.chunk_ptr[k + 1] - P.chunk_ptr[k];
+      rbad += n != (int)P.bin_ent.size() || P.bin_ent.size() != (size_t)(ng - (ng + 3) / 7) || P.n_x != (size_t)3 * 2 * P.cgroups * nt * P.xpitch ||
+              P.n_y != (size_t)3 * 2 * P.cgroups * nt * nd || P.n_pow != (size_t)3 * P.cgroups * nr * nd;
+    }
+    DelayFringePlan<T> R;
+    rows[(size_t)ng * nt - 1] = p.nbls;  // a row past the last
+    rbad += plan_delay_fringe(p.nbls, p.nfreqs, p.fpad, &fd, kCsScratchDefault, R) != CAL_ERR_INVALID;
+    rows[(size_t)ng * nt - 1] = 0;
+    scale[1] = std::numeric_limits<double>::infinity();
+    rbad += plan_delay_fringe(p.nbls, p.nfreqs, p.fpad, &fd, kCsScratchDefault, R) != CAL_ERR_INVALID;
+    fd.scale = nullptr;  // no scales: ones
+    opt_i[(size_t)nt * nr - 1] = std::numeric_limits<double>::quiet_NaN();
+    rbad += plan_delay_fringe(p.nbls, p.nfreqs, p.fpad, &fd, kCsScratchDefault, R) != CAL_ERR_INVALID;
+    opt_i[(size_t)nt * nr - 1] = 0.0;
+    for (const int bad_nt : {0, 65}) {
+      fd.ntimes = bad_nt;
+      rbad += plan_delay_fringe(p.nbls, p.nfreqs, p.fpad, &fd, kCsScratchDefault, R) != CAL_ERR_INVALID;
+    }
+    fd.ntimes = nt;
+    for (const int bad_nr : {0, 65}) {
+      fd.nrates = bad_nr;
+      rbad += plan_delay_fringe(p.nbls, p.nfreqs, p.fpad, &fd, kCsScratchDefault, R) != CAL_ERR_INVALID;
+    }
+    fd.nrates = nr;
+    fd.ngroups = 0;
+    rbad += plan_delay_fringe(p.nbls, p.nfreqs, p.fpad, &fd, kCsScratchDefault, R) != CAL_ERR_INVALID;
+    fd.ngroups = ng;
+    bin_of_group[ng - 1] = nbins;  // a bin past the last
+    rbad += plan_delay_fringe(p.nbls, p.nfreqs, p.fpad, &fd, kCsScratchDefault, R) != CAL_ERR_INVALID;
+    bin_of_group[ng - 1] = -1;
+    fd.what = 4;
+    rbad += plan_delay_fringe(p.nbls, p.nfreqs, p.fpad, &fd, kCsScratchDefault, R) != CAL_OK || R.nq != 1 || R.scale[1] != 1.0;
   }
   for (const bool band : {false, true}) {
     DegeneracyPlan P;
