@@ -124,6 +124,16 @@ class DelayFringeDesc(C.Structure):
                 ("op_r", C.c_void_p), ("op_i", C.c_void_p), ("norm_f", C.c_void_p), ("opt_r", C.c_void_p), ("opt_i", C.c_void_p)]
 
 
+class DelayCoherentDesc(C.Structure):
+    """cal_delay_coherent_desc (include/calamity_hip.h: cal_solver_delay_coherent_spectrum): the fields of DelayFringeDesc with ``rows``
+    replaced by the ragged sets -- set_ptr [ngroups ntimes + 1] int64, member_row [nmembers] int32, member_wgt [nmembers] float64 (NULL:
+    ones), member_conj [nmembers] uint8 (NULL: none), weighting 0 / 1 -- and nmembers at the end."""
+    _fields_ = [("ndelays", C.c_int32), ("what", C.c_int32), ("calibrated", C.c_int32), ("ngroups", C.c_int32), ("ntimes", C.c_int32),
+                ("nrates", C.c_int32), ("set_ptr", C.c_void_p), ("member_row", C.c_void_p), ("member_wgt", C.c_void_p), ("member_conj", C.c_void_p),
+                ("weighting", C.c_int32), ("scale", C.c_void_p), ("nbins", C.c_int32), ("bin_of_group", C.c_void_p), ("op_r", C.c_void_p),
+                ("op_i", C.c_void_p), ("norm_f", C.c_void_p), ("opt_r", C.c_void_p), ("opt_i", C.c_void_p), ("nmembers", C.c_int64)]
+
+
 class DelayTransferDesc(C.Structure):
     """cal_delay_transfer_desc (include/calamity_hip.h: cal_solver_delay_transfer): ndelays columns of the operator op_r + i op_i
     ([nfreqs][ndelays], solver dtype), calibrated 0 / 1, nbins and bin_of_bl [nbls] int32 in [-1, nbins) (NULL iff nbins == 0), the
@@ -254,6 +264,8 @@ SYMBOLS = {
     "cal_basis_foldable": (C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "cal_debug_plan": (C.c_int, [C.c_int, C.POINTER(ProblemDesc), C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "cal_debug_solve_plan": (C.c_int, [C.c_int, C.POINTER(ProblemDesc), C.c_int64, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "cal_debug_delay_coherent_plan": (C.c_int, [C.c_int, C.POINTER(ProblemDesc), C.POINTER(DelayCoherentDesc), C.c_int64, C.c_int, _P, C.c_int64,
+                                               C.POINTER(C.c_int64)]),
     "cal_debug_report_plan": (C.c_int, [C.c_int, C.POINTER(ProblemDesc), C.POINTER(ReportPlanDesc), C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "cal_debug_step_shape": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "cal_device_info": (C.c_int, [C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
@@ -289,6 +301,7 @@ SYMBOLS = {
     "cal_solver_set_delay_spectrum_scratch": (C.c_int, [_P, C.c_int64]),
     "cal_solver_delay_cross_spectrum": (C.c_int, [_P, C.POINTER(DelayCrossDesc), _P, _P, _P, _P, _P, _P, _P, _P]),
     "cal_solver_delay_fringe_spectrum": (C.c_int, [_P, C.POINTER(DelayFringeDesc), _P, _P, _P, _P, _P, _P]),
+    "cal_solver_delay_coherent_spectrum": (C.c_int, [_P, C.POINTER(DelayCoherentDesc), _P, _P, _P, _P, _P, _P]),
     "cal_solver_delay_transfer": (C.c_int, [_P, C.POINTER(DelayTransferDesc), _P, _P, _P, _P, _P, _P, C.POINTER(FitErrorsCounts)]),
     "cal_solver_set_delay_transfer_scratch": (C.c_int, [_P, C.c_int64]),
     "cal_solver_fix_degeneracies": (C.c_int, [_P, C.POINTER(DegeneracyDesc), _P, _P, _P, _P, _P, _P, _P]),

@@ -104,6 +104,35 @@ def split_groups(groups, rows, nbls):
     return sel, [where[groups[s]].astype(np.int32) for s in sel]
 
 
+def split_member_groups(set_ptr, member_row, ntimes, rows, nbls):
+    """``split_groups`` for groups of ``ntimes`` ragged sets (``HipFitSolver.delay_coherent_spectrum``): ``(sel, parts)`` with
+    ``sel[r]`` the positions of worker ``r``'s groups and ``parts[r] = (set_ptr, member_row, members)`` those groups' sets over its
+    local rows and the positions of their members in the caller's member arrays.  A group without members goes to worker 0.
+    ``ValueError`` for a group whose member rows lie on several workers and for a worker without a group."""
+    set_ptr, member_row = np.asarray(set_ptr, dtype=np.int64), np.asarray(member_row, dtype=np.int64)
+    ngroups = (len(set_ptr) - 1) // int(ntimes)
+    owner, where = np.full(nbls, -1, dtype=np.int64), np.zeros(nbls, dtype=np.int64)
+    for r, idx in enumerate(rows):
+        owner[idx], where[idx] = r, np.arange(len(idx))
+    gptr = set_ptr[:: int(ntimes)]  # the members of group g are gptr[g] .. gptr[g + 1]
+    own = np.zeros(ngroups, dtype=np.int64)
+    for g in range(ngroups):
+        o = owner[member_row[gptr[g]:gptr[g + 1]]]
+        if len(o) and np.any(o != o[0]):
+            raise ValueError(f"group {g} joins rows of several workers {tuple(int(v) for v in np.unique(o))}")
+        own[g] = o[0] if len(o) else 0
+    sel, parts = [np.nonzero(own == r)[0] for r in range(len(rows))], []
+    for r, s in enumerate(sel):
+        if len(s) == 0:
+            raise ValueError(f"worker {r} holds no group: every worker must take part in the exchange of the bins")
+        sets = (s[:, None] * int(ntimes) + np.arange(int(ntimes))[None, :]).ravel()
+        counts = set_ptr[sets + 1] - set_ptr[sets]
+        members = np.concatenate([np.arange(set_ptr[v], set_ptr[v + 1]) for v in sets]) if len(sets) else np.zeros(0, dtype=np.int64)
+        parts.append((np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), where[member_row[members.astype(np.int64)]].astype(np.int32),
+                      members.astype(np.int64)))
+    return sel, parts
+
+
 class _HostExchange:
     """In-process all-reduce between worker threads (cal_solver_set_exchange_hook): every worker leaves a view of its staging
     buffer, all of them reduce the views in rank order -- the same arithmetic on every worker -- and each writes the result
@@ -370,6 +399,40 @@ class SliceBatchFitter:
         sel, local = split_groups(rows, self.rows, self.nbls)
         outs = self._each(lambda r, s: s.delay_fringe_spectrum(op, norm_f, local[r], opt, scale=None if scale is None else scale[sel[r]],
                                                                bin_of_group=None if bins is None else bins[sel[r]], **kw))
+        out = dict(outs[0], norm_grp=self._scatter([o["norm_grp"] for o in outs], sel))
+        if per_group:
+            out["per_group"] = {q: self._scatter([o["per_group"][q] for o in outs], sel) for q in outs[0]["per_group"]}
+        return out
+
+    def delay_coherent_spectrum(self, op, norm_f, set_ptr, member_row, opt, member_wgt=None, member_conj=None, weighting="uniform", scale=None,
+                                what=("data", "model", "resid"), calibrated=False, bin_of_group=None, nbins=0, per_group=False, g_r=None, g_i=None):
+        """``HipFitSolver.delay_coherent_spectrum`` on global slice-major rows: ``member_row`` holds rows of the batch.  Every worker
+        takes the groups whose member rows it all holds, mapped to its local rows (a group without members goes to worker 0); a group
+        split over workers raises ``ValueError``, and so does a worker left without a group, as in ``delay_fringe_spectrum``.  The
+        binned arrays and ``count_bin`` are worker 0's (with several workers the library has summed them over the workers);
+        ``norm_grp`` and the ``per_group`` arrays are put back into the caller's order."""
+        set_ptr = np.asarray(set_ptr, dtype=np.int64)
+        member_row = np.asarray(member_row, dtype=np.int64)
+        ntimes = np.asarray(opt).shape[0] if np.asarray(opt).ndim == 2 else 0
+        if ntimes < 1 or set_ptr.ndim != 1 or len(set_ptr) < ntimes + 1 or (len(set_ptr) - 1) % ntimes:
+            raise ValueError(f"set_ptr must be [ngroups ntimes + 1] with ntimes = opt.shape[0] and ngroups >= 1, got shape {set_ptr.shape}")
+        if set_ptr[0] != 0 or np.any(np.diff(set_ptr) < 0) or set_ptr[-1] != len(member_row):
+            raise ValueError("set_ptr must start at 0, never fall and end at len(member_row)")
+        if len(member_row) and (member_row.min() < 0 or member_row.max() >= self.nbls):
+            raise ValueError(f"member_row must hold rows in [0, {self.nbls})")
+        kw = dict(weighting=weighting, what=what, calibrated=calibrated, nbins=nbins, per_group=per_group, g_r=g_r, g_i=g_i)
+        scale = None if scale is None else np.asarray(scale, dtype=np.float64)
+        bins = None if bin_of_group is None else np.asarray(bin_of_group)
+        wgt = None if member_wgt is None else np.asarray(member_wgt, dtype=np.float64)
+        cj = None if member_conj is None else np.asarray(member_conj)
+        if self.nworkers == 1:
+            return self.solvers[0].delay_coherent_spectrum(op, norm_f, set_ptr, member_row, opt, member_wgt=wgt, member_conj=cj, scale=scale,
+                                                           bin_of_group=bins, **kw)
+        sel, parts = split_member_groups(set_ptr, member_row, ntimes, self.rows, self.nbls)
+        outs = self._each(lambda r, s: s.delay_coherent_spectrum(
+            op, norm_f, parts[r][0], parts[r][1], opt, member_wgt=None if wgt is None else wgt[parts[r][2]],
+            member_conj=None if cj is None else cj[parts[r][2]], scale=None if scale is None else scale[sel[r]],
+            bin_of_group=None if bins is None else bins[sel[r]], **kw))
         out = dict(outs[0], norm_grp=self._scatter([o["norm_grp"] for o in outs], sel))
         if per_group:
             out["per_group"] = {q: self._scatter([o["per_group"][q] for o in outs], sel) for q in outs[0]["per_group"]}

@@ -1053,6 +1053,112 @@ def delay_fringe_entry(fringe, dspec, k, time_indices, prob, ant_array):
     return entry
 
 
+def _check_delay_redundant(delay_redundant_spectrum, delay_redundant_times, delay_redundant_taper, delay_redundant_weighting, delay_spectrum,
+                           delay_spectrum_calibrated, batch_slices, init_guesses_from_previous_time_step, device_split):
+    """The ``delay_redundant_spectrum`` keywords of ``calibrate_and_model_tensor``, checked before anything is touched (``ValueError``)."""
+    if not any(delay_redundant_spectrum is v for v in (False, True)) and delay_redundant_spectrum != "groups":
+        raise ValueError(f"delay_redundant_spectrum must be False, True or 'groups', got {delay_redundant_spectrum!r}")
+    if not delay_redundant_spectrum:
+        return
+    if not delay_spectrum:
+        raise ValueError("delay_redundant_spectrum needs delay_spectrum=True or 'baselines': it uses that spectrum's operator, taper and bin width")
+    if not delay_spectrum_calibrated:
+        raise ValueError("delay_redundant_spectrum needs delay_spectrum_calibrated=True: an average of uncalibrated rows of different antennas decoheres")
+    if isinstance(delay_redundant_times, bool) or not isinstance(delay_redundant_times, (int, np.integer)) or not 1 <= int(delay_redundant_times) <= 64:
+        raise ValueError(f"delay_redundant_spectrum: delay_redundant_times must be an integer in [1, 64], got {delay_redundant_times!r}")
+    try:
+        modeling.delay_taper(int(delay_redundant_times), delay_redundant_taper)
+    except ValueError:
+        raise ValueError(f"delay_redundant_spectrum: delay_redundant_taper must be 'bh4', 'none' or an array of delay_redundant_times values, "
+                         f"got {delay_redundant_taper!r}") from None
+    if not isinstance(delay_redundant_weighting, str) or delay_redundant_weighting not in ("weights", "uniform"):
+        raise ValueError(f"delay_redundant_spectrum: delay_redundant_weighting must be 'weights' or 'uniform', got {delay_redundant_weighting!r}")
+    if init_guesses_from_previous_time_step:
+        raise ValueError("delay_redundant_spectrum transforms along the times of a batch: init_guesses_from_previous_time_step (a chain of single times) contradicts it")
+    if batch_slices is not None and batch_slices is not True and int(batch_slices) < int(delay_redundant_times):
+        raise ValueError(f"delay_redundant_spectrum transforms along the times of a batch: batch_slices={batch_slices!r} holds no window of "
+                         f"delay_redundant_times={int(delay_redundant_times)} (True or at least that many)")
+    if device_split == "groups":
+        raise ValueError("delay_redundant_spectrum averages the rows of a redundant group: device_split='groups' would put them on several devices "
+                         "(use one device or device_split='slices')")
+
+
+def delay_redundant_setup(uvdata, ant_array, prob, ntimes, taper="none", weighting="weights", per_group=False, bllen_bin=1.0, red_tol=1.0,
+                          include_autos=False):
+    """What the redundant-average pass of every batch of a call shares.  The groups are those of
+    ``modeling.get_redundant_grps_data(uvdata, tol=red_tol, include_autos=include_autos)``: every pair of a group maps to its baseline row
+    of ``prob`` (``ant_array``: the antenna numbers ``prob``'s antenna indices count through), with ``conj = 1`` where the row holds the
+    pair reversed -- the average is taken in the group's orientation; a pair without a row is dropped, and so is a group without rows; no
+    row enters two sets.  ``rows``, ``conj`` and ``pairs`` list the kept members group by group, the groups in the order of their first rows; ``bin_of_group`` and ``bllen_m`` come from
+    ``baseline_length_bins`` on the GROUPS' lengths at ``bllen_bin``; the transform along time, its rates, ``times`` and ``dt`` are
+    ``delay_fringe_setup``'s."""
+    out = delay_fringe_setup(np.unique(uvdata.time_array), ntimes, taper, per_group)
+    _, grps, _, lengths = modeling.get_redundant_grps_data(uvdata, tol=red_tol, include_autos=include_autos)
+    ants = np.asarray(ant_array)
+    row_of = {}
+    for b, (i, j) in enumerate(zip(prob.bl_ant0, prob.bl_ant1)):
+        row_of.setdefault((int(ants[i]), int(ants[j])), b)
+    rows, conj, pairs, kept, used = [], [], [], [], set()
+    for grp, length in zip(grps, lengths):
+        r, c, p = [], [], []
+        for i, j in grp:
+            i, j = int(i), int(j)
+            b, flip = (row_of[(i, j)], 0) if (i, j) in row_of else (row_of.get((j, i)), 1)
+            if b is None or b in used:
+                continue
+            used.add(b)
+            r.append(b), c.append(flip), p.append((i, j))
+        if r:
+            rows.append(np.asarray(r, dtype=np.int32)), conj.append(np.asarray(c, dtype=np.uint8)), pairs.append(p), kept.append(float(length))
+    if not rows:
+        raise ValueError("delay_redundant_spectrum: no redundant group holds a baseline of the fit")
+    # the groups in the order of their first rows: a bin then adds its groups as delay_spectrum adds its rows
+    order = sorted(range(len(rows)), key=lambda g: int(rows[g][0]))
+    rows, conj, pairs, kept = ([x[g] for g in order] for x in (rows, conj, pairs, kept))
+    bin_of_group, bllen_m = baseline_length_bins(kept, bllen_bin)
+    out.update(weighting=weighting, rows=rows, conj=conj, pairs=pairs, lengths=np.asarray(kept), bin_of_group=bin_of_group, nbins=len(bllen_m), bllen_m=bllen_m)
+    return out
+
+
+def delay_redundant_sets(windows, red, rms, nbls):
+    """What ``SliceBatchFitter.delay_coherent_spectrum`` takes for the slice windows ``windows`` of a batch: group ``g`` of window ``k`` has
+    the sets ``t nbls + red["rows"][g]`` of the window's slices ``t`` with their ``rms`` as scales (ones for windows of one time:
+    ``delay_redundant_entry`` then multiplies by ``rms^2`` as ``delay_spectrum_entry`` does) and bin ``k nbins + bin_of_group[g]``.
+    Returns ``(set_ptr int64, member_row int32, member_conj uint8, scale [ngroups, ntimes], bin_of_group int32)``, window by window."""
+    sizes, members, conj, scale, bins = [], [], [], [], []
+    for k, win in enumerate(windows):
+        for g, r in enumerate(red["rows"]):
+            for t in win:
+                sizes.append(len(r)), members.append(t * nbls + r.astype(np.int64)), conj.append(red["conj"][g])
+            scale.append([float(rms[t]) if len(win) > 1 else 1.0 for t in win])  # (one time: the entry applies rms^2 behind the square)
+            bins.append(k * red["nbins"] + int(red["bin_of_group"][g]))
+    return (np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64), np.concatenate(members).astype(np.int32), np.concatenate(conj).astype(np.uint8),
+            np.asarray(scale, dtype=np.float64), np.asarray(bins, dtype=np.int32))
+
+
+def delay_redundant_entry(out, red, k, time_indices, rms=1.0):
+    """Window ``k`` of a ``delay_coherent_spectrum`` over ``delay_redundant_sets`` as what every member of it reports under
+    ``fit_history[...]["delay_spectrum"]["redundant"]``: ``time_indices`` of the window, ``fringe_rates`` in Hz, ``bllen_m`` of the GROUPS'
+    length bins, ``ngroups`` the counted groups per bin, ``nmembers`` the rows per group, ``data``, ``model``, ``resid``
+    ``[nbins, nrates, ndelays]``, the MEAN over the bin's groups of the power of the group's average in the data's units squared (the
+    scales were the slices' ``rms``; with windows of one time ``rms`` is the reporting slice's, applied here as ``rms^2 sum / count``
+    in ``delay_spectrum_entry``'s order of operations; 0 for a bin without a counted group), and with per-group planes ``groups`` keyed by
+    the group's first antenna pair: ``{"antpairs": its member pairs, "data", "model", "resid"}``."""
+    ng, nbins = len(red["rows"]), red["nbins"]
+    bins, grp = slice(k * nbins, (k + 1) * nbins), slice(k * ng, (k + 1) * ng)
+    count = np.asarray(out["count_bin"][bins], dtype=np.float64)
+    unit = float(rms) ** 2 if red["ntimes"] == 1 else 1.0
+    mean = (unit * np.divide(1.0, count, out=np.zeros_like(count), where=count > 0))[:, None, None]
+    entry = {"time_indices": [int(t) for t in time_indices], "fringe_rates": np.array(red["rates_hz"]), "bllen_m": np.array(red["bllen_m"]),
+             "ngroups": count.astype(np.int64), "nmembers": np.asarray([len(r) for r in red["rows"]], dtype=np.int64)}
+    for q in ("data", "model", "resid"):
+        entry[q] = mean * np.asarray(out[q][bins])
+    if "per_group" in out:
+        entry["groups"] = {p[0]: dict({q: unit * out["per_group"][q][grp][g] for q in ("data", "model", "resid")}, antpairs=list(p))
+                           for g, p in enumerate(red["pairs"])}
+    return entry
+
+
 def baseline_length_bins(lengths, width):
     """Baseline rows into bins of ``width`` metres, bin ``floor(length / width)``, only the bins that hold a row, in ascending order:
     ``(bin_of_bl [nbls] int32, bllen_m [nbins])`` with ``bllen_m`` the mean length of each bin's rows."""
@@ -1257,6 +1363,10 @@ def calibrate_and_model_tensor(
     fix_degeneracies=False,
     degeneracy_iters=6,
     degeneracy_phase_ref=True,
+    delay_redundant_spectrum=False,
+    delay_redundant_times=2,
+    delay_redundant_taper="none",
+    delay_redundant_weighting="weights",
     delay_fringe_spectrum=False,
     delay_fringe_times=8,
     delay_fringe_taper="bh4",
@@ -1465,6 +1575,20 @@ def calibrate_and_model_tensor(
       (the antenna pairs of ``fg_model_comps_dict``, the keys of ``per_baseline``): held as ``(j, i)`` its spectrum is the mirror image
       in delay of ``(i, j)``'s.  A joint time-basis fit reports every time on its own.
       ``ValueError`` before any device work for an unknown taper, a bin width that is not positive, a negative ``delay_spectrum_max_dly``.
+    * ``delay_redundant_spectrum`` (``False`` | ``True`` | ``"groups"``), ``delay_redundant_times`` (1 .. 64), ``delay_redundant_taper``,
+      ``delay_redundant_weighting`` (``"weights"`` | ``"uniform"``) (Python keywords only; default off: no call changes by a bit and no new
+      kernel is launched; needs ``delay_spectrum`` on, ``delay_spectrum_calibrated=True`` -- an average of uncalibrated rows of different
+      antennas decoheres -- and batches that hold a window, under the rules of ``delay_fringe_spectrum`` for ``batch_slices`` and
+      ``init_guesses_from_previous_time_step``; ``device_split="groups"`` is refused; else ``ValueError`` before anything is touched): delay /
+      fringe-rate power of the redundant groups' AVERAGES (``HipFitSolver.delay_coherent_spectrum``: one more device pass, at the reported
+      gains).  The calibrated rows of every group of ``modeling.get_redundant_grps_data`` (tolerance 1 m, this call's ``include_autos``) are
+      averaged per channel over the unflagged members -- weighted by the fit's weights, or uniformly --, a row that holds a pair reversed
+      conjugated; the averages of ``delay_redundant_times`` consecutive slices (the windows of ``delay_fringe_windows``) are then transformed
+      and squared as the delay / fringe-rate plane is: noise power falls as 1 / N in the group size, where the mean of the baselines'
+      powers cannot.  Every member of a window gets ``["delay_spectrum"]["redundant"]``: ``time_indices``, ``fringe_rates`` (Hz),
+      ``bllen_m`` (``baseline_length_bins`` on the GROUPS' lengths at ``delay_spectrum_bllen_bin``), ``ngroups`` the counted groups per
+      bin, ``nmembers`` the rows per group, ``data``, ``model``, ``resid`` ``[nbins, Nrates, Ndelays]`` -- the MEAN over the bin's groups,
+      data's units squared; ``"groups"`` adds ``groups``, every group's own plane keyed by its first antenna pair, with its member pairs.
     * ``delay_fringe_spectrum`` (``False`` | ``True`` | ``"baselines"``), ``delay_fringe_times`` (2 .. 64), ``delay_fringe_taper`` (Python
       keywords only; default off: no call changes by a bit and no new kernel is launched; needs ``delay_spectrum`` on and batches that
       hold a window, else ``ValueError`` before anything is touched -- ``batch_slices`` ``False`` or below ``delay_fringe_times`` and
@@ -1526,6 +1650,8 @@ def calibrate_and_model_tensor(
     _check_delay_transfer(delay_transfer, delay_transfer_ridge, delay_spectrum, freeze_model)
     _check_delay_cross(delay_cross_spectrum, delay_spectrum, batch_slices, init_guesses_from_previous_time_step)
     _check_delay_fringe(delay_fringe_spectrum, delay_fringe_times, delay_fringe_taper, delay_spectrum, batch_slices, init_guesses_from_previous_time_step)
+    _check_delay_redundant(delay_redundant_spectrum, delay_redundant_times, delay_redundant_taper, delay_redundant_weighting, delay_spectrum,
+                           delay_spectrum_calibrated, batch_slices, init_guesses_from_previous_time_step, device_split)
     controls = FitControls.pick(locals())
     controls.check(gain_basis is not None or gain_max_dly is not None, gain_time_basis is not None or gain_time_scale is not None, freeze_model, use_min)
     if gain_max_dly is not None:
@@ -1611,6 +1737,9 @@ def calibrate_and_model_tensor(
         dspec["cross"] = {False: None, True: "bins", "baselines": "baselines"}[delay_cross_spectrum]
         if delay_fringe_spectrum:
             dspec["fringe"] = delay_fringe_setup(np.unique(uvdata.time_array), delay_fringe_times, delay_fringe_taper, delay_fringe_spectrum == "baselines")
+        if delay_redundant_spectrum:
+            dspec["redundant"] = delay_redundant_setup(uvdata, gains.ant_array, prob, delay_redundant_times, delay_redundant_taper, delay_redundant_weighting,
+                                                       delay_redundant_spectrum == "groups", delay_spectrum_bllen_bin, include_autos=include_autos)
     degen = degeneracy_setup(uvdata, gains.ant_array, degen_mode, degeneracy_iters, degeneracy_phase_ref) if degen_mode is not None else None
     if parallel_fits is None:
         parallel_fits = 1
@@ -1618,7 +1747,8 @@ def calibrate_and_model_tensor(
         parallel_fits = 1
     times = np.unique(uvdata.time_array)
     if batch_slices is None:
-        batch_slices = parallel_fits <= 1 or gain_time_basis is not None or bool(delay_cross_spectrum) or bool(delay_fringe_spectrum)
+        batch_slices = (parallel_fits <= 1 or gain_time_basis is not None or bool(delay_cross_spectrum) or bool(delay_fringe_spectrum)
+                        or bool(delay_redundant_spectrum))
     if init_guesses_from_previous_time_step:
         batch_slices = False  # every time starts from the previous one's result: a chain, not a batch
     # the call's settings, once, for the loop and the batches alike (slice_pipeline's stages read them)
@@ -1642,6 +1772,9 @@ def calibrate_and_model_tensor(
             if delay_fringe_spectrum and batch_slices is True:
                 n = int(delay_fringe_times) * (2 if delay_cross_spectrum and int(delay_fringe_times) % 2 else 1)
                 max_batch = max(n, max_batch) // n * n  # whole windows inside a batch (and whole pairs, where both are asked for)
+            if delay_redundant_spectrum and batch_slices is True:
+                n = int(np.lcm.reduce([int(delay_redundant_times), 2 if delay_cross_spectrum else 1, int(delay_fringe_times) if delay_fringe_spectrum else 1]))
+                max_batch = max(n, max_batch) // n * n  # whole windows of the redundant averages too
         fit_history = _fit_slices_batched(cfg, max_batch)
         _file_gain_std(fit_history, errs, gains)
         return model, resid, gains, fit_history  # (every fitted slice left its write-back in its final state)
@@ -2049,6 +2182,10 @@ def calibrate_and_model_dpss(
     fix_degeneracies=False,
     degeneracy_iters=6,
     degeneracy_phase_ref=True,
+    delay_redundant_spectrum=False,
+    delay_redundant_times=2,
+    delay_redundant_taper="none",
+    delay_redundant_weighting="weights",
     delay_fringe_spectrum=False,
     delay_fringe_times=8,
     delay_fringe_taper="bh4",
@@ -2071,6 +2208,9 @@ def calibrate_and_model_dpss(
     _check_delay_cross(delay_cross_spectrum, delay_spectrum, fitting_kwargs.get("batch_slices"), fitting_kwargs.get("init_guesses_from_previous_time_step", False))
     _check_delay_fringe(delay_fringe_spectrum, delay_fringe_times, delay_fringe_taper, delay_spectrum, fitting_kwargs.get("batch_slices"),
                         fitting_kwargs.get("init_guesses_from_previous_time_step", False))
+    _check_delay_redundant(delay_redundant_spectrum, delay_redundant_times, delay_redundant_taper, delay_redundant_weighting, delay_spectrum,
+                           delay_spectrum_calibrated, fitting_kwargs.get("batch_slices"), fitting_kwargs.get("init_guesses_from_previous_time_step", False),
+                           fitting_kwargs.get("device_split"))
     _check_degeneracy_call(fix_degeneracies, degeneracy_iters, fitting_kwargs)
     waker = _wake_device(fitting_kwargs.get("devices"))
     try:
@@ -2083,7 +2223,8 @@ def calibrate_and_model_dpss(
             notebook_progressbar=notebook_progressbar, delay_spectrum=delay_spectrum, delay_spectrum_taper=delay_spectrum_taper,
             delay_spectrum_max_dly=delay_spectrum_max_dly, delay_spectrum_bllen_bin=delay_spectrum_bllen_bin,
             delay_spectrum_calibrated=delay_spectrum_calibrated, delay_transfer=delay_transfer, delay_transfer_ridge=delay_transfer_ridge, delay_cross_spectrum=delay_cross_spectrum,
-            delay_fringe_spectrum=delay_fringe_spectrum, delay_fringe_times=delay_fringe_times, delay_fringe_taper=delay_fringe_taper,
+            delay_fringe_spectrum=delay_fringe_spectrum, delay_fringe_times=delay_fringe_times, delay_fringe_taper=delay_fringe_taper, delay_redundant_spectrum=delay_redundant_spectrum,
+            delay_redundant_times=delay_redundant_times, delay_redundant_taper=delay_redundant_taper, delay_redundant_weighting=delay_redundant_weighting,
             fix_degeneracies=fix_degeneracies, degeneracy_iters=degeneracy_iters,
             degeneracy_phase_ref=degeneracy_phase_ref, **fitting_kwargs,
         )
@@ -2128,6 +2269,10 @@ def calibrate_and_model_mixed(
     fix_degeneracies=False,
     degeneracy_iters=6,
     degeneracy_phase_ref=True,
+    delay_redundant_spectrum=False,
+    delay_redundant_times=2,
+    delay_redundant_taper="none",
+    delay_redundant_weighting="weights",
     delay_fringe_spectrum=False,
     delay_fringe_times=8,
     delay_fringe_taper="bh4",
@@ -2152,6 +2297,9 @@ def calibrate_and_model_mixed(
     _check_delay_cross(delay_cross_spectrum, delay_spectrum, fitting_kwargs.get("batch_slices"), fitting_kwargs.get("init_guesses_from_previous_time_step", False))
     _check_delay_fringe(delay_fringe_spectrum, delay_fringe_times, delay_fringe_taper, delay_spectrum, fitting_kwargs.get("batch_slices"),
                         fitting_kwargs.get("init_guesses_from_previous_time_step", False))
+    _check_delay_redundant(delay_redundant_spectrum, delay_redundant_times, delay_redundant_taper, delay_redundant_weighting, delay_spectrum,
+                           delay_spectrum_calibrated, fitting_kwargs.get("batch_slices"), fitting_kwargs.get("init_guesses_from_previous_time_step", False),
+                           fitting_kwargs.get("device_split"))
     _check_degeneracy_call(fix_degeneracies, degeneracy_iters, fitting_kwargs)
     fitting_grps, blvecs, _, _ = modeling.get_uv_overlapping_grps_conjugated(
         uvdata, red_tol=red_tol, include_autos=include_autos, red_tol_freq=red_tol_freq, n_angle_bins=n_angle_bins,
@@ -2176,7 +2324,8 @@ def calibrate_and_model_mixed(
         notebook_progressbar=notebook_progressbar, use_redundancy=use_redundancy, delay_spectrum=delay_spectrum, delay_spectrum_taper=delay_spectrum_taper,
         delay_spectrum_max_dly=delay_spectrum_max_dly, delay_spectrum_bllen_bin=delay_spectrum_bllen_bin,
         delay_spectrum_calibrated=delay_spectrum_calibrated, delay_transfer=delay_transfer, delay_transfer_ridge=delay_transfer_ridge, delay_cross_spectrum=delay_cross_spectrum,
-            delay_fringe_spectrum=delay_fringe_spectrum, delay_fringe_times=delay_fringe_times, delay_fringe_taper=delay_fringe_taper,
+            delay_fringe_spectrum=delay_fringe_spectrum, delay_fringe_times=delay_fringe_times, delay_fringe_taper=delay_fringe_taper, delay_redundant_spectrum=delay_redundant_spectrum,
+            delay_redundant_times=delay_redundant_times, delay_redundant_taper=delay_redundant_taper, delay_redundant_weighting=delay_redundant_weighting,
             fix_degeneracies=fix_degeneracies, degeneracy_iters=degeneracy_iters,
         degeneracy_phase_ref=degeneracy_phase_ref, **fitting_kwargs,
     )
@@ -2291,6 +2440,10 @@ def read_calibrate_and_model_dpss(
     fix_degeneracies=False,
     degeneracy_iters=6,
     degeneracy_phase_ref=True,
+    delay_redundant_spectrum=False,
+    delay_redundant_times=2,
+    delay_redundant_taper="none",
+    delay_redundant_weighting="weights",
     delay_fringe_spectrum=False,
     delay_fringe_times=8,
     delay_fringe_taper="bh4",
@@ -2337,6 +2490,12 @@ def read_calibrate_and_model_dpss(
     indices of the slice's window; -1 for a slice outside every window), ``fringe_nbls`` ``[Npols, Ntimes, nbins]``, ``fringe_data``,
     ``fringe_model``, ``fringe_resid`` ``[Npols, Ntimes, nbins, Nrates, Ndelays]`` (``nan`` for a slice outside every window) and, with
     ``"baselines"``, ``fringe_antpairs`` and the same three with ``_bl`` ``[Npols, Ntimes, rows, Nrates, Ndelays]``.
+    ``delay_redundant_spectrum``, ``delay_redundant_times``, ``delay_redundant_taper``, ``delay_redundant_weighting`` are
+    ``calibrate_and_model_tensor``'s (Python keywords only); the archive then also holds ``redundant_rates`` ``[Nrates]`` (Hz),
+    ``redundant_bllen_m``, ``redundant_nmembers`` ``[ngroups]``, ``redundant_window`` ``[Npols, Ntimes, delay_redundant_times]`` (-1 for a
+    slice outside every window), ``redundant_ngroups`` ``[Npols, Ntimes, nbins]``, ``redundant_data``, ``redundant_model``,
+    ``redundant_resid`` ``[Npols, Ntimes, nbins, Nrates, Ndelays]`` (``nan`` outside every window) and, with ``"groups"``,
+    ``redundant_antpairs`` (every group's first pair) and the same three with ``_grp`` ``[Npols, Ntimes, ngroups, Nrates, Ndelays]``.
     ``fix_degeneracies``, ``degeneracy_iters``, ``degeneracy_phase_ref`` are ``calibrate_and_model_tensor``'s too (Python keywords only);
     the sky model is ``input_model_files`` and the written gains and model are the fixed ones.
     """
@@ -2345,6 +2504,9 @@ def read_calibrate_and_model_dpss(
     _check_delay_cross(delay_cross_spectrum, delay_spectrum, calibration_kwargs.get("batch_slices"), calibration_kwargs.get("init_guesses_from_previous_time_step", False))
     _check_delay_fringe(delay_fringe_spectrum, delay_fringe_times, delay_fringe_taper, delay_spectrum, calibration_kwargs.get("batch_slices"),
                         calibration_kwargs.get("init_guesses_from_previous_time_step", False))
+    _check_delay_redundant(delay_redundant_spectrum, delay_redundant_times, delay_redundant_taper, delay_redundant_weighting, delay_spectrum,
+                           delay_spectrum_calibrated, calibration_kwargs.get("batch_slices"), calibration_kwargs.get("init_guesses_from_previous_time_step", False),
+                           calibration_kwargs.get("device_split"))
     _check_degeneracy_call(fix_degeneracies, degeneracy_iters, dict(calibration_kwargs, sky_model=input_model_files))
     if delay_spectrum_outfile is not None and not delay_spectrum:
         raise ValueError("delay_spectrum_outfile needs delay_spectrum=True or 'baselines'")
@@ -2369,6 +2531,8 @@ def read_calibrate_and_model_dpss(
             **(dict(delay_cross_spectrum=delay_cross_spectrum) if delay_cross_spectrum else {}),
             **(dict(delay_fringe_spectrum=delay_fringe_spectrum, delay_fringe_times=delay_fringe_times, delay_fringe_taper=delay_fringe_taper)
                if delay_fringe_spectrum else {}),
+            **(dict(delay_redundant_spectrum=delay_redundant_spectrum, delay_redundant_times=delay_redundant_times, delay_redundant_taper=delay_redundant_taper,
+                    delay_redundant_weighting=delay_redundant_weighting) if delay_redundant_spectrum else {}),
             **(dict(fix_degeneracies=fix_degeneracies, degeneracy_iters=degeneracy_iters, degeneracy_phase_ref=degeneracy_phase_ref)
                if fix_degeneracies else {}),
             **(dict(gain_basis_errors=True) if gain_basis_errors else {}),
@@ -2466,12 +2630,34 @@ def delay_spectrum_tables(fit_info):
             out["fringe_antpairs"] = np.asarray(fpairs, dtype=np.int64).reshape(-1, 2)
             for k in ("data", "model", "resid"):
                 out["fringe_" + k + "_bl"] = np.full((len(pols), ntimes, len(fpairs), nr, nd), np.nan)
+    averaged = [e["redundant"] for e in entries if "redundant" in e]
+    if averaged:  # (nan, -1 and 0 groups for a slice outside every window)
+        nwin, nr, nrb = len(averaged[0]["time_indices"]), len(averaged[0]["fringe_rates"]), len(averaged[0]["bllen_m"])
+        out["redundant_rates"] = np.array(averaged[0]["fringe_rates"], dtype=np.float64)
+        out["redundant_bllen_m"] = np.array(averaged[0]["bllen_m"], dtype=np.float64)
+        out["redundant_nmembers"] = np.array(averaged[0]["nmembers"], dtype=np.int64)
+        out["redundant_window"] = np.full((len(pols), ntimes, nwin), -1, dtype=np.int64)
+        out["redundant_ngroups"] = np.zeros((len(pols), ntimes, nrb), dtype=np.int64)
+        for k in ("data", "model", "resid"):
+            out["redundant_" + k] = np.full((len(pols), ntimes, nrb, nr, nd), np.nan)
+        rkeys = list(averaged[0]["groups"]) if "groups" in averaged[0] else None
+        if rkeys is not None:
+            out["redundant_antpairs"] = np.asarray(rkeys, dtype=np.int64).reshape(-1, 2)  # every group's first pair
+            for k in ("data", "model", "resid"):
+                out["redundant_" + k + "_grp"] = np.full((len(pols), ntimes, len(rkeys), nr, nd), np.nan)
     for i, p in enumerate(pols):
         for t, h in fit_info[p].items():
             if "delay_spectrum" not in h:
                 continue
             e = h["delay_spectrum"]
             out["nbls"][i, t] = e["nbls"]
+            if "redundant" in e:
+                x = e["redundant"]
+                out["redundant_window"][i, t], out["redundant_ngroups"][i, t] = x["time_indices"], x["ngroups"]
+                for k in ("data", "model", "resid"):
+                    out["redundant_" + k][i, t] = x[k]
+                    if "groups" in x:
+                        out["redundant_" + k + "_grp"][i, t] = [x["groups"][ap][k] for ap in rkeys]
             if "fringe" in e:
                 x = e["fringe"]
                 out["fringe_window"][i, t], out["fringe_nbls"][i, t] = x["time_indices"], x["nbls"]

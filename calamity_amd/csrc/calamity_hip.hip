@@ -35,6 +35,7 @@
 #include "delay_spectrum_kernels.hpp"
 #include "delay_cross_kernels.hpp"
 #include "delay_fringe_kernels.hpp"
+#include "delay_coherent_kernels.hpp"
 #include "delay_transfer_kernels.hpp"
 #include "degeneracy_kernels.hpp"
 #include "gain_basis_solve_kernels.hpp"
@@ -197,6 +198,8 @@ struct cal_solver {
                                    double* cross_bin, double* diff_bin, double* count_bin) = 0;
   virtual int delay_fringe_spectrum(const cal_delay_fringe_desc* d, const void* g_r, const void* g_i, double* power_grp, double* norm_grp, double* power_bin,
                                     double* count_bin) = 0;
+  virtual int delay_coherent_spectrum(const cal_delay_coherent_desc* d, const void* g_r, const void* g_i, double* power_grp, double* norm_grp, double* power_bin,
+                                      double* count_bin) = 0;
   virtual int delay_transfer(const cal_delay_transfer_desc* d, const void* g_r, const void* g_i, double* absorbed_bl, double* noise_bl, double* absorbed_bin,
                              double* count_bin, cal_fit_errors_counts* counts) = 0;
   virtual int set_delay_transfer_scratch(int64_t bytes) = 0;
@@ -299,6 +302,9 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
   // delay_fringe_spectrum (delay_fringe_kernels.hpp) reuses them all as well, with chunks of whole groups: the rows of the groups in
   // dc_pairs, their scales in dc_scale, Y and then the power in ds_pow; opt_r | opt_i of a call
   DevBuf df_opt;
+  // delay_coherent_spectrum (delay_coherent_kernels.hpp) reuses those of the fringe call from the averaged planes on; the member lists
+  // of a call (set_ptr, rows, coefficients, conjugation flags) and a chunk's set masks
+  DevBuf dk_ptr, dk_row, dk_wgt, dk_conj, dk_mask;
   // delay_transfer (delay_transfer_kernels.hpp): the plan of a call (groups, order, Gram work, W offsets, runs, rows, the bins' lists and
   // the operator image); per chunk N (dt_n), the factor (dt_d) and W | S (dt_x); rhs of the Gram kernel (unused), coeff_var of the factor
   // kernel (unused), ok [ngrps] ints + the two counters; absorbed and noise [nbls][ndelays]; valid | absorbed_bin | count_bin (dt_out; the
@@ -671,7 +677,7 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     CAL_TRY(upload(ant_ptr, p.ant_ptr));
     CAL_TRY(upload(ant_ent, p.ant_ent));
 
-    for (DevBuf* b : {&gains_snap, &gains_alt, &coef_snap, &q1, &gcp1, &gc1, &model_buf, &scratch, &fq_out, &fq_gains, &gs_out, &gs_ptr, &gs_ent, &gs_mask, &cs_rhs, &rw_w0, &rw_out, &ds_op, &ds_normf, &ds_ent, &ds_ptr, &ds_x, &ds_pow, &ds_out, &dc_pairs, &dc_scale, &df_opt, &dt_grp, &dt_order, &dt_work, &dt_woff, &dt_runs, &dt_rows, &dt_ent, &dt_ptr, &dt_op, &dt_n, &dt_d, &dt_x, &dt_rhs, &dt_cv, &dt_ok, &dt_abs, &dt_noise, &dt_out, &dg_z, &dg_w, &dg_geo, &dg_idx, &dg_part, &dg_st, &dg_gout, &dg_gref,
+    for (DevBuf* b : {&gains_snap, &gains_alt, &coef_snap, &q1, &gcp1, &gc1, &model_buf, &scratch, &fq_out, &fq_gains, &gs_out, &gs_ptr, &gs_ent, &gs_mask, &cs_rhs, &rw_w0, &rw_out, &ds_op, &ds_normf, &ds_ent, &ds_ptr, &ds_x, &ds_pow, &ds_out, &dc_pairs, &dc_scale, &df_opt, &dk_ptr, &dk_row, &dk_wgt, &dk_conj, &dk_mask, &dt_grp, &dt_order, &dt_work, &dt_woff, &dt_runs, &dt_rows, &dt_ent, &dt_ptr, &dt_op, &dt_n, &dt_d, &dt_x, &dt_rhs, &dt_cv, &dt_ok, &dt_abs, &dt_noise, &dt_out, &dg_z, &dg_w, &dg_geo, &dg_idx, &dg_part, &dg_st, &dg_gout, &dg_gref,
                        &gn_s, &gn_g0, &gn_save, &gn_x, &gn_res, &gn_ns, &gn_D, &gn_m, &gn_sd, &gn_rows, &gn_part, &gn_scal, &gn_lam, &gn_grp, &gn_rowptr,
                        &lb_vec, &lb_part, &lb_dots, &lb_state, &lb_losses, &lb_count})
       b->release();
@@ -2024,14 +2030,40 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     if (d->nbins == 0 && (power_bin || count_bin)) return fail(CAL_ERR_INVALID, "delay_fringe_spectrum: binned outputs need nbins > 0");
     DelayFringePlan<T> P;  // the refusals of groups, rows, scales and opt; the bins' groups, the chunks, the operator image (report_plan.hpp)
     CAL_TRY(plan_delay_fringe(nbls, nfreqs, fpad, d, ds_bound, P));
-    const int nd = d->ndelays, nbins = d->nbins, ng = d->ngroups, nt = d->ntimes, nr = d->nrates, nq = P.nq, xpitch = P.xpitch, ndpad = P.ndpad,
-              cgroups = P.cgroups;
+    const int ng = d->ngroups, nt = d->ntimes;
+    FringeRun R;
+    CAL_TRY(fringe_begin(d->ndelays, d->nbins, ng, nt, d->nrates, P, power_grp, R));
+    CAL_TRY(dc_pairs.reserve((size_t)ng * nt * sizeof(int32_t), false));
+    HIP_TRY(copy_sync(dc_pairs.p, d->rows, (size_t)ng * nt * sizeof(int32_t), hipMemcpyHostToDevice));
+    CAL_TRY(model_pass(2, [&](T* model_r, T* model_i, T*) {
+      for (int c = 0; c < P.nchunks; ++c) {
+        const long long g0 = (long long)c * P.cgroups;
+        const int nc = (int)std::min<long long>(P.cgroups, ng - g0);
+        hipLaunchKernelGGL(dfringe_rows_kernel<T>, dim3((nc + 3) / 4), dim3(256), 0, stream, model_r, model_i, data_r.as<T>(), data_i.as<T>(), wgts.as<T>(), g,
+                           bl_ant.as<int2>(), dc_pairs.as<int>() + g0 * nt, ds_normf.as<double>(), nc, nt, nfreqs, fpad, P.xpitch, d->what, d->calibrated,
+                           ds_x.as<T>(), R.o_norm + g0);
+        fringe_chunk_tail(R, c, g0, nc);
+      }
+    }));
+    return fringe_end(R, norm_grp, power_bin, count_bin);
+  }
+
+  // What cal_solver_delay_fringe_spectrum and cal_solver_delay_coherent_spectrum share from the masked planes x on: the plan's arrays
+  // on the device and the outputs' places (fringe_begin), per chunk dfringe_transform_kernel, dfringe_time_kernel, dspec_bin_kernel and
+  // the copies of the per-group power (fringe_chunk_tail; the chunk's x in ds_x and its norm_grp are there), then the all-reduce of the
+  // bins and the outputs (fringe_end).
+  struct FringeRun {
+    int nd, nbins, ng, nt, nr, nq, xpitch, ndpad, ncols;
+    size_t nbin_out, time_lds;
+    double *o_norm, *o_pbin, *o_cbin, *y, *pw, *power_grp;
+    const double *opt_r, *opt_i;
+    hipError_t copy_err;
+  };
+  int fringe_begin(int nd, int nbins, int ng, int nt, int nr, const DelayFringePlan<T>& P, double* power_grp, FringeRun& R) {
     CAL_TRY(put(ds_op, P.image, false));
     CAL_TRY(put(ds_normf, P.norm_f, false));
     CAL_TRY(put(dc_scale, P.scale, false));
     CAL_TRY(put(df_opt, P.opt, false));
-    CAL_TRY(dc_pairs.reserve((size_t)ng * nt * sizeof(int32_t), false));
-    HIP_TRY(copy_sync(dc_pairs.p, d->rows, (size_t)ng * nt * sizeof(int32_t), hipMemcpyHostToDevice));
     if (nbins) {
       CAL_TRY(put(ds_ent, P.bin_ent, false));
       CAL_TRY(put(ds_ptr, P.chunk_ptr, false));
@@ -2039,45 +2071,88 @@ struct SolverT final : DevBufRegistry, cal_solver, PlanScalars {  // PlanScalars
     CAL_TRY(ds_out.reserve(P.n_out * sizeof(double)));
     CAL_TRY(ds_x.reserve(P.n_x * sizeof(T), false));
     CAL_TRY(ds_pow.reserve((P.n_y + P.n_pow) * sizeof(double), false));
-    const int ncols = nr * nd;                          // columns of a group's power: [nrates][ndelays]
-    const size_t nbin_out = P.n_out - ng;               // power_bin | count_bin: the exchange payload
-    double* o_norm = ds_out.as<double>();
-    double* o_pbin = o_norm + ng;
-    double* o_cbin = o_pbin + (size_t)nq * nbins * ncols;
-    double* y = ds_pow.as<double>();
-    double* pw = y + P.n_y;
-    const double* opt_r = df_opt.as<double>();
-    const double* opt_i = opt_r + (size_t)nt * nr;
-    const size_t time_lds = (size_t)nt * 2 * kDfCols * sizeof(double);
-    hipError_t copy_err = hipSuccess;
-    CAL_TRY(model_pass(2, [&](T* model_r, T* model_i, T*) {
-      for (int c = 0; c < P.nchunks; ++c) {
-        const long long g0 = (long long)c * cgroups;
-        const int nc = (int)std::min<long long>(cgroups, ng - g0);
-        const int nrows = nc * nt;
-        hipLaunchKernelGGL(dfringe_rows_kernel<T>, dim3((nc + 3) / 4), dim3(256), 0, stream, model_r, model_i, data_r.as<T>(), data_i.as<T>(), wgts.as<T>(), g,
-                           bl_ant.as<int2>(), dc_pairs.as<int>() + g0 * nt, ds_normf.as<double>(), nc, nt, nfreqs, fpad, xpitch, d->what, d->calibrated,
-                           ds_x.as<T>(), o_norm + g0);
-        hipLaunchKernelGGL(dfringe_transform_kernel<T>, dim3((nrows + kDsRows - 1) / kDsRows, ndpad / kDsCols, nq), dim3(256), 0, stream, ds_x.as<T>(),
-                           ds_op.as<T>(), dc_scale.as<double>() + g0 * nt, nrows, xpitch, nd, ndpad, y);
-        hipLaunchKernelGGL(dfringe_time_kernel, dim3(nc, (nd + kDfCols - 1) / kDfCols, nq), dim3(256), time_lds, stream, y, opt_r, opt_i, o_norm + g0, nc, nt,
-                           nr, nd, pw);
-        if (nbins)
-          hipLaunchKernelGGL(dspec_bin_kernel, dim3(nbins, (ncols + 255) / 256, nq), dim3(256), 0, stream, pw, o_norm + g0,
-                             ds_ptr.as<int>() + (size_t)c * nbins * 2, ds_ent.as<int>(), (int)g0, nc, ncols, nbins, c == 0 ? 1 : 0, o_pbin, o_cbin);
-        for (int q = 0; q < nq && power_grp && copy_err == hipSuccess; ++q)  // (the stream orders the copy before the next chunk's kernels)
-          copy_err = hipMemcpyAsync(power_grp + ((size_t)q * ng + g0) * ncols, pw + (size_t)q * nc * ncols, (size_t)nc * ncols * sizeof(double),
-                                    hipMemcpyDeviceToHost, stream);
-      }
-    }));
-    HIP_TRY(copy_err);
+    R.nd = nd, R.nbins = nbins, R.ng = ng, R.nt = nt, R.nr = nr, R.nq = P.nq, R.xpitch = P.xpitch, R.ndpad = P.ndpad;
+    R.ncols = nr * nd;               // columns of a group's power: [nrates][ndelays]
+    R.nbin_out = P.n_out - ng;       // power_bin | count_bin: the exchange payload
+    R.o_norm = ds_out.as<double>();
+    R.o_pbin = R.o_norm + ng;
+    R.o_cbin = R.o_pbin + (size_t)P.nq * nbins * R.ncols;
+    R.y = ds_pow.as<double>();
+    R.pw = R.y + P.n_y;
+    R.opt_r = df_opt.as<double>();
+    R.opt_i = R.opt_r + (size_t)nt * nr;
+    R.time_lds = (size_t)nt * 2 * kDfCols * sizeof(double);
+    R.power_grp = power_grp;
+    R.copy_err = hipSuccess;
+    return CAL_OK;
+  }
+  void fringe_chunk_tail(FringeRun& R, int c, long long g0, int nc) {
+    const int nrows = nc * R.nt, nd = R.nd, nq = R.nq, nbins = R.nbins, ncols = R.ncols;
+    hipLaunchKernelGGL(dfringe_transform_kernel<T>, dim3((nrows + kDsRows - 1) / kDsRows, R.ndpad / kDsCols, nq), dim3(256), 0, stream, ds_x.as<T>(),
+                       ds_op.as<T>(), dc_scale.as<double>() + g0 * R.nt, nrows, R.xpitch, nd, R.ndpad, R.y);
+    hipLaunchKernelGGL(dfringe_time_kernel, dim3(nc, (nd + kDfCols - 1) / kDfCols, nq), dim3(256), R.time_lds, stream, R.y, R.opt_r, R.opt_i, R.o_norm + g0, nc,
+                       R.nt, R.nr, nd, R.pw);
+    if (nbins)
+      hipLaunchKernelGGL(dspec_bin_kernel, dim3(nbins, (ncols + 255) / 256, nq), dim3(256), 0, stream, R.pw, R.o_norm + g0,
+                         ds_ptr.as<int>() + (size_t)c * nbins * 2, ds_ent.as<int>(), (int)g0, nc, ncols, nbins, c == 0 ? 1 : 0, R.o_pbin, R.o_cbin);
+    for (int q = 0; q < nq && R.power_grp && R.copy_err == hipSuccess; ++q)  // (the stream orders the copy before the next chunk's kernels)
+      R.copy_err = hipMemcpyAsync(R.power_grp + ((size_t)q * R.ng + g0) * ncols, R.pw + (size_t)q * nc * ncols, (size_t)nc * ncols * sizeof(double),
+                                  hipMemcpyDeviceToHost, stream);
+  }
+  int fringe_end(FringeRun& R, double* norm_grp, double* power_bin, double* count_bin) {
+    HIP_TRY(R.copy_err);
     // the bins of every rank's groups add up to the array's: ONE all-reduce of nwhat nbins nrates ndelays + nbins doubles
-    if (nbins && comm_on()) CAL_TRY(all_reduce(o_pbin, nbin_out, CAL_XCHG_F64, CAL_XCHG_SUM));
-    CAL_TRY(give(norm_grp, o_norm, (size_t)ng));
-    CAL_TRY(give(power_bin, o_pbin, (size_t)nq * nbins * ncols));
-    CAL_TRY(give(count_bin, o_cbin, (size_t)nbins));
+    if (R.nbins && comm_on()) CAL_TRY(all_reduce(R.o_pbin, R.nbin_out, CAL_XCHG_F64, CAL_XCHG_SUM));
+    CAL_TRY(give(norm_grp, R.o_norm, (size_t)R.ng));
+    CAL_TRY(give(power_bin, R.o_pbin, (size_t)R.nq * R.nbins * R.ncols));
+    CAL_TRY(give(count_bin, R.o_cbin, (size_t)R.nbins));
     HIP_TRY(hipStreamSynchronize(stream));
     return CAL_OK;
+  }
+
+  // cal_solver_delay_coherent_spectrum: the model pass of model(), then per chunk of whole groups dcoherent_rows_kernel and
+  // dcoherent_mask_kernel (delay_coherent_kernels.hpp) for the averaged planes, and the fringe call's tail as it is.  The member lists
+  // are uploaded once; the buffers are those of delay_spectrum and the bound is ds_bound.
+  int delay_coherent_spectrum(const cal_delay_coherent_desc* d, const void* g_r, const void* g_i, double* power_grp, double* norm_grp, double* power_bin,
+                              double* count_bin) override {
+    HIP_TRY(hipSetDevice(device));
+    if (!d) return fail(CAL_ERR_INVALID, "delay_coherent_spectrum: null description");
+    CAL_TRY(require_set("delay_coherent_spectrum", false));
+    const T2* g = nullptr;
+    CAL_TRY(report_gains("delay_coherent_spectrum", g_r, g_i, &g));
+    if (d->ndelays < 1 || d->ndelays > 4096) return fail(CAL_ERR_INVALID, "delay_coherent_spectrum: ndelays = %d lies outside [1, 4096]", d->ndelays);
+    if ((d->what & 7) == 0 || (d->what & ~7))
+      return fail(CAL_ERR_INVALID, "delay_coherent_spectrum: what = %d: bits 0 (data), 1 (model), 2 (residual), at least one", d->what);
+    if (d->calibrated != 0 && d->calibrated != 1) return fail(CAL_ERR_INVALID, "delay_coherent_spectrum: calibrated = %d (0 or 1)", d->calibrated);
+    if (!d->op_r || !d->op_i || !d->norm_f) return fail(CAL_ERR_INVALID, "delay_coherent_spectrum: null operator or norm_f");
+    if (d->nbins < 0) return fail(CAL_ERR_INVALID, "delay_coherent_spectrum: nbins = %d", d->nbins);
+    if ((d->nbins == 0) != (d->bin_of_group == nullptr)) return fail(CAL_ERR_INVALID, "delay_coherent_spectrum: bin_of_group goes with nbins > 0, and only with it");
+    if (d->nbins == 0 && (power_bin || count_bin)) return fail(CAL_ERR_INVALID, "delay_coherent_spectrum: binned outputs need nbins > 0");
+    DelayCoherentPlan<T> P;  // every other refusal; the fringe plan over the averaged planes, the member lists (report_plan.hpp)
+    CAL_TRY(plan_delay_coherent(nbls, nfreqs, fpad, d, ds_bound, P));
+    const int ng = d->ngroups, nt = d->ntimes;
+    FringeRun R;
+    CAL_TRY(fringe_begin(d->ndelays, d->nbins, ng, nt, d->nrates, P.F, power_grp, R));
+    CAL_TRY(put(dk_ptr, P.set_ptr, false));
+    CAL_TRY(put(dk_row, P.member_row, false));
+    CAL_TRY(put(dk_wgt, P.member_wgt, false));
+    CAL_TRY(put(dk_conj, P.member_conj, false));
+    CAL_TRY(dk_mask.reserve(P.n_mask, false));
+    CAL_TRY(model_pass(2, [&](T* model_r, T* model_i, T*) {
+      for (int c = 0; c < P.F.nchunks; ++c) {
+        const long long g0 = (long long)c * P.F.cgroups;
+        const int nc = (int)std::min<long long>(P.F.cgroups, ng - g0);
+        const long long nwaves = (long long)nc * nt * P.nspans;
+        hipLaunchKernelGGL(dcoherent_rows_kernel<T>, dim3((unsigned)((nwaves + 3) / 4)), dim3(256), 0, stream, model_r, model_i, data_r.as<T>(), data_i.as<T>(),
+                           wgts.as<T>(), g, bl_ant.as<int2>(), dk_ptr.as<long long>() + g0 * nt, dk_row.as<int>(), dk_wgt.as<double>(),
+                           dk_conj.as<unsigned char>(), nc * nt, P.nspans, nfreqs, fpad, P.F.xpitch, d->what, d->calibrated, d->weighting, ds_x.as<T>(),
+                           dk_mask.as<unsigned char>());
+        hipLaunchKernelGGL(dcoherent_mask_kernel<T>, dim3((nc + 3) / 4), dim3(256), 0, stream, dk_mask.as<unsigned char>(), ds_normf.as<double>(), nc, nt,
+                           P.F.xpitch, 2 * P.F.nq, ds_x.as<T>(), R.o_norm + g0);
+        fringe_chunk_tail(R, c, g0, nc);
+      }
+    }));
+    return fringe_end(R, norm_grp, power_bin, count_bin);
   }
 
   // cal_solver_delay_transfer: the model pass of model() and coeff_solve_rows_kernel for q (at the call's gains), then per chunk of
@@ -3447,6 +3522,34 @@ int debug_solve_plan(const cal_problem_desc* d, int64_t bound, int what, void* o
   }
   return give(P.lwork);
 }
+// cal_debug_delay_coherent_plan: plan_delay_coherent's arrays as bytes
+template <typename T>
+int debug_delay_coherent_plan(const cal_problem_desc* d, const cal_delay_coherent_desc* x, int64_t scratch_bytes, int what, void* out, int64_t cap, int64_t* bytes) {
+  const char* who = "cal_debug_delay_coherent_plan";
+  auto give = [&](const auto& v) { return plan_bytes(v, out, cap, bytes, who); };
+  ProblemPlan<T> p;
+  CAL_TRY(plan_problem(d, p));
+  if (what < 70 || what > 77) return fail(CAL_ERR_INVALID, "%s: what = %d", who, what);
+  if (x->ndelays < 1 || (x->what & 7) == 0 || (x->what & ~7) || x->nbins < 0 || (x->nbins == 0) != (x->bin_of_group == nullptr) || !x->op_r || !x->op_i ||
+      !x->norm_f || scratch_bytes < 0)
+    return fail(CAL_ERR_INVALID, "%s: what = %d takes a description cal_solver_delay_coherent_spectrum would plan for, and a bound >= 0", who, what);
+  DelayCoherentPlan<T> P;
+  CAL_TRY(plan_delay_coherent(p.nbls, p.nfreqs, p.fpad, x, scratch_bytes == 0 ? kCsScratchDefault : scratch_bytes, P));
+  const DelayFringePlan<T>& F = P.F;
+  switch (what) {
+    case 70:
+      return give(std::vector<int64_t>{F.nq, F.xpitch, F.ndpad, F.cgroups, F.nchunks, (int64_t)F.n_x, (int64_t)(F.n_y + F.n_pow), (int64_t)F.n_out,
+                                       (int64_t)P.n_mask, P.nspans});
+    case 71: return give(F.bin_ent);
+    case 72: return give(F.chunk_ptr);
+    case 73: return give(F.image);
+    case 74: return give(F.norm_f);
+    case 75: return give(F.scale);
+    case 76: return give(F.opt);
+  }
+  return give(P.chunk_members);
+}
+
 // cal_debug_report_plan: the arrays of report_plan.hpp as bytes
 template <typename T>
 int debug_report_plan(const cal_problem_desc* d, const cal_report_plan_desc* r, int what, void* out, int64_t cap, int64_t* bytes) {
@@ -3990,6 +4093,12 @@ int cal_debug_solve_plan(int dtype, const cal_problem_desc* d, int64_t scratch_b
   return dtype == CAL_F32 ? debug_solve_plan<float>(d, bound, what, out, cap_bytes, bytes) : debug_solve_plan<double>(d, bound, what, out, cap_bytes, bytes);
 }
 
+int cal_debug_delay_coherent_plan(int dtype, const cal_problem_desc* d, const cal_delay_coherent_desc* desc, int64_t scratch_bytes, int what, void* out,
+                                  int64_t cap_bytes, int64_t* bytes) {
+  if (!desc || !out || !bytes || cap_bytes < 0 || (dtype != CAL_F32 && dtype != CAL_F64)) return fail(CAL_ERR_INVALID, "cal_debug_delay_coherent_plan: bad argument");
+  return dtype == CAL_F32 ? debug_delay_coherent_plan<float>(d, desc, scratch_bytes, what, out, cap_bytes, bytes)
+                          : debug_delay_coherent_plan<double>(d, desc, scratch_bytes, what, out, cap_bytes, bytes);
+}
 int cal_debug_report_plan(int dtype, const cal_problem_desc* d, const cal_report_plan_desc* r, int what, void* out, int64_t cap_bytes, int64_t* bytes) {
   if (!r || !out || !bytes || cap_bytes < 0 || (dtype != CAL_F32 && dtype != CAL_F64)) return fail(CAL_ERR_INVALID, "cal_debug_report_plan: bad argument");
   return dtype == CAL_F32 ? debug_report_plan<float>(d, r, what, out, cap_bytes, bytes) : debug_report_plan<double>(d, r, what, out, cap_bytes, bytes);
@@ -4226,6 +4335,11 @@ int cal_solver_delay_fringe_spectrum(cal_solver* s, const cal_delay_fringe_desc*
                                      double* power_bin, double* count_bin) {
   NEED(s);
   return s->delay_fringe_spectrum(desc, g_r, g_i, power_grp, norm_grp, power_bin, count_bin);
+}
+int cal_solver_delay_coherent_spectrum(cal_solver* s, const cal_delay_coherent_desc* desc, const void* g_r, const void* g_i, double* power_grp, double* norm_grp,
+                                       double* power_bin, double* count_bin) {
+  NEED(s);
+  return s->delay_coherent_spectrum(desc, g_r, g_i, power_grp, norm_grp, power_bin, count_bin);
 }
 int cal_solver_delay_transfer(cal_solver* s, const cal_delay_transfer_desc* desc, const void* g_r, const void* g_i, double* absorbed_bl, double* noise_bl,
                               double* absorbed_bin, double* count_bin, cal_fit_errors_counts* counts) {

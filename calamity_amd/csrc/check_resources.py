@@ -23,6 +23,7 @@ two waves per SIMD in the transform kernel.
 SIMD in the transform kernel.
 `dfringe_rows_kernel`, `dfringe_transform_kernel` (both dtypes), `dfringe_time_kernel` (delay_fringe_kernels.hpp): no scratch, no spilled
 VGPRs, two waves per SIMD in the transform kernel and in the time kernel (two workgroups of four waves per CU at 64 times).
+`dcoherent_rows_kernel`, `dcoherent_mask_kernel` (delay_coherent_kernels.hpp), both dtypes: no scratch, no spilled VGPRs.
 `dtransfer_basis_kernel`, `dtransfer_power_kernel` (delay_transfer_kernels.hpp), both dtypes: no scratch, no spilled VGPRs, and two waves
 per SIMD in the power kernel.
 `degen_rows_kernel`, `degen_sum_kernel`, `degen_solve_kernel`, `degen_phase_kernel`, `degen_apply_gains_kernel`, `degen_apply_rows_kernel`
@@ -105,6 +106,13 @@ for line in sys.stdin:
             if ("dfringe_transform_kernel" in cur or "dfringe_time_kernel" in cur) and int(m.group(2)) < 2:
                 bad.append(f"{cur}: occupancy {m.group(2)} waves/SIMD (< 2)")
         elif m and int(m.group(2)) != 0:
+            bad.append(f"{cur}: {m.group(1)} = {m.group(2)}")
+        continue
+    if cur is not None and any(k in cur for k in ("dcoherent_rows_kernel", "dcoherent_mask_kernel")):
+        # the two in front of the coherent spectrum: a set's sums in double stay in registers (28 doubles per lane in fp32): no scratch, no
+        # spilled VGPRs
+        m = re.search(r"remark:\s+(ScratchSize \[bytes/lane\]|VGPRs Spill): (\d+)", line)
+        if m and int(m.group(2)) != 0:
             bad.append(f"{cur}: {m.group(1)} = {m.group(2)}")
         continue
     if cur is not None and any(k in cur for k in ("dtransfer_basis_kernel", "dtransfer_power_kernel")):

@@ -1,5 +1,5 @@
 // report_plan.hpp -- what the post-fit reports cal_solver_delay_spectrum, cal_solver_delay_cross_spectrum, cal_solver_delay_fringe_spectrum,
-// cal_solver_delay_transfer and cal_solver_fix_degeneracies decide
+// cal_solver_delay_coherent_spectrum, cal_solver_delay_transfer and cal_solver_fix_degeneracies decide
 // before they launch, on the host alone: the rows of every bin and of every slice, how they are cut into chunks and segments, and the padded images the kernels read.
 // No HIP or RCCL runtime call and no solver: SolverT uploads these plans at every call; cal_debug_report_plan returns them as bytes
 // (tests/test_report_plan_host.py).  dspec_bin_kernel adds a bin's rows, and degen_sum_kernel a slice's segments, in the order written
@@ -11,6 +11,7 @@
 #include "delay_spectrum_kernels.hpp"
 #include "delay_cross_kernels.hpp"
 #include "delay_fringe_kernels.hpp"
+#include "delay_coherent_kernels.hpp"
 #include "delay_transfer_kernels.hpp"
 #include "degeneracy_kernels.hpp"
 
@@ -180,42 +181,42 @@ struct DelayFringePlan {
 // A chunk of whole groups' scratch -- per group nq 2 T xpitch elements of T for the masked planes, nq 2 T ndelays doubles of Y and
 // nq nrates ndelays doubles of power -- stays under `bound` bytes (never less than one group).  Everything of the description that can
 // be refused on the host is refused here: ngroups, ntimes, nrates, the rows, the scales, opt, the bins.
-template <typename T>
-int plan_delay_fringe(int nbls, int nfreqs, int fpad, const cal_delay_fringe_desc* d, int64_t bound, DelayFringePlan<T>& P) {
+// plan_fringe_core is the rule itself, shared with plan_delay_coherent below: `rows(0)` refuses what stands in for the rows when it is
+// null, `rows(1)` its contents, at the places the fringe call has always refused them; `extra` bytes per group are added to the scratch.
+template <typename T, typename Rows>
+int plan_fringe_core(const char* who, int nfreqs, int fpad, const cal_delay_fringe_desc* d, Rows rows, size_t extra, int64_t bound, DelayFringePlan<T>& P) {
   const int nd = d->ndelays, nbins = d->nbins, ng = d->ngroups, nt = d->ntimes, nr = d->nrates;
-  if (ng < 1) return fail(CAL_ERR_INVALID, "delay_fringe_spectrum: ngroups = %d (at least 1)", ng);
-  if (nt < 1 || nt > 64) return fail(CAL_ERR_INVALID, "delay_fringe_spectrum: ntimes = %d lies outside [1, 64]", nt);
-  if (nr < 1 || nr > 64) return fail(CAL_ERR_INVALID, "delay_fringe_spectrum: nrates = %d lies outside [1, 64]", nr);
-  if (!d->rows) return fail(CAL_ERR_INVALID, "delay_fringe_spectrum: null rows");
-  if (!d->opt_r || !d->opt_i) return fail(CAL_ERR_INVALID, "delay_fringe_spectrum: null opt");
+  if (ng < 1) return fail(CAL_ERR_INVALID, "%s: ngroups = %d (at least 1)", who, ng);
+  if (nt < 1 || nt > 64) return fail(CAL_ERR_INVALID, "%s: ntimes = %d lies outside [1, 64]", who, nt);
+  if (nr < 1 || nr > 64) return fail(CAL_ERR_INVALID, "%s: nrates = %d lies outside [1, 64]", who, nr);
+  CAL_TRY(rows(0));
+  if (!d->opt_r || !d->opt_i) return fail(CAL_ERR_INVALID, "%s: null opt", who);
   const size_t nrow = (size_t)ng * nt;
-  if (nrow > (size_t)(1u << 30)) return fail(CAL_ERR_INVALID, "delay_fringe_spectrum: ngroups ntimes = %lld is too many", (long long)nrow);
-  for (size_t k = 0; k < nrow; ++k)
-    if (d->rows[k] < 0 || d->rows[k] >= nbls)
-      return fail(CAL_ERR_INVALID, "delay_fringe_spectrum: rows[%d][%d] = %d lies outside [0, %d)", (int)(k / nt), (int)(k % nt), d->rows[k], nbls);
+  if (nrow > (size_t)(1u << 30)) return fail(CAL_ERR_INVALID, "%s: ngroups ntimes = %lld is too many", who, (long long)nrow);
+  CAL_TRY(rows(1));
   P.scale.assign(nrow, 1.0);
   if (d->scale) {
     for (size_t k = 0; k < nrow; ++k)
-      if (!std::isfinite(d->scale[k])) return fail(CAL_ERR_INVALID, "delay_fringe_spectrum: scale[%d][%d] is not finite", (int)(k / nt), (int)(k % nt));
+      if (!std::isfinite(d->scale[k])) return fail(CAL_ERR_INVALID, "%s: scale[%d][%d] is not finite", who, (int)(k / nt), (int)(k % nt));
     std::copy(d->scale, d->scale + nrow, P.scale.begin());
   }
   const size_t nopt = (size_t)nt * nr;
   for (size_t k = 0; k < nopt; ++k)
     if (!std::isfinite(d->opt_r[k]) || !std::isfinite(d->opt_i[k]))
-      return fail(CAL_ERR_INVALID, "delay_fringe_spectrum: opt[%d][%d] is not finite", (int)(k / nr), (int)(k % nr));
+      return fail(CAL_ERR_INVALID, "%s: opt[%d][%d] is not finite", who, (int)(k / nr), (int)(k % nr));
   P.opt.resize(2 * nopt);
   std::copy(d->opt_r, d->opt_r + nopt, P.opt.begin());
   std::copy(d->opt_i, d->opt_i + nopt, P.opt.begin() + nopt);
   P.nq = (d->what & 1) + (d->what >> 1 & 1) + (d->what >> 2 & 1);
-  if ((long long)P.nq * nbins * nr * nd + nbins > (1ll << 31) - 1) return fail(CAL_ERR_INVALID, "delay_fringe_spectrum: nbins = %d is too many", nbins);
+  if ((long long)P.nq * nbins * nr * nd + nbins > (1ll << 31) - 1) return fail(CAL_ERR_INVALID, "%s: nbins = %d is too many", who, nbins);
   for (int g = 0; g < ng && nbins; ++g)
     if (d->bin_of_group[g] < -1 || d->bin_of_group[g] >= nbins)
-      return fail(CAL_ERR_INVALID, "delay_fringe_spectrum: bin_of_group[%d] = %d lies outside [-1, %d)", g, d->bin_of_group[g], nbins);
+      return fail(CAL_ERR_INVALID, "%s: bin_of_group[%d] = %d lies outside [-1, %d)", who, g, d->bin_of_group[g], nbins);
   std::vector<int> bin_ptr;
-  CAL_TRY(plan_bin_lists("delay_fringe_spectrum", ng, nbins, d->bin_of_group, bin_ptr, P.bin_ent));
+  CAL_TRY(plan_bin_lists(who, ng, nbins, d->bin_of_group, bin_ptr, P.bin_ent));
   P.xpitch = ds_xpitch(fpad);
   P.ndpad = ds_ndpad(nd);
-  const size_t group_bytes = (size_t)P.nq * 2 * nt * P.xpitch * sizeof(T) + (size_t)P.nq * 2 * nt * nd * sizeof(double) + (size_t)P.nq * nr * nd * sizeof(double);
+  const size_t group_bytes = (size_t)P.nq * 2 * nt * P.xpitch * sizeof(T) + (size_t)P.nq * 2 * nt * nd * sizeof(double) + (size_t)P.nq * nr * nd * sizeof(double) + extra;
   long long cgroups = std::max<long long>(1, bound / (long long)group_bytes);
   cgroups = std::min<long long>(cgroups, ng);  // (ngroups ntimes fits an int: so do a chunk's rows)
   P.cgroups = (int)cgroups;
@@ -237,6 +238,88 @@ int plan_delay_fringe(int nbls, int nfreqs, int fpad, const cal_delay_fringe_des
   P.n_y = (size_t)P.nq * 2 * cgroups * nt * nd;
   P.n_pow = (size_t)P.nq * cgroups * nr * nd;
   P.n_out = (size_t)ng + (size_t)P.nq * nbins * nr * nd + nbins;
+  return CAL_OK;
+}
+
+template <typename T>
+int plan_delay_fringe(int nbls, int nfreqs, int fpad, const cal_delay_fringe_desc* d, int64_t bound, DelayFringePlan<T>& P) {
+  const int nt = d->ntimes;
+  const size_t nrow = (size_t)d->ngroups * nt;
+  return plan_fringe_core<T>("delay_fringe_spectrum", nfreqs, fpad, d, [&](int contents) -> int {
+    if (!contents) return d->rows ? (int)CAL_OK : fail(CAL_ERR_INVALID, "delay_fringe_spectrum: null rows");
+    for (size_t k = 0; k < nrow; ++k)
+      if (d->rows[k] < 0 || d->rows[k] >= nbls)
+        return fail(CAL_ERR_INVALID, "delay_fringe_spectrum: rows[%d][%d] = %d lies outside [0, %d)", (int)(k / nt), (int)(k % nt), d->rows[k], nbls);
+    return CAL_OK;
+  }, 0, bound, P);
+}
+
+// ---- cal_solver_delay_coherent_spectrum --------------------------------------------------------------------------------------------
+// The fringe plan over the averaged planes (F: the same chunks of whole groups, bins, images, scales and opt), the member lists as they
+// are uploaded once per call, and every chunk's range of members.
+template <typename T>
+struct DelayCoherentPlan {
+  DelayFringePlan<T> F;
+  std::vector<long long> set_ptr;       // [ngroups ntimes + 1]
+  std::vector<int> member_row;          // [nmembers]
+  std::vector<double> member_wgt;       // [nmembers]: the description's, or ones
+  std::vector<unsigned char> member_conj;  // [nmembers]: the description's, or zeros
+  std::vector<int64_t> chunk_members;   // [nchunks][2]: the chunk's members as positions in the member arrays
+  int nspans = 0;                       // spans of 64 V channels of a row of the averaged planes
+  size_t n_mask = 0;                    // bytes of a chunk's set masks
+};
+
+// plan_fringe_core with the sets in the place of the rows, and a group's set masks (ntimes pitch bytes) counted into its scratch.
+// Refused here as well: a set_ptr that does not start at 0, falls, or does not end at nmembers; a member row outside [0, nbls); a
+// coefficient that is negative or not finite; a member_conj other than 0 or 1; a weighting other than 0 or 1; nmembers above 2^30.
+template <typename T>
+int plan_delay_coherent(int nbls, int nfreqs, int fpad, const cal_delay_coherent_desc* d, int64_t bound, DelayCoherentPlan<T>& P) {
+  const char* who = "delay_coherent_spectrum";
+  const cal_delay_fringe_desc fd{d->ndelays, d->what, d->calibrated, d->ngroups, d->ntimes, d->nrates, nullptr, d->scale, d->nbins, d->bin_of_group,
+                                 d->op_r, d->op_i, d->norm_f, d->opt_r, d->opt_i};
+  const int nt = d->ntimes;
+  const int64_t nm = d->nmembers;
+  const size_t nsets = (size_t)std::max(d->ngroups, 0) * (size_t)std::max(nt, 0);
+  const size_t mask_bytes = (size_t)std::max(nt, 0) * ds_xpitch(fpad);
+  CAL_TRY(plan_fringe_core<T>(who, nfreqs, fpad, &fd, [&](int contents) -> int {
+    if (!contents) {
+      if (d->weighting != 0 && d->weighting != 1) return fail(CAL_ERR_INVALID, "%s: weighting = %d (0: the coefficients, 1: coefficients times weights)", who, d->weighting);
+      if (nm < 0 || nm > (int64_t)1 << 30) return fail(CAL_ERR_INVALID, "%s: nmembers = %lld lies outside [0, 2^30]", who, (long long)nm);
+      if (!d->set_ptr) return fail(CAL_ERR_INVALID, "%s: null set_ptr", who);
+      if (nm > 0 && !d->member_row) return fail(CAL_ERR_INVALID, "%s: null member_row", who);
+      return CAL_OK;
+    }
+    if (d->set_ptr[0] != 0) return fail(CAL_ERR_INVALID, "%s: set_ptr[0] = %lld (it starts at 0)", who, (long long)d->set_ptr[0]);
+    for (size_t v = 0; v < nsets; ++v)
+      if (d->set_ptr[v + 1] < d->set_ptr[v])
+        return fail(CAL_ERR_INVALID, "%s: set_ptr[%lld] = %lld falls below set_ptr[%lld] = %lld", who, (long long)v + 1, (long long)d->set_ptr[v + 1], (long long)v,
+                    (long long)d->set_ptr[v]);
+    if (d->set_ptr[nsets] != nm)
+      return fail(CAL_ERR_INVALID, "%s: set_ptr ends at %lld, not at nmembers = %lld", who, (long long)d->set_ptr[nsets], (long long)nm);
+    for (int64_t k = 0; k < nm; ++k) {
+      if (d->member_row[k] < 0 || d->member_row[k] >= nbls)
+        return fail(CAL_ERR_INVALID, "%s: member_row[%lld] = %d lies outside [0, %d)", who, (long long)k, d->member_row[k], nbls);
+      if (d->member_wgt && !(std::isfinite(d->member_wgt[k]) && d->member_wgt[k] >= 0.0))
+        return fail(CAL_ERR_INVALID, "%s: member_wgt[%lld] is negative or not finite", who, (long long)k);
+      if (d->member_conj && d->member_conj[k] > 1) return fail(CAL_ERR_INVALID, "%s: member_conj[%lld] = %d (0 or 1)", who, (long long)k, (int)d->member_conj[k]);
+    }
+    return CAL_OK;
+  }, mask_bytes, bound, P.F));
+  P.set_ptr.assign(d->set_ptr, d->set_ptr + nsets + 1);
+  P.member_row.assign(d->member_row, d->member_row + nm);
+  P.member_wgt.assign((size_t)nm, 1.0);
+  if (d->member_wgt) std::copy(d->member_wgt, d->member_wgt + nm, P.member_wgt.begin());
+  P.member_conj.assign((size_t)nm, 0);
+  if (d->member_conj) std::copy(d->member_conj, d->member_conj + nm, P.member_conj.begin());
+  P.chunk_members.resize((size_t)P.F.nchunks * 2);
+  for (int c = 0; c < P.F.nchunks; ++c) {
+    const long long g0 = (long long)c * P.F.cgroups, g1 = std::min<long long>(d->ngroups, g0 + P.F.cgroups);
+    P.chunk_members[2 * c] = P.set_ptr[(size_t)g0 * nt];
+    P.chunk_members[2 * c + 1] = P.set_ptr[(size_t)g1 * nt];
+  }
+  constexpr int V = 16 / (int)sizeof(T);
+  P.nspans = (P.F.xpitch + 64 * V - 1) / (64 * V);
+  P.n_mask = (size_t)P.F.cgroups * mask_bytes;
   return CAL_OK;
 }
 

@@ -144,7 +144,7 @@ def batch_time_slices(parts, per_slice=False):
     return out, start
 
 
-def exchange_spec(nants, nfreqs, reg_sum=False, delay_spectrum=None, delay_transfer=None, delay_cross=None, delay_fringe=None):
+def exchange_spec(nants, nfreqs, reg_sum=False, delay_spectrum=None, delay_transfer=None, delay_cross=None, delay_fringe=None, delay_coherent=None):
     """What one step exchanges between ranks: the gain-gradient parts (interleaved re/im, one part
     without and three with the "sum" regulariser) in the fit dtype, plus four float64 scalars (loss, S_r, S_i, spare).
     ``fit_quality_f64``: what ONE ``fit_quality`` call exchanges, once (not per step): the planes chisq_ant | wsum_ant,
@@ -158,7 +158,9 @@ def exchange_spec(nants, nfreqs, reg_sum=False, delay_spectrum=None, delay_trans
     ``delay_cross_f64`` (only with ``delay_cross=(nstat, nwhat, nbins, ndelays)``): what ONE ``delay_cross_spectrum`` call with bins
     exchanges, once: cross_bin | diff_bin | count_bin, ``nstat nwhat nbins ndelays + nbins`` float64 (cal_solver_delay_cross_spectrum).
     ``delay_fringe_f64`` (only with ``delay_fringe=(nwhat, nbins, nrates, ndelays)``): what ONE ``delay_fringe_spectrum`` call with bins
-    exchanges, once: power_bin | count_bin, ``nwhat nbins nrates ndelays + nbins`` float64 (cal_solver_delay_fringe_spectrum)."""
+    exchanges, once: power_bin | count_bin, ``nwhat nbins nrates ndelays + nbins`` float64 (cal_solver_delay_fringe_spectrum).
+    ``delay_coherent_f64`` (only with ``delay_coherent=(nwhat, nbins, nrates, ndelays)``): the same for ONE ``delay_coherent_spectrum``
+    call with bins (cal_solver_delay_coherent_spectrum)."""
     spec = dict(gain_grad_reals=(3 if reg_sum else 1) * 2 * nants * nfreqs, scalars_f64=4, fit_quality_f64=2 * nants * nfreqs,
                 gain_solve_f64=3 * nants * nfreqs)
     if delay_spectrum is not None:
@@ -173,4 +175,7 @@ def exchange_spec(nants, nfreqs, reg_sum=False, delay_spectrum=None, delay_trans
     if delay_fringe is not None:
         nwhat, nbins, nrates, ndelays = (int(v) for v in delay_fringe)
         spec["delay_fringe_f64"] = nwhat * nbins * nrates * ndelays + nbins
+    if delay_coherent is not None:
+        nwhat, nbins, nrates, ndelays = (int(v) for v in delay_coherent)
+        spec["delay_coherent_f64"] = nwhat * nbins * nrates * ndelays + nbins
     return spec

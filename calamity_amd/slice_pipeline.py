@@ -193,7 +193,7 @@ def report(fitter, nt, arrs, cfg, result):
     """Stage 3, after ``drive``: the reported parameters (every slice's own minimum with ``use_min``, calibration.py:702-710; the
     coefficients the fit was handed with ``freeze_model``, :730-732), the model rows from one ``A c`` pass (:1271-1292), then what
     was asked for at those parameters, on the data and weights the fit used: quality, errors (with the ``chisq_bl`` of the quality
-    pass), delay spectra, their transfer, the cross spectra of paired times and the delay / fringe-rate planes of whole windows -- and the degeneracy fix last, which leaves the product they depend on as it is.  ``fitted``: the reported
+    pass), delay spectra, their transfer, the cross spectra of paired times, the delay / fringe-rate planes of whole windows and those of the redundant groups' averages -- and the degeneracy fix last, which leaves the product they depend on as it is.  ``fitted``: the reported
     ``(g_r, g_i, c_r, c_i)`` before that fix, what the loop hands to the next time."""
     prob, errs, dspec, degen = cfg.prob, cfg.errs, cfg.dspec, cfg.degen
     results = result.loops * nt if cfg.gain_time_basis is not None else result.loops  # a joint fit is one loop: every time reports it
@@ -209,7 +209,7 @@ def report(fitter, nt, arrs, cfg, result):
                 cm_r[gb], cm_i[gb] = best[2][gb], best[3][gb]
     fitter.set_params(c_r=cm_r, c_i=cm_i)
     m_r, m_i = fitter.model()
-    out = dict(result=result, results=results, fitted=(gm_r, gm_i, cm_r, cm_i), quality=None, errors=None, spectra=None, transfer=None, cross=None, fringe=None, fixed=None)
+    out = dict(result=result, results=results, fitted=(gm_r, gm_i, cm_r, cm_i), quality=None, errors=None, spectra=None, transfer=None, cross=None, fringe=None, redundant=None, fixed=None)
     if cfg.fit_quality:
         out["quality"] = fitter.fit_quality(gm_r, gm_i)
     if errs is not None and (errs["with_gains"] or errs["basis_gains"] or not cfg.freeze_model):
@@ -239,6 +239,14 @@ def report(fitter, nt, arrs, cfg, result):
             out["fringe"] = dict(fitter.delay_fringe_spectrum(dspec["op"], dspec["norm_f"], rows, fr["opt"], scale=scale, calibrated=dspec["calibrated"],
                                                               bin_of_group=bins, nbins=len(windows) * dspec["nbins"], per_group=fr["per_group"], g_r=gm_r, g_i=gm_i),
                                  windows=windows, time_index=list(arrs["time_index"]))
+        rd = dspec.get("redundant")
+        windows = cal.delay_fringe_windows(arrs["polnum"], arrs["time_index"], rd["ntimes"], rd["times"], rd["dt"]) if rd is not None else []
+        if windows:  # the redundant groups' averages over whole windows: the spectrum's operator and gains, calibrated; a bin per (window, length bin of the groups)
+            set_ptr, member_row, member_conj, scale, bins = cal.delay_redundant_sets(windows, rd, arrs["rms"], prob.nbls)
+            out["redundant"] = dict(fitter.delay_coherent_spectrum(dspec["op"], dspec["norm_f"], set_ptr, member_row, rd["opt"], member_conj=member_conj,
+                                                                   weighting=rd["weighting"], scale=scale, calibrated=True, bin_of_group=bins,
+                                                                   nbins=len(windows) * rd["nbins"], per_group=rd["per_group"], g_r=gm_r, g_i=gm_i),
+                                    windows=windows, time_index=list(arrs["time_index"]))
     if degen is not None:
         ref_phase = (arrs["g_r"], arrs["g_i"]) if degen["phase_ref"] else (None, None)
         out["fixed"] = fitter.fix_degeneracies(arrs["s_r"], arrs["s_i"], degen["antpos"], ref_w=arrs["r_w"], mode=degen["mode"], iters=degen["iters"],
@@ -297,6 +305,11 @@ def write(cfg, sl, t, out):
                 if t in win:
                     hist["delay_spectrum"]["fringe"] = cal.delay_fringe_entry(out["fringe"], cfg.dspec, k, [out["fringe"]["time_index"][m] for m in win], prob,
                                                                               gains.ant_array)
+        if out["redundant"] is not None:
+            for k, win in enumerate(out["redundant"]["windows"]):
+                if t in win:
+                    hist["delay_spectrum"]["redundant"] = cal.delay_redundant_entry(out["redundant"], cfg.dspec["redundant"], k,
+                                                                                    [out["redundant"]["time_index"][m] for m in win], rms)
     if out["results"][t][1]:
         echo(f"Tolerance thresshold met for time {sl['time_index']}. Terminating...\n ", verbose=cfg.verbose)
     if not cfg.freeze_model and cfg.model_regularization == "post_hoc":

@@ -583,6 +583,93 @@ class HipFitSolver:
             out["per_group"] = {q: p_grp[i] for i, q in enumerate(names)}
         return out
 
+    def delay_coherent_spectrum(self, op, norm_f, set_ptr, member_row, opt, member_wgt=None, member_conj=None, weighting="uniform", scale=None,
+                                what=("data", "model", "resid"), calibrated=False, bin_of_group=None, nbins=0, per_group=False, g_r=None, g_i=None):
+        """Delay / fringe-rate power of redundant averages (cal_solver_delay_coherent_spectrum): the rows of a redundant group are
+        averaged BEFORE they are transformed and squared, so that noise power falls as 1 / N in the group size, where the mean of
+        ``delay_fringe_spectrum``'s powers cannot.  ``op``, ``norm_f``, ``opt``, ``scale``, ``what``, ``calibrated``, the bins, ``g_r``,
+        ``g_i`` and the returned dictionary are ``delay_fringe_spectrum``'s.  A group has ``T = opt.shape[0]`` SETS of rows; set
+        ``v = g T + t`` holds the members ``set_ptr[v] .. set_ptr[v + 1]`` (``set_ptr`` ``[ngroups T + 1]``, from 0, never falling) of
+        ``member_row`` (rows of this solver, repeats allowed), with coefficients ``member_wgt`` (finite, ``>= 0``; ``None``: ones) and
+        flags ``member_conj`` (0 / 1: the row holds the pair reversed; ``None``: none)::
+
+            u_k      = member_wgt[k]                          weighting="uniform"
+                     = member_wgt[k] w[row_k]                 weighting="weights"      both 0 where w[row_k] == 0
+            xbar_q[v]= sum_k u_k c_k(q[row_k]) / sum_k u_k    in float64, k ascending, rounded once to the dtype; 0 where the sum of u is 0
+            mask_g   = AND over t of (sum_k u_k > 0)
+            x_q[g][t]= mask_g xbar_q[g T + t]
+
+        and from ``x_q`` on everything is ``delay_fringe_spectrum``'s.  An empty set gives its group ``norm_grp == 0``, power 0 and no
+        bin.  Sets of one member with unit coefficient give ``delay_fringe_spectrum`` of those rows to the bit."""
+        if (g_r is None) != (g_i is None):
+            raise ValueError("give both g_r and g_i, or neither")
+        if weighting not in ("uniform", "weights"):
+            raise ValueError(f"weighting must be 'uniform' or 'weights', got {weighting!r}")
+        what = (what,) if isinstance(what, str) else tuple(what)
+        if not what or any(q not in _lib.DELAY_SPECTRUM_WHAT for q in what) or len(set(what)) != len(what):
+            raise ValueError(f"what must name one or more of {sorted(_lib.DELAY_SPECTRUM_WHAT)} once each, got {what!r}")
+        names = [q for q in ("data", "model", "resid") if q in what]  # the library's order
+        op = np.asarray(op)
+        if op.ndim != 2 or op.shape[0] != self.nfreqs:
+            raise ValueError(f"op must be [nfreqs = {self.nfreqs}, ndelays], got shape {op.shape}")
+        nd = op.shape[1]
+        op_r, op_i = self._real(op.real), self._real(op.imag)
+        norm_f = np.ascontiguousarray(norm_f, dtype=np.float64)
+        if norm_f.shape != (self.nfreqs,):
+            raise ValueError(f"norm_f must be [nfreqs = {self.nfreqs}], got shape {norm_f.shape}")
+        opt = np.asarray(opt, dtype=np.complex128)
+        if opt.ndim != 2 or opt.shape[0] < 1 or opt.shape[1] < 1:
+            raise ValueError(f"opt must be [ntimes >= 1, nrates >= 1], got shape {opt.shape}")
+        ntimes, nrates = opt.shape
+        opt_r, opt_i = np.ascontiguousarray(opt.real), np.ascontiguousarray(opt.imag)
+        set_ptr = np.ascontiguousarray(set_ptr, dtype=np.int64)
+        if set_ptr.ndim != 1 or len(set_ptr) < ntimes + 1 or (len(set_ptr) - 1) % ntimes:
+            raise ValueError(f"set_ptr must be [ngroups ntimes + 1] with ntimes = {ntimes} and ngroups >= 1, got shape {set_ptr.shape}")
+        ngroups = (len(set_ptr) - 1) // ntimes
+        member_row = np.ascontiguousarray(member_row, dtype=np.int32)
+        if member_row.ndim != 1:
+            raise ValueError(f"member_row must be [nmembers], got shape {member_row.shape}")
+        nmembers = len(member_row)
+        if member_wgt is not None:
+            member_wgt = np.ascontiguousarray(member_wgt, dtype=np.float64)
+            if member_wgt.shape != (nmembers,):
+                raise ValueError(f"member_wgt must be [nmembers = {nmembers}], got shape {member_wgt.shape}")
+        if member_conj is not None:
+            member_conj = np.ascontiguousarray(member_conj, dtype=np.uint8)  # (the library refuses anything but 0 and 1)
+            if member_conj.shape != (nmembers,):
+                raise ValueError(f"member_conj must be [nmembers = {nmembers}], got shape {member_conj.shape}")
+        if scale is not None:
+            scale = np.ascontiguousarray(scale, dtype=np.float64)
+            if scale.shape != (ngroups, ntimes):
+                raise ValueError(f"scale must be [ngroups = {ngroups}, ntimes = {ntimes}], got shape {scale.shape}")
+        nbins = int(nbins)
+        if (bin_of_group is None) != (nbins == 0):
+            raise ValueError("give bin_of_group and nbins > 0 together, or neither")
+        bins = None
+        if bin_of_group is not None:
+            bins = np.ascontiguousarray(bin_of_group, dtype=np.int32)
+            if bins.shape != (ngroups,):
+                raise ValueError(f"bin_of_group must be [ngroups = {ngroups}], got shape {bins.shape}")
+        gs = (self.nants, self.nfreqs)
+        a = None if g_r is None else self._real(g_r, gs)
+        b = None if g_i is None else self._real(g_i, gs)
+        d = _lib.DelayCoherentDesc(nd, sum(_lib.DELAY_SPECTRUM_WHAT[q] for q in names), int(bool(calibrated)), ngroups, ntimes, nrates, set_ptr.ctypes.data,
+                                   member_row.ctypes.data if nmembers else None, None if member_wgt is None else member_wgt.ctypes.data,
+                                   None if member_conj is None else member_conj.ctypes.data, int(weighting == "weights"),
+                                   None if scale is None else scale.ctypes.data, nbins, None if bins is None else bins.ctypes.data, op_r.ctypes.data,
+                                   op_i.ctypes.data, norm_f.ctypes.data, opt_r.ctypes.data, opt_i.ctypes.data, nmembers)
+        norm_grp = np.empty(ngroups, dtype=np.float64)
+        p_grp = np.empty((len(names), ngroups, nrates, nd), dtype=np.float64) if per_group else None
+        p_bin = np.empty((len(names), nbins, nrates, nd), dtype=np.float64) if nbins else None
+        c_bin = np.empty(nbins, dtype=np.float64) if nbins else None
+        _lib.check(self._lib.cal_solver_delay_coherent_spectrum(self._h, C.byref(d), _ptr(a), _ptr(b), _ptr(p_grp), _ptr(norm_grp), _ptr(p_bin), _ptr(c_bin)))
+        out = {"norm_grp": norm_grp}
+        if nbins:
+            out.update({q: p_bin[i] for i, q in enumerate(names)}, count_bin=c_bin)
+        if per_group:
+            out["per_group"] = {q: p_grp[i] for i, q in enumerate(names)}
+        return out
+
     def delay_transfer(self, op, ridge=1e-6, calibrated=False, bin_of_bl=None, nbins=0, per_baseline=False, g_r=None, g_i=None):
         """The signal loss of the fit in delay space (cal_solver_delay_transfer): the share of the power at every delay that the
         coefficient fit itself removes.  ``op`` ``[nfreqs, ndelays]`` complex: the operator of ``delay_spectrum``.  With

@@ -862,6 +862,84 @@ typedef struct cal_delay_fringe_desc {
 } cal_delay_fringe_desc;
 int cal_solver_delay_fringe_spectrum(cal_solver* s, const cal_delay_fringe_desc* desc, const void* g_r, const void* g_i, double* power_grp,
                                      double* norm_grp, double* power_bin, double* count_bin);
+/* Delay / fringe-rate power of redundant averages: the coherent sum.  cal_solver_delay_spectrum, cal_solver_delay_cross_spectrum and
+ * cal_solver_delay_fringe_spectrum square ONE baseline row at a time and reach a baseline-length bin only as a mean of powers, an
+ * incoherent average.  A power-spectrum pipeline for a redundant array adds the calibrated visibilities of a redundant group first,
+ * then transforms and squares: noise power then falls as 1 / N in the group size.  The notation is that of
+ * cal_solver_delay_fringe_spectrum: row b, G, m, w and the quantities q = data, model, residual (calibrated or not), formed in the
+ * solver's dtype exactly as there, under the row's own mask (w[b][f] != 0).
+ * A group g has T = ntimes SETS.  Set v = g T + t holds the members k in [set_ptr[v], set_ptr[v + 1]).  Each member has a row
+ * member_row[k] in [0, nbls), repeats allowed; a coefficient omega_k = member_wgt[k], finite and >= 0 (NULL: ones); a flag
+ * member_conj[k] in {0, 1} (NULL: none).
+ *   u_k[f]      = omega_k                        (weighting = 0)
+ *               = omega_k (double) w[b_k][f]     (weighting = 1)
+ *                 both taken as 0 where w[b_k][f] == 0
+ *   den_v[f]    = sum_k u_k[f]                   in double, k ascending from 0
+ *   xbar_q[v][f]= ( sum_k u_k[f] c_k(q[b_k][f]) ) / den_v[f]
+ *                 c_k negates Im where member_conj[k]
+ *                 re and im are summed separately, in double, k ascending from 0,
+ *                 acc += u * (double) q with contraction off
+ *                 then divided, then rounded ONCE to the solver's dtype
+ *                 0 where den_v[f] == 0
+ *   mask_v[f]   = den_v[f] > 0
+ *   mask_g[f]   = AND over t of mask_(g,t)[f]
+ *   x_q[g][t][f]= mask_g[f] ? xbar_q[g T + t][f] : 0
+ * From x_q on, everything is cal_solver_delay_fringe_spectrum's definition, word for word: X = x op on the matrix cores by the same
+ * loop, Y_t = scale[g][t] X in double, Z = sum_t opt Y_t in the stated order, norm_grp = sum_f mask_g norm_f, power = |Z|^2 / norm_grp,
+ * the bins and count_bin.  Outputs: power_grp [nwhat][ngroups][nrates][ndelays], norm_grp [ngroups], power_bin
+ * [nwhat][nbins][nrates][ndelays], count_bin [nbins]; all doubles, any of them may be NULL.  An empty set gives its group norm_grp == 0,
+ * power 0 and no bin.
+ * Hence, to the bit: (a) sets of one member with unit coefficient, no conjugation and weighting = 0 give
+ * cal_solver_delay_fringe_spectrum on rows[g][t] = that member (1.0 q / 1.0 is exact); (b) a set that holds one row twice gives the
+ * bits of that row once; (c) with ntimes = 1 and opt = [[1]], singleton sets all conjugated and the operator conj(op) give the bits of
+ * the unconjugated sets with op (every product of the complex transform changes sign or keeps it as a whole, and IEEE rounding is
+ * sign-symmetric); two calls give the same bits, and so does any scratch bound.
+ * set_ptr is int64 [ngroups ntimes + 1]; it starts at 0, never falls and ends at nmembers.
+ * Errors, before any launch: those of cal_solver_delay_fringe_spectrum (with set_ptr and member_row in the place of rows);
+ * CAL_ERR_INVALID for a set_ptr that does not start at 0, falls, or does not end at nmembers, a member row outside [0, nbls), a
+ * coefficient that is negative or not finite, a member_conj other than 0 or 1, a weighting other than 0 or 1, nmembers above 2^30.
+ * Works for every layout and kernel path, bl_alias, nslices > 1 and the joint time-basis layout.  A post-fit pass like
+ * cal_solver_delay_fringe_spectrum: it puts the loop state back, and it reads the ONE weight plane cal_solver_robust_weights rewrites.
+ * The groups are worked through in chunks of whole groups whose scratch -- the fringe call's per group over the averaged planes, plus
+ * ntimes pitch bytes of set masks -- stays under the bound of cal_solver_set_delay_spectrum_scratch (never less than one group); the
+ * member lists are uploaded once per call; the device buffers of cal_solver_delay_spectrum are reused.
+ * Under a communicator or exchange hook power_bin | count_bin are summed over the ranks in ONE all-reduce of
+ * nwhat nbins nrates ndelays + nbins doubles (CAL_XCHG_F64, CAL_XCHG_SUM), whichever outputs are asked for (nbins == 0: none); the
+ * per-group outputs stay the rank's own, and the caller keeps a group's rows on one rank. */
+typedef struct cal_delay_coherent_desc {
+  int32_t ndelays;             /* as in cal_delay_fringe_desc */
+  int32_t what;
+  int32_t calibrated;
+  int32_t ngroups;             /* >= 1 */
+  int32_t ntimes;              /* sets of a group, 1 <= ntimes <= 64 */
+  int32_t nrates;              /* columns of opt, 1 <= nrates <= 64 */
+  const int64_t* set_ptr;      /* [ngroups ntimes + 1]: set v's members are [set_ptr[v], set_ptr[v + 1]) */
+  const int32_t* member_row;   /* [nmembers]: rows of the solver, each in [0, nbls), repeats allowed */
+  const double* member_wgt;    /* [nmembers], finite and >= 0; NULL: ones */
+  const uint8_t* member_conj;  /* [nmembers], 0 or 1; NULL: none */
+  int32_t weighting;           /* 0: u = omega; 1: u = omega w */
+  const double* scale;         /* [ngroups][ntimes], finite; NULL: ones */
+  int32_t nbins;               /* 0: no binned output */
+  const int32_t* bin_of_group; /* [ngroups] in [-1, nbins); NULL iff nbins == 0 */
+  const void* op_r;            /* [nfreqs][ndelays], solver dtype */
+  const void* op_i;
+  const double* norm_f;        /* [nfreqs] */
+  const double* opt_r;         /* [ntimes][nrates], finite */
+  const double* opt_i;
+  int64_t nmembers;            /* 0 <= nmembers <= 2^30 */
+} cal_delay_coherent_desc;
+int cal_solver_delay_coherent_spectrum(cal_solver* s, const cal_delay_coherent_desc* desc, const void* g_r, const void* g_i, double* power_grp,
+                                       double* norm_grp, double* power_bin, double* count_bin);
+/* Host only, like cal_debug_report_plan: the plan of cal_solver_delay_coherent_spectrum for `desc` (every field is read; the operator
+ * in `dtype`) under the bound scratch_bytes of cal_solver_set_delay_spectrum_scratch (0: the default), as bytes.  The selectors mirror
+ * 70 .. 76 of cal_debug_report_plan --
+ *   70: int64 nwhat, the row pitch of the averaged planes, the columns of the operator image, groups per chunk, chunks, the elements
+ *   of the chunk's planes (dtype), of its Y and power (double), of norm_grp | power_bin | count_bin, the bytes of the chunk's set
+ *   masks and the spans of a row; 71: the bins' sorted group lists; 72: [chunks][nbins][2] a bin's piece of a chunk as positions in 71;
+ *   73: the operator image [re, im][pitch][columns] (dtype); 74: norm_f padded to the pitch (double); 75: the scales [ngroups][ntimes]
+ *   (double; ones for NULL); 76: opt_r | opt_i (double); 77: int64 [chunks][2], the chunk's members as positions in the member arrays. */
+int cal_debug_delay_coherent_plan(int dtype, const cal_problem_desc* d, const cal_delay_coherent_desc* desc, int64_t scratch_bytes, int what, void* out,
+                                  int64_t cap_bytes, int64_t* bytes);
 /* The signal loss of the fit in delay space: the share of the power at every delay that the coefficient fit itself removes.  The
  * foreground basis absorbs every component of the data in its span -- noise and cosmological signal as well as foregrounds -- so a
  * residual delay spectrum (cal_solver_delay_spectrum) is biased low near the edge of the basis; this is the factor that undoes it.

@@ -1,7 +1,7 @@
 // plan_sanitize.hip -- the set-up planner (calamity_amd/csrc/problem_plan.hpp), the planner of the closed-form calls
 // (calamity_amd/csrc/solve_plan.hpp), of the post-fit reports (calamity_amd/csrc/report_plan.hpp), the step's shape (calamity_amd/csrc/step_plan.hpp) and the two-loop recursion of L-BFGS on
 // coefficients (calamity_amd/csrc/lbfgs_core.hpp) under the host sanitizers, with no device and no interpreter: four problems built in code (folded STREAM, heads of baselines that share tiles, forced dense, multi-baseline runs),
-// planned for fp32 and fp64; the closed-form plans, the delay-spectrum plan, the cross-spectrum plan and the delay / fringe-rate plan (each with its refusals) at the default scratch bound and at a bound of 1 byte, the degeneracy plan in both modes,
+// planned for fp32 and fp64; the closed-form plans, the delay-spectrum plan, the cross-spectrum plan, the delay / fringe-rate plan and the plan of the redundant averages (each with its refusals) at the default scratch bound and at a bound of 1 byte, the degeneracy plan in both modes,
 // the caller's arrays of exactly the sizes the planners may read; plan_step over its whole input
 // table; lbfgs_two_loop on Gram matrices of 0 .. 16 pairs held in arrays of exactly the sizes it may touch.  Exits non-zero on a planner error or an inconsistent plan; the sanitizers abort on a finding.
 //
@@ -183,6 +183,73 @@ int run(const Case& c) {
     bin_of_group[ng - 1] = -1;
     fd.what = 4;
     rbad += plan_delay_fringe(p.nbls, p.nfreqs, p.fpad, &fd, kCsScratchDefault, R) != CAL_OK || R.nq != 1 || R.scale[1] != 1.0;
+  }
+  // the plan of the redundant averages: a group of two sets per row (k % 4 members and one, the first group's first set empty), member
+  // arrays of exactly nmembers entries and a set_ptr of exactly ngroups ntimes + 1; both bounds; then its refusals
+  {
+    const int ng = p.nbls, nt = 2, nr = 2;
+    std::vector<int64_t> set_ptr(1, 0);
+    std::vector<int32_t> member_row, bin_of_group(ng);
+    for (int k = 0; k < ng; ++k) {
+      for (int j = 0; j < k % 4; ++j) member_row.push_back((k + 3 * j) % ng);
+      set_ptr.push_back((int64_t)member_row.size());
+      member_row.push_back(k);
+      set_ptr.push_back((int64_t)member_row.size());
+      bin_of_group[k] = k % 7 == 3 ? -1 : k % (nbins - 1);
+    }
+    const int64_t nm = (int64_t)member_row.size();
+    std::vector<double> wgt((size_t)nm, 0.75), scale((size_t)ng * nt, 1.5), opt_r((size_t)nt * nr, 0.5), opt_i((size_t)nt * nr, -0.25);
+    std::vector<uint8_t> cj((size_t)nm, 0);
+    cj[nm - 1] = 1;
+    cal_delay_coherent_desc kd{nd, 7, 1, ng, nt, nr, set_ptr.data(), member_row.data(), wgt.data(), cj.data(), 1, scale.data(), nbins, bin_of_group.data(),
+                               op_r.data(), op_i.data(), norm_f.data(), opt_r.data(), opt_i.data(), nm};
+    for (const int64_t bound : {kCsScratchDefault, (int64_t)1}) {
+      DelayCoherentPlan<T> P;
+      rbad += plan_delay_coherent(p.nbls, p.nfreqs, p.fpad, &kd, bound, P) != CAL_OK || P.F.nchunks != (bound == 1 ? ng : 1) || P.F.cgroups != (bound == 1 ? 1 : ng) ||
+              P.set_ptr.size() != (size_t)ng * nt + 1 || P.member_row.size() != (size_t)nm || P.member_wgt[0] != 0.75 || P.member_conj[nm - 1] != 1 ||
+              P.chunk_members.size() != 2 * (size_t)P.F.nchunks || P.chunk_members[0] != 0 || P.chunk_members.back() != nm ||
+              P.n_mask != (size_t)P.F.cgroups * nt * P.F.xpitch || P.nspans < 1;
+      for (int c = 1; c < P.F.nchunks; ++c) rbad += P.chunk_members[2 * c] != P.chunk_members[2 * c - 1];
+    }
+    DelayCoherentPlan<T> R;
+    auto refused = [&]() { return plan_delay_coherent(p.nbls, p.nfreqs, p.fpad, &kd, kCsScratchDefault, R) != CAL_ERR_INVALID; };
+    member_row[nm - 1] = p.nbls;  // a row past the last
+    rbad += refused();
+    member_row[nm - 1] = 0;
+    wgt[1] = -1.0;
+    rbad += refused();
+    wgt[1] = std::numeric_limits<double>::quiet_NaN();
+    rbad += refused();
+    kd.member_wgt = nullptr;  // no coefficients: ones
+    cj[0] = 2;
+    rbad += refused();
+    kd.member_conj = nullptr;  // no flags: none
+    set_ptr[0] = 1;
+    rbad += refused();
+    set_ptr[0] = 0;
+    std::swap(set_ptr[2], set_ptr[3]);  // (set_ptr[3] > set_ptr[2]: group 1 has a member in its first set) it falls
+    rbad += refused();
+    std::swap(set_ptr[2], set_ptr[3]);
+    kd.nmembers = nm - 1;
+    rbad += refused();
+    kd.nmembers = ((int64_t)1 << 30) + 1;
+    rbad += refused();
+    kd.nmembers = nm;
+    for (const int bad_w : {-1, 2}) {
+      kd.weighting = bad_w;
+      rbad += refused();
+    }
+    kd.weighting = 0;
+    for (const int bad_nt : {0, 65}) {
+      kd.ntimes = bad_nt;
+      rbad += refused();
+    }
+    kd.ntimes = nt;
+    kd.set_ptr = nullptr;
+    rbad += refused();
+    kd.set_ptr = set_ptr.data();
+    kd.what = 4;
+    rbad += plan_delay_coherent(p.nbls, p.nfreqs, p.fpad, &kd, kCsScratchDefault, R) != CAL_OK || R.F.nq != 1 || R.member_wgt[1] != 1.0 || R.member_conj[0] != 0;
   }
   for (const bool band : {false, true}) {
     DegeneracyPlan P;
